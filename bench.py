@@ -18,7 +18,12 @@ rank runs the same per-GPU work (weak scaling, no per-chunk collective).  The sa
 and the host-buffer boundary of the reference (`latency_ms_host_buffer`: rvc_infer with H2D + D2H inside the call = SURVEY 8d's
 latency definition).  `latency_ms` of the headline comes from a soak of >= 1000 synchronised chunks inside the run (p50 / p99 / p99.9).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--index] [--only-headline] [--no-cpu] [--dry-launch]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--index] [--dump-outputs DIR] [--full [--only-headline] [--no-cpu]] [--dry-launch]
+
+A plain run measures the headline leg only: set-up, W warm-up steps, the K timed steps, the outputs of the last timed step if --dump-outputs is
+given, and one short JSON line (the contract keys, `latency_ms` of the K timed steps, `summary_ms`).  Everything else described here -- the latency soak, the
+roofline, the in-run calibration and box sensors, the informational legs, `sub_configs`, `cpu_baseline` and the verbose record -- is measured
+with --full only.
 
 The ONE JSON line on stdout is compact (it must survive a tail of ~8 KB): the contract keys, `roofline`, `cpu_baseline`, the box's own
 peaks measured in-run (`peak_measured`: rvc_calibrate at the start and at the end of the run), one short record per sub-configuration
@@ -61,7 +66,9 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--streams", type=int, default=1, help="streams per GPU of the HEADLINE leg (default 1 = BASELINE configs[1])")
     ap.add_argument("--index", action="store_true", help="headline leg with the 100k x 768 index (BASELINE configs[2])")
-    ap.add_argument("--only-headline", action="store_true", help="skip the sub_configs / informational legs")
+    ap.add_argument("--full", action="store_true", help="besides the headline: latency soak, roofline, calibration, informational legs, sub_configs, cpu_baseline, verbose record")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the output audio of the last timed step as DIR/output.npy (float32 [streams, samples]; rank r > 0: output_rank<r>.npy)")
+    ap.add_argument("--only-headline", action="store_true", help="with --full: skip the sub_configs / informational legs")
     ap.add_argument("--graph", action="store_true", help="replay each chunk from a hipGraph (default: eager launches with interleaved branch submission, measured faster)")
     ap.add_argument("--no-graph", action="store_true", help="accepted for compatibility: eager launches are the default")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
@@ -360,12 +367,12 @@ def make_rings(S, stream_ids, n_rings, g):
 
 def timed_leg(job, eng, d_rings, d_out, g, steps, warmup):
     """W warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides; every step synchronised so that the
-    per-chunk latency is observed.  -> (elapsed seconds = max over ranks, this rank's per-step latencies)"""
+    per-chunk latency is observed.  -> (elapsed seconds = max over ranks, this rank's per-step latencies, step, samples per stream of the last step)"""
     L, chunk, N = g.input_buffer_16k_size, g.sample_frame_16k, g.model_return_size
     n_rings = d_rings.shape[0]
 
     def step(i):
-        eng.infer_device(d_rings[i % n_rings].data_ptr(), L, chunk, 12, g.skip_head, g.model_return_length, d_out.data_ptr(), N, sync=True)
+        return eng.infer_device(d_rings[i % n_rings].data_ptr(), L, chunk, 12, g.skip_head, g.model_return_length, d_out.data_ptr(), N, sync=True)
 
     for i in range(warmup):
         step(i)
@@ -379,12 +386,27 @@ def timed_leg(job, eng, d_rings, d_out, g, steps, warmup):
     t0 = time.perf_counter()
     for i in range(steps):
         t1 = time.perf_counter()
-        step(i)
+        n_out = step(i)
         lat.append(time.perf_counter() - t1)
     job.torch.cuda.synchronize()
     job.barrier()
     elapsed = job.max_over_ranks(time.perf_counter() - t0)
-    return elapsed, lat, step
+    return elapsed, lat, step, n_out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir, job, d_out, n_out):
+    """--dump-outputs: what the last timed step handed back -- the output audio of every stream of this rank, float32 [streams, samples] -- as
+    <dir>/output.npy (rank r > 0: output_rank<r>.npy).  Above 64 MB over all ranks, a fixed seeded sample of whole streams."""
+    out = d_out[:, :n_out].cpu().numpy()
+    cap = DUMP_MAX_BYTES // job.world
+    if out.nbytes > cap:
+        keep = max(1, cap // out[0].nbytes)
+        out = out[np.sort(np.random.default_rng(0).choice(out.shape[0], keep, replace=False))]
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "output.npy" if job.rank == 0 else "output_rank%d.npy" % job.rank), np.ascontiguousarray(out, np.float32))
 
 
 def committed_traffic(S, with_index=False, version=2, preset="full"):
@@ -507,9 +529,11 @@ def finish_roofline(roof, ms_per_step, peaks, probe):
     return roof
 
 
-def run_config(job, z, g, S, with_index, steps, warmup, graph, index_vecs, want_roofline=True, version=2, soak=0, preset="full", gemm_precision=0):
+def run_config(job, z, g, S, with_index, steps, warmup, graph, index_vecs, want_roofline=True, version=2, soak=0, preset="full", gemm_precision=0,
+               dump_dir=None):
     """One configuration on every rank: S streams per GPU, retrieval on/off.  soak > 0: that many more synchronised chunks after the
-    timed region for the latency distribution (p99.9 needs >= 1000 samples).  -> record (rank 0) / None"""
+    timed region for the latency distribution (p99.9 needs >= 1000 samples).  dump_dir: dump_outputs of the last timed step.
+    -> record (rank 0) / None"""
     from obs_rvc_amd import dist as rdist
     from obs_rvc_amd.rvc import RvcInfer
     torch = job.torch
@@ -542,9 +566,11 @@ def run_config(job, z, g, S, with_index, steps, warmup, graph, index_vecs, want_
     rings = make_rings(S, stream_ids, n_rings, g)
     d_rings = torch.from_numpy(rings).cuda()
     d_out = torch.empty((S, g.model_return_size), dtype=torch.float32, device="cuda")
-    elapsed, lat, step = timed_leg(job, eng, d_rings, d_out, g, steps, warmup)
+    elapsed, lat, step, n_out = timed_leg(job, eng, d_rings, d_out, g, steps, warmup)
     gpu_ms_last = eng.last_gpu_ms()            # device time of the last timed chunk (events around the call's launches): next to the wall clock, it
     soak_lat = []                              # tells a slow GPU from a slow submitting thread
+    if dump_dir:                               # before the soak and the probes below overwrite d_out
+        dump_outputs(dump_dir, job, d_out, n_out)
     for i in range(soak):                        # latency distribution: more synchronised chunks behind the timed region
         t1 = time.perf_counter(); step(i); soak_lat.append(time.perf_counter() - t1)
     gc.enable()
@@ -769,9 +795,10 @@ def main(argv=None):
         print("bench: --gpus %d but WORLD_SIZE=%d: running the %d ranks that exist" % (args.gpus, job.world, job.world), file=sys.stderr)
     from common import BASELINE_160MS as g, zoo
     from obs_rvc_amd import weights as W
+    headline_only = args.only_headline or not args.full
     if job.rank == 0:                      # one rank writes the model zoo, the others read it
         z = zoo(args.preset)
-        if not args.only_headline and args.preset == "full" and args.streams == 1 and not args.index:
+        if not headline_only and args.preset == "full" and args.streams == 1 and not args.index:
             zoo(args.preset, 1)
     job.barrier()
     z = zoo(args.preset)
@@ -784,13 +811,13 @@ def main(argv=None):
         from common import set_opt
         set_opt(*hk.split("=", 1))
     CTX["autotune"] = not args.no_autotune
-    index_vecs = W.make_index() if (job.rank == 0 and full) else None      # only rank 0 ever holds the host copy
+    index_vecs = W.make_index() if (job.rank == 0 and full and (args.full or args.index)) else None      # only rank 0 ever holds the host copy
 
     # ---- the box: sensor probe + in-run calibration (what this GPU's matrix cores and HBM sustain right now; every rank calibrates its own GPU)
     # (under rocprofv3 the in-kernel clock monitor is left out: counter collection serialises dispatches, and a monitor that waits for a host flag would
     #  hold every later kernel back until its own time-out)
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_", "ROCPROFILER")) for k in os.environ)
-    CTX["calib"] = not args.no_calibration and not under_profiler
+    CTX["calib"] = args.full and not args.no_calibration and not under_profiler
     bdf = None
     try:
         pr = job.torch.cuda.get_device_properties(job.local_rank)
@@ -807,10 +834,29 @@ def main(argv=None):
 
     # ---- headline: BASELINE configs[1] (or what --streams / --index ask for) on every rank
     S = args.streams
-    soak_n = int(os.environ.get("RVC_BENCH_SOAK", "1000")) if (S == 1 and full and not args.only_headline) else 0
-    head, eng, rings, d_rings = run_config(job, z, g, S, args.index and full, args.steps, args.warmup, graph, index_vecs, soak=soak_n, preset=args.preset)
+    soak_n = int(os.environ.get("RVC_BENCH_SOAK", "1000")) if (S == 1 and full and not headline_only) else 0
+    head, eng, rings, d_rings = run_config(job, z, g, S, args.index and full, args.steps, args.warmup, graph, index_vecs, want_roofline=args.full,
+                                           soak=soak_n, preset=args.preset, dump_dir=args.dump_outputs)
+    workload = ("BASELINE configs[%d]: %d stream(s)/GPU, ContentVec v2-768 + RMVPE + NSF-HiFiGAN v2-48k, retrieval %s, preset %s"
+                % (2 if args.index else (1 if S == 1 else 3), S, "100k x768 flat-L2 k=4" if args.index else "off", args.preset))
+    if job.rank == 0:
+        line = {"metric": "audio frames/sec (10 ms hops of new input, 160 ms chunks @16 kHz)", "value": head["frames_per_s"], "unit": "frames/s",
+                "n_gpus": job.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "gpu_ms_last_chunk": head.get("gpu_ms_last_chunk"),
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic"}
+        line_config = {"workload": workload, "streams_per_gpu": S, "streams_total": S * job.world, "chunk_ms": 160, "hip_graph": graph,
+                       "timed_api": "rvc_infer_device (inputs in HBM, one sync per chunk)"}
+    if not args.full:
+        if job.rank == 0:
+            line.update(config=line_config, latency_ms=head["latency_ms"], rtf=head["rtf"], per_rank_frames_per_s=head["per_rank_frames_per_s"],
+                        serial_branches=bool(args.serial_branches), plan_autotune=bool(CTX["autotune"]))
+            if args.hook:
+                line["hooks"] = args.hook
+            line["summary_ms"] = {"headline": head["ms_per_step"]}
+            print_line(line)
+        job.close()
+        return
     extra = {}
-    if job.rank == 0 and not args.only_headline:
+    if job.rank == 0 and not headline_only:
         skip = os.environ.get("RVC_BENCH_SKIP", "").split(",")     # debugging aid: leg names to leave out
 
         def informational(name, fn):                       # informational legs never cost the headline line
@@ -832,7 +878,7 @@ def main(argv=None):
 
     # ---- sub-configurations: every rank takes part (the timed regions are bracketed by barriers)
     sub = {}
-    if not args.only_headline and full and S == 1 and not args.index:
+    if not headline_only and full and S == 1 and not args.index:
         # Each leg raises only where every rank raises together (index broadcast: agreed through Job.all_ok; anything else is deterministic
         # per configuration), so skipping a failed leg cannot strand a rank in a collective.
         # latency distributions of the two sub-configurations VERDICT r3 asked for come from >= 200 synchronised chunks (p99 of 20 samples
@@ -921,8 +967,6 @@ def main(argv=None):
     if job.rank == 0:
         if args.serial_branches:
             head["serial_branches"] = True
-        workload = ("BASELINE configs[%d]: %d stream(s)/GPU, ContentVec v2-768 + RMVPE + NSF-HiFiGAN v2-48k, retrieval %s, preset %s"
-                    % (2 if args.index else (1 if S == 1 else 3), S, "100k x768 flat-L2 k=4" if args.index else "off", args.preset))
         rccl_ranks = (((sub.get("streams64") or {}).get("index_broadcast") or (sub.get("index100k") or {}).get("index_broadcast") or head.get("index_broadcast") or {}).get("rccl_ranks", 0))
         gpu_name = None
         try:
@@ -931,10 +975,7 @@ def main(argv=None):
             pass
         box = {"gpu": gpu_name, "pci": bdf, "uuid": CTX["box"].uuid, "sensor_source": CTX["box"].source, "host_cpus": os.cpu_count(), "idle": box_idle, "headline_under_load": head.get("box_under_load")}
         # ---- the verbose record: everything, with notes and sources (file + optionally stderr)
-        full_rec = {
-            "metric": "audio frames/sec (10 ms hops of new input, 160 ms chunks @16 kHz)", "value": head["frames_per_s"], "unit": "frames/s",
-            "n_gpus": job.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "gpu_ms_last_chunk": head.get("gpu_ms_last_chunk"),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        full_rec = dict(line, **{
             "config": {"workload": workload, "streams_per_gpu": S, "streams_total": S * job.world, "chunk_ms": 160, "input_samples_16k": g.input_buffer_16k_size,
                        "output_samples": g.model_return_size, "hip_graph": graph,
                        "timed_api": "rvc_infer_device: inputs resident in HBM when the timed region starts, one synchronisation per chunk; the host-buffer boundary (H2D + D2H inside the call) is latency_ms_host_buffer"},
@@ -951,7 +992,7 @@ def main(argv=None):
                 "box": "sclk / W / C per leg: shader clock from that monitor; socket power (W, against power_cap_w) and hotspot temperature from the SMU (amdsmi, device matched by PCI bus id) sampled every 100 ms during the same probe steps",
                 "serial_pass": "profiles/<round>_serial_<S>streams.json: rocprofv3 kernel-trace sum of the implicit-GEMM class per step of one serial-branch process on the builder's box (whole steps behind the plan build's autotune trials: tests/tools/trace_stats.py); this_run_events_over_committed_rocprof = this unprofiled run's HIP-event sum over it (1.00 on the same build and box)",
             },
-        }
+        })
         if args.index and head.get("index_broadcast"):
             full_rec["index_broadcast"] = head["index_broadcast"]
         if job.world > 1 and sub.get("streams64"):
@@ -970,10 +1011,7 @@ def main(argv=None):
             print(json.dumps(full_rec), file=sys.stderr)
         # ---- the line: compact, `summary_ms` last
         hb = extra.get("latency_ms_host_buffer") or {}
-        out = {k: full_rec[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "gpu_ms_last_chunk", "higher_is_better", "scaling",
-                                        "vs_baseline", "dtype", "data")}
-        out["config"] = {"workload": workload, "streams_per_gpu": S, "streams_total": S * job.world, "chunk_ms": 160, "hip_graph": graph,
-                         "timed_api": "rvc_infer_device (inputs in HBM, one sync per chunk)"}
+        out = dict(line, config=line_config)
         out["latency_ms"] = head["latency_ms"]; out["rtf"] = head["rtf"]; out["rccl_ranks"] = rccl_ranks
         out["per_rank_frames_per_s"] = head["per_rank_frames_per_s"]
         out["latency_ms_host_buffer"] = {k: hb[k] for k in ("p50", "p99", "samples") if k in hb} or None
@@ -1001,16 +1039,20 @@ def main(argv=None):
             if k in sub:
                 summ[k] = (sub[k] or {}).get("ms_per_step")
         out["summary_ms"] = summ           # LAST key: survives a truncated tail
-        # librccl prints a version banner through C stdio when its first communicator is created: push it out now so that the
-        # JSON line below is the LAST line on stdout
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        sys.stdout.flush()
-        print(json.dumps(out), flush=True)
+        print_line(out)
     job.close()
+
+
+def print_line(out):
+    # librccl prints a version banner through C stdio when its first communicator is created: push it out now so that the
+    # JSON line below is the LAST line on stdout
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    sys.stdout.flush()
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

@@ -186,7 +186,7 @@ def test_index_setup_behind_the_broadcast_stays_on_the_device():
 
 def test_bench_line_single_rank_smoke():
     # the bench contract on the tiny preset: one JSON line, the keys the driver reads, n_gpus = ranks that ran
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "tiny", "--steps", "5", "--warmup", "2", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--preset", "tiny", "--steps", "5", "--warmup", "2", "--no-cpu"],
                        capture_output=True, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1]
@@ -194,6 +194,29 @@ def test_bench_line_single_rank_smoke():
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in j, k
     assert j["n_gpus"] == 1 and j["steps"] == 5 and j["value"] > 0 and j["roofline"]["frac"] > 0 and j["roofline"]["sum_kernel_ms"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    # a plain run: the headline leg only, exactly --steps timed steps, and --dump-outputs holds what the last timed step returned -- the same
+    # chunk sequence (W warm-up + K timed steps over the seeded rings, noise seed 1234) through the oracle gives the same audio
+    from common import chunk_stream
+    steps, warmup = 3, 2
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "tiny", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    j = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == steps and j["latency_ms"]["samples"] == steps and j["ms_per_step"] > 0 and j["value"] > 0
+    assert "roofline" not in j and "sub_configs" not in j and "cpu_baseline" not in j
+    chunk = g.sample_frame_16k                        # bench.py make_rings: stream 0, 8 rings
+    rings = list(chunk_stream(voice_signal(chunk * (8 + 14), seed=0), g.input_buffer_16k_size, chunk))[-8:]
+    o = _oracle(zoo("tiny"), 1234, 0)
+    for i in list(range(warmup)) + list(range(steps)):
+        yo = o.infer(rings[i % 8], chunk, 12, g.skip_head, g.model_return_length)
+    y = np.load(str(tmp_path / "output.npy"))         # the samples the call returned (the tiny synthesizer's rate: fewer than the 48 kHz model_return_size)
+    assert y.dtype == np.float32 and y.shape == (1, yo.size) and np.isfinite(y).all()
+    assert rms(y[0] - yo) < PCM_TOL, rms(y[0] - yo)
 
 
 def test_binary_was_built_from_these_sources():

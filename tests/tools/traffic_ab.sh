@@ -4,7 +4,7 @@
 # usage (gpurun): bash tests/tools/traffic_ab.sh   -> gpurun_out/traffic_ab/{panel1,panel0}.json
 R=$GRAFT_REPO_ROOT; raw=/tmp/prof_tab; out=$R/gpurun_out/traffic_ab; mkdir -p $raw $out; cd /tmp; export TMPDIR=/tmp
 for v in 1 0; do
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $raw/f$v -- python $R/bench.py --only-headline --no-cpu --no-calibration --no-autotune --steps 6 --warmup 2 --streams 64 --hook RVC_G32L_PANEL=$v > $out/bench_$v.json 2> $out/bench_$v.err
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $raw/f$v -- python $R/bench.py --full --only-headline --no-cpu --no-calibration --no-autotune --steps 6 --warmup 2 --streams 64 --hook RVC_G32L_PANEL=$v > $out/bench_$v.json 2> $out/bench_$v.err
   python $R/tests/tools/pmc_traffic.py $raw/f$v/*/*counter_collection.csv - $out/panel$v.json "bench.py --only-headline --streams 64 --no-autotune --hook RVC_G32L_PANEL=$v:" '{"streams": 64, "index": false, "version": 2, "preset": "full", "hook": "RVC_G32L_PANEL='$v'"}' 13.9e9 > /dev/null
 done
 python - <<EOF
