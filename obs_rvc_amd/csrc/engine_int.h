@@ -273,6 +273,15 @@ struct Plan {
     bool final_out_honoured = false;     // the chunk's last convolution was queued on a launch path that writes Plan::cur_out (queue_igemm reports it)
     // graph
     hipGraphExec_t graph_exec = nullptr;
+    // run time: the next profile slot of this run (its events are created on first use; the engine rewinds prof_used per run), nullptr when not profiling
+    ProfEvent *prof_slot(double flops, double bytes, int desc)
+    {
+        if (!profile) return nullptr;
+        if (prof_used == prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); prof.push_back(e); }
+        ProfEvent *pe = &prof[prof_used++];
+        pe->flops = flops; pe->bytes = bytes; pe->desc = desc;
+        return pe;
+    }
     ~Plan()
     {
         for (float *p : owned_dev) wfree(p);
@@ -288,6 +297,9 @@ extern unsigned long long *g_kprobe;      // tuning build (-DRVC_KPROBE): destin
 extern int g_last_waves, g_last_wgs, g_ncu;
 extern char g_last_kernel[16];          // family of the most recently queued implicit-GEMM launch ("reg", "g32", "c32s", ...)
 void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phases, bool final_out = false);
+// one GEMM-class launch of the planner (description, FLOPs, launch shape, profile slot, final_out): launch(q, ea, eb, stream) gets the IgemmP to use and the
+// slot's events.  Defined and instantiated in plan.hip (the body is inlined into the op, as lean as a hand-written one)
+template <class Launch> void queue_gemm_launch(Plan &pl, const char *desc, double flops, int wgs, int waves, bool final_out, const IgemmP &p, Launch launch);
 void fill_epilogue(IgemmP &p, const ConvW &cw, const ConvOpts &o);
 void add_conv1d(Plan &pl, const ConvW &cw, const T1 &x, const T1 &y, int stride, int pad, int dil, ConvOpts o = ConvOpts());
 void add_conv1d_multi(Plan &pl, const std::vector<const ConvW *> &cws, const T1 &x, bool x_grouped, const T1 &y,

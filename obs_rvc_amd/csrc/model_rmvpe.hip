@@ -51,11 +51,7 @@ static bool add_rm_block_fused(Plan &pl, const ResBlockW &w, const T2 &x, const 
     { char d[176]; snprintf(d, sizeof d, "rmb M=%d N=%d K=%d B=%d nph=1 tile=%dx%d grid=%ux%u lds=%zu sc=%d", w.co, x.H * x.W, 9 * w.ci + 9 * w.co + (w.has_sc ? w.ci : 0), x.B, q.TH, q.TW, grid.x, grid.y, lds, (int)w.has_sc); pl.descs.push_back(d); }
     const int desc_id = (int)pl.descs.size() - 1;
     pl.ops.push_back([=](hipStream_t s) {
-        ProfEvent *pe = nullptr;
-        if (plp->profile) {
-            if (plp->prof_used == plp->prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); e.flops = 0; e.bytes = 0; plp->prof.push_back(e); }
-            pe = &plp->prof[plp->prof_used++]; pe->flops = flops; pe->bytes = 0; pe->desc = desc_id;
-        }
+        const ProfEvent *pe = plp->prof_slot(flops, 0, desc_id);
         hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
 #define RVC_RMB_LAUNCH(MT_, N1_, N2_)                                                                                         \
         { if (ea) hipExtLaunchKernelGGL((rm_block_kernel<MT_, N1_, N2_>), grid, dim3(256), (uint32_t)lds, s, ea, eb, 0, q);  \

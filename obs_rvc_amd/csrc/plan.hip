@@ -6,14 +6,21 @@
 
 namespace rvc {
 
-static const char *const kTestHooks[] = {"RVC_FORCE_CFG", "RVC_CONV_TILE", "RVC_CONV_TILE_KS", "RVC_NO_LN_FUSE", "RVC_NO_CONV0_MULTI", "RVC_KNN_NO_GEMM",
-                                         "RVC_KNN_EXHAUSTIVE", "RVC_STAMPS", "RVC_SERIAL_BRANCHES", "RVC_NO_WN_COMPOSE", "RVC_KNN_LOSE_TICKET", "RVC_FORCE_G2W", "RVC_F0_XCDS", "RVC_CONV32S", "RVC_CONV32S_TILE", "RVC_G32L", "RVC_G32L_TALL", "RVC_G32L_TAB", "RVC_CONV32S_BUF", "RVC_FORCE_CHOICE", "RVC_G32L_PANEL", "RVC_MEAN3", "RVC_RM_FUSE", "RVC_G2W_LN", "RVC_RELPOS_MFMA_MAX"};
+// the test hooks rvc_debug_option accepts; planner = a kernel / tile choice of queue_igemm (a plan built while one is set is not autotuned: the hook IS the choice)
+struct TestHook { const char *name; bool planner; };
+static const TestHook kTestHooks[] = {
+    {"RVC_FORCE_CFG", true}, {"RVC_CONV_TILE", true}, {"RVC_CONV_TILE_KS", true}, {"RVC_NO_LN_FUSE", false}, {"RVC_NO_CONV0_MULTI", false},
+    {"RVC_KNN_NO_GEMM", false}, {"RVC_KNN_EXHAUSTIVE", false}, {"RVC_STAMPS", false}, {"RVC_SERIAL_BRANCHES", false}, {"RVC_NO_WN_COMPOSE", false},
+    {"RVC_KNN_LOSE_TICKET", false}, {"RVC_FORCE_G2W", true}, {"RVC_F0_XCDS", false}, {"RVC_CONV32S", true}, {"RVC_CONV32S_TILE", true},
+    {"RVC_G32L", true}, {"RVC_G32L_TALL", true}, {"RVC_G32L_TAB", true}, {"RVC_CONV32S_BUF", true}, {"RVC_FORCE_CHOICE", true},
+    {"RVC_G32L_PANEL", true}, {"RVC_MEAN3", false}, {"RVC_RM_FUSE", false}, {"RVC_G2W_LN", false}, {"RVC_RELPOS_MFMA_MAX", false}
+};
 std::atomic<unsigned> g_opt_gen{0};       // bumped by every rvc_debug_option call: plans built under another generation are dropped (engine.hip get_plan)
 static std::mutex g_opt_mu;
 static std::map<std::string, std::string> g_opts;
 static bool is_test_hook(const char *name)
 {
-    for (const char *h : kTestHooks) if (!strcmp(h, name)) return true;
+    for (const TestHook &h : kTestHooks) if (!strcmp(h.name, name)) return true;
     return false;
 }
 static const char *opt_lookup(const char *name)
@@ -258,57 +265,99 @@ int g_last_waves = 0, g_last_wgs = 0;
 char g_last_kernel[16] = "";
 static void note_kernel(const char *d) { size_t i = 0; for (; i < sizeof(g_last_kernel) - 1 && d[i] && d[i] != ' '; i++) g_last_kernel[i] = d[i]; g_last_kernel[i] = 0; }
 
-// One stream, stride-1 1-D convolution with a long output: conv_tile_kernel (conv_tile.hip.h) stages the input rows once per workgroup.
-// Builds the LDS-offset tables (k -> row * RS + tap column) from the layer's gather table and a work-item table that balances the
-// unequal phases of a fused launch over the CUs (workgroup b lands on CU b % ncu: tests/tools/place_probe.hip).  false = not eligible.
+// Every GEMM-class launch of the planner is queued here: its description (rvc_debug_profile_dump, rvc_debug_last_kernel), the plan's FLOP count, the
+// launch shape of the last queued kernel.  At run time the op takes a profile slot and hands `launch` the IgemmP to use: the plan's own, or -- final_out,
+// the chunk's last layer -- a copy that writes the caller's buffer (Plan::cur_out) when the call provides one.
+template <class Launch> void queue_gemm_launch(Plan &pl, const char *desc, double flops, int wgs, int waves, bool final_out, const IgemmP &p, Launch launch)
+{
+    pl.descs.push_back(desc); note_kernel(desc);
+    g_last_wgs = wgs; g_last_waves = waves;
+    pl.igemm_flops += flops; pl.n_igemm++;
+    if (final_out) pl.final_out_honoured = true;
+    Plan *plp = &pl;
+    const int desc_id = (int)pl.descs.size() - 1;
+    pl.ops.push_back([=](hipStream_t s) {
+        const ProfEvent *pe = plp->prof_slot(flops, 0, desc_id);
+        hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
+        if (final_out && plp->cur_out) { IgemmP q = p; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch(q, ea, eb, s); }
+        else launch(p, ea, eb, s);
+    });
+}
+
 int g_ncu = 256;
 
 // Plan-time selection by measurement (rvc_set_plan_autotune, queue_igemm below): a trial build of a layer runs under a forced Choice -- the same switch points
-// the test hooks RVC_CONV32S_TILE / RVC_FORCE_G2W / RVC_FORCE_CFG use, per layer and thread-local instead of process-wide.  A choice the layer is not eligible
-// for falls through to the rules (the trial then reports the same kernel description as the rule-based build and is not timed twice).
+// the test hooks RVC_CONV32S_TILE / RVC_FORCE_G2W / RVC_FORCE_CFG use, per layer instead of process-wide.  A choice the layer is not eligible for falls
+// through to the rules (the trial then reports the same kernel description as the rule-based build and is not timed twice).
 struct Choice {
     int kind = 0;      // 0 = the rules; 1 = conv32s_kernel (a = tile | 4 for the buffer-load variant of tile 1); 2 = igemm2w_kernel (tile a, K split b);
     int a = 0, b = 0;  // 3 = workgroup-tiled kernels (lds_cfg a: 3 4 5 7 8); 4 = register-direct kernel (tile a, K split b)
     bool operator==(const Choice &o) const { return kind == o.kind && a == o.a && b == o.b; }
 };
-static thread_local Choice t_choice;
 
-static bool queue_conv_tile(Plan &pl, IgemmP &p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phv, double ksum, bool final_out)
+// One queue_igemm_impl call as the kernel families see it.  Every family function answers "does this family take the layer" and, if it does, queues it.
+struct GemmCall {
+    Plan &pl;
+    const std::vector<int> &koff;   // the layer's gather table (element offsets)
+    bool final_out;
+    const Choice &ch;               // forced by a trial, the tuner's cache or RVC_FORCE_CHOICE (kind 0: the rules)
+    int streams;                    // B of the caller (before the streams are folded into N)
+    double ksum = 0;                // sum of the phases' K (phases of a fused launch may differ; p.K is the maximum)
+    bool phase_epi = false;         // per-phase activation / output tensor: igemm2 only
+    bool ln_fold = false;           // folded LayerNorm lives in the register-direct kernel's K-split epilogue
+    Choice built;                   // what was queued, in the tuner's terms (kind 0: the staged-tile convolution or split-bf16, which it does not vary)
+};
+
+static void set_phases(Plan &pl, IgemmP &p, const std::vector<PhaseD> &ph) { p.ph = pl.arena.upload(ph); p.nphase = (int)ph.size(); p.ph0 = ph[0]; }
+
+// A phase whose gather table is a stride-1 1-D convolution -- entry k = ci * KW + tap holds ci * x_ld + dmin + tap * dil -- with cin a multiple of `cblk`:
+// fills the staged kernels' t_tab = KW | dil << 8, t_cin, t_dmin.  false = another pattern.
+static bool decode_taps(PhaseD &q, const std::vector<int> &koff, const IgemmP &p, int cblk)
 {
-    const int mode = t_choice.kind ? 0 : test_opt_int("RVC_CONV_TILE", 1);       // test hook: 0 = off, 2 = wherever eligible; read per plan
-    auto no = [&](int why) { (void)why; return false; };
+    const int K = q.nchunks * 16;
+    int cin = 1;
+    for (int k = 0; k < K; k++) cin = std::max(cin, (int)std::floor((double)koff[q.koff_off + k] / p.x_ld + 0.5) + 1);
+    if (cin % cblk != 0 || K % cin != 0) return false;
+    const int KW = K / cin;
+    if (KW > 255) return false;
+    const int dmin = koff[q.koff_off];
+    const int dil = KW > 1 ? koff[q.koff_off + 1] - koff[q.koff_off] : 1;
+    if (dil < 1 || dil > 255 || dmin > 0 || dmin < p.x_lo) return false;
+    for (int k = 0; k < K; k++) if (koff[q.koff_off + k] != (k / KW) * p.x_ld + dmin + (k % KW) * dil) return false;
+    q.t_tab = KW | (dil << 8); q.t_cin = cin; q.t_dmin = dmin;
+    return true;
+}
+
+// One stream, stride-1 1-D convolution with a long output: conv_tile_kernel (conv_tile.hip.h) stages the input rows once per workgroup.
+// Builds the LDS-offset tables (k -> row * RS + tap column) from the layer's gather table and a work-item table that balances the
+// unequal phases of a fused launch over the CUs (workgroup b lands on CU b % ncu: tests/tools/place_probe.hip).  false = not eligible.
+static bool queue_conv_tile(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &phv)
+{
+    const int mode = c.ch.kind ? 0 : test_opt_int("RVC_CONV_TILE", 1);       // test hook: 0 = off, 2 = wherever eligible; read per plan
     // streams: one always; two to four with the same narrow tiles and the streams in the item table (measured -1 % / -2 % at 2 / 4 streams, nothing at
     // 8; wider tiles for many streams measured slower than the 32x32x2 kernels and are gone)
-    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.lin_cs4 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part) return no(1);
-    if (B > 4) return no(2);
-    if (p.M > 128 && mode < 2) return no(3);
+    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.lin_cs4 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part) return false;
+    if (B > 4) return false;
+    if (p.M > 128 && mode < 2) return false;
     const int kshares = test_opt_int("RVC_CONV_TILE_KS", 2);      // test hook: 1 = one wave per fragment set
     const int tc0 = p.M > 64 ? 0 : (p.M > 32 ? 1 : 2);            // 128 x 16, 64 x 32, 32 x 64
     const int BM = kTileBM[tc0], BN = kTileBN[tc0];
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-    if (ntm > 255 || ntn > 32767 || phv.size() > 255) return no(4);
+    if (ntm > 255 || ntn > 32767 || phv.size() > 255) return false;
     const long long nitems = (long long)ntm * ntn * (long long)phv.size() * B;
-    if (mode < 2 && nitems < 3 * g_ncu / 2) return no(5);                // short outputs: the K-split kernel fills the chip better
-    // per phase: (channel, tap) of every k from the gather table (entries are ci * ld + tap * dil - pad, k = ci * KW + tap); the kernel walks K
-    // tap-major in chunks of 16 channels, so the phase's weights are repacked: chunk t * G + g, slot kk <- k = (g * 16 + kk) * KW + t
+    if (mode < 2 && nitems < 3 * g_ncu / 2) return false;                // short outputs: the K-split kernel fills the chip better
+    // per phase: (channel, tap) of every k from the gather table; the kernel walks K tap-major in chunks of 16 channels, so the phase's weights are
+    // repacked: chunk t * G + g, slot kk <- k = (g * 16 + kk) * KW + t
     std::vector<PhaseD> phs(phv);
     std::vector<float> wnew;
     size_t lds_max = 0;
     const int mt = (p.M + 15) / 16;
     for (PhaseD &q : phs) {
-        const int K = q.nchunks * 16;
-        int cin = 1;
-        for (int k = 0; k < K; k++) cin = std::max(cin, (int)std::floor((double)koff[q.koff_off + k] / p.x_ld + 0.5) + 1);
-        if (cin % 16 != 0 || K % cin != 0) return no(6);
-        const int KW = K / cin;
-        if (KW > 255) return no(7);
-        const int dmin = koff[q.koff_off];
-        const int dil = KW > 1 ? koff[q.koff_off + 1] - koff[q.koff_off] : 1;
-        if (dil < 1 || dil > 255 || dmin > 0 || dmin < p.x_lo) return no(8);
-        for (int k = 0; k < K; k++) if (koff[q.koff_off + k] != (k / KW) * p.x_ld + dmin + (k % KW) * dil) return no(9);
+        if (!decode_taps(q, c.koff, p, 16)) return false;
+        const int KW = q.t_tab & 0xff, dil = q.t_tab >> 8, cin = q.t_cin;
         const int rl = BN + (KW - 1) * dil, rt = rl | 1, cs = cin + 8;
-        q.t_tab = KW | (dil << 8); q.t_cin = cin; q.t_rs = rt; q.t_dmin = dmin;
-        if (q.nchunks < 2 || cin / 16 < kshares) return no(10);          // (every K share needs a chunk; the kernel steps its tap / group counters by the share count)
+        q.t_rs = rt;
+        if (q.nchunks < 2 || cin / 16 < kshares) return false;          // (every K share needs a chunk; the kernel steps its tap / group counters by the share count)
         lds_max = std::max(lds_max, (std::max<size_t>(((size_t)cin * rt + 63) / 64 * 64, (size_t)kTileWF[tc0] * 256) + (size_t)rl * cs) * 4);
         std::vector<float> wold((size_t)mt * q.nchunks * 256);
         HIPCHK(hipMemcpy(wold.data(), p.w + q.w_off, wold.size() * 4, hipMemcpyDeviceToHost));
@@ -326,7 +375,8 @@ static bool queue_conv_tile(Plan &pl, IgemmP &p, int B, const std::vector<int> &
                         }
         q.w_off = (long long)base;
     }
-    if (lds_max > 100 * 1024) return no(11);
+    if (lds_max > 100 * 1024) return false;
+    Plan &pl = c.pl;
     wnew.resize(wnew.size() + (size_t)16 * 2 * 256, 0.f);      // slack: the kernel's weight requests run DA x KS chunks past a wave's last chunk
     p.w = pl.arena.upload(wnew);
     // work items, longest first, dealt to the CUs by longest-processing-time; block r * ncu + j = the r-th item of CU j
@@ -366,29 +416,13 @@ static bool queue_conv_tile(Plan &pl, IgemmP &p, int B, const std::vector<int> &
     }
     p.items = pl.arena.upload(order);
     p.ttab = nullptr;
-    p.ph = pl.arena.upload(phs);
-    p.nphase = (int)phs.size();
-    p.ph0 = phs[0];
+    set_phases(pl, p, phs);
     p.ntm = ntm; p.ntn = ntn; p.ksplit = 1; p.nbatch = B; p.m_fast = 0;
     const dim3 grid((unsigned)(order.size() / 2), 1u);
-    g_last_wgs = (int)nitems; g_last_waves = 4;
-    const double flops = 2.0 * p.M * (double)p.N * ksum * B;
-    pl.igemm_flops += flops; pl.n_igemm++;
-    Plan *plp = &pl;
-    { char d[200]; snprintf(d, sizeof d, "tile M=%d N=%d K=%d B=%d nph=%d tile=%dx%d items=%lld grid=%u lds=%zu pre=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, BM, BN, nitems, grid.x, lds_max, (int)(p.pre_act != ACT_NONE), ksum); pl.descs.push_back(d); note_kernel(d); }
-    const int desc_id = (int)pl.descs.size() - 1;
-    const IgemmP pc = p;
-    if (final_out) pl.final_out_honoured = true;
-    pl.ops.push_back([=](hipStream_t s) {
-        ProfEvent *pe = nullptr;
-        if (plp->profile) {
-            if (plp->prof_used == plp->prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); e.flops = 0; e.bytes = 0; plp->prof.push_back(e); }
-            pe = &plp->prof[plp->prof_used++]; pe->flops = flops; pe->bytes = 0; pe->desc = desc_id;
-        }
-        hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
-        if (final_out && plp->cur_out) { IgemmP q = pc; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch_conv_tile(tc0, kshares, q, grid, lds_max, s, ea, eb); }
-        else launch_conv_tile(tc0, kshares, pc, grid, lds_max, s, ea, eb);
-    });
+    char d[200];
+    snprintf(d, sizeof d, "tile M=%d N=%d K=%d B=%d nph=%d tile=%dx%d items=%lld grid=%u lds=%zu pre=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, BM, BN, nitems, grid.x, lds_max, (int)(p.pre_act != ACT_NONE), c.ksum);
+    queue_gemm_launch(pl, d, 2.0 * p.M * (double)p.N * c.ksum * B, (int)nitems, 4, c.final_out, p,
+                      [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) { launch_conv_tile(tc0, kshares, q, grid, lds_max, s, ea, eb); });
     return true;
 }
 
@@ -396,99 +430,113 @@ static bool queue_conv_tile(Plan &pl, IgemmP &p, int B, const std::vector<int> &
 // block once per workgroup and walks the taps from LDS (32x32x2 MFMAs); igemm32_kernel re-gathers the activation tile for every 16-deep K step, i.e.
 // once per tap.  The streams stay a grid dimension (tiles never straddle streams).  Test hook RVC_CONV32S: 0 = off, 2 = wherever eligible (any stream
 // count, any size), "RVC_CONV32S_TILE" forces a tile (0..2).  false = not eligible.
-static bool queue_conv32s(Plan &pl, IgemmP &p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phv, double ksum, bool final_out)
+static bool queue_conv32s(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &phv)
 {
-    if (t_choice.kind != 0 && t_choice.kind != 1) return false;          // (a trial of another kernel family)
-    const bool chosen = t_choice.kind == 1;                               // (a trial of THIS family: the size rules below are what is being measured)
+    if (c.ch.kind != 0 && c.ch.kind != 1) return false;          // (a trial of another kernel family)
+    const bool chosen = c.ch.kind == 1;                           // (a trial of THIS family: the size rules below are what is being measured)
     const int mode = chosen ? 2 : test_opt_int("RVC_CONV32S", 1);
-    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.y_ws != 1 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part || p.bf3 || pl.bf3) return false;
+    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.y_ws != 1 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part || p.bf3 || c.pl.bf3) return false;
     if (mode < 2 && (B <= 4 || p.N < 200 || p.M < 32)) return false;
     for (const PhaseD &q : phv) if (q.act_p1 != 0 || q.y_off != 0 || q.y_pos != 0) return false;
     // tile by the height of the weight panel; every wave owns 32 x 64 outputs (round 5 sweep of six tiles per layer at 8 / 16 / 32 / 64 streams, gpurun_out
     // of tests/tools/c32s_layers.py: 2 x 2 accumulator blocks per wave -- 128 x 128, 64 x 256 -- lose to these at every count but 64, where they tie)
     auto wgs_of = [&](int t) { return (long long)((p.M + kC32sBM[t] - 1) / kC32sBM[t]) * ((p.N + kC32sBN[t] - 1) / kC32sBN[t]) * (long long)phv.size() * B; };
     int tile = p.M <= 32 ? 0 : (p.M <= 64 ? 1 : 2);
-    const int forced = chosen ? (t_choice.a & 3) : test_opt_int("RVC_CONV32S_TILE", -1);
+    const int forced = chosen ? (c.ch.a & 3) : test_opt_int("RVC_CONV32S_TILE", -1);
     if (forced >= 0 && forced <= 2) tile = forced;
     // under two workgroups per CU the register-direct kernels with their K split win (256-row stage at 32 streams: 684 vs 720 us)
     if (mode < 2 && wgs_of(tile) < 2 * g_ncu) return false;
-    const int BM = kC32sBM[tile], BN = kC32sBN[tile], CB = kC32sCB;
+    const int BM = kC32sBM[tile], BN = kC32sBN[tile];
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
     if (phv.size() > 65535 || B > 65535) return false;
     std::vector<PhaseD> phs(phv);
     size_t lds_max = 0;
+    int kw_max = 0;
     for (PhaseD &q : phs) {
-        const int K = q.nchunks * 16;
-        int cin = 1;
-        for (int k = 0; k < K; k++) cin = std::max(cin, (int)std::floor((double)koff[q.koff_off + k] / p.x_ld + 0.5) + 1);
-        if (cin % CB != 0 || K % cin != 0) return false;
-        const int KW = K / cin;
-        if (KW > 255) return false;
-        const int dmin = koff[q.koff_off];
-        const int dil = KW > 1 ? koff[q.koff_off + 1] - koff[q.koff_off] : 1;
-        if (dil < 1 || dil > 255 || dmin > 0 || dmin < p.x_lo) return false;
-        for (int k = 0; k < K; k++) if (koff[q.koff_off + k] != (k / KW) * p.x_ld + dmin + (k % KW) * dil) return false;
+        if (!decode_taps(q, c.koff, p, kC32sCB)) return false;
+        const int KW = q.t_tab & 0xff, dil = q.t_tab >> 8;
         if ((KW - 1) * dil > 64) return false;          // (the kernel's staging grid covers BN + 64 columns)
-        q.t_tab = KW | (dil << 8); q.t_cin = cin; q.t_rs = 0; q.t_dmin = dmin;
+        q.t_rs = 0;
         lds_max = std::max(lds_max, (size_t)(BN + (KW - 1) * dil) * kC32sCS * 4);
-        // K order of the kernel: chunk (block * KW + tap) * 2 + group, slot kk of a chunk <- source k = (block * 32 + group * 16 + kk) * KW + tap: the phase's
-        // panel in that order comes from the per-model cache (c32s_panel: built once on the device, shared by all plans)
-        q.t_rs = KW;          // (scratch until the panels are fetched below: the staged kernel does not read t_rs)
+        kw_max = std::max(kw_max, KW);
     }
     if (lds_max > 60 * 1024) return false;
     // three-tap layers of the 64- / 128- / 256-row panels at 24 streams and more stay on igemm32_kernel: a channel block is only six chunks there, shorter than
     // the latency of the next block's staging loads that the first weight wait behind them has to sit out (32 / 64 streams: 546 vs 496, 998 vs 919 us for the
     // six 128-row layers, 351 vs 331, 592 vs 564 for the 64-row ones; at 16 streams this kernel wins them too: 294 vs 301, 182 vs 207)
-    {
-        int kw_max = 0;
-        for (const PhaseD &q : phs) kw_max = std::max(kw_max, q.t_tab & 0xff);
-        if (mode < 2 && kw_max <= 3 && p.M >= 64 && B >= 24) return false;
+    if (mode < 2 && kw_max <= 3 && p.M >= 64 && B >= 24) return false;
+    // K order of the kernel: chunk (block * KW + tap) * 2 + group, slot kk of a chunk <- source k = (block * 32 + group * 16 + kk) * KW + tap: the phase's
+    // panel in that order comes from the per-model cache (c32s_panel: built once on the device, shared by all plans)
+    const float *w0 = nullptr;
+    for (PhaseD &q : phs) {
+        const float *panel = c32s_panel(p.w + q.w_off, p.M, q.nchunks, q.t_cin, q.t_tab & 0xff);
+        if (!w0) w0 = panel;
+        q.w_off = panel - w0;          // (device pointers of one flat address space)
     }
-    {
-        const float *w0 = nullptr;
-        for (PhaseD &q : phs) {
-            const float *panel = c32s_panel(p.w + q.w_off, p.M, q.nchunks, q.t_cin, q.t_rs);
-            if (!w0) w0 = panel;
-            q.w_off = panel - w0;          // (device pointers of one flat address space)
-            q.t_rs = 0;
-        }
-        p.w = w0;
-    }
+    p.w = w0;
     p.koff = nullptr; p.items = nullptr; p.ttab = nullptr;
-    p.ph = pl.arena.upload(phs);
-    p.nphase = (int)phs.size();
-    p.ph0 = phs[0];
+    set_phases(c.pl, p, phs);
     p.ntm = ntm; p.ntn = ntn; p.ksplit = 1; p.nbatch = B; p.m_fast = 0;
     // conv32s_kernel's three ablation branches (timing only: they drop loads, i.e. change results) are reachable in the -DRVC_TUNING build alone; the product
     // always passes 0.  The never-taken branches stay in the kernel because they delimit the scheduler's regions (finding 6).
     p.pad2_ = tune_env("RVC_C32S_DBG") ? atoi(tune_env("RVC_C32S_DBG")) : 0;
     // the 64 x 128 tile takes the buffer-load kernel below 24 streams (us per six launches, all-buffer build against this one: 8 streams 437 vs 474, 16 streams 461 vs 479,
     // 32 streams 842 vs 775, 64 streams 1 543 vs 1 510-1 533); test hook RVC_CONV32S_BUF: 0 never, 2 always
-    const int buf_opt = chosen ? ((t_choice.a & 4) ? 2 : 0) : test_opt_int("RVC_CONV32S_BUF", 1);
+    const int buf_opt = chosen ? ((c.ch.a & 4) ? 2 : 0) : test_opt_int("RVC_CONV32S_BUF", 1);
     const int ltile = tile | ((tile == 1 && (buf_opt == 2 || (buf_opt == 1 && B < 24))) ? 4 : 0);
     const dim3 grid((unsigned)(ntm * ntn), (unsigned)B, (unsigned)p.nphase);
-    g_last_wgs = (int)(grid.x * grid.y * grid.z); g_last_waves = 4;
-    const double flops = 2.0 * p.M * (double)p.N * ksum * B;
-    pl.igemm_flops += flops; pl.n_igemm++;
-    Plan *plp = &pl;
-    { char d[200]; snprintf(d, sizeof d, "c32s M=%d N=%d K=%d B=%d nph=%d tile=%dx%d%s grid=%ux%ux%u lds=%zu pre=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, BM, BN, (ltile & 4) ? "b" : "", grid.x, grid.y, grid.z, lds_max, (int)(p.pre_act != ACT_NONE), ksum); pl.descs.push_back(d); note_kernel(d); }
-    const int desc_id = (int)pl.descs.size() - 1;
-    const IgemmP pc = p;
-    if (final_out) pl.final_out_honoured = true;
-    pl.ops.push_back([=](hipStream_t s) {
-        ProfEvent *pe = nullptr;
-        if (plp->profile) {
-            if (plp->prof_used == plp->prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); e.flops = 0; e.bytes = 0; plp->prof.push_back(e); }
-            pe = &plp->prof[plp->prof_used++]; pe->flops = flops; pe->bytes = 0; pe->desc = desc_id;
-        }
-        hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
-        if (final_out && plp->cur_out) { IgemmP q = pc; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch_conv32s(ltile, q, grid, lds_max, s, ea, eb); }
-        else launch_conv32s(ltile, pc, grid, lds_max, s, ea, eb);
-    });
+    char d[200];
+    snprintf(d, sizeof d, "c32s M=%d N=%d K=%d B=%d nph=%d tile=%dx%d%s grid=%ux%ux%u lds=%zu pre=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, BM, BN, (ltile & 4) ? "b" : "", grid.x, grid.y, grid.z, lds_max, (int)(p.pre_act != ACT_NONE), c.ksum);
+    queue_gemm_launch(c.pl, d, 2.0 * p.M * (double)p.N * c.ksum * B, (int)(grid.x * grid.y * grid.z), 4, c.final_out, p,
+                      [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) { launch_conv32s(ltile, q, grid, lds_max, s, ea, eb); });
+    c.built = Choice{1, ltile, 0};
     return true;
 }
 
-// generic: the caller fills geometry (N, NW, strides, koff, phases); this picks the tile + split-K and queues the op
+// exploratory split-bf16 GEMM (rvc_set_gemm_precision(e, 1); never the default): every 1-D layer the 32x32x2 kernel could take with >= 128 rows and
+// >= 250 workgroups of 128 x 128 (below that the fp32 kernels with their finer tiles win -- 16 streams, 768-row panels, 84 workgroups: 162 vs 86 us)
+static bool queue_bf3(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &phv)
+{
+    const int nchunks = p.K / 16;
+    if (!((p.bf3 || c.pl.bf3) && !p.glu && !c.ln_fold && B == 1 && p.x_hs == 0 && p.y_hm == 0 && p.M >= 128 && nchunks >= 2 && !p.accumulate &&
+          (size_t)nchunks * 64 + 2 * 2 * 128 * 48 <= 60 * 1024 &&
+          (long long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.nphase >= 250)) return false;
+    const bool pre = p.pre_act != ACT_NONE;
+    const bool lin = p.lin_cs4 != 0 && p.nphase == 1 && !pre;
+    const int nblk = (p.M + 31) / 32;
+    // every phase's fp32 fragment panel -> its split panels ([32-row block][chunk][hi | lo][lane][8 bf16]); phases keep their own K
+    size_t tot = 0;
+    std::vector<size_t> off(phv.size());
+    for (size_t f = 0; f < phv.size(); f++) { off[f] = tot; tot += (size_t)nblk * phv[f].nchunks * 2048; }
+    float *wsplit = (float *)wmalloc_plan(tot);
+    for (size_t f = 0; f < phv.size(); f++) bf3_pack(p.w + phv[f].w_off, p.M, phv[f].nchunks, (char *)wsplit + off[f], nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    c.pl.owned_dev.push_back(wsplit);
+    std::vector<PhaseD> ph3(phv);
+    for (size_t f = 0; f < ph3.size(); f++) ph3[f].w_off = (long long)(off[f] / 4);
+    p.w = wsplit;
+    set_phases(c.pl, p, ph3);
+    p.ksplit = 1; p.chunks_per_split = nchunks;
+    p.ntm = (p.M + 127) / 128; p.ntn = (p.N + 127) / 128;
+    p.m_fast = p.fold_n ? 1 : 0;
+    const dim3 grid((unsigned)(p.ntm * p.ntn), (unsigned)p.nphase);
+    const size_t lds = (lin ? 0 : (size_t)nchunks * 64) + (size_t)2 * 2 * 128 * 48;
+    char d[176];
+    snprintf(d, sizeof d, "bf3 M=%d N=%d K=%d B=1 nph=%d tile=128x128 grid=%ux%u lin=%d pre=%d", p.M, p.N, p.K, p.nphase, grid.x, grid.y, (int)lin, (int)pre);
+    queue_gemm_launch(c.pl, d, 2.0 * p.M * (double)p.N * c.ksum, (int)(grid.x * grid.y), 4, c.final_out, p,
+                      [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) { launch_igemm_bf3(lin, pre, q, grid, lds, s, ea, eb); });
+    return true;
+}
+
+// igemm2w_kernel's K split for 32 x 32 wave tiles: the one that puts ~4 800 waves into the launch, every wave keeping >= 4 chunks of K
+static int g2w_ksplit(int M, long long N, int nchunks)
+{
+    const long long tiles = (long long)((M + 31) / 32) * ((N + 31) / 32), want = (4800 + tiles / 2) / std::max<long long>(tiles, 1);
+    int ks = want <= 1 ? 1 : (want == 2 ? 2 : (want == 3 ? 3 : (want <= 4 ? 4 : 8)));
+    while (ks > 1 && nchunks / ks < 4) ks = ks == 8 ? 4 : ks - 1;
+    return ks;
+}
+
 // Which table-free 1x1 layers take igemm2w_kernel, and with what tile / K split (filled in from per-layer measurements: tests/tools/g2w_sweep.py).
 // gt < 0: not this kernel.
 // Round 5, tests/tools/g2w_sweep.py (isolated launches, one box; us, planner's previous choice -> this kernel):
@@ -508,118 +556,60 @@ static void g2w_rule(const IgemmP &p, int nchunks, int &gt, int &gk)
     // (round 5, after igemm32l_kernel: from 24 streams -- 2 664 columns -- the 768-row panels run faster on its 64 x 64 / 128 x 64 tiles: step time with this kernel
     //  / without, same process: 20 streams 14.73 / 14.91, 24 streams 16.19 / 15.81, 32 streams 20.16 / 19.70 ms; at 16 streams 11.34 / 11.47-11.60)
     if (p.M > 1024 ? p.N > 1000 : p.N > 2400) return;
-    const long long tiles = (long long)((p.M + 31) / 32) * ((p.N + 31) / 32);
-    const long long want = (4800 + tiles / 2) / tiles;
-    int ks = want <= 1 ? 1 : (want == 2 ? 2 : (want == 3 ? 3 : (want <= 4 ? 4 : 8)));
-    while (ks > 1 && nchunks / ks < 4) ks = ks == 8 ? 4 : ks - 1;
-    gt = 0; gk = ks;
+    gt = 0; gk = g2w_ksplit(p.M, p.N, nchunks);
 }
 
-static void queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phases, bool final_out)
+// igemm2w_kernel: register-direct 32x32x2 tiles for the table-free 1x1 layers at a few streams (igemm.hip.h).  Test hook RVC_FORCE_G2W = "tile,ks"
+// (tile 0 = 32 x 32 per wave, 1 = 64 x 32, 2 = 64 x 64; ks = 1 / 2 / 3 / 4 / 6 / 8 waves splitting K) forces it wherever it is eligible.
+static bool queue_g2w(GemmCall &c, IgemmP p, int B)
 {
-    p.probe = g_kprobe;
-    // many streams: fold them into the N axis (one launch-wide column index instead of a grid dimension), so that tiles are cut from
-    // B * N columns -- the ContentVec window (N = 111), the text encoder (N = 21) or RMVPE's deep levels (N = 4..64) no longer pad
-    // every stream up to a tile.  All offsets stay below 2^31 bytes / elements for every geometry the plugin can ask for (checked).
-    const int streams = B;
-    if (B > 1) {
-        // two to four streams, stride-1 1-D convolution: the staged-tile kernel with the streams in its work-item table (tried before the fold)
-        std::vector<PhaseD> phq(phases);
-        double ks0 = 0;
-        for (PhaseD &q : phq) { if (q.nchunks == 0) q.nchunks = p.K / 16; ks0 += q.nchunks * 16.0; }
-        std::stable_sort(phq.begin(), phq.end(), [](const PhaseD &a, const PhaseD &b) { return a.nchunks > b.nchunks; });
-        IgemmP pt = p;
-        if (queue_conv_tile(pl, pt, B, koff, phq, ks0, final_out)) return;
-        // five streams and more: the staged 32x32x2 convolution (streams as a grid dimension: also before the fold)
-        pt = p;
-        if (queue_conv32s(pl, pt, B, koff, phq, ks0, final_out)) return;
-        // (round 6: the same structure for RMVPE's Conv2d 3x3 layers -- conv2d32s_kernel, the padded planes as flat 1-D rows -- was built, parity-green and
-        //  SLOWER than the register-direct kernel at 16 / 64 / 128 streams, 41-54 against 60-67 TF/s: the layers are 0.6-1.2 GFLOP with K = 288-576, a tile's
-        //  K loop is 18-36 chunks behind a 50 KB staging prologue.  Not in the tree; DESIGN.md section 7 round 6, profiles/r06_conv2d32s_*.txt)
-    }
-    if (B == 1 && test_opt_int("RVC_CONV32S", 1) == 2) {           // test hook: the kernel forced onto one stream
-        std::vector<PhaseD> phq(phases);
-        double ks0 = 0;
-        for (PhaseD &q : phq) { if (q.nchunks == 0) q.nchunks = p.K / 16; ks0 += q.nchunks * 16.0; }
-        IgemmP pt = p;
-        if (queue_conv32s(pl, pt, B, koff, phq, ks0, final_out)) return;
-    }
-    if (B > 1 && !tune_env("RVC_NO_FOLD")) {
-        const long long lim = (1LL << 29);
-        if ((long long)B * p.x_bs < lim && (long long)B * p.y_bs < lim && (long long)B * (p.res ? p.res_bs : 0) < lim && (long long)B * p.N < (1LL << 30) &&
-            (size_t)(p.K / 16) * 64 <= 60 * 1024) {      // (the two-stage grid split-K fallback keeps the batch as a grid dimension)
-            p.fold_n = p.N; p.N = B * p.N; B = 1;
-        }
-    }
-    (void)streams;
-    // table entries become non-negative byte offsets; the kernel moves the base pointer back by koff_bias bytes
-    std::vector<int> kb(koff);
-    int kmin = 0;
-    for (int v : kb) kmin = std::min(kmin, v);
-    for (int &v : kb) v = (v - kmin) * 4;
-    p.koff_bias = -kmin * 4;
-    const bool pre = p.pre_act != ACT_NONE;
-    {
-        auto it = pl.koff_tabs.find(kb);
-        if (it == pl.koff_tabs.end()) it = pl.koff_tabs.emplace(kb, pl.arena.upload(kb)).first;
-        p.koff = it->second;
-    }
-    std::vector<PhaseD> phv(phases);
-    double ksum = 0;   // sum of the phases' K (phases of a fused launch may differ; p.K is the maximum)
-    for (PhaseD &q : phv) { if (q.nchunks == 0) q.nchunks = p.K / 16; ksum += q.nchunks * 16.0; }
-    // phases of unequal length (the fused ResBlock chains: kernel sizes 3 / 7 / 11) are dispatched longest first: the grid's z axis
-    // is walked last, so the workgroups of phase 0 start first and the short phases fill the tail instead of the long one forming it
-    if (!tune_env("RVC_NO_LPT"))
-        std::stable_sort(phv.begin(), phv.end(), [](const PhaseD &a, const PhaseD &b) { return a.nchunks > b.nchunks; });
-    p.ph = pl.arena.upload(phv);
-    p.nphase = (int)phv.size();
-    p.ph0 = phv[0];
     const int nchunks = p.K / 16;
-    auto tiles = [&](int c) {
-        long long tm = (p.M + 16 * kMF[c] - 1) / (16 * kMF[c]), tn = (p.N + 16 * kNF[c] - 1) / (16 * kNF[c]);
-        return tm * tn * B * p.nphase;
-    };
-    // Pick the largest tile that still yields >= 1024 waves (one per SIMD), using the in-workgroup K split
-    // (KS = 4/8/16 waves per tile) when the layer has too few tiles.  A wave keeps >= 4 chunks of K.
-    const int order_big[3] = {4, 3, 0}, order_small[3] = {2, 1, 0};
-    // a panel whose 32-row tiling would be >= 25 % padding (48 rows: the grouped positional convolution) takes the 16-row tiles
-    // (measured at one stream: 16 x 32, K split 8: 25 us against 37 us for the 32 x 32 tile the size rule picked)
-    const bool pad32 = p.M > 16 && (((p.M + 31) / 32 * 32 - p.M) * 4 >= p.M);
-    const int *order = (p.M > 16 && !pad32) ? order_big : order_small;
-    int cfg = 0, wg_ks = 1;
-    long long best_waves = -1;
-    bool found = false;
-    // phases of unequal length (fused ResBlock chains, kernel sizes 3/7/11) are all co-resident: finer tiles even out the
-    // per-SIMD load (measured on the decoder: 32x32 tiles 185 vs 200 us at C = 128, 127 vs 133 us at C = 64; folding the
-    // chains' average into one K-concatenated GEMM was also measured: no gain)
-    bool uneven = false;
-    for (const PhaseD &q : phv) uneven = uneven || q.nchunks != phv[0].nchunks;
-    long long want_waves = (uneven && p.M >= 64) ? 2048 : 1024;
-    if (const char *f = tune_env("RVC_WANT_WAVES")) { if (p.fold_n) want_waves = atoll(f); }      // tuning aid
-    for (int oi = 0; oi < 3 && !found; oi++) {
-        const int c = order[oi];
-        for (int ks = 1; ks <= 16; ks = ks == 1 ? 4 : ks * 2) {
-            if (ks > 1 && (nchunks / ks < 4 || ks * kMF[c] * kNF[c] > 32)) break;
-            if ((size_t)nchunks * 64 + (ks > 1 ? (size_t)ks * kMF[c] * kNF[c] * 1024 : 0) > 60 * 1024) break;
-            const long long w = tiles(c) * ks;
-            if (w > best_waves) { best_waves = w; cfg = c; wg_ks = ks; }
-            // streams folded into N: the workgroups must also spread evenly over the CUs (768 x 3072 at 8 streams: 336 workgroups of 32 x 64 tiles
-            // are one or two per CU, 52 TF/s; 672 of 32 x 32 tiles 68 TF/s).  Below four rounds a last round under 80 % full sends the choice on
-            // to the next smaller tile.  (One stream keeps its own, latency-tuned rule.)
-            if (p.fold_n && oi == 0 && !tune_env("RVC_NO_BALANCE")) {         // (one step down only: the 16 x 16 tile loses more than an uneven last round costs)
-                const long long wgs = ks > 1 ? tiles(c) : (tiles(c) + 3) / 4, rounds = (wgs + g_ncu - 1) / g_ncu;
-                if (rounds < 4 && wgs * 5 < rounds * g_ncu * 4) continue;
-            }
-            if (w >= want_waves) { cfg = c; wg_ks = ks; found = true; break; }
-        }
-    }
-    // throughput mode (many streams): workgroup-tiled kernel with the activation tile shared through LDS
+    // (round 6) a layer that consumes a not yet normalised tensor (IgemmP::ln_wsum) can take the kernel's LayerNorm-consumer variant: 32 x 32 wave tile, four or
+    // eight K shares.  One stream, tests/tools/g2w_sweep.py: the 2304- / 3072-row projections 12.4 / 13.4 -> 9.5 / 10.0 us against igemm2_kernel's LNB tiles;
+    // the 768-row layers (output projection, second FFN layer, feature projection) stay: 6.0 / 13.5 / 5.0 vs 6.3 / 15.0 / 5.4.  Test hook RVC_G2W_LN = 0: never.
+    const bool g2w_ln = p.ln_wsum && !p.ln_stats_in && !c.phase_epi;
+    const bool g2w_ok = p.lin_cs4 != 0 && p.nphase == 1 && p.pre_act == ACT_NONE && !p.glu && (!c.ln_fold || g2w_ln) && B == 1 && nchunks >= 1;
+    int gt = -1, gk = 1;
+    if (c.ch.kind == 2) { gt = c.ch.a; gk = c.ch.b; }
+    else if (c.ch.kind != 0) gt = -1;
+    else if (const char *f = test_opt("RVC_FORCE_G2W")) { if (sscanf(f, "%d,%d", &gt, &gk) < 1) gt = -1; }
+    else if (g2w_ln) { if (c.streams == 1 && p.M >= 2048 && nchunks >= 32 && test_opt_int("RVC_G2W_LN", 1) != 0) { gt = 0; gk = 8; } }
+    else g2w_rule(p, nchunks, gt, gk);
+    if (g2w_ln && (gt != 0 || (gk != 4 && gk != 8) || nchunks < gk)) gt = -1;          // (only those two instantiations exist)
+    if (!g2w_ok || gt < 0 || gt > 2) return false;
+    if (!(gt == 0 && (gk == 12 || gk == 16)) && gk != 1 && gk != 2 && gk != 3 && gk != 4 && gk != 6 && gk != 8) gk = gk > 8 ? 8 : 4;
+    while (gk > 1 && nchunks < gk) gk = gk == 16 ? 12 : (gk == 12 ? 8 : (gk == 8 ? 6 : (gk == 6 ? 4 : gk - 1)));
+    const int bm = 32 * kG2wMT[gt], bn = 32 * kG2wNT[gt];
+    p.ksplit = 1; p.chunks_per_split = nchunks;
+    p.ntm = (p.M + bm - 1) / bm; p.ntn = (p.N + bn - 1) / bn;
+    const bool wh = p.ntm >= 2;           // all column tiles of one weight-row block on one XCD (its L2 is private)
+    p.m_fast = wh ? (p.ntm + 7) / 8 * 8 : 0;
+    unsigned gx = (unsigned)(wh ? p.ntm : p.ntn);
+    if (wh && gx >= 8) gx = (gx + 7) / 8 * 8;
+    const dim3 grid(gx, (unsigned)(wh ? p.ntn : p.ntm), 1);
+    if (grid.y > 65535) throw ShapeError("implicit GEMM grid too large");
+    p.nbatch = 1;
+    const size_t lds = gk > 1 ? (size_t)gk * kG2wMT[gt] * kG2wNT[gt] * 1024 * sizeof(float) + (g2w_ln ? (size_t)gk * 32 * 2 * sizeof(float) : 0) : 0;
+    char d[176];
+    snprintf(d, sizeof d, "g2w M=%d N=%d K=%d B=1 nph=1 tile=%dx%d ks=%d grid=%ux%u%s", p.M, p.N, p.K, bm, bn, gk, grid.x, grid.y, g2w_ln ? " ln=1" : "");
+    queue_gemm_launch(c.pl, d, 2.0 * p.M * (double)p.N * c.ksum, (int)(grid.x * grid.y), gk, c.final_out, p,
+                      [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) {
+                          if (g2w_ln) launch_igemm2w_ln(gk, q, grid, lds, s, ea, eb);
+                          else launch_igemm2w(gt, gk, q, grid, lds, s, ea, eb);
+                      });
+    c.built = Choice{2, gt, gk};
+    return true;
+}
+
+// throughput mode (many streams): workgroup-tiled kernels with the activation tile shared through LDS -- lds_cfg 3 4 5 7 8: the 32x32x2 kernels
+// (igemm32 / igemm32l), 0 1 2 6: the 16x16x4 LDS kernel
+static bool queue_tiled(GemmCall &c, IgemmP p, int B)
+{
+    const int nchunks = p.K / 16;
+    const bool pre = p.pre_act != ACT_NONE;
+    const bool g32_ok = !c.ln_fold && !p.glu && nchunks >= 2 && (size_t)nchunks * 64 + 2 * 256 * 20 * 4 <= 60 * 1024;
     int lds_cfg = -1;
-    bool phase_epi = false;                               // per-phase activation / output tensor: igemm2 only
-    for (const PhaseD &q : phv) phase_epi = phase_epi || q.act_p1 != 0 || q.y_off != 0;
-    if (queue_conv_tile(pl, p, B, koff, phv, ksum, final_out)) return;
-    const bool ln_fold = p.ln_wsum || p.ln_stats_in || phase_epi;      // folded LayerNorm lives in the register-direct kernel's K-split epilogue
-    if (!ln_fold && !tune_env("RVC_NO_LDS_GEMM") && nchunks >= 2 && (size_t)nchunks * 64 + 2 * 256 * 20 * 4 <= 60 * 1024) {
+    if (!c.ln_fold && !tune_env("RVC_NO_LDS_GEMM") && nchunks >= 2 && (size_t)nchunks * 64 + 2 * 256 * 20 * 4 <= 60 * 1024) {
         int bm = p.M >= 96 ? 128 : (p.M >= 48 ? 64 : (p.M > 16 ? 32 : 0));
         if (const char *f = tune_env("RVC_G32_BM")) { const int v = atoi(f); if (v == 32 || v == 64 || v == 128) bm = v; }   // tuning aid
         const int bn = bm == 128 ? 128 : 256;
@@ -657,7 +647,7 @@ static void queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &
     // streams 3006 -> 2774, 768 x 768 883 -> 771 --; a 256-row panel with 252 workgroups loses to the register-direct kernel, 731 -> 1103)
     static const long long g32_narrow_env = tune_env("RVC_G32_NARROW") ? atoll(tune_env("RVC_G32_NARROW")) : -1;     // 0 = off
     const long long g32_narrow_min = g32_narrow_env >= 0 ? g32_narrow_env : (p.M >= 512 ? 250 : 500);
-    if (lds_cfg < 0 && !ln_fold && g32_narrow_min > 0 && !tune_env("RVC_NO_LDS_GEMM") && !p.glu && nchunks >= 2 && p.M >= 96 && (size_t)nchunks * 64 + 2 * 64 * 20 * 4 <= 60 * 1024) {
+    if (lds_cfg < 0 && !c.ln_fold && g32_narrow_min > 0 && !tune_env("RVC_NO_LDS_GEMM") && !p.glu && nchunks >= 2 && p.M >= 96 && (size_t)nchunks * 64 + 2 * 64 * 20 * 4 <= 60 * 1024) {
         const long long wgs = (long long)((p.M + 127) / 128) * ((p.N + 63) / 64) * B * p.nphase;
         if (wgs >= g32_narrow_min) lds_cfg = 7;
         // between one and two workgroups per CU the 128 x 64 tile leaves half of the slots empty: 64 x 64 tiles (one 32 x 32 accumulator per wave) double them
@@ -666,173 +656,113 @@ static void queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &
         //  128 x 64 -- run 119-120 us on the 128 x 64 tile against 148-152 on 64 x 64, isolated, at 4 and 16 streams: tests/tools/tile_sweep.py)
         if (lds_cfg == 7 && wgs < 500 && p.lin_cs4 != 0 && !tune_env("RVC_NO_G32_SQ64")) lds_cfg = 8;
     }
-    // exploratory split-bf16 GEMM (rvc_set_gemm_precision(e, 1); never the default): every 1-D layer the 32x32x2 kernel could take with >= 128 rows and
-    // >= 250 workgroups of 128 x 128 (below that the fp32 kernels with their finer tiles win -- 16 streams, 768-row panels, 84 workgroups: 162 vs 86 us)
-    if ((p.bf3 || pl.bf3) && !p.glu && !ln_fold && B == 1 && p.x_hs == 0 && p.y_hm == 0 && p.M >= 128 && nchunks >= 2 && !p.accumulate &&
-        (size_t)nchunks * 64 + 2 * 2 * 128 * 48 <= 60 * 1024 &&
-        (long long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.nphase >= 250) {
-        const bool lin = p.lin_cs4 != 0 && p.nphase == 1 && !pre;
-        const int nblk = (p.M + 31) / 32;
-        // every phase's fp32 fragment panel -> its split panels ([32-row block][chunk][hi | lo][lane][8 bf16]); phases keep their own K
-        size_t tot = 0;
-        std::vector<size_t> off(phv.size());
-        for (size_t f = 0; f < phv.size(); f++) { off[f] = tot; tot += (size_t)nblk * phv[f].nchunks * 2048; }
-        float *wsplit = (float *)wmalloc_plan(tot);
-        for (size_t f = 0; f < phv.size(); f++) bf3_pack(p.w + phv[f].w_off, p.M, phv[f].nchunks, (char *)wsplit + off[f], nullptr);
-        HIPCHK(hipDeviceSynchronize());
-        pl.owned_dev.push_back(wsplit);
-        std::vector<PhaseD> ph3(phv);
-        for (size_t f = 0; f < ph3.size(); f++) ph3[f].w_off = (long long)(off[f] / 4);
-        p.w = wsplit; p.ph = pl.arena.upload(ph3); p.ph0 = ph3[0];
-        p.ksplit = 1; p.chunks_per_split = nchunks;
-        p.ntm = (p.M + 127) / 128; p.ntn = (p.N + 127) / 128;
-        p.m_fast = p.fold_n ? 1 : 0;
-        const dim3 grid((unsigned)(p.ntm * p.ntn), (unsigned)p.nphase);
-        const size_t lds = (lin ? 0 : (size_t)nchunks * 64) + (size_t)2 * 2 * 128 * 48;
-        g_last_wgs = (int)(grid.x * grid.y); g_last_waves = 4;
-        const double flops = 2.0 * p.M * (double)p.N * ksum;
-        pl.igemm_flops += flops; pl.n_igemm++;
-        Plan *plp = &pl;
-        { char d[176]; snprintf(d, sizeof d, "bf3 M=%d N=%d K=%d B=1 nph=%d tile=128x128 grid=%ux%u lin=%d pre=%d", p.M, p.N, p.K, p.nphase, grid.x, grid.y, (int)lin, (int)pre); pl.descs.push_back(d); note_kernel(d); }
-        const int desc_id = (int)pl.descs.size() - 1;
-        if (final_out) pl.final_out_honoured = true;
-        pl.ops.push_back([=](hipStream_t s) {
-            ProfEvent *pe = nullptr;
-            if (plp->profile) {
-                if (plp->prof_used == plp->prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); e.flops = 0; e.bytes = 0; plp->prof.push_back(e); }
-                pe = &plp->prof[plp->prof_used++]; pe->flops = flops; pe->bytes = 0; pe->desc = desc_id;
-            }
-            hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
-            if (final_out && plp->cur_out) { IgemmP q = p; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch_igemm_bf3(lin, pre, q, grid, lds, s, ea, eb); }
-            else launch_igemm_bf3(lin, pre, p, grid, lds, s, ea, eb);
-        });
-        return;
-    }
-    // igemm2w_kernel: register-direct 32x32x2 tiles for the table-free 1x1 layers at a few streams (igemm.hip.h).  Test hook RVC_FORCE_G2W = "tile,ks"
-    // (tile 0 = 32 x 32 per wave, 1 = 64 x 32, 2 = 64 x 64; ks = 1 / 2 / 3 / 4 / 6 / 8 waves splitting K) forces it wherever it is eligible.
-    {
-        // (round 6) a layer that consumes a not yet normalised tensor (IgemmP::ln_wsum) can take the kernel's LayerNorm-consumer variant: 32 x 32 wave tile, four or
-        // eight K shares.  One stream, tests/tools/g2w_sweep.py: the 2304- / 3072-row projections 12.4 / 13.4 -> 9.5 / 10.0 us against igemm2_kernel's LNB tiles;
-        // the 768-row layers (output projection, second FFN layer, feature projection) stay: 6.0 / 13.5 / 5.0 vs 6.3 / 15.0 / 5.4.  Test hook RVC_G2W_LN = 0: never.
-        const bool g2w_ln = p.ln_wsum && !p.ln_stats_in && !phase_epi;
-        const bool g2w_ok = p.lin_cs4 != 0 && p.nphase == 1 && !pre && !p.glu && (!ln_fold || g2w_ln) && B == 1 && nchunks >= 1;
-        int gt = -1, gk = 1;
-        if (t_choice.kind == 2) { gt = t_choice.a; gk = t_choice.b; }
-        else if (t_choice.kind != 0) gt = -1;
-        else if (const char *f = test_opt("RVC_FORCE_G2W")) { if (sscanf(f, "%d,%d", &gt, &gk) < 1) gt = -1; }
-        else if (g2w_ln) { if (streams == 1 && p.M >= 2048 && nchunks >= 32 && test_opt_int("RVC_G2W_LN", 1) != 0) { gt = 0; gk = 8; } }
-        else g2w_rule(p, nchunks, gt, gk);
-        if (g2w_ln && (gt != 0 || (gk != 4 && gk != 8) || nchunks < gk)) gt = -1;          // (only those two instantiations exist)
-        if (g2w_ok && gt >= 0 && gt <= 2) {
-            if (!(gt == 0 && (gk == 12 || gk == 16)) && gk != 1 && gk != 2 && gk != 3 && gk != 4 && gk != 6 && gk != 8) gk = gk > 8 ? 8 : 4;
-            while (gk > 1 && nchunks < gk) gk = gk == 16 ? 12 : (gk == 12 ? 8 : (gk == 8 ? 6 : (gk == 6 ? 4 : gk - 1)));
-            const int bm = 32 * kG2wMT[gt], bn = 32 * kG2wNT[gt];
-            p.ksplit = 1; p.chunks_per_split = nchunks;
-            p.ntm = (p.M + bm - 1) / bm; p.ntn = (p.N + bn - 1) / bn;
-            const bool wh = p.ntm >= 2;           // all column tiles of one weight-row block on one XCD (its L2 is private)
-            p.m_fast = wh ? (p.ntm + 7) / 8 * 8 : 0;
-            unsigned gx = (unsigned)(wh ? p.ntm : p.ntn);
-            if (wh && gx >= 8) gx = (gx + 7) / 8 * 8;
-            const dim3 grid(gx, (unsigned)(wh ? p.ntn : p.ntm), 1);
-            if (grid.y > 65535) throw ShapeError("implicit GEMM grid too large");
-            p.nbatch = 1;
-            const size_t lds = gk > 1 ? (size_t)gk * kG2wMT[gt] * kG2wNT[gt] * 1024 * sizeof(float) + (g2w_ln ? (size_t)gk * 32 * 2 * sizeof(float) : 0) : 0;
-            g_last_wgs = (int)(grid.x * grid.y); g_last_waves = gk;
-            const double flops = 2.0 * p.M * (double)p.N * ksum;
-            pl.igemm_flops += flops; pl.n_igemm++;
-            Plan *plp = &pl;
-            { char d[176]; snprintf(d, sizeof d, "g2w M=%d N=%d K=%d B=1 nph=1 tile=%dx%d ks=%d grid=%ux%u%s", p.M, p.N, p.K, bm, bn, gk, grid.x, grid.y, g2w_ln ? " ln=1" : ""); pl.descs.push_back(d); note_kernel(d); }
-            const int desc_id = (int)pl.descs.size() - 1;
-            if (final_out) pl.final_out_honoured = true;
-            pl.ops.push_back([=](hipStream_t s) {
-                ProfEvent *pe = nullptr;
-                if (plp->profile) {
-                    if (plp->prof_used == plp->prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); e.flops = 0; e.bytes = 0; plp->prof.push_back(e); }
-                    pe = &plp->prof[plp->prof_used++]; pe->flops = flops; pe->bytes = 0; pe->desc = desc_id;
-                }
-                hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
-                if (g2w_ln) launch_igemm2w_ln(gk, p, grid, lds, s, ea, eb);
-                else if (final_out && plp->cur_out) { IgemmP q = p; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch_igemm2w(gt, gk, q, grid, lds, s, ea, eb); }
-                else launch_igemm2w(gt, gk, p, grid, lds, s, ea, eb);
-            });
-            return;
-        }
-    }
     // tuning aid: RVC_G32W = "lc" forces one of the 32x32x2 tiles (3 4 5 7 8) on every layer that kernel can take, "-1" the register-direct kernel
     // (then RVC_FORCE_CFG picks its tile): tests/tools/tile_sweep.py
     if (const char *f = tune_env("RVC_G32W")) {
         const int wl = atoi(f);
-        const bool g32_ok = !ln_fold && !p.glu && nchunks >= 2 && (size_t)nchunks * 64 + 2 * 256 * 20 * 4 <= 60 * 1024;
         if (g32_ok && (wl == 3 || wl == 4 || wl == 5 || wl == 7 || wl == 8)) lds_cfg = wl;
         else if (wl == -1) lds_cfg = -1;
     }
-    if (t_choice.kind == 3) {
-        const int wl = t_choice.a;
-        const bool g32_ok = !ln_fold && !p.glu && nchunks >= 2 && (size_t)nchunks * 64 + 2 * 256 * 20 * 4 <= 60 * 1024;
+    if (c.ch.kind == 3) {
+        const int wl = c.ch.a;
         const int need_m = (wl == 3 || wl == 7) ? 96 : ((wl == 4 || wl == 8) ? 48 : 17);
         if (g32_ok && (wl == 3 || wl == 4 || wl == 5 || wl == 7 || wl == 8) && p.M >= need_m) lds_cfg = wl;
-    } else if (t_choice.kind == 4) lds_cfg = -1;
+    } else if (c.ch.kind == 4) lds_cfg = -1;
     // igemm32l_kernel (one-phase 1-D layers, buffer loads with scalar offsets): its 128 x 64 tile beats the 128 x 128 tile of either kernel on every layer it can
     // take -- the 3072-row projection (64 streams 36.12 -> 35.81 ms), the 2304-row one (35.31 -> 35.05), the strided stem (35.28 -> 35.05; 16 / 32 streams
     // 11.35 / 19.70 -> 11.23 / 19.50) -- so those layers move there (test hook RVC_G32L_TALL = 0: keep the 128 x 128 tile)
-    const bool g32l_on = p.lin_cs4 != 0 && p.nphase == 1 && !pre && !p.bf3 && !pl.bf3 && test_opt_int("RVC_G32L", 1) != 0;
-    const bool g32t_on = !g32l_on && p.lin_cs4 == 0 && p.nphase == 1 && B == 1 && p.x_hs == 0 && p.y_hm == 0 && !p.bf3 && !pl.bf3 && !p.glu &&
+    const bool g32l_on = p.lin_cs4 != 0 && p.nphase == 1 && !pre && !p.bf3 && !c.pl.bf3 && test_opt_int("RVC_G32L", 1) != 0;
+    const bool g32t_on = !g32l_on && p.lin_cs4 == 0 && p.nphase == 1 && B == 1 && p.x_hs == 0 && p.y_hm == 0 && !p.bf3 && !c.pl.bf3 && !p.glu &&
                          test_opt_int("RVC_G32L", 1) != 0 && test_opt_int("RVC_G32L_TAB", 1) != 0;
-    if ((g32l_on || (g32t_on && !pre)) && lds_cfg == 3 && t_choice.kind != 3 && test_opt_int("RVC_G32L_TALL", 1) != 0) lds_cfg = 7;
-    if (lds_cfg >= 0) {
-        const int bm = lds_cfg == 8 ? 64 : (lds_cfg == 7 ? 128 : (lds_cfg == 6 ? 48 : (lds_cfg % 3 == 0 ? 128 : (lds_cfg % 3 == 1 ? 64 : 32))));
-        const int bn = (lds_cfg == 7 || lds_cfg == 8) ? 64 : ((lds_cfg != 6 && lds_cfg % 3 == 0) ? 128 : 256);
-        p.ksplit = 1; p.chunks_per_split = nchunks;
-        p.ntm = (p.M + bm - 1) / bm; p.ntn = (p.N + bn - 1) / bn;
-        // tile order of the tiled kernels when the streams are folded into N: m fastest over XCD-local tile ids (1), or over the raw block index (2)
-        // where that keeps a large weight matrix partitioned over the XCDs (igemm.hip.h, xcd_tile_id)
-        p.m_fast = p.fold_n ? ((p.ntm % 8 == 0 && (size_t)p.M * (size_t)ksum * sizeof(float) > ((size_t)4 << 20)) ? 2 : 1) : 0;
-        dim3 grid(p.ntm * p.ntn, B * p.nphase);
-        const bool g32k = lds_cfg >= 3 && lds_cfg != 6;            // igemm32_kernel keeps its activation tile column-major, [2][bn][20]
-        const size_t lds = (size_t)nchunks * 64 + (g32k ? (size_t)2 * bn * 20 * 4 : (size_t)2 * 16 * (bn + 4) * 4);
-        g_last_wgs = (int)(grid.x * grid.y); g_last_waves = 4;
-        const double flops = 2.0 * p.M * (double)p.N * ksum * B;
-        pl.igemm_flops += flops; pl.n_igemm++;
-        Plan *plp = &pl;
-        const int lc = lds_cfg;
-        // table-free 1x1 layers on tiles 3 / 7 / 8: igemm32l_kernel (buffer loads with scalar row offsets, no offset table in LDS); test hook RVC_G32L = 0: off
-        // ... and the one-phase 1-D layers WITH a table (the strided stem of ContentVec, three-tap decoder layers): the same kernel with the table entries as
-        // scalar loads (test hook RVC_G32L_TAB = 0: off)
-        const bool g32t = (lc == 3 || lc == 7 || lc == 8) && g32t_on &&
-                          !(lc == 3 && pre);           // (the decoder's three-tap 128-row layers with the fused input activation: 167 vs 152 us on the 128 x 128 tile)
-        const bool g32l = ((lc == 3 || lc == 7 || lc == 8) && g32l_on && !(lc == 3 && p.m_fast == 2)) || g32t;
-        const int g32l_mode = g32t ? (pre ? 2 : 1) : 0;
-        const size_t lds_l = (size_t)2 * bn * 20 * 4;
-        // panel order inside the XCDs (igemm32l.hip.h, m_fast = 3) for tall table-free panels whose weights exceed an L2: mp m-tiles = the largest panel of
-        // <= 2.5 MB; test hook RVC_G32L_PANEL = 0: the orders of round 4 (m fastest over XCD-local ids / the raw block index)
-        if (g32l && !g32t && p.fold_n && B == 1 && (lc == 7 || lc == 8) && p.ntm >= 8 && p.ntn >= 64 && test_opt_int("RVC_G32L_PANEL", 1) != 0) {          // (from ~37 streams: at 16 streams -- 28 n-tiles, 3.5 per XCD -- the padded grid costs 2.4 %)
-            const size_t per_tile = (size_t)bm * (size_t)ksum * sizeof(float);
-            const int mp = (int)std::max<size_t>(1, ((size_t)5 << 19) / per_tile);
-            if ((size_t)p.M * (size_t)ksum * sizeof(float) > ((size_t)5 << 19) && mp < p.ntm) {
-                p.m_fast = 3; p.pad2_ = mp;
-                const int nx_max = (p.ntn + 7) / 8;
-                grid = dim3((unsigned)(8 * nx_max * p.ntm), 1u);
-            }
+    if ((g32l_on || (g32t_on && !pre)) && lds_cfg == 3 && c.ch.kind != 3 && test_opt_int("RVC_G32L_TALL", 1) != 0) lds_cfg = 7;
+    if (lds_cfg < 0) return false;
+    const int lc = lds_cfg;
+    const int bm = lc == 8 ? 64 : (lc == 7 ? 128 : (lc == 6 ? 48 : (lc % 3 == 0 ? 128 : (lc % 3 == 1 ? 64 : 32))));
+    const int bn = (lc == 7 || lc == 8) ? 64 : ((lc != 6 && lc % 3 == 0) ? 128 : 256);
+    p.ksplit = 1; p.chunks_per_split = nchunks;
+    p.ntm = (p.M + bm - 1) / bm; p.ntn = (p.N + bn - 1) / bn;
+    // tile order of the tiled kernels when the streams are folded into N: m fastest over XCD-local tile ids (1), or over the raw block index (2)
+    // where that keeps a large weight matrix partitioned over the XCDs (igemm.hip.h, xcd_tile_id)
+    p.m_fast = p.fold_n ? ((p.ntm % 8 == 0 && (size_t)p.M * (size_t)c.ksum * sizeof(float) > ((size_t)4 << 20)) ? 2 : 1) : 0;
+    dim3 grid(p.ntm * p.ntn, B * p.nphase);
+    const bool g32k = lc >= 3 && lc != 6;            // igemm32_kernel keeps its activation tile column-major, [2][bn][20]
+    const size_t lds = (size_t)nchunks * 64 + (g32k ? (size_t)2 * bn * 20 * 4 : (size_t)2 * 16 * (bn + 4) * 4);
+    const int wgs = (int)(grid.x * grid.y);
+    // table-free 1x1 layers on tiles 3 / 7 / 8: igemm32l_kernel (buffer loads with scalar row offsets, no offset table in LDS); test hook RVC_G32L = 0: off
+    // ... and the one-phase 1-D layers WITH a table (the strided stem of ContentVec, three-tap decoder layers): the same kernel with the table entries as
+    // scalar loads (test hook RVC_G32L_TAB = 0: off)
+    const bool g32t = (lc == 3 || lc == 7 || lc == 8) && g32t_on &&
+                      !(lc == 3 && pre);           // (the decoder's three-tap 128-row layers with the fused input activation: 167 vs 152 us on the 128 x 128 tile)
+    const bool g32l = ((lc == 3 || lc == 7 || lc == 8) && g32l_on && !(lc == 3 && p.m_fast == 2)) || g32t;
+    const int g32l_mode = g32t ? (pre ? 2 : 1) : 0;
+    const size_t lds_l = (size_t)2 * bn * 20 * 4;
+    // panel order inside the XCDs (igemm32l.hip.h, m_fast = 3) for tall table-free panels whose weights exceed an L2: mp m-tiles = the largest panel of
+    // <= 2.5 MB; test hook RVC_G32L_PANEL = 0: the orders of round 4 (m fastest over XCD-local ids / the raw block index)
+    if (g32l && !g32t && p.fold_n && B == 1 && (lc == 7 || lc == 8) && p.ntm >= 8 && p.ntn >= 64 && test_opt_int("RVC_G32L_PANEL", 1) != 0) {          // (from ~37 streams: at 16 streams -- 28 n-tiles, 3.5 per XCD -- the padded grid costs 2.4 %)
+        const size_t per_tile = (size_t)bm * (size_t)c.ksum * sizeof(float);
+        const int mp = (int)std::max<size_t>(1, ((size_t)5 << 19) / per_tile);
+        if ((size_t)p.M * (size_t)c.ksum * sizeof(float) > ((size_t)5 << 19) && mp < p.ntm) {
+            p.m_fast = 3; p.pad2_ = mp;
+            const int nx_max = (p.ntn + 7) / 8;
+            grid = dim3((unsigned)(8 * nx_max * p.ntm), 1u);
         }
-        { char d[160]; snprintf(d, sizeof d, "%s M=%d N=%d K=%d B=%d nph=%d tile=%dx%d grid=%ux%u", g32t ? "g32t" : g32l ? "g32l" : (lds_cfg >= 3 && lds_cfg != 6) ? "g32" : "lds", p.M, p.N, p.K, B, p.nphase, bm, bn, grid.x, grid.y); pl.descs.push_back(d); note_kernel(d); }
-        const int desc_id = (int)pl.descs.size() - 1;
-        if (final_out) pl.final_out_honoured = true;
-        pl.ops.push_back([=](hipStream_t s) {
-            ProfEvent *pe = nullptr;
-            if (plp->profile) {
-                if (plp->prof_used == plp->prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); e.flops = 0; e.bytes = 0; plp->prof.push_back(e); }
-                pe = &plp->prof[plp->prof_used++]; pe->flops = flops; pe->bytes = 0; pe->desc = desc_id;
+    }
+    char d[160];
+    snprintf(d, sizeof d, "%s M=%d N=%d K=%d B=%d nph=%d tile=%dx%d grid=%ux%u", g32t ? "g32t" : g32l ? "g32l" : g32k ? "g32" : "lds", p.M, p.N, p.K, B, p.nphase, bm, bn, grid.x, grid.y);
+    queue_gemm_launch(c.pl, d, 2.0 * p.M * (double)p.N * c.ksum * B, wgs, 4, c.final_out, p,
+                      [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) {
+                          if (g32l) launch_igemm32l(lc, g32l_mode, q, grid, lds_l, s, ea, eb);
+                          else launch_igemm_tiled(lc, pre, q, grid, lds, s, ea, eb);
+                      });
+    c.built = Choice{3, lc, 0};
+    return true;
+}
+
+// the register-direct kernel (igemm2): takes every layer the families above leave
+static void queue_reg(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &phv)
+{
+    const int nchunks = p.K / 16;
+    const bool pre = p.pre_act != ACT_NONE;
+    // tile cf with a K split of ks waves: a wave keeps >= 4 chunks, at most 32 accumulator fragments per tile, the offset slice and the split's partial sums in LDS
+    auto fits = [&](int cf, int ks) {
+        return (ks == 1 || (nchunks / ks >= 4 && ks * kMF[cf] * kNF[cf] <= 32)) && (size_t)nchunks * 64 + (ks > 1 ? (size_t)ks * kMF[cf] * kNF[cf] * 1024 : 0) <= 60 * 1024;
+    };
+    auto tiles = [&](int cf) {
+        long long tm = (p.M + 16 * kMF[cf] - 1) / (16 * kMF[cf]), tn = (p.N + 16 * kNF[cf] - 1) / (16 * kNF[cf]);
+        return tm * tn * B * p.nphase;
+    };
+    // Pick the largest tile that still yields >= 1024 waves (one per SIMD), using the in-workgroup K split
+    // (KS = 4/8/16 waves per tile) when the layer has too few tiles.  A wave keeps >= 4 chunks of K.
+    const int order_big[3] = {4, 3, 0}, order_small[3] = {2, 1, 0};
+    // a panel whose 32-row tiling would be >= 25 % padding (48 rows: the grouped positional convolution) takes the 16-row tiles
+    // (measured at one stream: 16 x 32, K split 8: 25 us against 37 us for the 32 x 32 tile the size rule picked)
+    const bool pad32 = p.M > 16 && (((p.M + 31) / 32 * 32 - p.M) * 4 >= p.M);
+    const int *order = (p.M > 16 && !pad32) ? order_big : order_small;
+    int cfg = 0, wg_ks = 1;
+    long long best_waves = -1;
+    bool found = false;
+    // phases of unequal length (fused ResBlock chains, kernel sizes 3/7/11) are all co-resident: finer tiles even out the
+    // per-SIMD load (measured on the decoder: 32x32 tiles 185 vs 200 us at C = 128, 127 vs 133 us at C = 64; folding the
+    // chains' average into one K-concatenated GEMM was also measured: no gain)
+    bool uneven = false;
+    for (const PhaseD &q : phv) uneven = uneven || q.nchunks != phv[0].nchunks;
+    long long want_waves = (uneven && p.M >= 64) ? 2048 : 1024;
+    if (const char *f = tune_env("RVC_WANT_WAVES")) { if (p.fold_n) want_waves = atoll(f); }      // tuning aid
+    for (int oi = 0; oi < 3 && !found; oi++) {
+        const int cf = order[oi];
+        for (int ks = 1; ks <= 16; ks = ks == 1 ? 4 : ks * 2) {
+            if (!fits(cf, ks)) break;
+            const long long w = tiles(cf) * ks;
+            if (w > best_waves) { best_waves = w; cfg = cf; wg_ks = ks; }
+            // streams folded into N: the workgroups must also spread evenly over the CUs (768 x 3072 at 8 streams: 336 workgroups of 32 x 64 tiles
+            // are one or two per CU, 52 TF/s; 672 of 32 x 32 tiles 68 TF/s).  Below four rounds a last round under 80 % full sends the choice on
+            // to the next smaller tile.  (One stream keeps its own, latency-tuned rule.)
+            if (p.fold_n && oi == 0 && !tune_env("RVC_NO_BALANCE")) {         // (one step down only: the 16 x 16 tile loses more than an uneven last round costs)
+                const long long wgs = ks > 1 ? tiles(cf) : (tiles(cf) + 3) / 4, rounds = (wgs + g_ncu - 1) / g_ncu;
+                if (rounds < 4 && wgs * 5 < rounds * g_ncu * 4) continue;
             }
-            hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
-            if (g32l) {
-                if (final_out && plp->cur_out) { IgemmP q = p; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch_igemm32l(lc, g32l_mode, q, grid, lds_l, s, ea, eb); }
-                else launch_igemm32l(lc, g32l_mode, p, grid, lds_l, s, ea, eb);
-                return;
-            }
-            if (final_out && plp->cur_out) { IgemmP q = p; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch_igemm_tiled(lc, pre, q, grid, lds, s, ea, eb); }
-            else launch_igemm_tiled(lc, pre, p, grid, lds, s, ea, eb);
-        });
-        return;
+            if (w >= want_waves) { cfg = cf; wg_ks = ks; found = true; break; }
+        }
     }
     // one stream, table-free layers of the ContentVec window (N = 111) that the size rule sends to lone 16 x 16 fragments: every B fragment costs
     // four dword gathers (9-12 clocks each on the CU's single vector-memory path) for ONE MFMA row block; two fragments along N per wave and eight
@@ -848,16 +778,14 @@ static void queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &
     if (const char *f = test_opt("RVC_FORCE_CFG")) {   // tuning aid: "cfg,ks[,mfast]"
         int fc = 0, fk = 1; if (sscanf(f, "%d,%d", &fc, &fk) >= 1) { cfg = fc; wg_ks = fk; }
     }
-    if (t_choice.kind == 4 && !(p.ln_wsum || p.ln_stats_in)) {
-        const int fc = t_choice.a, fk = t_choice.b;
-        const bool ok = fc >= 0 && fc <= 4 && (fk == 1 || ((fk == 4 || fk == 8 || fk == 16) && nchunks / fk >= 4 && fk * kMF[fc] * kNF[fc] <= 32)) &&
-                        (size_t)nchunks * 64 + (fk > 1 ? (size_t)fk * kMF[fc] * kNF[fc] * 1024 : 0) <= 60 * 1024;
-        if (ok) { cfg = fc; wg_ks = fk; }
+    if (c.ch.kind == 4 && !(p.ln_wsum || p.ln_stats_in)) {
+        const int fc = c.ch.a, fk = c.ch.b;
+        if (fc >= 0 && fc <= 4 && (fk == 1 || fk == 4 || fk == 8 || fk == 16) && fits(fc, fk)) { cfg = fc; wg_ks = fk; }
     }
     if (p.ln_wsum || p.ln_stats_in) {
         // folded LayerNorm: one stream or a few folded into N (statistics are per launch column), in-workgroup K split (the statistics / the
         // normalised residual live in that epilogue)
-        if (lds_cfg >= 0 || B != 1 || p.nphase != 1) throw std::logic_error("folded LayerNorm outside its supported launch shape");
+        if (B != 1 || p.nphase != 1) throw std::logic_error("folded LayerNorm outside its supported launch shape");
         if (wg_ks == 1) {
             wg_ks = 4;
             while (cfg > 0 && (nchunks / wg_ks < 4 || wg_ks * kMF[cfg] * kNF[cfg] > 32)) cfg = cfg == 4 ? 3 : (cfg == 3 ? 1 : 0);
@@ -865,7 +793,7 @@ static void queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &
         if (p.ln_wsum && (p.lin_cs4 == 0 || pre || nchunks / wg_ks < 1)) throw std::logic_error("LayerNorm consumer must be a table-free 1x1 layer");
     }
     int ksplit = 1;
-    if ((size_t)nchunks * 64 > 60 * 1024 && (p.glu || phase_epi)) throw ShapeError("fused conv too long for the in-workgroup K split");
+    if ((size_t)nchunks * 64 > 60 * 1024 && (p.glu || c.phase_epi)) throw ShapeError("fused conv too long for the in-workgroup K split");
     if ((size_t)nchunks * 64 > 60 * 1024) {     // koff slice would not fit in LDS: grid-level split (two-stage, rare)
         ksplit = (int)(((size_t)nchunks * 64 + 60 * 1024 - 1) / (60 * 1024));
         cfg = 0; wg_ks = 1;
@@ -875,7 +803,7 @@ static void queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &
     p.ksplit = ksplit; p.chunks_per_split = cps;
     p.ntm = (p.M + 16 * kMF[cfg] - 1) / (16 * kMF[cfg]);
     p.ntn = (p.N + 16 * kNF[cfg] - 1) / (16 * kNF[cfg]);
-    if (ksplit > 1) p.part = pl.arena.floats((size_t)B * p.nphase * ksplit * p.M * p.N);
+    if (ksplit > 1) p.part = c.pl.arena.floats((size_t)B * p.nphase * ksplit * p.M * p.N);
     // weight-heavy layers (short N: the transformer at T=111, RMVPE's deep levels, the synth encoder): keep all tiles that
     // read the same weight rows on one XCD so each weight byte crosses the fabric once (per-XCD L2s are private)
     bool weight_heavy = (p.N <= 512 && (long long)p.M * p.K >= 64 * 1024 && p.ntm >= 8) || (p.fold_n && p.ntm >= 2);
@@ -901,30 +829,74 @@ static void queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &
         lds2 = (lin ? 0 : (size_t)nchunks * 64) + (wg_ks > 1 ? (size_t)wg_ks * kMF[cfg] * kNF[cfg] * 1024 : 0) + (p.ln_wsum ? (size_t)wg_ks * kNF[cfg] * 16 * 2 * 4 : 0);
         if (p.ln_wsum && !lin) throw std::logic_error("LayerNorm consumer did not get the table-free kernel");
     }
-    g_last_wgs = (int)(grid.x * grid.y * grid.z); g_last_waves = wg_ks > 1 ? wg_ks : 4;
-    const double flops = 2.0 * p.M * (double)p.N * ksum * B;
-    pl.igemm_flops += flops;
-    pl.n_igemm++;
-    Plan *plp = &pl;
-    { char d[200]; snprintf(d, sizeof d, "reg M=%d N=%d K=%d B=%d nph=%d tile=%dx%d ks=%d mfast=%d grid=%ux%ux%u pre=%d lin=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, 16 * kMF[cfg], 16 * kNF[cfg], wg_ks, p.m_fast, grid.x, grid.y, grid.z, (int)pre, (int)lin, ksum); pl.descs.push_back(d); note_kernel(d); }
-    const int desc_id = (int)pl.descs.size() - 1;
-    if (final_out && lean) pl.final_out_honoured = true;      // (the two-stage grid split-K fallback writes through a second kernel: it keeps the plan's own tensor)
-    pl.ops.push_back([=](hipStream_t s) {
-        ProfEvent *pe = nullptr;
-        if (plp->profile) {
-            if (plp->prof_used == plp->prof.size()) {
-                ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); e.flops = 0; e.bytes = 0; plp->prof.push_back(e);
-            }
-            pe = &plp->prof[plp->prof_used++];
-            pe->flops = flops; pe->bytes = 0; pe->desc = desc_id;
-            if (ksplit > 1) HIPCHK(hipEventRecord(pe->a, s));
+    char d[200];
+    snprintf(d, sizeof d, "reg M=%d N=%d K=%d B=%d nph=%d tile=%dx%d ks=%d mfast=%d grid=%ux%ux%u pre=%d lin=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, 16 * kMF[cfg], 16 * kNF[cfg], wg_ks, p.m_fast, grid.x, grid.y, grid.z, (int)pre, (int)lin, c.ksum);
+    // (the two-stage grid split-K fallback writes through a second kernel and keeps the plan's own tensor: final_out on the lean path only; it records
+    //  the profile events around both of its launches)
+    queue_gemm_launch(c.pl, d, 2.0 * p.M * (double)p.N * c.ksum * B, (int)(grid.x * grid.y * grid.z), wg_ks > 1 ? wg_ks : 4, c.final_out && lean, p,
+                      [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) {
+                          if (lean) { launch_igemm2(cfg, wg_ks, pre, lin, q, grid, lds2, s, ea, eb); return; }
+                          if (ea && ksplit > 1) HIPCHK(hipEventRecord(ea, s));
+                          launch_igemm_v1(pre, q, grid, s);
+                          if (ksplit > 1) hipLaunchKernelGGL(splitk_epilogue_kernel, egrid, dim3(256), 0, s, q);
+                          if (eb && ksplit > 1) HIPCHK(hipEventRecord(eb, s));
+                      });
+    c.built = Choice{4, cfg, wg_ks};
+}
+
+// generic: the caller fills geometry (N, NW, strides, koff, phases); the kernel families below are tried in a fixed order and the first that takes the
+// layer queues it.  `ch` forces a family / tile (kind 0: the rules).  Returns what was queued, in the tuner's terms.
+static Choice queue_igemm_impl(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phases, bool final_out, const Choice &ch)
+{
+    p.probe = g_kprobe;
+    GemmCall c{pl, koff, final_out, ch, B};
+    std::vector<PhaseD> ph(phases);
+    for (PhaseD &q : ph) {
+        if (q.nchunks == 0) q.nchunks = p.K / 16;
+        c.ksum += q.nchunks * 16.0;
+        c.phase_epi = c.phase_epi || q.act_p1 != 0 || q.y_off != 0;
+    }
+    c.ln_fold = p.ln_wsum || p.ln_stats_in || c.phase_epi;
+    // phases of unequal length (the fused ResBlock chains: kernel sizes 3 / 7 / 11) are dispatched longest first: the grid's z axis
+    // is walked last, so the workgroups of phase 0 start first and the short phases fill the tail instead of the long one forming it
+    std::vector<PhaseD> lpt(ph);
+    std::stable_sort(lpt.begin(), lpt.end(), [](const PhaseD &a, const PhaseD &b) { return a.nchunks > b.nchunks; });
+    if (B > 1) {
+        // two to four streams, stride-1 1-D convolution: the staged-tile kernel with the streams in its work-item table (tried before the fold)
+        if (queue_conv_tile(c, p, B, lpt)) return c.built;
+        // five streams and more: the staged 32x32x2 convolution (streams as a grid dimension: also before the fold)
+        if (queue_conv32s(c, p, B, lpt)) return c.built;
+        // (round 6: the same structure for RMVPE's Conv2d 3x3 layers -- conv2d32s_kernel, the padded planes as flat 1-D rows -- was built, parity-green and
+        //  SLOWER than the register-direct kernel at 16 / 64 / 128 streams, 41-54 against 60-67 TF/s: the layers are 0.6-1.2 GFLOP with K = 288-576, a tile's
+        //  K loop is 18-36 chunks behind a 50 KB staging prologue.  Not in the tree; DESIGN.md section 7 round 6, profiles/r06_conv2d32s_*.txt)
+    }
+    if (B == 1 && test_opt_int("RVC_CONV32S", 1) == 2 && queue_conv32s(c, p, B, ph)) return c.built;        // test hook: the kernel forced onto one stream
+    // many streams: fold them into the N axis (one launch-wide column index instead of a grid dimension), so that tiles are cut from
+    // B * N columns -- the ContentVec window (N = 111), the text encoder (N = 21) or RMVPE's deep levels (N = 4..64) no longer pad
+    // every stream up to a tile.  All offsets stay below 2^31 bytes / elements for every geometry the plugin can ask for (checked).
+    if (B > 1 && !tune_env("RVC_NO_FOLD")) {
+        const long long lim = (1LL << 29);
+        if ((long long)B * p.x_bs < lim && (long long)B * p.y_bs < lim && (long long)B * (p.res ? p.res_bs : 0) < lim && (long long)B * p.N < (1LL << 30) &&
+            (size_t)(p.K / 16) * 64 <= 60 * 1024) {      // (the two-stage grid split-K fallback keeps the batch as a grid dimension)
+            p.fold_n = p.N; p.N = B * p.N; B = 1;
         }
-        if (lean && final_out && plp->cur_out) { IgemmP q = p; q.y = plp->cur_out; q.y_bs = plp->cur_out_bs; launch_igemm2(cfg, wg_ks, pre, lin, q, grid, lds2, s, pe ? pe->a : nullptr, pe ? pe->b : nullptr); }
-        else if (lean) launch_igemm2(cfg, wg_ks, pre, lin, p, grid, lds2, s, pe ? pe->a : nullptr, pe ? pe->b : nullptr);
-        else launch_igemm_v1(pre, p, grid, s);
-        if (ksplit > 1) hipLaunchKernelGGL(splitk_epilogue_kernel, egrid, dim3(256), 0, s, p);
-        if (pe && ksplit > 1) HIPCHK(hipEventRecord(pe->b, s));
-    });
+    }
+    // table entries become non-negative byte offsets; the kernel moves the base pointer back by koff_bias bytes
+    std::vector<int> kb(koff);
+    int kmin = 0;
+    for (int v : kb) kmin = std::min(kmin, v);
+    for (int &v : kb) v = (v - kmin) * 4;
+    p.koff_bias = -kmin * 4;
+    {
+        auto it = pl.koff_tabs.find(kb);
+        if (it == pl.koff_tabs.end()) it = pl.koff_tabs.emplace(kb, pl.arena.upload(kb)).first;
+        p.koff = it->second;
+    }
+    if (!tune_env("RVC_NO_LPT")) ph = lpt;
+    set_phases(pl, p, ph);
+    if (queue_conv_tile(c, p, B, ph) || queue_bf3(c, p, B, ph) || queue_g2w(c, p, B) || queue_tiled(c, p, B)) return c.built;
+    queue_reg(c, p, B, ph);
+    return c.built;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -952,14 +924,15 @@ hipStream_t tune_stream()
 }
 bool planner_hook_set()
 {
-    static const char *const names[] = {"RVC_FORCE_CFG", "RVC_CONV_TILE", "RVC_CONV_TILE_KS", "RVC_FORCE_G2W", "RVC_CONV32S", "RVC_CONV32S_TILE", "RVC_G32L", "RVC_G32L_TALL", "RVC_G32L_TAB", "RVC_CONV32S_BUF", "RVC_FORCE_CHOICE", "RVC_G32L_PANEL"};
-    for (const char *n : names) if (test_opt(n)) return true;
+    for (const TestHook &h : kTestHooks) if (h.planner && test_opt(h.name)) return true;
     return false;
 }
 }
 
-// one candidate in a scratch plan: -> microseconds per launch (best of `reps`), < 0 if it cannot be built; *desc = the kernel it really became
-static double tune_trial(const Plan &pl, const IgemmP &p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phases, const Choice &c, int reps, std::string *desc)
+// one candidate in a scratch plan: -> microseconds per launch (best of `reps`), < 0 if it cannot be built; *desc = the kernel it really became, *built = the
+// same in the tuner's terms
+static double tune_trial(const Plan &pl, const IgemmP &p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phases, const Choice &c, int reps, std::string *desc,
+                         Choice *built = nullptr)
 {
     // one scratch plan per thread, rewound between trials (its arena holds a layer's tables only)
     // (a plain pointer, never freed at thread / process exit: a destructor that calls hipFree behind the runtime's own teardown crashed the process
@@ -972,13 +945,12 @@ static double tune_trial(const Plan &pl, const IgemmP &p, int B, const std::vect
     HIPCHK(hipStreamSynchronize(tune_stream()));          // (the previous trial's launches still read the tables that are about to be overwritten)
     tp.ops = OpList(); tp.descs.clear(); tp.koff_tabs.clear(); tp.arena.rewind();
     tp.B = pl.B; tp.bf3 = pl.bf3; tp.autotune = false; tp.profile = false; tp.igemm_flops = 0; tp.n_igemm = 0;
-    const Choice saved = t_choice;
-    t_choice = c;
-    try { queue_igemm_impl(tp, p, B, koff, phases, false); }
-    catch (...) { t_choice = saved; return -1.0; }
-    t_choice = saved;
+    Choice b;
+    try { b = queue_igemm_impl(tp, p, B, koff, phases, false, c); }
+    catch (...) { return -1.0; }
     if (tp.ops.v.empty() || tp.descs.empty()) return -1.0;
     *desc = tp.descs.back();
+    if (built) *built = b;
     hipStream_t st = tune_stream();
     static thread_local hipEvent_t ea = nullptr, eb = nullptr;
     if (!ea) { HIPCHK(hipEventCreate(&ea)); HIPCHK(hipEventCreate(&eb)); }
@@ -1005,13 +977,10 @@ void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const 
 {
     if (const char *f = test_opt("RVC_FORCE_CHOICE")) {          // test hook "kind,a,b": every layer built under ONE of the choices the tuner can make (tests/test_gpu_tiles.py)
         Choice c; if (sscanf(f, "%d,%d,%d", &c.kind, &c.a, &c.b) < 1) c = Choice();
-        const Choice saved = t_choice;
-        t_choice = c;
-        try { queue_igemm_impl(pl, p, B, koff, phases, final_out); } catch (...) { t_choice = saved; throw; }
-        t_choice = saved;
+        queue_igemm_impl(pl, p, B, koff, phases, final_out, c);
         return;
     }
-    if (!pl.autotune || B <= 4 || pl.bf3 || p.bf3 || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || planner_hook_set() || t_choice.kind != 0) return queue_igemm_impl(pl, p, B, koff, phases, final_out);
+    if (!pl.autotune || B <= 4 || pl.bf3 || p.bf3 || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || planner_hook_set()) { queue_igemm_impl(pl, p, B, koff, phases, final_out, Choice()); return; }
     // layer signature: everything the kernels' speed depends on (shape, strides, taps, epilogue class), not the tensors
     std::string key;
     {
@@ -1030,10 +999,7 @@ void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const 
         std::lock_guard<std::mutex> lk(g_tune_mu);
         auto it = g_tune.find(key);
         if (it != g_tune.end()) {
-            const Choice c = it->second.c;
-            t_choice = c;
-            try { queue_igemm_impl(pl, p, B, koff, phases, final_out); } catch (...) { t_choice = Choice(); throw; }
-            t_choice = Choice();
+            queue_igemm_impl(pl, p, B, koff, phases, final_out, it->second.c);
             pl.tune_hits++;
             return;
         }
@@ -1041,46 +1007,39 @@ void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const 
     const auto t0 = std::chrono::steady_clock::now();
     // the rule-based build first: its family decides which neighbours are worth a trial
     std::string d0;
-    const double us0 = tune_trial(pl, p, B, koff, phases, Choice(), 2, &d0);
-    if (us0 < 0) return queue_igemm_impl(pl, p, B, koff, phases, final_out);
-    const std::string fam = d0.substr(0, d0.find(' '));
+    Choice b0;
+    const double us0 = tune_trial(pl, p, B, koff, phases, Choice(), 2, &d0, &b0);
+    if (us0 < 0) { queue_igemm_impl(pl, p, B, koff, phases, final_out, Choice()); return; }
     std::vector<Choice> cands;
-    auto add = [&](int kind, int a, int b) { Choice c; c.kind = kind; c.a = a; c.b = b; for (const Choice &o : cands) if (o == c) return; cands.push_back(c); };
+    auto add = [&](int kind, int a, int b) { Choice c{kind, a, b}; for (const Choice &o : cands) if (o == c) return; cands.push_back(c); };
     const bool one_d = p.x_ld > 0 && p.x_hs == 0 && p.x_ws == 1 && p.y_hm == 0 && p.y_ws == 1 && !p.glu;      // conv32s_kernel's domain (it checks the rest itself)
     const bool lin = p.lin_cs4 != 0 && phases.size() == 1 && p.pre_act == ACT_NONE && !p.glu;
     const int t32 = p.M <= 32 ? 0 : (p.M <= 64 ? 1 : 2);                                              // conv32s tile by panel height
     const int lc_m = p.M >= 96 ? 7 : (p.M >= 48 ? 8 : 5);                                             // a 32x32x2 workgroup tile by panel height
-    int nchunks = p.K / 16;
-    auto g2w_ks = [&](int &ks) {          // g2w_rule's K split on the folded column count (the rule itself sees the layer after the fold)
-        const long long tiles = (long long)((p.M + 31) / 32) * (((long long)B * p.N + 31) / 32), want = (4800 + tiles / 2) / std::max<long long>(tiles, 1);
-        ks = want <= 1 ? 1 : (want == 2 ? 2 : (want == 3 ? 3 : (want <= 4 ? 4 : 8)));
-        while (ks > 1 && nchunks / ks < 4) ks = ks == 8 ? 4 : ks - 1;
-    };
-    if (fam == "c32s") {
+    const int nchunks = p.K / 16;
+    const int g2w_ks = g2w_ksplit(p.M, (long long)B * p.N, nchunks);          // g2w_rule's K split on the folded column count
+    if (b0.kind == 1) {
         add(1, t32 == 2 ? 1 : t32 + 1, 0); if (t32 > 0) add(1, t32 - 1, 0);
         if (t32 == 1) { add(1, 1 | 4, 0); add(1, 1, 0); }            // both load variants of the 64 x 128 tile
         add(3, lc_m, 0);
-    } else if (fam == "g2w") {
-        int ks; g2w_ks(ks);
+    } else if (b0.kind == 2) {
+        const int ks = b0.b;
         add(2, 0, ks == 1 ? 2 : ks / 2); if (ks < 8) add(2, 0, ks == 3 ? 4 : ks * 2);
         add(3, p.M >= 96 ? 8 : lc_m, 0); add(4, 3, 4);
-    } else if (fam == "g32l" || fam == "g32t" || fam == "g32" || fam == "lds") {
+    } else if (b0.kind == 3) {
         // the neighbouring workgroup tiles, the staged convolution / the register-direct 32x32x2 kernel where the layer is in their domain, the register-direct 16x16x4 kernel
         if (p.M >= 96) { add(3, 7, 0); add(3, 3, 0); add(3, 8, 0); } else if (p.M >= 48) { add(3, 4, 0); add(3, 8, 0); add(3, 5, 0); } else add(3, 5, 0);
         if (one_d && !lin) add(1, t32, 0);
-        if (lin && p.M >= 256) { int ks; g2w_ks(ks); add(2, 0, ks); }
+        if (lin && p.M >= 256) add(2, 0, g2w_ks);
         add(4, p.M > 16 ? 3 : 1, nchunks >= 16 ? 4 : 1);
-    } else if (fam == "reg") {
+    } else if (b0.kind == 4) {
         if (one_d && !lin) add(1, t32, 0);
-        if (lin && p.M >= 256) { int ks; g2w_ks(ks); add(2, 0, ks); }
+        if (lin && p.M >= 256) add(2, 0, g2w_ks);
         if (p.M > 16) add(3, lc_m, 0);
         // the other K split of the same tile (the rule wants >= 1024 waves; with streams folded into N a wave count between the steps goes either way)
-        {
-            int ks = 1; const char *q = strstr(d0.c_str(), " ks="); if (q) ks = atoi(q + 4);
-            int cf = 0; const char *t = strstr(d0.c_str(), " tile="); int bm = 16, bn = 16; if (t && sscanf(t + 6, "%dx%d", &bm, &bn) == 2) { for (int c = 0; c < 5; c++) if (16 * kMF[c] == bm && 16 * kNF[c] == bn) cf = c; }
-            add(4, cf, ks == 1 ? 4 : (ks == 4 ? 8 : 4));
-            if (cf == 4 || cf == 3) add(4, cf == 4 ? 3 : 0, ks);
-        }
+        const int cf = b0.a, ks = b0.b;
+        add(4, cf, ks == 1 ? 4 : (ks == 4 ? 8 : 4));
+        if (cf == 4 || cf == 3) add(4, cf == 4 ? 3 : 0, ks);
     }
     struct Res { Choice c; std::string d; double us; };
     std::vector<Res> res;
@@ -1108,9 +1067,7 @@ void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const 
     pl.tune_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     pl.tuned_layers++;
     if (bi != 0) pl.tune_changed++;
-    t_choice = res[bi].c;
-    try { queue_igemm_impl(pl, p, B, koff, phases, final_out); } catch (...) { t_choice = Choice(); throw; }
-    t_choice = Choice();
+    queue_igemm_impl(pl, p, B, koff, phases, final_out, res[bi].c);
 }
 
 // the autotuner's decisions of this process, one line each: "<key> -> <kernel description> <us> (<candidates>)"; returns the number of entries (test / tool aid)

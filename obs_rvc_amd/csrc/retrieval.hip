@@ -57,11 +57,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
                 Plan *plp = &pl;
                 const double scan_bytes = (double)e->index_n * C * sizeof(float) * B;     // algorithmic bytes: the index, read once per query group
                 pl.ops.push_back([=](hipStream_t s) {
-                    ProfEvent *pe = nullptr;
-                    if (plp->profile) {
-                        if (plp->prof_used == plp->prof.size()) { ProfEvent ev; HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b)); ev.flops = 0; ev.bytes = 0; plp->prof.push_back(ev); }
-                        pe = &plp->prof[plp->prof_used++]; pe->flops = 0; pe->bytes = scan_bytes;
-                    }
+                    const ProfEvent *pe = plp->prof_slot(0, scan_bytes, -1);
                     if (g_knn_test_lose.load(std::memory_order_relaxed)) {       // test hook (rvc_debug_option RVC_KNN_LOSE_TICKET): a hand-off that cannot complete
                         KnnFusedP f2 = fp; f2.test_lose = 1; f2.spin_limit = 1u << 12;
                         hipLaunchKernelGGL(knn_scan_select_kernel, grid, dim3(256), lds, s, f2);
