@@ -27,13 +27,37 @@ int rvc_debug_profile_dump(rvc_engine *e, char *buf, size_t cap);
 double rvc_debug_conv_check(rvc_engine *e, int M, int Cin, int KW, int dil, int N, int streams, int pre_act);
 double rvc_debug_conv2d_check(rvc_engine *e, int M, int Cin, int H, int W, int streams, int kind, int residual);
 double rvc_debug_ln_fold_check(rvc_engine *e, int M, int K, int N, float offset);
+/* one convolution layer built with the planner calls and options the models use (prep_conv / prep_convT1d, merge_convs, add_conv1d /
+ * add_convT1d / add_conv1d_multi / add_conv1d_two / add_conv2d), run once through whatever kernel the planner (or a hook) picks.
+ * Weights and biases come in PyTorch layout (form: layout of w; bias):
+ *   0 conv1d        [cout][cin / groups][kw]; [cout]      (glu: cout = 2H rows in model order, tanh half first; the output has H channels)
+ *   1 convT1d       [cin][cout][kw]; [cout]               (stride = the upsampling factor, pad = (kw - stride) / 2)
+ *   2 conv1d_multi  n blocks [cout][cin][kws[j]]; [n][cout] (phase j = conv j, y has n * cout rows)
+ *   3 conv1d_two    two blocks [cout][cin]; [2][cout] (the pair bias); y has 3 cout + 16 rows, the first output at row 16, the second at row 16 + 2 cout
+ *   4 conv2d 3x3    [cout][cin][3][3]; [cout]             (t_in = H, t_out = W; y_ws: the image written transposed into a [cout * W][H] 1-D tensor)
+ * bias may be NULL (no bias).  x / y / r are the WHOLE allocations of the input, output and residual tensors (guard zones, halos, ld padding,
+ * every stream): uploaded before the launch, downloaded after it.  geo[3][8] receives, for x, y, r: allocation size (floats), offset of element
+ * (0, 0, 0) from the allocation's start, C, T (2-D: W), ld (row stride), bs (stream stride), cs (channel stride), H (1-D: 1).  With x == NULL only
+ * geo is filled.  0 = done, else an rvc_status (rvc_last_error_message). */
+typedef struct rvc_debug_layer_spec {
+    int form, streams;
+    int cin, cout, kw, stride, pad, dil, groups;
+    int t_in, t_out, x_halo, y_halo, r_halo;
+    int act; float slope; float scale; int accumulate;
+    int pre_act; float pre_slope;
+    int no_bias, final_out, glu;
+    int res;                         /* 0 none; 1 a tensor of its own (multi: n * cout rows if res_grouped); 2 one row shared by every channel and stream (res_cs = res_bs = 0); 3 the output tensor; 4 the input tensor (1-D) */
+    int n, kws[4], dils[4], pads[4];
+    int x_grouped, res_grouped, y_ws;
+} rvc_debug_layer_spec;
+int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w, const float *bias, float *x, float *y, float *r, long long *geo);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);
 void rvc_debug_autotune_reset(void);
 /* weight slabs alive on a device: count and bytes (obs_rvc_amd/csrc/plan.hip, wmalloc) */
 int rvc_debug_weight_slabs(int device, int *count, size_t *bytes);
-/* the kernel the planner chose for the last rvc_debug_conv*_check launch ("reg", "g32", "c32s", ...) */
+/* the kernel the planner chose for the last rvc_debug_conv*_check / rvc_debug_layer launch ("reg", "g32", "c32s", ...) */
 const char *rvc_debug_last_kernel(void);
 
 #ifdef __cplusplus

@@ -5,6 +5,7 @@
 // All compute is launched as hand-written gfx950 kernels (kernels.hip.h); nothing here falls
 // back to a CPU path: without a HIP device every entry point returns RVC_BACKEND.
 #include "engine_int.h"
+#include "../../include/rvc_mi355x_debug.h"
 #include <chrono>
 
 // The HIP runtime multiplexes all streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The engine runs four
@@ -1319,6 +1320,96 @@ double rvc_debug_conv2d_check(rvc_engine *e, int M, int Cin, int H, int W, int s
         return RVC_OK;
     });
     return worst;
+}
+
+// test aid: one convolution layer as the models build it (include/rvc_mi355x_debug.h, tests/test_gpu_layers.py).  The caller owns every float of the
+// tensors' allocations: what the layer must not touch is compared bit for bit afterwards.
+int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w, const float *bias, float *x, float *y, float *r, long long *geo)
+{
+    return (int)guarded(e, [&]() {
+        if (!s || !geo || s->streams < 1 || s->form < 0 || s->form > 4 || ((s->form == 2 || s->form == 3) && (s->n < 1 || s->n > 4))) throw ShapeError("layer spec");
+        const int B = s->streams, form = s->form, n = form == 3 ? 2 : s->n;
+        Plan pl; pl.B = B;
+        struct Geo { float *base = nullptr; long long g[8] = {0, 0, 0, 0, 0, 0, 0, 1}; };
+        auto g1 = [](const T1 &t) { Geo q; const size_t gd = t1_guard(t.ld); q.base = t.p - gd - t.halo; q.g[0] = (long long)t.B * t.bs + 2 * (long long)gd; q.g[1] = (long long)gd + t.halo; q.g[2] = t.C; q.g[3] = t.T; q.g[4] = t.ld; q.g[5] = t.bs; q.g[6] = t.ld; return q; };
+        auto g2 = [](const T2 &t) { Geo q; const size_t gd = t2_guard(t.ld); q.base = t.p - gd - t.ld - 1; q.g[0] = (long long)t.B * t.bs + 2 * (long long)gd; q.g[1] = (long long)gd + t.ld + 1; q.g[2] = t.C; q.g[3] = t.W; q.g[4] = t.ld; q.g[5] = t.bs; q.g[6] = t.cs; q.g[7] = t.H; return q; };
+        Geo gx, gy, gr;
+        T1 x1, y1, r1; T2 x2, y2, r2;
+        const int yrows = form == 2 ? n * s->cout : (form == 3 ? 3 * s->cout + 16 : (s->glu ? s->cout / 2 : s->cout));
+        if (form == 4) {
+            x2 = make_t2(pl.arena, B, s->cin, s->t_in, s->t_out); gx = g2(x2);
+            if (s->y_ws) {
+                y1 = make_t1(pl.arena, B, s->cout * s->t_out, s->t_in, 0); gy = g1(y1);
+                y2.p = y1.p; y2.B = B; y2.C = s->cout; y2.H = s->t_in; y2.W = s->t_out; y2.cs = s->t_out * y1.ld; y2.ld = 1; y2.bs = y1.bs;
+            } else { y2 = make_t2(pl.arena, B, s->cout, s->t_in, s->t_out); gy = g2(y2); }
+            if (s->res == 1) { r2 = make_t2(pl.arena, B, s->cout, s->t_in, s->t_out); gr = g2(r2); }
+        } else {
+            x1 = make_t1(pl.arena, B, (form == 2 && s->x_grouped) ? n * s->cin : s->cin, s->t_in, s->x_halo); gx = g1(x1);
+            y1 = make_t1(pl.arena, B, yrows, s->t_out, s->y_halo); gy = g1(y1);
+            if (s->res == 1) { r1 = make_t1(pl.arena, B, (form == 2 && s->res_grouped) ? n * s->cout : s->cout, s->t_out, s->r_halo); gr = g1(r1); }
+        }
+        if (s->res == 2) { r1 = make_t1(pl.arena, 1, 1, s->t_out, 0); gr = g1(r1); }
+        for (int i = 0; i < 8; i++) { geo[i] = gx.g[i]; geo[8 + i] = gy.g[i]; geo[16 + i] = gr.g[i]; }
+        if (!x) return RVC_OK;
+        if (!y || !w || ((s->res == 1 || s->res == 2) && !r)) throw ShapeError("layer buffers");
+        HIPCHK(hipMemcpy(gx.base, x, (size_t)gx.g[0] * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(gy.base, y, (size_t)gy.g[0] * 4, hipMemcpyHostToDevice));
+        if (gr.base) HIPCHK(hipMemcpy(gr.base, r, (size_t)gr.g[0] * 4, hipMemcpyHostToDevice));
+        ConvOpts o;
+        o.act = s->act; o.slope = s->slope; o.scale = s->scale; o.accumulate = s->accumulate != 0;
+        o.pre_act = s->pre_act; o.pre_slope = s->pre_slope; o.no_bias = s->no_bias != 0; o.final_out = s->final_out != 0; o.glu = s->glu != 0;
+        if (s->res == 1 && form == 4) { o.res = r2.p; o.res_cs = r2.cs; o.res_bs = r2.bs; o.res_rs = r2.ld; }
+        else if (s->res == 1) { o.res = r1.p; o.res_cs = r1.ld; o.res_bs = r1.bs; }
+        else if (s->res == 2) { o.res = r1.p; o.res_cs = 0; o.res_bs = 0; }
+        else if (s->res == 3 && form == 4) { o.res = y2.p; o.res_cs = y2.cs; o.res_bs = y2.bs; o.res_rs = y2.ld; }
+        else if (s->res == 3) { o.res = y1.p; o.res_cs = y1.ld; o.res_bs = y1.bs; }
+        else if (s->res == 4 && form != 4) { o.res = x1.p; o.res_cs = x1.ld; o.res_bs = x1.bs; }
+        if (s->y_ws) o.y_ws = y1.ld;
+        std::vector<ConvW> cws;
+        float *pair = nullptr;
+        if (form == 0 && s->glu) {
+            std::vector<float> wp, bp;
+            if (!bias) throw ShapeError("GLU layer without bias");
+            glu_pack_rows(w, bias, s->cout / 2, (size_t)s->cin * s->kw, wp, bp);
+            cws.push_back(prep_conv(wp.data(), bp.data(), s->cout, s->cin, s->kw, 1));
+        } else if (form == 0) cws.push_back(prep_conv(w, bias, s->cout, s->cin, s->kw, s->groups));
+        else if (form == 1) cws.push_back(prep_convT1d(w, bias, s->cin, s->cout, s->kw, s->stride));
+        else if (form == 4) cws.push_back(prep_conv(w, bias, s->cout, s->cin, 9, 1));
+        else {
+            size_t ow = 0;
+            for (int j = 0; j < n; j++) {
+                const int kw = form == 3 ? 1 : s->kws[j];
+                cws.push_back(prep_conv(w + ow, bias ? bias + (size_t)j * s->cout : nullptr, s->cout, s->cin, kw, 1));
+                ow += (size_t)s->cout * s->cin * kw;
+            }
+            if (form == 2 && n > 1) { std::vector<ConvW *> m; for (ConvW &c : cws) m.push_back(&c); merge_convs(m); }
+            if (form == 3) { if (!bias) throw ShapeError("pair launch without bias"); pair = upload_f(bias, (size_t)2 * s->cout); }
+        }
+        try {
+            if (form == 0) add_conv1d(pl, cws[0], x1, y1, s->stride, s->pad, s->dil, o);
+            else if (form == 1) add_convT1d(pl, cws[0], x1, y1, s->pad, o);
+            else if (form == 2) {
+                std::vector<const ConvW *> cp; std::vector<int> pads, dils;
+                for (int j = 0; j < n; j++) { cp.push_back(&cws[j]); pads.push_back(s->pads[j]); dils.push_back(s->dils[j]); }
+                add_conv1d_multi(pl, cp, x1, s->x_grouped != 0, y1, pads, dils, o, s->res_grouped != 0);
+            } else if (form == 3) add_conv1d_two(pl, cws[0], cws[1], pair, x1, y1.rows(16, s->cout), y1.rows(16 + 2 * s->cout, s->cout));
+            else add_conv2d(pl, cws[0], x2, y2, o);
+            HIPCHK(hipDeviceSynchronize());
+            for (auto &op : pl.ops.v) op(e->stream);
+            HIPCHK(hipStreamSynchronize(e->stream));
+            HIPCHK(hipGetLastError());
+        } catch (...) {
+            for (ConvW &c : cws) free_conv(c);
+            if (pair) wfree(pair);
+            throw;
+        }
+        for (ConvW &c : cws) free_conv(c);
+        if (pair) wfree(pair);
+        HIPCHK(hipMemcpy(x, gx.base, (size_t)gx.g[0] * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(y, gy.base, (size_t)gy.g[0] * 4, hipMemcpyDeviceToHost));
+        if (gr.base) HIPCHK(hipMemcpy(r, gr.base, (size_t)gr.g[0] * 4, hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
 }
 
 // the kernel family of the most recently queued implicit-GEMM launch (the first word of its description): tests assert which path they exercised

@@ -122,6 +122,8 @@ struct T2 {
     T2 chans(int c0, int n) const { T2 r = *this; r.p = p + (long long)c0 * cs; r.C = n; return r; }
 };
 
+static inline size_t t1_guard(int ld) { return (size_t)ld + 64; }
+static inline size_t t2_guard(int ld) { return (size_t)ld * 2 + 64; }
 static inline T1 make_t1(Arena &a, int B, int C, int T, int halo)
 {
     T1 t;
@@ -129,7 +131,7 @@ static inline T1 make_t1(Arena &a, int B, int C, int T, int halo)
     t.ld = (T + 2 * halo + 3) / 4 * 4;
     t.bs = (long long)C * t.ld;
     // guard rows in front and behind so clamped/garbage tail reads stay inside the allocation
-    size_t guard = (size_t)t.ld + 64;
+    const size_t guard = t1_guard(t.ld);
     float *base = a.floats((size_t)B * t.bs + 2 * guard);
     t.p = base + guard + halo;
     return t;
@@ -141,7 +143,7 @@ static inline T2 make_t2(Arena &a, int B, int C, int H, int W)
     t.ld = W + 2;
     t.cs = (H + 2) * t.ld;
     t.bs = (long long)C * t.cs;
-    size_t guard = (size_t)t.ld * 2 + 64;
+    const size_t guard = t2_guard(t.ld);
     float *base = a.floats((size_t)B * t.bs + 2 * guard);
     t.p = base + guard + t.ld + 1;
     return t;
@@ -524,6 +526,20 @@ struct ModelRM {
     }
 };
 
+// GLU row packing of a WaveNet in-layer (kernels.hip.h glu_store): packed row f*16 + kq*4 + r <- model row f*8 + kq*2 + (r&1) of the tanh half (r < 2)
+// or the sigmoid half (r >= 2, + H).  w: [2H][K] in model row order, bias: [2H]
+template <typename T> static inline void glu_pack_rows(const T *w, const float *bias, int H, size_t K, std::vector<float> &wp, std::vector<float> &bp)
+{
+    if (H % 8 != 0) throw std::runtime_error("GLU-gated layer: channel count must be a multiple of 8");
+    wp.resize((size_t)2 * H * K); bp.resize((size_t)2 * H);
+    for (int r = 0; r < 2 * H; r++) {
+        const int f = r >> 4, kq = (r & 15) >> 2, rr = r & 3;
+        const int src = f * 8 + kq * 2 + (rr & 1) + (rr >= 2 ? H : 0);
+        for (size_t q = 0; q < K; q++) wp[(size_t)r * K + q] = (float)w[(size_t)src * K + q];
+        bp[r] = bias[src];
+    }
+}
+
 struct ModelSY {
     int phone_dim, hidden, inter, filter, heads, enc_layers, enc_k, window, flow_n, wn_layers, wn_k, gin, up_init, n_ups, n_rb, n_rbd, sr;
     int up_rate[8], up_kernel[8], rb_k[8], rb_d[8];
@@ -619,17 +635,10 @@ struct ModelSY {
                     bias[r] = ib[r] + a;
                 }
                 {
-                    // GLU row packing (kernels.hip.h glu_store): packed row f*16 + kq*4 + r <- channel f*8 + kq*2 + (r&1), sigmoid half for r >= 2
-                    if (H % 8 != 0) throw std::runtime_error("synth hidden size must be a multiple of 8");
                     const float *iw = b.w(fmt("sy.flow%d.in%d.w", i, j));
                     const size_t Kin = (size_t)H * wn_k;
-                    std::vector<float> w((size_t)2 * H * Kin), pb((size_t)2 * H);
-                    for (int r = 0; r < 2 * H; r++) {
-                        const int f = r >> 4, kq = (r & 15) >> 2, rr = r & 3;
-                        const int src = f * 8 + kq * 2 + (rr & 1) + (rr >= 2 ? H : 0);
-                        memcpy(&w[(size_t)r * Kin], iw + (size_t)src * Kin, Kin * sizeof(float));
-                        pb[r] = bias[src];
-                    }
+                    std::vector<float> w, pb;
+                    glu_pack_rows(iw, bias.data(), H, Kin, w, pb);
                     F.in.push_back(prep_conv(w.data(), pb.data(), 2 * H, H, wn_k, 1));
                     F.h_in_w.emplace_back(iw, iw + (size_t)2 * H * Kin); F.h_in_b.push_back(bias);
                 }
@@ -736,13 +745,8 @@ struct ModelSY {
                             w[((size_t)o * Cin) * K5 + t] += one;
                         }
                 }
-                std::vector<float> wp((size_t)2 * H * Cin * K5), pb((size_t)2 * H);
-                for (int r = 0; r < 2 * H; r++) {                      // GLU row packing, as for the plain in-layers
-                    const int f = r >> 4, kq = (r & 15) >> 2, rr = r & 3;
-                    const int src = f * 8 + kq * 2 + (rr & 1) + (rr >= 2 ? H : 0);
-                    for (size_t q = 0; q < (size_t)Cin * K5; q++) wp[(size_t)r * Cin * K5 + q] = (float)w[(size_t)src * Cin * K5 + q];
-                    pb[r] = F.h_in_b[j][src];
-                }
+                std::vector<float> wp, pb;
+                glu_pack_rows(w.data(), F.h_in_b[j].data(), H, (size_t)Cin * K5, wp, pb);      // as for the plain in-layers
                 WJ[fi][j] = std::move(wp); BJ[fi][j] = std::move(pb);
             }
         };
