@@ -61,6 +61,11 @@ extern "C" {
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 
+    // ---- formant shift (the plugin's resonance shift), semitones in [-5, 5]
+    pub fn rvc_set_formant_shift(e: *mut RvcEngine, semitones: f64) -> c_int;
+    pub fn rvc_set_formant_shift_stream(e: *mut RvcEngine, stream: c_int, semitones: f64) -> c_int;
+    pub fn rvc_formant_geometry(return_length: usize, sample_rate: usize, semitones: f64, out: *mut usize) -> c_int;
+
     // ---- multi-GPU: the one collective (index broadcast at load, RCCL over xGMI)
     pub fn rvc_rccl_unique_id(id128: *mut c_void) -> c_int;
     pub fn rvc_index_broadcast(e: *mut RvcEngine, unique_id128: *const c_void, rank: c_int, world: c_int,

@@ -171,6 +171,12 @@ impl RvcInfer {
     pub fn set_noise_seed(&mut self, seed: u32, stream_id: u32) {
         unsafe { ffi::rvc_set_noise_seed(self.handle, seed, stream_id) }
     }
+
+    /// the plugin's resonance shift (obs-rvc/src/lib.rs:446-451: `state.resonance_shift`), semitones in [-5, 5], every stream
+    pub fn set_formant_shift(&mut self, semitones: f64) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_formant_shift(self.handle, semitones) };
+        self.check(rc)
+    }
 }
 
 impl Drop for RvcInfer {

@@ -91,6 +91,19 @@ long long rvc_retrieval_recoveries(rvc_engine *e);
 void rvc_set_noise_seed(rvc_engine *e, uint32_t seed, uint32_t stream_id);
 void rvc_reset_state(rvc_engine *e);     /* zero the 1024-entry pitch cache and the chunk counter */
 
+/* ---- formant shift: the plugin's resonance shift (obs-rvc/src/lib.rs:80,103,176,369-375,446-451), semitones in [-5, 5] ---- */
+/* Moves the formants (the timbre) and keeps the pitch: with f = 2^(phi / 12), the latent and the harmonic source are stretched to
+ * R2 = ceil(R f) frames (the source's f0 scaled by R2 / R), the decoder runs on them, and its output is resampled from upp_res =
+ * floor(f sr / 100) to sr / 100 samples per frame; the f0 the pitch cache keeps is multiplied by (float)2^(-phi / 12).  The output
+ * is always R sr / 100 samples; phi = 0 is the plain path (same plan, same output).  Per stream, like pitch_shift: rvc_set_formant_shift
+ * sets every stream and the default of streams rvc_set_streams adds later (existing streams keep theirs); rvc_reset_state leaves the
+ * values alone.  Out of range or NaN: RVC_SHAPE.  Streams whose values give different R2 run one bucket per R2 (synchronously; not with
+ * graph replay or chunk pipelining: RVC_SHAPE).  DESIGN.md "Formant shift" has the definition. */
+rvc_status rvc_set_formant_shift(rvc_engine *e, double semitones);
+rvc_status rvc_set_formant_shift_stream(rvc_engine *e, int stream, double semitones);
+/* host only, pure: out = {R2, upp_res} of a return_length, a model sample rate (a multiple of 100) and a shift */
+rvc_status rvc_formant_geometry(size_t return_length, size_t sample_rate, double semitones, size_t out[2]);
+
 /* ---- multi-GPU (BASELINE configs[4]; no counterpart in the reference: one RvcInfer per process, rvc.rs:133-134) ---- */
 /* Streams shard across GPUs with NO per-chunk collective: one process + one engine per GPU, stream s on rank s mod world.  The one
  * exchange step is at load: the shared retrieval index travels from rank 0 into every rank's HBM with ONE ncclBroadcast over
@@ -191,7 +204,8 @@ rvc_status rvc_resampler_process_device(rvc_resampler *r, const void *d_in, void
  * resamplers, RvcInfer::infer, RMS envelope mixing and SOLA.  One H2D copy (the new chunk), one D2H copy (the finished frame) and
  * one synchronisation per chunk.  Lengths in seconds as in the plugin's settings; skip_inference != 0 = pass-through mode
  * (lib.rs:224-227).  The session covers every stream of the engine (rvc_set_streams before rvc_session_create): process then takes
- * input [streams][n] and writes output [streams][cap], sola_offset [streams].  Destroy the session before the engine. */
+ * input [streams][n] and writes output [streams][cap], sola_offset [streams].  Destroy the session before the engine.  The session has no
+ * formant setting of its own: it honours the engine's per-stream values (rvc_set_formant_shift[_stream]). */
 typedef struct rvc_session rvc_session;
 rvc_status rvc_session_create(rvc_engine *e, size_t sample_rate, double sample_length, double crossfade_length, double extra_inference_time,
                               size_t model_output_sample_rate, int32_t pitch_shift, double rms_mix_rate, int skip_inference, rvc_session **out);

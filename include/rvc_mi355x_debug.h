@@ -59,6 +59,9 @@ void rvc_debug_autotune_reset(void);
 int rvc_debug_weight_slabs(int device, int *count, size_t *bytes);
 /* the kernel the planner chose for the last rvc_debug_conv*_check / rvc_debug_layer launch ("reg", "g32", "c32s", ...) */
 const char *rvc_debug_last_kernel(void);
+/* host only: the formant resampler's full filter table h[n][K] (o -> n, K = 2 w + o; obs_rvc_amd/csrc/formant.hip.h) as fp32.  *width = K;
+ * returns 0, 1 when cap < n K (nothing written to out), -1 for bad arguments */
+int rvc_debug_formant_table(size_t o, size_t n, float *out, size_t cap, size_t *width);
 
 #ifdef __cplusplus
 }

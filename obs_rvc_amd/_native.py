@@ -26,18 +26,19 @@ SYMBOLS = [
     "rvc_set_plan_cache", "rvc_plan_cache_info", "rvc_set_plan_autotune", "rvc_plan_autotune_info", "rvc_retrieval_recoveries", "rvc_set_gemm_precision",
     "rvc_calibrate", "rvc_clock_monitor_start", "rvc_clock_monitor_stop",
     "rvc_session_create", "rvc_session_destroy", "rvc_session_process", "rvc_session_frame_size", "rvc_session_set_params", "rvc_session_set_params_stream", "rvc_session_geometry",
+    "rvc_set_formant_shift", "rvc_set_formant_shift_stream", "rvc_formant_geometry",
 ]
 
 
 SOURCES = ("engine.hip", "engine_int.h", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_synth.hip", "retrieval.hip", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "igemm2_inst.hip", "igemm_tiled_inst.hip", "igemm2w_inst.hip", "igemm_bf3_inst.hip", "conv_tile.hip.h", "conv_tile_inst.hip", "conv32s.hip.h", "conv32s_inst.hip", "rmblock.hip.h", "igemm32l.hip.h", "igemm32l_inst.hip", "version.cpp", "calib.hip", "exports.map",
-           "state.hip.h",
+           "state.hip.h", "formant.hip.h",
            "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h", "blob.h", "rvc_rpc.cpp")
 
 # translation units of the library: (source, extra flags, files whose contents decide whether the object is stale).  The implicit-GEMM
 # template instantiations are the bulk of the compile time; as separate units they build in parallel (5 min -> about 1.5 min on 8 cores)
 # and are not rebuilt when only the engine changes.
 _IGEMM_DEPS = ("igemm.hip.h", "igemm_launch.h")
-_INT_DEPS = ("engine_int.h", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "blob.h", "state.hip.h")
+_INT_DEPS = ("engine_int.h", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "blob.h", "state.hip.h", "formant.hip.h")
 _ENGINE_DEPS = ("engine.hip", "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h") + _INT_DEPS
 UNITS = [("engine.hip", [], _ENGINE_DEPS), ("calib.hip", [], ("calib.hip",))] + [(u, [], (u,) + _INT_DEPS + (("rmblock.hip.h",) if u == "model_rmvpe.hip" else ())) for u in ("plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_synth.hip", "retrieval.hip")] + \
         [("igemm2_inst.hip", ["-DRVC_IGEMM2_CFG=%d" % c], ("igemm2_inst.hip",) + _IGEMM_DEPS) for c in range(5)] + \
@@ -225,6 +226,12 @@ def lib():
         L.rvc_retrieval_recoveries.restype = C.c_longlong
     if hasattr(L, "rvc_set_gemm_precision") or not override:
         L.rvc_set_gemm_precision.argtypes = [vp, C.c_int]
+    if hasattr(L, "rvc_set_formant_shift") or not override:
+        L.rvc_set_formant_shift.argtypes = [vp, C.c_double]
+        L.rvc_set_formant_shift_stream.argtypes = [vp, C.c_int, C.c_double]
+        L.rvc_formant_geometry.argtypes = [sz, sz, C.c_double, C.POINTER(sz)]
+        L.rvc_debug_formant_table.argtypes = [sz, sz, fp, sz, C.POINTER(sz)]
+        L.rvc_debug_formant_table.restype = C.c_int
     L.rvc_set_pipeline.argtypes = [vp, C.c_int]
     L.rvc_set_pipeline.restype = None
     L.rvc_last_gpu_ms.argtypes = [vp]

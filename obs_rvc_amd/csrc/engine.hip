@@ -178,14 +178,18 @@ static void alloc_state(rvc_engine *e)
     if (e->d_state_bucket) { (void)hipFree(e->d_state_bucket); e->d_state_bucket = nullptr; }
     if (e->d_bucket_idx) { (void)hipFree(e->d_bucket_idx); e->d_bucket_idx = nullptr; }
     HIPCHK(hipMalloc(&e->d_state, sizeof(StreamState) * e->n_streams));
+    e->formant.resize(e->n_streams, e->formant_default);     // existing streams keep their formant shift, new ones get the default
     reset_state(e);
     e->plans.clear();
     e->last_plan = nullptr;
 }
 
 // ------------------------------- plan -------------------------------------------------
-static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32_t skip_head, uint32_t R, int slot = 0, int bucket_B = 0)
+static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32_t skip_head, uint32_t R, int slot = 0, int bucket_B = 0,
+                      uint32_t R2 = 0, bool fstage = false)
 {
+    // fstage: the plan carries the formant stage, the decoder runs on R2 frames (formant.hip.h); without it the key is today's (R2 = R)
+    if (!fstage) R2 = R;
     // bucket_B > 0 (rvc_infer_batch_g): a plan for bucket_B of the engine's streams, whose states the caller gathers into d_state_bucket.
     // The builders read the stream count and the state block from the engine: both are swapped for the duration of the build.
     struct Swap {
@@ -205,7 +209,8 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         } else i++;
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
-            p->with_index == with_index && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0)) {
+            p->with_index == with_index && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
+            p->R2 == R2 && p->fstage == fstage) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -218,6 +223,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
     pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
+    pl.R2 = R2; pl.fstage = fstage;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
     T1 sal0, src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;
@@ -367,17 +373,93 @@ static void run_plan(rvc_engine *e, Plan &pl)
     e->last_plan = &pl;
 }
 
+
+// ------------------------------- formant shift ----------------------------------------
+static_assert(offsetof(StreamState, f_ident) + sizeof(int) - offsetof(StreamState, f_tab) == sizeof(FormantDesc), "StreamState formant fields != FormantDesc");
+
+// the device form of the filter table o -> n, built once per engine (the descriptors of a captured graph's streams point at it)
+static const FormantTable &formant_table_dev(rvc_engine *e, int o, int n)
+{
+    auto it = e->ftabs.find({o, n});
+    if (it != e->ftabs.end()) return it->second;
+    std::vector<float> ht; std::vector<int> kb; FormantTable t; t.o = o; t.n = n;
+    formant_table_compact((size_t)o, (size_t)n, ht, kb, &t.w, &t.Kt);
+    HIPCHK(hipMalloc(&t.tab, ht.size() * sizeof(float)));
+    HIPCHK(hipMalloc(&t.kb, kb.size() * sizeof(int)));
+    HIPCHK(hipMemcpy(t.tab, ht.data(), ht.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.kb, kb.data(), kb.size() * sizeof(int), hipMemcpyHostToDevice));
+    return e->ftabs[{o, n}] = t;
+}
+
+// stream s of a call with return_length R: its decoder length R2 and whether it resamples (upp_res != upp)
+static void formant_geo(rvc_engine *e, int s, uint32_t R, uint32_t *R2, bool *res)
+{
+    size_t r2 = R, ur = 0;
+    const size_t upp = (size_t)e->sy->upp();
+    if (R < 1) { *R2 = R; *res = false; return; }        // (rejected by the planner)
+    if (!formant_geometry(R, (size_t)e->sy->sr, e->formant[s], &r2, &ur)) throw ShapeError("formant shift: geometry out of range");
+    *R2 = (uint32_t)r2; *res = ur != upp;
+}
+
+// the descriptor of stream s (StreamState::f_*) for return_length R
+static FormantDesc formant_desc(rvc_engine *e, int s, uint32_t R)
+{
+    size_t R2 = R, ur = 0;
+    const size_t upp = (size_t)e->sy->upp();
+    FormantDesc d{};
+    if (R < 1) return d;
+    if (!formant_geometry(R, (size_t)e->sy->sr, e->formant[s], &R2, &ur)) throw ShapeError("formant shift: geometry out of range");
+    if (ur == upp) {
+        if (R2 < R) throw ShapeError("formant shift: decoder shorter than the chunk");
+        d.ident = 1;
+        return d;
+    }
+    if ((size_t)R * ur > R2 * upp) throw ShapeError("formant shift: resampler input beyond the decoder output");
+    const size_t g = formant_gcd(ur, upp);
+    const FormantTable &t = formant_table_dev(e, (int)(ur / g), (int)(upp / g));
+    d.tab = t.tab; d.kb = t.kb; d.o = t.o; d.n = t.n; d.w = t.w; d.kt = t.Kt; d.nx = (int)((size_t)R * ur);
+    return d;
+}
+
+// the plan key of a set of streams (all of them: ids == nullptr) at return_length R -> false when their decoder lengths differ
+static bool formant_key(rvc_engine *e, uint32_t R, const std::vector<int> *ids, uint32_t *R2, bool *fstage)
+{
+    const int n = ids ? (int)ids->size() : e->n_streams;
+    bool any = false;
+    for (int j = 0; j < n; j++) {
+        uint32_t r2; bool res;
+        formant_geo(e, ids ? (*ids)[j] : j, R, &r2, &res);
+        if (j == 0) *R2 = r2;
+        else if (r2 != *R2) return false;
+        any = any || res;
+    }
+    *fstage = any || *R2 != R;
+    return true;
+}
+
 static float uppower(int32_t pitch_shift) { return ldexpf(1.0f, pitch_shift / 12); }   // rvc.rs:121, truncating division (Q1)
 
 // Per-call parameters: the seed (CallParams) and one pitch-shift multiplier PER STREAM (StreamState::uppower: every stream of a batch
 // is its own caller with its own settings, obs-rvc/src/lib.rs:701-707).  shifts == nullptr: `pitch_shift` for every stream.
-static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *shifts = nullptr)
+// Rs (infer calls: the return_length of every stream): the multiplier also carries the stream's formant factor (float)2^(-phi / 12), and
+// the stream's formant descriptor is written next to it; without Rs (hubert / pitch) no formant factor and the descriptors stay.
+static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *shifts = nullptr, const uint32_t *Rs = nullptr)
 {
     const int B = e->n_streams;
+    std::vector<float> up(B);
+    std::vector<FormantDesc> fd((size_t)B, FormantDesc{});
+    if (!Rs && (int)e->pushed_fd.size() == B) fd = e->pushed_fd;
+    for (int b = 0; b < B; b++) {
+        up[b] = uppower(shifts ? shifts[b] : pitch_shift);
+        if (Rs) {
+            up[b] *= (float)std::pow(2.0, -e->formant[b] / 12.0);
+            fd[b] = formant_desc(e, b, Rs[b]);
+        }
+    }
     // The device already holds these values (every write to them is ordered on the main stream, and the last one wrote exactly this):
     // nothing to copy -- a small H2D copy is a 4-5 us blit kernel in front of both branches of every chunk otherwise.
-    bool same = e->pushed_valid && e->pushed_seed == e->seed && (int)e->pushed_up.size() == B;
-    for (int b = 0; b < B && same; b++) same = e->pushed_up[b] == uppower(shifts ? shifts[b] : pitch_shift);
+    bool same = e->pushed_valid && e->pushed_seed == e->seed && (int)e->pushed_up.size() == B && (int)e->pushed_fd.size() == B;
+    for (int b = 0; b < B && same; b++) same = e->pushed_up[b] == up[b] && e->pushed_fd[b] == fd[b];
     if (same) return;
     if (e->pipeline) HIPCHK(hipDeviceSynchronize());   // the f0 branch of the next chunk may already be running: drain before the values change
     // every call writes its own pinned block: an unsynchronised call's copy may still be pending when the next call arrives
@@ -393,9 +475,11 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
     const unsigned us = e->up_slot++ & 7u;
     if (e->ev_up_used[us]) HIPCHK(hipEventSynchronize(e->ev_up[us]));
     float *hu = e->h_up + (size_t)us * 4096;
-    e->pushed_up.resize(B);
-    for (int b = 0; b < B; b++) hu[b] = e->pushed_up[b] = uppower(shifts ? shifts[b] : pitch_shift);
+    FormantDesc *hf = e->h_fd + (size_t)us * 4096;
+    for (int b = 0; b < B; b++) { hu[b] = up[b]; hf[b] = fd[b]; }
+    e->pushed_up = up; e->pushed_fd = fd;
     HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, uppower), sizeof(StreamState), hu, sizeof(float), sizeof(float), (size_t)B, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, f_tab), sizeof(StreamState), hf, sizeof(FormantDesc), sizeof(FormantDesc), (size_t)B, hipMemcpyHostToDevice, e->stream));
     if (!e->ev_up[us]) HIPCHK(hipEventCreateWithFlags(&e->ev_up[us], hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->ev_up[us], e->stream)); e->ev_up_used[us] = true;
     e->pushed_seed = e->seed; e->pushed_valid = true;
@@ -472,6 +556,37 @@ static rvc_status recover_retrieval(rvc_engine *e, Plan &pl)
     return RVC_OK;
 }
 
+// Streams in buckets (rvc_infer_batch_g: one per geometry; the other infer calls: one per formant decoder length R2): every bucket runs as one batch
+// through its own plan on a gathered copy of its streams' states (pitch cache, counters, status, multiplier, formant descriptor), scattered back
+// afterwards.  in(s) / out(s): stream s's input / output buffer.
+struct BucketRun { Plan *pl; std::vector<int> ids; };
+// the gathered state block the bucket plans are built on (their kernels bake its address): allocated before the first bucket plan
+static void ensure_bucket_state(rvc_engine *e)
+{
+    if (!e->d_state_bucket) { HIPCHK(hipMalloc(&e->d_state_bucket, sizeof(StreamState) * e->n_streams)); HIPCHK(hipMalloc(&e->d_bucket_idx, sizeof(int) * e->n_streams)); }
+}
+static rvc_status run_buckets(rvc_engine *e, std::vector<BucketRun> &work, const std::function<const void *(int)> &in, bool in_dev,
+                              const std::function<void *(int)> &out, bool out_dev)
+{
+    for (auto &w : work)
+        { bool ok = false; for (auto &p : e->plans) ok = ok || p.get() == w.pl; if (!ok) throw std::logic_error("bucketed call: a plan of this call left the cache"); }
+    for (auto &w : work) {
+        Plan *pl = w.pl; const std::vector<int> &ids = w.ids; const int Bk = (int)ids.size();
+        HIPCHK(hipMemcpyAsync(e->d_bucket_idx, ids.data(), sizeof(int) * Bk, hipMemcpyHostToDevice, e->stream));
+        hipLaunchKernelGGL(state_gather_kernel, dim3(Bk), dim3(256), 0, e->stream, e->d_state, e->d_state_bucket, e->d_bucket_idx, 0);
+        for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(pl->d_in + (size_t)j * pl->L, in(ids[j]), pl->L * sizeof(float), in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+        pl->cur_in = nullptr; pl->cur_out = nullptr;
+        run_plan(e, *pl);
+        for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(out(ids[j]), pl->audio.p + (size_t)j * pl->N, pl->N * sizeof(float), out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
+        hipLaunchKernelGGL(state_gather_kernel, dim3(Bk), dim3(256), 0, e->stream, e->d_state, e->d_state_bucket, e->d_bucket_idx, 1);
+        HIPCHK(hipStreamSynchronize(e->stream));        // (ids / the pinned-less host buffers of this bucket are free again; the next bucket reuses the state block)
+    }
+    e->last_knn_rows = 0;
+    queue_status(e);                                     // the streams' own status words (the plans wrote bucket-local ones)
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return final_status(e);
+}
+
 static std::string native_path(const std::string &p)
 {
     if (p.size() > 5 && p.substr(p.size() - 5) == ".onnx") return p.substr(0, p.size() - 5) + ".rvcw";
@@ -510,6 +625,7 @@ rvc_status rvc_create(const char *data_path, int device, rvc_engine **out)
         HIPCHK(hipHostMalloc((void **)&e->h_status, 4096 * sizeof(int)));
         memset(e->h_status, 0, 4096 * sizeof(int));
         HIPCHK(hipHostMalloc((void **)&e->h_up, (size_t)8 * 4096 * sizeof(float)));
+        HIPCHK(hipHostMalloc((void **)&e->h_fd, (size_t)8 * 4096 * sizeof(FormantDesc)));
         init_constants(e);
         alloc_state(e);
     } catch (const std::exception &x) {
@@ -543,6 +659,8 @@ void rvc_destroy(rvc_engine *e)
     if (e->h_cp) (void)hipHostFree(e->h_cp);
     if (e->h_status) (void)hipHostFree(e->h_status);
     if (e->h_up) (void)hipHostFree(e->h_up);
+    if (e->h_fd) (void)hipHostFree(e->h_fd);
+    for (auto &kv : e->ftabs) { (void)hipFree(kv.second.tab); (void)hipFree(kv.second.kb); }
     for (int i = 0; i < 8; i++) if (e->ev_up[i]) (void)hipEventDestroy(e->ev_up[i]);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -662,6 +780,31 @@ rvc_status rvc_pitch(rvc_engine *e, const float *input, size_t n, int32_t pitch_
     });
 }
 
+// Streams whose formant shifts give different decoder lengths R2: one bucket per R2 (run_buckets), synchronous
+static rvc_status infer_r2_buckets(rvc_engine *e, const void *input, bool input_on_device, size_t n, size_t frame16k, int32_t pitch_shift,
+                                   uint32_t skip_head, uint32_t return_length, void *out, bool out_on_device, size_t cap, size_t *out_len, const int32_t *shifts)
+{
+    if (e->pipeline || e->use_graph) throw ShapeError("formant shift: streams with different decoder lengths in one call are not served with chunk pipelining / graph replay");
+    const int S = e->n_streams;
+    std::map<uint32_t, std::vector<int>> by;
+    for (int s = 0; s < S; s++) { uint32_t r2; bool res; formant_geo(e, s, return_length, &r2, &res); by[r2].push_back(s); }
+    if ((int)by.size() > e->plan_cap) throw ShapeError("formant shift: more different decoder lengths in one call than the plan cache holds (rvc_set_plan_cache)");
+    ensure_bucket_state(e);
+    std::vector<BucketRun> work;
+    for (auto &kv : by) {
+        uint32_t r2 = 0; bool fstage = false;
+        formant_key(e, return_length, &kv.second, &r2, &fstage);
+        Plan *pl = get_plan(e, 0, n, frame16k, skip_head, return_length, 0, (int)kv.second.size(), r2, fstage);
+        if (out_len) *out_len = pl->N;
+        if (cap < pl->N) return RVC_SHAPE;
+        work.push_back({pl, kv.second});
+    }
+    std::vector<uint32_t> Rs((size_t)S, return_length);
+    push_call_params(e, pitch_shift, shifts, Rs.data());
+    return run_buckets(e, work, [&](int s) { return (const void *)((const float *)input + (size_t)s * n); }, input_on_device,
+                       [&](int s) { return (void *)((float *)out + (size_t)s * cap); }, out_on_device);
+}
+
 static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_device, size_t n, size_t frame16k, int32_t pitch_shift,
                                uint32_t skip_head, uint32_t return_length, void *out, bool out_on_device, size_t cap, size_t *out_len, bool sync,
                                const int32_t *shifts = nullptr)
@@ -669,12 +812,18 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
     if (!e->sy) return RVC_MODEL_NOT_LOADED;             // rvc.rs:141-143
     if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;        // rvc.rs:85-88 (via extract_feature at rvc.rs:151)
     if (!e->rm) return RVC_F0_NOT_LOADED;                // reference: unreachable!() at rvc.rs:125
+    uint32_t R2 = return_length; bool fstage = false;
+    if (!formant_key(e, return_length, nullptr, &R2, &fstage))
+        return infer_r2_buckets(e, input, input_on_device, n, frame16k, pitch_shift, skip_head, return_length, out, out_on_device, cap, out_len, shifts);
     const bool pipe = e->pipeline && !sync && input_on_device && out_on_device && e->partitioned && !e->use_graph && !e->profile_on && !e->taps_on;
-    Plan *pl = get_plan(e, 0, n, frame16k, skip_head, return_length, pipe ? (e->pipe_slot ^= 1) : 0);
+    Plan *pl = get_plan(e, 0, n, frame16k, skip_head, return_length, pipe ? (e->pipe_slot ^= 1) : 0, 0, R2, fstage);
     if (out_len) *out_len = pl->N;
     if (cap < pl->N) return RVC_SHAPE;
     const int B = pl->B;
-    push_call_params(e, pitch_shift, shifts);
+    {
+        std::vector<uint32_t> Rs((size_t)B, return_length);
+        push_call_params(e, pitch_shift, shifts, Rs.data());
+    }
     // Device-resident callers: the first kernels read the caller's buffer and the last one writes the caller's buffer (eager launches
     // take the pointers at launch time) -- no staging copy in front of the chunk, no copy behind it.  A captured graph bakes its
     // pointers and keeps both copies; pipelined calls keep the input copy (it decouples the caller's buffer from the chunk in flight).
@@ -780,41 +929,29 @@ rvc_status rvc_infer_batch_g(rvc_engine *e, const float *const *inputs, const si
         if (!e->rm) return RVC_F0_NOT_LOADED;
         const int S = e->n_streams;
         if (e->pipeline || e->use_graph) throw ShapeError("infer_batch_g: not with chunk pipelining / graph replay");
-        struct Key { size_t n, f; uint32_t sh, rl; bool operator<(const Key &o) const { return std::tie(n, f, sh, rl) < std::tie(o.n, o.f, o.sh, o.rl); } };
+        // (R2, fstage: the formant decoder length of the stream and whether its bucket carries the formant stage, formant.hip.h)
+        struct Key { size_t n, f; uint32_t sh, rl, r2; bool operator<(const Key &o) const { return std::tie(n, f, sh, rl, r2) < std::tie(o.n, o.f, o.sh, o.rl, o.r2); } };
         std::map<Key, std::vector<int>> buckets;
         for (int s = 0; s < S; s++) {
             if (!inputs[s] || !outs[s]) throw ShapeError("infer_batch_g: null stream buffer");
-            buckets[Key{n[s], sample_frame_16k_size[s], skip_head[s], return_length[s]}].push_back(s);
+            uint32_t r2; bool res; formant_geo(e, s, return_length[s], &r2, &res);
+            buckets[Key{n[s], sample_frame_16k_size[s], skip_head[s], return_length[s], r2}].push_back(s);
         }
         // every bucket's plan must stay cached until the call has run it: the cache is LRU and the call's plans are its most recent entries, so the
         // only way to lose one is more buckets than slots
         if ((int)buckets.size() > e->plan_cap) throw ShapeError("infer_batch_g: more different geometries in one call than the plan cache holds (rvc_set_plan_cache)");
-        if (!e->d_state_bucket) { HIPCHK(hipMalloc(&e->d_state_bucket, sizeof(StreamState) * S)); HIPCHK(hipMalloc(&e->d_bucket_idx, sizeof(int) * S)); }
+        ensure_bucket_state(e);
         // plans first (a geometry the engine rejects must not leave some buckets already advanced), then the work
-        std::vector<std::pair<Plan *, const std::vector<int> *>> work;
+        std::vector<BucketRun> work;
         for (auto &kv : buckets) {
-            Plan *pl = get_plan(e, 0, kv.first.n, kv.first.f, kv.first.sh, kv.first.rl, 0, (int)kv.second.size());
+            uint32_t r2 = 0; bool fstage = false;
+            formant_key(e, kv.first.rl, &kv.second, &r2, &fstage);
+            Plan *pl = get_plan(e, 0, kv.first.n, kv.first.f, kv.first.sh, kv.first.rl, 0, (int)kv.second.size(), r2, fstage);
             for (int s : kv.second) { if (out_lens) out_lens[s] = pl->N; if (caps[s] < pl->N) return RVC_SHAPE; }
-            work.push_back({pl, &kv.second});
+            work.push_back({pl, kv.second});
         }
-        for (auto &w : work)
-            { bool ok = false; for (auto &p : e->plans) ok = ok || p.get() == w.first; if (!ok) throw std::logic_error("infer_batch_g: a plan of this call left the cache"); }
-        push_call_params(e, 0, pitch_shift);            // per-stream multipliers into the streams' own states (a null array: no shift)
-        for (auto &w : work) {
-            Plan *pl = w.first; const std::vector<int> &ids = *w.second; const int Bk = (int)ids.size();
-            HIPCHK(hipMemcpyAsync(e->d_bucket_idx, ids.data(), sizeof(int) * Bk, hipMemcpyHostToDevice, e->stream));
-            hipLaunchKernelGGL(state_gather_kernel, dim3(Bk), dim3(256), 0, e->stream, e->d_state, e->d_state_bucket, e->d_bucket_idx, 0);
-            for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(pl->d_in + (size_t)j * pl->L, inputs[ids[j]], pl->L * sizeof(float), hipMemcpyHostToDevice, e->stream));
-            pl->cur_in = nullptr; pl->cur_out = nullptr;
-            run_plan(e, *pl);
-            for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(outs[ids[j]], pl->audio.p + (size_t)j * pl->N, pl->N * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-            hipLaunchKernelGGL(state_gather_kernel, dim3(Bk), dim3(256), 0, e->stream, e->d_state, e->d_state_bucket, e->d_bucket_idx, 1);
-            HIPCHK(hipStreamSynchronize(e->stream));        // (ids / the pinned-less host buffers of this bucket are free again; the next bucket reuses the state block)
-        }
-        e->last_knn_rows = 0;
-        queue_status(e);                                     // the streams' own status words (the plans wrote bucket-local ones)
-        HIPCHK(hipStreamSynchronize(e->stream));
-        return final_status(e);
+        push_call_params(e, 0, pitch_shift, return_length);      // per-stream multipliers into the streams' own states (a null array: no shift)
+        return run_buckets(e, work, [&](int s) { return (const void *)inputs[s]; }, false, [&](int s) { return (void *)outs[s]; }, false);
     });
 }
 
@@ -942,6 +1079,45 @@ void rvc_get_pitch_cache(rvc_engine *e, int stream, float *out1024)
         HIPCHK(hipMemcpy(out1024, e->d_state[stream].cache_pitchf, 1024 * sizeof(float), hipMemcpyDeviceToHost));
         return RVC_OK;
     });
+}
+
+// formant shift (the plugin's resonance shift, obs-rvc/src/lib.rs:80,103,176,369-375,446-451; formant.hip.h): semitones in [-5, 5]
+rvc_status rvc_set_formant_shift(rvc_engine *e, double semitones)
+{
+    return guarded(e, [&]() {
+        if (!(semitones >= -FORMANT_MAX && semitones <= FORMANT_MAX)) throw ShapeError("formant shift: semitones outside [-5, 5]");
+        e->formant_default = semitones;
+        for (auto &v : e->formant) v = semitones;
+        return RVC_OK;
+    });
+}
+rvc_status rvc_set_formant_shift_stream(rvc_engine *e, int stream, double semitones)
+{
+    return guarded(e, [&]() {
+        if (stream < 0 || stream >= e->n_streams) throw ShapeError("formant shift: stream out of range");
+        if (!(semitones >= -FORMANT_MAX && semitones <= FORMANT_MAX)) throw ShapeError("formant shift: semitones outside [-5, 5]");
+        e->formant[stream] = semitones;
+        return RVC_OK;
+    });
+}
+rvc_status rvc_formant_geometry(size_t return_length, size_t sample_rate, double semitones, size_t out[2])
+{
+    if (!out) return RVC_SHAPE;
+    size_t R2 = 0, ur = 0;
+    if (!formant_geometry(return_length, sample_rate, semitones, &R2, &ur)) return RVC_SHAPE;
+    out[0] = R2; out[1] = ur;
+    return RVC_OK;
+}
+// the full filter table h[n][K] of the resampler o -> n (host only): 0, -1 on bad arguments, 1 when cap < n K (*width is written)
+int rvc_debug_formant_table(size_t o, size_t n, float *out, size_t cap, size_t *width)
+{
+    if (o < 1 || n < 1 || o > 100000 || n > 100000) return -1;
+    std::vector<float> h; size_t w, K;
+    formant_table(o, n, h, &w, &K);
+    if (width) *width = K;
+    if (!out || cap < h.size()) return 1;
+    memcpy(out, h.data(), h.size() * sizeof(float));
+    return 0;
 }
 
 rvc_status rvc_profile_last(rvc_engine *e, int *launches, double *kernel_ms, double *flops)

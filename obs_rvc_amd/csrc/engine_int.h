@@ -9,6 +9,7 @@
 #include "../../include/rvc_mi355x.h"
 #include "blob.h"
 #include "kernels.hip.h"
+#include "formant.hip.h"
 #include "igemm_launch.h"
 #include <hip/hip_ext.h>
 
@@ -245,6 +246,10 @@ struct Plan {
     double tune_ms = 0; int tuned_layers = 0, tune_changed = 0, tune_hits = 0;      // time spent in trials, layers tuned here / changed against the rules / taken from the process cache
     bool plain_plan = false;      // taps level 1: the explicit plan (LayerNorm launches, WaveNets layer by layer); level 2 taps the production plan
     int mode = 0;   // 0 infer, 1 hubert only, 2 pitch only
+    // formant shift (formant.hip.h): fstage = the plan has the formant stage (some stream stretches or resamples); the decoder then runs
+    // on R2 frames and formant_resample_kernel brings every stream back to R upp samples.  fstage = false: today's plan, R2 = R
+    uint32_t R2 = 0; bool fstage = false;
+    int dec_frames() const { return fstage ? (int)R2 : (int)R; }
     // I/O tensors
     float *d_in = nullptr;  // [B][L]
     T1 cv_out, audio;
@@ -892,6 +897,12 @@ struct rvc_engine {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.f;
     size_t last_knn_rows = 0;
+    // formant shift (formant.hip.h): semitones per stream (rvc_set_formant_shift[_stream]) and the default of new streams; filter tables by
+    // ratio (o, n), device memory for the engine's life (a captured graph's descriptors point at them); the descriptors the device holds
+    std::vector<double> formant; double formant_default = 0.0;
+    std::map<std::pair<int, int>, rvc::FormantTable> ftabs;
+    std::vector<rvc::FormantDesc> pushed_fd;
+    rvc::FormantDesc *h_fd = nullptr;     // pinned ring of 8 blocks of 4096 descriptors, written and read with h_up's blocks
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };

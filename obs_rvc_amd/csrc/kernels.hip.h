@@ -1285,6 +1285,7 @@ struct SrcP {
     int T, upp; float sr;
     float lin_w, lin_b;
     const StreamState *st; const CallParams *cp;
+    int f0_num, f0_den;    // formant shift: the source reads f0 x f0_num / f0_den in fp32 (R2 / R, formant.hip.h); equal: f0 as it is
 };
 
 static __global__ __launch_bounds__(1024) void nsf_source_kernel(SrcP p)
@@ -1297,7 +1298,11 @@ static __global__ __launch_bounds__(1024) void nsf_source_kernel(SrcP p)
     const float *f0 = p.pitchf + (long long)b * T;
     if (tid == 0) {
         float c = 0.f;
-        for (int t = 0; t < T; t++) { float r = fmodf(f0[t] / p.sr, 1.0f); rad[t] = r; c += r; cum[t] = c * (float)upp; }
+        const bool scale = p.f0_num != p.f0_den;
+        for (int t = 0; t < T; t++) {
+            const float f = scale ? (f0[t] * (float)p.f0_num) / (float)p.f0_den : f0[t];
+            float r = fmodf(f / p.sr, 1.0f); rad[t] = r; c += r; cum[t] = c * (float)upp;
+        }
     }
     __syncthreads();
     // each thread owns a contiguous segment whose length is a multiple of 4 (one Philox block = 4 samples)

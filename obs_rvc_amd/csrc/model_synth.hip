@@ -9,7 +9,7 @@ T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
 {
     ModelSY &m = *e->sy;
     Arena &A = pl.arena;
-    const int R = (int)pl.R;
+    const int R = (int)pl.R, R2 = pl.dec_frames();
     const int upp = m.upp();
     const size_t N = (size_t)R * upp;
     if (R > 512) throw ShapeError("return_length too long for the NSF source kernel");
@@ -18,10 +18,20 @@ T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
     {
         SrcP sp{}; sp.pitchf = d_pitchf; sp.src = src.p; sp.src_bs = src.bs; sp.T = R; sp.upp = upp; sp.sr = (float)m.sr;
         sp.lin_w = m.src_w; sp.lin_b = m.src_b; sp.st = e->d_state; sp.cp = e->d_cp;
+        sp.f0_num = R2; sp.f0_den = R;        // formant shift: f0 x R2 / R compensates the time stretch below (1 without one)
         pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(nsf_source_kernel, dim3(B), dim3(1024), 0, s, sp); });
     }
     add_tap(pl, "sy.src", src);
-    return src;
+    if (!pl.fstage) return src;
+    // formant shift: the source stretched to R2 frames (formant.hip.h)
+    T1 srci = src;
+    if (R2 != R) {
+        srci = make_t1(A, B, 1, R2 * upp, max_sf + 2);
+        const int Nin = (int)N, Nout = R2 * upp; dim3 grid((Nout + 255) / 256, B);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(time_lerp_kernel, grid, dim3(256), 0, s, src.p, src.ld, src.bs, srci.p, srci.ld, srci.bs, 1, Nin, Nout); });
+    }
+    add_tap(pl, "sy.srci", srci);
+    return srci;
 }
 
 // The decoder adds a strided convolution of the harmonic source to the output of every upsampling stage.  Those convolutions depend on
@@ -31,7 +41,7 @@ std::vector<T1> build_noise_convs(rvc_engine *e, Plan &pl, int B, const T1 &src)
 {
     ModelSY &m = *e->sy;
     std::vector<T1> nz;
-    int c = m.up_init, Tc = (int)pl.R;
+    int c = m.up_init, Tc = pl.dec_frames();
     for (int i = 0; i < m.n_ups; i++) {
         const int co = c / 2, Tn = Tc * m.up_rate[i];
         T1 t = make_t1(pl.arena, B, co, Tn, 0);
@@ -160,13 +170,21 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
     }
     add_tap(pl, "sy.z", z);
     const int upp = m.upp();
-    const size_t N = (size_t)R * upp;
-    (void)N;
+    const int R2 = pl.dec_frames();
+    if (pl.fstage) {
+        // formant shift: the latent stretched to R2 frames; the decoder runs on them (formant.hip.h)
+        if (R2 != R) {
+            T1 zi = make_t1(A, B, I, R2, HALO); dim3 grid((I * R2 + 255) / 256, B); T1 zs = z;
+            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(time_lerp_kernel, grid, dim3(256), 0, s, zs.p, zs.ld, zs.bs, zi.p, zi.ld, zi.bs, I, R, R2); });
+            z = zi;
+        }
+        add_tap(pl, "sy.zi", z);
+    }
     // decoder
     int max_pad = 3;
     for (int j = 0; j < m.n_rb; j++) for (int q = 0; q < m.n_rbd; q++) max_pad = std::max(max_pad, (m.rb_k[j] * m.rb_d[q] - m.rb_d[q]) / 2);
     const int DH = (max_pad + 3) / 4 * 4;
-    int c = m.up_init, Tc = R;
+    int c = m.up_init, Tc = R2;
     if (src_join_sid > 0) pl.ops.join(src_join_sid);     // the harmonic source was produced on a side stream
     T1 xd = make_t1(A, B, c, Tc, DH);
     add_conv1d(pl, m.dec_pre, z, xd, 1, 3, 1);
@@ -242,6 +260,26 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         }
         if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.rb%d", i); add_tap(pl, nm, xs); } else add_stamp(pl, "sy.rb");
         xd = xs; c = co; Tc = Tn;
+    }
+    if (pl.fstage) {
+        // formant shift: the decoder's output y2 (R2 upp samples) back to the model rate, R upp samples per stream, by each stream's own
+        // descriptor; the kernel writes the caller's buffer when the call provides one (Plan::cur_out)
+        T1 dec = make_t1(A, B, 1, Tc, 0);
+        { ConvOpts o; o.pre_act = ACT_LRELU; o.pre_slope = 0.01f; o.act = ACT_TANH; o.no_bias = true; add_conv1d(pl, m.dec_post, xd, dec, 1, 3, 1, o); }
+        add_tap(pl, "sy.dec", dec);
+        const int No = R * upp;
+        // (R2 < R for negative shifts: the output is longer than y2; each stream reads y2[0 : R upp_res], checked against R2 upp at upload)
+        T1 a; a.p = A.floats((size_t)B * No); a.B = B; a.C = 1; a.T = No; a.ld = No; a.halo = 0; a.bs = No;
+        pl.audio = a;
+        const Plan *pp = &pl; const StreamState *st = e->d_state; dim3 grid((No + 255) / 256, B);
+        pl.ops.push_back([=](hipStream_t s) {
+            float *y = pp->cur_out ? pp->cur_out : a.p; const long long ybs = pp->cur_out ? pp->cur_out_bs : (long long)No;
+            hipLaunchKernelGGL(formant_resample_kernel, grid, dim3(256), 0, s, dec.p, dec.bs, y, ybs, No, st);
+        });
+        pl.N = (size_t)No;
+        pl.out_direct_ok = !pl.with_taps;
+        add_stamp(pl, "sy.audio");
+        return;
     }
     pl.audio = make_t1(A, B, 1, Tc, 0);
     { ConvOpts o; o.pre_act = ACT_LRELU; o.pre_slope = 0.01f; o.act = ACT_TANH; o.no_bias = true; o.final_out = true; add_conv1d(pl, m.dec_post, xd, pl.audio, 1, 3, 1, o); }

@@ -182,8 +182,12 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
             //  many-stream plans search through the distance GEMM and hand nothing over inside a launch: their chain stays asynchronous)
             bool sync_infer = false;
             if (e->d_index && e->index_rate > 0.f) {
-                Plan *peek = get_plan(e, 0, (size_t)s->input_buffer_16k_size, (size_t)s->sample_frame_16k, (uint32_t)s->skip_head, (uint32_t)s->model_return_length, 0);
-                sync_infer = !peek->knn_fallback.empty();
+                // (the plan infer_common will run: its formant key; streams in several formant buckets run synchronously anyway)
+                uint32_t r2 = 0; bool fstage = false;
+                if (formant_key(e, (uint32_t)s->model_return_length, nullptr, &r2, &fstage)) {
+                    Plan *peek = get_plan(e, 0, (size_t)s->input_buffer_16k_size, (size_t)s->sample_frame_16k, (uint32_t)s->skip_head, (uint32_t)s->model_return_length, 0, 0, r2, fstage);
+                    sync_infer = !peek->knn_fallback.empty();
+                } else sync_infer = true;
             }
             rvc_status rc = infer_common(e, ring16, true, (size_t)s->input_buffer_16k_size, (size_t)s->sample_frame_16k, 0, (uint32_t)s->skip_head,
                                          (uint32_t)s->model_return_length, s->d_model, true, (size_t)s->model_return_size, &got, sync_infer, s->pitch_shift.data());

@@ -19,7 +19,11 @@ struct StreamState {        // one per stream
     uint32_t chunk;
     uint32_t stream_id;
     int status;             // 0 ok, else a set of ST_* bits (atomicOr by the kernels, read and cleared by the host: engine.hip check_status)
-    float uppower;          // this stream's 2^(pitch_shift / 12), truncating division (rvc.rs:121): every stream is its own caller
+    float uppower;          // this stream's 2^(pitch_shift / 12), truncating division (rvc.rs:121), times its formant multiplier 2^(-phi / 12): every stream is its own caller
+    // formant stage of this stream (formant.hip.h formant_resample_kernel; written by the host with the multiplier, engine.hip push_call_params)
+    const float *f_tab;     // [n][kt] filter rows (the engine's table cache), nullptr when f_ident
+    const int *f_kb;        // [n] first tap of each row
+    int f_o, f_n, f_w, f_kt, f_nx, f_ident;     // ratio o -> n, left width, taps per row, valid input samples (R upp_res), 1 = copy
 };
 
 // status bits of a stream (several kernels of one chunk may report; a plain store would lose the earlier report)

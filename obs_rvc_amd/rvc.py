@@ -157,6 +157,24 @@ class RvcInfer:
     def reset_state(self):
         self._L.rvc_reset_state(self._h)
 
+    def set_formant_shift(self, semitones: float, stream: int = None):
+        """Formant shift (the plugin's resonance shift, obs-rvc/src/lib.rs:80,103,176) in semitones, -5..5: every stream and the
+        default of streams added later, or (stream given) one stream (rvc_set_formant_shift[_stream])."""
+        if stream is None:
+            self._chk(self._L.rvc_set_formant_shift(self._h, float(semitones)))
+        else:
+            self._chk(self._L.rvc_set_formant_shift_stream(self._h, int(stream), float(semitones)))
+
+    @staticmethod
+    def formant_geometry(return_length: int, sample_rate: int, semitones: float):
+        """-> (R2, upp_res): the decoder's frame count and the resampler's input samples per frame of a formant shift
+        (rvc_formant_geometry; host only)."""
+        out = (C.c_size_t * 2)()
+        rc = _native.lib().rvc_formant_geometry(int(return_length), int(sample_rate), float(semitones), out)
+        if rc != 0:
+            raise RvcInferError(rc, "formant geometry out of range")
+        return int(out[0]), int(out[1])
+
     def set_streams(self, n: int):
         self._chk(self._L.rvc_set_streams(self._h, int(n)))
         self.n_streams = int(n)

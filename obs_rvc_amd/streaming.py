@@ -106,6 +106,10 @@ class NativeStreamingSession:
         elif int(self._L.rvc_session_set_params_stream(self._h, int(stream), int(pitch_shift), float(rms_mix_rate))) != 0:
             raise ValueError("stream out of range")
 
+    def set_formant_shift(self, semitones: float, stream: int = None) -> None:
+        """The plugin's resonance shift (obs-rvc/src/lib.rs:446-451): forwarded to the engine, whose per-stream values the session honours."""
+        self._engine.set_formant_shift(semitones, stream)
+
     def process_one_frame(self, input_sample: np.ndarray) -> np.ndarray:
         """One chunk of one stream (shape (sample_frame_size,)) or of every stream of the engine ((streams, sample_frame_size))."""
         C = self._C
