@@ -51,13 +51,32 @@ typedef struct rvc_debug_layer_spec {
     int x_grouped, res_grouped, y_ws;
 } rvc_debug_layer_spec;
 int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w, const float *bias, float *x, float *y, float *r, long long *geo);
+/* one transformer / recurrent op built with the helpers the models call (obs_rvc_amd/csrc/plan.hip add_attention, add_relpos_attention, add_layernorm,
+ * add_gru, with their rules and forcing hooks) and run `reps` times eagerly, or -- graph != 0 -- captured once and the graph replayed `reps` times.
+ * op: tensors x; y, weights w0; w1 in PyTorch layout (hd = E / heads):
+ *   0 MHA (ContentVec)     qkv [3E][T] (q, k, v rows); out [E][T]                  -
+ *   1 relative MHA (VITS)  qkv [3E][T]; out [E][T]                                 rel_k [2 window + 1][hd]; rel_v [2 window + 1][hd]
+ *   2 LayerNorm            x [C][T], normalised in place (y unused)                gamma [C]; beta [C]
+ *   3 bidirectional GRU    gi [6H][T]: gate pre-activations, b_ih included         weight_hh_l0 then weight_hh_l0_reverse, [2][3H][H];
+ *                          (forward r, z, n, then reverse r, z, n); out [2H][T]    bias_hh_l0 then _reverse, [2][3H]
+ * T is the length (R of the synthesizer, Tm of RMVPE).  x / y are the WHOLE allocations, as for rvc_debug_layer; geo[2][8] receives their geometry
+ * (x, y) as there.  status (GRU): receives every stream's status word, int[streams] (0 = fine).  With x == NULL only geo is filled.  0 = done, else
+ * an rvc_status (rvc_last_error_message); rvc_debug_last_kernel then names the variant ("attn_mfma2_qloop", "relpos_small", "ln_strip12", "gru_multi"). */
+typedef struct rvc_debug_op_spec {
+    int op, streams;
+    int E, heads, T, window, C, H;
+    int x_halo, y_halo;
+    int reps, graph;
+} rvc_debug_op_spec;
+int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, const float *w1, float *x, float *y, int *status, long long *geo);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);
 void rvc_debug_autotune_reset(void);
 /* weight slabs alive on a device: count and bytes (obs_rvc_amd/csrc/plan.hip, wmalloc) */
 int rvc_debug_weight_slabs(int device, int *count, size_t *bytes);
-/* the kernel the planner chose for the last rvc_debug_conv*_check / rvc_debug_layer launch ("reg", "g32", "c32s", ...) */
+/* the kernel the planner chose for this thread's last rvc_debug_conv*_check / rvc_debug_layer launch ("reg", "g32", "c32s", ...), or the variant of
+ * its last rvc_debug_op */
 const char *rvc_debug_last_kernel(void);
 /* host only: the formant resampler's full filter table h[n][K] (o -> n, K = 2 w + o; obs_rvc_amd/csrc/formant.hip.h) as fp32.  *width = K;
  * returns 0, 1 when cap < n K (nothing written to out), -1 for bad arguments */

@@ -31,7 +31,7 @@ static void init_kernel_attrs()
     int dev = 0; HIPCHK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(mu);
     if (dev >= 0 && dev < 64) { if (done[dev]) return; done[dev] = true; }
-    plan_kernel_attrs(); cv_kernel_attrs(); rmvpe_kernel_attrs(); synth_kernel_attrs(); retrieval_kernel_attrs();
+    plan_kernel_attrs(); retrieval_kernel_attrs();
 }
 
 static void init_constants(rvc_engine *e)
@@ -1500,14 +1500,23 @@ double rvc_debug_conv2d_check(rvc_engine *e, int M, int Cin, int H, int W, int s
 
 // test aid: one convolution layer as the models build it (include/rvc_mi355x_debug.h, tests/test_gpu_layers.py).  The caller owns every float of the
 // tensors' allocations: what the layer must not touch is compared bit for bit afterwards.
+// the whole allocation of a test aid's tensor: its start and geo = (size, offset of element (0, 0, 0), C, T, ld, bs, cs, H)
+struct DebugGeo { float *base = nullptr; long long g[8] = {0, 0, 0, 0, 0, 0, 0, 1}; };
+static DebugGeo debug_geo1(const T1 &t)
+{
+    DebugGeo q; const size_t gd = t1_guard(t.ld);
+    q.base = t.p - gd - t.halo; q.g[0] = (long long)t.B * t.bs + 2 * (long long)gd; q.g[1] = (long long)gd + t.halo; q.g[2] = t.C; q.g[3] = t.T; q.g[4] = t.ld; q.g[5] = t.bs; q.g[6] = t.ld;
+    return q;
+}
+
 int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w, const float *bias, float *x, float *y, float *r, long long *geo)
 {
     return (int)guarded(e, [&]() {
         if (!s || !geo || s->streams < 1 || s->form < 0 || s->form > 4 || ((s->form == 2 || s->form == 3) && (s->n < 1 || s->n > 4))) throw ShapeError("layer spec");
         const int B = s->streams, form = s->form, n = form == 3 ? 2 : s->n;
         Plan pl; pl.B = B;
-        struct Geo { float *base = nullptr; long long g[8] = {0, 0, 0, 0, 0, 0, 0, 1}; };
-        auto g1 = [](const T1 &t) { Geo q; const size_t gd = t1_guard(t.ld); q.base = t.p - gd - t.halo; q.g[0] = (long long)t.B * t.bs + 2 * (long long)gd; q.g[1] = (long long)gd + t.halo; q.g[2] = t.C; q.g[3] = t.T; q.g[4] = t.ld; q.g[5] = t.bs; q.g[6] = t.ld; return q; };
+        using Geo = DebugGeo;
+        auto g1 = debug_geo1;
         auto g2 = [](const T2 &t) { Geo q; const size_t gd = t2_guard(t.ld); q.base = t.p - gd - t.ld - 1; q.g[0] = (long long)t.B * t.bs + 2 * (long long)gd; q.g[1] = (long long)gd + t.ld + 1; q.g[2] = t.C; q.g[3] = t.W; q.g[4] = t.ld; q.g[5] = t.bs; q.g[6] = t.cs; q.g[7] = t.H; return q; };
         Geo gx, gy, gr;
         T1 x1, y1, r1; T2 x2, y2, r2;
@@ -1584,6 +1593,78 @@ int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w
         HIPCHK(hipMemcpy(x, gx.base, (size_t)gx.g[0] * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(y, gy.base, (size_t)gy.g[0] * 4, hipMemcpyDeviceToHost));
         if (gr.base) HIPCHK(hipMemcpy(r, gr.base, (size_t)gr.g[0] * 4, hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
+// test aid: one attention / LayerNorm / GRU op as the models build it (include/rvc_mi355x_debug.h, tests/test_gpu_ops.py).  As for rvc_debug_layer, the caller
+// owns every float of the tensors' allocations.
+int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, const float *w1, float *x, float *y, int *status, long long *geo)
+{
+    return (int)guarded(e, [&]() {
+        if (!s || !geo || s->streams < 1 || s->op < 0 || s->op > 3 || s->T < 1 || s->reps < 1 || s->x_halo < 0 || s->y_halo < 0) throw ShapeError("op spec");
+        if ((s->op <= 1 && (s->E < 1 || s->heads < 1 || s->E % s->heads)) || (s->op == 1 && s->window < 0) || (s->op == 2 && s->C < 1) || (s->op == 3 && s->H < 1))
+            throw ShapeError("op spec");
+        const int B = s->streams, op = s->op;
+        Plan pl; pl.B = B;
+        T1 x1, y1;
+        if (op <= 1) { x1 = make_t1(pl.arena, B, 3 * s->E, s->T, s->x_halo); y1 = make_t1(pl.arena, B, s->E, s->T, s->y_halo); }
+        else if (op == 2) x1 = make_t1(pl.arena, B, s->C, s->T, s->x_halo);
+        else { x1 = make_t1(pl.arena, B, 6 * s->H, s->T, s->x_halo); y1 = make_t1(pl.arena, B, 2 * s->H, s->T, s->y_halo); }
+        const DebugGeo gx = debug_geo1(x1), gy = op == 2 ? DebugGeo() : debug_geo1(y1);
+        for (int i = 0; i < 8; i++) { geo[i] = gx.g[i]; geo[8 + i] = gy.g[i]; }
+        if (!x) return RVC_OK;
+        if ((op != 2 && !y) || (op != 0 && (!w0 || !w1)) || (op == 3 && !status)) throw ShapeError("op buffers");
+        HIPCHK(hipMemcpy(gx.base, x, (size_t)gx.g[0] * 4, hipMemcpyHostToDevice));
+        if (gy.base) HIPCHK(hipMemcpy(gy.base, y, (size_t)gy.g[0] * 4, hipMemcpyHostToDevice));
+        std::vector<float *> wts;          // device copies of the weights, freed on every exit
+        int *d_status = nullptr;
+        try {
+            if (op == 0) add_attention(pl, x1, y1, s->heads);
+            else if (op == 1) {
+                const size_t n = (size_t)(2 * s->window + 1) * (s->E / s->heads);
+                wts.push_back(upload_f(w0, n)); wts.push_back(upload_f(w1, n));
+                add_relpos_attention(pl, x1, y1, s->heads, wts[0], wts[1], s->window);
+            } else if (op == 2) {
+                wts.push_back(upload_f(w0, (size_t)s->C)); wts.push_back(upload_f(w1, (size_t)s->C));
+                add_layernorm(pl, x1, wts[0], wts[1]);
+            } else {
+                const int H = s->H;
+                const float *whh_dir[2] = {w0, w0 + (size_t)3 * H * H};
+                std::vector<float> wt, wr;
+                gru_prep_whh(whh_dir, H, wt, wr);
+                wts.push_back(upload_f(wt)); wts.push_back(upload_f(wr)); wts.push_back(upload_f(w1, (size_t)6 * H));
+                d_status = (int *)pl.arena.alloc((size_t)B * sizeof(int));
+                HIPCHK(hipMemset(d_status, 0, (size_t)B * sizeof(int)));
+                add_gru(pl, x1, y1, H, wts[1], wts[0], wts[2], d_status, 1);
+            }
+            HIPCHK(hipDeviceSynchronize());
+            if (s->graph) {
+                hipGraph_t g; hipGraphExec_t ge;
+                HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+                for (auto &o : pl.ops.v) o(e->stream);
+                HIPCHK(hipStreamEndCapture(e->stream, &g));
+                const hipError_t ie = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+                (void)hipGraphDestroy(g);
+                HIPCHK(ie);
+                hipError_t le = hipSuccess;
+                for (int r = 0; r < s->reps && le == hipSuccess; r++) le = hipGraphLaunch(ge, e->stream);
+                const hipError_t se = hipStreamSynchronize(e->stream);
+                (void)hipGraphExecDestroy(ge);
+                HIPCHK(le); HIPCHK(se);
+            } else {
+                for (int r = 0; r < s->reps; r++) for (auto &o : pl.ops.v) o(e->stream);
+                HIPCHK(hipStreamSynchronize(e->stream));
+            }
+            HIPCHK(hipGetLastError());
+        } catch (...) {
+            for (float *p : wts) wfree(p);
+            throw;
+        }
+        for (float *p : wts) wfree(p);
+        HIPCHK(hipMemcpy(x, gx.base, (size_t)gx.g[0] * 4, hipMemcpyDeviceToHost));
+        if (gy.base) HIPCHK(hipMemcpy(y, gy.base, (size_t)gy.g[0] * 4, hipMemcpyDeviceToHost));
+        if (d_status) HIPCHK(hipMemcpy(status, d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
         return RVC_OK;
     });
 }

@@ -302,7 +302,7 @@ struct Plan {
 // ---- planner entry points (plan.hip) ----
 extern unsigned long long *g_kprobe;      // tuning build (-DRVC_KPROBE): destination of the per-wave phase stamps
 extern int g_last_waves, g_last_wgs, g_ncu;
-extern char g_last_kernel[16];          // family of the most recently queued implicit-GEMM launch ("reg", "g32", "c32s", ...)
+extern thread_local char g_last_kernel[32];      // this thread's most recently queued launch: implicit-GEMM family ("reg", "g32", "c32s", ...) or op variant ("attn_mfma2", "ln_strip12", ...)
 void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phases, bool final_out = false);
 // one GEMM-class launch of the planner (description, FLOPs, launch shape, profile slot, final_out): launch(q, ea, eb, stream) gets the IgemmP to use and the
 // slot's events.  Defined and instantiated in plan.hip (the body is inlined into the op, as lean as a hand-written one)
@@ -316,11 +316,18 @@ void add_convT1d(Plan &pl, const ConvW &cw, const T1 &x, const T1 &y, int pad, C
 void add_conv2d(Plan &pl, const ConvW &cw, const T2 &x, const T2 &y, ConvOpts o = ConvOpts());
 void add_convT2d(Plan &pl, const ConvW &cw, const T2 &x, const T2 &y, ConvOpts o = ConvOpts());
 void add_layernorm(Plan &pl, const T1 &x, const float *g, const float *b);
+// multi-head self-attention over qkv [B][3E][ld] (q, k, v rows) into out [B][E][ld], scale 1/sqrt(head size): ContentVec (plain) and the synthesizer's
+// text encoder (relative positions: rel_k / rel_v [2 window + 1][head size]).  Kernel variants and their test hooks: plan.hip
+void add_attention(Plan &pl, const T1 &qkv, const T1 &out, int heads);
+void add_relpos_attention(Plan &pl, const T1 &qkv, const T1 &out, int heads, const float *rel_k, const float *rel_v, int window);
+// bidirectional GRU recurrence: gi [B][6H][ld] gate pre-activations (b_ih included) -> out [B][2H][ld]; whh / whhT / bhh: gru_prep_whh layouts (device);
+// status: per-stream status words (stride status_stride ints), raised by the multi-workgroup kernel on a hand-off timeout
+void add_gru(Plan &pl, const T1 &gi, const T1 &out, int H, const float *whh, const float *whhT, const float *bhh, int *status, int status_stride);
 void add_stamp(Plan &pl, const char *name);
 void add_tap(Plan &pl, const char *name, const T1 &t);
 void add_tap2(Plan &pl, const char *name, const T2 &t);
 void plan_kernel_attrs();                 // per-device function attributes of the kernels each unit launches
-void cv_kernel_attrs(); void rmvpe_kernel_attrs(); void synth_kernel_attrs(); void retrieval_kernel_attrs();
+void retrieval_kernel_attrs();
 
 // ---------------------------------------------------------------------------------------
 // models
@@ -442,6 +449,18 @@ static inline std::vector<float> rm_block_panel(const float *w, int co, int ci, 
                 }
     return pk;
 }
+// the recurrent weights of a bidirectional GRU (PyTorch weight_hh_l0 / _reverse, [3H][H] each, gates r, z, n) in the two layouts of the kernels:
+// whhT [2][H][3H] (gru_kernel: lanes read consecutive rows) and whh [2][3H][H] row-major (gru_multi_kernel)
+static inline void gru_prep_whh(const float *const whh_dir[2], int H, std::vector<float> &whhT, std::vector<float> &whh)
+{
+    whhT.resize((size_t)2 * H * 3 * H); whh.resize((size_t)2 * 3 * H * H);
+    for (int d = 0; d < 2; d++) {
+        const float *w = whh_dir[d];
+        for (int r = 0; r < 3 * H; r++) for (int j = 0; j < H; j++) whhT[((size_t)d * H + j) * 3 * H + r] = w[(size_t)r * H + j];
+        memcpy(&whh[(size_t)d * 3 * H * H], w, (size_t)3 * H * H * sizeof(float));
+    }
+}
+
 struct ModelRM {
     int en_out, levels, n_blocks, inter_layers, n_mels, gru_hidden, n_out;
     float bn_scale, bn_shift;
@@ -500,21 +519,20 @@ struct ModelRM {
         }
         cnn = prep_conv(b.w("rm.cnn.w"), b.w("rm.cnn.b"), 3, en_out, 9, 1);
         const int H = gru_hidden, I = 3 * n_mels;
-        std::vector<float> wih((size_t)6 * H * I), bih((size_t)6 * H), wt((size_t)2 * H * 3 * H), bh((size_t)6 * H);
+        std::vector<float> wih((size_t)6 * H * I), bih((size_t)6 * H), bh((size_t)6 * H);
         const char *sfx[2] = {"f", "b"};
+        const float *whh_dir[2];
         for (int d = 0; d < 2; d++) {
             memcpy(&wih[(size_t)d * 3 * H * I], b.w(std::string("rm.gru.w_ih_") + sfx[d]), (size_t)3 * H * I * 4);
             memcpy(&bih[(size_t)d * 3 * H], b.w(std::string("rm.gru.b_ih_") + sfx[d]), (size_t)3 * H * 4);
             memcpy(&bh[(size_t)d * 3 * H], b.w(std::string("rm.gru.b_hh_") + sfx[d]), (size_t)3 * H * 4);
-            const float *whh = b.w(std::string("rm.gru.w_hh_") + sfx[d]);
-            for (int r = 0; r < 3 * H; r++) for (int j = 0; j < H; j++) wt[((size_t)d * H + j) * 3 * H + r] = whh[(size_t)r * H + j];
+            whh_dir[d] = b.w(std::string("rm.gru.w_hh_") + sfx[d]);
         }
         gru_ih = prep_conv(wih.data(), bih.data(), 6 * H, I, 1, 1);
-        whhT = upload_f(wt); bhh = upload_f(bh);
         {
-            std::vector<float> wr((size_t)2 * 3 * H * H);
-            for (int d = 0; d < 2; d++) memcpy(&wr[(size_t)d * 3 * H * H], b.w(std::string("rm.gru.w_hh_") + sfx[d]), (size_t)3 * H * H * 4);
-            whh = upload_f(wr);
+            std::vector<float> wt, wr;
+            gru_prep_whh(whh_dir, H, wt, wr);
+            whhT = upload_f(wt); bhh = upload_f(bh); whh = upload_f(wr);
         }
         fc = prep_conv(b.w("rm.fc.w"), b.w("rm.fc.b"), n_out, 2 * H, 1, 1);
         weight_bytes = b.bytes();

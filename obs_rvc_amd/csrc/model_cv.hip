@@ -74,10 +74,6 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
     if (!fuse_ln) add_layernorm(pl, h2, m.encln_g, m.encln_b);      // (folded: layer 0 consumes the not yet normalised sum, see below)
     add_tap(pl, fuse_ln ? "cv.pos.raw" : "cv.pos", h2);
     T1 qkv = make_t1(A, B, 3 * E, T, 0), att = make_t1(A, B, E, T, 0), ff = make_t1(A, B, m.ffn, T, 0);
-    const int hd = E / m.heads, Tp = T | 1;
-    const size_t attn_lds = ((size_t)((hd * Tp + 3) & ~3) + 16 * Tp + 16 * hd) * sizeof(float);
-    if (attn_lds > 160 * 1024) throw ShapeError("ContentVec attention: window too long for the LDS-resident kernel (T <= ~490 at head size 64)");
-    HIPCHK(hipFuncSetAttribute((const void *)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // One stream: the 2 LayerNorm launches of a layer are folded into the GEMMs around them (h2 then holds the NOT yet normalised sum;
     // `raw` says so, with the pending LayerNorm's scale / shift and the buffer its column statistics are published in)
     bool raw = fuse_ln; const float *raw_g = m.encln_g, *raw_b = m.encln_b; float *raw_st = nullptr;
@@ -89,19 +85,7 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
             else add_conv1d(pl, Ly.qkv, h2, qkv, 1, 0, 1);
         } else
         { ConvOpts o; o.bf3 = pl.bf3; add_conv1d(pl, Ly.qkv, h2, qkv, 1, 0, 1, o); }
-        AttnP ap{}; ap.qkv = qkv.p; ap.out = att.p; ap.E = E; ap.T = T; ap.heads = m.heads; ap.cs = qkv.ld; ap.bs = qkv.bs; ap.o_cs = att.ld; ap.o_bs = att.bs;
-        ap.scale = 1.0f / sqrtf((float)hd); ap.rel_k = nullptr; ap.rel_v = nullptr; ap.window = 0;
-        dim3 ag(m.heads * ((T + 15) / 16), B);
-        if (B >= 16 && hd == 64 && T <= 256 && !tune_env("RVC_ATTN_VALU") && !tune_env("RVC_NO_QLOOP")) { ap.qloop = 1; ag = dim3(m.heads, B); }
-        if (hd == 64 && T <= 128 && !tune_env("RVC_ATTN_VALU")) {
-            const size_t mfma_lds = ((size_t)16 * (2 * 64 + 1) + 128) * sizeof(float);
-            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL((attention_mfma_kernel<64, 2>), ag, dim3(256), mfma_lds, s, ap); });
-        } else if (hd == 64 && T <= 256 && !tune_env("RVC_ATTN_VALU")) {
-            const size_t mfma_lds = ((size_t)16 * (4 * 64 + 1) + 128) * sizeof(float);
-            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL((attention_mfma_kernel<64, 4>), ag, dim3(256), mfma_lds, s, ap); });
-        } else {
-            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(attention_kernel, ag, dim3(256), attn_lds, s, ap); });
-        }
+        add_attention(pl, qkv, att, m.heads);
         if (fuse_ln) {
             float *st_1 = A.floats((size_t)2 * T + 16);
             {   // attention output projection + residual; the residual is LayerNorm2 of the previous layer when that one is still pending
@@ -129,9 +113,4 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
     return out;
 }
 
-
-void cv_kernel_attrs()
-{
-    HIPCHK(hipFuncSetAttribute((const void *)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
 }  // namespace rvc

@@ -224,38 +224,7 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
         pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(gru_input_kernel, grid, dim3(256), 0, s, cn.p, cn.ld, cn.cs, cn.bs, feat.p, feat.ld, feat.bs, Tm, nm); });
     }
     add_conv1d(pl, m.gru_ih, feat, gi, 1, 0, 1);
-    {
-        if (3 * Hg > 1024) throw ShapeError("GRU hidden size too large for the single-workgroup recurrence");
-        int threads = (3 * Hg + 63) / 64 * 64;
-        size_t lds = (size_t)4 * Hg * sizeof(float);
-        float *wt = m.whhT, *bh = m.bhh;
-        dim3 grid(2, B);
-        if (Hg == 256 && B <= 8 && Tm <= 256 && !tune_env("RVC_GRU_GENERIC")) {
-            // few streams: spread each direction over 8 CUs with W_hh resident in LDS (granule hand-off per step)
-            GruMultiP gp{}; gp.gi = gi.p; gp.gi_cs = gi.ld; gp.gi_bs = gi.bs; gp.whh = m.whh; gp.bhh = m.bhh; gp.out = gout.p; gp.o_cs = gout.ld; gp.o_bs = gout.bs;
-            gp.Tm = Tm; gp.status = &e->d_state[0].status; gp.status_stride = (int)(sizeof(StreamState) / sizeof(int));
-            const size_t gbytes = (size_t)B * 2 * 2 * 256 * sizeof(unsigned long long);
-            gp.gran = (unsigned long long *)pl.arena.alloc(gbytes);
-            const size_t lds3 = (size_t)(256 + 96 + (size_t)Tm * 96) * sizeof(float);      // h, gate pre-activations, this slice's input gates for all steps
-            const dim3 g3(8, 2, B);
-            // eager launches: the tags advance by Tm per launch (host-side counter of this plan), so the granules of earlier chunks are stale by construction and
-            // the buffer is zeroed only in front of the plan's first launch (and when the 32-bit tag space runs out); a captured graph bakes its arguments and keeps the
-            // memset node + epoch 0
-            auto next_epoch = std::make_shared<unsigned>(0u);
-            auto dirty = std::make_shared<bool>(true);
-            pl.ops.push_back([=](hipStream_t s) {
-                GruMultiP g2 = gp;
-                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                (void)hipStreamIsCapturing(s, &cs);
-                if (cs != hipStreamCaptureStatusNone) { HIPCHK(hipMemsetAsync(g2.gran, 0, gbytes, s)); g2.epoch = 0; *dirty = true; }
-                else if (*dirty || *next_epoch > 0xFFF00000u) { HIPCHK(hipMemsetAsync(g2.gran, 0, gbytes, s)); g2.epoch = 0; *next_epoch = (unsigned)Tm; *dirty = false; }
-                else { g2.epoch = *next_epoch; *next_epoch += (unsigned)Tm; }
-                hipLaunchKernelGGL(gru_multi_kernel, g3, dim3(384), lds3, s, g2);
-            });
-        } else {
-            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(gru_kernel, grid, dim3(threads), lds, s, gi.p, gi.ld, gi.bs, wt, bh, gout.p, gout.ld, gout.bs, Hg, Tm); });
-        }
-    }
+    add_gru(pl, gi, gout, Hg, m.whh, m.whhT, m.bhh, &e->d_state[0].status, (int)(sizeof(StreamState) / sizeof(int)));
     { ConvOpts o; o.act = ACT_SIGMOID; add_conv1d(pl, m.fc, gout, sal, 1, 0, 1, o); }
     if (pl.with_taps) { add_tap(pl, "rm.sal_ct", sal); add_tap(pl, "rm.gru_ct", gout); add_tap(pl, "rm.cnn_ct", feat); } else add_stamp(pl, "rm.sal");
     return sal;
@@ -289,9 +258,4 @@ void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update
     pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(pitch_post_kernel, dim3(B), dim3(1024), 0, s, pp); });
 }
 
-
-void rmvpe_kernel_attrs()
-{
-    HIPCHK(hipFuncSetAttribute((const void *)gru_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
 }  // namespace rvc

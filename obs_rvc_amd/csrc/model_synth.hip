@@ -71,9 +71,6 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         }
         add_tap(pl, "sy.emb", x);
         T1 qkv = make_t1(A, B, 3 * H, R, 0), att = make_t1(A, B, H, R, 0), ff = make_t1(A, B, F, R, HALO);
-        const int kc = H / m.heads, Tp = R | 1;
-        const size_t attn_lds = ((size_t)((kc * Tp + 3) & ~3) + 16 * Tp + 16 * kc) * sizeof(float);
-        if (attn_lds > 160 * 1024) throw ShapeError("synth attention: return_length too long for the LDS-resident kernel");
         // one stream: the second LayerNorm of every encoder layer is folded into the next projection (see build_contentvec)
         const bool fuse_ln = B <= LN_FOLD_MAX_STREAMS && m.has_folded && !pl.plain_plan && !test_opt("RVC_NO_LN_FUSE");
         bool raw = false; const float *raw_g = nullptr, *raw_b = nullptr; float *raw_st = nullptr;
@@ -81,23 +78,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
             ModelSY::Layer &Ly = m.layers[l];
             if (raw) { raw_st = A.floats((size_t)2 * R + 16); ConvOpts o; o.ln_wsum = Ly.qkv_wsum; o.ln_stats_out = raw_st; o.ln_rows = H; add_conv1d(pl, Ly.qkv_f, x, qkv, 1, 0, 1, o); }
             else add_conv1d(pl, Ly.qkv, x, qkv, 1, 0, 1);
-            AttnP ap{}; ap.qkv = qkv.p; ap.out = att.p; ap.E = H; ap.T = R; ap.heads = m.heads; ap.cs = qkv.ld; ap.bs = qkv.bs; ap.o_cs = att.ld; ap.o_bs = att.bs;
-            ap.scale = 1.0f / sqrtf((float)kc); ap.rel_k = Ly.rel_k; ap.rel_v = Ly.rel_v; ap.window = m.window;
-            const size_t small_lds = ((size_t)2 * kc * Tp + 2 * (2 * m.window + 1) * kc + 4 * kc + 4 * 64) * sizeof(float);
-            // the matrix-core form (VALU form at one stream: 12.4 us per layer of dependent LDS reads; round 6: at every stream count -- 21.5 -> ~12 us per launch at 64
-            // streams, step 5 / 8 / 16 / 64 streams 4.585 / 6.156 / 11.03 / 34.24 -> 4.577 / 6.145 / 11.00 / 34.20 ms; test hook RVC_RELPOS_MFMA_MAX = 4: the round-5 rule)
-            const int a_tp = R | 1, a_nr = 2 * m.window + 1, a_jf = (R + 15) / 16, a_pw = (a_nr + 15) / 16 * 16, a_nrp = (a_nr + 3) / 4 * 4;
-            const size_t mfma_lds = ((size_t)kc * 16 + 2 * (size_t)kc * a_tp + (size_t)a_pw * kc + (size_t)a_nrp * kc + 16 * a_jf * 16 + 2 * 16 * a_pw + 64) * sizeof(float);
-            if (B <= test_opt_int("RVC_RELPOS_MFMA_MAX", 1 << 20) && R <= 64 && kc % 16 == 0 && mfma_lds <= 160 * 1024 && !tune_env("RVC_NO_SMALL_ATTN") && !tune_env("RVC_ATTN_VALU") && !tune_env("RVC_NO_SMALL_ATTN_MFMA")) {
-                dim3 ag(m.heads * a_jf, B);
-                pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(relpos_attention_mfma_kernel, ag, dim3(256), mfma_lds, s, ap); });
-            } else if (R <= 64 && small_lds <= 160 * 1024 && !tune_env("RVC_NO_SMALL_ATTN")) {
-                dim3 ag(m.heads * ((R + 3) / 4), B);
-                pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(relpos_attention_small_kernel, ag, dim3(256), small_lds, s, ap); });
-            } else {
-                dim3 ag(m.heads * ((R + 15) / 16), B);
-                pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(attention_kernel, ag, dim3(256), attn_lds, s, ap); });
-            }
+            add_relpos_attention(pl, qkv, att, m.heads, Ly.rel_k, Ly.rel_v, m.window);
             {
                 ConvOpts o; o.res = x.p; o.res_cs = x.ld; o.res_bs = x.bs;
                 if (raw) { o.ln_stats_in = raw_st; o.ln_g = raw_g; o.ln_b = raw_b; }
@@ -295,11 +276,4 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
     add_stamp(pl, "sy.audio");
 }
 
-
-void synth_kernel_attrs()
-{
-    HIPCHK(hipFuncSetAttribute((const void *)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)relpos_attention_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)relpos_attention_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
 }  // namespace rvc

@@ -13,7 +13,8 @@ static const TestHook kTestHooks[] = {
     {"RVC_KNN_NO_GEMM", false}, {"RVC_KNN_EXHAUSTIVE", false}, {"RVC_STAMPS", false}, {"RVC_SERIAL_BRANCHES", false}, {"RVC_NO_WN_COMPOSE", false},
     {"RVC_KNN_LOSE_TICKET", false}, {"RVC_FORCE_G2W", true}, {"RVC_F0_XCDS", false}, {"RVC_CONV32S", true}, {"RVC_CONV32S_TILE", true},
     {"RVC_G32L", true}, {"RVC_G32L_TALL", true}, {"RVC_G32L_TAB", true}, {"RVC_CONV32S_BUF", true}, {"RVC_FORCE_CHOICE", true},
-    {"RVC_G32L_PANEL", true}, {"RVC_MEAN3", false}, {"RVC_RM_FUSE", false}, {"RVC_G2W_LN", false}, {"RVC_RELPOS_MFMA_MAX", false}
+    {"RVC_G32L_PANEL", true}, {"RVC_MEAN3", false}, {"RVC_RM_FUSE", false}, {"RVC_G2W_LN", false}, {"RVC_RELPOS_MFMA_MAX", false},
+    {"RVC_ATTN_KERNEL", false}, {"RVC_RELPOS_KERNEL", false}, {"RVC_LN_KERNEL", false}, {"RVC_GRU_KERNEL", false}
 };
 std::atomic<unsigned> g_opt_gen{0};       // bumped by every rvc_debug_option call: plans built under another generation are dropped (engine.hip get_plan)
 static std::mutex g_opt_mu;
@@ -262,7 +263,7 @@ void merge_convs(const std::vector<ConvW *> &cs)
 
 unsigned long long *g_kprobe = nullptr;   // tuning build (-DRVC_KPROBE): destination of the per-wave phase stamps
 int g_last_waves = 0, g_last_wgs = 0;
-char g_last_kernel[16] = "";
+thread_local char g_last_kernel[32] = "";
 static void note_kernel(const char *d) { size_t i = 0; for (; i < sizeof(g_last_kernel) - 1 && d[i] && d[i] != ' '; i++) g_last_kernel[i] = d[i]; g_last_kernel[i] = 0; }
 
 // Every GEMM-class launch of the planner is queued here: its description (rvc_debug_profile_dump, rvc_debug_last_kernel), the plan's FLOP count, the
@@ -1262,35 +1263,167 @@ void add_convT2d(Plan &pl, const ConvW &cw, const T2 &x, const T2 &y, ConvOpts o
     queue_igemm(pl, p, x.B, koff, ph);
 }
 
+// The transformer and recurrent ops.  Each helper decides its kernel variant by the production rules, records it (rvc_debug_last_kernel: "ln_strip12",
+// "attn_mfma2_qloop", "relpos_small", "gru_multi", ...) and queues it.  A forcing test hook (RVC_LN_KERNEL, RVC_ATTN_KERNEL, RVC_RELPOS_KERNEL,
+// RVC_GRU_KERNEL = a variant name without the family prefix) replaces the rules' choice, but only by a variant whose eligibility -- what the kernel
+// itself needs of the shape -- holds: otherwise the build fails with a ShapeError and nothing is queued.
+static std::string op_variant(const char *hook, const char *family, const std::string &rule, const std::vector<std::pair<const char *, bool>> &eligible)
+{
+    std::string v = rule;
+    if (const char *f = test_opt(hook)) {
+        v = f;
+        bool known = false, ok = false;
+        for (const auto &e : eligible) if (v == e.first) { known = true; ok = e.second; }
+        if (!known) throw ShapeError(std::string(hook) + ": unknown variant '" + v + "'");
+        if (!ok) throw ShapeError(std::string(hook) + ": variant '" + v + "' is not eligible for this shape");
+    }
+    snprintf(g_last_kernel, sizeof g_last_kernel, "%s_%s", family, v.c_str());
+    return v;
+}
+
 void add_layernorm(Plan &pl, const T1 &x, const float *g, const float *b)
 {
     dim3 grid((x.T + 3) / 4, x.B);
     if (x.C > 1024) throw ShapeError("layernorm: more than 1024 channels");
-    const bool small = x.C <= 256;
-    // many streams: 16-column strips held in registers (float4 rows; needs 16-byte aligned rows, which every plan tensor has: ld and
-    // halo are multiples of 4).  Reading the padding columns behind T is safe (inside the row), they are never written.
-    if (x.B >= 16 && x.ld % 4 == 0 && x.halo % 4 == 0 && ((x.T + 3) / 4 * 4 <= x.ld - x.halo) && !tune_env("RVC_NO_LN_STRIP")) {
+    const int nr = (x.C + 63) / 64;
+    // strips: float4 rows, so 16-byte aligned rows (every plan tensor has them: make_t1 makes ld and halo multiples of 4); reading the padding columns
+    // behind T is safe (inside the row, or the guard zone behind the last one), they are never written.  Tile: the [C][33] tile within 150 KB of LDS
+    const bool strip_ok = x.ld % 4 == 0 && x.halo % 4 == 0 && ((x.T + 3) / 4 * 4 <= x.ld - x.halo);
+    const bool tile_ok = (size_t)x.C * 33 * 4 <= 150 * 1024;
+    // many streams: 16-column strips held in registers.  The tile kernel is taken only where strips are not eligible -- no plan tensor
+    std::string rule = x.C <= 256 ? "ct4" : "ct16";
+    if (x.B >= 16 && strip_ok && !tune_env("RVC_NO_LN_STRIP")) rule = nr <= 4 ? "strip4" : (nr <= 12 ? "strip12" : "strip16");
+    else if (x.B >= 16 && x.C > 256 && tile_ok && !tune_env("RVC_NO_LN_TILE")) rule = "tile";
+    const std::string v = op_variant("RVC_LN_KERNEL", "ln", rule, {{"ct4", x.C <= 256}, {"ct16", true}, {"tile", tile_ok}, {"strip4", strip_ok && nr <= 4},
+                                                                  {"strip12", strip_ok && nr <= 12}, {"strip16", strip_ok}});
+    if (v.compare(0, 5, "strip") == 0) {
         // grid x = stream, y = strip: workgroup (b, strip) runs on XCD (strip * B + b) % 8 = b % 8 when B is a multiple of 8, so the two
         // 64-byte halves of every 128-byte line (adjacent strips of one stream) are fetched by the same XCD's L2, once
         dim3 sg(x.B, (x.T + 15) / 16);
-        const int nr = (x.C + 63) / 64;
+        const int snr = v == "strip4" ? 4 : (v == "strip12" ? 12 : 16);
         pl.ops.push_back([=](hipStream_t s) {
-            if (nr <= 4) hipLaunchKernelGGL((layernorm_strip_kernel<4>), sg, dim3(256), 0, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs);
-            else if (nr <= 12) hipLaunchKernelGGL((layernorm_strip_kernel<12>), sg, dim3(256), 0, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs);
+            if (snr == 4) hipLaunchKernelGGL((layernorm_strip_kernel<4>), sg, dim3(256), 0, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs);
+            else if (snr == 12) hipLaunchKernelGGL((layernorm_strip_kernel<12>), sg, dim3(256), 0, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs);
             else hipLaunchKernelGGL((layernorm_strip_kernel<16>), sg, dim3(256), 0, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs);
         });
         return;
     }
-    if (x.B >= 16 && x.C > 256 && (size_t)x.C * 33 * 4 <= 150 * 1024 && !tune_env("RVC_NO_LN_TILE")) {
+    if (v == "tile") {
         dim3 tg((x.T + 31) / 32, x.B);
         const size_t lds = (size_t)x.C * 33 * sizeof(float);
         pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(layernorm_tile_kernel, tg, dim3(256), lds, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs); });
         return;
     }
+    const bool small = v == "ct4";
     pl.ops.push_back([=](hipStream_t s) {
         if (small) hipLaunchKernelGGL((layernorm_ct_kernel<4>), grid, dim3(256), 0, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs);
         else hipLaunchKernelGGL((layernorm_ct_kernel<16>), grid, dim3(256), 0, s, x.p, x.p, g, b, x.C, x.T, x.ld, x.bs, x.ld, x.bs);
     });
+}
+
+static AttnP attn_params(const T1 &qkv, const T1 &out, int heads)
+{
+    AttnP ap{}; ap.qkv = qkv.p; ap.out = out.p; ap.E = out.C; ap.T = qkv.T; ap.heads = heads; ap.cs = qkv.ld; ap.bs = qkv.bs; ap.o_cs = out.ld; ap.o_bs = out.bs;
+    ap.scale = 1.0f / sqrtf((float)(out.C / heads)); ap.rel_k = nullptr; ap.rel_v = nullptr; ap.window = 0;
+    return ap;
+}
+static size_t attn_valu_lds(int hd, int T) { const int Tp = T | 1; return ((size_t)((hd * Tp + 3) & ~3) + 16 * Tp + 16 * hd) * sizeof(float); }
+
+// ContentVec: the matrix-core kernel up to T = 64 KF at head size 64 (KF = 2 / 4); many streams: one workgroup per (head, stream) walks all query
+// tiles (qloop).  Else the VALU kernel (K and V of a head LDS-resident).
+void add_attention(Plan &pl, const T1 &qkv, const T1 &out, int heads)
+{
+    const int B = qkv.B, E = out.C, T = qkv.T, hd = E / heads;
+    if (heads < 1 || E % heads || qkv.C != 3 * E || out.T != T || out.B != B) throw ShapeError("attention: inconsistent shapes");
+    const size_t attn_lds = attn_valu_lds(hd, T);
+    if (attn_lds > 160 * 1024) throw ShapeError("ContentVec attention: window too long for the LDS-resident kernel (T <= ~490 at head size 64)");
+    HIPCHK(hipFuncSetAttribute((const void *)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    AttnP ap = attn_params(qkv, out, heads);
+    std::string rule = "valu";
+    if (hd == 64 && T <= 256 && !tune_env("RVC_ATTN_VALU")) rule = std::string(T <= 128 ? "mfma2" : "mfma4") + (B >= 16 && !tune_env("RVC_NO_QLOOP") ? "_qloop" : "");
+    const bool m2 = hd == 64 && T <= 128, m4 = hd == 64 && T <= 256;
+    const std::string v = op_variant("RVC_ATTN_KERNEL", "attn", rule, {{"mfma2", m2}, {"mfma2_qloop", m2}, {"mfma4", m4}, {"mfma4_qloop", m4}, {"valu", true}});
+    dim3 ag(heads * ((T + 15) / 16), B);
+    if (v.find("_qloop") != std::string::npos) { ap.qloop = 1; ag = dim3(heads, B); }
+    if (v.compare(0, 5, "mfma2") == 0) {
+        const size_t mfma_lds = ((size_t)16 * (2 * 64 + 1) + 128) * sizeof(float);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL((attention_mfma_kernel<64, 2>), ag, dim3(256), mfma_lds, s, ap); });
+    } else if (v.compare(0, 5, "mfma4") == 0) {
+        const size_t mfma_lds = ((size_t)16 * (4 * 64 + 1) + 128) * sizeof(float);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL((attention_mfma_kernel<64, 4>), ag, dim3(256), mfma_lds, s, ap); });
+    } else {
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(attention_kernel, ag, dim3(256), attn_lds, s, ap); });
+    }
+}
+
+// synthesizer text encoder (VITS windowed relative positions): the matrix-core form (VALU form at one stream: 12.4 us per layer of dependent LDS reads;
+// round 6: at every stream count -- 21.5 -> ~12 us per launch at 64 streams, step 5 / 8 / 16 / 64 streams 4.585 / 6.156 / 11.03 / 34.24 -> 4.577 / 6.145 /
+// 11.00 / 34.20 ms; test hook RVC_RELPOS_MFMA_MAX = 4: the round-5 rule), the small-T VALU kernel, the generic kernel beyond T = 64
+void add_relpos_attention(Plan &pl, const T1 &qkv, const T1 &out, int heads, const float *rel_k, const float *rel_v, int window)
+{
+    const int B = qkv.B, H = out.C, R = qkv.T, kc = H / heads, Tp = R | 1;
+    if (heads < 1 || H % heads || qkv.C != 3 * H || out.T != R || out.B != B || window < 0) throw ShapeError("relative-position attention: inconsistent shapes");
+    const size_t attn_lds = attn_valu_lds(kc, R);
+    if (attn_lds > 160 * 1024) throw ShapeError("synth attention: return_length too long for the LDS-resident kernel");
+    AttnP ap = attn_params(qkv, out, heads);
+    ap.rel_k = rel_k; ap.rel_v = rel_v; ap.window = window;
+    const size_t small_lds = ((size_t)2 * kc * Tp + 2 * (2 * window + 1) * kc + 4 * kc + 4 * 64) * sizeof(float);
+    const int a_tp = R | 1, a_nr = 2 * window + 1, a_jf = (R + 15) / 16, a_pw = (a_nr + 15) / 16 * 16, a_nrp = (a_nr + 3) / 4 * 4;
+    const size_t mfma_lds = ((size_t)kc * 16 + 2 * (size_t)kc * a_tp + (size_t)a_pw * kc + (size_t)a_nrp * kc + 16 * a_jf * 16 + 2 * 16 * a_pw + 64) * sizeof(float);
+    const bool mfma_ok = R <= 64 && kc % 16 == 0 && mfma_lds <= 160 * 1024, small_ok = R <= 64 && small_lds <= 160 * 1024;
+    std::string rule = "valu";
+    if (B <= test_opt_int("RVC_RELPOS_MFMA_MAX", 1 << 20) && mfma_ok && !tune_env("RVC_NO_SMALL_ATTN") && !tune_env("RVC_ATTN_VALU") && !tune_env("RVC_NO_SMALL_ATTN_MFMA")) rule = "mfma";
+    else if (small_ok && !tune_env("RVC_NO_SMALL_ATTN")) rule = "small";
+    const std::string v = op_variant("RVC_RELPOS_KERNEL", "relpos", rule, {{"mfma", mfma_ok}, {"small", small_ok}, {"valu", true}});
+    if (v == "mfma") {
+        dim3 ag(heads * a_jf, B);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(relpos_attention_mfma_kernel, ag, dim3(256), mfma_lds, s, ap); });
+    } else if (v == "small") {
+        dim3 ag(heads * ((R + 3) / 4), B);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(relpos_attention_small_kernel, ag, dim3(256), small_lds, s, ap); });
+    } else {
+        dim3 ag(heads * ((R + 15) / 16), B);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(attention_kernel, ag, dim3(256), attn_lds, s, ap); });
+    }
+}
+
+// RMVPE's bidirectional GRU.  Few streams: each direction spread over 8 CUs with W_hh resident (gru_multi_kernel, granule hand-off per step; its
+// workgroups wait on each other, so it is never launched outside H = 256, B <= 8, Tm <= 256, forced or not).  Else one workgroup per direction.
+void add_gru(Plan &pl, const T1 &gi, const T1 &out, int Hg, const float *whh, const float *whhT, const float *bhh, int *status, int status_stride)
+{
+    const int B = gi.B, Tm = gi.T;
+    if (gi.C != 6 * Hg || out.C != 2 * Hg || out.T != Tm || out.B != B) throw ShapeError("GRU: inconsistent shapes");
+    if (3 * Hg > 1024) throw ShapeError("GRU hidden size too large for the single-workgroup recurrence");
+    const bool multi_ok = Hg == 256 && B <= 8 && Tm <= 256;
+    const std::string rule = multi_ok && !tune_env("RVC_GRU_GENERIC") ? "multi" : "generic";
+    const std::string v = op_variant("RVC_GRU_KERNEL", "gru", rule, {{"multi", multi_ok}, {"generic", true}});
+    if (v == "multi") {
+        GruMultiP gp{}; gp.gi = gi.p; gp.gi_cs = gi.ld; gp.gi_bs = gi.bs; gp.whh = whh; gp.bhh = bhh; gp.out = out.p; gp.o_cs = out.ld; gp.o_bs = out.bs;
+        gp.Tm = Tm; gp.status = status; gp.status_stride = status_stride;
+        const size_t gbytes = (size_t)B * 2 * 2 * 256 * sizeof(unsigned long long);
+        gp.gran = (unsigned long long *)pl.arena.alloc(gbytes);
+        const size_t lds3 = (size_t)(256 + 96 + (size_t)Tm * 96) * sizeof(float);      // h, gate pre-activations, this slice's input gates for all steps
+        const dim3 g3(8, 2, B);
+        // eager launches: the tags advance by Tm per launch (host-side counter of this plan), so the granules of earlier chunks are stale by construction and
+        // the buffer is zeroed only in front of the plan's first launch (and when the 32-bit tag space runs out); a captured graph bakes its arguments and keeps the
+        // memset node + epoch 0
+        auto next_epoch = std::make_shared<unsigned>(0u);
+        auto dirty = std::make_shared<bool>(true);
+        pl.ops.push_back([=](hipStream_t s) {
+            GruMultiP g2 = gp;
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            (void)hipStreamIsCapturing(s, &cs);
+            if (cs != hipStreamCaptureStatusNone) { HIPCHK(hipMemsetAsync(g2.gran, 0, gbytes, s)); g2.epoch = 0; *dirty = true; }
+            else if (*dirty || *next_epoch > 0xFFF00000u) { HIPCHK(hipMemsetAsync(g2.gran, 0, gbytes, s)); g2.epoch = 0; *next_epoch = (unsigned)Tm; *dirty = false; }
+            else { g2.epoch = *next_epoch; *next_epoch += (unsigned)Tm; }
+            hipLaunchKernelGGL(gru_multi_kernel, g3, dim3(384), lds3, s, g2);
+        });
+    } else {
+        const int threads = (3 * Hg + 63) / 64 * 64;
+        const size_t lds = (size_t)4 * Hg * sizeof(float);
+        const dim3 grid(2, B);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(gru_kernel, grid, dim3(threads), lds, s, gi.p, gi.ld, gi.bs, whhT, bhh, out.p, out.ld, out.bs, Hg, Tm); });
+    }
 }
 
 void add_stamp(Plan &pl, const char *name)
@@ -1353,6 +1486,10 @@ void add_conv1d_two(Plan &pl, const ConvW &c0, const ConvW &c1, const float *pai
 void plan_kernel_attrs()
 {
     HIPCHK(hipFuncSetAttribute((const void *)layernorm_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));   // + 1.3 KB static
+    HIPCHK(hipFuncSetAttribute((const void *)attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)relpos_attention_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)relpos_attention_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)gru_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     conv_tile_prepare_device();
     igemm2w_prepare_device();
 }
