@@ -108,6 +108,11 @@ extern "C" {
                               mix_rate: c_double) -> c_int;
     pub fn rvc_sola_step(e: *mut RvcEngine, output: *mut c_float, output_len: usize, sola_buffer: *mut c_float, sola_len: usize,
                          search: usize, frame: usize, frame_out: *mut c_float, sola_offset: *mut usize) -> c_int;
+    // the same step with a choice of crossfade (0 = linear, 1 = phase vocoder) and the session's input gate on host buffers
+    pub fn rvc_sola_step_x(e: *mut RvcEngine, output: *mut c_float, output_len: usize, sola_buffer: *mut c_float, sola_len: usize,
+                           search: usize, frame: usize, frame_out: *mut c_float, sola_offset: *mut usize, crossfade: c_int) -> c_int;
+    pub fn rvc_input_gate(e: *mut RvcEngine, hist3zc: *const c_float, chunk: *const c_float, n: usize, sample_rate: usize,
+                          threshold_db: c_double, out: *mut c_float, hist_out: *mut c_float) -> c_int;
     pub fn rvc_resampler_create(e: *mut RvcEngine, rate_in: usize, rate_out: usize, chunk_size_in: usize, out: *mut *mut RvcResampler) -> c_int;
     pub fn rvc_resampler_destroy(r: *mut RvcResampler);
     pub fn rvc_resampler_input_frames_next(r: *mut RvcResampler) -> usize;
@@ -122,6 +127,10 @@ extern "C" {
     pub fn rvc_session_frame_size(s: *mut RvcSession) -> usize;
     pub fn rvc_session_set_params(s: *mut RvcSession, pitch_shift: i32, rms_mix_rate: c_double);
     pub fn rvc_session_set_params_stream(s: *mut RvcSession, stream: c_int, pitch_shift: i32, rms_mix_rate: f64) -> c_int;
+    pub fn rvc_session_set_crossfade(s: *mut RvcSession, mode: c_int) -> c_int;
+    pub fn rvc_session_set_crossfade_stream(s: *mut RvcSession, stream: c_int, mode: c_int) -> c_int;
+    pub fn rvc_session_set_input_gate(s: *mut RvcSession, threshold_db: c_double) -> c_int;
+    pub fn rvc_session_set_input_gate_stream(s: *mut RvcSession, stream: c_int, threshold_db: c_double) -> c_int;
     pub fn rvc_session_geometry(s: *mut RvcSession, out: *mut i32);
     pub fn rvc_session_process(s: *mut RvcSession, input_sample: *const c_float, n: usize, output: *mut c_float, cap: usize,
                                sola_offset: *mut usize) -> c_int;

@@ -45,6 +45,12 @@ int main(int argc, char **argv)
         last = rms(frame, F);
     }
     printf("session: frame %zu samples, last rms %.6f, last sola offset %zu\n", F, last, off);
+    /* the same stream with the phase-vocoder crossfade at the seam and the input gate at -50 dB */
+    rc = rvc_session_set_crossfade(s, RVC_CROSSFADE_PHASE_VOCODER);
+    if (rc == RVC_OK) rc = rvc_session_set_input_gate(s, -50.0);
+    if (rc == RVC_OK) rc = rvc_session_process(s, chunk, F, frame, F, &off);
+    if (rc != RVC_OK && rc != RVC_PANIC) { fprintf(stderr, "phase-vocoder chunk failed (%d): %s\n", (int)rc, rvc_last_error_message(e)); return 1; }
+    printf("session: phase-vocoder crossfade, rms %.6f, sola offset %zu\n", rms(frame, F), off);
     rvc_session_destroy(s);
     rvc_destroy(e);
     free(in); free(out); free(chunk); free(frame);

@@ -182,6 +182,19 @@ rvc_status rvc_envelop_mixing(rvc_engine *e, const float *input, float *output, 
  * output needs sola_len + search + frame valid samples; sola_buffer (sola_len) is updated in place. */
 rvc_status rvc_sola_step(rvc_engine *e, float *output, size_t output_len, float *sola_buffer, size_t sola_len, size_t search,
                          size_t frame, float *frame_out, size_t *sola_offset);
+/* The same step with a choice of crossfade (no counterpart in the plugin; DESIGN.md "Phase-vocoder crossfade and input gate").  LINEAR is
+ * rvc_sola_step bit for bit.  PHASE_VOCODER replaces the sin^2 blend of output[offset .. offset + sola_len) by the blend of the upstream
+ * real-time client's "phase vocoder" switch: the magnitudes of the two windowed spectra are added and every bin's phase glides from the saved
+ * tail's to the new segment's along the seam; offset search, saved tail and frame extraction are unchanged.  sola_len < 2 blends linearly;
+ * sola_len > 4096 or an unknown mode: RVC_SHAPE. */
+enum { RVC_CROSSFADE_LINEAR = 0, RVC_CROSSFADE_PHASE_VOCODER = 1 };
+rvc_status rvc_sola_step_x(rvc_engine *e, float *output, size_t output_len, float *sola_buffer, size_t sola_len, size_t search,
+                           size_t frame, float *frame_out, size_t *sola_offset, int crossfade);
+/* Input gate of the session on host buffers (the upstream client's response threshold, restated causally).  zc = sample_rate / 100, n a multiple
+ * of zc, x = concat(hist3zc, chunk): block i (zc samples) of `out` is zero when 20 log10(max(rms(x[i zc .. i zc + 4 zc)), 1e-5)) < threshold_db
+ * and the chunk's samples otherwise; hist_out = the last 3 zc samples of x (ungated).  threshold_db <= -60 = off (out = chunk); NaN: RVC_SHAPE. */
+rvc_status rvc_input_gate(rvc_engine *e, const float *hist3zc, const float *chunk, size_t n, size_t sample_rate, double threshold_db,
+                          float *out, float *hist_out);
 
 /* ---- the plugin's two sample-rate converters ---- */
 /* rubato::FftFixedInOut::<f32>::new(rate_in, rate_out, chunk_size_in, 1) at obs-rvc/src/lib.rs:236-242 (host rate -> 16 kHz in front
@@ -202,7 +215,7 @@ rvc_status rvc_resampler_process_device(rvc_resampler *r, const void *d_in, void
 /* ---- the plugin's per-chunk state machine as one call (SURVEY.md section 8 rows f1-f3 chained, all buffers resident in HBM) ---- */
 /* `create`/`update` + `process_one_frame` of the filter (obs-rvc/src/lib.rs:181-260, 659-795): host-rate ring, 16 kHz ring, both
  * resamplers, RvcInfer::infer, RMS envelope mixing and SOLA.  One H2D copy (the new chunk), one D2H copy (the finished frame) and
- * one synchronisation per chunk.  Lengths in seconds as in the plugin's settings; skip_inference != 0 = pass-through mode
+ * one synchronisation per chunk (with the phase-vocoder crossfade and the input gate as well).  Lengths in seconds as in the plugin's settings; skip_inference != 0 = pass-through mode
  * (lib.rs:224-227).  The session covers every stream of the engine (rvc_set_streams before rvc_session_create): process then takes
  * input [streams][n] and writes output [streams][cap], sola_offset [streams].  Destroy the session before the engine.  The session has no
  * formant setting of its own: it honours the engine's per-stream values (rvc_set_formant_shift[_stream]). */
@@ -214,6 +227,15 @@ size_t rvc_session_frame_size(rvc_session *s);                 /* sample_frame_s
 void rvc_session_set_params(rvc_session *s, int32_t pitch_shift, double rms_mix_rate);      /* every stream */
 /* one stream's pitch shift and RMS mix rate (the plugin's per-instance settings, obs-rvc/src/lib.rs:174-185); the others keep theirs */
 rvc_status rvc_session_set_params_stream(rvc_session *s, int stream, int32_t pitch_shift, double rms_mix_rate);
+/* Crossfade of the SOLA seam (RVC_CROSSFADE_*; LINEAR at creation), every stream or one; a session whose streams use both serves them in the
+ * same call.  Unknown mode, stream out of range, PHASE_VOCODER with sola_buffer_frame_size > 4096: RVC_SHAPE with a message. */
+rvc_status rvc_session_set_crossfade(rvc_session *s, int mode);
+rvc_status rvc_session_set_crossfade_stream(rvc_session *s, int stream, int mode);
+/* Input gate (rvc_input_gate) in front of the host-rate ring, every stream or one: the resampler, the model and the RMS-mix input see the gated
+ * signal, in pass-through mode too.  Off at creation and at threshold_db <= -60 (the chunk passes bit for bit).  The 30 ms history is that of the
+ * ungated input; it is kept from the first time any stream's gate is switched on (zeros before).  NaN, stream out of range: RVC_SHAPE. */
+rvc_status rvc_session_set_input_gate(rvc_session *s, double threshold_db);
+rvc_status rvc_session_set_input_gate_stream(rvc_session *s, int stream, double threshold_db);
 void rvc_session_geometry(rvc_session *s, int32_t out[10]);   /* the derived sizes of lib.rs:200-227 (see session.hip.h) */
 rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t n, float *output, size_t cap, size_t *sola_offset);
 

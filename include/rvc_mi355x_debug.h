@@ -81,6 +81,9 @@ const char *rvc_debug_last_kernel(void);
 /* host only: the formant resampler's full filter table h[n][K] (o -> n, K = 2 w + o; obs_rvc_amd/csrc/formant.hip.h) as fp32.  *width = K;
  * returns 0, 1 when cap < n K (nothing written to out), -1 for bad arguments */
 int rvc_debug_formant_table(size_t o, size_t n, float *out, size_t cap, size_t *width);
+/* enable != 0: every later rvc_session_process records HIP events around its SOLA stage (offset search, blend, tail save; with the phase-vocoder
+ * crossfade its analysis and synthesis launches); returns the milliseconds of the last chunk processed with the events on (0 before one) */
+float rvc_debug_session_sola_ms(rvc_session *s, int enable);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
 // back to a CPU path: without a HIP device every entry point returns RVC_BACKEND.
 #include "engine_int.h"
 #include "../../include/rvc_mi355x_debug.h"
+#include "crossfade.hip.h"
 #include <chrono>
 
 // The HIP runtime multiplexes all streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The engine runs four
@@ -1157,27 +1158,81 @@ rvc_status rvc_envelop_mixing(rvc_engine *e, const float *input, float *output, 
     });
 }
 
-rvc_status rvc_sola_step(rvc_engine *e, float *output, size_t output_len, float *sola_buffer, size_t sola_len, size_t search,
-                         size_t frame, float *frame_out, size_t *sola_offset)
+// rvc_sola_step / rvc_sola_step_x: one SOLA step of one stream on host buffers.  crossfade = RVC_CROSSFADE_PHASE_VOCODER queues the analysis and the
+// synthesis (crossfade.hip.h) behind the offset search, which keeps the segment unblended for them; sola_len < 2 has no seam to analyse (linear blend)
+static rvc_status sola_step_host(rvc_engine *e, float *output, size_t output_len, float *sola_buffer, size_t sola_len, size_t search,
+                                 size_t frame, float *frame_out, size_t *sola_offset, int crossfade)
 {
     return guarded(e, [&]() {
+        if (crossfade != RVC_CROSSFADE_LINEAR && crossfade != RVC_CROSSFADE_PHASE_VOCODER) throw ShapeError("sola: unknown crossfade mode");
         if (search + 1 > 1024) throw ShapeError("sola search range too long");
         if (output_len < sola_len + search || output_len < search + frame + sola_len) throw PanicError("sola: output shorter than offset + frame + tail (the reference slices out of range)");
+        const bool pv = crossfade == RVC_CROSSFADE_PHASE_VOCODER && sola_len >= 2;
+        if (pv && sola_len > (size_t)PV_MAX_N) throw ShapeError("sola: the phase-vocoder crossfade takes a seam of at most 4096 samples");
         float *d_out, *d_sola, *d_frame, *d_cor; int *d_off;
         HIPCHK(hipMalloc(&d_out, output_len * 4)); HIPCHK(hipMalloc(&d_sola, sola_len * 4)); HIPCHK(hipMalloc(&d_frame, frame * 4)); HIPCHK(hipMalloc(&d_off, 4));
         HIPCHK(hipMalloc(&d_cor, (search + 1) * 4));
+        float *d_pva = nullptr, *d_tab = nullptr, *d_spec = nullptr;
+        const int n = (int)sola_len, K = n / 2 + 1;
+        if (pv) {
+            std::vector<float> tab; pv_tables(n, tab);
+            HIPCHK(hipMalloc(&d_pva, sola_len * 4)); HIPCHK(hipMalloc(&d_tab, tab.size() * 4)); HIPCHK(hipMalloc(&d_spec, (size_t)3 * K * 4));
+            HIPCHK(hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        }
         HIPCHK(hipMemcpyAsync(d_out, output, output_len * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipMemcpyAsync(d_sola, sola_buffer, sola_len * 4, hipMemcpyHostToDevice, e->stream));
         hipLaunchKernelGGL(post_sola_corr_kernel, dim3((unsigned)(search + 4) / 4), dim3(256), 0, e->stream, d_out, d_sola, (int)sola_len, (int)search, d_cor, 0LL, 0LL, 0LL);
-        hipLaunchKernelGGL(post_sola_kernel, dim3(1), dim3(1024), 0, e->stream, d_out, d_sola, (int)sola_len, (int)search, (int)frame, d_frame, d_off, d_cor, 0LL, 0LL, 0LL, 0LL);
+        hipLaunchKernelGGL(post_sola_kernel, dim3(1), dim3(1024), 0, e->stream, d_out, d_sola, (int)sola_len, (int)search, (int)frame, d_frame, d_off, d_cor, 0LL, 0LL, 0LL, 0LL,
+                           (const int *)nullptr, pv ? 1 : 0, d_pva, 0LL);
+        if (pv) {
+            hipLaunchKernelGGL(pv_analysis_kernel, dim3((K + PV_AT - 1) / PV_AT, 1), dim3(PV_AT), pv_analysis_lds(n), e->stream, d_out, d_pva, d_off, (const int *)nullptr, 1,
+                               d_tab, n, d_spec, 0LL, 0LL);
+            hipLaunchKernelGGL(pv_synth_kernel, dim3((n + PV_JT - 1) / PV_JT, 1), dim3(PV_JT * PV_KS), pv_synth_lds(n), e->stream, d_out, d_pva, d_sola, d_frame, d_off,
+                               (const int *)nullptr, 1, d_tab, d_spec, n, (int)frame, 0LL, 0LL, 0LL, 0LL);
+        }
         int off = 0;
         HIPCHK(hipMemcpyAsync(output, d_out, output_len * 4, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipMemcpyAsync(sola_buffer, d_sola, sola_len * 4, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipMemcpyAsync(frame_out, d_frame, frame * 4, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipMemcpyAsync(&off, d_off, 4, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipGetLastError());
         if (sola_offset) *sola_offset = (size_t)off;
         (void)hipFree(d_out); (void)hipFree(d_sola); (void)hipFree(d_frame); (void)hipFree(d_off); (void)hipFree(d_cor);
+        (void)hipFree(d_pva); (void)hipFree(d_tab); (void)hipFree(d_spec);
+        return RVC_OK;
+    });
+}
+rvc_status rvc_sola_step(rvc_engine *e, float *output, size_t output_len, float *sola_buffer, size_t sola_len, size_t search,
+                         size_t frame, float *frame_out, size_t *sola_offset)
+{
+    return sola_step_host(e, output, output_len, sola_buffer, sola_len, search, frame, frame_out, sola_offset, RVC_CROSSFADE_LINEAR);
+}
+rvc_status rvc_sola_step_x(rvc_engine *e, float *output, size_t output_len, float *sola_buffer, size_t sola_len, size_t search,
+                           size_t frame, float *frame_out, size_t *sola_offset, int crossfade)
+{
+    return sola_step_host(e, output, output_len, sola_buffer, sola_len, search, frame, frame_out, sola_offset, crossfade);
+}
+
+// the session's input gate on host buffers: hist3zc (3 zc samples before the chunk, ungated), chunk (n = a multiple of zc) -> out (n), hist_out (3 zc)
+rvc_status rvc_input_gate(rvc_engine *e, const float *hist3zc, const float *chunk, size_t n, size_t sample_rate, double threshold_db, float *out, float *hist_out)
+{
+    return guarded(e, [&]() {
+        const size_t zc = sample_rate / 100;
+        if (zc == 0 || sample_rate > 384000 || n < zc || n % zc != 0 || n > (size_t)1 << 30) throw ShapeError("input_gate: the chunk must be a whole number of 10 ms blocks");
+        if (threshold_db != threshold_db) throw ShapeError("input_gate: the threshold is not a number");
+        if (!hist3zc || !chunk || !out || !hist_out) throw ShapeError("input_gate: null buffer");
+        float *d_chunk, *d_out, *d_hist;
+        HIPCHK(hipMalloc(&d_chunk, n * 4)); HIPCHK(hipMalloc(&d_out, n * 4)); HIPCHK(hipMalloc(&d_hist, 6 * zc * 4));
+        HIPCHK(hipMemcpyAsync(d_chunk, chunk, n * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(d_hist, hist3zc, 3 * zc * 4, hipMemcpyHostToDevice, e->stream));
+        hipLaunchKernelGGL(input_gate_kernel, dim3((unsigned)(n / zc + 1), 1), dim3(256), 0, e->stream, d_chunk, d_out, d_hist, d_hist + 3 * zc, (const float *)nullptr,
+                           gate_threshold(threshold_db), (int)zc, (int)n, 0LL, 0LL);
+        HIPCHK(hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(hist_out, d_hist + 3 * zc, 3 * zc * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipGetLastError());
+        (void)hipFree(d_chunk); (void)hipFree(d_out); (void)hipFree(d_hist);
         return RVC_OK;
     });
 }

@@ -2375,9 +2375,10 @@ static __global__ __launch_bounds__(256) void post_sola_corr_kernel(const float 
 }
 
 // arg-max with the reference's tie rule (the LAST maximum wins, rt_utils.rs:79-88), sin^2 crossfade with the previous tail, tail save and
-// frame extraction (lib.rs:768-794)
+// frame extraction (lib.rs:768-794).  mode_v / mode_all: the crossfade of a stream (per stream, or one value for all when mode_v is NULL)
 static __global__ __launch_bounds__(1024) void post_sola_kernel(float *output, float *sola, int sola_len, int search, int frame, float *frame_out, int *offset_out,
-                                                         const float *cor_g, long long out_bs, long long sola_bs, long long frame_bs, long long cor_bs)
+                                                         const float *cor_g, long long out_bs, long long sola_bs, long long frame_bs, long long cor_bs,
+                                                         const int *mode_v = nullptr, int mode_all = 0, float *pv_a = nullptr, long long pva_bs = 0)
 {
     __shared__ float cor[1024];
     __shared__ int s_off;
@@ -2392,11 +2393,17 @@ static __global__ __launch_bounds__(1024) void post_sola_kernel(float *output, f
     }
     __syncthreads();
     float *o = output + s_off;
-    for (int i = t; i < sola_len; i += 1024) {
-        const float x = sola_len > 1 ? (float)i / (float)(sola_len - 1) : 0.f;
-        const float sn = sinf(x * 0.5f * 3.14159265358979323846f);
-        const float fi = sn * sn, fo = 1.0f - fi;
-        o[i] = o[i] * fi + sola[i] * fo;
+    // a phase-vocoder stream (crossfade.hip.h) keeps the segment unblended and hands the old tail to the kernels behind this one, which
+    // write the blend over output, frame and tail
+    if ((mode_v ? mode_v[blockIdx.x] : mode_all) == 1) {
+        for (int i = t; i < sola_len; i += 1024) pv_a[blockIdx.x * pva_bs + i] = sola[i];
+    } else {
+        for (int i = t; i < sola_len; i += 1024) {
+            const float x = sola_len > 1 ? (float)i / (float)(sola_len - 1) : 0.f;
+            const float sn = sinf(x * 0.5f * 3.14159265358979323846f);
+            const float fi = sn * sn, fo = 1.0f - fi;
+            o[i] = o[i] * fi + sola[i] * fo;
+        }
     }
     __syncthreads();
     for (int i = t; i < sola_len; i += 1024) sola[i] = o[frame + i];

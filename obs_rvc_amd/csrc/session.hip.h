@@ -7,6 +7,8 @@
 // queued on the engine's stream:
 //   shift+append (ping-pong ring) -> polyphase downsampler -> 16 kHz ring update -> infer plan -> polyphase upsampler
 //   -> RMS envelope mixing -> SOLA search / crossfade / tail save.
+// Two per-stream stages of this project's own (crossfade.hip.h, DESIGN.md "Phase-vocoder crossfade and input gate"), both off by default: the input
+// gate in front of shift+append and the phase-vocoder blend (analysis + synthesis launches) behind the SOLA search.
 #pragma once
 
 namespace rvc {
@@ -49,6 +51,14 @@ struct rvc_session {
     int *d_off = nullptr; int n_rms = 0;
     int B = 1;                     // streams (= the engine's stream count at creation); every buffer below has a leading [B] axis
     std::vector<int> h_off;
+    // crossfade mode per stream (RVC_CROSSFADE_*); the phase-vocoder buffers exist when the seam fits its kernels (sola_buffer_frame_size <= PV_MAX_N)
+    std::vector<int> xfade; int *d_xfade = nullptr; bool xfade_dirty = false; int n_pv = 0;
+    float *d_pva = nullptr, *d_pvtab = nullptr, *d_pvspec = nullptr;
+    // input gate: threshold per stream (-inf = off), the ungated history (ping-pong) and the gated chunk.  The stage is launched from the first
+    // time any stream's gate is switched on; until then the history is the zeros of creation
+    std::vector<float> gate_thr; float *d_gate_thr = nullptr, *d_hist[2] = {nullptr, nullptr}, *d_gated = nullptr; bool gate_dirty = false, gate_used = false; int par_h = 0;
+    // rvc_debug_session_sola_ms: HIP events around the SOLA stage
+    bool time_sola = false; hipEvent_t ev_sola[2] = {nullptr, nullptr}; float sola_ms = 0.f;
 };
 
 extern "C" {
@@ -61,6 +71,9 @@ void rvc_session_destroy(rvc_session *s)
     rvc_resampler_destroy(s->down); rvc_resampler_destroy(s->up);
     for (float *p : {s->d_in[0], s->d_in[1], s->d_in16[0], s->d_in16[1], s->d_chunk, s->d_down, s->d_model, s->d_up, s->d_rms, s->d_sola, s->d_frame, s->d_cor}) (void)hipFree(p);
     (void)hipFree(s->d_off); (void)hipFree(s->d_mixpow);
+    for (float *p : {s->d_pva, s->d_pvtab, s->d_pvspec, s->d_gate_thr, s->d_hist[0], s->d_hist[1], s->d_gated}) (void)hipFree(p);
+    (void)hipFree(s->d_xfade);
+    for (hipEvent_t ev : s->ev_sola) if (ev) (void)hipEventDestroy(ev);
     delete s;
 }
 
@@ -114,6 +127,14 @@ rvc_status rvc_session_create(rvc_engine *e, size_t sample_rate, double sample_l
         dev(&s->d_cor, (size_t)s->sola_search_frame_size + 1);
         HIPCHK(hipMalloc(&s->d_off, 4 * NB));
         HIPCHK(hipMalloc(&s->d_mixpow, 4 * NB));
+        s->xfade.assign(s->B, RVC_CROSSFADE_LINEAR); s->gate_thr.assign(s->B, -INFINITY);
+        HIPCHK(hipMalloc(&s->d_xfade, 4 * NB)); HIPCHK(hipMemsetAsync(s->d_xfade, 0, 4 * NB, e->stream));
+        if (s->sola_buffer_frame_size >= 2 && s->sola_buffer_frame_size <= PV_MAX_N) {
+            std::vector<float> tab; pv_tables(s->sola_buffer_frame_size, tab);
+            HIPCHK(hipMalloc(&s->d_pvtab, tab.size() * 4)); HIPCHK(hipMemcpy(s->d_pvtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+            dev(&s->d_pva, s->sola_buffer_frame_size); dev(&s->d_pvspec, (size_t)3 * (s->sola_buffer_frame_size / 2 + 1));
+        }
+        dev(&s->d_gate_thr, 1); dev(&s->d_hist[0], (size_t)3 * zc); dev(&s->d_hist[1], (size_t)3 * zc); dev(&s->d_gated, s->sample_frame_size);
         HIPCHK(hipStreamSynchronize(e->stream));
         *out = sp.release();
         return RVC_OK;
@@ -133,6 +154,43 @@ rvc_status rvc_session_set_params_stream(rvc_session *s, int stream, int32_t pit
     if (stream < 0 || stream >= s->B) { s->e->err = "session: stream out of range"; return RVC_SHAPE; }
     s->pitch_shift[stream] = pitch_shift; s->rms_mix_rate[stream] = rms_mix_rate; s->mix_dirty = true;
     return RVC_OK;
+}
+
+// crossfade of the SOLA seam, every stream or one: RVC_CROSSFADE_LINEAR (the plugin's sin^2 blend) or RVC_CROSSFADE_PHASE_VOCODER
+static rvc_status session_set_crossfade(rvc_session *s, int first, int last, int mode)
+{
+    if (!s) return RVC_BACKEND;
+    if (first < 0 || last > s->B || first >= last) { s->e->err = "session: stream out of range"; return RVC_SHAPE; }
+    if (mode != RVC_CROSSFADE_LINEAR && mode != RVC_CROSSFADE_PHASE_VOCODER) { s->e->err = "session: unknown crossfade mode"; return RVC_SHAPE; }
+    if (mode == RVC_CROSSFADE_PHASE_VOCODER && s->sola_buffer_frame_size > PV_MAX_N) { s->e->err = "session: the phase-vocoder crossfade takes a seam of at most 4096 samples"; return RVC_SHAPE; }
+    for (int b = first; b < last; b++) s->xfade[b] = mode;
+    s->n_pv = 0;
+    // (a seam of one sample has nothing to analyse: the linear blend serves it)
+    for (int b = 0; b < s->B; b++) s->n_pv += s->xfade[b] == RVC_CROSSFADE_PHASE_VOCODER && s->sola_buffer_frame_size >= 2;
+    s->xfade_dirty = true;
+    return RVC_OK;
+}
+rvc_status rvc_session_set_crossfade(rvc_session *s, int mode) { return session_set_crossfade(s, 0, s ? s->B : 0, mode); }
+rvc_status rvc_session_set_crossfade_stream(rvc_session *s, int stream, int mode) { return session_set_crossfade(s, stream, stream + 1, mode); }
+// input gate, every stream or one: 10 ms blocks whose 40 ms RMS is below threshold_db are zeroed in front of the host-rate ring; <= -60 = off
+static rvc_status session_set_gate(rvc_session *s, int first, int last, double threshold_db)
+{
+    if (!s) return RVC_BACKEND;
+    if (first < 0 || last > s->B || first >= last) { s->e->err = "session: stream out of range"; return RVC_SHAPE; }
+    if (threshold_db != threshold_db) { s->e->err = "session: the gate threshold is not a number"; return RVC_SHAPE; }
+    for (int b = first; b < last; b++) s->gate_thr[b] = gate_threshold(threshold_db);
+    if (threshold_db > -60.0) s->gate_used = true;
+    s->gate_dirty = true;
+    return RVC_OK;
+}
+rvc_status rvc_session_set_input_gate(rvc_session *s, double threshold_db) { return session_set_gate(s, 0, s ? s->B : 0, threshold_db); }
+rvc_status rvc_session_set_input_gate_stream(rvc_session *s, int stream, double threshold_db) { return session_set_gate(s, stream, stream + 1, threshold_db); }
+// test / measurement hook (include/rvc_mi355x_debug.h): enable != 0 records HIP events around the SOLA stage of every later chunk; -> ms of the last chunk
+float rvc_debug_session_sola_ms(rvc_session *s, int enable)
+{
+    if (!s) return -1.f;
+    s->time_sola = enable != 0;
+    return s->sola_ms;
 }
 
 // geometry as the plugin derives it (tests): 0 sample_frame_size, 1 sample_frame_16k, 2 input_buffer_size, 3 input_buffer_16k_size,
@@ -157,9 +215,19 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
         hipStream_t st = e->stream;
         const int T = 256, B = s->B;
         HIPCHK(hipMemcpyAsync(s->d_chunk, input_sample, (size_t)B * n * 4, hipMemcpyHostToDevice, st));
+        // settings that changed since the last chunk (as d_mixpow below: a blocking copy, paid by the chunk after a setter call only)
+        if (s->xfade_dirty) { HIPCHK(hipMemcpy(s->d_xfade, s->xfade.data(), 4 * (size_t)B, hipMemcpyHostToDevice)); s->xfade_dirty = false; }
+        if (s->gate_dirty) { HIPCHK(hipMemcpy(s->d_gate_thr, s->gate_thr.data(), 4 * (size_t)B, hipMemcpyHostToDevice)); s->gate_dirty = false; }
+        const float *chunk = s->d_chunk;
+        if (s->gate_used) {
+            hipLaunchKernelGGL(input_gate_kernel, dim3(s->sample_frame_size / s->zc + 1, B), dim3(256), 0, st, s->d_chunk, s->d_gated, s->d_hist[s->par_h], s->d_hist[s->par_h ^ 1],
+                               s->d_gate_thr, 0.f, s->zc, s->sample_frame_size, (long long)s->sample_frame_size, 3LL * s->zc);
+            s->par_h ^= 1;
+            chunk = s->d_gated;
+        }
         // lib.rs:661-665
         hipLaunchKernelGGL(ring_shift_append_kernel, dim3((s->input_buffer_size + T - 1) / T, B), dim3(T), 0, st, s->d_in[s->par], s->d_in[s->par ^ 1],
-                           s->input_buffer_size, s->sample_frame_size, s->d_chunk);
+                           s->input_buffer_size, s->sample_frame_size, chunk);
         s->par ^= 1;
         const float *ring = s->d_in[s->par];
         // lib.rs:669-683: the converter sees the new chunk plus the 2*zc samples before it; its first 160 outputs are dropped
@@ -214,14 +282,28 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
         }
         // lib.rs:768-794
         const long long cor_bs = s->sola_search_frame_size + 1;
+        if (s->time_sola) {
+            for (hipEvent_t &ev : s->ev_sola) if (!ev) HIPCHK(hipEventCreate(&ev));
+            HIPCHK(hipEventRecord(s->ev_sola[0], st));
+        }
         hipLaunchKernelGGL(post_sola_corr_kernel, dim3((unsigned)(s->sola_search_frame_size + 4) / 4, B), dim3(256), 0, st, s->d_up, s->d_sola,
                            s->sola_buffer_frame_size, s->sola_search_frame_size, s->d_cor, up_bs, (long long)s->sola_buffer_frame_size, cor_bs);
         hipLaunchKernelGGL(post_sola_kernel, dim3(B), dim3(1024), 0, st, s->d_up, s->d_sola, s->sola_buffer_frame_size, s->sola_search_frame_size,
-                           s->sample_frame_size, s->d_frame, s->d_off, s->d_cor, up_bs, (long long)s->sola_buffer_frame_size, (long long)s->sample_frame_size, cor_bs);
+                           s->sample_frame_size, s->d_frame, s->d_off, s->d_cor, up_bs, (long long)s->sola_buffer_frame_size, (long long)s->sample_frame_size, cor_bs,
+                           s->n_pv ? s->d_xfade : (const int *)nullptr, 0, s->d_pva, (long long)s->sola_buffer_frame_size);
+        if (s->n_pv) {      // phase-vocoder streams: the blend over output / frame / tail, from the offset the kernel above left on the device
+            const int pn = s->sola_buffer_frame_size, K = pn / 2 + 1;
+            hipLaunchKernelGGL(pv_analysis_kernel, dim3((K + PV_AT - 1) / PV_AT, B), dim3(PV_AT), pv_analysis_lds(pn), st, s->d_up, s->d_pva, s->d_off, s->d_xfade, 0,
+                               s->d_pvtab, pn, s->d_pvspec, up_bs, (long long)pn);
+            hipLaunchKernelGGL(pv_synth_kernel, dim3((pn + PV_JT - 1) / PV_JT, B), dim3(PV_JT * PV_KS), pv_synth_lds(pn), st, s->d_up, s->d_pva, s->d_sola, s->d_frame, s->d_off,
+                               s->d_xfade, 0, s->d_pvtab, s->d_pvspec, pn, s->sample_frame_size, up_bs, (long long)pn, (long long)pn, (long long)s->sample_frame_size);
+        }
+        if (s->time_sola) HIPCHK(hipEventRecord(s->ev_sola[1], st));
         HIPCHK(hipMemcpy2DAsync(output, cap * 4, s->d_frame, (size_t)s->sample_frame_size * 4, (size_t)s->sample_frame_size * 4, B, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(s->h_off.data(), s->d_off, 4 * (size_t)B, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
+        if (s->time_sola) HIPCHK(hipEventElapsedTime(&s->sola_ms, s->ev_sola[0], s->ev_sola[1]));
         if (sola_offset) for (int b = 0; b < B; b++) sola_offset[b] = (size_t)s->h_off[b];
         return s->skip_inference ? RVC_OK : final_status(e);
     });

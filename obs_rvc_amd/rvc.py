@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _native
-from .rvc_common import PitchAlgorithm, RvcInferError, RvcModelVersion
+from .rvc_common import CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, PitchAlgorithm, RvcInferError, RvcModelVersion  # noqa: F401
 
 _FP = C.POINTER(C.c_float)
 
@@ -307,15 +307,35 @@ class RvcInfer:
         self._chk(self._L.rvc_envelop_mixing(self._h, xp, o.ctypes.data_as(_FP), len(o), int(sample_rate), float(mix_rate)))
         return o
 
-    def sola_step(self, output, sola_buffer, search: int, frame: int):
-        """rt_utils.rs:60-90 + lib.rs:768-794; returns (offset, frame samples, new sola buffer)."""
+    def sola_step(self, output, sola_buffer, search: int, frame: int, crossfade: int = 0):
+        """rt_utils.rs:60-90 + lib.rs:768-794; returns (offset, frame samples, new sola buffer).  crossfade: CROSSFADE_LINEAR (the
+        plugin's sin^2 blend, rvc_sola_step) or CROSSFADE_PHASE_VOCODER (rvc_sola_step_x)."""
+        return self.sola_step_full(output, sola_buffer, search, frame, crossfade)[:3]
+
+    def sola_step_full(self, output, sola_buffer, search: int, frame: int, crossfade: int = 0):
+        """sola_step that also returns the blended copy of `output`: (offset, frame samples, new sola buffer, output)."""
         o = np.array(output, dtype=np.float32, copy=True)
         sb = np.array(sola_buffer, dtype=np.float32, copy=True)
         fr = np.empty(frame, np.float32)
         off = C.c_size_t()
-        self._chk(self._L.rvc_sola_step(self._h, o.ctypes.data_as(_FP), len(o), sb.ctypes.data_as(_FP), len(sb), int(search), int(frame),
-                                        fr.ctypes.data_as(_FP), C.byref(off)))
-        return off.value, fr, sb
+        if crossfade == CROSSFADE_LINEAR:
+            rc = self._L.rvc_sola_step(self._h, o.ctypes.data_as(_FP), len(o), sb.ctypes.data_as(_FP), len(sb), int(search), int(frame),
+                                       fr.ctypes.data_as(_FP), C.byref(off))
+        else:
+            rc = self._L.rvc_sola_step_x(self._h, o.ctypes.data_as(_FP), len(o), sb.ctypes.data_as(_FP), len(sb), int(search), int(frame),
+                                         fr.ctypes.data_as(_FP), C.byref(off), int(crossfade))
+        self._chk(rc)
+        return off.value, fr, sb, o
+
+    def input_gate(self, hist, chunk, sample_rate: int, threshold_db: float):
+        """rvc_input_gate: hist = the 3 * (sample_rate // 100) ungated samples before `chunk` -> (gated chunk, next history)."""
+        h, hp = _f32(hist)
+        x, xp = _f32(chunk)
+        if len(h) != 3 * (int(sample_rate) // 100):
+            raise RvcInferError(5, "input_gate: the history holds 30 ms")
+        out, hist_out = np.empty(len(x), np.float32), np.empty(len(h), np.float32)
+        self._chk(self._L.rvc_input_gate(self._h, hp, xp, len(x), int(sample_rate), float(threshold_db), out.ctypes.data_as(_FP), hist_out.ctypes.data_as(_FP)))
+        return out, hist_out
 
     def index_device_ptr(self):
         b = C.c_size_t()

@@ -6,6 +6,11 @@ from __future__ import annotations
 
 import enum
 
+# crossfade of the SOLA seam (include/rvc_mi355x.h RVC_CROSSFADE_*): the plugin's sin^2 blend, or the phase-vocoder blend
+CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER = 0, 1
+# input gate: a threshold at or below this many dB switches it off
+INPUT_GATE_OFF_DB = -60.0
+
 
 class RvcModelVersion(enum.Enum):
     V1 = 1

@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from .geometry import Geometry
+from .rvc_common import CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, INPUT_GATE_OFF_DB
 
 
 class StreamingSession:
@@ -35,10 +36,36 @@ class StreamingSession:
         self.input_buffer_16k = np.zeros(g.input_buffer_16k_size, np.float32)    # lib.rs:218
         self.sola_buffer = np.zeros(g.sola_buffer_frame_size, np.float32)        # lib.rs:229
         self.last_sola_offset = 0
+        # the two stages of this project's own (DESIGN.md "Phase-vocoder crossfade and input gate"), off by default
+        self.crossfade = CROSSFADE_LINEAR
+        self.gate_threshold_db = INPUT_GATE_OFF_DB
+        self.gate_hist = np.zeros(3 * g.zc, np.float32)          # the ungated input before the chunk
+        self._gate_used = False                                  # the history is kept from the first time the gate is switched on
+
+    def _one_stream(self, stream):
+        if stream not in (None, 0):
+            raise ValueError("stream out of range")
+
+    def set_crossfade(self, mode: int, stream: int = None) -> None:
+        """CROSSFADE_LINEAR (the plugin's sin^2 blend) or CROSSFADE_PHASE_VOCODER at the SOLA seam."""
+        self._one_stream(stream)
+        if mode not in (CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER):
+            raise ValueError("unknown crossfade mode")
+        self.crossfade = int(mode)
+
+    def set_input_gate(self, threshold_db: float, stream: int = None) -> None:
+        """10 ms blocks whose 40 ms RMS lies below threshold_db are zeroed in front of the host-rate ring; <= -60 switches the gate off."""
+        self._one_stream(stream)
+        if threshold_db != threshold_db:
+            raise ValueError("the gate threshold is not a number")
+        self.gate_threshold_db = float(threshold_db)
+        self._gate_used = self._gate_used or threshold_db > INPUT_GATE_OFF_DB
 
     def process_one_frame(self, input_sample: np.ndarray, chunk_16k: np.ndarray | None = None) -> np.ndarray:
         g = self.g
         assert len(input_sample) == g.sample_frame_size
+        if self._gate_used:
+            input_sample, self.gate_hist = self.e.input_gate(self.gate_hist, input_sample, g.sample_rate, self.gate_threshold_db)
         # lib.rs:661-665: move and append the last n samples
         self.input_buffer[:-g.sample_frame_size] = self.input_buffer[g.sample_frame_size:]
         self.input_buffer[-g.sample_frame_size:] = input_sample
@@ -65,7 +92,10 @@ class StreamingSession:
         if self.rms_mix_rate < 1.0:
             out = self.e.envelop_mixing(self.input_buffer[g.extra_frame_size:], out, g.sample_rate, self.rms_mix_rate)
         # lib.rs:768-794
-        off, frame, self.sola_buffer = self.e.sola_step(out, self.sola_buffer, g.sola_search_frame_size, g.sample_frame_size)
+        if self.crossfade == CROSSFADE_LINEAR:
+            off, frame, self.sola_buffer = self.e.sola_step(out, self.sola_buffer, g.sola_search_frame_size, g.sample_frame_size)
+        else:
+            off, frame, self.sola_buffer = self.e.sola_step(out, self.sola_buffer, g.sola_search_frame_size, g.sample_frame_size, crossfade=self.crossfade)
         self.last_sola_offset = off
         return frame
 
@@ -109,6 +139,24 @@ class NativeStreamingSession:
     def set_formant_shift(self, semitones: float, stream: int = None) -> None:
         """The plugin's resonance shift (obs-rvc/src/lib.rs:446-451): forwarded to the engine, whose per-stream values the session honours."""
         self._engine.set_formant_shift(semitones, stream)
+
+    def _set(self, rc) -> None:
+        if int(rc) != 0:
+            raise self._err(int(rc), (self._L.rvc_last_error_message(self._engine._h) or b"").decode())
+
+    def set_crossfade(self, mode: int, stream: int = None) -> None:
+        """CROSSFADE_LINEAR or CROSSFADE_PHASE_VOCODER at the SOLA seam, every stream or one (rvc_session_set_crossfade[_stream])."""
+        if stream is None:
+            self._set(self._L.rvc_session_set_crossfade(self._h, int(mode)))
+        else:
+            self._set(self._L.rvc_session_set_crossfade_stream(self._h, int(stream), int(mode)))
+
+    def set_input_gate(self, threshold_db: float, stream: int = None) -> None:
+        """Input gate in dB, every stream or one (rvc_session_set_input_gate[_stream]); <= -60 switches it off."""
+        if stream is None:
+            self._set(self._L.rvc_session_set_input_gate(self._h, float(threshold_db)))
+        else:
+            self._set(self._L.rvc_session_set_input_gate_stream(self._h, int(stream), float(threshold_db)))
 
     def process_one_frame(self, input_sample: np.ndarray) -> np.ndarray:
         """One chunk of one stream (shape (sample_frame_size,)) or of every stream of the engine ((streams, sample_frame_size))."""
