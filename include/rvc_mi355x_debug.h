@@ -69,6 +69,38 @@ typedef struct rvc_debug_op_spec {
     int reps, graph;
 } rvc_debug_op_spec;
 int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, const float *w1, float *x, float *y, int *status, long long *geo);
+/* the head and the tail of the f0 branch and ContentVec's first layer, each built with the plan helper the models call (add_mel_frontend, add_conv0_front,
+ * add_pitch_post, add_nsf_source: model_rmvpe.hip, model_cv.hip, model_synth.hip) and run once eagerly, or -- graph != 0 -- captured and the graph launched once.
+ * op: tensors buf[0..3] (each the WHOLE allocation, uploaded before the launch and downloaded after it; geo[4][8] as for rvc_debug_layer, zeros for an unused
+ * slot); weights w0; w1:
+ *   4 mel front end   buf0 audio [streams][n] (the last `frame` samples of each stream are analysed; 64 floats of slack behind the last stream, as the
+ *                     plan's input buffer has); buf1 log-mel [streams][128][Tm]; buf2 the RMVPE input image [streams][1][Tm + 2][128 + 2] (geo: C = 1,
+ *                     T = W = 128, H = Tm), = log-mel * scale + shift.  The engine's own window / twiddle / mel tables are used.
+ *   5 conv0           buf0 audio [streams][L] (+ 64); buf1 out [streams][C][To], To = (L - 10) / 5 + 1.  Conv1d(1 -> C, 10 taps, stride 5, no bias) +
+ *                     GroupNorm(C groups) + GELU.  w0 = weight [C][10], w1 = gamma [C] then beta [C].  rvc_debug_last_kernel names the path ("conv0_multi4",
+ *                     "conv0_multi8", "conv0_one8|16|32", "conv0_generic"); hook RVC_CONV0_KERNEL = multi | one | generic.
+ *   6 pitch decode    buf0 salience [streams][360][Tm] (a plan tensor: ld padding, guards); buf1 f0 [streams][Tm]; update != 0: buf2 pitchf [streams][R], buf3 the
+ *                     coarse pitch [streams][R] as int32 in the floats' place; the cache moves by `shift`, takes f0[3 .. Tm - 1) from cache_start on, and R values are
+ *                     read from read_start on (out-of-range values: RVC_PANIC, as the chunk would).  Threshold 0.03.
+ *   7 NSF source      buf0 pitchf [streams][T]; buf1 src [streams][1][T upp] with a halo of x_halo columns per side.  sr, lin_w, lin_b, f0_num / f0_den as given;
+ *                     T > 512: RVC_SHAPE.
+ * state[streams]: what the kernels read of a stream's state and of the call (uppower, stream_id, chunk, cache) goes in, status and the updated cache come back;
+ * seed is the call's noise seed.  With buf == NULL only geo is filled.  0 = done, else an rvc_status (rvc_last_error_message). */
+typedef struct rvc_debug_stream_state {
+    float uppower; unsigned stream_id, chunk; int status;
+    float cache_pitchf[1024];
+} rvc_debug_stream_state;
+typedef struct rvc_debug_front_spec {
+    int op, streams, graph;
+    int n, frame;                                    /* 4: samples per stream, analysed samples (frame = 160 (Tm - 1) rounded as the engine does: Tm = 1 + frame / 160) */
+    float bn_scale, bn_shift;
+    int C, L;                                        /* 5 */
+    int Tm, update, shift, cache_start, read_start, R;   /* 6 */
+    int T, upp, x_halo, f0_num, f0_den;              /* 7 */
+    float sr, lin_w, lin_b;
+    unsigned seed;
+} rvc_debug_front_spec;
+int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w0, const float *w1, float *const *buf, rvc_debug_stream_state *state, long long *geo);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);

@@ -1652,6 +1652,9 @@ int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w
     });
 }
 
+// a launch that throws while the stream is capturing must not leave it in capture mode: the capture is ended and its partial graph dropped
+static void end_failed_capture(hipStream_t st) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); }
+
 // test aid: one attention / LayerNorm / GRU op as the models build it (include/rvc_mi355x_debug.h, tests/test_gpu_ops.py).  As for rvc_debug_layer, the caller
 // owns every float of the tensors' allocations.
 int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, const float *w1, float *x, float *y, int *status, long long *geo)
@@ -1697,7 +1700,7 @@ int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, con
             if (s->graph) {
                 hipGraph_t g; hipGraphExec_t ge;
                 HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-                for (auto &o : pl.ops.v) o(e->stream);
+                try { for (auto &o : pl.ops.v) o(e->stream); } catch (...) { end_failed_capture(e->stream); throw; }
                 HIPCHK(hipStreamEndCapture(e->stream, &g));
                 const hipError_t ie = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
                 (void)hipGraphDestroy(g);
@@ -1720,6 +1723,108 @@ int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, con
         HIPCHK(hipMemcpy(x, gx.base, (size_t)gx.g[0] * 4, hipMemcpyDeviceToHost));
         if (gy.base) HIPCHK(hipMemcpy(y, gy.base, (size_t)gy.g[0] * 4, hipMemcpyDeviceToHost));
         if (d_status) HIPCHK(hipMemcpy(status, d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
+// test aid: the mel front end, ContentVec's first layer, the pitch decode and the NSF source as the models build them (include/rvc_mi355x_debug.h,
+// tests/test_gpu_front.py).  As for rvc_debug_layer, the caller owns every float of the tensors' allocations; the streams' states live in a block of the
+// aid's own, so the engine's streams are not touched.
+static DebugGeo debug_geo_flat(float *p, long long n, int C, int T) { DebugGeo q; q.base = p; q.g[0] = n; q.g[1] = 0; q.g[2] = C; q.g[3] = T; q.g[4] = T; q.g[5] = (long long)C * T; q.g[6] = T; return q; }
+int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w0, const float *w1, float *const *buf, rvc_debug_stream_state *state, long long *geo)
+{
+    return (int)guarded(e, [&]() {
+        if (!s || !geo || s->streams < 1 || s->streams > 4096 || s->op < 4 || s->op > 7) throw ShapeError("front spec");
+        const int B = s->streams, op = s->op;
+        Plan pl; pl.B = B;
+        Arena &A = pl.arena;
+        DebugGeo g[4];
+        T1 x1, y1; T2 img; int Tm = 0, R = 0;
+        float *f0 = nullptr, *pitchf = nullptr, *mel = nullptr; int *pitch = nullptr;
+        if (op == 4) {
+            if (s->n < 1 || s->n > (1 << 24) || s->frame < 1 || s->frame > s->n) throw ShapeError("front spec");
+            Tm = 1 + s->frame / 160;
+            if (Tm > 1024) throw ShapeError("f0 window too long");
+            const long long na = (long long)B * s->n + 64;
+            g[0] = debug_geo_flat(A.floats((size_t)na), na, 1, s->n);
+            mel = A.floats((size_t)B * 128 * Tm); g[1] = debug_geo_flat(mel, (long long)B * 128 * Tm, 128, Tm);
+            img = make_t2(A, B, 1, Tm, 128);
+            const size_t gd = t2_guard(img.ld);
+            g[2].base = img.p - gd - img.ld - 1; g[2].g[0] = (long long)B * img.bs + 2 * (long long)gd; g[2].g[1] = (long long)gd + img.ld + 1; g[2].g[2] = 1; g[2].g[3] = 128;
+            g[2].g[4] = img.ld; g[2].g[5] = img.bs; g[2].g[6] = img.cs; g[2].g[7] = Tm;
+        } else if (op == 5) {
+            if (s->C < 1 || s->C > 4096 || s->L < 10 || s->L > (1 << 22)) throw ShapeError("front spec");
+            const long long na = (long long)B * s->L + 64;
+            x1.p = A.floats((size_t)na); x1.B = B; x1.C = 1; x1.T = s->L; x1.ld = s->L; x1.halo = 0; x1.bs = s->L;      // the plan's input buffer (build_plan, build_contentvec)
+            g[0] = debug_geo_flat(x1.p, na, 1, s->L);
+            y1 = make_t1(A, B, s->C, (s->L - 10) / 5 + 1, 0); g[1] = debug_geo1(y1);
+        } else if (op == 6) {
+            Tm = s->Tm; R = s->update ? s->R : 0;
+            if (Tm < 1 || Tm > 1024 || R < 0 || R > 1024) throw ShapeError("front spec");
+            x1 = make_t1(A, B, 360, Tm, 0); g[0] = debug_geo1(x1);
+            f0 = A.floats((size_t)B * Tm); g[1] = debug_geo_flat(f0, (long long)B * Tm, 1, Tm);
+            if (s->update) {
+                pitchf = A.floats((size_t)B * std::max(R, 1)); g[2] = debug_geo_flat(pitchf, (long long)B * R, 1, R);
+                pitch = (int *)A.alloc((size_t)B * std::max(R, 1) * sizeof(int)); g[3] = debug_geo_flat((float *)pitch, (long long)B * R, 1, R);
+            }
+        } else {
+            if (s->T < 1 || s->T > 4096 || s->upp < 1 || s->upp > 4096 || s->x_halo < 0 || s->x_halo > 4096) throw ShapeError("front spec");
+            pitchf = A.floats((size_t)B * s->T); g[0] = debug_geo_flat(pitchf, (long long)B * s->T, 1, s->T);
+            y1 = make_t1(A, B, 1, s->T * s->upp, s->x_halo); g[1] = debug_geo1(y1);
+        }
+        for (int j = 0; j < 4; j++) for (int i = 0; i < 8; i++) geo[8 * j + i] = g[j].base ? g[j].g[i] : 0;
+        if (!buf) return RVC_OK;
+        if (!state) throw ShapeError("front buffers");
+        for (int j = 0; j < 4; j++) if (g[j].base && g[j].g[0] > 0 && !buf[j]) throw ShapeError("front buffers");
+        std::vector<StreamState> hst(B);
+        for (int b = 0; b < B; b++) {
+            memset(&hst[b], 0, sizeof(StreamState));
+            hst[b].uppower = state[b].uppower; hst[b].stream_id = state[b].stream_id; hst[b].chunk = state[b].chunk; hst[b].status = state[b].status;
+            memcpy(hst[b].cache_pitchf, state[b].cache_pitchf, sizeof hst[b].cache_pitchf);
+        }
+        StreamState *d_st = A.upload(hst);
+        CallParams hcp{}; hcp.seed = s->seed;
+        CallParams *d_cp = A.upload(std::vector<CallParams>(1, hcp));
+        std::vector<float *> wts;          // device copies of the weights, freed on every exit
+        ConvW cw;
+        try {
+            if (op == 4) add_mel_frontend(e, pl, B, g[0].base, s->n, s->n, s->frame, Tm, mel, img, s->bn_scale, s->bn_shift);
+            else if (op == 5) {
+                if (!w0 || !w1) throw ShapeError("front buffers");
+                wts.push_back(upload_f(w0, (size_t)s->C * 10)); wts.push_back(upload_f(w1, (size_t)2 * s->C));
+                cw = prep_conv(w0, nullptr, s->C, 1, 10, 1);
+                add_conv0_front(pl, cw, wts[0], wts[1], wts[1] + s->C, 10, 5, x1, y1);
+            } else if (op == 6) add_pitch_post(pl, B, x1, Tm, d_st, d_cp, f0, s->update != 0, s->shift, s->cache_start, s->read_start, R, pitchf, pitch);
+            else add_nsf_source(pl, B, pitchf, y1, s->T, s->upp, s->sr, s->lin_w, s->lin_b, d_st, d_cp, s->f0_num, s->f0_den);
+            for (int j = 0; j < 4; j++) if (g[j].base && g[j].g[0] > 0) HIPCHK(hipMemcpy(g[j].base, buf[j], (size_t)g[j].g[0] * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipDeviceSynchronize());
+            if (s->graph) {
+                hipGraph_t gr; hipGraphExec_t ge;
+                HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+                try { for (auto &o : pl.ops.v) o(e->stream); } catch (...) { end_failed_capture(e->stream); throw; }
+                HIPCHK(hipStreamEndCapture(e->stream, &gr));
+                const hipError_t ie = hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0);
+                (void)hipGraphDestroy(gr);
+                HIPCHK(ie);
+                const hipError_t le = hipGraphLaunch(ge, e->stream);
+                const hipError_t se = hipStreamSynchronize(e->stream);
+                (void)hipGraphExecDestroy(ge);
+                HIPCHK(le); HIPCHK(se);
+            } else {
+                for (auto &o : pl.ops.v) o(e->stream);
+                HIPCHK(hipStreamSynchronize(e->stream));
+            }
+            HIPCHK(hipGetLastError());
+        } catch (...) {
+            for (float *p : wts) wfree(p);
+            free_conv(cw);
+            throw;
+        }
+        for (float *p : wts) wfree(p);
+        free_conv(cw);
+        for (int j = 0; j < 4; j++) if (g[j].base && g[j].g[0] > 0) HIPCHK(hipMemcpy(buf[j], g[j].base, (size_t)g[j].g[0] * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hst.data(), d_st, sizeof(StreamState) * B, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; b++) { state[b].status = hst[b].status; memcpy(state[b].cache_pitchf, hst[b].cache_pitchf, sizeof hst[b].cache_pitchf); }
         return RVC_OK;
     });
 }

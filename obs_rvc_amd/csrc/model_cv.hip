@@ -4,6 +4,65 @@
 namespace rvc {
 
 // ------------------------------- ContentVec ------------------------------------------
+// First layer: Conv1d(1 -> C, k taps, no bias) + GroupNorm (one group per channel: statistics over time) + GELU on the raw input x [B][1][L] into
+// y [B][C][To].  Three paths: the fused multi-channel kernel (10 taps, To <= 8192, an even channel count), the fused one-channel kernel (<= 16 taps,
+// To <= 8192) and the generic convolution followed by groupnorm_gelu_kernel.  The path taken is recorded (rvc_debug_last_kernel: "conv0_multi4|8",
+// "conv0_one8|16|32", "conv0_generic"); the test hook RVC_CONV0_KERNEL = multi | one | generic replaces the rules' choice where that path is
+// eligible, and is refused (ShapeError, nothing queued) elsewhere.
+void add_conv0_front(Plan &pl, const ConvW &cw, const float *w_raw, const float *gn_g, const float *gn_b, int kt, int st, const T1 &x, const T1 &y)
+{
+    const int B = x.B, C = y.C, To = y.T;
+    const bool fuse_ok = kt <= 16 && To <= 32 * 256 && w_raw != nullptr;
+    // 16 channels per workgroup share one register copy of the input samples at many streams; one stream: 2 (256 workgroups of
+    // 1024 threads, half the strided gathers: 42.8 -> ~15 us, 25-30 us off the ContentVec branch; 4 and 8 measured the same / worse)
+    int cpw = B >= 16 ? 16 : (B >= 4 ? 4 : 2);
+    if (const char *f = tune_env("RVC_CONV0_CPW")) cpw = std::max(1, atoi(f));      // tuning aid
+    while (cpw > 1 && C % cpw) cpw >>= 1;
+    const bool multi_ok = fuse_ok && kt == 10 && To <= 8 * 1024 && cpw > 1;
+    const char *path = fuse_ok && !tune_env("RVC_NO_CONV0_FUSE") ? (multi_ok && !test_opt("RVC_NO_CONV0_MULTI") ? "multi" : "one") : "generic";
+    if (const char *f = test_opt("RVC_CONV0_KERNEL")) {
+        const bool known = !strcmp(f, "multi") || !strcmp(f, "one") || !strcmp(f, "generic");
+        if (!known) throw ShapeError(std::string("RVC_CONV0_KERNEL: unknown variant '") + f + "'");
+        if ((!strcmp(f, "multi") && !multi_ok) || (!strcmp(f, "one") && !fuse_ok)) throw ShapeError(std::string("RVC_CONV0_KERNEL: variant '") + f + "' is not eligible for this shape");
+        path = !strcmp(f, "multi") ? "multi" : (!strcmp(f, "one") ? "one" : "generic");
+    }
+    if (path[0] != 'g') {
+        // fused: conv (Cin = 1) + per-channel GroupNorm + GELU, outputs held in registers between the passes
+        dim3 grid(C, B);
+        const float *w0 = w_raw, *gg = gn_g, *bb = gn_b;
+        const float *ain = x.p; const long long abs_ = x.bs;
+        const int nt = (To + 255) / 256;
+        Plan *plp = &pl;
+        if (path[0] == 'm') {
+            dim3 gridm(C / cpw, B);
+            const int nt1k = (To + 1023) / 1024;
+            snprintf(g_last_kernel, sizeof g_last_kernel, "conv0_multi%d", nt1k <= 4 ? 4 : 8);
+            pl.ops.push_back([=](hipStream_t s) {
+                const float *in_ = plp->cur_in ? plp->cur_in : ain;      // a device-resident caller's buffer is read in place
+                if (nt1k <= 4) hipLaunchKernelGGL((conv0_gn_gelu_multi_kernel<4, 10>), gridm, dim3(1024), 0, s, in_, abs_, w0, st, gg, bb, y.p, To, y.ld, y.bs, cpw);
+                else hipLaunchKernelGGL((conv0_gn_gelu_multi_kernel<8, 10>), gridm, dim3(1024), 0, s, in_, abs_, w0, st, gg, bb, y.p, To, y.ld, y.bs, cpw);
+            });
+        } else {
+            snprintf(g_last_kernel, sizeof g_last_kernel, "conv0_one%d", nt <= 8 ? 8 : (nt <= 16 ? 16 : 32));
+            pl.ops.push_back([=](hipStream_t s) {
+                const float *in_ = plp->cur_in ? plp->cur_in : ain;
+                if (nt <= 8) hipLaunchKernelGGL((conv0_gn_gelu_kernel<8>), grid, dim3(256), 0, s, in_, abs_, w0, kt, st, gg, bb, y.p, To, y.ld, y.bs);
+                else if (nt <= 16) hipLaunchKernelGGL((conv0_gn_gelu_kernel<16>), grid, dim3(256), 0, s, in_, abs_, w0, kt, st, gg, bb, y.p, To, y.ld, y.bs);
+                else hipLaunchKernelGGL((conv0_gn_gelu_kernel<32>), grid, dim3(256), 0, s, in_, abs_, w0, kt, st, gg, bb, y.p, To, y.ld, y.bs);
+            });
+        }
+        add_tap(pl, "cv.conv0", y);
+        return;
+    }
+    ConvOpts o; o.act = ACT_NONE;
+    pl.in_direct_ok = false;      // (the generic convolution bakes its input pointer: this plan keeps the staging copy)
+    add_conv1d(pl, cw, x, y, st, 0, 1, o);
+    snprintf(g_last_kernel, sizeof g_last_kernel, "conv0_generic");
+    dim3 grid(C, B);
+    pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(groupnorm_gelu_kernel, grid, dim3(256), 0, s, y.p, gn_g, gn_b, y.T, y.ld, y.bs); });
+    add_tap(pl, "cv.conv0", y);
+}
+
 T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
 {
     ModelCV &m = *e->cv;
@@ -13,50 +72,13 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
     for (int i = 0; i < 7; i++) {
         int To = (T - m.conv_k[i]) / m.conv_s[i] + 1;
         T1 y = make_t1(A, B, m.conv_dim, To, 0);
-        if (i == 0 && m.conv_k[0] <= 16 && To <= 32 * 256 && m.conv0_raw && !tune_env("RVC_NO_CONV0_FUSE")) {
-            // first layer fused: conv (Cin = 1) + per-channel GroupNorm + GELU, outputs held in registers between the passes
-            dim3 grid(m.conv_dim, B);
-            const float *w0 = m.conv0_raw, *gg = m.gn_g, *bb = m.gn_b; const int kt = m.conv_k[0], st = m.conv_s[0];
-            const float *ain = x.p; const long long abs_ = x.bs;
-            const int nt = (To + 255) / 256;
-            // 16 channels per workgroup share one register copy of the input samples at many streams; one stream: 2 (256 workgroups of
-            // 1024 threads, half the strided gathers: 42.8 -> ~15 us, 25-30 us off the ContentVec branch; 4 and 8 measured the same / worse)
-            int cpw = B >= 16 ? 16 : (B >= 4 ? 4 : 2);
-            if (const char *f = tune_env("RVC_CONV0_CPW")) cpw = std::max(1, atoi(f));      // tuning aid
-            while (cpw > 1 && m.conv_dim % cpw) cpw >>= 1;
-            if (kt == 10 && To <= 8 * 1024 && cpw > 1 && !test_opt("RVC_NO_CONV0_MULTI")) {
-                dim3 gridm(m.conv_dim / cpw, B);
-                const int nt1k = (To + 1023) / 1024;
-                Plan *plp = &pl;
-                pl.ops.push_back([=](hipStream_t s) {
-                    const float *in_ = plp->cur_in ? plp->cur_in : ain;      // a device-resident caller's buffer is read in place
-                    if (nt1k <= 4) hipLaunchKernelGGL((conv0_gn_gelu_multi_kernel<4, 10>), gridm, dim3(1024), 0, s, in_, abs_, w0, st, gg, bb, y.p, To, y.ld, y.bs, cpw);
-                    else hipLaunchKernelGGL((conv0_gn_gelu_multi_kernel<8, 10>), gridm, dim3(1024), 0, s, in_, abs_, w0, st, gg, bb, y.p, To, y.ld, y.bs, cpw);
-                });
-                add_tap(pl, "cv.conv0", y);
-                x = y; T = To;
-                continue;
-            }
-            Plan *plp = &pl;
-            pl.ops.push_back([=](hipStream_t s) {
-                const float *in_ = plp->cur_in ? plp->cur_in : ain;
-                if (nt <= 8) hipLaunchKernelGGL((conv0_gn_gelu_kernel<8>), grid, dim3(256), 0, s, in_, abs_, w0, kt, st, gg, bb, y.p, To, y.ld, y.bs);
-                else if (nt <= 16) hipLaunchKernelGGL((conv0_gn_gelu_kernel<16>), grid, dim3(256), 0, s, in_, abs_, w0, kt, st, gg, bb, y.p, To, y.ld, y.bs);
-                else hipLaunchKernelGGL((conv0_gn_gelu_kernel<32>), grid, dim3(256), 0, s, in_, abs_, w0, kt, st, gg, bb, y.p, To, y.ld, y.bs);
-            });
-            add_tap(pl, "cv.conv0", y);
+        if (i == 0) {
+            add_conv0_front(pl, m.conv[0], m.conv0_raw, m.gn_g, m.gn_b, m.conv_k[0], m.conv_s[0], x, y);
             x = y; T = To;
             continue;
         }
-        ConvOpts o; o.act = i == 0 ? ACT_NONE : ACT_GELU;
-        if (i == 0) pl.in_direct_ok = false;      // (the generic convolution bakes its input pointer: this plan keeps the staging copy)
+        ConvOpts o; o.act = ACT_GELU;
         add_conv1d(pl, m.conv[i], x, y, m.conv_s[i], 0, 1, o);
-        if (i == 0) {
-            dim3 grid(m.conv_dim, B);
-            float *g = m.gn_g, *bb = m.gn_b;
-            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(groupnorm_gelu_kernel, grid, dim3(256), 0, s, y.p, g, bb, y.T, y.ld, y.bs); });
-            add_tap(pl, "cv.conv0", y);
-        }
         x = y; T = To;
     }
     add_tap(pl, "cv.feat", x);

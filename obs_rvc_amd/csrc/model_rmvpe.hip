@@ -132,6 +132,21 @@ static T2 res_block(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, co
     return out;
 }
 
+// RMVPE's front end on the last `frame` of the n samples of each stream (audio [B][audio_bs]): the raw log-mel into mel [B][128][Tm] and, with the network's
+// input affine, into the image img [B][1][Tm][128].  The engine's tables (window, twiddles, mel basis and bands) are used; an eager launch reads the
+// caller's device buffer (Plan::cur_in) in place of `audio` when there is one.
+void add_mel_frontend(rvc_engine *e, Plan &pl, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, float *mel, const T2 &img, float bn_scale, float bn_shift)
+{
+    if (frame < 513 || frame > n || Tm < 1 || (long long)(Tm - 1) * 160 > (long long)frame) throw ShapeError("mel front end: frame out of range");   // (one reflection per side)
+    MelP mp{};
+    mp.audio = audio; mp.audio_bs = audio_bs; mp.n = n; mp.frame = frame; mp.Tm = Tm;
+    mp.window = e->d_window; mp.twiddle = e->d_twiddle; mp.basis = e->d_basis; mp.band = e->d_band;
+    mp.mel = mel; mp.img = img.p; mp.img_bs = img.bs; mp.img_ld = img.ld; mp.bn_scale = bn_scale; mp.bn_shift = bn_shift;
+    dim3 grid(Tm, B);
+    Plan *plp = &pl;
+    pl.ops.push_back([=](hipStream_t s) { MelP m2 = mp; if (plp->cur_in) m2.audio = plp->cur_in; hipLaunchKernelGGL(mel_frontend_kernel, grid, dim3(256), 0, s, m2); });
+}
+
 T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache)
 {
     ModelRM &m = *e->rm;
@@ -150,17 +165,9 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
     if ((H0 >> m.levels) < 1 || (W0 >> m.levels) < 1) throw ShapeError("RMVPE: input too small for the U-Net depth");
     T2 img = make_t2(A, B, 1, H0, W0);
     float *d_mel = A.floats((size_t)B * 128 * Tm);
-    {
-        MelP mp{};
-        mp.audio = pl.d_in; mp.audio_bs = (long long)L; mp.n = (int)L; mp.frame = (int)fr; mp.Tm = Tm;
-        mp.window = e->d_window; mp.twiddle = e->d_twiddle; mp.basis = e->d_basis; mp.band = e->d_band;
-        mp.mel = d_mel; mp.img = img.p; mp.img_bs = img.bs; mp.img_ld = img.ld; mp.bn_scale = m.bn_scale; mp.bn_shift = m.bn_shift;
-        dim3 grid(Tm, B);
-        Plan *plp = &pl;
-        pl.ops.push_back([=](hipStream_t s) { MelP m2 = mp; if (plp->cur_in) m2.audio = plp->cur_in; hipLaunchKernelGGL(mel_frontend_kernel, grid, dim3(256), 0, s, m2); });
-        add_stamp(pl, "rm.mel0");
-        if (pl.with_taps) { T1 t; t.p = d_mel; t.B = B; t.C = 128; t.T = Tm; t.ld = Tm; t.halo = 0; t.bs = 128LL * Tm; add_tap(pl, "rm.mel", t); }
-    }
+    add_mel_frontend(e, pl, B, pl.d_in, (long long)L, (int)L, (int)fr, Tm, d_mel, img, m.bn_scale, m.bn_shift);
+    add_stamp(pl, "rm.mel0");
+    if (pl.with_taps) { T1 t; t.p = d_mel; t.B = B; t.C = 128; t.T = Tm; t.ld = Tm; t.halo = 0; t.bs = 128LL * Tm; add_tap(pl, "rm.mel", t); }
     // encoder; every level's pre-pool output is written straight into the second half of the decoder's concat buffer
     std::vector<T2> cat(m.levels);
     {
@@ -230,32 +237,45 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
     return sal;
 }
 
-// decode + pitch shift + pitch cache + get_f0_post (rmvpe.rs:118-133,243-248; rvc.rs:121,167-180; f0/mod.rs:7-12)
+// decode + pitch shift + pitch cache + get_f0_post (rmvpe.rs:118-133,243-248; rvc.rs:121,167-180; f0/mod.rs:7-12) of the salience sal [B][360][Tm] on the
+// states st [B] (uppower, cache_pitchf, status): f0 [B][Tm]; update: the cache is shifted by `shift`, the new f0 inserted from cache_start on and
+// R values from read_start sliced into pitchf / pitch [B][R]
+void add_pitch_post(Plan &pl, int B, const T1 &sal, int Tm, StreamState *st, const CallParams *cp, float *f0, bool update, long long shift, long long cache_start,
+                    long long read_start, int R, float *pitchf, int *pitch)
+{
+    if (sal.C != 360 || sal.T != Tm || Tm < 1 || Tm > 1024) throw ShapeError("pitch decode: salience shape");
+    PitchP pp{};
+    pp.sal = sal.p; pp.sal_cs = sal.ld; pp.sal_bs = sal.bs; pp.Tm = Tm;
+    pp.st = st; pp.cp = cp; pp.f0 = f0; pp.threshold = 0.03f;   // rvc.rs:122
+    if (update) {
+        if (shift < 0 || shift > 1024 || Tm < 5) throw PanicError("pitch cache shift out of range");
+        if (cache_start < 0 || read_start < 0 || read_start + R > 1024 || R < 0 || 3 + (1023 - cache_start) >= Tm) throw PanicError("pitch cache slice out of range");
+        pp.pitchf = pitchf; pp.pitch = pitch;
+        pp.shift = (int)shift; pp.cache_start = (int)cache_start; pp.read_start = (int)read_start; pp.R = R;
+    } else {
+        pp.R = 0; pp.shift = 0; pp.cache_start = 1 << 30; pp.read_start = 0; pp.pitchf = nullptr; pp.pitch = nullptr;
+    }
+    pp.update = update ? 1 : 0;
+    pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(pitch_post_kernel, dim3(B), dim3(1024), 0, s, pp); });
+}
+
 void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update_cache, size_t frame16k, size_t hubert_length,
                              float **pitchf_out, int **pitch_out)
 {
     Arena &A = pl.arena;
     const int Tm = pl.Tm;
     pl.d_f0 = A.floats((size_t)B * Tm);
-    PitchP pp{};
-    pp.sal = sal.p; pp.sal_cs = sal.ld; pp.sal_bs = sal.bs; pp.Tm = Tm;
-    pp.st = e->d_state; pp.cp = e->d_cp; pp.f0 = pl.d_f0; pp.threshold = 0.03f;   // rvc.rs:122
-    if (update_cache) {
-        const int R = (int)pl.R;
-        const size_t shift = frame16k / 160;                                   // rvc.rs:168
-        if (shift > 1024 || Tm < 5) throw PanicError("pitch cache shift out of range");
-        const long long cache_start = 1024 + 4 - Tm;                            // rvc.rs:172
-        const long long read_start = 1024 - (long long)hubert_length + pl.skip_head;   // rvc.rs:176
-        if (cache_start < 0 || read_start < 0 || read_start + R > 1024) throw PanicError("pitch cache slice out of range");
-        pp.pitchf = A.floats((size_t)B * R);
-        pp.pitch = (int *)A.alloc((size_t)B * R * sizeof(int));
-        pp.shift = (int)shift; pp.cache_start = (int)cache_start; pp.read_start = (int)read_start; pp.R = R;
-        *pitchf_out = pp.pitchf; *pitch_out = pp.pitch;
-    } else {
-        pp.R = 0; pp.shift = 0; pp.cache_start = 1 << 30; pp.read_start = 0; pp.pitchf = nullptr; pp.pitch = nullptr;
-    }
-    pp.update = update_cache ? 1 : 0;
-    pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(pitch_post_kernel, dim3(B), dim3(1024), 0, s, pp); });
+    if (!update_cache) { add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, false, 0, 0, 0, 0, nullptr, nullptr); return; }
+    const int R = (int)pl.R;
+    const size_t shift = frame16k / 160;                                   // rvc.rs:168
+    if (shift > 1024 || Tm < 5) throw PanicError("pitch cache shift out of range");
+    const long long cache_start = 1024 + 4 - Tm;                            // rvc.rs:172
+    const long long read_start = 1024 - (long long)hubert_length + pl.skip_head;   // rvc.rs:176
+    if (cache_start < 0 || read_start < 0 || read_start + R > 1024) throw PanicError("pitch cache slice out of range");
+    float *pitchf = A.floats((size_t)B * R);
+    int *pitch = (int *)A.alloc((size_t)B * R * sizeof(int));
+    add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, true, (long long)shift, cache_start, read_start, R, pitchf, pitch);
+    *pitchf_out = pitchf; *pitch_out = pitch;
 }
 
 }  // namespace rvc

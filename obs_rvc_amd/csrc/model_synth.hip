@@ -4,7 +4,20 @@
 namespace rvc {
 
 // ------------------------------- synthesizer ------------------------------------------
-// NSF harmonic source: depends only on the f0 branch, so it is queued on that branch's stream
+// NSF harmonic source (SineGen + Linear(1, 1) + tanh) of pitchf [B][R] into src [B][1][R upp]; the noise is drawn per stream from st / cp (stream_id, chunk, seed);
+// the source reads f0 x f0_num / f0_den.  The kernel keeps the per-frame phases of one stream in 512-entry tables: longer windows are refused.
+void add_nsf_source(Plan &pl, int B, const float *pitchf, const T1 &src, int R, int upp, float sr, float lin_w, float lin_b, const StreamState *st, const CallParams *cp,
+                    int f0_num, int f0_den)
+{
+    if (R > 512) throw ShapeError("return_length too long for the NSF source kernel");
+    if (R < 1 || upp < 1 || src.T != R * upp || src.C != 1 || f0_den < 1) throw ShapeError("NSF source: inconsistent shapes");
+    SrcP sp{}; sp.pitchf = pitchf; sp.src = src.p; sp.src_bs = src.bs; sp.T = R; sp.upp = upp; sp.sr = sr;
+    sp.lin_w = lin_w; sp.lin_b = lin_b; sp.st = st; sp.cp = cp;
+    sp.f0_num = f0_num; sp.f0_den = f0_den;
+    pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(nsf_source_kernel, dim3(B), dim3(1024), 0, s, sp); });
+}
+
+// The source depends only on the f0 branch, so it is queued on that branch's stream
 T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
 {
     ModelSY &m = *e->sy;
@@ -15,12 +28,7 @@ T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
     if (R > 512) throw ShapeError("return_length too long for the NSF source kernel");
     int max_sf = 1; { int sf = 1; for (int i = m.n_ups - 1; i >= 1; i--) { sf *= m.up_rate[i]; max_sf = std::max(max_sf, sf); } }
     T1 src = make_t1(A, B, 1, (int)N, max_sf + 2);
-    {
-        SrcP sp{}; sp.pitchf = d_pitchf; sp.src = src.p; sp.src_bs = src.bs; sp.T = R; sp.upp = upp; sp.sr = (float)m.sr;
-        sp.lin_w = m.src_w; sp.lin_b = m.src_b; sp.st = e->d_state; sp.cp = e->d_cp;
-        sp.f0_num = R2; sp.f0_den = R;        // formant shift: f0 x R2 / R compensates the time stretch below (1 without one)
-        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(nsf_source_kernel, dim3(B), dim3(1024), 0, s, sp); });
-    }
+    add_nsf_source(pl, B, d_pitchf, src, R, upp, (float)m.sr, m.src_w, m.src_b, e->d_state, e->d_cp, R2, R);        // formant shift: f0 x R2 / R compensates the time stretch below (1 without one)
     add_tap(pl, "sy.src", src);
     if (!pl.fstage) return src;
     // formant shift: the source stretched to R2 frames (formant.hip.h)
