@@ -31,7 +31,7 @@ SYMBOLS = [
 ]
 
 
-SOURCES = ("engine.hip", "engine_int.h", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_synth.hip", "retrieval.hip", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "igemm2_inst.hip", "igemm_tiled_inst.hip", "igemm2w_inst.hip", "igemm_bf3_inst.hip", "conv_tile.hip.h", "conv_tile_inst.hip", "conv32s.hip.h", "conv32s_inst.hip", "rmblock.hip.h", "igemm32l.hip.h", "igemm32l_inst.hip", "version.cpp", "calib.hip", "exports.map",
+SOURCES = ("engine.hip", "engine_int.h", "debug.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_synth.hip", "retrieval.hip", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "igemm2_inst.hip", "igemm_tiled_inst.hip", "igemm2w_inst.hip", "igemm_bf3_inst.hip", "conv_tile.hip.h", "conv_tile_inst.hip", "conv32s.hip.h", "conv32s_inst.hip", "rmblock.hip.h", "igemm32l.hip.h", "igemm32l_inst.hip", "version.cpp", "calib.hip", "exports.map",
            "state.hip.h", "formant.hip.h", "crossfade.hip.h",
            "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h", "blob.h", "rvc_rpc.cpp")
 
@@ -41,7 +41,7 @@ SOURCES = ("engine.hip", "engine_int.h", "plan.hip", "model_cv.hip", "model_rmvp
 _IGEMM_DEPS = ("igemm.hip.h", "igemm_launch.h")
 _INT_DEPS = ("engine_int.h", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "blob.h", "state.hip.h", "formant.hip.h")
 _ENGINE_DEPS = ("engine.hip", "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h", "crossfade.hip.h") + _INT_DEPS
-UNITS = [("engine.hip", [], _ENGINE_DEPS), ("calib.hip", [], ("calib.hip",))] + [(u, [], (u,) + _INT_DEPS + (("rmblock.hip.h",) if u == "model_rmvpe.hip" else ())) for u in ("plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_synth.hip", "retrieval.hip")] + \
+UNITS = [("engine.hip", [], _ENGINE_DEPS), ("debug.hip", [], ("debug.hip", "../../include/rvc_mi355x_debug.h") + _INT_DEPS), ("calib.hip", [], ("calib.hip",))] + [(u, [], (u,) + _INT_DEPS + (("rmblock.hip.h",) if u == "model_rmvpe.hip" else ())) for u in ("plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_synth.hip", "retrieval.hip")] + \
         [("igemm2_inst.hip", ["-DRVC_IGEMM2_CFG=%d" % c], ("igemm2_inst.hip",) + _IGEMM_DEPS) for c in range(5)] + \
         [("igemm_tiled_inst.hip", ["-DRVC_TILED_PART=%d" % c], ("igemm_tiled_inst.hip",) + _IGEMM_DEPS) for c in range(4)] + \
         [("igemm2w_inst.hip", ["-DRVC_G2W_PART=%d" % c], ("igemm2w_inst.hip",) + _IGEMM_DEPS) for c in range(3)] + \
@@ -72,11 +72,11 @@ def _tmp_name(path: str) -> str:
 
 
 def source_hash() -> str:
-    """sha256 over the library's sources (+ the public header), first 16 hex digits.  It is compiled into the binary
+    """sha256 over the library's sources (+ the public header and the test hooks' header), first 16 hex digits.  It is compiled into the binary
     (`rvc_version()` ends in "src:<hash>"), so a tested .so can be tied to the sources it was built from."""
     import hashlib
     h = hashlib.sha256()
-    for f in [os.path.join(CSRC, n) for n in SOURCES] + [os.path.join(os.path.dirname(_HERE), "include", "rvc_mi355x.h")]:
+    for f in [os.path.join(CSRC, n) for n in SOURCES] + [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("rvc_mi355x.h", "rvc_mi355x_debug.h")]:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
             h.update(fh.read())

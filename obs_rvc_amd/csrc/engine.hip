@@ -5,7 +5,6 @@
 // All compute is launched as hand-written gfx950 kernels (kernels.hip.h); nothing here falls
 // back to a CPU path: without a HIP device every entry point returns RVC_BACKEND.
 #include "engine_int.h"
-#include "../../include/rvc_mi355x_debug.h"
 #include "crossfade.hip.h"
 #include <chrono>
 
@@ -1237,606 +1236,6 @@ rvc_status rvc_input_gate(rvc_engine *e, const float *hist3zc, const float *chun
     });
 }
 
-// timeline of the last call (RVC_STAMPS=1): "name us-since-first-stamp" lines
-extern "C" int rvc_debug_stamps(rvc_engine *e, char *buf, size_t cap)
-{
-    if (!e || !e->last_plan || !e->last_plan->d_stamps) return 0;
-    Plan &pl = *e->last_plan;
-    std::vector<unsigned long long> h(pl.stamp_names.size());
-    if (hipMemcpy(h.data(), pl.d_stamps, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    unsigned long long t0 = ~0ull; for (auto v : h) t0 = std::min(t0, v);
-    std::string out;
-    for (size_t i = 0; i < h.size(); i++) { char ln[96]; snprintf(ln, sizeof ln, "%s %.2f\n", pl.stamp_names[i].c_str(), (double)(h[i] - t0) / 100.0); out += ln; }
-    if (out.size() + 1 > cap) return -1;
-    memcpy(buf, out.c_str(), out.size() + 1);
-    return (int)h.size();
-}
-
-#ifdef RVC_TUNING
-// tuning build only: time one Conv1d(Cin -> M, KW taps, dilation dil, stride 1, "same" padding) over N positions and `streams` streams,
-// through whatever kernel the planner (or RVC_FORCE_CFG) picks; returns microseconds per launch
-double rvc_debug_conv_bench(rvc_engine *e, int M, int Cin, int KW, int dil, int N, int iters, int pre_act, int streams, int act)
-{
-    double us = -1.0;
-    (void)guarded(e, [&]() {
-        std::vector<float> w((size_t)M * Cin * KW), bias(M, 0.1f);
-        for (size_t i = 0; i < w.size(); i++) w[i] = (float)((i * 2654435761u) % 1000) / 1000.0f - 0.5f;
-        ConvW cw = prep_conv(w.data(), bias.data(), M, Cin, KW, 1);
-        const int Bb = streams > 0 ? streams : 1;
-        Plan pl; pl.B = Bb;
-        const int pad = (KW - 1) * dil / 2;
-        T1 x = make_t1(pl.arena, Bb, Cin, N, (pad + 3) / 4 * 4), y = make_t1(pl.arena, Bb, M, N, 0);
-        std::vector<float> hx((size_t)Cin * x.ld, 0.25f);
-        for (int b = 0; b < Bb; b++) HIPCHK(hipMemcpy(x.p + (long long)b * x.bs - x.halo, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
-        ConvOpts o; if (pre_act) { o.pre_act = ACT_LRELU; o.pre_slope = 0.1f; }
-        o.act = act;
-        add_conv1d(pl, cw, x, y, 1, pad, dil, o);
-        HIPCHK(hipDeviceSynchronize());
-        for (int i = 0; i < 3; i++) for (auto &op : pl.ops.v) op(e->stream);
-        hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-        HIPCHK(hipEventRecord(a, e->stream));
-        for (int i = 0; i < iters; i++) for (auto &op : pl.ops.v) op(e->stream);
-        HIPCHK(hipEventRecord(b, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        float ms; HIPCHK(hipEventElapsedTime(&ms, a, b));
-        us = ms * 1e3 / iters;
-        (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-        free_conv(cw);
-        return RVC_OK;
-    });
-    return us;
-}
-#endif
-
-// test aid for the folded LayerNorm (IgemmP::ln_*): two launches on deterministic data against a double-precision host evaluation --
-//   (1) y1 = W1 . LN(x) + b1 through the folded weights on the RAW x, publishing the column statistics;
-//   (2) y2 = W2 . z + b2 + LN(x), the residual normalised on the fly from the statistics launch (1) published (needs M2 = K rows).
-// Tile shape / K split are whatever the planner (or RVC_FORCE_CFG) picks; the planner forces an in-workgroup K split.  Returns the
-// largest |gpu - host| / rms(host) over both outputs and the published (mean, rstd); negative on failure.  `offset` = mean of the
-// tensor being normalised (spread ~1.15): large values probe the cancellation in the one-pass statistics.
-double rvc_debug_ln_fold_check(rvc_engine *e, int M, int K, int N, float offset)
-{
-    double worst = -1.0;
-    (void)guarded(e, [&]() {
-        if (K % 16 != 0) throw ShapeError("K must be a multiple of 16");
-        auto rnd = [](size_t i, unsigned salt) { return (float)((((i + 1) * 2654435761u) ^ (salt * 40503u) ^ (i >> 5)) % 2001) / 1000.0f - 1.0f; };
-        std::vector<float> w1((size_t)M * K), b1(M), w2((size_t)K * M), b2(K), g(K), beta(K), hx((size_t)K * N), hz((size_t)M * N);
-        for (size_t i = 0; i < w1.size(); i++) w1[i] = 0.5f * rnd(i, 1);
-        for (size_t i = 0; i < w2.size(); i++) w2[i] = 0.5f * rnd(i, 2);
-        for (int m = 0; m < M; m++) b1[m] = 0.1f * rnd(m, 3);
-        for (int k = 0; k < K; k++) { b2[k] = 0.1f * rnd(k, 4); g[k] = 1.0f + 0.3f * rnd(k, 5); beta[k] = 0.2f * rnd(k, 6); }
-        for (size_t i = 0; i < hx.size(); i++) hx[i] = 2.0f * rnd(i, 7) + offset;        // column mean = offset, spread ~1.15
-        for (size_t i = 0; i < hz.size(); i++) hz[i] = rnd(i, 8);
-        float *wsum = nullptr;
-        ConvW c1 = ModelCV::fold_ln(w1.data(), b1.data(), M, K, g.data(), beta.data(), &wsum);
-        ConvW c2 = prep_conv(w2.data(), b2.data(), K, M, 1, 1);
-        float *dg = upload_f(g), *dbeta = upload_f(beta);
-        Plan pl; pl.B = 1;
-        T1 x = make_t1(pl.arena, 1, K, N, 0), y1 = make_t1(pl.arena, 1, M, N, 0), z = make_t1(pl.arena, 1, M, N, 0), y2 = make_t1(pl.arena, 1, K, N, 0);
-        float *st = pl.arena.floats((size_t)2 * N + 16);
-        for (int k = 0; k < K; k++) HIPCHK(hipMemcpy(x.p + (long long)k * x.ld, &hx[(size_t)k * N], (size_t)N * 4, hipMemcpyHostToDevice));
-        for (int m = 0; m < M; m++) HIPCHK(hipMemcpy(z.p + (long long)m * z.ld, &hz[(size_t)m * N], (size_t)N * 4, hipMemcpyHostToDevice));
-        { ConvOpts o; o.ln_wsum = wsum; o.ln_stats_out = st; o.ln_rows = K; add_conv1d(pl, c1, x, y1, 1, 0, 1, o); }
-        { ConvOpts o; o.res = x.p; o.res_cs = x.ld; o.res_bs = x.bs; o.ln_stats_in = st; o.ln_g = dg; o.ln_b = dbeta; add_conv1d(pl, c2, z, y2, 1, 0, 1, o); }
-        HIPCHK(hipDeviceSynchronize());
-        for (auto &op : pl.ops.v) op(e->stream);
-        HIPCHK(hipStreamSynchronize(e->stream));
-        HIPCHK(hipGetLastError());
-        // host: LayerNorm over the K rows of every column (two-pass, double), then the two layers
-        std::vector<double> ln((size_t)K * N), mean(N), rstd(N);
-        for (int n = 0; n < N; n++) {
-            double s = 0; for (int k = 0; k < K; k++) s += hx[(size_t)k * N + n];
-            const double mu = s / K; double q = 0;
-            for (int k = 0; k < K; k++) { const double d = hx[(size_t)k * N + n] - mu; q += d * d; }
-            mean[n] = mu; rstd[n] = 1.0 / std::sqrt(q / K + 1e-5);
-            for (int k = 0; k < K; k++) ln[(size_t)k * N + n] = (hx[(size_t)k * N + n] - mu) * rstd[n] * g[k] + beta[k];
-        }
-        double err = 0.0;
-        std::vector<float> row(N), hst((size_t)2 * N);
-        {
-            double ss = 0; std::vector<double> ref((size_t)M * N);
-            for (int m = 0; m < M; m++) for (int n = 0; n < N; n++) {
-                double a = b1[m]; for (int k = 0; k < K; k++) a += (double)w1[(size_t)m * K + k] * ln[(size_t)k * N + n];
-                ref[(size_t)m * N + n] = a; ss += a * a;
-            }
-            const double rms1 = std::sqrt(ss / ((double)M * N)) + 1e-12;
-            for (int m = 0; m < M; m++) {
-                HIPCHK(hipMemcpy(row.data(), y1.p + (long long)m * y1.ld, (size_t)N * 4, hipMemcpyDeviceToHost));
-                for (int n = 0; n < N; n++) err = std::max(err, std::fabs((double)row[n] - ref[(size_t)m * N + n]) / rms1);
-            }
-        }
-        {
-            double ss = 0; std::vector<double> ref((size_t)K * N);
-            for (int k = 0; k < K; k++) for (int n = 0; n < N; n++) {
-                double a = b2[k]; for (int m = 0; m < M; m++) a += (double)w2[(size_t)k * M + m] * hz[(size_t)m * N + n];
-                a += ln[(size_t)k * N + n];
-                ref[(size_t)k * N + n] = a; ss += a * a;
-            }
-            const double rms2 = std::sqrt(ss / ((double)K * N)) + 1e-12;
-            for (int k = 0; k < K; k++) {
-                HIPCHK(hipMemcpy(row.data(), y2.p + (long long)k * y2.ld, (size_t)N * 4, hipMemcpyDeviceToHost));
-                for (int n = 0; n < N; n++) err = std::max(err, std::fabs((double)row[n] - ref[(size_t)k * N + n]) / rms2);
-            }
-        }
-        HIPCHK(hipMemcpy(hst.data(), st, (size_t)2 * N * 4, hipMemcpyDeviceToHost));
-        for (int n = 0; n < N; n++) {
-            err = std::max(err, std::fabs((double)hst[2 * n] - mean[n]) / (std::fabs(mean[n]) + 1.0));
-            err = std::max(err, std::fabs((double)hst[2 * n + 1] - rstd[n]) / rstd[n]);
-        }
-        worst = err;
-        free_conv(c1); free_conv(c2);
-        wfree(wsum); wfree(dg); wfree(dbeta);
-        return RVC_OK;
-    });
-    return worst;
-}
-
-#ifdef RVC_TUNING
-// tuning build only (-DRVC_KPROBE): one launch of a Conv1d with per-wave phase stamps (device wall clock, 10 ns ticks):
-// out[wave][16]; returns the number of waves (workgroups * waves per workgroup), *event_us = the dispatch's own begin..end time
-int rvc_debug_conv_probe(rvc_engine *e, int M, int Cin, int KW, int dil, int N, unsigned long long *out, size_t cap_waves, double *event_us, int *waves_per_wg)
-{
-    int nw = -1;
-    (void)guarded(e, [&]() {
-        std::vector<float> w((size_t)M * Cin * KW), bias(M, 0.1f);
-        for (size_t i = 0; i < w.size(); i++) w[i] = (float)((i * 2654435761u) % 1000) / 1000.0f - 0.5f;
-        ConvW cw = prep_conv(w.data(), bias.data(), M, Cin, KW, 1);
-        Plan pl; pl.B = 1;
-        const int pad = (KW - 1) * dil / 2;
-        T1 x = make_t1(pl.arena, 1, Cin, N, (pad + 3) / 4 * 4), y = make_t1(pl.arena, 1, M, N, 0);
-        std::vector<float> hx((size_t)Cin * x.ld, 0.25f);
-        HIPCHK(hipMemcpy(x.p - x.halo, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
-        unsigned long long *d_probe; const size_t pbytes = (size_t)1 << 24;
-        HIPCHK(hipMalloc(&d_probe, pbytes)); HIPCHK(hipMemset(d_probe, 0, pbytes));
-        g_kprobe = d_probe;
-        ConvOpts o; if (const char *a = tune_env("RVC_BENCH_ACT")) o.act = atoi(a);
-        add_conv1d(pl, cw, x, y, 1, pad, dil, o);
-        g_kprobe = nullptr;
-        HIPCHK(hipDeviceSynchronize());
-        for (int i = 0; i < 5; i++) for (auto &op : pl.ops.v) op(e->stream);
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemset(d_probe, 0, pbytes));
-        HIPCHK(hipDeviceSynchronize());
-        pl.profile = true; pl.prof_used = 0;
-        for (auto &op : pl.ops.v) op(e->stream);
-        HIPCHK(hipDeviceSynchronize());
-        float t = 0.f; HIPCHK(hipEventElapsedTime(&t, pl.prof[0].a, pl.prof[0].b));
-        if (event_us) *event_us = t * 1e3;
-        nw = g_last_wgs * g_last_waves;
-        if (waves_per_wg) *waves_per_wg = g_last_waves;
-        if ((size_t)nw <= cap_waves && (size_t)nw * 128 <= pbytes) HIPCHK(hipMemcpy(out, d_probe, (size_t)nw * 128, hipMemcpyDeviceToHost));
-        else nw = -2;
-        (void)hipFree(d_probe);
-        free_conv(cw);
-        return RVC_OK;
-    });
-    return nw;
-}
-#endif
-
-// test aid: one Conv1d(Cin -> M, KW taps, dilation dil, "same" padding, bias, optional input LeakyReLU) over N positions and `streams`
-// streams on deterministic data, through whatever tile configuration the planner (or RVC_FORCE_CFG) picks, against a double-precision
-// host evaluation.  Returns the largest |gpu - host| / (rms(host) + 1e-12); negative on failure.
-double rvc_debug_conv_check(rvc_engine *e, int M, int Cin, int KW, int dil, int N, int streams, int pre_act)
-{
-    double worst = -1.0;
-    (void)guarded(e, [&]() {
-        std::vector<float> w((size_t)M * Cin * KW), bias(M);
-        for (size_t i = 0; i < w.size(); i++) w[i] = (float)((i * 2654435761u) % 1000) / 1000.0f - 0.5f;
-        for (int m = 0; m < M; m++) bias[m] = 0.01f * (float)(m % 7) - 0.02f;
-        ConvW cw = prep_conv(w.data(), bias.data(), M, Cin, KW, 1);
-        Plan pl; pl.B = streams;
-        const int pad = (KW - 1) * dil / 2, halo = (pad + 3) / 4 * 4;
-        T1 x = make_t1(pl.arena, streams, Cin, N, halo), y = make_t1(pl.arena, streams, M, N, 0);
-        std::vector<float> hx((size_t)streams * Cin * N);
-        for (size_t i = 0; i < hx.size(); i++) hx[i] = (float)(((i * 40503u) ^ (i >> 3)) % 2001) / 1000.0f - 1.0f;
-        for (int b = 0; b < streams; b++)
-            for (int c = 0; c < Cin; c++)
-                HIPCHK(hipMemcpy(x.p + (long long)b * x.bs + (long long)c * x.ld, &hx[((size_t)b * Cin + c) * N], (size_t)N * 4, hipMemcpyHostToDevice));
-        ConvOpts o; if (pre_act) { o.pre_act = ACT_LRELU; o.pre_slope = 0.1f; }
-        add_conv1d(pl, cw, x, y, 1, pad, dil, o);
-        HIPCHK(hipDeviceSynchronize());
-        for (auto &op : pl.ops.v) op(e->stream);
-        HIPCHK(hipStreamSynchronize(e->stream));
-        HIPCHK(hipGetLastError());
-        // host evaluation in double, the (stream, output row) pairs dealt to the host's threads (a test aid: the full-size shapes are 1e9 MACs each)
-        std::vector<float> hy((size_t)streams * M * N);
-        for (int b = 0; b < streams; b++)
-            HIPCHK(hipMemcpy2D(&hy[(size_t)b * M * N], (size_t)N * 4, y.p + (long long)b * y.bs, (size_t)y.ld * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
-        const int nthr = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        std::vector<double> errs(nthr, 0.0), sss(nthr, 0.0);
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nthr; t++)
-            pool.emplace_back([&, t]() {
-                std::vector<double> ref((size_t)N);
-                for (long long bm = t; bm < (long long)streams * M; bm += nthr) {
-                    const int b = (int)(bm / M), m = (int)(bm % M);
-                    for (int n = 0; n < N; n++) {
-                        double a = bias[m];
-                        for (int c = 0; c < Cin; c++)
-                            for (int k = 0; k < KW; k++) {
-                                const int tt = n + k * dil - pad;
-                                if (tt < 0 || tt >= N) continue;
-                                double v = hx[((size_t)b * Cin + c) * N + tt];
-                                if (pre_act && v < 0) v *= 0.1f;
-                                a += (double)w[((size_t)m * Cin + c) * KW + k] * v;
-                            }
-                        ref[n] = a; sss[t] += a * a;
-                    }
-                    const float *row = &hy[((size_t)b * M + m) * N];
-                    for (int n = 0; n < N; n++) errs[t] = std::max(errs[t], std::fabs((double)row[n] - ref[n]));
-                }
-            });
-        for (auto &th : pool) th.join();
-        double err = 0.0, ss = 0.0; const size_t cnt = (size_t)streams * M * N;
-        for (int t = 0; t < nthr; t++) { err = std::max(err, errs[t]); ss += sss[t]; }
-        worst = err / (std::sqrt(ss / (double)std::max<size_t>(cnt, 1)) + 1e-12);
-        free_conv(cw);
-        return RVC_OK;
-    });
-    return worst;
-}
-
-// test aid: one Conv2d(Cin -> M, 3x3, pad 1, bias, ReLU) [kind 0] or ConvTranspose2d(Cin -> M, 3x3, stride 2, pad 1, output_pad 1, bias, ReLU) [kind 1] on
-// `streams` images of H x W (RMVPE's layers, rvc/src/f0/rmvpe.rs:235-238), residual 0 = none, 1 = + a residual tensor, 2 = accumulate into the
-// output; deterministic data, whatever kernel the planner (or a hook) picks, against a double-precision host evaluation.
-// Returns the largest |gpu - host| / (rms(host) + 1e-12); negative on failure.
-double rvc_debug_conv2d_check(rvc_engine *e, int M, int Cin, int H, int W, int streams, int kind, int residual)
-{
-    double worst = -1.0;
-    (void)guarded(e, [&]() {
-        if (kind == 1 && residual) throw ShapeError("transposed test layer takes no residual");
-        std::vector<float> w((size_t)M * Cin * 9), bias(M);
-        for (size_t i = 0; i < w.size(); i++) w[i] = (float)((i * 2654435761u) % 1000) / 1000.0f - 0.5f;
-        for (int m = 0; m < M; m++) bias[m] = 0.01f * (float)(m % 7) - 0.02f;
-        // Conv2d: w [M][Cin][3][3]; ConvTranspose2d: w [Cin][M][3][3]
-        ConvW cw = kind == 0 ? prep_conv(w.data(), bias.data(), M, Cin, 9, 1) : prep_convT2d(w.data(), bias.data(), Cin, M);
-        Plan pl; pl.B = streams;
-        const int OH = kind ? 2 * H : H, OW = kind ? 2 * W : W;
-        T2 x = make_t2(pl.arena, streams, Cin, H, W), y = make_t2(pl.arena, streams, M, OH, OW), r = make_t2(pl.arena, streams, M, OH, OW);
-        std::vector<float> hx((size_t)streams * Cin * H * W), hr((size_t)streams * M * OH * OW);
-        for (size_t i = 0; i < hx.size(); i++) hx[i] = (float)(((i * 40503u) ^ (i >> 3)) % 2001) / 1000.0f - 1.0f;
-        for (size_t i = 0; i < hr.size(); i++) hr[i] = (float)(((i * 9973u) ^ (i >> 2)) % 1001) / 1000.0f - 0.5f;
-        for (int b = 0; b < streams; b++)
-            for (int c = 0; c < Cin; c++)
-                HIPCHK(hipMemcpy2D(x.p + (long long)b * x.bs + (long long)c * x.cs, (size_t)x.ld * 4, &hx[(((size_t)b * Cin + c) * H) * W], (size_t)W * 4, (size_t)W * 4, H, hipMemcpyHostToDevice));
-        for (int b = 0; b < streams; b++)
-            for (int c = 0; c < M; c++) {
-                T2 &dst = residual == 2 ? y : r;
-                HIPCHK(hipMemcpy2D(dst.p + (long long)b * dst.bs + (long long)c * dst.cs, (size_t)dst.ld * 4, &hr[(((size_t)b * M + c) * OH) * OW], (size_t)OW * 4, (size_t)OW * 4, OH, hipMemcpyHostToDevice));
-            }
-        ConvOpts o; o.act = ACT_RELU;
-        if (residual == 1) { o.res = r.p; o.res_cs = r.cs; o.res_bs = r.bs; o.res_rs = r.ld; }
-        if (residual == 2) o.accumulate = true;
-        if (kind == 0) add_conv2d(pl, cw, x, y, o); else add_convT2d(pl, cw, x, y, o);
-        HIPCHK(hipDeviceSynchronize());
-        for (auto &op : pl.ops.v) op(e->stream);
-        HIPCHK(hipStreamSynchronize(e->stream));
-        HIPCHK(hipGetLastError());
-        std::vector<float> hy((size_t)OH * OW);
-        std::vector<double> ref((size_t)OH * OW);
-        double err = 0.0, ss = 0.0; size_t cnt = 0;
-        for (int b = 0; b < streams; b++)
-            for (int m = 0; m < M; m++) {
-                HIPCHK(hipMemcpy2D(hy.data(), (size_t)OW * 4, y.p + (long long)b * y.bs + (long long)m * y.cs, (size_t)y.ld * 4, (size_t)OW * 4, OH, hipMemcpyDeviceToHost));
-                for (int oh = 0; oh < OH; oh++)
-                    for (int ow = 0; ow < OW; ow++) {
-                        double a = bias[m];
-                        for (int c = 0; c < Cin; c++) {
-                            const float *xc = &hx[(((size_t)b * Cin + c) * H) * W];
-                            for (int kh = 0; kh < 3; kh++)
-                                for (int kw = 0; kw < 3; kw++) {
-                                    if (kind == 0) {
-                                        const int ih = oh + kh - 1, iw = ow + kw - 1;
-                                        if (ih < 0 || ih >= H || iw < 0 || iw >= W) continue;
-                                        a += (double)w[(((size_t)m * Cin + c) * 3 + kh) * 3 + kw] * xc[(size_t)ih * W + iw];
-                                    } else {
-                                        // out[oh] += w[kh] * in[ih] with oh = 2 ih - 1 + kh
-                                        const int th = oh + 1 - kh, tw = ow + 1 - kw;
-                                        if (th < 0 || tw < 0 || (th & 1) || (tw & 1)) continue;
-                                        const int ih = th / 2, iw = tw / 2;
-                                        if (ih >= H || iw >= W) continue;
-                                        a += (double)w[(((size_t)c * M + m) * 3 + kh) * 3 + kw] * xc[(size_t)ih * W + iw];
-                                    }
-                                }
-                        }
-                        a = a > 0 ? a : 0;
-                        if (residual) a += hr[(((size_t)b * M + m) * OH + oh) * OW + ow];
-                        ref[(size_t)oh * OW + ow] = a; ss += a * a; cnt++;
-                    }
-                for (size_t i = 0; i < ref.size(); i++) err = std::max(err, std::fabs((double)hy[i] - ref[i]));
-            }
-        worst = err / (std::sqrt(ss / (double)std::max<size_t>(cnt, 1)) + 1e-12);
-        free_conv(cw);
-        return RVC_OK;
-    });
-    return worst;
-}
-
-// test aid: one convolution layer as the models build it (include/rvc_mi355x_debug.h, tests/test_gpu_layers.py).  The caller owns every float of the
-// tensors' allocations: what the layer must not touch is compared bit for bit afterwards.
-// the whole allocation of a test aid's tensor: its start and geo = (size, offset of element (0, 0, 0), C, T, ld, bs, cs, H)
-struct DebugGeo { float *base = nullptr; long long g[8] = {0, 0, 0, 0, 0, 0, 0, 1}; };
-static DebugGeo debug_geo1(const T1 &t)
-{
-    DebugGeo q; const size_t gd = t1_guard(t.ld);
-    q.base = t.p - gd - t.halo; q.g[0] = (long long)t.B * t.bs + 2 * (long long)gd; q.g[1] = (long long)gd + t.halo; q.g[2] = t.C; q.g[3] = t.T; q.g[4] = t.ld; q.g[5] = t.bs; q.g[6] = t.ld;
-    return q;
-}
-
-int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w, const float *bias, float *x, float *y, float *r, long long *geo)
-{
-    return (int)guarded(e, [&]() {
-        if (!s || !geo || s->streams < 1 || s->form < 0 || s->form > 4 || ((s->form == 2 || s->form == 3) && (s->n < 1 || s->n > 4))) throw ShapeError("layer spec");
-        const int B = s->streams, form = s->form, n = form == 3 ? 2 : s->n;
-        Plan pl; pl.B = B;
-        using Geo = DebugGeo;
-        auto g1 = debug_geo1;
-        auto g2 = [](const T2 &t) { Geo q; const size_t gd = t2_guard(t.ld); q.base = t.p - gd - t.ld - 1; q.g[0] = (long long)t.B * t.bs + 2 * (long long)gd; q.g[1] = (long long)gd + t.ld + 1; q.g[2] = t.C; q.g[3] = t.W; q.g[4] = t.ld; q.g[5] = t.bs; q.g[6] = t.cs; q.g[7] = t.H; return q; };
-        Geo gx, gy, gr;
-        T1 x1, y1, r1; T2 x2, y2, r2;
-        const int yrows = form == 2 ? n * s->cout : (form == 3 ? 3 * s->cout + 16 : (s->glu ? s->cout / 2 : s->cout));
-        if (form == 4) {
-            x2 = make_t2(pl.arena, B, s->cin, s->t_in, s->t_out); gx = g2(x2);
-            if (s->y_ws) {
-                y1 = make_t1(pl.arena, B, s->cout * s->t_out, s->t_in, 0); gy = g1(y1);
-                y2.p = y1.p; y2.B = B; y2.C = s->cout; y2.H = s->t_in; y2.W = s->t_out; y2.cs = s->t_out * y1.ld; y2.ld = 1; y2.bs = y1.bs;
-            } else { y2 = make_t2(pl.arena, B, s->cout, s->t_in, s->t_out); gy = g2(y2); }
-            if (s->res == 1) { r2 = make_t2(pl.arena, B, s->cout, s->t_in, s->t_out); gr = g2(r2); }
-        } else {
-            x1 = make_t1(pl.arena, B, (form == 2 && s->x_grouped) ? n * s->cin : s->cin, s->t_in, s->x_halo); gx = g1(x1);
-            y1 = make_t1(pl.arena, B, yrows, s->t_out, s->y_halo); gy = g1(y1);
-            if (s->res == 1) { r1 = make_t1(pl.arena, B, (form == 2 && s->res_grouped) ? n * s->cout : s->cout, s->t_out, s->r_halo); gr = g1(r1); }
-        }
-        if (s->res == 2) { r1 = make_t1(pl.arena, 1, 1, s->t_out, 0); gr = g1(r1); }
-        for (int i = 0; i < 8; i++) { geo[i] = gx.g[i]; geo[8 + i] = gy.g[i]; geo[16 + i] = gr.g[i]; }
-        if (!x) return RVC_OK;
-        if (!y || !w || ((s->res == 1 || s->res == 2) && !r)) throw ShapeError("layer buffers");
-        HIPCHK(hipMemcpy(gx.base, x, (size_t)gx.g[0] * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(gy.base, y, (size_t)gy.g[0] * 4, hipMemcpyHostToDevice));
-        if (gr.base) HIPCHK(hipMemcpy(gr.base, r, (size_t)gr.g[0] * 4, hipMemcpyHostToDevice));
-        ConvOpts o;
-        o.act = s->act; o.slope = s->slope; o.scale = s->scale; o.accumulate = s->accumulate != 0;
-        o.pre_act = s->pre_act; o.pre_slope = s->pre_slope; o.no_bias = s->no_bias != 0; o.final_out = s->final_out != 0; o.glu = s->glu != 0;
-        if (s->res == 1 && form == 4) { o.res = r2.p; o.res_cs = r2.cs; o.res_bs = r2.bs; o.res_rs = r2.ld; }
-        else if (s->res == 1) { o.res = r1.p; o.res_cs = r1.ld; o.res_bs = r1.bs; }
-        else if (s->res == 2) { o.res = r1.p; o.res_cs = 0; o.res_bs = 0; }
-        else if (s->res == 3 && form == 4) { o.res = y2.p; o.res_cs = y2.cs; o.res_bs = y2.bs; o.res_rs = y2.ld; }
-        else if (s->res == 3) { o.res = y1.p; o.res_cs = y1.ld; o.res_bs = y1.bs; }
-        else if (s->res == 4 && form != 4) { o.res = x1.p; o.res_cs = x1.ld; o.res_bs = x1.bs; }
-        if (s->y_ws) o.y_ws = y1.ld;
-        std::vector<ConvW> cws;
-        float *pair = nullptr;
-        if (form == 0 && s->glu) {
-            std::vector<float> wp, bp;
-            if (!bias) throw ShapeError("GLU layer without bias");
-            glu_pack_rows(w, bias, s->cout / 2, (size_t)s->cin * s->kw, wp, bp);
-            cws.push_back(prep_conv(wp.data(), bp.data(), s->cout, s->cin, s->kw, 1));
-        } else if (form == 0) cws.push_back(prep_conv(w, bias, s->cout, s->cin, s->kw, s->groups));
-        else if (form == 1) cws.push_back(prep_convT1d(w, bias, s->cin, s->cout, s->kw, s->stride));
-        else if (form == 4) cws.push_back(prep_conv(w, bias, s->cout, s->cin, 9, 1));
-        else {
-            size_t ow = 0;
-            for (int j = 0; j < n; j++) {
-                const int kw = form == 3 ? 1 : s->kws[j];
-                cws.push_back(prep_conv(w + ow, bias ? bias + (size_t)j * s->cout : nullptr, s->cout, s->cin, kw, 1));
-                ow += (size_t)s->cout * s->cin * kw;
-            }
-            if (form == 2 && n > 1) { std::vector<ConvW *> m; for (ConvW &c : cws) m.push_back(&c); merge_convs(m); }
-            if (form == 3) { if (!bias) throw ShapeError("pair launch without bias"); pair = upload_f(bias, (size_t)2 * s->cout); }
-        }
-        try {
-            if (form == 0) add_conv1d(pl, cws[0], x1, y1, s->stride, s->pad, s->dil, o);
-            else if (form == 1) add_convT1d(pl, cws[0], x1, y1, s->pad, o);
-            else if (form == 2) {
-                std::vector<const ConvW *> cp; std::vector<int> pads, dils;
-                for (int j = 0; j < n; j++) { cp.push_back(&cws[j]); pads.push_back(s->pads[j]); dils.push_back(s->dils[j]); }
-                add_conv1d_multi(pl, cp, x1, s->x_grouped != 0, y1, pads, dils, o, s->res_grouped != 0);
-            } else if (form == 3) add_conv1d_two(pl, cws[0], cws[1], pair, x1, y1.rows(16, s->cout), y1.rows(16 + 2 * s->cout, s->cout));
-            else add_conv2d(pl, cws[0], x2, y2, o);
-            HIPCHK(hipDeviceSynchronize());
-            for (auto &op : pl.ops.v) op(e->stream);
-            HIPCHK(hipStreamSynchronize(e->stream));
-            HIPCHK(hipGetLastError());
-        } catch (...) {
-            for (ConvW &c : cws) free_conv(c);
-            if (pair) wfree(pair);
-            throw;
-        }
-        for (ConvW &c : cws) free_conv(c);
-        if (pair) wfree(pair);
-        HIPCHK(hipMemcpy(x, gx.base, (size_t)gx.g[0] * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(y, gy.base, (size_t)gy.g[0] * 4, hipMemcpyDeviceToHost));
-        if (gr.base) HIPCHK(hipMemcpy(r, gr.base, (size_t)gr.g[0] * 4, hipMemcpyDeviceToHost));
-        return RVC_OK;
-    });
-}
-
-// a launch that throws while the stream is capturing must not leave it in capture mode: the capture is ended and its partial graph dropped
-static void end_failed_capture(hipStream_t st) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); }
-
-// test aid: one attention / LayerNorm / GRU op as the models build it (include/rvc_mi355x_debug.h, tests/test_gpu_ops.py).  As for rvc_debug_layer, the caller
-// owns every float of the tensors' allocations.
-int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, const float *w1, float *x, float *y, int *status, long long *geo)
-{
-    return (int)guarded(e, [&]() {
-        if (!s || !geo || s->streams < 1 || s->op < 0 || s->op > 3 || s->T < 1 || s->reps < 1 || s->x_halo < 0 || s->y_halo < 0) throw ShapeError("op spec");
-        if ((s->op <= 1 && (s->E < 1 || s->heads < 1 || s->E % s->heads)) || (s->op == 1 && s->window < 0) || (s->op == 2 && s->C < 1) || (s->op == 3 && s->H < 1))
-            throw ShapeError("op spec");
-        const int B = s->streams, op = s->op;
-        Plan pl; pl.B = B;
-        T1 x1, y1;
-        if (op <= 1) { x1 = make_t1(pl.arena, B, 3 * s->E, s->T, s->x_halo); y1 = make_t1(pl.arena, B, s->E, s->T, s->y_halo); }
-        else if (op == 2) x1 = make_t1(pl.arena, B, s->C, s->T, s->x_halo);
-        else { x1 = make_t1(pl.arena, B, 6 * s->H, s->T, s->x_halo); y1 = make_t1(pl.arena, B, 2 * s->H, s->T, s->y_halo); }
-        const DebugGeo gx = debug_geo1(x1), gy = op == 2 ? DebugGeo() : debug_geo1(y1);
-        for (int i = 0; i < 8; i++) { geo[i] = gx.g[i]; geo[8 + i] = gy.g[i]; }
-        if (!x) return RVC_OK;
-        if ((op != 2 && !y) || (op != 0 && (!w0 || !w1)) || (op == 3 && !status)) throw ShapeError("op buffers");
-        HIPCHK(hipMemcpy(gx.base, x, (size_t)gx.g[0] * 4, hipMemcpyHostToDevice));
-        if (gy.base) HIPCHK(hipMemcpy(gy.base, y, (size_t)gy.g[0] * 4, hipMemcpyHostToDevice));
-        std::vector<float *> wts;          // device copies of the weights, freed on every exit
-        int *d_status = nullptr;
-        try {
-            if (op == 0) add_attention(pl, x1, y1, s->heads);
-            else if (op == 1) {
-                const size_t n = (size_t)(2 * s->window + 1) * (s->E / s->heads);
-                wts.push_back(upload_f(w0, n)); wts.push_back(upload_f(w1, n));
-                add_relpos_attention(pl, x1, y1, s->heads, wts[0], wts[1], s->window);
-            } else if (op == 2) {
-                wts.push_back(upload_f(w0, (size_t)s->C)); wts.push_back(upload_f(w1, (size_t)s->C));
-                add_layernorm(pl, x1, wts[0], wts[1]);
-            } else {
-                const int H = s->H;
-                const float *whh_dir[2] = {w0, w0 + (size_t)3 * H * H};
-                std::vector<float> wt, wr;
-                gru_prep_whh(whh_dir, H, wt, wr);
-                wts.push_back(upload_f(wt)); wts.push_back(upload_f(wr)); wts.push_back(upload_f(w1, (size_t)6 * H));
-                d_status = (int *)pl.arena.alloc((size_t)B * sizeof(int));
-                HIPCHK(hipMemset(d_status, 0, (size_t)B * sizeof(int)));
-                add_gru(pl, x1, y1, H, wts[1], wts[0], wts[2], d_status, 1);
-            }
-            HIPCHK(hipDeviceSynchronize());
-            if (s->graph) {
-                hipGraph_t g; hipGraphExec_t ge;
-                HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-                try { for (auto &o : pl.ops.v) o(e->stream); } catch (...) { end_failed_capture(e->stream); throw; }
-                HIPCHK(hipStreamEndCapture(e->stream, &g));
-                const hipError_t ie = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(g);
-                HIPCHK(ie);
-                hipError_t le = hipSuccess;
-                for (int r = 0; r < s->reps && le == hipSuccess; r++) le = hipGraphLaunch(ge, e->stream);
-                const hipError_t se = hipStreamSynchronize(e->stream);
-                (void)hipGraphExecDestroy(ge);
-                HIPCHK(le); HIPCHK(se);
-            } else {
-                for (int r = 0; r < s->reps; r++) for (auto &o : pl.ops.v) o(e->stream);
-                HIPCHK(hipStreamSynchronize(e->stream));
-            }
-            HIPCHK(hipGetLastError());
-        } catch (...) {
-            for (float *p : wts) wfree(p);
-            throw;
-        }
-        for (float *p : wts) wfree(p);
-        HIPCHK(hipMemcpy(x, gx.base, (size_t)gx.g[0] * 4, hipMemcpyDeviceToHost));
-        if (gy.base) HIPCHK(hipMemcpy(y, gy.base, (size_t)gy.g[0] * 4, hipMemcpyDeviceToHost));
-        if (d_status) HIPCHK(hipMemcpy(status, d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
-        return RVC_OK;
-    });
-}
-
-// test aid: the mel front end, ContentVec's first layer, the pitch decode and the NSF source as the models build them (include/rvc_mi355x_debug.h,
-// tests/test_gpu_front.py).  As for rvc_debug_layer, the caller owns every float of the tensors' allocations; the streams' states live in a block of the
-// aid's own, so the engine's streams are not touched.
-static DebugGeo debug_geo_flat(float *p, long long n, int C, int T) { DebugGeo q; q.base = p; q.g[0] = n; q.g[1] = 0; q.g[2] = C; q.g[3] = T; q.g[4] = T; q.g[5] = (long long)C * T; q.g[6] = T; return q; }
-int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w0, const float *w1, float *const *buf, rvc_debug_stream_state *state, long long *geo)
-{
-    return (int)guarded(e, [&]() {
-        if (!s || !geo || s->streams < 1 || s->streams > 4096 || s->op < 4 || s->op > 7) throw ShapeError("front spec");
-        const int B = s->streams, op = s->op;
-        Plan pl; pl.B = B;
-        Arena &A = pl.arena;
-        DebugGeo g[4];
-        T1 x1, y1; T2 img; int Tm = 0, R = 0;
-        float *f0 = nullptr, *pitchf = nullptr, *mel = nullptr; int *pitch = nullptr;
-        if (op == 4) {
-            if (s->n < 1 || s->n > (1 << 24) || s->frame < 1 || s->frame > s->n) throw ShapeError("front spec");
-            Tm = 1 + s->frame / 160;
-            if (Tm > 1024) throw ShapeError("f0 window too long");
-            const long long na = (long long)B * s->n + 64;
-            g[0] = debug_geo_flat(A.floats((size_t)na), na, 1, s->n);
-            mel = A.floats((size_t)B * 128 * Tm); g[1] = debug_geo_flat(mel, (long long)B * 128 * Tm, 128, Tm);
-            img = make_t2(A, B, 1, Tm, 128);
-            const size_t gd = t2_guard(img.ld);
-            g[2].base = img.p - gd - img.ld - 1; g[2].g[0] = (long long)B * img.bs + 2 * (long long)gd; g[2].g[1] = (long long)gd + img.ld + 1; g[2].g[2] = 1; g[2].g[3] = 128;
-            g[2].g[4] = img.ld; g[2].g[5] = img.bs; g[2].g[6] = img.cs; g[2].g[7] = Tm;
-        } else if (op == 5) {
-            if (s->C < 1 || s->C > 4096 || s->L < 10 || s->L > (1 << 22)) throw ShapeError("front spec");
-            const long long na = (long long)B * s->L + 64;
-            x1.p = A.floats((size_t)na); x1.B = B; x1.C = 1; x1.T = s->L; x1.ld = s->L; x1.halo = 0; x1.bs = s->L;      // the plan's input buffer (build_plan, build_contentvec)
-            g[0] = debug_geo_flat(x1.p, na, 1, s->L);
-            y1 = make_t1(A, B, s->C, (s->L - 10) / 5 + 1, 0); g[1] = debug_geo1(y1);
-        } else if (op == 6) {
-            Tm = s->Tm; R = s->update ? s->R : 0;
-            if (Tm < 1 || Tm > 1024 || R < 0 || R > 1024) throw ShapeError("front spec");
-            x1 = make_t1(A, B, 360, Tm, 0); g[0] = debug_geo1(x1);
-            f0 = A.floats((size_t)B * Tm); g[1] = debug_geo_flat(f0, (long long)B * Tm, 1, Tm);
-            if (s->update) {
-                pitchf = A.floats((size_t)B * std::max(R, 1)); g[2] = debug_geo_flat(pitchf, (long long)B * R, 1, R);
-                pitch = (int *)A.alloc((size_t)B * std::max(R, 1) * sizeof(int)); g[3] = debug_geo_flat((float *)pitch, (long long)B * R, 1, R);
-            }
-        } else {
-            if (s->T < 1 || s->T > 4096 || s->upp < 1 || s->upp > 4096 || s->x_halo < 0 || s->x_halo > 4096) throw ShapeError("front spec");
-            pitchf = A.floats((size_t)B * s->T); g[0] = debug_geo_flat(pitchf, (long long)B * s->T, 1, s->T);
-            y1 = make_t1(A, B, 1, s->T * s->upp, s->x_halo); g[1] = debug_geo1(y1);
-        }
-        for (int j = 0; j < 4; j++) for (int i = 0; i < 8; i++) geo[8 * j + i] = g[j].base ? g[j].g[i] : 0;
-        if (!buf) return RVC_OK;
-        if (!state) throw ShapeError("front buffers");
-        for (int j = 0; j < 4; j++) if (g[j].base && g[j].g[0] > 0 && !buf[j]) throw ShapeError("front buffers");
-        std::vector<StreamState> hst(B);
-        for (int b = 0; b < B; b++) {
-            memset(&hst[b], 0, sizeof(StreamState));
-            hst[b].uppower = state[b].uppower; hst[b].stream_id = state[b].stream_id; hst[b].chunk = state[b].chunk; hst[b].status = state[b].status;
-            memcpy(hst[b].cache_pitchf, state[b].cache_pitchf, sizeof hst[b].cache_pitchf);
-        }
-        StreamState *d_st = A.upload(hst);
-        CallParams hcp{}; hcp.seed = s->seed;
-        CallParams *d_cp = A.upload(std::vector<CallParams>(1, hcp));
-        std::vector<float *> wts;          // device copies of the weights, freed on every exit
-        ConvW cw;
-        try {
-            if (op == 4) add_mel_frontend(e, pl, B, g[0].base, s->n, s->n, s->frame, Tm, mel, img, s->bn_scale, s->bn_shift);
-            else if (op == 5) {
-                if (!w0 || !w1) throw ShapeError("front buffers");
-                wts.push_back(upload_f(w0, (size_t)s->C * 10)); wts.push_back(upload_f(w1, (size_t)2 * s->C));
-                cw = prep_conv(w0, nullptr, s->C, 1, 10, 1);
-                add_conv0_front(pl, cw, wts[0], wts[1], wts[1] + s->C, 10, 5, x1, y1);
-            } else if (op == 6) add_pitch_post(pl, B, x1, Tm, d_st, d_cp, f0, s->update != 0, s->shift, s->cache_start, s->read_start, R, pitchf, pitch);
-            else add_nsf_source(pl, B, pitchf, y1, s->T, s->upp, s->sr, s->lin_w, s->lin_b, d_st, d_cp, s->f0_num, s->f0_den);
-            for (int j = 0; j < 4; j++) if (g[j].base && g[j].g[0] > 0) HIPCHK(hipMemcpy(g[j].base, buf[j], (size_t)g[j].g[0] * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipDeviceSynchronize());
-            if (s->graph) {
-                hipGraph_t gr; hipGraphExec_t ge;
-                HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-                try { for (auto &o : pl.ops.v) o(e->stream); } catch (...) { end_failed_capture(e->stream); throw; }
-                HIPCHK(hipStreamEndCapture(e->stream, &gr));
-                const hipError_t ie = hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(gr);
-                HIPCHK(ie);
-                const hipError_t le = hipGraphLaunch(ge, e->stream);
-                const hipError_t se = hipStreamSynchronize(e->stream);
-                (void)hipGraphExecDestroy(ge);
-                HIPCHK(le); HIPCHK(se);
-            } else {
-                for (auto &o : pl.ops.v) o(e->stream);
-                HIPCHK(hipStreamSynchronize(e->stream));
-            }
-            HIPCHK(hipGetLastError());
-        } catch (...) {
-            for (float *p : wts) wfree(p);
-            free_conv(cw);
-            throw;
-        }
-        for (float *p : wts) wfree(p);
-        free_conv(cw);
-        for (int j = 0; j < 4; j++) if (g[j].base && g[j].g[0] > 0) HIPCHK(hipMemcpy(buf[j], g[j].base, (size_t)g[j].g[0] * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hst.data(), d_st, sizeof(StreamState) * B, hipMemcpyDeviceToHost));
-        for (int b = 0; b < B; b++) { state[b].status = hst[b].status; memcpy(state[b].cache_pitchf, hst[b].cache_pitchf, sizeof hst[b].cache_pitchf); }
-        return RVC_OK;
-    });
-}
-
-// the kernel family of the most recently queued implicit-GEMM launch (the first word of its description): tests assert which path they exercised
-const char *rvc_debug_last_kernel(void)
-{
-    static thread_local std::string buf;
-    buf = g_last_kernel;
-    return buf.c_str();
-}
-
 rvc_status rvc_profile_last_knn(rvc_engine *e, int *launches, double *kernel_ms, double *bytes)
 {
     return guarded(e, [&]() {
@@ -1850,35 +1249,6 @@ rvc_status rvc_profile_last_knn(rvc_engine *e, int *launches, double *kernel_ms,
         if (bytes) *bytes = by;
         return RVC_OK;
     });
-}
-
-// test aid: launches (ops) of the last call's plan
-int rvc_debug_last_plan(rvc_engine *e, int *n_ops)
-{
-    if (!e || !e->last_plan) return 0;
-    int n = 0;
-    for (size_t i = 0; i < e->last_plan->ops.v.size(); i++) if (e->last_plan->ops.kind[i] == 0) n++;
-    if (n_ops) *n_ops = n;
-    return 1;
-}
-
-// tuning aid: one line per profiled launch of the last call: "<us> <gflop> <description>"
-int rvc_debug_profile_dump(rvc_engine *e, char *buf, size_t cap)
-{
-    if (!e || !e->last_plan) return 0;
-    Plan &pl = *e->last_plan;
-    if (hipDeviceSynchronize() != hipSuccess) return 0;
-    std::string out;
-    for (size_t i = 0; i < pl.prof_used; i++) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, pl.prof[i].a, pl.prof[i].b) != hipSuccess) continue;
-        char ln[320];
-        snprintf(ln, sizeof ln, "%.2f %.4f %s\n", t * 1e3, pl.prof[i].flops * 1e-9, pl.prof[i].desc >= 0 ? pl.descs[pl.prof[i].desc].c_str() : (pl.prof[i].bytes > 0 ? "knn_scan_select" : "?"));
-        out += ln;
-    }
-    if (out.size() + 1 > cap) return -1;
-    memcpy(buf, out.c_str(), out.size() + 1);
-    return (int)pl.prof_used;
 }
 
 rvc_status rvc_get_tap(rvc_engine *e, const char *name, float *out, size_t cap, size_t *n)

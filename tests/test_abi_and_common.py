@@ -179,6 +179,30 @@ def test_header_is_plain_c(tmp_path):
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(src)])
 
 
+def test_debug_spec_mirrors_match_the_header(tmp_path):
+    # tests/debug_abi.py restates the structs of include/rvc_mi355x_debug.h for ctypes: the size of each and the offset of every field, as the host C
+    # compiler lays them out, against the mirrors (a field added to one side only would shift everything behind it without any GPU test saying why)
+    import shutil, subprocess
+    import debug_abi as D
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if not cc:
+        pytest.skip("no C compiler found")
+    mirrors = [("rvc_debug_layer_spec", D.LayerSpec), ("rvc_debug_op_spec", D.OpSpec), ("rvc_debug_front_spec", D.FrontSpec), ("rvc_debug_stream_state", D.StreamState)]
+    c_name = {"cache": "cache_pitchf"}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rvc_mi355x_debug.h"', 'int main(void) {']
+    want = []
+    for cname, mirror in mirrors:
+        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
+        want.append(ctypes.sizeof(mirror))
+        for f, _ in mirror._fields_:
+            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (cname, c_name.get(f, f)))
+            want.append(getattr(mirror, f).offset)
+    (tmp_path / "layout.c").write_text("\n".join(lines + ["return 0; }", ""]))
+    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")])
+    got = [int(v) for v in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == want, (got, want)
+
+
 def _c_decls(text):
     """name -> parameter count of every function declared in the C header (comments stripped)."""
     import re

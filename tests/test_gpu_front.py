@@ -46,12 +46,11 @@ import pytest
 
 import front_ref as R
 from common import set_opt
-from obs_rvc_amd import _native
+from debug_abi import RVC_SHAPE, FrontSpec, Handle, StreamState, index, ptr, same_bits, stray
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-RVC_SHAPE = 5
 OP_MEL, OP_CONV0, OP_PITCH, OP_NSF = 4, 5, 6, 7
 SENT = np.float32(-7777.25)
 ST_PANIC = 1
@@ -63,65 +62,36 @@ RTOL_F0 = 7e-6
 MEASURED = {}                      # worst figures of this run, printed by every test before it asserts
 
 
-class Spec(C.Structure):
-    _fields_ = [("op", C.c_int), ("streams", C.c_int), ("graph", C.c_int), ("n", C.c_int), ("frame", C.c_int), ("bn_scale", C.c_float), ("bn_shift", C.c_float),
-                ("C", C.c_int), ("L", C.c_int), ("Tm", C.c_int), ("update", C.c_int), ("shift", C.c_int), ("cache_start", C.c_int), ("read_start", C.c_int),
-                ("R", C.c_int), ("T", C.c_int), ("upp", C.c_int), ("x_halo", C.c_int), ("f0_num", C.c_int), ("f0_den", C.c_int), ("sr", C.c_float),
-                ("lin_w", C.c_float), ("lin_b", C.c_float), ("seed", C.c_uint)]
-
-
-class State(C.Structure):
-    _fields_ = [("uppower", C.c_float), ("stream_id", C.c_uint), ("chunk", C.c_uint), ("status", C.c_int), ("cache", C.c_float * 1024)]
-
-
 def _note(key, value):
     MEASURED[key] = max(MEASURED.get(key, 0.0), float(value))
 
 
-def _same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-class Front:
-    def __init__(self):
-        self.L = _native.lib()
-        self.L.rvc_debug_front.restype = C.c_int
-        self.L.rvc_debug_front.argtypes = [C.c_void_p, C.POINTER(Spec), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(State), C.POINTER(C.c_longlong)]
-        self.L.rvc_debug_last_kernel.restype = C.c_char_p
-        self.L.rvc_last_error_message.restype = C.c_char_p
-        self.L.rvc_last_error_message.argtypes = [C.c_void_p]
-        self.h = C.c_void_p()
-        assert self.L.rvc_create(b"/tmp", 0, C.byref(self.h)) == 0
-
-    def close(self):
-        self.L.rvc_destroy(self.h)
-
+class Front(Handle):
     def run(self, fill, w0=None, w1=None, states=None, **spec):
         """fill(geo, bufs): writes the inputs into the sentinel-filled allocations.  -> (rc, bufs after, bufs before, geo [4][8], states after, kernel name)"""
-        s = Spec()
+        s = FrontSpec()
         for k, v in spec.items():
             setattr(s, k, v)
         geo = (C.c_longlong * 32)()
         rc = self.L.rvc_debug_front(self.h, C.byref(s), None, None, None, None, geo)
         if rc != 0:
-            return rc, None, None, None, None, self.L.rvc_last_error_message(self.h).decode()
+            return rc, None, None, None, None, self.last_error()
         g = [list(geo[8 * j:8 * j + 8]) for j in range(4)]
         bufs = [np.full(max(int(q[0]), 0), SENT, np.float32) for q in g]
         fill(g, bufs)
         before = [b.copy() for b in bufs]
         B = s.streams
-        st = (State * B)()
+        st = (StreamState * B)()
         for b in range(B):
             d = (states or {}).get(b, {})
             st[b].uppower, st[b].stream_id, st[b].chunk, st[b].status = d.get("uppower", 1.0), d.get("stream_id", b), d.get("chunk", 0), 0
             C.memmove(st[b].cache, np.ascontiguousarray(d.get("cache", np.zeros(1024)), np.float32).ctypes.data, 4096)
         ptrs = (C.c_void_p * 4)(*[b.ctypes.data if b.size else None for b in bufs])
-        ptr = lambda a: None if a is None else a.ctypes.data
         rc = self.L.rvc_debug_front(self.h, C.byref(s), ptr(w0), ptr(w1), ptrs, st, geo)
         if rc != 0:
-            return rc, None, None, g, None, self.L.rvc_last_error_message(self.h).decode()
+            return rc, None, None, g, None, self.last_error()
         out = [dict(status=int(st[b].status), cache=np.array(st[b].cache, np.float32)) for b in range(B)]
-        return 0, bufs, before, g, out, self.L.rvc_debug_last_kernel().decode()
+        return 0, bufs, before, g, out, self.last_kernel()
 
 
 @pytest.fixture(scope="module")
@@ -133,18 +103,6 @@ def front():
         set_opt("RVC_CONV0_KERNEL", None)
         f.close()
         print("\nmeasured: " + ", ".join("%s %.3e" % kv for kv in sorted(MEASURED.items())))
-
-
-def _index(g, B, nC, T):
-    """element offsets of [B][nC][T] in an allocation of geometry g = (size, offset, C, T, ld, bs, cs, H)"""
-    return g[1] + np.arange(B)[:, None, None] * g[5] + np.arange(nC)[None, :, None] * g[6] + np.arange(T)[None, None, :]
-
-
-def _stray(after, before, written_idx):
-    """number of floats that changed outside written_idx"""
-    ch = after.view(np.uint32) != before.view(np.uint32)
-    ch[np.asarray(written_idx).ravel()] = False
-    return int(np.count_nonzero(ch))
 
 
 def _rng(label):
@@ -247,10 +205,10 @@ def test_mel_frontend(front, Tm, B, extra, k0):
     rc, bufs, before, g, _, _ = front.run(fill, op=OP_MEL, streams=B, n=n, frame=frame, bn_scale=scale, bn_shift=shift)
     assert rc == 0
     assert g[1][0] == B * 128 * Tm and g[2][7] == Tm and g[2][3] == 128
-    assert _same(bufs[0], before[0]), "audio changed"
+    assert same_bits(bufs[0], before[0]), "audio changed"
     mel = bufs[1].reshape(B, 128, Tm)
     ii = g[2][1] + np.arange(B)[:, None, None] * g[2][5] + np.arange(Tm)[None, :, None] * g[2][4] + np.arange(128)[None, None, :]
-    assert _stray(bufs[2], before[2], ii) == 0, "image written outside its interior"
+    assert stray(bufs[2], before[2], ii).size == 0, "image written outside its interior"
     img = bufs[2][ii]                                                         # [B][Tm][128]
     lm_t = mel.transpose(0, 2, 1)
     unfused = (lm_t * scale).astype(np.float32) + shift
@@ -354,12 +312,12 @@ def conv0_run(front, C0, To, B, data, forced=None):
     if rc != 0:
         return rc, None, ["%s: failed (%d): %s" % (tag, rc, name)]
     bad = []
-    if not _same(bufs[0], before[0]):
+    if not same_bits(bufs[0], before[0]):
         bad.append("%s: input changed" % tag)
-    yi = _index(g[1], B, C0, To)
+    yi = index(g[1], B, 0, C0, To)
     if g[1][2] != C0 or g[1][3] != To:
         bad.append("%s: output geometry %s" % (tag, g[1]))
-    n = _stray(bufs[1], before[1], yi)
+    n = stray(bufs[1], before[1], yi).size
     if n:
         bad.append("%s [%s]: %d floats written outside the output's interior" % (tag, name, n))
     got = bufs[1][yi].astype(np.float64)
@@ -508,13 +466,13 @@ def test_pitch_decode(front, B, Tm):
     rc, bufs, before, g, st, _ = pitch_run(front, sal, ups, caches=caches)
     assert rc == 0
     assert g[0][4] == (Tm + 3) // 4 * 4 and g[0][5] == 360 * g[0][4]
-    assert _same(bufs[0], before[0]), "salience changed"
+    assert same_bits(bufs[0], before[0]), "salience changed"
     e = check_f0(bufs[1].reshape(B, Tm).astype(np.float64), ref)
     _note("f0_rel", e)
     print("pitch decode B %d Tm %d: worst relative f0 error %.3e" % (B, Tm, e))
     assert e <= RTOL_F0
     for b in range(B):                                                       # update = 0: status clear, the cache bit-identical
-        assert st[b]["status"] == 0 and _same(st[b]["cache"], caches[b])
+        assert st[b]["status"] == 0 and same_bits(st[b]["cache"], caches[b])
 
 
 @pytest.mark.parametrize("Tm", [32, 96, 1024])
@@ -527,21 +485,21 @@ def test_pitch_cache(front, Tm):
     for shift in (0, 1, 16, 30, 1024):
         for read_start in (0, 1024 - Rr):
             rc, bufs, before, g, st, _ = pitch_run(front, sal, ups, update=1, shift=shift, read_start=read_start, Rr=Rr, caches=caches)
-            assert rc == 0 and _same(bufs[0], before[0])
+            assert rc == 0 and same_bits(bufs[0], before[0])
             f0 = bufs[1].reshape(B, Tm)
             assert check_f0(f0.astype(np.float64), ref) <= RTOL_F0
             pitch = bufs[3].view(np.int32).reshape(B, Rr)
             for b in range(B):
                 want, pf = R.update_cache(caches[b], f0[b], shift, 1028 - Tm, read_start, Rr)
                 assert st[b]["status"] == 0
-                assert _same(st[b]["cache"], want.astype(np.float32)), (shift, read_start, b)
-                assert _same(bufs[2].reshape(B, Rr)[b], pf.astype(np.float32)), (shift, read_start, b)
+                assert same_bits(st[b]["cache"], want.astype(np.float32)), (shift, read_start, b)
+                assert same_bits(bufs[2].reshape(B, Rr)[b], pf.astype(np.float32)), (shift, read_start, b)
                 ci, dist = R.coarse_pitch(pf)
                 assert np.array_equal(pitch[b][dist > 1e-3], ci[dist > 1e-3])
     # eager equals one graph launch bit for bit
     a = pitch_run(front, sal, ups, update=1, shift=16, read_start=0, Rr=Rr, caches=caches)
     b2 = pitch_run(front, sal, ups, update=1, shift=16, read_start=0, Rr=Rr, caches=caches, graph=1)
-    assert a[0] == 0 and b2[0] == 0 and all(_same(p, q) for p, q in zip(a[1], b2[1])) and all(_same(p["cache"], q["cache"]) for p, q in zip(a[4], b2[4]))
+    assert a[0] == 0 and b2[0] == 0 and all(same_bits(p, q) for p, q in zip(a[1], b2[1])) and all(same_bits(p["cache"], q["cache"]) for p, q in zip(a[4], b2[4]))
 
 
 def test_pitch_panic_is_per_stream(front):
@@ -569,7 +527,7 @@ def test_coarse_pitch(front):
     caches = [np.concatenate([freqs[b], np.zeros(1024 - Rr, np.float32)]) for b in range(B)]
     rc, bufs, before, g, st, _ = pitch_run(front, sal, [1.0] * B, update=1, shift=0, read_start=0, Rr=Rr, caches=caches)
     assert rc == 0
-    assert _same(bufs[2].reshape(B, Rr), freqs)
+    assert same_bits(bufs[2].reshape(B, Rr), freqs)
     got = bufs[3].view(np.int32).reshape(B, Rr)
     want, dist = R.coarse_pitch(freqs)
     clear = dist > 1e-3
@@ -628,9 +586,9 @@ def nsf_check(front, T, upp, B, lin, ratio, label):
     rc, bufs, before, g, st, _ = nsf_run(front, f0, upp, sr, lin, ratio, ids)
     assert rc == 0, (label, rc)
     N = T * upp
-    assert _same(bufs[0], before[0]), "pitch input changed"
-    yi = _index(g[1], B, 1, N)
-    assert _stray(bufs[1], before[1], yi) == 0, "source written outside its interior (halo, padding, guards)"
+    assert same_bits(bufs[0], before[0]), "pitch input changed"
+    yi = index(g[1], B, 0, 1, N)
+    assert stray(bufs[1], before[1], yi).size == 0, "source written outside its interior (halo, padding, guards)"
     out = bufs[1][yi].reshape(B, N).astype(np.float64)
     assert np.all(np.abs(out) < 1.0)
     sw = (np.arctanh(out) - np.float64(np.float32(lin[1]))) / np.float64(np.float32(lin[0]))
@@ -682,13 +640,13 @@ def test_nsf_streams_chunks_and_graph(front):
     f0 = np.zeros((3, T), np.float32)                                         # unvoiced: the output is the noise alone
     a = nsf_run(front, f0, upp, sr, (1.0, 0.0), (1, 1), [(5, 9), (6, 9), (5, 10)])
     assert a[0] == 0
-    out = a[1][1][_index(a[3][1], 3, 1, T * upp)].reshape(3, -1)
+    out = a[1][1][index(a[3][1], 3, 0, 1, T * upp)].reshape(3, -1)
     assert not np.array_equal(out[0], out[1]), "two stream ids drew the same noise"
     assert not np.array_equal(out[0], out[2]), "chunk and chunk + 1 drew the same noise"
     f0 = np.stack([nsf_track(k, T, sr) for k in ("glide", "alt7", "c440")])
     a = nsf_run(front, f0, upp, sr, (2.5, 0.01), (40, 35), [(5, 9), (6, 9), (5, 10)])
     b = nsf_run(front, f0, upp, sr, (2.5, 0.01), (40, 35), [(5, 9), (6, 9), (5, 10)], graph=1)
-    assert a[0] == 0 and b[0] == 0 and _same(a[1][1], b[1][1]), "eager and graph launch differ"
+    assert a[0] == 0 and b[0] == 0 and same_bits(a[1][1], b[1][1]), "eager and graph launch differ"
 
 
 def test_nsf_refuses_more_than_512_frames(front):

@@ -15,19 +15,12 @@ import pytest
 
 import layer_ref as R
 from common import set_opt
-from obs_rvc_amd import _native
+from debug_abi import Handle, LayerSpec, index, ptr, same_bits, stray
 from test_gpu_tiles import CHOICES, HOOKS, TOL
 
 pytestmark = pytest.mark.gpu
 
 SENT_X, SENT_Y, SENT_R = np.float32(-7777.25), np.float32(5555.5), np.float32(3333.75)
-
-
-class Spec(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("form", "streams", "cin", "cout", "kw", "stride", "pad", "dil", "groups", "t_in", "t_out", "x_halo", "y_halo", "r_halo", "act")] + \
-               [("slope", C.c_float), ("scale", C.c_float), ("accumulate", C.c_int), ("pre_act", C.c_int), ("pre_slope", C.c_float)] + \
-               [(n, C.c_int) for n in ("no_bias", "final_out", "glu", "res", "n")] + [(n, C.c_int * 4) for n in ("kws", "dils", "pads")] + \
-               [(n, C.c_int) for n in ("x_grouped", "res_grouped", "y_ws")]
 
 
 class Case:
@@ -41,7 +34,7 @@ class Case:
         self.p = dict(self.DEFAULTS, **kw)
 
     def spec(self, streams):
-        s = Spec()
+        s = LayerSpec()
         for k, v in self.p.items():
             if k in ("kws", "dils", "pads"):
                 getattr(s, k)[:] = (list(v) + [0] * 4)[:4]
@@ -232,15 +225,7 @@ def R_rms(a):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
-# tensor allocations: geo = (size, offset of element 0, C, T (2-D: W), ld, bs, cs, H)
-def _index(g, B, C0, nC, T, H=None):
-    off, ld, bs, cs = g[1], g[4], g[5], g[6]
-    b = np.arange(B)[:, None, None] * bs + np.arange(C0, C0 + nC)[None, :, None] * cs
-    if H is None:
-        return off + b + np.arange(T)[None, None, :]
-    return off + b[..., None] + (np.arange(H) * ld)[None, None, :, None] + np.arange(T)[None, None, None, :]
-
-
+# tensor allocations: geo = (size, offset of element 0, C, T (2-D: W), ld, bs, cs, H) (debug_abi.index)
 def _y_index(case, g, B, j):
     """element offsets of output tensor j's interior ([B][C][T] or [B][C][H][W])"""
     p = case.p
@@ -251,25 +236,15 @@ def _y_index(case, g, B, j):
         o, h, w = np.meshgrid(np.arange(p["cout"]), np.arange(H), np.arange(W), indexing="ij")
         return g[1] + np.arange(B)[:, None, None, None] * g[5] + ((o * W + w) * g[4] + h)[None]
     if f == 4:
-        return _index(g, B, 0, p["cout"], p["t_out"], H=p["t_in"])
+        return index(g, B, 0, p["cout"], p["t_out"], H=p["t_in"])
     if f == 3:
-        return _index(g, B, 16 + 2 * p["cout"] * j, p["cout"], p["t_out"])
+        return index(g, B, 16 + 2 * p["cout"] * j, p["cout"], p["t_out"])
     if f == 2:
-        return _index(g, B, j * p["cout"], p["cout"], p["t_out"])
-    return _index(g, B, 0, p["cout"] // 2 if p["glu"] else p["cout"], p["t_out"])
+        return index(g, B, j * p["cout"], p["cout"], p["t_out"])
+    return index(g, B, 0, p["cout"] // 2 if p["glu"] else p["cout"], p["t_out"])
 
 
-class Layer:
-    def __init__(self):
-        self.L = _native.lib()
-        self.L.rvc_debug_layer.restype = C.c_int
-        self.L.rvc_debug_layer.argtypes = [C.c_void_p, C.POINTER(Spec)] + [C.c_void_p] * 5 + [C.POINTER(C.c_longlong)]
-        self.L.rvc_debug_last_kernel.restype = C.c_char_p
-        self.L.rvc_last_error_message.restype = C.c_char_p
-        self.L.rvc_last_error_message.argtypes = [C.c_void_p]
-        self.h = C.c_void_p()
-        assert self.L.rvc_create(b"/tmp", 0, C.byref(self.h)) == 0
-
+class Layer(Handle):
     def run(self, case, streams):
         """-> (family, list of problems)"""
         p, B = case.p, streams
@@ -282,40 +257,36 @@ class Layer:
         # input: sentinel, the whole row of every channel zero (halo and interior), then the interior
         x = np.full(gx[0], SENT_X, np.float32)
         if f == 4:
-            x[_index(gx, B, 0, gx[2], gx[3] + 2, H=gx[7] + 2) - gx[4] - 1] = 0.0
-            x[_index(gx, B, 0, p["cin"], p["t_out"], H=p["t_in"])] = d.x
+            x[index(gx, B, 0, gx[2], gx[3] + 2, H=gx[7] + 2) - gx[4] - 1] = 0.0
+            x[index(gx, B, 0, p["cin"], p["t_out"], H=p["t_in"])] = d.x
         else:
-            x[_index(gx, B, 0, gx[2], gx[3] + 2 * p["x_halo"]) - p["x_halo"]] = 0.0
-            x[_index(gx, B, 0, gx[2], gx[3])] = d.x
+            x[index(gx, B, 0, gx[2], gx[3] + 2 * p["x_halo"]) - p["x_halo"]] = 0.0
+            x[index(gx, B, 0, gx[2], gx[3])] = d.x
         y = np.full(gy[0], SENT_Y, np.float32)
         yidx = [_y_index(case, gy, B, j) for j in range(len(d.refs))]
-        written = np.zeros(gy[0], bool)
         for j, yi in enumerate(yidx):
-            written[yi] = True
             if p["accumulate"] or p["res"] == 3:
                 y[yi] = d.y0[j]
         r = None
         if p["res"] == 1:
             r = np.full(gr[0], SENT_R, np.float32)
-            r[_index(gr, B, 0, gr[2], gr[3], H=gr[7] if f == 4 else None)] = d.r
+            r[index(gr, B, 0, gr[2], gr[3], H=gr[7] if f == 4 else None)] = d.r
         elif p["res"] == 2:
             r = np.full(gr[0], SENT_R, np.float32)
-            r[_index(gr, 1, 0, 1, gr[3])] = d.r
+            r[index(gr, 1, 0, 1, gr[3])] = d.r
         x0, y0, r0 = x.copy(), y.copy(), None if r is None else r.copy()
         wcat = np.concatenate([w_.ravel() for w_ in d.ws])
-        ptr = lambda a: None if a is None else a.ctypes.data
         rc = self.L.rvc_debug_layer(self.h, C.byref(s), ptr(wcat), ptr(d.b), ptr(x), ptr(y), ptr(r), geo)
         if rc != 0:
-            return "?", ["rvc_debug_layer failed (%d): %s" % (rc, self.L.rvc_last_error_message(self.h).decode())]
-        fam = self.L.rvc_debug_last_kernel().decode()
+            return "?", ["rvc_debug_layer failed (%d): %s" % (rc, self.last_error())]
+        fam = self.last_kernel()
         bad = []
-        if not np.array_equal(x.view(np.uint32), x0.view(np.uint32)):
+        if not same_bits(x, x0):
             bad.append("input tensor changed at %d positions" % int(np.count_nonzero(x.view(np.uint32) != x0.view(np.uint32))))
-        if r is not None and not np.array_equal(r.view(np.uint32), r0.view(np.uint32)):
+        if r is not None and not same_bits(r, r0):
             bad.append("residual tensor changed")
-        stray = (y.view(np.uint32) != y0.view(np.uint32)) & ~written
-        if stray.any():
-            pos = np.flatnonzero(stray)
+        pos = stray(y, y0, yidx)
+        if pos.size:
             col = (pos - gy[1]) % gy[4] if f != 4 else pos
             bad.append("%d floats written outside the output's interior (first at offset %d, row column %d; ld %d, T %d)" %
                        (pos.size, pos[0] - gy[1], int(col[0]), gy[4], gy[3]))
@@ -326,9 +297,6 @@ class Layer:
                 wi = np.unravel_index(int(np.argmax(np.abs(got - ref))), ref.shape)
                 bad.append("output %d: max err / rms %.3e at %s (gpu %.6g, ref %.6g)" % (j, e, wi, got[wi], ref[wi]))
         return fam, bad
-
-    def close(self):
-        self.L.rvc_destroy(self.h)
 
 
 @pytest.fixture(scope="module")

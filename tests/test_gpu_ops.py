@@ -19,11 +19,10 @@ import pytest
 
 import op_ref as R
 from common import set_opt
-from obs_rvc_amd import _native
+from debug_abi import RVC_SHAPE, Handle, OpSpec, index, ptr, same_bits, stray
 
 pytestmark = pytest.mark.gpu
 
-RVC_SHAPE = 5
 OP_MHA, OP_REL, OP_LN, OP_GRU = 0, 1, 2, 3
 SENT_X, SENT_Y, SENT_STATUS = np.float32(-7777.25), np.float32(5555.5), -99
 HOOK = {OP_MHA: "RVC_ATTN_KERNEL", OP_REL: "RVC_RELPOS_KERNEL", OP_LN: "RVC_LN_KERNEL", OP_GRU: "RVC_GRU_KERNEL"}
@@ -51,32 +50,10 @@ TOL_GRU = 2e-5
 U32 = 2.0 ** -24                   # fp32 unit roundoff
 
 
-class Spec(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("op", "streams", "E", "heads", "T", "window", "C", "H", "x_halo", "y_halo", "reps", "graph")]
-
-
-def _index(g, B, C0, nC, T):
-    """element offsets of [B][C0:C0+nC][0:T] in an allocation of geometry g = (size, offset, C, T, ld, bs, cs, H)"""
-    return g[1] + np.arange(B)[:, None, None] * g[5] + np.arange(C0, C0 + nC)[None, :, None] * g[6] + np.arange(T)[None, None, :]
-
-
-class Ops:
-    def __init__(self):
-        self.L = _native.lib()
-        self.L.rvc_debug_op.restype = C.c_int
-        self.L.rvc_debug_op.argtypes = [C.c_void_p, C.POINTER(Spec)] + [C.c_void_p] * 5 + [C.POINTER(C.c_longlong)]
-        self.L.rvc_debug_last_kernel.restype = C.c_char_p
-        self.L.rvc_last_error_message.restype = C.c_char_p
-        self.L.rvc_last_error_message.argtypes = [C.c_void_p]
-        self.h = C.c_void_p()
-        assert self.L.rvc_create(b"/tmp", 0, C.byref(self.h)) == 0
-
-    def close(self):
-        self.L.rvc_destroy(self.h)
-
+class Ops(Handle):
     def run(self, case, reps=1, graph=0):
         """-> (rc, variant, output interior [B][C][T] as float32, list of problems, status words)"""
-        s = Spec()
+        s = OpSpec()
         for k, v in case.spec.items():
             setattr(s, k, v)
         s.reps, s.graph = reps, graph
@@ -85,31 +62,27 @@ class Ops:
         gx, gy = list(geo[0:8]), list(geo[8:16])
         B, T, xh = case.B, case.T, case.spec["x_halo"]
         x = np.full(gx[0], SENT_X, np.float32)
-        x[_index(gx, B, 0, gx[2], T + 2 * xh) - xh] = 0.0            # halos zero, as the plan's arena leaves them
-        xi = _index(gx, B, 0, gx[2], T)
+        x[index(gx, B, 0, gx[2], T + 2 * xh) - xh] = 0.0            # halos zero, as the plan's arena leaves them
+        xi = index(gx, B, 0, gx[2], T)
         x[xi] = case.x
         y, yi = None, None
         if case.op != OP_LN:
             y = np.full(gy[0], SENT_Y, np.float32)
-            yi = _index(gy, B, 0, gy[2], T)
+            yi = index(gy, B, 0, gy[2], T)
         status = np.full(B, SENT_STATUS, np.int32)
         x0, y0 = x.copy(), None if y is None else y.copy()
-        ptr = lambda a: None if a is None else a.ctypes.data
         rc = self.L.rvc_debug_op(self.h, C.byref(s), ptr(case.w0), ptr(case.w1), ptr(x), ptr(y), ptr(status), geo)
         if rc != 0:
-            return rc, None, None, [self.L.rvc_last_error_message(self.h).decode()], None
-        var = self.L.rvc_debug_last_kernel().decode()
+            return rc, None, None, [self.last_error()], None
+        var = self.last_kernel()
         bad = []
         # what may change: the output's interior (LayerNorm: the input's, in place)
         tgt, t0, ti, g = (x, x0, xi, gx) if case.op == OP_LN else (y, y0, yi, gy)
-        written = np.zeros(tgt.size, bool)
-        written[ti] = True
-        stray = (tgt.view(np.uint32) != t0.view(np.uint32)) & ~written
-        if stray.any():
-            pos = np.flatnonzero(stray)
+        pos = stray(tgt, t0, ti)
+        if pos.size:
             bad.append("%d floats written outside the output's interior (first at offset %d, row column %d; ld %d, T %d)" %
                        (pos.size, pos[0] - g[1], int((pos[0] - g[1]) % g[4]), g[4], T))
-        if case.op != OP_LN and not np.array_equal(x.view(np.uint32), x0.view(np.uint32)):
+        if case.op != OP_LN and not same_bits(x, x0):
             bad.append("input tensor changed at %d positions" % int(np.count_nonzero(x.view(np.uint32) != x0.view(np.uint32))))
         if case.op != OP_GRU:
             status = None

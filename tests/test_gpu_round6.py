@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import debug_abi
 from common import BASELINE_160MS as g, rms, voice_signal, zoo
 from obs_rvc_amd import _native, weights as W
 
@@ -71,14 +72,6 @@ def test_sixty_four_streams_with_the_100k_index_is_one_rank_of_config4():
     eng.close()
 
 
-def _conv2d_check():
-    L = _native.lib()
-    L.rvc_debug_conv2d_check.restype = C.c_double
-    L.rvc_debug_conv2d_check.argtypes = [C.c_void_p] + [C.c_int] * 7
-    L.rvc_debug_last_kernel.restype = C.c_char_p
-    return L
-
-
 # RMVPE's shapes at Tm = 32 (rvc/src/f0/rmvpe.rs:225-241: E2E(4, 1, (2, 2)), levels 16 .. 256 channels, images 32 x 128 .. 2 x 8) and ragged ones
 C2D_SHAPES = [(16, 16, 32, 128), (32, 32, 16, 64), (64, 64, 8, 32), (128, 128, 4, 16), (256, 256, 2, 8), (32, 16, 16, 64), (64, 128, 8, 32),
               (48, 32, 5, 19), (32, 64, 3, 7), (16, 1, 32, 128), (3, 16, 32, 128)]
@@ -93,7 +86,7 @@ def test_conv2d_3x3_every_planner_choice_against_fp64(streams, residual):
     from obs_rvc_amd.rvc import RvcInfer
     z = zoo("tiny")
     eng = RvcInfer(z["data"])
-    L = _conv2d_check()
+    L = debug_abi.lib()
     seen = set()
     for (M, Cin, H, Wd) in C2D_SHAPES:
         err = L.rvc_debug_conv2d_check(eng._h, M, Cin, H, Wd, streams, 0, residual)
@@ -109,7 +102,7 @@ def test_conv_transpose2d_against_fp64(streams):
     from obs_rvc_amd.rvc import RvcInfer
     z = zoo("tiny")
     eng = RvcInfer(z["data"])
-    L = _conv2d_check()
+    L = debug_abi.lib()
     for (M, Cin, H, Wd) in [(16, 32, 16, 64), (32, 64, 8, 32), (64, 128, 4, 16), (128, 256, 2, 8), (256, 512, 1, 4), (24, 16, 3, 5)]:
         err = L.rvc_debug_conv2d_check(eng._h, M, Cin, H, Wd, streams, 1, 0)
         assert 0 <= err < 2e-5, (M, Cin, H, Wd, streams, err)

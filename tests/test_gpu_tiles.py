@@ -2,12 +2,10 @@
 (rvc_debug_conv_check, through the C ABI): one parametrised test per kernel family and configuration, so that one failing tile does not hide the others
 (VERDICT r5 weak #13), plus every choice the plan-time autotuner can make (round 6) -- SURVEY.md section 8 rows a3, a12, a16: the layers ContentVec /
 RMVPE / the synthesizer are made of (the reference runs them inside its ONNX graphs, rvc/src/rvc.rs:92,195, rvc/src/f0/rmvpe.rs:235)."""
-import ctypes as C
-
 import pytest
 
 from common import set_opt
-from obs_rvc_amd import _native
+from debug_abi import Handle
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5          # largest |gpu - fp64 host| / rms(host): fp32 accumulation over K <= 5632
@@ -19,22 +17,17 @@ SHAPES = [(48, 48, 1, 1, 111, 0), (144, 48, 1, 1, 111, 0), (96, 384, 1, 1, 37, 0
 
 @pytest.fixture()
 def conv():
-    L = _native.lib()
-    L.rvc_debug_conv_check.restype = C.c_double
-    L.rvc_debug_conv_check.argtypes = [C.c_void_p] + [C.c_int] * 7
-    L.rvc_debug_last_kernel.restype = C.c_char_p
-    h = C.c_void_p()
-    assert L.rvc_create(b"/tmp", 0, C.byref(h)) == 0
+    eng = Handle()
 
     def check(M, Cin, KW, dil, N, streams, pre):
-        return L.rvc_debug_conv_check(h, M, Cin, KW, dil, N, streams, pre)
-    check.kernel = lambda: L.rvc_debug_last_kernel().decode()
+        return eng.L.rvc_debug_conv_check(eng.h, M, Cin, KW, dil, N, streams, pre)
+    check.kernel = eng.last_kernel
     try:
         yield check
     finally:
         for k in HOOKS:
             set_opt(k, None)
-        L.rvc_destroy(h)
+        eng.close()
 
 
 @pytest.mark.parametrize("ks", [1, 4, 8, 16])
