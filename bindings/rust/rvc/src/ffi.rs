@@ -36,6 +36,8 @@ pub const RVC_BACKEND: c_int = 4;
 pub const RVC_SHAPE: c_int = 5;
 pub const RVC_PANIC: c_int = 6;
 pub const RVC_RCCL_UNIQUE_ID_BYTES: usize = 128;
+pub const RVC_F0_RMVPE: c_int = 1;
+pub const RVC_F0_YIN: c_int = 2;
 
 extern "C" {
     // ---- RvcInfer (rvc/src/rvc.rs:30-220)
@@ -52,6 +54,9 @@ extern "C" {
     pub fn rvc_infer(e: *mut RvcEngine, input: *const c_float, n: usize, sample_frame_16k_size: usize, has_pitch_shift: c_int,
                      pitch_shift: i32, skip_head: u32, return_length: u32, out: *mut c_float, cap: usize, out_len: *mut usize) -> c_int;
     pub fn rvc_last_error_message(e: *mut RvcEngine) -> *const c_char;
+    // ---- f0 method: RVC_F0_RMVPE (= rvc_load_f0) or RVC_F0_YIN (no weight file)
+    pub fn rvc_load_f0_method(e: *mut RvcEngine, method: c_int) -> c_int;
+    pub fn rvc_f0_method(e: *mut RvcEngine) -> c_int;
 
     // ---- retrieval index, noise seed, state
     pub fn rvc_load_index(e: *mut RvcEngine, vectors: *const c_float, n: usize, dim: usize) -> c_int;

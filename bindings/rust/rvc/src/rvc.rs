@@ -77,6 +77,12 @@ impl RvcInfer {
         self.check_load(unsafe { ffi::rvc_load_f0(self.handle, a as i32) })
     }
 
+    /// Not in the reference: the engine's f0 method by `ffi::RVC_F0_RMVPE` (the same as `load_f0`) or `ffi::RVC_F0_YIN`,
+    /// the weight-free time-domain tracker (no `<data>/f0/rmvpe.rvcw` needed)
+    pub fn load_f0_method(&mut self, method: i32) -> Result<(), BackendError> {
+        self.check_load(unsafe { ffi::rvc_load_f0_method(self.handle, method) })
+    }
+
     /// rvc.rs:77-79
     pub fn unload_model(&mut self) {
         unsafe { ffi::rvc_unload_model(self.handle) }

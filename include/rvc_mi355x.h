@@ -74,6 +74,16 @@ rvc_status rvc_infer(rvc_engine *e, const float *input, size_t n, size_t sample_
                      int32_t pitch_shift, uint32_t skip_head, uint32_t return_length, float *out, size_t cap, size_t *out_len);
 const char *rvc_last_error_message(rvc_engine *e);
 
+/* ---- f0 methods: RMVPE (the reference's only one), or YIN, a time-domain tracker that needs no weight file ---- */
+/* rvc_load_f0 keeps the reference's one-variant PitchAlgorithm (every value loads RMVPE); the engine's method is chosen here by constants of
+ * its own.  YIN (de Cheveigne & Kawahara 2002; DESIGN.md "YIN pitch") reads the frames RMVPE's front end reads -- the same number of f0 rows
+ * with the same meaning -- in one kernel, needs no <data>/f0/rmvpe.rvcw, and feeds the same pitch shift, pitch cache and get_f0_post; 0 Hz =
+ * unvoiced.  The method is engine-wide (not per stream), may be changed between calls, and is part of a plan's identity. */
+#define RVC_F0_RMVPE 1
+#define RVC_F0_YIN   2     /* weight-free; DESIGN.md "YIN pitch" */
+rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rvc_load_f0; YIN: needs no file; other values: RVC_SHAPE */
+int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded */
+
 /* ---- capabilities the reference plumbs through but never implements / bakes into its export ---- */
 /* flat-L2 retrieval index (index_path / index_rate settings, obs-rvc/src/lib.rs:78,81; rvc.rs:159 TODO) */
 rvc_status rvc_load_index(rvc_engine *e, const float *vectors, size_t n, size_t dim);

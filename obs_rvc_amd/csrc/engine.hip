@@ -185,6 +185,19 @@ static void alloc_state(rvc_engine *e)
 }
 
 // ------------------------------- plan -------------------------------------------------
+// the f0 branch of the engine's method: RMVPE's network and salience decode, or the YIN launch; behind either the same pitch tail (shift, cache, get_f0_post)
+static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache, size_t hubert_length, float **pitchf_out, int **pitch_out)
+{
+    if (e->f0_method == RVC_F0_YIN) {
+        const float *f0 = build_yin(e, pl, B, L, frame16k);
+        build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
+        return;
+    }
+    if (!e->rm) throw std::logic_error("f0 method");
+    const T1 sal = build_rmvpe(e, pl, B, L, frame16k, update_cache);
+    build_pitch_post(e, pl, B, sal, update_cache, frame16k, hubert_length, pitchf_out, pitch_out);
+}
+
 static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32_t skip_head, uint32_t R, int slot = 0, int bucket_B = 0,
                       uint32_t R2 = 0, bool fstage = false)
 {
@@ -210,7 +223,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
             p->with_index == with_index && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
-            p->R2 == R2 && p->fstage == fstage) {
+            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -223,11 +236,13 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
     pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
-    pl.R2 = R2; pl.fstage = fstage;
+    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
-    T1 sal0, src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
+    T1 src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;
-    const bool part = mode == 0 && e->partitioned;
+    // YIN's f0 branch is two short launches.  Test hook RVC_YIN_CV_ALL_CUS = 1 leaves ContentVec on the main stream with every CU under it (measured against
+    // the partition: DESIGN.md section 11); not for pipelined calls, whose front branches are the masked pair
+    const bool part = mode == 0 && e->partitioned && !(e->f0_method == RVC_F0_YIN && !e->pipeline && test_opt_int("RVC_YIN_CV_ALL_CUS", 0) == 1);
     const int f0_sid = 1, cv_sid = part ? 3 : 0;
     if (mode == 0) {
         // f0 branch first (auxiliary stream): independent of ContentVec until the synthesizer
@@ -237,8 +252,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         pl.ops.fork(f0_sid);
         rm_begin = pl.ops.v.size();
         pl.ops.cur = f0_sid;
-        sal0 = build_rmvpe(e, pl, B, L, frame16k, true);
-        build_pitch_post(e, pl, B, sal0, true, frame16k, hubert_length0, &d_pitchf0, &d_pitch0);
+        build_f0(e, pl, B, L, frame16k, true, hubert_length0, &d_pitchf0, &d_pitch0);
         pl.ops.cur = 0;
         rm_end = pl.ops.v.size();
     }
@@ -256,9 +270,8 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         }
     }
     if (mode == 2) {
-        T1 sal = build_rmvpe(e, pl, B, L, frame16k, false);
         float *pf; int *pi;
-        build_pitch_post(e, pl, B, sal, false, frame16k, 0, &pf, &pi);
+        build_f0(e, pl, B, L, frame16k, false, 0, &pf, &pi);
     }
     if (mode == 0) {
         const int T = pl.T, C = pl.C;
@@ -711,9 +724,22 @@ rvc_status rvc_load_f0(rvc_engine *e, int pitch_algorithm)
         HIPCHK(hipDeviceSynchronize());      // unsynchronised calls may still be running on the plans freed below
         e->plans.clear(); e->last_plan = nullptr;
         e->rm.reset(new ModelRM(b));
+        e->f0_method = RVC_F0_RMVPE;
         return RVC_OK;
     });
 }
+// the f0 method by its own constants (rvc_load_f0 keeps the reference's one-variant enum): RMVPE loads its weights, YIN has none.  The method is part of
+// a plan's key, so a plan built for one never serves the other.
+rvc_status rvc_load_f0_method(rvc_engine *e, int method)
+{
+    if (method == RVC_F0_RMVPE) return rvc_load_f0(e, RVC_PITCH_RMVPE);
+    return guarded(e, [&]() {
+        if (method != RVC_F0_YIN) throw ShapeError("f0 method: RVC_F0_RMVPE or RVC_F0_YIN");
+        e->f0_method = RVC_F0_YIN;
+        return RVC_OK;
+    });
+}
+int rvc_f0_method(rvc_engine *e) { return e ? e->f0_method : 0; }
 // rvc.rs:77-79
 void rvc_unload_model(rvc_engine *e)
 {
@@ -767,7 +793,7 @@ rvc_status rvc_extract_feature(rvc_engine *e, const float *input, size_t n, floa
 rvc_status rvc_pitch(rvc_engine *e, const float *input, size_t n, int32_t pitch_shift, size_t sample_frame_16k_size, float *out, size_t cap, size_t *out_len)
 {
     return guarded(e, [&]() {
-        if (!e->rm) return RVC_F0_NOT_LOADED;   // the reference hits unreachable!() here (rvc.rs:125)
+        if (!e->f0_method) return RVC_F0_NOT_LOADED;   // the reference hits unreachable!() here (rvc.rs:125)
         if (e->n_streams != 1) throw ShapeError("pitch() is a single-stream call");
         Plan *pl = get_plan(e, 2, n, sample_frame_16k_size, 0, 0);
         *out_len = (size_t)pl->Tm;
@@ -811,7 +837,7 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
 {
     if (!e->sy) return RVC_MODEL_NOT_LOADED;             // rvc.rs:141-143
     if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;        // rvc.rs:85-88 (via extract_feature at rvc.rs:151)
-    if (!e->rm) return RVC_F0_NOT_LOADED;                // reference: unreachable!() at rvc.rs:125
+    if (!e->f0_method) return RVC_F0_NOT_LOADED;         // reference: unreachable!() at rvc.rs:125
     uint32_t R2 = return_length; bool fstage = false;
     if (!formant_key(e, return_length, nullptr, &R2, &fstage))
         return infer_r2_buckets(e, input, input_on_device, n, frame16k, pitch_shift, skip_head, return_length, out, out_on_device, cap, out_len, shifts);
@@ -926,7 +952,7 @@ rvc_status rvc_infer_batch_g(rvc_engine *e, const float *const *inputs, const si
         if (!inputs || !n || !sample_frame_16k_size || !skip_head || !return_length || !outs || !caps) throw ShapeError("infer_batch_g: null argument array");
         if (!e->sy) return RVC_MODEL_NOT_LOADED;
         if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;
-        if (!e->rm) return RVC_F0_NOT_LOADED;
+        if (!e->f0_method) return RVC_F0_NOT_LOADED;
         const int S = e->n_streams;
         if (e->pipeline || e->use_graph) throw ShapeError("infer_batch_g: not with chunk pipelining / graph replay");
         // (R2, fstage: the formant decoder length of the stream and whether its bucket carries the formant stage, formant.hip.h)

@@ -1,6 +1,7 @@
 // engine_int.h -- internal declarations shared by the translation units of librvc_mi355x.so:
 //   plan.hip         the planner: device memory, prepared convolution weights, the op list, implicit-GEMM tile selection, test-hook table
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
+//   model_yin.hip    YIN f0 (build_yin)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: load, device-side layouts, the plan's search section
 //   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
@@ -247,6 +248,7 @@ struct Plan {
     double tune_ms = 0; int tuned_layers = 0, tune_changed = 0, tune_hits = 0;      // time spent in trials, layers tuned here / changed against the rules / taken from the process cache
     bool plain_plan = false;      // taps level 1: the explicit plan (LayerNorm launches, WaveNets layer by layer); level 2 taps the production plan
     int mode = 0;   // 0 infer, 1 hubert only, 2 pitch only
+    int f0_method = 0;            // the engine's f0 method when the plan was built (its f0 branch is that method's)
     // formant shift (formant.hip.h): fstage = the plan has the formant stage (some stream stretches or resamples); the decoder then runs
     // on R2 frames and formant_resample_kernel brings every stream back to R upp samples.  fstage = false: today's plan, R2 = R
     uint32_t R2 = 0; bool fstage = false;
@@ -880,6 +882,7 @@ struct rvc_engine {
     hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
     std::unique_ptr<ModelCV> cv;
     std::unique_ptr<ModelRM> rm;
+    int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights); engine-wide and part of a plan's identity
     std::unique_ptr<ModelSY> sy;
     // constants for the mel front end
     float *d_window = nullptr, *d_twiddle = nullptr, *d_basis = nullptr; int *d_band = nullptr;
@@ -942,13 +945,14 @@ template <typename Fn> static rvc_status guarded(rvc_engine *e, Fn fn)
 // ---- model builders (model_*.hip) and the retrieval unit (retrieval.hip) ----
 T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L);
 T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache);
-void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update_cache, size_t frame16k, size_t hubert_length, float **pitchf_out, int **pitch_out);
+void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update_cache, size_t frame16k, size_t hubert_length, float **pitchf_out, int **pitch_out, const float *f0_in = nullptr);
+float *build_yin(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
 T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf);
 // the head and the tail of the f0 branch and ContentVec's first layer as plan helpers: the builders above call them, and so does rvc_debug_front (debug.hip)
 void add_conv0_front(Plan &pl, const ConvW &cw, const float *w_raw, const float *gn_g, const float *gn_b, int kt, int st, const T1 &x, const T1 &y);
 void add_mel_frontend(rvc_engine *e, Plan &pl, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, float *mel, const T2 &img, float bn_scale, float bn_shift);
 void add_pitch_post(Plan &pl, int B, const T1 &sal, int Tm, StreamState *st, const CallParams *cp, float *f0, bool update, long long shift, long long cache_start,
-                    long long read_start, int R, float *pitchf, int *pitch);
+                    long long read_start, int R, float *pitchf, int *pitch, const float *f0_in = nullptr);
 void add_nsf_source(Plan &pl, int B, const float *pitchf, const T1 &src, int R, int upp, float sr, float lin_w, float lin_b, const StreamState *st, const CallParams *cp,
                     int f0_num, int f0_den);
 std::vector<T1> build_noise_convs(rvc_engine *e, Plan &pl, int B, const T1 &src);

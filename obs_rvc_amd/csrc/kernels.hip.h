@@ -1073,6 +1073,7 @@ static __global__ __launch_bounds__(384) void gru_multi_kernel(GruMultiP p)
 // slice (rvc.rs:167-179) + get_f0_post (f0/mod.rs:7-12).  One workgroup per stream.
 struct PitchP {
     const float *sal; int sal_cs; long long sal_bs;   // salience [B][360][ld] (channel-major)
+    const float *f0_in;   // [B][Tm] f0 in Hz from another method (yin.hip.h): when set, the salience decode and its threshold are skipped and the tail below runs on it
     int Tm;
     StreamState *st; const CallParams *cp;
     float *f0;            // [B][Tm] (shifted f0, tap)
@@ -1097,7 +1098,7 @@ static __global__ __launch_bounds__(1024) void pitch_post_kernel(PitchP p)
     int TT = 1; while (TT < p.Tm) TT <<= 1;
     TT = TT < 1024 ? TT : 1024;
     const int NG = 1024 / TT, BPG = (360 + NG - 1) / NG, tt = t & (TT - 1), grp = t / TT;
-    {
+    if (!p.f0_in) {
         float best = 0.f, mx = -INFINITY; int start = 0;
         if (tt < p.Tm) {
             const float *col = p.sal + (long long)b * p.sal_bs + tt;
@@ -1112,13 +1113,14 @@ static __global__ __launch_bounds__(1024) void pitch_post_kernel(PitchP p)
     if (grp == 0 && tt < p.Tm) {
         const float *col = p.sal + (long long)b * p.sal_bs + tt;
         int start = 0; float best = 0.f, mx = -INFINITY;
-        for (int g = 0; g < NG; g++) {
+        for (int g = 0; g < (p.f0_in ? 0 : NG); g++) {
             const float v = f0s[g * TT + tt];
             if (v > best) { best = v; start = idxs[g * TT + tt]; }
             mx = fmaxf(mx, cache[g * TT + tt]);
         }
         float hz = 0.f;
-        if (start + 8 >= 360) { atomicOr(&st->status, (int)ST_PANIC); }
+        if (p.f0_in) hz = p.f0_in[(long long)b * p.Tm + tt];
+        else if (start + 8 >= 360) { atomicOr(&st->status, (int)ST_PANIC); }
         else {
             float sv[9];
 #pragma unroll

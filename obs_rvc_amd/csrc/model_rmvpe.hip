@@ -239,13 +239,13 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
 
 // decode + pitch shift + pitch cache + get_f0_post (rmvpe.rs:118-133,243-248; rvc.rs:121,167-180; f0/mod.rs:7-12) of the salience sal [B][360][Tm] on the
 // states st [B] (uppower, cache_pitchf, status): f0 [B][Tm]; update: the cache is shifted by `shift`, the new f0 inserted from cache_start on and
-// R values from read_start sliced into pitchf / pitch [B][R]
+// R values from read_start sliced into pitchf / pitch [B][R].  f0_in [B][Tm] (another method's f0 in Hz, model_yin.hip): sal is not read, the decode is skipped
 void add_pitch_post(Plan &pl, int B, const T1 &sal, int Tm, StreamState *st, const CallParams *cp, float *f0, bool update, long long shift, long long cache_start,
-                    long long read_start, int R, float *pitchf, int *pitch)
+                    long long read_start, int R, float *pitchf, int *pitch, const float *f0_in)
 {
-    if (sal.C != 360 || sal.T != Tm || Tm < 1 || Tm > 1024) throw ShapeError("pitch decode: salience shape");
+    if ((!f0_in && (sal.C != 360 || sal.T != Tm)) || Tm < 1 || Tm > 1024) throw ShapeError("pitch decode: salience shape");
     PitchP pp{};
-    pp.sal = sal.p; pp.sal_cs = sal.ld; pp.sal_bs = sal.bs; pp.Tm = Tm;
+    pp.sal = sal.p; pp.sal_cs = sal.ld; pp.sal_bs = sal.bs; pp.Tm = Tm; pp.f0_in = f0_in;
     pp.st = st; pp.cp = cp; pp.f0 = f0; pp.threshold = 0.03f;   // rvc.rs:122
     if (update) {
         if (shift < 0 || shift > 1024 || Tm < 5) throw PanicError("pitch cache shift out of range");
@@ -260,12 +260,12 @@ void add_pitch_post(Plan &pl, int B, const T1 &sal, int Tm, StreamState *st, con
 }
 
 void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update_cache, size_t frame16k, size_t hubert_length,
-                             float **pitchf_out, int **pitch_out)
+                             float **pitchf_out, int **pitch_out, const float *f0_in)
 {
     Arena &A = pl.arena;
     const int Tm = pl.Tm;
     pl.d_f0 = A.floats((size_t)B * Tm);
-    if (!update_cache) { add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, false, 0, 0, 0, 0, nullptr, nullptr); return; }
+    if (!update_cache) { add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, false, 0, 0, 0, 0, nullptr, nullptr, f0_in); return; }
     const int R = (int)pl.R;
     const size_t shift = frame16k / 160;                                   // rvc.rs:168
     if (shift > 1024 || Tm < 5) throw PanicError("pitch cache shift out of range");
@@ -274,7 +274,7 @@ void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update
     if (cache_start < 0 || read_start < 0 || read_start + R > 1024) throw PanicError("pitch cache slice out of range");
     float *pitchf = A.floats((size_t)B * R);
     int *pitch = (int *)A.alloc((size_t)B * R * sizeof(int));
-    add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, true, (long long)shift, cache_start, read_start, R, pitchf, pitch);
+    add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, true, (long long)shift, cache_start, read_start, R, pitchf, pitch, f0_in);
     *pitchf_out = pitchf; *pitch_out = pitch;
 }
 

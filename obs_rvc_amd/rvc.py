@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _native
-from .rvc_common import CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, PitchAlgorithm, RvcInferError, RvcModelVersion  # noqa: F401
+from .rvc_common import CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_RMVPE, F0_YIN, PitchAlgorithm, RvcInferError, RvcModelVersion  # noqa: F401
 
 _FP = C.POINTER(C.c_float)
 
@@ -55,6 +55,19 @@ class RvcInfer:
 
     def load_f0(self, pitch_algorithm=PitchAlgorithm.Rmvpe):
         self._chk(self._L.rvc_load_f0(self._h, int(PitchAlgorithm.from_value(pitch_algorithm))))
+
+    def load_f0_method(self, method):
+        """The engine's f0 method: "rmvpe" / F0_RMVPE (loads <data>/f0/rmvpe.rvcw, as load_f0) or "yin" / F0_YIN (needs no file)."""
+        if isinstance(method, str):
+            if method.lower() not in ("rmvpe", "yin"):
+                raise ValueError("f0 method: 'rmvpe' or 'yin', not %r" % method)
+            method = {"rmvpe": F0_RMVPE, "yin": F0_YIN}[method.lower()]
+        self._chk(self._L.rvc_load_f0_method(self._h, int(method)))
+
+    @property
+    def f0_method(self) -> int:
+        """0 = none loaded, F0_RMVPE, F0_YIN"""
+        return int(self._L.rvc_f0_method(self._h))
 
     def unload_model(self):
         self._L.rvc_unload_model(self._h)

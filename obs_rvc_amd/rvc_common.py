@@ -8,6 +8,8 @@ import enum
 
 # crossfade of the SOLA seam (include/rvc_mi355x.h RVC_CROSSFADE_*): the plugin's sin^2 blend, or the phase-vocoder blend
 CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER = 0, 1
+# f0 methods of rvc_load_f0_method (include/rvc_mi355x.h RVC_F0_*): PitchAlgorithm below stays the reference's one-variant enum
+F0_RMVPE, F0_YIN = 1, 2
 # input gate: a threshold at or below this many dB switches it off
 INPUT_GATE_OFF_DB = -60.0
 
