@@ -70,6 +70,15 @@ extern "C" {
     pub fn rvc_set_formant_shift(e: *mut RvcEngine, semitones: f64) -> c_int;
     pub fn rvc_set_formant_shift_stream(e: *mut RvcEngine, stream: c_int, semitones: f64) -> c_int;
     pub fn rvc_formant_geometry(return_length: usize, sample_rate: usize, semitones: f64, out: *mut usize) -> c_int;
+    // ---- pitch controls: transpose in semitones [-24, 24], voiced range in Hz, f0 median radius 0..7, snap to a 12-bit pitch-class mask
+    pub fn rvc_set_pitch_semitones(e: *mut RvcEngine, semitones: f64) -> c_int;
+    pub fn rvc_set_pitch_semitones_stream(e: *mut RvcEngine, stream: c_int, semitones: f64) -> c_int;
+    pub fn rvc_set_f0_range(e: *mut RvcEngine, lo_hz: f64, hi_hz: f64) -> c_int;
+    pub fn rvc_set_f0_range_stream(e: *mut RvcEngine, stream: c_int, lo_hz: f64, hi_hz: f64) -> c_int;
+    pub fn rvc_set_f0_median(e: *mut RvcEngine, radius: c_int) -> c_int;
+    pub fn rvc_set_f0_median_stream(e: *mut RvcEngine, stream: c_int, radius: c_int) -> c_int;
+    pub fn rvc_set_f0_snap(e: *mut RvcEngine, pitch_class_mask: u32, strength: f64) -> c_int;
+    pub fn rvc_set_f0_snap_stream(e: *mut RvcEngine, stream: c_int, pitch_class_mask: u32, strength: f64) -> c_int;
 
     // ---- multi-GPU: the one collective (index broadcast at load, RCCL over xGMI)
     pub fn rvc_rccl_unique_id(id128: *mut c_void) -> c_int;

@@ -183,6 +183,31 @@ impl RvcInfer {
         let rc = unsafe { ffi::rvc_set_formant_shift(self.handle, semitones) };
         self.check(rc)
     }
+
+    /// transpose in semitones, [-24, 24], fractions allowed, every stream; the integer `pitch_shift` of `pitch` / `infer` keeps the
+    /// reference's whole-octave meaning (rvc.rs:121)
+    pub fn set_pitch_semitones(&mut self, semitones: f64) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_pitch_semitones(self.handle, semitones) };
+        self.check(rc)
+    }
+
+    /// voiced range in Hz, every stream: a voiced f0 row outside [lo_hz, hi_hz] becomes unvoiced; (0, +inf) = off
+    pub fn set_f0_range(&mut self, lo_hz: f64, hi_hz: f64) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_f0_range(self.handle, lo_hz, hi_hz) };
+        self.check(rc)
+    }
+
+    /// median filter on the f0 curve (upstream's `filter_radius`), radius 0..7, every stream
+    pub fn set_f0_median(&mut self, radius: i32) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_f0_median(self.handle, radius) };
+        self.check(rc)
+    }
+
+    /// snap f0 to a scale, every stream: bit k of `pitch_class_mask` allows pitch class k (C = 0), `strength` in [0, 1]; mask 0 = off
+    pub fn set_f0_snap(&mut self, pitch_class_mask: u32, strength: f64) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_f0_snap(self.handle, pitch_class_mask, strength) };
+        self.check(rc)
+    }
 }
 
 impl Drop for RvcInfer {

@@ -114,6 +114,30 @@ rvc_status rvc_set_formant_shift_stream(rvc_engine *e, int stream, double semito
 /* host only, pure: out = {R2, upp_res} of a return_length, a model sample rate (a multiple of 100) and a shift */
 rvc_status rvc_formant_geometry(size_t return_length, size_t sample_rate, double semitones, size_t out[2]);
 
+/* ---- pitch controls: transpose in semitones, voiced range, f0 median filter, snap to a scale (DESIGN.md "Pitch controls") ---- */
+/* The integer pitch_shift arguments of rvc_pitch / rvc_infer* / rvc_session_* keep the reference's meaning bit for bit: 2^(pitch_shift / 12) with
+ * Rust's truncating division (rvc.rs:121), i.e. whole octaves only -- pitch_shift = 7 shifts nothing.  rvc_set_pitch_semitones is the real
+ * transpose.  Per stream and per chunk, on the f0 rows of the window (0 Hz = unvoiced), from either f0 method, in this order:
+ *   1. f *= 2^(pitch_shift / 12) [* the formant factor on infer calls] * (float)2^(semitones / 12); semitones = 0 multiplies by nothing
+ *   2. range gate: a voiced row with f < lo_hz or f > hi_hz becomes unvoiced; lo_hz = 0 and hi_hz = +inf = off
+ *   3. median filter of radius 0..7 (window 2 r + 1, rows outside the window are 0, unvoiced zeros take part): scipy.signal.medfilt
+ *   4. scale snap: bit k of pitch_class_mask allows pitch class k (C = 0; MIDI note n is allowed iff bit n mod 12 is set); with
+ *      n = 69 + 12 log2(f / 440) and target = the nearest allowed note (a tie goes to the lower one), f *= 2^(strength (target - n) / 12);
+ *      mask = 0 or strength = 0 = off; mask bits above bit 11, strength outside [0, 1]: RVC_SHAPE
+ * The conditioned rows are what rvc_pitch returns, what the "f0" tap shows and what the pitch cache and the synthesizer get.  Semantics as
+ * rvc_set_formant_shift[_stream]: the engine-wide call sets every stream and the default of streams rvc_set_streams adds later,
+ * rvc_reset_state leaves the values alone, a bad stream number gives RVC_SHAPE with a message.  Unlike the formant shift the values are no
+ * part of a plan's identity: changing them between chunks builds no plan, and they hold under graph replay, chunk pipelining,
+ * rvc_infer_batch_g and the session. */
+rvc_status rvc_set_pitch_semitones(rvc_engine *e, double semitones);                   /* [-24, 24]; NaN / out of range: RVC_SHAPE */
+rvc_status rvc_set_pitch_semitones_stream(rvc_engine *e, int stream, double semitones);
+rvc_status rvc_set_f0_range(rvc_engine *e, double lo_hz, double hi_hz);                /* 0, +inf = off; lo > hi, negative, NaN: RVC_SHAPE */
+rvc_status rvc_set_f0_range_stream(rvc_engine *e, int stream, double lo_hz, double hi_hz);
+rvc_status rvc_set_f0_median(rvc_engine *e, int radius);                               /* 0..7 */
+rvc_status rvc_set_f0_median_stream(rvc_engine *e, int stream, int radius);
+rvc_status rvc_set_f0_snap(rvc_engine *e, uint32_t pitch_class_mask, double strength);
+rvc_status rvc_set_f0_snap_stream(rvc_engine *e, int stream, uint32_t pitch_class_mask, double strength);
+
 /* ---- multi-GPU (BASELINE configs[4]; no counterpart in the reference: one RvcInfer per process, rvc.rs:133-134) ---- */
 /* Streams shard across GPUs with NO per-chunk collective: one process + one engine per GPU, stream s on rank s mod world.  The one
  * exchange step is at load: the shared retrieval index travels from rank 0 into every rank's HBM with ONE ncclBroadcast over
@@ -228,7 +252,8 @@ rvc_status rvc_resampler_process_device(rvc_resampler *r, const void *d_in, void
  * one synchronisation per chunk (with the phase-vocoder crossfade and the input gate as well).  Lengths in seconds as in the plugin's settings; skip_inference != 0 = pass-through mode
  * (lib.rs:224-227).  The session covers every stream of the engine (rvc_set_streams before rvc_session_create): process then takes
  * input [streams][n] and writes output [streams][cap], sola_offset [streams].  Destroy the session before the engine.  The session has no
- * formant setting of its own: it honours the engine's per-stream values (rvc_set_formant_shift[_stream]). */
+ * formant setting and no pitch controls of its own: it honours the engine's per-stream values (rvc_set_formant_shift[_stream],
+ * rvc_set_pitch_semitones / rvc_set_f0_range / rvc_set_f0_median / rvc_set_f0_snap [_stream]). */
 typedef struct rvc_session rvc_session;
 rvc_status rvc_session_create(rvc_engine *e, size_t sample_rate, double sample_length, double crossfade_length, double extra_inference_time,
                               size_t model_output_sample_rate, int32_t pitch_shift, double rms_mix_rate, int skip_inference, rvc_session **out);

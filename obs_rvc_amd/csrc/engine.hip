@@ -179,6 +179,7 @@ static void alloc_state(rvc_engine *e)
     if (e->d_bucket_idx) { (void)hipFree(e->d_bucket_idx); e->d_bucket_idx = nullptr; }
     HIPCHK(hipMalloc(&e->d_state, sizeof(StreamState) * e->n_streams));
     e->formant.resize(e->n_streams, e->formant_default);     // existing streams keep their formant shift, new ones get the default
+    e->pitch_ctl.resize(e->n_streams, e->pitch_ctl_default); // the same for the pitch controls
     reset_state(e);
     e->plans.clear();
     e->last_plan = nullptr;
@@ -389,6 +390,8 @@ static void run_plan(rvc_engine *e, Plan &pl)
 
 // ------------------------------- formant shift ----------------------------------------
 static_assert(offsetof(StreamState, f_ident) + sizeof(int) - offsetof(StreamState, f_tab) == sizeof(FormantDesc), "StreamState formant fields != FormantDesc");
+static_assert(offsetof(StreamState, c_strength) + sizeof(float) - offsetof(StreamState, c_on) == sizeof(F0Cond), "StreamState pitch-control fields != F0Cond");
+static_assert(sizeof(StreamState) % 4 == 0, "state_gather_kernel copies StreamState in 32-bit words");
 
 // the device form of the filter table o -> n, built once per engine (the descriptors of a captured graph's streams point at it)
 static const FormantTable &formant_table_dev(rvc_engine *e, int o, int n)
@@ -456,11 +459,14 @@ static float uppower(int32_t pitch_shift) { return ldexpf(1.0f, pitch_shift / 12
 // is its own caller with its own settings, obs-rvc/src/lib.rs:701-707).  shifts == nullptr: `pitch_shift` for every stream.
 // Rs (infer calls: the return_length of every stream): the multiplier also carries the stream's formant factor (float)2^(-phi / 12), and
 // the stream's formant descriptor is written next to it; without Rs (hubert / pitch) no formant factor and the descriptors stay.
+// Every call: a stream with a semitone transpose st != 0 has (float)2^(st / 12) multiplied in last (st = 0 multiplies by nothing), and the
+// stream's other pitch controls (F0Cond) are copied when they differ from what the device holds.
 static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *shifts = nullptr, const uint32_t *Rs = nullptr)
 {
     const int B = e->n_streams;
     std::vector<float> up(B);
     std::vector<FormantDesc> fd((size_t)B, FormantDesc{});
+    std::vector<F0Cond> fc((size_t)B);
     if (!Rs && (int)e->pushed_fd.size() == B) fd = e->pushed_fd;
     for (int b = 0; b < B; b++) {
         up[b] = uppower(shifts ? shifts[b] : pitch_shift);
@@ -468,12 +474,16 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
             up[b] *= (float)std::pow(2.0, -e->formant[b] / 12.0);
             fd[b] = formant_desc(e, b, Rs[b]);
         }
+        const rvc_engine::PitchCtl &pc = e->pitch_ctl[b];
+        if (pc.semitones != 0.0) up[b] *= (float)std::pow(2.0, pc.semitones / 12.0);
+        fc[b] = f0cond_pack(pc.lo, pc.hi, pc.radius, pc.mask, pc.strength);
     }
     // The device already holds these values (every write to them is ordered on the main stream, and the last one wrote exactly this):
     // nothing to copy -- a small H2D copy is a 4-5 us blit kernel in front of both branches of every chunk otherwise.
     bool same = e->pushed_valid && e->pushed_seed == e->seed && (int)e->pushed_up.size() == B && (int)e->pushed_fd.size() == B;
+    const bool fc_same = same && e->pushed_fc == fc;
     for (int b = 0; b < B && same; b++) same = e->pushed_up[b] == up[b] && e->pushed_fd[b] == fd[b];
-    if (same) return;
+    if (same && fc_same) return;
     if (e->pipeline) HIPCHK(hipDeviceSynchronize());   // the f0 branch of the next chunk may already be running: drain before the values change
     // every call writes its own pinned block: an unsynchronised call's copy may still be pending when the next call arrives
     if (!e->pushed_valid || e->pushed_seed != e->seed) {
@@ -489,10 +499,12 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
     if (e->ev_up_used[us]) HIPCHK(hipEventSynchronize(e->ev_up[us]));
     float *hu = e->h_up + (size_t)us * 4096;
     FormantDesc *hf = e->h_fd + (size_t)us * 4096;
-    for (int b = 0; b < B; b++) { hu[b] = up[b]; hf[b] = fd[b]; }
-    e->pushed_up = up; e->pushed_fd = fd;
+    F0Cond *hc = e->h_fc + (size_t)us * 4096;
+    for (int b = 0; b < B; b++) { hu[b] = up[b]; hf[b] = fd[b]; hc[b] = fc[b]; }
+    e->pushed_up = up; e->pushed_fd = fd; e->pushed_fc = fc;
     HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, uppower), sizeof(StreamState), hu, sizeof(float), sizeof(float), (size_t)B, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, f_tab), sizeof(StreamState), hf, sizeof(FormantDesc), sizeof(FormantDesc), (size_t)B, hipMemcpyHostToDevice, e->stream));
+    if (!fc_same) HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, c_on), sizeof(StreamState), hc, sizeof(F0Cond), sizeof(F0Cond), (size_t)B, hipMemcpyHostToDevice, e->stream));
     if (!e->ev_up[us]) HIPCHK(hipEventCreateWithFlags(&e->ev_up[us], hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->ev_up[us], e->stream)); e->ev_up_used[us] = true;
     e->pushed_seed = e->seed; e->pushed_valid = true;
@@ -639,6 +651,7 @@ rvc_status rvc_create(const char *data_path, int device, rvc_engine **out)
         memset(e->h_status, 0, 4096 * sizeof(int));
         HIPCHK(hipHostMalloc((void **)&e->h_up, (size_t)8 * 4096 * sizeof(float)));
         HIPCHK(hipHostMalloc((void **)&e->h_fd, (size_t)8 * 4096 * sizeof(FormantDesc)));
+        HIPCHK(hipHostMalloc((void **)&e->h_fc, (size_t)8 * 4096 * sizeof(F0Cond)));
         init_constants(e);
         alloc_state(e);
     } catch (const std::exception &x) {
@@ -673,6 +686,7 @@ void rvc_destroy(rvc_engine *e)
     if (e->h_status) (void)hipHostFree(e->h_status);
     if (e->h_up) (void)hipHostFree(e->h_up);
     if (e->h_fd) (void)hipHostFree(e->h_fd);
+    if (e->h_fc) (void)hipHostFree(e->h_fc);
     for (auto &kv : e->ftabs) { (void)hipFree(kv.second.tab); (void)hipFree(kv.second.kb); }
     for (int i = 0; i < 8; i++) if (e->ev_up[i]) (void)hipEventDestroy(e->ev_up[i]);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -1126,6 +1140,48 @@ rvc_status rvc_set_formant_shift_stream(rvc_engine *e, int stream, double semito
         return RVC_OK;
     });
 }
+
+// pitch controls (f0cond.hip.h; DESIGN.md "Pitch controls"): per stream, read by the pitch tail every chunk, no part of a plan's identity.  The
+// engine-wide calls set every stream and the default of streams rvc_set_streams adds later; rvc_reset_state leaves the values alone.
+static rvc_status set_pitch_ctl(rvc_engine *e, const int *stream, const char *what, const std::function<const char *()> &check, const std::function<void(rvc_engine::PitchCtl &)> &set)
+{
+    return guarded(e, [&]() {
+        if (stream && (*stream < 0 || *stream >= e->n_streams)) throw ShapeError(std::string(what) + ": stream out of range");
+        if (const char *bad = check()) throw ShapeError(std::string(what) + ": " + bad);
+        if (stream) set(e->pitch_ctl[*stream]);
+        else { set(e->pitch_ctl_default); for (auto &c : e->pitch_ctl) set(c); }
+        return RVC_OK;
+    });
+}
+static rvc_status set_pitch_semitones(rvc_engine *e, const int *stream, double st)
+{
+    return set_pitch_ctl(e, stream, "pitch semitones", [&]() -> const char * { return st >= -PITCH_SEMITONES_MAX && st <= PITCH_SEMITONES_MAX ? nullptr : "semitones outside [-24, 24]"; },
+                         [&](rvc_engine::PitchCtl &c) { c.semitones = st; });
+}
+static rvc_status set_f0_range(rvc_engine *e, const int *stream, double lo, double hi)
+{
+    return set_pitch_ctl(e, stream, "f0 range", [&]() -> const char * { return lo >= 0.0 && hi >= lo ? nullptr : "needs 0 <= lo_hz <= hi_hz"; },
+                         [&](rvc_engine::PitchCtl &c) { c.lo = (float)lo; c.hi = (float)hi; });
+}
+static rvc_status set_f0_median(rvc_engine *e, const int *stream, int radius)
+{
+    return set_pitch_ctl(e, stream, "f0 median", [&]() -> const char * { return radius >= 0 && radius <= F0_MEDIAN_MAX ? nullptr : "radius outside 0..7"; },
+                         [&](rvc_engine::PitchCtl &c) { c.radius = radius; });
+}
+static rvc_status set_f0_snap(rvc_engine *e, const int *stream, uint32_t mask, double strength)
+{
+    return set_pitch_ctl(e, stream, "f0 snap", [&]() -> const char * { return mask > 0xFFFu ? "pitch-class mask has bits above bit 11" : (strength >= 0.0 && strength <= 1.0 ? nullptr : "strength outside [0, 1]"); },
+                         [&](rvc_engine::PitchCtl &c) { c.mask = mask; c.strength = (float)strength; });
+}
+rvc_status rvc_set_pitch_semitones(rvc_engine *e, double semitones) { return set_pitch_semitones(e, nullptr, semitones); }
+rvc_status rvc_set_pitch_semitones_stream(rvc_engine *e, int stream, double semitones) { return set_pitch_semitones(e, &stream, semitones); }
+rvc_status rvc_set_f0_range(rvc_engine *e, double lo_hz, double hi_hz) { return set_f0_range(e, nullptr, lo_hz, hi_hz); }
+rvc_status rvc_set_f0_range_stream(rvc_engine *e, int stream, double lo_hz, double hi_hz) { return set_f0_range(e, &stream, lo_hz, hi_hz); }
+rvc_status rvc_set_f0_median(rvc_engine *e, int radius) { return set_f0_median(e, nullptr, radius); }
+rvc_status rvc_set_f0_median_stream(rvc_engine *e, int stream, int radius) { return set_f0_median(e, &stream, radius); }
+rvc_status rvc_set_f0_snap(rvc_engine *e, uint32_t pitch_class_mask, double strength) { return set_f0_snap(e, nullptr, pitch_class_mask, strength); }
+rvc_status rvc_set_f0_snap_stream(rvc_engine *e, int stream, uint32_t pitch_class_mask, double strength) { return set_f0_snap(e, &stream, pitch_class_mask, strength); }
+
 rvc_status rvc_formant_geometry(size_t return_length, size_t sample_rate, double semitones, size_t out[2])
 {
     if (!out) return RVC_SHAPE;

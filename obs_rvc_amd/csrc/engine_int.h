@@ -12,6 +12,7 @@
 #include "blob.h"
 #include "kernels.hip.h"
 #include "formant.hip.h"
+#include "f0cond.hip.h"
 #include "igemm_launch.h"
 #include <hip/hip_ext.h>
 
@@ -925,6 +926,12 @@ struct rvc_engine {
     std::map<std::pair<int, int>, rvc::FormantTable> ftabs;
     std::vector<rvc::FormantDesc> pushed_fd;
     rvc::FormantDesc *h_fd = nullptr;     // pinned ring of 8 blocks of 4096 descriptors, written and read with h_up's blocks
+    // pitch controls (f0cond.hip.h; rvc_set_pitch_semitones / f0_range / f0_median / f0_snap [_stream]): per stream and the default of new streams.  No part
+    // of a plan's identity: the transpose is a factor of the pushed multiplier, the rest travels as F0Cond words next to the formant descriptor
+    struct PitchCtl { double semitones = 0.0; float lo = 0.f, hi = INFINITY; int radius = 0; uint32_t mask = 0; float strength = 0.f; };
+    std::vector<PitchCtl> pitch_ctl; PitchCtl pitch_ctl_default;
+    std::vector<rvc::F0Cond> pushed_fc;
+    rvc::F0Cond *h_fc = nullptr;          // pinned ring of 8 blocks of 4096, as h_fd
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };

@@ -3,6 +3,7 @@
 #pragma once
 #include "igemm.hip.h"
 #include "state.hip.h"
+#include "f0cond.hip.h"
 
 namespace rvc {
 
@@ -1069,8 +1070,8 @@ static __global__ __launch_bounds__(384) void gru_multi_kernel(GruMultiP p)
 // ------------------------------------------------------------------------------------
 // (CallParams / StreamState: state.hip.h)
 
-// RMVPE decode (rmvpe.rs:118-133, 243-248) + pitch shift (rvc.rs:121-122) + pitch cache update and
-// slice (rvc.rs:167-179) + get_f0_post (f0/mod.rs:7-12).  One workgroup per stream.
+// RMVPE decode (rmvpe.rs:118-133, 243-248) + pitch shift (rvc.rs:121-122) + the stream's pitch controls (f0cond.hip.h) + pitch cache
+// update and slice (rvc.rs:167-179) + get_f0_post (f0/mod.rs:7-12).  One workgroup per stream.
 struct PitchP {
     const float *sal; int sal_cs; long long sal_bs;   // salience [B][360][ld] (channel-major)
     const float *f0_in;   // [B][Tm] f0 in Hz from another method (yin.hip.h): when set, the salience decode and its threshold are skipped and the tail below runs on it
@@ -1135,10 +1136,19 @@ static __global__ __launch_bounds__(1024) void pitch_post_kernel(PitchP p)
         }
         hz *= up;
         hz_out = hz;
-        p.f0[(long long)b * p.Tm + tt] = hz;
     }
     __syncthreads();
-    if (grp == 0 && tt < p.Tm) f0s[tt] = hz_out;
+    // pitch controls (f0cond.hip.h): gate, median and scale snap on the multiplied rows, for either f0 method and for update = 0; a stream with every
+    // control neutral (c_on == 0, uniform over the workgroup) passes with this one load
+    const uint32_t con = st->c_on;
+    if (con) {
+        const float lo = st->c_lo, hi = st->c_hi, strength = st->c_strength;
+        if (grp == 0 && tt < p.Tm) f0s[tt] = f0cond_gate(hz_out, con, lo, hi);
+        __syncthreads();
+        if (grp == 0 && tt < p.Tm) hz_out = f0cond_row(f0s, p.Tm, tt, con, strength);     // (kept in the register across the barrier: the neighbours still read f0s[])
+        __syncthreads();
+    }
+    if (grp == 0 && tt < p.Tm) { f0s[tt] = hz_out; p.f0[(long long)b * p.Tm + tt] = hz_out; }
     if (!p.update) return;
     __syncthreads();
     cache[t] = st->cache_pitchf[t];

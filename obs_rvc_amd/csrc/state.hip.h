@@ -24,6 +24,11 @@ struct StreamState {        // one per stream
     const float *f_tab;     // [n][kt] filter rows (the engine's table cache), nullptr when f_ident
     const int *f_kb;        // [n] first tap of each row
     int f_o, f_n, f_w, f_kt, f_nx, f_ident;     // ratio o -> n, left width, taps per row, valid input samples (R upp_res), 1 = copy
+    // pitch controls of this stream (f0cond.hip.h F0Cond, read by pitch_post_kernel every chunk; written by the host like the formant fields).  The
+    // semitone transpose has no field: it is a factor of uppower
+    uint32_t c_on;          // 0 = every control neutral (the tail skips the stage); bits 0-3 median radius, 4-15 pitch-class mask, 16 range gate
+    float c_lo, c_hi;       // range gate in Hz
+    float c_strength;       // scale snap strength, (0, 1]
 };
 
 // status bits of a stream (several kernels of one chunk may report; a plain store would lose the earlier report)

@@ -9,7 +9,8 @@ import os
 import numpy as np
 
 from . import _native
-from .rvc_common import CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_RMVPE, F0_YIN, PitchAlgorithm, RvcInferError, RvcModelVersion  # noqa: F401
+from .rvc_common import (CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_RMVPE, F0_YIN, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
+                         RvcInferError, RvcModelVersion, scale_mask)
 
 _FP = C.POINTER(C.c_float)
 
@@ -177,6 +178,44 @@ class RvcInfer:
             self._chk(self._L.rvc_set_formant_shift(self._h, float(semitones)))
         else:
             self._chk(self._L.rvc_set_formant_shift_stream(self._h, int(stream), float(semitones)))
+
+    def set_pitch_semitones(self, st: float, stream: int = None):
+        """Transpose in semitones, -24..24, fractions allowed: every stream and the default of streams added later, or (stream given) one
+        stream (rvc_set_pitch_semitones[_stream]).  The integer pitch_shift of pitch / infer keeps the reference's whole-octave meaning."""
+        if stream is None:
+            self._chk(self._L.rvc_set_pitch_semitones(self._h, float(st)))
+        else:
+            self._chk(self._L.rvc_set_pitch_semitones_stream(self._h, int(stream), float(st)))
+
+    def set_f0_range(self, lo: float, hi: float, stream: int = None):
+        """Voiced range in Hz: a voiced f0 row outside [lo, hi] becomes unvoiced; (0, inf) = off (rvc_set_f0_range[_stream])."""
+        if stream is None:
+            self._chk(self._L.rvc_set_f0_range(self._h, float(lo), float(hi)))
+        else:
+            self._chk(self._L.rvc_set_f0_range_stream(self._h, int(stream), float(lo), float(hi)))
+
+    def set_f0_median(self, r: int, stream: int = None):
+        """Median filter on the f0 rows of a chunk, radius 0..7 (upstream's filter_radius; rvc_set_f0_median[_stream])."""
+        if stream is None:
+            self._chk(self._L.rvc_set_f0_median(self._h, int(r)))
+        else:
+            self._chk(self._L.rvc_set_f0_median_stream(self._h, int(stream), int(r)))
+
+    def set_f0_snap(self, mask_or_name, strength: float, stream: int = None):
+        """Snap f0 to a scale with a strength in [0, 1]: a 12-bit pitch-class mask (SCALE_CHROMATIC, SCALE_C_MAJOR, scale_mask(root, kind);
+        0 = off) or a name "<root> <kind>" such as "C major", "F# minor", "chromatic" (rvc_set_f0_snap[_stream])."""
+        if isinstance(mask_or_name, str):
+            words = mask_or_name.split()
+            if len(words) not in (1, 2):
+                raise ValueError("scale: '<root> <kind>' or 'chromatic', not %r" % mask_or_name)
+            mask_or_name = scale_mask(0 if len(words) == 1 else words[0], words[-1].lower())
+        mask = int(mask_or_name)
+        if not 0 <= mask < 1 << 32:
+            raise RvcInferError(5, "f0 snap: the pitch-class mask is a 12-bit value")
+        if stream is None:
+            self._chk(self._L.rvc_set_f0_snap(self._h, mask, float(strength)))
+        else:
+            self._chk(self._L.rvc_set_f0_snap_stream(self._h, int(stream), mask, float(strength)))
 
     @staticmethod
     def formant_geometry(return_length: int, sample_rate: int, semitones: float):

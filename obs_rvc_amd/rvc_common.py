@@ -12,6 +12,29 @@ CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER = 0, 1
 F0_RMVPE, F0_YIN = 1, 2
 # input gate: a threshold at or below this many dB switches it off
 INPUT_GATE_OFF_DB = -60.0
+# scale snap (rvc_set_f0_snap): bit k of a mask allows pitch class k, C = 0, so MIDI note n is allowed iff bit n % 12 is set
+SCALE_CHROMATIC = 0xFFF
+_SCALE_STEPS = {"major": (0, 2, 4, 5, 7, 9, 11), "minor": (0, 2, 3, 5, 7, 8, 10), "chromatic": tuple(range(12))}
+_NOTE_NAMES = {"c": 0, "d": 2, "e": 4, "f": 5, "g": 7, "a": 9, "b": 11}
+
+
+def scale_mask(root, kind: str = "major") -> int:
+    """The pitch-class mask of a scale: root = a pitch class 0..11 or a note name ("C", "F#", "Bb"), kind = "major" | "minor" (natural
+    minor) | "chromatic"."""
+    if isinstance(root, str):
+        name = root.strip().lower()
+        if not name or name[0] not in _NOTE_NAMES or name[1:] not in ("", "#", "b"):
+            raise ValueError("scale root: a note name such as 'C', 'F#', 'Bb', not %r" % root)
+        root = _NOTE_NAMES[name[0]] + {"": 0, "#": 1, "b": -1}[name[1:]]
+    if kind not in _SCALE_STEPS:
+        raise ValueError("scale kind: 'major', 'minor' or 'chromatic', not %r" % kind)
+    mask = 0
+    for s in _SCALE_STEPS[kind]:
+        mask |= 1 << ((int(root) + s) % 12)
+    return mask
+
+
+SCALE_C_MAJOR = scale_mask(0, "major")        # 0xAB5
 
 
 class RvcModelVersion(enum.Enum):
