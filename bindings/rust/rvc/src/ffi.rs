@@ -79,6 +79,9 @@ extern "C" {
     pub fn rvc_set_f0_median_stream(e: *mut RvcEngine, stream: c_int, radius: c_int) -> c_int;
     pub fn rvc_set_f0_snap(e: *mut RvcEngine, pitch_class_mask: u32, strength: f64) -> c_int;
     pub fn rvc_set_f0_snap_stream(e: *mut RvcEngine, stream: c_int, pitch_class_mask: u32, strength: f64) -> c_int;
+    // ---- consonant protection (upstream's `protect`): [0, 0.5], 0.5 = off; unvoiced rows are mixed back towards the raw ContentVec features
+    pub fn rvc_set_protect(e: *mut RvcEngine, protect: f64) -> c_int;
+    pub fn rvc_set_protect_stream(e: *mut RvcEngine, stream: c_int, protect: f64) -> c_int;
 
     // ---- multi-GPU: the one collective (index broadcast at load, RCCL over xGMI)
     pub fn rvc_rccl_unique_id(id128: *mut c_void) -> c_int;

@@ -208,6 +208,13 @@ impl RvcInfer {
         let rc = unsafe { ffi::rvc_set_f0_snap(self.handle, pitch_class_mask, strength) };
         self.check(rc)
     }
+
+    /// consonant protection (upstream's `protect`), [0, 0.5], 0.5 = off, every stream: on calls that use the index, unvoiced rows become
+    /// `protect * blended + (1 - protect) * raw` ContentVec features
+    pub fn set_protect(&mut self, protect: f64) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_protect(self.handle, protect) };
+        self.check(rc)
+    }
 }
 
 impl Drop for RvcInfer {

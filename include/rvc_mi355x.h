@@ -138,6 +138,20 @@ rvc_status rvc_set_f0_median_stream(rvc_engine *e, int stream, int radius);
 rvc_status rvc_set_f0_snap(rvc_engine *e, uint32_t pitch_class_mask, double strength);
 rvc_status rvc_set_f0_snap_stream(rvc_engine *e, int stream, uint32_t pitch_class_mask, double strength);
 
+/* ---- consonant protection: upstream RVC's `protect`, next to the index rate (DESIGN.md "Consonant protection") ---- */
+/* With the index rate up, breaths and voiceless consonants are pulled towards index vectors as well, and they have no pitch for the synthesizer to hang them
+ * on ("tearing": buzzing on s, t, f).  Per stream, protect is a double in [0, 0.5]; 0.5 = off, the default (upstream: `protect < 0.5` enables it).  On an infer
+ * call whose plan uses the index (an index is loaded and the index rate is > 0), after the retrieval has blended and with the pitchf rows the synthesizer
+ * gets (pitch shift, pitch controls and the cache update done): a row r with pitchf[r] < 1.0f is unvoiced, and on unvoiced rows every channel becomes
+ *   phone[c][r] = p * phone[c][r] + (1 - p) * raw[c][r],   p = (float)protect, 1 - p in float, raw = the ContentVec feature the row had before the retrieval.
+ * Voiced rows, streams at 0.5 and calls without an index keep their bits; p = 0 gives the raw row.  rvc_get_knn's hits, rvc_hubert, rvc_extract_feature,
+ * rvc_pitch and the pitch cache are unaffected.  Semantics as rvc_set_pitch_semitones[_stream]: the engine-wide call sets every stream and the default of
+ * streams rvc_set_streams adds later, rvc_reset_state leaves the values alone, a bad stream number gives RVC_SHAPE with a message.  Whether ANY stream of
+ * a call is below 0.5 is part of a plan's identity (the first such call builds a plan, as the first call with an index does); the values are not: changing
+ * 0.33 to 0.2 between chunks builds nothing, and they hold under graph replay, chunk pipelining, rvc_infer_batch_g and the session. */
+rvc_status rvc_set_protect(rvc_engine *e, double protect);                 /* [0, 0.5]; 0.5 = off; NaN / out of range: RVC_SHAPE */
+rvc_status rvc_set_protect_stream(rvc_engine *e, int stream, double protect);
+
 /* ---- multi-GPU (BASELINE configs[4]; no counterpart in the reference: one RvcInfer per process, rvc.rs:133-134) ---- */
 /* Streams shard across GPUs with NO per-chunk collective: one process + one engine per GPU, stream s on rank s mod world.  The one
  * exchange step is at load: the shared retrieval index travels from rank 0 into every rank's HBM with ONE ncclBroadcast over
@@ -252,8 +266,8 @@ rvc_status rvc_resampler_process_device(rvc_resampler *r, const void *d_in, void
  * one synchronisation per chunk (with the phase-vocoder crossfade and the input gate as well).  Lengths in seconds as in the plugin's settings; skip_inference != 0 = pass-through mode
  * (lib.rs:224-227).  The session covers every stream of the engine (rvc_set_streams before rvc_session_create): process then takes
  * input [streams][n] and writes output [streams][cap], sola_offset [streams].  Destroy the session before the engine.  The session has no
- * formant setting and no pitch controls of its own: it honours the engine's per-stream values (rvc_set_formant_shift[_stream],
- * rvc_set_pitch_semitones / rvc_set_f0_range / rvc_set_f0_median / rvc_set_f0_snap [_stream]). */
+ * formant setting, no pitch controls and no consonant protection of its own: it honours the engine's per-stream values (rvc_set_formant_shift[_stream],
+ * rvc_set_pitch_semitones / rvc_set_f0_range / rvc_set_f0_median / rvc_set_f0_snap [_stream], rvc_set_protect[_stream]). */
 typedef struct rvc_session rvc_session;
 rvc_status rvc_session_create(rvc_engine *e, size_t sample_rate, double sample_length, double crossfade_length, double extra_inference_time,
                               size_t model_output_sample_rate, int32_t pitch_shift, double rms_mix_rate, int skip_inference, rvc_session **out);

@@ -101,6 +101,14 @@ typedef struct rvc_debug_front_spec {
     unsigned seed;
 } rvc_debug_front_spec;
 int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w0, const float *w1, float *const *buf, rvc_debug_stream_state *state, long long *geo);
+/* protect_mix_kernel alone (obs_rvc_amd/csrc/protect.hip.h; DESIGN.md "Consonant protection"), launched as a plan launches it: phone [streams][C][ph_ld]
+ * (R rows used; uploaded, mixed in place, downloaded whole: the padding comes back as it went in), cv [streams][C][cv_ld] (T columns used: the ContentVec
+ * output, channel-major), pitchf [streams][R], protect [streams] in [0, 0.5] (stored as float, as rvc_set_protect_stream stores it).  Needs ph_ld >= R,
+ * cv_ld >= T and skip_head + R <= 2 T + 1 (RVC_SHAPE otherwise).  graph != 0: captured and the graph launched once.  0 = done, else an rvc_status. */
+typedef struct rvc_debug_protect_spec {
+    int streams, C, R, T, skip_head, ph_ld, cv_ld, graph;
+} rvc_debug_protect_spec;
+int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *phone, const float *cv, const float *pitchf, const double *protect);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);

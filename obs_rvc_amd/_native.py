@@ -30,19 +30,20 @@ SYMBOLS = [
     "rvc_load_f0_method", "rvc_f0_method",
     "rvc_set_pitch_semitones", "rvc_set_pitch_semitones_stream", "rvc_set_f0_range", "rvc_set_f0_range_stream",
     "rvc_set_f0_median", "rvc_set_f0_median_stream", "rvc_set_f0_snap", "rvc_set_f0_snap_stream",
+    "rvc_set_protect", "rvc_set_protect_stream",
     "rvc_sola_step_x", "rvc_input_gate", "rvc_session_set_crossfade", "rvc_session_set_crossfade_stream", "rvc_session_set_input_gate", "rvc_session_set_input_gate_stream",
 ]
 
 
 SOURCES = ("engine.hip", "engine_int.h", "debug.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "yin.hip.h", "model_synth.hip", "retrieval.hip", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "igemm2_inst.hip", "igemm_tiled_inst.hip", "igemm2w_inst.hip", "igemm_bf3_inst.hip", "conv_tile.hip.h", "conv_tile_inst.hip", "conv32s.hip.h", "conv32s_inst.hip", "rmblock.hip.h", "igemm32l.hip.h", "igemm32l_inst.hip", "version.cpp", "calib.hip", "exports.map",
-           "state.hip.h", "formant.hip.h", "f0cond.hip.h", "crossfade.hip.h",
+           "state.hip.h", "formant.hip.h", "f0cond.hip.h", "protect.hip.h", "crossfade.hip.h",
            "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h", "blob.h", "rvc_rpc.cpp")
 
 # translation units of the library: (source, extra flags, files whose contents decide whether the object is stale).  The implicit-GEMM
 # template instantiations are the bulk of the compile time; as separate units they build in parallel (5 min -> about 1.5 min on 8 cores)
 # and are not rebuilt when only the engine changes.
 _IGEMM_DEPS = ("igemm.hip.h", "igemm_launch.h")
-_INT_DEPS = ("engine_int.h", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "blob.h", "state.hip.h", "formant.hip.h", "f0cond.hip.h")
+_INT_DEPS = ("engine_int.h", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "blob.h", "state.hip.h", "formant.hip.h", "f0cond.hip.h", "protect.hip.h")
 _ENGINE_DEPS = ("engine.hip", "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h", "crossfade.hip.h") + _INT_DEPS
 UNITS = [("engine.hip", [], _ENGINE_DEPS), ("debug.hip", [], ("debug.hip", "../../include/rvc_mi355x_debug.h") + _INT_DEPS), ("calib.hip", [], ("calib.hip",))] + [(u, [], (u,) + _INT_DEPS + (("rmblock.hip.h",) if u == "model_rmvpe.hip" else ()) + (("yin.hip.h",) if u == "model_yin.hip" else ())) for u in ("plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "model_synth.hip", "retrieval.hip")] + \
         [("igemm2_inst.hip", ["-DRVC_IGEMM2_CFG=%d" % c], ("igemm2_inst.hip",) + _IGEMM_DEPS) for c in range(5)] + \
@@ -302,6 +303,9 @@ def lib():
         L.rvc_set_f0_median_stream.argtypes = [vp, C.c_int, C.c_int]
         L.rvc_set_f0_snap.argtypes = [vp, u32, C.c_double]
         L.rvc_set_f0_snap_stream.argtypes = [vp, C.c_int, u32, C.c_double]
+    if hasattr(L, "rvc_set_protect") or not override:
+        L.rvc_set_protect.argtypes = [vp, C.c_double]
+        L.rvc_set_protect_stream.argtypes = [vp, C.c_int, C.c_double]
     if hasattr(L, "rvc_set_plan_autotune") or not override:
         L.rvc_set_plan_autotune.argtypes = [vp, C.c_int]
         L.rvc_plan_autotune_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]

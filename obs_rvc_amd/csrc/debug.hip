@@ -543,6 +543,7 @@ int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w
         std::vector<StreamState> hst(B);
         for (int b = 0; b < B; b++) {
             memset(&hst[b], 0, sizeof(StreamState));
+            hst[b].protect = (float)PROTECT_OFF;       // (a zero word would mean full protection, state.hip.h; none of these ops reads it)
             hst[b].uppower = state[b].uppower; hst[b].stream_id = state[b].stream_id; hst[b].chunk = state[b].chunk; hst[b].status = state[b].status;
             memcpy(hst[b].cache_pitchf, state[b].cache_pitchf, sizeof hst[b].cache_pitchf);
         }
@@ -561,6 +562,38 @@ int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w
         for (int j = 0; j < 4; j++) g[j].download(buf[j]);
         HIPCHK(hipMemcpy(hst.data(), d_st, sizeof(StreamState) * B, hipMemcpyDeviceToHost));
         for (int b = 0; b < B; b++) { state[b].status = hst[b].status; memcpy(state[b].cache_pitchf, hst[b].cache_pitchf, sizeof hst[b].cache_pitchf); }
+        return RVC_OK;
+    });
+}
+
+// test aid: protect_mix_kernel alone (protect.hip.h; tests/test_gpu_protect.py) on the caller's arrays with the caller's leading dimensions, launched as the plan
+// launches it.  The streams' states are a block of the aid's own: zero but for the protect word.
+int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *phone, const float *cv, const float *pitchf, const double *protect)
+{
+    return (int)guarded(e, [&]() {
+        if (!s || !phone || !cv || !pitchf || !protect) throw ShapeError("protect spec");
+        const int B = s->streams, C = s->C, R = s->R, T = s->T;
+        if (B < 1 || B > 4096 || C < 1 || C > 4096 || R < 1 || R > 4096 || T < 1 || T > (1 << 20) || s->skip_head < 0 || s->ph_ld < R || s->cv_ld < T || s->ph_ld > (1 << 20) ||
+            s->cv_ld > (1 << 21) || (long long)s->skip_head + R > 2LL * T + 1)
+            throw ShapeError("protect spec");
+        for (int b = 0; b < B; b++) if (!(protect[b] >= 0.0 && protect[b] <= PROTECT_OFF)) throw ShapeError("protect: value outside [0, 0.5]");
+        Plan pl; pl.B = B;
+        Arena &A = pl.arena;
+        const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_pf = (size_t)B * R;
+        float *d_ph = A.floats(n_ph), *d_cv = A.floats(n_cv), *d_pf = A.floats(n_pf);
+        std::vector<StreamState> hst(B);
+        for (int b = 0; b < B; b++) { memset(&hst[b], 0, sizeof(StreamState)); hst[b].protect = (float)protect[b]; }
+        const StreamState *d_st = A.upload(hst);
+        HIPCHK(hipMemcpy(d_ph, phone, n_ph * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_cv, cv, n_cv * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_pf, pitchf, n_pf * 4, hipMemcpyHostToDevice));
+        const int ph_ld = s->ph_ld, cv_ld = s->cv_ld, skip_head = s->skip_head;
+        const dim3 grid = protect_grid(R, B, C);
+        pl.ops.push_back([=](hipStream_t st) {
+            hipLaunchKernelGGL(protect_mix_kernel, grid, dim3(PROTECT_ROWS, PROTECT_LANES), 0, st, d_st, d_pf, d_cv, cv_ld, (long long)C * cv_ld, C, T, skip_head, R, d_ph, ph_ld, (long long)C * ph_ld);
+        });
+        run_ops(e, pl, 1, s->graph != 0);
+        HIPCHK(hipMemcpy(phone, d_ph, n_ph * 4, hipMemcpyDeviceToHost));
         return RVC_OK;
     });
 }

@@ -180,6 +180,7 @@ static void alloc_state(rvc_engine *e)
     HIPCHK(hipMalloc(&e->d_state, sizeof(StreamState) * e->n_streams));
     e->formant.resize(e->n_streams, e->formant_default);     // existing streams keep their formant shift, new ones get the default
     e->pitch_ctl.resize(e->n_streams, e->pitch_ctl_default); // the same for the pitch controls
+    e->protect.resize(e->n_streams, e->protect_default);     // and for consonant protection
     reset_state(e);
     e->plans.clear();
     e->last_plan = nullptr;
@@ -200,7 +201,7 @@ static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, 
 }
 
 static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32_t skip_head, uint32_t R, int slot = 0, int bucket_B = 0,
-                      uint32_t R2 = 0, bool fstage = false)
+                      uint32_t R2 = 0, bool fstage = false, const std::vector<int> *bucket_ids = nullptr)
 {
     // fstage: the plan carries the formant stage, the decoder runs on R2 frames (formant.hip.h); without it the key is today's (R2 = R)
     if (!fstage) R2 = R;
@@ -213,6 +214,13 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     } swap_guard(e, bucket_B, e->d_state_bucket);
     const int B = e->n_streams;
     const bool with_index = mode == 0 && e->d_index && e->index_rate > 0.f;
+    // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams (bucket_ids: the
+    // streams of a bucket plan; else every stream) has it on.  Which value a stream has is no part of the key: the kernel reads it every chunk
+    bool with_protect = false;
+    if (with_index) {
+        if (bucket_ids) { for (int s : *bucket_ids) with_protect = with_protect || e->protect[s] < PROTECT_OFF; }
+        else for (double v : e->protect) with_protect = with_protect || v < PROTECT_OFF;
+    }
     // plans built before a test hook changed are stale (the hooks are process-global and not part of the key)
     const unsigned gen = g_opt_gen.load();
     for (size_t i = 0; i < e->plans.size();)
@@ -223,7 +231,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         } else i++;
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
-            p->with_index == with_index && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
+            p->with_index == with_index && p->with_protect == with_protect && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
             p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
@@ -235,7 +243,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     std::unique_ptr<Plan> up(new Plan());
     Plan &pl = *up;
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
-    pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
+    pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_protect = with_protect; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
     pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
@@ -314,6 +322,30 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         }
         if (cv_sid) pl.ops.join(cv_sid);
         pl.ops.join(f0_sid);
+        // consonant protection: `phone` is final (the retrieval has blended into it) and the pitch tail has written this call's pitchf rows; nothing of the
+        // synthesizer is queued yet.  Behind op_ret_end, so recover_retrieval replays it with the rest of the chunk (on the re-gathered, re-blended phone)
+        if (with_protect) {
+            T1 cvo = pl.cv_out; const StreamState *stp = e->d_state; const float *pf = d_pitchf0;
+            const dim3 grid = protect_grid((int)R, B, C);
+            if (pl.with_taps && phone.bs == (long long)C * phone.ld && cvo.bs == (long long)C * cvo.ld) {       // (streams back to back, as make_t1 lays them out)
+                // what the stage reads, every stream of the plan (phone_ct and cv.out are stream 0's): the blended rows [B][C][R] and the ContentVec output [B][C][T]
+                T1 blend = phone; blend.B = 1; blend.C = B * C;
+                add_tap(pl, "phone_blend", blend);
+                T1 cva = cvo; cva.B = 1; cva.C = B * C;
+                add_tap(pl, "cv.out_all", cva);
+            }
+            pl.ops.push_back([=](hipStream_t s) {
+                hipLaunchKernelGGL(protect_mix_kernel, grid, dim3(PROTECT_ROWS, PROTECT_LANES), 0, s, stp, pf, cvo.p, cvo.ld, cvo.bs, C, T, (int)skip_head, (int)R, phone.p, phone.ld, phone.bs);
+            });
+            // tap of every stream of the plan, stream-major [B][C][R] (the streams of a plan tensor lie back to back)
+            T1 all = phone; all.B = 1; all.C = B * C;
+            if (pl.with_taps) add_tap(pl, "phone_prot", all);
+        }
+        if (pl.with_taps) {
+            // the call's pitchf rows as the synthesizer gets them, every stream of the plan: [B][R]
+            T1 pft; pft.p = d_pitchf0; pft.B = 1; pft.C = B; pft.T = (int)R; pft.ld = (int)R; pft.halo = 0; pft.bs = (long long)B * R;
+            add_tap(pl, "pitchf", pft);
+        }
         // the NSF harmonic source is first needed by the decoder: it runs on a side stream next to the text encoder and the flow
         pl.ops.fork(2); pl.ops.cur = 2;
         src0 = build_nsf_source(e, pl, B, d_pitchf0);
@@ -391,6 +423,7 @@ static void run_plan(rvc_engine *e, Plan &pl)
 // ------------------------------- formant shift ----------------------------------------
 static_assert(offsetof(StreamState, f_ident) + sizeof(int) - offsetof(StreamState, f_tab) == sizeof(FormantDesc), "StreamState formant fields != FormantDesc");
 static_assert(offsetof(StreamState, c_strength) + sizeof(float) - offsetof(StreamState, c_on) == sizeof(F0Cond), "StreamState pitch-control fields != F0Cond");
+static_assert(offsetof(StreamState, protect) == offsetof(StreamState, c_strength) + sizeof(float), "StreamState::protect sits behind the pitch-control words");
 static_assert(sizeof(StreamState) % 4 == 0, "state_gather_kernel copies StreamState in 32-bit words");
 
 // the device form of the filter table o -> n, built once per engine (the descriptors of a captured graph's streams point at it)
@@ -467,6 +500,7 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
     std::vector<float> up(B);
     std::vector<FormantDesc> fd((size_t)B, FormantDesc{});
     std::vector<F0Cond> fc((size_t)B);
+    std::vector<float> pr((size_t)B);
     if (!Rs && (int)e->pushed_fd.size() == B) fd = e->pushed_fd;
     for (int b = 0; b < B; b++) {
         up[b] = uppower(shifts ? shifts[b] : pitch_shift);
@@ -477,13 +511,14 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
         const rvc_engine::PitchCtl &pc = e->pitch_ctl[b];
         if (pc.semitones != 0.0) up[b] *= (float)std::pow(2.0, pc.semitones / 12.0);
         fc[b] = f0cond_pack(pc.lo, pc.hi, pc.radius, pc.mask, pc.strength);
+        pr[b] = (float)e->protect[b];
     }
     // The device already holds these values (every write to them is ordered on the main stream, and the last one wrote exactly this):
     // nothing to copy -- a small H2D copy is a 4-5 us blit kernel in front of both branches of every chunk otherwise.
     bool same = e->pushed_valid && e->pushed_seed == e->seed && (int)e->pushed_up.size() == B && (int)e->pushed_fd.size() == B;
-    const bool fc_same = same && e->pushed_fc == fc;
+    const bool fc_same = same && e->pushed_fc == fc, pr_same = same && e->pushed_pr == pr;
     for (int b = 0; b < B && same; b++) same = e->pushed_up[b] == up[b] && e->pushed_fd[b] == fd[b];
-    if (same && fc_same) return;
+    if (same && fc_same && pr_same) return;
     if (e->pipeline) HIPCHK(hipDeviceSynchronize());   // the f0 branch of the next chunk may already be running: drain before the values change
     // every call writes its own pinned block: an unsynchronised call's copy may still be pending when the next call arrives
     if (!e->pushed_valid || e->pushed_seed != e->seed) {
@@ -500,11 +535,13 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
     float *hu = e->h_up + (size_t)us * 4096;
     FormantDesc *hf = e->h_fd + (size_t)us * 4096;
     F0Cond *hc = e->h_fc + (size_t)us * 4096;
-    for (int b = 0; b < B; b++) { hu[b] = up[b]; hf[b] = fd[b]; hc[b] = fc[b]; }
-    e->pushed_up = up; e->pushed_fd = fd; e->pushed_fc = fc;
+    float *hp = e->h_pr + (size_t)us * 4096;
+    for (int b = 0; b < B; b++) { hu[b] = up[b]; hf[b] = fd[b]; hc[b] = fc[b]; hp[b] = pr[b]; }
+    e->pushed_up = up; e->pushed_fd = fd; e->pushed_fc = fc; e->pushed_pr = pr;
     HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, uppower), sizeof(StreamState), hu, sizeof(float), sizeof(float), (size_t)B, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, f_tab), sizeof(StreamState), hf, sizeof(FormantDesc), sizeof(FormantDesc), (size_t)B, hipMemcpyHostToDevice, e->stream));
     if (!fc_same) HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, c_on), sizeof(StreamState), hc, sizeof(F0Cond), sizeof(F0Cond), (size_t)B, hipMemcpyHostToDevice, e->stream));
+    if (!pr_same) HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, protect), sizeof(StreamState), hp, sizeof(float), sizeof(float), (size_t)B, hipMemcpyHostToDevice, e->stream));
     if (!e->ev_up[us]) HIPCHK(hipEventCreateWithFlags(&e->ev_up[us], hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->ev_up[us], e->stream)); e->ev_up_used[us] = true;
     e->pushed_seed = e->seed; e->pushed_valid = true;
@@ -652,6 +689,7 @@ rvc_status rvc_create(const char *data_path, int device, rvc_engine **out)
         HIPCHK(hipHostMalloc((void **)&e->h_up, (size_t)8 * 4096 * sizeof(float)));
         HIPCHK(hipHostMalloc((void **)&e->h_fd, (size_t)8 * 4096 * sizeof(FormantDesc)));
         HIPCHK(hipHostMalloc((void **)&e->h_fc, (size_t)8 * 4096 * sizeof(F0Cond)));
+        HIPCHK(hipHostMalloc((void **)&e->h_pr, (size_t)8 * 4096 * sizeof(float)));
         init_constants(e);
         alloc_state(e);
     } catch (const std::exception &x) {
@@ -687,6 +725,7 @@ void rvc_destroy(rvc_engine *e)
     if (e->h_up) (void)hipHostFree(e->h_up);
     if (e->h_fd) (void)hipHostFree(e->h_fd);
     if (e->h_fc) (void)hipHostFree(e->h_fc);
+    if (e->h_pr) (void)hipHostFree(e->h_pr);
     for (auto &kv : e->ftabs) { (void)hipFree(kv.second.tab); (void)hipFree(kv.second.kb); }
     for (int i = 0; i < 8; i++) if (e->ev_up[i]) (void)hipEventDestroy(e->ev_up[i]);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -834,7 +873,7 @@ static rvc_status infer_r2_buckets(rvc_engine *e, const void *input, bool input_
     for (auto &kv : by) {
         uint32_t r2 = 0; bool fstage = false;
         formant_key(e, return_length, &kv.second, &r2, &fstage);
-        Plan *pl = get_plan(e, 0, n, frame16k, skip_head, return_length, 0, (int)kv.second.size(), r2, fstage);
+        Plan *pl = get_plan(e, 0, n, frame16k, skip_head, return_length, 0, (int)kv.second.size(), r2, fstage, &kv.second);
         if (out_len) *out_len = pl->N;
         if (cap < pl->N) return RVC_SHAPE;
         work.push_back({pl, kv.second});
@@ -986,7 +1025,7 @@ rvc_status rvc_infer_batch_g(rvc_engine *e, const float *const *inputs, const si
         for (auto &kv : buckets) {
             uint32_t r2 = 0; bool fstage = false;
             formant_key(e, kv.first.rl, &kv.second, &r2, &fstage);
-            Plan *pl = get_plan(e, 0, kv.first.n, kv.first.f, kv.first.sh, kv.first.rl, 0, (int)kv.second.size(), r2, fstage);
+            Plan *pl = get_plan(e, 0, kv.first.n, kv.first.f, kv.first.sh, kv.first.rl, 0, (int)kv.second.size(), r2, fstage, &kv.second);
             for (int s : kv.second) { if (out_lens) out_lens[s] = pl->N; if (caps[s] < pl->N) return RVC_SHAPE; }
             work.push_back({pl, kv.second});
         }
@@ -1181,6 +1220,20 @@ rvc_status rvc_set_f0_median(rvc_engine *e, int radius) { return set_f0_median(e
 rvc_status rvc_set_f0_median_stream(rvc_engine *e, int stream, int radius) { return set_f0_median(e, &stream, radius); }
 rvc_status rvc_set_f0_snap(rvc_engine *e, uint32_t pitch_class_mask, double strength) { return set_f0_snap(e, nullptr, pitch_class_mask, strength); }
 rvc_status rvc_set_f0_snap_stream(rvc_engine *e, int stream, uint32_t pitch_class_mask, double strength) { return set_f0_snap(e, &stream, pitch_class_mask, strength); }
+
+// consonant protection (protect.hip.h; DESIGN.md "Consonant protection"): per stream, [0, 0.5], 0.5 = off; the semantics of the pitch controls
+static rvc_status set_protect(rvc_engine *e, const int *stream, double protect)
+{
+    return guarded(e, [&]() {
+        if (stream && (*stream < 0 || *stream >= e->n_streams)) throw ShapeError("protect: stream out of range");
+        if (!(protect >= 0.0 && protect <= PROTECT_OFF)) throw ShapeError("protect: value outside [0, 0.5]");
+        if (stream) e->protect[*stream] = protect;
+        else { e->protect_default = protect; for (auto &v : e->protect) v = protect; }
+        return RVC_OK;
+    });
+}
+rvc_status rvc_set_protect(rvc_engine *e, double protect) { return set_protect(e, nullptr, protect); }
+rvc_status rvc_set_protect_stream(rvc_engine *e, int stream, double protect) { return set_protect(e, &stream, protect); }
 
 rvc_status rvc_formant_geometry(size_t return_length, size_t sample_rate, double semitones, size_t out[2])
 {

@@ -239,6 +239,7 @@ struct Plan {
     int B = 1; size_t L = 0, frame16k = 0; uint32_t skip_head = 0, R = 0;
     int T = 0, Tm = 0, C = 0; size_t N = 0;
     bool with_index = false, with_taps = false;
+    bool with_protect = false;    // with_index and some stream of the plan had protect < 0.5 when it was built: the plan carries protect_mix_kernel (protect.hip.h)
     bool bucket = false;          // a plan of rvc_infer_batch_g: built for a subset of the streams on the gathered state block (rvc_engine::d_state_bucket)
     // gather tables by content (round 6): the 3x3 layers of one RMVPE level have identical k -> offset tables; with one device copy per distinct table the second
     // and later layers of a level find it in the L2 instead of fetching a cold 6 KB table from HBM in front of their first operand gather
@@ -932,6 +933,11 @@ struct rvc_engine {
     std::vector<PitchCtl> pitch_ctl; PitchCtl pitch_ctl_default;
     std::vector<rvc::F0Cond> pushed_fc;
     rvc::F0Cond *h_fc = nullptr;          // pinned ring of 8 blocks of 4096, as h_fd
+    // consonant protection (protect.hip.h; rvc_set_protect[_stream]): per stream and the default of new streams, [0, 0.5], 0.5 = off.  Whether ANY stream
+    // of a plan is below 0.5 is part of the plan's identity (with_protect); the values travel as StreamState::protect and are not
+    std::vector<double> protect; double protect_default = rvc::PROTECT_OFF;
+    std::vector<float> pushed_pr;
+    float *h_pr = nullptr;                // pinned ring of 8 blocks of 4096, as h_fd
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };

@@ -4,6 +4,7 @@
 #include "igemm.hip.h"
 #include "state.hip.h"
 #include "f0cond.hip.h"
+#include "protect.hip.h"
 
 namespace rvc {
 
@@ -1175,14 +1176,14 @@ static __global__ __launch_bounds__(1024) void pitch_post_kernel(PitchP p)
 // ------------------------------------------------------------------------------------
 // small glue kernels
 // ------------------------------------------------------------------------------------
-// phone[c][r] = feats[min((skip_head + r) / 2, T - 1)][c]   (rvc.rs:99-109 + 155; Q2, Q8)
+// phone[c][r] = feats[min((skip_head + r) / 2, T - 1)][c]   (rvc.rs:99-109 + 155; Q2, Q8; the column rule: protect.hip.h phone_src_col)
 static __global__ void gather_phone_kernel(const float *cv, int cv_cs, long long cv_bs, int C, int T, int skip_head, int R,
                                     float *phone, int ph_cs, long long ph_bs)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (i >= C * R) return;
     int c = i / R, r = i - c * R;
-    int s = (skip_head + r) / 2; s = s < T - 1 ? s : T - 1;
+    int s = phone_src_col(skip_head, r, T);
     phone[(long long)b * ph_bs + (long long)c * ph_cs + r] = cv[(long long)b * cv_bs + (long long)c * cv_cs + s];
 }
 

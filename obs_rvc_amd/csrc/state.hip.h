@@ -29,6 +29,9 @@ struct StreamState {        // one per stream
     uint32_t c_on;          // 0 = every control neutral (the tail skips the stage); bits 0-3 median radius, 4-15 pitch-class mask, 16 range gate
     float c_lo, c_hi;       // range gate in Hz
     float c_strength;       // scale snap strength, (0, 1]
+    // consonant protection of this stream (protect.hip.h protect_mix_kernel; written by the host like the pitch controls): the value itself, [0, 0.5],
+    // 0.5 = off.  A zero-filled state therefore means FULL protection: whoever builds a state by hand sets the word (debug.hip does)
+    float protect;
 };
 
 // status bits of a stream (several kernels of one chunk may report; a plain store would lose the earlier report)

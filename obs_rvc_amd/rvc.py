@@ -217,6 +217,15 @@ class RvcInfer:
         else:
             self._chk(self._L.rvc_set_f0_snap_stream(self._h, int(stream), mask, float(strength)))
 
+    def set_protect(self, value: float, stream: int = None):
+        """Consonant protection (upstream RVC's `protect`), 0..0.5, 0.5 = off: on calls that use the index, unvoiced rows (pitchf < 1) become
+        value * blended + (1 - value) * raw ContentVec features.  Every stream and the default of streams added later, or (stream given) one
+        stream (rvc_set_protect[_stream])."""
+        if stream is None:
+            self._chk(self._L.rvc_set_protect(self._h, float(value)))
+        else:
+            self._chk(self._L.rvc_set_protect_stream(self._h, int(stream), float(value)))
+
     @staticmethod
     def formant_geometry(return_length: int, sample_rate: int, semitones: float):
         """-> (R2, upp_res): the decoder's frame count and the resampler's input samples per frame of a formant shift

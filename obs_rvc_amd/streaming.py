@@ -103,7 +103,8 @@ class StreamingSession:
 class NativeStreamingSession:
     """The same state machine as one native call per chunk with every buffer resident in HBM (`rvc_session_*`,
     csrc/session.hip.h): one H2D copy, one D2H copy and one synchronisation per chunk.  The session honours the engine's per-stream
-    formant shift and pitch controls (engine.set_pitch_semitones / set_f0_range / set_f0_median / set_f0_snap)."""
+    formant shift, pitch controls (engine.set_pitch_semitones / set_f0_range / set_f0_median / set_f0_snap) and consonant protection
+    (engine.set_protect)."""
 
     def __init__(self, engine, sample_rate: int = 48000, sample_length: float = 0.30, crossfade_length: float = 0.07,
                  extra_inference_time: float = 2.0, model_output_sample_rate: int = 40000, pitch_shift: int = 12,
