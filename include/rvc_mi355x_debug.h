@@ -109,6 +109,25 @@ typedef struct rvc_debug_protect_spec {
     int streams, C, R, T, skip_head, ph_ld, cv_ld, graph;
 } rvc_debug_protect_spec;
 int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *phone, const float *cv, const float *pitchf, const double *protect);
+/* one ConvBlockRes of RMVPE (conv3x3 + ReLU, conv3x3 + ReLU, + 1x1 shortcut or the input) queued as build_rmvpe queues it (obs_rvc_amd/csrc/model_rmvpe.hip:
+ * make_res_block, add_rm_block_fused, add_res_block, add_avgpool2) and run `reps` times eagerly, or -- graph != 0 -- captured once and the graph replayed `reps`
+ * times.  Weights in PyTorch layout: w1 [cout][cin][3][3], w2 [cout][cout][3][3], wsc [cout][cin] or NULL (identity shortcut: cin = cout), biases [cout].
+ *   pool_in   x is [cin][2 H][2 W] and the block sees its AvgPool2d(2, 2): staged by the fused block itself when a dry run says so (hook RVC_RM_FUSE = 3: never),
+ *             else a pooling launch into a tensor of the aid's own in front of the block
+ *   pool_out  p [cout][H / 2][W / 2] = AvgPool2d(2, 2) of the result: a second output of the fused block when a dry run says so, else a pooling launch behind it
+ *   y_in_cat  y has 2 cout channels and the block writes channels [cout, 2 cout) (where an encoder level's last block writes)
+ *   next      1: the launch is given a second block's panels to warm (the fused kernel's extra workgroup)
+ *   rm_fuse   Plan::rm_fuse (build_rmvpe: the f0 branch has its own partition and there are at most four streams); hook RVC_RM_FUSE applies on top
+ * x / y / p are the WHOLE allocations, as for rvc_debug_layer (p may be NULL without pool_out); geo[3][8] receives their geometry (x, y, p) as there, zeros for
+ * an unused p.  With x == NULL only geo is filled.  0 = done, else an rvc_status (rvc_last_error_message); rvc_debug_last_kernel then names what ran: "rmb_1_3_2" /
+ * "rmb_2_2_1" (rm_block_kernel<MT, NT1, NT2>, + "+pool_in" / "+pool_out" for a pooling folded into it), "pair" (c1 + shortcut in one launch, then c2) or "plain". */
+typedef struct rvc_debug_rm_block_spec {
+    int streams, cin, cout, H, W;
+    int pool_in, pool_out, y_in_cat, next, rm_fuse;
+    int graph, reps;
+} rvc_debug_rm_block_spec;
+int rvc_debug_rm_block(rvc_engine *e, const rvc_debug_rm_block_spec *s, const float *w1, const float *b1, const float *w2, const float *b2, const float *wsc,
+                       const float *bsc, float *x, float *y, float *p, long long *geo);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);

@@ -59,12 +59,13 @@ void run_ops(rvc_engine *e, Plan &pl, int reps, bool graph)
 
 // the device weights of one aid, released on every exit (a throw included).  Declared behind the aid's Plan, so that they go before the plan does.
 struct DebugWeights {
-    std::deque<ConvW> convs; std::vector<float *> raw;
+    std::deque<ConvW> convs; std::deque<ResBlockW> blocks; std::vector<float *> raw;
     DebugWeights() = default;
     DebugWeights(const DebugWeights &) = delete;
     ConvW &conv(ConvW c) { convs.push_back(std::move(c)); return convs.back(); }
+    ResBlockW &block(ResBlockW b) { blocks.push_back(std::move(b)); return blocks.back(); }
     float *dev(float *p) { raw.push_back(p); return p; }
-    ~DebugWeights() { for (ConvW &c : convs) free_conv(c); for (float *p : raw) wfree(p); }
+    ~DebugWeights() { for (ConvW &c : convs) free_conv(c); for (ResBlockW &b : blocks) free_res_block(b); for (float *p : raw) wfree(p); }
 };
 
 // the deterministic data of the *_check / tuning aids
@@ -598,7 +599,50 @@ int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *pho
     });
 }
 
-// the kernel family of the most recently queued implicit-GEMM launch (the first word of its description): tests assert which path they exercised
+// test aid: one ConvBlockRes of RMVPE as build_rmvpe queues it -- rm_block_kernel when the block is eligible, else the implicit-GEMM launches, with the poolings
+// folded into the block or queued as launches of their own by the model's own dry runs (include/rvc_mi355x_debug.h, tests/test_gpu_rmblock.py).  As for
+// rvc_debug_layer, the caller owns every float of the tensors' allocations.
+int rvc_debug_rm_block(rvc_engine *e, const rvc_debug_rm_block_spec *s, const float *w1, const float *b1, const float *w2, const float *b2, const float *wsc,
+                       const float *bsc, float *x, float *y, float *p, long long *geo)
+{
+    return (int)guarded(e, [&]() {
+        if (!s || !geo || s->streams < 1 || s->streams > 64 || s->cin < 1 || s->cin > 1024 || s->cout < 1 || s->cout > 1024 || s->H < 1 || s->H > 1024 || s->W < 1 ||
+            s->W > 1024 || s->reps < 1 || (s->pool_out && (s->H < 2 || s->W < 2)))
+            throw ShapeError("rm block spec");
+        const int B = s->streams, ci = s->cin, co = s->cout, H = s->H, W = s->W;
+        Plan pl; pl.B = B; pl.rm_fuse = s->rm_fuse != 0;
+        DebugWeights wts;
+        Arena &A = pl.arena;
+        const T2 src = s->pool_in ? make_t2(A, B, ci, 2 * H, 2 * W) : make_t2(A, B, ci, H, W);
+        const T2 ybuf = make_t2(A, B, s->y_in_cat ? 2 * co : co, H, W), out = s->y_in_cat ? ybuf.chans(co, co) : ybuf;
+        T2 pooled;
+        if (s->pool_out) pooled = make_t2(A, B, co, H / 2, W / 2);
+        const DebugGeo gx = debug_geo2(src), gy = debug_geo2(ybuf), gp = s->pool_out ? debug_geo2(pooled) : DebugGeo();
+        for (int i = 0; i < 8; i++) { geo[i] = gx.g[i]; geo[8 + i] = gy.g[i]; geo[16 + i] = gp.base ? gp.g[i] : 0; }
+        if (!x) return RVC_OK;
+        if (!y || !w1 || !b1 || !w2 || !b2 || (s->pool_out && !p) || (wsc && !bsc) || (!wsc && ci != co)) throw ShapeError("rm block buffers");
+        const ResBlockW &w = wts.block(make_res_block(w1, b1, w2, b2, wsc, bsc, ci, co));
+        const ResBlockW *next = s->next ? &wts.block(make_res_block(w1, b1, w2, b2, wsc, bsc, ci, co)) : nullptr;
+        // the poolings, decided as build_rmvpe decides them: a dry run of the fused block with the pooled input / the pooled second output
+        const int hook = test_opt_int("RVC_RM_FUSE", 1);
+        T2 xin = src; const T2 *pool_src = nullptr;
+        if (s->pool_in) {
+            xin = make_t2(A, B, ci, H, W);          // (the block pools while it stages: only the geometry of this tensor is used)
+            if (hook != 3 && add_rm_block_fused(pl, w, xin, out, nullptr, &src, true)) pool_src = &src;
+            else add_avgpool2(pl, src, xin);
+        }
+        const bool by_block = s->pool_out && hook != 3 && add_rm_block_fused(pl, w, xin, out, nullptr, pool_src, true, &pooled);
+        add_res_block(pl, w, xin, out, next, pool_src, by_block ? &pooled : nullptr);
+        if (s->pool_out && !by_block) add_avgpool2(pl, out, pooled);
+        gx.upload(x); gy.upload(y); gp.upload(p);
+        run_ops(e, pl, s->reps, s->graph != 0);
+        gx.download(x); gy.download(y); gp.download(p);
+        return RVC_OK;
+    });
+}
+
+// the kernel family of the most recently queued implicit-GEMM launch (the first word of its description), the variant of the last op or the form of the
+// last ConvBlockRes: tests assert which path they exercised
 const char *rvc_debug_last_kernel(void)
 {
     static thread_local std::string buf;

@@ -454,6 +454,38 @@ static inline std::vector<float> rm_block_panel(const float *w, int co, int ci, 
                 }
     return pk;
 }
+// one ConvBlockRes from weights in PyTorch layout: w1 [co][ci][3][3], w2 [co][co][3][3], wsc [co][ci] (nullptr: identity shortcut), biases [co] (BatchNorm
+// folded): the prepared convolutions, the pair bias of the c1 + shortcut launch and -- 16 / 32 output channels, at most 64 input channels -- rm_block_kernel's
+// panels.  ModelRM builds its blocks with it, and so does rvc_debug_rm_block (debug.hip)
+static inline ResBlockW make_res_block(const float *w1, const float *b1, const float *w2, const float *b2, const float *wsc, const float *bsc, int ci, int co)
+{
+    ResBlockW r; r.ci = ci; r.co = co;
+    r.c1 = prep_conv(w1, b1, co, ci, 9, 1);
+    r.c2 = prep_conv(w2, b2, co, co, 9, 1);
+    if (wsc) {
+        r.has_sc = true; r.sc = prep_conv(wsc, bsc, co, ci, 1, 1);
+        std::vector<float> pb(b1, b1 + co);
+        pb.insert(pb.end(), bsc, bsc + co);
+        r.pair_bias = upload_f(pb);
+    }
+    if ((co == 16 || co == 32) && ci <= 64) {
+        std::vector<float> all = rm_block_panel(w1, co, ci, 9);
+        const size_t o2 = all.size();
+        { std::vector<float> t = rm_block_panel(w2, co, co, 9); all.insert(all.end(), t.begin(), t.end()); }
+        const size_t o3 = all.size();
+        if (r.has_sc) { std::vector<float> t = rm_block_panel(wsc, co, ci, 1); all.insert(all.end(), t.begin(), t.end()); }
+        all.resize((all.size() + 31) / 32 * 32, 0.f);
+        r.f_w1 = upload_f(all); r.f_w2 = r.f_w1 + o2; r.f_sc = r.has_sc ? r.f_w1 + o3 : nullptr; r.f_lines = (int)(all.size() / 32);
+    }
+    return r;
+}
+static inline void free_res_block(ResBlockW &r)
+{
+    free_conv(r.c1); free_conv(r.c2); free_conv(r.sc);
+    if (r.pair_bias) wfree(r.pair_bias);
+    if (r.f_w1) wfree(r.f_w1);
+    r.pair_bias = nullptr; r.f_w1 = r.f_w2 = r.f_sc = nullptr; r.f_lines = 0;
+}
 // the recurrent weights of a bidirectional GRU (PyTorch weight_hh_l0 / _reverse, [3H][H] each, gates r, z, n) in the two layouts of the kernels:
 // whhT [2][H][3H] (gru_kernel: lanes read consecutive rows) and whh [2][3H][H] row-major (gru_multi_kernel)
 static inline void gru_prep_whh(const float *const whh_dir[2], int H, std::vector<float> &whhT, std::vector<float> &whh)
@@ -476,25 +508,8 @@ struct ModelRM {
     size_t weight_bytes = 0;
     static ResBlockW block(const Blob &b, const std::string &pre, int ci, int co)
     {
-        ResBlockW r; r.ci = ci; r.co = co;
-        r.c1 = prep_conv(b.w(pre + "c1.w"), b.w(pre + "c1.b"), co, ci, 9, 1);
-        r.c2 = prep_conv(b.w(pre + "c2.w"), b.w(pre + "c2.b"), co, co, 9, 1);
-        if (ci != co) {
-            r.has_sc = true; r.sc = prep_conv(b.w(pre + "sc.w"), b.w(pre + "sc.b"), co, ci, 1, 1);
-            std::vector<float> pb(b.w(pre + "c1.b"), b.w(pre + "c1.b") + co);
-            pb.insert(pb.end(), b.w(pre + "sc.b"), b.w(pre + "sc.b") + co);
-            r.pair_bias = upload_f(pb);
-        }
-        if ((co == 16 || co == 32) && ci <= 64) {
-            std::vector<float> all = rm_block_panel(b.w(pre + "c1.w"), co, ci, 9);
-            const size_t o2 = all.size();
-            { std::vector<float> t = rm_block_panel(b.w(pre + "c2.w"), co, co, 9); all.insert(all.end(), t.begin(), t.end()); }
-            const size_t o3 = all.size();
-            if (r.has_sc) { std::vector<float> t = rm_block_panel(b.w(pre + "sc.w"), co, ci, 1); all.insert(all.end(), t.begin(), t.end()); }
-            all.resize((all.size() + 31) / 32 * 32, 0.f);
-            r.f_w1 = upload_f(all); r.f_w2 = r.f_w1 + o2; r.f_sc = r.has_sc ? r.f_w1 + o3 : nullptr; r.f_lines = (int)(all.size() / 32);
-        }
-        return r;
+        const bool sc = ci != co;
+        return make_res_block(b.w(pre + "c1.w"), b.w(pre + "c1.b"), b.w(pre + "c2.w"), b.w(pre + "c2.b"), sc ? b.w(pre + "sc.w") : nullptr, sc ? b.w(pre + "sc.b") : nullptr, ci, co);
     }
     explicit ModelRM(const Blob &b)
     {
@@ -544,7 +559,7 @@ struct ModelRM {
     }
     ~ModelRM()
     {
-        auto fb = [](std::vector<std::vector<ResBlockW>> &vv) { for (auto &v : vv) for (auto &r : v) { free_conv(r.c1); free_conv(r.c2); free_conv(r.sc); if (r.pair_bias) wfree(r.pair_bias); if (r.f_w1) wfree(r.f_w1); } };
+        auto fb = [](std::vector<std::vector<ResBlockW>> &vv) { for (auto &v : vv) for (auto &r : v) free_res_block(r); };
         fb(enc); fb(inter); fb(dec);
         for (auto &u : up) free_conv(u);
         free_conv(cnn); free_conv(gru_ih); free_conv(fc);
@@ -966,6 +981,12 @@ void add_conv0_front(Plan &pl, const ConvW &cw, const float *w_raw, const float 
 void add_mel_frontend(rvc_engine *e, Plan &pl, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, float *mel, const T2 &img, float bn_scale, float bn_shift);
 void add_pitch_post(Plan &pl, int B, const T1 &sal, int Tm, StreamState *st, const CallParams *cp, float *f0, bool update, long long shift, long long cache_start,
                     long long read_start, int R, float *pitchf, int *pitch, const float *f0_in = nullptr);
+// one ConvBlockRes of RMVPE as build_rmvpe queues it (model_rmvpe.hip; rvc_debug_rm_block calls the same three).  add_rm_block_fused: the block as ONE launch of
+// rm_block_kernel when it is eligible (false = not taken; dry: eligibility only, nothing queued); add_res_block: that launch, or c1 + shortcut in one launch and c2
+// ("pair"), or one launch per convolution ("plain"); add_avgpool2: AvgPool2d(2, 2) of x into p as a launch of its own
+bool add_rm_block_fused(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, const ResBlockW *next, const T2 *pool_src = nullptr, bool dry = false, const T2 *pool_dst = nullptr);
+T2 add_res_block(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, const ResBlockW *next = nullptr, const T2 *pool_src = nullptr, const T2 *pool_dst = nullptr);
+void add_avgpool2(Plan &pl, const T2 &x, const T2 &p);
 void add_nsf_source(Plan &pl, int B, const float *pitchf, const T1 &src, int R, int upp, float sr, float lin_w, float lin_b, const StreamState *st, const CallParams *cp,
                     int f0_num, int f0_den);
 std::vector<T1> build_noise_convs(rvc_engine *e, Plan &pl, int B, const T1 &src);

@@ -6,10 +6,11 @@ namespace rvc {
 
 // One launch per ConvBlockRes on the shallow levels (rm_block_kernel, rmblock.hip.h): few streams only -- there the f0 branch is a chain of dependent
 // 5-8 us launches on its own CU partition and the block's halo recomputation costs nothing that matters; with many streams folded into a launch the two
-// convolutions fill the chip by themselves and keep the implicit-GEMM kernels.  Test hook RVC_RM_FUSE = 0: never, 2: at any stream count.  false = not taken.
+// convolutions fill the chip by themselves and keep the implicit-GEMM kernels.  Test hook RVC_RM_FUSE = 0: never, 2: at any stream count, 3: by the rule, but
+// build_rmvpe folds no pooling into a block (neither the AvgPool2d in front of a level's first block nor the pooled second output of its last).  false = not taken.
 // pool_src != nullptr: the block's input is AvgPool2d(2, 2) of that tensor, averaged while the tile is staged (the pooling launch in front of the block disappears);
-// dry: eligibility only, nothing queued
-static bool add_rm_block_fused(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, const ResBlockW *next, const T2 *pool_src = nullptr, bool dry = false, const T2 *pool_dst = nullptr)
+// dry: eligibility only, nothing queued.  A queued block is recorded (rvc_debug_last_kernel: "rmb_<MT>_<NT1>_<NT2>", "+pool_in" / "+pool_out" for the folded poolings)
+bool add_rm_block_fused(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, const ResBlockW *next, const T2 *pool_src, bool dry, const T2 *pool_dst)
 {
     const int mode = test_opt_int("RVC_RM_FUSE", 1);
     if (!w.f_w1 || mode == 0 || (!pl.rm_fuse && mode != 2)) return false;
@@ -50,6 +51,7 @@ static bool add_rm_block_fused(Plan &pl, const ResBlockW &w, const T2 &x, const 
     Plan *plp = &pl;
     { char d[176]; snprintf(d, sizeof d, "rmb M=%d N=%d K=%d B=%d nph=1 tile=%dx%d grid=%ux%u lds=%zu sc=%d", w.co, x.H * x.W, 9 * w.ci + 9 * w.co + (w.has_sc ? w.ci : 0), x.B, q.TH, q.TW, grid.x, grid.y, lds, (int)w.has_sc); pl.descs.push_back(d); }
     const int desc_id = (int)pl.descs.size() - 1;
+    snprintf(g_last_kernel, sizeof g_last_kernel, "rmb_%d_%d_%d%s%s", MT, NT1, NT2, q.pool ? "+pool_in" : "", q.ypool ? "+pool_out" : "");
     pl.ops.push_back([=](hipStream_t s) {
         const ProfEvent *pe = plp->prof_slot(flops, 0, desc_id);
         hipEvent_t ea = pe ? pe->a : nullptr, eb = pe ? pe->b : nullptr;
@@ -109,7 +111,8 @@ static void add_conv2d_with_shortcut(Plan &pl, const ResBlockW &w, const T2 &x, 
     queue_igemm(pl, p, x.B, koff, ph);
 }
 
-static T2 res_block(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, const ResBlockW *next = nullptr, const T2 *pool_src = nullptr, const T2 *pool_dst = nullptr)
+// the unfused forms are recorded as "pair" / "plain" (rvc_debug_last_kernel)
+T2 add_res_block(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, const ResBlockW *next, const T2 *pool_src, const T2 *pool_dst)
 {
     Arena &A = pl.arena;
     if (add_rm_block_fused(pl, w, x, out, (next && next->f_w1) ? next : nullptr, pool_src, false, pool_dst)) return out;
@@ -120,6 +123,7 @@ static T2 res_block(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, co
     if (w.has_sc && w.pair_bias && x.B <= 4 && (x.B == 1 || y1.bs == out.bs) && !tune_env("RVC_NO_SC_MERGE")) {      // (one stream stride for both outputs)
         add_conv2d_with_shortcut(pl, w, x, y1, out);
         ConvOpts o; o.act = ACT_RELU; o.accumulate = true; add_conv2d(pl, w.c2, y1, out, o);
+        snprintf(g_last_kernel, sizeof g_last_kernel, "pair");
         return out;
     }
     { ConvOpts o; o.act = ACT_RELU; add_conv2d(pl, w.c1, x, y1, o); }
@@ -129,7 +133,18 @@ static T2 res_block(Plan &pl, const ResBlockW &w, const T2 &x, const T2 &out, co
     } else {
         ConvOpts o; o.act = ACT_RELU; o.res = x.p; o.res_cs = x.cs; o.res_bs = x.bs; o.res_rs = x.ld; add_conv2d(pl, w.c2, y1, out, o);
     }
+    snprintf(g_last_kernel, sizeof g_last_kernel, "plain");
     return out;
+}
+
+// AvgPool2d(2, 2) of x [B][C][H][W] into p [B][C][H / 2][W / 2] as a launch of its own
+void add_avgpool2(Plan &pl, const T2 &x, const T2 &p)
+{
+    const int co = p.C;
+    dim3 grid((co * p.H * p.W + 255) / 256, x.B);
+    pl.ops.push_back([=](hipStream_t s) {
+        hipLaunchKernelGGL(avgpool2_kernel, grid, dim3(256), 0, s, x.p, x.ld, x.cs, x.bs, p.p, p.ld, p.cs, p.bs, co, p.H, p.W);
+    });
 }
 
 // RMVPE's front end on the last `frame` of the n samples of each stream (audio [B][audio_bs]): the raw log-mel into mel [B][128][Tm] and, with the network's
@@ -189,31 +204,25 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
             const bool last = j == m.n_blocks - 1;
             const T2 xin = x;
             pooled_by_block = last && !next_takes_pool && test_opt_int("RVC_RM_FUSE", 1) != 3 && add_rm_block_fused(pl, m.enc[lv][j], xin, out, nullptr, (j == 0 && pooled_in_block) ? &pool_from : nullptr, true, &p);
-            x = res_block(pl, m.enc[lv][j], xin, out, j + 1 < m.n_blocks ? &m.enc[lv][j + 1] : (lv + 1 < m.levels ? &m.enc[lv + 1][0] : nullptr), (j == 0 && pooled_in_block) ? &pool_from : nullptr,
+            x = add_res_block(pl, m.enc[lv][j], xin, out, j + 1 < m.n_blocks ? &m.enc[lv][j + 1] : (lv + 1 < m.levels ? &m.enc[lv + 1][0] : nullptr), (j == 0 && pooled_in_block) ? &pool_from : nullptr,
                           pooled_by_block ? &p : nullptr);
         }
         if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "rm.enc%d", lv); add_tap2(pl, nm, x); }
         // the next level's first block stages AvgPool2d(2, 2) of this level's output itself when it is a fused block (one more launch off the f0 branch)
         pooled_in_block = next_takes_pool;
         if (pooled_in_block) pool_from = x;
-        else if (!pooled_by_block) {
-            T2 xi = x;
-            dim3 grid((co * (H / 2) * (W / 2) + 255) / 256, B);
-            pl.ops.push_back([=](hipStream_t s) {
-                hipLaunchKernelGGL(avgpool2_kernel, grid, dim3(256), 0, s, xi.p, xi.ld, xi.cs, xi.bs, p.p, p.ld, p.cs, p.bs, co, p.H, p.W);
-            });
-        }
+        else if (!pooled_by_block) add_avgpool2(pl, x, p);
         x = p; H /= 2; W /= 2;
     }
     for (int lv = 0; lv < m.inter_layers; lv++)
-        for (int j = 0; j < m.n_blocks; j++) { T2 out = make_t2(A, B, m.inter[lv][j].co, H, W); x = res_block(pl, m.inter[lv][j], x, out); }
+        for (int j = 0; j < m.n_blocks; j++) { T2 out = make_t2(A, B, m.inter[lv][j].co, H, W); x = add_res_block(pl, m.inter[lv][j], x, out); }
     add_tap2(pl, "rm.int", x);
     for (int lv = 0; lv < m.levels; lv++) {
         const int sl = m.levels - 1 - lv, co = m.up[lv].Cout;
         H *= 2; W *= 2;
         { ConvOpts o; o.act = ACT_RELU; add_convT2d(pl, m.up[lv], x, cat[sl].chans(0, co), o); }
         x = cat[sl];
-        for (int j = 0; j < m.n_blocks; j++) { T2 out = make_t2(A, B, co, H, W); x = res_block(pl, m.dec[lv][j], x, out, j + 1 < m.n_blocks ? &m.dec[lv][j + 1] : (lv + 1 < m.levels ? &m.dec[lv + 1][0] : nullptr)); }
+        for (int j = 0; j < m.n_blocks; j++) { T2 out = make_t2(A, B, co, H, W); x = add_res_block(pl, m.dec[lv][j], x, out, j + 1 < m.n_blocks ? &m.dec[lv][j + 1] : (lv + 1 < m.levels ? &m.dec[lv + 1][0] : nullptr)); }
         if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "rm.dec%d", lv); add_tap2(pl, nm, x); }
     }
     const int Hg = m.gru_hidden, I = 3 * m.n_mels;

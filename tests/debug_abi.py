@@ -33,6 +33,11 @@ class FrontSpec(C.Structure):
         [("sr", C.c_float), ("lin_w", C.c_float), ("lin_b", C.c_float), ("seed", C.c_uint)]
 
 
+class RmBlockSpec(C.Structure):
+    """rvc_debug_rm_block_spec"""
+    _fields_ = _ints("streams", "cin", "cout", "H", "W", "pool_in", "pool_out", "y_in_cat", "next", "rm_fuse", "graph", "reps")
+
+
 class StreamState(C.Structure):
     """rvc_debug_stream_state (cache = cache_pitchf)"""
     _fields_ = [("uppower", C.c_float), ("stream_id", C.c_uint), ("chunk", C.c_uint), ("status", C.c_int), ("cache", C.c_float * 1024)]
@@ -45,6 +50,7 @@ def lib():
     L.rvc_debug_layer.argtypes = [vp, C.POINTER(LayerSpec)] + [vp] * 5 + [geo]
     L.rvc_debug_op.argtypes = [vp, C.POINTER(OpSpec)] + [vp] * 5 + [geo]
     L.rvc_debug_front.argtypes = [vp, C.POINTER(FrontSpec), vp, vp, C.POINTER(vp), C.POINTER(StreamState), geo]
+    L.rvc_debug_rm_block.argtypes = [vp, C.POINTER(RmBlockSpec)] + [vp] * 9 + [geo]
     L.rvc_debug_conv_check.argtypes = L.rvc_debug_conv2d_check.argtypes = [vp] + [C.c_int] * 7
     L.rvc_debug_conv_check.restype = L.rvc_debug_conv2d_check.restype = C.c_double
     L.rvc_debug_last_kernel.restype = C.c_char_p
