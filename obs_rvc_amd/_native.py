@@ -35,24 +35,34 @@ SYMBOLS = [
 ]
 
 
-SOURCES = ("engine.hip", "engine_int.h", "debug.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "yin.hip.h", "model_synth.hip", "retrieval.hip", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "igemm2_inst.hip", "igemm_tiled_inst.hip", "igemm2w_inst.hip", "igemm_bf3_inst.hip", "conv_tile.hip.h", "conv_tile_inst.hip", "conv32s.hip.h", "conv32s_inst.hip", "rmblock.hip.h", "igemm32l.hip.h", "igemm32l_inst.hip", "version.cpp", "calib.hip", "exports.map",
-           "state.hip.h", "formant.hip.h", "f0cond.hip.h", "protect.hip.h", "crossfade.hip.h",
-           "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h", "blob.h", "rvc_rpc.cpp")
+def _include_closure(src):
+    """every file `src` (relative to csrc) reaches through #include "..." lines, itself included, each resolved against the including file.  A plain scan:
+    an include under a preprocessor conditional counts too (a superset is safe for a cache key).  -> sorted tuple of paths relative to csrc"""
+    import re
+    seen, todo = set(), [os.path.normpath(src)]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.add(f)
+        with open(os.path.join(CSRC, f)) as fh:
+            todo += [os.path.normpath(os.path.join(os.path.dirname(f), i)) for i in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', fh.read(), re.M)]
+    return tuple(sorted(seen))
 
-# translation units of the library: (source, extra flags, files whose contents decide whether the object is stale).  The implicit-GEMM
-# template instantiations are the bulk of the compile time; as separate units they build in parallel (5 min -> about 1.5 min on 8 cores)
+
+# translation units of the library: (source, extra flags, files whose contents decide whether the object is stale = the source's include closure).  The
+# implicit-GEMM template instantiations are the bulk of the compile time; as separate units they build in parallel (5 min -> about 1.5 min on 8 cores)
 # and are not rebuilt when only the engine changes.
-_IGEMM_DEPS = ("igemm.hip.h", "igemm_launch.h")
-_INT_DEPS = ("engine_int.h", "kernels.hip.h", "igemm.hip.h", "igemm_launch.h", "blob.h", "state.hip.h", "formant.hip.h", "f0cond.hip.h", "protect.hip.h")
-_ENGINE_DEPS = ("engine.hip", "resample.hip.h", "session.hip.h", "rccl_bcast.hip.h", "crossfade.hip.h") + _INT_DEPS
-UNITS = [("engine.hip", [], _ENGINE_DEPS), ("debug.hip", [], ("debug.hip", "../../include/rvc_mi355x_debug.h") + _INT_DEPS), ("calib.hip", [], ("calib.hip",))] + [(u, [], (u,) + _INT_DEPS + (("rmblock.hip.h",) if u == "model_rmvpe.hip" else ()) + (("yin.hip.h",) if u == "model_yin.hip" else ())) for u in ("plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "model_synth.hip", "retrieval.hip")] + \
-        [("igemm2_inst.hip", ["-DRVC_IGEMM2_CFG=%d" % c], ("igemm2_inst.hip",) + _IGEMM_DEPS) for c in range(5)] + \
-        [("igemm_tiled_inst.hip", ["-DRVC_TILED_PART=%d" % c], ("igemm_tiled_inst.hip",) + _IGEMM_DEPS) for c in range(4)] + \
-        [("igemm2w_inst.hip", ["-DRVC_G2W_PART=%d" % c], ("igemm2w_inst.hip",) + _IGEMM_DEPS) for c in range(3)] + \
-        [("igemm_bf3_inst.hip", [], ("igemm_bf3_inst.hip",) + _IGEMM_DEPS)] + \
-        [("conv_tile_inst.hip", [], ("conv_tile_inst.hip", "conv_tile.hip.h") + _IGEMM_DEPS)] + \
-        [("conv32s_inst.hip", ["-DRVC_C32S_PART=%d" % c], ("conv32s_inst.hip", "conv32s.hip.h") + _IGEMM_DEPS) for c in range(3)] + \
-        [("igemm32l_inst.hip", ["-DRVC_G32L_PART=%d" % c], ("igemm32l_inst.hip", "igemm32l.hip.h") + _IGEMM_DEPS) for c in range(2)]
+UNITS = [(src, flags, _include_closure(src)) for src, flags in
+         [(u, []) for u in ("engine.hip", "debug.hip", "calib.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "model_synth.hip", "retrieval.hip")] +
+         [("igemm2_inst.hip", ["-DRVC_IGEMM2_CFG=%d" % c]) for c in range(5)] +
+         [("igemm_tiled_inst.hip", ["-DRVC_TILED_PART=%d" % c]) for c in range(4)] +
+         [("igemm2w_inst.hip", ["-DRVC_G2W_PART=%d" % c]) for c in range(3)] +
+         [("igemm_bf3_inst.hip", []), ("conv_tile_inst.hip", [])] +
+         [("conv32s_inst.hip", ["-DRVC_C32S_PART=%d" % c]) for c in range(3)] +
+         [("igemm32l_inst.hip", ["-DRVC_G32L_PART=%d" % c]) for c in range(2)]]
+# what source_hash covers: every unit's closure inside csrc, and what is built or read besides the units
+SOURCES = tuple(sorted({d for _, _, deps in UNITS for d in deps if not d.startswith("..")} | {"version.cpp", "exports.map", "rvc_rpc.cpp"}))
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # Object cache: content-addressed (sources + flags).  It lives under the repository's build/ directory (git- and gpurun-ignored), is
 # created 0700, and a directory that is not ours (other owner, or writable by group / others) is refused: objects are linked straight
@@ -102,7 +112,7 @@ def binary_hash(path: str = None) -> str:
 def _unit_key(src, flags, deps, extra_flags):
     import hashlib
     h = hashlib.sha256(" ".join(HIPCC_FLAGS + list(flags) + list(extra_flags)).encode())
-    for n in tuple(deps) + ("../../include/rvc_mi355x.h",):
+    for n in deps:
         with open(os.path.join(CSRC, n), "rb") as fh:
             h.update(n.encode() + b"\0" + fh.read())
     return "%s-%s" % (os.path.splitext(src)[0], h.hexdigest()[:20])

@@ -1,5 +1,5 @@
 // crossfade.hip.h -- the two per-stream session stages that have no counterpart in the plugin (DESIGN.md "Phase-vocoder crossfade and input
-// gate"), included by engine.hip behind kernels.hip.h:
+// gate"), included by engine.hip behind chunk.hip.h:
 //   * the phase-vocoder blend of the SOLA seam: analysis (windowed DFT of the saved tail and of the aligned new segment at n/2+1 bins, any n)
 //     and synthesis (oscillator bank: every bin's phase glides from the old segment's to the new one's along the seam);
 //   * the input gate: 10 ms blocks whose 40 ms RMS lies below a threshold are zeroed in front of the host-rate ring.

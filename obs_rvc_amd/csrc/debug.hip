@@ -589,10 +589,7 @@ int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *pho
         HIPCHK(hipMemcpy(d_cv, cv, n_cv * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_pf, pitchf, n_pf * 4, hipMemcpyHostToDevice));
         const int ph_ld = s->ph_ld, cv_ld = s->cv_ld, skip_head = s->skip_head;
-        const dim3 grid = protect_grid(R, B, C);
-        pl.ops.push_back([=](hipStream_t st) {
-            hipLaunchKernelGGL(protect_mix_kernel, grid, dim3(PROTECT_ROWS, PROTECT_LANES), 0, st, d_st, d_pf, d_cv, cv_ld, (long long)C * cv_ld, C, T, skip_head, R, d_ph, ph_ld, (long long)C * ph_ld);
-        });
+        pl.ops.push_back([=](hipStream_t st) { launch_protect_mix(st, B, d_st, d_pf, d_cv, cv_ld, (long long)C * cv_ld, C, T, skip_head, R, d_ph, ph_ld, (long long)C * ph_ld); });
         run_ops(e, pl, 1, s->graph != 0);
         HIPCHK(hipMemcpy(phone, d_ph, n_ph * 4, hipMemcpyDeviceToHost));
         return RVC_OK;

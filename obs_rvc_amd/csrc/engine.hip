@@ -2,9 +2,10 @@
 //
 // Mirrors rvc::RvcInfer (reference: rvc/src/rvc.rs:18-220): model handles, the 1024-entry
 // pitch cache, and the per-chunk pipeline hubert -> (retrieval) -> pitch -> synthesizer.
-// All compute is launched as hand-written gfx950 kernels (kernels.hip.h); nothing here falls
+// All compute is launched as hand-written gfx950 kernels (the *.hip.h headers); nothing here falls
 // back to a CPU path: without a HIP device every entry point returns RVC_BACKEND.
 #include "engine_int.h"
+#include "chunk.hip.h"
 #include "crossfade.hip.h"
 #include <chrono>
 
@@ -32,6 +33,12 @@ static void init_kernel_attrs()
     std::lock_guard<std::mutex> lk(mu);
     if (dev >= 0 && dev < 64) { if (done[dev]) return; done[dev] = true; }
     plan_kernel_attrs(); retrieval_kernel_attrs();
+}
+
+void launch_protect_mix(hipStream_t s, int B, const StreamState *st, const float *pitchf, const float *cv, int cv_cs, long long cv_bs, int C, int T, int skip_head, int R,
+                        float *phone, int ph_cs, long long ph_bs)
+{
+    hipLaunchKernelGGL(protect_mix_kernel, protect_grid(R, B, C), dim3(PROTECT_ROWS, PROTECT_LANES), 0, s, st, pitchf, cv, cv_cs, cv_bs, C, T, skip_head, R, phone, ph_cs, ph_bs);
 }
 
 static void init_constants(rvc_engine *e)
@@ -326,7 +333,6 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         // synthesizer is queued yet.  Behind op_ret_end, so recover_retrieval replays it with the rest of the chunk (on the re-gathered, re-blended phone)
         if (with_protect) {
             T1 cvo = pl.cv_out; const StreamState *stp = e->d_state; const float *pf = d_pitchf0;
-            const dim3 grid = protect_grid((int)R, B, C);
             if (pl.with_taps && phone.bs == (long long)C * phone.ld && cvo.bs == (long long)C * cvo.ld) {       // (streams back to back, as make_t1 lays them out)
                 // what the stage reads, every stream of the plan (phone_ct and cv.out are stream 0's): the blended rows [B][C][R] and the ContentVec output [B][C][T]
                 T1 blend = phone; blend.B = 1; blend.C = B * C;
@@ -334,9 +340,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
                 T1 cva = cvo; cva.B = 1; cva.C = B * C;
                 add_tap(pl, "cv.out_all", cva);
             }
-            pl.ops.push_back([=](hipStream_t s) {
-                hipLaunchKernelGGL(protect_mix_kernel, grid, dim3(PROTECT_ROWS, PROTECT_LANES), 0, s, stp, pf, cvo.p, cvo.ld, cvo.bs, C, T, (int)skip_head, (int)R, phone.p, phone.ld, phone.bs);
-            });
+            pl.ops.push_back([=](hipStream_t s) { launch_protect_mix(s, B, stp, pf, cvo.p, cvo.ld, cvo.bs, C, T, (int)skip_head, (int)R, phone.p, phone.ld, phone.bs); });
             // tap of every stream of the plan, stream-major [B][C][R] (the streams of a plan tensor lie back to back)
             T1 all = phone; all.B = 1; all.C = B * C;
             if (pl.with_taps) add_tap(pl, "phone_prot", all);
@@ -584,7 +588,7 @@ static rvc_status check_status(rvc_engine *e)
         return RVC_BACKEND;
     }
     if (any & ST_KNN_TIMEOUT) {
-        // the retrieval's counters were poisoned by the selector that gave up (kernels.hip.h): re-arm them, whatever else happens
+        // the retrieval's counters were poisoned by the selector that gave up (knn.hip.h): re-arm them, whatever else happens
         HIPCHK(hipDeviceSynchronize());
         for (auto &p : e->plans) if (p->knn_ticket) HIPCHK(hipMemset(p->knn_ticket, 0, p->knn_ticket_bytes));
     }

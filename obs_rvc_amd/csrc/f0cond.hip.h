@@ -1,4 +1,4 @@
-// f0cond.hip.h -- per-stream conditioning of the f0 window inside the pitch tail (pitch_post_kernel, kernels.hip.h; DESIGN.md "Pitch controls"):
+// f0cond.hip.h -- per-stream conditioning of the f0 window inside the pitch tail (pitch_post_kernel, rmvpe.hip.h; DESIGN.md "Pitch controls"):
 //   gate     a voiced row outside [lo, hi] Hz becomes unvoiced (0)
 //   median   scipy.signal.medfilt(f, 2 r + 1), r <= 7: rows outside the window count as 0, unvoiced zeros take part as values
 //   snap     n = 69 + 12 log2(f / 440); target = the nearest MIDI note whose pitch class is in the mask (a tie goes to the lower note);

@@ -1,5 +1,5 @@
-// formant.hip.h -- formant shift (the plugin's resonance shift, obs-rvc/src/lib.rs:80,103,176,369-375,446-451): geometry, the
-// windowed-sinc filter table, and the two kernels of the synthesizer's formant stage (DESIGN.md "Formant shift").
+// formant.hip.h -- formant shift (the plugin's resonance shift, obs-rvc/src/lib.rs:80,103,176,369-375,446-451): geometry and the
+// windowed-sinc filter table of the synthesizer's formant stage (DESIGN.md "Formant shift"; host code only, the two kernels: synth.hip.h).
 //   geometry   f = 2^(phi / 12), R2 = ceil(R f), upp_res = floor(f sr / 100)
 //   stretch    the NSF source (R upp samples) and the latent z (R frames) are linearly interpolated to R2 upp / R2 (time_lerp_kernel)
 //   decoder    runs on R2 frames
@@ -73,44 +73,6 @@ static inline void formant_table_compact(size_t o, size_t n, std::vector<float> 
     for (size_t j = 0; j < n; j++)
         for (int t = 0; t < Kt && (size_t)(kb[j] + t) < K; t++) ht[j * Kt + t] = h[j * K + kb[j] + t];
     *w_out = (int)w; *Kt_out = Kt;
-}
-
-// y[b][c][0:Nout] = linear interpolation of x[b][c][0:Nin] (torch.nn.functional.interpolate, mode "linear", align_corners=False)
-static __global__ __launch_bounds__(256) void time_lerp_kernel(const float *x, int xld, long long xbs, float *y, int yld, long long ybs, int C, int Nin, int Nout)
-{
-    const int b = blockIdx.y;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)C * Nout) return;
-    const int c = (int)(idx / Nout), i = (int)(idx - (long long)c * Nout);
-    const float s = (float)Nin / (float)Nout;
-    const float xs = fmaxf(__fmul_rn(s, (float)i + 0.5f) - 0.5f, 0.f);
-    const int i0 = min((int)xs, Nin - 1), i1 = i0 + (i0 < Nin - 1 ? 1 : 0);
-    const float l = fminf(fmaxf(xs - (float)i0, 0.f), 1.f);
-    const float *row = x + (long long)b * xbs + (long long)c * xld;
-    y[(long long)b * ybs + (long long)c * yld + i] = __fmul_rn(1.f - l, row[i0]) + __fmul_rn(l, row[i1]);
-}
-
-// Back to the model rate, per stream from its descriptor (StreamState::f_*, so that the streams of one plan may differ and a captured
-// graph stays valid when the shift changes): y[q n + j] = sum_t ht[j][t] x[q o + kb[j] + t - w], x = y2[0 : nx] and zero outside;
-// an identity stream (upp_res = upp) copies y2[0 : N].  One thread per output sample.
-static __global__ __launch_bounds__(256) void formant_resample_kernel(const float *x, long long xbs, float *y, long long ybs, int N, const StreamState *st)
-{
-    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const StreamState &s = st[b];
-    const float *row = x + (long long)b * xbs;
-    float *out = y + (long long)b * ybs;
-    if (s.f_ident) { out[i] = row[i]; return; }
-    const int n = s.f_n, q = i / n, j = i - q * n, Kt = s.f_kt, nx = s.f_nx;
-    const float *h = s.f_tab + (long long)j * Kt;
-    const int base = q * s.f_o + s.f_kb[j] - s.f_w;
-    float acc = 0.f;
-    for (int t = 0; t < Kt; t++) {
-        const int k = base + t;
-        const float v = (k >= 0 && k < nx) ? row[k] : 0.f;
-        acc = fmaf(h[t], v, acc);
-    }
-    out[i] = acc;
 }
 
 }  // namespace rvc

@@ -1688,7 +1688,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G32Occ<MT, 
 // runs at 1/16 of the bf16 rate (v_mfma_f32_32x32x2_f32: 4 096 flops in 64 clocks; v_mfma_f32_32x32x16_bf16: 32 768 in 32), so three bf16 MFMAs per
 // 16-deep chunk cost 96 clocks where the fp32 form costs 512.  The kernel is igemm32_kernel's anatomy (128 x 128 workgroup tile, 2 x 2 waves of 64 x 64,
 // activation tile staged through LDS once per workgroup, one barrier per K step of 16):
-//   * weights: split at plan time (bf3_pack_kernel) into panels [32-row block][chunk][hi | lo][lane][8 bf16] -- a lane's 16 bytes are its row's eight
+//   * weights: split at plan time (bf3_pack_kernel, igemm_bf3_inst.hip) into panels [32-row block][chunk][hi | lo][lane][8 bf16] -- a lane's 16 bytes are its row's eight
 //     k values (k = (lane >> 5) * 8 + i) of one half, a wave instruction reads 1 KB contiguous;
 //   * activations: a staging thread gathers the eight k rows of one k group for its column (8 dword loads), splits them (v_cvt_pk_bf16_f32) and writes
 //     two 16-byte pieces; LDS holds [hi | lo][column][k group 0 | k group 1 | pad] at 48 bytes per column (16 lanes x 16 bytes on disjoint banks);
@@ -1699,26 +1699,6 @@ __device__ __forceinline__ void bf3_split(const float (&v)[8], bf16x8 &hi, bf16x
 {
 #pragma unroll
     for (int i = 0; i < 8; i++) { hi[i] = (__bf16)v[i]; lo[i] = (__bf16)(v[i] - (float)hi[i]); }
-}
-static __global__ void bf3_pack_kernel(const float *wfrag, int M, int nchunks, bf16x8 *out, long long total)
-{
-    // out element (blk32, chunk, half, lane): eight bf16 of row blk32 * 32 + (lane & 31), k = chunk * 16 + (lane >> 5) * 8 + i, from the fp32
-    // fragment packing [m_tile16][chunk][lane16x4][4]
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int lane = (int)(e & 63), half = (int)((e >> 6) & 1);
-    const long long bc = e >> 7;
-    const int chunk = (int)(bc % nchunks), blk = (int)(bc / nchunks);
-    const int m = blk * 32 + (lane & 31), mt16 = (M + 15) >> 4;
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int kk = (lane >> 5) * 8 + i;
-        v[i] = (m >> 4) < mt16 ? wfrag[((((long long)(m >> 4) * nchunks + chunk) * 64) + (kk >> 2) * 16 + (m & 15)) * 4 + (kk & 3)] : 0.f;
-    }
-    bf16x8 hi, lo;
-    bf3_split(v, hi, lo);
-    out[e] = half ? lo : hi;
 }
 template <int WM, int WN, int MT, int NT, bool LIN, bool PRE>
 __global__ __launch_bounds__(256) void igemm_bf3_kernel(IgemmP p)

@@ -1,7 +1,81 @@
 // model_cv.hip -- ContentVec / HuBERT-base feature extractor as a plan (reference: rvc/src/rvc.rs:81-97, ort::Session::run at rvc.rs:92)
 #include "engine_int.h"
+#include "contentvec.hip.h"
 
 namespace rvc {
+
+// ------------------------------- the model as loaded (struct ModelCV: engine_int.h) ------------------------------------------
+ConvW ModelCV::fold_ln(const float *w, const float *bias, int M, int K, const float *g, const float *beta, float **wsum_dev)
+{
+    std::vector<float> wf((size_t)M * K), bf(M), ws(M);
+    for (int m = 0; m < M; m++) {
+        double sb = bias ? bias[m] : 0.0, sw = 0.0;
+        for (int k = 0; k < K; k++) {
+            const float v = w[(size_t)m * K + k] * g[k];
+            wf[(size_t)m * K + k] = v;
+            sb += (double)w[(size_t)m * K + k] * beta[k];
+            sw += v;
+        }
+        bf[m] = (float)sb; ws[m] = (float)sw;
+    }
+    *wsum_dev = upload_f(ws);
+    return prep_conv(wf.data(), bf.data(), M, K, 1, 1);
+}
+ModelCV::ModelCV(const Blob &b)
+{
+    conv_dim = b.icfg("conv_dim"); embed = b.icfg("embed"); heads = b.icfg("heads"); ffn = b.icfg("ffn");
+    run_layers = b.icfg("run_layers"); pos_k = b.icfg("pos_k"); pos_groups = b.icfg("pos_groups"); out_dim = b.icfg("out_dim");
+    int cin = 1;
+    for (int i = 0; i < 7; i++) {
+        conv_k[i] = b.icfg(fmt("conv_k%d", i)); conv_s[i] = b.icfg(fmt("conv_s%d", i));
+        conv[i] = prep_conv(b.w(fmt("cv.conv%d.w", i)), nullptr, conv_dim, cin, conv_k[i], 1);
+        cin = conv_dim;
+    }
+    auto own = [&](const std::string &n) { float *p = dv(b, n); owned.push_back(p); return p; };
+    conv0_raw = own("cv.conv0.w");
+    gn_g = own("cv.gn.g"); gn_b = own("cv.gn.b"); ln0_g = own("cv.ln0.g"); ln0_b = own("cv.ln0.b");
+    proj = prep_conv(b.w("cv.proj.w"), b.w("cv.proj.b"), embed, conv_dim, 1, 1);
+    pos = prep_conv(b.w("cv.pos.w"), b.w("cv.pos.b"), embed, embed, pos_k, pos_groups);
+    encln_g = own("cv.enc_ln.g"); encln_b = own("cv.enc_ln.b");
+    const int E = embed;
+    for (int l = 0; l < run_layers; l++) {
+        Layer L;
+        std::vector<float> w((size_t)3 * E * E), bb((size_t)3 * E);
+        const char *nm[3] = {"q", "k", "v"};
+        for (int j = 0; j < 3; j++) {
+            memcpy(&w[(size_t)j * E * E], b.w(fmt("cv.l%d.", l) + nm[j] + ".w"), (size_t)E * E * 4);
+            memcpy(&bb[(size_t)j * E], b.w(fmt("cv.l%d.", l) + nm[j] + ".b"), (size_t)E * 4);
+        }
+        L.qkv = prep_conv(w.data(), bb.data(), 3 * E, E, 1, 1);
+        L.o = prep_conv(b.w(fmt("cv.l%d.o.w", l)), b.w(fmt("cv.l%d.o.b", l)), E, E, 1, 1);
+        L.ff1 = prep_conv(b.w(fmt("cv.l%d.ff1.w", l)), b.w(fmt("cv.l%d.ff1.b", l)), ffn, E, 1, 1);
+        L.ff2 = prep_conv(b.w(fmt("cv.l%d.ff2.w", l)), b.w(fmt("cv.l%d.ff2.b", l)), E, ffn, 1, 1);
+        L.ln1_g = own(fmt("cv.l%d.ln1.g", l)); L.ln1_b = own(fmt("cv.l%d.ln1.b", l));
+        L.ln2_g = own(fmt("cv.l%d.ln2.g", l)); L.ln2_b = own(fmt("cv.l%d.ln2.b", l));
+        if (E >= 256 && E % 64 == 0 && ffn % 64 == 0 && !test_opt("RVC_NO_LN_FUSE")) {
+            has_folded = true;
+            L.ff1_f = fold_ln(b.w(fmt("cv.l%d.ff1.w", l)), b.w(fmt("cv.l%d.ff1.b", l)), ffn, E, b.w(fmt("cv.l%d.ln1.g", l)), b.w(fmt("cv.l%d.ln1.b", l)), &L.ff1_wsum);
+            if (l > 0) L.qkv_f = fold_ln(w.data(), bb.data(), 3 * E, E, b.w(fmt("cv.l%d.ln2.g", l - 1)), b.w(fmt("cv.l%d.ln2.b", l - 1)), &L.qkv_wsum);
+            else L.qkv_f = fold_ln(w.data(), bb.data(), 3 * E, E, b.w("cv.enc_ln.g"), b.w("cv.enc_ln.b"), &L.qkv_wsum);      // layer 0: the encoder's input LayerNorm
+        }
+        layers.push_back(L);
+    }
+    if (out_dim != E) final_proj = prep_conv(b.w("cv.final_proj.w"), b.w("cv.final_proj.b"), out_dim, E, 1, 1);
+    if (has_folded && conv_dim % 64 == 0) proj_f = fold_ln(b.w("cv.proj.w"), b.w("cv.proj.b"), embed, conv_dim, b.w("cv.ln0.g"), b.w("cv.ln0.b"), &proj_wsum);
+    weight_bytes = b.bytes();
+}
+ModelCV::~ModelCV()
+{
+    for (auto &c : conv) free_conv(c);
+    free_conv(proj); free_conv(pos); free_conv(final_proj); free_conv(proj_f);
+    if (proj_wsum) wfree(proj_wsum);
+    for (auto &L : layers) {
+        free_conv(L.qkv); free_conv(L.o); free_conv(L.ff1); free_conv(L.ff2); free_conv(L.qkv_f); free_conv(L.ff1_f);
+        if (L.qkv_wsum) wfree(L.qkv_wsum);
+        if (L.ff1_wsum) wfree(L.ff1_wsum);
+    }
+    for (float *p : owned) wfree(p);
+}
 
 // ------------------------------- ContentVec ------------------------------------------
 // First layer: Conv1d(1 -> C, k taps, no bias) + GroupNorm (one group per channel: statistics over time) + GELU on the raw input x [B][1][L] into

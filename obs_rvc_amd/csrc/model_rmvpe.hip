@@ -1,8 +1,124 @@
 // model_rmvpe.hip -- RMVPE f0 estimator (mel front end, U-Net, BiGRU, salience) and the decode / pitch-cache step as a plan (reference: rvc/src/f0/rmvpe.rs:118-133, 225-248; rvc/src/rvc.rs:111-131, 167-180)
 #include "engine_int.h"
+#include "rmvpe.hip.h"
 #include "rmblock.hip.h"
 
 namespace rvc {
+
+// ------------------------------- the model as loaded (struct ModelRM, ResBlockW: engine_int.h) ------------------------------------------
+// -> fragment-order panel of a [co][ci * taps] convolution weight for rm_block_kernel
+static std::vector<float> rm_block_panel(const float *w, int co, int ci, int taps)
+{
+    const int c16 = (ci + 15) / 16 * 16, steps = c16 / 4, MT = co / 16;
+    std::vector<float> pk((size_t)taps * steps * MT * 64, 0.f);
+    for (int t = 0; t < taps; t++)
+        for (int c4 = 0; c4 < steps; c4++)
+            for (int mt = 0; mt < MT; mt++)
+                for (int l = 0; l < 64; l++) {
+                    const int m = mt * 16 + (l & 15), c = c4 * 4 + (l >> 4);
+                    if (c < ci) pk[(((size_t)t * steps + c4) * MT + mt) * 64 + l] = w[(size_t)m * ci * taps + (size_t)c * taps + t];
+                }
+    return pk;
+}
+ResBlockW make_res_block(const float *w1, const float *b1, const float *w2, const float *b2, const float *wsc, const float *bsc, int ci, int co)
+{
+    ResBlockW r; r.ci = ci; r.co = co;
+    r.c1 = prep_conv(w1, b1, co, ci, 9, 1);
+    r.c2 = prep_conv(w2, b2, co, co, 9, 1);
+    if (wsc) {
+        r.has_sc = true; r.sc = prep_conv(wsc, bsc, co, ci, 1, 1);
+        std::vector<float> pb(b1, b1 + co);
+        pb.insert(pb.end(), bsc, bsc + co);
+        r.pair_bias = upload_f(pb);
+    }
+    if ((co == 16 || co == 32) && ci <= 64) {
+        std::vector<float> all = rm_block_panel(w1, co, ci, 9);
+        const size_t o2 = all.size();
+        { std::vector<float> t = rm_block_panel(w2, co, co, 9); all.insert(all.end(), t.begin(), t.end()); }
+        const size_t o3 = all.size();
+        if (r.has_sc) { std::vector<float> t = rm_block_panel(wsc, co, ci, 1); all.insert(all.end(), t.begin(), t.end()); }
+        all.resize((all.size() + 31) / 32 * 32, 0.f);
+        r.f_w1 = upload_f(all); r.f_w2 = r.f_w1 + o2; r.f_sc = r.has_sc ? r.f_w1 + o3 : nullptr; r.f_lines = (int)(all.size() / 32);
+    }
+    return r;
+}
+void free_res_block(ResBlockW &r)
+{
+    free_conv(r.c1); free_conv(r.c2); free_conv(r.sc);
+    if (r.pair_bias) wfree(r.pair_bias);
+    if (r.f_w1) wfree(r.f_w1);
+    r.pair_bias = nullptr; r.f_w1 = r.f_w2 = r.f_sc = nullptr; r.f_lines = 0;
+}
+void gru_prep_whh(const float *const whh_dir[2], int H, std::vector<float> &whhT, std::vector<float> &whh)
+{
+    whhT.resize((size_t)2 * H * 3 * H); whh.resize((size_t)2 * 3 * H * H);
+    for (int d = 0; d < 2; d++) {
+        const float *w = whh_dir[d];
+        for (int r = 0; r < 3 * H; r++) for (int j = 0; j < H; j++) whhT[((size_t)d * H + j) * 3 * H + r] = w[(size_t)r * H + j];
+        memcpy(&whh[(size_t)d * 3 * H * H], w, (size_t)3 * H * H * sizeof(float));
+    }
+}
+ResBlockW ModelRM::block(const Blob &b, const std::string &pre, int ci, int co)
+{
+    const bool sc = ci != co;
+    return make_res_block(b.w(pre + "c1.w"), b.w(pre + "c1.b"), b.w(pre + "c2.w"), b.w(pre + "c2.b"), sc ? b.w(pre + "sc.w") : nullptr, sc ? b.w(pre + "sc.b") : nullptr, ci, co);
+}
+ModelRM::ModelRM(const Blob &b)
+{
+    en_out = b.icfg("en_out"); levels = b.icfg("levels"); n_blocks = b.icfg("n_blocks"); inter_layers = b.icfg("inter_layers");
+    n_mels = b.icfg("n_mels"); gru_hidden = b.icfg("gru_hidden"); n_out = b.icfg("n_out");
+    bn_scale = b.w("rm.bn0")[0]; bn_shift = b.w("rm.bn0")[1];
+    int ci = 1, co = en_out;
+    for (int lv = 0; lv < levels; lv++) {
+        std::vector<ResBlockW> v;
+        for (int j = 0; j < n_blocks; j++) v.push_back(block(b, fmt("rm.enc%d.b%d.", lv, j), j == 0 ? ci : co, co));
+        enc.push_back(v);
+        ci = co; co *= 2;
+    }
+    for (int lv = 0; lv < inter_layers; lv++) {
+        std::vector<ResBlockW> v;
+        for (int j = 0; j < n_blocks; j++) v.push_back(block(b, fmt("rm.int%d.b%d.", lv, j), j == 0 ? (lv == 0 ? ci : co) : co, co));
+        inter.push_back(v);
+    }
+    ci = co;
+    for (int lv = 0; lv < levels; lv++) {
+        co = ci / 2;
+        up.push_back(prep_convT2d(b.w(fmt("rm.dec%d.up.w", lv)), b.w(fmt("rm.dec%d.up.b", lv)), ci, co));
+        std::vector<ResBlockW> v;
+        for (int j = 0; j < n_blocks; j++) v.push_back(block(b, fmt("rm.dec%d.b%d.", lv, j), j == 0 ? 2 * co : co, co));
+        dec.push_back(v);
+        ci = co;
+    }
+    cnn = prep_conv(b.w("rm.cnn.w"), b.w("rm.cnn.b"), 3, en_out, 9, 1);
+    const int H = gru_hidden, I = 3 * n_mels;
+    std::vector<float> wih((size_t)6 * H * I), bih((size_t)6 * H), bh((size_t)6 * H);
+    const char *sfx[2] = {"f", "b"};
+    const float *whh_dir[2];
+    for (int d = 0; d < 2; d++) {
+        memcpy(&wih[(size_t)d * 3 * H * I], b.w(std::string("rm.gru.w_ih_") + sfx[d]), (size_t)3 * H * I * 4);
+        memcpy(&bih[(size_t)d * 3 * H], b.w(std::string("rm.gru.b_ih_") + sfx[d]), (size_t)3 * H * 4);
+        memcpy(&bh[(size_t)d * 3 * H], b.w(std::string("rm.gru.b_hh_") + sfx[d]), (size_t)3 * H * 4);
+        whh_dir[d] = b.w(std::string("rm.gru.w_hh_") + sfx[d]);
+    }
+    gru_ih = prep_conv(wih.data(), bih.data(), 6 * H, I, 1, 1);
+    {
+        std::vector<float> wt, wr;
+        gru_prep_whh(whh_dir, H, wt, wr);
+        whhT = upload_f(wt); bhh = upload_f(bh); whh = upload_f(wr);
+    }
+    fc = prep_conv(b.w("rm.fc.w"), b.w("rm.fc.b"), n_out, 2 * H, 1, 1);
+    weight_bytes = b.bytes();
+}
+ModelRM::~ModelRM()
+{
+    auto fb = [](std::vector<std::vector<ResBlockW>> &vv) { for (auto &v : vv) for (auto &r : v) free_res_block(r); };
+    fb(enc); fb(inter); fb(dec);
+    for (auto &u : up) free_conv(u);
+    free_conv(cnn); free_conv(gru_ih); free_conv(fc);
+    if (whhT) wfree(whhT);
+    if (bhh) wfree(bhh);
+    if (whh) wfree(whh);
+}
 
 // One launch per ConvBlockRes on the shallow levels (rm_block_kernel, rmblock.hip.h): few streams only -- there the f0 branch is a chain of dependent
 // 5-8 us launches on its own CU partition and the block's halo recomputation costs nothing that matters; with many streams folded into a launch the two

@@ -1,7 +1,291 @@
 // model_synth.hip -- the synthesizer (text encoder, prior sample, flows, NSF source, HiFiGAN decoder) as a plan (reference: rvc/src/rvc.rs:182-214, ort::Session::run at rvc.rs:195)
 #include "engine_int.h"
+#include "synth.hip.h"
 
 namespace rvc {
+
+// ------------------------------- the model as loaded (struct ModelSY: engine_int.h) ------------------------------------------
+template <typename T> void glu_pack_rows(const T *w, const float *bias, int H, size_t K, std::vector<float> &wp, std::vector<float> &bp)
+{
+    if (H % 8 != 0) throw std::runtime_error("GLU-gated layer: channel count must be a multiple of 8");
+    wp.resize((size_t)2 * H * K); bp.resize((size_t)2 * H);
+    for (int r = 0; r < 2 * H; r++) {
+        const int f = r >> 4, kq = (r & 15) >> 2, rr = r & 3;
+        const int src = f * 8 + kq * 2 + (rr & 1) + (rr >= 2 ? H : 0);
+        for (size_t q = 0; q < K; q++) wp[(size_t)r * K + q] = (float)w[(size_t)src * K + q];
+        bp[r] = bias[src];
+    }
+}
+template void glu_pack_rows<float>(const float *, const float *, int, size_t, std::vector<float> &, std::vector<float> &);
+template void glu_pack_rows<double>(const double *, const float *, int, size_t, std::vector<float> &, std::vector<float> &);      // (compose_flows)
+ModelSY::ModelSY(const Blob &b)
+{
+    phone_dim = b.icfg("phone_dim"); hidden = b.icfg("hidden"); inter = b.icfg("inter"); filter = b.icfg("filter"); heads = b.icfg("heads");
+    enc_layers = b.icfg("enc_layers"); enc_k = b.icfg("enc_k"); window = b.icfg("window"); flow_n = b.icfg("flow_n");
+    wn_layers = b.icfg("wn_layers"); wn_k = b.icfg("wn_k"); gin = b.icfg("gin"); up_init = b.icfg("up_init"); n_ups = b.icfg("n_ups");
+    n_rb = b.icfg("n_rb"); n_rbd = b.icfg("n_rbd"); sr = b.icfg("sr");
+    for (int i = 0; i < n_ups; i++) { up_rate[i] = b.icfg(fmt("up_rate%d", i)); up_kernel[i] = b.icfg(fmt("up_kernel%d", i)); }
+    for (int j = 0; j < n_rb; j++) rb_k[j] = b.icfg(fmt("rb_k%d", j));
+    for (int m = 0; m < n_rbd; m++) rb_d[m] = b.icfg(fmt("rb_d%d", m));
+    auto own = [&](const std::string &n) { float *p = dv(b, n); owned.push_back(p); return p; };
+    const int H = hidden, G = gin;
+    const float *g = b.w("sy.g");
+    phone = prep_conv(b.w("sy.enc.phone.w"), b.w("sy.enc.phone.b"), H, phone_dim, 1, 1);
+    pitch_emb = own("sy.enc.pitch_emb");
+    for (int l = 0; l < enc_layers; l++) {
+        Layer L;
+        std::vector<float> w((size_t)3 * H * H), bb((size_t)3 * H);
+        const char *nm[3] = {"q", "k", "v"};
+        for (int j = 0; j < 3; j++) {
+            memcpy(&w[(size_t)j * H * H], b.w(fmt("sy.enc.l%d.", l) + nm[j] + ".w"), (size_t)H * H * 4);
+            memcpy(&bb[(size_t)j * H], b.w(fmt("sy.enc.l%d.", l) + nm[j] + ".b"), (size_t)H * 4);
+        }
+        L.qkv = prep_conv(w.data(), bb.data(), 3 * H, H, 1, 1);
+        L.o = prep_conv(b.w(fmt("sy.enc.l%d.o.w", l)), b.w(fmt("sy.enc.l%d.o.b", l)), H, H, 1, 1);
+        L.ff1 = prep_conv(b.w(fmt("sy.enc.l%d.ff1.w", l)), b.w(fmt("sy.enc.l%d.ff1.b", l)), filter, H, enc_k, 1);
+        L.ff2 = prep_conv(b.w(fmt("sy.enc.l%d.ff2.w", l)), b.w(fmt("sy.enc.l%d.ff2.b", l)), H, filter, enc_k, 1);
+        L.rel_k = own(fmt("sy.enc.l%d.rel_k", l)); L.rel_v = own(fmt("sy.enc.l%d.rel_v", l));
+        L.ln1_g = own(fmt("sy.enc.l%d.ln1.g", l)); L.ln1_b = own(fmt("sy.enc.l%d.ln1.b", l));
+        L.ln2_g = own(fmt("sy.enc.l%d.ln2.g", l)); L.ln2_b = own(fmt("sy.enc.l%d.ln2.b", l));
+        if (H >= 128 && H % 16 == 0 && !test_opt("RVC_NO_LN_FUSE")) {
+            has_folded = true;
+            if (l > 0) L.qkv_f = ModelCV::fold_ln(w.data(), bb.data(), 3 * H, H, b.w(fmt("sy.enc.l%d.ln2.g", l - 1)), b.w(fmt("sy.enc.l%d.ln2.b", l - 1)), &L.qkv_wsum);
+        }
+        layers.push_back(L);
+    }
+    proj = prep_conv(b.w("sy.enc.proj.w"), b.w("sy.enc.proj.b"), 2 * inter, H, 1, 1);
+    if (has_folded)
+        proj_f = ModelCV::fold_ln(b.w("sy.enc.proj.w"), b.w("sy.enc.proj.b"), 2 * inter, H, b.w(fmt("sy.enc.l%d.ln2.g", enc_layers - 1)), b.w(fmt("sy.enc.l%d.ln2.b", enc_layers - 1)), &proj_wsum);
+    const int half = inter / 2;
+    for (int i = 0; i < flow_n; i++) {
+        Flow F;
+        // Flip layers are folded into the weights: the latent stays in its physical channel order and a flow that sees it
+        // flipped (inference runs flip -> coupling from the last flow to the first: flow i after flow_n - i flips) reads its
+        // x0 from the upper half with reversed input columns and writes x1 to the lower half with reversed output rows
+        F.flipped = ((flow_n - i) & 1) != 0;
+        {
+            // rows H..2H are zero: the launch also clears the skip accumulator that sits behind hh in one tensor
+            std::vector<float> w((size_t)2 * H * half, 0.f), bb((size_t)2 * H, 0.f);
+            const float *pw = b.w(fmt("sy.flow%d.pre.w", i)), *pb = b.w(fmt("sy.flow%d.pre.b", i));
+            for (int r = 0; r < H; r++) {
+                bb[r] = pb[r];
+                for (int q = 0; q < half; q++) w[(size_t)r * half + q] = pw[(size_t)r * half + (F.flipped ? half - 1 - q : q)];
+            }
+            F.pre = prep_conv(w.data(), bb.data(), 2 * H, half, 1, 1);
+            F.h_pre_w.assign(w.begin(), w.begin() + (size_t)H * half); F.h_pre_b.assign(bb.begin(), bb.begin() + H);
+        }
+        // speaker conditioning is a load-time constant (sid baked, rvc.rs:186-187): fold cond(g) into the in-layer biases
+        const float *cw = b.w(fmt("sy.flow%d.cond.w", i)), *cb = b.w(fmt("sy.flow%d.cond.b", i));
+        for (int j = 0; j < wn_layers; j++) {
+            std::vector<float> bias(2 * H);
+            const float *ib = b.w(fmt("sy.flow%d.in%d.b", i, j));
+            for (int r = 0; r < 2 * H; r++) {
+                float a = cb[j * 2 * H + r];
+                for (int q = 0; q < G; q++) a += cw[(size_t)(j * 2 * H + r) * G + q] * g[q];
+                bias[r] = ib[r] + a;
+            }
+            {
+                const float *iw = b.w(fmt("sy.flow%d.in%d.w", i, j));
+                const size_t Kin = (size_t)H * wn_k;
+                std::vector<float> w, pb;
+                glu_pack_rows(iw, bias.data(), H, Kin, w, pb);
+                F.in.push_back(prep_conv(w.data(), pb.data(), 2 * H, H, wn_k, 1));
+                F.h_in_w.emplace_back(iw, iw + (size_t)2 * H * Kin); F.h_in_b.push_back(bias);
+            }
+            int rs_c = j < wn_layers - 1 ? 2 * H : H;
+            F.rs.push_back(prep_conv(b.w(fmt("sy.flow%d.rs%d.w", i, j)), b.w(fmt("sy.flow%d.rs%d.b", i, j)), rs_c, H, 1, 1));
+            { const float *rw = b.w(fmt("sy.flow%d.rs%d.w", i, j)), *rb = b.w(fmt("sy.flow%d.rs%d.b", i, j)); F.h_rs_w.emplace_back(rw, rw + (size_t)rs_c * H); F.h_rs_b.emplace_back(rb, rb + rs_c); }
+        }
+        {
+            const float *pw = b.w(fmt("sy.flow%d.post.w", i)), *pb = b.w(fmt("sy.flow%d.post.b", i));
+            std::vector<float> w((size_t)half * H), bb(half);
+            for (int r = 0; r < half; r++) {
+                const int src = F.flipped ? half - 1 - r : r;
+                memcpy(&w[(size_t)r * H], pw + (size_t)src * H, (size_t)H * sizeof(float));
+                bb[r] = pb[src];
+            }
+            F.post = prep_conv(w.data(), bb.data(), half, H, 1, 1);
+            F.h_post_w = w; F.h_post_b = bb;
+        }
+        flows.push_back(F);
+    }
+    // composed WaveNets (one to eight streams): built with the model, 20 tasks on the host's cores, so that no first chunk pays for them
+    if (hidden % 16 == 0 && inter == hidden && !test_opt("RVC_NO_WN_COMPOSE")) compose_flows();
+    {
+        std::vector<float> bias(up_init);
+        const float *cw = b.w("sy.dec.cond.w"), *cb = b.w("sy.dec.cond.b"), *pb = b.w("sy.dec.pre.b");
+        for (int c = 0; c < up_init; c++) { float a = cb[c]; for (int q = 0; q < G; q++) a += cw[(size_t)c * G + q] * g[q]; bias[c] = pb[c] + a; }
+        dec_pre = prep_conv(b.w("sy.dec.pre.w"), bias.data(), up_init, inter, 7, 1);
+    }
+    int c = up_init;
+    for (int i = 0; i < n_ups; i++) {
+        int co = c / 2;
+        ups.push_back(prep_convT1d(b.w(fmt("sy.dec.up%d.w", i)), b.w(fmt("sy.dec.up%d.b", i)), c, co, up_kernel[i], up_rate[i]));
+        int sf = 1; for (int q = i + 1; q < n_ups; q++) sf *= up_rate[q];
+        int nk = i + 1 < n_ups ? 2 * sf : 1;
+        ncs.push_back(prep_conv(b.w(fmt("sy.dec.nc%d.w", i)), b.w(fmt("sy.dec.nc%d.b", i)), co, 1, nk, 1));
+        std::vector<std::vector<std::pair<ConvW, ConvW>>> stage;
+        for (int j = 0; j < n_rb; j++) {
+            std::vector<std::pair<ConvW, ConvW>> chain;
+            for (int m = 0; m < n_rbd; m++) {
+                ConvW c1 = prep_conv(b.w(fmt("sy.dec.rb%d_%d.c1_%d.w", i, j, m)), b.w(fmt("sy.dec.rb%d_%d.c1_%d.b", i, j, m)), co, co, rb_k[j], 1);
+                ConvW c2 = prep_conv(b.w(fmt("sy.dec.rb%d_%d.c2_%d.w", i, j, m)), b.w(fmt("sy.dec.rb%d_%d.c2_%d.b", i, j, m)), co, co, rb_k[j], 1);
+                chain.push_back({c1, c2});
+            }
+            stage.push_back(chain);
+        }
+        rbs.push_back(stage);
+        // the n_rb chains' q-th convs run as phases of one launch: their weights share an allocation
+        for (int m = 0; m < n_rbd && n_rb > 1; m++) {
+            std::vector<ConvW *> a, bb;
+            for (int j = 0; j < n_rb; j++) { a.push_back(&rbs.back()[j][m].first); bb.push_back(&rbs.back()[j][m].second); }
+            merge_convs(a); merge_convs(bb);
+        }
+        c = co;
+    }
+    dec_post = prep_conv(b.w("sy.dec.post.w"), nullptr, 1, c, 7, 1);
+    src_w = b.w("sy.src")[0]; src_b = b.w("sy.src")[1];
+    weight_bytes = b.bytes();
+    // the f0 / feature frame rate is 100 Hz (rvc.rs:153, 160 samples @16 kHz): a synthesizer whose hop is not sr / 100 would
+    // return audio of the wrong length without any error (e.g. an import that guessed the first upsample rate)
+    if (sr != 100 * upp()) throw std::runtime_error(fmt("synthesizer: sr %d", sr) + fmt(" != 100 * prod(upsample rates) = %d", 100 * upp()));
+}
+// One stream: every flow's WaveNet runs 4 x (gated k-tap in-layer, 1x1 res_skip layer) -- ten dependent launches of a 21-column window.  The
+// res_skip layers are linear, so they are composed into what follows them (exactly, in double, when the model is loaded):
+//   x_j = h0 + sum_{i<j} (R_i a_i + r_i)                      =>  in_j(x_j) = W_j * [1 | h0 | a_0 .. a_{j-1}]   with W_j(a_i) = W_j o R_i
+//   post(skip) = P (sum_j S_j a_j + s_j) + p                   =>  one 1x1 layer over [a_0 .. a_{n-1}]
+// (R_i / S_i: the residual / skip rows of res_skip layer i; the constant r_i rides on a row of ones -- zero in the halo, like the zero padding
+// the in-layer sees -- so the edges of the window stay exact.)  The latent z rides in the same tensor ([ones | h0 | a_0 .. | z]), and a flow's
+// post layer and the NEXT flow's pre layer become one 1x1 layer over [a_0 .. a_{n-1} | z] that writes h0_next and z_next into the other of two
+// such tensors (two phases of one launch: same input, two outputs): five launches per flow (+ one pre at the start) instead of ten.
+void ModelSY::compose_flows()
+{
+    if (composed) return;
+    const int H = hidden, I = inter, half = inter / 2, K5 = wn_k, nl = wn_layers;
+    const int nfl = (int)flows.size();
+    // per flow: x0 / x1 rows of the latent, the full-latent pre weights [H][I] (zero on the x1 half), post rows on the x1 half
+    auto x1_row0 = [&](const Flow &F) { return F.flipped ? 0 : half; };
+    auto x0_row0 = [&](const Flow &F) { return F.flipped ? half : 0; };
+    std::vector<std::vector<std::vector<float>>> WJ(nfl), BJ(nfl);
+    std::vector<std::vector<float>> WM(nfl), BM(nfl), WH(nfl), BH(nfl), WP1(nfl), BP1(nfl);
+    // in-layer j of flow fi over [ones16 | h0 | a_0 .. a_{j-1}] (one task each: 1.7 GFLOP of double arithmetic in all, spread over the host's cores)
+    auto in_layer = [&](int fi, int j) {
+        Flow &F = flows[fi];
+        {
+            const int Cin = 16 + H * (j + 1), a0 = 16 + H;
+            std::vector<double> w((size_t)2 * H * Cin * K5, 0.0);
+            const float *W5 = F.h_in_w[j].data();                 // [2H][H][K5], model row order
+            for (int o = 0; o < 2 * H; o++)
+                for (int mm = 0; mm < H; mm++)
+                    for (int t = 0; t < K5; t++) w[((size_t)o * Cin + 16 + mm) * K5 + t] = W5[((size_t)o * H + mm) * K5 + t];
+            std::vector<double> acc(H);
+            for (int i = 0; i < j; i++) {
+                const float *Rr = F.h_rs_w[i].data(), *rb = F.h_rs_b[i].data();      // rows 0..H: the residual part
+                for (int o = 0; o < 2 * H; o++)
+                    for (int t = 0; t < K5; t++) {
+                        std::fill(acc.begin(), acc.end(), 0.0);
+                        double one = 0.0;
+                        for (int mm = 0; mm < H; mm++) {
+                            const double v = W5[((size_t)o * H + mm) * K5 + t];
+                            const float *Rm = Rr + (size_t)mm * H;
+                            for (int c = 0; c < H; c++) acc[c] += v * Rm[c];
+                            one += v * rb[mm];
+                        }
+                        for (int c = 0; c < H; c++) w[((size_t)o * Cin + a0 + H * i + c) * K5 + t] = acc[c];
+                        w[((size_t)o * Cin) * K5 + t] += one;
+                    }
+            }
+            std::vector<float> wp, pb;
+            glu_pack_rows(w.data(), F.h_in_b[j].data(), H, (size_t)Cin * K5, wp, pb);      // as for the plain in-layers
+            WJ[fi][j] = std::move(wp); BJ[fi][j] = std::move(pb);
+        }
+    };
+    auto one_flow = [&](int fi) {
+        Flow &F = flows[fi];
+        // first launch of the flow when it has no predecessor in processing order: h0 = pre(x0) from the full latent
+        WP1[fi].assign((size_t)H * I, 0.f); BP1[fi] = F.h_pre_b;
+        for (int r = 0; r < H; r++) for (int q = 0; q < half; q++) WP1[fi][(size_t)r * I + x0_row0(F) + q] = F.h_pre_w[(size_t)r * half + q];
+        // composed post over [a_0 .. a_{n-1}]: P (sum_j S_j a_j + s_j) + p, rows = the x1 half in its physical order
+        const int KA = nl * H, Kin = KA + I;                       // last launch's input: [a_0 .. a_{n-1} | z]
+        std::vector<double> pc((size_t)half * KA, 0.0), pcb(half, 0.0);
+        for (int r = 0; r < half; r++) {
+            double bacc = F.h_post_b[r];
+            for (int j = 0; j < nl; j++) {
+                const int row0 = j < nl - 1 ? H : 0;               // skip rows of res_skip layer j
+                const float *S = F.h_rs_w[j].data() + (size_t)row0 * H, *sb = F.h_rs_b[j].data() + row0;
+                for (int h = 0; h < H; h++) {
+                    const double v = F.h_post_w[(size_t)r * H + h];
+                    for (int c = 0; c < H; c++) pc[(size_t)r * KA + (size_t)j * H + c] += v * S[(size_t)h * H + c];
+                    bacc += v * sb[h];
+                }
+            }
+            pcb[r] = bacc;
+        }
+        // last launch of the flow, input [A | z] (K = n H + I): z_next = z - [0 ; post(A)] on the x1 rows, and for the next flow in processing order
+        //   h0_next = pre_next(z_next) = Wn z - Wn[:, x1 rows] post(A) + (bn - Wn[:, x1 rows] p)        (two phases of one launch: same input, two outputs)
+        const bool has_next = fi > 0;
+        const int r1 = x1_row0(F);
+        std::vector<double> wz((size_t)I * Kin, 0.0), bz(I, 0.0);
+        for (int c = 0; c < I; c++) wz[(size_t)c * Kin + KA + c] = 1.0;
+        for (int r = 0; r < half; r++) {
+            for (int q = 0; q < KA; q++) wz[(size_t)(r1 + r) * Kin + q] = -pc[(size_t)r * KA + q];
+            bz[r1 + r] = -pcb[r];
+        }
+        WM[fi].resize(wz.size()); BM[fi].resize(I);
+        for (size_t q = 0; q < wz.size(); q++) WM[fi][q] = (float)wz[q];
+        for (int r = 0; r < I; r++) BM[fi][r] = (float)bz[r];
+        if (has_next) {
+            const Flow &N = flows[fi - 1];
+            std::vector<double> wh((size_t)H * Kin, 0.0);
+            WH[fi].resize(wh.size()); BH[fi].resize(H);
+            for (int r = 0; r < H; r++) {
+                double bacc = N.h_pre_b[r];
+                for (int q = 0; q < half; q++) {
+                    const double v = N.h_pre_w[(size_t)r * half + q];
+                    const int zc = x0_row0(N) + q;                 // latent row this weight multiplies
+                    wh[(size_t)r * Kin + KA + zc] += v;
+                    if (zc >= r1 && zc < r1 + half) {
+                        const int pr = zc - r1;
+                        for (int c = 0; c < KA; c++) wh[(size_t)r * Kin + c] -= v * pc[(size_t)pr * KA + c];
+                        bacc -= v * pcb[pr];
+                    }
+                }
+                BH[fi][r] = (float)bacc;
+            }
+            for (size_t q = 0; q < wh.size(); q++) WH[fi][q] = (float)wh[q];
+        }
+    };
+    for (int i = 0; i < nfl; i++) { WJ[i].resize(nl); BJ[i].resize(nl); }
+    std::vector<std::thread> th;
+    for (int i = 0; i < nfl; i++) {
+        th.emplace_back([&, i]() { one_flow(i); });
+        for (int j = 0; j < nl; j++) th.emplace_back([&, i, j]() { in_layer(i, j); });
+    }
+    for (auto &t : th) t.join();
+    for (int i = 0; i < nfl; i++) {
+        Flow &F = flows[i];
+        F.pre1 = prep_conv(WP1[i].data(), BP1[i].data(), H, I, 1, 1);
+        for (int j = 0; j < nl; j++) F.inc.push_back(prep_conv(WJ[i][j].data(), BJ[i][j].data(), 2 * H, 16 + H * (j + 1), K5, 1));
+        F.postc = prep_conv(WM[i].data(), BM[i].data(), I, nl * H + I, 1, 1);
+        if (i > 0) {
+            F.posth = prep_conv(WH[i].data(), BH[i].data(), H, nl * H + I, 1, 1);
+            std::vector<float> pb(BH[i]); pb.insert(pb.end(), BM[i].begin(), BM[i].end());
+            F.pair_bias = upload_f(pb); owned.push_back(F.pair_bias);
+        }
+    }
+    composed = true;
+}
+ModelSY::~ModelSY()
+{
+    free_conv(phone); free_conv(proj); free_conv(dec_pre); free_conv(dec_post);
+    for (auto &L : layers) { free_conv(L.qkv); free_conv(L.o); free_conv(L.ff1); free_conv(L.ff2); free_conv(L.qkv_f); if (L.qkv_wsum) wfree(L.qkv_wsum); }
+    free_conv(proj_f); if (proj_wsum) wfree(proj_wsum);
+    for (auto &F : flows) { free_conv(F.pre); free_conv(F.post); for (auto &c : F.in) free_conv(c); for (auto &c : F.rs) free_conv(c); if (composed) { free_conv(F.pre1); free_conv(F.postc); free_conv(F.posth); for (auto &c : F.inc) free_conv(c); } }
+    for (auto &c : ups) free_conv(c);
+    for (auto &c : ncs) free_conv(c);
+    for (auto &s : rbs) for (auto &ch : s) for (auto &pr : ch) { free_conv(pr.first); free_conv(pr.second); }
+    for (float *p : owned) wfree(p);
+}
 
 // ------------------------------- synthesizer ------------------------------------------
 // NSF harmonic source (SineGen + Linear(1, 1) + tanh) of pitchf [B][R] into src [B][1][R upp]; the noise is drawn per stream from st / cp (stream_id, chunk, seed);

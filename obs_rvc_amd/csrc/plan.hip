@@ -2,6 +2,7 @@
 // order), and the translation of a layer (Conv1d / ConvT1d / Conv2d / ConvT2d / Linear, fused variants) into implicit-GEMM launches: tile
 // choice, in-workgroup K split, streams folded into N, staged-tile convolution, 32x32x2 throughput kernels.
 #include "engine_int.h"
+#include "plan_ops.hip.h"
 #include <chrono>
 
 namespace rvc {

@@ -10,8 +10,6 @@
 
 namespace rvc {
 
-constexpr double PROTECT_OFF = 0.5;       // the setting lives in [0, PROTECT_OFF]; PROTECT_OFF and above = no protection (upstream: `protect < 0.5` enables it)
-
 // the ContentVec column behind row r of `phone`: feats[min((skip_head + r) / 2, T - 1)]   (rvc.rs:99-109 + 155; Q2, Q8).  gather_phone_kernel and
 // protect_mix_kernel both go through this, so that what protection calls "raw" is what the gather wrote
 __device__ __forceinline__ int phone_src_col(int skip_head, int r, int T)

@@ -1,6 +1,7 @@
 // retrieval.hip -- flat-L2 index retrieval (rvc/src/rvc.rs:159 is a TODO in the reference; definition: SURVEY.md Appendix A.4, BASELINE configs 3-5):
 // index load and its device-side layouts, the search section of an infer plan, the index entry points of the C ABI.
 #include "engine_int.h"
+#include "knn.hip.h"
 
 namespace rvc {
 

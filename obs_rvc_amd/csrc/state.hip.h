@@ -1,4 +1,4 @@
-// state.hip.h -- per-stream state, per-call parameters and the counter-based noise generator (kernels.hip.h).
+// state.hip.h -- per-stream state, per-call parameters and the counter-based noise generator.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,7 +20,7 @@ struct StreamState {        // one per stream
     uint32_t stream_id;
     int status;             // 0 ok, else a set of ST_* bits (atomicOr by the kernels, read and cleared by the host: engine.hip check_status)
     float uppower;          // this stream's 2^(pitch_shift / 12), truncating division (rvc.rs:121), times its formant multiplier 2^(-phi / 12): every stream is its own caller
-    // formant stage of this stream (formant.hip.h formant_resample_kernel; written by the host with the multiplier, engine.hip push_call_params)
+    // formant stage of this stream (synth.hip.h formant_resample_kernel; written by the host with the multiplier, engine.hip push_call_params)
     const float *f_tab;     // [n][kt] filter rows (the engine's table cache), nullptr when f_ident
     const int *f_kb;        // [n] first tap of each row
     int f_o, f_n, f_w, f_kt, f_nx, f_ident;     // ratio o -> n, left width, taps per row, valid input samples (R upp_res), 1 = copy
@@ -33,6 +33,8 @@ struct StreamState {        // one per stream
     // 0.5 = off.  A zero-filled state therefore means FULL protection: whoever builds a state by hand sets the word (debug.hip does)
     float protect;
 };
+#define KNN_K 4                            // neighbours per retrieval query (knn.hip.h; rccl_bcast.hip.h refuses a smaller index)
+constexpr double PROTECT_OFF = 0.5;       // the setting lives in [0, PROTECT_OFF]; PROTECT_OFF and above = no protection (upstream: `protect < 0.5` enables it)
 
 // status bits of a stream (several kernels of one chunk may report; a plain store would lose the earlier report)
 enum { ST_PANIC = 1,          // the reference would have panicked (rmvpe.rs:124 out-of-bounds gather)

@@ -69,6 +69,10 @@ def test_entry_points_are_mirrored():
     for name in ("rvc_set_protect", "rvc_set_protect_stream"):
         assert name in _native.SYMBOLS and re.search(r"\b%s\s*\(" % name, hdr) and re.search(r"pub fn %s\s*\(" % name, ffi), name
     assert re.search(r"pub fn set_protect\s*\(", shim) and hasattr(RvcInfer, "set_protect")
-    assert "protect.hip.h" in _native.SOURCES and "protect.hip.h" in _native._INT_DEPS
+    # the header is hashed into the library, and into the object of every unit that reaches it through its #include lines: the unit that builds the plan op for one
+    assert "protect.hip.h" in _native.SOURCES
+    reach = [src for src, _, _ in _native.UNITS if "protect.hip.h" in _native._include_closure(src)]
+    assert reach and "engine.hip" in reach
+    assert all("protect.hip.h" in deps for src, _, deps in _native.UNITS if src in reach)
     dbg = open(os.path.join(ROOT, "include", "rvc_mi355x_debug.h")).read()
     assert re.search(r"\brvc_debug_protect\s*\(", dbg)

@@ -1,4 +1,4 @@
-// knn_probe.hip -- TEST INFRASTRUCTURE: the one-launch retrieval kernel (knn_scan_select_kernel of kernels.hip.h) alone, on BASELINE's index
+// knn_probe.hip -- TEST INFRASTRUCTURE: the one-launch retrieval kernel (knn_scan_select_kernel of knn.hip.h) alone, on BASELINE's index
 // (100 k x 768 fp32, N(0, 0.35^2), 11 queries): launch time with the index cold (1 GiB of other traffic between launches), wall-clock stamps
 // of the phases (scan end, ticket, all arrived, lists read, exact re-rank, end), and the hits against the exhaustive definition
 // (knn_scan_kernel + knn_merge_blend_kernel of the same header).
@@ -11,7 +11,7 @@
 #include <cmath>
 #include <algorithm>
 #include <random>
-#include "kernels.hip.h"
+#include "knn.hip.h"
 #define CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 using namespace rvc;
 
