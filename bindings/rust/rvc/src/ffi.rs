@@ -13,6 +13,10 @@ pub struct RvcResampler {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct RvcDenoiser {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct RvcSession {
     _private: [u8; 0],
 }
@@ -38,6 +42,8 @@ pub const RVC_PANIC: c_int = 6;
 pub const RVC_RCCL_UNIQUE_ID_BYTES: usize = 128;
 pub const RVC_F0_RMVPE: c_int = 1;
 pub const RVC_F0_YIN: c_int = 2;
+pub const RVC_DENOISE_INPUT: c_int = 0;
+pub const RVC_DENOISE_OUTPUT: c_int = 1;
 
 extern "C" {
     // ---- RvcInfer (rvc/src/rvc.rs:30-220)
@@ -137,6 +143,15 @@ extern "C" {
     pub fn rvc_resampler_reset(r: *mut RvcResampler);
     pub fn rvc_resampler_process(r: *mut RvcResampler, input: *const c_float, n_in: usize, out: *mut c_float, cap: usize, n_out: *mut usize) -> c_int;
     pub fn rvc_resampler_process_device(r: *mut RvcResampler, d_in: *const c_void, d_out: *mut c_void, sync: c_int) -> c_int;
+    // streaming spectral-gate noise reduction: strength in [0, 1] (0 = off, undelayed), threshold in [0, 16]; 10 ms delay; stream -1 = all
+    pub fn rvc_denoiser_create(e: *mut RvcEngine, sample_rate: usize, n_streams: c_int, out: *mut *mut RvcDenoiser) -> c_int;
+    pub fn rvc_denoiser_destroy(d: *mut RvcDenoiser);
+    pub fn rvc_denoiser_reset(d: *mut RvcDenoiser);
+    pub fn rvc_denoiser_set(d: *mut RvcDenoiser, stream: c_int, strength: c_double, threshold: c_double) -> c_int;
+    pub fn rvc_denoiser_latency(d: *mut RvcDenoiser) -> usize;
+    pub fn rvc_denoiser_process(d: *mut RvcDenoiser, input: *const c_float, n: usize, out: *mut c_float) -> c_int;
+    pub fn rvc_denoiser_process_device(d: *mut RvcDenoiser, d_in: *const c_void, d_out: *mut c_void, n: usize, in_stride: usize, out_stride: usize,
+                                       sync: c_int) -> c_int;
     pub fn rvc_session_create(e: *mut RvcEngine, sample_rate: usize, sample_length: c_double, crossfade_length: c_double,
                               extra_inference_time: c_double, model_output_sample_rate: usize, pitch_shift: i32, rms_mix_rate: c_double,
                               skip_inference: c_int, out: *mut *mut RvcSession) -> c_int;
@@ -148,6 +163,8 @@ extern "C" {
     pub fn rvc_session_set_crossfade_stream(s: *mut RvcSession, stream: c_int, mode: c_int) -> c_int;
     pub fn rvc_session_set_input_gate(s: *mut RvcSession, threshold_db: c_double) -> c_int;
     pub fn rvc_session_set_input_gate_stream(s: *mut RvcSession, stream: c_int, threshold_db: c_double) -> c_int;
+    pub fn rvc_session_set_noise_reduction(s: *mut RvcSession, side: c_int, strength: c_double, threshold: c_double) -> c_int;
+    pub fn rvc_session_set_noise_reduction_stream(s: *mut RvcSession, stream: c_int, side: c_int, strength: c_double, threshold: c_double) -> c_int;
     pub fn rvc_session_geometry(s: *mut RvcSession, out: *mut i32);
     pub fn rvc_session_process(s: *mut RvcSession, input_sample: *const c_float, n: usize, output: *mut c_float, cap: usize,
                                sola_offset: *mut usize) -> c_int;

@@ -260,6 +260,34 @@ rvc_status rvc_resampler_process(rvc_resampler *r, const float *in, size_t n_in,
 /* device-resident variant (HIP device pointers, engine's stream; no sync unless sync != 0) */
 rvc_status rvc_resampler_process_device(rvc_resampler *r, const void *d_in, void *d_out, int sync);
 
+/* ---- streaming spectral-gate noise reduction (the upstream real-time client's input / output noise reduction; DESIGN.md "Spectral-gate noise reduction") ---- */
+/* No counterpart in the plugin.  Causal, no look-ahead, 10 ms delay.  Per stream at sample_rate (a multiple of 100, at most 192000: the frame must fit
+ * the kernels' LDS budget, N <= 3840): zc = sample_rate / 100 is the hop, N = 2 zc the frame (50 Hz bins), K = zc + 1 bins, w[j] = sin(pi (j + 0.5) / N)
+ * the analysis and synthesis window (w[j]^2 + w[j + zc]^2 = 1: an all-ones mask reconstructs the input).  Input = hop blocks x_0, x_1, ... with x_{-1} = 0,
+ * frame m = concat(x_{m-1}, x_m); state per stream: S[k] = 0, g[k] = 0, the previous block, the previous frame's synthesis tail.  Frame m, bin k:
+ *   1. X[k] = sum_j w[j] frame[j] exp(-2 pi i k j / N), M = |X[k]|
+ *   2. slope = (M - S[k]) / max(S[k], 1e-8), then S[k] = a S[k] + (1 - a) M, a = (float)exp(-10 / 200)        (200 ms noise floor)
+ *   3. g0[k] = 1 / (1 + exp(-(slope - threshold) / 0.1))
+ *   4. g1[k] = sum_{|d| <= 10, 0 <= k + d < K} t[d] g0[k + d] / sum_{same d} t[d], t[d] = 11 - |d|             (+-500 Hz triangle)
+ *   5. g[k] = max(g1[k], b g[k]), b = (float)exp(-10 / 50)                                                     (50 ms release hold)
+ *   6. Y[k] = (strength g[k] + (1 - strength)) X[k]
+ *   7. f = w . irfft_N(Y); output block m = f_{m-1}[zc:] + f_m[:zc] = the gated x_{m-1}: the input delayed by zc samples.
+ * strength in [0, 1], 0 = off and the default: that stream is copied UNDELAYED, bit for bit, and its state is left alone; threshold in [0, 16], default 2.
+ * NaN / out of range, a stream out of range, n not a positive multiple of zc (or more than 4096 hops), an unsupported sample_rate: RVC_SHAPE with a message.  A stream's result
+ * depends neither on the other streams nor on how its signal is cut into calls.  The denoiser runs on the engine's device and stream and must be
+ * destroyed before the engine. */
+typedef struct rvc_denoiser rvc_denoiser;
+rvc_status rvc_denoiser_create(rvc_engine *e, size_t sample_rate, int n_streams, rvc_denoiser **out);
+void rvc_denoiser_destroy(rvc_denoiser *d);
+void rvc_denoiser_reset(rvc_denoiser *d);                      /* zero every stream's state; the settings stay */
+rvc_status rvc_denoiser_set(rvc_denoiser *d, int stream /* -1 = all */, double strength, double threshold);
+size_t rvc_denoiser_latency(rvc_denoiser *d);                  /* zc: samples of delay of a stream whose strength is > 0 */
+/* host buffers in [n_streams][n], out [n_streams][n] */
+rvc_status rvc_denoiser_process(rvc_denoiser *d, const float *in, size_t n, float *out);
+/* device-resident variant (HIP device pointers, stream b at d_in + b in_stride / d_out + b out_stride floats; engine's stream; no sync unless sync != 0);
+ * d_in == d_out with equal strides is allowed */
+rvc_status rvc_denoiser_process_device(rvc_denoiser *d, const void *d_in, void *d_out, size_t n, size_t in_stride, size_t out_stride, int sync);
+
 /* ---- the plugin's per-chunk state machine as one call (SURVEY.md section 8 rows f1-f3 chained, all buffers resident in HBM) ---- */
 /* `create`/`update` + `process_one_frame` of the filter (obs-rvc/src/lib.rs:181-260, 659-795): host-rate ring, 16 kHz ring, both
  * resamplers, RvcInfer::infer, RMS envelope mixing and SOLA.  One H2D copy (the new chunk), one D2H copy (the finished frame) and
@@ -285,6 +313,16 @@ rvc_status rvc_session_set_crossfade_stream(rvc_session *s, int stream, int mode
  * ungated input; it is kept from the first time any stream's gate is switched on (zeros before).  NaN, stream out of range: RVC_SHAPE. */
 rvc_status rvc_session_set_input_gate(rvc_session *s, double threshold_db);
 rvc_status rvc_session_set_input_gate_stream(rvc_session *s, int stream, double threshold_db);
+/* Spectral-gate noise reduction (rvc_denoiser above) inside the session, per side and per stream, every stream or one; strength 0 (the default) = off.
+ * RVC_DENOISE_INPUT sits between the input gate and the host-rate ring: the resampler, the model and the RMS-mix input see the denoised chunk, in
+ * pass-through mode too.  RVC_DENOISE_OUTPUT runs on the finished frame behind SOLA and the crossfade, at the host rate.  Each side's denoiser is created the
+ * first time a stream switches the side on and is not launched before that; streams at strength 0 keep their bits.  Switching a side on adds zc samples
+ * (10 ms) of delay on that side for that stream from that chunk on; delay and state survive rvc_session_set_params.  The chunk keeps its one H2D copy, one
+ * D2H copy and one synchronisation (the chunk after a setter call uploads the settings with one more of each).  NaN / out of range, unknown side, stream
+ * out of range, a session above 192000 Hz: RVC_SHAPE with a message. */
+enum { RVC_DENOISE_INPUT = 0, RVC_DENOISE_OUTPUT = 1 };
+rvc_status rvc_session_set_noise_reduction(rvc_session *s, int side, double strength, double threshold);
+rvc_status rvc_session_set_noise_reduction_stream(rvc_session *s, int stream, int side, double strength, double threshold);
 void rvc_session_geometry(rvc_session *s, int32_t out[10]);   /* the derived sizes of lib.rs:200-227 (see session.hip.h) */
 rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t n, float *output, size_t cap, size_t *sola_offset);
 

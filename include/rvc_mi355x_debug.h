@@ -143,6 +143,9 @@ int rvc_debug_formant_table(size_t o, size_t n, float *out, size_t cap, size_t *
 /* enable != 0: every later rvc_session_process records HIP events around its SOLA stage (offset search, blend, tail save; with the phase-vocoder
  * crossfade its analysis and synthesis launches); returns the milliseconds of the last chunk processed with the events on (0 before one) */
 float rvc_debug_session_sola_ms(rvc_session *s, int enable);
+/* the same around the session's two noise-reduction stages (rvc_session_set_noise_reduction): the milliseconds of both sides added, of the last chunk
+ * processed with the events on while a side was in use (0 before one) */
+float rvc_debug_session_denoise_ms(rvc_session *s, int enable);
 
 #ifdef __cplusplus
 }

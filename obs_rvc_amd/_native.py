@@ -32,6 +32,8 @@ SYMBOLS = [
     "rvc_set_f0_median", "rvc_set_f0_median_stream", "rvc_set_f0_snap", "rvc_set_f0_snap_stream",
     "rvc_set_protect", "rvc_set_protect_stream",
     "rvc_sola_step_x", "rvc_input_gate", "rvc_session_set_crossfade", "rvc_session_set_crossfade_stream", "rvc_session_set_input_gate", "rvc_session_set_input_gate_stream",
+    "rvc_denoiser_create", "rvc_denoiser_destroy", "rvc_denoiser_reset", "rvc_denoiser_set", "rvc_denoiser_latency", "rvc_denoiser_process", "rvc_denoiser_process_device",
+    "rvc_session_set_noise_reduction", "rvc_session_set_noise_reduction_stream",
 ]
 
 
@@ -301,6 +303,21 @@ def lib():
         L.rvc_session_set_input_gate_stream.argtypes = [vp, C.c_int, C.c_double]
         L.rvc_debug_session_sola_ms.argtypes = [vp, C.c_int]
         L.rvc_debug_session_sola_ms.restype = C.c_float
+    if hasattr(L, "rvc_denoiser_create") or not override:
+        L.rvc_denoiser_create.argtypes = [vp, sz, C.c_int, C.POINTER(vp)]
+        L.rvc_denoiser_destroy.argtypes = [vp]
+        L.rvc_denoiser_destroy.restype = None
+        L.rvc_denoiser_reset.argtypes = [vp]
+        L.rvc_denoiser_reset.restype = None
+        L.rvc_denoiser_set.argtypes = [vp, C.c_int, C.c_double, C.c_double]
+        L.rvc_denoiser_latency.argtypes = [vp]
+        L.rvc_denoiser_latency.restype = sz
+        L.rvc_denoiser_process.argtypes = [vp, fp, sz, fp]
+        L.rvc_denoiser_process_device.argtypes = [vp, vp, vp, sz, sz, sz, C.c_int]
+        L.rvc_session_set_noise_reduction.argtypes = [vp, C.c_int, C.c_double, C.c_double]
+        L.rvc_session_set_noise_reduction_stream.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double]
+        L.rvc_debug_session_denoise_ms.argtypes = [vp, C.c_int]
+        L.rvc_debug_session_denoise_ms.restype = C.c_float
     if hasattr(L, "rvc_load_f0_method") or not override:
         L.rvc_load_f0_method.argtypes = [vp, C.c_int]
         L.rvc_f0_method.argtypes = [vp]

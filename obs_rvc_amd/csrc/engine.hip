@@ -1424,5 +1424,6 @@ rvc_status rvc_get_tap(rvc_engine *e, const char *name, float *out, size_t cap, 
 }  // extern "C"
 
 #include "resample.hip.h"
+#include "denoise.hip.h"
 #include "session.hip.h"
 #include "rccl_bcast.hip.h"

@@ -9,6 +9,9 @@
 //   -> RMS envelope mixing -> SOLA search / crossfade / tail save.
 // Two per-stream stages of this project's own (crossfade.hip.h, DESIGN.md "Phase-vocoder crossfade and input gate"), both off by default: the input
 // gate in front of shift+append and the phase-vocoder blend (analysis + synthesis launches) behind the SOLA search.
+// Spectral-gate noise reduction (denoise.hip.h, DESIGN.md "Spectral-gate noise reduction"), per stream and per side, off by default: the input side
+// sits between the input gate and shift+append, the output side behind the SOLA / phase-vocoder launches on the finished frame.  Each side owns
+// a denoiser that is created the first time a stream switches the side on and is not launched before that.
 #pragma once
 
 namespace rvc {
@@ -57,6 +60,11 @@ struct rvc_session {
     // input gate: threshold per stream (-inf = off), the ungated history (ping-pong) and the gated chunk.  The stage is launched from the first
     // time any stream's gate is switched on; until then the history is the zeros of creation
     std::vector<float> gate_thr; float *d_gate_thr = nullptr, *d_hist[2] = {nullptr, nullptr}, *d_gated = nullptr; bool gate_dirty = false, gate_used = false; int par_h = 0;
+    // noise reduction, [RVC_DENOISE_INPUT | RVC_DENOISE_OUTPUT]: the settings per stream, the side's denoiser (null until a stream switches the side on) and
+    // the buffer it writes (the denoised chunk in front of the ring / the denoised frame that is copied to the host)
+    std::vector<double> dn_strength[2], dn_threshold[2]; rvc_denoiser *dn[2] = {nullptr, nullptr}; float *d_dn[2] = {nullptr, nullptr};
+    // rvc_debug_session_denoise_ms: HIP events around both noise-reduction stages
+    bool time_dn = false; hipEvent_t ev_dn[4] = {nullptr, nullptr, nullptr, nullptr}; float dn_ms = 0.f;
     // rvc_debug_session_sola_ms: HIP events around the SOLA stage
     bool time_sola = false; hipEvent_t ev_sola[2] = {nullptr, nullptr}; float sola_ms = 0.f;
 };
@@ -69,6 +77,8 @@ void rvc_session_destroy(rvc_session *s)
     (void)hipSetDevice(s->e->device);
     (void)hipStreamSynchronize(s->e->stream);
     rvc_resampler_destroy(s->down); rvc_resampler_destroy(s->up);
+    for (int side = 0; side < 2; side++) { rvc_denoiser_destroy(s->dn[side]); (void)hipFree(s->d_dn[side]); }
+    for (hipEvent_t ev : s->ev_dn) if (ev) (void)hipEventDestroy(ev);
     for (float *p : {s->d_in[0], s->d_in[1], s->d_in16[0], s->d_in16[1], s->d_chunk, s->d_down, s->d_model, s->d_up, s->d_rms, s->d_sola, s->d_frame, s->d_cor}) (void)hipFree(p);
     (void)hipFree(s->d_off); (void)hipFree(s->d_mixpow);
     for (float *p : {s->d_pva, s->d_pvtab, s->d_pvspec, s->d_gate_thr, s->d_hist[0], s->d_hist[1], s->d_gated}) (void)hipFree(p);
@@ -128,6 +138,7 @@ rvc_status rvc_session_create(rvc_engine *e, size_t sample_rate, double sample_l
         HIPCHK(hipMalloc(&s->d_off, 4 * NB));
         HIPCHK(hipMalloc(&s->d_mixpow, 4 * NB));
         s->xfade.assign(s->B, RVC_CROSSFADE_LINEAR); s->gate_thr.assign(s->B, -INFINITY);
+        for (int side = 0; side < 2; side++) { s->dn_strength[side].assign(s->B, 0.0); s->dn_threshold[side].assign(s->B, 2.0); }
         HIPCHK(hipMalloc(&s->d_xfade, 4 * NB)); HIPCHK(hipMemsetAsync(s->d_xfade, 0, 4 * NB, e->stream));
         if (s->sola_buffer_frame_size >= 2 && s->sola_buffer_frame_size <= PV_MAX_N) {
             std::vector<float> tab; pv_tables(s->sola_buffer_frame_size, tab);
@@ -185,6 +196,46 @@ static rvc_status session_set_gate(rvc_session *s, int first, int last, double t
 }
 rvc_status rvc_session_set_input_gate(rvc_session *s, double threshold_db) { return session_set_gate(s, 0, s ? s->B : 0, threshold_db); }
 rvc_status rvc_session_set_input_gate_stream(rvc_session *s, int stream, double threshold_db) { return session_set_gate(s, stream, stream + 1, threshold_db); }
+// noise reduction of one side, every stream or one.  The side's denoiser and its output buffer are created the first time a stream asks for strength > 0
+// (a stream at strength 0 passes bit for bit, undelayed); from the chunk after that call the stream's signal on that side is delayed by zc samples (10 ms)
+static rvc_status session_set_noise_reduction(rvc_session *s, int first, int last, int side, double strength, double threshold)
+{
+    if (!s) return RVC_BACKEND;
+    return guarded(s->e, [&]() {
+        if (first < 0 || last > s->B || first >= last) throw ShapeError("session: stream out of range");
+        if (side != RVC_DENOISE_INPUT && side != RVC_DENOISE_OUTPUT) throw ShapeError("session: unknown noise-reduction side");
+        denoiser_check(strength, threshold);
+        if (strength > 0.0 && !s->dn[side]) {
+            if (2 * s->zc > DN_MAX_N) throw ShapeError("session: noise reduction takes sample rates up to 192000");
+            if (!s->d_dn[side]) {
+                const size_t bytes = (size_t)s->B * std::max(s->sample_frame_size, 4) * 4;
+                HIPCHK(hipMalloc(&s->d_dn[side], bytes)); HIPCHK(hipMemsetAsync(s->d_dn[side], 0, bytes, s->e->stream));
+            }
+            rvc_status rc = denoiser_create_n(s->e, (size_t)s->sample_rate, s->B, s->sample_frame_size / s->zc, &s->dn[side]);
+            if (rc != RVC_OK) return rc;
+            for (int b = 0; b < s->B; b++) denoiser_set_range(s->dn[side], b, b + 1, s->dn_strength[side][b], s->dn_threshold[side][b]);
+        }
+        for (int b = first; b < last; b++) { s->dn_strength[side][b] = strength; s->dn_threshold[side][b] = threshold; }
+        if (s->dn[side]) denoiser_set_range(s->dn[side], first, last, strength, threshold);
+        return RVC_OK;
+    });
+}
+rvc_status rvc_session_set_noise_reduction(rvc_session *s, int side, double strength, double threshold)
+{
+    return session_set_noise_reduction(s, 0, s ? s->B : 0, side, strength, threshold);
+}
+rvc_status rvc_session_set_noise_reduction_stream(rvc_session *s, int stream, int side, double strength, double threshold)
+{
+    return session_set_noise_reduction(s, stream, stream + 1, side, strength, threshold);
+}
+// test / measurement hook (include/rvc_mi355x_debug.h): enable != 0 records HIP events around both noise-reduction stages of every later chunk; -> ms of the
+// last chunk (the two sides added; 0 while neither side is in use)
+float rvc_debug_session_denoise_ms(rvc_session *s, int enable)
+{
+    if (!s) return -1.f;
+    s->time_dn = enable != 0;
+    return s->dn_ms;
+}
 // test / measurement hook (include/rvc_mi355x_debug.h): enable != 0 records HIP events around the SOLA stage of every later chunk; -> ms of the last chunk
 float rvc_debug_session_sola_ms(rvc_session *s, int enable)
 {
@@ -224,6 +275,16 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
                                s->d_gate_thr, 0.f, s->zc, s->sample_frame_size, (long long)s->sample_frame_size, 3LL * s->zc);
             s->par_h ^= 1;
             chunk = s->d_gated;
+        }
+        // a side whose streams are all back at strength 0 is skipped like one that was never switched on
+        const bool dn_on[2] = {s->dn[0] && s->dn[0]->n_on > 0, s->dn[1] && s->dn[1]->n_on > 0};
+        const bool time_dn = s->time_dn && (dn_on[0] || dn_on[1]);
+        if (time_dn) for (hipEvent_t &ev : s->ev_dn) if (!ev) HIPCHK(hipEventCreate(&ev));
+        if (dn_on[RVC_DENOISE_INPUT]) {
+            if (time_dn) HIPCHK(hipEventRecord(s->ev_dn[0], st));
+            denoiser_launch(s->dn[0], chunk, s->d_dn[0], s->sample_frame_size, (long long)s->sample_frame_size, (long long)s->sample_frame_size);
+            if (time_dn) HIPCHK(hipEventRecord(s->ev_dn[1], st));
+            chunk = s->d_dn[0];
         }
         // lib.rs:661-665
         hipLaunchKernelGGL(ring_shift_append_kernel, dim3((s->input_buffer_size + T - 1) / T, B), dim3(T), 0, st, s->d_in[s->par], s->d_in[s->par ^ 1],
@@ -299,11 +360,22 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
                                s->d_xfade, 0, s->d_pvtab, s->d_pvspec, pn, s->sample_frame_size, up_bs, (long long)pn, (long long)pn, (long long)s->sample_frame_size);
         }
         if (s->time_sola) HIPCHK(hipEventRecord(s->ev_sola[1], st));
-        HIPCHK(hipMemcpy2DAsync(output, cap * 4, s->d_frame, (size_t)s->sample_frame_size * 4, (size_t)s->sample_frame_size * 4, B, hipMemcpyDeviceToHost, st));
+        const float *frame = s->d_frame;
+        if (dn_on[RVC_DENOISE_OUTPUT]) {
+            if (time_dn) HIPCHK(hipEventRecord(s->ev_dn[2], st));
+            denoiser_launch(s->dn[1], s->d_frame, s->d_dn[1], s->sample_frame_size, (long long)s->sample_frame_size, (long long)s->sample_frame_size);
+            if (time_dn) HIPCHK(hipEventRecord(s->ev_dn[3], st));
+            frame = s->d_dn[1];
+        }
+        HIPCHK(hipMemcpy2DAsync(output, cap * 4, frame, (size_t)s->sample_frame_size * 4, (size_t)s->sample_frame_size * 4, B, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(s->h_off.data(), s->d_off, 4 * (size_t)B, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
         if (s->time_sola) HIPCHK(hipEventElapsedTime(&s->sola_ms, s->ev_sola[0], s->ev_sola[1]));
+        if (time_dn) {
+            s->dn_ms = 0.f;
+            for (int side = 0; side < 2; side++) if (dn_on[side]) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, s->ev_dn[2 * side], s->ev_dn[2 * side + 1])); s->dn_ms += ms; }
+        }
         if (sola_offset) for (int b = 0; b < B; b++) sola_offset[b] = (size_t)s->h_off[b];
         return s->skip_inference ? RVC_OK : final_status(e);
     });

@@ -12,6 +12,8 @@ CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER = 0, 1
 F0_RMVPE, F0_YIN = 1, 2
 # input gate: a threshold at or below this many dB switches it off
 INPUT_GATE_OFF_DB = -60.0
+# sides of the session's spectral-gate noise reduction (include/rvc_mi355x.h RVC_DENOISE_*): in front of the host-rate ring, or on the finished frame
+DENOISE_INPUT, DENOISE_OUTPUT = 0, 1
 # scale snap (rvc_set_f0_snap): bit k of a mask allows pitch class k, C = 0, so MIDI note n is allowed iff bit n % 12 is set
 SCALE_CHROMATIC = 0xFFF
 _SCALE_STEPS = {"major": (0, 2, 4, 5, 7, 9, 11), "minor": (0, 2, 3, 5, 7, 8, 10), "chromatic": tuple(range(12))}

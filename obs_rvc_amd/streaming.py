@@ -160,6 +160,14 @@ class NativeStreamingSession:
         else:
             self._set(self._L.rvc_session_set_input_gate_stream(self._h, int(stream), float(threshold_db)))
 
+    def set_noise_reduction(self, side: int, strength: float, threshold: float = 2.0, stream: int = None) -> None:
+        """Spectral-gate noise reduction of one side (rvc_common.DENOISE_INPUT in front of the host-rate ring, DENOISE_OUTPUT on the finished frame), every
+        stream or one (rvc_session_set_noise_reduction[_stream]); strength 0 = off.  Switching a side on delays that stream by 10 ms on that side."""
+        if stream is None:
+            self._set(self._L.rvc_session_set_noise_reduction(self._h, int(side), float(strength), float(threshold)))
+        else:
+            self._set(self._L.rvc_session_set_noise_reduction_stream(self._h, int(stream), int(side), float(strength), float(threshold)))
+
     def process_one_frame(self, input_sample: np.ndarray) -> np.ndarray:
         """One chunk of one stream (shape (sample_frame_size,)) or of every stream of the engine ((streams, sample_frame_size))."""
         C = self._C
