@@ -128,6 +128,24 @@ typedef struct rvc_debug_rm_block_spec {
 } rvc_debug_rm_block_spec;
 int rvc_debug_rm_block(rvc_engine *e, const rvc_debug_rm_block_spec *s, const float *w1, const float *b1, const float *w2, const float *b2, const float *wsc,
                        const float *bsc, float *x, float *y, float *p, long long *geo);
+/* the retrieval section of an infer plan alone (obs_rvc_amd/csrc/retrieval.hip build_retrieval; DESIGN.md "Retrieval: what is tested") on an engine that has an
+ * index loaded (rvc_load_index on a bare rvc_create engine is enough): cv [streams][C][cv_ld], the ContentVec output in channel-major layout with T columns
+ * used; phone [streams][C][ph_ld], R columns written; idx / dist [streams][R][4]; overflow [streams], the many-stream path's flag word per stream (zeros on the
+ * other paths).  cv and phone are uploaded, the ops run `reps` times eagerly, or -- graph != 0 -- captured once and the graph replayed `reps` times, and both come
+ * back whole: the padding as it went in.  path 0: the planner's choice; 1: the plan's row-major exhaustive list (what a chunk runs after a hand-off time-out;
+ * RVC_SHAPE when the plan has none).  The other paths are forced with the hooks RVC_KNN_EXHAUSTIVE and RVC_KNN_NO_GEMM, the one-launch form's grid with
+ * RVC_KNN_WGS; rvc_debug_last_kernel then names what was queued: "knn_fused", "knn_gemm", "knn_exhaustive" or "knn_fallback".  Needs ph_ld >= R, cv_ld >= T,
+ * skip_head + R <= 2 T + 1, C = the index dimension, rate in [0, 1] (RVC_SHAPE otherwise).  RVC_BACKEND when a stream's status word was raised or the one-launch
+ * form left its ticket words non-zero.  0 = done, else an rvc_status. */
+typedef struct rvc_debug_retrieval_spec {
+    int streams, C, T, cv_ld, skip_head, R, ph_ld;
+    float rate;
+    int path, reps, graph;
+} rvc_debug_retrieval_spec;
+int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float *cv, float *phone, int *idx, float *dist, int *overflow);
+/* the device-side copies of the loaded index besides the row-major matrix: bit 0 = MFMA-fragment order, bit 1 = the transposed copy (built by the first plan that
+ * needs it; while it is absent, the exhaustive scan of a fallback list walks the row-major matrix); 0 without an index */
+int rvc_debug_index_layouts(rvc_engine *e);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);

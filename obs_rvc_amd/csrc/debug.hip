@@ -638,6 +638,65 @@ int rvc_debug_rm_block(rvc_engine *e, const rvc_debug_rm_block_spec *s, const fl
     });
 }
 
+// test aid: the retrieval section of an infer plan alone (retrieval.hip build_retrieval; tests/test_gpu_knn.py) on the caller's arrays with the caller's leading
+// dimensions.  The streams' states are a block of the aid's own (the one-launch form raises ST_KNN_TIMEOUT there), the engine's index rate is the spec's for
+// the duration of the call.
+int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float *cv, float *phone, int *idx, float *dist, int *overflow)
+{
+    return (int)guarded(e, [&]() {
+        if (!s || !cv || !phone || !idx || !dist || !overflow) throw ShapeError("retrieval spec");
+        const int B = s->streams, C = s->C, T = s->T, R = s->R;
+        if (B < 1 || B > 4096 || C < 1 || C > 4096 || R < 1 || R > 4096 || T < 1 || T > (1 << 20) || s->skip_head < 0 || s->ph_ld < R || s->cv_ld < T || s->ph_ld > (1 << 20) ||
+            s->cv_ld > (1 << 21) || (long long)s->skip_head + R > 2LL * T + 1 || s->reps < 1 || s->reps > 64 || s->path < 0 || s->path > 1 || !(s->rate >= 0.f && s->rate <= 1.f))
+            throw ShapeError("retrieval spec");
+        if (!e->d_index) throw ShapeError("no index loaded");
+        if (e->index_dim != (size_t)C) throw ShapeError("index dimension does not match the feature dimension");
+        Plan pl; pl.B = B;
+        Arena &A = pl.arena;
+        const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_hit = (size_t)B * R * KNN_K;
+        T1 cvo, ph;
+        cvo.p = A.floats(n_cv); cvo.B = B; cvo.C = C; cvo.T = T; cvo.ld = s->cv_ld; cvo.halo = 0; cvo.bs = (long long)C * s->cv_ld;
+        ph.p = A.floats(n_ph); ph.B = B; ph.C = C; ph.T = R; ph.ld = s->ph_ld; ph.halo = 0; ph.bs = (long long)C * s->ph_ld;
+        pl.cv_out = cvo;
+        std::vector<StreamState> hst(B);
+        for (int b = 0; b < B; b++) { memset(&hst[b], 0, sizeof(StreamState)); hst[b].protect = (float)PROTECT_OFF; }
+        StreamState *d_st = A.upload(hst);
+        // the plan is built against the aid's states and rate; the engine gets its own back on every exit
+        struct Swap {
+            rvc_engine *e; StreamState *st; int n; float rate;
+            Swap(rvc_engine *e_, StreamState *s_, int B_, float r_) : e(e_), st(e_->d_state), n(e_->n_streams), rate(e_->index_rate) { e->d_state = s_; e->n_streams = B_; e->index_rate = r_; }
+            ~Swap() { e->d_state = st; e->n_streams = n; e->index_rate = rate; }
+        } swap_guard(e, d_st, B, s->rate);
+        build_retrieval(e, pl, B, T, C, (uint32_t)s->skip_head, (uint32_t)R, ph);
+        if (s->path == 1) {
+            if (pl.knn_fallback.empty()) throw ShapeError("this plan has no fallback list");
+            pl.ops = OpList();
+            for (Op &o : pl.knn_fallback) pl.ops.push_back(o);
+            snprintf(g_last_kernel, sizeof g_last_kernel, "knn_fallback");
+        }
+        HIPCHK(hipMemcpy(cvo.p, cv, n_cv * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ph.p, phone, n_ph * 4, hipMemcpyHostToDevice));
+        run_ops(e, pl, s->reps, s->graph != 0);
+        HIPCHK(hipMemcpy(cv, cvo.p, n_cv * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(phone, ph.p, n_ph * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(idx, pl.d_knn_idx, n_hit * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist, pl.d_knn_dist, n_hit * sizeof(float), hipMemcpyDeviceToHost));
+        memset(overflow, 0, (size_t)B * sizeof(int));
+        if (pl.d_knn_overflow && s->path == 0) HIPCHK(hipMemcpy(overflow, pl.d_knn_overflow, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hst.data(), d_st, sizeof(StreamState) * B, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; b++) if (hst[b].status != 0) throw std::runtime_error("retrieval raised a stream's status word");
+        if (pl.knn_ticket && s->path == 0) {
+            std::vector<unsigned> tk(pl.knn_ticket_bytes / sizeof(unsigned));
+            HIPCHK(hipMemcpy(tk.data(), pl.knn_ticket, pl.knn_ticket_bytes, hipMemcpyDeviceToHost));
+            for (unsigned v : tk) if (v != 0) throw std::runtime_error("the one-launch retrieval left its ticket words non-zero");
+        }
+        return RVC_OK;
+    });
+}
+
+// test aid: which copies of the index exist (a fallback list built while the transposed copy is absent walks the row-major matrix)
+int rvc_debug_index_layouts(rvc_engine *e) { return e ? (e->d_indexF ? 1 : 0) | (e->d_indexT ? 2 : 0) : 0; }
+
 // the kernel family of the most recently queued implicit-GEMM launch (the first word of its description), the variant of the last op or the form of the
 // last ConvBlockRes: tests assert which path they exercised
 const char *rvc_debug_last_kernel(void)

@@ -264,6 +264,7 @@ struct Plan {
     float *d_f0 = nullptr;  // [B][Tm]
     float *d_feat = nullptr; // extract_feature output (1,2T+1,C)
     int *d_knn_idx = nullptr; float *d_knn_dist = nullptr;
+    int *d_knn_overflow = nullptr;                     // many-stream retrieval: one word per stream, raised when its candidate set overflowed (nullptr on the one-launch form)
     // one-launch retrieval: its ticket counters, and what runs instead when a selector gave up (engine.hip recover_retrieval)
     unsigned *knn_ticket = nullptr; size_t knn_ticket_bytes = 0;
     std::vector<Op> knn_fallback;

@@ -66,7 +66,8 @@ static __global__ __launch_bounds__(256) void knn_scan_kernel(KnnP p)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // per query: wave-level top-4 by repeated argmin over (distance, index)
     for (int j = 0; j < p.nq; j++) {
-        float d = i < p.n ? acc[j] : INFINITY; int id = i < p.n ? i : 0x7fffffff;
+        const bool ok = i < p.n && acc[j] < INFINITY;     // (a non-finite distance -- a NaN or an Inf in the query -- is no candidate: the definition's `acc < best` never holds for it, and the other paths report -1)
+        float d = ok ? acc[j] : INFINITY; int id = ok ? i : 0x7fffffff;
         for (int k = 0; k < KNN_K; k++) {
             float md = d; int mi = id;
 #pragma unroll

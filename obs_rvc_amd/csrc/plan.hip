@@ -16,7 +16,7 @@ static const TestHook kTestHooks[] = {
     {"RVC_G32L", true}, {"RVC_G32L_TALL", true}, {"RVC_G32L_TAB", true}, {"RVC_CONV32S_BUF", true}, {"RVC_FORCE_CHOICE", true},
     {"RVC_G32L_PANEL", true}, {"RVC_MEAN3", false}, {"RVC_RM_FUSE", false}, {"RVC_G2W_LN", false}, {"RVC_RELPOS_MFMA_MAX", false},
     {"RVC_ATTN_KERNEL", false}, {"RVC_RELPOS_KERNEL", false}, {"RVC_LN_KERNEL", false}, {"RVC_GRU_KERNEL", false}, {"RVC_CONV0_KERNEL", false},
-    {"RVC_YIN_CV_ALL_CUS", false}
+    {"RVC_YIN_CV_ALL_CUS", false}, {"RVC_KNN_WGS", true}
 };
 std::atomic<unsigned> g_opt_gen{0};       // bumped by every rvc_debug_option call: plans built under another generation are dropped (engine.hip get_plan)
 static std::mutex g_opt_mu;

@@ -37,9 +37,13 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         if (fast && !gemm_scan) {
             // one stream / few streams: ONE launch per group of 16 queries (knn_scan_select_kernel: scan, select, exact re-rank, blend)
             // three workgroups per CU of the stream this runs on, all resident at once (the ContentVec branch is CU-masked at <= 4 streams)
-            const unsigned knn_wgs = tune_env("RVC_KNN_WGS") ? (unsigned)atoi(tune_env("RVC_KNN_WGS")) : 3u * (unsigned)e->cv_cus;
+            // (test hook RVC_KNN_WGS: another grid for the same result -- tiles per workgroup and the KNN_FUSED_MAXG cap without a 100 k-row index; tuning builds
+            // also take it from the environment)
+            const int wgs_opt = test_opt_int("RVC_KNN_WGS", 0);
+            const unsigned knn_wgs = wgs_opt > 0 ? (unsigned)wgs_opt : 3u * (unsigned)e->cv_cus;
             const unsigned G = std::min(std::min((unsigned)((e->index_n + 63) / 64), std::max(knn_wgs / (unsigned)B, 64u)), (unsigned)KNN_FUSED_MAXG);
             const int ngroups = (nq + 15) / 16;
+            snprintf(g_last_kernel, sizeof g_last_kernel, "knn_fused");
             unsigned long long *lists = (unsigned long long *)pl.arena.alloc((size_t)ngroups * B * 16 * G * KNN_K * sizeof(unsigned long long));
             unsigned *ticket = (unsigned *)pl.arena.alloc((size_t)ngroups * B * 2 * sizeof(unsigned));
             HIPCHK(hipMemset(ticket, 0, (size_t)ngroups * B * 2 * sizeof(unsigned)));
@@ -88,6 +92,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         }
         // the exhaustive exact scan below runs for every stream (the definition), or only for streams whose candidate set overflowed
         int *d_overflow = (int *)pl.arena.alloc((size_t)B * sizeof(int));
+        pl.d_knn_overflow = d_overflow;
         if (fast) {
             float *d_approx = pl.arena.floats((size_t)Qpad * e->index_n);
             float *d_qf = pl.arena.floats((size_t)Qpad * C);
@@ -114,6 +119,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
             pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(knn_select_blend_kernel, sgrid, dim3(1024), slds, s, sp); });
         }
         build_exhaustive(e, pl, B, C, nq, nblk, first_raw, skip_head, R, T, phone, cvo, fast, d_overflow, d_q, cand_d, cand_i);
+        snprintf(g_last_kernel, sizeof g_last_kernel, fast ? "knn_gemm" : "knn_exhaustive");      // (behind add_conv1d, which notes the GEMM's own family)
 }
 
 // The exhaustive exact scan (= the definition) + merge + blend.  d_q == nullptr: the section also gathers its own queries and owns its buffers.

@@ -38,6 +38,11 @@ class RmBlockSpec(C.Structure):
     _fields_ = _ints("streams", "cin", "cout", "H", "W", "pool_in", "pool_out", "y_in_cat", "next", "rm_fuse", "graph", "reps")
 
 
+class RetrievalSpec(C.Structure):
+    """rvc_debug_retrieval_spec"""
+    _fields_ = _ints("streams", "C", "T", "cv_ld", "skip_head", "R", "ph_ld") + [("rate", C.c_float)] + _ints("path", "reps", "graph")
+
+
 class StreamState(C.Structure):
     """rvc_debug_stream_state (cache = cache_pitchf)"""
     _fields_ = [("uppower", C.c_float), ("stream_id", C.c_uint), ("chunk", C.c_uint), ("status", C.c_int), ("cache", C.c_float * 1024)]
@@ -51,6 +56,8 @@ def lib():
     L.rvc_debug_op.argtypes = [vp, C.POINTER(OpSpec)] + [vp] * 5 + [geo]
     L.rvc_debug_front.argtypes = [vp, C.POINTER(FrontSpec), vp, vp, C.POINTER(vp), C.POINTER(StreamState), geo]
     L.rvc_debug_rm_block.argtypes = [vp, C.POINTER(RmBlockSpec)] + [vp] * 9 + [geo]
+    L.rvc_debug_retrieval.argtypes = [vp, C.POINTER(RetrievalSpec)] + [vp] * 5
+    L.rvc_load_index.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
     L.rvc_debug_conv_check.argtypes = L.rvc_debug_conv2d_check.argtypes = [vp] + [C.c_int] * 7
     L.rvc_debug_conv_check.restype = L.rvc_debug_conv2d_check.restype = C.c_double
     L.rvc_debug_last_kernel.restype = C.c_char_p

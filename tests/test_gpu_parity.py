@@ -345,9 +345,10 @@ def test_retrieval_scan_exact_on_identical_queries():
     assert io2[0, :3].tolist() == [50, 100, 2000]
 
 
-def test_retrieval_degenerate_index_takes_exhaustive_fallback():
-    # thousands of exact duplicates: every one is within the error margin of the 4th-nearest, the candidate set overflows
-    # and the exhaustive exact scan must produce the same hits (ties broken by ascending index)
+def test_retrieval_degenerate_index_reranks_flagged_workgroups():
+    # thousands of exact duplicates: sixty copies of the nearest vector tie inside the error margin.  One stream runs the one-launch form, where nothing
+    # can overflow: every workgroup whose list the copies saturate is flagged and all of its vectors are re-ranked exactly; the hits must be the
+    # definition's (ties broken by ascending index).  The many-stream twin below is the one whose candidate set overflows
     from oracle import oracle as O
     z, ora, eng = _pair("tiny", taps=True)
     base = W.make_index(40, 48, seed=3)
@@ -361,6 +362,34 @@ def test_retrieval_degenerate_index_takes_exhaustive_fallback():
     assert np.array_equal(ie, io) and np.allclose(de, do, rtol=1e-4)
     assert (np.diff(ie, axis=1) == 40).all()               # the four smallest indices of one duplicated vector
     assert rms(ye - yo) < PCM_TOL
+
+
+def test_retrieval_degenerate_index_many_streams_take_the_overflow_fallback():
+    # the many-stream twin: 12 streams x 11 queries = 132 >= 128 go through the query GEMM and knn_select_blend_kernel, which holds at most KNN_CAND = 512
+    # candidates.  The same 40 vectors, each repeated 600 times: the copies of a query's nearest vector alone are 600 candidates with one approximate
+    # distance, so every stream overflows and knn_scan_kernel + knn_merge_blend_kernel recompute it inside a real plan (60 copies, as above, stay below 512).
+    # Hits of three streams against their own oracles, bit-exact; the four smallest indices of one duplicated vector
+    from oracle import oracle as O
+    from obs_rvc_amd.rvc import RvcInfer
+    z = zoo("tiny")
+    S = 12
+    base = W.make_index(40, 48, seed=3)
+    index = np.tile(base, (600, 1))
+    eng = RvcInfer(z["data"]); eng.load_contentvec(2); eng.load_f0(); eng.load_model(z["model"])
+    eng.set_streams(S); eng.set_noise_seed(1234, 0); eng.load_index(index); eng.set_index_rate(0.5)
+    xin = np.stack([voice_signal(g.input_buffer_16k_size, seed=30 + s) for s in range(S)])
+    ye = eng.infer_batch(xin, 2560, 12, 200, 21)
+    ie, de = eng.knn(rows_cap=S * 64)
+    assert ie.shape == (S * 21, 4)
+    assert (np.diff(ie, axis=1) == 40).all()
+    for s in (0, 5, 11):
+        o = O.OracleRvcInfer(z["data"]); o.load_contentvec(2); o.load_f0(1); o.load_model(z["model"]); o.set_noise_seed(1234, s)
+        o.load_index(index); o.set_index_rate(0.5)
+        yo = o.infer(xin[s], 2560, 12, 200, 21)
+        io, do = o.knn()
+        assert np.array_equal(ie[s * 21:(s + 1) * 21], io) and np.allclose(de[s * 21:(s + 1) * 21], do, rtol=1e-4), s
+        assert rms(ye[s] - yo) < PCM_TOL, s
+    eng.close()
 
 
 def test_retrieval_runs_of_duplicates_expand_the_workgroups_that_hide_them():
