@@ -109,6 +109,29 @@ typedef struct rvc_debug_protect_spec {
     int streams, C, R, T, skip_head, ph_ld, cv_ld, graph;
 } rvc_debug_protect_spec;
 int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *phone, const float *cv, const float *pitchf, const double *protect);
+/* the caller-side post-processing, the session's ring updates and a converter of several streams (obs_rvc_amd/csrc/chunk.hip.h, session.hip.h, resample.hip.h;
+ * DESIGN.md "Post-processing and resamplers: what is tested"), each launch queued as rvc_session_process queues it, on the caller's arrays with the caller's
+ * stream strides.  op: buffers buf[0..3] (each the WHOLE allocation, [streams][stride] floats, uploaded before the launches and downloaded after them: the
+ * padding comes back as it went in):
+ *   0 envelope mixing   buf0 input [in_bs] (n used); buf1 model output [out_bs] (n used, mixed in place); buf2 [r_bs]: the RMS track of the input (nf values) and,
+ *                       from nf on, that of the output, nf = (n + 2 (frame / 2) - frame) / hop + 1; mix_power [streams]: the exponent 1 - mix_rate per stream.  (The tracks are f64 on the device: buf2 is widened going up and rounded to float coming back.)
+ *   1 SOLA step, linear buf0 output [out_bs] (search + frame + sola_len used; blended in place); buf1 the saved tail [sola_bs] (sola_len; replaced); buf2 the
+ *                       frame [frame_bs]; buf3 the search + 1 normalised correlations [cor_bs]; offsets [streams]
+ *   2 ring_shift_append buf0 ring in [n]; buf1 ring out [n]; buf2 chunk [f]                       (contiguous: the kernel takes no strides)
+ *   3 ring16_update     buf0 ring in [n]; buf1 ring out [n]; buf2 the converter's output [x_bs]   (rings contiguous); skip, copy_begin as the session passes them
+ *   4 converter         a converter of `streams` streams for (rate_in, rate_out, chunk), `chunks` calls, destroyed before the hook returns:
+ *                       buf0 [chunks][streams][x_bs] (input_frames_next used), buf1 [chunks][streams][out_bs] (output_frames_max written)
+ * graph != 0: the launches are captured and the graph launched once.  RVC_SHAPE for a stride smaller than the row it strides over, search > 1023 and sizes
+ * out of range; nothing is queued then.  0 = done, else an rvc_status (rvc_last_error_message). */
+typedef struct rvc_debug_post_spec {
+    int op, streams, graph;
+    int n, frame, hop;                       /* 0 (n: samples); 1: frame; 2, 3: n = ring length */
+    int sola_len, search;                    /* 1 */
+    int f, skip, copy_begin;                 /* 2, 3 */
+    int rate_in, rate_out, chunk, chunks;    /* 4 */
+    long long in_bs, out_bs, r_bs, sola_bs, frame_bs, cor_bs, x_bs;
+} rvc_debug_post_spec;
+int rvc_debug_post(rvc_engine *e, const rvc_debug_post_spec *s, float *const *buf, const float *mix_power, int *offsets);
 /* one ConvBlockRes of RMVPE (conv3x3 + ReLU, conv3x3 + ReLU, + 1x1 shortcut or the input) queued as build_rmvpe queues it (obs_rvc_amd/csrc/model_rmvpe.hip:
  * make_res_block, add_rm_block_fused, add_res_block, add_avgpool2) and run `reps` times eagerly, or -- graph != 0 -- captured once and the graph replayed `reps`
  * times.  Weights in PyTorch layout: w1 [cout][cin][3][3], w2 [cout][cout][3][3], wsc [cout][cin] or NULL (identity shortcut: cin = cout), biases [cout].

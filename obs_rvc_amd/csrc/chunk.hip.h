@@ -62,42 +62,47 @@ static __global__ void rewind_chunk_kernel(StreamState *st, int B)
 // ------------------------------------------------------------------------------------
 // rt_utils.rs:94-103: zero-pad frame/2, square, windowed mean (window frame, step hop), sqrt.  One workgroup per frame.
 // (all post-processing kernels take a stream index in blockIdx.y -- blockIdx.x for post_sola_kernel -- and per-stream strides)
-static __global__ __launch_bounds__(256) void post_rms_kernel(const float *y, int n, int frame, int hop, float *out, long long y_bs, long long out_bs)
+// The envelope is evaluated in f64 from the f32 samples and rounded once, where the mixed sample is stored: the result is the correctly rounded
+// value of the definition, which no ordering of f32 roundings guarantees (DESIGN.md "Post-processing and resamplers: what is tested"; a few
+// dozen values per stream and chunk: the cost is not measurable).  The tracks stay f64 between the two kernels.
+static __global__ __launch_bounds__(256) void post_rms_kernel(const float *y, int n, int frame, int hop, double *out, long long y_bs, long long out_bs)
 {
-    __shared__ float red[16];
+    __shared__ double red[256];
     y += blockIdx.y * y_bs; out += blockIdx.y * out_bs;
     const int f = blockIdx.x, pad = frame / 2;
-    float s = 0.f;
+    double s = 0.0;
     for (int j = threadIdx.x; j < frame; j += 256) {
         int q = f * hop + j - pad;
-        float v = (q >= 0 && q < n) ? y[q] : 0.f;
+        const double v = (q >= 0 && q < n) ? (double)y[q] : 0.0;
         s += v * v;
     }
-    s = block_sum(s, red);
-    if (threadIdx.x == 0) out[f] = sqrtf(s / (float)frame);
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) out[f] = sqrt(red[0] / (double)frame);
 }
 // rt_utils.rs:105-117 evaluated at one index of the (size)-point output
-__device__ __forceinline__ float lerp_align_corners_at(const float *in, int n_in, int size, int i)
+__device__ __forceinline__ double lerp_align_corners_at(const double *in, int n_in, int size, int i)
 {
-    const float step = (float)(n_in - 1) / (float)(size - 1);
-    const float idx = (float)i * step;
-    int fl = (int)floorf(idx), ce = (int)ceilf(idx);
+    const double step = (double)(n_in - 1) / (double)(size - 1);
+    const double idx = (double)i * step;
+    int fl = (int)floor(idx), ce = (int)ceil(idx);
     fl = fl < 0 ? 0 : (fl > n_in - 1 ? n_in - 1 : fl);
     ce = ce < 0 ? 0 : (ce > n_in - 1 ? n_in - 1 : ce);
-    const float fr = idx - (float)fl;
-    return in[fl] * (1.0f - fr) + in[ce] * fr;
+    const double fr = idx - (double)fl;
+    return in[fl] * (1.0 - fr) + in[ce] * fr;
 }
 // rt_utils.rs:119-132
-// mix_power_v: per-stream exponent (or nullptr: mix_power for every stream); an exponent of 0 leaves the stream untouched (powf(x, 0) = 1)
-static __global__ void post_mix_kernel(float *out, int n, const float *r1, int n1, const float *r2, int n2, float mix_power, long long out_bs, long long r_bs, const float *mix_power_v)
+// mix_power_v: per-stream exponent (or nullptr: mix_power for every stream); an exponent of 0 leaves the stream untouched (pow(x, 0) = 1)
+static __global__ void post_mix_kernel(float *out, int n, const double *r1, int n1, const double *r2, int n2, float mix_power, long long out_bs, long long r_bs, const float *mix_power_v)
 {
     if (mix_power_v) mix_power = mix_power_v[blockIdx.y];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     out += blockIdx.y * out_bs; r1 += blockIdx.y * r_bs; r2 += blockIdx.y * r_bs;
-    const float a = lerp_align_corners_at(r1, n1, n + 1, i);
-    const float b = fmaxf(lerp_align_corners_at(r2, n2, n + 1, i), 1e-3f);
-    out[i] = out[i] * powf(a / b, mix_power);
+    const double a = lerp_align_corners_at(r1, n1, n + 1, i);
+    const double b = fmax(lerp_align_corners_at(r2, n2, n + 1, i), (double)1e-3f);       // (the reference's floor is the f32 constant)
+    out[i] = (float)((double)out[i] * pow(a / b, (double)mix_power));
 }
 // rt_utils.rs:60-90 + lib.rs:768-794 in one workgroup: normalised cross-correlation over search+1 lags (last maximum wins),
 // sin^2 crossfade with the previous tail, new tail saved, first `frame` samples returned.

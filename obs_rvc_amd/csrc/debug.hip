@@ -596,6 +596,110 @@ int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *pho
     });
 }
 
+// test aid: the caller-side post-processing, the session's ring updates and a converter of several streams (chunk.hip.h, session.hip.h, resample.hip.h;
+// tests/test_gpu_post.py) on the caller's arrays with the caller's stream strides, each launch queued as the session queues it (engine_int.h launch_post_* /
+// launch_ring_* / launch_resampler).  Every size is checked against the strides on the host before anything is queued.
+int rvc_debug_post(rvc_engine *e, const rvc_debug_post_spec *s, float *const *buf, const float *mix_power, int *offsets)
+{
+    return (int)guarded(e, [&]() {
+        if (!s || !buf) throw ShapeError("post spec");
+        const int B = s->streams, op = s->op;
+        const long long LIM = 1ll << 22;
+        auto in = [](long long v, long long lo, long long hi) { return v >= lo && v <= hi; };
+        if (op < 0 || op > 4 || !in(B, 1, 64)) throw ShapeError("post spec");
+        Plan pl; pl.B = B;
+        Arena &A = pl.arena;
+        A.set_chunk_min((size_t)1 << 20);
+        // the buffers of the op: floats per buffer (0 = unused); each is the whole allocation, uploaded before the launches and downloaded after them
+        long long size[4] = {0, 0, 0, 0};
+        float *d[4] = {nullptr, nullptr, nullptr, nullptr};
+        auto alloc_all = [&]() {
+            for (int j = 0; j < 4; j++) if (size[j] > 0) {
+                if (!buf[j]) throw ShapeError("post buffers");
+                d[j] = A.floats((size_t)size[j]);
+                HIPCHK(hipMemcpy(d[j], buf[j], (size_t)size[j] * 4, hipMemcpyHostToDevice));
+            }
+        };
+        struct Conv { rvc_resampler *r = nullptr; ~Conv() { rvc_resampler_destroy(r); } } conv;
+        int *d_off = nullptr; double *d_trk = nullptr; size_t n_trk = 0;
+        if (op == 0) {
+            const int n = s->n, frame = s->frame, hop = s->hop;
+            if (!in(n, 1, LIM) || !in(frame, 1, 1 << 16) || !in(hop, 1, 1 << 16) || !mix_power) throw ShapeError("post spec: envelope sizes");
+            const int nf = (n + 2 * (frame / 2) - frame) / hop + 1;
+            if (!in(s->in_bs, n, LIM) || !in(s->out_bs, n, LIM) || !in(s->r_bs, 2LL * nf, LIM)) throw ShapeError("post spec: a stride is smaller than its row");
+            size[0] = B * s->in_bs; size[1] = B * s->out_bs;
+            alloc_all();
+            if (!buf[2]) throw ShapeError("post buffers");
+            // the tracks are f64 on the device: the caller's floats go up widened and come back rounded (the padding is exact either way)
+            n_trk = (size_t)(B * s->r_bs);
+            std::vector<double> trk(buf[2], buf[2] + n_trk);
+            d_trk = A.upload(trk);
+            const float *d_mp = A.upload(std::vector<float>(mix_power, mix_power + B));
+            float *x = d[0], *y = d[1]; double *r = d_trk;
+            const long long in_bs = s->in_bs, out_bs = s->out_bs, r_bs = s->r_bs;
+            pl.ops.push_back([=](hipStream_t st) { launch_post_rms(st, B, x, n, frame, hop, nf, r, in_bs, r_bs); });
+            pl.ops.push_back([=](hipStream_t st) { launch_post_rms(st, B, y, n, frame, hop, nf, r + nf, out_bs, r_bs); });
+            pl.ops.push_back([=](hipStream_t st) { launch_post_mix(st, B, y, n, r, nf, r + nf, nf, 0.f, out_bs, r_bs, d_mp); });
+        } else if (op == 1) {
+            const int n = s->sola_len, search = s->search, frame = s->frame;
+            if (!in(search, 0, 1023)) throw ShapeError("post spec: sola search range too long");
+            if (!in(n, 1, 1 << 16) || !in(frame, 1, LIM) || !offsets) throw ShapeError("post spec: sola sizes");
+            if (!in(s->out_bs, (long long)search + frame + n, LIM) || !in(s->sola_bs, n, LIM) || !in(s->frame_bs, frame, LIM) || !in(s->cor_bs, search + 1, LIM))
+                throw ShapeError("post spec: a stride is smaller than its row");
+            size[0] = B * s->out_bs; size[1] = B * s->sola_bs; size[2] = B * s->frame_bs; size[3] = B * s->cor_bs;
+            alloc_all();
+            d_off = (int *)A.alloc((size_t)B * 4);
+            float *o = d[0], *sb = d[1], *fr = d[2], *cor = d[3];
+            const long long out_bs = s->out_bs, sola_bs = s->sola_bs, frame_bs = s->frame_bs, cor_bs = s->cor_bs;
+            pl.ops.push_back([=](hipStream_t st) { launch_post_sola_corr(st, B, o, sb, n, search, cor, out_bs, sola_bs, cor_bs); });
+            pl.ops.push_back([=](hipStream_t st) { launch_post_sola(st, B, o, sb, n, search, frame, fr, d_off, cor, out_bs, sola_bs, frame_bs, cor_bs, nullptr, 0, nullptr, 0LL); });
+        } else if (op == 2 || op == 3) {
+            const int n = s->n, f = s->f, skip = s->skip, cb = s->copy_begin;
+            if (!in(n, 1, LIM) || !in(f, 1, n)) throw ShapeError("post spec: ring sizes");
+            size[0] = size[1] = (long long)B * n;
+            if (op == 2) {
+                size[2] = (long long)B * f;
+                alloc_all();
+                const float *ri = d[0], *ch = d[2]; float *ro = d[1];
+                pl.ops.push_back([=](hipStream_t st) { launch_ring_shift_append(st, B, ri, ro, n, f, ch); });
+            } else {
+                // samples in front of copy_begin come from in[i + f]; [copy_begin, n) from res[skip ..]
+                if (!in(skip, 0, LIM) || !in(cb, 0, n - f)) throw ShapeError("post spec: ring sizes");
+                if (!in(s->x_bs, (long long)skip + n - cb, LIM)) throw ShapeError("post spec: a stride is smaller than its row");
+                size[2] = B * s->x_bs;
+                alloc_all();
+                const float *ri = d[0], *res = d[2]; float *ro = d[1];
+                const long long res_bs = s->x_bs;
+                pl.ops.push_back([=](hipStream_t st) { launch_ring16_update(st, B, ri, ro, n, f, res, skip, cb, res_bs); });
+            }
+        } else {
+            const int chunks = s->chunks;
+            if (!in(s->rate_in, 1, 1 << 20) || !in(s->rate_out, 1, 1 << 20) || !in(s->chunk, 1, 1 << 16) || !in(chunks, 1, 16)) throw ShapeError("post spec: converter sizes");
+            int fi = 0, fo = 0;
+            const rvc_status rc = resampler_create_streams(e, (size_t)s->rate_in, (size_t)s->rate_out, (size_t)s->chunk, B, &conv.r, &fi, &fo);
+            if (rc != RVC_OK) return rc;
+            if (!in(s->x_bs, fi, LIM) || !in(s->out_bs, fo, LIM)) throw ShapeError("post spec: a stride is smaller than its row");
+            size[0] = (long long)chunks * B * s->x_bs; size[1] = (long long)chunks * B * s->out_bs;
+            alloc_all();
+            rvc_resampler *r = conv.r;
+            const long long x_bs = s->x_bs, out_bs = s->out_bs;
+            for (int c = 0; c < chunks; c++) {
+                const float *x = d[0] + (long long)c * B * x_bs; float *y = d[1] + (long long)c * B * out_bs;
+                pl.ops.push_back([=](hipStream_t) { launch_resampler(r, x, y, x_bs, out_bs); });
+            }
+        }
+        run_ops(e, pl, 1, s->graph != 0);
+        for (int j = 0; j < 4; j++) if (size[j] > 0) HIPCHK(hipMemcpy(buf[j], d[j], (size_t)size[j] * 4, hipMemcpyDeviceToHost));
+        if (d_trk) {
+            std::vector<double> trk(n_trk);
+            HIPCHK(hipMemcpy(trk.data(), d_trk, n_trk * 8, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n_trk; i++) buf[2][i] = (float)trk[i];
+        }
+        if (d_off) HIPCHK(hipMemcpy(offsets, d_off, (size_t)B * 4, hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
 // test aid: one ConvBlockRes of RMVPE as build_rmvpe queues it -- rm_block_kernel when the block is eligible, else the implicit-GEMM launches, with the poolings
 // folded into the block or queued as launches of their own by the model's own dry runs (include/rvc_mi355x_debug.h, tests/test_gpu_rmblock.py).  As for
 // rvc_debug_layer, the caller owns every float of the tensors' allocations.

@@ -41,6 +41,27 @@ void launch_protect_mix(hipStream_t s, int B, const StreamState *st, const float
     hipLaunchKernelGGL(protect_mix_kernel, protect_grid(R, B, C), dim3(PROTECT_ROWS, PROTECT_LANES), 0, s, st, pitchf, cv, cv_cs, cv_bs, C, T, skip_head, R, phone, ph_cs, ph_bs);
 }
 
+// the caller-side post-processing launches (chunk.hip.h), B streams each: rvc_envelop_mixing, sola_step_host and rvc_session_process queue them through
+// these, and so does rvc_debug_post (debug.hip)
+void launch_post_rms(hipStream_t s, int B, const float *y, int n, int frame, int hop, int nf, double *out, long long y_bs, long long out_bs)
+{
+    hipLaunchKernelGGL(post_rms_kernel, dim3(nf, B), dim3(256), 0, s, y, n, frame, hop, out, y_bs, out_bs);
+}
+void launch_post_mix(hipStream_t s, int B, float *out, int n, const double *r1, int n1, const double *r2, int n2, float mix_power, long long out_bs, long long r_bs, const float *mix_power_v)
+{
+    hipLaunchKernelGGL(post_mix_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, out, n, r1, n1, r2, n2, mix_power, out_bs, r_bs, mix_power_v);
+}
+void launch_post_sola_corr(hipStream_t s, int B, const float *output, const float *sola, int sola_len, int search, float *cor, long long out_bs, long long sola_bs, long long cor_bs)
+{
+    hipLaunchKernelGGL(post_sola_corr_kernel, dim3((unsigned)(search + 4) / 4, B), dim3(256), 0, s, output, sola, sola_len, search, cor, out_bs, sola_bs, cor_bs);
+}
+void launch_post_sola(hipStream_t s, int B, float *output, float *sola, int sola_len, int search, int frame, float *frame_out, int *offset_out, const float *cor, long long out_bs,
+                      long long sola_bs, long long frame_bs, long long cor_bs, const int *mode_v, int mode_all, float *pv_a, long long pva_bs)
+{
+    hipLaunchKernelGGL(post_sola_kernel, dim3(B), dim3(1024), 0, s, output, sola, sola_len, search, frame, frame_out, offset_out, cor, out_bs, sola_bs, frame_bs, cor_bs,
+                       mode_v, mode_all, pv_a, pva_bs);
+}
+
 static void init_constants(rvc_engine *e)
 {
     init_kernel_attrs();
@@ -1282,13 +1303,13 @@ rvc_status rvc_envelop_mixing(rvc_engine *e, const float *input, float *output, 
         if (zc == 0 || output_len < zc) throw ShapeError("envelop_mixing: output shorter than one 10 ms hop");
         const int n = (int)output_len, frame = (int)(4 * zc), hop = (int)zc;
         const int nf = (n + 2 * (frame / 2) - frame) / hop + 1;
-        float *d_in, *d_out, *d_r;
-        HIPCHK(hipMalloc(&d_in, output_len * 4)); HIPCHK(hipMalloc(&d_out, output_len * 4)); HIPCHK(hipMalloc(&d_r, (size_t)2 * nf * 4));
+        float *d_in, *d_out; double *d_r;
+        HIPCHK(hipMalloc(&d_in, output_len * 4)); HIPCHK(hipMalloc(&d_out, output_len * 4)); HIPCHK(hipMalloc(&d_r, (size_t)2 * nf * 8));
         HIPCHK(hipMemcpyAsync(d_in, input, output_len * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipMemcpyAsync(d_out, output, output_len * 4, hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(post_rms_kernel, dim3(nf), dim3(256), 0, e->stream, d_in, n, frame, hop, d_r, 0LL, 0LL);
-        hipLaunchKernelGGL(post_rms_kernel, dim3(nf), dim3(256), 0, e->stream, d_out, n, frame, hop, d_r + nf, 0LL, 0LL);
-        hipLaunchKernelGGL(post_mix_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, d_out, n, d_r, nf, d_r + nf, nf, (float)(1.0 - mix_rate), 0LL, 0LL, (const float *)nullptr);
+        launch_post_rms(e->stream, 1, d_in, n, frame, hop, nf, d_r, 0LL, 0LL);
+        launch_post_rms(e->stream, 1, d_out, n, frame, hop, nf, d_r + nf, 0LL, 0LL);
+        launch_post_mix(e->stream, 1, d_out, n, d_r, nf, d_r + nf, nf, (float)(1.0 - mix_rate), 0LL, 0LL, nullptr);
         HIPCHK(hipMemcpyAsync(output, d_out, output_len * 4, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_r);
@@ -1319,9 +1340,8 @@ static rvc_status sola_step_host(rvc_engine *e, float *output, size_t output_len
         }
         HIPCHK(hipMemcpyAsync(d_out, output, output_len * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipMemcpyAsync(d_sola, sola_buffer, sola_len * 4, hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(post_sola_corr_kernel, dim3((unsigned)(search + 4) / 4), dim3(256), 0, e->stream, d_out, d_sola, (int)sola_len, (int)search, d_cor, 0LL, 0LL, 0LL);
-        hipLaunchKernelGGL(post_sola_kernel, dim3(1), dim3(1024), 0, e->stream, d_out, d_sola, (int)sola_len, (int)search, (int)frame, d_frame, d_off, d_cor, 0LL, 0LL, 0LL, 0LL,
-                           (const int *)nullptr, pv ? 1 : 0, d_pva, 0LL);
+        launch_post_sola_corr(e->stream, 1, d_out, d_sola, (int)sola_len, (int)search, d_cor, 0LL, 0LL, 0LL);
+        launch_post_sola(e->stream, 1, d_out, d_sola, (int)sola_len, (int)search, (int)frame, d_frame, d_off, d_cor, 0LL, 0LL, 0LL, 0LL, nullptr, pv ? 1 : 0, d_pva, 0LL);
         if (pv) {
             hipLaunchKernelGGL(pv_analysis_kernel, dim3((K + PV_AT - 1) / PV_AT, 1), dim3(PV_AT), pv_analysis_lds(n), e->stream, d_out, d_pva, d_off, (const int *)nullptr, 1,
                                d_tab, n, d_spec, 0LL, 0LL);
@@ -1427,3 +1447,24 @@ rvc_status rvc_get_tap(rvc_engine *e, const char *name, float *out, size_t cap, 
 #include "denoise.hip.h"
 #include "session.hip.h"
 #include "rccl_bcast.hip.h"
+
+namespace rvc {
+
+// the session's ring launches (session.hip.h) and one converter call (resample.hip.h) for rvc_session_process and rvc_debug_post (debug.hip)
+void launch_ring_shift_append(hipStream_t s, int B, const float *in, float *out, int n, int f, const float *chunk)
+{
+    hipLaunchKernelGGL(ring_shift_append_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, in, out, n, f, chunk);
+}
+void launch_ring16_update(hipStream_t s, int B, const float *in, float *out, int n, int f, const float *res, int skip, int copy_begin, long long res_bs)
+{
+    hipLaunchKernelGGL(ring16_update_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, in, out, n, f, res, skip, copy_begin, res_bs);
+}
+rvc_status resampler_create_streams(rvc_engine *e, size_t rate_in, size_t rate_out, size_t chunk_size_in, int nb, rvc_resampler **out, int *fft_in, int *fft_out)
+{
+    const rvc_status rc = resampler_create_n(e, rate_in, rate_out, chunk_size_in, nb, out);
+    if (rc == RVC_OK) { *fft_in = (*out)->fft_in; *fft_out = (*out)->fft_out; }
+    return rc;
+}
+void launch_resampler(rvc_resampler *r, const float *d_in, float *d_out, long long in_bs, long long out_bs) { resampler_launch(r, d_in, d_out, in_bs, out_bs); }
+
+}  // namespace rvc

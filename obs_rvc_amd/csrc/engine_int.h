@@ -550,6 +550,18 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
 // (engine.hip get_plan) and of rvc_debug_protect (debug.hip)
 void launch_protect_mix(hipStream_t s, int B, const StreamState *st, const float *pitchf, const float *cv, int cv_cs, long long cv_bs, int C, int T, int skip_head, int R,
                         float *phone, int ph_cs, long long ph_bs);
+// the caller-side post-processing (chunk.hip.h), the session's ring updates (session.hip.h) and one converter call of every stream (resample.hip.h), each launch
+// as rvc_envelop_mixing / rvc_sola_step / rvc_session_process queue it (engine.hip) and as rvc_debug_post does (debug.hip).  B = streams; nf = RMS frames (the tracks are f64)
+void launch_post_rms(hipStream_t s, int B, const float *y, int n, int frame, int hop, int nf, double *out, long long y_bs, long long out_bs);
+void launch_post_mix(hipStream_t s, int B, float *out, int n, const double *r1, int n1, const double *r2, int n2, float mix_power, long long out_bs, long long r_bs, const float *mix_power_v);
+void launch_post_sola_corr(hipStream_t s, int B, const float *output, const float *sola, int sola_len, int search, float *cor, long long out_bs, long long sola_bs, long long cor_bs);
+void launch_post_sola(hipStream_t s, int B, float *output, float *sola, int sola_len, int search, int frame, float *frame_out, int *offset_out, const float *cor, long long out_bs,
+                      long long sola_bs, long long frame_bs, long long cor_bs, const int *mode_v, int mode_all, float *pv_a, long long pva_bs);
+void launch_ring_shift_append(hipStream_t s, int B, const float *in, float *out, int n, int f, const float *chunk);
+void launch_ring16_update(hipStream_t s, int B, const float *in, float *out, int n, int f, const float *res, int skip, int copy_begin, long long res_bs);
+// a converter of nb streams (rvc_session_create's; released with rvc_resampler_destroy) and its chunk sizes; one call of it queued on the engine's stream
+rvc_status resampler_create_streams(rvc_engine *e, size_t rate_in, size_t rate_out, size_t chunk_size_in, int nb, rvc_resampler **out, int *fft_in, int *fft_out);
+void launch_resampler(rvc_resampler *r, const float *d_in, float *d_out, long long in_bs, long long out_bs);
 void build_index_aux(rvc_engine *e);
 void ensure_index_transposed(rvc_engine *e);
 }  // namespace rvc

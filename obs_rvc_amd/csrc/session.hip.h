@@ -50,8 +50,8 @@ struct rvc_session {
     rvc_resampler *down = nullptr, *up = nullptr;
     float *d_in[2] = {nullptr, nullptr}, *d_in16[2] = {nullptr, nullptr};
     int par = 0, par16 = 0;
-    float *d_chunk = nullptr, *d_down = nullptr, *d_model = nullptr, *d_up = nullptr, *d_rms = nullptr, *d_sola = nullptr, *d_frame = nullptr, *d_cor = nullptr;
-    int *d_off = nullptr; int n_rms = 0;
+    float *d_chunk = nullptr, *d_down = nullptr, *d_model = nullptr, *d_up = nullptr, *d_sola = nullptr, *d_frame = nullptr, *d_cor = nullptr;
+    int *d_off = nullptr; int n_rms = 0; double *d_rms = nullptr;      // the two RMS tracks of envelope mixing, [B][2][n_rms] in f64
     int B = 1;                     // streams (= the engine's stream count at creation); every buffer below has a leading [B] axis
     std::vector<int> h_off;
     // crossfade mode per stream (RVC_CROSSFADE_*); the phase-vocoder buffers exist when the seam fits its kernels (sola_buffer_frame_size <= PV_MAX_N)
@@ -79,7 +79,8 @@ void rvc_session_destroy(rvc_session *s)
     rvc_resampler_destroy(s->down); rvc_resampler_destroy(s->up);
     for (int side = 0; side < 2; side++) { rvc_denoiser_destroy(s->dn[side]); (void)hipFree(s->d_dn[side]); }
     for (hipEvent_t ev : s->ev_dn) if (ev) (void)hipEventDestroy(ev);
-    for (float *p : {s->d_in[0], s->d_in[1], s->d_in16[0], s->d_in16[1], s->d_chunk, s->d_down, s->d_model, s->d_up, s->d_rms, s->d_sola, s->d_frame, s->d_cor}) (void)hipFree(p);
+    for (float *p : {s->d_in[0], s->d_in[1], s->d_in16[0], s->d_in16[1], s->d_chunk, s->d_down, s->d_model, s->d_up, s->d_sola, s->d_frame, s->d_cor}) (void)hipFree(p);
+    (void)hipFree(s->d_rms);
     (void)hipFree(s->d_off); (void)hipFree(s->d_mixpow);
     for (float *p : {s->d_pva, s->d_pvtab, s->d_pvspec, s->d_gate_thr, s->d_hist[0], s->d_hist[1], s->d_gated}) (void)hipFree(p);
     (void)hipFree(s->d_xfade);
@@ -133,7 +134,8 @@ rvc_status rvc_session_create(rvc_engine *e, size_t sample_rate, double sample_l
         dev(&s->d_chunk, s->sample_frame_size); dev(&s->d_down, s->down->fft_out); dev(&s->d_model, s->model_return_size); dev(&s->d_up, s->up_out);
         const int frame = 4 * zc, hop = zc;
         s->n_rms = (s->up_out + 2 * (frame / 2) - frame) / hop + 1;
-        dev(&s->d_rms, (size_t)2 * s->n_rms); dev(&s->d_sola, s->sola_buffer_frame_size); dev(&s->d_frame, s->sample_frame_size);
+        HIPCHK(hipMalloc(&s->d_rms, (size_t)2 * s->n_rms * NB * 8)); HIPCHK(hipMemsetAsync(s->d_rms, 0, (size_t)2 * s->n_rms * NB * 8, e->stream));
+        dev(&s->d_sola, s->sola_buffer_frame_size); dev(&s->d_frame, s->sample_frame_size);
         dev(&s->d_cor, (size_t)s->sola_search_frame_size + 1);
         HIPCHK(hipMalloc(&s->d_off, 4 * NB));
         HIPCHK(hipMalloc(&s->d_mixpow, 4 * NB));
@@ -264,7 +266,7 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
         if (n != (size_t)s->sample_frame_size || cap < (size_t)s->sample_frame_size || !input_sample || !output) throw ShapeError("session: wrong chunk size");
         if (e->n_streams != s->B) throw ShapeError("session: the engine's stream count changed since the session was created");
         hipStream_t st = e->stream;
-        const int T = 256, B = s->B;
+        const int B = s->B;
         HIPCHK(hipMemcpyAsync(s->d_chunk, input_sample, (size_t)B * n * 4, hipMemcpyHostToDevice, st));
         // settings that changed since the last chunk (as d_mixpow below: a blocking copy, paid by the chunk after a setter call only)
         if (s->xfade_dirty) { HIPCHK(hipMemcpy(s->d_xfade, s->xfade.data(), 4 * (size_t)B, hipMemcpyHostToDevice)); s->xfade_dirty = false; }
@@ -287,16 +289,14 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
             chunk = s->d_dn[0];
         }
         // lib.rs:661-665
-        hipLaunchKernelGGL(ring_shift_append_kernel, dim3((s->input_buffer_size + T - 1) / T, B), dim3(T), 0, st, s->d_in[s->par], s->d_in[s->par ^ 1],
-                           s->input_buffer_size, s->sample_frame_size, chunk);
+        launch_ring_shift_append(st, B, s->d_in[s->par], s->d_in[s->par ^ 1], s->input_buffer_size, s->sample_frame_size, chunk);
         s->par ^= 1;
         const float *ring = s->d_in[s->par];
         // lib.rs:669-683: the converter sees the new chunk plus the 2*zc samples before it; its first 160 outputs are dropped
         const int down_start = s->input_buffer_size - s->sample_frame_size - 2 * s->sample_rate / 100;
         resampler_launch(s->down, ring + down_start, s->d_down, s->input_buffer_size, s->down->fft_out);
         const int copy_begin = s->input_buffer_16k_size - (s->sample_frame_size / (s->sample_rate / 100) + 1) * 160;
-        hipLaunchKernelGGL(ring16_update_kernel, dim3((s->input_buffer_16k_size + T - 1) / T, B), dim3(T), 0, st, s->d_in16[s->par16], s->d_in16[s->par16 ^ 1],
-                           s->input_buffer_16k_size, s->sample_frame_16k, s->d_down, 160, copy_begin, (long long)s->down->fft_out);
+        launch_ring16_update(st, B, s->d_in16[s->par16], s->d_in16[s->par16 ^ 1], s->input_buffer_16k_size, s->sample_frame_16k, s->d_down, 160, copy_begin, (long long)s->down->fft_out);
         s->par16 ^= 1;
         const float *ring16 = s->d_in16[s->par16];
         // lib.rs:694-707
@@ -337,9 +337,9 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
                 s->mix_dirty = false;
             }
             const int nn = s->up_out, frame = 4 * s->zc, hop = s->zc, nf = s->n_rms;
-            hipLaunchKernelGGL(post_rms_kernel, dim3(nf, B), dim3(256), 0, st, ring + s->extra_frame_size, nn, frame, hop, s->d_rms, (long long)s->input_buffer_size, 2LL * nf);
-            hipLaunchKernelGGL(post_rms_kernel, dim3(nf, B), dim3(256), 0, st, s->d_up, nn, frame, hop, s->d_rms + nf, up_bs, 2LL * nf);
-            hipLaunchKernelGGL(post_mix_kernel, dim3((nn + 255) / 256, B), dim3(256), 0, st, s->d_up, nn, s->d_rms, nf, s->d_rms + nf, nf, 0.f, up_bs, 2LL * nf, s->d_mixpow);
+            launch_post_rms(st, B, ring + s->extra_frame_size, nn, frame, hop, nf, s->d_rms, (long long)s->input_buffer_size, 2LL * nf);
+            launch_post_rms(st, B, s->d_up, nn, frame, hop, nf, s->d_rms + nf, up_bs, 2LL * nf);
+            launch_post_mix(st, B, s->d_up, nn, s->d_rms, nf, s->d_rms + nf, nf, 0.f, up_bs, 2LL * nf, s->d_mixpow);
         }
         // lib.rs:768-794
         const long long cor_bs = s->sola_search_frame_size + 1;
@@ -347,11 +347,10 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
             for (hipEvent_t &ev : s->ev_sola) if (!ev) HIPCHK(hipEventCreate(&ev));
             HIPCHK(hipEventRecord(s->ev_sola[0], st));
         }
-        hipLaunchKernelGGL(post_sola_corr_kernel, dim3((unsigned)(s->sola_search_frame_size + 4) / 4, B), dim3(256), 0, st, s->d_up, s->d_sola,
-                           s->sola_buffer_frame_size, s->sola_search_frame_size, s->d_cor, up_bs, (long long)s->sola_buffer_frame_size, cor_bs);
-        hipLaunchKernelGGL(post_sola_kernel, dim3(B), dim3(1024), 0, st, s->d_up, s->d_sola, s->sola_buffer_frame_size, s->sola_search_frame_size,
-                           s->sample_frame_size, s->d_frame, s->d_off, s->d_cor, up_bs, (long long)s->sola_buffer_frame_size, (long long)s->sample_frame_size, cor_bs,
-                           s->n_pv ? s->d_xfade : (const int *)nullptr, 0, s->d_pva, (long long)s->sola_buffer_frame_size);
+        launch_post_sola_corr(st, B, s->d_up, s->d_sola, s->sola_buffer_frame_size, s->sola_search_frame_size, s->d_cor, up_bs, (long long)s->sola_buffer_frame_size, cor_bs);
+        launch_post_sola(st, B, s->d_up, s->d_sola, s->sola_buffer_frame_size, s->sola_search_frame_size, s->sample_frame_size, s->d_frame, s->d_off, s->d_cor, up_bs,
+                         (long long)s->sola_buffer_frame_size, (long long)s->sample_frame_size, cor_bs, s->n_pv ? s->d_xfade : (const int *)nullptr, 0, s->d_pva,
+                         (long long)s->sola_buffer_frame_size);
         if (s->n_pv) {      // phase-vocoder streams: the blend over output / frame / tail, from the offset the kernel above left on the device
             const int pn = s->sola_buffer_frame_size, K = pn / 2 + 1;
             hipLaunchKernelGGL(pv_analysis_kernel, dim3((K + PV_AT - 1) / PV_AT, B), dim3(PV_AT), pv_analysis_lds(pn), st, s->d_up, s->d_pva, s->d_off, s->d_xfade, 0,

@@ -43,6 +43,12 @@ class RetrievalSpec(C.Structure):
     _fields_ = _ints("streams", "C", "T", "cv_ld", "skip_head", "R", "ph_ld") + [("rate", C.c_float)] + _ints("path", "reps", "graph")
 
 
+class PostSpec(C.Structure):
+    """rvc_debug_post_spec"""
+    _fields_ = _ints("op", "streams", "graph", "n", "frame", "hop", "sola_len", "search", "f", "skip", "copy_begin", "rate_in", "rate_out", "chunk", "chunks") + \
+        [(n, C.c_longlong) for n in ("in_bs", "out_bs", "r_bs", "sola_bs", "frame_bs", "cor_bs", "x_bs")]
+
+
 class StreamState(C.Structure):
     """rvc_debug_stream_state (cache = cache_pitchf)"""
     _fields_ = [("uppower", C.c_float), ("stream_id", C.c_uint), ("chunk", C.c_uint), ("status", C.c_int), ("cache", C.c_float * 1024)]
@@ -57,6 +63,7 @@ def lib():
     L.rvc_debug_front.argtypes = [vp, C.POINTER(FrontSpec), vp, vp, C.POINTER(vp), C.POINTER(StreamState), geo]
     L.rvc_debug_rm_block.argtypes = [vp, C.POINTER(RmBlockSpec)] + [vp] * 9 + [geo]
     L.rvc_debug_retrieval.argtypes = [vp, C.POINTER(RetrievalSpec)] + [vp] * 5
+    L.rvc_debug_post.argtypes = [vp, C.POINTER(PostSpec), C.POINTER(vp), vp, vp]
     L.rvc_load_index.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
     L.rvc_debug_conv_check.argtypes = L.rvc_debug_conv2d_check.argtypes = [vp] + [C.c_int] * 7
     L.rvc_debug_conv_check.restype = L.rvc_debug_conv2d_check.restype = C.c_double

@@ -188,7 +188,8 @@ def test_debug_spec_mirrors_match_the_header(tmp_path):
     if not cc:
         pytest.skip("no C compiler found")
     mirrors = [("rvc_debug_layer_spec", D.LayerSpec), ("rvc_debug_op_spec", D.OpSpec), ("rvc_debug_front_spec", D.FrontSpec), ("rvc_debug_stream_state", D.StreamState),
-               ("rvc_debug_rm_block_spec", D.RmBlockSpec), ("rvc_debug_retrieval_spec", D.RetrievalSpec)]
+               ("rvc_debug_rm_block_spec", D.RmBlockSpec), ("rvc_debug_retrieval_spec", D.RetrievalSpec),
+               ("rvc_debug_post_spec", D.PostSpec)]
     c_name = {"cache": "cache_pitchf"}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rvc_mi355x_debug.h"', 'int main(void) {']
     want = []
