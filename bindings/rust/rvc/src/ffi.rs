@@ -69,6 +69,11 @@ extern "C" {
     pub fn rvc_load_index_device(e: *mut RvcEngine, d_vectors: *const c_void, n: usize, dim: usize) -> c_int;
     pub fn rvc_set_index_rate(e: *mut RvcEngine, rate: c_float);
     pub fn rvc_get_knn(e: *mut RvcEngine, idx: *mut i32, dist: *mut c_float, cap_rows: usize, rows: *mut usize) -> c_int;
+    // IVF-probed retrieval: the structure of an IndexIVFFlat file over the loaded index, and how many lists a query probes (0 = flat search)
+    pub fn rvc_set_index_ivf(e: *mut RvcEngine, centroids: *const c_float, nlist: usize, dim: usize, assign: *const i32, n: usize) -> c_int;
+    pub fn rvc_set_index_nprobe(e: *mut RvcEngine, nprobe: c_int) -> c_int;
+    pub fn rvc_index_nprobe(e: *mut RvcEngine) -> c_int;
+    pub fn rvc_index_ivf_info(e: *mut RvcEngine, nlist: *mut usize, longest_list: *mut usize, empty_lists: *mut usize) -> c_int;
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 

@@ -150,6 +150,28 @@ impl RvcInfer {
         self.check(unsafe { ffi::rvc_load_index(self.handle, v.as_ptr(), v.nrows(), v.ncols()) })
     }
 
+    /// Attach an IVF structure (coarse centroids and the list number of every row) to the loaded index.
+    pub fn set_index_ivf(&mut self, centroids: ndarray::ArrayView2<f32>, assign: &[i32]) -> Result<(), RvcInferError> {
+        let c = centroids.as_standard_layout();
+        self.check(unsafe { ffi::rvc_set_index_ivf(self.handle, c.as_ptr(), c.nrows(), c.ncols(), assign.as_ptr(), assign.len()) })
+    }
+
+    /// Lists probed per query: 0 = flat search, 1..=64 = IVF search (clamped to the number of lists).
+    pub fn set_index_nprobe(&mut self, nprobe: i32) -> Result<(), RvcInferError> {
+        self.check(unsafe { ffi::rvc_set_index_nprobe(self.handle, nprobe) })
+    }
+
+    pub fn index_nprobe(&self) -> i32 {
+        unsafe { ffi::rvc_index_nprobe(self.handle) }
+    }
+
+    /// (lists, rows of the longest list, empty lists) of the attached IVF structure.
+    pub fn index_ivf_info(&mut self) -> Result<(usize, usize, usize), RvcInferError> {
+        let (mut nlist, mut longest, mut empty) = (0usize, 0usize, 0usize);
+        self.check(unsafe { ffi::rvc_index_ivf_info(self.handle, &mut nlist, &mut longest, &mut empty) })?;
+        Ok((nlist, longest, empty))
+    }
+
     pub fn set_index_rate(&mut self, rate: f32) {
         unsafe { ffi::rvc_set_index_rate(self.handle, rate) }
     }

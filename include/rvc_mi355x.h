@@ -97,6 +97,17 @@ rvc_status rvc_get_knn(rvc_engine *e, int32_t *idx, float *dist, size_t cap_rows
    and the call still returns RVC_OK with the same hits.  This counts such chunks (0 on a GPU of one's own).  Unsynchronised calls (sync = 0) cannot
    be recomputed in order: there the time-out is reported by rvc_synchronize as RVC_BACKEND. */
 long long rvc_retrieval_recoveries(rvc_engine *e);
+/* IVF-probed retrieval: search the index as upstream searches its IndexIVFFlat files -- the nprobe nearest lists, then exact L2 inside
+   them -- instead of scanning every row.  rvc_set_index_ivf attaches the structure (coarse centroids [nlist][dim] and the list number of every row) to the index
+   the engine holds, after rvc_load_index / rvc_load_index_device / rvc_index_broadcast; both arrays are copied.  Rows keep their numbers: the ids of rvc_get_knn
+   mean what they mean for the flat search.  Fewer than four rows in the probed lists: the missing hits are idx -1 / dist +inf and that frame is not blended.
+   RVC_SHAPE: no index loaded, dim or n different from the index, nlist 0 or above 65536, an assignment outside [0, nlist), a non-finite centroid, nprobe outside
+   [0, 64], nprobe >= 1 without a structure.  Loading or broadcasting a new index drops the structure and returns nprobe to 0.  nprobe is engine-wide (not per
+   stream) and part of a plan's identity. */
+rvc_status rvc_set_index_ivf(rvc_engine *e, const float *centroids, size_t nlist, size_t dim, const int32_t *assign, size_t n);
+rvc_status rvc_set_index_nprobe(rvc_engine *e, int nprobe);   /* 0 = flat search (default); 1..64 = probe that many lists, clamped to nlist */
+int rvc_index_nprobe(rvc_engine *e);                          /* 0 = flat */
+rvc_status rvc_index_ivf_info(rvc_engine *e, size_t *nlist, size_t *longest_list, size_t *empty_lists);
 /* the synthesizer's two noise inputs are explicit counter-based (Philox4x32-10) streams */
 void rvc_set_noise_seed(rvc_engine *e, uint32_t seed, uint32_t stream_id);
 void rvc_reset_state(rvc_engine *e);     /* zero the 1024-entry pitch cache and the chunk counter */

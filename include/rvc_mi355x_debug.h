@@ -167,7 +167,7 @@ typedef struct rvc_debug_retrieval_spec {
 } rvc_debug_retrieval_spec;
 int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float *cv, float *phone, int *idx, float *dist, int *overflow);
 /* the device-side copies of the loaded index besides the row-major matrix: bit 0 = MFMA-fragment order, bit 1 = the transposed copy (built by the first plan that
- * needs it; while it is absent, the exhaustive scan of a fallback list walks the row-major matrix); 0 without an index */
+ * needs it; while it is absent, the exhaustive scan of a fallback list walks the row-major matrix), bit 2 = an IVF structure is attached; 0 without an index */
 int rvc_debug_index_layouts(rvc_engine *e);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */

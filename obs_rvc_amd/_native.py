@@ -34,6 +34,7 @@ SYMBOLS = [
     "rvc_sola_step_x", "rvc_input_gate", "rvc_session_set_crossfade", "rvc_session_set_crossfade_stream", "rvc_session_set_input_gate", "rvc_session_set_input_gate_stream",
     "rvc_denoiser_create", "rvc_denoiser_destroy", "rvc_denoiser_reset", "rvc_denoiser_set", "rvc_denoiser_latency", "rvc_denoiser_process", "rvc_denoiser_process_device",
     "rvc_session_set_noise_reduction", "rvc_session_set_noise_reduction_stream",
+    "rvc_set_index_ivf", "rvc_set_index_nprobe", "rvc_index_nprobe", "rvc_index_ivf_info",
 ]
 
 
@@ -223,6 +224,11 @@ def lib():
     L.rvc_set_index_rate.argtypes = [vp, C.c_float]
     L.rvc_set_index_rate.restype = None
     L.rvc_get_knn.argtypes = [vp, C.POINTER(i32), fp, sz, C.POINTER(sz)]
+    if hasattr(L, "rvc_set_index_ivf") or not override:
+        L.rvc_set_index_ivf.argtypes = [vp, fp, sz, sz, C.POINTER(i32), sz]
+        L.rvc_set_index_nprobe.argtypes = [vp, C.c_int]
+        L.rvc_index_nprobe.argtypes = [vp]
+        L.rvc_index_ivf_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.rvc_set_noise_seed.argtypes = [vp, u32, u32]
     L.rvc_set_noise_seed.restype = None
     L.rvc_reset_state.argtypes = [vp]

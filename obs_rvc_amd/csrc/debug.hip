@@ -578,7 +578,7 @@ int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *pho
             s->cv_ld > (1 << 21) || (long long)s->skip_head + R > 2LL * T + 1)
             throw ShapeError("protect spec");
         for (int b = 0; b < B; b++) if (!(protect[b] >= 0.0 && protect[b] <= PROTECT_OFF)) throw ShapeError("protect: value outside [0, 0.5]");
-        Plan pl; pl.B = B;
+        Plan pl; pl.B = B; pl.nprobe = e->index_nprobe;
         Arena &A = pl.arena;
         const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_pf = (size_t)B * R;
         float *d_ph = A.floats(n_ph), *d_cv = A.floats(n_cv), *d_pf = A.floats(n_pf);
@@ -755,7 +755,7 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
             throw ShapeError("retrieval spec");
         if (!e->d_index) throw ShapeError("no index loaded");
         if (e->index_dim != (size_t)C) throw ShapeError("index dimension does not match the feature dimension");
-        Plan pl; pl.B = B;
+        Plan pl; pl.B = B; pl.nprobe = e->index_nprobe;
         Arena &A = pl.arena;
         const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_hit = (size_t)B * R * KNN_K;
         T1 cvo, ph;
@@ -773,6 +773,7 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
         } swap_guard(e, d_st, B, s->rate);
         build_retrieval(e, pl, B, T, C, (uint32_t)s->skip_head, (uint32_t)R, ph);
         if (s->path == 1) {
+            if (pl.nprobe > 0) throw ShapeError("the IVF retrieval has no exhaustive list");
             if (pl.knn_fallback.empty()) throw ShapeError("this plan has no fallback list");
             pl.ops = OpList();
             for (Op &o : pl.knn_fallback) pl.ops.push_back(o);
@@ -799,7 +800,7 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
 }
 
 // test aid: which copies of the index exist (a fallback list built while the transposed copy is absent walks the row-major matrix)
-int rvc_debug_index_layouts(rvc_engine *e) { return e ? (e->d_indexF ? 1 : 0) | (e->d_indexT ? 2 : 0) : 0; }
+int rvc_debug_index_layouts(rvc_engine *e) { return e ? (e->d_indexF ? 1 : 0) | (e->d_indexT ? 2 : 0) | (e->d_ivf_cent ? 4 : 0) : 0; }
 
 // the kernel family of the most recently queued implicit-GEMM launch (the first word of its description), the variant of the last op or the form of the
 // last ConvBlockRes: tests assert which path they exercised
@@ -831,7 +832,7 @@ int rvc_debug_profile_dump(rvc_engine *e, char *buf, size_t cap)
         float t = 0.f;
         if (hipEventElapsedTime(&t, pl.prof[i].a, pl.prof[i].b) != hipSuccess) continue;
         char ln[320];
-        snprintf(ln, sizeof ln, "%.2f %.4f %s\n", t * 1e3, pl.prof[i].flops * 1e-9, pl.prof[i].desc >= 0 ? pl.descs[pl.prof[i].desc].c_str() : (pl.prof[i].bytes > 0 ? "knn_scan_select" : "?"));
+        snprintf(ln, sizeof ln, "%.2f %.4f %s\n", t * 1e3, pl.prof[i].flops * 1e-9, pl.prof[i].desc >= 0 ? pl.descs[pl.prof[i].desc].c_str() : (pl.prof[i].name ? pl.prof[i].name : "?"));
         out += ln;
     }
     if (out.size() + 1 > cap) return -1;

@@ -260,7 +260,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
             p->with_index == with_index && p->with_protect == with_protect && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
-            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method) {
+            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method && p->nprobe == (with_index ? e->index_nprobe : 0)) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -273,7 +273,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
     pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_protect = with_protect; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
-    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method;
+    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method; pl.nprobe = with_index ? e->index_nprobe : 0;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
     T1 src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;
@@ -741,6 +741,7 @@ void rvc_destroy(rvc_engine *e)
     if (e->d_ynorm) (void)hipFree(e->d_ynorm);
     if (e->d_nhn) (void)hipFree(e->d_nhn);
     if (e->d_indexF) (void)hipFree(e->d_indexF);
+    drop_index_ivf(e);
     if (e->d_state) (void)hipFree(e->d_state);
     if (e->d_state_bucket) (void)hipFree(e->d_state_bucket);
     if (e->d_bucket_idx) (void)hipFree(e->d_bucket_idx);
@@ -1288,7 +1289,7 @@ rvc_status rvc_profile_last(rvc_engine *e, int *launches, double *kernel_ms, dou
         HIPCHK(hipDeviceSynchronize());
         double ms = 0, fl = 0;
         int nl = 0;
-        for (size_t i = 0; i < pl->prof_used; i++) { if (pl->prof[i].bytes > 0) continue; float t; HIPCHK(hipEventElapsedTime(&t, pl->prof[i].a, pl->prof[i].b)); ms += t; fl += pl->prof[i].flops; nl++; }
+        for (size_t i = 0; i < pl->prof_used; i++) { if (pl->prof[i].retrieval) continue; float t; HIPCHK(hipEventElapsedTime(&t, pl->prof[i].a, pl->prof[i].b)); ms += t; fl += pl->prof[i].flops; nl++; }
         if (launches) *launches = nl;
         if (kernel_ms) *kernel_ms = ms;
         if (flops) *flops = pl->prof_used ? fl : pl->igemm_flops;
@@ -1402,7 +1403,12 @@ rvc_status rvc_profile_last_knn(rvc_engine *e, int *launches, double *kernel_ms,
         if (!pl) return RVC_SHAPE;
         HIPCHK(hipDeviceSynchronize());
         double ms = 0, by = 0; int nl = 0;
-        for (size_t i = 0; i < pl->prof_used; i++) { if (!(pl->prof[i].bytes > 0)) continue; float t; HIPCHK(hipEventElapsedTime(&t, pl->prof[i].a, pl->prof[i].b)); ms += t; by += pl->prof[i].bytes; nl++; }
+        for (size_t i = 0; i < pl->prof_used; i++) { if (!pl->prof[i].retrieval) continue; float t; HIPCHK(hipEventElapsedTime(&t, pl->prof[i].a, pl->prof[i].b)); ms += t; by += pl->prof[i].bytes; nl++; }
+        if (nl && pl->d_ivf_scanned) {       // IVF retrieval: the centroid table (the coarse launch's slot) plus the rows the last run's probe sets held
+            std::vector<int> rows(pl->ivf_queries);
+            HIPCHK(hipMemcpy(rows.data(), pl->d_ivf_scanned, rows.size() * sizeof(int), hipMemcpyDeviceToHost));
+            for (int r : rows) by += (double)r * e->index_dim * sizeof(float);
+        }
         if (launches) *launches = nl;
         if (kernel_ms) *kernel_ms = ms;
         if (bytes) *bytes = by;

@@ -212,7 +212,9 @@ struct ConvOpts {
     const float *ln_stats_in = nullptr, *ln_g = nullptr, *ln_b = nullptr;
 };
 
-struct ProfEvent { hipEvent_t a, b; double flops; double bytes; int desc = -1; };   // bytes > 0: HBM-bound retrieval scan (flops = 0)
+// retrieval: a launch of the retrieval section (rvc_profile_last_knn counts it; bytes = its algorithmic bytes, 0 where they depend on the data); name: what
+// rvc_debug_profile_dump calls a launch that has no description of its own
+struct ProfEvent { hipEvent_t a, b; double flops; double bytes; int desc = -1; bool retrieval = false; const char *name = nullptr; };
 
 struct Plan;
 typedef std::function<void(hipStream_t)> Op;
@@ -264,6 +266,8 @@ struct Plan {
     float *d_f0 = nullptr;  // [B][Tm]
     float *d_feat = nullptr; // extract_feature output (1,2T+1,C)
     int *d_knn_idx = nullptr; float *d_knn_dist = nullptr;
+    int nprobe = 0;                                    // the engine's index_nprobe when the plan was built (with_index plans; 0 = flat search)
+    int *d_ivf_scanned = nullptr; int ivf_queries = 0;  // IVF retrieval: rows scanned per (stream, query) of the last run, and how many such words
     int *d_knn_overflow = nullptr;                     // many-stream retrieval: one word per stream, raised when its candidate set overflowed (nullptr on the one-launch form)
     // one-launch retrieval: its ticket counters, and what runs instead when a selector gave up (engine.hip recover_retrieval)
     unsigned *knn_ticket = nullptr; size_t knn_ticket_bytes = 0;
@@ -290,12 +294,12 @@ struct Plan {
     // graph
     hipGraphExec_t graph_exec = nullptr;
     // run time: the next profile slot of this run (its events are created on first use; the engine rewinds prof_used per run), nullptr when not profiling
-    ProfEvent *prof_slot(double flops, double bytes, int desc)
+    ProfEvent *prof_slot(double flops, double bytes, int desc, const char *retrieval_name = nullptr)
     {
         if (!profile) return nullptr;
         if (prof_used == prof.size()) { ProfEvent e; HIPCHK(hipEventCreate(&e.a)); HIPCHK(hipEventCreate(&e.b)); prof.push_back(e); }
         ProfEvent *pe = &prof[prof_used++];
-        pe->flops = flops; pe->bytes = bytes; pe->desc = desc;
+        pe->flops = flops; pe->bytes = bytes; pe->desc = desc; pe->retrieval = retrieval_name != nullptr; pe->name = retrieval_name;
         return pe;
     }
     ~Plan()
@@ -460,6 +464,9 @@ struct rvc_engine {
     // retrieval index
     float *d_index = nullptr, *d_indexT = nullptr, *d_indexF = nullptr, *d_ynorm = nullptr, *d_nhn = nullptr; size_t index_n = 0, index_dim = 0; bool index_owned = true;
     float index_rate = 0.f;
+    // IVF structure over the loaded index (rvc_set_index_ivf; ivf.hip.h): centroids, CSR offsets and the row permutation, all on the device.
+    // index_nprobe: 0 = flat search, else the lists probed per query; engine-wide and part of a plan's identity.  A new index drops both (build_index_aux)
+    float *d_ivf_cent = nullptr; int *d_ivf_offs = nullptr, *d_ivf_perm = nullptr; size_t ivf_nlist = 0, ivf_longest = 0, ivf_empty = 0; int index_nprobe = 0;
     float index_prep_ms = 0.f;                                  // device-side repack + norms of the last index load
     double bcast_ms[3] = {0, 0, 0}; int bcast_ranks = 0;         // last rvc_index_broadcast: communicator set-up, broadcast, repack (ms); ranks the communicator reports
     // streams
@@ -564,4 +571,5 @@ rvc_status resampler_create_streams(rvc_engine *e, size_t rate_in, size_t rate_o
 void launch_resampler(rvc_resampler *r, const float *d_in, float *d_out, long long in_bs, long long out_bs);
 void build_index_aux(rvc_engine *e);
 void ensure_index_transposed(rvc_engine *e);
+void drop_index_ivf(rvc_engine *e);
 }  // namespace rvc

@@ -1,5 +1,5 @@
 // knn.hip.h -- the kernels of the flat-L2 retrieval: index layouts, the scan / merge pair, the one-launch scan + select, the matrix-core candidate search.
-// Included by retrieval.hip only (KNN_K: state.hip.h).
+// Included by retrieval.hip only (KNN_K: state.hip.h); ivf.hip.h builds on its distance and blend device functions.
 #pragma once
 #include "igemm.hip.h"
 #include "state.hip.h"
@@ -14,6 +14,67 @@ namespace rvc {
 // keeps its own top-4 per query.  Stage 2 merges the per-workgroup candidates
 // (ascending (distance, index)), forms w = (1/d)^2 and blends.
 // ------------------------------------------------------------------------------------
+// The engine's exact distance d(x, y) (tests/knn_ref.py): an fp32 sequential fmaf chain over the rounded differences (x[c] - y[c]) in
+// ascending c.  knn_dist_step is one link of it; every kernel that owes the definition's bits (the exhaustive scan, the exact re-rank, the IVF coarse and
+// fine scans of ivf.hip.h) goes through it, whatever it stages its operands in.
+__device__ __forceinline__ float knn_dist_step(float acc, float x, float y) { const float df = x - y; return fmaf(df, df, acc); }
+__device__ __forceinline__ float knn_dist_exact(const float *x, const float *y, int dim)
+{
+    float acc = 0.f;
+    for (int d = 0; d < dim; d++) acc = knn_dist_step(acc, x[d], y[d]);
+    return acc;
+}
+// The blend: w = (1/d)^2 normalised over the four hits, feat = rate * sum w_k y_k + (1 - rate) * x.  A hit without a row (-1 or the
+// 0x7fffffff sentinel: a non-finite query) contributes nothing.  One definition for every blend kernel, so that they agree bit for bit.
+__device__ __forceinline__ void knn_blend_weights(const float *sd, float (&wn)[4])
+{
+    float ws = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const float inv = 1.0f / sd[k]; wn[k] = inv * inv; ws += wn[k]; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) wn[k] = wn[k] / ws;
+}
+__device__ __forceinline__ float knn_blend_channel(const float *index, int dim, int c, const int *si, const float (&wn)[4], float rate, float x)
+{
+    float y[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) y[k] = (si[k] >= 0 && si[k] != 0x7fffffff) ? index[(long long)si[k] * dim + c] : 0.f;
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (si[k] >= 0 && si[k] != 0x7fffffff) acc = fmaf(wn[k], y[k], acc);
+    return fmaf(rate, acc, (1.0f - rate) * x);      // (explicit fmaf: no contraction choice is left to the compiler)
+}
+
+// The four smallest (distance, index) pairs of a 256-thread workgroup whose threads each hold a sorted list of four (+inf / 0x7fffffff = no entry): per wave by
+// four rounds of a minimum over the lanes' heads, then one thread merges the four waves' lists into sd / si (sorted; visible to every thread on return).
+__device__ __forceinline__ void knn_block_top4(const float (&ld)[4], const int (&li)[4], float (&wd)[4][4], int (&wi)[4][4], float (&sd)[4], int (&si)[4])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int pos = 0;
+    for (int k = 0; k < 4; k++) {
+        float md = pos == 0 ? ld[0] : pos == 1 ? ld[1] : pos == 2 ? ld[2] : pos == 3 ? ld[3] : INFINITY;
+        int mi = pos == 0 ? li[0] : pos == 1 ? li[1] : pos == 2 ? li[2] : pos == 3 ? li[3] : 0x7fffffff;
+        const float d0 = md; const int i0 = mi;
+        wave_min_pair(md, mi);
+        if (d0 == md && i0 == mi && mi != 0x7fffffff) pos++;
+        if (lane == 0) { wd[wave][k] = md; wi[wave][k] = mi; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int ps[4] = {0, 0, 0, 0};
+        for (int k = 0; k < 4; k++) {
+            float md = INFINITY; int mi = 0x7fffffff, mw = 0;
+            for (int w = 0; w < 4; w++) if (ps[w] < 4) {
+                float od = wd[w][ps[w]]; int oi = wi[w][ps[w]];
+                if (od < md || (od == md && oi < mi)) { md = od; mi = oi; mw = w; }
+            }
+            ps[mw]++;
+            sd[k] = md; si[k] = mi;
+        }
+    }
+    __syncthreads();
+}
+
 #define KNN_MAXQ 16
 struct KnnP {
     const float *indexT;     // [dim][n] (or nullptr: the scan walks the row-major index, v_stride = dim, d_stride = 1)
@@ -54,13 +115,13 @@ static __global__ __launch_bounds__(256) void knn_scan_kernel(KnnP p)
 #pragma unroll
             for (int u = 0; u < 8; u++) {
 #pragma unroll
-                for (int j = 0; j < KNN_MAXQ; j++) if (j < p.nq) { float df = smem[j * p.dim + d + u] - v[u]; acc[j] = fmaf(df, df, acc[j]); }
+                for (int j = 0; j < KNN_MAXQ; j++) if (j < p.nq) acc[j] = knn_dist_step(acc[j], smem[j * p.dim + d + u], v[u]);
             }
         }
         for (; d < p.dim; d++) {
             float v = col[(long long)d * p.d_stride];
 #pragma unroll
-            for (int j = 0; j < KNN_MAXQ; j++) if (j < p.nq) { float df = smem[j * p.dim + d] - v; acc[j] = fmaf(df, df, acc[j]); }
+            for (int j = 0; j < KNN_MAXQ; j++) if (j < p.nq) acc[j] = knn_dist_step(acc[j], smem[j * p.dim + d], v);
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -129,34 +190,9 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_kernel(KnnBlendP p
             ld[q] = d; li[q] = id;
         }
     }
-    int pos = 0;
-    for (int k = 0; k < KNN_K; k++) {
-        float md = pos < KNN_K ? ld[pos] : INFINITY; int mi = pos < KNN_K ? li[pos] : 0x7fffffff;
-        float d0 = md; int i0 = mi;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            float od = __shfl_xor(md, o, 64); int oi = __shfl_xor(mi, o, 64);
-            if (od < md || (od == md && oi < mi)) { md = od; mi = oi; }
-        }
-        if (d0 == md && i0 == mi && mi != 0x7fffffff) pos++;
-        if (lane == 0) { wd[wave][k] = md; wi[wave][k] = mi; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int ps[4] = {0, 0, 0, 0};
-        for (int k = 0; k < KNN_K; k++) {
-            float md = INFINITY; int mi = 0x7fffffff, mw = 0;
-            for (int w = 0; w < 4; w++) if (ps[w] < KNN_K) {
-                float od = wd[w][ps[w]]; int oi = wi[w][ps[w]];
-                if (od < md || (od == md && oi < mi)) { md = od; mi = oi; mw = w; }
-            }
-            ps[mw]++;
-            sd[k] = md; si[k] = mi;
-        }
-    }
-    __syncthreads();
-    float w[KNN_K], ws = 0.f;
-    for (int k = 0; k < KNN_K; k++) { float inv = 1.0f / sd[k]; w[k] = inv * inv; ws += w[k]; }
+    knn_block_top4(ld, li, wd, wi, sd, si);
+    float w[KNN_K];
+    knn_blend_weights(sd, w);
     const float *qv = p.q + ((long long)b * p.nq + j) * p.dim;
     for (int r = 0; r < p.R; r++) {
         int s = (p.skip_head + r) / 2; s = s < p.T - 1 ? s : p.T - 1;
@@ -165,11 +201,8 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_kernel(KnnBlendP p
             p.out_idx[((long long)b * p.R + r) * KNN_K + threadIdx.x] = si[threadIdx.x] == 0x7fffffff ? -1 : si[threadIdx.x];
             p.out_dist[((long long)b * p.R + r) * KNN_K + threadIdx.x] = sd[threadIdx.x];
         }
-        for (int c = threadIdx.x; c < p.dim; c += 256) {
-            float acc = 0.f;
-            for (int k = 0; k < KNN_K; k++) if (si[k] >= 0 && si[k] != 0x7fffffff) acc = fmaf(w[k] / ws, p.index[(long long)si[k] * p.dim + c], acc);   // no valid hit for a non-finite query
-            p.phone[(long long)b * p.ph_bs + (long long)c * p.ph_cs + r] = fmaf(p.rate, acc, (1.0f - p.rate) * qv[c]);      // (explicit fmaf: the three blend kernels agree bit for bit)
-        }
+        for (int c = threadIdx.x; c < p.dim; c += 256)
+            p.phone[(long long)b * p.ph_bs + (long long)c * p.ph_cs + r] = knn_blend_channel(p.index, p.dim, c, si, w, p.rate, qv[c]);
     }
 }
 
@@ -649,23 +682,14 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
         KNN_STAMP(8);
         // 4. blend: w = (1/d)^2 normalised, feat = rate * sum w_i y_i + (1 - rate) * feat; computed once per
         //    query, written to every sliced frame that duplicates it (a contiguous range of r: frames (skip_head + r) / 2, clamped to T - 1)
-        float wn[KNN_K], ws = 0.f;
-#pragma unroll
-        for (int k = 0; k < KNN_K; k++) { const float inv = 1.0f / sd[k]; wn[k] = inv * inv; ws += wn[k]; }
-#pragma unroll
-        for (int k = 0; k < KNN_K; k++) wn[k] = wn[k] / ws;
+        float wn[KNN_K];
+        knn_blend_weights(sd, wn);
         const int raw = j + p.first_raw;
         int r_lo = 2 * raw - p.skip_head, r_hi = raw >= p.T - 1 ? p.R : 2 * raw + 2 - p.skip_head;
         r_lo = r_lo < 0 ? 0 : r_lo; r_hi = r_hi > p.R ? p.R : r_hi;
         float *ph = p.phone + (long long)b * p.ph_bs;
         for (int c = tid; c < p.dim; c += 256) {
-            float y[KNN_K];
-#pragma unroll
-            for (int k = 0; k < KNN_K; k++) y[k] = (si[k] >= 0 && si[k] != 0x7fffffff) ? p.index[(long long)si[k] * p.dim + c] : 0.f;   // (no valid hit for a non-finite query)
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < KNN_K; k++) if (si[k] >= 0 && si[k] != 0x7fffffff) acc = fmaf(wn[k], y[k], acc);
-            const float val = fmaf(p.rate, acc, (1.0f - p.rate) * s_x[c]);
+            const float val = knn_blend_channel(p.index, p.dim, c, si, wn, p.rate, s_x[c]);
             for (int r = r_lo; r < r_hi; r++) ph[(long long)c * p.ph_cs + r] = val;
         }
         KNN_STAMP(9);
@@ -893,9 +917,7 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
             __syncthreads();
             if (tid < 32 && base + tid < ncand) {
                 const float *v = s_rows + tid * RS;
-                float acc = 0.f;
-                for (int d = 0; d < p.dim; d++) { const float df = s_qv[d] - v[d]; acc = fmaf(df, df, acc); }
-                cand_d[base + tid] = acc;
+                cand_d[base + tid] = knn_dist_exact(s_qv, v, p.dim);
             }
         }
     }
@@ -913,9 +935,8 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
     }
     __syncthreads();
     // 4. blend: w = (1/d)^2 normalised, feat = rate * sum w_i y_i + (1 - rate) * feat
-    float w[KNN_K], ws = 0.f;
-#pragma unroll
-    for (int k = 0; k < KNN_K; k++) { float inv = 1.0f / sd[k]; w[k] = inv * inv; ws += w[k]; }
+    float w[KNN_K];
+    knn_blend_weights(sd, w);
     for (int r = 0; r < p.R; r++) {
         int s = (p.skip_head + r) / 2; s = s < p.T - 1 ? s : p.T - 1;
         if (s - p.first_raw != j) continue;
@@ -923,12 +944,8 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
             p.out_idx[((long long)b * p.R + r) * KNN_K + tid] = si[tid] == 0x7fffffff ? -1 : si[tid];   // -1: no hit (non-finite query)
             p.out_dist[((long long)b * p.R + r) * KNN_K + tid] = sd[tid];
         }
-        for (int c = tid; c < p.dim; c += 1024) {
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < KNN_K; k++) if (si[k] >= 0 && si[k] != 0x7fffffff) acc = fmaf(w[k] / ws, p.index[(long long)si[k] * p.dim + c], acc);   // no valid hit for a non-finite query
-            p.phone[(long long)b * p.ph_bs + (long long)c * p.ph_cs + r] = fmaf(p.rate, acc, (1.0f - p.rate) * qv[c]);      // (explicit fmaf: the three blend kernels agree bit for bit)
-        }
+        for (int c = tid; c < p.dim; c += 1024)
+            p.phone[(long long)b * p.ph_bs + (long long)c * p.ph_cs + r] = knn_blend_channel(p.index, p.dim, c, si, w, p.rate, qv[c]);
     }
 }
 

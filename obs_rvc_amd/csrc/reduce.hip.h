@@ -17,6 +17,15 @@ __device__ __forceinline__ float wave_max(float v)
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// the smallest (value, index) pair of the wave, ties by the lower index, left in every lane
+__device__ __forceinline__ void wave_min_pair(float &d, int &i)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float od = __shfl_xor(d, o, 64); const int oi = __shfl_xor(i, o, 64);
+        if (od < d || (od == d && oi < i)) { d = od; i = oi; }
+    }
+}
 // blockDim.x must be a multiple of 64 and <= 1024; red must hold 16 floats
 __device__ __forceinline__ float block_sum(float v, float *red)
 {

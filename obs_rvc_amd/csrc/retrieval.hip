@@ -1,7 +1,8 @@
 // retrieval.hip -- flat-L2 index retrieval (rvc/src/rvc.rs:159 is a TODO in the reference; definition: SURVEY.md Appendix A.4, BASELINE configs 3-5):
-// index load and its device-side layouts, the search section of an infer plan, the index entry points of the C ABI.
+// index load and its device-side layouts, the search section of an infer plan (flat, or IVF-probed: ivf.hip.h), the index entry points of the C ABI.
 #include "engine_int.h"
 #include "knn.hip.h"
+#include "ivf.hip.h"
 
 namespace rvc {
 
@@ -10,6 +11,45 @@ namespace rvc {
 std::atomic<int> g_knn_test_lose{0};
 static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int nblk, int first_raw, uint32_t skip_head, uint32_t R, int T, const T1 &phone, const T1 &cvo,
                              bool fast, int *d_overflow, float *d_q = nullptr, float *cand_d = nullptr, int *cand_i = nullptr);
+
+// The IVF section, in place of the flat one for every stream count: two launches, no fallback list, nothing that can time out.
+static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_raw, uint32_t skip_head, uint32_t R, int T, const T1 &phone, const T1 &cvo)
+{
+        if (!e->d_ivf_cent) throw ShapeError("no IVF structure attached to the index");
+        const int nlist = (int)e->ivf_nlist, Q = B * nq;
+        const int nprobe = std::min(pl.nprobe, nlist);
+        float *D = pl.arena.floats((size_t)Q * nlist);
+        int *scanned = (int *)pl.arena.alloc((size_t)Q * sizeof(int));
+        pl.d_ivf_scanned = scanned; pl.ivf_queries = Q;
+        snprintf(g_last_kernel, sizeof g_last_kernel, "knn_ivf");
+        Plan *plp = &pl;
+        {
+            IvfCoarseP cp{}; cp.cent = e->d_ivf_cent; cp.nlist = nlist; cp.dim = C; cp.cv = cvo.p; cp.cv_cs = cvo.ld; cp.cv_bs = cvo.bs; cp.first_raw = first_raw; cp.nq = nq; cp.Q = Q; cp.D = D;
+            const size_t lds = (size_t)IVF_TQ * ivf_qs(C) * sizeof(float);
+            if (lds > 128 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
+            dim3 grid((nlist + IVF_TC - 1) / IVF_TC, (Q + IVF_TQ - 1) / IVF_TQ);
+            const double bytes = (double)nlist * C * sizeof(float);            // algorithmic bytes: the centroid table, once per launch
+            pl.ops.push_back([=](hipStream_t s) {
+                const ProfEvent *pe = plp->prof_slot(0, bytes, -1, "knn_ivf_coarse");
+                if (pe) hipExtLaunchKernelGGL(ivf_coarse_kernel, grid, dim3(256), (uint32_t)lds, s, pe->a, pe->b, 0, cp);
+                else hipLaunchKernelGGL(ivf_coarse_kernel, grid, dim3(256), lds, s, cp);
+            });
+        }
+        {
+            IvfScanP sp{}; sp.D = D; sp.nlist = nlist; sp.nprobe = nprobe; sp.offs = e->d_ivf_offs; sp.perm = e->d_ivf_perm; sp.index = e->d_index; sp.dim = C;
+            sp.cv = cvo.p; sp.cv_cs = cvo.ld; sp.cv_bs = cvo.bs; sp.first_raw = first_raw; sp.nq = nq;
+            sp.skip_head = (int)skip_head; sp.T = T; sp.R = (int)R; sp.rate = e->index_rate;
+            sp.phone = phone.p; sp.ph_cs = phone.ld; sp.ph_bs = phone.bs; sp.out_idx = pl.d_knn_idx; sp.out_dist = pl.d_knn_dist; sp.scanned = scanned;
+            const size_t lds = ((size_t)IVF_TILE + C) * sizeof(float);
+            if (lds > 144 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
+            dim3 grid(nq, B);
+            pl.ops.push_back([=](hipStream_t s) {
+                const ProfEvent *pe = plp->prof_slot(0, 0, -1, "knn_ivf_scan");     // (bytes: the rows the probe sets held, read back by rvc_profile_last_knn)
+                if (pe) hipExtLaunchKernelGGL(ivf_scan_blend_kernel, grid, dim3(256), (uint32_t)lds, s, pe->a, pe->b, 0, sp);
+                else hipLaunchKernelGGL(ivf_scan_blend_kernel, grid, dim3(256), lds, s, sp);
+            });
+        }
+}
 
 void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip_head, uint32_t R, const T1 &phone)
 {
@@ -21,6 +61,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         pl.d_knn_idx = (int *)pl.arena.alloc((size_t)B * R * KNN_K * sizeof(int));
         pl.d_knn_dist = pl.arena.floats((size_t)B * R * KNN_K);
         T1 cvo = pl.cv_out;
+        if (pl.nprobe > 0) { build_ivf(e, pl, B, C, nq, first_raw, skip_head, R, T, phone, cvo); return; }
         // Stage A + B: approximate distances on the matrix cores in one pass over the index (HBM-bound), exact re-rank of a
         // provably sufficient candidate set.
         const bool fast = C % 16 == 0 && !test_opt("RVC_KNN_EXHAUSTIVE");
@@ -62,7 +103,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
                 Plan *plp = &pl;
                 const double scan_bytes = (double)e->index_n * C * sizeof(float) * B;     // algorithmic bytes: the index, read once per query group
                 pl.ops.push_back([=](hipStream_t s) {
-                    const ProfEvent *pe = plp->prof_slot(0, scan_bytes, -1);
+                    const ProfEvent *pe = plp->prof_slot(0, scan_bytes, -1, "knn_scan_select");
                     if (g_knn_test_lose.load(std::memory_order_relaxed)) {       // test hook (rvc_debug_option RVC_KNN_LOSE_TICKET): a hand-off that cannot complete
                         KnnFusedP f2 = fp; f2.test_lose = 1; f2.spin_limit = 1u << 12;
                         hipLaunchKernelGGL(knn_scan_select_kernel, grid, dim3(256), lds, s, f2);
@@ -159,8 +200,18 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
 // (uploaded once, or delivered by the RCCL broadcast): the MFMA-fragment-order copy for the one-pass approximate scan and the vector
 // norms.  No host round trip (round 2 copied the 307 MB matrix back to the host, repacked it in a single-threaded loop and uploaded two
 // more copies: seconds per rank behind a 2 ms broadcast).  The transposed copy is NOT built here: see ensure_index_transposed.
+void drop_index_ivf(rvc_engine *e)
+{
+    if (e->d_ivf_cent) (void)hipFree(e->d_ivf_cent);
+    if (e->d_ivf_offs) (void)hipFree(e->d_ivf_offs);
+    if (e->d_ivf_perm) (void)hipFree(e->d_ivf_perm);
+    e->d_ivf_cent = nullptr; e->d_ivf_offs = e->d_ivf_perm = nullptr;
+    e->ivf_nlist = e->ivf_longest = e->ivf_empty = 0; e->index_nprobe = 0;
+}
+
 void build_index_aux(rvc_engine *e)
 {
+    drop_index_ivf(e);          // a new index: the structure described the old rows, and the search is flat again
     if (e->d_indexT) { (void)hipFree(e->d_indexT); e->d_indexT = nullptr; }
     if (e->d_indexF) { (void)hipFree(e->d_indexF); e->d_indexF = nullptr; }
     if (e->d_ynorm) (void)hipFree(e->d_ynorm);
@@ -201,6 +252,8 @@ void retrieval_kernel_attrs()
 {
     HIPCHK(hipFuncSetAttribute((const void *)knn_select_blend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));   // + ~5 KB static
     HIPCHK(hipFuncSetAttribute((const void *)knn_scan_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)ivf_coarse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));         // + 16 KB static
+    HIPCHK(hipFuncSetAttribute((const void *)ivf_scan_blend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));     // + ~2 KB static
 }
 
 }  // namespace rvc
@@ -260,6 +313,78 @@ rvc_status rvc_get_knn(rvc_engine *e, int32_t *idx, float *dist, size_t cap_rows
         HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemcpy(idx, pl->d_knn_idx, r * KNN_K * sizeof(int), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(dist, pl->d_knn_dist, r * KNN_K * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
+// Attach an IVF structure to the loaded index: centroids and assignment are copied, validated on the host, and the CSR (list offsets + row permutation, rows
+// ascending inside every list) is built on the device by a counting sort.  The matrix itself is not copied: the scan gathers whole rows by id.
+rvc_status rvc_set_index_ivf(rvc_engine *e, const float *centroids, size_t nlist, size_t dim, const int32_t *assign, size_t n)
+{
+    return guarded(e, [&]() {
+        if (!e->d_index) throw ShapeError("no index loaded");
+        if (!centroids || !assign) throw ShapeError("IVF structure: null centroids or assignment");
+        if (dim != e->index_dim || n != e->index_n) throw ShapeError("IVF structure does not match the loaded index (dim or n)");
+        if (nlist < 1 || nlist > IVF_MAX_NLIST) throw ShapeError("IVF structure: nlist must be in [1, 65536]");
+        for (size_t i = 0; i < n; i++) if (assign[i] < 0 || (size_t)assign[i] >= nlist) throw ShapeError("IVF structure: an assignment is outside [0, nlist)");
+        for (size_t i = 0; i < nlist * dim; i++) if (!std::isfinite(centroids[i])) throw ShapeError("IVF structure: a centroid is not finite");
+        HIPCHK(hipDeviceSynchronize());
+        drop_index_ivf(e);
+        e->plans.clear(); e->last_plan = nullptr;
+        int *d_assign = nullptr, *d_counts = nullptr;
+        try {
+            HIPCHK(hipMalloc(&e->d_ivf_cent, nlist * dim * sizeof(float)));
+            HIPCHK(hipMalloc(&e->d_ivf_offs, (nlist + 1) * sizeof(int)));
+            HIPCHK(hipMalloc(&e->d_ivf_perm, n * sizeof(int)));
+            HIPCHK(hipMalloc(&d_assign, n * sizeof(int)));
+            HIPCHK(hipMalloc(&d_counts, nlist * sizeof(int)));
+            HIPCHK(hipMemcpy(e->d_ivf_cent, centroids, nlist * dim * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_assign, assign, n * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHK(hipMemsetAsync(d_counts, 0, nlist * sizeof(int), e->stream));
+            hipLaunchKernelGGL(ivf_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, d_assign, (int)n, d_counts);
+            hipLaunchKernelGGL(ivf_offsets_kernel, dim3(1), dim3(256), 0, e->stream, d_counts, (int)nlist, e->d_ivf_offs);
+            hipLaunchKernelGGL(ivf_fill_kernel, dim3((unsigned)((nlist + 3) / 4)), dim3(256), 0, e->stream, d_assign, (int)n, (int)nlist, e->d_ivf_offs, e->d_ivf_perm);
+            HIPCHK(hipStreamSynchronize(e->stream));
+            HIPCHK(hipGetLastError());
+            std::vector<int> offs(nlist + 1);
+            HIPCHK(hipMemcpy(offs.data(), e->d_ivf_offs, offs.size() * sizeof(int), hipMemcpyDeviceToHost));
+            if (offs[0] != 0 || (size_t)offs[nlist] != n) throw std::runtime_error("IVF structure: the device-side list offsets do not add up");
+            e->ivf_nlist = nlist;
+            for (size_t l = 0; l < nlist; l++) {
+                const size_t len = (size_t)(offs[l + 1] - offs[l]);
+                e->ivf_longest = std::max(e->ivf_longest, len); e->ivf_empty += len == 0;
+            }
+        } catch (...) {
+            if (d_assign) (void)hipFree(d_assign);
+            if (d_counts) (void)hipFree(d_counts);
+            drop_index_ivf(e);
+            throw;
+        }
+        (void)hipFree(d_assign); (void)hipFree(d_counts);
+        return RVC_OK;
+    });
+}
+
+rvc_status rvc_set_index_nprobe(rvc_engine *e, int nprobe)
+{
+    return guarded(e, [&]() {
+        if (!e->d_index) throw ShapeError("no index loaded");
+        if (nprobe < 0 || nprobe > IVF_MAX_NPROBE) throw ShapeError("nprobe must be in [0, 64]");
+        if (nprobe >= 1 && !e->d_ivf_cent) throw ShapeError("nprobe >= 1 needs an IVF structure (rvc_set_index_ivf)");
+        e->index_nprobe = nprobe >= 1 ? (int)std::min((size_t)nprobe, e->ivf_nlist) : 0;
+        return RVC_OK;
+    });
+}
+
+int rvc_index_nprobe(rvc_engine *e) { return e ? e->index_nprobe : 0; }
+
+rvc_status rvc_index_ivf_info(rvc_engine *e, size_t *nlist, size_t *longest_list, size_t *empty_lists)
+{
+    return guarded(e, [&]() {
+        if (!e->d_ivf_cent) throw ShapeError("no IVF structure attached to the index");
+        if (nlist) *nlist = e->ivf_nlist;
+        if (longest_list) *longest_list = e->ivf_longest;
+        if (empty_lists) *empty_lists = e->ivf_empty;
         return RVC_OK;
     });
 }

@@ -59,8 +59,9 @@ def _header(r: _R) -> Tuple[int, int, int]:
     return d, ntotal, metric
 
 
-def _read(r: _R) -> Tuple[np.ndarray, Optional[np.ndarray]]:
-    """-> (vectors (n, d) in storage order, ids or None when storage order is id order)."""
+def _read(r: _R, ivf: Optional[dict] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """-> (vectors (n, d) in storage order, ids or None when storage order is id order).  `ivf`: a dict that receives the outermost IndexIVFFlat's structure
+    (nprobe, centroids, sizes = rows per list in storage order)."""
     cc = r.fourcc()
     if cc in ("IxF2", "IxFI", "IxFl"):
         d, ntotal, _ = _header(r)
@@ -70,13 +71,13 @@ def _read(r: _R) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         return xb.reshape(ntotal, d), None
     if cc == "IxMp" or cc == "IxM2":                    # IndexIDMap(2): sub-index + id_map
         _header(r)
-        v, ids = _read(r)
+        v, ids = _read(r, ivf)
         idmap = r.vec(np.int64)
         return v, (idmap if ids is None else idmap[ids])
     if cc == "IwFl":
         d, ntotal, _ = _header(r)
-        nlist = r.u64(); r.u64()                        # nprobe
-        _read(r)                                        # coarse quantizer (IndexFlat of the nlist centroids): not needed
+        nlist = r.u64(); nprobe = r.u64()
+        cent, _ = _read(r)                              # coarse quantizer (IndexFlat of the nlist centroids)
         dm_type = r.u8()                                # direct map
         r.vec(np.int64)
         if dm_type == 2:
@@ -102,6 +103,10 @@ def _read(r: _R) -> Tuple[np.ndarray, Optional[np.ndarray]]:
             raise IndexFormatError("unsupported list-size encoding %r" % lt)
         if sizes.size != nlist or int(sizes.sum()) != ntotal:
             raise IndexFormatError("inverted-list sizes do not add up to ntotal")
+        if ivf is not None:
+            if cent.shape != (nlist, d):
+                raise IndexFormatError("coarse quantizer holds %s centroids for nlist %d, d %d" % (cent.shape, nlist, d))
+            ivf.update(nprobe=int(nprobe), centroids=cent, sizes=sizes)
         vs: List[np.ndarray] = []; ids: List[np.ndarray] = []
         for n in sizes:
             n = int(n)
@@ -125,6 +130,41 @@ def read_index(path: str) -> np.ndarray:
     out = np.empty_like(v)
     out[ids] = v
     return out
+
+
+def _ids_in_order(v: np.ndarray, ids: np.ndarray):
+    if ids.size != v.shape[0] or (ids.size and (ids.min() < 0 or ids.max() >= ids.size or np.unique(ids).size != ids.size)):
+        raise IndexFormatError("ids are not a permutation of 0..ntotal-1: cannot reconstruct in id order")
+
+
+def _read_ivf(path: str):
+    ivf: dict = {}
+    with open(path, "rb") as f:
+        v, ids = _read(_R(f), ivf)
+    if not ivf:
+        if ids is not None:
+            _ids_in_order(v, ids)
+            out = np.empty_like(v); out[ids] = v; v = out
+        return np.ascontiguousarray(v), None, None, 0
+    _ids_in_order(v, ids)
+    out = np.empty_like(v)
+    out[ids] = v
+    assign = np.empty(v.shape[0], np.int32)
+    assign[ids] = np.repeat(np.arange(ivf["sizes"].size, dtype=np.int32), ivf["sizes"])
+    return out, np.ascontiguousarray(ivf["centroids"], np.float32), assign, ivf["nprobe"]
+
+
+def read_index_ivf(path: str, with_nprobe: bool = False):
+    """-> (vectors, centroids, assign): `vectors` as read_index returns them; for an IndexIVFFlat file `centroids` (nlist, d) float32 and `assign` (ntotal,) int32,
+    the inverted list that holds row i -- the structure RvcInfer.set_index_ivf takes; (vectors, None, None) for a flat file.  with_nprobe: a fourth value, the
+    nprobe the file stores (upstream's files carry 1; 0 for a flat file), from the same pass over the file."""
+    v, cent, assign, nprobe = _read_ivf(path)
+    return (v, cent, assign, nprobe) if with_nprobe else (v, cent, assign)
+
+
+def read_index_nprobe(path: str) -> int:
+    """the nprobe an IndexIVFFlat file stores (upstream's files carry 1); 0 for a flat file"""
+    return _read_ivf(path)[3]
 
 
 # ----------------------------------------------------------------------------- writers (tests / export)

@@ -111,18 +111,60 @@ class RvcInfer:
         return out[: n.value].copy()
 
     # -- extensions ---------------------------------------------------------------------
-    def load_index(self, vectors):
+    def load_index(self, vectors, nprobe=None):
         """`vectors`: an (n, dim) float32 array, or the path of a Faiss `.index` file (IndexFlat / IndexIVFFlat: the stored
-        vectors are reconstructed in id order, obs_rvc_amd.faiss_index) or of a `.npy` matrix (upstream's total_fea.npy)."""
+        vectors are reconstructed in id order, obs_rvc_amd.faiss_index) or of a `.npy` matrix (upstream's total_fea.npy).
+        `nprobe`: None = the flat search over every row; an integer >= 1 = keep an IndexIVFFlat file's structure and search it as upstream
+        does, that many nearest lists per query (rvc_set_index_ivf + rvc_set_index_nprobe); "file" = the nprobe the file stores.  A source
+        without an IVF structure (an array, a .npy matrix, a flat file) with nprobe >= 1 or "file" raises the RVC_SHAPE error (NdarrayShapeError)
+        before anything is loaded: the engine keeps the index it had."""
+        centroids = assign = None
+        stored = 0
         if isinstance(vectors, (str, os.PathLike)):
             path = os.fspath(vectors)
             if path.endswith(".npy"):
                 vectors = np.load(path)
-            else:
+            elif nprobe is None:
                 from .faiss_index import read_index
                 vectors = read_index(path)
+            else:
+                from .faiss_index import read_index_ivf
+                vectors, centroids, assign, stored = read_index_ivf(path, with_nprobe=True)
+        if nprobe is not None:
+            # decided before anything is loaded, so that a refused call leaves the engine's index as it was: a source without an IVF structure (an array,
+            # a .npy matrix, a flat file) has no lists to probe and no stored value -- the engine's own RVC_SHAPE error for nprobe >= 1 without a structure
+            if isinstance(nprobe, str) and nprobe != "file":
+                raise ValueError('nprobe is an integer or "file"')
+            if centroids is None and (nprobe == "file" or int(nprobe) >= 1):
+                raise RvcInferError(5, "nprobe >= 1 needs an IVF structure: the index source has none")
+            nprobe = int(stored) if nprobe == "file" else int(nprobe)
+            if not 0 <= nprobe <= 64:
+                raise RvcInferError(5, "nprobe must be in [0, 64]")
         v, vp = _f32(vectors)
         self._chk(self._L.rvc_load_index(self._h, vp, v.shape[0], v.shape[1]))
+        if nprobe is not None:
+            if centroids is not None:
+                self.set_index_ivf(centroids, assign)
+            self.set_index_nprobe(nprobe)
+
+    def set_index_ivf(self, centroids, assign):
+        """rvc_set_index_ivf: attach an IVF structure to the loaded index: `centroids` (nlist, dim) float32, `assign` (n,) the list of every row."""
+        c, cp = _f32(centroids)
+        a = np.ascontiguousarray(assign, np.int32)
+        self._chk(self._L.rvc_set_index_ivf(self._h, cp, c.shape[0], c.shape[1], a.ctypes.data_as(C.POINTER(C.c_int32)), a.shape[0]))
+
+    def set_index_nprobe(self, k: int):
+        """rvc_set_index_nprobe: 0 = flat search, 1..64 = probe that many lists of the attached IVF structure (clamped to its nlist)."""
+        self._chk(self._L.rvc_set_index_nprobe(self._h, int(k)))
+
+    def index_nprobe(self) -> int:
+        return int(self._L.rvc_index_nprobe(self._h))
+
+    def index_ivf_info(self):
+        """(nlist, rows of the longest list, empty lists) of the attached IVF structure"""
+        a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._chk(self._L.rvc_index_ivf_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def rccl_unique_id(self) -> bytes:
         """rvc_rccl_unique_id: rank 0 creates the 128-byte ncclUniqueId the host then hands to the other ranks."""
