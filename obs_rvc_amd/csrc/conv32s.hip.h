@@ -17,25 +17,18 @@
 
 namespace rvc {
 
-// The epilogue of the family (one body for conv32s_kernel and conv32s_buf_kernel): igemm32_kernel's C / D layout -- col = lane & 31,
-// row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) --, bias -> activation -> residual -> scale (-> accumulate); full tiles without accumulation take the
-// straight-line path (operands in store-free batches, one predicate per column block), everything else the general one.
-template <int WM, int WN, int MT, int NT>
-__device__ __forceinline__ void c32s_epilogue(const IgemmP &p, const PhaseD &ph, f32x16 (&acc)[MT][NT], const int tm, const int tn, const int wm, const int wn, const int c32,
-                                              const int ks, const int b)
+// The epilogue of the family (one body for conv32s_kernel, conv32s_buf_kernel and conv_tile.hip.h's 32x32x2 body): igemm32_kernel's C / D layout -- col = lane & 31,
+// row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) --, bias -> activation -> residual -> scale (-> accumulate); full tiles take the straight-line path
+// (operands in store-free batches, one predicate per column block), everything else the general one.  c32s_epilogue_at is the body on located columns:
+// row0 = the lane's first row (tile row + 4 * (lane >> 5)), yb = the stream's output tensor, act_sel = the activation of this launch / phase.
+template <int MT, int NT>
+__device__ __forceinline__ void c32s_epilogue_at(const IgemmP &p, const PhaseD &ph, f32x16 (&acc)[MT][NT], const ColOut (&cols)[NT], const int row0, const bool full_m,
+                                                 const float *resb, float *yb, const int act_sel)
 {
-    constexpr int BN = WN * NT * 32;
-    const float *resb = p.res ? p.res + (long long)b * p.res_bs : nullptr;
-    float *yb = p.y + (long long)b * p.y_bs;
-    ColOut cols[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) cols[nt] = col_locate(p, ph, tn * BN + (wn * NT + nt) * 32 + c32);
-    const int row0 = (tm * WM + wm) * MT * 32 + ks * 4;
-    const bool full_m = row0 - ks * 4 + MT * 32 <= p.M;
     if (full_m) {
         const float slope = p.slope, scale = p.scale;
         const long long cs = p.y_cs, rcs = p.res_cs;
-        RVC_ACT_DISPATCH(
+        RVC_ACT_DISPATCH_SEL(act_sel,
             _Pragma("unroll") for (int mt = 0; mt < MT; mt++) {
                 const int m0 = row0 + mt * 32;
                 float bias_r[16];
@@ -61,7 +54,7 @@ __device__ __forceinline__ void c32s_epilogue(const IgemmP &p, const PhaseD &ph,
         )
         return;
     }
-    RVC_ACT_DISPATCH(
+    RVC_ACT_DISPATCH_SEL(act_sel,
         _Pragma("unroll") for (int mt = 0; mt < MT; mt++) {
             float bias_r[16];
             _Pragma("unroll") for (int r = 0; r < 16; r++) {
@@ -78,6 +71,18 @@ __device__ __forceinline__ void c32s_epilogue(const IgemmP &p, const PhaseD &ph,
             }
         }
     )
+}
+
+template <int WM, int WN, int MT, int NT>
+__device__ __forceinline__ void c32s_epilogue(const IgemmP &p, const PhaseD &ph, f32x16 (&acc)[MT][NT], const int tm, const int tn, const int wm, const int wn, const int c32,
+                                              const int ks, const int b)
+{
+    constexpr int BN = WN * NT * 32;
+    ColOut cols[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; nt++) cols[nt] = col_locate(p, ph, tn * BN + (wn * NT + nt) * 32 + c32);
+    const int row0 = (tm * WM + wm) * MT * 32 + ks * 4;
+    c32s_epilogue_at<MT, NT>(p, ph, acc, cols, row0, row0 - ks * 4 + MT * 32 <= p.M, p.res ? p.res + (long long)b * p.res_bs : nullptr, p.y + (long long)b * p.y_bs, p.act);
 }
 
 // (2 x 2 accumulator blocks per wave + the staging registers of the next block pass 170 registers: two waves per SIMD there, three for the 1 x 2 tiles

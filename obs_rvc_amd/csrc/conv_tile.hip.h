@@ -16,8 +16,25 @@
 // Work items (phase, m-tile, n-tile) are handed to workgroups through a table built at plan time: the hardware places workgroup b on
 // CU b % 256 (tests/tools/place_probe.hip), so the table pairs long items (kernel size 11) with short ones (kernel size 3) on a CU
 // instead of leaving the balance to the dispatch order.
+//
+// Two bodies share the item table, the IgemmP / PhaseD fields and the epilogue semantics (bias -> activation -> residual -> scale -> accumulate, y_c0
+// grouping, per-phase activation and output, nothing written outside the output interior):
+//   conv_tile_kernel    16x16x4 fragments, the whole [Cin][BN + reach] input staged once (above); LDS grows with Cin (up to 100 KB).
+//   conv_tile32_kernel  32x32x2 fragments, conv32s_kernel's scheme cut to one-stream items: K is walked (32-channel block, tap, channel group)-major
+//                       from the per-model panels of c32s_panel (no repack per plan), the block [32][BN + reach] is staged once per block with the
+//                       input LeakyReLU applied once, the B operand is one ds_read_b128 per four k-steps.  A 32x32x2 MFMA needs half the operand
+//                       reads per flop of a 16x16x4 one, and a tile stages BN + reach columns for BN = 32 .. 128 outputs instead of 16 .. 64.
+//                       Every wave owns ONE 32 x 32 accumulator; tiles (WM x WN waves, KS K shares; four waves always):
+//                         128 x 32 (4, 1, 1), 64 x 64 (2, 2, 1), 32 x 128 (1, 4, 1): the waves split M, then N;
+//                         64 x 32 (2, 1, 2), 32 x 64 (1, 2, 2): half the height, the freed waves take the odd 16-deep chunk of every tap (channel
+//                         group 1 of the block), summed in one fixed-order LDS reduction at the end -- the forms whose item count and length match
+//                         the 16x16x4 tiles', i.e. the ones the one-stream item table balances.
+//                       LDS: two buffers (block b + 1 is written while block b is read: one barrier per block change) of (BN + reach) x 36 floats,
+//                       reach = (KW - 1) * dil <= 64, independent of Cin; at the decoder's reach of 50: BN = 32 23 616 B, BN = 64 32 832 B,
+//                       BN = 128 51 264 B (the K shares' reduction, 8 KB, reuses them).
 #pragma once
 #include "igemm.hip.h"
+#include "conv32s.hip.h"
 
 namespace rvc {
 
@@ -225,5 +242,158 @@ __global__ __launch_bounds__(64 * WM * WN * KS) __attribute__((amdgpu_waves_per_
     RVC_KP(6);
 }
 #undef COMMA_
+
+// ------------------------------------------------------------------------------------------------------------------------
+// conv_tile32_kernel -- the 32x32x2 body (header comment).  Weight layout: c32s_panel's [m_tile16][chunk][lane16x4][4], chunk = (block * KW + tap) * 2 + group.
+// A wave walks ITS chunks i = 0 .. nloc - 1 (global chunk i * KS + kh: with two K shares the share is the channel group) with the weights of DA chunks in
+// flight in a register ring and the next chunk's B operand requested between the MFMAs of the current one.
+template <int WM, int WN, int KS>
+__global__ __launch_bounds__(256) void conv_tile32_kernel(IgemmP p)
+{
+    static_assert(WM * WN * KS == 4 && (KS == 1 || KS == 2), "four waves: WM x WN accumulators, one or two K shares");
+    constexpr int WPS = WM * WN;                    // waves per K share
+    constexpr int BN = WN * 32;
+    constexpr int CB = 32, CS = CB + 4;             // channels staged per block, LDS column stride in floats (conv32s_kernel's)
+    constexpr int DA = 4;                           // weight chunks in flight per wave (DA * KS <= the 16 chunks of slack behind a panel)
+    constexpr int NCP = BN + 64, NI = (CB / 4) * NCP / 256;      // staging item grid [CB / 4 channel quads][NCP columns], NI items per thread
+    static_assert((CB / 4) * NCP % 256 == 0, "item grid must divide over the workgroup");
+    extern __shared__ __attribute__((aligned(16))) float s_x32[];      // 2 x [BN + (KW - 1) * dil][CS]
+    const int item = p.items[2 * blockIdx.x];
+    if (item < 0) return;
+    const int phase = item & 0xff, tm = (item >> 8) & 0xff, tn = item >> 16;
+    const int b = p.items[2 * blockIdx.x + 1];
+    const PhaseD ph = p.nphase == 1 ? p.ph0 : p.ph[phase];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int kh = wave / WPS, w4 = wave % WPS;     // K share, wave inside the share
+    const int wm = w4 / WN, wn = w4 % WN;
+    const int c32 = lane & 31, ks = lane >> 5;
+    // (the phase descriptor comes through a select: its fields are forced scalar so that the loops below are scalar loops -- conv32s_buf_kernel)
+    const int nchunks = __builtin_amdgcn_readfirstlane(ph.nchunks);
+    const int t_tab = __builtin_amdgcn_readfirstlane(ph.t_tab);
+    const int kw = t_tab & 0xff, dil = t_tab >> 8;
+    const int nblk = __builtin_amdgcn_readfirstlane(ph.t_cin) / CB;
+    const int ncol = BN + (kw - 1) * dil;
+    const int bufsz = ncol * CS;                    // floats per staging buffer
+    const int nq = kw * 2 / KS;                     // this wave's chunks per block
+    const int nloc = nblk * nq;
+    // weights: the lane's float4 of chunk c, half u (k-slot ks: channels (2u + ks) * 4 .. + 3 of the chunk) = wl[c * 256 + u * 128 ..]
+    const int mtiles = (p.M + 15) >> 4;
+    int t16 = (tm * WM + wm) * 2 + (c32 >> 4);
+    t16 = t16 < mtiles ? t16 : mtiles - 1;
+    const float *wl = p.w + ph.w_off + (long long)t16 * nchunks * 256 + (ks * 16 + (c32 & 15)) * 4 + kh * 256;
+    f32x4 a_st[DA][2];
+#pragma unroll
+    for (int s = 0; s < DA; s++)
+#pragma unroll
+        for (int u = 0; u < 2; u++) a_st[s][u] = *reinterpret_cast<const f32x4 *>(wl + s * KS * 256 + u * 128);      // (past the wave's last chunk: the slack behind the panel)
+    const float *wnext = wl + DA * KS * 256;
+    // staging items of this thread: channel quad qd, staged column s_ (conv32s_kernel's request / commit with a per-thread item map: NCP is no multiple of 64 here)
+    const float pre_slope = p.pre_slope;
+    const float *xb = p.x + (long long)b * p.x_bs + ph.x_off;
+    const int n0 = tn * BN + ph.t_dmin;
+    int xo[NI], lo[NI];
+#pragma unroll
+    for (int r = 0; r < NI; r++) {
+        const int e = r * 256 + (int)threadIdx.x;
+        const int qd = e / NCP, s_ = e - qd * NCP;
+        int gc = n0 + (s_ < ncol ? s_ : ncol - 1);       // (columns past the tile's reach re-read its last one and are not stored)
+        gc = gc < p.x_lo ? p.x_lo : (gc > p.x_lim ? p.x_lim : gc);
+        xo[r] = qd * 4 * p.x_ld + gc;
+        lo[r] = s_ < ncol ? s_ * CS + qd * 4 : -1;
+    }
+    f32x4 pf[NI];
+    auto request = [&](const int blk) {
+        const float *xk = xb + (long long)blk * CB * p.x_ld;
+#pragma unroll
+        for (int r = 0; r < NI; r++)
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) pf[r][jj] = xk[xo[r] + jj * p.x_ld];
+    };
+    auto commit = [&](float *dst) {
+#pragma unroll
+        for (int r = 0; r < NI; r++) {
+            f32x4 v;
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) v[jj] = fmaxf(pf[r][jj], pf[r][jj] * pre_slope);
+            if (lo[r] >= 0) *reinterpret_cast<f32x4 *>(dst + lo[r]) = v;
+        }
+    };
+    request(0);
+    f32x16 acc[1][1];
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[0][0][r] = 0.f;
+    const float *bl = s_x32 + (wn * 32 + c32) * CS + ks * 4 + (KS == 2 ? kh * 16 : 0);      // B operand base of this lane
+    const int tap_step = dil * CS;
+    int q = 0, blk = 0;                              // chunk inside the block, block
+    const float *bq = bl;                            // B operand of the current chunk
+    f32x4 bcur[2], bnx[2];
+    bnx[0] = bnx[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // One chunk: (first of a block: write the staged rows -- requested a block earlier -- into the buffer the block before last was read from, barrier,
+    // request the next block's rows), eight MFMAs with the next chunk's B operand requested behind the first, then the ring slot's reload.
+#define RVC_CT32_STEP(S)                                                                               \
+    {                                                                                                  \
+        if (q == 0) {                                                                                  \
+            float *dst_ = s_x32 + (blk & 1) * bufsz;                                                   \
+            commit(dst_);                                                                              \
+            __syncthreads();                                                                           \
+            if (blk + 1 < nblk) request(blk + 1);                                                      \
+            bq = bl + (blk & 1) * bufsz;                                                               \
+            bcur[0] = *reinterpret_cast<const f32x4 *>(bq);                                            \
+            bcur[1] = *reinterpret_cast<const f32x4 *>(bq + 8);                                        \
+        }                                                                                              \
+        const float *bqn_ = bq + (KS == 2 ? tap_step : ((q & 1) ? tap_step - 16 : 16));                \
+        const bool more_ = q + 1 < nq;                                                                 \
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_st[S][0][0], bcur[0][0], acc[0][0], 0, 0, 0); \
+        if (more_) {                                                                                   \
+            bnx[0] = *reinterpret_cast<const f32x4 *>(bqn_);                                           \
+            bnx[1] = *reinterpret_cast<const f32x4 *>(bqn_ + 8);                                       \
+        }                                                                                              \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
+        _Pragma("unroll") for (int j = 1; j < 4; j++)                                                  \
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_st[S][0][j], bcur[0][j], acc[0][0], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < 4; j++)                                                  \
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_st[S][1][j], bcur[1][j], acc[0][0], 0, 0, 0); \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
+        /* the weights are reloaded BEHIND their last use (conv_tile_kernel, round 5) */               \
+        a_st[S][0] = *reinterpret_cast<const f32x4 *>(wnext);                                          \
+        a_st[S][1] = *reinterpret_cast<const f32x4 *>(wnext + 128);                                    \
+        wnext += KS * 256;                                                                             \
+        bq = bqn_; bcur[0] = bnx[0]; bcur[1] = bnx[1];                                                 \
+        if (++q == nq) { q = 0; blk++; }                                                               \
+    }
+    int c = 0;
+    for (; c + DA <= nloc; c += DA) {
+#pragma unroll
+        for (int s = 0; s < DA; s++) RVC_CT32_STEP(s)
+    }
+#pragma unroll
+    for (int s = 0; s < DA; s++)
+        if (c + s < nloc) RVC_CT32_STEP(s)
+#undef RVC_CT32_STEP
+    if (KS == 2) {
+        // the odd-group waves hand their partial sums over through LDS, summed in one fixed order
+        __syncthreads();                               // every wave has left the last block's tile
+        f32x4 *red = reinterpret_cast<f32x4 *>(s_x32) + w4 * 4 * 64 + lane;
+        if (kh) {
+#pragma unroll
+            for (int r4 = 0; r4 < 4; r4++) red[r4 * 64] = (f32x4){acc[0][0][r4 * 4], acc[0][0][r4 * 4 + 1], acc[0][0][r4 * 4 + 2], acc[0][0][r4 * 4 + 3]};
+        }
+        __syncthreads();
+        if (kh) return;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; r4++) {
+            const f32x4 o = red[r4 * 64];
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[0][0][r4 * 4 + j] += o[j];
+        }
+    }
+    // epilogue: conv32s's body on this family's terms (per-phase output tensor and activation)
+    ColOut cols[1];
+    cols[0] = col_locate(p, ph, tn * BN + wn * 32 + c32);
+    const int row_t = (tm * WM + wm) * 32;
+    c32s_epilogue_at<1, 1>(p, ph, acc, cols, row_t + ks * 4, row_t + 32 <= p.M, p.res ? p.res + (long long)b * p.res_bs : nullptr, p.y + (long long)b * p.y_bs + ph.y_off,
+                           ph.act_p1 ? ph.act_p1 - 1 : p.act);
+}
 
 }  // namespace rvc

@@ -29,6 +29,9 @@ void launch_igemm_tiled_p3(int lc, bool pre, const IgemmP &p, dim3 grid, size_t 
 // conv_tile_kernel (conv_tile.hip.h) tiles: 0 = 128 x 16 (four waves stacked in M), 1 = 64 x 32, 2 = 32 x 64 (2 x 2 waves), each with one or two K shares.
 // WF = waves per K share x MF x NF.
 static const int kTileBM[3] = {128, 64, 32}, kTileBN[3] = {16, 32, 64}, kTileWF[3] = {8, 8, 8};
+// conv_tile32_kernel (the family's 32x32x2 body: one 32 x 32 accumulator per wave, four waves) is tiles 3 .. 7 of launch_conv_tile, index - 3 here:
+// 128 x 32, 64 x 64, 32 x 128 (the waves split M, then N) and the half-height 64 x 32, 32 x 64 whose freed waves take the odd chunk of every tap.
+static const int kTile32BM[5] = {128, 64, 32, 64, 32}, kTile32BN[5] = {32, 64, 128, 32, 64}, kTile32KS[5] = {1, 1, 1, 2, 2};
 void conv_tile_prepare_device();
 void launch_conv_tile(int tile, int kshares, const IgemmP &p, dim3 grid, size_t lds, hipStream_t s, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr);
 

@@ -16,7 +16,7 @@ static const TestHook kTestHooks[] = {
     {"RVC_G32L", true}, {"RVC_G32L_TALL", true}, {"RVC_G32L_TAB", true}, {"RVC_CONV32S_BUF", true}, {"RVC_FORCE_CHOICE", true},
     {"RVC_G32L_PANEL", true}, {"RVC_MEAN3", false}, {"RVC_RM_FUSE", false}, {"RVC_G2W_LN", false}, {"RVC_RELPOS_MFMA_MAX", false},
     {"RVC_ATTN_KERNEL", false}, {"RVC_RELPOS_KERNEL", false}, {"RVC_LN_KERNEL", false}, {"RVC_GRU_KERNEL", false}, {"RVC_CONV0_KERNEL", false},
-    {"RVC_YIN_CV_ALL_CUS", false}, {"RVC_KNN_WGS", true}
+    {"RVC_YIN_CV_ALL_CUS", false}, {"RVC_KNN_WGS", true}, {"RVC_CONV_TILE_MFMA", true}
 };
 std::atomic<unsigned> g_opt_gen{0};       // bumped by every rvc_debug_option call: plans built under another generation are dropped (engine.hip get_plan)
 static std::mutex g_opt_mu;
@@ -331,65 +331,12 @@ static bool decode_taps(PhaseD &q, const std::vector<int> &koff, const IgemmP &p
     return true;
 }
 
-// One stream, stride-1 1-D convolution with a long output: conv_tile_kernel (conv_tile.hip.h) stages the input rows once per workgroup.
-// Builds the LDS-offset tables (k -> row * RS + tap column) from the layer's gather table and a work-item table that balances the
-// unequal phases of a fused launch over the CUs (workgroup b lands on CU b % ncu: tests/tools/place_probe.hip).  false = not eligible.
-static bool queue_conv_tile(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &phv)
+// The work-item table of the conv_tile family: items (weight w, code = phase | m-tile << 8 | n-tile << 16, stream b), longest first, dealt to the CUs by
+// longest-processing-time; block r * ncu + j = the r-th item of CU j.  Returns the uploaded (code, stream) pairs and their count (= the grid).
+struct TileItem { int w, code, b; };
+static const int *conv_tile_items(Plan &pl, std::vector<TileItem> &items, unsigned *grid)
 {
-    const int mode = c.ch.kind ? 0 : test_opt_int("RVC_CONV_TILE", 1);       // test hook: 0 = off, 2 = wherever eligible; read per plan
-    // streams: one always; two to four with the same narrow tiles and the streams in the item table (measured -1 % / -2 % at 2 / 4 streams, nothing at
-    // 8; wider tiles for many streams measured slower than the 32x32x2 kernels and are gone)
-    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.lin_cs4 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part) return false;
-    if (B > 4) return false;
-    if (p.M > 128 && mode < 2) return false;
-    const int kshares = test_opt_int("RVC_CONV_TILE_KS", 2);      // test hook: 1 = one wave per fragment set
-    const int tc0 = p.M > 64 ? 0 : (p.M > 32 ? 1 : 2);            // 128 x 16, 64 x 32, 32 x 64
-    const int BM = kTileBM[tc0], BN = kTileBN[tc0];
-    const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-    if (ntm > 255 || ntn > 32767 || phv.size() > 255) return false;
-    const long long nitems = (long long)ntm * ntn * (long long)phv.size() * B;
-    if (mode < 2 && nitems < 3 * g_ncu / 2) return false;                // short outputs: the K-split kernel fills the chip better
-    // per phase: (channel, tap) of every k from the gather table; the kernel walks K tap-major in chunks of 16 channels, so the phase's weights are
-    // repacked: chunk t * G + g, slot kk <- k = (g * 16 + kk) * KW + t
-    std::vector<PhaseD> phs(phv);
-    std::vector<float> wnew;
-    size_t lds_max = 0;
-    const int mt = (p.M + 15) / 16;
-    for (PhaseD &q : phs) {
-        if (!decode_taps(q, c.koff, p, 16)) return false;
-        const int KW = q.t_tab & 0xff, dil = q.t_tab >> 8, cin = q.t_cin;
-        const int rl = BN + (KW - 1) * dil, rt = rl | 1, cs = cin + 8;
-        q.t_rs = rt;
-        if (q.nchunks < 2 || cin / 16 < kshares) return false;          // (every K share needs a chunk; the kernel steps its tap / group counters by the share count)
-        lds_max = std::max(lds_max, (std::max<size_t>(((size_t)cin * rt + 63) / 64 * 64, (size_t)kTileWF[tc0] * 256) + (size_t)rl * cs) * 4);
-        std::vector<float> wold((size_t)mt * q.nchunks * 256);
-        HIPCHK(hipMemcpy(wold.data(), p.w + q.w_off, wold.size() * 4, hipMemcpyDeviceToHost));
-        const size_t base = wnew.size();
-        wnew.resize(base + wold.size());
-        const int G = cin / 16;
-        for (int t = 0; t < mt; t++)
-            for (int tap = 0; tap < KW; tap++)
-                for (int g = 0; g < G; g++)
-                    for (int l = 0; l < 64; l++)
-                        for (int j = 0; j < 4; j++) {
-                            const int k = (g * 16 + (l >> 4) * 4 + j) * KW + tap;          // the source's k
-                            wnew[base + (((size_t)t * q.nchunks + tap * G + g) * 64 + l) * 4 + j] =
-                                wold[(((size_t)t * q.nchunks + k / 16) * 64 + (((k % 16) / 4) << 4 | (l & 15))) * 4 + (k % 4)];
-                        }
-        q.w_off = (long long)base;
-    }
-    if (lds_max > 100 * 1024) return false;
-    Plan &pl = c.pl;
-    wnew.resize(wnew.size() + (size_t)16 * 2 * 256, 0.f);      // slack: the kernel's weight requests run DA x KS chunks past a wave's last chunk
-    p.w = pl.arena.upload(wnew);
-    // work items, longest first, dealt to the CUs by longest-processing-time; block r * ncu + j = the r-th item of CU j
-    struct It { int w, code, b; };
-    std::vector<It> items;
-    for (int bb = 0; bb < B; bb++)
-        for (size_t f = 0; f < phs.size(); f++)
-            for (int tm = 0; tm < ntm; tm++)
-                for (int tn = 0; tn < ntn; tn++) items.push_back({phs[f].nchunks + 12, (int)f | (tm << 8) | (tn << 16), bb});
-    std::stable_sort(items.begin(), items.end(), [](const It &a, const It &b) { return a.w > b.w; });
+    std::stable_sort(items.begin(), items.end(), [](const TileItem &a, const TileItem &b) { return a.w > b.w; });
     const int nb = g_ncu;
     std::vector<std::vector<int>> bins(nb);          // indices into items
     {
@@ -417,11 +364,126 @@ static bool queue_conv_tile(GemmCall &c, IgemmP p, int B, const std::vector<Phas
         const std::vector<int> &bn = bins[slot_bin(j)];
         for (size_t r = 0; r < bn.size(); r++) { order[(r * nb + j) * 2] = items[bn[r]].code; order[(r * nb + j) * 2 + 1] = items[bn[r]].b; }
     }
-    p.items = pl.arena.upload(order);
+    *grid = (unsigned)(order.size() / 2);
+    return pl.arena.upload(order);
+}
+
+// The family's 32x32x2 body (conv_tile32_kernel) on a layer queue_conv_tile has found eligible and decoded: tile by the panel height, weights from the
+// per-model panel cache (c32s_panel: nothing is copied to the host), the same item table with this body's item lengths.
+static void queue_conv_tile32(GemmCall &c, IgemmP p, int B, std::vector<PhaseD> &phs, int kshares)
+{
+    // half-height tiles with two K shares by default (item count and length of the 16x16x4 tiles: what the one-stream table balances); RVC_CONV_TILE_KS = 1:
+    // the waves split M, then N
+    const int t32 = kshares == 2 ? (p.M > 32 ? 3 : 4) : (p.M > 64 ? 0 : (p.M > 32 ? 1 : 2));
+    const int BM = kTile32BM[t32], BN = kTile32BN[t32], KS = kTile32KS[t32];
+    const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
+    size_t lds = (size_t)(4 / KS) * 4096 * (KS - 1);          // the K shares' reduction: 16 floats per lane of the odd-group waves
+    const float *w0 = nullptr;
+    for (PhaseD &q : phs) {
+        const int KW = q.t_tab & 0xff, dil = q.t_tab >> 8;
+        q.t_rs = 0;
+        lds = std::max(lds, (size_t)2 * (BN + (KW - 1) * dil) * kC32sCS * 4);
+        const float *panel = c32s_panel(p.w + q.w_off, p.M, q.nchunks, q.t_cin, KW);
+        if (!w0) w0 = panel;
+        q.w_off = panel - w0;          // (device pointers of one flat address space)
+    }
+    p.w = w0;
+    Plan &pl = c.pl;
+    // item length in 16-deep chunks of the panel: the chunks themselves, ~12 of prologue + epilogue (the 16x16x4 body's figure), and one block change
+    // (write the staged rows, barrier, first B read: about one chunk of a wave, i.e. KS of the panel) per 32-channel block
+    std::vector<TileItem> items;
+    for (int bb = 0; bb < B; bb++)
+        for (size_t f = 0; f < phs.size(); f++)
+            for (int tm = 0; tm < ntm; tm++)
+                for (int tn = 0; tn < ntn; tn++) items.push_back({phs[f].nchunks + 12 + KS * (phs[f].t_cin / kC32sCB), (int)f | (tm << 8) | (tn << 16), bb});
+    const long long nitems = (long long)items.size();
+    unsigned gx = 0;
+    p.items = conv_tile_items(pl, items, &gx);
+    p.ttab = nullptr; p.koff = nullptr;
+    set_phases(pl, p, phs);
+    p.ntm = ntm; p.ntn = ntn; p.ksplit = 1; p.nbatch = B; p.m_fast = 0;
+    const dim3 grid(gx, 1u);
+    char d[200];
+    snprintf(d, sizeof d, "tile M=%d N=%d K=%d B=%d nph=%d tile=%dx%d mfma=32 ks=%d items=%lld grid=%u lds=%zu pre=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, BM, BN, KS, nitems, grid.x, lds,
+             (int)(p.pre_act != ACT_NONE), c.ksum);
+    queue_gemm_launch(pl, d, 2.0 * p.M * (double)p.N * c.ksum * B, (int)nitems, 4, c.final_out, p,
+                      [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) { launch_conv_tile(3 + t32, KS, q, grid, lds, s, ea, eb); });
+}
+
+// One stream, stride-1 1-D convolution with a long output: the conv_tile family (conv_tile.hip.h) stages the input rows once per workgroup.
+// Decodes the phases' taps from the layer's gather table and builds a work-item table that balances the unequal phases of a fused launch over the
+// CUs (workgroup b lands on CU b % ncu: tests/tools/place_probe.hip).  Two bodies: 16x16x4 fragments on the whole staged input (weights repacked
+// per plan), 32x32x2 fragments on 32-channel blocks (queue_conv_tile32) for layers whose channels come in 32s.  false = not eligible.
+static bool queue_conv_tile(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &phv)
+{
+    const int mode = c.ch.kind ? 0 : test_opt_int("RVC_CONV_TILE", 1);       // test hook: 0 = off, 2 = wherever eligible; read per plan
+    // streams: one always; two to four with the same narrow tiles and the streams in the item table (measured -1 % / -2 % at 2 / 4 streams, nothing at
+    // 8; wider tiles for many streams measured slower than the 32x32x2 kernels and are gone)
+    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.lin_cs4 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part) return false;
+    if (B > 4) return false;
+    if (p.M > 128 && mode < 2) return false;
+    const int kshares = test_opt_int("RVC_CONV_TILE_KS", 2);      // test hook: 1 = one wave per fragment set
+    const int tc0 = p.M > 64 ? 0 : (p.M > 32 ? 1 : 2);            // 128 x 16, 64 x 32, 32 x 64
+    const int BM = kTileBM[tc0], BN = kTileBN[tc0];
+    const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
+    if (ntm > 255 || ntn > 32767 || phv.size() > 255) return false;
+    const long long nitems = (long long)ntm * ntn * (long long)phv.size() * B;
+    if (mode < 2 && nitems < 3 * g_ncu / 2) return false;                // short outputs: the K-split kernel fills the chip better
+    // eligibility is that of the 16x16x4 body for BOTH bodies (one rule per family: the 32x32x2 body takes a subset of these layers)
+    std::vector<PhaseD> phs(phv);
+    size_t lds_max = 0;
+    bool can32 = (p.M + 31) / 32 <= 255;          // (m-tiles of the 32x32x2 body's lowest tile: eight bits of an item)
+    for (PhaseD &q : phs) {
+        if (!decode_taps(q, c.koff, p, 16)) return false;
+        const int KW = q.t_tab & 0xff, dil = q.t_tab >> 8, cin = q.t_cin;
+        const int rl = BN + (KW - 1) * dil, rt = rl | 1, cs = cin + 8;
+        q.t_rs = rt;
+        if (q.nchunks < 2 || cin / 16 < kshares) return false;          // (every K share needs a chunk; the kernel steps its tap / group counters by the share count)
+        lds_max = std::max(lds_max, (std::max<size_t>(((size_t)cin * rt + 63) / 64 * 64, (size_t)kTileWF[tc0] * 256) + (size_t)rl * cs) * 4);
+        can32 = can32 && cin % kC32sCB == 0 && (KW - 1) * dil <= 64;     // (32-channel blocks; the staging grid covers BN + 64 columns)
+    }
+    if (lds_max > 100 * 1024) return false;
+    // Body: test hook RVC_CONV_TILE_MFMA = 16 | 32 (read per plan), else the rule per panel height ("The conv_tile family on 32x32x2
+    // fragments"): at one stream the 128- / 64- / 32-row decoder stages measured 26.8 / 16.2 / 11.7 -> 25.0 / 15.0 / 9.7 us per launch, so every height from 32
+    // rows takes the new body; lower panels and the 2-4 stream plans were not measured with it and keep the old one.
+    const int body_opt = test_opt_int("RVC_CONV_TILE_MFMA", 0);
+    const bool rule32 = B == 1 && p.M >= 32;
+    if (can32 && (body_opt == 32 || (body_opt != 16 && rule32))) { queue_conv_tile32(c, p, B, phs, kshares == 2 ? 2 : 1); return true; }
+    // 16x16x4 body: the kernel walks K tap-major in chunks of 16 channels, so the phase's weights are repacked: chunk t * G + g, slot kk <- k = (g * 16 + kk) * KW + t
+    std::vector<float> wnew;
+    const int mt = (p.M + 15) / 16;
+    for (PhaseD &q : phs) {
+        const int KW = q.t_tab & 0xff, cin = q.t_cin;
+        std::vector<float> wold((size_t)mt * q.nchunks * 256);
+        HIPCHK(hipMemcpy(wold.data(), p.w + q.w_off, wold.size() * 4, hipMemcpyDeviceToHost));
+        const size_t base = wnew.size();
+        wnew.resize(base + wold.size());
+        const int G = cin / 16;
+        for (int t = 0; t < mt; t++)
+            for (int tap = 0; tap < KW; tap++)
+                for (int g = 0; g < G; g++)
+                    for (int l = 0; l < 64; l++)
+                        for (int j = 0; j < 4; j++) {
+                            const int k = (g * 16 + (l >> 4) * 4 + j) * KW + tap;          // the source's k
+                            wnew[base + (((size_t)t * q.nchunks + tap * G + g) * 64 + l) * 4 + j] =
+                                wold[(((size_t)t * q.nchunks + k / 16) * 64 + (((k % 16) / 4) << 4 | (l & 15))) * 4 + (k % 4)];
+                        }
+        q.w_off = (long long)base;
+    }
+    Plan &pl = c.pl;
+    wnew.resize(wnew.size() + (size_t)16 * 2 * 256, 0.f);      // slack: the kernel's weight requests run DA x KS chunks past a wave's last chunk
+    p.w = pl.arena.upload(wnew);
+    std::vector<TileItem> items;
+    for (int bb = 0; bb < B; bb++)
+        for (size_t f = 0; f < phs.size(); f++)
+            for (int tm = 0; tm < ntm; tm++)
+                for (int tn = 0; tn < ntn; tn++) items.push_back({phs[f].nchunks + 12, (int)f | (tm << 8) | (tn << 16), bb});
+    unsigned gx = 0;
+    p.items = conv_tile_items(pl, items, &gx);
     p.ttab = nullptr;
     set_phases(pl, p, phs);
     p.ntm = ntm; p.ntn = ntn; p.ksplit = 1; p.nbatch = B; p.m_fast = 0;
-    const dim3 grid((unsigned)(order.size() / 2), 1u);
+    const dim3 grid(gx, 1u);
     char d[200];
     snprintf(d, sizeof d, "tile M=%d N=%d K=%d B=%d nph=%d tile=%dx%d items=%lld grid=%u lds=%zu pre=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, BM, BN, nitems, grid.x, lds_max, (int)(p.pre_act != ACT_NONE), c.ksum);
     queue_gemm_launch(pl, d, 2.0 * p.M * (double)p.N * c.ksum * B, (int)nitems, 4, c.final_out, p,
