@@ -20,6 +20,10 @@ int rvc_debug_option(const char *name, const char *value);
 int rvc_debug_stamps(rvc_engine *e, char *buf, size_t cap);
 /* launches (ops) of the last call's plan */
 int rvc_debug_last_plan(rvc_engine *e, int *n_ops);
+/* the named tap (rvc_enable_taps) of one stream of the last call, as rvc_get_tap returns stream 0's: plans built with taps on snapshot every stream of a
+ * tapped tensor.  RVC_SHAPE for a stream the plan did not have (and for streams > 0 of the taps that hold the whole plan in one tensor: "pitchf",
+ * "phone_prot", "phone_blend", "cv.out_all"); else as rvc_get_tap */
+int rvc_debug_tap(rvc_engine *e, const char *name, int stream, float *out, size_t cap, size_t *n);
 /* one line per profiled launch of the last call: "<us> <gflop> <description>" */
 int rvc_debug_profile_dump(rvc_engine *e, char *buf, size_t cap);
 /* one Conv1d / one Conv2d 3x3 or ConvTranspose2d 3x3 stride 2 / the folded-LayerNorm launch pair on deterministic data through whatever kernel

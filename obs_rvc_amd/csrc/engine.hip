@@ -1416,36 +1416,46 @@ rvc_status rvc_profile_last_knn(rvc_engine *e, int *launches, double *kernel_ms,
     });
 }
 
-rvc_status rvc_get_tap(rvc_engine *e, const char *name, float *out, size_t cap, size_t *n)
+// the named tap of one stream of the last call's plan (snapshots and RMVPE images hold every stream of the plan, stream-major)
+static rvc_status read_tap(rvc_engine *e, const char *name, int stream, float *out, size_t cap, size_t *n)
 {
     return guarded(e, [&]() {
         Plan *pl = e->last_plan;
-        if (!pl) return RVC_SHAPE;
+        if (!pl || !name) return RVC_SHAPE;
+        if (stream < 0 || stream >= pl->B) { e->err = "tap: the last call's plan has no such stream"; return RVC_SHAPE; }
         HIPCHK(hipDeviceSynchronize());
         for (auto &t : pl->taps) {
             if (t.name != name) continue;
             if (t.rank == 1) {
+                if (stream >= t.t1.B) { e->err = std::string("tap ") + name + " is one tensor for the whole plan: stream 0 holds it"; return RVC_SHAPE; }
                 size_t need = (size_t)t.t1.C * t.t1.T; if (n) *n = need;
                 if (cap < need) return RVC_SHAPE;
-                HIPCHK(hipMemcpy2D(out, (size_t)t.t1.T * 4, t.t1.p, (size_t)t.t1.ld * 4, (size_t)t.t1.T * 4, t.t1.C, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy2D(out, (size_t)t.t1.T * 4, t.t1.p + (long long)stream * t.t1.bs, (size_t)t.t1.ld * 4, (size_t)t.t1.T * 4, t.t1.C, hipMemcpyDeviceToHost));
             } else {
+                if (stream >= t.t2.B) return RVC_SHAPE;
                 size_t need = (size_t)t.t2.C * t.t2.H * t.t2.W; if (n) *n = need;
                 if (cap < need) return RVC_SHAPE;
+                const float *src = t.t2.p + (long long)stream * t.t2.bs;
                 for (int c = 0; c < t.t2.C; c++)
-                    HIPCHK(hipMemcpy2D(out + (size_t)c * t.t2.H * t.t2.W, (size_t)t.t2.W * 4, t.t2.p + (size_t)c * t.t2.cs, (size_t)t.t2.ld * 4, (size_t)t.t2.W * 4, t.t2.H, hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy2D(out + (size_t)c * t.t2.H * t.t2.W, (size_t)t.t2.W * 4, src + (size_t)c * t.t2.cs, (size_t)t.t2.ld * 4, (size_t)t.t2.W * 4, t.t2.H, hipMemcpyDeviceToHost));
             }
             return RVC_OK;
         }
         if (!strcmp(name, "f0") && pl->d_f0) {
             if (n) *n = (size_t)pl->Tm;
             if (cap < (size_t)pl->Tm) return RVC_SHAPE;
-            HIPCHK(hipMemcpy(out, pl->d_f0, (size_t)pl->Tm * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out, pl->d_f0 + (size_t)stream * pl->Tm, (size_t)pl->Tm * 4, hipMemcpyDeviceToHost));
             return RVC_OK;
         }
         e->err = std::string("unknown tap ") + name;
         return RVC_SHAPE;
     });
 }
+
+rvc_status rvc_get_tap(rvc_engine *e, const char *name, float *out, size_t cap, size_t *n) { return read_tap(e, name, 0, out, cap, n); }
+
+// test hook (include/rvc_mi355x_debug.h): the named tap of stream `stream` of the last call; RVC_SHAPE for a stream the plan did not have
+int rvc_debug_tap(rvc_engine *e, const char *name, int stream, float *out, size_t cap, size_t *n) { return (int)read_tap(e, name, stream, out, cap, n); }
 
 }  // extern "C"
 

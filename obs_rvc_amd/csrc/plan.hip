@@ -1504,10 +1504,12 @@ void add_tap(Plan &pl, const char *name, const T1 &t)
 {
     add_stamp(pl, name);
     if (!pl.with_taps) return;
-    // snapshot into a private contiguous-row tensor so later in-place ops do not clobber it
-    T1 snap = make_t1(pl.arena, 1, t.C, t.T, 0);
+    // snapshot into a private contiguous-row tensor so later in-place ops do not clobber it: every stream of the tensor, each from its own
+    // slice (t.bs), stream-major (rvc_get_tap reads stream 0, rvc_debug_tap any of them)
+    T1 snap = make_t1(pl.arena, t.B, t.C, t.T, 0);
     pl.ops.push_back([=](hipStream_t s) {
-        HIPCHK(hipMemcpy2DAsync(snap.p, (size_t)snap.ld * 4, t.p, (size_t)t.ld * 4, (size_t)t.T * 4, t.C, hipMemcpyDeviceToDevice, s));
+        for (int b = 0; b < t.B; b++)
+            HIPCHK(hipMemcpy2DAsync(snap.p + (long long)b * snap.bs, (size_t)snap.ld * 4, t.p + (long long)b * t.bs, (size_t)t.ld * 4, (size_t)t.T * 4, t.C, hipMemcpyDeviceToDevice, s));
     });
     TapRec r; r.name = name; r.rank = 1; r.t1 = snap; pl.taps.push_back(r);
 }

@@ -390,11 +390,17 @@ class RvcInfer:
         assert self._L.rvc_debug_last_plan(self._h, C.byref(n)) == 1
         return int(n.value)
 
-    def tap(self, name: str):
+    def tap(self, name: str, stream: int = 0):
+        """the named tap of one stream of the last call (enable_taps): stream 0 through rvc_get_tap, any other through the test hook rvc_debug_tap"""
         n = C.c_size_t()
         cap = 1 << 24
         out = np.empty(cap, np.float32)
-        self._chk(self._L.rvc_get_tap(self._h, name.encode(), out.ctypes.data_as(_FP), cap, C.byref(n)))
+        if stream == 0:
+            self._chk(self._L.rvc_get_tap(self._h, name.encode(), out.ctypes.data_as(_FP), cap, C.byref(n)))
+        else:
+            self._L.rvc_debug_tap.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _FP, C.c_size_t, C.POINTER(C.c_size_t)]
+            self._L.rvc_debug_tap.restype = C.c_int
+            self._chk(self._L.rvc_debug_tap(self._h, name.encode(), int(stream), out.ctypes.data_as(_FP), cap, C.byref(n)))
         return out[: n.value].copy()
 
     def pitch_cache(self, stream: int = 0):

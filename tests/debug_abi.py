@@ -68,7 +68,16 @@ def lib():
     L.rvc_debug_conv_check.argtypes = L.rvc_debug_conv2d_check.argtypes = [vp] + [C.c_int] * 7
     L.rvc_debug_conv_check.restype = L.rvc_debug_conv2d_check.restype = C.c_double
     L.rvc_debug_last_kernel.restype = C.c_char_p
+    L.rvc_debug_tap.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rvc_debug_tap.restype = C.c_int
     return L
+
+
+def debug_tap(eng, name, stream, cap=1 << 22):
+    """rvc_debug_tap on an RvcInfer engine -> (status, the tap of that stream of the last call)"""
+    out, n = np.empty(cap, np.float32), C.c_size_t()
+    rc = lib().rvc_debug_tap(eng._h, name.encode(), int(stream), out.ctypes.data, cap, C.byref(n))
+    return rc, out[: n.value].copy() if rc == 0 else None
 
 
 class Handle:

@@ -3,6 +3,7 @@ pin the C oracle's dense layers (the oracle's im2col+sgemm code vs torch's conv/
 ContentVec vs the HuggingFace HuBERT class).  Test infrastructure; never imported by the product."""
 from __future__ import annotations
 
+import contextlib
 import math
 
 import numpy as np
@@ -10,8 +11,21 @@ import torch
 import torch.nn.functional as F
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).float()
+_DTYPE = [torch.float32]
+
+
+@contextlib.contextmanager
+def precision(dtype):
+    """Evaluate the layers below in `dtype` (synth_ref.py: torch.float64); the default is fp32, what the oracle is pinned against."""
+    _DTYPE.append(dtype)
+    try:
+        yield
+    finally:
+        _DTYPE.pop()
+
+
+def _t(a, dtype=None):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype or _DTYPE[-1])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -152,72 +166,118 @@ def _rel_attn(t, l, x, heads, window):
     return F.conv1d(out, _t(t[pre + "o.w"])[:, :, None], _t(t[pre + "o.b"]))
 
 
+# The synthesizer in pieces, each a function of torch tensors with a leading batch axis of 1 (synth_until_z / synth_decoder chain them in fp32;
+# tests/synth_ref.py evaluates them one at a time in fp64 under precision()).
+def sy_embed(cfg, t, phone, pitch):
+    """phone (R, C), pitch int (R,) -> (1, H, R)"""
+    Hd = int(cfg["hidden"])
+    x = F.linear(_t(phone)[None], _t(t["sy.enc.phone.w"]), _t(t["sy.enc.phone.b"])) + _t(t["sy.enc.pitch_emb"])[torch.from_numpy(np.asarray(pitch).astype(np.int64))][None]
+    return F.leaky_relu(x * math.sqrt(Hd), 0.1).transpose(1, 2)
+
+
+def sy_encoder(cfg, t, x):
+    heads, window, ek = int(cfg["heads"]), int(cfg["window"]), int(cfg["enc_k"])
+    for l in range(int(cfg["enc_layers"])):
+        pre = "sy.enc.l%d." % l
+        x = _ln_c(x + _rel_attn(t, l, x, heads, window), _t(t[pre + "ln1.g"]), _t(t[pre + "ln1.b"]))
+        y = F.conv1d(F.relu(F.conv1d(x, _t(t[pre + "ff1.w"]), _t(t[pre + "ff1.b"]), padding=ek // 2)), _t(t[pre + "ff2.w"]), _t(t[pre + "ff2.b"]), padding=ek // 2)
+        x = _ln_c(x + y, _t(t[pre + "ln2.g"]), _t(t[pre + "ln2.b"]))
+    return x
+
+
+def sy_stats(cfg, t, x):
+    return F.conv1d(x, _t(t["sy.enc.proj.w"])[:, :, None], _t(t["sy.enc.proj.b"]))
+
+
+def sy_prior(cfg, stats, eps):
+    I = int(cfg["inter"])
+    m, logs = stats[:, :I], stats[:, I:]
+    return m + torch.exp(logs) * _t(eps)[None] * 0.66666
+
+
+def sy_wavenet(cfg, t, fi, x0):
+    """the coupling layer's network: x0 (1, I/2, R) -> m (1, I/2, R)"""
+    Hd, wk, wl = int(cfg["hidden"]), int(cfg["wn_k"]), int(cfg["wn_layers"])
+    g = _t(t["sy.g"])[None, :, None]
+    pre = "sy.flow%d." % fi
+    h = F.conv1d(x0, _t(t[pre + "pre.w"])[:, :, None], _t(t[pre + "pre.b"]))
+    cond = F.conv1d(g, _t(t[pre + "cond.w"])[:, :, None], _t(t[pre + "cond.b"]))
+    out = torch.zeros_like(h)
+    for j in range(wl):
+        a = F.conv1d(h, _t(t[pre + "in%d.w" % j]), _t(t[pre + "in%d.b" % j]), padding=(wk - 1) // 2) + cond[:, j * 2 * Hd:(j + 1) * 2 * Hd]
+        acts = torch.tanh(a[:, :Hd]) * torch.sigmoid(a[:, Hd:])
+        rs = F.conv1d(acts, _t(t[pre + "rs%d.w" % j])[:, :, None], _t(t[pre + "rs%d.b" % j]))
+        if j < wl - 1:
+            h = h + rs[:, :Hd]
+            out = out + rs[:, Hd:]
+        else:
+            out = out + rs
+    return F.conv1d(out, _t(t[pre + "post.w"])[:, :, None], _t(t[pre + "post.b"]))
+
+
+def sy_flow(cfg, t, fi, z):
+    """Flip, then the reverse coupling layer fi (the reference's module order at inference)"""
+    half = int(cfg["inter"]) // 2
+    z = torch.flip(z, [1])
+    x0, x1 = z[:, :half], z[:, half:]
+    return torch.cat([x0, x1 - sy_wavenet(cfg, t, fi, x0)], 1)
+
+
+def sy_dec_pre(cfg, t, z):
+    g = _t(t["sy.g"])[None, :, None]
+    return F.conv1d(z, _t(t["sy.dec.pre.w"]), _t(t["sy.dec.pre.b"]), padding=3) + F.conv1d(g, _t(t["sy.dec.cond.w"])[:, :, None], _t(t["sy.dec.cond.b"]))
+
+
+def sy_dec_up(cfg, t, i, x, s):
+    """upsampling stage i of x plus its strided convolution of the harmonic source s (1, 1, N)"""
+    n_ups = int(cfg["n_ups"])
+    rates = [int(cfg["up_rate%d" % q]) for q in range(n_ups)]
+    kerns = [int(cfg["up_kernel%d" % q]) for q in range(n_ups)]
+    x = F.leaky_relu(x, 0.1)
+    x = F.conv_transpose1d(x, _t(t["sy.dec.up%d.w" % i]), _t(t["sy.dec.up%d.b" % i]), stride=rates[i], padding=(kerns[i] - rates[i]) // 2)
+    if i + 1 < n_ups:
+        sf = int(np.prod(rates[i + 1:]))
+        return x + F.conv1d(s, _t(t["sy.dec.nc%d.w" % i]), _t(t["sy.dec.nc%d.b" % i]), stride=sf, padding=sf // 2)
+    return x + F.conv1d(s, _t(t["sy.dec.nc%d.w" % i]), _t(t["sy.dec.nc%d.b" % i]))
+
+
+def sy_dec_rb(cfg, t, i, x):
+    """the ResBlock chains of stage i and their mean"""
+    n_rb, n_rbd = int(cfg["n_rb"]), int(cfg["n_rbd"])
+    xs = None
+    for j in range(n_rb):
+        k = int(cfg["rb_k%d" % j])
+        r = x
+        for m in range(n_rbd):
+            d = int(cfg["rb_d%d" % m])
+            xt = F.conv1d(F.leaky_relu(r, 0.1), _t(t["sy.dec.rb%d_%d.c1_%d.w" % (i, j, m)]), _t(t["sy.dec.rb%d_%d.c1_%d.b" % (i, j, m)]), dilation=d, padding=(k * d - d) // 2)
+            xt = F.conv1d(F.leaky_relu(xt, 0.1), _t(t["sy.dec.rb%d_%d.c2_%d.w" % (i, j, m)]), _t(t["sy.dec.rb%d_%d.c2_%d.b" % (i, j, m)]), padding=(k - 1) // 2)
+            r = xt + r
+        xs = r if xs is None else xs + r
+    return xs / n_rb
+
+
+def sy_dec_post(cfg, t, x):
+    return torch.tanh(F.conv1d(F.leaky_relu(x, 0.01), _t(t["sy.dec.post.w"]), None, padding=3))
+
+
 def synth_until_z(cfg, t, phone: np.ndarray, pitch: np.ndarray, eps: np.ndarray):
     """TextEncoder + prior + reverse flow.  phone (R, C), pitch int (R,), eps (inter, R) -> (enc_out, stats, z)."""
-    Hd, I, heads, window = int(cfg["hidden"]), int(cfg["inter"]), int(cfg["heads"]), int(cfg["window"])
-    ek, wk, wl, fn = int(cfg["enc_k"]), int(cfg["wn_k"]), int(cfg["wn_layers"]), int(cfg["flow_n"])
-    g = _t(t["sy.g"])[None, :, None]
     with torch.no_grad():
-        x = F.linear(_t(phone)[None], _t(t["sy.enc.phone.w"]), _t(t["sy.enc.phone.b"])) + _t(t["sy.enc.pitch_emb"])[torch.from_numpy(pitch.astype(np.int64))][None]
-        x = F.leaky_relu(x * math.sqrt(Hd), 0.1).transpose(1, 2)
-        for l in range(int(cfg["enc_layers"])):
-            pre = "sy.enc.l%d." % l
-            x = _ln_c(x + _rel_attn(t, l, x, heads, window), _t(t[pre + "ln1.g"]), _t(t[pre + "ln1.b"]))
-            y = F.conv1d(F.relu(F.conv1d(x, _t(t[pre + "ff1.w"]), _t(t[pre + "ff1.b"]), padding=ek // 2)), _t(t[pre + "ff2.w"]), _t(t[pre + "ff2.b"]), padding=ek // 2)
-            x = _ln_c(x + y, _t(t[pre + "ln2.g"]), _t(t[pre + "ln2.b"]))
-        enc = x
-        stats = F.conv1d(x, _t(t["sy.enc.proj.w"])[:, :, None], _t(t["sy.enc.proj.b"]))
-        m, logs = stats[:, :I], stats[:, I:]
-        z = m + torch.exp(logs) * _t(eps)[None] * 0.66666
-        half = I // 2
-        for fi in reversed(range(fn)):
-            z = torch.flip(z, [1])
-            pre = "sy.flow%d." % fi
-            x0, x1 = z[:, :half], z[:, half:]
-            h = F.conv1d(x0, _t(t[pre + "pre.w"])[:, :, None], _t(t[pre + "pre.b"]))
-            cond = F.conv1d(g, _t(t[pre + "cond.w"])[:, :, None], _t(t[pre + "cond.b"]))
-            out = torch.zeros_like(h)
-            for j in range(wl):
-                a = F.conv1d(h, _t(t[pre + "in%d.w" % j]), _t(t[pre + "in%d.b" % j]), padding=(wk - 1) // 2) + cond[:, j * 2 * Hd:(j + 1) * 2 * Hd]
-                acts = torch.tanh(a[:, :Hd]) * torch.sigmoid(a[:, Hd:])
-                rs = F.conv1d(acts, _t(t[pre + "rs%d.w" % j])[:, :, None], _t(t[pre + "rs%d.b" % j]))
-                if j < wl - 1:
-                    h = h + rs[:, :Hd]
-                    out = out + rs[:, Hd:]
-                else:
-                    out = out + rs
-            mm = F.conv1d(out, _t(t[pre + "post.w"])[:, :, None], _t(t[pre + "post.b"]))
-            z = torch.cat([x0, x1 - mm], 1)
+        enc = sy_encoder(cfg, t, sy_embed(cfg, t, phone, pitch))
+        stats = sy_stats(cfg, t, enc)
+        z = sy_prior(cfg, stats, eps)
+        for fi in reversed(range(int(cfg["flow_n"]))):
+            z = sy_flow(cfg, t, fi, z)
     return enc[0].numpy(), stats[0].numpy(), z[0].numpy()
 
 
 def synth_decoder(cfg, t, z: np.ndarray, src: np.ndarray) -> np.ndarray:
     """NSF-HiFiGAN decoder given the latent z (inter, R) and the harmonic source (N,)."""
-    n_ups, n_rb, n_rbd = int(cfg["n_ups"]), int(cfg["n_rb"]), int(cfg["n_rbd"])
-    rates = [int(cfg["up_rate%d" % i]) for i in range(n_ups)]
-    kerns = [int(cfg["up_kernel%d" % i]) for i in range(n_ups)]
-    g = _t(t["sy.g"])[None, :, None]
     with torch.no_grad():
-        x = F.conv1d(_t(z)[None], _t(t["sy.dec.pre.w"]), _t(t["sy.dec.pre.b"]), padding=3) + F.conv1d(g, _t(t["sy.dec.cond.w"])[:, :, None], _t(t["sy.dec.cond.b"]))
+        x = sy_dec_pre(cfg, t, _t(z)[None])
         s = _t(src)[None, None]
-        for i in range(n_ups):
-            x = F.leaky_relu(x, 0.1)
-            x = F.conv_transpose1d(x, _t(t["sy.dec.up%d.w" % i]), _t(t["sy.dec.up%d.b" % i]), stride=rates[i], padding=(kerns[i] - rates[i]) // 2)
-            if i + 1 < n_ups:
-                sf = int(np.prod(rates[i + 1:]))
-                x = x + F.conv1d(s, _t(t["sy.dec.nc%d.w" % i]), _t(t["sy.dec.nc%d.b" % i]), stride=sf, padding=sf // 2)
-            else:
-                x = x + F.conv1d(s, _t(t["sy.dec.nc%d.w" % i]), _t(t["sy.dec.nc%d.b" % i]))
-            xs = None
-            for j in range(n_rb):
-                k = int(cfg["rb_k%d" % j])
-                r = x
-                for m in range(n_rbd):
-                    d = int(cfg["rb_d%d" % m])
-                    xt = F.conv1d(F.leaky_relu(r, 0.1), _t(t["sy.dec.rb%d_%d.c1_%d.w" % (i, j, m)]), _t(t["sy.dec.rb%d_%d.c1_%d.b" % (i, j, m)]), dilation=d, padding=(k * d - d) // 2)
-                    xt = F.conv1d(F.leaky_relu(xt, 0.1), _t(t["sy.dec.rb%d_%d.c2_%d.w" % (i, j, m)]), _t(t["sy.dec.rb%d_%d.c2_%d.b" % (i, j, m)]), padding=(k - 1) // 2)
-                    r = xt + r
-                xs = r if xs is None else xs + r
-            x = xs / n_rb
-        x = torch.tanh(F.conv1d(F.leaky_relu(x, 0.01), _t(t["sy.dec.post.w"]), None, padding=3))
+        for i in range(int(cfg["n_ups"])):
+            x = sy_dec_rb(cfg, t, i, sy_dec_up(cfg, t, i, x, s))
+        x = sy_dec_post(cfg, t, x)
     return x[0, 0].numpy()
