@@ -74,6 +74,10 @@ extern "C" {
     pub fn rvc_set_index_nprobe(e: *mut RvcEngine, nprobe: c_int) -> c_int;
     pub fn rvc_index_nprobe(e: *mut RvcEngine) -> c_int;
     pub fn rvc_index_ivf_info(e: *mut RvcEngine, nlist: *mut usize, longest_list: *mut usize, empty_lists: *mut usize) -> c_int;
+    // k-means training of an IVF structure for the loaded index, its report, and the attached structure read back
+    pub fn rvc_train_index_ivf(e: *mut RvcEngine, nlist: usize, iters: c_int, init_rows: *const i32, seed: u32) -> c_int;
+    pub fn rvc_index_ivf_train_info(e: *mut RvcEngine, iters_run: *mut c_int, moved_last: *mut usize, objective: *mut f64, cap: usize, n_obj: *mut usize, ms: *mut f64) -> c_int;
+    pub fn rvc_get_index_ivf(e: *mut RvcEngine, centroids: *mut c_float, cap_centroid_floats: usize, assign: *mut i32, cap_rows: usize) -> c_int;
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 

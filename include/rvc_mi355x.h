@@ -108,6 +108,20 @@ rvc_status rvc_set_index_ivf(rvc_engine *e, const float *centroids, size_t nlist
 rvc_status rvc_set_index_nprobe(rvc_engine *e, int nprobe);   /* 0 = flat search (default); 1..64 = probe that many lists, clamped to nlist */
 int rvc_index_nprobe(rvc_engine *e);                          /* 0 = flat */
 rvc_status rvc_index_ivf_info(rvc_engine *e, size_t *nlist, size_t *longest_list, size_t *empty_lists);
+/* Train an IVF structure for the loaded index on the device: Lloyd's k-means over the rows in HBM -- c_j starts as row init_rows[j], an
+   assign step (every row to the list with the smallest (d, j), d the exact distance of the probe) and then up to `iters` update steps (the fp64 mean of a list's
+   rows, rounded once; an empty list keeps its centroid: no splitting, no reseeding), each followed by an assign step; it stops early behind an assign step that
+   moved no row.  The result is attached exactly as rvc_set_index_ivf would (same CSR build, plans cleared, nprobe back to 0).  nlist 0 = upstream's rule
+   min(floor(16 sqrt(n)), n / 39) clamped to [1, 65536]; iters 0..100; init_rows NULL = the seeded sample (the nlist rows with the smallest (h(seed, i), i), in
+   ascending row number).  The same index and arguments give the same bits on every run and every rank.  RVC_SHAPE, the engine keeping the structure it had: no
+   index loaded, nlist above n or 65536, iters outside [0, 100], an initial row out of range or named twice, a row of the index that holds a NaN or an Inf (the
+   message names the first).  A failure behind these checks leaves the engine with no structure and a flat search. */
+rvc_status rvc_train_index_ivf(rvc_engine *e, size_t nlist, int iters, const int32_t *init_rows, uint32_t seed);
+/* of the last training on this engine: update steps done, rows moved by the last assign step, the objectives of the assign steps
+   (up to cap of them; *n_obj = how many there are), device milliseconds {assign, update, total}; RVC_SHAPE before a training has completed */
+rvc_status rvc_index_ivf_train_info(rvc_engine *e, int *iters_run, size_t *moved_last, double *objective, size_t cap, size_t *n_obj, double ms[3]);
+/* read the attached structure back, trained or set (export, tests): RVC_SHAPE when none is attached or a capacity is short */
+rvc_status rvc_get_index_ivf(rvc_engine *e, float *centroids, size_t cap_centroid_floats, int32_t *assign, size_t cap_rows);
 /* the synthesizer's two noise inputs are explicit counter-based (Philox4x32-10) streams */
 void rvc_set_noise_seed(rvc_engine *e, uint32_t seed, uint32_t stream_id);
 void rvc_reset_state(rvc_engine *e);     /* zero the 1024-entry pitch cache and the chunk counter */

@@ -173,6 +173,12 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
 /* the device-side copies of the loaded index besides the row-major matrix: bit 0 = MFMA-fragment order, bit 1 = the transposed copy (built by the first plan that
  * needs it; while it is absent, the exhaustive scan of a fallback list walks the row-major matrix), bit 2 = an IVF structure is attached; 0 without an index */
 int rvc_debug_index_layouts(rvc_engine *e);
+/* one assign step and one update step of the k-means training (obs_rvc_amd/csrc/kmeans.hip.h) on the loaded index, from the caller's
+ * centroids [nlist][dim]: assign_out / dist_out [n] and objective_out are the assign step's, moved_out its rows whose list differs from prev_assign_or_null (all n
+ * when that is null), centroids_out [nlist][dim] the update step's means over assign_out.  Nothing is attached and the engine's structure stays.  RVC_SHAPE
+ * without an index or with nlist outside [1, min(n, 65536)].  0 = done, else an rvc_status. */
+int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist, const int32_t *prev_assign_or_null, int32_t *assign_out, float *dist_out,
+                          float *centroids_out, double *objective_out, long long *moved_out);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);

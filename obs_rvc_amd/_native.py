@@ -35,6 +35,7 @@ SYMBOLS = [
     "rvc_denoiser_create", "rvc_denoiser_destroy", "rvc_denoiser_reset", "rvc_denoiser_set", "rvc_denoiser_latency", "rvc_denoiser_process", "rvc_denoiser_process_device",
     "rvc_session_set_noise_reduction", "rvc_session_set_noise_reduction_stream",
     "rvc_set_index_ivf", "rvc_set_index_nprobe", "rvc_index_nprobe", "rvc_index_ivf_info",
+    "rvc_train_index_ivf", "rvc_index_ivf_train_info", "rvc_get_index_ivf",
 ]
 
 
@@ -229,6 +230,10 @@ def lib():
         L.rvc_set_index_nprobe.argtypes = [vp, C.c_int]
         L.rvc_index_nprobe.argtypes = [vp]
         L.rvc_index_ivf_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    if hasattr(L, "rvc_train_index_ivf") or not override:
+        L.rvc_train_index_ivf.argtypes = [vp, sz, C.c_int, C.POINTER(i32), u32]
+        L.rvc_index_ivf_train_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(C.c_double), sz, C.POINTER(sz), C.POINTER(C.c_double)]
+        L.rvc_get_index_ivf.argtypes = [vp, fp, sz, C.POINTER(i32), sz]
     L.rvc_set_noise_seed.argtypes = [vp, u32, u32]
     L.rvc_set_noise_seed.restype = None
     L.rvc_reset_state.argtypes = [vp]

@@ -802,6 +802,29 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
 // test aid: which copies of the index exist (a fallback list built while the transposed copy is absent walks the row-major matrix)
 int rvc_debug_index_layouts(rvc_engine *e) { return e ? (e->d_indexF ? 1 : 0) | (e->d_indexT ? 2 : 0) | (e->d_ivf_cent ? 4 : 0) : 0; }
 
+// test aid: one assign step and one update step of the k-means training (retrieval.hip kmeans_assign_step / kmeans_update_step; tests/test_gpu_kmeans.py)
+int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist, const int32_t *prev_assign_or_null, int32_t *assign_out, float *dist_out,
+                          float *centroids_out, double *objective_out, long long *moved_out)
+{
+    return (int)guarded(e, [&]() {
+        if (!centroids_in || !assign_out || !dist_out || !centroids_out || !objective_out || !moved_out) throw ShapeError("k-means step: null argument");
+        if (!e->d_index) throw ShapeError("no index loaded");
+        const size_t n = e->index_n, dim = e->index_dim;
+        if (nlist < 1 || nlist > n || nlist > 65536) throw ShapeError("k-means step: nlist must be in [1, min(n, 65536)]");
+        HIPCHK(hipDeviceSynchronize());
+        KmeansWork w;
+        w.alloc(n, dim, nlist);
+        HIPCHK(hipMemcpy(w.cent, centroids_in, nlist * dim * sizeof(float), hipMemcpyHostToDevice));
+        if (prev_assign_or_null) HIPCHK(hipMemcpy(w.assign[1], prev_assign_or_null, n * sizeof(int), hipMemcpyHostToDevice));
+        kmeans_assign_step(e, w, prev_assign_or_null ? w.assign[1] : nullptr, 0, objective_out, moved_out);
+        HIPCHK(hipMemcpy(assign_out, w.assign[0], n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist_out, w.dist, n * sizeof(float), hipMemcpyDeviceToHost));
+        kmeans_update_step(e, w, 0);
+        HIPCHK(hipMemcpy(centroids_out, w.cent, nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
 // the kernel family of the most recently queued implicit-GEMM launch (the first word of its description), the variant of the last op or the form of the
 // last ConvBlockRes: tests assert which path they exercised
 const char *rvc_debug_last_kernel(void)

@@ -468,6 +468,8 @@ struct rvc_engine {
     // index_nprobe: 0 = flat search, else the lists probed per query; engine-wide and part of a plan's identity.  A new index drops both (build_index_aux)
     float *d_ivf_cent = nullptr; int *d_ivf_offs = nullptr, *d_ivf_perm = nullptr; size_t ivf_nlist = 0, ivf_longest = 0, ivf_empty = 0; int index_nprobe = 0;
     float index_prep_ms = 0.f;                                  // device-side repack + norms of the last index load
+    // the last k-means training of an IVF structure (rvc_train_index_ivf; kmeans.hip.h): what rvc_index_ivf_train_info reports
+    bool km_valid = false; int km_iters_run = 0; size_t km_moved_last = 0; std::vector<double> km_obj; double km_ms[3] = {0, 0, 0};
     double bcast_ms[3] = {0, 0, 0}; int bcast_ranks = 0;         // last rvc_index_broadcast: communicator set-up, broadcast, repack (ms); ranks the communicator reports
     // streams
     int n_streams = 1;
@@ -572,4 +574,17 @@ void launch_resampler(rvc_resampler *r, const float *d_in, float *d_out, long lo
 void build_index_aux(rvc_engine *e);
 void ensure_index_transposed(rvc_engine *e);
 void drop_index_ivf(rvc_engine *e);
+// k-means training of an IVF structure (retrieval.hip, kmeans.hip.h): the device buffers of one training and its two steps, as rvc_train_index_ivf runs them and
+// as rvc_debug_kmeans_step does (debug.hip).  assign[2]: the current and the previous assignment, swapped per step
+struct KmeansWork {
+    size_t n = 0, dim = 0, nlist = 0; int nwg = 0, nparts = 0;
+    float *cent = nullptr, *dist = nullptr; int *assign[2] = {nullptr, nullptr}, *moved_wg = nullptr, *counts = nullptr, *offs = nullptr, *perm = nullptr;
+    double *part = nullptr, *obj = nullptr; long long *moved = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr}; double ms_assign = 0, ms_update = 0;
+    KmeansWork() = default; KmeansWork(const KmeansWork &) = delete; KmeansWork &operator=(const KmeansWork &) = delete;
+    void alloc(size_t n, size_t dim, size_t nlist);
+    ~KmeansWork();
+};
+void kmeans_assign_step(rvc_engine *e, KmeansWork &w, const int *prev, int cur, double *objective, long long *moved);
+void kmeans_update_step(rvc_engine *e, KmeansWork &w, int cur);
 }  // namespace rvc

@@ -3,6 +3,7 @@
 #include "engine_int.h"
 #include "knn.hip.h"
 #include "ivf.hip.h"
+#include "kmeans.hip.h"
 
 namespace rvc {
 
@@ -209,6 +210,102 @@ void drop_index_ivf(rvc_engine *e)
     e->ivf_nlist = e->ivf_longest = e->ivf_empty = 0; e->index_nprobe = 0;
 }
 
+// The CSR of an assignment (list offsets + row permutation, rows ascending inside every list) by the counting sort of ivf.hip.h, queued on the engine's stream:
+// what rvc_set_index_ivf attaches and what every update step of the k-means training walks.
+static void ivf_build_csr(rvc_engine *e, const int *d_assign, size_t n, size_t nlist, int *d_counts, int *d_offs, int *d_perm)
+{
+    HIPCHK(hipMemsetAsync(d_counts, 0, nlist * sizeof(int), e->stream));
+    hipLaunchKernelGGL(ivf_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, d_assign, (int)n, d_counts);
+    hipLaunchKernelGGL(ivf_offsets_kernel, dim3(1), dim3(256), 0, e->stream, d_counts, (int)nlist, d_offs);
+    hipLaunchKernelGGL(ivf_fill_kernel, dim3((unsigned)((nlist + 3) / 4)), dim3(256), 0, e->stream, d_assign, (int)n, (int)nlist, d_offs, d_perm);
+}
+// behind ivf_build_csr into the engine's own arrays: check the offsets and note what rvc_index_ivf_info reports
+static void ivf_note_lists(rvc_engine *e, size_t n, size_t nlist)
+{
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    std::vector<int> offs(nlist + 1);
+    HIPCHK(hipMemcpy(offs.data(), e->d_ivf_offs, offs.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (offs[0] != 0 || (size_t)offs[nlist] != n) throw std::runtime_error("IVF structure: the device-side list offsets do not add up");
+    e->ivf_nlist = nlist; e->ivf_longest = e->ivf_empty = 0;
+    for (size_t l = 0; l < nlist; l++) {
+        const size_t len = (size_t)(offs[l + 1] - offs[l]);
+        e->ivf_longest = std::max(e->ivf_longest, len); e->ivf_empty += len == 0;
+    }
+}
+
+// ---- k-means training (kmeans.hip.h) ----
+void KmeansWork::alloc(size_t n_, size_t dim_, size_t nlist_)
+{
+    n = n_; dim = dim_; nlist = nlist_;
+    nwg = (int)((n + KM_TR - 1) / KM_TR); nparts = (int)((n + KM_RB - 1) / KM_RB);
+    HIPCHK(hipMalloc(&cent, nlist * dim * sizeof(float)));
+    HIPCHK(hipMalloc(&assign[0], n * sizeof(int))); HIPCHK(hipMalloc(&assign[1], n * sizeof(int)));
+    HIPCHK(hipMalloc(&dist, n * sizeof(float)));
+    HIPCHK(hipMalloc(&moved_wg, (size_t)nwg * sizeof(int)));
+    HIPCHK(hipMalloc(&part, (size_t)nparts * sizeof(double)));
+    HIPCHK(hipMalloc(&obj, sizeof(double))); HIPCHK(hipMalloc(&moved, sizeof(long long)));
+    HIPCHK(hipMalloc(&counts, nlist * sizeof(int))); HIPCHK(hipMalloc(&offs, (nlist + 1) * sizeof(int))); HIPCHK(hipMalloc(&perm, n * sizeof(int)));
+    HIPCHK(hipEventCreate(&ev[0])); HIPCHK(hipEventCreate(&ev[1]));
+}
+KmeansWork::~KmeansWork()
+{
+    for (void *p : {(void *)cent, (void *)assign[0], (void *)assign[1], (void *)dist, (void *)moved_wg, (void *)part, (void *)obj, (void *)moved, (void *)counts, (void *)offs, (void *)perm})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
+}
+// one assign step against w.cent into w.assign[cur] / w.dist; prev: the assignment `moved` is counted against (null: every row counts).  Synchronises.
+void kmeans_assign_step(rvc_engine *e, KmeansWork &w, const int *prev, int cur, double *objective, long long *moved)
+{
+    KmeansAssignP ap{}; ap.index = e->d_index; ap.n = (int)w.n; ap.dim = (int)w.dim; ap.cent = w.cent; ap.nlist = (int)w.nlist;
+    ap.prev = prev; ap.assign = w.assign[cur]; ap.dist = w.dist; ap.moved_wg = w.moved_wg;
+    HIPCHK(hipEventRecord(w.ev[0], e->stream));
+    hipLaunchKernelGGL(kmeans_assign_kernel, dim3((unsigned)w.nwg), dim3(256), 0, e->stream, ap);
+    hipLaunchKernelGGL(kmeans_objective_kernel, dim3((unsigned)w.nparts), dim3(256), 0, e->stream, w.dist, (int)w.n, w.part);
+    hipLaunchKernelGGL(kmeans_objective_final_kernel, dim3(1), dim3(256), 0, e->stream, w.part, w.nparts, w.moved_wg, w.nwg, w.obj, w.moved);
+    HIPCHK(hipEventRecord(w.ev[1], e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(objective, w.obj, sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(moved, w.moved, sizeof(long long), hipMemcpyDeviceToHost));
+    float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    w.ms_assign += ms;
+}
+// one update step: the CSR of w.assign[cur], then the means into w.cent in place (a list reads rows and writes its own centroid only).  Synchronises.
+void kmeans_update_step(rvc_engine *e, KmeansWork &w, int cur)
+{
+    HIPCHK(hipEventRecord(w.ev[0], e->stream));
+    ivf_build_csr(e, w.assign[cur], w.n, w.nlist, w.counts, w.offs, w.perm);
+    hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, e->d_index, (int)w.dim, w.offs, w.perm, w.cent);
+    HIPCHK(hipEventRecord(w.ev[1], e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    w.ms_update += ms;
+}
+
+// upstream's rule for IVF<n>,Flat: min(floor(16 sqrt(n)), n / 39), clamped to [1, 65536]
+static size_t kmeans_default_nlist(size_t n)
+{
+    size_t a = (size_t)std::floor(16.0 * std::sqrt((double)n));
+    while (a > 0 && (double)a > 16.0 * std::sqrt((double)n)) a--;
+    return std::min<size_t>(std::max<size_t>(std::min(a, n / 39), 1), IVF_MAX_NLIST);
+}
+// The seeded sample: the nlist rows with the smallest (h(seed, i), i), taken in ascending row number.  h is the 32-bit mixer "lowbias32"
+// (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16) applied as h(seed, i) = m(i ^ m(seed + 0x9e3779b9)); tests/kmeans_ref.py restates it.
+static inline uint32_t kmeans_mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
+static std::vector<int32_t> kmeans_seeded_rows(size_t n, size_t nlist, uint32_t seed)
+{
+    const uint32_t ms = kmeans_mix(seed + 0x9e3779b9u);
+    std::vector<uint64_t> key(n);
+    for (size_t i = 0; i < n; i++) key[i] = ((uint64_t)kmeans_mix((uint32_t)i ^ ms) << 32) | (uint32_t)i;
+    std::nth_element(key.begin(), key.begin() + (nlist - 1), key.end());
+    std::vector<int32_t> rows(nlist);
+    for (size_t j = 0; j < nlist; j++) rows[j] = (int32_t)(uint32_t)key[j];
+    std::sort(rows.begin(), rows.end());
+    return rows;
+}
+
 void build_index_aux(rvc_engine *e)
 {
     drop_index_ivf(e);          // a new index: the structure described the old rows, and the search is flat again
@@ -340,20 +437,8 @@ rvc_status rvc_set_index_ivf(rvc_engine *e, const float *centroids, size_t nlist
             HIPCHK(hipMalloc(&d_counts, nlist * sizeof(int)));
             HIPCHK(hipMemcpy(e->d_ivf_cent, centroids, nlist * dim * sizeof(float), hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(d_assign, assign, n * sizeof(int), hipMemcpyHostToDevice));
-            HIPCHK(hipMemsetAsync(d_counts, 0, nlist * sizeof(int), e->stream));
-            hipLaunchKernelGGL(ivf_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, d_assign, (int)n, d_counts);
-            hipLaunchKernelGGL(ivf_offsets_kernel, dim3(1), dim3(256), 0, e->stream, d_counts, (int)nlist, e->d_ivf_offs);
-            hipLaunchKernelGGL(ivf_fill_kernel, dim3((unsigned)((nlist + 3) / 4)), dim3(256), 0, e->stream, d_assign, (int)n, (int)nlist, e->d_ivf_offs, e->d_ivf_perm);
-            HIPCHK(hipStreamSynchronize(e->stream));
-            HIPCHK(hipGetLastError());
-            std::vector<int> offs(nlist + 1);
-            HIPCHK(hipMemcpy(offs.data(), e->d_ivf_offs, offs.size() * sizeof(int), hipMemcpyDeviceToHost));
-            if (offs[0] != 0 || (size_t)offs[nlist] != n) throw std::runtime_error("IVF structure: the device-side list offsets do not add up");
-            e->ivf_nlist = nlist;
-            for (size_t l = 0; l < nlist; l++) {
-                const size_t len = (size_t)(offs[l + 1] - offs[l]);
-                e->ivf_longest = std::max(e->ivf_longest, len); e->ivf_empty += len == 0;
-            }
+            ivf_build_csr(e, d_assign, n, nlist, d_counts, e->d_ivf_offs, e->d_ivf_perm);
+            ivf_note_lists(e, n, nlist);
         } catch (...) {
             if (d_assign) (void)hipFree(d_assign);
             if (d_counts) (void)hipFree(d_counts);
@@ -361,6 +446,109 @@ rvc_status rvc_set_index_ivf(rvc_engine *e, const float *centroids, size_t nlist
             throw;
         }
         (void)hipFree(d_assign); (void)hipFree(d_counts);
+        return RVC_OK;
+    });
+}
+
+// k-means over the loaded index (kmeans.hip.h), then the attachment rvc_set_index_ivf makes.  Everything that can refuse the call is decided before the structure
+// the engine has is dropped; a failure behind that point leaves no structure and a flat search.
+rvc_status rvc_train_index_ivf(rvc_engine *e, size_t nlist, int iters, const int32_t *init_rows, uint32_t seed)
+{
+    return guarded(e, [&]() {
+        if (!e->d_index) throw ShapeError("no index loaded");
+        const size_t n = e->index_n, dim = e->index_dim;
+        if (nlist == 0) nlist = kmeans_default_nlist(n);
+        if (nlist > n || nlist > IVF_MAX_NLIST) throw ShapeError("k-means: nlist must be at most the number of rows and at most 65536");
+        if (iters < 0 || iters > 100) throw ShapeError("k-means: iters must be in [0, 100]");
+        std::vector<int32_t> rows;
+        if (init_rows) {
+            rows.assign(init_rows, init_rows + nlist);
+            std::vector<char> seen(n, 0);
+            for (size_t j = 0; j < nlist; j++) {
+                if (rows[j] < 0 || (size_t)rows[j] >= n) throw ShapeError("k-means: initial row " + std::to_string(j) + " is outside the index");
+                if (seen[rows[j]]) throw ShapeError("k-means: row " + std::to_string(rows[j]) + " appears twice among the initial rows");
+                seen[rows[j]] = 1;
+            }
+        } else rows = kmeans_seeded_rows(n, nlist, seed);
+        HIPCHK(hipDeviceSynchronize());
+        int *d_rows = nullptr;                                               // (also the word the non-finite search answers in)
+        HIPCHK(hipMalloc(&d_rows, std::max(nlist, (size_t)1) * sizeof(int)));
+        struct Free { int *p; ~Free() { (void)hipFree(p); } } free_rows{d_rows};
+        int first = 0x7fffffff;
+        HIPCHK(hipMemcpy(d_rows, &first, sizeof(int), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(kmeans_nonfinite_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->d_index, e->d_ynorm, (int)n, (int)dim, d_rows);
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(&first, d_rows, sizeof(int), hipMemcpyDeviceToHost));
+        if (first != 0x7fffffff) throw ShapeError("k-means: row " + std::to_string(first) + " of the index holds a NaN or an Inf");
+        // ---- from here on the old structure is gone ----
+        drop_index_ivf(e);
+        e->plans.clear(); e->last_plan = nullptr;
+        e->km_valid = false;
+        try {
+            KmeansWork w;
+            w.alloc(n, dim, nlist);
+            hipEvent_t t0, t1; HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1));
+            struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evs{t0, t1};
+            HIPCHK(hipEventRecord(t0, e->stream));
+            HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nlist * sizeof(int), hipMemcpyHostToDevice, e->stream));
+            hipLaunchKernelGGL(kmeans_gather_kernel, dim3((unsigned)nlist), dim3(256), 0, e->stream, e->d_index, (int)dim, d_rows, w.cent);
+            std::vector<double> obj(1);
+            long long moved = 0;
+            int cur = 0, run = 0;
+            kmeans_assign_step(e, w, nullptr, cur, &obj[0], &moved);
+            while (run < iters && moved != 0) {
+                kmeans_update_step(e, w, cur);
+                double j = 0.0;
+                kmeans_assign_step(e, w, w.assign[cur], cur ^ 1, &j, &moved);
+                obj.push_back(j); cur ^= 1; run++;
+            }
+            // attach: the centroids as they are, the CSR of the last assign step into arrays the engine keeps
+            HIPCHK(hipMalloc(&e->d_ivf_offs, (nlist + 1) * sizeof(int)));
+            HIPCHK(hipMalloc(&e->d_ivf_perm, n * sizeof(int)));
+            ivf_build_csr(e, w.assign[cur], n, nlist, w.counts, e->d_ivf_offs, e->d_ivf_perm);
+            HIPCHK(hipEventRecord(t1, e->stream));
+            e->d_ivf_cent = w.cent; w.cent = nullptr;
+            ivf_note_lists(e, n, nlist);
+            float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, t0, t1));
+            e->km_iters_run = run; e->km_moved_last = (size_t)moved; e->km_obj = obj;
+            e->km_ms[0] = w.ms_assign; e->km_ms[1] = w.ms_update; e->km_ms[2] = ms;
+            e->km_valid = true;
+        } catch (...) {
+            drop_index_ivf(e);
+            throw;
+        }
+        return RVC_OK;
+    });
+}
+
+rvc_status rvc_index_ivf_train_info(rvc_engine *e, int *iters_run, size_t *moved_last, double *objective, size_t cap, size_t *n_obj, double ms[3])
+{
+    return guarded(e, [&]() {
+        if (!e->km_valid) throw ShapeError("no k-means training has completed on this engine");
+        if (iters_run) *iters_run = e->km_iters_run;
+        if (moved_last) *moved_last = e->km_moved_last;
+        if (n_obj) *n_obj = e->km_obj.size();
+        if (objective) for (size_t i = 0; i < std::min(cap, e->km_obj.size()); i++) objective[i] = e->km_obj[i];
+        if (ms) for (int i = 0; i < 3; i++) ms[i] = e->km_ms[i];
+        return RVC_OK;
+    });
+}
+
+// the attached structure, trained or set: the centroids as stored, the assignment rebuilt from the CSR
+rvc_status rvc_get_index_ivf(rvc_engine *e, float *centroids, size_t cap_centroid_floats, int32_t *assign, size_t cap_rows)
+{
+    return guarded(e, [&]() {
+        if (!e->d_ivf_cent) throw ShapeError("no IVF structure attached to the index");
+        const size_t nlist = e->ivf_nlist, n = e->index_n, dim = e->index_dim;
+        if (!centroids || !assign || cap_centroid_floats < nlist * dim || cap_rows < n) throw ShapeError("IVF structure: the caller's arrays are too short");
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(centroids, e->d_ivf_cent, nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
+        std::vector<int> offs(nlist + 1), perm(n);
+        HIPCHK(hipMemcpy(offs.data(), e->d_ivf_offs, offs.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(perm.data(), e->d_ivf_perm, n * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t l = 0; l < nlist; l++)
+            for (int q = offs[l]; q < offs[l + 1]; q++) assign[perm[q]] = (int32_t)l;
         return RVC_OK;
     });
 }

@@ -204,3 +204,30 @@ def write_ivf_flat(path: str, vectors: np.ndarray, centroids: np.ndarray, sparse
             ids = np.nonzero(assign == l)[0].astype("<i8")
             if ids.size:
                 f.write(v[ids].astype("<f4").tobytes()); f.write(ids.tobytes())
+
+
+def write_ivf_flat_assigned(path: str, vectors: np.ndarray, centroids: np.ndarray, assign: np.ndarray, nprobe: int = 1):
+    """IndexIVFFlat with the given coarse centroids AND the given list of every row (a trained structure: RvcInfer.index_ivf), ids = row numbers, rows ascending
+    inside every list; the file stores `nprobe`.  The bytes of write_ivf_flat for the same assignment and nprobe 1, without its n x nlist x dim temporary."""
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    c = np.ascontiguousarray(centroids, dtype=np.float32)
+    a = np.ascontiguousarray(assign, dtype=np.int64)
+    n, d = v.shape
+    nlist = c.shape[0]
+    if c.ndim != 2 or c.shape[1] != d or a.shape != (n,) or nlist < 1 or (n and (a.min() < 0 or a.max() >= nlist)) or nprobe < 0:
+        raise IndexFormatError("centroids (nlist, d), one list in [0, nlist) per row and nprobe >= 0 are needed")
+    order = np.argsort(a, kind="stable")                                  # rows grouped by list, ascending inside every list
+    sizes = np.bincount(a, minlength=nlist).astype(np.uint64)
+    with open(path, "wb") as f:
+        f.write(b"IwFl"); _w_header(f, d, n)
+        f.write(struct.pack("<QQ", nlist, int(nprobe)))
+        write_flat(f, c)
+        f.write(struct.pack("<B", 0)); f.write(struct.pack("<Q", 0))            # direct map: NoMap, empty array
+        f.write(b"ilar"); f.write(struct.pack("<QQ", nlist, 4 * d))
+        f.write(b"full"); f.write(struct.pack("<Q", sizes.size)); f.write(sizes.astype("<u8").tobytes())
+        at = 0
+        for l in range(nlist):
+            ids = order[at:at + int(sizes[l])]
+            at += int(sizes[l])
+            if ids.size:
+                f.write(v[ids].astype("<f4").tobytes()); f.write(ids.astype("<i8").tobytes())

@@ -111,13 +111,16 @@ class RvcInfer:
         return out[: n.value].copy()
 
     # -- extensions ---------------------------------------------------------------------
-    def load_index(self, vectors, nprobe=None):
+    def load_index(self, vectors, nprobe=None, train=False):
         """`vectors`: an (n, dim) float32 array, or the path of a Faiss `.index` file (IndexFlat / IndexIVFFlat: the stored
         vectors are reconstructed in id order, obs_rvc_amd.faiss_index) or of a `.npy` matrix (upstream's total_fea.npy).
         `nprobe`: None = the flat search over every row; an integer >= 1 = keep an IndexIVFFlat file's structure and search it as upstream
         does, that many nearest lists per query (rvc_set_index_ivf + rvc_set_index_nprobe); "file" = the nprobe the file stores.  A source
         without an IVF structure (an array, a .npy matrix, a flat file) with nprobe >= 1 or "file" raises the RVC_SHAPE error (NdarrayShapeError)
-        before anything is loaded: the engine keeps the index it had."""
+        before anything is loaded: the engine keeps the index it had.
+        `train`: True, or a dict of train_index_ivf's arguments (nlist, iters, init_rows, seed): with `nprobe` given, a source without a structure is trained
+        on the device after loading (k-means, rvc_train_index_ivf) instead of refused; "file" then means 1, upstream's stored value.  A file's own structure is
+        kept as it is.  False (the default): everything above."""
         centroids = assign = None
         stored = 0
         if isinstance(vectors, (str, os.PathLike)):
@@ -135,16 +138,21 @@ class RvcInfer:
             # a .npy matrix, a flat file) has no lists to probe and no stored value -- the engine's own RVC_SHAPE error for nprobe >= 1 without a structure
             if isinstance(nprobe, str) and nprobe != "file":
                 raise ValueError('nprobe is an integer or "file"')
-            if centroids is None and (nprobe == "file" or int(nprobe) >= 1):
+            if centroids is None and not train and (nprobe == "file" or int(nprobe) >= 1):
                 raise RvcInferError(5, "nprobe >= 1 needs an IVF structure: the index source has none")
+            if centroids is None and train and nprobe == "file":
+                stored = 1
             nprobe = int(stored) if nprobe == "file" else int(nprobe)
             if not 0 <= nprobe <= 64:
                 raise RvcInferError(5, "nprobe must be in [0, 64]")
         v, vp = _f32(vectors)
         self._chk(self._L.rvc_load_index(self._h, vp, v.shape[0], v.shape[1]))
+        self._index_shape = (int(v.shape[0]), int(v.shape[1]))
         if nprobe is not None:
             if centroids is not None:
                 self.set_index_ivf(centroids, assign)
+            elif train and nprobe >= 1:
+                self.train_index_ivf(**(train if isinstance(train, dict) else {}))
             self.set_index_nprobe(nprobe)
 
     def set_index_ivf(self, centroids, assign):
@@ -166,6 +174,69 @@ class RvcInfer:
         self._chk(self._L.rvc_index_ivf_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def train_index_ivf(self, nlist=None, iters: int = 10, init_rows=None, seed: int = 0, nprobe=None) -> dict:
+        """rvc_train_index_ivf: k-means over the loaded index on the device, the result attached as set_index_ivf would.  nlist None = upstream's rule
+        min(floor(16 sqrt(n)), n // 39); init_rows None = the seeded sample.  nprobe given: set after training (training itself returns it to 0).
+        -> {nlist, longest_list, empty_lists, iters_run, moved_last, objective: [...], ms_assign, ms_update, ms_total}"""
+        rows = None if init_rows is None else np.ascontiguousarray(init_rows, np.int32)
+        if rows is not None and (rows.ndim != 1 or nlist not in (None, 0, rows.shape[0])):
+            raise RvcInferError(5, "init_rows: one row number per list")
+        self._chk(self._L.rvc_train_index_ivf(self._h, int(nlist or 0) if rows is None else rows.shape[0], int(iters),
+                                              None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_int32)), int(seed) & 0xffffffff))
+        if nprobe is not None:
+            self.set_index_nprobe(nprobe)
+        return self.index_ivf_train_info()
+
+    def index_ivf_train_info(self) -> dict:
+        """rvc_index_ivf_train_info + rvc_index_ivf_info of the last training on this engine"""
+        it, moved, n_obj = C.c_int(), C.c_size_t(), C.c_size_t()
+        obj, ms = (C.c_double * 101)(), (C.c_double * 3)()
+        self._chk(self._L.rvc_index_ivf_train_info(self._h, C.byref(it), C.byref(moved), obj, 101, C.byref(n_obj), ms))
+        nl, longest, empty = self.index_ivf_info()
+        return {"nlist": nl, "longest_list": longest, "empty_lists": empty, "iters_run": it.value, "moved_last": moved.value,
+                "objective": [obj[i] for i in range(n_obj.value)], "ms_assign": ms[0], "ms_update": ms[1], "ms_total": ms[2]}
+
+    def _index_dims(self):
+        """(n, dim) of the loaded index: noted by load_index / index_broadcast, checked against the bytes the engine holds"""
+        shape = getattr(self, "_index_shape", None)
+        _, nbytes = self.index_device_ptr()
+        if not shape or shape[0] * shape[1] * 4 != nbytes:
+            raise RvcInferError(5, "the shape of the loaded index is not known to this object (load it with load_index, or broadcast with vectors / expect)")
+        return shape
+
+    def index_ivf(self):
+        """rvc_get_index_ivf: the attached structure, trained or set -> (centroids (nlist, dim) float32, assign (n,) int32)"""
+        n, dim = self._index_dims()
+        nlist = self.index_ivf_info()[0]
+        cent, assign = np.empty((nlist, dim), np.float32), np.empty(n, np.int32)
+        self._chk(self._L.rvc_get_index_ivf(self._h, cent.ctypes.data_as(_FP), cent.size, assign.ctypes.data_as(C.POINTER(C.c_int32)), n))
+        return cent, assign
+
+    def index_vectors(self) -> np.ndarray:
+        """the loaded index (n, dim) copied back from the device (export: save_index)"""
+        n, dim = self._index_dims()
+        p, nbytes = self.index_device_ptr()
+        out = np.empty((n, dim), np.float32)
+        self.synchronize()
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        rc = hip.hipMemcpy(out.ctypes.data, p, nbytes, 2)                 # hipMemcpyDeviceToHost
+        if rc != 0:
+            raise RvcInferError(4, "hipMemcpy of the index failed (%d)" % rc)
+        return out
+
+    def save_index(self, path):
+        """Write the loaded index as a Faiss file upstream reads: an IndexIVFFlat with the attached structure (trained or set) and the engine's nprobe (1 while
+        the search is flat), or an IndexFlat when no structure is attached."""
+        from . import faiss_index as F
+        v = self.index_vectors()
+        try:
+            cent, assign = self.index_ivf()
+        except RvcInferError:
+            F.write_flat(os.fspath(path), v)
+            return
+        F.write_ivf_flat_assigned(os.fspath(path), v, cent, assign, nprobe=max(1, self.index_nprobe()))
+
     def rccl_unique_id(self) -> bytes:
         """rvc_rccl_unique_id: rank 0 creates the 128-byte ncclUniqueId the host then hands to the other ranks."""
         buf = C.create_string_buffer(128)
@@ -180,9 +251,11 @@ class RvcInfer:
         if vectors is not None:
             v, vp = _f32(vectors)
             self._chk(self._L.rvc_index_broadcast(self._h, unique_id, int(rank), int(world), vp, v.shape[0], v.shape[1]))
+            self._index_shape = (int(v.shape[0]), int(v.shape[1]))
         else:
             n, dim = expect if expect else (0, 0)
             self._chk(self._L.rvc_index_broadcast(self._h, unique_id, int(rank), int(world), None, int(n), int(dim)))
+            self._index_shape = (int(n), int(dim)) if expect else None
 
     def rccl_available(self) -> bool:
         """rvc_rccl_available: can this process load librccl?  (no communicator is created)"""
