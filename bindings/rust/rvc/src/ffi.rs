@@ -73,6 +73,9 @@ extern "C" {
     pub fn rvc_set_index_ivf(e: *mut RvcEngine, centroids: *const c_float, nlist: usize, dim: usize, assign: *const i32, n: usize) -> c_int;
     pub fn rvc_set_index_nprobe(e: *mut RvcEngine, nprobe: c_int) -> c_int;
     pub fn rvc_index_nprobe(e: *mut RvcEngine) -> c_int;
+    // neighbours blended per query: 4 (default) or upstream's 8; rvc_get_knn then writes idx / dist [rows][k]
+    pub fn rvc_set_index_k(e: *mut RvcEngine, k: c_int) -> c_int;
+    pub fn rvc_index_k(e: *mut RvcEngine) -> c_int;
     pub fn rvc_index_ivf_info(e: *mut RvcEngine, nlist: *mut usize, longest_list: *mut usize, empty_lists: *mut usize) -> c_int;
     // k-means training of an IVF structure for the loaded index, its report, and the attached structure read back
     pub fn rvc_train_index_ivf(e: *mut RvcEngine, nlist: usize, iters: c_int, init_rows: *const i32, seed: u32) -> c_int;

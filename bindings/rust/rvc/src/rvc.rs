@@ -165,6 +165,15 @@ impl RvcInfer {
         unsafe { ffi::rvc_index_nprobe(self.handle) }
     }
 
+    /// Neighbours blended per query: 4 (the default) or 8 (what upstream's pipelines search with).  Kept across index loads.
+    pub fn set_index_k(&mut self, k: i32) -> Result<(), RvcInferError> {
+        self.check(unsafe { ffi::rvc_set_index_k(self.handle, k) })
+    }
+
+    pub fn index_k(&self) -> i32 {
+        unsafe { ffi::rvc_index_k(self.handle) }
+    }
+
     /// (lists, rows of the longest list, empty lists) of the attached IVF structure.
     pub fn index_ivf_info(&mut self) -> Result<(usize, usize, usize), RvcInferError> {
         let (mut nlist, mut longest, mut empty) = (0usize, 0usize, 0usize);

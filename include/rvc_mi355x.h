@@ -89,9 +89,17 @@ int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded *
 rvc_status rvc_load_index(rvc_engine *e, const float *vectors, size_t n, size_t dim);
 rvc_status rvc_load_index_device(rvc_engine *e, const void *d_vectors, size_t n, size_t dim);  /* already in HBM (RCCL-broadcast) */
 void rvc_set_index_rate(rvc_engine *e, float rate);
-/* kNN hits of the last infer: idx[rows][4], squared distances; rows = return_length for stream 0, followed (stream-major) by the rows of as many
+/* kNN hits of the last infer: idx[rows][k], squared distances [rows][k], k = the rvc_index_k the last plan was built with (4 unless rvc_set_index_k changed it:
+   size the arrays for cap_rows * rvc_index_k(e) entries); rows = return_length for stream 0, followed (stream-major) by the rows of as many
    further streams of a batched call as cap_rows holds whole.  After rvc_infer_batch_g (streams bucketed by geometry) no rows are reported: *rows = 0. */
 rvc_status rvc_get_knn(rvc_engine *e, int32_t *idx, float *dist, size_t cap_rows, size_t *rows);
+/* Neighbours blended per query: 4 (the default) or 8, what every upstream RVC pipeline searches its index with.  The hits are the k
+   smallest by (exact fp32 distance, row number), the weights (1/d)^2 normalised over the k; the first four of the eight are the k = 4 hits.  Engine-wide, part of
+   a plan's identity, and a preference of the caller rather than a property of the index: it may be set before or after an index is loaded and survives
+   rvc_load_index*, rvc_index_broadcast, rvc_set_index_ivf and rvc_train_index_ivf.  The index needs at least k rows.  RVC_SHAPE: k other than 4 or 8; k = 8 on
+   a loaded index of fewer than 8 rows (and loading or broadcasting an index of fewer than k rows: the engine keeps what it had). */
+rvc_status rvc_set_index_k(rvc_engine *e, int k);
+int rvc_index_k(rvc_engine *e);                               /* 4 on a fresh engine */
 /* The one-launch retrieval (up to 11 streams) hands its partial lists from workgroup to workgroup inside the launch; if a workgroup does not arrive
    in time (a GPU shared with another process), the engine recomputes that chunk's retrieval through the exhaustive scan and the rest of the chunk,
    and the call still returns RVC_OK with the same hits.  This counts such chunks (0 on a GPU of one's own).  Unsynchronised calls (sync = 0) cannot
@@ -100,7 +108,7 @@ long long rvc_retrieval_recoveries(rvc_engine *e);
 /* IVF-probed retrieval: search the index as upstream searches its IndexIVFFlat files -- the nprobe nearest lists, then exact L2 inside
    them -- instead of scanning every row.  rvc_set_index_ivf attaches the structure (coarse centroids [nlist][dim] and the list number of every row) to the index
    the engine holds, after rvc_load_index / rvc_load_index_device / rvc_index_broadcast; both arrays are copied.  Rows keep their numbers: the ids of rvc_get_knn
-   mean what they mean for the flat search.  Fewer than four rows in the probed lists: the missing hits are idx -1 / dist +inf and that frame is not blended.
+   mean what they mean for the flat search.  Fewer than k rows (rvc_index_k: four, or eight) in the probed lists: the missing hits are idx -1 / dist +inf and that frame is not blended.
    RVC_SHAPE: no index loaded, dim or n different from the index, nlist 0 or above 65536, an assignment outside [0, nlist), a non-finite centroid, nprobe outside
    [0, 64], nprobe >= 1 without a structure.  Loading or broadcasting a new index drops the structure and returns nprobe to 0.  nprobe is engine-wide (not per
    stream) and part of a plan's identity. */

@@ -157,7 +157,7 @@ int rvc_debug_rm_block(rvc_engine *e, const rvc_debug_rm_block_spec *s, const fl
                        const float *bsc, float *x, float *y, float *p, long long *geo);
 /* the retrieval section of an infer plan alone (obs_rvc_amd/csrc/retrieval.hip build_retrieval; DESIGN.md "Retrieval: what is tested") on an engine that has an
  * index loaded (rvc_load_index on a bare rvc_create engine is enough): cv [streams][C][cv_ld], the ContentVec output in channel-major layout with T columns
- * used; phone [streams][C][ph_ld], R columns written; idx / dist [streams][R][4]; overflow [streams], the many-stream path's flag word per stream (zeros on the
+ * used; phone [streams][C][ph_ld], R columns written; idx / dist [streams][R][k], k = rvc_index_k (the plan the aid builds carries it, as it carries nprobe); overflow [streams], the many-stream path's flag word per stream (zeros on the
  * other paths).  cv and phone are uploaded, the ops run `reps` times eagerly, or -- graph != 0 -- captured once and the graph replayed `reps` times, and both come
  * back whole: the padding as it went in.  path 0: the planner's choice; 1: the plan's row-major exhaustive list (what a chunk runs after a hand-off time-out;
  * RVC_SHAPE when the plan has none).  The other paths are forced with the hooks RVC_KNN_EXHAUSTIVE and RVC_KNN_NO_GEMM, the one-launch form's grid with

@@ -36,6 +36,7 @@ SYMBOLS = [
     "rvc_session_set_noise_reduction", "rvc_session_set_noise_reduction_stream",
     "rvc_set_index_ivf", "rvc_set_index_nprobe", "rvc_index_nprobe", "rvc_index_ivf_info",
     "rvc_train_index_ivf", "rvc_index_ivf_train_info", "rvc_get_index_ivf",
+    "rvc_set_index_k", "rvc_index_k",
 ]
 
 
@@ -230,6 +231,9 @@ def lib():
         L.rvc_set_index_nprobe.argtypes = [vp, C.c_int]
         L.rvc_index_nprobe.argtypes = [vp]
         L.rvc_index_ivf_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    if hasattr(L, "rvc_set_index_k") or not override:
+        L.rvc_set_index_k.argtypes = [vp, C.c_int]
+        L.rvc_index_k.argtypes = [vp]
     if hasattr(L, "rvc_train_index_ivf") or not override:
         L.rvc_train_index_ivf.argtypes = [vp, sz, C.c_int, C.POINTER(i32), u32]
         L.rvc_index_ivf_train_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(C.c_double), sz, C.POINTER(sz), C.POINTER(C.c_double)]

@@ -755,9 +755,9 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
             throw ShapeError("retrieval spec");
         if (!e->d_index) throw ShapeError("no index loaded");
         if (e->index_dim != (size_t)C) throw ShapeError("index dimension does not match the feature dimension");
-        Plan pl; pl.B = B; pl.nprobe = e->index_nprobe;
+        Plan pl; pl.B = B; pl.nprobe = e->index_nprobe; pl.knn_k = e->index_k;
         Arena &A = pl.arena;
-        const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_hit = (size_t)B * R * KNN_K;
+        const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_hit = (size_t)B * R * pl.knn_k;
         T1 cvo, ph;
         cvo.p = A.floats(n_cv); cvo.B = B; cvo.C = C; cvo.T = T; cvo.ld = s->cv_ld; cvo.halo = 0; cvo.bs = (long long)C * s->cv_ld;
         ph.p = A.floats(n_ph); ph.B = B; ph.C = C; ph.T = R; ph.ld = s->ph_ld; ph.halo = 0; ph.bs = (long long)C * s->ph_ld;

@@ -260,7 +260,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
             p->with_index == with_index && p->with_protect == with_protect && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
-            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method && p->nprobe == (with_index ? e->index_nprobe : 0)) {
+            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -273,7 +273,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
     pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_protect = with_protect; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
-    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method; pl.nprobe = with_index ? e->index_nprobe : 0;
+    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
     T1 src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;

@@ -267,6 +267,7 @@ struct Plan {
     float *d_feat = nullptr; // extract_feature output (1,2T+1,C)
     int *d_knn_idx = nullptr; float *d_knn_dist = nullptr;
     int nprobe = 0;                                    // the engine's index_nprobe when the plan was built (with_index plans; 0 = flat search)
+    int knn_k = KNN_K;                                 // the engine's index_k when the plan was built: the K of its retrieval kernels and the width of d_knn_idx / d_knn_dist
     int *d_ivf_scanned = nullptr; int ivf_queries = 0;  // IVF retrieval: rows scanned per (stream, query) of the last run, and how many such words
     int *d_knn_overflow = nullptr;                     // many-stream retrieval: one word per stream, raised when its candidate set overflowed (nullptr on the one-launch form)
     // one-launch retrieval: its ticket counters, and what runs instead when a selector gave up (engine.hip recover_retrieval)
@@ -467,6 +468,7 @@ struct rvc_engine {
     // IVF structure over the loaded index (rvc_set_index_ivf; ivf.hip.h): centroids, CSR offsets and the row permutation, all on the device.
     // index_nprobe: 0 = flat search, else the lists probed per query; engine-wide and part of a plan's identity.  A new index drops both (build_index_aux)
     float *d_ivf_cent = nullptr; int *d_ivf_offs = nullptr, *d_ivf_perm = nullptr; size_t ivf_nlist = 0, ivf_longest = 0, ivf_empty = 0; int index_nprobe = 0;
+    int index_k = KNN_K;                                        // neighbours blended per query (rvc_set_index_k: 4 or 8); the caller's preference, kept across index loads; part of a plan's identity
     float index_prep_ms = 0.f;                                  // device-side repack + norms of the last index load
     // the last k-means training of an IVF structure (rvc_train_index_ivf; kmeans.hip.h): what rvc_index_ivf_train_info reports
     bool km_valid = false; int km_iters_run = 0; size_t km_moved_last = 0; std::vector<double> km_obj; double km_ms[3] = {0, 0, 0};

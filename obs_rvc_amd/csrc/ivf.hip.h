@@ -1,5 +1,5 @@
 // ivf.hip.h -- IVF-probed retrieval: the structure's device-side build at attach time and the two launches of the per-chunk section.
-// Included by retrieval.hip only.  The distance, the block-level top-4 and the blend are knn.hip.h's device functions: a probe of every list returns the
+// Included by retrieval.hip only.  The distance, the block-level top-K and the blend are knn.hip.h's device functions: a probe of every list returns the
 // flat search's bits.
 #pragma once
 #include "knn.hip.h"
@@ -107,7 +107,7 @@ static __global__ __launch_bounds__(256) void ivf_coarse_kernel(IvfCoarseP p)
 // ---- per chunk, launch 2: probe selection, exact scan of the probed lists, hits, blend ----
 // One workgroup per (query, stream).  The nprobe smallest (D, j) are found by nprobe rounds of a workgroup minimum "beyond the previous pick" over the query's
 // row of D, kept in LDS (a non-finite distance is no candidate, as in the flat search).  The probed lists' rows -- whole contiguous rows of the row-major matrix, gathered by
-// id through the CSR -- are staged in LDS tiles of up to 256 rows; thread r walks row r's chain and keeps a sorted list of four.  No margin, no overflow word,
+// id through the CSR -- are staged in LDS tiles of up to 256 rows; thread r walks row r's chain and keeps a sorted list of K (4 or 8: the plan's k).  No margin, no overflow word,
 // no hand-off: every probed row is scanned exactly.
 struct IvfScanP {
     const float *D; int nlist, nprobe;
@@ -118,13 +118,13 @@ struct IvfScanP {
     int *out_idx; float *out_dist;     // [B][R][K]
     int *scanned;                      // [B][nq]: rows this query's probe set held (rvc_profile_last_knn)
 };
-static __global__ __launch_bounds__(256) void ivf_scan_blend_kernel(IvfScanP p)
+template <int K> __device__ __forceinline__ void ivf_scan_blend_body(const IvfScanP p)
 {
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];            // row tile [IVF_TILE] | the query [dim]
     __shared__ int s_row[256];
     __shared__ int s_pl[IVF_MAX_NPROBE], s_ps[IVF_MAX_NPROBE + 1];           // the probed lists, nearest first, and the running sum of their lengths
-    __shared__ float wd[4][KNN_K]; __shared__ int wi[4][KNN_K];
-    __shared__ float sd[KNN_K]; __shared__ int si[KNN_K];
+    __shared__ float wd[4][K]; __shared__ int wi[4][K];
+    __shared__ float sd[K]; __shared__ int si[K];
     const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *tile = s_dyn, *s_x = s_dyn + IVF_TILE;
     const float *cvb = p.cv + (long long)b * p.cv_bs + p.first_raw + j;
@@ -166,9 +166,9 @@ static __global__ __launch_bounds__(256) void ivf_scan_blend_kernel(IvfScanP p)
     __syncthreads();
     const int total = s_ps[np];
     // 2. exact distances of the probed rows
-    float bd[KNN_K]; int bi[KNN_K];
+    float bd[K]; int bi[K];
 #pragma unroll
-    for (int k = 0; k < KNN_K; k++) { bd[k] = INFINITY; bi[k] = 0x7fffffff; }
+    for (int k = 0; k < K; k++) { bd[k] = INFINITY; bi[k] = 0x7fffffff; }
     for (int base = 0; base < total; base += 256) {
         const int nr = total - base < 256 ? total - base : 256;
         const int sh = nr <= 64 ? 8 : nr <= 128 ? 7 : 6, SD = 1 << sh, RS = SD + 1;      // dimensions per staged chunk: the fewer rows, the longer their pieces
@@ -217,7 +217,7 @@ static __global__ __launch_bounds__(256) void ivf_scan_blend_kernel(IvfScanP p)
         if (tid < nr && acc < INFINITY) {                                    // (a non-finite distance is no candidate)
             float cd = acc; int ci = row;
 #pragma unroll
-            for (int k = 0; k < KNN_K; k++) {
+            for (int k = 0; k < K; k++) {
                 const bool sw = cd < bd[k] || (cd == bd[k] && ci < bi[k]);
                 const float t0 = sw ? bd[k] : cd; const int t1 = sw ? bi[k] : ci;
                 bd[k] = sw ? cd : bd[k]; bi[k] = sw ? ci : bi[k];
@@ -225,25 +225,28 @@ static __global__ __launch_bounds__(256) void ivf_scan_blend_kernel(IvfScanP p)
             }
         }
     }
-    // 3. the four smallest (d, i) of the workgroup
-    knn_block_top4(bd, bi, wd, wi, sd, si);
-    // 4. hits and blend for the sliced frames that duplicate this raw frame; fewer than four hits: the frame keeps its raw feature
-    const bool four = si[KNN_K - 1] != 0x7fffffff;
-    float wn[KNN_K];
+    // 3. the K smallest (d, i) of the workgroup
+    knn_block_topk(bd, bi, wd, wi, sd, si);
+    // 4. hits and blend for the sliced frames that duplicate this raw frame; fewer than K hits: the frame keeps its raw feature
+    const bool full = si[K - 1] != 0x7fffffff;
+    float wn[K];
     knn_blend_weights(sd, wn);
     const int raw = j + p.first_raw;
     int r_lo = 2 * raw - p.skip_head, r_hi = raw >= p.T - 1 ? p.R : 2 * raw + 2 - p.skip_head;
     r_lo = r_lo < 0 ? 0 : r_lo; r_hi = r_hi > p.R ? p.R : r_hi;
     float *ph = p.phone + (long long)b * p.ph_bs;
     for (int c = tid; c < p.dim; c += 256) {
-        const float val = four ? knn_blend_channel(p.index, p.dim, c, si, wn, p.rate, s_x[c]) : s_x[c];
+        const float val = full ? knn_blend_channel(p.index, p.dim, c, si, wn, p.rate, s_x[c]) : s_x[c];
         for (int r = r_lo; r < r_hi; r++) ph[(long long)c * p.ph_cs + r] = val;
     }
-    if (tid < KNN_K)
+    if (tid < K)
         for (int r = r_lo; r < r_hi; r++) {
-            p.out_idx[((long long)b * p.R + r) * KNN_K + tid] = si[tid] == 0x7fffffff ? -1 : si[tid];
-            p.out_dist[((long long)b * p.R + r) * KNN_K + tid] = sd[tid];
+            p.out_idx[((long long)b * p.R + r) * K + tid] = si[tid] == 0x7fffffff ? -1 : si[tid];
+            p.out_dist[((long long)b * p.R + r) * K + tid] = sd[tid];
         }
 }
+// the entry points: K = 4 under the kernel's own name (profiles and rvc_profile_last_knn know it), K = 8 beside it; the plan's k picks one (retrieval.hip)
+static __global__ __launch_bounds__(256) void ivf_scan_blend_kernel(IvfScanP p) { ivf_scan_blend_body<KNN_K>(p); }
+static __global__ __launch_bounds__(256) void ivf_scan_blend_k8_kernel(IvfScanP p) { ivf_scan_blend_body<KNN_KMAX>(p); }
 
 }  // namespace rvc

@@ -11,7 +11,7 @@ namespace rvc {
 // flat-L2 retrieval (rvc.rs:159 is a TODO; definition in SURVEY.md Appendix A.4).
 // Stage 1: every thread owns one index vector (transposed index [dim][n] -> coalesced) and
 // accumulates exact sequential-fmaf distances to all queries of its stream; each workgroup
-// keeps its own top-4 per query.  Stage 2 merges the per-workgroup candidates
+// keeps its own top-K per query (K = 4, or 8: the plan's k; every kernel body here is template <int K>, instantiated for both behind two plain entry points, one of which the plan picks).  Stage 2 merges the per-workgroup candidates
 // (ascending (distance, index)), forms w = (1/d)^2 and blends.
 // ------------------------------------------------------------------------------------
 // The engine's exact distance d(x, y) (tests/knn_ref.py): an fp32 sequential fmaf chain over the rounded differences (x[c] - y[c]) in
@@ -24,36 +24,46 @@ __device__ __forceinline__ float knn_dist_exact(const float *x, const float *y, 
     for (int d = 0; d < dim; d++) acc = knn_dist_step(acc, x[d], y[d]);
     return acc;
 }
-// The blend: w = (1/d)^2 normalised over the four hits, feat = rate * sum w_k y_k + (1 - rate) * x.  A hit without a row (-1 or the
-// 0x7fffffff sentinel: a non-finite query) contributes nothing.  One definition for every blend kernel, so that they agree bit for bit.
-__device__ __forceinline__ void knn_blend_weights(const float *sd, float (&wn)[4])
+// The blend: w = (1/d)^2 normalised over the K hits (K = 4, or upstream's 8: rvc_set_index_k), feat = rate * sum w_k y_k + (1 - rate) * x,
+// the sum accumulated by fmaf in ascending hit order.  A hit without a row (-1 or the 0x7fffffff sentinel: a non-finite query) contributes nothing.  One
+// definition for every blend kernel, so that they agree bit for bit.
+template <int K> __device__ __forceinline__ void knn_blend_weights(const float *sd, float (&wn)[K])
 {
     float ws = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; k++) { const float inv = 1.0f / sd[k]; wn[k] = inv * inv; ws += wn[k]; }
+    for (int k = 0; k < K; k++) { const float inv = 1.0f / sd[k]; wn[k] = inv * inv; ws += wn[k]; }
 #pragma unroll
-    for (int k = 0; k < 4; k++) wn[k] = wn[k] / ws;
+    for (int k = 0; k < K; k++) wn[k] = wn[k] / ws;
 }
-__device__ __forceinline__ float knn_blend_channel(const float *index, int dim, int c, const int *si, const float (&wn)[4], float rate, float x)
+template <int K> __device__ __forceinline__ float knn_blend_channel(const float *index, int dim, int c, const int *si, const float (&wn)[K], float rate, float x)
 {
-    float y[4];
+    float y[K];
 #pragma unroll
-    for (int k = 0; k < 4; k++) y[k] = (si[k] >= 0 && si[k] != 0x7fffffff) ? index[(long long)si[k] * dim + c] : 0.f;
+    for (int k = 0; k < K; k++) y[k] = (si[k] >= 0 && si[k] != 0x7fffffff) ? index[(long long)si[k] * dim + c] : 0.f;
     float acc = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; k++) if (si[k] >= 0 && si[k] != 0x7fffffff) acc = fmaf(wn[k], y[k], acc);
+    for (int k = 0; k < K; k++) if (si[k] >= 0 && si[k] != 0x7fffffff) acc = fmaf(wn[k], y[k], acc);
     return fmaf(rate, acc, (1.0f - rate) * x);      // (explicit fmaf: no contraction choice is left to the compiler)
 }
 
-// The four smallest (distance, index) pairs of a 256-thread workgroup whose threads each hold a sorted list of four (+inf / 0x7fffffff = no entry): per wave by
-// four rounds of a minimum over the lanes' heads, then one thread merges the four waves' lists into sd / si (sorted; visible to every thread on return).
-__device__ __forceinline__ void knn_block_top4(const float (&ld)[4], const int (&li)[4], float (&wd)[4][4], int (&wi)[4][4], float (&sd)[4], int (&si)[4])
+// Element `pos` of a sorted register list, `none` past its end: a chain of selects under static indices (a dynamic index would put the list in scratch memory).
+template <int K, typename T> __device__ __forceinline__ T knn_pick(const T (&a)[K], int pos, T none)
+{
+    T v = none;
+#pragma unroll
+    for (int q = K - 1; q >= 0; q--) v = pos == q ? a[q] : v;
+    return v;
+}
+
+// The K smallest (distance, index) pairs of a 256-thread workgroup whose threads each hold a sorted list of K (+inf / 0x7fffffff = no entry): per wave by
+// K rounds of a minimum over the lanes' heads, then one thread merges the four waves' lists into sd / si (sorted; visible to every thread on return).
+template <int K> __device__ __forceinline__ void knn_block_topk(const float (&ld)[K], const int (&li)[K], float (&wd)[4][K], int (&wi)[4][K], float (&sd)[K], int (&si)[K])
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int pos = 0;
-    for (int k = 0; k < 4; k++) {
-        float md = pos == 0 ? ld[0] : pos == 1 ? ld[1] : pos == 2 ? ld[2] : pos == 3 ? ld[3] : INFINITY;
-        int mi = pos == 0 ? li[0] : pos == 1 ? li[1] : pos == 2 ? li[2] : pos == 3 ? li[3] : 0x7fffffff;
+    for (int k = 0; k < K; k++) {
+        float md = knn_pick(ld, pos, INFINITY);
+        int mi = knn_pick(li, pos, 0x7fffffff);
         const float d0 = md; const int i0 = mi;
         wave_min_pair(md, mi);
         if (d0 == md && i0 == mi && mi != 0x7fffffff) pos++;
@@ -62,9 +72,9 @@ __device__ __forceinline__ void knn_block_top4(const float (&ld)[4], const int (
     __syncthreads();
     if (threadIdx.x == 0) {
         int ps[4] = {0, 0, 0, 0};
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < K; k++) {
             float md = INFINITY; int mi = 0x7fffffff, mw = 0;
-            for (int w = 0; w < 4; w++) if (ps[w] < 4) {
+            for (int w = 0; w < 4; w++) if (ps[w] < K) {
                 float od = wd[w][ps[w]]; int oi = wi[w][ps[w]];
                 if (od < md || (od == md && oi < mi)) { md = od; mi = oi; mw = w; }
             }
@@ -89,11 +99,11 @@ struct KnnP {
     const int *overflow;     // when set: run only for streams whose candidate set overflowed (exhaustive fallback)
 };
 
-static __global__ __launch_bounds__(256) void knn_scan_kernel(KnnP p)
+template <int K> __device__ __forceinline__ void knn_scan_body(const KnnP &p)
 {
     if (p.overflow && p.overflow[blockIdx.y] == 0) return;
-    __shared__ float bd[KNN_MAXQ][4][KNN_K];
-    __shared__ int bi[KNN_MAXQ][4][KNN_K];
+    __shared__ float bd[KNN_MAXQ][4][K];
+    __shared__ int bi[KNN_MAXQ][4][K];
     const int b = blockIdx.y;
     // the queries are wave-uniform: read through the scalar cache (s_load) so they cost no LDS/VALU bandwidth
     const float *__restrict__ smem = p.q + (long long)b * p.q_bs;
@@ -125,11 +135,11 @@ static __global__ __launch_bounds__(256) void knn_scan_kernel(KnnP p)
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // per query: wave-level top-4 by repeated argmin over (distance, index)
+    // per query: wave-level top-K by repeated argmin over (distance, index)
     for (int j = 0; j < p.nq; j++) {
         const bool ok = i < p.n && acc[j] < INFINITY;     // (a non-finite distance -- a NaN or an Inf in the query -- is no candidate: the definition's `acc < best` never holds for it, and the other paths report -1)
         float d = ok ? acc[j] : INFINITY; int id = ok ? i : 0x7fffffff;
-        for (int k = 0; k < KNN_K; k++) {
+        for (int k = 0; k < K; k++) {
             float md = d; int mi = id;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
@@ -145,18 +155,23 @@ static __global__ __launch_bounds__(256) void knn_scan_kernel(KnnP p)
     if (threadIdx.x < p.nq) {
         const int j = threadIdx.x;
         int pos[4] = {0, 0, 0, 0};
-        for (int k = 0; k < KNN_K; k++) {
+        for (int k = 0; k < K; k++) {
             float md = INFINITY; int mi = 0x7fffffff, mw = 0;
-            for (int w = 0; w < 4; w++) if (pos[w] < KNN_K) {
+#pragma unroll
+            for (int w = 0; w < 4; w++) if (pos[w] < K) {
                 float od = bd[j][w][pos[w]]; int oi = bi[j][w][pos[w]];
                 if (od < md || (od == md && oi < mi)) { md = od; mi = oi; mw = w; }
             }
-            pos[mw]++;
-            long long o = (long long)b * p.cand_bs + ((long long)j * p.nblk + blockIdx.x) * KNN_K + k;
+#pragma unroll
+            for (int w = 0; w < 4; w++) pos[w] += w == mw ? 1 : 0;
+            long long o = (long long)b * p.cand_bs + ((long long)j * p.nblk + blockIdx.x) * K + k;
             p.cand_d[o] = md; p.cand_i[o] = mi;
         }
     }
 }
+// the entry points: K = 4 under the kernel's own name (profiles and rvc_profile_last_knn know it), K = 8 beside it; the plan's k picks one (retrieval.hip)
+static __global__ __launch_bounds__(256) void knn_scan_kernel(KnnP p) { knn_scan_body<KNN_K>(p); }
+static __global__ __launch_bounds__(256) void knn_scan_k8_kernel(KnnP p) { knn_scan_body<KNN_KMAX>(p); }
 
 struct KnnBlendP {
     const float *cand_d; const int *cand_i; int nblk, nq;
@@ -170,41 +185,47 @@ struct KnnBlendP {
 };
 
 // one workgroup per (unique query, stream): merge candidates, then blend every sliced frame that maps to it
-static __global__ __launch_bounds__(256) void knn_merge_blend_kernel(KnnBlendP p)
+template <int K> __device__ __forceinline__ void knn_merge_blend_body(const KnnBlendP &p)
 {
-    __shared__ float sd[KNN_K]; __shared__ int si[KNN_K];
-    __shared__ float wd[4][KNN_K]; __shared__ int wi[4][KNN_K];
+    __shared__ float sd[K]; __shared__ int si[K];
+    __shared__ float wd[4][K]; __shared__ int wi[4][K];
     const int j = blockIdx.x, b = blockIdx.y;
     if (p.overflow && p.overflow[b] == 0) return;
-    const long long base = ((long long)b * p.nq + j) * p.nblk * KNN_K;
-    const int total = p.nblk * KNN_K;
+    const long long base = ((long long)b * p.nq + j) * p.nblk * K;
+    const int total = p.nblk * K;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // each thread keeps a sorted local top-4 of its strided candidates
-    float ld[KNN_K]; int li[KNN_K];
-    for (int k = 0; k < KNN_K; k++) { ld[k] = INFINITY; li[k] = 0x7fffffff; }
+    // each thread keeps a sorted local top-K of its strided candidates (sorted insert by (distance, index) under static indices: the lists stay in registers)
+    float ld[K]; int li[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) { ld[k] = INFINITY; li[k] = 0x7fffffff; }
     for (int c = threadIdx.x; c < total; c += 256) {
-        float d = p.cand_d[base + c]; int id = p.cand_i[base + c];
-        if (d < ld[KNN_K - 1] || (d == ld[KNN_K - 1] && id < li[KNN_K - 1])) {
-            int q = KNN_K - 1;
-            while (q > 0 && (d < ld[q - 1] || (d == ld[q - 1] && id < li[q - 1]))) { ld[q] = ld[q - 1]; li[q] = li[q - 1]; q--; }
-            ld[q] = d; li[q] = id;
+        float cd = p.cand_d[base + c]; int ci = p.cand_i[base + c];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const bool sw = cd < ld[k] || (cd == ld[k] && ci < li[k]);
+            const float t0 = sw ? ld[k] : cd; const int t1 = sw ? li[k] : ci;
+            ld[k] = sw ? cd : ld[k]; li[k] = sw ? ci : li[k];
+            cd = t0; ci = t1;
         }
     }
-    knn_block_top4(ld, li, wd, wi, sd, si);
-    float w[KNN_K];
+    knn_block_topk(ld, li, wd, wi, sd, si);
+    float w[K];
     knn_blend_weights(sd, w);
     const float *qv = p.q + ((long long)b * p.nq + j) * p.dim;
     for (int r = 0; r < p.R; r++) {
         int s = (p.skip_head + r) / 2; s = s < p.T - 1 ? s : p.T - 1;
         if (s - p.first_raw != j) continue;
-        if (threadIdx.x < KNN_K) {
-            p.out_idx[((long long)b * p.R + r) * KNN_K + threadIdx.x] = si[threadIdx.x] == 0x7fffffff ? -1 : si[threadIdx.x];
-            p.out_dist[((long long)b * p.R + r) * KNN_K + threadIdx.x] = sd[threadIdx.x];
+        if (threadIdx.x < K) {
+            p.out_idx[((long long)b * p.R + r) * K + threadIdx.x] = si[threadIdx.x] == 0x7fffffff ? -1 : si[threadIdx.x];
+            p.out_dist[((long long)b * p.R + r) * K + threadIdx.x] = sd[threadIdx.x];
         }
         for (int c = threadIdx.x; c < p.dim; c += 256)
             p.phone[(long long)b * p.ph_bs + (long long)c * p.ph_cs + r] = knn_blend_channel(p.index, p.dim, c, si, w, p.rate, qv[c]);
     }
 }
+// the entry points: K = 4 under the kernel's own name (profiles and rvc_profile_last_knn know it), K = 8 beside it; the plan's k picks one (retrieval.hip)
+static __global__ __launch_bounds__(256) void knn_merge_blend_kernel(KnnBlendP p) { knn_merge_blend_body<KNN_K>(p); }
+static __global__ __launch_bounds__(256) void knn_merge_blend_k8_kernel(KnnBlendP p) { knn_merge_blend_body<KNN_KMAX>(p); }
 
 // ---- HBM-roofline retrieval: approximate distances on the matrix cores, exact re-rank of a provably sufficient candidate set ----
 // Stage A for one stream / few streams lives in knn_scan_select_kernel (below); with many streams it is one implicit GEMM (retrieval.hip).
@@ -215,25 +236,44 @@ __device__ __forceinline__ void knn_cx(float &d0, int &i0, float &d1, int &i1)
     const float td = sw ? d1 : d0, ud = sw ? d0 : d1; const int ti = sw ? i1 : i0, ui = sw ? i0 : i1;
     d0 = td; i0 = ti; d1 = ud; i1 = ui;
 }
+// bitonic clean-up of N = 4 or 8 pairs in registers (a bitonic sequence in, ascending out): strides N/2 .. 1
+template <int N> __device__ __forceinline__ void knn_bitonic_clean(float (&d)[N], int (&i)[N])
+{
+#pragma unroll
+    for (int st = N / 2; st >= 1; st >>= 1) {
+#pragma unroll
+        for (int a = 0; a < N; a++) if ((a & st) == 0) knn_cx(d[a], i[a], d[a + st], i[a + st]);
+    }
+}
+// the N smallest of two ascending lists of N, ascending, into a: min(a[r], b[N - 1 - r]) by (distance, index) is bitonic, then the clean-up
+template <int N> __device__ __forceinline__ void knn_merge_low(float (&ad)[N], int (&ai)[N], const float (&bd)[N], const int (&bi)[N])
+{
+#pragma unroll
+    for (int r = 0; r < N; r++) {
+        const bool tk = bd[N - 1 - r] < ad[r] || (bd[N - 1 - r] == ad[r] && bi[N - 1 - r] < ai[r]);
+        ad[r] = tk ? bd[N - 1 - r] : ad[r]; ai[r] = tk ? bi[N - 1 - r] : ai[r];
+    }
+    knn_bitonic_clean(ad, ai);
+}
 // One stream / few streams: the WHOLE retrieval as one launch (round 4; before: knn_queries + knn_dot + knn_select_blend + two idle
 // fallback launches = 116 us of kernels for a 307 MB scan).
 //  * scan: a workgroup owns tiles of 16 consecutive index vectors (a contiguous 16*dim*4-byte block of HBM in MFMA-fragment order, read
 //    exactly once; tiles blockIdx.x, + gridDim.x, ...) against up to 16 queries; its four waves split the K range of every tile (dot
 //    products on v_mfma_f32_16x16x4_f32, each wave streams its 12 KB of the tile with the NEXT tile's fragments requested as the slots
-//    free up), the partial 16 x 16 tiles meet in LDS and one wave (in turn) forms approx = |y|^2 - 2 x.y and keeps a running top-4 per
+//    free up), the partial 16 x 16 tiles meet in LDS and one wave (in turn) forms approx = |y|^2 - 2 x.y and keeps a running top-K per
 //    query.  Splitting K instead of handing whole tiles to waves makes the unit of work a quarter as long: 6 250 tiles over 768
 //    workgroups is 8 or 9 each, where 3 072 waves had 2 or 3 (the last third of the launch ran at 3 % occupancy).  The queries are
-//    gathered straight from the ContentVec output; NO approximate distance is written: the workgroup publishes 4 {distance, index}
+//    gathered straight from the ContentVec output; NO approximate distance is written: the workgroup publishes K {distance, index}
 //    granules per query (agent-scope stores, no cache maintenance), then takes a ticket;
 //  * select: the last S = min(queries, workgroups) arrivals stay, wait until every list of their stream is published and each runs
-//    stages 1-4 of knn_select_blend_kernel for its query: the global top-4 of the approximations is in the union of the workgroups'
-//    lists; a workgroup whose 4th entry is inside the margin may hide a 5th candidate ("flagged"): ALL of its vectors become candidates,
+//    stages 1-4 of knn_select_blend_kernel for its query: the global top-K of the approximations is in the union of the workgroups'
+//    lists; a workgroup whose K-th entry is inside the margin may hide a (K + 1)-th candidate ("flagged"): ALL of its vectors become candidates,
 //    so no approximation array and no second pass exist, and nothing can overflow (a degenerate index costs exact distances for the
 //    flagged workgroups' vectors, 8 per round).  Same candidate superset, same exact re-rank, same hits as the three-launch form.
 struct KnnFusedP {
     const float *indexF, *index, *ynorm; int n, dim;
     const float *cv; int cv_cs; long long cv_bs; int first_raw, nq, q0;
-    unsigned long long *lists;         // [B][16][gridDim.x][4] granules: low word = distance bits, high word = index
+    unsigned long long *lists;         // [B][16][gridDim.x][K] granules: low word = distance bits, high word = index
     unsigned *ticket;                  // [B][2]: arrivals, selectors done; zero between launches
     unsigned spin_limit;               // polls of the arrival counter before a selector gives up (ST_KNN_TIMEOUT)
     int test_lose;                     // test hook RVC_KNN_LOSE_TICKET: workgroup 0 of every stream never takes its ticket (a hand-off that cannot complete)
@@ -264,21 +304,24 @@ __device__ __forceinline__ float wave_min_dpp(float v)
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 48));
     return fminf(fminf(r0, r1), fminf(r2, r3));
 }
-#define KNN_FUSED_MAXG 1024            // workgroups per stream (a selector thread keeps 4 workgroup lists in registers)
-#define KNN_FUSED_ROWS 10              // candidate rows staged per round of the exact re-rank (<= 16: the final four are found among lanes 0..15)
-// dynamic LDS, in floats: scan = query rows + two buffers of partial tiles; select = query row + candidate ids + staged rows
-__host__ __device__ inline size_t knn_fused_lds_floats(int dim, int nqg, int G)
+#define KNN_FUSED_MAXG 1024            // workgroups per stream (a selector thread looks at 4 workgroup lists: all in registers at K = 4, two at a time at K = 8)
+// Candidate rows staged per round of the exact re-rank.  <= 16 for every K: thread r < KNN_FUSED_ROWS keeps the sorted K smallest of the rows IT walked, so the
+// final K are in the union of those lists, and the K rounds of a minimum that extract them exchange over xor 8 .. 1, i.e. among lanes 0..15.  K does not enter:
+// a deeper list costs registers in those lanes (2 K), not lanes.
+#define KNN_FUSED_ROWS 10
+// dynamic LDS, in floats: scan = query rows + two buffers of partial tiles; select = query row + candidate ids (<= K - 1 per unflagged workgroup) + staged rows
+__host__ __device__ inline size_t knn_fused_lds_floats(int dim, int nqg, int G, int K)
 {
-    const size_t QS = (size_t)dim + 4, scan = (size_t)nqg * QS + 2 * 4 * 256, sel = QS + (((size_t)3 * G + 3) & ~(size_t)3) + (size_t)KNN_FUSED_ROWS * QS;
+    const size_t QS = (size_t)dim + 4, scan = (size_t)nqg * QS + 2 * 4 * 256, sel = QS + (((size_t)(K - 1) * G + 3) & ~(size_t)3) + (size_t)KNN_FUSED_ROWS * QS;
     return scan > sel ? scan : sel;
 }
-static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p)
+template <int K> __device__ __forceinline__ void knn_scan_select_body(const KnnFusedP &p)
 {
     constexpr int D = 12;
     extern __shared__ __attribute__((aligned(16))) float s_q[];
-    __shared__ float wl_d[4][16][KNN_K]; __shared__ int wl_i[4][16][KNN_K];
-    __shared__ __attribute__((aligned(16))) float wd[4][KNN_K];
-    __shared__ float sd[KNN_K]; __shared__ int si[KNN_K];
+    __shared__ float wl_d[4][16][K]; __shared__ int wl_i[4][16][K];
+    __shared__ __attribute__((aligned(16))) float wd[4][K];
+    __shared__ float sd[K]; __shared__ int si[K];
     __shared__ float s_red[4];
     __shared__ int s_role, s_cnt, s_dead;
     __shared__ unsigned s_flag[KNN_FUSED_MAXG / 32];
@@ -319,9 +362,9 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
     float *part = s_q + (size_t)nqg * QS;                                 // [2][4 waves][64 lanes][4]
     __syncthreads();
     KNN_STAMP(1);
-    float rd[KNN_K]; int ri[KNN_K];
+    float rd[K]; int ri[K];
 #pragma unroll
-    for (int k = 0; k < KNN_K; k++) { rd[k] = INFINITY; ri[k] = 0x7fffffff; }
+    for (int k = 0; k < K; k++) { rd[k] = INFINITY; ri[k] = 0x7fffffff; }
     // (query columns past the last query of the group repeat it: their results are never read)
     const float *br = s_q + (li < nqg ? li : nqg - 1) * QS + kq * 4;
     for (int it = 0; t < ntile; t += G, it++) {
@@ -372,42 +415,54 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
                 vd[r] = (v < p.n && a == a) ? a : INFINITY;            // (a NaN never is a candidate; as +inf it cannot upset the sorting networks either)
                 vi[r] = v < p.n ? (int)v : 0x7fffffff;
             }
-            // the tile's 4 smallest per query column: sort the lane's 4, two bitonic merges with the lanes holding the column's other rows
+            // the lane's 4 sorted; the column's other 12 rows are in lanes ^ 16, ^ 32
             knn_cx(vd[0], vi[0], vd[1], vi[1]); knn_cx(vd[2], vi[2], vd[3], vi[3]); knn_cx(vd[0], vi[0], vd[2], vi[2]);
             knn_cx(vd[1], vi[1], vd[3], vi[3]); knn_cx(vd[1], vi[1], vd[2], vi[2]);
+            if constexpr (K == 4) {
+                // the tile's 4 smallest per query column: two bitonic merges with the lanes holding the column's other rows
 #pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) {
-                float od[4]; int oi[4];
+                for (int o = 16; o <= 32; o <<= 1) {
+                    float od[4]; int oi[4];
 #pragma unroll
-                for (int r = 0; r < 4; r++) { od[r] = __shfl_xor(vd[3 - r], o, 64); oi[r] = __shfl_xor(vi[3 - r], o, 64); }
+                    for (int r = 0; r < 4; r++) { od[r] = __shfl_xor(vd[r], o, 64); oi[r] = __shfl_xor(vi[r], o, 64); }
+                    knn_merge_low(vd, vi, od, oi);
+                }
+                // ... merged into the wave's running list (both sorted: min(a[k], b[3 - k]) keeps the 4 smallest, then the bitonic clean-up)
+                knn_merge_low(rd, ri, vd, vi);
+            } else {
+                // the tile's 8 smallest per query column: the lane's 4 ascending and lane ^ 16's 4 descending are a bitonic 8 (all of the pair's rows: nothing
+                // is dropped yet), sorted by the clean-up in both lanes of the pair; one merge with lane ^ 32's sorted 8 keeps the 8 smallest of the 16
+                float ed[8]; int ei[8];
 #pragma unroll
-                for (int r = 0; r < 4; r++) { const bool tk = od[r] < vd[r] || (od[r] == vd[r] && oi[r] < vi[r]); vd[r] = tk ? od[r] : vd[r]; vi[r] = tk ? oi[r] : vi[r]; }
-                knn_cx(vd[0], vi[0], vd[2], vi[2]); knn_cx(vd[1], vi[1], vd[3], vi[3]); knn_cx(vd[0], vi[0], vd[1], vi[1]); knn_cx(vd[2], vi[2], vd[3], vi[3]);
+                for (int r = 0; r < 4; r++) { ed[r] = vd[r]; ei[r] = vi[r]; ed[4 + r] = __shfl_xor(vd[3 - r], 16, 64); ei[4 + r] = __shfl_xor(vi[3 - r], 16, 64); }
+                knn_bitonic_clean(ed, ei);
+                float od[8]; int oi[8];
+#pragma unroll
+                for (int r = 0; r < 8; r++) { od[r] = __shfl_xor(ed[r], 32, 64); oi[r] = __shfl_xor(ei[r], 32, 64); }
+                knn_merge_low(ed, ei, od, oi);
+                // ... merged into the wave's running list
+                knn_merge_low(rd, ri, ed, ei);
             }
-            // ... merged into the wave's running list (both sorted: min(a[k], b[3 - k]) keeps the 4 smallest, then the bitonic clean-up)
-#pragma unroll
-            for (int r = 0; r < 4; r++) { const bool tk = vd[3 - r] < rd[r] || (vd[3 - r] == rd[r] && vi[3 - r] < ri[r]); rd[r] = tk ? vd[3 - r] : rd[r]; ri[r] = tk ? vi[3 - r] : ri[r]; }
-            knn_cx(rd[0], ri[0], rd[2], ri[2]); knn_cx(rd[1], ri[1], rd[3], ri[3]); knn_cx(rd[0], ri[0], rd[1], ri[1]); knn_cx(rd[2], ri[2], rd[3], ri[3]);
         }
     }
     if (kq == 0) {
 #pragma unroll
-        for (int k = 0; k < KNN_K; k++) { wl_d[wave][li][k] = rd[k]; wl_i[wave][li][k] = ri[k]; }
+        for (int k = 0; k < K; k++) { wl_d[wave][li][k] = rd[k]; wl_i[wave][li][k] = ri[k]; }
     }
     __syncthreads();
     KNN_STAMP(2);
-    // the workgroup's list per query: merge of its four waves' lists, published as 4 granules; then the ticket (same wave: program order)
+    // the workgroup's list per query: merge of its four waves' lists, published as K granules; then the ticket (same wave: program order)
     if (tid < 16) {
         int pos[4] = {0, 0, 0, 0};
-        unsigned long long *out = p.lists + (((long long)b * 16 + tid) * G + blockIdx.x) * KNN_K;
+        unsigned long long *out = p.lists + (((long long)b * 16 + tid) * G + blockIdx.x) * K;
 #pragma unroll
-        for (int k = 0; k < KNN_K; k++) {
+        for (int k = 0; k < K; k++) {
             float md = INFINITY; int mi = 0x7fffffff, mw = 0;
 #pragma unroll
             for (int w = 0; w < 4; w++) {
-                const int pw = pos[w] < KNN_K ? pos[w] : KNN_K - 1;
+                const int pw = pos[w] < K ? pos[w] : K - 1;
                 const float od = wl_d[w][tid][pw]; const int oi = wl_i[w][tid][pw];
-                if (pos[w] < KNN_K && (od < md || (od == md && oi < mi))) { md = od; mi = oi; mw = w; }
+                if (pos[w] < K && (od < md || (od == md && oi < mi))) { md = od; mi = oi; mw = w; }
             }
 #pragma unroll
             for (int w = 0; w < 4; w++) pos[w] += (w == mw && mi != 0x7fffffff) ? 1 : 0;
@@ -442,10 +497,14 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
     }
     __syncthreads();
     KNN_STAMP(4);
-    // select-phase layout of the dynamic LDS: query row | candidate ids (<= 3 per unflagged workgroup) | KNN_FUSED_ROWS staged rows
+    // select-phase layout of the dynamic LDS: query row | candidate ids (<= K - 1 per unflagged workgroup) | KNN_FUSED_ROWS staged rows
     float *s_x = s_q;
     int *cand = reinterpret_cast<int *>(s_q + QS);
-    float *s_rows = s_q + QS + ((3 * G + 3) & ~3);
+    float *s_rows = s_q + QS + (((K - 1) * G + 3) & ~3);
+    // A selector thread looks at the lists of workgroups tid + 256 u, u < 4.  K = 4: all four in registers, loaded once.  K = 8: four lists are 64 granules
+    // (128 registers, live from the loads to the candidate collection, on top of the re-rank's 64): two rounds of two lists, fetched again (from the L2) for the
+    // collection, keep the kernel at the K = 4 register budget and out of scratch
+    constexpr int LPR = K == 4 ? 4 : 2, NLR = 4 / LPR;
     const int nv = p.dim >> 2;
     for (int jq = sel; jq < nqg && !s_dead; jq += S) {
         const int j = p.q0 + jq;
@@ -462,54 +521,59 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
         if (lane == 0) s_red[wave] = xn;
         if (tid < KNN_FUSED_MAXG / 32) s_flag[tid] = 0u;
         if (tid == 0) s_cnt = 0;
-        // this thread's workgroup lists: w = tid + 256 * u
-        float ld_[4][KNN_K]; int li_[4][KNN_K];
-        const unsigned long long *lq = p.lists + ((long long)b * 16 + jq) * G * KNN_K;
-        {
-            unsigned long long x[4][KNN_K];
+        // this thread's workgroup lists: w = tid + 256 * (lr * LPR + u)
+        float ld_[LPR][K]; int li_[LPR][K];
+        const unsigned long long *lq = p.lists + ((long long)b * 16 + jq) * G * K;
+        auto load_lists = [&](int lr) {
+            unsigned long long x[LPR][K];
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int w = tid + 256 * u;
+            for (int u = 0; u < LPR; u++) {
+                const int w = tid + 256 * (lr * LPR + u);
 #pragma unroll
-                for (int k = 0; k < KNN_K; k++) {
+                for (int k = 0; k < K; k++) {
                     x[u][k] = 0x7fffffff7f800000ull;      // {+inf, no index}
-                    if (w < G) x[u][k] = __hip_atomic_load(lq + (long long)w * KNN_K + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (w < G) x[u][k] = __hip_atomic_load(lq + (long long)w * K + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
+            for (int u = 0; u < LPR; u++) {
 #pragma unroll
-                for (int k = 0; k < KNN_K; k++) { ld_[u][k] = __uint_as_float((unsigned)x[u][k]); li_[u][k] = (int)(unsigned)(x[u][k] >> 32); }
+                for (int k = 0; k < K; k++) { ld_[u][k] = __uint_as_float((unsigned)x[u][k]); li_[u][k] = (int)(unsigned)(x[u][k] >> 32); }
             }
-        }
+        };
+        // 1. the K-th smallest approximate distance: per-thread sorted top-K (static indices only), wave extraction, 4-way merge
+        float td[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) td[k] = INFINITY;
+#pragma unroll
+        for (int lr = 0; lr < NLR; lr++) {
+            if (NLR > 1 && lr * LPR * 256 >= G) break;
+            load_lists(lr);
 #ifdef RVC_KNN_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        KNN_STAMP(12);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            KNN_STAMP(12);
 #endif
-        // 1. the 4th smallest approximate distance: per-thread sorted top-4 (static indices only), wave extraction, 4-way merge
-        float td[KNN_K];
 #pragma unroll
-        for (int k = 0; k < KNN_K; k++) td[k] = INFINITY;
+            for (int u = 0; u < LPR; u++) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
+                for (int k = 0; k < K; k++) {
+                    const float d = ld_[u][k];
+                    if (d < td[K - 1]) {
 #pragma unroll
-            for (int k = 0; k < KNN_K; k++) {
-                const float d = ld_[u][k];
-                if (d < td[KNN_K - 1]) {
-#pragma unroll
-                    for (int q = KNN_K - 1; q >= 1; q--) {
-                        const bool left = d < td[q - 1], here = !left && d < td[q];
-                        td[q] = left ? td[q - 1] : (here ? d : td[q]);
+                        for (int q = K - 1; q >= 1; q--) {
+                            const bool left = d < td[q - 1], here = !left && d < td[q];
+                            td[q] = left ? td[q - 1] : (here ? d : td[q]);
+                        }
+                        if (d < td[0]) td[0] = d;
                     }
-                    if (d < td[0]) td[0] = d;
                 }
             }
         }
         {
-            // the wave's four smallest, with multiplicity: the minimum of the lanes' heads, the lowest lane holding it moves on
+            // the wave's K smallest, with multiplicity: the minimum of the lanes' heads, the lowest lane holding it moves on
             int pos = 0;
-            for (int k = 0; k < KNN_K; k++) {
-                const float d0 = pos == 0 ? td[0] : pos == 1 ? td[1] : pos == 2 ? td[2] : pos == 3 ? td[3] : INFINITY;
+            for (int k = 0; k < K; k++) {
+                const float d0 = knn_pick(td, pos, INFINITY);
                 const float md = wave_min_dpp(d0);
                 const unsigned long long holders = __ballot(d0 == md && md < INFINITY);
                 if (holders && lane == __ffsll((long long)holders) - 1) pos++;
@@ -518,53 +582,61 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
         }
         KNN_STAMP(13);
         __syncthreads();
-        // (every thread merges the four waves' lists itself: 16 broadcast reads instead of a one-thread merge between two barriers)
-        float a4;
+        // (every thread merges the four waves' lists itself: 4 K broadcast reads instead of a one-thread merge between two barriers)
+        float aK;
         {
-            float m4[KNN_K];
+            float mK[K];
 #pragma unroll
-            for (int k = 0; k < KNN_K; k++) m4[k] = INFINITY;
+            for (int k = 0; k < K; k++) mK[k] = INFINITY;
 #pragma unroll
             for (int w = 0; w < 4; w++) {
-                const f32x4 wv = *reinterpret_cast<const f32x4 *>(&wd[w][0]);
 #pragma unroll
-                for (int k = 0; k < KNN_K; k++) {
-                    const float d = wv[k];
-                    if (d < m4[KNN_K - 1]) {
+                for (int k4 = 0; k4 < K; k4 += 4) {
+                    const f32x4 wv = *reinterpret_cast<const f32x4 *>(&wd[w][k4]);
 #pragma unroll
-                        for (int q = KNN_K - 1; q >= 1; q--) {
-                            const bool left = d < m4[q - 1], here = !left && d < m4[q];
-                            m4[q] = left ? m4[q - 1] : (here ? d : m4[q]);
+                    for (int k = 0; k < 4; k++) {
+                        const float d = wv[k];
+                        if (d < mK[K - 1]) {
+#pragma unroll
+                            for (int q = K - 1; q >= 1; q--) {
+                                const bool left = d < mK[q - 1], here = !left && d < mK[q];
+                                mK[q] = left ? mK[q - 1] : (here ? d : mK[q]);
+                            }
+                            if (d < mK[0]) mK[0] = d;
                         }
-                        if (d < m4[0]) m4[0] = d;
                     }
                 }
             }
-            a4 = m4[KNN_K - 1];
+            aK = mK[K - 1];
         }
         KNN_STAMP(5);
-        // 2. candidates within the error margin of the approximate 4th distance (bound and margin as in knn_select_blend_kernel)
+        // 2. candidates within the error margin of the approximate K-th distance (bound and margin as in knn_select_blend_kernel)
         const float s_xn = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-        const float margin = 2e-3f * (fabsf(a4 + s_xn) + s_xn + 1e-3f);
-        const float thr = a4 + margin;
+        const float margin = 2e-3f * (fabsf(aK + s_xn) + s_xn + 1e-3f);
+        const float thr = aK + margin;
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int w = tid + 256 * u;
-            if (w < G) {
-                if (ld_[u][KNN_K - 1] <= thr) atomicOr(&s_flag[w >> 5], 1u << (w & 31));     // may hide a 5th candidate: expanded below
-                else {
+        for (int lr = 0; lr < NLR; lr++) {
+            if (NLR > 1 && lr * LPR * 256 >= G) break;
+            if constexpr (NLR > 1) load_lists(lr);
 #pragma unroll
-                    for (int k = 0; k < KNN_K - 1; k++) if (ld_[u][k] <= thr) cand[atomicAdd(&s_cnt, 1)] = li_[u][k];
+            for (int u = 0; u < LPR; u++) {
+                const int w = tid + 256 * (lr * LPR + u);
+                if (w < G) {
+                    if (ld_[u][K - 1] <= thr) atomicOr(&s_flag[w >> 5], 1u << (w & 31));     // may hide a (K + 1)-th candidate: expanded below
+                    else {
+#pragma unroll
+                        for (int k = 0; k < K - 1; k++) if (ld_[u][k] <= thr) cand[atomicAdd(&s_cnt, 1)] = li_[u][k];
+                    }
                 }
             }
         }
         __syncthreads();
         // 3. exact distances in the reference's order (ascending-d sequential fmaf).  The rows are fetched with coalesced 16-byte loads
         //    and staged in LDS as DIFFERENCES x - y (every thread subtracts what it fetched), so that the one thread per row that walks
-        //    the chain issues a single dependent fmaf per dimension; thread r < KNN_FUSED_ROWS keeps a sorted top-4 of what it has seen
-        float bd[KNN_K]; int bi[KNN_K];
+        //    the chain issues a single dependent fmaf per dimension; thread r < KNN_FUSED_ROWS keeps a sorted top-K of what it has seen
+        float bd[K]; int bi[K];
 #pragma unroll
-        for (int k = 0; k < KNN_K; k++) { bd[k] = INFINITY; bi[k] = 0x7fffffff; }
+        for (int k = 0; k < K; k++) { bd[k] = INFINITY; bi[k] = 0x7fffffff; }
         auto round = [&](auto row_of, int nrows) {
             __syncthreads();
             for (int i = tid; i < nrows * nv; i += 256) {
@@ -633,7 +705,7 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
                 float cd = acc; int ci = row_of(tid);
                 // sorted insert by (distance, index); a NaN distance never enters
 #pragma unroll
-                for (int k = 0; k < KNN_K; k++) {
+                for (int k = 0; k < K; k++) {
                     const bool sw = cd < bd[k] || (cd == bd[k] && ci < bi[k]);
                     const float t0 = sw ? bd[k] : cd; const int t1 = sw ? bi[k] : ci;
                     bd[k] = sw ? cd : bd[k]; bi[k] = sw ? ci : bi[k];
@@ -662,12 +734,12 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
             }
         }
         KNN_STAMP(6);
-        // the final four: wave 0 holds every list (threads < KNN_FUSED_ROWS); four rounds of a minimum by (distance, index) over those lanes
+        // the final K: wave 0 holds every list (threads < KNN_FUSED_ROWS); K rounds of a minimum by (distance, index) over those lanes
         if (wave == 0) {
             int pos = 0;
-            for (int k = 0; k < KNN_K; k++) {
-                float md = pos == 0 ? bd[0] : pos == 1 ? bd[1] : pos == 2 ? bd[2] : pos == 3 ? bd[3] : INFINITY;
-                int mi = pos == 0 ? bi[0] : pos == 1 ? bi[1] : pos == 2 ? bi[2] : pos == 3 ? bi[3] : 0x7fffffff;
+            for (int k = 0; k < K; k++) {
+                float md = knn_pick(bd, pos, INFINITY);
+                int mi = knn_pick(bi, pos, 0x7fffffff);
                 int ml = lane;
 #pragma unroll
                 for (int o = 8; o > 0; o >>= 1) {
@@ -682,7 +754,7 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
         KNN_STAMP(8);
         // 4. blend: w = (1/d)^2 normalised, feat = rate * sum w_i y_i + (1 - rate) * feat; computed once per
         //    query, written to every sliced frame that duplicates it (a contiguous range of r: frames (skip_head + r) / 2, clamped to T - 1)
-        float wn[KNN_K];
+        float wn[K];
         knn_blend_weights(sd, wn);
         const int raw = j + p.first_raw;
         int r_lo = 2 * raw - p.skip_head, r_hi = raw >= p.T - 1 ? p.R : 2 * raw + 2 - p.skip_head;
@@ -693,10 +765,10 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
             for (int r = r_lo; r < r_hi; r++) ph[(long long)c * p.ph_cs + r] = val;
         }
         KNN_STAMP(9);
-        if (tid < KNN_K)
+        if (tid < K)
             for (int r = r_lo; r < r_hi; r++) {
-                p.out_idx[((long long)b * p.R + r) * KNN_K + tid] = si[tid] == 0x7fffffff ? -1 : si[tid];   // -1: no hit (non-finite query)
-                p.out_dist[((long long)b * p.R + r) * KNN_K + tid] = sd[tid];
+                p.out_idx[((long long)b * p.R + r) * K + tid] = si[tid] == 0x7fffffff ? -1 : si[tid];   // -1: no hit (non-finite query)
+                p.out_dist[((long long)b * p.R + r) * K + tid] = sd[tid];
             }
     }
     __syncthreads();
@@ -710,6 +782,9 @@ static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p
         }
     }
 }
+// the entry points: K = 4 under the kernel's own name (profiles and rvc_profile_last_knn know it), K = 8 beside it; the plan's k picks one (retrieval.hip)
+static __global__ __launch_bounds__(256) void knn_scan_select_kernel(KnnFusedP p) { knn_scan_select_body<KNN_K>(p); }
+static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void knn_scan_select_k8_kernel(KnnFusedP p) { knn_scan_select_body<KNN_KMAX>(p); }
 
 // |y_i|^2 for every index vector (load time); nhn = -|y_i|^2 / 2 is the per-column "residual" of the many-stream distance GEMM
 static __global__ void knn_norms_kernel(const float *index, int n, int dim, float *ynorm, float *nhn)
@@ -763,9 +838,9 @@ static __global__ __launch_bounds__(64) void knn_pack_queries_kernel(const float
 }
 
 // Stage B (knn_select_blend_kernel): one workgroup per (unique query, stream).
-//  1. exact top-4 of the APPROXIMATE distances -> 4th smallest a4;
-//  2. candidate set = { i : approx_i <= a4 + margin }: since |approx - true| <= err < margin/2, every vector of the true top-4
-//     (true distance <= true 4th distance <= a4 + err) is in the set;
+//  1. exact top-K of the APPROXIMATE distances -> K-th smallest a_K (K = 4 or 8: the plan's k);
+//  2. candidate set = { i : approx_i <= a_K + margin }: since |approx - true| <= err < margin/2, every vector of the true top-K
+//     (true distance <= true K-th distance <= a_K + err) is in the set;
 //  3. exact sequential-fmaf distances (the reference definition) for the candidates, final order by (distance, index);
 //  4. w = (1/d)^2 blend of the duplicated frames (as before).
 // More than KNN_CAND candidates (degenerate data, e.g. thousands of duplicate vectors): overflow[b] is raised and the
@@ -778,10 +853,10 @@ struct KnnSelP {
     float *phone; int ph_cs; long long ph_bs;
     int *out_idx; float *out_dist; int *overflow;
 };
-static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p)
+template <int K> __device__ __forceinline__ void knn_select_blend_body(const KnnSelP &p)
 {
-    __shared__ float wd[16][KNN_K]; __shared__ int wi[16][KNN_K];
-    __shared__ float sd[KNN_K]; __shared__ int si[KNN_K];
+    __shared__ float wd[16][K]; __shared__ int wi[16][K];
+    __shared__ float sd[K]; __shared__ int si[K];
     __shared__ int cand_i[KNN_CAND]; __shared__ float cand_d[KNN_CAND];
     __shared__ int cnt; __shared__ float s_xn;
     extern __shared__ __attribute__((aligned(16))) float s_rows[];     // [32][dim + 4] candidate rows + the query
@@ -797,16 +872,16 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
     __syncthreads();
     if (tid == 0) { float t = 0.f; for (int w = 0; w < 16; w++) t += wd[w][0]; s_xn = t; }
     __syncthreads();
-    // 1. per-thread sorted top-4 of the approximate distances
-    float ld[KNN_K]; int li_[KNN_K];
+    // 1. per-thread sorted top-K of the approximate distances
+    float ld[K]; int li_[K];
 #pragma unroll
-    for (int k = 0; k < KNN_K; k++) { ld[k] = INFINITY; li_[k] = 0x7fffffff; }
+    for (int k = 0; k < K; k++) { ld[k] = INFINITY; li_[k] = 0x7fffffff; }
     // sorted insert with static indices only (a `while (q > 0 && d < ld[q - 1])` walk indexes the arrays dynamically, which puts them
     // in scratch memory): slot q takes its left neighbour if d belongs further left, d itself if it belongs here
     auto keep = [&](float d, int i) {
-        if (d < ld[KNN_K - 1]) {
+        if (d < ld[K - 1]) {
 #pragma unroll
-            for (int q = KNN_K - 1; q >= 1; q--) {
+            for (int q = K - 1; q >= 1; q--) {
                 const bool left = d < ld[q - 1], here = !left && d < ld[q];
                 ld[q] = left ? ld[q - 1] : (here ? d : ld[q]);
                 li_[q] = left ? li_[q - 1] : (here ? i : li_[q]);
@@ -833,8 +908,8 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
     }
     for (int i = 4 * n4 + tid; i < p.n; i += 1024) keep(a[i], i);
     int pos = 0;
-    for (int k = 0; k < KNN_K; k++) {
-        float md = pos < KNN_K ? ld[pos] : INFINITY; int mi = pos < KNN_K ? li_[pos] : 0x7fffffff;
+    for (int k = 0; k < K; k++) {
+        float md = knn_pick(ld, pos, INFINITY); int mi = knn_pick(li_, pos, 0x7fffffff);
         const float d0 = md; const int i0 = mi;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -849,27 +924,29 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
         int ps[16];
         for (int w = 0; w < 16; w++) ps[w] = 0;
         float last = INFINITY;
-        for (int k = 0; k < KNN_K; k++) {
+        for (int k = 0; k < K; k++) {
             float md = INFINITY; int mi = 0x7fffffff, mw = 0;
-            for (int w = 0; w < 16; w++) if (ps[w] < KNN_K) {
+#pragma unroll
+            for (int w = 0; w < 16; w++) if (ps[w] < K) {
                 float od = wd[w][ps[w]]; int oi = wi[w][ps[w]];
                 if (od < md || (od == md && oi < mi)) { md = od; mi = oi; mw = w; }
             }
-            ps[mw]++;
+#pragma unroll
+            for (int w = 0; w < 16; w++) ps[w] += w == mw ? 1 : 0;
             last = md;
         }
-        sd[0] = last;      // approximate 4th-smallest
+        sd[0] = last;      // approximate K-th smallest
     }
     __syncthreads();
-    // 2. candidates within the error margin of the approximate 4th distance.  fp32 error of approx is bounded by
+    // 2. candidates within the error margin of the approximate K-th distance.  fp32 error of approx is bounded by
     //    ~dim*2^-24*(|y|^2 + 2|x||y|) <= 1e-4*(|x|^2 + |y|^2) for dim <= 1024; the margin is 20x that.
-    const float a4 = sd[0];
-    const float margin = 2e-3f * (fabsf(a4 + s_xn) + s_xn + 1e-3f);
-    const float thr = a4 + margin;
+    const float aK = sd[0];
+    const float margin = 2e-3f * (fabsf(aK + s_xn) + s_xn + 1e-3f);
+    const float thr = aK + margin;
     __syncthreads();
-    // The candidates are among the per-thread top-4 lists unless some thread holds MORE than four values within the margin (its list is
-    // then truncated: its 4th entry is still <= thr).  Common case: collect from the lists, no second pass over the n distances.
-    if (ld[KNN_K - 1] <= thr) atomicOr(&cnt, 0x40000000);       // (a truncated list sends the stream through the full pass below)
+    // The candidates are among the per-thread top-K lists unless some thread holds MORE than K values within the margin (its list is
+    // then truncated: its K-th entry is still <= thr).  Common case: collect from the lists, no second pass over the n distances.
+    if (ld[K - 1] <= thr) atomicOr(&cnt, 0x40000000);       // (a truncated list sends the stream through the full pass below)
     __syncthreads();
     const bool truncated = (cnt & 0x40000000) != 0;
     __syncthreads();
@@ -877,7 +954,7 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
     __syncthreads();
     if (!truncated) {
 #pragma unroll
-        for (int k = 0; k < KNN_K; k++)
+        for (int k = 0; k < K; k++)
             if (ld[k] <= thr) { int c = atomicAdd(&cnt, 1); if (c < KNN_CAND) cand_i[c] = li_[k]; }
     } else {
     for (int i4 = tid; i4 < n4; i4 += 4 * 1024) {
@@ -923,7 +1000,7 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
     }
     __syncthreads();
     if (tid == 0) {
-        for (int k = 0; k < KNN_K; k++) {
+        for (int k = 0; k < K; k++) {
             float md = INFINITY; int mi = 0x7fffffff, mc = -1;
             for (int c = 0; c < ncand; c++) {
                 const float od = cand_d[c]; const int oi = cand_i[c];
@@ -935,19 +1012,22 @@ static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p
     }
     __syncthreads();
     // 4. blend: w = (1/d)^2 normalised, feat = rate * sum w_i y_i + (1 - rate) * feat
-    float w[KNN_K];
+    float w[K];
     knn_blend_weights(sd, w);
     for (int r = 0; r < p.R; r++) {
         int s = (p.skip_head + r) / 2; s = s < p.T - 1 ? s : p.T - 1;
         if (s - p.first_raw != j) continue;
-        if (tid < KNN_K) {
-            p.out_idx[((long long)b * p.R + r) * KNN_K + tid] = si[tid] == 0x7fffffff ? -1 : si[tid];   // -1: no hit (non-finite query)
-            p.out_dist[((long long)b * p.R + r) * KNN_K + tid] = sd[tid];
+        if (tid < K) {
+            p.out_idx[((long long)b * p.R + r) * K + tid] = si[tid] == 0x7fffffff ? -1 : si[tid];   // -1: no hit (non-finite query)
+            p.out_dist[((long long)b * p.R + r) * K + tid] = sd[tid];
         }
         for (int c = tid; c < p.dim; c += 1024)
             p.phone[(long long)b * p.ph_bs + (long long)c * p.ph_cs + r] = knn_blend_channel(p.index, p.dim, c, si, w, p.rate, qv[c]);
     }
 }
+// the entry points: K = 4 under the kernel's own name (profiles and rvc_profile_last_knn know it), K = 8 beside it; the plan's k picks one (retrieval.hip)
+static __global__ __launch_bounds__(1024) void knn_select_blend_kernel(KnnSelP p) { knn_select_blend_body<KNN_K>(p); }
+static __global__ __launch_bounds__(1024) void knn_select_blend_k8_kernel(KnnSelP p) { knn_select_blend_body<KNN_KMAX>(p); }
 
 // unique query rows for retrieval: q[j][c] = cv[c][first_raw + j]
 static __global__ void knn_queries_kernel(const float *cv, int cv_cs, long long cv_bs, int C, int first_raw, int nq, float *q)

@@ -93,7 +93,7 @@ rvc_status rvc_index_broadcast(rvc_engine *e, const void *unique_id128, int rank
         if (world < 1 || rank < 0 || rank >= world || !unique_id128) throw ShapeError("index broadcast: bad rank / world / unique id");
         std::string root_err;
         if (rank == 0 && !vectors && !e->d_index) root_err = "index broadcast: rank 0 has neither host vectors nor a loaded index";
-        else if (rank == 0 && vectors && (n < KNN_K || dim < 1)) root_err = "index broadcast: index needs at least 4 vectors";
+        else if (rank == 0 && vectors && (n < (size_t)e->index_k || dim < 1)) root_err = "index broadcast: index needs at least " + std::to_string(e->index_k) + " vectors";
         RcclApi &api = rccl_api();
         if (!api.lib) throw std::runtime_error(api.err);
         HIPCHK(hipDeviceSynchronize());
@@ -121,7 +121,7 @@ rvc_status rvc_index_broadcast(rvc_engine *e, const void *unique_id128, int rank
             // a rank that simply threw here would leave the others blocked in the payload broadcast
             int ok = 1;
             if (!root_err.empty()) { ok = 0; local_err = root_err; }
-            else if (bn < KNN_K || bd < 1 || bn * bd > ((size_t)1 << 36)) { ok = 0; local_err = "index broadcast: rank 0 sent no usable index (its arguments were rejected there, or the size is implausible)"; }
+            else if (bn < (size_t)e->index_k || bd < 1 || bn * bd > ((size_t)1 << 36)) { ok = 0; local_err = "index broadcast: rank 0 sent no usable index (its arguments were rejected there, or the size is implausible)"; }
             else if (rank != 0 && n && dim && (n != bn || dim != bd)) { ok = 0; local_err = "index broadcast: this rank expected a different index shape than rank 0 sent"; }
             else if (hipMalloc(&d_new, bn * bd * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); d_new = nullptr; ok = 0; local_err = "index broadcast: out of device memory for the index"; }
             int *d_ok = reinterpret_cast<int *>(d_hdr + 2);

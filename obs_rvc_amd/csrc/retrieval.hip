@@ -10,6 +10,8 @@ namespace rvc {
 // The retrieval section of an infer plan: queries from the ContentVec output, one-pass approximate scan (or one implicit GEMM for many streams),
 // exact re-rank + blend into `phone`, exhaustive fallback for streams whose candidate set overflowed.
 std::atomic<int> g_knn_test_lose{0};
+// the plan's k picks the entry point of a retrieval kernel (bodies are template <int K>, K = 4 or 8; there is no run-time k inside the kernels)
+#define KNN_KERNEL_FOR(stem, k) ((k) == KNN_KMAX ? stem##_k8_kernel : stem##_kernel)
 static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int nblk, int first_raw, uint32_t skip_head, uint32_t R, int T, const T1 &phone, const T1 &cvo,
                              bool fast, int *d_overflow, float *d_q = nullptr, float *cand_d = nullptr, int *cand_i = nullptr);
 
@@ -44,10 +46,11 @@ static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_r
             const size_t lds = ((size_t)IVF_TILE + C) * sizeof(float);
             if (lds > 144 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
             dim3 grid(nq, B);
+            const auto scan_kernel = KNN_KERNEL_FOR(ivf_scan_blend, pl.knn_k);
             pl.ops.push_back([=](hipStream_t s) {
                 const ProfEvent *pe = plp->prof_slot(0, 0, -1, "knn_ivf_scan");     // (bytes: the rows the probe sets held, read back by rvc_profile_last_knn)
-                if (pe) hipExtLaunchKernelGGL(ivf_scan_blend_kernel, grid, dim3(256), (uint32_t)lds, s, pe->a, pe->b, 0, sp);
-                else hipLaunchKernelGGL(ivf_scan_blend_kernel, grid, dim3(256), lds, s, sp);
+                if (pe) hipExtLaunchKernelGGL(scan_kernel, grid, dim3(256), (uint32_t)lds, s, pe->a, pe->b, 0, sp);
+                else hipLaunchKernelGGL(scan_kernel, grid, dim3(256), lds, s, sp);
             });
         }
 }
@@ -59,8 +62,11 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         const int first_raw = std::min((int)skip_head / 2, T - 1), last_raw = std::min((int)(skip_head + R - 1) / 2, T - 1);
         const int nq = last_raw - first_raw + 1;
         const int nblk = (int)((e->index_n + 255) / 256);
-        pl.d_knn_idx = (int *)pl.arena.alloc((size_t)B * R * KNN_K * sizeof(int));
-        pl.d_knn_dist = pl.arena.floats((size_t)B * R * KNN_K);
+        const int K = pl.knn_k;
+        if (K != KNN_K && K != KNN_KMAX) throw ShapeError("k must be 4 or 8");
+        if (e->index_n < (size_t)K) throw ShapeError("index needs at least " + std::to_string(K) + " vectors");
+        pl.d_knn_idx = (int *)pl.arena.alloc((size_t)B * R * K * sizeof(int));
+        pl.d_knn_dist = pl.arena.floats((size_t)B * R * K);
         T1 cvo = pl.cv_out;
         if (pl.nprobe > 0) { build_ivf(e, pl, B, C, nq, first_raw, skip_head, R, T, phone, cvo); return; }
         // Stage A + B: approximate distances on the matrix cores in one pass over the index (HBM-bound), exact re-rank of a
@@ -86,16 +92,16 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
             const unsigned G = std::min(std::min((unsigned)((e->index_n + 63) / 64), std::max(knn_wgs / (unsigned)B, 64u)), (unsigned)KNN_FUSED_MAXG);
             const int ngroups = (nq + 15) / 16;
             snprintf(g_last_kernel, sizeof g_last_kernel, "knn_fused");
-            unsigned long long *lists = (unsigned long long *)pl.arena.alloc((size_t)ngroups * B * 16 * G * KNN_K * sizeof(unsigned long long));
+            unsigned long long *lists = (unsigned long long *)pl.arena.alloc((size_t)ngroups * B * 16 * G * K * sizeof(unsigned long long));
             unsigned *ticket = (unsigned *)pl.arena.alloc((size_t)ngroups * B * 2 * sizeof(unsigned));
             HIPCHK(hipMemset(ticket, 0, (size_t)ngroups * B * 2 * sizeof(unsigned)));
             pl.knn_ticket = ticket; pl.knn_ticket_bytes = (size_t)ngroups * B * 2 * sizeof(unsigned);
             for (int gi = 0; gi < ngroups; gi++) {
-                const size_t lds = knn_fused_lds_floats(C, std::min(16, nq - gi * 16), (int)G) * sizeof(float);
+                const size_t lds = knn_fused_lds_floats(C, std::min(16, nq - gi * 16), (int)G, K) * sizeof(float);
                 if (lds > 128 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
                 KnnFusedP fp{}; fp.indexF = e->d_indexF; fp.index = e->d_index; fp.ynorm = e->d_ynorm; fp.n = (int)e->index_n; fp.dim = C;
                 fp.cv = cvo.p; fp.cv_cs = cvo.ld; fp.cv_bs = cvo.bs; fp.first_raw = first_raw; fp.nq = nq; fp.q0 = gi * 16;
-                fp.lists = lists + (size_t)gi * B * 16 * G * KNN_K; fp.ticket = ticket + (size_t)gi * B * 2;
+                fp.lists = lists + (size_t)gi * B * 16 * G * K; fp.ticket = ticket + (size_t)gi * B * 2;
                 fp.skip_head = (int)skip_head; fp.T = T; fp.R = (int)R; fp.rate = e->index_rate;
                 fp.phone = phone.p; fp.ph_cs = phone.ld; fp.ph_bs = phone.bs; fp.out_idx = pl.d_knn_idx; fp.out_dist = pl.d_knn_dist;
                 fp.status = &e->d_state[0].status; fp.status_stride = (int)(sizeof(StreamState) / sizeof(int));
@@ -103,13 +109,14 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
                 dim3 grid(G, B);
                 Plan *plp = &pl;
                 const double scan_bytes = (double)e->index_n * C * sizeof(float) * B;     // algorithmic bytes: the index, read once per query group
+                const auto fused_kernel = KNN_KERNEL_FOR(knn_scan_select, K);
                 pl.ops.push_back([=](hipStream_t s) {
                     const ProfEvent *pe = plp->prof_slot(0, scan_bytes, -1, "knn_scan_select");
                     if (g_knn_test_lose.load(std::memory_order_relaxed)) {       // test hook (rvc_debug_option RVC_KNN_LOSE_TICKET): a hand-off that cannot complete
                         KnnFusedP f2 = fp; f2.test_lose = 1; f2.spin_limit = 1u << 12;
-                        hipLaunchKernelGGL(knn_scan_select_kernel, grid, dim3(256), lds, s, f2);
-                    } else if (pe) hipExtLaunchKernelGGL(knn_scan_select_kernel, grid, dim3(256), (uint32_t)lds, s, pe->a, pe->b, 0, fp);
-                    else hipLaunchKernelGGL(knn_scan_select_kernel, grid, dim3(256), lds, s, fp);
+                        hipLaunchKernelGGL(fused_kernel, grid, dim3(256), lds, s, f2);
+                    } else if (pe) hipExtLaunchKernelGGL(fused_kernel, grid, dim3(256), (uint32_t)lds, s, pe->a, pe->b, 0, fp);
+                    else hipLaunchKernelGGL(fused_kernel, grid, dim3(256), lds, s, fp);
                 });
             }
             // What the engine runs instead when a selector gave up (ST_KNN_TIMEOUT: a workgroup of the launch did not arrive in time, e.g. on a GPU
@@ -126,8 +133,8 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         }
         // many streams (GEMM scan) or the exhaustive definition: explicit query rows, candidate lists per 256-vector block
         float *d_q = pl.arena.floats((size_t)B * nq * C);
-        float *cand_d = pl.arena.floats((size_t)B * nq * nblk * KNN_K);
-        int *cand_i = (int *)pl.arena.alloc((size_t)B * nq * nblk * KNN_K * sizeof(int));
+        float *cand_d = pl.arena.floats((size_t)B * nq * nblk * K);
+        int *cand_i = (int *)pl.arena.alloc((size_t)B * nq * nblk * K * sizeof(int));
         {
             dim3 grid((nq * C + 255) / 256, B);
             pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(knn_queries_kernel, grid, dim3(256), 0, s, cvo.p, cvo.ld, cvo.bs, C, first_raw, nq, d_q); });
@@ -158,7 +165,8 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
             dim3 sgrid(nq, B);
             const size_t slds = (size_t)33 * (C + 4) * sizeof(float);
             if (slds > 128 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
-            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(knn_select_blend_kernel, sgrid, dim3(1024), slds, s, sp); });
+            const auto select_kernel = KNN_KERNEL_FOR(knn_select_blend, K);
+            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(select_kernel, sgrid, dim3(1024), slds, s, sp); });
         }
         build_exhaustive(e, pl, B, C, nq, nblk, first_raw, skip_head, R, T, phone, cvo, fast, d_overflow, d_q, cand_d, cand_i);
         snprintf(g_last_kernel, sizeof g_last_kernel, fast ? "knn_gemm" : "knn_exhaustive");      // (behind add_conv1d, which notes the GEMM's own family)
@@ -168,10 +176,11 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
 static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int nblk, int first_raw, uint32_t skip_head, uint32_t R, int T, const T1 &phone, const T1 &cvo,
                              bool fast, int *d_overflow, float *d_q, float *cand_d, int *cand_i)
 {
+        const int K = pl.knn_k;
         if (!d_q) {
             d_q = pl.arena.floats((size_t)B * nq * C);
-            cand_d = pl.arena.floats((size_t)B * nq * nblk * KNN_K);
-            cand_i = (int *)pl.arena.alloc((size_t)B * nq * nblk * KNN_K * sizeof(int));
+            cand_d = pl.arena.floats((size_t)B * nq * nblk * K);
+            cand_i = (int *)pl.arena.alloc((size_t)B * nq * nblk * K * sizeof(int));
             dim3 grid((nq * C + 255) / 256, B);
             pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(knn_queries_kernel, grid, dim3(256), 0, s, cvo.p, cvo.ld, cvo.bs, C, first_raw, nq, d_q); });
         }
@@ -180,13 +189,14 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
             KnnP kp{}; kp.indexT = e->d_indexT; kp.index = e->d_index; kp.n = (int)e->index_n; kp.dim = C; kp.nblk = nblk;
             kp.v_stride = e->d_indexT ? 1 : C; kp.d_stride = e->d_indexT ? (long long)e->index_n : 1;
             // query sub-range: pointers offset so that [B][nq] strides stay those of the full arrays
-            kp.q = d_q + (size_t)q0 * C; kp.nq = qn; kp.cand_d = cand_d + (size_t)q0 * nblk * KNN_K; kp.cand_i = cand_i + (size_t)q0 * nblk * KNN_K;
+            kp.q = d_q + (size_t)q0 * C; kp.nq = qn; kp.cand_d = cand_d + (size_t)q0 * nblk * K; kp.cand_i = cand_i + (size_t)q0 * nblk * K;
             kp.overflow = fast ? d_overflow : nullptr;
             const int nq_total = nq;
             dim3 grid(nblk, B);
+            const auto scan_kernel = KNN_KERNEL_FOR(knn_scan, K);
             pl.ops.push_back([=](hipStream_t s) {
-                KnnP k2 = kp; k2.q_bs = (long long)nq_total * C; k2.cand_bs = (long long)nq_total * nblk * KNN_K;
-                hipLaunchKernelGGL(knn_scan_kernel, grid, dim3(256), 0, s, k2);
+                KnnP k2 = kp; k2.q_bs = (long long)nq_total * C; k2.cand_bs = (long long)nq_total * nblk * K;
+                hipLaunchKernelGGL(scan_kernel, grid, dim3(256), 0, s, k2);
             });
         }
         KnnBlendP bp{}; bp.cand_d = cand_d; bp.cand_i = cand_i; bp.nblk = nblk; bp.nq = nq; bp.index = e->d_index; bp.dim = C; bp.q = d_q;
@@ -194,7 +204,8 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
         bp.phone = phone.p; bp.ph_cs = phone.ld; bp.ph_bs = phone.bs; bp.out_idx = pl.d_knn_idx; bp.out_dist = pl.d_knn_dist;
         bp.overflow = fast ? d_overflow : nullptr;
         dim3 grid(nq, B);
-        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(knn_merge_blend_kernel, grid, dim3(256), 0, s, bp); });
+        const auto merge_kernel = KNN_KERNEL_FOR(knn_merge_blend, K);
+        pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(merge_kernel, grid, dim3(256), 0, s, bp); });
 }
 
 // // Everything the retrieval kernels need besides the row-major matrix, built ON THE DEVICE from the copy that is already in HBM
@@ -348,9 +359,12 @@ void ensure_index_transposed(rvc_engine *e)
 void retrieval_kernel_attrs()
 {
     HIPCHK(hipFuncSetAttribute((const void *)knn_select_blend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));   // + ~5 KB static
+    HIPCHK(hipFuncSetAttribute((const void *)knn_select_blend_k8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)knn_scan_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)knn_scan_select_k8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));   // + ~5 KB static
     HIPCHK(hipFuncSetAttribute((const void *)ivf_coarse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));         // + 16 KB static
     HIPCHK(hipFuncSetAttribute((const void *)ivf_scan_blend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));     // + ~2 KB static
+    HIPCHK(hipFuncSetAttribute((const void *)ivf_scan_blend_k8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
 }
 
 }  // namespace rvc
@@ -361,7 +375,7 @@ extern "C" {
 rvc_status rvc_load_index(rvc_engine *e, const float *vectors, size_t n, size_t dim)
 {
     return guarded(e, [&]() {
-        if (n < KNN_K || dim < 1) throw ShapeError("index needs at least 4 vectors");
+        if (n < (size_t)e->index_k || dim < 1) throw ShapeError("index needs at least " + std::to_string(e->index_k) + " vectors");
         HIPCHK(hipDeviceSynchronize());
         if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
         HIPCHK(hipMalloc(&e->d_index, n * dim * sizeof(float)));
@@ -377,7 +391,7 @@ rvc_status rvc_load_index(rvc_engine *e, const float *vectors, size_t n, size_t 
 rvc_status rvc_load_index_device(rvc_engine *e, const void *d_vectors, size_t n, size_t dim)
 {
     return guarded(e, [&]() {
-        if (n < KNN_K || dim < 1) throw ShapeError("index needs at least 4 vectors");
+        if (n < (size_t)e->index_k || dim < 1) throw ShapeError("index needs at least " + std::to_string(e->index_k) + " vectors");
         HIPCHK(hipDeviceSynchronize());
         if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
         HIPCHK(hipMalloc(&e->d_index, n * dim * sizeof(float)));
@@ -408,8 +422,8 @@ rvc_status rvc_get_knn(rvc_engine *e, int32_t *idx, float *dist, size_t cap_rows
         const size_t r = pl->R * std::min((size_t)pl->B, cap_rows / pl->R);
         if (rows) *rows = r;
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(idx, pl->d_knn_idx, r * KNN_K * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(dist, pl->d_knn_dist, r * KNN_K * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(idx, pl->d_knn_idx, r * pl->knn_k * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist, pl->d_knn_dist, r * pl->knn_k * sizeof(float), hipMemcpyDeviceToHost));
         return RVC_OK;
     });
 }
@@ -565,6 +579,20 @@ rvc_status rvc_set_index_nprobe(rvc_engine *e, int nprobe)
 }
 
 int rvc_index_nprobe(rvc_engine *e) { return e ? e->index_nprobe : 0; }
+
+// Neighbours per query: 4 (the default) or upstream's 8.  A preference of the caller: it outlives index loads, broadcasts and IVF structures, and the plans
+// keyed on it stay in the cache (changing it back finds them).
+rvc_status rvc_set_index_k(rvc_engine *e, int k)
+{
+    return guarded(e, [&]() {
+        if (k != KNN_K && k != KNN_KMAX) throw ShapeError("k must be 4 or 8");
+        if (e->d_index && e->index_n < (size_t)k) throw ShapeError("the loaded index has fewer than " + std::to_string(k) + " vectors");
+        e->index_k = k;
+        return RVC_OK;
+    });
+}
+
+int rvc_index_k(rvc_engine *e) { return e ? e->index_k : KNN_K; }
 
 rvc_status rvc_index_ivf_info(rvc_engine *e, size_t *nlist, size_t *longest_list, size_t *empty_lists)
 {

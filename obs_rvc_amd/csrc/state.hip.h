@@ -33,7 +33,8 @@ struct StreamState {        // one per stream
     // 0.5 = off.  A zero-filled state therefore means FULL protection: whoever builds a state by hand sets the word (debug.hip does)
     float protect;
 };
-#define KNN_K 4                            // neighbours per retrieval query (knn.hip.h; rccl_bcast.hip.h refuses a smaller index)
+#define KNN_K 4                            // neighbours per retrieval query: the default and the minimum (knn.hip.h kernels are template <int K>) ...
+#define KNN_KMAX 8                         // ... and upstream's eight (rvc_set_index_k; an index holds at least k rows)
 constexpr double PROTECT_OFF = 0.5;       // the setting lives in [0, PROTECT_OFF]; PROTECT_OFF and above = no protection (upstream: `protect < 0.5` enables it)
 
 // status bits of a stream (several kernels of one chunk may report; a plain store would lose the earlier report)

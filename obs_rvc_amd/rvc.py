@@ -111,7 +111,7 @@ class RvcInfer:
         return out[: n.value].copy()
 
     # -- extensions ---------------------------------------------------------------------
-    def load_index(self, vectors, nprobe=None, train=False):
+    def load_index(self, vectors, nprobe=None, train=False, k=None):
         """`vectors`: an (n, dim) float32 array, or the path of a Faiss `.index` file (IndexFlat / IndexIVFFlat: the stored
         vectors are reconstructed in id order, obs_rvc_amd.faiss_index) or of a `.npy` matrix (upstream's total_fea.npy).
         `nprobe`: None = the flat search over every row; an integer >= 1 = keep an IndexIVFFlat file's structure and search it as upstream
@@ -120,7 +120,15 @@ class RvcInfer:
         before anything is loaded: the engine keeps the index it had.
         `train`: True, or a dict of train_index_ivf's arguments (nlist, iters, init_rows, seed): with `nprobe` given, a source without a structure is trained
         on the device after loading (k-means, rvc_train_index_ivf) instead of refused; "file" then means 1, upstream's stored value.  A file's own structure is
-        kept as it is.  False (the default): everything above."""
+        kept as it is.  False (the default): everything above.
+        `k`: neighbours blended per query.  None leaves the engine's value (4 unless set_index_k changed it); 4 or 8; "upstream" = 8, what upstream's
+        pipelines search with.  Set before the load, so an index of fewer than k rows is refused and the engine keeps the index it had (and its k)."""
+        if k is not None:
+            if isinstance(k, str) and k != "upstream":
+                raise ValueError('k is 4, 8 or "upstream"')
+            k = 8 if k == "upstream" else int(k)
+            if k not in (4, 8):
+                raise RvcInferError(5, "k must be 4 or 8")
         centroids = assign = None
         stored = 0
         if isinstance(vectors, (str, os.PathLike)):
@@ -146,8 +154,14 @@ class RvcInfer:
             if not 0 <= nprobe <= 64:
                 raise RvcInferError(5, "nprobe must be in [0, 64]")
         v, vp = _f32(vectors)
+        if k is not None and v.shape[0] < k:
+            raise RvcInferError(5, "index needs at least %d vectors" % k)
+        if k is not None and k < self.index_k():
+            self.set_index_k(k)          # (lowering never fails; raising waits for the new index, which has the rows for it)
         self._chk(self._L.rvc_load_index(self._h, vp, v.shape[0], v.shape[1]))
         self._index_shape = (int(v.shape[0]), int(v.shape[1]))
+        if k is not None:
+            self.set_index_k(k)
         if nprobe is not None:
             if centroids is not None:
                 self.set_index_ivf(centroids, assign)
@@ -167,6 +181,13 @@ class RvcInfer:
 
     def index_nprobe(self) -> int:
         return int(self._L.rvc_index_nprobe(self._h))
+
+    def set_index_k(self, k: int):
+        """rvc_set_index_k: neighbours blended per query, 4 (the default) or 8 (upstream's).  Engine-wide; kept across index loads."""
+        self._chk(self._L.rvc_set_index_k(self._h, int(k)))
+
+    def index_k(self) -> int:
+        return int(self._L.rvc_index_k(self._h))
 
     def index_ivf_info(self):
         """(nlist, rows of the longest list, empty lists) of the attached IVF structure"""
@@ -272,13 +293,16 @@ class RvcInfer:
         self._L.rvc_set_index_rate(self._h, float(rate))
 
     def knn(self, rows_cap: int = 4096):
-        """hits of the last infer: (rows, 4) indices and squared distances; rows = return_length per stream, stream-major, for as many streams
-        of a batched call as rows_cap holds whole"""
-        idx = np.empty((rows_cap, 4), np.int32)
-        dist = np.empty((rows_cap, 4), np.float32)
+        """hits of the last infer: (rows, k) indices and squared distances, k = index_k(); rows = return_length per stream, stream-major, for as many
+        streams of a batched call as rows_cap holds whole"""
+        k = self.index_k()       # (the last plan was built with it: the setting is part of a plan's identity)
+        idx = np.empty((rows_cap, k), np.int32)
+        dist = np.empty((rows_cap, k), np.float32)
         rows = C.c_size_t()
         self._chk(self._L.rvc_get_knn(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(_FP), rows_cap, C.byref(rows)))
         return idx[: rows.value].copy(), dist[: rows.value].copy()
+
+    get_knn = knn
 
     def set_noise_seed(self, seed: int, stream_id: int = 0):
         self._L.rvc_set_noise_seed(self._h, int(seed), int(stream_id))
