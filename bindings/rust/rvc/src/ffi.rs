@@ -81,6 +81,14 @@ extern "C" {
     pub fn rvc_train_index_ivf(e: *mut RvcEngine, nlist: usize, iters: c_int, init_rows: *const i32, seed: u32) -> c_int;
     pub fn rvc_index_ivf_train_info(e: *mut RvcEngine, iters_run: *mut c_int, moved_last: *mut usize, objective: *mut f64, cap: usize, n_obj: *mut usize, ms: *mut f64) -> c_int;
     pub fn rvc_get_index_ivf(e: *mut RvcEngine, centroids: *mut c_float, cap_centroid_floats: usize, assign: *mut i32, cap_rows: usize) -> c_int;
+    // index builder: ContentVec frames of a voice's recordings into a row store on the device (window 0 = 48 000 samples, capacity_hint 0 = 4096 rows),
+    // then installed as the engine's index (max_rows = reduce_to = 0: above 200 000 rows, 10 000 k-means centres)
+    pub fn rvc_index_build_begin(e: *mut RvcEngine, window: usize, capacity_hint: usize) -> c_int;
+    pub fn rvc_index_build_add(e: *mut RvcEngine, pcm16k: *const c_float, n: usize, rows_added: *mut usize) -> c_int;
+    pub fn rvc_index_build_add_device(e: *mut RvcEngine, d_pcm16k: *const c_void, n: usize, rows_added: *mut usize) -> c_int;
+    pub fn rvc_index_build_info(e: *mut RvcEngine, rows: *mut usize, capacity: *mut usize, windows: *mut usize, dropped_nonfinite: *mut usize, ms: *mut f64) -> c_int;
+    pub fn rvc_index_build_finish(e: *mut RvcEngine, max_rows: usize, reduce_to: usize, iters: c_int, seed: u32) -> c_int;
+    pub fn rvc_index_build_abort(e: *mut RvcEngine);
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 

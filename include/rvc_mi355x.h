@@ -130,6 +130,32 @@ rvc_status rvc_train_index_ivf(rvc_engine *e, size_t nlist, int iters, const int
 rvc_status rvc_index_ivf_train_info(rvc_engine *e, int *iters_run, size_t *moved_last, double *objective, size_t cap, size_t *n_obj, double ms[3]);
 /* read the attached structure back, trained or set (export, tests): RVC_SHAPE when none is attached or a capacity is short */
 rvc_status rvc_get_index_ivf(rvc_engine *e, float *centroids, size_t cap_centroid_floats, int32_t *assign, size_t cap_rows);
+/* Build a voice's index from its recordings on the device: upstream's "train feature index" with this engine's own ContentVec, so that
+   the rows and the queries that will search them come from the same arithmetic.  begin opens a build, add appends the ContentVec frames of one recording to a
+   row store in HBM, finish installs the store as the engine's index; the rows never visit the host.
+   begin: needs ContentVec (RVC_CONTENTVEC_NOT_LOADED).  window = samples at 16 kHz per ContentVec run, 0 = 48 000 (3 s); the run is rvc_hubert's one-stream plan
+   of that length whatever rvc_set_streams says, so the rows are rvc_hubert's rows bit for bit; a window ContentVec yields no frame for: RVC_SHAPE.
+   capacity_hint = rows the store [capacity][dim] (fp32, one device allocation) starts with, 0 = 4096; an append that would overflow it grows it to twice its
+   size, or to the needed size if that is larger, with a device-to-device copy.  A second begin while a build is open: RVC_SHAPE.
+   add / add_device (host / device samples): the recording is cut into consecutive windows, no overlap, no padding; every full window contributes its T frames
+   as T rows, the tail runs at its own length and is dropped silently when it is shorter than ContentVec's receptive field (where rvc_hubert says "input too
+   short").  The rows of one add are exactly the frames rvc_hubert returns for each of these slices, in time order; nothing carries from one add to the next.
+   A row that holds a NaN or an Inf is not stored but counted (dropped_nonfinite); *rows_added excludes such rows.  One synchronisation per add.  Without begin:
+   RVC_SHAPE.  The engine's loaded index keeps serving rvc_infer while a build is open: nothing before finish touches it.
+   finish: rows > max_rows: Lloyd's k-means with reduce_to centres over the store -- the trainer of rvc_train_index_ivf (same seeded sample, assign and update
+   steps, early stop; iters 0..100), deterministic bit for bit -- and the centres in centre order become the rows.  max_rows = 0 and reduce_to = 0 select
+   upstream's rule: above 200 000 rows, 10 000 centres.  The result is installed as rvc_load_index_device installs a matrix (auxiliary layouts rebuilt, plans
+   cleared, any IVF structure dropped, nprobe back to 0) and the build is closed; no IVF structure is trained (rvc_train_index_ivf does that).  RVC_SHAPE, the
+   build staying open and the engine keeping its index: fewer rows than rvc_index_k(e) to install, reduce_to above the rows held or above 65536, iters out of
+   range.
+   abort frees the store; rvc_destroy aborts an open build.  info: rows stored, the store's capacity, ContentVec runs so far, rows dropped, device milliseconds
+   {ContentVec runs, appends, reduction}; RVC_SHAPE when no build is open. */
+rvc_status rvc_index_build_begin(rvc_engine *e, size_t window, size_t capacity_hint);
+rvc_status rvc_index_build_add(rvc_engine *e, const float *pcm16k, size_t n, size_t *rows_added);
+rvc_status rvc_index_build_add_device(rvc_engine *e, const void *d_pcm16k, size_t n, size_t *rows_added);
+rvc_status rvc_index_build_info(rvc_engine *e, size_t *rows, size_t *capacity, size_t *windows, size_t *dropped_nonfinite, double ms[3]);
+rvc_status rvc_index_build_finish(rvc_engine *e, size_t max_rows, size_t reduce_to, int iters, uint32_t seed);
+void       rvc_index_build_abort(rvc_engine *e);
 /* the synthesizer's two noise inputs are explicit counter-based (Philox4x32-10) streams */
 void rvc_set_noise_seed(rvc_engine *e, uint32_t seed, uint32_t stream_id);
 void rvc_reset_state(rvc_engine *e);     /* zero the 1024-entry pitch cache and the chunk counter */

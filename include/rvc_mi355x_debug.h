@@ -179,6 +179,13 @@ int rvc_debug_index_layouts(rvc_engine *e);
  * without an index or with nlist outside [1, min(n, 65536)].  0 = done, else an rvc_status. */
 int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist, const int32_t *prev_assign_or_null, int32_t *assign_out, float *dist_out,
                           float *centroids_out, double *objective_out, long long *moved_out);
+/* one append of the index builder (obs_rvc_amd/csrc/index_build.hip.h) on a store of its own: cv [C][ld] is a window's ContentVec output
+ * in channel-major layout with T columns used; the store starts with `capacity` rows of room and `cursor` rows in it (head_rows [cursor][C], may be null when
+ * cursor is 0).  The aid reserves room for cursor + T rows as rvc_index_build_add does (so a capacity below that grows the store), runs index_append_kernel and
+ * index_compact_kernel, and returns the store's rows [*rows_out][C] in store_out (cap_rows >= cursor + T), the row count and the rows dropped for a NaN or an
+ * Inf.  The engine's own build, if one is open, is not touched.  0 = done, else an rvc_status. */
+int rvc_debug_index_append(rvc_engine *e, const float *cv, int C, int T, int ld, size_t cursor, size_t capacity, const float *head_rows, float *store_out,
+                           size_t cap_rows, size_t *rows_out, size_t *dropped_out);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);

@@ -37,6 +37,7 @@ SYMBOLS = [
     "rvc_set_index_ivf", "rvc_set_index_nprobe", "rvc_index_nprobe", "rvc_index_ivf_info",
     "rvc_train_index_ivf", "rvc_index_ivf_train_info", "rvc_get_index_ivf",
     "rvc_set_index_k", "rvc_index_k",
+    "rvc_index_build_begin", "rvc_index_build_add", "rvc_index_build_add_device", "rvc_index_build_info", "rvc_index_build_finish", "rvc_index_build_abort",
 ]
 
 
@@ -238,6 +239,14 @@ def lib():
         L.rvc_train_index_ivf.argtypes = [vp, sz, C.c_int, C.POINTER(i32), u32]
         L.rvc_index_ivf_train_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(C.c_double), sz, C.POINTER(sz), C.POINTER(C.c_double)]
         L.rvc_get_index_ivf.argtypes = [vp, fp, sz, C.POINTER(i32), sz]
+    if hasattr(L, "rvc_index_build_begin") or not override:
+        L.rvc_index_build_begin.argtypes = [vp, sz, sz]
+        L.rvc_index_build_add.argtypes = [vp, fp, sz, C.POINTER(sz)]
+        L.rvc_index_build_add_device.argtypes = [vp, vp, sz, C.POINTER(sz)]
+        L.rvc_index_build_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_double)]
+        L.rvc_index_build_finish.argtypes = [vp, sz, sz, C.c_int, u32]
+        L.rvc_index_build_abort.argtypes = [vp]
+        L.rvc_index_build_abort.restype = None
     L.rvc_set_noise_seed.argtypes = [vp, u32, u32]
     L.rvc_set_noise_seed.restype = None
     L.rvc_reset_state.argtypes = [vp]

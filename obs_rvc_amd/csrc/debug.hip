@@ -825,6 +825,37 @@ int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist
     });
 }
 
+// test aid: one append of the index builder (retrieval.hip index_build_reserve / index_build_append; tests/test_gpu_index_build.py) on a store of its own
+int rvc_debug_index_append(rvc_engine *e, const float *cv, int C, int T, int ld, size_t cursor, size_t capacity, const float *head_rows, float *store_out,
+                           size_t cap_rows, size_t *rows_out, size_t *dropped_out)
+{
+    return (int)guarded(e, [&]() {
+        if (!cv || !store_out || !rows_out || !dropped_out || (cursor && !head_rows)) throw ShapeError("index append: null argument");
+        if (C < 1 || T < 1 || ld < T || capacity < 1 || cursor > capacity) throw ShapeError("index append: needs C >= 1, 1 <= T <= ld, cursor <= capacity, capacity >= 1");
+        if (cap_rows < cursor + (size_t)T) throw ShapeError("index append: store_out holds fewer than cursor + T rows");
+        HIPCHK(hipDeviceSynchronize());
+        IndexBuild b;
+        b.alloc((size_t)C, capacity);
+        float *d_cv = nullptr;
+        HIPCHK(hipMalloc(&d_cv, (size_t)C * ld * sizeof(float)));
+        struct Free { float *p; ~Free() { (void)hipFree(p); } } free_cv{d_cv};
+        HIPCHK(hipMemcpy(d_cv, cv, (size_t)C * ld * sizeof(float), hipMemcpyHostToDevice));
+        if (cursor) HIPCHK(hipMemcpy(b.store, head_rows, cursor * C * sizeof(float), hipMemcpyHostToDevice));
+        const int cnt0[2] = {(int)cursor, 0};
+        HIPCHK(hipMemcpy(b.d_cnt, cnt0, sizeof cnt0, hipMemcpyHostToDevice));
+        index_build_reserve(e, b, cursor, cursor + (size_t)T);
+        index_build_append(e, b, d_cv, C, T, ld);
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipGetLastError());
+        int cnt[2] = {0, 0};
+        HIPCHK(hipMemcpy(cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+        if (cnt[0] < (int)cursor || (size_t)cnt[0] > cursor + (size_t)T) throw std::runtime_error("index append: the device-side row count is out of range");
+        HIPCHK(hipMemcpy(store_out, b.store, (size_t)cnt[0] * C * sizeof(float), hipMemcpyDeviceToHost));
+        *rows_out = (size_t)cnt[0]; *dropped_out = (size_t)cnt[1];
+        return RVC_OK;
+    });
+}
+
 // the kernel family of the most recently queued implicit-GEMM launch (the first word of its description), the variant of the last op or the form of the
 // last ConvBlockRes: tests assert which path they exercised
 const char *rvc_debug_last_kernel(void)

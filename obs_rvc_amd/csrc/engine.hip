@@ -392,6 +392,15 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     return e->plans.back().get();
 }
 
+static void run_plan(rvc_engine *e, Plan &pl);
+// what the index builder (retrieval.hip) needs of the planner: rvc_hubert's plan whatever the stream count, and one run of it
+Plan *hubert_plan(rvc_engine *e, size_t L)
+{
+    struct One { rvc_engine *e; int n; explicit One(rvc_engine *e_) : e(e_), n(e_->n_streams) { e->n_streams = 1; } ~One() { e->n_streams = n; } } one(e);
+    return get_plan(e, 1, L, 0, 0, 0);
+}
+void run_hubert_plan(rvc_engine *e, Plan &pl) { run_plan(e, pl); }
+
 static void issue_ops(rvc_engine *e, Plan &pl, bool capturing)
 {
     // fork/join through events; under stream capture the auxiliary streams become parallel branches of the hipGraph
@@ -733,6 +742,7 @@ void rvc_destroy(rvc_engine *e)
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
     e->plans.clear();
+    index_build_abort(e);
     e->cv.reset(); e->rm.reset(); e->sy.reset();
     wfree(e->d_window); wfree(e->d_twiddle); wfree(e->d_basis);      // (upload_f: slab memory)
     if (e->d_band) (void)hipFree(e->d_band);

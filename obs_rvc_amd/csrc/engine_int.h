@@ -443,7 +443,7 @@ struct ModelSY {
 
 }  // namespace rvc
 
-namespace rvc { struct StreamSet; }
+namespace rvc { struct StreamSet; struct IndexBuild; }
 using namespace rvc;
 
 struct rvc_engine {
@@ -472,6 +472,7 @@ struct rvc_engine {
     float index_prep_ms = 0.f;                                  // device-side repack + norms of the last index load
     // the last k-means training of an IVF structure (rvc_train_index_ivf; kmeans.hip.h): what rvc_index_ivf_train_info reports
     bool km_valid = false; int km_iters_run = 0; size_t km_moved_last = 0; std::vector<double> km_obj; double km_ms[3] = {0, 0, 0};
+    rvc::IndexBuild *ib = nullptr;                              // an open index build (rvc_index_build_begin .. _finish / _abort; retrieval.hip); never touches d_index before finish
     double bcast_ms[3] = {0, 0, 0}; int bcast_ranks = 0;         // last rvc_index_broadcast: communicator set-up, broadcast, repack (ms); ranks the communicator reports
     // streams
     int n_streams = 1;
@@ -584,9 +585,34 @@ struct KmeansWork {
     double *part = nullptr, *obj = nullptr; long long *moved = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr}; double ms_assign = 0, ms_update = 0;
     KmeansWork() = default; KmeansWork(const KmeansWork &) = delete; KmeansWork &operator=(const KmeansWork &) = delete;
-    void alloc(size_t n, size_t dim, size_t nlist);
+    const float *rows = nullptr;          // the matrix trained on; null = the engine's loaded index
+    void alloc(size_t n, size_t dim, size_t nlist, const float *rows = nullptr);
     ~KmeansWork();
 };
 void kmeans_assign_step(rvc_engine *e, KmeansWork &w, const int *prev, int cur, double *objective, long long *moved);
 void kmeans_update_step(rvc_engine *e, KmeansWork &w, int cur);
+// The index builder (retrieval.hip, index_build.hip.h): the row store of one build and its device-side counters.  index_build_reserve
+// grows the store to hold `need` rows (twice its size, or `need` if that is larger; the old allocation is retired until the stream has been synchronised);
+// index_build_append queues index_append_kernel + index_compact_kernel for one window's ContentVec output cv [C][ld], T columns used, on the engine's stream.
+// rvc_index_build_add runs them per window and so does rvc_debug_index_append (debug.hip).
+struct IndexBuild {
+    size_t window = 0, dim = 0, capacity = 0;
+    size_t rows = 0, windows = 0, dropped = 0;      // as of the last add (the device counters are read once per add)
+    float *store = nullptr;                         // [capacity][dim] fp32
+    int *d_cnt = nullptr;                           // {rows, dropped} on the device
+    int *d_bad = nullptr; size_t bad_cap = 0;       // one word per frame of a window, zero between windows
+    std::vector<void *> retired;                    // allocations the store outgrew, freed behind the add's synchronisation
+    std::vector<hipEvent_t> ev;                     // timing of an add's run w: 3 w = before its ContentVec run, 3 w + 1 = behind it, 3 w + 2 = behind its append
+    double ms[3] = {0, 0, 0};                       // device milliseconds: ContentVec runs, appends, the reduction
+    IndexBuild() = default; IndexBuild(const IndexBuild &) = delete; IndexBuild &operator=(const IndexBuild &) = delete;
+    void alloc(size_t dim, size_t capacity);
+    ~IndexBuild();
+};
+void index_build_reserve(rvc_engine *e, IndexBuild &b, size_t upper, size_t need);
+void index_build_append(rvc_engine *e, IndexBuild &b, const float *cv, int C, int T, int ld);
+void index_build_abort(rvc_engine *e);
+// engine.hip: the one-stream ContentVec-only plan of length L -- rvc_hubert's plan, get_plan(e, 1, L, 0, 0, 0) -- whatever rvc_set_streams says, and one run of
+// it on the engine's stream over the samples already in pl.d_in
+Plan *hubert_plan(rvc_engine *e, size_t L);
+void run_hubert_plan(rvc_engine *e, Plan &pl);
 }  // namespace rvc

@@ -4,6 +4,7 @@
 #include "knn.hip.h"
 #include "ivf.hip.h"
 #include "kmeans.hip.h"
+#include "index_build.hip.h"
 
 namespace rvc {
 
@@ -246,9 +247,9 @@ static void ivf_note_lists(rvc_engine *e, size_t n, size_t nlist)
 }
 
 // ---- k-means training (kmeans.hip.h) ----
-void KmeansWork::alloc(size_t n_, size_t dim_, size_t nlist_)
+void KmeansWork::alloc(size_t n_, size_t dim_, size_t nlist_, const float *rows_)
 {
-    n = n_; dim = dim_; nlist = nlist_;
+    n = n_; dim = dim_; nlist = nlist_; rows = rows_;
     nwg = (int)((n + KM_TR - 1) / KM_TR); nparts = (int)((n + KM_RB - 1) / KM_RB);
     HIPCHK(hipMalloc(&cent, nlist * dim * sizeof(float)));
     HIPCHK(hipMalloc(&assign[0], n * sizeof(int))); HIPCHK(hipMalloc(&assign[1], n * sizeof(int)));
@@ -268,7 +269,7 @@ KmeansWork::~KmeansWork()
 // one assign step against w.cent into w.assign[cur] / w.dist; prev: the assignment `moved` is counted against (null: every row counts).  Synchronises.
 void kmeans_assign_step(rvc_engine *e, KmeansWork &w, const int *prev, int cur, double *objective, long long *moved)
 {
-    KmeansAssignP ap{}; ap.index = e->d_index; ap.n = (int)w.n; ap.dim = (int)w.dim; ap.cent = w.cent; ap.nlist = (int)w.nlist;
+    KmeansAssignP ap{}; ap.index = w.rows ? w.rows : e->d_index; ap.n = (int)w.n; ap.dim = (int)w.dim; ap.cent = w.cent; ap.nlist = (int)w.nlist;
     ap.prev = prev; ap.assign = w.assign[cur]; ap.dist = w.dist; ap.moved_wg = w.moved_wg;
     HIPCHK(hipEventRecord(w.ev[0], e->stream));
     hipLaunchKernelGGL(kmeans_assign_kernel, dim3((unsigned)w.nwg), dim3(256), 0, e->stream, ap);
@@ -287,7 +288,7 @@ void kmeans_update_step(rvc_engine *e, KmeansWork &w, int cur)
 {
     HIPCHK(hipEventRecord(w.ev[0], e->stream));
     ivf_build_csr(e, w.assign[cur], w.n, w.nlist, w.counts, w.offs, w.perm);
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, e->d_index, (int)w.dim, w.offs, w.perm, w.cent);
+    hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, w.rows ? w.rows : e->d_index, (int)w.dim, w.offs, w.perm, w.cent);
     HIPCHK(hipEventRecord(w.ev[1], e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
@@ -315,6 +316,26 @@ static std::vector<int32_t> kmeans_seeded_rows(size_t n, size_t nlist, uint32_t 
     for (size_t j = 0; j < nlist; j++) rows[j] = (int32_t)(uint32_t)key[j];
     std::sort(rows.begin(), rows.end());
     return rows;
+}
+
+// Lloyd's iterations of one training over w's matrix: c_j = row init_rows[j], an assign step, then up to `iters` update steps each followed
+// by an assign step, stopping behind an assign step that moved no row.  d_rows: device scratch of nlist ints.  -> the assignment buffer the last step wrote.
+// rvc_train_index_ivf runs it over the loaded index, rvc_index_build_finish over the row store of a build.
+static int kmeans_lloyd(rvc_engine *e, KmeansWork &w, const std::vector<int32_t> &init_rows, int *d_rows, int iters, std::vector<double> &obj, long long *moved, int *run)
+{
+    HIPCHK(hipMemcpyAsync(d_rows, init_rows.data(), w.nlist * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(kmeans_gather_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, w.rows ? w.rows : e->d_index, (int)w.dim, d_rows, w.cent);
+    obj.assign(1, 0.0);
+    int cur = 0;
+    *run = 0; *moved = 0;
+    kmeans_assign_step(e, w, nullptr, cur, &obj[0], moved);
+    while (*run < iters && *moved != 0) {
+        kmeans_update_step(e, w, cur);
+        double j = 0.0;
+        kmeans_assign_step(e, w, w.assign[cur], cur ^ 1, &j, moved);
+        obj.push_back(j); cur ^= 1; (*run)++;
+    }
+    return cur;
 }
 
 void build_index_aux(rvc_engine *e)
@@ -354,6 +375,118 @@ void ensure_index_transposed(rvc_engine *e)
     hipLaunchKernelGGL(knn_transpose_kernel, grid, dim3(256), 0, e->stream, e->d_index, (long long)e->index_n, (int)e->index_dim, e->d_indexT);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
+}
+
+// ---- the index builder (index_build.hip.h) ----
+void IndexBuild::alloc(size_t dim_, size_t capacity_)
+{
+    dim = dim_; capacity = capacity_;
+    HIPCHK(hipMalloc(&store, capacity * dim * sizeof(float)));
+    HIPCHK(hipMalloc(&d_cnt, 2 * sizeof(int)));
+    HIPCHK(hipMemset(d_cnt, 0, 2 * sizeof(int)));
+}
+IndexBuild::~IndexBuild()
+{
+    for (void *p : retired) (void)hipFree(p);
+    if (store) (void)hipFree(store);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (d_bad) (void)hipFree(d_bad);
+    for (hipEvent_t v : ev) (void)hipEventDestroy(v);
+}
+// room for `need` rows; `upper` = an upper bound of the rows the store holds (the device's own count is not known between the windows of an add)
+void index_build_reserve(rvc_engine *e, IndexBuild &b, size_t upper, size_t need)
+{
+    if (need > (size_t)0x7fffffff) throw ShapeError("index build: more than 2^31 - 1 rows");
+    if (need <= b.capacity) return;
+    const size_t cap = std::max(2 * b.capacity, need);
+    float *grown = nullptr;
+    HIPCHK(hipMalloc(&grown, cap * b.dim * sizeof(float)));
+    if (upper) {
+        const hipError_t rc = hipMemcpyAsync(grown, b.store, upper * b.dim * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
+        if (rc != hipSuccess) { (void)hipFree(grown); HIPCHK(rc); }
+    }
+    b.retired.push_back(b.store);      // (the copy above, and appends queued before it, still read it)
+    b.store = grown; b.capacity = cap;
+}
+void index_build_append(rvc_engine *e, IndexBuild &b, const float *cv, int C, int T, int ld)
+{
+    if ((size_t)C != b.dim || T < 1 || ld < T) throw ShapeError("index build: the window's feature matrix does not match the store");
+    if ((size_t)T > b.bad_cap) {
+        if (b.d_bad) b.retired.push_back(b.d_bad);
+        b.d_bad = nullptr; b.bad_cap = 0;
+        const size_t cap = std::max((size_t)T, (size_t)1024);
+        HIPCHK(hipMalloc(&b.d_bad, cap * sizeof(int)));
+        b.bad_cap = cap;
+        HIPCHK(hipMemsetAsync(b.d_bad, 0, cap * sizeof(int), e->stream));
+    }
+    IndexAppendP p{}; p.cv = cv; p.C = C; p.T = T; p.ld = ld; p.rows = b.store; p.capacity = (long long)b.capacity; p.cnt = b.d_cnt; p.bad = b.d_bad;
+    dim3 grid((unsigned)((T + IB_TILE - 1) / IB_TILE), (unsigned)((C + IB_TILE - 1) / IB_TILE));
+    hipLaunchKernelGGL(index_append_kernel, grid, dim3(256), 0, e->stream, p);
+    hipLaunchKernelGGL(index_compact_kernel, dim3(1), dim3(256), 0, e->stream, b.store, C, (long long)b.capacity, b.d_bad, T, b.d_cnt);
+}
+void index_build_abort(rvc_engine *e)
+{
+    if (!e->ib) return;
+    (void)hipDeviceSynchronize();
+    delete e->ib;
+    e->ib = nullptr;
+}
+static hipEvent_t ib_event(IndexBuild &b, size_t i)
+{
+    while (b.ev.size() <= i) { hipEvent_t v; HIPCHK(hipEventCreate(&v)); b.ev.push_back(v); }
+    return b.ev[i];
+}
+// One recording: consecutive windows, the tail at its own length when ContentVec yields a frame for it.  Per run: the samples into the plan's input, the plan,
+// the append.  One synchronisation and one read of the device counters at the end.
+static rvc_status index_build_add(rvc_engine *e, const void *pcm, size_t n, bool on_device, size_t *rows_added)
+{
+    if (rows_added) *rows_added = 0;
+    if (!e->ib) throw ShapeError("index build: no build is open (rvc_index_build_begin)");
+    if (!e->cv) { e->err = "index build: ContentVec is not loaded"; return RVC_CONTENTVEC_NOT_LOADED; }
+    if (!pcm && n) throw ShapeError("index build: null recording");
+    IndexBuild &b = *e->ib;
+    size_t upper = b.rows, runs = 0;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    try {
+        for (size_t start = 0; start < n; start += b.window) {
+            const size_t len = std::min(b.window, n - start);
+            const int T = e->cv->out_frames(len);
+            if (T < 1) break;                                    // (the tail, shorter than ContentVec's receptive field: dropped)
+            Plan *pl = hubert_plan(e, len);
+            if ((size_t)pl->C != b.dim || pl->T != T) throw ShapeError("index build: ContentVec changed while the build was open");
+            HIPCHK(hipMemcpyAsync(pl->d_in, (const float *)pcm + start, len * sizeof(float), kind, e->stream));
+            HIPCHK(hipEventRecord(ib_event(b, 3 * runs), e->stream));
+            run_hubert_plan(e, *pl);
+            HIPCHK(hipEventRecord(ib_event(b, 3 * runs + 1), e->stream));
+            index_build_reserve(e, b, upper, upper + (size_t)T);
+            index_build_append(e, b, pl->cv_out.p, pl->C, T, pl->cv_out.ld);
+            HIPCHK(hipEventRecord(ib_event(b, 3 * runs + 2), e->stream));
+            upper += (size_t)T; runs++;
+        }
+    } catch (...) {
+        // what was queued still runs: bring the host's view up to date before the error leaves
+        int cnt[2] = {0, 0};
+        if (hipStreamSynchronize(e->stream) == hipSuccess && hipMemcpy(cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost) == hipSuccess) { b.rows = (size_t)cnt[0]; b.dropped = (size_t)cnt[1]; }
+        for (void *p : b.retired) (void)hipFree(p);
+        b.retired.clear();
+        throw;
+    }
+    int cnt[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    for (void *p : b.retired) (void)hipFree(p);
+    b.retired.clear();
+    for (size_t w = 0; w < runs; w++) {
+        float a = 0.f, c = 0.f;
+        HIPCHK(hipEventElapsedTime(&a, b.ev[3 * w], b.ev[3 * w + 1]));
+        HIPCHK(hipEventElapsedTime(&c, b.ev[3 * w + 1], b.ev[3 * w + 2]));
+        b.ms[0] += a; b.ms[1] += c;
+    }
+    if ((size_t)cnt[0] + (size_t)(cnt[1] - (int)b.dropped) != upper) throw std::runtime_error("index build: the device-side row count does not add up");
+    if (rows_added) *rows_added = (size_t)cnt[0] - b.rows;
+    b.rows = (size_t)cnt[0]; b.dropped = (size_t)cnt[1]; b.windows += runs;
+    return RVC_OK;
 }
 
 void retrieval_kernel_attrs()
@@ -505,18 +638,10 @@ rvc_status rvc_train_index_ivf(rvc_engine *e, size_t nlist, int iters, const int
             hipEvent_t t0, t1; HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1));
             struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evs{t0, t1};
             HIPCHK(hipEventRecord(t0, e->stream));
-            HIPCHK(hipMemcpyAsync(d_rows, rows.data(), nlist * sizeof(int), hipMemcpyHostToDevice, e->stream));
-            hipLaunchKernelGGL(kmeans_gather_kernel, dim3((unsigned)nlist), dim3(256), 0, e->stream, e->d_index, (int)dim, d_rows, w.cent);
-            std::vector<double> obj(1);
+            std::vector<double> obj;
             long long moved = 0;
-            int cur = 0, run = 0;
-            kmeans_assign_step(e, w, nullptr, cur, &obj[0], &moved);
-            while (run < iters && moved != 0) {
-                kmeans_update_step(e, w, cur);
-                double j = 0.0;
-                kmeans_assign_step(e, w, w.assign[cur], cur ^ 1, &j, &moved);
-                obj.push_back(j); cur ^= 1; run++;
-            }
+            int run = 0;
+            const int cur = kmeans_lloyd(e, w, rows, d_rows, iters, obj, &moved, &run);
             // attach: the centroids as they are, the CSR of the last assign step into arrays the engine keeps
             HIPCHK(hipMalloc(&e->d_ivf_offs, (nlist + 1) * sizeof(int)));
             HIPCHK(hipMalloc(&e->d_ivf_perm, n * sizeof(int)));
@@ -603,6 +728,103 @@ rvc_status rvc_index_ivf_info(rvc_engine *e, size_t *nlist, size_t *longest_list
         if (empty_lists) *empty_lists = e->ivf_empty;
         return RVC_OK;
     });
+}
+
+// ---- the index builder: ContentVec frames of a voice's recordings into a row store on the device, then installed as the engine's index ----
+rvc_status rvc_index_build_begin(rvc_engine *e, size_t window, size_t capacity_hint)
+{
+    return guarded(e, [&]() {
+        if (!e->cv) { e->err = "index build: ContentVec is not loaded"; return RVC_CONTENTVEC_NOT_LOADED; }
+        if (e->ib) throw ShapeError("index build: a build is already open (finish or abort it first)");
+        if (window == 0) window = 48000;
+        if (capacity_hint == 0) capacity_hint = 4096;
+        if (capacity_hint > (size_t)0x7fffffff) throw ShapeError("index build: more than 2^31 - 1 rows");
+        Plan *pl = hubert_plan(e, window);                      // ("input too short for ContentVec": RVC_SHAPE)
+        std::unique_ptr<IndexBuild> b(new IndexBuild());
+        b->window = window;
+        b->alloc((size_t)pl->C, capacity_hint);
+        e->ib = b.release();
+        return RVC_OK;
+    });
+}
+
+rvc_status rvc_index_build_add(rvc_engine *e, const float *pcm16k, size_t n, size_t *rows_added)
+{
+    return guarded(e, [&]() { return index_build_add(e, pcm16k, n, false, rows_added); });
+}
+
+rvc_status rvc_index_build_add_device(rvc_engine *e, const void *d_pcm16k, size_t n, size_t *rows_added)
+{
+    return guarded(e, [&]() { return index_build_add(e, d_pcm16k, n, true, rows_added); });
+}
+
+rvc_status rvc_index_build_info(rvc_engine *e, size_t *rows, size_t *capacity, size_t *windows, size_t *dropped_nonfinite, double ms[3])
+{
+    return guarded(e, [&]() {
+        if (!e->ib) throw ShapeError("index build: no build is open (rvc_index_build_begin)");
+        if (rows) *rows = e->ib->rows;
+        if (capacity) *capacity = e->ib->capacity;
+        if (windows) *windows = e->ib->windows;
+        if (dropped_nonfinite) *dropped_nonfinite = e->ib->dropped;
+        if (ms) for (int i = 0; i < 3; i++) ms[i] = e->ib->ms[i];
+        return RVC_OK;
+    });
+}
+
+// Everything that can refuse the call is decided before anything changes: a refused finish leaves the build open and the engine's index in place.
+rvc_status rvc_index_build_finish(rvc_engine *e, size_t max_rows, size_t reduce_to, int iters, uint32_t seed)
+{
+    return guarded(e, [&]() {
+        if (!e->ib) throw ShapeError("index build: no build is open (rvc_index_build_begin)");
+        IndexBuild &b = *e->ib;
+        if (max_rows == 0) max_rows = 200000;                   // upstream's rule: above 200 000 rows ...
+        if (reduce_to == 0) reduce_to = 10000;                  // ... 10 000 k-means centres
+        const size_t rows = b.rows, dim = b.dim;
+        const bool reduce = rows > max_rows;
+        if (reduce && reduce_to > rows) throw ShapeError("index build: reduce_to is above the " + std::to_string(rows) + " rows the build holds");
+        if (reduce && reduce_to > IVF_MAX_NLIST) throw ShapeError("index build: reduce_to must be at most 65536");
+        if (reduce && (iters < 0 || iters > 100)) throw ShapeError("k-means: iters must be in [0, 100]");
+        const size_t n = reduce ? reduce_to : rows;
+        if (n < (size_t)e->index_k) throw ShapeError("index needs at least " + std::to_string(e->index_k) + " vectors (the build would install " + std::to_string(n) + ")");
+        HIPCHK(hipDeviceSynchronize());
+        float *installed = nullptr;
+        if (reduce) {
+            // the trainer of rvc_train_index_ivf on the store's pointer: same seeded sample, same steps, same early stop.  The centroid table is an allocation
+            // of exactly [reduce_to][dim] in centre order: it becomes the index as it is (no copy into the store's head), and the store is freed.
+            const std::vector<int32_t> init = kmeans_seeded_rows(rows, reduce_to, seed);
+            int *d_rows = nullptr;
+            HIPCHK(hipMalloc(&d_rows, reduce_to * sizeof(int)));
+            struct Free { int *p; ~Free() { (void)hipFree(p); } } free_rows{d_rows};
+            KmeansWork w;
+            w.alloc(rows, dim, reduce_to, b.store);
+            std::vector<double> obj; long long moved = 0; int run = 0;
+            (void)kmeans_lloyd(e, w, init, d_rows, iters, obj, &moved, &run);
+            b.ms[2] += w.ms_assign + w.ms_update;
+            installed = w.cent; w.cent = nullptr;
+        } else if (b.capacity - rows > rows / 4) {
+            // the store was grown by doubling: more than a quarter of slack is not worth keeping for the index's life
+            HIPCHK(hipMalloc(&installed, rows * dim * sizeof(float)));
+            const hipError_t rc = hipMemcpy(installed, b.store, rows * dim * sizeof(float), hipMemcpyDeviceToDevice);
+            if (rc != hipSuccess) { (void)hipFree(installed); HIPCHK(rc); }
+        } else {
+            installed = b.store; b.store = nullptr;             // handed over without a copy
+        }
+        // installed as rvc_load_index_device installs a matrix: auxiliary layouts rebuilt, the IVF structure dropped (build_index_aux), plans cleared
+        delete e->ib; e->ib = nullptr;
+        if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
+        e->d_index = installed; e->index_owned = true;
+        e->index_n = n; e->index_dim = dim;
+        build_index_aux(e);
+        e->plans.clear(); e->last_plan = nullptr;
+        return RVC_OK;
+    });
+}
+
+void rvc_index_build_abort(rvc_engine *e)
+{
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    index_build_abort(e);
 }
 
 // chunks whose retrieval was recomputed through the exhaustive launches after a hand-off time-out of the one-launch form (they returned RVC_OK)

@@ -258,6 +258,80 @@ class RvcInfer:
             return
         F.write_ivf_flat_assigned(os.fspath(path), v, cent, assign, nprobe=max(1, self.index_nprobe()))
 
+    # -- index builder (rvc_index_build_*) ---------------------------------
+    def index_build_begin(self, window: int = 0, capacity_hint: int = 0):
+        """rvc_index_build_begin: open a build; window in 16 kHz samples (0 = 48 000), capacity_hint in rows (0 = 4096)."""
+        self._chk(self._L.rvc_index_build_begin(self._h, int(window), int(capacity_hint)))
+
+    def index_build_add(self, pcm16k) -> int:
+        """rvc_index_build_add: the ContentVec frames of one 16 kHz recording as rows of the open build -> rows added"""
+        x, xp = _f32(pcm16k)
+        if x.ndim != 1:
+            raise RvcInferError(5, "index build: a recording is a 1-D array")
+        n = C.c_size_t()
+        self._chk(self._L.rvc_index_build_add(self._h, xp, len(x), C.byref(n)))
+        return int(n.value)
+
+    def index_build_info(self) -> dict:
+        """rvc_index_build_info of the open build -> {rows, capacity, windows, dropped_nonfinite, ms_contentvec, ms_append, ms_reduce}"""
+        r, c, w, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        ms = (C.c_double * 3)()
+        self._chk(self._L.rvc_index_build_info(self._h, C.byref(r), C.byref(c), C.byref(w), C.byref(d), ms))
+        return {"rows": r.value, "capacity": c.value, "windows": w.value, "dropped_nonfinite": d.value,
+                "ms_contentvec": ms[0], "ms_append": ms[1], "ms_reduce": ms[2]}
+
+    def index_build_finish(self, max_rows: int = 0, reduce_to: int = 0, iters: int = 10, seed: int = 0) -> int:
+        """rvc_index_build_finish: install the build as the engine's index (k-means reduction above max_rows; 0, 0 = upstream's 200 000 -> 10 000)
+        -> rows of the installed index"""
+        rows = self.index_build_info()["rows"]
+        self._chk(self._L.rvc_index_build_finish(self._h, int(max_rows), int(reduce_to), int(iters), int(seed) & 0xffffffff))
+        n = (int(reduce_to) or 10000) if rows > (int(max_rows) or 200000) else rows        # (the rule of the C entry point)
+        _, nbytes = self.index_device_ptr()
+        self._index_shape = (n, nbytes // (4 * n))
+        return n
+
+    def index_build_abort(self):
+        self._L.rvc_index_build_abort(self._h)
+
+    def build_index(self, recordings, window=None, max_rows=None, reduce_to=None, iters: int = 10, seed: int = 0, train: bool = True, nprobe: int = 1) -> dict:
+        """Build this voice's index from its recordings on the device and install it.  `recordings`: an iterable of 1-D float arrays at 16 kHz, or of
+        (array, rate) pairs; a pair whose rate is not 16 000 goes through the package's resampler (resample.FftFixedInOut, one call over the whole
+        recording) first.  window in 16 kHz samples (None = 48 000).  train=True: ends with train_index_ivf() (upstream's nlist rule, the same iters and
+        seed) and sets nprobe.  -> the index_build_info fields as they stood before the build closed, "index_rows" = rows of the installed index, and
+        "ivf" = train_index_ivf's report when trained."""
+        self.index_build_begin(window or 0, 0)
+        try:
+            for rec in recordings:
+                rate = 16000
+                if isinstance(rec, tuple):
+                    rec, rate = rec
+                x = np.ascontiguousarray(rec, np.float32)
+                if x.ndim != 1:
+                    raise RvcInferError(5, "index build: a recording is a 1-D array")
+                if int(rate) != 16000 and len(x):
+                    x = self._to_16k(x, int(rate))
+                self.index_build_add(x)
+            info = self.index_build_info()
+            info["index_rows"] = self.index_build_finish(max_rows or 0, reduce_to or 0, iters, seed)
+        except BaseException:
+            self.index_build_abort()
+            raise
+        if train:
+            info["ivf"] = self.train_index_ivf(iters=iters, seed=seed, nprobe=nprobe)
+        return info
+
+    def _to_16k(self, x: np.ndarray, rate: int) -> np.ndarray:
+        """a whole recording through the package's converter (resample.FftFixedInOut, the plugin's rubato mirror) in blocks of about 20 ms, the last one
+        zero-padded and one block of zeros behind it to flush the converter; its start-up delay (half a block) stays in as leading silence"""
+        from .resample import FftFixedInOut
+        r = FftFixedInOut(self, rate, 16000, max(rate // 50, 1))
+        nin = r.input_frames_next()
+        nblk = -(-len(x) // nin) + 1
+        xp = np.zeros(nblk * nin, np.float32)
+        xp[: len(x)] = x
+        y = np.concatenate([np.array(r.process(xp[i * nin:(i + 1) * nin]), np.float32) for i in range(nblk)])
+        return y[: -(-len(x) * 16000 // rate) + r.output_frames_max() // 2]
+
     def rccl_unique_id(self) -> bytes:
         """rvc_rccl_unique_id: rank 0 creates the 128-byte ncclUniqueId the host then hands to the other ranks."""
         buf = C.create_string_buffer(128)
