@@ -85,7 +85,8 @@ rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rv
 int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded */
 
 /* ---- capabilities the reference plumbs through but never implements / bakes into its export ---- */
-/* flat-L2 retrieval index (index_path / index_rate settings, obs-rvc/src/lib.rs:78,81; rvc.rs:159 TODO) */
+/* flat-L2 retrieval index (index_path / index_rate settings, obs-rvc/src/lib.rs:78,81; rvc.rs:159 TODO).  A load that fails behind its argument checks
+   (RVC_BACKEND: no device memory, a failed copy) leaves the engine with no index at all -- rvc_index_device_ptr returns NULL, k and the index rate are kept. */
 rvc_status rvc_load_index(rvc_engine *e, const float *vectors, size_t n, size_t dim);
 rvc_status rvc_load_index_device(rvc_engine *e, const void *d_vectors, size_t n, size_t dim);  /* already in HBM (RCCL-broadcast) */
 void rvc_set_index_rate(rvc_engine *e, float rate);

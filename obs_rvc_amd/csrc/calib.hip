@@ -7,7 +7,7 @@
 //   rvc_clock_monitor_start  eight sleeping waves (one per XCD) that count shader cycles (s_memtime) against the 100 MHz real-time counter
 //   / _stop                  (s_memrealtime) WHILE the engine works: the effective shader clock of a leg under its real load
 #include "../../include/rvc_mi355x.h"
-#include <hip/hip_runtime.h>
+#include "dev_raii.h"
 
 #include <algorithm>
 #include <chrono>
@@ -16,12 +16,6 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
-
-#define HIPCHK(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
 
 namespace rvc {
 namespace {
@@ -119,12 +113,12 @@ rvc_status rvc_calibrate(int device, rvc_calibration *out)
         HIPCHK(hipSetDevice(device));
         hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, device));
         const int ncu = prop.multiProcessorCount;
-        float *sink = nullptr; long long *clk = nullptr; float4 *buf = nullptr;
+        DevBuf<float> d_sink; DevBuf<long long> d_clk; DevBuf<float4> d_buf;
         const size_t bytes = (size_t)1 << 30, n4 = bytes / 16;
-        HIPCHK(hipMalloc(&sink, (size_t)ncu * 4 * 256 * sizeof(float)));
-        HIPCHK(hipMalloc(&clk, 4 * sizeof(long long)));
-        HIPCHK(hipMalloc(&buf, bytes));
-        hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+        d_sink.alloc((size_t)ncu * 4 * 256); d_clk.alloc(4); d_buf.alloc(n4);
+        float *const sink = d_sink.get(); long long *const clk = d_clk.get(); float4 *const buf = d_buf.get();
+        DevEvent ev0, ev1;
+        const hipEvent_t e0 = ev0.get(), e1 = ev1.get();
         const auto t_begin = std::chrono::steady_clock::now();
         // fp32 MFMA: 4 workgroups of 4 waves per CU = 4 waves per SIMD; 16 MFMAs per iteration and wave; ~20 ms per launch, the third launch counts
         const int iters = 12000, grid = ncu * 4;
@@ -156,8 +150,6 @@ rvc_status rvc_calibrate(int device, rvc_calibration *out)
         out->hbm_sclk_mhz = h[3] > 0 ? (double)h[2] / (double)h[3] * 100.0 : 0.0;
         out->compute_units = ncu;
         out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        (void)hipFree(buf); (void)hipFree(clk); (void)hipFree(sink);
         return RVC_OK;
     } catch (const std::exception &) { return RVC_BACKEND; }
 }

@@ -753,8 +753,8 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
         if (B < 1 || B > 4096 || C < 1 || C > 4096 || R < 1 || R > 4096 || T < 1 || T > (1 << 20) || s->skip_head < 0 || s->ph_ld < R || s->cv_ld < T || s->ph_ld > (1 << 20) ||
             s->cv_ld > (1 << 21) || (long long)s->skip_head + R > 2LL * T + 1 || s->reps < 1 || s->reps > 64 || s->path < 0 || s->path > 1 || !(s->rate >= 0.f && s->rate <= 1.f))
             throw ShapeError("retrieval spec");
-        if (!e->d_index) throw ShapeError("no index loaded");
-        if (e->index_dim != (size_t)C) throw ShapeError("index dimension does not match the feature dimension");
+        if (!e->index.rows) throw ShapeError("no index loaded");
+        if (e->index.dim != (size_t)C) throw ShapeError("index dimension does not match the feature dimension");
         Plan pl; pl.B = B; pl.nprobe = e->index_nprobe; pl.knn_k = e->index_k;
         Arena &A = pl.arena;
         const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_hit = (size_t)B * R * pl.knn_k;
@@ -800,7 +800,7 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
 }
 
 // test aid: which copies of the index exist (a fallback list built while the transposed copy is absent walks the row-major matrix)
-int rvc_debug_index_layouts(rvc_engine *e) { return e ? (e->d_indexF ? 1 : 0) | (e->d_indexT ? 2 : 0) | (e->d_ivf_cent ? 4 : 0) : 0; }
+int rvc_debug_index_layouts(rvc_engine *e) { return e ? (e->index.rowsF ? 1 : 0) | (e->index.rowsT ? 2 : 0) | (e->index.ivf.cent ? 4 : 0) : 0; }
 
 // test aid: one assign step and one update step of the k-means training (retrieval.hip kmeans_assign_step / kmeans_update_step; tests/test_gpu_kmeans.py)
 int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist, const int32_t *prev_assign_or_null, int32_t *assign_out, float *dist_out,
@@ -808,19 +808,19 @@ int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist
 {
     return (int)guarded(e, [&]() {
         if (!centroids_in || !assign_out || !dist_out || !centroids_out || !objective_out || !moved_out) throw ShapeError("k-means step: null argument");
-        if (!e->d_index) throw ShapeError("no index loaded");
-        const size_t n = e->index_n, dim = e->index_dim;
+        if (!e->index.rows) throw ShapeError("no index loaded");
+        const size_t n = e->index.n, dim = e->index.dim;
         if (nlist < 1 || nlist > n || nlist > 65536) throw ShapeError("k-means step: nlist must be in [1, min(n, 65536)]");
         HIPCHK(hipDeviceSynchronize());
         KmeansWork w;
         w.alloc(n, dim, nlist);
-        HIPCHK(hipMemcpy(w.cent, centroids_in, nlist * dim * sizeof(float), hipMemcpyHostToDevice));
-        if (prev_assign_or_null) HIPCHK(hipMemcpy(w.assign[1], prev_assign_or_null, n * sizeof(int), hipMemcpyHostToDevice));
-        kmeans_assign_step(e, w, prev_assign_or_null ? w.assign[1] : nullptr, 0, objective_out, moved_out);
-        HIPCHK(hipMemcpy(assign_out, w.assign[0], n * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(dist_out, w.dist, n * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(w.cent.get(), centroids_in, nlist * dim * sizeof(float), hipMemcpyHostToDevice));
+        if (prev_assign_or_null) HIPCHK(hipMemcpy(w.assign[1].get(), prev_assign_or_null, n * sizeof(int), hipMemcpyHostToDevice));
+        kmeans_assign_step(e, w, prev_assign_or_null ? w.assign[1].get() : nullptr, 0, objective_out, moved_out);
+        HIPCHK(hipMemcpy(assign_out, w.assign[0].get(), n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist_out, w.dist.get(), n * sizeof(float), hipMemcpyDeviceToHost));
         kmeans_update_step(e, w, 0);
-        HIPCHK(hipMemcpy(centroids_out, w.cent, nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(centroids_out, w.cent.get(), nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
         return RVC_OK;
     });
 }
@@ -836,21 +836,19 @@ int rvc_debug_index_append(rvc_engine *e, const float *cv, int C, int T, int ld,
         HIPCHK(hipDeviceSynchronize());
         IndexBuild b;
         b.alloc((size_t)C, capacity);
-        float *d_cv = nullptr;
-        HIPCHK(hipMalloc(&d_cv, (size_t)C * ld * sizeof(float)));
-        struct Free { float *p; ~Free() { (void)hipFree(p); } } free_cv{d_cv};
-        HIPCHK(hipMemcpy(d_cv, cv, (size_t)C * ld * sizeof(float), hipMemcpyHostToDevice));
-        if (cursor) HIPCHK(hipMemcpy(b.store, head_rows, cursor * C * sizeof(float), hipMemcpyHostToDevice));
+        DevBuf<float> d_cv; d_cv.alloc((size_t)C * ld);
+        HIPCHK(hipMemcpy(d_cv.get(), cv, (size_t)C * ld * sizeof(float), hipMemcpyHostToDevice));
+        if (cursor) HIPCHK(hipMemcpy(b.store.get(), head_rows, cursor * C * sizeof(float), hipMemcpyHostToDevice));
         const int cnt0[2] = {(int)cursor, 0};
-        HIPCHK(hipMemcpy(b.d_cnt, cnt0, sizeof cnt0, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.d_cnt.get(), cnt0, sizeof cnt0, hipMemcpyHostToDevice));
         index_build_reserve(e, b, cursor, cursor + (size_t)T);
-        index_build_append(e, b, d_cv, C, T, ld);
+        index_build_append(e, b, d_cv.get(), C, T, ld);
         HIPCHK(hipStreamSynchronize(e->stream));
         HIPCHK(hipGetLastError());
         int cnt[2] = {0, 0};
-        HIPCHK(hipMemcpy(cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cnt, b.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
         if (cnt[0] < (int)cursor || (size_t)cnt[0] > cursor + (size_t)T) throw std::runtime_error("index append: the device-side row count is out of range");
-        HIPCHK(hipMemcpy(store_out, b.store, (size_t)cnt[0] * C * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(store_out, b.store.get(), (size_t)cnt[0] * C * sizeof(float), hipMemcpyDeviceToHost));
         *rows_out = (size_t)cnt[0]; *dropped_out = (size_t)cnt[1];
         return RVC_OK;
     });

@@ -241,7 +241,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         ~Swap() { if (on) { e->n_streams = n0; e->d_state = s0; } }
     } swap_guard(e, bucket_B, e->d_state_bucket);
     const int B = e->n_streams;
-    const bool with_index = mode == 0 && e->d_index && e->index_rate > 0.f;
+    const bool with_index = mode == 0 && e->index.rows && e->index_rate > 0.f;
     // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams (bucket_ids: the
     // streams of a bucket plan; else every stream) has it on.  Which value a stream has is no part of the key: the kernel reads it every chunk
     bool with_protect = false;
@@ -746,12 +746,6 @@ void rvc_destroy(rvc_engine *e)
     e->cv.reset(); e->rm.reset(); e->sy.reset();
     wfree(e->d_window); wfree(e->d_twiddle); wfree(e->d_basis);      // (upload_f: slab memory)
     if (e->d_band) (void)hipFree(e->d_band);
-    if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
-    if (e->d_indexT) (void)hipFree(e->d_indexT);
-    if (e->d_ynorm) (void)hipFree(e->d_ynorm);
-    if (e->d_nhn) (void)hipFree(e->d_nhn);
-    if (e->d_indexF) (void)hipFree(e->d_indexF);
-    drop_index_ivf(e);
     if (e->d_state) (void)hipFree(e->d_state);
     if (e->d_state_bucket) (void)hipFree(e->d_state_bucket);
     if (e->d_bucket_idx) (void)hipFree(e->d_bucket_idx);
@@ -1417,7 +1411,7 @@ rvc_status rvc_profile_last_knn(rvc_engine *e, int *launches, double *kernel_ms,
         if (nl && pl->d_ivf_scanned) {       // IVF retrieval: the centroid table (the coarse launch's slot) plus the rows the last run's probe sets held
             std::vector<int> rows(pl->ivf_queries);
             HIPCHK(hipMemcpy(rows.data(), pl->d_ivf_scanned, rows.size() * sizeof(int), hipMemcpyDeviceToHost));
-            for (int r : rows) by += (double)r * e->index_dim * sizeof(float);
+            for (int r : rows) by += (double)r * e->index.dim * sizeof(float);
         }
         if (launches) *launches = nl;
         if (kernel_ms) *kernel_ms = ms;

@@ -2,7 +2,7 @@
 //   plan.hip         the planner: device memory, prepared convolution weights, the op list, implicit-GEMM tile selection, test-hook table
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
 //   model_yin.hip    YIN f0 (build_yin)
-//   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: load, device-side layouts, the plan's search section
+//   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
 //   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
@@ -17,6 +17,7 @@
 #include "formant.hip.h"
 #include "f0cond.hip.h"
 #include "igemm_launch.h"
+#include "dev_raii.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -55,12 +56,6 @@ const char *tune_env(const char *name);
 #else
 static inline const char *tune_env(const char *) { return nullptr; }
 #endif
-
-#define HIPCHK(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
 
 struct ShapeError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct PanicError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -443,7 +438,18 @@ struct ModelSY {
 
 }  // namespace rvc
 
-namespace rvc { struct StreamSet; struct IndexBuild; }
+namespace rvc {
+struct StreamSet; struct IndexBuild;
+// The retrieval index as the engine owns it (retrieval.hip install_index is the one place that fills it): the row-major matrix, its device-side layouts (rowsT:
+// [dim][n], built on demand by ensure_index_transposed; rowsF: MFMA fragment order; ynorm / nhn: |y|^2 and -|y|^2 / 2) and the IVF structure over its rows
+// (rvc_set_index_ivf / rvc_train_index_ivf; ivf.hip.h): centroids, CSR offsets and the row permutation.  An empty `rows` = no index.
+struct IvfLists { DevBuf<float> cent; DevBuf<int> offs, perm; size_t nlist = 0, longest = 0, empty = 0; };
+struct RetrievalIndex {
+    DevBuf<float> rows, rowsT, rowsF, ynorm, nhn; size_t n = 0, dim = 0;
+    float prep_ms = 0.f;                              // device-side repack + norms of the load
+    IvfLists ivf;
+};
+}  // namespace rvc
 using namespace rvc;
 
 struct rvc_engine {
@@ -462,17 +468,15 @@ struct rvc_engine {
     std::unique_ptr<ModelSY> sy;
     // constants for the mel front end
     float *d_window = nullptr, *d_twiddle = nullptr, *d_basis = nullptr; int *d_band = nullptr;
-    // retrieval index
-    float *d_index = nullptr, *d_indexT = nullptr, *d_indexF = nullptr, *d_ynorm = nullptr, *d_nhn = nullptr; size_t index_n = 0, index_dim = 0; bool index_owned = true;
+    // retrieval index: what is loaded (index) and the caller's preferences, which are no part of it.  index_nprobe: 0 = flat search, else the lists probed per
+    // query; engine-wide and part of a plan's identity; a new index or a dropped IVF structure resets it
+    rvc::RetrievalIndex index;
     float index_rate = 0.f;
-    // IVF structure over the loaded index (rvc_set_index_ivf; ivf.hip.h): centroids, CSR offsets and the row permutation, all on the device.
-    // index_nprobe: 0 = flat search, else the lists probed per query; engine-wide and part of a plan's identity.  A new index drops both (build_index_aux)
-    float *d_ivf_cent = nullptr; int *d_ivf_offs = nullptr, *d_ivf_perm = nullptr; size_t ivf_nlist = 0, ivf_longest = 0, ivf_empty = 0; int index_nprobe = 0;
+    int index_nprobe = 0;
     int index_k = KNN_K;                                        // neighbours blended per query (rvc_set_index_k: 4 or 8); the caller's preference, kept across index loads; part of a plan's identity
-    float index_prep_ms = 0.f;                                  // device-side repack + norms of the last index load
     // the last k-means training of an IVF structure (rvc_train_index_ivf; kmeans.hip.h): what rvc_index_ivf_train_info reports
     bool km_valid = false; int km_iters_run = 0; size_t km_moved_last = 0; std::vector<double> km_obj; double km_ms[3] = {0, 0, 0};
-    rvc::IndexBuild *ib = nullptr;                              // an open index build (rvc_index_build_begin .. _finish / _abort; retrieval.hip); never touches d_index before finish
+    rvc::IndexBuild *ib = nullptr;                              // an open index build (rvc_index_build_begin .. _finish / _abort; retrieval.hip); never touches `index` before finish
     double bcast_ms[3] = {0, 0, 0}; int bcast_ranks = 0;         // last rvc_index_broadcast: communicator set-up, broadcast, repack (ms); ranks the communicator reports
     // streams
     int n_streams = 1;
@@ -574,20 +578,17 @@ void launch_ring16_update(hipStream_t s, int B, const float *in, float *out, int
 // a converter of nb streams (rvc_session_create's; released with rvc_resampler_destroy) and its chunk sizes; one call of it queued on the engine's stream
 rvc_status resampler_create_streams(rvc_engine *e, size_t rate_in, size_t rate_out, size_t chunk_size_in, int nb, rvc_resampler **out, int *fft_in, int *fft_out);
 void launch_resampler(rvc_resampler *r, const float *d_in, float *d_out, long long in_bs, long long out_bs);
-void build_index_aux(rvc_engine *e);
+void install_index(rvc_engine *e, DevBuf<float> rows, size_t n, size_t dim);      // the one way a matrix becomes the engine's index (contract: retrieval.hip)
 void ensure_index_transposed(rvc_engine *e);
-void drop_index_ivf(rvc_engine *e);
 // k-means training of an IVF structure (retrieval.hip, kmeans.hip.h): the device buffers of one training and its two steps, as rvc_train_index_ivf runs them and
 // as rvc_debug_kmeans_step does (debug.hip).  assign[2]: the current and the previous assignment, swapped per step
 struct KmeansWork {
     size_t n = 0, dim = 0, nlist = 0; int nwg = 0, nparts = 0;
-    float *cent = nullptr, *dist = nullptr; int *assign[2] = {nullptr, nullptr}, *moved_wg = nullptr, *counts = nullptr, *offs = nullptr, *perm = nullptr;
-    double *part = nullptr, *obj = nullptr; long long *moved = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr}; double ms_assign = 0, ms_update = 0;
-    KmeansWork() = default; KmeansWork(const KmeansWork &) = delete; KmeansWork &operator=(const KmeansWork &) = delete;
+    DevBuf<float> cent, dist; DevBuf<int> assign[2], moved_wg, counts, offs, perm;
+    DevBuf<double> part, obj; DevBuf<long long> moved;
+    DevTimer step; double ms_assign = 0, ms_update = 0;
     const float *rows = nullptr;          // the matrix trained on; null = the engine's loaded index
     void alloc(size_t n, size_t dim, size_t nlist, const float *rows = nullptr);
-    ~KmeansWork();
 };
 void kmeans_assign_step(rvc_engine *e, KmeansWork &w, const int *prev, int cur, double *objective, long long *moved);
 void kmeans_update_step(rvc_engine *e, KmeansWork &w, int cur);
@@ -598,15 +599,13 @@ void kmeans_update_step(rvc_engine *e, KmeansWork &w, int cur);
 struct IndexBuild {
     size_t window = 0, dim = 0, capacity = 0;
     size_t rows = 0, windows = 0, dropped = 0;      // as of the last add (the device counters are read once per add)
-    float *store = nullptr;                         // [capacity][dim] fp32
-    int *d_cnt = nullptr;                           // {rows, dropped} on the device
-    int *d_bad = nullptr; size_t bad_cap = 0;       // one word per frame of a window, zero between windows
-    std::vector<void *> retired;                    // allocations the store outgrew, freed behind the add's synchronisation
-    std::vector<hipEvent_t> ev;                     // timing of an add's run w: 3 w = before its ContentVec run, 3 w + 1 = behind it, 3 w + 2 = behind its append
+    DevBuf<float> store;                            // [capacity][dim] fp32
+    DevBuf<int> d_cnt;                              // {rows, dropped} on the device
+    DevBuf<int> d_bad; size_t bad_cap = 0;          // one word per frame of a window, zero between windows
+    std::vector<DevBuf<char>> retired;              // allocations the store outgrew, freed behind the add's synchronisation
+    std::vector<DevEvent> ev;                       // timing of an add's run w: 3 w = before its ContentVec run, 3 w + 1 = behind it, 3 w + 2 = behind its append
     double ms[3] = {0, 0, 0};                       // device milliseconds: ContentVec runs, appends, the reduction
-    IndexBuild() = default; IndexBuild(const IndexBuild &) = delete; IndexBuild &operator=(const IndexBuild &) = delete;
     void alloc(size_t dim, size_t capacity);
-    ~IndexBuild();
 };
 void index_build_reserve(rvc_engine *e, IndexBuild &b, size_t upper, size_t need);
 void index_build_append(rvc_engine *e, IndexBuild &b, const float *cv, int C, int T, int ld);

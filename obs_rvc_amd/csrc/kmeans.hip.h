@@ -12,7 +12,7 @@ namespace rvc {
 #define KM_DC 32                       // ... dimensions per staged chunk
 #define KM_RB 256                      // kmeans_objective_kernel: distances per partial
 
-// ---- before training: the first row that holds a NaN or an Inf (a non-finite norm of build_index_aux is only a hint: a finite row's norm can overflow) ----
+// ---- before training: the first row that holds a NaN or an Inf (a non-finite norm of install_index is only a hint: a finite row's norm can overflow) ----
 static __global__ void kmeans_nonfinite_kernel(const float *index, const float *ynorm, int n, int dim, int *first)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -92,7 +92,7 @@ rvc_status rvc_index_broadcast(rvc_engine *e, const void *unique_id128, int rank
         // header instead; every rank then rejects it in the agreement all-reduce and all of them return the error together.
         if (world < 1 || rank < 0 || rank >= world || !unique_id128) throw ShapeError("index broadcast: bad rank / world / unique id");
         std::string root_err;
-        if (rank == 0 && !vectors && !e->d_index) root_err = "index broadcast: rank 0 has neither host vectors nor a loaded index";
+        if (rank == 0 && !vectors && !e->index.rows) root_err = "index broadcast: rank 0 has neither host vectors nor a loaded index";
         else if (rank == 0 && vectors && (n < (size_t)e->index_k || dim < 1)) root_err = "index broadcast: index needs at least " + std::to_string(e->index_k) + " vectors";
         RcclApi &api = rccl_api();
         if (!api.lib) throw std::runtime_error(api.err);
@@ -105,17 +105,17 @@ rvc_status rvc_index_broadcast(rvc_engine *e, const void *unique_id128, int rank
         int ranks = 0;
         (void)api.CommCount(comm, &ranks);
         const auto t1 = clk::now();
-        float *d_new = nullptr; unsigned long long *d_hdr = nullptr;
+        DevBuf<float> d_new; DevBuf<unsigned long long> d_hdr;
         std::string local_err;
         try {
             // header first: the other ranks learn (n, dim) from rank 0
             unsigned long long hdr[2] = {0, 0};
-            if (rank == 0 && root_err.empty()) { hdr[0] = vectors ? n : e->index_n; hdr[1] = vectors ? dim : e->index_dim; }
-            HIPCHK(hipMalloc(&d_hdr, 4 * sizeof(unsigned long long)));
-            HIPCHK(hipMemcpy(d_hdr, hdr, sizeof hdr, hipMemcpyHostToDevice));
-            RCCLCHK(api, api.Broadcast(d_hdr, d_hdr, sizeof hdr, /*ncclUint8*/ 1, 0, comm, e->stream));
+            if (rank == 0 && root_err.empty()) { hdr[0] = vectors ? n : e->index.n; hdr[1] = vectors ? dim : e->index.dim; }
+            d_hdr.alloc(4);
+            HIPCHK(hipMemcpy(d_hdr.get(), hdr, sizeof hdr, hipMemcpyHostToDevice));
+            RCCLCHK(api, api.Broadcast(d_hdr.get(), d_hdr.get(), sizeof hdr, /*ncclUint8*/ 1, 0, comm, e->stream));
             HIPCHK(hipStreamSynchronize(e->stream));
-            HIPCHK(hipMemcpy(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hdr, d_hdr.get(), sizeof hdr, hipMemcpyDeviceToHost));
             const size_t bn = (size_t)hdr[0], bd = (size_t)hdr[1];
             // local verdict on the header (shape, memory), then ONE all-reduce of it: every rank leaves together or goes on together --
             // a rank that simply threw here would leave the others blocked in the payload broadcast
@@ -123,8 +123,9 @@ rvc_status rvc_index_broadcast(rvc_engine *e, const void *unique_id128, int rank
             if (!root_err.empty()) { ok = 0; local_err = root_err; }
             else if (bn < (size_t)e->index_k || bd < 1 || bn * bd > ((size_t)1 << 36)) { ok = 0; local_err = "index broadcast: rank 0 sent no usable index (its arguments were rejected there, or the size is implausible)"; }
             else if (rank != 0 && n && dim && (n != bn || dim != bd)) { ok = 0; local_err = "index broadcast: this rank expected a different index shape than rank 0 sent"; }
-            else if (hipMalloc(&d_new, bn * bd * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); d_new = nullptr; ok = 0; local_err = "index broadcast: out of device memory for the index"; }
-            int *d_ok = reinterpret_cast<int *>(d_hdr + 2);
+            else if (float *p = nullptr; forget_failure(hipMalloc(&p, bn * bd * sizeof(float))) != hipSuccess) { ok = 0; local_err = "index broadcast: out of device memory for the index"; }
+            else d_new = DevBuf<float>(p);
+            int *d_ok = reinterpret_cast<int *>(d_hdr.get() + 2);
             HIPCHK(hipMemcpy(d_ok, &ok, sizeof ok, hipMemcpyHostToDevice));
             RCCLCHK(api, api.AllReduce(d_ok, d_ok, 1, /*ncclInt32*/ 2, /*ncclMin*/ 3, comm, e->stream));
             HIPCHK(hipStreamSynchronize(e->stream));
@@ -132,28 +133,21 @@ rvc_status rvc_index_broadcast(rvc_engine *e, const void *unique_id128, int rank
             HIPCHK(hipMemcpy(&all_ok, d_ok, sizeof all_ok, hipMemcpyDeviceToHost));
             if (!all_ok) throw ShapeError(local_err.empty() ? "index broadcast: another rank rejected the index" : local_err);
             if (rank == 0) {
-                if (vectors) HIPCHK(hipMemcpy(d_new, vectors, bn * bd * sizeof(float), hipMemcpyHostToDevice));
-                else HIPCHK(hipMemcpy(d_new, e->d_index, bn * bd * sizeof(float), hipMemcpyDeviceToDevice));
+                if (vectors) HIPCHK(hipMemcpy(d_new.get(), vectors, bn * bd * sizeof(float), hipMemcpyHostToDevice));
+                else HIPCHK(hipMemcpy(d_new.get(), e->index.rows.get(), bn * bd * sizeof(float), hipMemcpyDeviceToDevice));
             }
             // one ncclBroadcast of the whole matrix: 307 MB for 100k x 768; over the xGMI mesh the root feeds its peers on distinct links
-            RCCLCHK(api, api.Broadcast(d_new, d_new, bn * bd, /*ncclFloat32*/ 7, 0, comm, e->stream));
+            RCCLCHK(api, api.Broadcast(d_new.get(), d_new.get(), bn * bd, /*ncclFloat32*/ 7, 0, comm, e->stream));
             HIPCHK(hipStreamSynchronize(e->stream));
             const auto t2 = clk::now();
-            if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
-            e->d_index = d_new; d_new = nullptr; e->index_owned = true;
-            e->index_n = bn; e->index_dim = bd;
-            build_index_aux(e);                       // fragment-order copy + norms, on the device
-            e->plans.clear(); e->last_plan = nullptr;
+            install_index(e, std::move(d_new), bn, bd);      // fragment-order copy + norms, on the device
             const auto t3 = clk::now();
             auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             e->bcast_ms[0] = ms(t0, t1); e->bcast_ms[1] = ms(t1, t2); e->bcast_ms[2] = ms(t2, t3); e->bcast_ranks = ranks;
         } catch (...) {
-            if (d_new) (void)hipFree(d_new);
-            if (d_hdr) (void)hipFree(d_hdr);
             (void)api.CommDestroy(comm);
             throw;
         }
-        (void)hipFree(d_hdr);
         RCCLCHK(api, api.CommDestroy(comm));
         return RVC_OK;
     });

@@ -19,8 +19,8 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
 // The IVF section, in place of the flat one for every stream count: two launches, no fallback list, nothing that can time out.
 static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_raw, uint32_t skip_head, uint32_t R, int T, const T1 &phone, const T1 &cvo)
 {
-        if (!e->d_ivf_cent) throw ShapeError("no IVF structure attached to the index");
-        const int nlist = (int)e->ivf_nlist, Q = B * nq;
+        if (!e->index.ivf.cent) throw ShapeError("no IVF structure attached to the index");
+        const int nlist = (int)e->index.ivf.nlist, Q = B * nq;
         const int nprobe = std::min(pl.nprobe, nlist);
         float *D = pl.arena.floats((size_t)Q * nlist);
         int *scanned = (int *)pl.arena.alloc((size_t)Q * sizeof(int));
@@ -28,7 +28,7 @@ static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_r
         snprintf(g_last_kernel, sizeof g_last_kernel, "knn_ivf");
         Plan *plp = &pl;
         {
-            IvfCoarseP cp{}; cp.cent = e->d_ivf_cent; cp.nlist = nlist; cp.dim = C; cp.cv = cvo.p; cp.cv_cs = cvo.ld; cp.cv_bs = cvo.bs; cp.first_raw = first_raw; cp.nq = nq; cp.Q = Q; cp.D = D;
+            IvfCoarseP cp{}; cp.cent = e->index.ivf.cent.get(); cp.nlist = nlist; cp.dim = C; cp.cv = cvo.p; cp.cv_cs = cvo.ld; cp.cv_bs = cvo.bs; cp.first_raw = first_raw; cp.nq = nq; cp.Q = Q; cp.D = D;
             const size_t lds = (size_t)IVF_TQ * ivf_qs(C) * sizeof(float);
             if (lds > 128 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
             dim3 grid((nlist + IVF_TC - 1) / IVF_TC, (Q + IVF_TQ - 1) / IVF_TQ);
@@ -40,7 +40,7 @@ static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_r
             });
         }
         {
-            IvfScanP sp{}; sp.D = D; sp.nlist = nlist; sp.nprobe = nprobe; sp.offs = e->d_ivf_offs; sp.perm = e->d_ivf_perm; sp.index = e->d_index; sp.dim = C;
+            IvfScanP sp{}; sp.D = D; sp.nlist = nlist; sp.nprobe = nprobe; sp.offs = e->index.ivf.offs.get(); sp.perm = e->index.ivf.perm.get(); sp.index = e->index.rows.get(); sp.dim = C;
             sp.cv = cvo.p; sp.cv_cs = cvo.ld; sp.cv_bs = cvo.bs; sp.first_raw = first_raw; sp.nq = nq;
             sp.skip_head = (int)skip_head; sp.T = T; sp.R = (int)R; sp.rate = e->index_rate;
             sp.phone = phone.p; sp.ph_cs = phone.ld; sp.ph_bs = phone.bs; sp.out_idx = pl.d_knn_idx; sp.out_dist = pl.d_knn_dist; sp.scanned = scanned;
@@ -58,14 +58,14 @@ static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_r
 
 void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip_head, uint32_t R, const T1 &phone)
 {
-        if (e->index_dim != (size_t)C) throw std::runtime_error("index dimension does not match the feature dimension");
+        if (e->index.dim != (size_t)C) throw std::runtime_error("index dimension does not match the feature dimension");
         // unique raw frames behind the sliced frames (Q2): first_raw .. last_raw
         const int first_raw = std::min((int)skip_head / 2, T - 1), last_raw = std::min((int)(skip_head + R - 1) / 2, T - 1);
         const int nq = last_raw - first_raw + 1;
-        const int nblk = (int)((e->index_n + 255) / 256);
+        const int nblk = (int)((e->index.n + 255) / 256);
         const int K = pl.knn_k;
         if (K != KNN_K && K != KNN_KMAX) throw ShapeError("k must be 4 or 8");
-        if (e->index_n < (size_t)K) throw ShapeError("index needs at least " + std::to_string(K) + " vectors");
+        if (e->index.n < (size_t)K) throw ShapeError("index needs at least " + std::to_string(K) + " vectors");
         pl.d_knn_idx = (int *)pl.arena.alloc((size_t)B * R * K * sizeof(int));
         pl.d_knn_dist = pl.arena.floats((size_t)B * R * K);
         T1 cvo = pl.cv_out;
@@ -80,8 +80,8 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         const int Q = B * nq, Qpad = (Q + 127) / 128 * 128;
         // (the GEMM path addresses its operands with 32-bit byte / element offsets: the one-pass scan, whose strides are 64-bit, takes
         // indexes beyond that range)
-        const bool gemm_fits = (size_t)C * e->index_n * sizeof(float) < ((size_t)1 << 31) && (size_t)Qpad * e->index_n < ((size_t)1 << 31);
-        const bool gemm_scan = fast && Q >= 128 && gemm_fits && e->d_nhn && !test_opt("RVC_KNN_NO_GEMM");
+        const bool gemm_fits = (size_t)C * e->index.n * sizeof(float) < ((size_t)1 << 31) && (size_t)Qpad * e->index.n < ((size_t)1 << 31);
+        const bool gemm_scan = fast && Q >= 128 && gemm_fits && e->index.nhn && !test_opt("RVC_KNN_NO_GEMM");
         if (gemm_scan || !fast) ensure_index_transposed(e);
         if (fast && !gemm_scan) {
             // one stream / few streams: ONE launch per group of 16 queries (knn_scan_select_kernel: scan, select, exact re-rank, blend)
@@ -90,7 +90,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
             // also take it from the environment)
             const int wgs_opt = test_opt_int("RVC_KNN_WGS", 0);
             const unsigned knn_wgs = wgs_opt > 0 ? (unsigned)wgs_opt : 3u * (unsigned)e->cv_cus;
-            const unsigned G = std::min(std::min((unsigned)((e->index_n + 63) / 64), std::max(knn_wgs / (unsigned)B, 64u)), (unsigned)KNN_FUSED_MAXG);
+            const unsigned G = std::min(std::min((unsigned)((e->index.n + 63) / 64), std::max(knn_wgs / (unsigned)B, 64u)), (unsigned)KNN_FUSED_MAXG);
             const int ngroups = (nq + 15) / 16;
             snprintf(g_last_kernel, sizeof g_last_kernel, "knn_fused");
             unsigned long long *lists = (unsigned long long *)pl.arena.alloc((size_t)ngroups * B * 16 * G * K * sizeof(unsigned long long));
@@ -100,7 +100,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
             for (int gi = 0; gi < ngroups; gi++) {
                 const size_t lds = knn_fused_lds_floats(C, std::min(16, nq - gi * 16), (int)G, K) * sizeof(float);
                 if (lds > 128 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
-                KnnFusedP fp{}; fp.indexF = e->d_indexF; fp.index = e->d_index; fp.ynorm = e->d_ynorm; fp.n = (int)e->index_n; fp.dim = C;
+                KnnFusedP fp{}; fp.indexF = e->index.rowsF.get(); fp.index = e->index.rows.get(); fp.ynorm = e->index.ynorm.get(); fp.n = (int)e->index.n; fp.dim = C;
                 fp.cv = cvo.p; fp.cv_cs = cvo.ld; fp.cv_bs = cvo.bs; fp.first_raw = first_raw; fp.nq = nq; fp.q0 = gi * 16;
                 fp.lists = lists + (size_t)gi * B * 16 * G * K; fp.ticket = ticket + (size_t)gi * B * 2;
                 fp.skip_head = (int)skip_head; fp.T = T; fp.R = (int)R; fp.rate = e->index_rate;
@@ -109,7 +109,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
                 fp.spin_limit = 1u << 22;
                 dim3 grid(G, B);
                 Plan *plp = &pl;
-                const double scan_bytes = (double)e->index_n * C * sizeof(float) * B;     // algorithmic bytes: the index, read once per query group
+                const double scan_bytes = (double)e->index.n * C * sizeof(float) * B;     // algorithmic bytes: the index, read once per query group
                 const auto fused_kernel = KNN_KERNEL_FOR(knn_scan_select, K);
                 pl.ops.push_back([=](hipStream_t s) {
                     const ProfEvent *pe = plp->prof_slot(0, scan_bytes, -1, "knn_scan_select");
@@ -144,9 +144,9 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         int *d_overflow = (int *)pl.arena.alloc((size_t)B * sizeof(int));
         pl.d_knn_overflow = d_overflow;
         if (fast) {
-            float *d_approx = pl.arena.floats((size_t)Qpad * e->index_n);
+            float *d_approx = pl.arena.floats((size_t)Qpad * e->index.n);
             float *d_qf = pl.arena.floats((size_t)Qpad * C);
-            const int n_idx = (int)e->index_n;
+            const int n_idx = (int)e->index.n;
             {
                 dim3 grid(Qpad / 16, C / 16); int *ovf = d_overflow; const int nb = B;
                 pl.ops.push_back([=](hipStream_t s) {
@@ -155,12 +155,12 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
                 });
             }
             ConvW qw; qw.w = d_qf; qw.bias = nullptr; qw.M = Qpad; qw.K = C; qw.Kp = C; qw.Cin = C; qw.Cout = Qpad; qw.KW = 1; qw.groups = 1; qw.nphase = 1; qw.owns = false;
-            T1 xi; xi.p = e->d_indexT; xi.B = 1; xi.C = C; xi.T = n_idx; xi.ld = n_idx; xi.halo = 0; xi.bs = (long long)C * n_idx;
+            T1 xi; xi.p = e->index.rowsT.get(); xi.B = 1; xi.C = C; xi.T = n_idx; xi.ld = n_idx; xi.halo = 0; xi.bs = (long long)C * n_idx;
             T1 ya; ya.p = d_approx; ya.B = 1; ya.C = Qpad; ya.T = n_idx; ya.ld = n_idx; ya.halo = 0; ya.bs = (long long)Qpad * n_idx;
-            ConvOpts o; o.no_bias = true; o.res = e->d_nhn; o.res_cs = 0; o.res_bs = 0; o.scale = -2.0f;
+            ConvOpts o; o.no_bias = true; o.res = e->index.nhn.get(); o.res_cs = 0; o.res_bs = 0; o.scale = -2.0f;
             add_conv1d(pl, qw, xi, ya, 1, 0, 1, o);
-            KnnSelP sp{}; sp.approx = d_approx; sp.approx_bs = (long long)nq * e->index_n; sp.n = (int)e->index_n; sp.dim = C; sp.nq = nq;
-            sp.index = e->d_index; sp.q = d_q; sp.q_bs = (long long)nq * C; sp.skip_head = (int)skip_head; sp.T = T; sp.R = (int)R; sp.first_raw = first_raw;
+            KnnSelP sp{}; sp.approx = d_approx; sp.approx_bs = (long long)nq * e->index.n; sp.n = (int)e->index.n; sp.dim = C; sp.nq = nq;
+            sp.index = e->index.rows.get(); sp.q = d_q; sp.q_bs = (long long)nq * C; sp.skip_head = (int)skip_head; sp.T = T; sp.R = (int)R; sp.first_raw = first_raw;
             sp.rate = e->index_rate; sp.phone = phone.p; sp.ph_cs = phone.ld; sp.ph_bs = phone.bs; sp.out_idx = pl.d_knn_idx; sp.out_dist = pl.d_knn_dist;
             sp.overflow = d_overflow;
             dim3 sgrid(nq, B);
@@ -187,8 +187,8 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
         }
         for (int q0 = 0; q0 < nq; q0 += KNN_MAXQ) {
             const int qn = std::min(KNN_MAXQ, nq - q0);
-            KnnP kp{}; kp.indexT = e->d_indexT; kp.index = e->d_index; kp.n = (int)e->index_n; kp.dim = C; kp.nblk = nblk;
-            kp.v_stride = e->d_indexT ? 1 : C; kp.d_stride = e->d_indexT ? (long long)e->index_n : 1;
+            KnnP kp{}; kp.indexT = e->index.rowsT.get(); kp.index = e->index.rows.get(); kp.n = (int)e->index.n; kp.dim = C; kp.nblk = nblk;
+            kp.v_stride = e->index.rowsT ? 1 : C; kp.d_stride = e->index.rowsT ? (long long)e->index.n : 1;
             // query sub-range: pointers offset so that [B][nq] strides stay those of the full arrays
             kp.q = d_q + (size_t)q0 * C; kp.nq = qn; kp.cand_d = cand_d + (size_t)q0 * nblk * K; kp.cand_i = cand_i + (size_t)q0 * nblk * K;
             kp.overflow = fast ? d_overflow : nullptr;
@@ -200,7 +200,7 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
                 hipLaunchKernelGGL(scan_kernel, grid, dim3(256), 0, s, k2);
             });
         }
-        KnnBlendP bp{}; bp.cand_d = cand_d; bp.cand_i = cand_i; bp.nblk = nblk; bp.nq = nq; bp.index = e->d_index; bp.dim = C; bp.q = d_q;
+        KnnBlendP bp{}; bp.cand_d = cand_d; bp.cand_i = cand_i; bp.nblk = nblk; bp.nq = nq; bp.index = e->index.rows.get(); bp.dim = C; bp.q = d_q;
         bp.skip_head = (int)skip_head; bp.T = T; bp.R = (int)R; bp.first_raw = first_raw; bp.rate = e->index_rate;
         bp.phone = phone.p; bp.ph_cs = phone.ld; bp.ph_bs = phone.bs; bp.out_idx = pl.d_knn_idx; bp.out_dist = pl.d_knn_dist;
         bp.overflow = fast ? d_overflow : nullptr;
@@ -209,17 +209,11 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
         pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(merge_kernel, grid, dim3(256), 0, s, bp); });
 }
 
-// // Everything the retrieval kernels need besides the row-major matrix, built ON THE DEVICE from the copy that is already in HBM
-// (uploaded once, or delivered by the RCCL broadcast): the MFMA-fragment-order copy for the one-pass approximate scan and the vector
-// norms.  No host round trip (round 2 copied the 307 MB matrix back to the host, repacked it in a single-threaded loop and uploaded two
-// more copies: seconds per rank behind a 2 ms broadcast).  The transposed copy is NOT built here: see ensure_index_transposed.
-void drop_index_ivf(rvc_engine *e)
+// the engine's IVF structure goes: the search is flat again, and no plan that probed the lists stays
+static void drop_index_ivf(rvc_engine *e)
 {
-    if (e->d_ivf_cent) (void)hipFree(e->d_ivf_cent);
-    if (e->d_ivf_offs) (void)hipFree(e->d_ivf_offs);
-    if (e->d_ivf_perm) (void)hipFree(e->d_ivf_perm);
-    e->d_ivf_cent = nullptr; e->d_ivf_offs = e->d_ivf_perm = nullptr;
-    e->ivf_nlist = e->ivf_longest = e->ivf_empty = 0; e->index_nprobe = 0;
+    e->index.ivf = IvfLists(); e->index_nprobe = 0;
+    e->plans.clear(); e->last_plan = nullptr;
 }
 
 // The CSR of an assignment (list offsets + row permutation, rows ascending inside every list) by the counting sort of ivf.hip.h, queued on the engine's stream:
@@ -231,19 +225,33 @@ static void ivf_build_csr(rvc_engine *e, const int *d_assign, size_t n, size_t n
     hipLaunchKernelGGL(ivf_offsets_kernel, dim3(1), dim3(256), 0, e->stream, d_counts, (int)nlist, d_offs);
     hipLaunchKernelGGL(ivf_fill_kernel, dim3((unsigned)((nlist + 3) / 4)), dim3(256), 0, e->stream, d_assign, (int)n, (int)nlist, d_offs, d_perm);
 }
-// behind ivf_build_csr into the engine's own arrays: check the offsets and note what rvc_index_ivf_info reports
-static void ivf_note_lists(rvc_engine *e, size_t n, size_t nlist)
+// behind ivf_build_csr into l's arrays: check the offsets and note what rvc_index_ivf_info reports
+static void ivf_note_lists(rvc_engine *e, IvfLists &l, size_t n, size_t nlist)
 {
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
     std::vector<int> offs(nlist + 1);
-    HIPCHK(hipMemcpy(offs.data(), e->d_ivf_offs, offs.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(offs.data(), l.offs.get(), offs.size() * sizeof(int), hipMemcpyDeviceToHost));
     if (offs[0] != 0 || (size_t)offs[nlist] != n) throw std::runtime_error("IVF structure: the device-side list offsets do not add up");
-    e->ivf_nlist = nlist; e->ivf_longest = e->ivf_empty = 0;
-    for (size_t l = 0; l < nlist; l++) {
-        const size_t len = (size_t)(offs[l + 1] - offs[l]);
-        e->ivf_longest = std::max(e->ivf_longest, len); e->ivf_empty += len == 0;
+    l.nlist = nlist; l.longest = l.empty = 0;
+    for (size_t i = 0; i < nlist; i++) {
+        const size_t len = (size_t)(offs[i + 1] - offs[i]);
+        l.longest = std::max(l.longest, len); l.empty += len == 0;
     }
+}
+// The one way a structure is attached, behind drop_index_ivf: the CSR of d_assign (d_counts: scratch of nlist ints) next to the centroids, built in a structure
+// of its own that becomes the engine's only once its offsets have been accepted -- a failure leaves no structure and a flat search.  behind_csr: recorded
+// behind the CSR's launches (the training's total time ends there).
+static void attach_ivf(rvc_engine *e, DevBuf<float> cent, const int *d_assign, int *d_counts, size_t nlist, DevEvent *behind_csr = nullptr)
+{
+    const size_t n = e->index.n;
+    IvfLists l;
+    l.cent = std::move(cent);
+    l.offs.alloc(nlist + 1); l.perm.alloc(n);
+    ivf_build_csr(e, d_assign, n, nlist, d_counts, l.offs.get(), l.perm.get());
+    if (behind_csr) behind_csr->record(e->stream);
+    ivf_note_lists(e, l, n, nlist);
+    e->index.ivf = std::move(l);
 }
 
 // ---- k-means training (kmeans.hip.h) ----
@@ -251,49 +259,36 @@ void KmeansWork::alloc(size_t n_, size_t dim_, size_t nlist_, const float *rows_
 {
     n = n_; dim = dim_; nlist = nlist_; rows = rows_;
     nwg = (int)((n + KM_TR - 1) / KM_TR); nparts = (int)((n + KM_RB - 1) / KM_RB);
-    HIPCHK(hipMalloc(&cent, nlist * dim * sizeof(float)));
-    HIPCHK(hipMalloc(&assign[0], n * sizeof(int))); HIPCHK(hipMalloc(&assign[1], n * sizeof(int)));
-    HIPCHK(hipMalloc(&dist, n * sizeof(float)));
-    HIPCHK(hipMalloc(&moved_wg, (size_t)nwg * sizeof(int)));
-    HIPCHK(hipMalloc(&part, (size_t)nparts * sizeof(double)));
-    HIPCHK(hipMalloc(&obj, sizeof(double))); HIPCHK(hipMalloc(&moved, sizeof(long long)));
-    HIPCHK(hipMalloc(&counts, nlist * sizeof(int))); HIPCHK(hipMalloc(&offs, (nlist + 1) * sizeof(int))); HIPCHK(hipMalloc(&perm, n * sizeof(int)));
-    HIPCHK(hipEventCreate(&ev[0])); HIPCHK(hipEventCreate(&ev[1]));
-}
-KmeansWork::~KmeansWork()
-{
-    for (void *p : {(void *)cent, (void *)assign[0], (void *)assign[1], (void *)dist, (void *)moved_wg, (void *)part, (void *)obj, (void *)moved, (void *)counts, (void *)offs, (void *)perm})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
+    cent.alloc(nlist * dim); assign[0].alloc(n); assign[1].alloc(n); dist.alloc(n);
+    moved_wg.alloc((size_t)nwg); part.alloc((size_t)nparts); obj.alloc(1); moved.alloc(1);
+    counts.alloc(nlist); offs.alloc(nlist + 1); perm.alloc(n);
 }
 // one assign step against w.cent into w.assign[cur] / w.dist; prev: the assignment `moved` is counted against (null: every row counts).  Synchronises.
 void kmeans_assign_step(rvc_engine *e, KmeansWork &w, const int *prev, int cur, double *objective, long long *moved)
 {
-    KmeansAssignP ap{}; ap.index = w.rows ? w.rows : e->d_index; ap.n = (int)w.n; ap.dim = (int)w.dim; ap.cent = w.cent; ap.nlist = (int)w.nlist;
-    ap.prev = prev; ap.assign = w.assign[cur]; ap.dist = w.dist; ap.moved_wg = w.moved_wg;
-    HIPCHK(hipEventRecord(w.ev[0], e->stream));
+    KmeansAssignP ap{}; ap.index = w.rows ? w.rows : e->index.rows.get(); ap.n = (int)w.n; ap.dim = (int)w.dim; ap.cent = w.cent.get(); ap.nlist = (int)w.nlist;
+    ap.prev = prev; ap.assign = w.assign[cur].get(); ap.dist = w.dist.get(); ap.moved_wg = w.moved_wg.get();
+    w.step.start(e->stream);
     hipLaunchKernelGGL(kmeans_assign_kernel, dim3((unsigned)w.nwg), dim3(256), 0, e->stream, ap);
-    hipLaunchKernelGGL(kmeans_objective_kernel, dim3((unsigned)w.nparts), dim3(256), 0, e->stream, w.dist, (int)w.n, w.part);
-    hipLaunchKernelGGL(kmeans_objective_final_kernel, dim3(1), dim3(256), 0, e->stream, w.part, w.nparts, w.moved_wg, w.nwg, w.obj, w.moved);
-    HIPCHK(hipEventRecord(w.ev[1], e->stream));
+    hipLaunchKernelGGL(kmeans_objective_kernel, dim3((unsigned)w.nparts), dim3(256), 0, e->stream, w.dist.get(), (int)w.n, w.part.get());
+    hipLaunchKernelGGL(kmeans_objective_final_kernel, dim3(1), dim3(256), 0, e->stream, w.part.get(), w.nparts, w.moved_wg.get(), w.nwg, w.obj.get(), w.moved.get());
+    w.step.stop(e->stream);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(objective, w.obj, sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(moved, w.moved, sizeof(long long), hipMemcpyDeviceToHost));
-    float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    w.ms_assign += ms;
+    HIPCHK(hipMemcpy(objective, w.obj.get(), sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(moved, w.moved.get(), sizeof(long long), hipMemcpyDeviceToHost));
+    w.ms_assign += w.step.ms();
 }
 // one update step: the CSR of w.assign[cur], then the means into w.cent in place (a list reads rows and writes its own centroid only).  Synchronises.
 void kmeans_update_step(rvc_engine *e, KmeansWork &w, int cur)
 {
-    HIPCHK(hipEventRecord(w.ev[0], e->stream));
-    ivf_build_csr(e, w.assign[cur], w.n, w.nlist, w.counts, w.offs, w.perm);
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, w.rows ? w.rows : e->d_index, (int)w.dim, w.offs, w.perm, w.cent);
-    HIPCHK(hipEventRecord(w.ev[1], e->stream));
+    w.step.start(e->stream);
+    ivf_build_csr(e, w.assign[cur].get(), w.n, w.nlist, w.counts.get(), w.offs.get(), w.perm.get());
+    hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, w.rows ? w.rows : e->index.rows.get(), (int)w.dim, w.offs.get(), w.perm.get(), w.cent.get());
+    w.step.stop(e->stream);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
-    float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    w.ms_update += ms;
+    w.ms_update += w.step.ms();
 }
 
 // upstream's rule for IVF<n>,Flat: min(floor(16 sqrt(n)), n / 39), clamped to [1, 65536]
@@ -324,7 +319,7 @@ static std::vector<int32_t> kmeans_seeded_rows(size_t n, size_t nlist, uint32_t 
 static int kmeans_lloyd(rvc_engine *e, KmeansWork &w, const std::vector<int32_t> &init_rows, int *d_rows, int iters, std::vector<double> &obj, long long *moved, int *run)
 {
     HIPCHK(hipMemcpyAsync(d_rows, init_rows.data(), w.nlist * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(kmeans_gather_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, w.rows ? w.rows : e->d_index, (int)w.dim, d_rows, w.cent);
+    hipLaunchKernelGGL(kmeans_gather_kernel, dim3((unsigned)w.nlist), dim3(256), 0, e->stream, w.rows ? w.rows : e->index.rows.get(), (int)w.dim, d_rows, w.cent.get());
     obj.assign(1, 0.0);
     int cur = 0;
     *run = 0; *moved = 0;
@@ -332,36 +327,47 @@ static int kmeans_lloyd(rvc_engine *e, KmeansWork &w, const std::vector<int32_t>
     while (*run < iters && *moved != 0) {
         kmeans_update_step(e, w, cur);
         double j = 0.0;
-        kmeans_assign_step(e, w, w.assign[cur], cur ^ 1, &j, moved);
+        kmeans_assign_step(e, w, w.assign[cur].get(), cur ^ 1, &j, moved);
         obj.push_back(j); cur ^= 1; (*run)++;
     }
     return cur;
 }
 
-void build_index_aux(rvc_engine *e)
+// no index: the matrix, every layout and the IVF structure go, the search is flat, and no plan of the old index stays
+static void drop_index(rvc_engine *e)
 {
-    drop_index_ivf(e);          // a new index: the structure described the old rows, and the search is flat again
-    if (e->d_indexT) { (void)hipFree(e->d_indexT); e->d_indexT = nullptr; }
-    if (e->d_indexF) { (void)hipFree(e->d_indexF); e->d_indexF = nullptr; }
-    if (e->d_ynorm) (void)hipFree(e->d_ynorm);
-    if (e->d_nhn) (void)hipFree(e->d_nhn);
-    e->d_ynorm = e->d_nhn = nullptr;
-    hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-    HIPCHK(hipEventRecord(a, e->stream));
-    if (e->index_dim % 16 == 0) {
-        const long long nt = ((long long)e->index_n + 15) / 16, nc = (long long)e->index_dim / 16, total4 = nt * nc * 64;
-        HIPCHK(hipMalloc(&e->d_indexF, (size_t)total4 * 4 * sizeof(float)));
-        hipLaunchKernelGGL(knn_pack_index_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, e->stream, e->d_index, (long long)e->index_n, (int)e->index_dim, e->d_indexF, total4);
-    }
-    HIPCHK(hipMalloc(&e->d_ynorm, e->index_n * sizeof(float)));
-    HIPCHK(hipMalloc(&e->d_nhn, e->index_n * sizeof(float)));
-    hipLaunchKernelGGL(knn_norms_kernel, dim3((unsigned)((e->index_n + 255) / 256)), dim3(256), 0, e->stream, e->d_index, (int)e->index_n, (int)e->index_dim, e->d_ynorm, e->d_nhn);
-    HIPCHK(hipEventRecord(b, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipGetLastError());
-    float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, a, b));
-    e->index_prep_ms = ms;
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    e->index = RetrievalIndex(); e->index_nprobe = 0;
+    e->plans.clear(); e->last_plan = nullptr;
+}
+
+// The one way a matrix becomes the engine's index: rvc_load_index[_device], rvc_index_build_finish and rvc_index_broadcast all end here.  Everything the
+// retrieval kernels need besides the row-major matrix is built ON THE DEVICE from the copy that is already in HBM (uploaded once, handed over by a build, or
+// delivered by the RCCL broadcast): the MFMA-fragment-order copy for the one-pass approximate scan and the vector norms.  No host round trip (round 2 copied
+// the 307 MB matrix back to the host, repacked it in a single-threaded loop and uploaded two more copies: seconds per rank behind a 2 ms broadcast).  The
+// transposed copy is NOT built here: see ensure_index_transposed.
+// The contract: whatever refuses a call before it gets here (n < index_k, dim < 1, a finish refused by its checks, a broadcast refused in its agreement round)
+// leaves the old index in place.  From the first line of this function on the engine has either the new index complete -- flat search, no IVF structure, no
+// plan of the old one -- or, when a step throws, no index and no stale plans; never a mixture.  index_k and index_rate survive either way.
+void install_index(rvc_engine *e, DevBuf<float> rows, size_t n, size_t dim)
+{
+    drop_index(e);
+    RetrievalIndex &ix = e->index;
+    try {
+        ix.rows = std::move(rows);
+        DevTimer prep; prep.start(e->stream);
+        if (dim % 16 == 0) {
+            const long long nt = ((long long)n + 15) / 16, nc = (long long)dim / 16, total4 = nt * nc * 64;
+            ix.rowsF.alloc((size_t)total4 * 4);
+            hipLaunchKernelGGL(knn_pack_index_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, e->stream, ix.rows.get(), (long long)n, (int)dim, ix.rowsF.get(), total4);
+        }
+        ix.ynorm.alloc(n); ix.nhn.alloc(n);
+        hipLaunchKernelGGL(knn_norms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, ix.rows.get(), (int)n, (int)dim, ix.ynorm.get(), ix.nhn.get());
+        prep.stop(e->stream);
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipGetLastError());
+        ix.prep_ms = prep.ms();
+        ix.n = n; ix.dim = dim;
+    } catch (...) { ix = RetrievalIndex(); throw; }
 }
 
 // [dim][n] copy of the index, built by a device transpose the first time a plan needs it: the many-stream distance GEMM (the index is
@@ -369,10 +375,11 @@ void build_index_aux(rvc_engine *e)
 // row-major for the exact re-rank and the blend, fragment order for the scan); its degenerate-data fallback walks the row-major copy.
 void ensure_index_transposed(rvc_engine *e)
 {
-    if (e->d_indexT || !e->d_index) return;
-    HIPCHK(hipMalloc(&e->d_indexT, e->index_n * e->index_dim * sizeof(float)));
-    dim3 grid((unsigned)((e->index_n + 31) / 32), (unsigned)((e->index_dim + 31) / 32));
-    hipLaunchKernelGGL(knn_transpose_kernel, grid, dim3(256), 0, e->stream, e->d_index, (long long)e->index_n, (int)e->index_dim, e->d_indexT);
+    RetrievalIndex &ix = e->index;
+    if (ix.rowsT || !ix.rows) return;
+    ix.rowsT.alloc(ix.n * ix.dim);
+    dim3 grid((unsigned)((ix.n + 31) / 32), (unsigned)((ix.dim + 31) / 32));
+    hipLaunchKernelGGL(knn_transpose_kernel, grid, dim3(256), 0, e->stream, ix.rows.get(), (long long)ix.n, (int)ix.dim, ix.rowsT.get());
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
 }
@@ -381,17 +388,9 @@ void ensure_index_transposed(rvc_engine *e)
 void IndexBuild::alloc(size_t dim_, size_t capacity_)
 {
     dim = dim_; capacity = capacity_;
-    HIPCHK(hipMalloc(&store, capacity * dim * sizeof(float)));
-    HIPCHK(hipMalloc(&d_cnt, 2 * sizeof(int)));
-    HIPCHK(hipMemset(d_cnt, 0, 2 * sizeof(int)));
-}
-IndexBuild::~IndexBuild()
-{
-    for (void *p : retired) (void)hipFree(p);
-    if (store) (void)hipFree(store);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (d_bad) (void)hipFree(d_bad);
-    for (hipEvent_t v : ev) (void)hipEventDestroy(v);
+    store.alloc(capacity * dim);
+    d_cnt.alloc(2);
+    HIPCHK(hipMemset(d_cnt.get(), 0, 2 * sizeof(int)));
 }
 // room for `need` rows; `upper` = an upper bound of the rows the store holds (the device's own count is not known between the windows of an add)
 void index_build_reserve(rvc_engine *e, IndexBuild &b, size_t upper, size_t need)
@@ -399,30 +398,26 @@ void index_build_reserve(rvc_engine *e, IndexBuild &b, size_t upper, size_t need
     if (need > (size_t)0x7fffffff) throw ShapeError("index build: more than 2^31 - 1 rows");
     if (need <= b.capacity) return;
     const size_t cap = std::max(2 * b.capacity, need);
-    float *grown = nullptr;
-    HIPCHK(hipMalloc(&grown, cap * b.dim * sizeof(float)));
-    if (upper) {
-        const hipError_t rc = hipMemcpyAsync(grown, b.store, upper * b.dim * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
-        if (rc != hipSuccess) { (void)hipFree(grown); HIPCHK(rc); }
-    }
-    b.retired.push_back(b.store);      // (the copy above, and appends queued before it, still read it)
-    b.store = grown; b.capacity = cap;
+    DevBuf<float> grown; grown.alloc(cap * b.dim);
+    if (upper) HIPCHK(hipMemcpyAsync(grown.get(), b.store.get(), upper * b.dim * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    b.retired.emplace_back((char *)b.store.release());      // (the copy above, and appends queued before it, still read it)
+    b.store = std::move(grown); b.capacity = cap;
 }
 void index_build_append(rvc_engine *e, IndexBuild &b, const float *cv, int C, int T, int ld)
 {
     if ((size_t)C != b.dim || T < 1 || ld < T) throw ShapeError("index build: the window's feature matrix does not match the store");
     if ((size_t)T > b.bad_cap) {
-        if (b.d_bad) b.retired.push_back(b.d_bad);
-        b.d_bad = nullptr; b.bad_cap = 0;
+        if (b.d_bad) b.retired.emplace_back((char *)b.d_bad.release());
+        b.bad_cap = 0;
         const size_t cap = std::max((size_t)T, (size_t)1024);
-        HIPCHK(hipMalloc(&b.d_bad, cap * sizeof(int)));
+        b.d_bad.alloc(cap);
         b.bad_cap = cap;
-        HIPCHK(hipMemsetAsync(b.d_bad, 0, cap * sizeof(int), e->stream));
+        HIPCHK(hipMemsetAsync(b.d_bad.get(), 0, cap * sizeof(int), e->stream));
     }
-    IndexAppendP p{}; p.cv = cv; p.C = C; p.T = T; p.ld = ld; p.rows = b.store; p.capacity = (long long)b.capacity; p.cnt = b.d_cnt; p.bad = b.d_bad;
+    IndexAppendP p{}; p.cv = cv; p.C = C; p.T = T; p.ld = ld; p.rows = b.store.get(); p.capacity = (long long)b.capacity; p.cnt = b.d_cnt.get(); p.bad = b.d_bad.get();
     dim3 grid((unsigned)((T + IB_TILE - 1) / IB_TILE), (unsigned)((C + IB_TILE - 1) / IB_TILE));
     hipLaunchKernelGGL(index_append_kernel, grid, dim3(256), 0, e->stream, p);
-    hipLaunchKernelGGL(index_compact_kernel, dim3(1), dim3(256), 0, e->stream, b.store, C, (long long)b.capacity, b.d_bad, T, b.d_cnt);
+    hipLaunchKernelGGL(index_compact_kernel, dim3(1), dim3(256), 0, e->stream, b.store.get(), C, (long long)b.capacity, b.d_bad.get(), T, b.d_cnt.get());
 }
 void index_build_abort(rvc_engine *e)
 {
@@ -433,8 +428,8 @@ void index_build_abort(rvc_engine *e)
 }
 static hipEvent_t ib_event(IndexBuild &b, size_t i)
 {
-    while (b.ev.size() <= i) { hipEvent_t v; HIPCHK(hipEventCreate(&v)); b.ev.push_back(v); }
-    return b.ev[i];
+    if (b.ev.size() <= i) b.ev.resize(i + 1);
+    return b.ev[i].get();
 }
 // One recording: consecutive windows, the tail at its own length when ContentVec yields a frame for it.  Per run: the samples into the plan's input, the plan,
 // the append.  One synchronisation and one read of the device counters at the end.
@@ -466,21 +461,19 @@ static rvc_status index_build_add(rvc_engine *e, const void *pcm, size_t n, bool
     } catch (...) {
         // what was queued still runs: bring the host's view up to date before the error leaves
         int cnt[2] = {0, 0};
-        if (hipStreamSynchronize(e->stream) == hipSuccess && hipMemcpy(cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost) == hipSuccess) { b.rows = (size_t)cnt[0]; b.dropped = (size_t)cnt[1]; }
-        for (void *p : b.retired) (void)hipFree(p);
+        if (hipStreamSynchronize(e->stream) == hipSuccess && hipMemcpy(cnt, b.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost) == hipSuccess) { b.rows = (size_t)cnt[0]; b.dropped = (size_t)cnt[1]; }
         b.retired.clear();
         throw;
     }
     int cnt[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(cnt, b.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
-    for (void *p : b.retired) (void)hipFree(p);
     b.retired.clear();
     for (size_t w = 0; w < runs; w++) {
         float a = 0.f, c = 0.f;
-        HIPCHK(hipEventElapsedTime(&a, b.ev[3 * w], b.ev[3 * w + 1]));
-        HIPCHK(hipEventElapsedTime(&c, b.ev[3 * w + 1], b.ev[3 * w + 2]));
+        HIPCHK(hipEventElapsedTime(&a, b.ev[3 * w].get(), b.ev[3 * w + 1].get()));
+        HIPCHK(hipEventElapsedTime(&c, b.ev[3 * w + 1].get(), b.ev[3 * w + 2].get()));
         b.ms[0] += a; b.ms[1] += c;
     }
     if ((size_t)cnt[0] + (size_t)(cnt[1] - (int)b.dropped) != upper) throw std::runtime_error("index build: the device-side row count does not add up");
@@ -505,43 +498,30 @@ void retrieval_kernel_attrs()
 using namespace rvc;
 extern "C" {
 
-rvc_status rvc_load_index(rvc_engine *e, const float *vectors, size_t n, size_t dim)
+// rvc_load_index / rvc_load_index_device: the old index goes before the new matrix is allocated (HBM never holds two matrices), so a failure behind the
+// argument checks leaves no index
+static rvc_status load_index(rvc_engine *e, const void *vectors, size_t n, size_t dim, hipMemcpyKind kind)
 {
     return guarded(e, [&]() {
         if (n < (size_t)e->index_k || dim < 1) throw ShapeError("index needs at least " + std::to_string(e->index_k) + " vectors");
         HIPCHK(hipDeviceSynchronize());
-        if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
-        HIPCHK(hipMalloc(&e->d_index, n * dim * sizeof(float)));
-        e->index_owned = true;
-        HIPCHK(hipMemcpy(e->d_index, vectors, n * dim * sizeof(float), hipMemcpyHostToDevice));
-        e->index_n = n; e->index_dim = dim;
-        build_index_aux(e);
-        e->plans.clear(); e->last_plan = nullptr;
+        drop_index(e);
+        DevBuf<float> rows; rows.alloc(n * dim);
+        HIPCHK(hipMemcpy(rows.get(), vectors, n * dim * sizeof(float), kind));
+        install_index(e, std::move(rows), n, dim);
         return RVC_OK;
     });
 }
 
-rvc_status rvc_load_index_device(rvc_engine *e, const void *d_vectors, size_t n, size_t dim)
-{
-    return guarded(e, [&]() {
-        if (n < (size_t)e->index_k || dim < 1) throw ShapeError("index needs at least " + std::to_string(e->index_k) + " vectors");
-        HIPCHK(hipDeviceSynchronize());
-        if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
-        HIPCHK(hipMalloc(&e->d_index, n * dim * sizeof(float)));
-        e->index_owned = true;
-        HIPCHK(hipMemcpy(e->d_index, d_vectors, n * dim * sizeof(float), hipMemcpyDeviceToDevice));
-        e->index_n = n; e->index_dim = dim;
-        build_index_aux(e);
-        e->plans.clear(); e->last_plan = nullptr;
-        return RVC_OK;
-    });
-}
+rvc_status rvc_load_index(rvc_engine *e, const float *vectors, size_t n, size_t dim) { return load_index(e, vectors, n, dim, hipMemcpyHostToDevice); }
+
+rvc_status rvc_load_index_device(rvc_engine *e, const void *d_vectors, size_t n, size_t dim) { return load_index(e, d_vectors, n, dim, hipMemcpyDeviceToDevice); }
 
 void *rvc_index_device_ptr(rvc_engine *e, size_t *bytes)
 {
-    if (!e || !e->d_index) { if (bytes) *bytes = 0; return nullptr; }
-    if (bytes) *bytes = e->index_n * e->index_dim * sizeof(float);
-    return e->d_index;
+    if (!e || !e->index.rows) { if (bytes) *bytes = 0; return nullptr; }
+    if (bytes) *bytes = e->index.n * e->index.dim * sizeof(float);
+    return e->index.rows.get();
 }
 
 rvc_status rvc_get_knn(rvc_engine *e, int32_t *idx, float *dist, size_t cap_rows, size_t *rows)
@@ -566,33 +546,19 @@ rvc_status rvc_get_knn(rvc_engine *e, int32_t *idx, float *dist, size_t cap_rows
 rvc_status rvc_set_index_ivf(rvc_engine *e, const float *centroids, size_t nlist, size_t dim, const int32_t *assign, size_t n)
 {
     return guarded(e, [&]() {
-        if (!e->d_index) throw ShapeError("no index loaded");
+        if (!e->index.rows) throw ShapeError("no index loaded");
         if (!centroids || !assign) throw ShapeError("IVF structure: null centroids or assignment");
-        if (dim != e->index_dim || n != e->index_n) throw ShapeError("IVF structure does not match the loaded index (dim or n)");
+        if (dim != e->index.dim || n != e->index.n) throw ShapeError("IVF structure does not match the loaded index (dim or n)");
         if (nlist < 1 || nlist > IVF_MAX_NLIST) throw ShapeError("IVF structure: nlist must be in [1, 65536]");
         for (size_t i = 0; i < n; i++) if (assign[i] < 0 || (size_t)assign[i] >= nlist) throw ShapeError("IVF structure: an assignment is outside [0, nlist)");
         for (size_t i = 0; i < nlist * dim; i++) if (!std::isfinite(centroids[i])) throw ShapeError("IVF structure: a centroid is not finite");
         HIPCHK(hipDeviceSynchronize());
         drop_index_ivf(e);
-        e->plans.clear(); e->last_plan = nullptr;
-        int *d_assign = nullptr, *d_counts = nullptr;
-        try {
-            HIPCHK(hipMalloc(&e->d_ivf_cent, nlist * dim * sizeof(float)));
-            HIPCHK(hipMalloc(&e->d_ivf_offs, (nlist + 1) * sizeof(int)));
-            HIPCHK(hipMalloc(&e->d_ivf_perm, n * sizeof(int)));
-            HIPCHK(hipMalloc(&d_assign, n * sizeof(int)));
-            HIPCHK(hipMalloc(&d_counts, nlist * sizeof(int)));
-            HIPCHK(hipMemcpy(e->d_ivf_cent, centroids, nlist * dim * sizeof(float), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d_assign, assign, n * sizeof(int), hipMemcpyHostToDevice));
-            ivf_build_csr(e, d_assign, n, nlist, d_counts, e->d_ivf_offs, e->d_ivf_perm);
-            ivf_note_lists(e, n, nlist);
-        } catch (...) {
-            if (d_assign) (void)hipFree(d_assign);
-            if (d_counts) (void)hipFree(d_counts);
-            drop_index_ivf(e);
-            throw;
-        }
-        (void)hipFree(d_assign); (void)hipFree(d_counts);
+        DevBuf<float> cent; DevBuf<int> d_assign, d_counts;
+        cent.alloc(nlist * dim); d_assign.alloc(n); d_counts.alloc(nlist);
+        HIPCHK(hipMemcpy(cent.get(), centroids, nlist * dim * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_assign.get(), assign, n * sizeof(int), hipMemcpyHostToDevice));
+        attach_ivf(e, std::move(cent), d_assign.get(), d_counts.get(), nlist);
         return RVC_OK;
     });
 }
@@ -602,8 +568,8 @@ rvc_status rvc_set_index_ivf(rvc_engine *e, const float *centroids, size_t nlist
 rvc_status rvc_train_index_ivf(rvc_engine *e, size_t nlist, int iters, const int32_t *init_rows, uint32_t seed)
 {
     return guarded(e, [&]() {
-        if (!e->d_index) throw ShapeError("no index loaded");
-        const size_t n = e->index_n, dim = e->index_dim;
+        if (!e->index.rows) throw ShapeError("no index loaded");
+        const size_t n = e->index.n, dim = e->index.dim;
         if (nlist == 0) nlist = kmeans_default_nlist(n);
         if (nlist > n || nlist > IVF_MAX_NLIST) throw ShapeError("k-means: nlist must be at most the number of rows and at most 65536");
         if (iters < 0 || iters > 100) throw ShapeError("k-means: iters must be in [0, 100]");
@@ -618,45 +584,28 @@ rvc_status rvc_train_index_ivf(rvc_engine *e, size_t nlist, int iters, const int
             }
         } else rows = kmeans_seeded_rows(n, nlist, seed);
         HIPCHK(hipDeviceSynchronize());
-        int *d_rows = nullptr;                                               // (also the word the non-finite search answers in)
-        HIPCHK(hipMalloc(&d_rows, std::max(nlist, (size_t)1) * sizeof(int)));
-        struct Free { int *p; ~Free() { (void)hipFree(p); } } free_rows{d_rows};
+        DevBuf<int> d_rows;                                                  // (also the word the non-finite search answers in)
+        d_rows.alloc(std::max(nlist, (size_t)1));
         int first = 0x7fffffff;
-        HIPCHK(hipMemcpy(d_rows, &first, sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(kmeans_nonfinite_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->d_index, e->d_ynorm, (int)n, (int)dim, d_rows);
+        HIPCHK(hipMemcpy(d_rows.get(), &first, sizeof(int), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(kmeans_nonfinite_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->index.rows.get(), e->index.ynorm.get(), (int)n, (int)dim, d_rows.get());
         HIPCHK(hipStreamSynchronize(e->stream));
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(&first, d_rows, sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&first, d_rows.get(), sizeof(int), hipMemcpyDeviceToHost));
         if (first != 0x7fffffff) throw ShapeError("k-means: row " + std::to_string(first) + " of the index holds a NaN or an Inf");
         // ---- from here on the old structure is gone ----
         drop_index_ivf(e);
-        e->plans.clear(); e->last_plan = nullptr;
         e->km_valid = false;
-        try {
-            KmeansWork w;
-            w.alloc(n, dim, nlist);
-            hipEvent_t t0, t1; HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1));
-            struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evs{t0, t1};
-            HIPCHK(hipEventRecord(t0, e->stream));
-            std::vector<double> obj;
-            long long moved = 0;
-            int run = 0;
-            const int cur = kmeans_lloyd(e, w, rows, d_rows, iters, obj, &moved, &run);
-            // attach: the centroids as they are, the CSR of the last assign step into arrays the engine keeps
-            HIPCHK(hipMalloc(&e->d_ivf_offs, (nlist + 1) * sizeof(int)));
-            HIPCHK(hipMalloc(&e->d_ivf_perm, n * sizeof(int)));
-            ivf_build_csr(e, w.assign[cur], n, nlist, w.counts, e->d_ivf_offs, e->d_ivf_perm);
-            HIPCHK(hipEventRecord(t1, e->stream));
-            e->d_ivf_cent = w.cent; w.cent = nullptr;
-            ivf_note_lists(e, n, nlist);
-            float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, t0, t1));
-            e->km_iters_run = run; e->km_moved_last = (size_t)moved; e->km_obj = obj;
-            e->km_ms[0] = w.ms_assign; e->km_ms[1] = w.ms_update; e->km_ms[2] = ms;
-            e->km_valid = true;
-        } catch (...) {
-            drop_index_ivf(e);
-            throw;
-        }
+        KmeansWork w;
+        w.alloc(n, dim, nlist);
+        DevTimer total; total.start(e->stream);
+        std::vector<double> obj; long long moved = 0; int run = 0;
+        const int cur = kmeans_lloyd(e, w, rows, d_rows.get(), iters, obj, &moved, &run);
+        // attach: the centroids as they are, the CSR of the last assign step
+        attach_ivf(e, std::move(w.cent), w.assign[cur].get(), w.counts.get(), nlist, &total.b);
+        e->km_iters_run = run; e->km_moved_last = (size_t)moved; e->km_obj = obj;
+        e->km_ms[0] = w.ms_assign; e->km_ms[1] = w.ms_update; e->km_ms[2] = total.ms();
+        e->km_valid = true;
         return RVC_OK;
     });
 }
@@ -678,14 +627,14 @@ rvc_status rvc_index_ivf_train_info(rvc_engine *e, int *iters_run, size_t *moved
 rvc_status rvc_get_index_ivf(rvc_engine *e, float *centroids, size_t cap_centroid_floats, int32_t *assign, size_t cap_rows)
 {
     return guarded(e, [&]() {
-        if (!e->d_ivf_cent) throw ShapeError("no IVF structure attached to the index");
-        const size_t nlist = e->ivf_nlist, n = e->index_n, dim = e->index_dim;
+        if (!e->index.ivf.cent) throw ShapeError("no IVF structure attached to the index");
+        const size_t nlist = e->index.ivf.nlist, n = e->index.n, dim = e->index.dim;
         if (!centroids || !assign || cap_centroid_floats < nlist * dim || cap_rows < n) throw ShapeError("IVF structure: the caller's arrays are too short");
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(centroids, e->d_ivf_cent, nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(centroids, e->index.ivf.cent.get(), nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
         std::vector<int> offs(nlist + 1), perm(n);
-        HIPCHK(hipMemcpy(offs.data(), e->d_ivf_offs, offs.size() * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(perm.data(), e->d_ivf_perm, n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(offs.data(), e->index.ivf.offs.get(), offs.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(perm.data(), e->index.ivf.perm.get(), n * sizeof(int), hipMemcpyDeviceToHost));
         for (size_t l = 0; l < nlist; l++)
             for (int q = offs[l]; q < offs[l + 1]; q++) assign[perm[q]] = (int32_t)l;
         return RVC_OK;
@@ -695,10 +644,10 @@ rvc_status rvc_get_index_ivf(rvc_engine *e, float *centroids, size_t cap_centroi
 rvc_status rvc_set_index_nprobe(rvc_engine *e, int nprobe)
 {
     return guarded(e, [&]() {
-        if (!e->d_index) throw ShapeError("no index loaded");
+        if (!e->index.rows) throw ShapeError("no index loaded");
         if (nprobe < 0 || nprobe > IVF_MAX_NPROBE) throw ShapeError("nprobe must be in [0, 64]");
-        if (nprobe >= 1 && !e->d_ivf_cent) throw ShapeError("nprobe >= 1 needs an IVF structure (rvc_set_index_ivf)");
-        e->index_nprobe = nprobe >= 1 ? (int)std::min((size_t)nprobe, e->ivf_nlist) : 0;
+        if (nprobe >= 1 && !e->index.ivf.cent) throw ShapeError("nprobe >= 1 needs an IVF structure (rvc_set_index_ivf)");
+        e->index_nprobe = nprobe >= 1 ? (int)std::min((size_t)nprobe, e->index.ivf.nlist) : 0;
         return RVC_OK;
     });
 }
@@ -711,7 +660,7 @@ rvc_status rvc_set_index_k(rvc_engine *e, int k)
 {
     return guarded(e, [&]() {
         if (k != KNN_K && k != KNN_KMAX) throw ShapeError("k must be 4 or 8");
-        if (e->d_index && e->index_n < (size_t)k) throw ShapeError("the loaded index has fewer than " + std::to_string(k) + " vectors");
+        if (e->index.rows && e->index.n < (size_t)k) throw ShapeError("the loaded index has fewer than " + std::to_string(k) + " vectors");
         e->index_k = k;
         return RVC_OK;
     });
@@ -722,10 +671,10 @@ int rvc_index_k(rvc_engine *e) { return e ? e->index_k : KNN_K; }
 rvc_status rvc_index_ivf_info(rvc_engine *e, size_t *nlist, size_t *longest_list, size_t *empty_lists)
 {
     return guarded(e, [&]() {
-        if (!e->d_ivf_cent) throw ShapeError("no IVF structure attached to the index");
-        if (nlist) *nlist = e->ivf_nlist;
-        if (longest_list) *longest_list = e->ivf_longest;
-        if (empty_lists) *empty_lists = e->ivf_empty;
+        if (!e->index.ivf.cent) throw ShapeError("no IVF structure attached to the index");
+        if (nlist) *nlist = e->index.ivf.nlist;
+        if (longest_list) *longest_list = e->index.ivf.longest;
+        if (empty_lists) *empty_lists = e->index.ivf.empty;
         return RVC_OK;
     });
 }
@@ -787,35 +736,28 @@ rvc_status rvc_index_build_finish(rvc_engine *e, size_t max_rows, size_t reduce_
         const size_t n = reduce ? reduce_to : rows;
         if (n < (size_t)e->index_k) throw ShapeError("index needs at least " + std::to_string(e->index_k) + " vectors (the build would install " + std::to_string(n) + ")");
         HIPCHK(hipDeviceSynchronize());
-        float *installed = nullptr;
+        DevBuf<float> installed;
         if (reduce) {
             // the trainer of rvc_train_index_ivf on the store's pointer: same seeded sample, same steps, same early stop.  The centroid table is an allocation
             // of exactly [reduce_to][dim] in centre order: it becomes the index as it is (no copy into the store's head), and the store is freed.
             const std::vector<int32_t> init = kmeans_seeded_rows(rows, reduce_to, seed);
-            int *d_rows = nullptr;
-            HIPCHK(hipMalloc(&d_rows, reduce_to * sizeof(int)));
-            struct Free { int *p; ~Free() { (void)hipFree(p); } } free_rows{d_rows};
+            DevBuf<int> d_rows; d_rows.alloc(reduce_to);
             KmeansWork w;
-            w.alloc(rows, dim, reduce_to, b.store);
+            w.alloc(rows, dim, reduce_to, b.store.get());
             std::vector<double> obj; long long moved = 0; int run = 0;
-            (void)kmeans_lloyd(e, w, init, d_rows, iters, obj, &moved, &run);
+            (void)kmeans_lloyd(e, w, init, d_rows.get(), iters, obj, &moved, &run);
             b.ms[2] += w.ms_assign + w.ms_update;
-            installed = w.cent; w.cent = nullptr;
+            installed = std::move(w.cent);
         } else if (b.capacity - rows > rows / 4) {
             // the store was grown by doubling: more than a quarter of slack is not worth keeping for the index's life
-            HIPCHK(hipMalloc(&installed, rows * dim * sizeof(float)));
-            const hipError_t rc = hipMemcpy(installed, b.store, rows * dim * sizeof(float), hipMemcpyDeviceToDevice);
-            if (rc != hipSuccess) { (void)hipFree(installed); HIPCHK(rc); }
+            installed.alloc(rows * dim);
+            HIPCHK(hipMemcpy(installed.get(), b.store.get(), rows * dim * sizeof(float), hipMemcpyDeviceToDevice));
         } else {
-            installed = b.store; b.store = nullptr;             // handed over without a copy
+            installed = std::move(b.store);                     // handed over without a copy
         }
-        // installed as rvc_load_index_device installs a matrix: auxiliary layouts rebuilt, the IVF structure dropped (build_index_aux), plans cleared
+        // installed as rvc_load_index_device installs a matrix
         delete e->ib; e->ib = nullptr;
-        if (e->d_index && e->index_owned) (void)hipFree(e->d_index);
-        e->d_index = installed; e->index_owned = true;
-        e->index_n = n; e->index_dim = dim;
-        build_index_aux(e);
-        e->plans.clear(); e->last_plan = nullptr;
+        install_index(e, std::move(installed), n, dim);
         return RVC_OK;
     });
 }

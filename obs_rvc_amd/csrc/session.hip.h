@@ -310,7 +310,7 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
             // (only plans that CAN be recovered pay for that -- the one-launch retrieval of up to 11 streams, whose plan carries the fallback launches;
             //  many-stream plans search through the distance GEMM and hand nothing over inside a launch: their chain stays asynchronous)
             bool sync_infer = false;
-            if (e->d_index && e->index_rate > 0.f) {
+            if (e->index.rows && e->index_rate > 0.f) {
                 // (the plan infer_common will run: its formant key; streams in several formant buckets run synchronously anyway)
                 uint32_t r2 = 0; bool fstage = false;
                 if (formant_key(e, (uint32_t)s->model_return_length, nullptr, &r2, &fstage)) {
