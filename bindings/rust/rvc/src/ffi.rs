@@ -89,6 +89,18 @@ extern "C" {
     pub fn rvc_index_build_info(e: *mut RvcEngine, rows: *mut usize, capacity: *mut usize, windows: *mut usize, dropped_nonfinite: *mut usize, ms: *mut f64) -> c_int;
     pub fn rvc_index_build_finish(e: *mut RvcEngine, max_rows: usize, reduce_to: usize, iters: c_int, seed: u32) -> c_int;
     pub fn rvc_index_build_abort(e: *mut RvcEngine);
+    // whole-recording conversion: windows of one geometry through the batched infer path, SOLA-stitched on the device (k, context, crossfade: 0 = 14 / 48 / 5
+    // frames); geometry out[8] = {windows, n, sample_frame_16k_size, skip_head, return_length, hop, zc, output samples}; info ms[4] = {high-pass, gather + model,
+    // stitch, total}
+    pub fn rvc_convert_geometry(n16k: usize, sample_rate: usize, k: usize, context: usize, crossfade: usize, out: *mut usize) -> c_int;
+    pub fn rvc_convert(e: *mut RvcEngine, pcm16k: *const c_float, n: usize, k: usize, context: usize, crossfade: usize, pitch_shift: i32, highpass: c_int,
+                       out: *mut c_float, cap: usize, out_len: *mut usize) -> c_int;
+    pub fn rvc_convert_device(e: *mut RvcEngine, d_pcm16k: *const c_void, n: usize, k: usize, context: usize, crossfade: usize, pitch_shift: i32, highpass: c_int,
+                              d_out: *mut c_void, cap: usize, out_len: *mut usize) -> c_int;
+    pub fn rvc_convert_info(e: *mut RvcEngine, windows: *mut usize, batches: *mut usize, offsets: *mut i32, cap_offsets: usize, ms: *mut f64) -> c_int;
+    pub fn rvc_sola_stitch(e: *mut RvcEngine, windows: *const c_float, n_windows: usize, window_len: usize, sola_len: usize, search: usize, frame: usize,
+                           out: *mut c_float, offsets: *mut i32) -> c_int;
+    pub fn rvc_highpass(e: *mut RvcEngine, pcm16k: *const c_float, n: usize, out: *mut c_float) -> c_int;
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 

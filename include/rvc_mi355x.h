@@ -386,6 +386,42 @@ rvc_status rvc_session_set_noise_reduction_stream(rvc_session *s, int stream, in
 void rvc_session_geometry(rvc_session *s, int32_t out[10]);   /* the derived sizes of lib.rs:200-227 (see session.hip.h) */
 rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t n, float *output, size_t cap, size_t *sola_offset);
 
+/* ---- conversion of a whole recording (upstream's "model inference" tab, vc_single) ---- */
+/* A 16 kHz signal of any length -> the voice's audio at the model's rate.  The recording is cut into windows of ONE geometry, so one plan serves the whole
+ * file; the windows run S = rvc_set_streams at a time through the batched infer path (window w = i S + s on stream s in batch i) and are stitched on the
+ * device by the plugin's SOLA step in its LINEAR crossfade, chained over the windows.  In frames of 10 ms (160 samples at 16 kHz, zc = rate / 100 at the
+ * model's rate), with k the window size in [2, 32], C the context on each side, >= 3, X the crossfade, >= 1, Q = 1 the SOLA search; 0 selects k = 14,
+ * C = 48, X = 5 (14: the longest window whose return_length, 351 with C = 48, the synthesizer's LDS-resident attention takes at RVC's head size; a longer
+ * one fails at the plan build with that kernel's message):
+ *   F = 32 k - 1 frames per window, n = 160 F samples, sample_frame_16k_size = 5120 (k - 1), skip_head = C, hop H = F - 2 C - X - Q (H >= X),
+ *   return_length = H + X + Q;   Nf = ceil(N / 160), W = ceil(Nf / H) windows, window w = samples [160 (w H - C), + n), zero outside [0, N).
+ * A short last batch is padded with all-zero windows whose outputs are dropped.  Stitch: sola_len = X zc, search = Q zc, frame = H zc, the tail starts as
+ * zeros; the output is the W frames in order, cut to Nf zc samples.  With C >= 3 every pitch row a window uses is computed from that window alone.
+ * The call BEGINS WITH WHAT rvc_reset_state DOES (pitch caches and chunk counters zeroed): the result depends on the recording and the settings, not on what
+ * the engine ran before.  Every batch is one batched infer call with the integer pitch_shift (whole octaves, as everywhere): every per-stream setting
+ * (formant shift, pitch controls, protect, noise seeds), the index (rate, k, nprobe), the f0 method and graph replay apply as to any infer call;
+ * rvc_set_pipeline is ignored.  highpass != 0 (upstream filters every file it converts): the 48 Hz high-pass of rvc_highpass in front.
+ * RVC_MODEL_NOT_LOADED / RVC_CONTENTVEC_NOT_LOADED / RVC_F0_NOT_LOADED as for rvc_infer, before any argument is looked at.  RVC_SHAPE with a message: n = 0; a
+ * synthesizer whose rate is not a multiple of 100; k, C or X out of range; H < X; Q zc > 1023 (the SOLA kernels' limit); cap short (*out_len is written). */
+/* host only, pure: out = {windows, n, sample_frame_16k_size, skip_head, return_length, hop, zc, output samples} */
+rvc_status rvc_convert_geometry(size_t n16k, size_t sample_rate, size_t k, size_t context, size_t crossfade, size_t out[8]);
+rvc_status rvc_convert(rvc_engine *e, const float *pcm16k, size_t n, size_t k, size_t context, size_t crossfade, int32_t pitch_shift,
+                       int highpass, float *out, size_t cap, size_t *out_len);
+/* device-resident variant (HIP device pointers on the engine's device); returns synchronised */
+rvc_status rvc_convert_device(rvc_engine *e, const void *d_pcm16k, size_t n, size_t k, size_t context, size_t crossfade, int32_t pitch_shift,
+                              int highpass, void *d_out, size_t cap, size_t *out_len);
+/* of the last completed convert: windows, batches, the SOLA offset of every window (the first cap_offsets of them), device ms = {high-pass, gather + model,
+   stitch, total}; any pointer may be NULL.  RVC_SHAPE before one has completed */
+rvc_status rvc_convert_info(rvc_engine *e, size_t *windows, size_t *batches, int32_t *offsets, size_t cap_offsets, double ms[4]);
+/* the chained LINEAR rvc_sola_step over windows [n_windows][window_len], tail = zeros at the start: out [n_windows][frame], offsets [n_windows] (may be NULL);
+   offsets and samples are rvc_sola_step's, bit for bit.  frame >= sola_len >= 1, search <= 1023, window_len >= search + frame + sola_len, else RVC_SHAPE */
+rvc_status rvc_sola_stitch(rvc_engine *e, const float *windows, size_t n_windows, size_t window_len, size_t sola_len, size_t search, size_t frame,
+                           float *out, int32_t *offsets);
+/* 48 Hz zero-phase high-pass at 16 kHz, a direct FIR of 2 M + 1 taps, M = 1024, over the zero-extended signal; out [n].  In fp64, rounded once to fp32:
+   lp[j] = 2 fc sinc(2 fc (j - M)) (0.42 - 0.5 cos(2 pi j / 2M) + 0.08 cos(4 pi j / 2M)), fc = 48 / 16000, scaled to sum 1; h = delta[j - M] - lp;
+   y[i] = sum_j h[j] x[i + M - j], accumulated in fp32 in the order j = 0 .. 2M.  n = 0: RVC_SHAPE */
+rvc_status rvc_highpass(rvc_engine *e, const float *pcm16k, size_t n, float *out);
+
 /* ---- what THIS GPU sustains, measured in-run (bench.py; boxes of one pool differ by ~10 % on matrix-core-bound work) ---- */
 /* rvc_calibrate: ~50 ms of device time.  A bare v_mfma_f32_32x32x2_f32 stream on every SIMD (four waves per SIMD, non-zero operands) -> fp32 matrix-core
  * TFLOP/s actually reached and the shader clock it ran at (s_memtime cycles per s_memrealtime tick); a float4 read stream over 1 GiB -> HBM TB/s. */

@@ -38,6 +38,7 @@ SYMBOLS = [
     "rvc_train_index_ivf", "rvc_index_ivf_train_info", "rvc_get_index_ivf",
     "rvc_set_index_k", "rvc_index_k",
     "rvc_index_build_begin", "rvc_index_build_add", "rvc_index_build_add_device", "rvc_index_build_info", "rvc_index_build_finish", "rvc_index_build_abort",
+    "rvc_convert_geometry", "rvc_convert", "rvc_convert_device", "rvc_convert_info", "rvc_sola_stitch", "rvc_highpass",
 ]
 
 
@@ -247,6 +248,13 @@ def lib():
         L.rvc_index_build_finish.argtypes = [vp, sz, sz, C.c_int, u32]
         L.rvc_index_build_abort.argtypes = [vp]
         L.rvc_index_build_abort.restype = None
+    if hasattr(L, "rvc_convert") or not override:
+        L.rvc_convert_geometry.argtypes = [sz, sz, sz, sz, sz, C.POINTER(sz)]
+        L.rvc_convert.argtypes = [vp, fp, sz, sz, sz, sz, i32, C.c_int, fp, sz, C.POINTER(sz)]
+        L.rvc_convert_device.argtypes = [vp, vp, sz, sz, sz, sz, i32, C.c_int, vp, sz, C.POINTER(sz)]
+        L.rvc_convert_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(i32), sz, C.POINTER(C.c_double)]
+        L.rvc_sola_stitch.argtypes = [vp, fp, sz, sz, sz, sz, sz, fp, C.POINTER(i32)]
+        L.rvc_highpass.argtypes = [vp, fp, sz, fp]
     L.rvc_set_noise_seed.argtypes = [vp, u32, u32]
     L.rvc_set_noise_seed.restype = None
     L.rvc_reset_state.argtypes = [vp]

@@ -1,0 +1,127 @@
+"""python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin] [--index I --index-rate r --index-k 4|8 --nprobe p]
+       [--pitch semitones] [--formant st] [--protect p] [--streams S] [--window k --context C --crossfade X] [--no-highpass] [--rate out_rate]
+
+Upstream's "model inference" tab with this engine: a WAV file through RvcInfer.convert -- windows of one geometry run `--streams` at a
+time through the batched infer path and are SOLA-stitched on the GPU -- and the result written as 16-bit PCM.  The WAV file is read with
+build_index.read_wav and written with the standard library; like upstream the output is divided by peak / 0.99 when its peak exceeds 1.  Argument parsing and
+WAV writing are plain functions; only main() touches the GPU."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import wave
+
+import numpy as np
+
+from .build_index import read_wav
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(prog="python -m obs_rvc_amd.convert", description="convert a WAV recording to a voice on the GPU")
+    p.add_argument("input", help="the WAV file to convert (16-bit or 32-bit integer PCM, mono or stereo)")
+    p.add_argument("-o", "--output", required=True, help="the WAV file to write (16-bit PCM, mono)")
+    p.add_argument("--model", required=True, help="the voice: <model>.rvcw (or its .onnx sibling's name)")
+    p.add_argument("--data", default=None, help="the engine's data directory (contentvec/, f0/); default: the model zoo of the package")
+    p.add_argument("--version", type=int, choices=(1, 2), default=2, help="RVC model version: 1 = 256-dim features, 2 = 768-dim (default)")
+    p.add_argument("--f0", choices=("rmvpe", "yin"), default="rmvpe", help="f0 method (default rmvpe)")
+    p.add_argument("--index", default=None, help="retrieval index: a Faiss .index file or a .npy matrix")
+    p.add_argument("--index-rate", type=float, default=0.75, help="share of the retrieved features (default 0.75, with --index only)")
+    p.add_argument("--index-k", type=int, choices=(4, 8), default=8, help="neighbours blended per frame (default 8, upstream's)")
+    p.add_argument("--nprobe", type=int, default=0, help="IVF lists probed per frame; 0 = search every row (default)")
+    p.add_argument("--pitch", type=float, default=0.0, help="transpose in semitones, -24..24 (default 0)")
+    p.add_argument("--formant", type=float, default=0.0, help="formant shift in semitones, -5..5 (default 0)")
+    p.add_argument("--protect", type=float, default=0.5, help="consonant protection, 0..0.5; 0.5 = off (default)")
+    p.add_argument("--streams", type=int, default=8, help="windows converted at a time (default 8)")
+    p.add_argument("--window", type=int, default=0, help="window size k: a window is 32 k - 1 frames of 10 ms; 2..32 (default 14)")
+    p.add_argument("--context", type=int, default=0, help="context frames on each side of a window, >= 3 (default 48)")
+    p.add_argument("--crossfade", type=int, default=0, help="crossfade frames between windows, >= 1 (default 5)")
+    p.add_argument("--no-highpass", dest="highpass", action="store_false", help="skip the 48 Hz high-pass in front of the model")
+    p.add_argument("--rate", type=int, default=0, help="output sample rate (default: the model's)")
+    p.add_argument("--device", type=int, default=-1)
+    a = p.parse_args(argv)
+    if not -24.0 <= a.pitch <= 24.0:
+        p.error("--pitch is -24..24 semitones")
+    if not -5.0 <= a.formant <= 5.0:
+        p.error("--formant is -5..5 semitones")
+    if not 0.0 <= a.protect <= 0.5:
+        p.error("--protect is 0..0.5")
+    if not 0.0 <= a.index_rate <= 1.0:
+        p.error("--index-rate is 0..1")
+    if not 1 <= a.streams <= 4096:
+        p.error("--streams is 1..4096")
+    if not 0 <= a.nprobe <= 64:
+        p.error("--nprobe is 0..64")
+    if a.window and not 2 <= a.window <= 32:
+        p.error("--window is 2..32")
+    if a.context and a.context < 3:
+        p.error("--context is at least 3")
+    if a.crossfade < 0 or a.context < 0:
+        p.error("--context and --crossfade are frame counts")
+    if a.rate < 0 or a.rate % 100:
+        p.error("--rate is a multiple of 100")
+    return a
+
+
+def normalise_peak(x: np.ndarray) -> np.ndarray:
+    """upstream's rule for a converted file: a peak above 1 is brought down to 0.99, anything else is left alone"""
+    x = np.asarray(x, np.float32)
+    peak = float(np.max(np.abs(x))) if len(x) else 0.0
+    return x / np.float32(peak / 0.99) if peak > 1.0 else x
+
+
+def write_wav(path, x, rate: int) -> None:
+    """mono 16-bit PCM: the peak rule, then round(x * 32767) clipped to the int16 range (build_index.read_wav divides by 32768)"""
+    x = normalise_peak(x)
+    pcm = np.clip(np.rint(x.astype(np.float64) * 32767.0), -32768, 32767).astype("<i2")
+    with wave.open(os.fspath(path), "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(int(rate))
+        w.writeframes(pcm.tobytes())
+
+
+def _resample(eng, x: np.ndarray, rate_in: int, rate_out: int) -> np.ndarray:
+    """a whole signal through the package's converter in blocks of about 20 ms (as RvcInfer._to_16k), its start-up delay of half a block trimmed"""
+    from .resample import FftFixedInOut
+    r = FftFixedInOut(eng, rate_in, rate_out, max(rate_in // 50, 1))
+    nin = r.input_frames_next()
+    nblk = -(-len(x) // nin) + 1
+    xp = np.zeros(nblk * nin, np.float32)
+    xp[: len(x)] = x
+    y = np.concatenate([np.array(r.process(xp[i * nin:(i + 1) * nin]), np.float32) for i in range(nblk)])
+    delay, n = r.output_frames_max() // 2, -(-len(x) * rate_out // rate_in)
+    return y[delay: delay + n]
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    x, rate = read_wav(a.input)
+    if not len(x):
+        print("%s holds no samples" % a.input, file=sys.stderr)
+        return 2
+    from . import weights as W
+    from .rvc import RvcInfer
+    eng = RvcInfer(a.data or W.default_zoo_root("full"), device=a.device)
+    eng.load_contentvec(a.version)
+    eng.load_f0_method(a.f0)
+    eng.load_model(a.model)
+    eng.set_streams(a.streams)
+    if a.index:
+        eng.load_index(a.index, nprobe=a.nprobe or None, k=a.index_k)
+        eng.set_index_rate(a.index_rate)
+    eng.set_pitch_semitones(a.pitch)
+    eng.set_formant_shift(a.formant)
+    eng.set_protect(a.protect)
+    y, model_rate = eng.convert(x, rate=rate, k=a.window, context=a.context, crossfade=a.crossfade, pitch_shift=0, highpass=a.highpass)
+    info = eng.convert_info()
+    out_rate = a.rate or model_rate
+    if out_rate != model_rate:
+        y = _resample(eng, y, model_rate, out_rate)
+    write_wav(a.output, y, out_rate)
+    print("%s: %.2f s at %d Hz from %d windows in %d batches; device ms: high-pass %.2f, model %.2f, stitch %.2f, total %.2f"
+          % (a.output, len(y) / out_rate, out_rate, info["windows"], info["batches"], info["ms_highpass"], info["ms_model"], info["ms_stitch"], info["ms_total"]))
+    eng.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

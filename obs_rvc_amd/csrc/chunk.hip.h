@@ -108,17 +108,38 @@ static __global__ void post_mix_kernel(float *out, int n, const double *r1, int 
 // sin^2 crossfade with the previous tail, new tail saved, first `frame` samples returned.
 // normalised cross-correlation of get_sola_offset (rt_utils.rs:60-77), one wave per lag: cor[l] = <out[l..], sola> / sqrt(<out[l..], out[l..]> + 1e-8)
 // with f64 accumulation (the reference's FFT convolution carries f32 rounding noise of the same order as an f32 direct sum)
+// (one lag by one whole wave, every lane gets the value: shared with the file converter's offset chain, stitch.hip.h, which must pick the same offsets)
+__device__ __forceinline__ float sola_corr_lag(const float *out_l, const float *sola, int sola_len, int lane)
+{
+    double nom = 0.0, den = 0.0;
+    for (int j = lane; j < sola_len; j += 64) { const double v = (double)out_l[j]; nom += v * (double)sola[j]; den += v * v; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { nom += __shfl_xor(nom, o, 64); den += __shfl_xor(den, o, 64); }
+    return (float)nom / sqrtf((float)den + 1e-8f);
+}
 static __global__ __launch_bounds__(256) void post_sola_corr_kernel(const float *output, const float *sola, int sola_len, int search, float *cor,
                                                              long long out_bs, long long sola_bs, long long cor_bs)
 {
     const int lane = threadIdx.x & 63, l = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (l > search) return;
     output += blockIdx.y * out_bs; sola += blockIdx.y * sola_bs; cor += blockIdx.y * cor_bs;
-    double nom = 0.0, den = 0.0;
-    for (int j = lane; j < sola_len; j += 64) { const double v = (double)output[l + j]; nom += v * (double)sola[j]; den += v * v; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { nom += __shfl_xor(nom, o, 64); den += __shfl_xor(den, o, 64); }
-    if (lane == 0) cor[l] = (float)nom / sqrtf((float)den + 1e-8f);
+    const float c = sola_corr_lag(output + l, sola, sola_len, lane);
+    if (lane == 0) cor[l] = c;
+}
+// arg-max over cor[0 .. search] with the reference's tie rule: the LAST maximum wins (rt_utils.rs:79-88)
+__device__ __forceinline__ int sola_argmax_last(const float *cor, int search)
+{
+    int best = 0; float bv = cor[0];
+    for (int l = 1; l <= search; l++) if (!(bv > cor[l])) { best = l; bv = cor[l]; }
+    return best;
+}
+// sample i of the sin^2 crossfade of the new segment `o` with the saved tail `s` over sola_len samples (lib.rs:768-781)
+__device__ __forceinline__ float sola_fade(float o, float s, int i, int sola_len)
+{
+    const float x = sola_len > 1 ? (float)i / (float)(sola_len - 1) : 0.f;
+    const float sn = sinf(x * 0.5f * 3.14159265358979323846f);
+    const float fi = sn * sn, fo = 1.0f - fi;
+    return o * fi + s * fo;
 }
 
 // arg-max with the reference's tie rule (the LAST maximum wins, rt_utils.rs:79-88), sin^2 crossfade with the previous tail, tail save and
@@ -134,8 +155,7 @@ static __global__ __launch_bounds__(1024) void post_sola_kernel(float *output, f
     for (int l = t; l <= search; l += 1024) cor[l] = cor_g[l];
     __syncthreads();
     if (t == 0) {
-        int best = 0; float bv = cor[0];
-        for (int l = 1; l <= search; l++) if (!(bv > cor[l])) { best = l; bv = cor[l]; }
+        const int best = sola_argmax_last(cor, search);
         s_off = best; *offset_out = best;
     }
     __syncthreads();
@@ -145,12 +165,7 @@ static __global__ __launch_bounds__(1024) void post_sola_kernel(float *output, f
     if ((mode_v ? mode_v[blockIdx.x] : mode_all) == 1) {
         for (int i = t; i < sola_len; i += 1024) pv_a[blockIdx.x * pva_bs + i] = sola[i];
     } else {
-        for (int i = t; i < sola_len; i += 1024) {
-            const float x = sola_len > 1 ? (float)i / (float)(sola_len - 1) : 0.f;
-            const float sn = sinf(x * 0.5f * 3.14159265358979323846f);
-            const float fi = sn * sn, fo = 1.0f - fi;
-            o[i] = o[i] * fi + sola[i] * fo;
-        }
+        for (int i = t; i < sola_len; i += 1024) o[i] = sola_fade(o[i], sola[i], i, sola_len);
     }
     __syncthreads();
     for (int i = t; i < sola_len; i += 1024) sola[i] = o[frame + i];

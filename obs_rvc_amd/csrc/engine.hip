@@ -1467,6 +1467,7 @@ int rvc_debug_tap(rvc_engine *e, const char *name, int stream, float *out, size_
 #include "denoise.hip.h"
 #include "session.hip.h"
 #include "rccl_bcast.hip.h"
+#include "convert.hip.h"
 
 namespace rvc {
 

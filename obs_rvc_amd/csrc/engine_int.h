@@ -3,11 +3,11 @@
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
 //   model_yin.hip    YIN f0 (build_yin)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
-//   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h)
+//   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
-// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, ...)
+// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
 // or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm.hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
@@ -523,6 +523,10 @@ struct rvc_engine {
     std::vector<double> protect; double protect_default = rvc::PROTECT_OFF;
     std::vector<float> pushed_pr;
     float *h_pr = nullptr;                // pinned ring of 8 blocks of 4096, as h_fd
+    // the file converter (convert.hip.h): the high-pass taps on the device (uploaded by the first call that filters) and what
+    // rvc_convert_info reports of the last completed convert
+    rvc::DevBuf<float> hp_taps;
+    struct ConvertInfo { bool valid = false; size_t windows = 0, batches = 0; std::vector<int32_t> offsets; double ms[4] = {0, 0, 0, 0}; } conv;
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };

@@ -332,6 +332,67 @@ class RvcInfer:
         y = np.concatenate([np.array(r.process(xp[i * nin:(i + 1) * nin]), np.float32) for i in range(nblk)])
         return y[: -(-len(x) * 16000 // rate) + r.output_frames_max() // 2]
 
+    # -- whole-recording conversion (rvc_convert*) ---------------------------
+    @staticmethod
+    def convert_geometry(n16k: int, sample_rate: int, k: int = 0, context: int = 0, crossfade: int = 0) -> dict:
+        """rvc_convert_geometry (host only): the window geometry of a recording of n16k samples for a model at sample_rate; k / context / crossfade in
+        10 ms frames, 0 = 14 / 48 / 5 -> {windows, n, sample_frame_16k_size, skip_head, return_length, hop, zc, output_samples}"""
+        out = (C.c_size_t * 8)()
+        rc = _native.lib().rvc_convert_geometry(int(n16k), int(sample_rate), int(k), int(context), int(crossfade), out)
+        if rc != 0:
+            raise RvcInferError(rc, "convert geometry out of range")
+        return dict(zip(("windows", "n", "sample_frame_16k_size", "skip_head", "return_length", "hop", "zc", "output_samples"), (int(v) for v in out)))
+
+    def convert(self, x, rate: int = 16000, k: int = 0, context: int = 0, crossfade: int = 0, pitch_shift: int = 0, highpass: bool = True):
+        """rvc_convert: a whole recording -> (audio at the model's rate, that rate).  The windows run n_streams at a time (set_streams) and are SOLA-stitched on
+        the device; the call starts from reset_state().  A rate other than 16 000 goes through the package's converter first, its start-up delay trimmed.
+        pitch_shift is the integer, whole-octave shift of infer; set_pitch_semitones transposes by semitones."""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim != 1:
+            raise RvcInferError(5, "convert: a recording is a 1-D array")
+        if int(rate) != 16000 and len(x):
+            n16 = -(-len(x) * 16000 // int(rate))
+            y = self._to_16k(x, int(rate))
+            x = np.ascontiguousarray(y[len(y) - n16:])
+        n = C.c_size_t()
+        # (the first call sizes the output: a capacity of 0 is short for every recording, empty ones and unloaded models report their own status)
+        rc = self._L.rvc_convert(self._h, x.ctypes.data_as(_FP), len(x), int(k), int(context), int(crossfade), int(pitch_shift), 1 if highpass else 0, None, 0, C.byref(n))
+        if rc != 5 or n.value == 0:
+            self._chk(rc)
+        out = np.empty(n.value, np.float32)
+        self._chk(self._L.rvc_convert(self._h, x.ctypes.data_as(_FP), len(x), int(k), int(context), int(crossfade), int(pitch_shift), 1 if highpass else 0,
+                                      out.ctypes.data_as(_FP), len(out), C.byref(n)))
+        # n_out = ceil(n / 160) zc samples and the model's rate is 100 zc
+        return out[: n.value], 100 * (n.value // -(-len(x) // 160))
+
+    def convert_info(self) -> dict:
+        """rvc_convert_info of the last convert -> {windows, batches, offsets (int32 array), ms_highpass, ms_model, ms_stitch, ms_total} (device milliseconds)"""
+        w, b = C.c_size_t(), C.c_size_t()
+        ms = (C.c_double * 4)()
+        self._chk(self._L.rvc_convert_info(self._h, C.byref(w), C.byref(b), None, 0, ms))
+        off = np.empty(w.value, np.int32)
+        self._chk(self._L.rvc_convert_info(self._h, None, None, off.ctypes.data_as(C.POINTER(C.c_int32)), len(off), None))
+        return {"windows": w.value, "batches": b.value, "offsets": off, "ms_highpass": ms[0], "ms_model": ms[1], "ms_stitch": ms[2], "ms_total": ms[3]}
+
+    def sola_stitch(self, windows, sola_len: int, search: int, frame: int):
+        """rvc_sola_stitch: the chained LINEAR sola_step over windows (n_windows, window_len), the tail starting as zeros -> (audio (n_windows * frame,),
+        offsets (n_windows,) int32)"""
+        y, yp = _f32(windows)
+        if y.ndim != 2:
+            raise RvcInferError(5, "sola_stitch: windows is an (n_windows, window_len) array")
+        out = np.empty(y.shape[0] * int(frame), np.float32)
+        off = np.empty(y.shape[0], np.int32)
+        self._chk(self._L.rvc_sola_stitch(self._h, yp, y.shape[0], y.shape[1], int(sola_len), int(search), int(frame), out.ctypes.data_as(_FP),
+                                          off.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, off
+
+    def highpass(self, pcm16k):
+        """rvc_highpass: the converter's 48 Hz zero-phase high-pass (2049-tap FIR) of a 16 kHz signal"""
+        x, xp = _f32(pcm16k)
+        out = np.empty(len(x), np.float32)
+        self._chk(self._L.rvc_highpass(self._h, xp, len(x), out.ctypes.data_as(_FP)))
+        return out
+
     def rccl_unique_id(self) -> bytes:
         """rvc_rccl_unique_id: rank 0 creates the 128-byte ncclUniqueId the host then hands to the other ranks."""
         buf = C.create_string_buffer(128)
