@@ -101,6 +101,18 @@ extern "C" {
     pub fn rvc_sola_stitch(e: *mut RvcEngine, windows: *const c_float, n_windows: usize, window_len: usize, sola_len: usize, search: usize, frame: usize,
                            out: *mut c_float, offsets: *mut i32) -> c_int;
     pub fn rvc_highpass(e: *mut RvcEngine, pcm16k: *const c_float, n: usize, out: *mut c_float) -> c_int;
+    // a file at any rate, with the volume envelope: geometry out[4] = {o, n, w, N_out}; info ms[7] = {resample in, high-pass,
+    // gather + model, stitch, envelope, resample out, total}
+    pub fn rvc_resample_geometry(rate_in: usize, rate_out: usize, n_in: usize, out: *mut usize) -> c_int;
+    pub fn rvc_resample(e: *mut RvcEngine, input: *const c_float, n_in: usize, rate_in: usize, rate_out: usize, out: *mut c_float, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn rvc_resample_device(e: *mut RvcEngine, d_in: *const c_void, n_in: usize, rate_in: usize, rate_out: usize, d_out: *mut c_void, cap: usize,
+                               n_out: *mut usize) -> c_int;
+    pub fn rvc_change_rms(e: *mut RvcEngine, src: *const c_float, n_src: usize, rate_src: usize, y: *mut c_float, n_y: usize, rate_y: usize, rate: f64) -> c_int;
+    pub fn rvc_convert_file(e: *mut RvcEngine, pcm: *const c_float, n: usize, rate_in: usize, k: usize, context: usize, crossfade: usize, pitch_shift: i32,
+                            highpass: c_int, rms_mix_rate: f64, rate_out: usize, out: *mut c_float, cap: usize, out_len: *mut usize) -> c_int;
+    pub fn rvc_convert_file_device(e: *mut RvcEngine, d_pcm: *const c_void, n: usize, rate_in: usize, k: usize, context: usize, crossfade: usize, pitch_shift: i32,
+                                   highpass: c_int, rms_mix_rate: f64, rate_out: usize, d_out: *mut c_void, cap: usize, out_len: *mut usize) -> c_int;
+    pub fn rvc_convert_file_info(e: *mut RvcEngine, ms: *mut f64, rate_out: *mut usize, peak: *mut c_float) -> c_int;
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 

@@ -422,6 +422,40 @@ rvc_status rvc_sola_stitch(rvc_engine *e, const float *windows, size_t n_windows
    y[i] = sum_j h[j] x[i + M - j], accumulated in fp32 in the order j = 0 .. 2M.  n = 0: RVC_SHAPE */
 rvc_status rvc_highpass(rvc_engine *e, const float *pcm16k, size_t n, float *out);
 
+/* ---- a file at any rate, with the volume envelope ---- */
+/* One-shot sample-rate conversion of a whole signal: a windowed-sinc polyphase converter with the formant stage's filter (Hann-windowed sinc, width 6,
+ * rolloff 0.99; torchaudio.functional.resample at its defaults), NOT the streaming converter above.  g = gcd(rate_in, rate_out), o = rate_in / g,
+ * n = rate_out / g, b = 0.99 min(o, n), w = ceil(6 o / b), K = 2 w + o; the taps h[j][k], j < n, k < K, are evaluated in fp64 and rounded once to fp32;
+ *   N_out = ceil(N_in n / o),   y[i n + j] = sum_{k = 0 .. K-1} h[j][k] x[i o + k - w],   x = 0 outside [0, N_in).
+ * Each output is one fp32 fma chain over ascending k; o == n is a copy, bit for bit.  RVC_SHAPE with a message: a rate of 0; o or n above 2048; N_in = 0
+ * (or above 2^40); cap short (*n_out is written). */
+/* host only, pure: out = {o, n, w, N_out} */
+rvc_status rvc_resample_geometry(size_t rate_in, size_t rate_out, size_t n_in, size_t out[4]);
+rvc_status rvc_resample(rvc_engine *e, const float *in, size_t n_in, size_t rate_in, size_t rate_out, float *out, size_t cap, size_t *n_out);
+/* device-resident variant (HIP device pointers on the engine's device); returns synchronised */
+rvc_status rvc_resample_device(rvc_engine *e, const void *d_in, size_t n_in, size_t rate_in, size_t rate_out, void *d_out, size_t cap, size_t *n_out);
+/* The whole-file volume envelope (upstream's rms_mix_rate / change_rms; not rvc_envelop_mixing, the plugin's streaming form): y [n_y] at rate_y is rewritten
+ * in place; src [n_src] at rate_src is the signal whose envelope it takes on.  For signal s in {1 = src, 2 = y}: L_s = 2 (rate_s / 2), hop_s = rate_s / 2,
+ * F_s = 1 + N_s / hop_s, r_s[f] = sqrt(mean(xpad[f hop_s .. f hop_s + L_s)^2)) over the signal zero-padded by L_s / 2 on both sides; both tracks are brought
+ * to N_2 points by linear interpolation with half-pixel centres (u = max((i + 0.5) F_s / N_2 - 0.5, 0), i0 = floor(u), i1 = min(i0 + 1, F_s - 1));
+ *   out[i] = y[i] R_1[i]^(1 - rate) max(R_2[i], 1e-6)^(rate - 1),
+ * the tracks and the product in fp64, rounded once at the store.  rate = 1 leaves y untouched.  RVC_SHAPE: rate outside [0, 1] or NaN; a sample rate below 2
+ * (or above 2^20); n_src = 0 or n_y = 0 (or above 2^30). */
+rvc_status rvc_change_rms(rvc_engine *e, const float *src, size_t n_src, size_t rate_src, float *y, size_t n_y, size_t rate_y, double rate);
+/* A recording at rate_in -> the voice at rate_out (0 = the model's), all on the device: rvc_resample rate_in -> 16 000 (skipped when equal); everything
+ * rvc_convert does on that signal; rvc_change_rms with the 16 kHz signal the model saw as the source (behind the high-pass when it is on; skipped at
+ * rms_mix_rate = 1); rvc_resample model rate -> rate_out (skipped when equal); a max-abs reduction.  The result is that composition of the public calls,
+ * bit for bit.  Statuses: the three *_NOT_LOADED as for rvc_convert, before any argument is looked at; then the RVC_SHAPE cases of each stage in that
+ * order; cap short (*out_len is written).  rvc_convert_info reports the windows and offsets of the inner conversion. */
+rvc_status rvc_convert_file(rvc_engine *e, const float *pcm, size_t n, size_t rate_in, size_t k, size_t context, size_t crossfade, int32_t pitch_shift,
+                            int highpass, double rms_mix_rate, size_t rate_out, float *out, size_t cap, size_t *out_len);
+/* device-resident variant; returns synchronised */
+rvc_status rvc_convert_file_device(rvc_engine *e, const void *d_pcm, size_t n, size_t rate_in, size_t k, size_t context, size_t crossfade, int32_t pitch_shift,
+                                   int highpass, double rms_mix_rate, size_t rate_out, void *d_out, size_t cap, size_t *out_len);
+/* of the last completed rvc_convert_file: device ms = {resample in, high-pass, gather + model, stitch, envelope, resample out, total}, the output rate,
+   peak = max |out| (exact); any pointer may be NULL.  RVC_SHAPE before one has completed */
+rvc_status rvc_convert_file_info(rvc_engine *e, double ms[7], size_t *rate_out, float *peak);
+
 /* ---- what THIS GPU sustains, measured in-run (bench.py; boxes of one pool differ by ~10 % on matrix-core-bound work) ---- */
 /* rvc_calibrate: ~50 ms of device time.  A bare v_mfma_f32_32x32x2_f32 stream on every SIMD (four waves per SIMD, non-zero operands) -> fp32 matrix-core
  * TFLOP/s actually reached and the shader clock it ran at (s_memtime cycles per s_memrealtime tick); a float4 read stream over 1 GiB -> HBM TB/s. */

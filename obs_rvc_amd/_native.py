@@ -39,6 +39,7 @@ SYMBOLS = [
     "rvc_set_index_k", "rvc_index_k",
     "rvc_index_build_begin", "rvc_index_build_add", "rvc_index_build_add_device", "rvc_index_build_info", "rvc_index_build_finish", "rvc_index_build_abort",
     "rvc_convert_geometry", "rvc_convert", "rvc_convert_device", "rvc_convert_info", "rvc_sola_stitch", "rvc_highpass",
+    "rvc_resample_geometry", "rvc_resample", "rvc_resample_device", "rvc_change_rms", "rvc_convert_file", "rvc_convert_file_device", "rvc_convert_file_info",
 ]
 
 
@@ -255,6 +256,14 @@ def lib():
         L.rvc_convert_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(i32), sz, C.POINTER(C.c_double)]
         L.rvc_sola_stitch.argtypes = [vp, fp, sz, sz, sz, sz, sz, fp, C.POINTER(i32)]
         L.rvc_highpass.argtypes = [vp, fp, sz, fp]
+    if hasattr(L, "rvc_convert_file") or not override:
+        L.rvc_resample_geometry.argtypes = [sz, sz, sz, C.POINTER(sz)]
+        L.rvc_resample.argtypes = [vp, fp, sz, sz, sz, fp, sz, C.POINTER(sz)]
+        L.rvc_resample_device.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.POINTER(sz)]
+        L.rvc_change_rms.argtypes = [vp, fp, sz, sz, fp, sz, sz, C.c_double]
+        L.rvc_convert_file.argtypes = [vp, fp, sz, sz, sz, sz, sz, i32, C.c_int, C.c_double, sz, fp, sz, C.POINTER(sz)]
+        L.rvc_convert_file_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, i32, C.c_int, C.c_double, sz, vp, sz, C.POINTER(sz)]
+        L.rvc_convert_file_info.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(sz), fp]
     L.rvc_set_noise_seed.argtypes = [vp, u32, u32]
     L.rvc_set_noise_seed.restype = None
     L.rvc_reset_state.argtypes = [vp]

@@ -1,4 +1,4 @@
-"""python -m obs_rvc_amd.build_index <wav-dir-or-files...> -o added.index [--version 2] [--window 3.0] [--max-rows N] [--reduce-to N]
+"""python -m obs_rvc_amd.build_index <wav-dir-or-files...> -o added.index [--version 2] [--window 3.0] [--max-rows N] [--reduce-to N] [--resampler blocks|device]
 
 Upstream's "train feature index" with this engine: ContentVec over a voice's recordings on the GPU, the frames stacked in HBM
 (RvcInfer.build_index), reduced by k-means when there are too many, an IVF structure trained, and the result written as a Faiss file upstream reads
@@ -23,6 +23,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--window", type=float, default=3.0, help="seconds of audio per ContentVec run (default 3.0)")
     p.add_argument("--max-rows", type=int, default=0, help="reduce by k-means above this many rows (default: upstream's 200000)")
     p.add_argument("--reduce-to", type=int, default=0, help="k-means centres kept when reducing (default: upstream's 10000)")
+    p.add_argument("--resampler", choices=("blocks", "device"), default="blocks",
+                   help="route of a recording to 16 kHz: blocks = the streaming converter block by block (default), device = the whole-signal converter")
     p.add_argument("--device", type=int, default=-1)
     a = p.parse_args(argv)
     if not a.window > 0:
@@ -73,7 +75,8 @@ def main(argv=None) -> int:
     from .rvc import RvcInfer
     eng = RvcInfer(a.data or W.default_zoo_root("full"), device=a.device)
     eng.load_contentvec(a.version)
-    info = eng.build_index((read_wav(f) for f in files), window=int(round(a.window * 16000)), max_rows=a.max_rows, reduce_to=a.reduce_to)
+    info = eng.build_index((read_wav(f) for f in files), window=int(round(a.window * 16000)), max_rows=a.max_rows, reduce_to=a.reduce_to,
+                           resampler=a.resampler)
     eng.save_index(a.output)
     print("%s: %d rows from %d files (%d ContentVec runs, %d rows dropped as non-finite)" % (a.output, info["index_rows"], len(files), info["windows"], info["dropped_nonfinite"]))
     eng.close()

@@ -1,10 +1,12 @@
 """python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin] [--index I --index-rate r --index-k 4|8 --nprobe p]
        [--pitch semitones] [--formant st] [--protect p] [--streams S] [--window k --context C --crossfade X] [--no-highpass] [--rate out_rate]
+       [--rms-mix-rate r] [--resampler blocks|device]
 
 Upstream's "model inference" tab with this engine: a WAV file through RvcInfer.convert -- windows of one geometry run `--streams` at a
 time through the batched infer path and are SOLA-stitched on the GPU -- and the result written as 16-bit PCM.  The WAV file is read with
 build_index.read_wav and written with the standard library; like upstream the output is divided by peak / 0.99 when its peak exceeds 1.  Argument parsing and
-WAV writing are plain functions; only main() touches the GPU."""
+WAV writing are plain functions; only main() touches the GPU.  With --resampler device, or --rms-mix-rate below 1 (upstream's volume envelope), the file goes
+through RvcInfer.convert_file instead: both rate conversions and the envelope run on the GPU too, and the peak comes back with the audio."""
 from __future__ import annotations
 
 import argparse
@@ -38,8 +40,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--crossfade", type=int, default=0, help="crossfade frames between windows, >= 1 (default 5)")
     p.add_argument("--no-highpass", dest="highpass", action="store_false", help="skip the 48 Hz high-pass in front of the model")
     p.add_argument("--rate", type=int, default=0, help="output sample rate (default: the model's)")
+    p.add_argument("--rms-mix-rate", type=float, default=1.0, help="volume envelope, 0..1: 0 = the input's envelope, 1 = the model's own (default)")
+    p.add_argument("--resampler", choices=("blocks", "device"), default="blocks",
+                   help="sample-rate conversion: blocks = the streaming converter block by block (default), device = the whole-signal converter")
     p.add_argument("--device", type=int, default=-1)
     a = p.parse_args(argv)
+    if not 0.0 <= a.rms_mix_rate <= 1.0:
+        p.error("--rms-mix-rate is 0..1")
     if not -24.0 <= a.pitch <= 24.0:
         p.error("--pitch is -24..24 semitones")
     if not -5.0 <= a.formant <= 5.0:
@@ -63,16 +70,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     return a
 
 
-def normalise_peak(x: np.ndarray) -> np.ndarray:
-    """upstream's rule for a converted file: a peak above 1 is brought down to 0.99, anything else is left alone"""
+def normalise_peak(x: np.ndarray, peak=None) -> np.ndarray:
+    """upstream's rule for a converted file: a peak above 1 is brought down to 0.99, anything else is left alone.  peak: max |x| where the caller has it already"""
     x = np.asarray(x, np.float32)
-    peak = float(np.max(np.abs(x))) if len(x) else 0.0
+    if peak is None:
+        peak = float(np.max(np.abs(x))) if len(x) else 0.0
+    peak = float(peak)
     return x / np.float32(peak / 0.99) if peak > 1.0 else x
 
 
-def write_wav(path, x, rate: int) -> None:
+def write_wav(path, x, rate: int, peak=None) -> None:
     """mono 16-bit PCM: the peak rule, then round(x * 32767) clipped to the int16 range (build_index.read_wav divides by 32768)"""
-    x = normalise_peak(x)
+    x = normalise_peak(x, peak)
     pcm = np.clip(np.rint(x.astype(np.float64) * 32767.0), -32768, 32767).astype("<i2")
     with wave.open(os.fspath(path), "wb") as w:
         w.setnchannels(1); w.setsampwidth(2); w.setframerate(int(rate))
@@ -111,12 +120,19 @@ def main(argv=None) -> int:
     eng.set_pitch_semitones(a.pitch)
     eng.set_formant_shift(a.formant)
     eng.set_protect(a.protect)
-    y, model_rate = eng.convert(x, rate=rate, k=a.window, context=a.context, crossfade=a.crossfade, pitch_shift=0, highpass=a.highpass)
-    info = eng.convert_info()
-    out_rate = a.rate or model_rate
-    if out_rate != model_rate:
-        y = _resample(eng, y, model_rate, out_rate)
-    write_wav(a.output, y, out_rate)
+    if a.resampler == "device" or a.rms_mix_rate < 1.0:
+        y, out_rate = eng.convert_file(x, rate, k=a.window, context=a.context, crossfade=a.crossfade, pitch_shift=0, highpass=a.highpass, rms_mix_rate=a.rms_mix_rate,
+                                       out_rate=a.rate)
+        info, f = eng.convert_info(), eng.convert_file_info()
+        write_wav(a.output, y, out_rate, peak=f["peak"])
+        print("device ms: resample in %.2f, envelope %.2f, resample out %.2f, file total %.2f" % (f["ms_resample_in"], f["ms_envelope"], f["ms_resample_out"], f["ms_total"]))
+    else:
+        y, model_rate = eng.convert(x, rate=rate, k=a.window, context=a.context, crossfade=a.crossfade, pitch_shift=0, highpass=a.highpass)
+        info = eng.convert_info()
+        out_rate = a.rate or model_rate
+        if out_rate != model_rate:
+            y = _resample(eng, y, model_rate, out_rate)
+        write_wav(a.output, y, out_rate)
     print("%s: %.2f s at %d Hz from %d windows in %d batches; device ms: high-pass %.2f, model %.2f, stitch %.2f, total %.2f"
           % (a.output, len(y) / out_rate, out_rate, info["windows"], info["batches"], info["ms_highpass"], info["ms_model"], info["ms_stitch"], info["ms_total"]))
     eng.close()

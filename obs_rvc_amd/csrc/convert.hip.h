@@ -8,6 +8,8 @@
 #include "convert_geometry.h"
 #include "highpass.hip.h"
 #include "stitch.hip.h"
+#include "resample_whole.hip.h"
+#include "change_rms.hip.h"
 
 namespace rvc {
 
@@ -44,16 +46,30 @@ static void launch_stitch(hipStream_t st, const float *y, long long y_bs, int w0
                        (const float *)tails, (const int *)offsets, out, n_out);
 }
 
-// statuses and arguments of rvc_convert / rvc_convert_device, in the order the header documents; fills the geometry and *out_len
-static rvc_status convert_check(rvc_engine *e, const void *pcm, size_t n, size_t k, size_t context, size_t crossfade, const void *out, size_t cap, size_t *out_len, ConvertGeometry *g)
+// the statuses of a call that runs the models, as rvc_infer's: before any argument is looked at
+static rvc_status convert_loaded(rvc_engine *e)
 {
     if (!e->sy) return RVC_MODEL_NOT_LOADED;
     if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;
     if (!e->f0_method) return RVC_F0_NOT_LOADED;
+    return RVC_OK;
+}
+
+// the shape checks of a conversion of n samples at 16 kHz; fills the geometry
+static void convert_shape(rvc_engine *e, size_t n, size_t k, size_t context, size_t crossfade, ConvertGeometry *g)
+{
     if (n == 0) throw ShapeError("convert: empty recording");
     if (e->sy->sr <= 0 || e->sy->sr % 100 != 0) throw ShapeError("convert: the synthesizer's sample rate is not a multiple of 100");
     if (const char *why = convert_geometry(n, (size_t)e->sy->sr, k, context, crossfade, g)) throw ShapeError(why);
     if (g->windows > (size_t)1 << 30 || g->out_samples > (size_t)1 << 40) throw ShapeError("convert: recording too long");
+}
+
+// statuses and arguments of rvc_convert / rvc_convert_device, in the order the header documents; fills the geometry and *out_len
+static rvc_status convert_check(rvc_engine *e, const void *pcm, size_t n, size_t k, size_t context, size_t crossfade, const void *out, size_t cap, size_t *out_len, ConvertGeometry *g)
+{
+    const rvc_status rc = convert_loaded(e);
+    if (rc != RVC_OK) return rc;
+    convert_shape(e, n, k, context, crossfade, g);
     if (out_len) *out_len = g->out_samples;
     if (cap < g->out_samples) { e->err = "convert: output buffer too small"; return RVC_SHAPE; }
     if (!pcm || !out) throw ShapeError("convert: null buffer");
@@ -61,8 +77,10 @@ static rvc_status convert_check(rvc_engine *e, const void *pcm, size_t n, size_t
 }
 
 // the conversion proper, device to device.  Begins with what rvc_reset_state does (pitch caches and chunk counters zeroed), so that a window's result depends
-// on the recording alone; every per-stream setting, the index, the f0 method and graph replay apply as to any infer call
-static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const ConvertGeometry &g, int32_t pitch_shift, bool highpass, float *d_out)
+// on the recording alone; every per-stream setting, the index, the f0 method and graph replay apply as to any infer call.  keep_filtered (rvc_convert_file): the
+// high-passed signal is handed to the caller instead of being freed
+static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const ConvertGeometry &g, int32_t pitch_shift, bool highpass, float *d_out,
+                              DevBuf<float> *keep_filtered = nullptr)
 {
     hipStream_t st = e->stream;
     const size_t S = (size_t)e->n_streams, W = g.windows, batches = (W + S - 1) / S;
@@ -113,6 +131,96 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
     e->conv.windows = W; e->conv.batches = batches;
     e->conv.ms[0] = highpass ? (double)t_hp.ms() : 0.0; e->conv.ms[1] = ms_model; e->conv.ms[2] = ms_stitch; e->conv.ms[3] = (double)t_total.ms();
     e->conv.valid = true;
+    if (keep_filtered) *keep_filtered = std::move(filtered);
+    return RVC_OK;
+}
+
+// peak[0] = max |x[i]| as the bits of a non-negative float (peak starts as 0; unsigned order = float order there): exact, max is order-free
+static __global__ __launch_bounds__(256) void absmax_kernel(const float *x, long long n, unsigned *peak)
+{
+    float m = 0.f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(peak, __float_as_uint(m));
+}
+
+// what rvc_convert_file / rvc_convert_file_device check, in the order the header documents, and the sizes of every stage
+struct FileGeometry {
+    bool res_in = false, res_out = false;
+    ResampleGeometry rin, rout;      // rate_in -> 16 000; model rate -> rate_out
+    ConvertGeometry cg;
+    RmsGeometry r1, r2;
+    size_t n16 = 0, rate_out = 0, n_out = 0;
+};
+static rvc_status convert_file_check(rvc_engine *e, const void *pcm, size_t n, size_t rate_in, size_t k, size_t context, size_t crossfade, double rms_mix_rate, size_t rate_out,
+                                     const void *out, size_t cap, size_t *out_len, FileGeometry *f)
+{
+    const rvc_status rc = convert_loaded(e);
+    if (rc != RVC_OK) return rc;
+    if (const char *why = resample_geometry(rate_in, 16000, n, &f->rin)) throw ShapeError(why);
+    f->res_in = rate_in != 16000;
+    f->n16 = f->rin.n_out;
+    convert_shape(e, f->n16, k, context, crossfade, &f->cg);
+    const size_t sr = (size_t)e->sy->sr;
+    change_rms_check(f->n16, 16000, f->cg.out_samples, sr, rms_mix_rate, &f->r1, &f->r2);
+    f->rate_out = rate_out ? rate_out : sr;
+    f->res_out = f->rate_out != sr;
+    if (const char *why = resample_geometry(sr, f->rate_out, f->cg.out_samples, &f->rout)) throw ShapeError(why);
+    f->n_out = f->rout.n_out;
+    if (out_len) *out_len = f->n_out;
+    if (cap < f->n_out) { e->err = "convert_file: output buffer too small"; return RVC_SHAPE; }
+    if (!pcm || !out) throw ShapeError("convert_file: null buffer");
+    return RVC_OK;
+}
+
+// the chain, device to device: resample to 16 kHz, convert_run, change_rms against the signal the model saw, resample to rate_out, peak
+static rvc_status convert_file_run(rvc_engine *e, const float *d_pcm, size_t n, const FileGeometry &f, int32_t pitch_shift, bool highpass, double rms_mix_rate, float *d_out)
+{
+    hipStream_t st = e->stream;
+    e->file.valid = false;
+    DevTimer t_total, t_in, t_env, t_out;
+    DevBuf<float> sig16, filtered, model_out; DevBuf<double> tracks; DevBuf<unsigned> peak;
+    peak.alloc(1);
+    t_total.start(st);
+    const float *x16 = d_pcm;
+    if (f.res_in) {
+        sig16.alloc(f.n16);
+        t_in.start(st);
+        launch_resample_whole(e, d_pcm, n, f.rin, sig16.get());
+        t_in.stop(st);
+        x16 = sig16.get();
+    }
+    float *y = d_out;      // the model's output: in place when nothing is resampled behind it
+    if (f.res_out) { model_out.alloc(f.cg.out_samples); y = model_out.get(); }
+    const rvc_status rc = convert_run(e, x16, f.n16, f.cg, pitch_shift, highpass, y, &filtered);
+    if (rc != RVC_OK) return rc;
+    const bool env = rms_mix_rate != 1.0;
+    if (env) {
+        t_env.start(st);
+        launch_change_rms(e, highpass ? filtered.get() : x16, f.n16, f.r1, y, f.cg.out_samples, f.r2, rms_mix_rate, tracks);
+        t_env.stop(st);
+    }
+    if (f.res_out) {
+        t_out.start(st);
+        launch_resample_whole(e, y, f.cg.out_samples, f.rout, d_out);
+        t_out.stop(st);
+    }
+    HIPCHK(hipMemsetAsync(peak.get(), 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<size_t>((f.n_out + 255) / 256, 2048)), dim3(256), 0, st, (const float *)d_out, (long long)f.n_out, peak.get());
+    t_total.stop(st);
+    unsigned bits = 0;
+    HIPCHK(hipMemcpyAsync(&bits, peak.get(), sizeof bits, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    float pk; memcpy(&pk, &bits, sizeof pk);
+    e->file.ms[0] = f.res_in ? (double)t_in.ms() : 0.0;
+    for (int i = 0; i < 3; i++) e->file.ms[1 + i] = e->conv.ms[i];
+    e->file.ms[4] = env ? (double)t_env.ms() : 0.0;
+    e->file.ms[5] = f.res_out ? (double)t_out.ms() : 0.0;
+    e->file.ms[6] = (double)t_total.ms();
+    e->file.rate_out = f.rate_out; e->file.peak = pk;
+    e->file.valid = true;
     return RVC_OK;
 }
 
@@ -155,6 +263,47 @@ rvc_status rvc_convert(rvc_engine *e, const float *pcm16k, size_t n, size_t k, s
         rc = convert_run(e, d_in.get(), n, g, pitch_shift, highpass != 0, d_out.get());
         if (rc != RVC_OK) { (void)hipStreamSynchronize(e->stream); return rc; }
         HIPCHK(hipMemcpy(out, d_out.get(), g.out_samples * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
+// a recording at any rate -> the voice at rate_out (0 = the model's), with the volume envelope of the input; PCM in, PCM out, one upload and one download
+rvc_status rvc_convert_file_device(rvc_engine *e, const void *d_pcm, size_t n, size_t rate_in, size_t k, size_t context, size_t crossfade, int32_t pitch_shift, int highpass,
+                                   double rms_mix_rate, size_t rate_out, void *d_out, size_t cap, size_t *out_len)
+{
+    return guarded(e, [&]() {
+        FileGeometry f;
+        const rvc_status rc = convert_file_check(e, d_pcm, n, rate_in, k, context, crossfade, rms_mix_rate, rate_out, d_out, cap, out_len, &f);
+        if (rc != RVC_OK) return rc;
+        return convert_file_run(e, (const float *)d_pcm, n, f, pitch_shift, highpass != 0, rms_mix_rate, (float *)d_out);
+    });
+}
+
+rvc_status rvc_convert_file(rvc_engine *e, const float *pcm, size_t n, size_t rate_in, size_t k, size_t context, size_t crossfade, int32_t pitch_shift, int highpass,
+                            double rms_mix_rate, size_t rate_out, float *out, size_t cap, size_t *out_len)
+{
+    return guarded(e, [&]() {
+        FileGeometry f;
+        rvc_status rc = convert_file_check(e, pcm, n, rate_in, k, context, crossfade, rms_mix_rate, rate_out, out, cap, out_len, &f);
+        if (rc != RVC_OK) return rc;
+        DevBuf<float> d_in, d_out;
+        d_in.alloc(n); d_out.alloc(f.n_out);
+        HIPCHK(hipMemcpyAsync(d_in.get(), pcm, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        rc = convert_file_run(e, d_in.get(), n, f, pitch_shift, highpass != 0, rms_mix_rate, d_out.get());
+        if (rc != RVC_OK) { (void)hipStreamSynchronize(e->stream); return rc; }
+        HIPCHK(hipMemcpy(out, d_out.get(), f.n_out * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
+// of the last completed rvc_convert_file: device ms = {resample in, high-pass, gather + model, stitch, envelope, resample out, total}, the output rate, max |out|
+rvc_status rvc_convert_file_info(rvc_engine *e, double ms[7], size_t *rate_out, float *peak)
+{
+    return guarded(e, [&]() {
+        if (!e->file.valid) throw ShapeError("convert_file_info: no convert_file has completed on this engine");
+        if (ms) for (int i = 0; i < 7; i++) ms[i] = e->file.ms[i];
+        if (rate_out) *rate_out = e->file.rate_out;
+        if (peak) *peak = e->file.peak;
         return RVC_OK;
     });
 }

@@ -3,7 +3,8 @@
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
 //   model_yin.hip    YIN f0 (build_yin)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
-//   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter)
+//   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter, with
+//                    resample_whole.hip.h and change_rms.hip.h)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
@@ -527,6 +528,8 @@ struct rvc_engine {
     // rvc_convert_info reports of the last completed convert
     rvc::DevBuf<float> hp_taps;
     struct ConvertInfo { bool valid = false; size_t windows = 0, batches = 0; std::vector<int32_t> offsets; double ms[4] = {0, 0, 0, 0}; } conv;
+    // ... and rvc_convert_file_info of the last completed rvc_convert_file
+    struct FileInfo { bool valid = false; double ms[7] = {0, 0, 0, 0, 0, 0, 0}; size_t rate_out = 0; float peak = 0.f; } file;
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };

@@ -293,12 +293,15 @@ class RvcInfer:
     def index_build_abort(self):
         self._L.rvc_index_build_abort(self._h)
 
-    def build_index(self, recordings, window=None, max_rows=None, reduce_to=None, iters: int = 10, seed: int = 0, train: bool = True, nprobe: int = 1) -> dict:
+    def build_index(self, recordings, window=None, max_rows=None, reduce_to=None, iters: int = 10, seed: int = 0, train: bool = True, nprobe: int = 1,
+                    resampler: str = "blocks") -> dict:
         """Build this voice's index from its recordings on the device and install it.  `recordings`: an iterable of 1-D float arrays at 16 kHz, or of
         (array, rate) pairs; a pair whose rate is not 16 000 goes through the package's resampler (resample.FftFixedInOut, one call over the whole
-        recording) first.  window in 16 kHz samples (None = 48 000).  train=True: ends with train_index_ivf() (upstream's nlist rule, the same iters and
+        recording) first, or with resampler="device" through resample() (one launch).  window in 16 kHz samples (None = 48 000).  train=True: ends with train_index_ivf() (upstream's nlist rule, the same iters and
         seed) and sets nprobe.  -> the index_build_info fields as they stood before the build closed, "index_rows" = rows of the installed index, and
         "ivf" = train_index_ivf's report when trained."""
+        if resampler not in ("blocks", "device"):
+            raise ValueError("resampler: 'blocks' or 'device', not %r" % (resampler,))
         self.index_build_begin(window or 0, 0)
         try:
             for rec in recordings:
@@ -309,7 +312,7 @@ class RvcInfer:
                 if x.ndim != 1:
                     raise RvcInferError(5, "index build: a recording is a 1-D array")
                 if int(rate) != 16000 and len(x):
-                    x = self._to_16k(x, int(rate))
+                    x = self._to_16k(x, int(rate)) if resampler == "blocks" else self.resample(x, int(rate), 16000)
                 self.index_build_add(x)
             info = self.index_build_info()
             info["index_rows"] = self.index_build_finish(max_rows or 0, reduce_to or 0, iters, seed)
@@ -373,6 +376,63 @@ class RvcInfer:
         off = np.empty(w.value, np.int32)
         self._chk(self._L.rvc_convert_info(self._h, None, None, off.ctypes.data_as(C.POINTER(C.c_int32)), len(off), None))
         return {"windows": w.value, "batches": b.value, "offsets": off, "ms_highpass": ms[0], "ms_model": ms[1], "ms_stitch": ms[2], "ms_total": ms[3]}
+
+    # -- a file at any rate, with the volume envelope ------------------------
+    @staticmethod
+    def resample_geometry(rate_in: int, rate_out: int, n_in: int) -> dict:
+        """rvc_resample_geometry (host only) -> {o, n, w, n_out} of the whole-signal converter rate_in -> rate_out over n_in samples"""
+        out = (C.c_size_t * 4)()
+        rc = _native.lib().rvc_resample_geometry(int(rate_in), int(rate_out), int(n_in), out)
+        if rc != 0:
+            raise RvcInferError(rc, "resample geometry out of range")
+        return dict(zip(("o", "n", "w", "n_out"), (int(v) for v in out)))
+
+    def resample(self, x, rate_in: int, rate_out: int):
+        """rvc_resample: a whole signal rate_in -> rate_out in one launch (windowed sinc, width 6, rolloff 0.99); ceil(len(x) rate_out / rate_in) samples"""
+        x, xp = _f32(x)
+        if x.ndim != 1:
+            raise RvcInferError(5, "resample: a signal is a 1-D array")
+        n = C.c_size_t()
+        rc = self._L.rvc_resample(self._h, xp, len(x), int(rate_in), int(rate_out), None, 0, C.byref(n))      # (sizes the output, as convert does)
+        if rc != 5 or n.value == 0:
+            self._chk(rc)
+        out = np.empty(n.value, np.float32)
+        self._chk(self._L.rvc_resample(self._h, xp, len(x), int(rate_in), int(rate_out), out.ctypes.data_as(_FP), len(out), C.byref(n)))
+        return out
+
+    def change_rms(self, src, rate_src: int, y, rate_y: int, rate: float):
+        """rvc_change_rms (upstream's rms_mix_rate): the copy of `y` (at rate_y) that takes on the volume envelope of `src` (at rate_src); rate = 1 leaves it as it is,
+        rate = 0 gives it the source's envelope"""
+        s, sp = _f32(src)
+        o = np.array(y, dtype=np.float32, copy=True)
+        self._chk(self._L.rvc_change_rms(self._h, sp, len(s), int(rate_src), o.ctypes.data_as(_FP), len(o), int(rate_y), float(rate)))
+        return o
+
+    def convert_file(self, x, rate: int, k: int = 0, context: int = 0, crossfade: int = 0, pitch_shift: int = 0, highpass: bool = True, rms_mix_rate: float = 1.0,
+                     out_rate: int = 0):
+        """rvc_convert_file: a recording at `rate` -> (audio, its rate): resampled to 16 kHz, converted as convert() does, given the input's volume envelope
+        (rms_mix_rate below 1), resampled to out_rate (0 = the model's) -- all on the device, one upload and one download.  convert_file_info() has the peak."""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim != 1:
+            raise RvcInferError(5, "convert_file: a recording is a 1-D array")
+        n = C.c_size_t()
+        a = (x.ctypes.data_as(_FP), len(x), int(rate), int(k), int(context), int(crossfade), int(pitch_shift), 1 if highpass else 0, float(rms_mix_rate), int(out_rate))
+        rc = self._L.rvc_convert_file(self._h, *a, None, 0, C.byref(n))
+        if rc != 5 or n.value == 0:
+            self._chk(rc)
+        out = np.empty(n.value, np.float32)
+        self._chk(self._L.rvc_convert_file(self._h, *a, out.ctypes.data_as(_FP), len(out), C.byref(n)))
+        return out[: n.value], self.convert_file_info()["rate"]
+
+    def convert_file_info(self) -> dict:
+        """rvc_convert_file_info of the last convert_file -> {ms_resample_in, ms_highpass, ms_model, ms_stitch, ms_envelope, ms_resample_out, ms_total (device
+        milliseconds), rate (of the output), peak (max |audio|, exact)}"""
+        ms = (C.c_double * 7)()
+        rate, peak = C.c_size_t(), C.c_float()
+        self._chk(self._L.rvc_convert_file_info(self._h, ms, C.byref(rate), C.byref(peak)))
+        d = dict(zip(("ms_resample_in", "ms_highpass", "ms_model", "ms_stitch", "ms_envelope", "ms_resample_out", "ms_total"), (float(v) for v in ms)))
+        d["rate"], d["peak"] = int(rate.value), np.float32(peak.value)
+        return d
 
     def sola_stitch(self, windows, sola_len: int, search: int, frame: int):
         """rvc_sola_stitch: the chained LINEAR sola_step over windows (n_windows, window_len), the tail starting as zeros -> (audio (n_windows * frame,),
