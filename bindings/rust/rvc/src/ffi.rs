@@ -42,6 +42,10 @@ pub const RVC_PANIC: c_int = 6;
 pub const RVC_RCCL_UNIQUE_ID_BYTES: usize = 128;
 pub const RVC_F0_RMVPE: c_int = 1;
 pub const RVC_F0_YIN: c_int = 2;
+pub const RVC_F0_CREPE: c_int = 4;
+pub const RVC_F0_CREPE_TINY: c_int = 5;
+pub const RVC_CREPE_VITERBI: c_int = 0;
+pub const RVC_CREPE_ARGMAX: c_int = 1;
 pub const RVC_DENOISE_INPUT: c_int = 0;
 pub const RVC_DENOISE_OUTPUT: c_int = 1;
 
@@ -63,6 +67,9 @@ extern "C" {
     // ---- f0 method: RVC_F0_RMVPE (= rvc_load_f0) or RVC_F0_YIN (no weight file)
     pub fn rvc_load_f0_method(e: *mut RvcEngine, method: c_int) -> c_int;
     pub fn rvc_f0_method(e: *mut RvcEngine) -> c_int;
+    // ---- CREPE (RVC_F0_CREPE / RVC_F0_CREPE_TINY: <data>/f0/crepe-full.rvcw / crepe-tiny.rvcw): its decoder, RVC_CREPE_VITERBI (default) or RVC_CREPE_ARGMAX
+    pub fn rvc_set_crepe_decoder(e: *mut RvcEngine, decoder: c_int) -> c_int;
+    pub fn rvc_crepe_decoder(e: *mut RvcEngine) -> c_int;
 
     // ---- retrieval index, noise seed, state
     pub fn rvc_load_index(e: *mut RvcEngine, vectors: *const c_float, n: usize, dim: usize) -> c_int;

@@ -77,10 +77,16 @@ impl RvcInfer {
         self.check_load(unsafe { ffi::rvc_load_f0(self.handle, a as i32) })
     }
 
-    /// Not in the reference: the engine's f0 method by `ffi::RVC_F0_RMVPE` (the same as `load_f0`) or `ffi::RVC_F0_YIN`,
-    /// the weight-free time-domain tracker (no `<data>/f0/rmvpe.rvcw` needed)
+    /// Not in the reference: the engine's f0 method by `ffi::RVC_F0_RMVPE` (the same as `load_f0`), `ffi::RVC_F0_YIN`, the weight-free
+    /// time-domain tracker (no `<data>/f0/rmvpe.rvcw` needed), or `ffi::RVC_F0_CREPE` / `ffi::RVC_F0_CREPE_TINY`
+    /// (`<data>/f0/crepe-full.rvcw` / `crepe-tiny.rvcw`)
     pub fn load_f0_method(&mut self, method: i32) -> Result<(), BackendError> {
         self.check_load(unsafe { ffi::rvc_load_f0_method(self.handle, method) })
+    }
+
+    /// Not in the reference: CREPE's decoder, `ffi::RVC_CREPE_VITERBI` (the default) or `ffi::RVC_CREPE_ARGMAX`
+    pub fn set_crepe_decoder(&mut self, decoder: i32) -> Result<(), BackendError> {
+        self.check_load(unsafe { ffi::rvc_set_crepe_decoder(self.handle, decoder) })
     }
 
     /// rvc.rs:77-79

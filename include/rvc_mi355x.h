@@ -81,8 +81,22 @@ const char *rvc_last_error_message(rvc_engine *e);
  * unvoiced.  The method is engine-wide (not per stream), may be changed between calls, and is part of a plan's identity. */
 #define RVC_F0_RMVPE 1
 #define RVC_F0_YIN   2     /* weight-free; DESIGN.md "YIN pitch" */
-rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rvc_load_f0; YIN: needs no file; other values: RVC_SHAPE */
+/* CREPE (Kim et al. 2018; DESIGN.md "CREPE pitch"): the six-layer 1-D conv net on the same frame grid, decoded as upstream decodes it -- Viterbi over the 360
+ * bins -- and fed to the same pitch tail.  Full (capacity 32) reads <data>/f0/crepe-full.rvcw, tiny (capacity 4) <data>/f0/crepe-tiny.rvcw
+ * (python -m obs_rvc_amd.importers crepe writes them); a missing file gives what a missing rmvpe.rvcw gives (RVC_BACKEND) and leaves the method as it was.
+ * A preset is read once per engine: going back to it reads no file and finds its plans.  The value 3 is not a method: it stays the unknown value it was.
+ * Limits: every frame of every stream is in flight at once, so streams x frames of the f0 window may not exceed 65535 (RVC_SHAPE beyond), and a plan holds
+ * about 1.9 MB of activations per frame at full capacity (0.24 MB tiny): 60 MB at the 32 frames of a 160 ms chunk, 2 GB per stream at 1024 frames. */
+#define RVC_F0_CREPE      4
+#define RVC_F0_CREPE_TINY 5
+rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rvc_load_f0; YIN: needs no file; CREPE, CREPE_TINY: see above; other values: RVC_SHAPE */
 int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded */
+/* CREPE's decoder: 0 = Viterbi (the default, upstream's), 1 = arg-max (the same decoder without the transition term).  Engine-wide, may be changed between
+ * calls, part of a CREPE plan's identity; other values: RVC_SHAPE. */
+#define RVC_CREPE_VITERBI 0
+#define RVC_CREPE_ARGMAX  1
+rvc_status rvc_set_crepe_decoder(rvc_engine *e, int decoder);
+int rvc_crepe_decoder(rvc_engine *e);
 
 /* ---- capabilities the reference plumbs through but never implements / bakes into its export ---- */
 /* flat-L2 retrieval index (index_path / index_rate settings, obs-rvc/src/lib.rs:78,81; rvc.rs:159 TODO).  A load that fails behind its argument checks

@@ -113,6 +113,11 @@ typedef struct rvc_debug_protect_spec {
     int streams, C, R, T, skip_head, ph_ld, cv_ld, graph;
 } rvc_debug_protect_spec;
 int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *phone, const float *cv, const float *pitchf, const double *protect);
+/* crepe_decode_kernel alone (obs_rvc_amd/csrc/crepe.hip.h; DESIGN.md "CREPE pitch"), launched as a CREPE plan launches it, on the caller's posteriors prob
+ * [B][Tm][360]: decoder 0 = Viterbi, 1 = arg-max.  f0_out [B][Tm] is what the plan hands to the pitch tail (Hz, filtered, 0 = unvoiced); bins_out [B][Tm] the
+ * decoded path and pd_out [B][Tm] its periodicity prob[t][bin[t]] before the median filter (either may be NULL).  Needs no weights.  B in [1, 64], Tm in
+ * [2, 1024] (RVC_SHAPE otherwise).  0 = done, else an rvc_status. */
+int rvc_debug_crepe_decode(rvc_engine *e, const float *prob, int B, int Tm, int decoder, float *f0_out, int *bins_out, float *pd_out);
 /* the caller-side post-processing, the session's ring updates and a converter of several streams (obs_rvc_amd/csrc/chunk.hip.h, session.hip.h, resample.hip.h;
  * DESIGN.md "Post-processing and resamplers: what is tested"), each launch queued as rvc_session_process queues it, on the caller's arrays with the caller's
  * stream strides.  op: buffers buf[0..3] (each the WHOLE allocation, [streams][stride] floats, uploaded before the launches and downloaded after them: the

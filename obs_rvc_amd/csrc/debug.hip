@@ -596,6 +596,29 @@ int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *pho
     });
 }
 
+// test aid: CREPE's decoder alone (crepe.hip.h; tests/test_gpu_crepe.py) on the caller's posteriors, through the launch a plan uses (launch_crepe_decode)
+int rvc_debug_crepe_decode(rvc_engine *e, const float *prob, int B, int Tm, int decoder, float *f0_out, int *bins_out, float *pd_out)
+{
+    return (int)guarded(e, [&]() {
+        if (!prob || !f0_out || B < 1 || B > 64 || Tm < 2 || Tm > 1024 || (decoder != 0 && decoder != 1)) throw ShapeError("crepe decode: B in [1, 64], Tm in [2, 1024], decoder 0 or 1");
+        const size_t n = (size_t)B * Tm;
+        DevBuf<float> d_prob, d_f0, d_pd, d_tab; DevBuf<int> d_bins; DevBuf<unsigned char> d_bp;
+        d_prob.alloc(n * 360); d_f0.alloc(n); d_pd.alloc(n); d_bins.alloc(n); d_tab.alloc(360);
+        if (const size_t bpn = crepe_backpointer_bytes(B, Tm)) d_bp.alloc(bpn);
+        const std::vector<float> tab = crepe_f0_table();
+        HIPCHK(hipMemcpy(d_tab.get(), tab.data(), 360 * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_prob.get(), prob, n * 360 * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipDeviceSynchronize());
+        launch_crepe_decode(e->stream, B, d_prob.get(), Tm, decoder, d_tab.get(), d_bp.get(), d_f0.get(), d_bins.get(), d_pd.get());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipMemcpy(f0_out, d_f0.get(), n * sizeof(float), hipMemcpyDeviceToHost));
+        if (bins_out) HIPCHK(hipMemcpy(bins_out, d_bins.get(), n * sizeof(int), hipMemcpyDeviceToHost));
+        if (pd_out) HIPCHK(hipMemcpy(pd_out, d_pd.get(), n * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
 // test aid: the caller-side post-processing, the session's ring updates and a converter of several streams (chunk.hip.h, session.hip.h, resample.hip.h;
 // tests/test_gpu_post.py) on the caller's arrays with the caller's stream strides, each launch queued as the session queues it (engine_int.h launch_post_* /
 // launch_ring_* / launch_resampler).  Every size is checked against the strides on the host before anything is queued.

@@ -215,11 +215,18 @@ static void alloc_state(rvc_engine *e)
 }
 
 // ------------------------------- plan -------------------------------------------------
-// the f0 branch of the engine's method: RMVPE's network and salience decode, or the YIN launch; behind either the same pitch tail (shift, cache, get_f0_post)
+static inline bool is_crepe(int method) { return method == RVC_F0_CREPE || method == RVC_F0_CREPE_TINY; }
+// the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, or CREPE's network and decoder; behind each the same pitch tail
+// (shift, cache, get_f0_post)
 static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache, size_t hubert_length, float **pitchf_out, int **pitch_out)
 {
     if (e->f0_method == RVC_F0_YIN) {
         const float *f0 = build_yin(e, pl, B, L, frame16k);
+        build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
+        return;
+    }
+    if (is_crepe(e->f0_method)) {
+        const float *f0 = build_crepe(e, pl, B, L, frame16k);
         build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
         return;
     }
@@ -260,7 +267,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
             p->with_index == with_index && p->with_protect == with_protect && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
-            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
+            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method && p->crepe_decoder == (is_crepe(e->f0_method) ? e->crepe_decoder : 0) && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -273,7 +280,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
     pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_protect = with_protect; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
-    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
+    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method; pl.crepe_decoder = is_crepe(e->f0_method) ? e->crepe_decoder : 0; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
     T1 src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;
@@ -743,7 +750,7 @@ void rvc_destroy(rvc_engine *e)
     (void)hipDeviceSynchronize();
     e->plans.clear();
     index_build_abort(e);
-    e->cv.reset(); e->rm.reset(); e->sy.reset();
+    e->cv.reset(); e->rm.reset(); e->cr_full.reset(); e->cr_tiny.reset(); e->sy.reset();
     wfree(e->d_window); wfree(e->d_twiddle); wfree(e->d_basis);      // (upload_f: slab memory)
     if (e->d_band) (void)hipFree(e->d_band);
     if (e->d_state) (void)hipFree(e->d_state);
@@ -817,12 +824,32 @@ rvc_status rvc_load_f0_method(rvc_engine *e, int method)
 {
     if (method == RVC_F0_RMVPE) return rvc_load_f0(e, RVC_PITCH_RMVPE);
     return guarded(e, [&]() {
-        if (method != RVC_F0_YIN) throw ShapeError("f0 method: RVC_F0_RMVPE or RVC_F0_YIN");
+        if (is_crepe(method)) {
+            // a preset is read once and kept: the plans built on its weights stay valid, so going back to it finds them
+            std::unique_ptr<ModelCR> &slot = method == RVC_F0_CREPE ? e->cr_full : e->cr_tiny;
+            if (!slot) {
+                Blob b(e->data_path + (method == RVC_F0_CREPE ? "/f0/crepe-full.rvcw" : "/f0/crepe-tiny.rvcw"));
+                slot.reset(new ModelCR(b));
+            }
+            e->f0_method = method;
+            return RVC_OK;
+        }
+        if (method != RVC_F0_YIN) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE or RVC_F0_CREPE_TINY");
         e->f0_method = RVC_F0_YIN;
         return RVC_OK;
     });
 }
 int rvc_f0_method(rvc_engine *e) { return e ? e->f0_method : 0; }
+// CREPE's decoder (crepe_decode_kernel): part of a CREPE plan's key, so a plan built for one never serves the other
+rvc_status rvc_set_crepe_decoder(rvc_engine *e, int decoder)
+{
+    return guarded(e, [&]() {
+        if (decoder != RVC_CREPE_VITERBI && decoder != RVC_CREPE_ARGMAX) throw ShapeError("crepe decoder: RVC_CREPE_VITERBI or RVC_CREPE_ARGMAX");
+        e->crepe_decoder = decoder;
+        return RVC_OK;
+    });
+}
+int rvc_crepe_decoder(rvc_engine *e) { return e ? e->crepe_decoder : 0; }
 // rvc.rs:77-79
 void rvc_unload_model(rvc_engine *e)
 {

@@ -1,14 +1,14 @@
 // engine_int.h -- internal declarations shared by the translation units of librvc_mi355x.so:
 //   plan.hip         the planner: device memory, prepared convolution weights, the op list, implicit-GEMM tile selection, test-hook table
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
-//   model_yin.hip    YIN f0 (build_yin)
+//   model_yin.hip    YIN f0 (build_yin)                      model_crepe.hip   CREPE f0 (build_crepe, the decoder's launch)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
 //   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter, with
 //                    resample_whole.hip.h and change_rms.hip.h)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
-// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
+// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, crepe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
 // or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm.hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
@@ -252,6 +252,7 @@ struct Plan {
     bool plain_plan = false;      // taps level 1: the explicit plan (LayerNorm launches, WaveNets layer by layer); level 2 taps the production plan
     int mode = 0;   // 0 infer, 1 hubert only, 2 pitch only
     int f0_method = 0;            // the engine's f0 method when the plan was built (its f0 branch is that method's)
+    int crepe_decoder = 0;        // ... and, for the CREPE methods, the engine's decoder (0 = Viterbi, 1 = arg-max; 0 on every other plan)
     // formant shift (formant.hip.h): fstage = the plan has the formant stage (some stream stretches or resamples); the decoder then runs
     // on R2 frames and formant_resample_kernel brings every stream back to R upp samples.  fstage = false: today's plan, R2 = R
     uint32_t R2 = 0; bool fstage = false;
@@ -399,6 +400,18 @@ struct ModelRM {
     ~ModelRM();
 };
 
+// CREPE (model_crepe.hip): six convolutions (capacity `cap`: 32 = full, 4 = tiny), BatchNorm as per-channel scale and shift applied
+// behind the ReLU, the classifier as a 1x1 convolution over the [4 * 16 cap] features (time major, channel minor), Hz per bin
+struct ModelCR {
+    int cap = 0;
+    ConvW conv[6], fc;
+    float *scale[6] = {}, *shift[6] = {}, *f0tab = nullptr;
+    size_t weight_bytes = 0;
+    explicit ModelCR(const Blob &b);
+    ~ModelCR();
+    ModelCR(const ModelCR &) = delete; ModelCR &operator=(const ModelCR &) = delete;
+};
+
 // GLU row packing of a WaveNet in-layer (igemm.hip.h glu_store): packed row f*16 + kq*4 + r <- model row f*8 + kq*2 + (r&1) of the tanh half (r < 2)
 // or the sigmoid half (r >= 2, + H).  w: [2H][K] in model row order, bias: [2H]
 template <typename T> void glu_pack_rows(const T *w, const float *bias, int H, size_t K, std::vector<float> &wp, std::vector<float> &bp);      // (model_synth.hip: float and double)
@@ -465,7 +478,9 @@ struct rvc_engine {
     hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
     std::unique_ptr<ModelCV> cv;
     std::unique_ptr<ModelRM> rm;
-    int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights); engine-wide and part of a plan's identity
+    int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights), RVC_F0_CREPE / _TINY (cr_full / cr_tiny); engine-wide and part of a plan's identity
+    std::unique_ptr<ModelCR> cr_full, cr_tiny;        // each stays loaded once read: going back to it costs no file and keeps its plans
+    int crepe_decoder = 0;                            // rvc_set_crepe_decoder: 0 = Viterbi, 1 = arg-max; engine-wide and part of a CREPE plan's identity
     std::unique_ptr<ModelSY> sy;
     // constants for the mel front end
     float *d_window = nullptr, *d_twiddle = nullptr, *d_basis = nullptr; int *d_band = nullptr;
@@ -552,6 +567,12 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L);
 T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache);
 void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update_cache, size_t frame16k, size_t hubert_length, float **pitchf_out, int **pitch_out, const float *f0_in = nullptr);
 float *build_yin(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
+float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
+// CREPE's decoder alone (crepe_decode_kernel, crepe.hip.h): the plan's launch and rvc_debug_crepe_decode's (debug.hip).  prob [B][Tm][360]; bp: B * Tm * 360 bytes of
+// back-pointers where crepe_backpointer_bytes says so (long windows; shorter ones keep them in LDS); bins / pd may be null
+std::vector<float> crepe_f0_table();
+size_t crepe_backpointer_bytes(int B, int Tm);
+void launch_crepe_decode(hipStream_t s, int B, const float *prob, int Tm, int decoder, const float *f0tab, unsigned char *bp, float *f0, int *bins, float *pd);
 T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf);
 // the head and the tail of the f0 branch and ContentVec's first layer as plan helpers: the builders above call them, and so does rvc_debug_front (debug.hip)
 void add_conv0_front(Plan &pl, const ConvW &cw, const float *w_raw, const float *gn_g, const float *gn_b, int kt, int st, const T1 &x, const T1 &y);

@@ -21,6 +21,7 @@ structure and parameter names (tests/test_importers.py) -- a real file may still
 
 CLI:  python -m obs_rvc_amd.importers contentvec|rmvpe|synth <input> <output.rvcw> [--version 2] [--sid 0] [--sr 48000]
                                       [--up-rates 10,10,2,2]
+      python -m obs_rvc_amd.importers crepe <full.pth|tiny.pth> <output.rvcw>      (-> <data>/f0/crepe-full.rvcw or crepe-tiny.rvcw)
 """
 from __future__ import annotations
 
@@ -552,6 +553,44 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
     return cfg, t
 
 
+def import_crepe(named: Named) -> Tuple[dict, Named]:
+    """A torchcrepe state dict (full.pth / tiny.pth): convN.weight [out][in][k][1], convN.bias, convN_BN.{weight, bias, running_mean, running_var} for N = 1..6,
+    classifier.{weight, bias}.  The capacity comes from conv1.weight.shape[0] (1024 = full, 128 = tiny); BatchNorm (eps = W.CREPE_BN_EPS) is stored as the
+    per-channel scale and shift applied behind the ReLU.  The table is checked on synthesized dicts; the value-level pin against torchcrepe is open."""
+    need = ["conv%d%s" % (n, sfx) for n in range(1, 7) for sfx in (".weight", ".bias", "_BN.weight", "_BN.bias", "_BN.running_mean", "_BN.running_var")]
+    need += ["classifier.weight", "classifier.bias"]
+    missing = [k for k in need if k not in named]
+    if missing:
+        raise ImportError_("crepe: missing tensors: " + ", ".join(missing))
+    c1 = int(named["conv1.weight"].shape[0])
+    caps = {32 * m: m for m in (W.CREPE_PRESETS["full"], W.CREPE_PRESETS["tiny"])}
+    if c1 not in caps:
+        raise ImportError_("crepe: conv1.weight has %d output channels: neither full (1024) nor tiny (128)" % c1)
+    m = caps[c1]
+    t: Named = {}
+    cin = 1
+    for n in range(1, 7):
+        co, k = W.CREPE_CHANNELS[n - 1] * m, W.CREPE_KERNELS[n - 1]
+        w = np.asarray(named["conv%d.weight" % n])
+        if w.shape != (co, cin, k, 1):
+            raise ImportError_("crepe: conv%d.weight is %s, expected %s" % (n, tuple(w.shape), (co, cin, k, 1)))
+        bn = [np.asarray(named["conv%d_BN.%s" % (n, f)], np.float64) for f in ("weight", "bias", "running_mean", "running_var")]
+        if any(a.shape != (co,) for a in bn) or np.asarray(named["conv%d.bias" % n]).shape != (co,):
+            raise ImportError_("crepe: conv%d bias / BatchNorm vectors are not [%d]" % (n, co))
+        scale = bn[0] / np.sqrt(bn[3] + W.CREPE_BN_EPS)
+        t["cr.conv%d.w" % n] = w[..., 0]
+        t["cr.conv%d.b" % n] = np.asarray(named["conv%d.bias" % n])
+        t["cr.bn%d.scale" % n] = scale
+        t["cr.bn%d.shift" % n] = bn[1] - bn[2] * scale
+        cin = co
+    fw = np.asarray(named["classifier.weight"])
+    if fw.shape != (360, 4 * cin) or np.asarray(named["classifier.bias"]).shape != (360,):
+        raise ImportError_("crepe: classifier is %s, expected (360, %d)" % (tuple(fw.shape), 4 * cin))
+    t["cr.fc.w"] = fw
+    t["cr.fc.b"] = np.asarray(named["classifier.bias"])
+    return dict(kind=4, cap=m), t
+
+
 def convert(kind: str, src: str, dst: str, **kw) -> None:
     named = load_named_tensors(src)
     if kind == "synth" and kw.get("config") is None:
@@ -562,13 +601,13 @@ def convert(kind: str, src: str, dst: str, **kw) -> None:
         cfg, t = import_rmvpe_structural(inits, nodes)
         W.write_blob(dst, cfg, {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in t.items()})
         return
-    cfg, t = {"contentvec": import_contentvec, "rmvpe": import_rmvpe, "synth": import_synth}[kind](named, **kw)
+    cfg, t = {"contentvec": import_contentvec, "rmvpe": import_rmvpe, "synth": import_synth, "crepe": import_crepe}[kind](named, **kw)
     W.write_blob(dst, cfg, {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in t.items()})
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("kind", choices=["contentvec", "rmvpe", "synth"])
+    ap.add_argument("kind", choices=["contentvec", "rmvpe", "synth", "crepe"])
     ap.add_argument("src"); ap.add_argument("dst")
     ap.add_argument("--version", type=int, default=2); ap.add_argument("--sid", type=int, default=0); ap.add_argument("--sr", type=int, default=None)
     ap.add_argument("--up-rates", default=None, help="synthesizer upsample rates, e.g. 10,10,2,2 (default: the checkpoint's config list, else from --sr)")

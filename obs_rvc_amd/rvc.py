@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _native
-from .rvc_common import (CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_RMVPE, F0_YIN, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
+from .rvc_common import (CREPE_ARGMAX, CREPE_VITERBI, CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_CREPE, F0_CREPE_TINY, F0_RMVPE, F0_YIN, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
                          RvcInferError, RvcModelVersion, scale_mask)
 
 _FP = C.POINTER(C.c_float)
@@ -57,18 +57,33 @@ class RvcInfer:
     def load_f0(self, pitch_algorithm=PitchAlgorithm.Rmvpe):
         self._chk(self._L.rvc_load_f0(self._h, int(PitchAlgorithm.from_value(pitch_algorithm))))
 
+    _F0_NAMES = {"rmvpe": F0_RMVPE, "yin": F0_YIN, "crepe": F0_CREPE, "crepe-full": F0_CREPE, "crepe-tiny": F0_CREPE_TINY}
+
     def load_f0_method(self, method):
-        """The engine's f0 method: "rmvpe" / F0_RMVPE (loads <data>/f0/rmvpe.rvcw, as load_f0) or "yin" / F0_YIN (needs no file)."""
+        """The engine's f0 method: "rmvpe" / F0_RMVPE (loads <data>/f0/rmvpe.rvcw, as load_f0), "yin" / F0_YIN (needs no file), "crepe" = "crepe-full" / F0_CREPE
+        (<data>/f0/crepe-full.rvcw) or "crepe-tiny" / F0_CREPE_TINY (<data>/f0/crepe-tiny.rvcw)."""
         if isinstance(method, str):
-            if method.lower() not in ("rmvpe", "yin"):
-                raise ValueError("f0 method: 'rmvpe' or 'yin', not %r" % method)
-            method = {"rmvpe": F0_RMVPE, "yin": F0_YIN}[method.lower()]
+            if method.lower() not in self._F0_NAMES:
+                raise ValueError("f0 method: 'rmvpe', 'yin', 'crepe' (= 'crepe-full') or 'crepe-tiny', not %r" % method)
+            method = self._F0_NAMES[method.lower()]
         self._chk(self._L.rvc_load_f0_method(self._h, int(method)))
 
     @property
     def f0_method(self) -> int:
-        """0 = none loaded, F0_RMVPE, F0_YIN"""
+        """0 = none loaded, F0_RMVPE, F0_YIN, F0_CREPE, F0_CREPE_TINY"""
         return int(self._L.rvc_f0_method(self._h))
+
+    def set_crepe_decoder(self, decoder):
+        """CREPE's decoder: "viterbi" / CREPE_VITERBI (the default) or "argmax" / CREPE_ARGMAX; engine-wide"""
+        if isinstance(decoder, str):
+            if decoder.lower() not in ("viterbi", "argmax"):
+                raise ValueError("crepe decoder: 'viterbi' or 'argmax', not %r" % decoder)
+            decoder = {"viterbi": CREPE_VITERBI, "argmax": CREPE_ARGMAX}[decoder.lower()]
+        self._chk(self._L.rvc_set_crepe_decoder(self._h, int(decoder)))
+
+    @property
+    def crepe_decoder(self) -> int:
+        return int(self._L.rvc_crepe_decoder(self._h))
 
     def unload_model(self):
         self._L.rvc_unload_model(self._h)

@@ -224,6 +224,58 @@ def make_rmvpe(preset: str = "full", seed: int = 4321):
     return cfg, g.t
 
 
+# CREPE (Kim et al. 2018): capacity multiplier per preset -- full and tiny are upstream's, micro exists for tests (4-channel layers)
+CREPE_PRESETS = {"full": 32, "tiny": 4, "micro": 1}
+CREPE_CHANNELS = (32, 4, 4, 4, 8, 16)          # output channels per unit of capacity
+CREPE_KERNELS = (512, 64, 64, 64, 64, 64)
+CREPE_BN_EPS = 0.0010000000474974513
+# make_crepe: He gain per layer (the late layers see 32 / 16 samples under a 64-tap kernel: most taps meet the zero padding, so their fan-in is scaled up) and
+# the classifier's gain per preset, set once by hand so that the posteriors on voiced input spread over (0.05, 0.95)
+_CREPE_GAINS = (1.4, 1.4, 1.4, 1.7, 2.2, 3.0)
+_CREPE_FC_GAIN = {"full": 1.6, "tiny": 1.6, "micro": 4.0}
+
+
+def make_crepe(preset: str = "full", seed: int = 2468):
+    """Seeded CREPE weights in blob layout: cr.convN.w [out][in][k], cr.convN.b, cr.bnN.scale / .shift (BatchNorm in inference form, applied behind the
+    ReLU; about one scale in four is negative, as a trained net has them), cr.fc.w [360][4 * 16 m] (column = time * channels + channel), cr.fc.b.
+    He-scaled convolutions keep the activations of order one; conv biases and shifts are small, so a silent frame stays near the classifier's bias (-3: a
+    posterior of 0.05, unvoiced) while a frame with signal swings the logits by a few units either way: posteriors neither pinned at 0 nor at 1."""
+    from scipy.ndimage import gaussian_filter1d
+
+    m = CREPE_PRESETS[preset]
+    g = _Gen(seed)
+    cin = 1
+    for n in range(1, 7):
+        co, k = CREPE_CHANNELS[n - 1] * m, CREPE_KERNELS[n - 1]
+        g.fan("cr.conv%d.w" % n, (co, cin, k), cin * k, _CREPE_GAINS[n - 1])
+        g.normal("cr.conv%d.b" % n, (co,), 0.02)
+        sign = np.where(g.rng.random(co) < 0.25, -1.0, 1.0)
+        g.t["cr.bn%d.scale" % n] = (sign * (1.0 + 0.1 * g.rng.standard_normal(co))).astype(np.float32)
+        g.normal("cr.bn%d.shift" % n, (co,), 0.02)
+        cin = co
+    feat = 4 * cin
+    w = g.rng.standard_normal(size=(360, feat))
+    w = gaussian_filter1d(w, sigma=4.0, axis=0, mode="nearest")
+    w *= _CREPE_FC_GAIN[preset] / (np.sqrt(np.mean(w ** 2)) * np.sqrt(feat))
+    g.t["cr.fc.w"] = w.astype(np.float32)
+    g.t["cr.fc.b"] = np.full(360, -3.0, np.float32)
+    return dict(kind=4, cap=m), g.t
+
+
+def crepe_blob_name(preset: str) -> str:
+    """what rvc_load_f0_method reads: <data>/f0/crepe-full.rvcw, crepe-tiny.rvcw (micro is installed under either name by the tests that want it)"""
+    return "crepe-%s.rvcw" % preset
+
+
+def write_crepe(data_dir: str, preset: str = "full", as_preset: str | None = None, force: bool = False) -> str:
+    """<data_dir>/f0/crepe-<as_preset or preset>.rvcw with make_crepe(preset); idempotent (an existing file is kept).  -> its path"""
+    os.makedirs(os.path.join(data_dir, "f0"), exist_ok=True)
+    path = os.path.join(data_dir, "f0", crepe_blob_name(as_preset or preset))
+    if force or not os.path.exists(path):
+        write_blob(path, *make_crepe(preset))
+    return path
+
+
 SYNTH_PRESETS = {
     # SynthesizerTrnMs768NSFsid v2-48k: SURVEY.md Appendix A.3
     "full": dict(inter=192, hidden=192, filter=768, heads=2, enc_layers=6, enc_k=3, window=10,
