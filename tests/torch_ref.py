@@ -134,11 +134,141 @@ def rmvpe_salience(cfg, t, mel: np.ndarray) -> np.ndarray:
     return y[0].numpy()
 
 
+def _ln_c(x, g, b):
+    return F.layer_norm(x.transpose(1, 2), (x.shape[1],), g, b, 1e-5).transpose(1, 2)
+
+
+# ------------------------------------------------------------------------------------------------
+# ContentVec and RMVPE in pieces, each a function of torch tensors with a leading batch axis of 1, written with torch.nn.functional alone
+# (tests/front_stage_ref.py evaluates them one at a time in fp64 under precision(); tests/test_front_stage_ref.py pins their fp32 chain
+# to contentvec_hf / rmvpe_salience above and to the oracle's taps).  The keyword arguments that are not None / True / "back" / False by
+# default exist for the planted mistakes of that test only.
+# ------------------------------------------------------------------------------------------------
+def _lin_c(x, w, b=None):
+    """a Linear layer on [1][C][T]"""
+    return F.conv1d(x, _t(w)[:, :, None], None if b is None else _t(b))
+
+
+def cv_conv0(cfg, t, wav):
+    """wav (1, L) -> (1, C, T0): Conv1d(1 -> C, no bias) + GroupNorm with one group per channel + GELU"""
+    C = int(cfg["conv_dim"])
+    y = F.conv1d(wav[:, None], _t(t["cv.conv0.w"]), stride=int(cfg["conv_s0"]))
+    return F.gelu(F.group_norm(y, C, _t(t["cv.gn.g"]), _t(t["cv.gn.b"]), 1e-5))
+
+
+def cv_stem(cfg, t, x):
+    """the six strided convolutions behind the first, each followed by GELU"""
+    for i in range(1, 7):
+        x = F.gelu(F.conv1d(x, _t(t["cv.conv%d.w" % i]), stride=int(cfg["conv_s%d" % i])))
+    return x
+
+
+def cv_proj(cfg, t, x):
+    return _lin_c(_ln_c(x, _t(t["cv.ln0.g"]), _t(t["cv.ln0.b"])), t["cv.proj.w"], t["cv.proj.b"])
+
+
+def cv_pos(cfg, t, h, norm=True, pad=None, drop="back"):
+    """h + GELU(grouped positional convolution), then the encoder's LayerNorm (norm=False: the sum alone)"""
+    pk = int(cfg["pos_k"])
+    pc = F.conv1d(h, _t(t["cv.pos.w"]), _t(t["cv.pos.b"]), padding=pk // 2 if pad is None else pad, groups=int(cfg["pos_groups"]))
+    if pk % 2 == 0:
+        pc = pc[:, :, :-1] if drop == "back" else pc[:, :, 1:]
+    if pc.shape[2] != h.shape[2]:                       # (a planted padding mistake shortens the convolution: aligned at the front)
+        pc = F.pad(pc, (0, h.shape[2] - pc.shape[2]))
+    x = h + F.gelu(pc)
+    return _ln_c(x, _t(t["cv.enc_ln.g"]), _t(t["cv.enc_ln.b"])) if norm else x
+
+
+def cv_attention(cfg, t, l, x):
+    """HuBERT self-attention of layer l including the output projection, without the residual"""
+    pre, heads = "cv.l%d." % l, int(cfg["heads"])
+    b, E, T = x.shape
+    d = E // heads
+    q = _lin_c(x, t[pre + "q.w"], t[pre + "q.b"]) * d ** -0.5
+    k = _lin_c(x, t[pre + "k.w"], t[pre + "k.b"])
+    v = _lin_c(x, t[pre + "v.w"], t[pre + "v.b"])
+    q, k, v = (a.view(b, heads, d, T).transpose(2, 3) for a in (q, k, v))
+    p = F.softmax(torch.matmul(q, k.transpose(-2, -1)), dim=-1)
+    a = torch.matmul(p, v).transpose(2, 3).contiguous().view(b, E, T)
+    return _lin_c(a, t[pre + "o.w"], t[pre + "o.b"])
+
+
+def cv_layer(cfg, t, l, x, norm=True):
+    """post-LN HuBERT layer l (norm=False: up to and including the residual sum behind ff2, without its LayerNorm)"""
+    pre = "cv.l%d." % l
+    h = _ln_c(x + cv_attention(cfg, t, l, x), _t(t[pre + "ln1.g"]), _t(t[pre + "ln1.b"]))
+    y = h + _lin_c(F.gelu(_lin_c(h, t[pre + "ff1.w"], t[pre + "ff1.b"])), t[pre + "ff2.w"], t[pre + "ff2.b"])
+    return _ln_c(y, _t(t[pre + "ln2.g"]), _t(t[pre + "ln2.b"])) if norm else y
+
+
+def cv_pending_ln(cfg, t, l):
+    """the LayerNorm a not yet normalised input of layer l is waiting for: the encoder's for layer 0, ln2 of layer l - 1 otherwise"""
+    return (t["cv.enc_ln.g"], t["cv.enc_ln.b"]) if l == 0 else (t["cv.l%d.ln2.g" % (l - 1)], t["cv.l%d.ln2.b" % (l - 1)])
+
+
+def cv_final_proj(cfg, t, x):
+    return _lin_c(x, t["cv.final_proj.w"], t["cv.final_proj.b"])
+
+
+def rm_input(cfg, t, mel):
+    """log-mel (1, 128, Tm) -> the network's image (1, 1, Tm, 128)"""
+    return mel.transpose(1, 2)[:, None] * float(t["rm.bn0"][0]) + float(t["rm.bn0"][1])
+
+
+def rm_blocks(t, fmt, n, x):
+    for j in range(n):
+        x = _cbr(t, fmt % j, x)
+    return x
+
+
+def rm_pool(x, pick=False):
+    """AvgPool2d(2) (pick: the planted mistake, the top left pixel of every 2 x 2 square)"""
+    return x[:, :, ::2, ::2] if pick else F.avg_pool2d(x, 2)
+
+
+def rm_enc(cfg, t, lv, x, pick=False):
+    """encoder level lv from the previous level's output before its pooling (level 0: from rm_input's image)"""
+    if lv > 0:
+        x = rm_pool(x, pick)
+    return rm_blocks(t, "rm.enc%d.b%%d." % lv, int(cfg["n_blocks"]), x)
+
+
+def rm_int(cfg, t, x, pick=False):
+    x = rm_pool(x, pick)
+    for lv in range(int(cfg["inter_layers"])):
+        x = rm_blocks(t, "rm.int%d.b%%d." % lv, int(cfg["n_blocks"]), x)
+    return x
+
+
+def rm_dec(cfg, t, lv, x, skip, swap=False):
+    """decoder level lv: transposed convolution + ReLU, concat (up first, skip second; swap: the planted mistake), blocks"""
+    up = F.relu(F.conv_transpose2d(x, _t(t["rm.dec%d.up.w" % lv]), _t(t["rm.dec%d.up.b" % lv]), stride=2, padding=1, output_padding=1))
+    return rm_blocks(t, "rm.dec%d.b%%d." % lv, int(cfg["n_blocks"]), torch.cat([skip, up] if swap else [up, skip], dim=1))
+
+
+def rm_cnn(cfg, t, x):
+    """the head convolution in the GRU's layout: (1, 3 * 128, Tm), row c * 128 + mel"""
+    y = F.conv2d(x, _t(t["rm.cnn.w"]), _t(t["rm.cnn.b"]), padding=1)           # (1, 3, Tm, 128)
+    return y.permute(0, 1, 3, 2).reshape(y.shape[0], -1, y.shape[2])
+
+
+def rm_gru(cfg, t, feat):
+    """(1, 384, Tm) -> (1, 2 H, Tm): input projection + bidirectional GRU"""
+    H = int(cfg["gru_hidden"])
+    gru = torch.nn.GRU(feat.shape[1], H, num_layers=1, batch_first=True, bidirectional=True).to(feat.dtype)
+    for sfx, mine in (("", "f"), ("_reverse", "b")):
+        for hf, nm in (("weight_ih", "w_ih"), ("weight_hh", "w_hh"), ("bias_ih", "b_ih"), ("bias_hh", "b_hh")):
+            getattr(gru, hf + "_l0" + sfx).copy_(_t(t["rm.gru.%s_%s" % (nm, mine)]))
+    return gru(feat.transpose(1, 2))[0].transpose(1, 2)
+
+
+def rm_sal(cfg, t, y):
+    return torch.sigmoid(_lin_c(y, t["rm.fc.w"], t["rm.fc.b"]))
+
+
 # ------------------------------------------------------------------------------------------------
 # synthesizer
 # ------------------------------------------------------------------------------------------------
-def _ln_c(x, g, b):
-    return F.layer_norm(x.transpose(1, 2), (x.shape[1],), g, b, 1e-5).transpose(1, 2)
 
 
 def _rel_attn(t, l, x, heads, window):
