@@ -182,6 +182,7 @@ GEOMS = {
     16: (0, 32, 16),
     17: (5, 34, 19),        # skip_head + R = 2 T + 1: frames 36, 37 and 38 all read the last column (the clamp bites for frame 38)
     33: (0, 66, 33),        # three query groups of the one-launch form: 16, 16, 1
+    176: (48, 351, 223),    # the file converter's default window (k = 14): frames 0 .. 350 read ContentVec columns 24 .. 199, eleven query groups
 }
 
 

@@ -99,3 +99,23 @@ def test_wav_round_trip_and_peak_rule(tmp_path):
     assert rate == 40000 and np.allclose(z, [0.2475, -0.99, 0.495], rtol=0, atol=2.0 / 32768.0) and np.max(np.abs(z)) < 1.0
     write_wav(tmp_path / "c.wav", np.zeros(0, np.float32), 16000)
     assert len(read_wav(tmp_path / "c.wav")[0]) == 0
+
+
+def test_long_window_geometries_of_the_stage_tests():
+    # tests/test_gpu_long_windows.py: one window is n = 5120 k - 160 samples, Tm = 32 k f0 frames (n == the f0 frame), T = 16 k - 1 ContentVec frames and
+    # R = F - 2 C returned ones -- its table against rvc_convert_geometry, and the far-end row's context C = ceil((F - 351) / 2)
+    import long_shapes as LW
+    import yin_ref as Y
+    rows = dict(LW.GEOMETRIES)
+    for k in (31, 32):
+        rows[(k, LW.far_end_context(k), 1)] = (32 * k, 16 * k - 1, 351)
+    assert LW.far_end_context(31) == 320 and LW.far_end_context(32) == 336 and LW.far_end_context(14) == 48
+    for (k, ctx, xf), (Tm, T, R_) in rows.items():
+        geo = RvcInfer.convert_geometry(160, 4800, k, ctx, xf)
+        F = 32 * k - 1
+        assert geo["n"] == 160 * F == 5120 * k - 160 and geo["skip_head"] == ctx and geo["return_length"] == R_ == F - 2 * ctx
+        assert geo["sample_frame_16k_size"] == 5120 * (k - 1) and Y.f0_frame(geo["sample_frame_16k_size"]) == geo["n"]      # n == frame
+        assert Tm == 32 * k == 1 + geo["n"] // 160 and T == 16 * k - 1 == (F - 1) // 2 and 2 * T + 1 == F
+        assert ctx + R_ <= 2 * T + 1 and R_ <= LW.R_MAX
+        assert LW.geometry(k, ctx, xf) == (geo["n"], geo["sample_frame_16k_size"], ctx, R_)
+    assert RvcInfer.convert_geometry(160, 4800) == RvcInfer.convert_geometry(160, 4800, 14, 48, 5)

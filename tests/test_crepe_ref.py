@@ -198,6 +198,19 @@ def test_what_the_gpu_tests_assume_of_their_inputs():
             o = R.crepe(t, x, 2560, dec)
             assert np.min(o["margin"]) >= 1e-4, (preset, dec, np.min(o["margin"]))
         assert 0.0 < o["prob"].min() < 0.05 and 0.5 < o["prob"].max() < 0.99
+    # the whole-window input (n == frame: the f0 window is the whole buffer, frames 0..3 and Tm - 4.. are zero-extended past its ends): inside the 10 % cap,
+    # an end frame voiced (else the edge is not tested), float32 decodes the same bins, posteriors not saturated
+    x = Y.whole_window_signal(5120)
+    assert len(x) == Y.f0_frame(5120) == 10080
+    for preset in ("tiny", "micro"):
+        t = W.make_crepe(preset)[1]
+        o, o32 = R.crepe(t, x, 5120, "viterbi"), R.crepe(t, x, 5120, "viterbi", np.float32)
+        assert o["f0"].shape == (64,) and np.sum(o["margin"] < 1e-4) <= 6
+        assert np.any(o["f0"][:4] > 0) or np.any(o["f0"][-4:] > 0)
+        assert np.array_equal(o["bins"], o32["bins"])
+        assert 0.0 < o["prob"].min() < 0.05 and 0.5 < o["prob"].max() < 0.99
+        # frame 0: 512 zeros in front of the buffer's first 512 samples, then normalised -- its first half is one constant, its second is not
+        assert np.ptp(o["frames"][0][:512]) == 0.0 and np.ptp(o["frames"][0][512:]) > 0.1 and np.ptp(o["frames"][63][-511:]) == 0.0
 
 
 def test_cli_names_the_presets_by_their_files():

@@ -156,3 +156,21 @@ def test_inputs_of_the_gpu_tests_sit_on_no_decision_boundary():
     # the settings changed between two chunks of one stream (stream 0's first chunk neutral, stream 1's second chunk conditioned)
     assert np.sum(_quality(*Y.yin(xs[1][1], 2560), "changed", 12, 0.0) > 0) >= 6
     assert np.sum(Y.yin(xs[0][0], 2560)[1] < 1e-4) == 0
+
+
+def test_whole_window_input_of_the_gpu_test():
+    # tests/test_gpu_f0cond.py test_pitch_over_the_default_converter_window: the k = 14 window (448 rows) under a width-7 median and a C major snap leaves at
+    # most 10 % of its rows next to a decision boundary, keeps voiced rows at the window's end, and float32 changes no sure decision
+    frame16k = 5120 * 13
+    x = Y.whole_window_signal(frame16k)
+    f0, ym = Y.yin(x, frame16k)
+    kw = F.settings("stream1")
+    assert kw["r"] == 3 and kw["mask"] == F.SCALE_C_MAJOR
+    ref, margin, gm, _ = F.condition(f0, parts=True, **kw)
+    sure = (F.window_min(ym, 3) >= 1e-4) & (margin >= F.SNAP_MARGIN) & (gm >= F.GATE_MARGIN)
+    assert ref.shape == (448,) and np.sum(~sure) <= 0.10 * 448, np.sum(~sure)
+    assert np.any((ref[-4:] > 0) & sure[-4:]) and np.sum((ref > 0) & sure) >= 224
+    f32, _ = F.condition(Y.yin(x, frame16k, np.float32)[0], dtype=np.float32, **kw)
+    assert np.array_equal(f32[sure] > 0, ref[sure] > 0)
+    v = sure & (ref > 0)
+    assert np.max(np.abs(f32[v].astype(np.float64) - ref[v]) / ref[v]) < 1e-5

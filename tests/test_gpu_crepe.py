@@ -92,6 +92,28 @@ def test_stages_against_float64(data, preset):
     e.close()
 
 
+@pytest.mark.parametrize("preset", ["tiny", "micro"])
+def test_stages_over_a_whole_converter_window(data, preset):
+    """n == frame, as every window of the file converter: the f0 window starts at sample 0 of the buffer, so frames 0..3 and 60..63 are zero-extended
+    past the buffer's own ends (a DC step sits on each).  64 frames (k = 2); the bounds are _check_stages' own, from this input's float32 run"""
+    frame16k = 5120
+    x = Y.whole_window_signal(frame16k)
+    assert len(x) == Y.f0_frame(frame16k)
+    e = _engine(data["zoo"]["data"] if preset == "tiny" else data["micro"])
+    e.enable_taps(True)
+    f0 = e.pitch(x, 0, frame16k)
+    assert f0.shape == (64,) and np.all(np.isfinite(f0))
+    t = data[preset + "_t"]
+    r64, r32 = R.crepe(t, x, frame16k, "viterbi"), R.crepe(t, x, frame16k, "viterbi", np.float32)
+    assert np.array_equal(r64["bins"], r32["bins"])
+    _check_stages(e, r64, r32, what="whole window, " + preset)
+    v = (r64["f0"] > 0) & (r32["f0"] > 0)
+    base = float(np.max(np.abs(r32["f0"][v].astype(np.float64) - r64["f0"][v]) / r64["f0"][v])) if v.any() else 0.0
+    _check_f0(f0, r64["f0"], r64["margin"], max(8.0 * base, 1e-6))
+    assert np.any(r64["f0"][:4] > 0) or np.any(r64["f0"][-4:] > 0)
+    e.close()
+
+
 def test_stages_three_streams(data):
     z = data["zoo"]
     xs = np.stack([voice_signal(g.input_buffer_16k_size, seed=s + 1) for s in range(3)])

@@ -208,6 +208,38 @@ def test_pitch_against_the_reference(base, name, case):
             assert not np.array_equal(got, got0)
 
 
+def test_pitch_over_the_default_converter_window():
+    """the file converter's default window (k = 14): 71 520 samples, n == the f0 frame, 448 rows in the LDS-resident window.  A median of width 7 and a
+    C major snap of strength 0.7 (case `stream1`) filter it across its whole length; the same reference, margins and bound rule as above"""
+    frame16k, case = 5120 * 13, "stream1"
+    x = Y.whole_window_signal(frame16k)
+    assert len(x) == Y.f0_frame(frame16k) == 71520
+    c = F.CASES[case]
+    ref0, ymargin = Y.yin(x, frame16k)
+    b = {"ref": ref0, "margin": ymargin, "f32": Y.yin(x, frame16k, np.float32)[0]}
+    bound = _bound(b, case)
+    ref, margin, gm, _ = F.condition(ref0, parts=True, **F.settings(case))
+    sure = _sure(ymargin, margin, gm, c["r"])
+    e = _engine(zoo("tiny"), full=False)
+    try:
+        got0 = e.pitch(x, 0, frame16k)
+        _apply(e, case)
+        got = e.pitch(x, 0, frame16k)
+    finally:
+        e.close()
+    assert got.shape == (448,) and got.dtype == np.float32
+    v = _check(got, ref, sure, bound, "whole window / %s" % case)
+    assert v[-4:].any() and v.sum() >= 224                              # voiced rows at the window's end, where the median's window leaves the buffer
+    assert not np.array_equal(got, got0)
+    # structure: with the snap off the filtered rows are medfilt of the same engine's unfiltered rows, bit for bit, over all 448
+    e = _engine(zoo("tiny"), full=False)
+    try:
+        _apply(e, "median3")
+        assert np.array_equal(e.pitch(x, 0, frame16k), medfilt(got0, 7))
+    finally:
+        e.close()
+
+
 # ---- 6. per stream, two chunks, three streams ----
 def _cache_ref(chunks, case, pitch_shift):
     """reference pitch cache of one stream after the chunks (infer calls: the formant factor (float)2^0 is part of the multiplier), and which entries are sure"""

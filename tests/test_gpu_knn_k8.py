@@ -131,6 +131,30 @@ def test_graph_replay(eng, cases):
             assert same_bits(g[key].view(np.float32), eager[p][key].view(np.float32)), (p, key)
 
 
+# ---- 2b. the file converter's default window ----
+@pytest.mark.parametrize("streams", [1, 3])
+def test_converter_window(eng, streams):
+    """k = 14: T = 223 ContentVec columns, skip_head 48, 351 frames -- 176 raw frames, eleven query groups of the one-launch form; 1 and 3 streams, every path
+    (the aid's path 0 and its fallback list, path 1, among them), eager and replayed.  Frame r reads column (48 + r) / 2: frame 350 reads column 199, and
+    the duplicate runs of the index sit on columns 24 and 199, the first and the last one read"""
+    case = R.make_case("near_runs12", dim=48, n=1023, streams=streams, nq=176, seed=1400 + streams)
+    assert (case.skip_head, case.R, case.T) == (48, 351, 223)
+    eager = run_case(eng, case, MANY)
+    assert eng.set_k(8) == 0
+    cv = R.to_cv(case.q, case.T + 5)
+    for p in ("fused", "fallback"):
+        g = eng.run(cv, case.skip_head, case.R, case.T, path=p, wgs=768, reps=2, graph=1)
+        for key in ("idx", "dist", "phone"):
+            assert same_bits(g[key].view(np.float32), eager[p][key].view(np.float32)), (p, key)
+        raw = eng.run(cv, case.skip_head, case.R, case.T, rate=0.0, path=p, wgs=768)          # rate 0: the gather alone
+        cols = R.col_map(case.skip_head, case.R, case.T)
+        assert cols[350] == 199 and same_bits(raw["phone"][:, :, 350], cv[:, :, 199])
+        assert same_bits(np.ascontiguousarray(raw["phone"][:, :, :case.R]), np.ascontiguousarray(cv[:, :, cols]))
+    b = streams - 1                                                                              # the runs planted on the last column read: frame 350's hits
+    rows = {r for pb, t, row, ln in case.meta["places"] if (pb, t) == (b, 199) for r in range(row, row + ln)}
+    assert len(rows) >= 12 and set(eager["fused"]["idx"][b, 350].tolist()) <= rows
+
+
 # ---- 3. the API ----
 def test_api(eng):
     fresh = Engine()

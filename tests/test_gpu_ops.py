@@ -20,6 +20,7 @@ import pytest
 import op_ref as R
 from common import set_opt
 from debug_abi import RVC_SHAPE, Handle, OpSpec, index, ptr, same_bits, stray
+from long_shapes import LDS_LIMIT, LONG_GRU, LONG_RELPOS, attn_valu_lds
 
 pytestmark = pytest.mark.gpu
 
@@ -92,11 +93,11 @@ class Ops(Handle):
 class Case:
     """one op at one shape: spec fields, host data (fp32 as uploaded) and the fp64 reference"""
 
-    def __init__(self, op, B, T, label, **spec):
-        self.op, self.B, self.T, self.label = op, B, T, label
+    def __init__(self, op, B, T, label, long=False, **spec):
+        self.op, self.B, self.T, self.label, self.long = op, B, T, label, long      # long: a file converter's window length (LONG_* below)
         self.spec = dict(op=op, streams=B, E=0, heads=1, T=T, window=0, C=0, H=0, x_halo=0, y_halo=0)
         self.spec.update(spec)
-        self._data = None
+        self._data, self._d32 = None, None
 
     def __repr__(self):
         return self.label
@@ -120,6 +121,15 @@ class Case:
             for h in range(heads):                                         # key T // 2 dominates query 1: logit 40 against the others' ~13
                 q1 = qkv[:, h * hd:(h + 1) * hd, 1].astype(np.float64)
                 qkv[:, E + h * hd:E + (h + 1) * hd, T // 2] = (q1 * (40.0 * np.sqrt(hd) / np.sum(q1 * q1, axis=1, keepdims=True))).astype(np.float32)
+        if self.long and T > 2 * self.spec["window"] + 8:
+            # converter lengths: the dominant key of query 2 sits in the last column and that of query 3 in column 0 (a dropped tail tile, a padding
+            # column taken for a key or a lost first column moves the output by O(1)); query T - 1 - window / 2 is query 2 again, so its weight
+            # also sits on key T - 1 -- inside its relative window, which is clamped at the end of the sequence
+            for h in range(heads):
+                for qi, kj in ((2, T - 1), (3, 0)):
+                    qq = qkv[:, h * hd:(h + 1) * hd, qi].astype(np.float64)
+                    qkv[:, E + h * hd:E + (h + 1) * hd, kj] = (qq * (40.0 * np.sqrt(hd) / np.sum(qq * qq, axis=1, keepdims=True))).astype(np.float32)
+            qkv[:, :E, T - 1 - self.spec["window"] // 2] = qkv[:, :E, 2]
         w0 = w1 = None
         if rel:
             w = self.spec["window"]
@@ -129,6 +139,27 @@ class Case:
         else:
             ref = R.mha(qkv, heads)
         return qkv, w0, w1, ref, np.ones(B)
+
+    def d32(self):
+        """deviation of the float32-numpy restatement from float64, in the metric of value_error (computed once)"""
+        if self._d32 is None:
+            self._d32 = value_error(self, self.ref32())
+        return self._d32
+
+    def tol(self):
+        """the family's tolerance; a converter-length case whose float32 restatement does not fit a quarter of it gets 4 x that deviation instead (the rule
+        of tests/test_gpu_stream_taps.py) -- never a wider constant"""
+        return max(TOL[self.op], 4.0 * self.d32()) if self.long else TOL[self.op]
+
+    def ref32(self):
+        """the fp64 definition of this case evaluated in float32 numpy on the same inputs (attention and GRU): the base a tolerance is judged against"""
+        x, w0, w1, _, _ = self.data()
+        if self.op == OP_GRU:
+            H = self.spec["H"]
+            return R.gru_bidir(x, w0.reshape(2, 3 * H, H), w1.reshape(2, 3 * H), dtype=np.float32)
+        if self.op == OP_REL:
+            return R.relpos_mha(x, self.spec["heads"], w0, w1, self.spec["window"], dtype=np.float32)
+        return R.mha(x, self.spec["heads"], dtype=np.float32)
 
     def _data_relpos(self, rng):
         return self._data_attn(rng, rel=True)
@@ -213,6 +244,12 @@ def attn_eligible(c, v):
     return {"mfma2": hd == 64 and T <= 128, "mfma4": hd == 64 and T <= 256, "valu": True}[v.replace("_qloop", "")]
 
 
+def long_cases():
+    """the converter-length cases of relative attention and GRU (tests/long_shapes.py; tests/test_op_ref.py holds their float32 restatements against a quarter
+    of the tolerance on the CPU)"""
+    return [c for c in relpos_cases() + gru_cases() if c.long]
+
+
 @functools.lru_cache(None)
 def relpos_cases():
     out = []
@@ -221,6 +258,8 @@ def relpos_cases():
             for T in sorted({1, 2, w, w + 1, 2 * w + 1, 16, 17, 21, 32, 33, 35, 63, 64, 65, 155}):
                 for B in ((1, 4, 5, 16) if kc != 96 else (1, 5, 16)):
                     out.append(Case(OP_REL, B, T, "relpos_kc%d_w%d_T%d_B%d" % (kc, w, T, B), E=2 * kc, heads=2, window=w))
+    for kc, T, B in LONG_RELPOS:
+        out.append(Case(OP_REL, B, T, "relpos_kc%d_w10_T%d_B%d" % (kc, T, B), long=True, E=2 * kc, heads=2, window=10))
     return out
 
 
@@ -266,6 +305,8 @@ def gru_cases():
                 if H == 256 and B == 9 and T in (2, 32, 160):
                     continue
                 out.append(Case(OP_GRU, B, T, "gru_H%d_T%d_B%d" % (H, T, B), H=H))
+    for H, T, B in LONG_GRU:
+        out.append(Case(OP_GRU, B, T, "gru_H%d_T%d_B%d" % (H, T, B), long=True, H=H))
     return out
 
 
@@ -306,7 +347,9 @@ def _run_checked(ops, case, forced=None, **kw):
         return None, ["%s: rvc_debug_op failed (%d): %s" % (tag, rc, bad[0])]
     bad = ["%s [%s]: %s" % (case.label, var, b) for b in bad]
     e = value_error(case, got)
-    if not e < TOL[case.op]:
+    if case.long:
+        print("%s [%s]: max err / rms %.3e, float32 numpy %.3e, ratio %.2f (bound %.2e)" % (tag, var, e, case.d32(), e / case.d32(), case.tol()))
+    if not e < case.tol():
         _, _, _, ref, _ = case.data()
         wi = np.unravel_index(int(np.argmax(np.abs(got.astype(np.float64) - ref))), ref.shape)
         bad.append("%s [%s]: max err / rms %.3e at %s (gpu %.7g, ref %.7g)" % (tag, var, e, wi, got[wi], ref[wi]))
@@ -338,7 +381,7 @@ def test_forced_variant(ops, op, variant):
     cases_of, _, eligible = FAMILIES[op]
     fails, ran = [], 0
     for c in cases_of():
-        if c.B not in (1, 5, 8, 9, 20):
+        if c.B not in (1, 5, 8, 9, 20) and not c.long:
             continue
         if eligible(c, variant):
             var, bad = _run_checked(ops, c, forced=variant)
@@ -369,6 +412,27 @@ def test_hook_rejects_unknown_variant(ops):
 def test_attention_beyond_the_lds_limit_is_refused(ops):
     for hd, E, T in ((64, 128, 500), (12, 24, 1456)):
         assert ops.run(Case(OP_MHA, 1, T, "attn_lds_T%d" % T, E=E, heads=2))[0] == RVC_SHAPE
+
+
+def test_relpos_attention_beyond_the_lds_limit_is_refused(ops):
+    """return_length 351 is the last the synthesizer's attention holds at head size 96: 352 and 353 (one odd-padded row of 353) are refused and nothing is
+    launched.  The rule is restated here (attn_valu_lds), so it cannot move without this test moving"""
+    assert attn_valu_lds(96, 351) == 163392 <= LDS_LIMIT < attn_valu_lds(96, 352) == attn_valu_lds(96, 353) == 164288
+    assert ops.run(Case(OP_REL, 1, 16, "relpos_lds_before", E=192, heads=2, window=10))[0] == 0
+    before = ops.last_kernel()
+    for T in (352, 353):
+        for B in (1, 3):
+            c = Case(OP_REL, B, T, "relpos_lds_T%d_B%d" % (T, B), E=192, heads=2, window=10)
+            c._data = (np.zeros((B, 3 * 192, T), np.float32), np.zeros((21, 96), np.float32), np.zeros((21, 96), np.float32), None, None)
+            rc, _, _, msg, _ = ops.run(c)
+            assert rc == RVC_SHAPE and "LDS" in msg[0], (T, B, rc, msg)
+            assert ops.last_kernel() == before, (T, B, ops.last_kernel())       # nothing was launched
+    for v in ("mfma", "small"):                                                # ... under a forced variant too
+        set_opt("RVC_RELPOS_KERNEL", v)
+        try:
+            assert ops.run(c)[0] == RVC_SHAPE
+        finally:
+            set_opt("RVC_RELPOS_KERNEL", None)
 
 
 @pytest.mark.parametrize("B,T", [(1, 64), (8, 256), (3, 17)])

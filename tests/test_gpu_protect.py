@@ -102,6 +102,34 @@ def test_kernel_alone(bare, Cc, R_, B):
     assert seen_parity == {0, 1}
 
 
+@pytest.mark.parametrize("ph_ld,cv_ld", [(352, 224), (353, 224)], ids=["plan_ld", "odd_ld"])
+def test_kernel_at_the_default_converter_window(bare, ph_ld, cv_ld):
+    """the file converter's default window (k = 14): 3 streams, 768 channels, T = 223 ContentVec frames, skip_head 48, 351 rows -- the last one is row
+    48 + 350 = 398, ContentVec frame 199.  Leading dimensions padded to 4 floats as the plan pads them, and an odd one.  Every stream has an unvoiced
+    run that starts at row 0 and one that ends at row 350; values 0 (the raw rows, bit for bit), 0.33 and 0.5 (off)"""
+    B, Cc, T, skip_head, R_ = 3, 768, 223, 48, 351
+    values = (0.0, 0.33, 0.5)
+    rng = np.random.default_rng(351 + ph_ld)
+    phone = rng.standard_normal((B, Cc, ph_ld)).astype(np.float32)
+    cv = rng.standard_normal((B, Cc, cv_ld)).astype(np.float32)
+    pitchf = np.full((B, R_), 220.0, np.float32)
+    for b in range(B):
+        pitchf[b, :7 + b] = 0.0                                          # from row 0
+        pitchf[b, R_ - 5 - 64 * b:] = 0.0                                # to row 350 (stream 2: across the 256th row)
+        pitchf[b, 100 + b:300:37] = 0.5                                  # single unvoiced rows in between
+    for graph in (False, True):
+        got = _debug_protect(bare, phone, cv, pitchf, values, R_, T, skip_head, graph=graph)
+        assert np.array_equal(got[:, :, R_:], phone[:, :, R_:])
+        for b in range(B):
+            uv = _check_mix(got[b, :, :R_], phone[b, :, :R_], cv[b, :, :T], pitchf[b], values[b], skip_head, "k = 14 window, ph_ld %d stream %d" % (ph_ld, b))
+            on = float(np.float32(values[b])) < 0.5
+            assert uv.sum() == (int(np.sum(pitchf[b] < 1)) if on else 0) and (not on or (uv[0] and uv[R_ - 1]))
+            if not on:
+                assert np.array_equal(got[b], phone[b])
+    assert np.array_equal(P.raw_rows(cv[0, :, :T], skip_head, R_)[:, R_ - 1], cv[0, :, (skip_head + R_ - 1) // 2])     # row 350 reads frame 199
+    assert (skip_head + R_ - 1) // 2 == 199
+
+
 def test_debug_hook_rejects_bad_shapes(bare):
     ph, cv, pf = np.zeros((1, 4, 8), np.float32), np.zeros((1, 4, 4), np.float32), np.zeros((1, 8), np.float32)
     for kw in (dict(R_=8, T=4, skip_head=2), dict(R_=8, T=5, skip_head=0)):       # skip_head + R > 2 T + 1; cv_ld < T

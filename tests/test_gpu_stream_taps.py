@@ -127,9 +127,10 @@ class Report:
         assert not self.bad, (self.tag, self.bad)
 
 
-def _front_taps(rep, eng, p, gs, otaps, phi=0.0):
+def _front_taps(rep, eng, p, gs, otaps, phi=0.0, hints=HINTS):
     """ContentVec, RMVPE and f0 of plan stream p (engine stream gs) against that stream's oracle.  phi: the stream's formant shift -- by definition
-     its f0 multiplier carries (float)2^(-phi/12); the oracle has no formant shift"""
+     its f0 multiplier carries (float)2^(-phi/12); the oracle has no formant shift.  hints: the f0 frames Tm of the
+    window, per transposed tap"""
     raw = _has(eng, "cv.pos.raw", p)             # plans with folded LayerNorms hold these two not yet normalised
     n = 0
     for oname, ename, tr in TAP_MAP:
@@ -140,14 +141,15 @@ def _front_taps(rep, eng, p, gs, otaps, phi=0.0):
         if oname == "f0" and phi:
             a = a * np.float32(2.0 ** (-phi / 12.0))
         if tr == "T":
-            b = b.reshape(-1, HINTS[oname]).T.reshape(-1)
+            b = b.reshape(-1, hints[oname]).T.reshape(-1)
         rep.add(gs, oname, rel_rms(b, a), 1e-4)
         n += 1
     assert n >= 12, n
 
 
-def _synth_stages(rep, cfg, tens, eng, p, gs, R, pcm, only=None):
-    """every tapped interval of the synthesizer of plan stream p (engine stream gs: its Philox stream id is ID0 + gs), teacher-forced"""
+def _synth_stages(rep, cfg, tens, eng, p, gs, R, pcm, only=None, skip_head=g.skip_head, chunk=1):
+    """every tapped interval of the synthesizer of plan stream p (engine stream gs: its Philox stream id is ID0 + gs), teacher-forced.  skip_head and
+    chunk (the Philox chunk counter of the call that was tapped) default to this file's: the streaming window, second chunk"""
     from oracle import oracle as O
     C, H, I, fn, n_ups = (int(cfg[k]) for k in ("phone_dim", "hidden", "inter", "flow_n", "n_ups"))
 
@@ -166,7 +168,7 @@ def _synth_stages(rep, cfg, tens, eng, p, gs, R, pcm, only=None):
     phone = tap("phone_ct", C)
     assert phone.shape == (C, R)
     if only is None:
-        rep.bits(gs, "gather", phone, SR.phone_gather(tap("cv.out", C), g.skip_head, R))
+        rep.bits(gs, "gather", phone, SR.phone_gather(tap("cv.out", C), skip_head, R))
     pitchf = eng.tap("pitchf").reshape(-1, R)[p]
     emb = tap("sy.emb", H)
     single("embed", emb, SR.embed, cfg, tens, phone, pitchf)
@@ -179,7 +181,7 @@ def _synth_stages(rep, cfg, tens, eng, p, gs, R, pcm, only=None):
         assert _has(eng, "sy.enc.raw", p)
         multi("enc+stats", stats, SR.encoder_stats, cfg, tens, emb)
     zp = tap("sy.zp", I)
-    eps = O.philox_normal(SEED, ID0 + gs, 1, 0, I * R).reshape(I, R)          # second chunk: chunk counter 1
+    eps = O.philox_normal(SEED, ID0 + gs, chunk, 0, I * R).reshape(I, R)      # (this file: second chunk, chunk counter 1)
     single("prior", zp, SR.prior, cfg, stats, eps)
     zin = zp
     for fi in reversed(range(fn)):

@@ -198,3 +198,26 @@ def test_formant_shift_and_native_session(yin_case):
     assert np.any(e.pitch_cache() > 0)
     del s
     e.close()
+
+
+@pytest.mark.parametrize("frame16k", [5120, 5120 * 13], ids=["Tm64", "Tm448"])
+def test_pitch_over_a_whole_converter_window(frame16k):
+    """n == frame, as every window of the file converter: the f0 window starts at sample 0 of the buffer, so the first and last frames reflect about
+    the buffer's own first and last samples (a DC step sits on each).  Tm = 64 (k = 2) and the default window's Tm = 448, one workgroup per frame.
+    The bound is this input's own: 8 x the float32-numpy deviation, floor 1e-6 (tests/test_yin_ref.py shows the reference side)"""
+    x = Y.whole_window_signal(frame16k)
+    Tm = frame16k // 160 + 32
+    assert len(x) == Y.f0_frame(frame16k) == 160 * (Tm - 1)
+    ref, margin = Y.yin(x, frame16k)
+    f32, _ = Y.yin(x, frame16k, np.float32)
+    v = (ref > 0) & (f32 > 0) & (margin >= MARGIN)
+    base = float(np.max(np.abs(f32[v].astype(np.float64) - ref[v]) / ref[v]))
+    bound = max(8.0 * base, 1e-6)
+    print("Tm %d: float32 numpy against float64 %.3e -> bound %.3e" % (Tm, base, bound))
+    e = _engine(zoo("tiny"), full=False)
+    got = e.pitch(x, 0, frame16k)
+    e.close()
+    assert got.shape == (Tm,) and np.any(ref[-4:] > 0)
+    _check(got, ref, margin, bound)
+    for t in (0, 1, 2, 3, Tm - 4, Tm - 3, Tm - 2, Tm - 1):
+        print("  frame %3d: gpu %.6f, float64 %.6f, margin %.2e" % (t, got[t], ref[t], margin[t]))

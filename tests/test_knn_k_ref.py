@@ -57,6 +57,21 @@ def test_candidate_counts_far_from_knn_cand(cases):
     assert counts(t).max() <= R.KNN_CAND // 8
 
 
+def test_converter_window_case():
+    """the file converter's default window as tests/test_gpu_knn_k8.py runs it: skip_head 48, 351 frames over T = 223 columns; frame r reads column
+    (48 + r) / 2 -- 24 for r = 0, 199 for r = 350, no clamp -- which is 176 raw frames; the duplicate runs sit on the first and the last of them; the
+    candidate counts are far from KNN_CAND at both stream counts"""
+    assert KR.GEOMS[176] == (48, 351, 223) and KR.raw_range(48, 351, 223) == (24, 176)
+    cols = KR.col_map(48, 351, 223)
+    assert cols[0] == 24 and cols[350] == 199 and cols[349] == 198 and cols.max() < 222
+    for streams in (1, 3):
+        c = R.make_case("near_runs12", dim=48, n=1023, streams=streams, nq=176, seed=1400 + streams)
+        assert (c.skip_head, c.R, c.T, c.first_raw) == (48, 351, 223, 24)
+        assert {t for _, t, _, _ in c.meta["places"]} == {24, 199}
+        n = counts(c)
+        assert n.min() >= 8 and n.max() <= R.KNN_CAND // 8, (streams, n.min(), n.max())
+
+
 def test_straddle_counts_at_k8():
     """knn_ref's `straddle` offset (scale 5.5, n = 4099) at K = 8: more than 2 KNN_CAND candidates for some query of every stream with the margin as it is, fewer
     than 0.6 KNN_CAND with half of it -- far from 512 either way, so the class is used as it is"""

@@ -82,3 +82,25 @@ def test_composite_input_of_the_gpu_test():
 
 def test_uppower_truncates_towards_zero():
     assert [Y.uppower(s) for s in (12, 0, -7, -12, 13, -13, 24)] == [2.0, 1.0, 1.0, 0.5, 2.0, 0.5, 4.0]
+
+
+def test_whole_window_input_of_the_gpu_test():
+    # what tests/test_gpu_yin.py's whole-window cases rely on (n == frame: the f0 window is the whole buffer), from the reference alone: at most 10 % of
+    # the frames within 1e-4 of the threshold, an end frame that is voiced (else the reflected edge is not tested), float32 changes no sure decision
+    for frame16k, Tm in ((5120, 64), (5120 * 13, 448)):
+        x = Y.whole_window_signal(frame16k)
+        assert len(x) == Y.f0_frame(frame16k) == 160 * (Tm - 1)
+        assert abs(float(np.mean(x[:512])) - 0.05) < 0.02 and abs(float(np.mean(x[-512:])) + 0.04) < 0.02          # the DC steps
+        F = Y.frames(x, frame16k)
+        assert F.shape == (Tm, 1024)
+        assert np.array_equal(F[0][:512], x[1:513][::-1]) and np.array_equal(F[0][512:], x[:512])           # reflected about sample 0 of the buffer
+        assert np.array_equal(F[Tm - 1][-512:], x[-513:-1][::-1])                                           # ... and about its last sample
+        f0, margin = Y.yin(x, frame16k)
+        assert f0.shape == (Tm,) and np.sum(margin < 1e-4) <= 0.10 * Tm
+        assert np.any(f0[:4] > 0) or np.any(f0[-4:] > 0)
+        assert np.sum(f0 > 0) >= Tm // 2 and np.sum(f0 == 0) >= 8                                            # the composite's unvoiced stretches
+        f32, _ = Y.yin(x, frame16k, np.float32)
+        ok = margin >= 1e-4
+        assert np.array_equal(f32[ok] > 0, f0[ok] > 0)
+        v = ok & (f0 > 0)
+        assert np.max(np.abs(f32[v].astype(np.float64) - f0[v]) / f0[v]) < 1e-6

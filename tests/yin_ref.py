@@ -92,3 +92,17 @@ def composite_signal(n=6000, seed=0):
     x[3600:4400] = 0.3 * np.sin(2.0 * np.pi * 800.0 * t(800) + 0.5)
     x[4560:] = 0.25 * sum(np.sin(2.0 * np.pi * 200.0 * k * t(400)) / k for k in range(1, 4))
     return np.concatenate([0.05 * rng.standard_normal(n - fr), x]).astype(np.float32)
+
+
+def whole_window_signal(frame16k=5120, seed=5):
+    """A whole converter window: exactly f0_frame(frame16k) samples, so the f0 window starts at sample 0 of the buffer (n == frame) and the first and last
+    frames' reflection (YIN) or zero extension (CREPE) touches the buffer's own ends.  voice_signal (a harmonic glide, voiced from the first sample to the
+    last) with the composite's 4960 samples spliced into the middle and a DC step of +0.05 / -0.04 over the first / last 512 samples."""
+    from common import voice_signal
+    n = f0_frame(frame16k)
+    x = voice_signal(n, seed=seed).astype(np.float64)
+    at = (n - 4960) // 2 // 160 * 160
+    x[at:at + 4960] = composite_signal()[-4960:]
+    x[:512] += 0.05
+    x[-512:] -= 0.04
+    return x.astype(np.float32)
