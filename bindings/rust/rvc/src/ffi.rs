@@ -67,6 +67,7 @@ extern "C" {
     // ---- f0 method: RVC_F0_RMVPE (= rvc_load_f0) or RVC_F0_YIN (no weight file)
     pub fn rvc_load_f0_method(e: *mut RvcEngine, method: c_int) -> c_int;
     pub fn rvc_f0_method(e: *mut RvcEngine) -> c_int;
+    pub fn rvc_model_has_f0(e: *mut RvcEngine) -> c_int;
     // ---- CREPE (RVC_F0_CREPE / RVC_F0_CREPE_TINY: <data>/f0/crepe-full.rvcw / crepe-tiny.rvcw): its decoder, RVC_CREPE_VITERBI (default) or RVC_CREPE_ARGMAX
     pub fn rvc_set_crepe_decoder(e: *mut RvcEngine, decoder: c_int) -> c_int;
     pub fn rvc_crepe_decoder(e: *mut RvcEngine) -> c_int;

@@ -89,6 +89,15 @@ impl RvcInfer {
         self.check_load(unsafe { ffi::rvc_set_crepe_decoder(self.handle, decoder) })
     }
 
+    /// Not in the reference: `Some(true)` = the loaded model was trained with pitch guidance, `Some(false)` = without (upstream's `_nono`
+    /// synthesizers: `infer` needs no f0 method and ignores `pitch_shift`), `None` = no model loaded
+    pub fn model_has_f0(&self) -> Option<bool> {
+        match unsafe { ffi::rvc_model_has_f0(self.handle) } {
+            v if v < 0 => None,
+            v => Some(v != 0),
+        }
+    }
+
     /// rvc.rs:77-79
     pub fn unload_model(&mut self) {
         unsafe { ffi::rvc_unload_model(self.handle) }

@@ -97,6 +97,13 @@ int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded *
 #define RVC_CREPE_ARGMAX  1
 rvc_status rvc_set_crepe_decoder(rvc_engine *e, int decoder);
 int rvc_crepe_decoder(rvc_engine *e);
+/* Models trained without pitch guidance (upstream's SynthesizerTrnMs{256,768}NSFsid_nono, `f0: 0` in the checkpoint; blob config key f0 = 0; DESIGN.md
+ * section 22): 1 = the loaded model has pitch guidance, 0 = it has none, -1 = no model loaded.  On a no-f0 model no call of the infer family (rvc_infer*,
+ * rvc_session_process, rvc_convert*, rvc_convert_file*) needs an f0 method or runs one that is loaded: pitch_shift / has_pitch_shift, the pitch controls
+ * (rvc_set_pitch_semitones, _f0_range, _f0_median, _f0_snap), rvc_set_protect, the f0 method and the CREPE decoder are ignored and no part of a plan's identity,
+ * the pitch cache is not written, the chunk counter advances.  Formant shift, the index, graph replay and every other setting apply; chunk pipelining
+ * (rvc_set_pipeline) has no front pair to overlap there: an infer call with it on returns RVC_SHAPE with a message.  rvc_pitch is the tracker's and unchanged. */
+int rvc_model_has_f0(rvc_engine *e);
 
 /* ---- capabilities the reference plumbs through but never implements / bakes into its export ---- */
 /* flat-L2 retrieval index (index_path / index_rate settings, obs-rvc/src/lib.rs:78,81; rvc.rs:159 TODO).  A load that fails behind its argument checks

@@ -27,7 +27,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--data", default=None, help="the engine's data directory (contentvec/, f0/); default: the model zoo of the package")
     p.add_argument("--version", type=int, choices=(1, 2), default=2, help="RVC model version: 1 = 256-dim features, 2 = 768-dim (default)")
     p.add_argument("--f0", choices=("rmvpe", "yin", "crepe-full", "crepe-tiny"), default="rmvpe",
-                   help="f0 method (default rmvpe); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw")
+                   help="f0 method (default rmvpe; not loaded for a model without pitch guidance); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw")
     p.add_argument("--index", default=None, help="retrieval index: a Faiss .index file or a .npy matrix")
     p.add_argument("--index-rate", type=float, default=0.75, help="share of the retrieved features (default 0.75, with --index only)")
     p.add_argument("--index-k", type=int, choices=(4, 8), default=8, help="neighbours blended per frame (default 8, upstream's)")
@@ -112,8 +112,9 @@ def main(argv=None) -> int:
     from .rvc import RvcInfer
     eng = RvcInfer(a.data or W.default_zoo_root("full"), device=a.device)
     eng.load_contentvec(a.version)
-    eng.load_f0_method(a.f0)
     eng.load_model(a.model)
+    if eng.model_has_f0():      # (a model trained without pitch guidance runs no tracker: --f0 names none for it)
+        eng.load_f0_method(a.f0)
     eng.set_streams(a.streams)
     if a.index:
         eng.load_index(a.index, nprobe=a.nprobe or None, k=a.index_k)

@@ -70,6 +70,7 @@ public:
         if (it == cfg_.end()) throw std::runtime_error("blob " + path_ + ": missing cfg " + k);
         return (int)it->second;
     }
+    int icfg_or(const std::string &k, int absent) const { auto it = cfg_.find(k); return it == cfg_.end() ? absent : (int)it->second; }
     bool has(const std::string &k) const { return ten_.count(k) != 0; }
     const BlobTensor &t(const std::string &k) const
     {

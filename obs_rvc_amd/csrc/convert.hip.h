@@ -51,7 +51,7 @@ static rvc_status convert_loaded(rvc_engine *e)
 {
     if (!e->sy) return RVC_MODEL_NOT_LOADED;
     if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;
-    if (!e->f0_method) return RVC_F0_NOT_LOADED;
+    if (!e->f0_method && e->sy->has_f0) return RVC_F0_NOT_LOADED;
     return RVC_OK;
 }
 

@@ -248,11 +248,15 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         ~Swap() { if (on) { e->n_streams = n0; e->d_state = s0; } }
     } swap_guard(e, bucket_B, e->d_state_bucket);
     const int B = e->n_streams;
+    // A model without pitch guidance (ModelSY::has_f0 false): its infer plan has no pitch branch, no source and no protect launch.  The
+    // engine's f0 method and CREPE decoder are no part of such a plan's key (key_f0 / key_dec = 0); the hubert and pitch plans keep theirs
+    const bool nof0 = mode == 0 && e->sy && !e->sy->has_f0;
+    const int key_f0 = nof0 ? 0 : e->f0_method, key_dec = !nof0 && is_crepe(e->f0_method) ? e->crepe_decoder : 0;
     const bool with_index = mode == 0 && e->index.rows && e->index_rate > 0.f;
     // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams (bucket_ids: the
     // streams of a bucket plan; else every stream) has it on.  Which value a stream has is no part of the key: the kernel reads it every chunk
     bool with_protect = false;
-    if (with_index) {
+    if (with_index && !nof0) {      // (upstream applies protect only where it has a pitch)
         if (bucket_ids) { for (int s : *bucket_ids) with_protect = with_protect || e->protect[s] < PROTECT_OFF; }
         else for (double v : e->protect) with_protect = with_protect || v < PROTECT_OFF;
     }
@@ -267,7 +271,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
             p->with_index == with_index && p->with_protect == with_protect && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
-            p->R2 == R2 && p->fstage == fstage && p->f0_method == e->f0_method && p->crepe_decoder == (is_crepe(e->f0_method) ? e->crepe_decoder : 0) && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
+            p->R2 == R2 && p->fstage == fstage && p->f0_method == key_f0 && p->crepe_decoder == key_dec && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -280,15 +284,16 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
     pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_protect = with_protect; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
-    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = e->f0_method; pl.crepe_decoder = is_crepe(e->f0_method) ? e->crepe_decoder : 0; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
+    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = key_f0; pl.crepe_decoder = key_dec; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
     T1 src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;
     // YIN's f0 branch is two short launches.  Test hook RVC_YIN_CV_ALL_CUS = 1 leaves ContentVec on the main stream with every CU under it (measured against
     // the partition: DESIGN.md section 11); not for pipelined calls, whose front branches are the masked pair
-    const bool part = mode == 0 && e->partitioned && !(e->f0_method == RVC_F0_YIN && !e->pipeline && test_opt_int("RVC_YIN_CV_ALL_CUS", 0) == 1);
+    // Without pitch guidance there is no f0 branch at all: the plan is one chain on the main stream, ContentVec with every CU under it
+    const bool part = mode == 0 && !nof0 && e->partitioned && !(e->f0_method == RVC_F0_YIN && !e->pipeline && test_opt_int("RVC_YIN_CV_ALL_CUS", 0) == 1);
     const int f0_sid = 1, cv_sid = part ? 3 : 0;
-    if (mode == 0) {
+    if (mode == 0 && !nof0) {
         // f0 branch first (auxiliary stream): independent of ContentVec until the synthesizer
         const int Tcv = e->cv->out_frames(L);
         if (Tcv < 1) throw ShapeError("input too short for ContentVec");
@@ -355,6 +360,11 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
             for (size_t i = rm_end; i < cv_end; i++) ol.order_graph.push_back((int)i);
             for (size_t i = rm_begin; i < rm_end; i++) ol.order_graph.push_back((int)i);
         }
+        if (nof0) {
+            // ContentVec -> gather (-> retrieval) -> synthesizer -> advance_chunk_kernel, nothing forked and nothing joined.  The pitch cache is not written;
+            // the chunk counter advances (the prior's Philox stream reads it)
+            build_synth(e, pl, B, phone, T1{}, nullptr, nullptr, 0, nullptr);
+        } else {
         if (cv_sid) pl.ops.join(cv_sid);
         pl.ops.join(f0_sid);
         // consonant protection: `phone` is final (the retrieval has blended into it) and the pitch tail has written this call's pitchf rows; nothing of the
@@ -386,6 +396,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         if (side_nz) nz = build_noise_convs(e, pl, B, src0);
         pl.ops.cur = 0;
         build_synth(e, pl, B, phone, src0, d_pitchf, d_pitch, 2, side_nz ? &nz : nullptr);
+        }
         StreamState *st = e->d_state;
         int *hst = e->h_status;      // (pinned host memory, mapped: the kernel writes the status words where the host reads them)
         pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(advance_chunk_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B, hst); });
@@ -840,6 +851,8 @@ rvc_status rvc_load_f0_method(rvc_engine *e, int method)
     });
 }
 int rvc_f0_method(rvc_engine *e) { return e ? e->f0_method : 0; }
+// the kind of the loaded synthesizer: 1 = trained with pitch guidance, 0 = without (config key f0 = 0: no tracker runs), -1 = none loaded
+int rvc_model_has_f0(rvc_engine *e) { return e && e->sy ? (e->sy->has_f0 ? 1 : 0) : -1; }
 // CREPE's decoder (crepe_decode_kernel): part of a CREPE plan's key, so a plan built for one never serves the other
 rvc_status rvc_set_crepe_decoder(rvc_engine *e, int decoder)
 {
@@ -947,7 +960,8 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
 {
     if (!e->sy) return RVC_MODEL_NOT_LOADED;             // rvc.rs:141-143
     if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;        // rvc.rs:85-88 (via extract_feature at rvc.rs:151)
-    if (!e->f0_method) return RVC_F0_NOT_LOADED;         // reference: unreachable!() at rvc.rs:125
+    if (!e->f0_method && e->sy->has_f0) return RVC_F0_NOT_LOADED;         // reference: unreachable!() at rvc.rs:125; a model without pitch guidance needs no tracker
+    if (!e->sy->has_f0 && e->pipeline) throw ShapeError("chunk pipelining overlaps the two front branches of consecutive chunks: a model without pitch guidance has no such pair (rvc_set_pipeline(e, 0))");
     uint32_t R2 = return_length; bool fstage = false;
     if (!formant_key(e, return_length, nullptr, &R2, &fstage))
         return infer_r2_buckets(e, input, input_on_device, n, frame16k, pitch_shift, skip_head, return_length, out, out_on_device, cap, out_len, shifts);
@@ -1062,7 +1076,7 @@ rvc_status rvc_infer_batch_g(rvc_engine *e, const float *const *inputs, const si
         if (!inputs || !n || !sample_frame_16k_size || !skip_head || !return_length || !outs || !caps) throw ShapeError("infer_batch_g: null argument array");
         if (!e->sy) return RVC_MODEL_NOT_LOADED;
         if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;
-        if (!e->f0_method) return RVC_F0_NOT_LOADED;
+        if (!e->f0_method && e->sy->has_f0) return RVC_F0_NOT_LOADED;
         const int S = e->n_streams;
         if (e->pipeline || e->use_graph) throw ShapeError("infer_batch_g: not with chunk pipelining / graph replay");
         // (R2, fstage: the formant decoder length of the stream and whether its bucket carries the formant stage, formant.hip.h)

@@ -419,6 +419,9 @@ template <typename T> void glu_pack_rows(const T *w, const float *bias, int H, s
 struct ModelSY {
     int phone_dim, hidden, inter, filter, heads, enc_layers, enc_k, window, flow_n, wn_layers, wn_k, gin, up_init, n_ups, n_rb, n_rbd, sr;
     int up_rate[8], up_kernel[8], rb_k[8], rb_d[8];
+    // has_f0 (config key f0, absent = 1): false = a model trained without pitch guidance (upstream's ..NSFsid_nono: no pitch embedding, a plain HiFi-GAN
+    // decoder).  Its blob has no sy.enc.pitch_emb, sy.src, sy.dec.nc*: pitch_emb stays null, ncs empty; its plans have no pitch branch (engine.hip get_plan)
+    bool has_f0 = true;
     ConvW phone, proj;
     float *pitch_emb = nullptr;
     // qkv_f: the projection with the previous layer's second LayerNorm folded in (ModelCV::fold_ln); proj_f likewise for the last layer.
@@ -441,7 +444,7 @@ struct ModelSY {
     ConvW dec_pre, dec_post;
     std::vector<ConvW> ups, ncs;
     std::vector<std::vector<std::vector<std::pair<ConvW, ConvW>>>> rbs;   // [stage][kernel][dilation] -> (c1, c2)
-    float src_w, src_b;
+    float src_w = 0.f, src_b = 0.f;
     std::vector<float *> owned;
     size_t weight_bytes = 0;
     explicit ModelSY(const Blob &b);
@@ -588,6 +591,7 @@ void add_avgpool2(Plan &pl, const T2 &x, const T2 &p);
 void add_nsf_source(Plan &pl, int B, const float *pitchf, const T1 &src, int R, int upp, float sr, float lin_w, float lin_b, const StreamState *st, const CallParams *cp,
                     int f0_num, int f0_den);
 std::vector<T1> build_noise_convs(rvc_engine *e, Plan &pl, int B, const T1 &src);
+// (a model without pitch guidance, ModelSY::has_f0 false: src, d_pitchf, d_pitch, nz are not looked at and src_join_sid is 0)
 void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src, float *d_pitchf, int *d_pitch, int src_join_sid, const std::vector<T1> *nz = nullptr);
 void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip_head, uint32_t R, const T1 &phone);
 // consonant protection on `phone` [B][C][R] against the ContentVec output `cv` [B][C][T] (protect_mix_kernel, protect.hip.h): the one launch of the plan op

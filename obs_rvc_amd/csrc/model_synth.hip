@@ -24,6 +24,7 @@ ModelSY::ModelSY(const Blob &b)
     enc_layers = b.icfg("enc_layers"); enc_k = b.icfg("enc_k"); window = b.icfg("window"); flow_n = b.icfg("flow_n");
     wn_layers = b.icfg("wn_layers"); wn_k = b.icfg("wn_k"); gin = b.icfg("gin"); up_init = b.icfg("up_init"); n_ups = b.icfg("n_ups");
     n_rb = b.icfg("n_rb"); n_rbd = b.icfg("n_rbd"); sr = b.icfg("sr");
+    has_f0 = b.icfg_or("f0", 1) != 0;
     for (int i = 0; i < n_ups; i++) { up_rate[i] = b.icfg(fmt("up_rate%d", i)); up_kernel[i] = b.icfg(fmt("up_kernel%d", i)); }
     for (int j = 0; j < n_rb; j++) rb_k[j] = b.icfg(fmt("rb_k%d", j));
     for (int m = 0; m < n_rbd; m++) rb_d[m] = b.icfg(fmt("rb_d%d", m));
@@ -31,7 +32,7 @@ ModelSY::ModelSY(const Blob &b)
     const int H = hidden, G = gin;
     const float *g = b.w("sy.g");
     phone = prep_conv(b.w("sy.enc.phone.w"), b.w("sy.enc.phone.b"), H, phone_dim, 1, 1);
-    pitch_emb = own("sy.enc.pitch_emb");
+    if (has_f0) pitch_emb = own("sy.enc.pitch_emb");
     for (int l = 0; l < enc_layers; l++) {
         Layer L;
         std::vector<float> w((size_t)3 * H * H), bb((size_t)3 * H);
@@ -123,7 +124,7 @@ ModelSY::ModelSY(const Blob &b)
         ups.push_back(prep_convT1d(b.w(fmt("sy.dec.up%d.w", i)), b.w(fmt("sy.dec.up%d.b", i)), c, co, up_kernel[i], up_rate[i]));
         int sf = 1; for (int q = i + 1; q < n_ups; q++) sf *= up_rate[q];
         int nk = i + 1 < n_ups ? 2 * sf : 1;
-        ncs.push_back(prep_conv(b.w(fmt("sy.dec.nc%d.w", i)), b.w(fmt("sy.dec.nc%d.b", i)), co, 1, nk, 1));
+        if (has_f0) ncs.push_back(prep_conv(b.w(fmt("sy.dec.nc%d.w", i)), b.w(fmt("sy.dec.nc%d.b", i)), co, 1, nk, 1));
         std::vector<std::vector<std::pair<ConvW, ConvW>>> stage;
         for (int j = 0; j < n_rb; j++) {
             std::vector<std::pair<ConvW, ConvW>> chain;
@@ -144,7 +145,7 @@ ModelSY::ModelSY(const Blob &b)
         c = co;
     }
     dec_post = prep_conv(b.w("sy.dec.post.w"), nullptr, 1, c, 7, 1);
-    src_w = b.w("sy.src")[0]; src_b = b.w("sy.src")[1];
+    if (has_f0) { src_w = b.w("sy.src")[0]; src_b = b.w("sy.src")[1]; }
     weight_bytes = b.bytes();
     // the f0 / feature frame rate is 100 Hz (rvc.rs:153, 160 samples @16 kHz): a synthesizer whose hop is not sr / 100 would
     // return audio of the wrong length without any error (e.g. an import that guessed the first upsample rate)
@@ -305,6 +306,7 @@ void add_nsf_source(Plan &pl, int B, const float *pitchf, const T1 &src, int R, 
 T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
 {
     ModelSY &m = *e->sy;
+    if (!m.has_f0) throw std::logic_error("NSF source on a model without pitch guidance");
     Arena &A = pl.arena;
     const int R = (int)pl.R, R2 = pl.dec_frames();
     const int upp = m.upp();
@@ -332,6 +334,7 @@ T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
 std::vector<T1> build_noise_convs(rvc_engine *e, Plan &pl, int B, const T1 &src)
 {
     ModelSY &m = *e->sy;
+    if (!m.has_f0) throw std::logic_error("noise convolutions on a model without pitch guidance");
     std::vector<T1> nz;
     int c = m.up_init, Tc = pl.dec_frames();
     for (int i = 0; i < m.n_ups; i++) {
@@ -359,7 +362,8 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         add_conv1d(pl, m.phone, phone, x, 1, 0, 1);
         {
             dim3 grid((H * R + 255) / 256, B); float *emb = m.pitch_emb; float sq = sqrtf((float)H);
-            pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(embed_pitch_kernel, grid, dim3(256), 0, s, x.p, x.ld, x.bs, emb, d_pitch, H, R, sq); });
+            if (m.has_f0) pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(embed_pitch_kernel, grid, dim3(256), 0, s, x.p, x.ld, x.bs, emb, d_pitch, H, R, sq); });
+            else pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(embed_nopitch_kernel, grid, dim3(256), 0, s, x.p, x.ld, x.bs, H, R, sq); });
         }
         add_tap(pl, "sy.emb", x);
         T1 qkv = make_t1(A, B, 3 * H, R, 0), att = make_t1(A, B, H, R, 0), ff = make_t1(A, B, F, R, HALO);
@@ -466,7 +470,10 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         const int co = c / 2, K = m.up_kernel[i], S = m.up_rate[i], Tn = Tc * S;
         if ((K - S) % 2 != 0) throw ShapeError("upsample kernel/stride parity not supported");
         T1 u = make_t1(A, B, co, Tn, DH);
-        if (nz) {
+        if (!m.has_f0) {
+            // a plain HiFi-GAN generator: no source, nothing to add to the upsampled tensor
+            ConvOpts o; o.pre_act = ACT_LRELU; o.pre_slope = 0.1f; add_convT1d(pl, m.ups[i], xd, u, (K - S) / 2, o);
+        } else if (nz) {
             const T1 &r = (*nz)[i];
             ConvOpts o; o.pre_act = ACT_LRELU; o.pre_slope = 0.1f; o.res = r.p; o.res_cs = r.ld; o.res_bs = r.bs;
             add_convT1d(pl, m.ups[i], xd, u, (K - S) / 2, o);

@@ -18,6 +18,17 @@ static __global__ void embed_pitch_kernel(float *x, int cs, long long bs, const 
     *xp = a > 0.f ? a : a * 0.1f;
 }
 
+// ... of a model without pitch guidance (ModelSY::has_f0 false): x = lrelu(lin * sqrt(H), 0.1)
+static __global__ void embed_nopitch_kernel(float *x, int cs, long long bs, int H, int R, float sq)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= H * R) return;
+    int c = i / R, t = i - c * R;
+    float *xp = x + (long long)b * bs + (long long)c * cs + t;
+    float a = *xp * sq;
+    *xp = a > 0.f ? a : a * 0.1f;
+}
+
 // Philox4x32-10, the same counter layout as oracle/rvc_oracle.c (ora_philox_normal)
 // (philox4x32_10 / u01 / philox_normal4: state.hip.h)
 

@@ -55,6 +55,19 @@ def load_checkpoint_config(path: str) -> Optional[list]:
     return list(cfg) if isinstance(cfg, (list, tuple)) and len(cfg) >= 18 else None
 
 
+def load_checkpoint_f0(path: str) -> Optional[int]:
+    """The `f0` entry an RVC model .pth carries ({"weight": sd, "config": [...], "f0": 1 | 0, ..}: 1 = trained with pitch guidance, 0 = without).
+    None for formats or files that have no such entry."""
+    if os.path.splitext(path)[1].lower() in (".onnx", ".safetensors"):
+        return None
+    import torch
+    obj = torch.load(path, map_location="cpu", weights_only=True)
+    v = obj.get("f0") if isinstance(obj, dict) else None
+    if hasattr(v, "numel") and v.numel() == 1:
+        v = v.item()
+    return int(v) if isinstance(v, (bool, int, float)) else None
+
+
 def load_named_tensors(path: str) -> Named:
     ext = os.path.splitext(path)[1].lower()
     if ext == ".onnx":
@@ -437,15 +450,30 @@ def import_rmvpe_structural(inits: Named, nodes: List[dict]) -> Tuple[dict, Name
 
 # --------------------------------------------------------------------------------------------- synthesizer
 def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates: Optional[List[int]] = None,
-                 heads: Optional[int] = None, window: int = 10, config: Optional[list] = None) -> Tuple[dict, Named]:
-    """RVC `SynthesizerTrnMs{256,768}NSFsid` state dict (the "weight" entry of a model .pth) -> (cfg, tensors) of weights.make_synth.
+                 heads: Optional[int] = None, window: int = 10, config: Optional[list] = None, f0: Optional[int] = None) -> Tuple[dict, Named]:
+    """RVC `SynthesizerTrnMs{256,768}NSFsid` or `..NSFsid_nono` state dict (the "weight" entry of a model .pth) -> (cfg, tensors) of weights.make_synth.
     The speaker embedding row `emb_g.weight[sid]` is baked, as in the reference's 3-input export (rvc/src/rvc.rs:186-203).
 
     Upsample rates cannot be read off the weights (official configs pair kernel 16 with rate 10 *and* with rate 8): they come from,
     in this order, `up_rates`, the checkpoint's `config` list (entries 12 / 14 / 17 = upsample_rates / upsample_kernel_sizes / sr,
     see load_checkpoint_config), or `sr` (the noise convs pin every rate but the first: rate0 = (sr / 100) / prod(rates[1:])).
     Without any of the three the import fails instead of guessing.  The result always satisfies sr == 100 * prod(rates), which the
-    engine checks at load."""
+    engine checks at load.
+
+    The kind of model is read off the state dict: one trained with pitch guidance has `enc_p.emb_pitch.weight`, `dec.m_source.*` and
+    `dec.noise_convs.*`, one trained without (`_nono`) has none of the three; the blob of the latter carries the config key f0 = 0 and
+    leaves the three tensor groups out.  A mixture fails, and so does a checkpoint whose own `f0` entry (load_checkpoint_f0) says
+    otherwise.  A no-f0 model has no noise convs to pin its rates: they come from `up_rates` or `config` only."""
+    groups = {"enc_p.emb_pitch.weight": any(k.endswith("enc_p.emb_pitch.weight") for k in named),
+              "dec.m_source.*": any("dec.m_source." in k for k in named),
+              "dec.noise_convs.*": any("dec.noise_convs." in k for k in named)}
+    has_f0 = all(groups.values())
+    if any(groups.values()) and not has_f0:
+        raise ImportError_("synthesizer: neither a model with pitch guidance nor one without: it has %s but not %s"
+                           % (", ".join(k for k, v in groups.items() if v), ", ".join(k for k, v in groups.items() if not v)))
+    if f0 is not None and bool(f0) != has_f0:
+        raise ImportError_("synthesizer: the checkpoint says f0 = %d, its tensors are those of a model %s pitch guidance (%s)"
+                           % (int(f0), "with" if has_f0 else "without", ", ".join(groups) + (" present" if has_f0 else " absent")))
     if config is not None:
         if up_rates is None:
             up_rates = [int(r) for r in config[12]]
@@ -460,7 +488,8 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
     t: Named = {}
     t["sy.g"] = s.get("emb_g.weight")[sid] if s.has("emb_g.weight") else s.get("emb_g.weight")
     t["sy.enc.phone.w"], t["sy.enc.phone.b"] = s.get("enc_p.emb_phone.weight"), s.get("enc_p.emb_phone.bias")
-    t["sy.enc.pitch_emb"] = s.get("enc_p.emb_pitch.weight")
+    if has_f0:
+        t["sy.enc.pitch_emb"] = s.get("enc_p.emb_pitch.weight")
     L = 0
     while s.has("enc_p.encoder.attn_layers.%d.conv_q.weight" % L):
         L += 1
@@ -491,7 +520,8 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
         t[q + "post.w"], t[q + "post.b"] = _sq(s.get(f + "post.weight"), 2), s.get(f + "post.bias")
     t["sy.dec.pre.w"], t["sy.dec.pre.b"] = s.get("dec.conv_pre.weight"), s.get("dec.conv_pre.bias")
     t["sy.dec.cond.w"], t["sy.dec.cond.b"] = _sq(s.get("dec.cond.weight"), 2), s.get("dec.cond.bias")
-    t["sy.src"] = np.array([float(s.get("dec.m_source.l_linear.weight").reshape(-1)[0]), float(s.get("dec.m_source.l_linear.bias").reshape(-1)[0])], np.float32)
+    if has_f0:
+        t["sy.src"] = np.array([float(s.get("dec.m_source.l_linear.weight").reshape(-1)[0]), float(s.get("dec.m_source.l_linear.bias").reshape(-1)[0])], np.float32)
     n_ups = 0
     while s.has("dec.ups.%d.bias" % n_ups):
         n_ups += 1
@@ -506,7 +536,8 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
     for i in range(n_ups):
         t["sy.dec.up%d.w" % i], t["sy.dec.up%d.b" % i] = s.weight("dec.ups.%d" % i), s.get("dec.ups.%d.bias" % i)
         kernels.append(int(t["sy.dec.up%d.w" % i].shape[-1]))
-        t["sy.dec.nc%d.w" % i], t["sy.dec.nc%d.b" % i] = s.get("dec.noise_convs.%d.weight" % i), s.get("dec.noise_convs.%d.bias" % i)
+        if has_f0:
+            t["sy.dec.nc%d.w" % i], t["sy.dec.nc%d.b" % i] = s.get("dec.noise_convs.%d.weight" % i), s.get("dec.noise_convs.%d.bias" % i)
         for j in range(n_rb):
             r, q = "dec.resblocks.%d." % (i * n_rb + j), "sy.dec.rb%d_%d." % (i, j)
             for m in range(n_rbd):
@@ -517,9 +548,12 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
     t["sy.dec.post.w"] = s.get("dec.conv_post.weight")
     s.check("synthesizer")
     # the noise conv of stage i spans 2 * prod(rates after i) samples (kernel): that pins every rate but the first
-    tail = [int(t["sy.dec.nc%d.w" % i].shape[-1]) // 2 for i in range(n_ups - 1)]      # prod(rates[i+1:])
+    tail = [int(t["sy.dec.nc%d.w" % i].shape[-1]) // 2 for i in range(n_ups - 1)] if has_f0 else []      # prod(rates[i+1:])
     tail_rates = [tail[i] // (tail[i + 1] if i + 1 < len(tail) else 1) for i in range(len(tail))]
     if up_rates is None:
+        if not has_f0:
+            raise ImportError_("synthesizer: a model without pitch guidance has no noise convs to pin its upsample rates%s; pass up_rates "
+                               "or the checkpoint's config list" % (": sr alone does not give them" if sr else ""))
         if not sr:
             raise ImportError_("synthesizer: the first upsample rate is not recoverable from the weights (kernel %d is used with rate %d "
                                "and other rates in official configs); pass up_rates, the checkpoint's config list or sr" % (kernels[0], kernels[0] // 2))
@@ -528,7 +562,9 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
             raise ImportError_("synthesizer: sr %d is not 100 * (a multiple of the tail rates' product %d)" % (sr, tp))
         up_rates = [sr // (100 * tp)] + tail_rates
     up_rates = [int(r) for r in up_rates]
-    if len(up_rates) != n_ups or up_rates[1:] != tail_rates:
+    if len(up_rates) != n_ups:
+        raise ImportError_("synthesizer: %d upsample rates %s for %d upsampling stages" % (len(up_rates), up_rates, n_ups))
+    if has_f0 and up_rates[1:] != tail_rates:
         raise ImportError_("synthesizer: upsample rates %s do not match the noise-conv geometry of the weights (rates after the first: %s)" % (up_rates, tail_rates))
     for i in range(n_ups):
         if kernels[i] < up_rates[i] or (kernels[i] - up_rates[i]) % 2 != 0:
@@ -550,6 +586,8 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
         cfg["rb_k%d" % j] = k
     for m, d in enumerate(rb_d):
         cfg["rb_d%d" % m] = d
+    if not has_f0:
+        cfg["f0"] = 0
     return cfg, t
 
 
@@ -595,6 +633,8 @@ def convert(kind: str, src: str, dst: str, **kw) -> None:
     named = load_named_tensors(src)
     if kind == "synth" and kw.get("config") is None:
         kw["config"] = load_checkpoint_config(src)
+    if kind == "synth" and kw.get("f0") is None:
+        kw["f0"] = load_checkpoint_f0(src)
     if kind == "rmvpe" and src.lower().endswith(".onnx") and not any(k.endswith("unet.encoder.bn.weight") for k in named):
         # name-anonymised export (Conv + BN folded by the exporter, GRU / Linear operands renamed): assign by topology
         inits, nodes = read_onnx(src)

@@ -88,6 +88,12 @@ class RvcInfer:
     def unload_model(self):
         self._L.rvc_unload_model(self._h)
 
+    def model_has_f0(self):
+        """True: the loaded model was trained with pitch guidance; False: without (no f0 method is needed or run, pitch_shift may be None everywhere, the pitch
+        controls and protect are ignored); None: no model loaded (rvc_model_has_f0)"""
+        v = int(self._L.rvc_model_has_f0(self._h))
+        return None if v < 0 else bool(v)
+
     # -- per-chunk API (rvc.rs:81-220) ----------------------------------------------------
     def hubert(self, input):
         """-> (1, C, T) float32 (rvc.rs:81-97)."""
@@ -374,11 +380,11 @@ class RvcInfer:
             x = np.ascontiguousarray(y[len(y) - n16:])
         n = C.c_size_t()
         # (the first call sizes the output: a capacity of 0 is short for every recording, empty ones and unloaded models report their own status)
-        rc = self._L.rvc_convert(self._h, x.ctypes.data_as(_FP), len(x), int(k), int(context), int(crossfade), int(pitch_shift), 1 if highpass else 0, None, 0, C.byref(n))
+        rc = self._L.rvc_convert(self._h, x.ctypes.data_as(_FP), len(x), int(k), int(context), int(crossfade), int(pitch_shift or 0), 1 if highpass else 0, None, 0, C.byref(n))
         if rc != 5 or n.value == 0:
             self._chk(rc)
         out = np.empty(n.value, np.float32)
-        self._chk(self._L.rvc_convert(self._h, x.ctypes.data_as(_FP), len(x), int(k), int(context), int(crossfade), int(pitch_shift), 1 if highpass else 0,
+        self._chk(self._L.rvc_convert(self._h, x.ctypes.data_as(_FP), len(x), int(k), int(context), int(crossfade), int(pitch_shift or 0), 1 if highpass else 0,
                                       out.ctypes.data_as(_FP), len(out), C.byref(n)))
         # n_out = ceil(n / 160) zc samples and the model's rate is 100 zc
         return out[: n.value], 100 * (n.value // -(-len(x) // 160))
@@ -431,7 +437,7 @@ class RvcInfer:
         if x.ndim != 1:
             raise RvcInferError(5, "convert_file: a recording is a 1-D array")
         n = C.c_size_t()
-        a = (x.ctypes.data_as(_FP), len(x), int(rate), int(k), int(context), int(crossfade), int(pitch_shift), 1 if highpass else 0, float(rms_mix_rate), int(out_rate))
+        a = (x.ctypes.data_as(_FP), len(x), int(rate), int(k), int(context), int(crossfade), int(pitch_shift or 0), 1 if highpass else 0, float(rms_mix_rate), int(out_rate))
         rc = self._L.rvc_convert_file(self._h, *a, None, 0, C.byref(n))
         if rc != 5 or n.value == 0:
             self._chk(rc)
@@ -597,6 +603,8 @@ class RvcInfer:
         n = C.c_size_t()
         cap = int(return_length) * 1024 + 16
         out = np.empty((self.n_streams, cap), np.float32)
+        if pitch_shift is None:      # (a model without pitch guidance has no use for one)
+            pitch_shift = 0
         if np.ndim(pitch_shift) == 0:
             self._chk(self._L.rvc_infer_batch(self._h, xp, x.shape[1], int(sample_frame_16k_size), int(pitch_shift), int(skip_head),
                                               int(return_length), out.ctypes.data_as(_FP), cap, C.byref(n)))
@@ -627,7 +635,7 @@ class RvcInfer:
     def infer_device(self, d_in_ptr: int, n: int, sample_frame_16k_size: int, pitch_shift: int, skip_head: int, return_length: int,
                      d_out_ptr: int, cap_per_stream: int, sync: bool = False) -> int:
         nn = C.c_size_t()
-        self._chk(self._L.rvc_infer_device(self._h, C.c_void_p(d_in_ptr), int(n), int(sample_frame_16k_size), int(pitch_shift), int(skip_head),
+        self._chk(self._L.rvc_infer_device(self._h, C.c_void_p(d_in_ptr), int(n), int(sample_frame_16k_size), int(pitch_shift or 0), int(skip_head),
                                            int(return_length), C.c_void_p(d_out_ptr), int(cap_per_stream), C.byref(nn), 1 if sync else 0))
         return nn.value
 

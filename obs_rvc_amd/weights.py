@@ -298,7 +298,10 @@ SYNTH_PRESETS = {
 }
 
 
-def make_synth(preset: str = "full", phone_dim: int = 768, seed: int = 777):
+def make_synth(preset: str = "full", phone_dim: int = 768, seed: int = 777, f0: bool = True):
+    """f0=False: a model trained without pitch guidance (upstream's SynthesizerTrnMs*NSFsid_nono).  The generator draws the same sequence either way, so
+    every tensor the two kinds share is identical; the no-f0 blob leaves out sy.enc.pitch_emb, sy.src and sy.dec.nc* and carries the config key f0 = 0
+    (an absent key means 1: an f0 blob is byte for byte what it always was)."""
     p = dict(SYNTH_PRESETS[preset])
     up_rates, up_kernels = p.pop("up_rates"), p.pop("up_kernels")
     rb_k, rb_d = p.pop("rb_k"), p.pop("rb_d")
@@ -372,7 +375,16 @@ def make_synth(preset: str = "full", phone_dim: int = 768, seed: int = 777):
         cfg["rb_k%d" % j] = k
     for m, d in enumerate(rb_d):
         cfg["rb_d%d" % m] = d
+    if not f0:
+        cfg["f0"] = 0
+        for k in [k for k in g.t if is_f0_only(k)]:
+            del g.t[k]
     return cfg, g.t
+
+
+def is_f0_only(name: str) -> bool:
+    """a synthesizer tensor that only a model with pitch guidance has: the pitch embedding, the NSF source's linear layer, the noise convolutions"""
+    return name in ("sy.enc.pitch_emb", "sy.src") or name.startswith("sy.dec.nc")
 
 
 def make_index(n: int = 100000, dim: int = 768, seed: int = 7) -> np.ndarray:
