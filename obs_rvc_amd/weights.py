@@ -286,7 +286,34 @@ SYNTH_PRESETS = {
                     flow_n=4, wn_layers=3, wn_k=5, gin=256, up_init=512, n_ups=4,
                     up_rates=(10, 10, 2, 2), up_kernels=(16, 16, 4, 4),
                     rb_k=(3, 7, 11), rb_d=(1, 3, 5), sr=40000),
-    # five upsampling stages and three ResBlock kernels at toy width (upstream's 32 kHz v1 layout is 10*4*2*2*2)
+    # Upstream's other decoder layouts (its configs/v1 and configs/v2; sr = 100 x the product of the rates): v1 48k and v1 32k have FIVE stages -- 512
+    # channels halve down to 16 --, v2 32k four.  v1 40k is "full40k"'s decoder, v2 48k is "full"'s.  The v1 ones go with a 256-d phone (zoo("full", 1, ...)).
+    "full_v1_48k": dict(inter=192, hidden=192, filter=768, heads=2, enc_layers=6, enc_k=3, window=10,
+                        flow_n=4, wn_layers=3, wn_k=5, gin=256, up_init=512, n_ups=5,
+                        up_rates=(10, 6, 2, 2, 2), up_kernels=(16, 16, 4, 4, 4),
+                        rb_k=(3, 7, 11), rb_d=(1, 3, 5), sr=48000),
+    "full_v1_32k": dict(inter=192, hidden=192, filter=768, heads=2, enc_layers=6, enc_k=3, window=10,
+                        flow_n=4, wn_layers=3, wn_k=5, gin=256, up_init=512, n_ups=5,
+                        up_rates=(10, 4, 2, 2, 2), up_kernels=(16, 16, 4, 4, 4),
+                        rb_k=(3, 7, 11), rb_d=(1, 3, 5), sr=32000),
+    "full32k": dict(inter=192, hidden=192, filter=768, heads=2, enc_layers=6, enc_k=3, window=10,
+                    flow_n=4, wn_layers=3, wn_k=5, gin=256, up_init=512, n_ups=4,
+                    up_rates=(10, 8, 2, 2), up_kernels=(20, 16, 4, 4),
+                    rb_k=(3, 7, 11), rb_d=(1, 3, 5), sr=32000),
+    # ... and their toy-width twins: tiny5's / tiny's widths with those rates, kernels and sr (five stages from 64 channels: the last one has 2)
+    "tiny_v1_48k": dict(inter=16, hidden=16, filter=32, heads=2, enc_layers=1, enc_k=3, window=4,
+                        flow_n=3, wn_layers=2, wn_k=5, gin=8, up_init=64, n_ups=5,
+                        up_rates=(10, 6, 2, 2, 2), up_kernels=(16, 16, 4, 4, 4),
+                        rb_k=(3, 7, 11), rb_d=(1, 3, 5), sr=48000),
+    "tiny_v1_32k": dict(inter=16, hidden=16, filter=32, heads=2, enc_layers=1, enc_k=3, window=4,
+                        flow_n=3, wn_layers=2, wn_k=5, gin=8, up_init=64, n_ups=5,
+                        up_rates=(10, 4, 2, 2, 2), up_kernels=(16, 16, 4, 4, 4),
+                        rb_k=(3, 7, 11), rb_d=(1, 3, 5), sr=32000),
+    "tiny32k": dict(inter=16, hidden=16, filter=32, heads=2, enc_layers=2, enc_k=3, window=4,
+                    flow_n=2, wn_layers=2, wn_k=5, gin=8, up_init=32, n_ups=4,
+                    up_rates=(10, 8, 2, 2), up_kernels=(20, 16, 4, 4),
+                    rb_k=(3, 7, 11), rb_d=(1, 3, 5), sr=32000),
+    # five upsampling stages and three ResBlock kernels at toy width, at a toy rate (a 4*2*2*2*2 decoder; upstream's five-stage layouts are the v1 ones above)
     "tiny5": dict(inter=16, hidden=16, filter=32, heads=2, enc_layers=1, enc_k=3, window=4,
                   flow_n=3, wn_layers=2, wn_k=5, gin=8, up_init=64, n_ups=5,
                   up_rates=(4, 2, 2, 2, 2), up_kernels=(8, 4, 4, 4, 4),

@@ -39,6 +39,20 @@ def zoo(preset: str = "tiny", version: int = 2, synth_preset=None):
     return W.build_model_zoo(W.default_zoo_root(preset), preset, version, synth_preset)
 
 
+# synthesizer presets that are not a zoo of their own: (front-end preset, ContentVec version).  The v1 layouts go with the 256-d (toy: 16-d) phone and
+# ContentVec v1, the combination real v1 voices have
+SYNTH_ZOO = {"tiny5": ("tiny", 2), "tiny32k": ("tiny", 2), "tiny_v1_48k": ("tiny", 1), "tiny_v1_32k": ("tiny", 1),
+             "full40k": ("full", 2), "full32k": ("full", 2), "full_v1_48k": ("full", 1), "full_v1_32k": ("full", 1)}
+
+
+def synth_zoo(preset: str):
+    """-> (zoo of a synthesizer preset, the ContentVec version to load with it)"""
+    if preset in SYNTH_ZOO:
+        front, version = SYNTH_ZOO[preset]
+        return zoo(front, version, preset), version
+    return zoo(preset), 2
+
+
 def rms(a):
     a = np.asarray(a, np.float64)
     return float(np.sqrt(np.mean(a * a))) if a.size else 0.0

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import resample_whole_ref as R
-from common import voice_signal, zoo
+from common import synth_zoo, voice_signal, zoo
 from obs_rvc_amd import _native
 from obs_rvc_amd.rvc import RvcInfer
 from obs_rvc_amd.rvc_common import RvcInferError
@@ -158,6 +158,32 @@ def test_convert_file_is_the_composition(highpass):
     assert jr == 100 * ZC and e.convert_file_info()["ms_resample_out"] == 0.0
     again, _ = guard(e.convert_file, x, RATE_IN, k=K, context=CTX, crossfade=XF, pitch_shift=SHIFT, highpass=highpass, rms_mix_rate=RMS_MIX, out_rate=RATE_OUT)
     assert same_bits(again, got) and e.convert_info()["offsets"].tolist() == ref_off and e.convert_file_info()["peak"] == f["peak"]
+    e.close()
+
+
+def test_convert_file_at_32k_five_stages_is_the_composition():
+    # the rate plumbing at a model rate of 32000 (zc = 320) behind a five-stage decoder: upstream's v1 32k layout at toy width (10 * 4 * 2 * 2 * 2, ContentVec v1),
+    # a 44.1 kHz file of the same 37 370 samples at 16 kHz, out at 22.05 kHz.  Not new numerics: bit for bit the composition of the public calls
+    rate_in, rate_out, zc = 44100, 22050, 320
+    z, version = synth_zoo("tiny_v1_32k")
+    e = RvcInfer(z["data"])
+    e.load_contentvec(version); e.load_model(z["model"]); e.load_f0_method("rmvpe")
+    e.set_streams(3); e.set_noise_seed(1234, 0)
+    x = voice_signal(2 * N_IN, seed=11, sr=rate_in)
+    x16 = guard(e.resample, x, rate_in, 16000)
+    y, sr = guard(e.convert, x16, k=K, context=CTX, crossfade=XF, pitch_shift=SHIFT, highpass=True)
+    off = e.convert_info()["offsets"].tolist()
+    assert sr == 100 * zc == 32000 and len(x16) == 37370 and y.shape == (234 * zc,)
+    y2 = guard(e.change_rms, guard(e.highpass, x16), 16000, y, sr, RMS_MIX)
+    ref = guard(e.resample, y2, sr, rate_out)
+    got, rate = guard(e.convert_file, x, rate_in, k=K, context=CTX, crossfade=XF, pitch_shift=SHIFT, highpass=True, rms_mix_rate=RMS_MIX, out_rate=rate_out)
+    info, f = e.convert_info(), e.convert_file_info()
+    assert rate == rate_out == f["rate"] and got.shape == (RvcInfer.resample_geometry(sr, rate_out, 234 * zc)["n_out"],) and info["windows"] == 5 and info["batches"] == 2
+    assert info["offsets"].tolist() == off
+    assert same_bits(got, ref) and np.all(np.isfinite(got)) and f["peak"] == np.max(np.abs(got)) and f["peak"] > 0
+    # ... and at the model's own rate: no output converter, 234 x 320 samples
+    own, rate = guard(e.convert_file, x, rate_in, k=K, context=CTX, crossfade=XF, pitch_shift=SHIFT, highpass=True, rms_mix_rate=RMS_MIX, out_rate=0)
+    assert rate == 32000 and same_bits(own, y2) and e.convert_file_info()["ms_resample_out"] == 0.0
     e.close()
 
 

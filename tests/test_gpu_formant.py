@@ -124,6 +124,12 @@ def test_stages_tiny(phi):
     _stage_case("tiny", None, phi)
 
 
+@pytest.mark.parametrize("phi", [3.5, -2.3])
+def test_stages_tiny_32k(phi):
+    # upstream's v2 32k decoder layout (10 * 8 * 2 * 2, upp = 320): the stretch and the resample back at a model rate of 32000, both directions
+    _stage_case("tiny", "tiny32k", phi)
+
+
 def test_zero_is_todays_path():
     z = zoo("tiny")
     x = voice_signal(g.input_buffer_16k_size, seed=5)

@@ -61,26 +61,32 @@ CASES = [
 ] + [
     Case("noise_sf%d" % sf, "model_synth.hip:185 (noise conv, accumulated)", cin=1, cout=co, kw=2 * sf, stride=sf, pad=sf // 2, t_in=t * sf, t_out=t,
          x_halo=sf + 2, y_halo=DH, accumulate=1)
-    for (sf, co, t) in ((40, 256, 70), (4, 64, 1403), (12, 128, 250))
+    # (40 / 4 / 12: the v2 48k and 40k layouts; 48 / 32 / 8 / 2: the first two, a middle and the fourth stage of the v1 48k / v1 32k / v2 32k layouts)
+    for (sf, co, t) in ((40, 256, 70), (4, 64, 1403), (12, 128, 250), (48, 256, 70), (32, 256, 70), (8, 128, 701), (2, 32, 1403))
+] + [
+    Case("noise_last_c16", "model_synth.hip:344 (last stage's noise conv: one tap onto 16 channels, accumulated)", cin=1, cout=16, kw=1, t_in=1601, t_out=1601,
+         x_halo=3, y_halo=DH, accumulate=1),
 ] + [
     Case("pos_T%d" % t, "model_cv.hip:73 (grouped, Tout = T + 1 dropped)", cin=768, cout=768, kw=128, pad=64, groups=16, t_in=t, t_out=t, x_halo=64,
          act=R.ACT_GELU, res=4)
     for t in (48, 37)
 ] + [
-    Case("convT_%d_%d%s" % (k, s, "_res" if res else ""), "model_synth.hip:180-183 (polyphase ConvTranspose1d)", form=1, cin=ci, cout=ci // 2, kw=k, stride=s,
+    Case("convT_%d_%d%s%s" % (k, s, "_to16" if ci == 32 else "", "_res" if res else ""), "model_synth.hip:180-183 (polyphase ConvTranspose1d)", form=1, cin=ci, cout=ci // 2, kw=k, stride=s,
          pad=(k - s) // 2, t_in=t, t_out=(t - 1) * s - (k - s) + k, x_halo=DH, y_halo=DH, pre_act=LR, pre_slope=0.1, res=res)
-    for (k, s, ci, t) in ((24, 12, 512, 9), (20, 10, 512, 11), (16, 10, 512, 7), (16, 8, 256, 13), (8, 4, 256, 21), (7, 3, 64, 45), (4, 2, 128, 99))
+    # (16 / 4 and 16 / 6: four and three taps per phase, the second stages of the v1 32k / v1 48k layouts; 4 / 2 from 32 channels: their fifth stage, 32 -> 16)
+    for (k, s, ci, t) in ((24, 12, 512, 9), (20, 10, 512, 11), (16, 10, 512, 7), (16, 8, 256, 13), (8, 4, 256, 21), (7, 3, 64, 45), (4, 2, 128, 99),
+                          (16, 4, 256, 21), (16, 6, 256, 13), (4, 2, 32, 99))
     for res in (0, 1)
 ] + [
     Case("multi_c1_%s_C%d_d%d" % ("grouped" if xg else "shared", co, d), "model_synth.hip:204 (ResBlock c1, fused chains)", form=2, cin=co, cout=co, n=3,
          kws=(3, 7, 11), dils=(d,) * 3, pads=tuple((k * d - d) // 2 for k in (3, 7, 11)), t_in=t, t_out=t, x_halo=DH, y_halo=DH, x_grouped=xg,
          pre_act=LR, pre_slope=0.1, act=LR, slope=0.1)
-    for (co, t) in ((128, 203), (32, 1601)) for (xg, d) in ((0, 1), (1, 3), (1, 5))
+    for (co, t) in ((128, 203), (32, 1601), (16, 1601)) for (xg, d) in ((0, 1), (1, 3), (1, 5))
 ] + [
     Case("multi_c2_res%s_C%d" % ("grouped" if rg else "shared", co), "model_synth.hip:208 (ResBlock c2 + residual, fused chains)", form=2, cin=co, cout=co,
          n=3, kws=(3, 7, 11), dils=(1, 1, 1), pads=(1, 3, 5), t_in=t, t_out=t, x_halo=DH, y_halo=0 if rg else DH, r_halo=DH, x_grouped=1, res=1,
          res_grouped=rg)
-    for (co, t) in ((128, 203), (64, 797)) for rg in (0, 1)
+    for (co, t) in ((128, 203), (64, 797), (16, 1601)) for rg in (0, 1)
 ] + [
     Case("pair", "model_synth.hip:138 (post + next pre, add_conv1d_two)", form=3, cin=768, cout=192, n=2, t_in=21, t_out=21, x_halo=4, y_halo=4),
     Case("pair_T37", "model_synth.hip:138 (post + next pre, add_conv1d_two)", form=3, cin=768, cout=192, n=2, t_in=37, t_out=37, x_halo=4, y_halo=4),
@@ -94,10 +100,16 @@ CASES = [
          r_halo=DH, res=1, scale=1.0 / 3),
     Case("rb_mean_acc", "model_synth.hip:228 (chain j > 0: x 1/n_rb, accumulate)", cin=128, cout=128, kw=11, pad=5, t_in=203, t_out=203, x_halo=DH,
          y_halo=DH, r_halo=DH, res=1, scale=1.0 / 3, accumulate=1),
+    Case("rb_mean_first_c16", "model_synth.hip:228 (chain 0 of a five-stage decoder's last stage)", cin=16, cout=16, kw=7, pad=3, t_in=1601, t_out=1601, x_halo=DH,
+         y_halo=DH, r_halo=DH, res=1, scale=1.0 / 3),
+    Case("rb_mean_acc_c16", "model_synth.hip:228 (chain j > 0 of a five-stage decoder's last stage)", cin=16, cout=16, kw=11, pad=5, t_in=1601, t_out=1601,
+         x_halo=DH, y_halo=DH, r_halo=DH, res=1, scale=1.0 / 3, accumulate=1),
     Case("ff1_relu", "model_synth.hip:97 (ReLU, 3 taps)", cin=192, cout=768, kw=3, pad=1, t_in=21, t_out=21, x_halo=4, y_halo=4, act=R.ACT_RELU),
     Case("ff2_res_self", "model_synth.hip:98 (residual = output tensor)", cin=768, cout=192, kw=3, pad=1, t_in=21, t_out=21, x_halo=4, y_halo=4, res=3),
     Case("dec_post_tanh", "model_synth.hip:247 (pre-LReLU 0.01, Tanh, no bias, final_out)", streams=(1, 2, 3, 6, 20, 64), cin=32, cout=1, kw=7, pad=3,
          t_in=4001, t_out=4001, x_halo=DH, pre_act=LR, pre_slope=0.01, act=R.ACT_TANH, no_bias=1, final_out=1),
+    Case("dec_post_tanh_c16", "model_synth.hip:247 (behind a five-stage decoder: 16 channels, K = 112)", streams=(1, 2, 3, 6, 20, 64), cin=16, cout=1, kw=7,
+         pad=3, t_in=4001, t_out=4001, x_halo=DH, pre_act=LR, pre_slope=0.01, act=R.ACT_TANH, no_bias=1, final_out=1),
     Case("fc_sigmoid", "model_rmvpe.hip:259 (Sigmoid)", cin=512, cout=360, t_in=37, t_out=37, act=R.ACT_SIGMOID),
     Case("cv_ff1_gelu", "model_cv.hip:119 (GELU)", streams=(1, 2, 3, 6, 20, 64), cin=768, cout=3072, t_in=37, t_out=37, act=R.ACT_GELU),
     Case("knn_bcast_res", "retrieval.hip:104 (broadcast residual, scale -2, no bias)", cin=768, cout=48, t_in=1001, t_out=1001, res=2, scale=-2.0,
@@ -348,6 +360,13 @@ def runs_of(case):
 #   lds   (16x16x4 LDS kernel) only panels of >= 2048 or <= 64 rows with >= 384 workgroups -- of these shapes the 3072-row projection;
 #   tile  (conv_tile) / c32s (conv32s): stride-1 1-D layers with a table, input channels per phase in 16s / 32s, no gate, no per-phase output; tile
 #         also needs its staged rows within 100 KB of LDS (not the 768-channel 3-tap layer) and c32s a tap reach <= 64 (not the positional conv)
+# 16 channels (the fifth stage of the v1 48k / v1 32k decoders, 512 >> 5) are outside every family but reg:
+#   c32s  decode_taps(.., kC32sCB = 32) refuses 16 input channels (queue_conv32s);
+#   tile  16 is a multiple of 16, and the LDS budget holds, but queue_conv_tile splits K over two waves ("every K share needs a chunk": cin / 16 >= kshares = 2,
+#         the production value of RVC_CONV_TILE_KS, which runs_of leaves alone): one 16-channel group cannot be shared, so the family declines;
+#   g32 / g32t  a 16-row weight panel has no tile (queue_tiled: bm = 0 unless M > 16; a forced choice needs M >= 17) -- the ResBlock convolutions (16 -> 16), the
+#         transposed conv 32 -> 16 and the one-tap noise conv onto 16 channels alike; the last layer behind them has one row.
+# Noise convs with K = 2 sf <= 16 (sf 8, 2, the one-tap last stage) are one chunk of K: reg only, as noise_sf4 (g32 needs two chunks).
 # Never: strided layers on tile / c32s (the stem, the noise convs), the polyphase transposed conv on tile / c32s (its table walks taps backwards, its
 # output columns are strided), the pair launch (per-phase activation and output tensor) and the gated in-layer on anything but reg; the 1-row
 # weight panel of the decoder's last layer on the tiled kernels (fewer than 17 rows); the RMVPE head (3 rows, 2-D) on anything but reg.
@@ -355,13 +374,15 @@ _STRIDED_TAB = {"reg", "g32", "g32t"}
 _TAPS = {"reg", "g32", "g32t", "tile", "c32s"}
 _ONE_BY_ONE = {"reg", "g32", "g32l", "g2w", "c32s"}
 EXPECTED = dict(
-    {"stem0": {"reg"}, "stem_gelu": _STRIDED_TAB, "stem_gelu_k2": _STRIDED_TAB, "noise_sf40": _STRIDED_TAB, "noise_sf4": {"reg"},      # (K = 8: one chunk)
+    {"noise_sf48": _STRIDED_TAB, "noise_sf32": _STRIDED_TAB, "noise_sf8": {"reg"}, "noise_sf2": {"reg"}, "noise_last_c16": {"reg"}, "rb_mean_first_c16": {"reg"},
+     "rb_mean_acc_c16": {"reg"}, "dec_post_tanh_c16": {"reg"},
+     "stem0": {"reg"}, "stem_gelu": _STRIDED_TAB, "stem_gelu_k2": _STRIDED_TAB, "noise_sf40": _STRIDED_TAB, "noise_sf4": {"reg"},      # (K = 8: one chunk)
      "noise_sf12": _STRIDED_TAB, "pos_T48": {"reg", "tile"}, "pos_T37": {"reg", "tile"}, "pair": {"reg"}, "pair_T37": {"reg"}, "glu": {"reg"},
      "glu_composed": {"reg"}, "rs_accumulate": _ONE_BY_ONE, "post_scale_m1": _ONE_BY_ONE, "rb_mean_first": _TAPS, "rb_mean_acc": _TAPS, "ff1_relu": _TAPS,
      "ff2_res_self": _TAPS - {"tile"}, "dec_post_tanh": {"reg", "tile", "c32s"}, "fc_sigmoid": _ONE_BY_ONE, "cv_ff1_gelu": _ONE_BY_ONE | {"lds"},
      "knn_bcast_res": _ONE_BY_ONE, "cnn_transposed": {"reg"}},
-    **{c.name: {"reg", "g32"} for c in CASES if c.p["form"] == 1},
-    **{c.name: {"reg", "g32", "tile", "c32s"} for c in CASES if c.p["form"] == 2})
+    **{c.name: {"reg", "g32"} if c.p["cout"] > 16 else {"reg"} for c in CASES if c.p["form"] == 1},
+    **{c.name: {"reg", "g32", "tile", "c32s"} if c.p["cout"] > 16 else {"reg"} for c in CASES if c.p["form"] == 2})
 
 
 def _check(layer, case, runs):

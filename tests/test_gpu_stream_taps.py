@@ -13,7 +13,8 @@ so an error is charged to the stage that made it.  Metric: e = max |gpu - ref64|
   * ContentVec / RMVPE taps and f0 of every stream against that stream's own oracle at test_stage_by_stage's 1e-4 relative RMS.
 
 Cases sit on the planner's thresholds (composed WaveNets and gru_multi up to 8 streams, CU partition up to 4, LayerNorm strips / LDS GEMMs from 16,
-ResBlock chains unfused from 16), not at workload size.  Every (stage, e, delta32, e / delta32) is printed; DESIGN.md "Synthesizer stages: what is tested"
+ResBlock chains unfused from 16), not at workload size.  Upstream's other decoder layouts (v1 48k, v1 32k: five stages down to 16 channels; v2 32k) run
+at toy width on both plans, at full width on the production plan and at 20 streams, where the profile shows which kernel ran which stage.  Every (stage, e, delta32, e / delta32) is printed; DESIGN.md "Synthesizer stages: what is tested"
 records the worst per stage and plan."""
 import functools
 
@@ -22,7 +23,7 @@ import pytest
 
 import debug_abi as D
 import synth_ref as SR
-from common import BASELINE_160MS as g, TAP_MAP, rel_rms, rms, set_opt, voice_signal, zoo
+from common import BASELINE_160MS as g, TAP_MAP, rel_rms, rms, set_opt, synth_zoo, voice_signal
 from obs_rvc_amd import weights as W
 from obs_rvc_amd.rvc_common import RvcInferError
 
@@ -30,16 +31,21 @@ pytestmark = pytest.mark.gpu
 TOL = 2e-5                 # the per-layer bound of tests/test_gpu_tiles.py
 PCM_TOL = 1e-3
 SEED, ID0 = 11, 40
-SHIFTS = [12, 0, -12, 5, 7, -7, 12, 3, -3, 0, 12, -12, 1, 2, 9, -9, 4, 6]
+SHIFTS = [12, 0, -12, 5, 7, -7, 12, 3, -3, 0, 12, -12, 1, 2, 9, -9, 4, 6, 8, -5]
 HINTS = {"rm.cnn": 32, "rm.gru": 32, "rm.sal": 32}
 PARENT_OPS_1, PARENT_OPS_5 = 121, 132      # launches of the taps-off plans of 1 / 5 streams on `tiny`, measured on the parent commit's library
 
 
 @functools.lru_cache(maxsize=None)
 def _model(preset):
-    z = zoo("tiny", 2, "tiny5") if preset == "tiny5" else zoo(preset)
+    z, _ = synth_zoo(preset)
     cfg, tens = W.read_blob(z["model"])
     return z, cfg, tens
+
+
+def _version(preset):
+    """the ContentVec version a preset's model takes (the v1 layouts: 1)"""
+    return synth_zoo(preset)[1]
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,7 +62,7 @@ def _oracles(preset, S, R, streams):
     xs = _inputs(S)
     out = {}
     for s in streams:
-        o = O.OracleRvcInfer(z["data"]); o.load_contentvec(2); o.load_f0(1); o.load_model(z["model"]); o.set_noise_seed(SEED, ID0 + s)
+        o = O.OracleRvcInfer(z["data"]); o.load_contentvec(_version(preset)); o.load_f0(1); o.load_model(z["model"]); o.set_noise_seed(SEED, ID0 + s)
         o.enable_taps(True)
         for c in range(2):
             y = o.infer(xs[c][s], g.sample_frame_16k, SHIFTS[s], g.skip_head, R)
@@ -75,7 +81,7 @@ def _oracles(preset, S, R, streams):
 def _engine(preset, S, level, formant=None):
     from obs_rvc_amd.rvc import RvcInfer
     z, _, _ = _model(preset)
-    eng = RvcInfer(z["data"]); eng.load_contentvec(2); eng.load_f0(); eng.load_model(z["model"])
+    eng = RvcInfer(z["data"]); eng.load_contentvec(_version(preset)); eng.load_f0(); eng.load_model(z["model"])
     if S > 1:
         eng.set_streams(S)
     eng.set_noise_seed(SEED, ID0)
@@ -222,7 +228,7 @@ def _case(preset, S, level, R=g.model_return_length, check=None, formant=None, p
         _front_taps(rep, eng, p, gs, ora[gs][0], (formant or {}).get(gs, 0.0))
         _synth_stages(rep, cfg, tens, eng, p, gs, R, y[gs])
         if not formant:
-            assert y[gs].shape == ora[gs][1].shape and rms(y[gs] - ora[gs][1]) < PCM_TOL, gs
+            assert y[gs].shape == ora[gs][1].shape == (R * int(cfg["sr"]) // 100,) and rms(y[gs] - ora[gs][1]) < PCM_TOL, gs
     # the hook's stream 0 is rvc_get_tap's, bit for bit; a stream the plan did not have is refused
     for name in ("cv.out", "rm.enc0", "rm.sal_ct", "phone_ct", "sy.stats", "sy.flow0", "sy.z", "sy.rb0"):
         rc, a = D.debug_tap(eng, name, 0)
@@ -320,6 +326,107 @@ def test_full_production_plan(S):
     _composed_or_not(cfg, S, ops1, ops2)
     if S == 1:
         assert ops2 < ops1 - 40                                  # as test_stage_by_stage: the folds took their launches out
+
+
+# ---- upstream's other decoder layouts (weights.py SYNTH_PRESETS): v1 48k 10*6*2*2*2, v1 32k 10*4*2*2*2 (five stages: 512 channels down to 16; transposed convs of
+# three / four taps per phase; noise convs of stride 48 / 32 / 8 / 2 and a one-tap one onto 16 channels; 256-d phone, ContentVec v1), v2 32k 10*8*2*2
+LAYOUTS_TOY = ["tiny_v1_48k", "tiny_v1_32k", "tiny32k"]
+LAYOUTS_FULL = ["full_v1_48k", "full_v1_32k", "full32k"]
+
+
+@pytest.mark.parametrize("S", [1, 3, 9])
+@pytest.mark.parametrize("preset", LAYOUTS_TOY)
+def test_layout_toy_every_stream_both_plans(preset, S):
+    ops1, _ = _case(preset, S, 1)
+    ops2, _ = _case(preset, S, 2)
+    _composed_or_not(_model(preset)[1], S, ops1, ops2)
+
+
+@pytest.mark.parametrize("S", [1, 2])
+@pytest.mark.parametrize("preset", LAYOUTS_FULL)
+def test_layout_full_production_plan(preset, S):
+    _, rep = _case(preset, S, 2, check=sorted({0, S - 1}))
+    assert ("enc+stats" in rep.worst) == (S == 1)
+    assert all("rb%d" % i in rep.worst and "up%d" % i in rep.worst for i in range(int(_model(preset)[1]["n_ups"])))
+
+
+def _profile(eng):
+    """the launches of the last (profiled) call that have a planner description: [(family, {M, N, K, B, nph})]"""
+    import ctypes
+    lib = eng._L
+    lib.rvc_debug_profile_dump.restype = ctypes.c_int
+    lib.rvc_debug_profile_dump.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+    buf = ctypes.create_string_buffer(1 << 21)
+    assert lib.rvc_debug_profile_dump(eng._h, buf, len(buf)) > 0
+    out = []
+    for ln in buf.value.decode().splitlines():
+        w = ln.split(" ", 2)[2].split()
+        kv = dict(x.split("=", 1) for x in w[1:] if "=" in x)
+        if all(k in kv for k in ("M", "N", "K", "B", "nph")):
+            out.append((w[0], {k: int(kv[k]) for k in ("M", "N", "K", "B", "nph")}))
+    return out
+
+
+MANY_STREAM_FAMILIES = {"c32s", "g32", "g32t", "g32l", "lds"}        # the workgroup-tiled / staged kernels of the many-stream plans (plan.hip queue_conv32s, queue_tiled)
+
+
+@pytest.mark.parametrize("preset", LAYOUTS_FULL)
+def test_layout_full_twenty_streams(preset):
+    """20 streams: past the 16-stream rules (ResBlock chains one after the other, each conv a launch of its own; the plan-time tuner on).  One chunk; the ResBlock
+    stages and the last layer of streams 0, 10 and 19 teacher-forced against fp64, their PCM against their own oracles, and from the profile which kernel
+    ran which decoder stage.  What the planner's rules fix, and is asserted:
+      * a 16-channel ResBlock convolution (the fifth stage of the v1 layouts) and the last layer behind it (1 x 16 x 7) can only run on reg: conv32s wants input
+        channels in 32s, conv_tile two K shares of 16 channels each, the workgroup-tiled kernels more than 16 rows (tests/test_gpu_layers.py, EXPECTED);
+      * so no c32s launch has a 16-channel input.
+    What they do not fix: at 20 streams and 21 frames the v1 layouts' wider stages have 400 conv32s workgroups, fewer than the two per CU its size rule wants
+    (plan.hip queue_conv32s), so the rules send them to reg / lds and the tuner decides by timing between that and conv32s / igemm32.  Asserted is therefore
+    that the decoder as a whole did not fall back -- some ResBlock convolution of 32 channels or more ran on a many-stream kernel; the launches per stage and
+    family are printed (DESIGN.md "Synthesizer stages: what is tested" has them from one run)."""
+    from oracle import oracle as O
+    S, R, check = 20, g.model_return_length, (0, 10, 19)
+    z, cfg, tens = _model(preset)
+    n_ups, c0 = int(cfg["n_ups"]), int(cfg["up_init"])
+    eng = _engine(preset, S, 2)
+    eng.set_profile(True)
+    xs = _inputs(S)[0]
+    y = eng.infer_batch(xs, g.sample_frame_16k, np.array(SHIFTS[:S], np.int32), g.skip_head, R)
+    assert y.shape == (S, R * int(cfg["sr"]) // 100)
+    prof = _profile(eng)
+    rep = Report("%s S=%d one chunk" % (preset, S))
+    for s in check:
+        _synth_stages(rep, cfg, tens, eng, s, s, R, y[s], only=("rb", "post"), chunk=0)
+    eng.close()
+    # which kernel ran which stage: ResBlock convolutions are the launches with M = the stage's channels, K = M x 3 / 7 / 11 and the stage's columns (a description
+    # has them per stream, or -- streams folded into N -- in all)
+    widths = [c0 >> (i + 1) for i in range(n_ups)]
+    cols = {m: S * R * int(np.prod([int(cfg["up_rate%d" % q]) for q in range(i + 1)])) for i, m in enumerate(widths)}
+    by_stage = {}
+    for fam, d in prof:
+        if d["M"] in widths and d["K"] in (3 * d["M"], 7 * d["M"], 11 * d["M"]) and d["N"] * d["B"] == cols[d["M"]]:
+            by_stage.setdefault(d["M"], {}).setdefault(fam, 0)
+            by_stage[d["M"]][fam] += 1
+    for m in widths:
+        print("%s S=%d ResBlock convolutions of the %3d-channel stage: %s" % (preset, S, m, by_stage.get(m)))
+        assert sum(by_stage.get(m, {}).values()) == 18, (m, by_stage.get(m))          # 3 kernels x 3 dilations x (c1, c2), one launch each
+    post = [(fam, d) for fam, d in prof if d["M"] == 1 and d["K"] == 7 * widths[-1] and d["N"] * d["B"] == cols[widths[-1]]]
+    print("%s S=%d last layer: %s" % (preset, S, post))
+    assert len(post) == 1
+    for fam, d in prof:
+        if fam == "c32s":
+            assert d["M"] >= 32 and d["K"] % 32 == 0 and not (d["M"] == 1 and d["K"] == 7 * 16), (fam, d)
+    if 16 in widths:
+        assert by_stage[16] == {"reg": 18} and post[0][0] == "reg", (by_stage[16], post)
+    many = sum(n for m in widths if m >= 32 for fam, n in by_stage[m].items() if fam in MANY_STREAM_FAMILIES)
+    assert many > 0, by_stage
+    for s in check:
+        o = O.OracleRvcInfer(z["data"]); o.load_contentvec(_version(preset)); o.load_f0(1); o.load_model(z["model"]); o.set_noise_seed(SEED, ID0 + s)
+        yo = o.infer(xs[s], g.sample_frame_16k, SHIFTS[s], g.skip_head, R)
+        o.close()
+        e = rms(y[s] - yo)
+        print("%s S=%d stream %2d PCM rms error %.2e (bound %.0e)" % (preset, S, s, e, PCM_TOL))
+        if not (y[s].shape == yo.shape and e < PCM_TOL):
+            rep.bad.append((s, "pcm", e, PCM_TOL))
+    rep.done()
 
 
 def test_plans_without_taps_are_unchanged():

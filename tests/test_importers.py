@@ -299,6 +299,33 @@ def test_synth_import_of_official_rate_kernel_pairs(tmp_path):
     assert int(W.read_blob(out)[0]["sr"]) == 40000
 
 
+@pytest.mark.parametrize("rates,kernels,sr", [((10, 6, 2, 2, 2), (16, 16, 4, 4, 4), 48000), ((10, 4, 2, 2, 2), (16, 16, 4, 4, 4), 32000), ((10, 8, 2, 2), (20, 16, 4, 4), 32000)],
+                         ids=["v1_48k", "v1_32k", "v2_32k"])
+def test_synth_import_of_the_other_upstream_layouts(rates, kernels, sr):
+    # upstream's v1 48k / v1 32k (five stages) and v2 32k decoder layouts, as a checkpoint's "config" list has them (entries 12 / 14 / 17), at toy width and
+    # in upstream's module structure: the blob carries the stage count, every rate, every kernel and sr; the 40k pairing is checked above
+    n = len(rates)
+    m = _upstream_synth(up_init=32 << (n - 4), rates=rates, kernels=kernels, rb_k=(3, 7, 11), rb_d=(1, 3, 5))
+    sd = {k: v.detach().numpy() for k, v in m.state_dict().items()}
+    config = [1025, 32, 16, 16, 32, 2, 2, 3, 0.0, "1", [3, 7, 11], [[1, 3, 5]] * 3, list(rates), 32 << (n - 4), list(kernels), 3, 8, sr]
+    cfg, tens = IM.import_synth(sd, sid=0, config=config)
+    assert int(cfg["n_ups"]) == n and int(cfg["sr"]) == sr == 100 * int(np.prod(rates)) and int(cfg["up_init"]) == 32 << (n - 4)
+    assert [int(cfg["up_rate%d" % i]) for i in range(n)] == list(rates) and [int(cfg["up_kernel%d" % i]) for i in range(n)] == list(kernels)
+    assert "up_rate%d" % n not in cfg and "up_kernel%d" % n not in cfg
+    assert [int(cfg["rb_k%d" % j]) for j in range(3)] == [3, 7, 11] and [int(cfg["rb_d%d" % j]) for j in range(3)] == [1, 3, 5]
+    c = 32 << (n - 4)
+    for i in range(n):
+        sf = int(np.prod(rates[i + 1:]))
+        assert tens["sy.dec.up%d.w" % i].shape == (c, c // 2, kernels[i]) and tens["sy.dec.nc%d.w" % i].shape == (c // 2, 1, 2 * sf if i + 1 < n else 1)
+        c //= 2
+    assert tens["sy.dec.post.w"].shape == (1, c, 7)
+    # without the list, sr pins the first rate (kernel 16 is neither 2 x 10 nor 2 x 6 / 4) and the noise convs the others
+    c2, _ = IM.import_synth(sd, sid=0, sr=sr)
+    assert [int(c2["up_rate%d" % i]) for i in range(n)] == list(rates) and int(c2["n_ups"]) == n
+    with pytest.raises(IM.ImportError_):
+        IM.import_synth(sd, sid=0, sr=40000)
+
+
 def test_checkpoint_files_and_cli(tmp_path):
     # the three container formats load_named_tensors accepts (.pth as RVC ships it: {"weight": state_dict, "config": [...]},
     # .safetensors, .onnx) and the command-line entry point

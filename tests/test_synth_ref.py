@@ -9,22 +9,22 @@ import pytest
 
 import synth_ref as SR
 import torch_ref as TR
-from common import BASELINE_160MS as g, rel_rms, voice_signal, zoo
+from common import BASELINE_160MS as g, rel_rms, synth_zoo, voice_signal
 from obs_rvc_amd import weights as W
 from oracle import oracle as O
 
 torch = pytest.importorskip("torch")
 
-PRESETS = ["tiny", "tiny5", "full"]
+PRESETS = ["tiny", "tiny5", "full", "tiny_v1_48k", "tiny_v1_32k", "tiny32k"]       # (the last three: upstream's v1 48k / v1 32k / v2 32k decoder layouts)
 SEED, STREAM = 3, 1
 
 
 @functools.lru_cache(maxsize=None)
 def _case(preset):
     """one oracle chunk with taps: (cfg, tensors, taps by name as [C][T] arrays, PCM)"""
-    z = zoo("tiny", 2, "tiny5") if preset == "tiny5" else zoo(preset)
+    z, version = synth_zoo(preset)
     cfg, tens = W.read_blob(z["model"])
-    ora = O.OracleRvcInfer(z["data"]); ora.load_contentvec(2); ora.load_f0(1); ora.load_model(z["model"]); ora.set_noise_seed(SEED, STREAM)
+    ora = O.OracleRvcInfer(z["data"]); ora.load_contentvec(version); ora.load_f0(1); ora.load_model(z["model"]); ora.set_noise_seed(SEED, STREAM)
     ora.enable_taps(True)
     R = g.model_return_length
     pcm = ora.infer(voice_signal(35840, seed=4), g.sample_frame_16k, 12, g.skip_head, R)
@@ -80,7 +80,7 @@ def test_chained_stages_reproduce_torch_ref_and_the_oracle(preset):
         x = SR.dec_rb(cfg, tens, i, x); got["sy.rb%d" % i] = x
     y = SR.dec_post(cfg, tens, x)[0]
     ref_audio = TR.synth_decoder(cfg, tens, taps["sy.z"], taps["sy.src"])
-    assert y.shape == ref_audio.shape == pcm.shape
+    assert y.shape == ref_audio.shape == pcm.shape == (g.model_return_length * int(cfg["sr"]) // 100,)
     assert rel_rms(y, ref_audio) < 1e-5 and rel_rms(pcm, y) < 1e-5, (rel_rms(y, ref_audio), rel_rms(pcm, y))
     for nm, a in got.items():
         e = rel_rms(taps[nm], a)
