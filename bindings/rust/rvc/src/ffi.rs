@@ -44,6 +44,7 @@ pub const RVC_F0_RMVPE: c_int = 1;
 pub const RVC_F0_YIN: c_int = 2;
 pub const RVC_F0_CREPE: c_int = 4;
 pub const RVC_F0_CREPE_TINY: c_int = 5;
+pub const RVC_F0_FCPE: c_int = 7;
 pub const RVC_CREPE_VITERBI: c_int = 0;
 pub const RVC_CREPE_ARGMAX: c_int = 1;
 pub const RVC_DENOISE_INPUT: c_int = 0;
@@ -71,6 +72,9 @@ extern "C" {
     // ---- CREPE (RVC_F0_CREPE / RVC_F0_CREPE_TINY: <data>/f0/crepe-full.rvcw / crepe-tiny.rvcw): its decoder, RVC_CREPE_VITERBI (default) or RVC_CREPE_ARGMAX
     pub fn rvc_set_crepe_decoder(e: *mut RvcEngine, decoder: c_int) -> c_int;
     pub fn rvc_crepe_decoder(e: *mut RvcEngine) -> c_int;
+    // ---- FCPE (RVC_F0_FCPE: <data>/f0/fcpe.rvcw): its voicing threshold in [0, 1), default 0.006
+    pub fn rvc_set_fcpe_threshold(e: *mut RvcEngine, threshold: c_double) -> c_int;
+    pub fn rvc_fcpe_threshold(e: *mut RvcEngine) -> c_double;
 
     // ---- retrieval index, noise seed, state
     pub fn rvc_load_index(e: *mut RvcEngine, vectors: *const c_float, n: usize, dim: usize) -> c_int;

@@ -79,7 +79,7 @@ impl RvcInfer {
 
     /// Not in the reference: the engine's f0 method by `ffi::RVC_F0_RMVPE` (the same as `load_f0`), `ffi::RVC_F0_YIN`, the weight-free
     /// time-domain tracker (no `<data>/f0/rmvpe.rvcw` needed), or `ffi::RVC_F0_CREPE` / `ffi::RVC_F0_CREPE_TINY`
-    /// (`<data>/f0/crepe-full.rvcw` / `crepe-tiny.rvcw`)
+    /// (`<data>/f0/crepe-full.rvcw` / `crepe-tiny.rvcw`), or `ffi::RVC_F0_FCPE` (`<data>/f0/fcpe.rvcw`)
     pub fn load_f0_method(&mut self, method: i32) -> Result<(), BackendError> {
         self.check_load(unsafe { ffi::rvc_load_f0_method(self.handle, method) })
     }
@@ -96,6 +96,15 @@ impl RvcInfer {
             v if v < 0 => None,
             v => Some(v != 0),
         }
+    }
+
+    /// Not in the reference: FCPE's voicing threshold in [0, 1) (default 0.006): f0 = 0 where a frame's largest posterior is at or below it
+    pub fn set_fcpe_threshold(&mut self, threshold: f64) -> Result<(), BackendError> {
+        self.check_load(unsafe { ffi::rvc_set_fcpe_threshold(self.handle, threshold) })
+    }
+
+    pub fn fcpe_threshold(&self) -> f64 {
+        unsafe { ffi::rvc_fcpe_threshold(self.handle) }
     }
 
     /// rvc.rs:77-79

@@ -89,7 +89,13 @@ const char *rvc_last_error_message(rvc_engine *e);
  * about 1.9 MB of activations per frame at full capacity (0.24 MB tiny): 60 MB at the 32 frames of a 160 ms chunk, 2 GB per stream at 1024 frames. */
 #define RVC_F0_CREPE      4
 #define RVC_F0_CREPE_TINY 5
-rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rvc_load_f0; YIN: needs no file; CREPE, CREPE_TINY: see above; other values: RVC_SHAPE */
+/* FCPE (torchfcpe's CFNaiveMelPE, convolutions only; DESIGN.md "FCPE pitch"): a light network tracker on the same frame grid -- 128 Slaney mels, an input stack,
+ * N blocks of LayerNorm -> pointwise -> GLU -> depthwise 31 -> SiLU -> pointwise with a residual, 360 posteriors per frame -- decoded by upstream's
+ * local_argmax (the arg-max bin and its four neighbours either side) and fed to the same pitch tail.  Reads <data>/f0/fcpe.rvcw once per engine
+ * (python -m obs_rvc_amd.importers fcpe writes it; the sizes come from the blob); a missing file gives what a missing rmvpe.rvcw gives (RVC_BACKEND) and leaves
+ * the method as it was.  The values 3 and 6 are not methods. */
+#define RVC_F0_FCPE       7
+rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rvc_load_f0; YIN: needs no file; CREPE, CREPE_TINY, FCPE: see above; other values: RVC_SHAPE */
 int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded */
 /* CREPE's decoder: 0 = Viterbi (the default, upstream's), 1 = arg-max (the same decoder without the transition term).  Engine-wide, may be changed between
  * calls, part of a CREPE plan's identity; other values: RVC_SHAPE. */
@@ -97,6 +103,10 @@ int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded *
 #define RVC_CREPE_ARGMAX  1
 rvc_status rvc_set_crepe_decoder(rvc_engine *e, int decoder);
 int rvc_crepe_decoder(rvc_engine *e);
+/* FCPE's voicing threshold: f0 = 0 on a frame whose largest posterior is at or below it.  Default 0.006 (what upstream's real-time client passes).  Engine-wide,
+ * may be changed between calls and holds from the next call on (part of an FCPE plan's identity); values outside [0, 1) and NaN: RVC_SHAPE. */
+rvc_status rvc_set_fcpe_threshold(rvc_engine *e, double threshold);
+double rvc_fcpe_threshold(rvc_engine *e);
 /* Models trained without pitch guidance (upstream's SynthesizerTrnMs{256,768}NSFsid_nono, `f0: 0` in the checkpoint; blob config key f0 = 0; DESIGN.md
  * section 22): 1 = the loaded model has pitch guidance, 0 = it has none, -1 = no model loaded.  On a no-f0 model no call of the infer family (rvc_infer*,
  * rvc_session_process, rvc_convert*, rvc_convert_file*) needs an f0 method or runs one that is loaded: pitch_shift / has_pitch_shift, the pitch controls

@@ -118,6 +118,13 @@ int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *pho
  * decoded path and pd_out [B][Tm] its periodicity prob[t][bin[t]] before the median filter (either may be NULL).  Needs no weights.  B in [1, 64], Tm in
  * [2, 1024] (RVC_SHAPE otherwise).  0 = done, else an rvc_status. */
 int rvc_debug_crepe_decode(rvc_engine *e, const float *prob, int B, int Tm, int decoder, float *f0_out, int *bins_out, float *pd_out);
+/* fcpe_decode_kernel alone (obs_rvc_amd/csrc/fcpe.hip.h; DESIGN.md "FCPE pitch"), launched as an FCPE plan launches it but on the caller's posteriors prob
+ * [B][Tm][360] (no sigmoid), under the engine's threshold (rvc_set_fcpe_threshold).  f0_out [B][Tm] is what the plan hands to the pitch tail (Hz, 0 = unvoiced);
+ * bins_out [B][Tm] the arg-max bins (may be NULL).  Needs no weights.  B in [1, 64], Tm in [1, 1024] (RVC_SHAPE otherwise).  0 = done, else an rvc_status. */
+int rvc_debug_fcpe_decode(rvc_engine *e, const float *prob, int B, int Tm, float *f0_out, int *bins_out);
+/* fcpe_glu_dw_silu_kernel alone, launched as an FCPE plan launches it, on contiguous arrays: z [B][2 I][T] (value rows, then gate rows), w [I][31], bias [I]
+ * -> y_out [B][I][T] = silu(bias + depthwise31(z[:I] * sigmoid(z[I:])), zero padding 15).  B in [1, 64], I and T in [1, 4096].  0 = done, else an rvc_status. */
+int rvc_debug_fcpe_dw(rvc_engine *e, const float *z, const float *w, const float *bias, int B, int I, int T, float *y_out);
 /* the caller-side post-processing, the session's ring updates and a converter of several streams (obs_rvc_amd/csrc/chunk.hip.h, session.hip.h, resample.hip.h;
  * DESIGN.md "Post-processing and resamplers: what is tested"), each launch queued as rvc_session_process queues it, on the caller's arrays with the caller's
  * stream strides.  op: buffers buf[0..3] (each the WHOLE allocation, [streams][stride] floats, uploaded before the launches and downloaded after them: the

@@ -27,7 +27,7 @@ SYMBOLS = [
     "rvc_calibrate", "rvc_clock_monitor_start", "rvc_clock_monitor_stop",
     "rvc_session_create", "rvc_session_destroy", "rvc_session_process", "rvc_session_frame_size", "rvc_session_set_params", "rvc_session_set_params_stream", "rvc_session_geometry",
     "rvc_set_formant_shift", "rvc_set_formant_shift_stream", "rvc_formant_geometry",
-    "rvc_load_f0_method", "rvc_f0_method", "rvc_set_crepe_decoder", "rvc_crepe_decoder", "rvc_model_has_f0",
+    "rvc_load_f0_method", "rvc_f0_method", "rvc_set_crepe_decoder", "rvc_crepe_decoder", "rvc_model_has_f0", "rvc_set_fcpe_threshold", "rvc_fcpe_threshold",
     "rvc_set_pitch_semitones", "rvc_set_pitch_semitones_stream", "rvc_set_f0_range", "rvc_set_f0_range_stream",
     "rvc_set_f0_median", "rvc_set_f0_median_stream", "rvc_set_f0_snap", "rvc_set_f0_snap_stream",
     "rvc_set_protect", "rvc_set_protect_stream",
@@ -62,7 +62,7 @@ def _include_closure(src):
 # implicit-GEMM template instantiations are the bulk of the compile time; as separate units they build in parallel (5 min -> about 1.5 min on 8 cores)
 # and are not rebuilt when only the engine changes.
 UNITS = [(src, flags, _include_closure(src)) for src, flags in
-         [(u, []) for u in ("engine.hip", "debug.hip", "calib.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "model_crepe.hip", "model_synth.hip", "retrieval.hip")] +
+         [(u, []) for u in ("engine.hip", "debug.hip", "calib.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "model_crepe.hip", "model_fcpe.hip", "model_synth.hip", "retrieval.hip")] +
          [("igemm2_inst.hip", ["-DRVC_IGEMM2_CFG=%d" % c]) for c in range(5)] +
          [("igemm_tiled_inst.hip", ["-DRVC_TILED_PART=%d" % c]) for c in range(4)] +
          [("igemm2w_inst.hip", ["-DRVC_G2W_PART=%d" % c]) for c in range(3)] +
@@ -366,6 +366,12 @@ def lib():
         L.rvc_set_crepe_decoder.argtypes = [vp, C.c_int]
         L.rvc_crepe_decoder.argtypes = [vp]
         L.rvc_debug_crepe_decode.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, vp, fp]
+    if hasattr(L, "rvc_set_fcpe_threshold") or not override:
+        L.rvc_set_fcpe_threshold.argtypes = [vp, C.c_double]
+        L.rvc_fcpe_threshold.argtypes = [vp]
+        L.rvc_fcpe_threshold.restype = C.c_double
+        L.rvc_debug_fcpe_decode.argtypes = [vp, fp, C.c_int, C.c_int, fp, vp]
+        L.rvc_debug_fcpe_dw.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
     if hasattr(L, "rvc_set_pitch_semitones") or not override:

@@ -1,4 +1,4 @@
-"""python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny] [--index I --index-rate r --index-k 4|8 --nprobe p]
+"""python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny|fcpe] [--index I --index-rate r --index-k 4|8 --nprobe p]
        [--pitch semitones] [--formant st] [--protect p] [--streams S] [--window k --context C --crossfade X] [--no-highpass] [--rate out_rate]
        [--rms-mix-rate r] [--resampler blocks|device]
 
@@ -26,8 +26,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--model", required=True, help="the voice: <model>.rvcw (or its .onnx sibling's name)")
     p.add_argument("--data", default=None, help="the engine's data directory (contentvec/, f0/); default: the model zoo of the package")
     p.add_argument("--version", type=int, choices=(1, 2), default=2, help="RVC model version: 1 = 256-dim features, 2 = 768-dim (default)")
-    p.add_argument("--f0", choices=("rmvpe", "yin", "crepe-full", "crepe-tiny"), default="rmvpe",
-                   help="f0 method (default rmvpe; not loaded for a model without pitch guidance); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw")
+    p.add_argument("--f0", choices=("rmvpe", "yin", "crepe-full", "crepe-tiny", "fcpe"), default="rmvpe",
+                   help="f0 method (default rmvpe; not loaded for a model without pitch guidance); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw; fcpe reads <data>/f0/fcpe.rvcw")
     p.add_argument("--index", default=None, help="retrieval index: a Faiss .index file or a .npy matrix")
     p.add_argument("--index-rate", type=float, default=0.75, help="share of the retrieved features (default 0.75, with --index only)")
     p.add_argument("--index-k", type=int, choices=(4, 8), default=8, help="neighbours blended per frame (default 8, upstream's)")

@@ -619,6 +619,49 @@ int rvc_debug_crepe_decode(rvc_engine *e, const float *prob, int B, int Tm, int 
     });
 }
 
+// test aid: FCPE's decoder alone (fcpe.hip.h; tests/test_gpu_fcpe.py) on the caller's posteriors, through the launch a plan uses (launch_fcpe_decode), under the
+// engine's threshold
+int rvc_debug_fcpe_decode(rvc_engine *e, const float *prob, int B, int Tm, float *f0_out, int *bins_out)
+{
+    return (int)guarded(e, [&]() {
+        if (!prob || !f0_out || B < 1 || B > 64 || Tm < 1 || Tm > 1024) throw ShapeError("fcpe decode: B in [1, 64], Tm in [1, 1024]");
+        const size_t n = (size_t)B * Tm;
+        DevBuf<float> d_prob, d_f0, d_tab; DevBuf<int> d_bins;
+        d_prob.alloc(n * 360); d_f0.alloc(n); d_bins.alloc(n); d_tab.alloc(360);
+        const std::vector<float> tab = fcpe_f0_table();
+        HIPCHK(hipMemcpy(d_tab.get(), tab.data(), 360 * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_prob.get(), prob, n * 360 * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipDeviceSynchronize());
+        launch_fcpe_decode(e->stream, B, Tm, nullptr, 0, 0, d_prob.get(), nullptr, d_tab.get(), e->fcpe_threshold, d_f0.get(), d_bins.get());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipMemcpy(f0_out, d_f0.get(), n * sizeof(float), hipMemcpyDeviceToHost));
+        if (bins_out) HIPCHK(hipMemcpy(bins_out, d_bins.get(), n * sizeof(int), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
+// test aid: FCPE's GLU + depthwise + SiLU kernel alone (fcpe.hip.h), through the launch a plan uses (launch_fcpe_glu_dw), on contiguous arrays: z [B][2 I][T],
+// w [I][31], bias [I] -> y [B][I][T].  Any T: the plan's lengths are multiples of 32, the kernel's time tile is 64
+int rvc_debug_fcpe_dw(rvc_engine *e, const float *z, const float *w, const float *bias, int B, int I, int T, float *y_out)
+{
+    return (int)guarded(e, [&]() {
+        if (!z || !w || !bias || !y_out || B < 1 || B > 64 || I < 1 || I > 4096 || T < 1 || T > 4096) throw ShapeError("fcpe depthwise: B in [1, 64], I, T in [1, 4096]");
+        const size_t nz = (size_t)B * 2 * I * T, ny = (size_t)B * I * T;
+        DevBuf<float> d_z, d_w, d_b, d_y;
+        d_z.alloc(nz); d_w.alloc((size_t)I * 31); d_b.alloc(I); d_y.alloc(ny);
+        HIPCHK(hipMemcpy(d_z.get(), z, nz * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_w.get(), w, (size_t)I * 31 * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_b.get(), bias, (size_t)I * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipDeviceSynchronize());
+        launch_fcpe_glu_dw(e->stream, B, I, T, d_z.get(), T, 2LL * I * T, d_w.get(), d_b.get(), d_y.get(), T, (long long)I * T);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipMemcpy(y_out, d_y.get(), ny * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
 // test aid: the caller-side post-processing, the session's ring updates and a converter of several streams (chunk.hip.h, session.hip.h, resample.hip.h;
 // tests/test_gpu_post.py) on the caller's arrays with the caller's stream strides, each launch queued as the session queues it (engine_int.h launch_post_* /
 // launch_ring_* / launch_resampler).  Every size is checked against the strides on the host before anything is queued.

@@ -216,7 +216,7 @@ static void alloc_state(rvc_engine *e)
 
 // ------------------------------- plan -------------------------------------------------
 static inline bool is_crepe(int method) { return method == RVC_F0_CREPE || method == RVC_F0_CREPE_TINY; }
-// the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, or CREPE's network and decoder; behind each the same pitch tail
+// the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, CREPE's or FCPE's network and decoder; behind each the same pitch tail
 // (shift, cache, get_f0_post)
 static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache, size_t hubert_length, float **pitchf_out, int **pitch_out)
 {
@@ -227,6 +227,11 @@ static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, 
     }
     if (is_crepe(e->f0_method)) {
         const float *f0 = build_crepe(e, pl, B, L, frame16k);
+        build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
+        return;
+    }
+    if (e->f0_method == RVC_F0_FCPE) {
+        const float *f0 = build_fcpe(e, pl, B, L, frame16k);
         build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
         return;
     }
@@ -252,6 +257,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     // engine's f0 method and CREPE decoder are no part of such a plan's key (key_f0 / key_dec = 0); the hubert and pitch plans keep theirs
     const bool nof0 = mode == 0 && e->sy && !e->sy->has_f0;
     const int key_f0 = nof0 ? 0 : e->f0_method, key_dec = !nof0 && is_crepe(e->f0_method) ? e->crepe_decoder : 0;
+    const double key_thr = key_f0 == RVC_F0_FCPE ? e->fcpe_threshold : 0.0;          // FCPE's voicing threshold is baked into its decoder's launch: part of the key likewise
     const bool with_index = mode == 0 && e->index.rows && e->index_rate > 0.f;
     // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams (bucket_ids: the
     // streams of a bucket plan; else every stream) has it on.  Which value a stream has is no part of the key: the kernel reads it every chunk
@@ -271,7 +277,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     for (auto &p : e->plans)
         if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
             p->with_index == with_index && p->with_protect == with_protect && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
-            p->R2 == R2 && p->fstage == fstage && p->f0_method == key_f0 && p->crepe_decoder == key_dec && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
+            p->R2 == R2 && p->fstage == fstage && p->f0_method == key_f0 && p->crepe_decoder == key_dec && p->fcpe_threshold == key_thr && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -284,7 +290,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
     pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_protect = with_protect; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
     pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
-    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = key_f0; pl.crepe_decoder = key_dec; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
+    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = key_f0; pl.crepe_decoder = key_dec; pl.fcpe_threshold = key_thr; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
     T1 src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;
@@ -761,7 +767,7 @@ void rvc_destroy(rvc_engine *e)
     (void)hipDeviceSynchronize();
     e->plans.clear();
     index_build_abort(e);
-    e->cv.reset(); e->rm.reset(); e->cr_full.reset(); e->cr_tiny.reset(); e->sy.reset();
+    e->cv.reset(); e->rm.reset(); e->cr_full.reset(); e->cr_tiny.reset(); e->fc.reset(); e->sy.reset();
     wfree(e->d_window); wfree(e->d_twiddle); wfree(e->d_basis);      // (upload_f: slab memory)
     if (e->d_band) (void)hipFree(e->d_band);
     if (e->d_state) (void)hipFree(e->d_state);
@@ -845,7 +851,12 @@ rvc_status rvc_load_f0_method(rvc_engine *e, int method)
             e->f0_method = method;
             return RVC_OK;
         }
-        if (method != RVC_F0_YIN) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE or RVC_F0_CREPE_TINY");
+        if (method == RVC_F0_FCPE) {
+            if (!e->fc) { Blob b(e->data_path + "/f0/fcpe.rvcw"); e->fc.reset(new ModelFC(b)); }          // read once and kept, as the CREPE presets are
+            e->f0_method = method;
+            return RVC_OK;
+        }
+        if (method != RVC_F0_YIN) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY or RVC_F0_FCPE");
         e->f0_method = RVC_F0_YIN;
         return RVC_OK;
     });
@@ -863,6 +874,16 @@ rvc_status rvc_set_crepe_decoder(rvc_engine *e, int decoder)
     });
 }
 int rvc_crepe_decoder(rvc_engine *e) { return e ? e->crepe_decoder : 0; }
+// FCPE's voicing threshold (fcpe_decode_kernel): part of an FCPE plan's key, so a changed value holds from the next call on
+rvc_status rvc_set_fcpe_threshold(rvc_engine *e, double threshold)
+{
+    return guarded(e, [&]() {
+        if (!(threshold >= 0.0 && threshold < 1.0)) throw ShapeError("fcpe threshold: a value in [0, 1)");
+        e->fcpe_threshold = threshold;
+        return RVC_OK;
+    });
+}
+double rvc_fcpe_threshold(rvc_engine *e) { return e ? e->fcpe_threshold : 0.0; }
 // rvc.rs:77-79
 void rvc_unload_model(rvc_engine *e)
 {

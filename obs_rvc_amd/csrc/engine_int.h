@@ -2,13 +2,14 @@
 //   plan.hip         the planner: device memory, prepared convolution weights, the op list, implicit-GEMM tile selection, test-hook table
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
 //   model_yin.hip    YIN f0 (build_yin)                      model_crepe.hip   CREPE f0 (build_crepe, the decoder's launch)
+//   model_fcpe.hip   FCPE f0 (build_fcpe, the decoder's and the depthwise kernel's launches)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
 //   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter, with
 //                    resample_whole.hip.h and change_rms.hip.h)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
-// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, crepe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
+// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
 // or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm.hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
@@ -253,6 +254,7 @@ struct Plan {
     int mode = 0;   // 0 infer, 1 hubert only, 2 pitch only
     int f0_method = 0;            // the engine's f0 method when the plan was built (its f0 branch is that method's)
     int crepe_decoder = 0;        // ... and, for the CREPE methods, the engine's decoder (0 = Viterbi, 1 = arg-max; 0 on every other plan)
+    double fcpe_threshold = 0;    // ... and, for FCPE, the engine's voicing threshold (baked into the decoder's launch; 0 on every other plan)
     // formant shift (formant.hip.h): fstage = the plan has the formant stage (some stream stretches or resamples); the decoder then runs
     // on R2 frames and formant_resample_kernel brings every stream back to R upp samples.  fstage = false: today's plan, R2 = R
     uint32_t R2 = 0; bool fstage = false;
@@ -412,6 +414,22 @@ struct ModelCR {
     ModelCR(const ModelCR &) = delete; ModelCR &operator=(const ModelCR &) = delete;
 };
 
+// FCPE (model_fcpe.hip): the input stack (two k = 3 convolutions around GroupNorm(4)), `layers` blocks of LayerNorm -> pointwise H -> 2 I ->
+// GLU -> depthwise 31 -> SiLU -> pointwise I -> H, the final LayerNorm and the classifier (weight norm folded by the importer); its own Slaney filterbank for
+// the mel front end (basis [128][513], band [128][2] as ints) and Hz per bin
+struct ModelFC {
+    int H = 0, I = 0, layers = 0;
+    ConvW in0, in1, out;
+    float *gn_g = nullptr, *gn_b = nullptr, *norm_g = nullptr, *norm_b = nullptr, *basis = nullptr, *f0tab = nullptr;
+    int *band = nullptr;
+    struct Layer { float *ln_g = nullptr, *ln_b = nullptr, *dw_w = nullptr, *dw_b = nullptr; ConvW pw1, pw2; };
+    std::vector<Layer> ly;
+    size_t weight_bytes = 0;
+    explicit ModelFC(const Blob &b);
+    ~ModelFC();
+    ModelFC(const ModelFC &) = delete; ModelFC &operator=(const ModelFC &) = delete;
+};
+
 // GLU row packing of a WaveNet in-layer (igemm.hip.h glu_store): packed row f*16 + kq*4 + r <- model row f*8 + kq*2 + (r&1) of the tanh half (r < 2)
 // or the sigmoid half (r >= 2, + H).  w: [2H][K] in model row order, bias: [2H]
 template <typename T> void glu_pack_rows(const T *w, const float *bias, int H, size_t K, std::vector<float> &wp, std::vector<float> &bp);      // (model_synth.hip: float and double)
@@ -483,6 +501,8 @@ struct rvc_engine {
     std::unique_ptr<ModelRM> rm;
     int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights), RVC_F0_CREPE / _TINY (cr_full / cr_tiny); engine-wide and part of a plan's identity
     std::unique_ptr<ModelCR> cr_full, cr_tiny;        // each stays loaded once read: going back to it costs no file and keeps its plans
+    std::unique_ptr<ModelFC> fc;                      // FCPE (RVC_F0_FCPE), kept once read like the CREPE presets
+    double fcpe_threshold = 0.006;                    // rvc_set_fcpe_threshold: f0 = 0 where the top posterior is at or below it; engine-wide and part of an FCPE plan's identity
     int crepe_decoder = 0;                            // rvc_set_crepe_decoder: 0 = Viterbi, 1 = arg-max; engine-wide and part of a CREPE plan's identity
     std::unique_ptr<ModelSY> sy;
     // constants for the mel front end
@@ -576,10 +596,20 @@ float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
 std::vector<float> crepe_f0_table();
 size_t crepe_backpointer_bytes(int B, int Tm);
 void launch_crepe_decode(hipStream_t s, int B, const float *prob, int Tm, int decoder, const float *f0tab, unsigned char *bp, float *f0, int *bins, float *pd);
+float *build_fcpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
+// FCPE's decoder and its GLU + depthwise + SiLU kernel alone (fcpe.hip.h): the plan's launches and the debug entries' (debug.hip).  Decoder: logit [B][360][l_ld]
+// (sigmoid applied, posteriors written to prob [B][Tm][360]) or, with logit null, the caller's posteriors prob_in; bins may be null.  Depthwise: z [B][2 I][z_ld] ->
+// y [B][I][y_ld], w [I][31], bias [I]
+std::vector<float> fcpe_f0_table();
+float fcpe_cent_step();
+void launch_fcpe_decode(hipStream_t s, int B, int Tm, const float *logit, int l_ld, long long l_bs, const float *prob_in, float *prob, const float *f0tab, double threshold, float *f0, int *bins);
+void launch_fcpe_glu_dw(hipStream_t s, int B, int I, int T, const float *z, int z_ld, long long z_bs, const float *w, const float *bias, float *y, int y_ld, long long y_bs);
 T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf);
 // the head and the tail of the f0 branch and ContentVec's first layer as plan helpers: the builders above call them, and so does rvc_debug_front (debug.hip)
 void add_conv0_front(Plan &pl, const ConvW &cw, const float *w_raw, const float *gn_g, const float *gn_b, int kt, int st, const T1 &x, const T1 &y);
 void add_mel_frontend(rvc_engine *e, Plan &pl, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, float *mel, const T2 &img, float bn_scale, float bn_shift);
+void add_mel_frontend_tables(rvc_engine *e, Plan &pl, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, float *mel, const T2 &img, float bn_scale,
+                             float bn_shift, const float *basis, const int *band);      // the same launch on another filterbank (device tables)
 void add_pitch_post(Plan &pl, int B, const T1 &sal, int Tm, StreamState *st, const CallParams *cp, float *f0, bool update, long long shift, long long cache_start,
                     long long read_start, int R, float *pitchf, int *pitch, const float *f0_in = nullptr);
 // one ConvBlockRes of RMVPE as build_rmvpe queues it (model_rmvpe.hip; rvc_debug_rm_block calls the same three).  add_rm_block_fused: the block as ONE launch of

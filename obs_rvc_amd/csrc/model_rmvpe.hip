@@ -268,10 +268,16 @@ void add_avgpool2(Plan &pl, const T2 &x, const T2 &p)
 // caller's device buffer (Plan::cur_in) in place of `audio` when there is one.
 void add_mel_frontend(rvc_engine *e, Plan &pl, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, float *mel, const T2 &img, float bn_scale, float bn_shift)
 {
+    add_mel_frontend_tables(e, pl, B, audio, audio_bs, n, frame, Tm, mel, img, bn_scale, bn_shift, e->d_basis, e->d_band);
+}
+// ... the same launch on another filterbank: basis [128][513] and band [128][2] (first / one-past-last non-zero bin) on the device (FCPE's Slaney bank, model_fcpe.hip)
+void add_mel_frontend_tables(rvc_engine *e, Plan &pl, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, float *mel, const T2 &img, float bn_scale,
+                             float bn_shift, const float *basis, const int *band)
+{
     if (frame < 513 || frame > n || Tm < 1 || (long long)(Tm - 1) * 160 > (long long)frame) throw ShapeError("mel front end: frame out of range");   // (one reflection per side)
     MelP mp{};
     mp.audio = audio; mp.audio_bs = audio_bs; mp.n = n; mp.frame = frame; mp.Tm = Tm;
-    mp.window = e->d_window; mp.twiddle = e->d_twiddle; mp.basis = e->d_basis; mp.band = e->d_band;
+    mp.window = e->d_window; mp.twiddle = e->d_twiddle; mp.basis = basis; mp.band = band;
     mp.mel = mel; mp.img = img.p; mp.img_bs = img.bs; mp.img_ld = img.ld; mp.bn_scale = bn_scale; mp.bn_shift = bn_shift;
     dim3 grid(Tm, B);
     Plan *plp = &pl;

@@ -22,6 +22,7 @@ structure and parameter names (tests/test_importers.py) -- a real file may still
 CLI:  python -m obs_rvc_amd.importers contentvec|rmvpe|synth <input> <output.rvcw> [--version 2] [--sid 0] [--sr 48000]
                                       [--up-rates 10,10,2,2]
       python -m obs_rvc_amd.importers crepe <full.pth|tiny.pth> <output.rvcw>      (-> <data>/f0/crepe-full.rvcw or crepe-tiny.rvcw)
+      python -m obs_rvc_amd.importers fcpe <in.pt> <output.rvcw>                   (-> <data>/f0/fcpe.rvcw)
 """
 from __future__ import annotations
 
@@ -629,6 +630,68 @@ def import_crepe(named: Named) -> Tuple[dict, Named]:
     return dict(kind=4, cap=m), t
 
 
+def import_fcpe(named: Named) -> Tuple[dict, Named]:
+    """A torchfcpe CFNaiveMelPE state dict with conv_only = true.  Key names as far as known: input_stack.{0,3}.{weight, bias} (Conv1d k = 3),
+    input_stack.1.{weight, bias} (GroupNorm), net.encoder_layers.N.conformer.net.{0 (LayerNorm), 2 (Conv1d H -> 2 I, k = 1), 4.conv (depthwise, [I][1][31]),
+    6 (Conv1d I -> H, k = 1)}.{weight, bias}, norm.{weight, bias}, output_proj.bias and output_proj's weight-normed weight in either spelling:
+    weight_g / weight_v or parametrizations.weight.original0 / original1.  Sizes come from the tensor shapes and every shape is checked; the weight norm is
+    folded (g v / |v| per output row); the filterbank is added (W.fcpe_mel_basis).  A dict that carries attention tensors (conv_only = false) is rejected:
+    that path is not built.  The table is checked on synthesized dicts; the pin against a real torchfcpe checkpoint is open."""
+    attn = sorted(k for k in named if ".attn." in k or ".attention." in k)
+    if attn:
+        raise ImportError_("fcpe: the state dict carries attention tensors (%s, ...): a model with conv_only = false, whose attention path is not built" % attn[0])
+    for wrap in ("model.", "module."):
+        if not any(k.startswith("input_stack.") for k in named) and any(k.startswith(wrap + "input_stack.") for k in named):
+            named = {k[len(wrap):]: v for k, v in named.items() if k.startswith(wrap)}
+    pre = "net.encoder_layers.%d.conformer.net."
+    N = 0
+    while (pre % N) + "0.weight" in named:
+        N += 1
+    need = ["input_stack.%d.%s" % (i, f) for i in (0, 1, 3) for f in ("weight", "bias")] + ["norm.weight", "norm.bias", "output_proj.bias"]
+    need += [(pre % l) + k + f for l in range(N) for k in ("0", "2", "4.conv", "6") for f in (".weight", ".bias")]
+    if "output_proj.weight_g" in named or "output_proj.weight_v" in named:
+        gk, vk = "output_proj.weight_g", "output_proj.weight_v"
+    else:
+        gk, vk = "output_proj.parametrizations.weight.original0", "output_proj.parametrizations.weight.original1"
+    need += [gk, vk]
+    missing = [k for k in need if k not in named]
+    if missing or N == 0:
+        raise ImportError_("fcpe: missing tensors: " + ", ".join(missing or [(pre % 0) + "0.weight"]))
+    a = lambda k: np.asarray(named[k])
+
+    def want(k, shape):
+        if tuple(a(k).shape) != tuple(shape):
+            raise ImportError_("fcpe: %s is %s, expected %s" % (k, tuple(a(k).shape), tuple(shape)))
+        return a(k)
+
+    w0 = a("input_stack.0.weight")
+    if w0.ndim != 3 or w0.shape[1:] != (W.FCPE_MELS, 3):
+        raise ImportError_("fcpe: input_stack.0.weight is %s, expected (H, %d, 3)" % (tuple(w0.shape), W.FCPE_MELS))
+    H = int(w0.shape[0])
+    p1 = a((pre % 0) + "2.weight")
+    if p1.ndim != 3 or p1.shape[0] % 2 or p1.shape[1:] != (H, 1):
+        raise ImportError_("fcpe: %s is %s, expected (2 I, %d, 1)" % ((pre % 0) + "2.weight", tuple(p1.shape), H))
+    I = int(p1.shape[0]) // 2
+    if H % 16 or I % 16:
+        raise ImportError_("fcpe: hidden %d and inner %d must be multiples of 16" % (H, I))
+    t: Named = {}
+    t["fc.in0.w"], t["fc.in0.b"] = w0, want("input_stack.0.bias", (H,))
+    t["fc.gn.g"], t["fc.gn.b"] = want("input_stack.1.weight", (H,)), want("input_stack.1.bias", (H,))
+    t["fc.in1.w"], t["fc.in1.b"] = want("input_stack.3.weight", (H, H, 3)), want("input_stack.3.bias", (H,))
+    for l in range(N):
+        q = pre % l
+        t["fc.l%d.ln.g" % l], t["fc.l%d.ln.b" % l] = want(q + "0.weight", (H,)), want(q + "0.bias", (H,))
+        t["fc.l%d.pw1.w" % l], t["fc.l%d.pw1.b" % l] = want(q + "2.weight", (2 * I, H, 1))[..., 0], want(q + "2.bias", (2 * I,))
+        t["fc.l%d.dw.w" % l], t["fc.l%d.dw.b" % l] = want(q + "4.conv.weight", (I, 1, W.FCPE_DW_K))[:, 0, :], want(q + "4.conv.bias", (I,))
+        t["fc.l%d.pw2.w" % l], t["fc.l%d.pw2.b" % l] = want(q + "6.weight", (H, I, 1))[..., 0], want(q + "6.bias", (H,))
+    t["fc.norm.g"], t["fc.norm.b"] = want("norm.weight", (H,)), want("norm.bias", (H,))
+    g, v = want(gk, (W.FCPE_BINS, 1)).astype(np.float64), want(vk, (W.FCPE_BINS, H)).astype(np.float64)
+    t["fc.out.w"] = g * v / np.sqrt(np.sum(v * v, axis=1, keepdims=True))
+    t["fc.out.b"] = want("output_proj.bias", (W.FCPE_BINS,))
+    t["fc.mel_basis"], t["fc.mel_band"] = W.fcpe_mel_basis()
+    return dict(kind=5, hidden=H, inner=I, layers=N), t
+
+
 def convert(kind: str, src: str, dst: str, **kw) -> None:
     named = load_named_tensors(src)
     if kind == "synth" and kw.get("config") is None:
@@ -641,13 +704,13 @@ def convert(kind: str, src: str, dst: str, **kw) -> None:
         cfg, t = import_rmvpe_structural(inits, nodes)
         W.write_blob(dst, cfg, {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in t.items()})
         return
-    cfg, t = {"contentvec": import_contentvec, "rmvpe": import_rmvpe, "synth": import_synth, "crepe": import_crepe}[kind](named, **kw)
+    cfg, t = {"contentvec": import_contentvec, "rmvpe": import_rmvpe, "synth": import_synth, "crepe": import_crepe, "fcpe": import_fcpe}[kind](named, **kw)
     W.write_blob(dst, cfg, {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in t.items()})
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("kind", choices=["contentvec", "rmvpe", "synth", "crepe"])
+    ap.add_argument("kind", choices=["contentvec", "rmvpe", "synth", "crepe", "fcpe"])
     ap.add_argument("src"); ap.add_argument("dst")
     ap.add_argument("--version", type=int, default=2); ap.add_argument("--sid", type=int, default=0); ap.add_argument("--sr", type=int, default=None)
     ap.add_argument("--up-rates", default=None, help="synthesizer upsample rates, e.g. 10,10,2,2 (default: the checkpoint's config list, else from --sr)")

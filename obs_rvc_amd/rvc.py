@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _native
-from .rvc_common import (CREPE_ARGMAX, CREPE_VITERBI, CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_CREPE, F0_CREPE_TINY, F0_RMVPE, F0_YIN, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
+from .rvc_common import (CREPE_ARGMAX, CREPE_VITERBI, CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_RMVPE, F0_YIN, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
                          RvcInferError, RvcModelVersion, scale_mask)
 
 _FP = C.POINTER(C.c_float)
@@ -57,20 +57,20 @@ class RvcInfer:
     def load_f0(self, pitch_algorithm=PitchAlgorithm.Rmvpe):
         self._chk(self._L.rvc_load_f0(self._h, int(PitchAlgorithm.from_value(pitch_algorithm))))
 
-    _F0_NAMES = {"rmvpe": F0_RMVPE, "yin": F0_YIN, "crepe": F0_CREPE, "crepe-full": F0_CREPE, "crepe-tiny": F0_CREPE_TINY}
+    _F0_NAMES = {"rmvpe": F0_RMVPE, "yin": F0_YIN, "crepe": F0_CREPE, "crepe-full": F0_CREPE, "crepe-tiny": F0_CREPE_TINY, "fcpe": F0_FCPE}
 
     def load_f0_method(self, method):
         """The engine's f0 method: "rmvpe" / F0_RMVPE (loads <data>/f0/rmvpe.rvcw, as load_f0), "yin" / F0_YIN (needs no file), "crepe" = "crepe-full" / F0_CREPE
-        (<data>/f0/crepe-full.rvcw) or "crepe-tiny" / F0_CREPE_TINY (<data>/f0/crepe-tiny.rvcw)."""
+        (<data>/f0/crepe-full.rvcw), "crepe-tiny" / F0_CREPE_TINY (<data>/f0/crepe-tiny.rvcw) or "fcpe" / F0_FCPE (<data>/f0/fcpe.rvcw)."""
         if isinstance(method, str):
             if method.lower() not in self._F0_NAMES:
-                raise ValueError("f0 method: 'rmvpe', 'yin', 'crepe' (= 'crepe-full') or 'crepe-tiny', not %r" % method)
+                raise ValueError("f0 method: 'rmvpe', 'yin', 'crepe' (= 'crepe-full'), 'crepe-tiny' or 'fcpe', not %r" % method)
             method = self._F0_NAMES[method.lower()]
         self._chk(self._L.rvc_load_f0_method(self._h, int(method)))
 
     @property
     def f0_method(self) -> int:
-        """0 = none loaded, F0_RMVPE, F0_YIN, F0_CREPE, F0_CREPE_TINY"""
+        """0 = none loaded, F0_RMVPE, F0_YIN, F0_CREPE, F0_CREPE_TINY, F0_FCPE"""
         return int(self._L.rvc_f0_method(self._h))
 
     def set_crepe_decoder(self, decoder):
@@ -84,6 +84,14 @@ class RvcInfer:
     @property
     def crepe_decoder(self) -> int:
         return int(self._L.rvc_crepe_decoder(self._h))
+
+    def set_fcpe_threshold(self, threshold: float):
+        """FCPE's voicing threshold in [0, 1): f0 = 0 where a frame's largest posterior is at or below it (default 0.006); engine-wide"""
+        self._chk(self._L.rvc_set_fcpe_threshold(self._h, float(threshold)))
+
+    @property
+    def fcpe_threshold(self) -> float:
+        return float(self._L.rvc_fcpe_threshold(self._h))
 
     def unload_model(self):
         self._L.rvc_unload_model(self._h)

@@ -11,6 +11,7 @@ CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER = 0, 1
 # f0 methods of rvc_load_f0_method (include/rvc_mi355x.h RVC_F0_*): PitchAlgorithm below stays the reference's one-variant enum
 F0_RMVPE, F0_YIN = 1, 2
 F0_CREPE, F0_CREPE_TINY = 4, 5          # (3 is no method: it stays the unknown value it was)
+F0_FCPE = 7                             # (nor is 6)
 # CREPE's decoders (rvc_set_crepe_decoder, RVC_CREPE_*)
 CREPE_VITERBI, CREPE_ARGMAX = 0, 1
 # input gate: a threshold at or below this many dB switches it off

@@ -276,6 +276,91 @@ def write_crepe(data_dir: str, preset: str = "full", as_preset: str | None = Non
     return path
 
 
+# FCPE (torchfcpe's CFNaiveMelPE, conv_only): hidden H, inner I, N layers -- full is upstream's, micro exists for tests
+FCPE_PRESETS = {"full": dict(hidden=512, inner=1024, layers=6), "micro": dict(hidden=64, inner=128, layers=2)}
+FCPE_MELS, FCPE_BINS, FCPE_DW_K = 128, 360, 31
+# make_fcpe: the classifier's gain and bias, set once by hand so that the posteriors on voiced input are neither flat nor saturated (tests/test_fcpe_ref.py
+# states the condition: on most frames the top bin is at least twice the ninth-largest)
+_FCPE_OUT_GAIN, _FCPE_OUT_BIAS = 2.2, -6.0
+
+
+def slaney_hz_to_mel(f):
+    """the Slaney mel scale: linear at 200 / 3 Hz per mel below 1000 Hz, logarithmic with step ln(6.4) / 27 above"""
+    f = np.asarray(f, np.float64)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0), f * (3.0 / 200.0))
+
+
+def slaney_mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), m * (200.0 / 3.0))
+
+
+def fcpe_mel_edges() -> np.ndarray:
+    """the 130 band edges in Hz: 128 filters from 0 to 8000 Hz, equally spaced in Slaney mels"""
+    return slaney_mel_to_hz(np.linspace(slaney_hz_to_mel(0.0), slaney_hz_to_mel(8000.0), FCPE_MELS + 2))
+
+
+def fcpe_mel_basis():
+    """FCPE's filterbank over the 513 bin centres of a 1024-point transform at 16 kHz: triangles between the Slaney edges, each scaled by 2 / (f[m + 2] - f[m]).
+    -> (basis [128][513] float32, band [128][2]: first and one-past-last non-zero bin of the float32 row)"""
+    f = fcpe_mel_edges()
+    bins = np.linspace(0.0, 8000.0, 513)
+    lower = (bins[None, :] - f[:-2, None]) / (f[1:-1] - f[:-2])[:, None]
+    upper = (f[2:, None] - bins[None, :]) / (f[2:] - f[1:-1])[:, None]
+    basis = (np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (f[2:] - f[:-2]))[:, None]).astype(np.float32)
+    band = np.zeros((FCPE_MELS, 2), np.float32)
+    for m in range(FCPE_MELS):
+        nz = np.nonzero(basis[m])[0]
+        if len(nz):
+            band[m] = (nz[0], nz[-1] + 1)
+    return basis, band
+
+
+def make_fcpe(preset: str = "full", seed: int = 1357):
+    """Seeded FCPE weights in blob layout: fc.in0.w [H][128][3], fc.gn.g / .b, fc.in1.w [H][H][3], per layer fc.lN.ln.g / .b, fc.lN.pw1.w [2 I][H],
+    fc.lN.dw.w [I][31], fc.lN.pw2.w [H][I] (biases .b beside each), fc.norm.g / .b, fc.out.w [360][H] (weight norm folded), fc.out.b, and the
+    filterbank fc.mel_basis [128][513] with fc.mel_band [128][2].  He-scaled convolutions keep the activations of order one; the classifier's rows are
+    smooth over neighbouring bins, so a frame's posteriors form ridges a few bins wide."""
+    from scipy.ndimage import gaussian_filter1d
+
+    c = FCPE_PRESETS[preset]
+    H, I, N = c["hidden"], c["inner"], c["layers"]
+    g = _Gen(seed)
+    g.fan("fc.in0.w", (H, FCPE_MELS, 3), FCPE_MELS * 3, 0.5)          # (log-mels are of order 5)
+    g.normal("fc.in0.b", (H,), 0.05)
+    g.affine("fc.gn", H)
+    g.fan("fc.in1.w", (H, H, 3), H * 3, 1.4)
+    g.normal("fc.in1.b", (H,), 0.05)
+    for l in range(N):
+        g.affine("fc.l%d.ln" % l, H)
+        g.fan("fc.l%d.pw1.w" % l, (2 * I, H), H, 1.2)
+        g.normal("fc.l%d.pw1.b" % l, (2 * I,), 0.05)
+        g.fan("fc.l%d.dw.w" % l, (I, FCPE_DW_K), FCPE_DW_K, 2.0)
+        g.normal("fc.l%d.dw.b" % l, (I,), 0.05)
+        g.fan("fc.l%d.pw2.w" % l, (H, I), I, 1.5)
+        g.normal("fc.l%d.pw2.b" % l, (H,), 0.05)
+    g.affine("fc.norm", H)
+    w = g.rng.standard_normal(size=(FCPE_BINS, H))
+    w = gaussian_filter1d(w, sigma=1.5, axis=0, mode="nearest")
+    w *= _FCPE_OUT_GAIN / (np.sqrt(np.mean(w ** 2)) * np.sqrt(H))
+    g.t["fc.out.w"] = w.astype(np.float32)
+    g.t["fc.out.b"] = np.full(FCPE_BINS, _FCPE_OUT_BIAS, np.float32)
+    g.t["fc.mel_basis"], g.t["fc.mel_band"] = fcpe_mel_basis()
+    return dict(kind=5, hidden=H, inner=I, layers=N), g.t
+
+
+def write_fcpe(data_dir: str, preset: str = "full", as_preset: str | None = None, force: bool = False) -> str:
+    """<data_dir>/f0/fcpe.rvcw with make_fcpe(preset); idempotent (an existing file is kept).  The engine reads one file name whatever the sizes (they are blob
+    config keys), so as_preset has nothing to choose: it is accepted for symmetry with write_crepe and must be None or "full".  -> its path"""
+    if as_preset not in (None, "full"):
+        raise ValueError("fcpe: the engine reads <data>/f0/fcpe.rvcw only")
+    os.makedirs(os.path.join(data_dir, "f0"), exist_ok=True)
+    path = os.path.join(data_dir, "f0", "fcpe.rvcw")
+    if force or not os.path.exists(path):
+        write_blob(path, *make_fcpe(preset))
+    return path
+
+
 SYNTH_PRESETS = {
     # SynthesizerTrnMs768NSFsid v2-48k: SURVEY.md Appendix A.3
     "full": dict(inter=192, hidden=192, filter=768, heads=2, enc_layers=6, enc_k=3, window=10,
