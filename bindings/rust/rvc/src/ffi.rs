@@ -69,6 +69,11 @@ extern "C" {
     pub fn rvc_load_f0_method(e: *mut RvcEngine, method: c_int) -> c_int;
     pub fn rvc_f0_method(e: *mut RvcEngine) -> c_int;
     pub fn rvc_model_has_f0(e: *mut RvcEngine) -> c_int;
+    // ---- speakers of a multi-speaker model: the table's rows, the speaker by id, a blend of up to 8 ids, the mix in force
+    pub fn rvc_model_speakers(e: *mut RvcEngine) -> c_int;
+    pub fn rvc_set_speaker(e: *mut RvcEngine, sid: c_int) -> c_int;
+    pub fn rvc_set_speaker_mix(e: *mut RvcEngine, sid: *const i32, weight: *const f64, n: usize) -> c_int;
+    pub fn rvc_speaker_mix(e: *mut RvcEngine, sid: *mut i32, weight: *mut f64, cap: usize, n: *mut usize) -> c_int;
     // ---- CREPE (RVC_F0_CREPE / RVC_F0_CREPE_TINY: <data>/f0/crepe-full.rvcw / crepe-tiny.rvcw): its decoder, RVC_CREPE_VITERBI (default) or RVC_CREPE_ARGMAX
     pub fn rvc_set_crepe_decoder(e: *mut RvcEngine, decoder: c_int) -> c_int;
     pub fn rvc_crepe_decoder(e: *mut RvcEngine) -> c_int;

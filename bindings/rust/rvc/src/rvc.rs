@@ -98,6 +98,32 @@ impl RvcInfer {
         }
     }
 
+    /// Not in the reference: rows of the loaded model's speaker table (1 for a model without one, 0 with no model loaded)
+    pub fn speakers(&self) -> usize {
+        unsafe { ffi::rvc_model_speakers(self.handle) }.max(0) as usize
+    }
+
+    /// Not in the reference: the speaker of a multi-speaker model by id; engine-wide, may change between any two chunks
+    pub fn set_speaker(&mut self, sid: i32) -> Result<(), BackendError> {
+        self.check_load(unsafe { ffi::rvc_set_speaker(self.handle, sid) })
+    }
+
+    /// Not in the reference: a blend of 1 to 8 distinct speakers, `(id, weight)` with weights >= 0 that are normalised to sum 1
+    pub fn set_speaker_mix(&mut self, mix: &[(i32, f64)]) -> Result<(), BackendError> {
+        let ids: Vec<i32> = mix.iter().map(|m| m.0).collect();
+        let ws: Vec<f64> = mix.iter().map(|m| m.1).collect();
+        self.check_load(unsafe { ffi::rvc_set_speaker_mix(self.handle, ids.as_ptr(), ws.as_ptr(), mix.len()) })
+    }
+
+    /// Not in the reference: the mix in force, `(id, normalised weight)`; empty with no model loaded
+    pub fn speaker_mix(&self) -> Vec<(i32, f64)> {
+        let (mut ids, mut ws, mut n) = ([0i32; 8], [0f64; 8], 0usize);
+        if unsafe { ffi::rvc_speaker_mix(self.handle, ids.as_mut_ptr(), ws.as_mut_ptr(), 8, &mut n) } != 0 {
+            return Vec::new();
+        }
+        (0..n.min(8)).map(|i| (ids[i], ws[i])).collect()
+    }
+
     /// Not in the reference: FCPE's voicing threshold in [0, 1) (default 0.006): f0 = 0 where a frame's largest posterior is at or below it
     pub fn set_fcpe_threshold(&mut self, threshold: f64) -> Result<(), BackendError> {
         self.check_load(unsafe { ffi::rvc_set_fcpe_threshold(self.handle, threshold) })

@@ -114,6 +114,22 @@ double rvc_fcpe_threshold(rvc_engine *e);
  * the pitch cache is not written, the chunk counter advances.  Formant shift, the index, graph replay and every other setting apply; chunk pipelining
  * (rvc_set_pipeline) has no front pair to overlap there: an infer call with it on returns RVC_SHAPE with a message.  rvc_pitch is the tracker's and unchanged. */
 int rvc_model_has_f0(rvc_engine *e);
+/* Speakers of a multi-speaker voice model, selected and blended at run time (upstream's `sid` of every vc_single call and `n_spk` of get_vc; DESIGN.md
+ * section 24).  A synthesizer blob may carry the speaker table sy.emb_g [n_spk][gin] (python -m obs_rvc_amd.importers synth ... --speakers all|N); one without
+ * has the one speaker 0, the row baked into it.  The setting is engine-wide (every stream), is the loaded model's (rvc_load_model / rvc_unload_model put it back
+ * to the blob's baked speaker) and may change between any two chunks: a set call only records the mix, the next chunk queues one small launch on the engine's
+ * stream in front of its synthesizer that rewrites the speaker-conditioned biases in place -- no host synchronisation, no plan rebuilt, no plan key changed;
+ * unsynchronised (sync = 0), pipelined and graph-replayed chunks see it in order.  Until the first set call nothing differs from a baked blob, bit for bit.
+ *   rvc_model_speakers   rows of the table; 1 without one; 0 = no model loaded
+ *   rvc_set_speaker      the speaker by id
+ *   rvc_set_speaker_mix  g = sum_i weight[i] emb_g[sid[i]] over 1 <= n <= 8 distinct ids; weights >= 0, finite, not all zero, normalised to sum 1 in double
+ *   rvc_speaker_mix      the mix in force (normalised weights); *n = its length, RVC_SHAPE when cap is smaller (nothing written but *n)
+ * RVC_SHAPE (state unchanged): an id outside [0, n_spk), n = 0 or n > 8, a repeated id, a negative or non-finite weight, a weight sum of 0.
+ * RVC_MODEL_NOT_LOADED without a model.  On a blob without a table rvc_set_speaker(e, 0) succeeds, launches nothing and leaves the output bit for bit. */
+int rvc_model_speakers(rvc_engine *e);
+rvc_status rvc_set_speaker(rvc_engine *e, int sid);
+rvc_status rvc_set_speaker_mix(rvc_engine *e, const int32_t *sid, const double *weight, size_t n);
+rvc_status rvc_speaker_mix(rvc_engine *e, int32_t *sid, double *weight, size_t cap, size_t *n);
 
 /* ---- capabilities the reference plumbs through but never implements / bakes into its export ---- */
 /* flat-L2 retrieval index (index_path / index_rate settings, obs-rvc/src/lib.rs:78,81; rvc.rs:159 TODO).  A load that fails behind its argument checks

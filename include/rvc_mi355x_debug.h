@@ -198,6 +198,14 @@ int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist
  * Inf.  The engine's own build, if one is open, is not touched.  0 = done, else an rvc_status. */
 int rvc_debug_index_append(rvc_engine *e, const float *cv, int C, int T, int ld, size_t cursor, size_t capacity, const float *head_rows, float *store_out,
                            size_t cap_rows, size_t *rows_out, size_t *dropped_out);
+/* run-time speaker selection (obs_rvc_amd/csrc/speaker.hip.h), read only: the live speaker-conditioned biases of the loaded synthesizer in
+ * model row order -- flow 0 in-layer 0 [2 hidden], flow 0 in-layer 1, ..., the last flow's last in-layer, dec_pre [up_init]; the in-layers un-packed from their
+ * GLU row order.  composed = 0: the plain in-layers' buffers; 1: the composed twins' (RVC_SHAPE while the flows are not composed); dec_pre is the same buffer
+ * either way.  *n = the count, flow_n wn_layers 2 hidden + up_init; RVC_SHAPE when cap is smaller.  Synchronises the device.  0 = done, else an rvc_status. */
+int rvc_debug_speaker_biases(rvc_engine *e, int composed, float *out, size_t cap, size_t *n);
+/* milliseconds of the last speaker_fold_kernel launch that was queued while rvc_set_profile was on (HIP events around the launch alone); -1 before one.
+ * Synchronises the device. */
+float rvc_debug_speaker_fold_ms(rvc_engine *e);
 /* the autotuner's decisions of this process, one line each ("<layer signature> -> [choice] <kernel description> | <us> (<candidates>)"); returns the number of
  * entries.  reset forgets them (the next plan build measures again). */
 int rvc_debug_autotune_dump(char *buf, size_t cap);

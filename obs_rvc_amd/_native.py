@@ -31,6 +31,7 @@ SYMBOLS = [
     "rvc_set_pitch_semitones", "rvc_set_pitch_semitones_stream", "rvc_set_f0_range", "rvc_set_f0_range_stream",
     "rvc_set_f0_median", "rvc_set_f0_median_stream", "rvc_set_f0_snap", "rvc_set_f0_snap_stream",
     "rvc_set_protect", "rvc_set_protect_stream",
+    "rvc_model_speakers", "rvc_set_speaker", "rvc_set_speaker_mix", "rvc_speaker_mix",
     "rvc_sola_step_x", "rvc_input_gate", "rvc_session_set_crossfade", "rvc_session_set_crossfade_stream", "rvc_session_set_input_gate", "rvc_session_set_input_gate_stream",
     "rvc_denoiser_create", "rvc_denoiser_destroy", "rvc_denoiser_reset", "rvc_denoiser_set", "rvc_denoiser_latency", "rvc_denoiser_process", "rvc_denoiser_process_device",
     "rvc_session_set_noise_reduction", "rvc_session_set_noise_reduction_stream",
@@ -374,6 +375,14 @@ def lib():
         L.rvc_debug_fcpe_dw.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
+    if hasattr(L, "rvc_model_speakers") or not override:
+        L.rvc_model_speakers.argtypes = [vp]
+        L.rvc_set_speaker.argtypes = [vp, C.c_int]
+        L.rvc_set_speaker_mix.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_double), sz]
+        L.rvc_speaker_mix.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_double), sz, C.POINTER(sz)]
+        L.rvc_debug_speaker_biases.argtypes = [vp, C.c_int, fp, sz, C.POINTER(sz)]
+        L.rvc_debug_speaker_fold_ms.argtypes = [vp]
+        L.rvc_debug_speaker_fold_ms.restype = C.c_float
     if hasattr(L, "rvc_set_pitch_semitones") or not override:
         L.rvc_set_pitch_semitones.argtypes = [vp, C.c_double]
         L.rvc_set_pitch_semitones_stream.argtypes = [vp, C.c_int, C.c_double]

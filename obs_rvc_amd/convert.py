@@ -1,6 +1,6 @@
 """python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny|fcpe] [--index I --index-rate r --index-k 4|8 --nprobe p]
        [--pitch semitones] [--formant st] [--protect p] [--streams S] [--window k --context C --crossfade X] [--no-highpass] [--rate out_rate]
-       [--rms-mix-rate r] [--resampler blocks|device]
+       [--rms-mix-rate r] [--resampler blocks|device] [--sid N | --sid-mix 0:0.3,2:0.7]
 
 Upstream's "model inference" tab with this engine: a WAV file through RvcInfer.convert -- windows of one geometry run `--streams` at a
 time through the batched infer path and are SOLA-stitched on the GPU -- and the result written as 16-bit PCM.  The WAV file is read with
@@ -44,8 +44,19 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--rms-mix-rate", type=float, default=1.0, help="volume envelope, 0..1: 0 = the input's envelope, 1 = the model's own (default)")
     p.add_argument("--resampler", choices=("blocks", "device"), default="blocks",
                    help="sample-rate conversion: blocks = the streaming converter block by block (default), device = the whole-signal converter")
+    p.add_argument("--sid", type=int, default=None, help="speaker id of a multi-speaker model (default: the speaker baked into the model file)")
+    p.add_argument("--sid-mix", default=None, help="a blend of up to 8 speakers as id:weight pairs, e.g. 0:0.3,2:0.7 (weights are normalised)")
     p.add_argument("--device", type=int, default=-1)
     a = p.parse_args(argv)
+    if a.sid is not None and a.sid_mix is not None:
+        p.error("--sid and --sid-mix exclude each other")
+    if a.sid is not None and a.sid < 0:
+        p.error("--sid is a speaker id, 0 or more")
+    if a.sid_mix is not None:
+        try:
+            a.sid_mix = parse_sid_mix(a.sid_mix)
+        except ValueError as x:
+            p.error("--sid-mix: %s" % x)
     if not 0.0 <= a.rms_mix_rate <= 1.0:
         p.error("--rms-mix-rate is 0..1")
     if not -24.0 <= a.pitch <= 24.0:
@@ -69,6 +80,24 @@ def parse_args(argv=None) -> argparse.Namespace:
     if a.rate < 0 or a.rate % 100:
         p.error("--rate is a multiple of 100")
     return a
+
+
+def parse_sid_mix(text: str) -> dict:
+    """"0:0.3,2:0.7" -> {0: 0.3, 2: 0.7}: 1 to 8 distinct ids, weights finite, >= 0 and not all zero (what rvc_set_speaker_mix takes)"""
+    mix = {}
+    for part in text.split(","):
+        k, sep, v = part.partition(":")
+        if not sep:
+            raise ValueError("%r is no id:weight pair" % part)
+        sid, w = int(k), float(v)
+        if sid < 0 or sid in mix:
+            raise ValueError("id %d is negative or repeated" % sid)
+        if not (w >= 0.0 and np.isfinite(w)):
+            raise ValueError("weight %r is negative or not finite" % v)
+        mix[sid] = w
+    if not 1 <= len(mix) <= 8 or not sum(mix.values()) > 0.0:
+        raise ValueError("1 to 8 speakers with a positive weight sum")
+    return mix
 
 
 def normalise_peak(x: np.ndarray, peak=None) -> np.ndarray:
@@ -116,6 +145,10 @@ def main(argv=None) -> int:
     if eng.model_has_f0():      # (a model trained without pitch guidance runs no tracker: --f0 names none for it)
         eng.load_f0_method(a.f0)
     eng.set_streams(a.streams)
+    if a.sid is not None:
+        eng.set_speaker(a.sid)
+    elif a.sid_mix is not None:
+        eng.set_speaker_mix(a.sid_mix)
     if a.index:
         eng.load_index(a.index, nprobe=a.nprobe or None, k=a.index_k)
         eng.set_index_rate(a.index_rate)

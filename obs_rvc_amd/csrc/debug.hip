@@ -868,6 +868,32 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
 // test aid: which copies of the index exist (a fallback list built while the transposed copy is absent walks the row-major matrix)
 int rvc_debug_index_layouts(rvc_engine *e) { return e ? (e->index.rowsF ? 1 : 0) | (e->index.rowsT ? 2 : 0) | (e->index.ivf.cent ? 4 : 0) : 0; }
 
+// test aids of the run-time speaker selection (model_synth.hip, speaker.hip.h; tests/test_gpu_speaker.py): the live folded biases, read only, and the
+// duration of the last fold queued under rvc_set_profile
+int rvc_debug_speaker_biases(rvc_engine *e, int composed, float *out, size_t cap, size_t *n)
+{
+    return (int)guarded(e, [&]() {
+        if (!e->sy) return RVC_MODEL_NOT_LOADED;
+        std::vector<float> v;
+        e->sy->speaker_biases(composed != 0, v);
+        if (n) *n = v.size();
+        if (!out || cap < v.size()) return RVC_SHAPE;
+        memcpy(out, v.data(), v.size() * sizeof(float));
+        return RVC_OK;
+    });
+}
+float rvc_debug_speaker_fold_ms(rvc_engine *e)
+{
+    float ms = -1.f;
+    (void)guarded(e, [&]() {
+        if (!e->sy || !e->sy->spk_prof_valid) return RVC_OK;
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipEventElapsedTime(&ms, e->sy->spk_prof[0], e->sy->spk_prof[1]));
+        return RVC_OK;
+    });
+    return ms;
+}
+
 // test aid: one assign step and one update step of the k-means training (retrieval.hip kmeans_assign_step / kmeans_update_step; tests/test_gpu_kmeans.py)
 int rvc_debug_kmeans_step(rvc_engine *e, const float *centroids_in, size_t nlist, const int32_t *prev_assign_or_null, int32_t *assign_out, float *dist_out,
                           float *centroids_out, double *objective_out, long long *moved_out)

@@ -458,6 +458,9 @@ static void run_plan(rvc_engine *e, Plan &pl)
 {
     pl.profile = e->profile_on;
     pl.prof_used = 0;
+    // run-time speaker selection: a set call since the last chunk (or a late compose_flows under a mix) refolds the conditioned biases in place, one launch on
+    // the main stream in front of the chunk -- behind the previous chunk's synthesizer, in front of this one's, eager, pipelined or replayed from a graph
+    if (e->sy) e->sy->queue_speaker_fold(e->stream, e->profile_on);
     HIPCHK(hipEventRecord(e->ev0, e->stream));
     if (e->use_graph && !e->profile_on) {
         if (!pl.graph_exec) {
@@ -884,6 +887,33 @@ rvc_status rvc_set_fcpe_threshold(rvc_engine *e, double threshold)
     });
 }
 double rvc_fcpe_threshold(rvc_engine *e) { return e ? e->fcpe_threshold : 0.0; }
+// Run-time speaker selection (model_synth.hip, speaker.hip.h).  The setting is the model's: a load or an unload puts it back to
+// "the speaker is sy.g".  A set call only records the mix; the fold is queued by the next chunk (run_plan), so no call here touches the device.
+int rvc_model_speakers(rvc_engine *e) { return e && e->sy ? e->sy->n_spk : 0; }
+rvc_status rvc_set_speaker_mix(rvc_engine *e, const int32_t *sid, const double *weight, size_t n)
+{
+    return guarded(e, [&]() {
+        if (!e->sy) return RVC_MODEL_NOT_LOADED;
+        e->sy->set_speaker_mix(sid, weight, n);
+        return RVC_OK;
+    });
+}
+rvc_status rvc_set_speaker(rvc_engine *e, int sid)
+{
+    const int32_t id = (int32_t)sid; const double one = 1.0;
+    return rvc_set_speaker_mix(e, &id, &one, 1);
+}
+rvc_status rvc_speaker_mix(rvc_engine *e, int32_t *sid, double *weight, size_t cap, size_t *n)
+{
+    return guarded(e, [&]() {
+        if (!e->sy) return RVC_MODEL_NOT_LOADED;
+        const ModelSY &m = *e->sy;
+        if (n) *n = (size_t)m.mix_n;
+        if (cap < (size_t)m.mix_n) return RVC_SHAPE;
+        for (int i = 0; i < m.mix_n; i++) { if (sid) sid[i] = m.mix_id[i]; if (weight) weight[i] = m.mix_w[i]; }
+        return RVC_OK;
+    });
+}
 // rvc.rs:77-79
 void rvc_unload_model(rvc_engine *e)
 {

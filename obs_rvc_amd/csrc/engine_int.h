@@ -433,6 +433,19 @@ struct ModelFC {
 // GLU row packing of a WaveNet in-layer (igemm.hip.h glu_store): packed row f*16 + kq*4 + r <- model row f*8 + kq*2 + (r&1) of the tanh half (r < 2)
 // or the sigmoid half (r >= 2, + H).  w: [2H][K] in model row order, bias: [2H]
 template <typename T> void glu_pack_rows(const T *w, const float *bias, int H, size_t K, std::vector<float> &wp, std::vector<float> &bp);      // (model_synth.hip: float and double)
+// ... the map itself, both ways (H a multiple of 8): the packed row that holds model row m of [2H], and the model row packed row p holds.  glu_pack_rows
+// walks the second, speaker_fold_kernel (speaker.hip.h) stores through the first
+__host__ __device__ static inline int glu_model_row(int p, int H) { const int f = p >> 4, kq = (p & 15) >> 2, rr = p & 3; return f * 8 + kq * 2 + (rr & 1) + (rr >= 2 ? H : 0); }
+__host__ __device__ static inline int glu_packed_row(int m, int H) { const int hi = m >= H ? 1 : 0, q = m - hi * H; return (q >> 3) * 16 + ((q & 7) >> 1) * 4 + (q & 1) + 2 * hi; }
+
+// Run-time speaker selection (speaker.hip.h).  The speaker enters the synthesizer as cond(g), a per-channel constant folded into the
+// biases of the flows' in-layers and of dec_pre.  A blob with a speaker table (sy.emb_g [n_spk][gin]) keeps the table, every cond layer and the unfolded biases
+// on the device; one launch of speaker_fold_kernel rewrites the live bias buffers in place for g = sum_i w_i emb_g[id_i].
+constexpr int SPK_MAX_MIX = 8;
+struct SpeakerMix { int n; int id[SPK_MAX_MIX]; float w[SPK_MAX_MIX]; };
+// one conditioned layer: bias[r] = base_b[r] + cond_b[r] + cond_w[r][:] . g for its `rows` model rows (global rows row0 ..), stored to dst0 and -- when not
+// null -- dst1, at the GLU-packed position of r (glu_h = the layer's H) or at r itself (glu_h = 0)
+struct SpeakerLayer { const float *base_b, *cond_w, *cond_b; float *dst0, *dst1; int row0, rows, glu_h; };
 
 struct ModelSY {
     int phone_dim, hidden, inter, filter, heads, enc_layers, enc_k, window, flow_n, wn_layers, wn_k, gin, up_init, n_ups, n_rb, n_rbd, sr;
@@ -465,6 +478,24 @@ struct ModelSY {
     float src_w = 0.f, src_b = 0.f;
     std::vector<float *> owned;
     size_t weight_bytes = 0;
+    // run-time speaker selection: n_spk = rows of the blob's table (1 without one: the one speaker is sy.g, id 0, and nothing below is allocated).  The mix in
+    // force is (mix_id, mix_w)[mix_n], weights normalised in double; spk_baked = the live biases are still the host fold of sy.g made at load (no set call has
+    // been made, mix = {sid_g: 1}); spk_dirty = a set call (or a late compose_flows) has left the live biases behind the mix: the next chunk queues the fold.
+    // The buffers the fold writes (F.in[j].bias, F.inc[j].bias, dec_pre.bias) belong to this ModelSY alone.
+    int n_spk = 1, sid_g = 0;
+    float *spk_emb = nullptr;                          // [n_spk][gin]
+    std::vector<SpeakerLayer> spk_layers; SpeakerLayer *d_spk_layers = nullptr; int spk_rows = 0;
+    SpeakerMix *d_spk_mix = nullptr, *h_spk_mix = nullptr;      // h: pinned ring of 8, one block per queued fold (its async copy reads the block later)
+    unsigned spk_slot = 0; hipEvent_t spk_ev[8] = {}; bool spk_ev_used[8] = {};
+    hipEvent_t spk_prof[2] = {nullptr, nullptr}; bool spk_prof_valid = false;      // around the last fold queued under rvc_set_profile
+    int mix_n = 1; int32_t mix_id[SPK_MAX_MIX] = {}; double mix_w[SPK_MAX_MIX] = {1.0};
+    bool spk_baked = true, spk_dirty = false;
+    bool has_speaker_table() const { return spk_emb != nullptr; }
+    void speaker_setup(const Blob &b);                                             // at load, when the blob has sy.emb_g
+    void speaker_targets();                                                        // (re)point the layer table at the live bias buffers
+    void set_speaker_mix(const int32_t *sid, const double *weight, size_t n);      // ShapeError on a bad mix, state unchanged
+    void queue_speaker_fold(hipStream_t s, bool profile);                          // the one launch (+ the copy of the mix), only when spk_dirty
+    void speaker_biases(bool composed_copy, std::vector<float> &out);              // the live folded biases in model row order (rvc_debug_speaker_biases)
     explicit ModelSY(const Blob &b);
     void compose_flows();      // (model_synth.hip)
     ~ModelSY();

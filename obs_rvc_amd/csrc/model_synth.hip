@@ -1,6 +1,7 @@
 // model_synth.hip -- the synthesizer (text encoder, prior sample, flows, NSF source, HiFiGAN decoder) as a plan (reference: rvc/src/rvc.rs:182-214, ort::Session::run at rvc.rs:195)
 #include "engine_int.h"
 #include "synth.hip.h"
+#include "speaker.hip.h"
 
 namespace rvc {
 
@@ -10,8 +11,7 @@ template <typename T> void glu_pack_rows(const T *w, const float *bias, int H, s
     if (H % 8 != 0) throw std::runtime_error("GLU-gated layer: channel count must be a multiple of 8");
     wp.resize((size_t)2 * H * K); bp.resize((size_t)2 * H);
     for (int r = 0; r < 2 * H; r++) {
-        const int f = r >> 4, kq = (r & 15) >> 2, rr = r & 3;
-        const int src = f * 8 + kq * 2 + (rr & 1) + (rr >= 2 ? H : 0);
+        const int src = glu_model_row(r, H);
         for (size_t q = 0; q < K; q++) wp[(size_t)r * K + q] = (float)w[(size_t)src * K + q];
         bp[r] = bias[src];
     }
@@ -75,7 +75,8 @@ ModelSY::ModelSY(const Blob &b)
             F.pre = prep_conv(w.data(), bb.data(), 2 * H, half, 1, 1);
             F.h_pre_w.assign(w.begin(), w.begin() + (size_t)H * half); F.h_pre_b.assign(bb.begin(), bb.begin() + H);
         }
-        // speaker conditioning is a load-time constant (sid baked, rvc.rs:186-187): fold cond(g) into the in-layer biases
+        // speaker conditioning is a constant of the chunk (sid baked, rvc.rs:186-187): fold cond(g) into the in-layer biases.  This host fold of sy.g
+        // is what holds after load; a blob with a speaker table can refold the same buffers on the device (speaker.hip.h, speaker_setup below)
         const float *cw = b.w(fmt("sy.flow%d.cond.w", i)), *cb = b.w(fmt("sy.flow%d.cond.b", i));
         for (int j = 0; j < wn_layers; j++) {
             std::vector<float> bias(2 * H);
@@ -150,6 +151,119 @@ ModelSY::ModelSY(const Blob &b)
     // the f0 / feature frame rate is 100 Hz (rvc.rs:153, 160 samples @16 kHz): a synthesizer whose hop is not sr / 100 would
     // return audio of the wrong length without any error (e.g. an import that guessed the first upsample rate)
     if (sr != 100 * upp()) throw std::runtime_error(fmt("synthesizer: sr %d", sr) + fmt(" != 100 * prod(upsample rates) = %d", 100 * upp()));
+    n_spk = b.icfg_or("n_spk", 1);
+    if (b.has("sy.emb_g")) speaker_setup(b);
+    else if (n_spk != 1) throw std::runtime_error(fmt("synthesizer: n_spk = %d without a speaker table (sy.emb_g)", n_spk));
+}
+
+// ------------------------------- run-time speaker selection (speaker.hip.h) ------------------------------------------
+// A blob with a speaker table: the table, every cond layer and the unfolded biases go to the device (about 5 MB at full size), and the table of the
+// conditioned layers is built: flow 0 layer 0, flow 0 layer 1, ..., dec_pre -- the order of rvc_debug_speaker_biases.  The biases themselves stay the
+// host fold of sy.g until a set call.
+void ModelSY::speaker_setup(const Blob &b)
+{
+    const BlobTensor &tb = b.t("sy.emb_g");
+    if (tb.dims.size() != 2 || tb.dims[0] != n_spk || tb.dims[1] != gin || n_spk < 1) throw std::runtime_error("synthesizer: sy.emb_g is not [n_spk][gin]");
+    const float *g = b.w("sy.g");
+    sid_g = -1;
+    for (int i = 0; i < n_spk && sid_g < 0; i++) if (memcmp(tb.data + (size_t)i * gin, g, (size_t)gin * sizeof(float)) == 0) sid_g = i;
+    if (sid_g < 0) throw std::runtime_error("synthesizer: sy.g is no row of the speaker table sy.emb_g");
+    mix_n = 1; mix_id[0] = sid_g; mix_w[0] = 1.0;
+    auto own = [&](const std::string &n) { float *p = dv(b, n); owned.push_back(p); return p; };
+    spk_emb = own("sy.emb_g");
+    const int H = hidden;
+    int row0 = 0;
+    for (int i = 0; i < flow_n; i++) {
+        const float *cw = own(fmt("sy.flow%d.cond.w", i)), *cb = own(fmt("sy.flow%d.cond.b", i));
+        for (int j = 0; j < wn_layers; j++) {
+            SpeakerLayer L{};
+            L.base_b = own(fmt("sy.flow%d.in%d.b", i, j)); L.cond_w = cw + (size_t)j * 2 * H * gin; L.cond_b = cb + (size_t)j * 2 * H;
+            L.row0 = row0; L.rows = 2 * H; L.glu_h = H;
+            spk_layers.push_back(L); row0 += L.rows;
+        }
+    }
+    {
+        SpeakerLayer L{};
+        L.base_b = own("sy.dec.pre.b"); L.cond_w = own("sy.dec.cond.w"); L.cond_b = own("sy.dec.cond.b");
+        L.row0 = row0; L.rows = up_init; L.glu_h = 0;
+        spk_layers.push_back(L); row0 += L.rows;
+    }
+    spk_rows = row0;
+    HIPCHK(hipMalloc(&d_spk_layers, spk_layers.size() * sizeof(SpeakerLayer)));
+    HIPCHK(hipMalloc(&d_spk_mix, sizeof(SpeakerMix)));
+    HIPCHK(hipHostMalloc(&h_spk_mix, 8 * sizeof(SpeakerMix)));
+    speaker_targets();
+}
+// where the fold stores: the live bias buffers as they are now (the composed twins exist only once compose_flows has run).  Called at load and behind every
+// compose_flows; a compose that comes late has built its biases from the host fold of sy.g, so a mix that a set call has put in force is folded again
+void ModelSY::speaker_targets()
+{
+    if (!d_spk_layers) return;
+    HIPCHK(hipDeviceSynchronize());      // a queued fold may still be reading the table
+    size_t k = 0;
+    for (int i = 0; i < flow_n; i++)
+        for (int j = 0; j < wn_layers; j++, k++) { spk_layers[k].dst0 = flows[i].in[j].bias; spk_layers[k].dst1 = composed ? flows[i].inc[j].bias : nullptr; }
+    spk_layers[k].dst0 = dec_pre.bias; spk_layers[k].dst1 = nullptr;
+    HIPCHK(hipMemcpy(d_spk_layers, spk_layers.data(), spk_layers.size() * sizeof(SpeakerLayer), hipMemcpyHostToDevice));
+    if (!spk_baked) spk_dirty = true;
+}
+// the mix by ids and weights: n in [1, 8], ids in [0, n_spk) and distinct, weights finite, >= 0 and not all zero; normalised to sum 1 in double.  A model
+// without a table has the one speaker 0 (sy.g): {0: w} is accepted and changes nothing
+void ModelSY::set_speaker_mix(const int32_t *sid, const double *weight, size_t n)
+{
+    if (n < 1 || n > (size_t)SPK_MAX_MIX || !sid || !weight) throw ShapeError("speaker mix: 1 to 8 (id, weight) pairs");
+    double sum = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        if (sid[i] < 0 || sid[i] >= n_spk) throw ShapeError(fmt("speaker mix: id %d outside [0, %d)", (int)sid[i], n_spk));
+        for (size_t k = 0; k < i; k++) if (sid[k] == sid[i]) throw ShapeError(fmt("speaker mix: id %d repeated", (int)sid[i]));
+        if (!std::isfinite(weight[i]) || weight[i] < 0.0) throw ShapeError("speaker mix: a weight is negative or not finite");
+        sum += weight[i];
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum)) throw ShapeError("speaker mix: the weights sum to 0 (or overflow)");
+    if (!has_speaker_table()) return;
+    double w[SPK_MAX_MIX];
+    for (size_t i = 0; i < n; i++) w[i] = weight[i] / sum;
+    bool same = !spk_baked && (size_t)mix_n == n;
+    for (size_t i = 0; i < n && same; i++) same = mix_id[i] == sid[i] && mix_w[i] == w[i];
+    if (same) return;
+    mix_n = (int)n;
+    for (size_t i = 0; i < n; i++) { mix_id[i] = sid[i]; mix_w[i] = w[i]; }
+    spk_baked = false; spk_dirty = true;
+}
+void ModelSY::queue_speaker_fold(hipStream_t s, bool profile)
+{
+    if (!spk_dirty || !has_speaker_table()) return;
+    // every fold writes its own pinned block; a block is rewritten only after the copy that last read it has completed
+    const unsigned us = spk_slot++ & 7u;
+    if (spk_ev_used[us]) HIPCHK(hipEventSynchronize(spk_ev[us]));
+    SpeakerMix *h = h_spk_mix + us;
+    memset(h, 0, sizeof *h);
+    h->n = mix_n;
+    for (int i = 0; i < mix_n; i++) { h->id[i] = mix_id[i]; h->w[i] = (float)mix_w[i]; }
+    HIPCHK(hipMemcpyAsync(d_spk_mix, h, sizeof(SpeakerMix), hipMemcpyHostToDevice, s));
+    if (!spk_ev[us]) HIPCHK(hipEventCreateWithFlags(&spk_ev[us], hipEventDisableTiming));
+    HIPCHK(hipEventRecord(spk_ev[us], s)); spk_ev_used[us] = true;
+    if (profile) { for (auto &ev : spk_prof) if (!ev) HIPCHK(hipEventCreate(&ev)); HIPCHK(hipEventRecord(spk_prof[0], s)); }
+    const int wgs = std::min((spk_rows + SPK_WAVES - 1) / SPK_WAVES, SPK_MAX_WGS);
+    hipLaunchKernelGGL(speaker_fold_kernel, dim3(wgs), dim3(SPK_WAVES * 64), (size_t)(gin + 3) / 4 * 16, s, d_spk_mix, spk_emb, n_spk, gin, d_spk_layers, (int)spk_layers.size(), spk_rows);
+    if (profile) { HIPCHK(hipEventRecord(spk_prof[1], s)); spk_prof_valid = true; }
+    spk_dirty = false;
+}
+// the live biases of every conditioned layer in model row order (the in-layers un-packed), of the plain copies or of the composed twins (+ dec_pre either way)
+void ModelSY::speaker_biases(bool composed_copy, std::vector<float> &out)
+{
+    if (composed_copy && !composed) throw ShapeError("speaker biases: the flows are not composed");
+    HIPCHK(hipDeviceSynchronize());
+    const int H = hidden;
+    out.clear();
+    std::vector<float> pk((size_t)std::max(2 * H, up_init));
+    for (int i = 0; i < flow_n; i++)
+        for (int j = 0; j < wn_layers; j++) {
+            HIPCHK(hipMemcpy(pk.data(), composed_copy ? flows[i].inc[j].bias : flows[i].in[j].bias, (size_t)2 * H * sizeof(float), hipMemcpyDeviceToHost));
+            for (int m = 0; m < 2 * H; m++) out.push_back(pk[glu_packed_row(m, H)]);
+        }
+    HIPCHK(hipMemcpy(pk.data(), dec_pre.bias, (size_t)up_init * sizeof(float), hipMemcpyDeviceToHost));
+    out.insert(out.end(), pk.begin(), pk.begin() + up_init);
 }
 // One stream: every flow's WaveNet runs 4 x (gated k-tap in-layer, 1x1 res_skip layer) -- ten dependent launches of a 21-column window.  The
 // res_skip layers are linear, so they are composed into what follows them (exactly, in double, when the model is loaded):
@@ -275,6 +389,7 @@ void ModelSY::compose_flows()
         }
     }
     composed = true;
+    speaker_targets();
 }
 ModelSY::~ModelSY()
 {
@@ -286,6 +401,11 @@ ModelSY::~ModelSY()
     for (auto &c : ncs) free_conv(c);
     for (auto &s : rbs) for (auto &ch : s) for (auto &pr : ch) { free_conv(pr.first); free_conv(pr.second); }
     for (float *p : owned) wfree(p);
+    if (d_spk_layers) (void)hipFree(d_spk_layers);
+    if (d_spk_mix) (void)hipFree(d_spk_mix);
+    if (h_spk_mix) (void)hipHostFree(h_spk_mix);
+    for (auto &ev : spk_ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : spk_prof) if (ev) (void)hipEventDestroy(ev);
 }
 
 // ------------------------------- synthesizer ------------------------------------------

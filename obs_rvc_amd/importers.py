@@ -19,7 +19,7 @@ of missing tensors instead of guessing.  No real checkpoint exists in this image
 against transformers.HubertModel, the RMVPE and synthesizer tables are checked end to end against nn.Modules written with upstream's
 structure and parameter names (tests/test_importers.py) -- a real file may still differ in details these tests cannot see.
 
-CLI:  python -m obs_rvc_amd.importers contentvec|rmvpe|synth <input> <output.rvcw> [--version 2] [--sid 0] [--sr 48000]
+CLI:  python -m obs_rvc_amd.importers contentvec|rmvpe|synth <input> <output.rvcw> [--version 2] [--sid 0] [--sr 48000] [--speakers all|N]
                                       [--up-rates 10,10,2,2]
       python -m obs_rvc_amd.importers crepe <full.pth|tiny.pth> <output.rvcw>      (-> <data>/f0/crepe-full.rvcw or crepe-tiny.rvcw)
       python -m obs_rvc_amd.importers fcpe <in.pt> <output.rvcw>                   (-> <data>/f0/fcpe.rvcw)
@@ -451,9 +451,13 @@ def import_rmvpe_structural(inits: Named, nodes: List[dict]) -> Tuple[dict, Name
 
 # --------------------------------------------------------------------------------------------- synthesizer
 def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates: Optional[List[int]] = None,
-                 heads: Optional[int] = None, window: int = 10, config: Optional[list] = None, f0: Optional[int] = None) -> Tuple[dict, Named]:
+                 heads: Optional[int] = None, window: int = 10, config: Optional[list] = None, f0: Optional[int] = None,
+                 speakers=None) -> Tuple[dict, Named]:
     """RVC `SynthesizerTrnMs{256,768}NSFsid` or `..NSFsid_nono` state dict (the "weight" entry of a model .pth) -> (cfg, tensors) of weights.make_synth.
-    The speaker embedding row `emb_g.weight[sid]` is baked, as in the reference's 3-input export (rvc/src/rvc.rs:186-203).
+    The speaker embedding row `emb_g.weight[sid]` is baked, as in the reference's 3-input export (rvc/src/rvc.rs:186-203), as `sy.g`: the speaker in force
+    after load.  `speakers` = "all" or a count N also keeps all / the first N rows of `emb_g.weight` as the table `sy.emb_g` [n_spk][gin] (config key
+    n_spk), from which the engine selects and blends speakers at run time (rvc_set_speaker, rvc_set_speaker_mix); `sid` must then be one of the rows kept.
+    Without it the output is what it always was.
 
     Upsample rates cannot be read off the weights (official configs pair kernel 16 with rate 10 *and* with rate 8): they come from,
     in this order, `up_rates`, the checkpoint's `config` list (entries 12 / 14 / 17 = upsample_rates / upsample_kernel_sizes / sr,
@@ -488,6 +492,18 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
     s = _Src(named, ("", "weight."))
     t: Named = {}
     t["sy.g"] = s.get("emb_g.weight")[sid] if s.has("emb_g.weight") else s.get("emb_g.weight")
+    n_spk = None
+    if speakers is not None:
+        emb = np.asarray(s.get("emb_g.weight"))
+        if emb.ndim != 2:
+            raise ImportError_("synthesizer: emb_g.weight is no [speakers][gin] table")
+        if isinstance(speakers, str) and speakers != "all":
+            raise ImportError_("synthesizer: speakers is \"all\" or a count")
+        n_spk = emb.shape[0] if speakers == "all" else int(speakers)
+        if not 1 <= n_spk <= emb.shape[0]:
+            raise ImportError_("synthesizer: %d speakers asked of a table of %d rows" % (n_spk, emb.shape[0]))
+        if not 0 <= sid < n_spk:
+            raise ImportError_("synthesizer: sid %d is not among the %d rows kept" % (sid, n_spk))
     t["sy.enc.phone.w"], t["sy.enc.phone.b"] = s.get("enc_p.emb_phone.weight"), s.get("enc_p.emb_phone.bias")
     if has_f0:
         t["sy.enc.pitch_emb"] = s.get("enc_p.emb_pitch.weight")
@@ -589,6 +605,9 @@ def import_synth(named: Named, sid: int = 0, sr: Optional[int] = None, up_rates:
         cfg["rb_d%d" % m] = d
     if not has_f0:
         cfg["f0"] = 0
+    if n_spk is not None:
+        t["sy.emb_g"] = emb[:n_spk]
+        cfg["n_spk"] = n_spk
     return cfg, t
 
 
@@ -714,9 +733,11 @@ def main(argv=None):
     ap.add_argument("src"); ap.add_argument("dst")
     ap.add_argument("--version", type=int, default=2); ap.add_argument("--sid", type=int, default=0); ap.add_argument("--sr", type=int, default=None)
     ap.add_argument("--up-rates", default=None, help="synthesizer upsample rates, e.g. 10,10,2,2 (default: the checkpoint's config list, else from --sr)")
+    ap.add_argument("--speakers", default=None, help="synthesizer: all | N -- keep all / the first N rows of the speaker table for run-time selection (default: --sid baked only)")
     a = ap.parse_args(argv)
     ur = [int(v) for v in a.up_rates.split(",")] if a.up_rates else None
-    kw = dict(version=a.version) if a.kind == "contentvec" else (dict(sid=a.sid, sr=a.sr, up_rates=ur) if a.kind == "synth" else {})
+    spk = None if a.speakers is None else ("all" if a.speakers == "all" else int(a.speakers))
+    kw = dict(version=a.version) if a.kind == "contentvec" else (dict(sid=a.sid, sr=a.sr, up_rates=ur, speakers=spk) if a.kind == "synth" else {})
     convert(a.kind, a.src, a.dst, **kw)
     print("wrote", a.dst)
 

@@ -102,6 +102,27 @@ class RvcInfer:
         v = int(self._L.rvc_model_has_f0(self._h))
         return None if v < 0 else bool(v)
 
+    # -- speakers of a multi-speaker model (rvc_set_speaker*): engine-wide, may change between any two chunks ----
+    def speakers(self) -> int:
+        """rows of the loaded model's speaker table; 1 for a model without one (its baked speaker, id 0); 0: no model loaded"""
+        return int(self._L.rvc_model_speakers(self._h))
+
+    def set_speaker(self, sid: int):
+        self._chk(self._L.rvc_set_speaker(self._h, int(sid)))
+
+    def set_speaker_mix(self, mix):
+        """{sid: weight, ...} over 1 to 8 speakers: the blend sum_i w_i emb_g[sid_i], weights >= 0 and normalised to sum 1"""
+        items = list(dict(mix).items())
+        ids = (C.c_int32 * max(len(items), 1))(*[int(k) for k, _ in items])
+        ws = (C.c_double * max(len(items), 1))(*[float(v) for _, v in items])
+        self._chk(self._L.rvc_set_speaker_mix(self._h, ids, ws, len(items)))
+
+    def speaker_mix(self) -> dict:
+        """the mix in force, {sid: normalised weight}"""
+        ids, ws, n = (C.c_int32 * 8)(), (C.c_double * 8)(), C.c_size_t()
+        self._chk(self._L.rvc_speaker_mix(self._h, ids, ws, 8, C.byref(n)))
+        return {int(ids[i]): float(ws[i]) for i in range(n.value)}
+
     # -- per-chunk API (rvc.rs:81-220) ----------------------------------------------------
     def hubert(self, input):
         """-> (1, C, T) float32 (rvc.rs:81-97)."""

@@ -410,8 +410,11 @@ SYNTH_PRESETS = {
 }
 
 
-def make_synth(preset: str = "full", phone_dim: int = 768, seed: int = 777, f0: bool = True):
-    """f0=False: a model trained without pitch guidance (upstream's SynthesizerTrnMs*NSFsid_nono).  The generator draws the same sequence either way, so
+def make_synth(preset: str = "full", phone_dim: int = 768, seed: int = 777, f0: bool = True, n_spk: int = 1):
+    """n_spk > 1: a multi-speaker model.  The blob also carries the speaker table sy.emb_g [n_spk][gin] and the config key n_spk; row 0 is sy.g (the
+    speaker in force after load), the other rows come from a generator of their own (seeded from `seed`), so every other tensor -- and every blob
+    written with n_spk = 1 -- is byte for byte what it always was.
+    f0=False: a model trained without pitch guidance (upstream's SynthesizerTrnMs*NSFsid_nono).  The generator draws the same sequence either way, so
     every tensor the two kinds share is identical; the no-f0 blob leaves out sy.enc.pitch_emb, sy.src and sy.dec.nc* and carries the config key f0 = 0
     (an absent key means 1: an f0 blob is byte for byte what it always was)."""
     p = dict(SYNTH_PRESETS[preset])
@@ -491,6 +494,12 @@ def make_synth(preset: str = "full", phone_dim: int = 768, seed: int = 777, f0: 
         cfg["f0"] = 0
         for k in [k for k in g.t if is_f0_only(k)]:
             del g.t[k]
+    if n_spk < 1:
+        raise ValueError("n_spk must be at least 1")
+    if n_spk > 1:
+        rows = np.random.Generator(np.random.PCG64([int(seed), 0x73706B])).standard_normal(size=(n_spk - 1, G), dtype=np.float32)
+        g.t["sy.emb_g"] = np.concatenate([g.t["sy.g"][None, :], rows], axis=0)
+        cfg["n_spk"] = n_spk
     return cfg, g.t
 
 
@@ -512,8 +521,8 @@ def cv_blob_name(version: int, preset: str = "full") -> str:
 
 
 def build_model_zoo(root: str, preset: str = "full", version: int = 2, synth_preset: str | None = None,
-                    force: bool = False) -> Dict[str, str]:
-    """Lay out <root> as the reference's data dir: contentvec/, f0/, plus a synth model file.
+                    force: bool = False, n_spk: int = 1) -> Dict[str, str]:
+    """Lay out <root> as the reference's data dir: contentvec/, f0/, plus a synth model file (n_spk > 1: a multi-speaker one, under a name of its own).
 
     Returns {"data": data_path, "model": model_path}.  Idempotent (re-uses existing files).
     """
@@ -532,9 +541,9 @@ def build_model_zoo(root: str, preset: str = "full", version: int = 2, synth_pre
         phone_dim = 256 if preset == "full" else 16
     else:
         phone_dim = cv_cfg["embed"]
-    mp = os.path.join(root, "model-%s-v%d.rvcw" % (sp, version))
+    mp = os.path.join(root, "model-%s-v%d%s.rvcw" % (sp, version, "" if n_spk == 1 else "-spk%d" % n_spk))
     if force or not os.path.exists(mp):
-        write_blob(mp, *make_synth(sp, phone_dim))
+        write_blob(mp, *make_synth(sp, phone_dim, n_spk=n_spk))
     return {"data": data, "model": mp}
 
 
