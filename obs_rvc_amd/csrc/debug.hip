@@ -101,7 +101,7 @@ double rvc_debug_conv_bench(rvc_engine *e, int M, int Cin, int KW, int dil, int 
         std::vector<float> w((size_t)M * Cin * KW), bias(M, 0.1f);
         fill_weights(w);
         const int Bb = streams > 0 ? streams : 1;
-        Plan pl; pl.B = Bb;
+        Plan pl; pl.key.B = Bb;
         DebugWeights wts;
         ConvW &cw = wts.conv(prep_conv(w.data(), bias.data(), M, Cin, KW, 1));
         const int pad = (KW - 1) * dil / 2;
@@ -133,7 +133,7 @@ int rvc_debug_conv_probe(rvc_engine *e, int M, int Cin, int KW, int dil, int N, 
     (void)guarded(e, [&]() {
         std::vector<float> w((size_t)M * Cin * KW), bias(M, 0.1f);
         fill_weights(w);
-        Plan pl; pl.B = 1;
+        Plan pl; pl.key.B = 1;
         DebugWeights wts;
         ConvW &cw = wts.conv(prep_conv(w.data(), bias.data(), M, Cin, KW, 1));
         const int pad = (KW - 1) * dil / 2;
@@ -182,7 +182,7 @@ double rvc_debug_ln_fold_check(rvc_engine *e, int M, int K, int N, float offset)
         for (int k = 0; k < K; k++) { b2[k] = 0.1f * rnd(k, 4); g[k] = 1.0f + 0.3f * rnd(k, 5); beta[k] = 0.2f * rnd(k, 6); }
         for (size_t i = 0; i < hx.size(); i++) hx[i] = 2.0f * rnd(i, 7) + offset;        // column mean = offset, spread ~1.15
         for (size_t i = 0; i < hz.size(); i++) hz[i] = rnd(i, 8);
-        Plan pl; pl.B = 1;
+        Plan pl; pl.key.B = 1;
         DebugWeights wts;
         float *wsum = nullptr;
         ConvW &c1 = wts.conv(ModelCV::fold_ln(w1.data(), b1.data(), M, K, g.data(), beta.data(), &wsum));
@@ -253,7 +253,7 @@ double rvc_debug_conv_check(rvc_engine *e, int M, int Cin, int KW, int dil, int 
         std::vector<float> w((size_t)M * Cin * KW), bias(M);
         fill_weights(w);
         for (int m = 0; m < M; m++) bias[m] = 0.01f * (float)(m % 7) - 0.02f;
-        Plan pl; pl.B = streams;
+        Plan pl; pl.key.B = streams;
         DebugWeights wts;
         ConvW &cw = wts.conv(prep_conv(w.data(), bias.data(), M, Cin, KW, 1));
         const int pad = (KW - 1) * dil / 2, halo = (pad + 3) / 4 * 4;
@@ -315,7 +315,7 @@ double rvc_debug_conv2d_check(rvc_engine *e, int M, int Cin, int H, int W, int s
         std::vector<float> w((size_t)M * Cin * 9), bias(M);
         fill_weights(w);
         for (int m = 0; m < M; m++) bias[m] = 0.01f * (float)(m % 7) - 0.02f;
-        Plan pl; pl.B = streams;
+        Plan pl; pl.key.B = streams;
         DebugWeights wts;
         // Conv2d: w [M][Cin][3][3]; ConvTranspose2d: w [Cin][M][3][3]
         ConvW &cw = wts.conv(kind == 0 ? prep_conv(w.data(), bias.data(), M, Cin, 9, 1) : prep_convT2d(w.data(), bias.data(), Cin, M));
@@ -383,7 +383,7 @@ int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w
     return (int)guarded(e, [&]() {
         if (!s || !geo || s->streams < 1 || s->form < 0 || s->form > 4 || ((s->form == 2 || s->form == 3) && (s->n < 1 || s->n > 4))) throw ShapeError("layer spec");
         const int B = s->streams, form = s->form, n = form == 3 ? 2 : s->n;
-        Plan pl; pl.B = B;
+        Plan pl; pl.key.B = B;
         DebugWeights wts;
         DebugGeo gx, gy, gr;
         T1 x1, y1, r1; T2 x2, y2, r2;
@@ -458,7 +458,7 @@ int rvc_debug_op(rvc_engine *e, const rvc_debug_op_spec *s, const float *w0, con
         if ((s->op <= 1 && (s->E < 1 || s->heads < 1 || s->E % s->heads)) || (s->op == 1 && s->window < 0) || (s->op == 2 && s->C < 1) || (s->op == 3 && s->H < 1))
             throw ShapeError("op spec");
         const int B = s->streams, op = s->op;
-        Plan pl; pl.B = B;
+        Plan pl; pl.key.B = B;
         DebugWeights wts;
         T1 x1, y1;
         if (op <= 1) { x1 = make_t1(pl.arena, B, 3 * s->E, s->T, s->x_halo); y1 = make_t1(pl.arena, B, s->E, s->T, s->y_halo); }
@@ -503,7 +503,7 @@ int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w
     return (int)guarded(e, [&]() {
         if (!s || !geo || s->streams < 1 || s->streams > 4096 || s->op < 4 || s->op > 7) throw ShapeError("front spec");
         const int B = s->streams, op = s->op;
-        Plan pl; pl.B = B;
+        Plan pl; pl.key.B = B;
         DebugWeights wts;
         Arena &A = pl.arena;
         DebugGeo g[4];
@@ -544,8 +544,8 @@ int rvc_debug_front(rvc_engine *e, const rvc_debug_front_spec *s, const float *w
         std::vector<StreamState> hst(B);
         for (int b = 0; b < B; b++) {
             memset(&hst[b], 0, sizeof(StreamState));
-            hst[b].protect = (float)PROTECT_OFF;       // (a zero word would mean full protection, state.hip.h; none of these ops reads it)
-            hst[b].uppower = state[b].uppower; hst[b].stream_id = state[b].stream_id; hst[b].chunk = state[b].chunk; hst[b].status = state[b].status;
+            hst[b].ctl.protect = (float)PROTECT_OFF;       // (a zero word would mean full protection, state.hip.h; none of these ops reads it)
+            hst[b].ctl.uppower = state[b].uppower; hst[b].stream_id = state[b].stream_id; hst[b].chunk = state[b].chunk; hst[b].status = state[b].status;
             memcpy(hst[b].cache_pitchf, state[b].cache_pitchf, sizeof hst[b].cache_pitchf);
         }
         StreamState *d_st = A.upload(hst);
@@ -578,12 +578,12 @@ int rvc_debug_protect(rvc_engine *e, const rvc_debug_protect_spec *s, float *pho
             s->cv_ld > (1 << 21) || (long long)s->skip_head + R > 2LL * T + 1)
             throw ShapeError("protect spec");
         for (int b = 0; b < B; b++) if (!(protect[b] >= 0.0 && protect[b] <= PROTECT_OFF)) throw ShapeError("protect: value outside [0, 0.5]");
-        Plan pl; pl.B = B; pl.nprobe = e->index_nprobe;
+        Plan pl; pl.key.B = B; pl.key.nprobe = e->index_nprobe;
         Arena &A = pl.arena;
         const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_pf = (size_t)B * R;
         float *d_ph = A.floats(n_ph), *d_cv = A.floats(n_cv), *d_pf = A.floats(n_pf);
         std::vector<StreamState> hst(B);
-        for (int b = 0; b < B; b++) { memset(&hst[b], 0, sizeof(StreamState)); hst[b].protect = (float)protect[b]; }
+        for (int b = 0; b < B; b++) { memset(&hst[b], 0, sizeof(StreamState)); hst[b].ctl.protect = (float)protect[b]; }
         const StreamState *d_st = A.upload(hst);
         HIPCHK(hipMemcpy(d_ph, phone, n_ph * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_cv, cv, n_cv * 4, hipMemcpyHostToDevice));
@@ -673,7 +673,7 @@ int rvc_debug_post(rvc_engine *e, const rvc_debug_post_spec *s, float *const *bu
         const long long LIM = 1ll << 22;
         auto in = [](long long v, long long lo, long long hi) { return v >= lo && v <= hi; };
         if (op < 0 || op > 4 || !in(B, 1, 64)) throw ShapeError("post spec");
-        Plan pl; pl.B = B;
+        Plan pl; pl.key.B = B;
         Arena &A = pl.arena;
         A.set_chunk_min((size_t)1 << 20);
         // the buffers of the op: floats per buffer (0 = unused); each is the whole allocation, uploaded before the launches and downloaded after them
@@ -777,7 +777,7 @@ int rvc_debug_rm_block(rvc_engine *e, const rvc_debug_rm_block_spec *s, const fl
             s->W > 1024 || s->reps < 1 || (s->pool_out && (s->H < 2 || s->W < 2)))
             throw ShapeError("rm block spec");
         const int B = s->streams, ci = s->cin, co = s->cout, H = s->H, W = s->W;
-        Plan pl; pl.B = B; pl.rm_fuse = s->rm_fuse != 0;
+        Plan pl; pl.key.B = B; pl.rm_fuse = s->rm_fuse != 0;
         DebugWeights wts;
         Arena &A = pl.arena;
         const T2 src = s->pool_in ? make_t2(A, B, ci, 2 * H, 2 * W) : make_t2(A, B, ci, H, W);
@@ -821,15 +821,15 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
             throw ShapeError("retrieval spec");
         if (!e->index.rows) throw ShapeError("no index loaded");
         if (e->index.dim != (size_t)C) throw ShapeError("index dimension does not match the feature dimension");
-        Plan pl; pl.B = B; pl.nprobe = e->index_nprobe; pl.knn_k = e->index_k;
+        Plan pl; pl.key.B = B; pl.key.nprobe = e->index_nprobe; pl.key.knn_k = e->index_k;
         Arena &A = pl.arena;
-        const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_hit = (size_t)B * R * pl.knn_k;
+        const size_t n_ph = (size_t)B * C * s->ph_ld, n_cv = (size_t)B * C * s->cv_ld, n_hit = (size_t)B * R * pl.key.knn_k;
         T1 cvo, ph;
         cvo.p = A.floats(n_cv); cvo.B = B; cvo.C = C; cvo.T = T; cvo.ld = s->cv_ld; cvo.halo = 0; cvo.bs = (long long)C * s->cv_ld;
         ph.p = A.floats(n_ph); ph.B = B; ph.C = C; ph.T = R; ph.ld = s->ph_ld; ph.halo = 0; ph.bs = (long long)C * s->ph_ld;
         pl.cv_out = cvo;
         std::vector<StreamState> hst(B);
-        for (int b = 0; b < B; b++) { memset(&hst[b], 0, sizeof(StreamState)); hst[b].protect = (float)PROTECT_OFF; }
+        for (int b = 0; b < B; b++) { memset(&hst[b], 0, sizeof(StreamState)); hst[b].ctl.protect = (float)PROTECT_OFF; }
         StreamState *d_st = A.upload(hst);
         // the plan is built against the aid's states and rate; the engine gets its own back on every exit
         struct Swap {
@@ -839,7 +839,7 @@ int rvc_debug_retrieval(rvc_engine *e, const rvc_debug_retrieval_spec *s, float 
         } swap_guard(e, d_st, B, s->rate);
         build_retrieval(e, pl, B, T, C, (uint32_t)s->skip_head, (uint32_t)R, ph);
         if (s->path == 1) {
-            if (pl.nprobe > 0) throw ShapeError("the IVF retrieval has no exhaustive list");
+            if (pl.key.nprobe > 0) throw ShapeError("the IVF retrieval has no exhaustive list");
             if (pl.knn_fallback.empty()) throw ShapeError("this plan has no fallback list");
             pl.ops = OpList();
             for (Op &o : pl.knn_fallback) pl.ops.push_back(o);

@@ -200,18 +200,26 @@ static void configure_aux_streams(rvc_engine *e)
     e->aux[2] = want ? e->sset->cv : e->sset->plain[1];
 }
 
+void drop_plans(rvc_engine *e)
+{
+    HIPCHK(hipDeviceSynchronize());      // unsynchronised calls may still be running on the plans freed here
+    e->plans.clear(); e->last_plan = nullptr;
+}
+// the `keep` most recently used plans stay (each owns its activation arena and graph)
+static void evict_lru(rvc_engine *e, size_t keep)
+{
+    while (e->plans.size() > keep) { if (e->last_plan == e->plans.front().get()) e->last_plan = nullptr; e->plans.erase(e->plans.begin()); }
+}
+
 static void alloc_state(rvc_engine *e)
 {
+    drop_plans(e);                       // (their kernels bake the address of the state block)
     if (e->d_state) (void)hipFree(e->d_state);
     if (e->d_state_bucket) { (void)hipFree(e->d_state_bucket); e->d_state_bucket = nullptr; }
     if (e->d_bucket_idx) { (void)hipFree(e->d_bucket_idx); e->d_bucket_idx = nullptr; }
     HIPCHK(hipMalloc(&e->d_state, sizeof(StreamState) * e->n_streams));
-    e->formant.resize(e->n_streams, e->formant_default);     // existing streams keep their formant shift, new ones get the default
-    e->pitch_ctl.resize(e->n_streams, e->pitch_ctl_default); // the same for the pitch controls
-    e->protect.resize(e->n_streams, e->protect_default);     // and for consonant protection
+    e->settings.resize(e->n_streams, e->settings_default);   // existing streams keep their settings, new ones get the default
     reset_state(e);
-    e->plans.clear();
-    e->last_plan = nullptr;
 }
 
 // ------------------------------- plan -------------------------------------------------
@@ -240,32 +248,16 @@ static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, 
     build_pitch_post(e, pl, B, sal, update_cache, frame16k, hubert_length, pitchf_out, pitch_out);
 }
 
-static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32_t skip_head, uint32_t R, int slot = 0, int bucket_B = 0,
-                      uint32_t R2 = 0, bool fstage = false, const std::vector<int> *bucket_ids = nullptr)
+// the cached plan of key k (engine.hip plan_key), built on a miss
+static Plan *get_plan(rvc_engine *e, const PlanKey &k)
 {
-    // fstage: the plan carries the formant stage, the decoder runs on R2 frames (formant.hip.h); without it the key is today's (R2 = R)
-    if (!fstage) R2 = R;
-    // bucket_B > 0 (rvc_infer_batch_g): a plan for bucket_B of the engine's streams, whose states the caller gathers into d_state_bucket.
-    // The builders read the stream count and the state block from the engine: both are swapped for the duration of the build.
+    // A bucket plan serves k.B of the engine's streams, whose states the caller gathers into d_state_bucket.  The builders read the stream count and the state
+    // block from the engine: both are swapped for the duration of the build.
     struct Swap {
         rvc_engine *e; int n0; StreamState *s0; bool on;
         Swap(rvc_engine *e_, int B, StreamState *st) : e(e_), n0(e_->n_streams), s0(e_->d_state), on(B > 0) { if (on) { e->n_streams = B; e->d_state = st; } }
         ~Swap() { if (on) { e->n_streams = n0; e->d_state = s0; } }
-    } swap_guard(e, bucket_B, e->d_state_bucket);
-    const int B = e->n_streams;
-    // A model without pitch guidance (ModelSY::has_f0 false; DESIGN.md section 22): its infer plan has no pitch branch, no source and no protect launch.  The
-    // engine's f0 method and CREPE decoder are no part of such a plan's key (key_f0 / key_dec = 0); the hubert and pitch plans keep theirs
-    const bool nof0 = mode == 0 && e->sy && !e->sy->has_f0;
-    const int key_f0 = nof0 ? 0 : e->f0_method, key_dec = !nof0 && is_crepe(e->f0_method) ? e->crepe_decoder : 0;
-    const double key_thr = key_f0 == RVC_F0_FCPE ? e->fcpe_threshold : 0.0;          // FCPE's voicing threshold is baked into its decoder's launch: part of the key likewise
-    const bool with_index = mode == 0 && e->index.rows && e->index_rate > 0.f;
-    // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams (bucket_ids: the
-    // streams of a bucket plan; else every stream) has it on.  Which value a stream has is no part of the key: the kernel reads it every chunk
-    bool with_protect = false;
-    if (with_index && !nof0) {      // (upstream applies protect only where it has a pitch)
-        if (bucket_ids) { for (int s : *bucket_ids) with_protect = with_protect || e->protect[s] < PROTECT_OFF; }
-        else for (double v : e->protect) with_protect = with_protect || v < PROTECT_OFF;
-    }
+    } swap_guard(e, k.bucket ? k.B : 0, e->d_state_bucket);
     // plans built before a test hook changed are stale (the hooks are process-global and not part of the key)
     const unsigned gen = g_opt_gen.load();
     for (size_t i = 0; i < e->plans.size();)
@@ -275,9 +267,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
             e->plans.erase(e->plans.begin() + i);
         } else i++;
     for (auto &p : e->plans)
-        if (p->mode == mode && p->L == L && p->frame16k == frame16k && p->skip_head == skip_head && p->R == R && p->B == B &&
-            p->with_index == with_index && p->with_protect == with_protect && p->bf3 == (e->gemm_precision == 1) && p->with_taps == (e->taps_on != 0) && p->plain_plan == (e->taps_on == 1) && p->slot == slot && p->bucket == (bucket_B > 0) &&
-            p->R2 == R2 && p->fstage == fstage && p->f0_method == key_f0 && p->crepe_decoder == key_dec && p->fcpe_threshold == key_thr && p->nprobe == (with_index ? e->index_nprobe : 0) && p->knn_k == (with_index ? e->index_k : KNN_K)) {
+        if (p->key == k) {
             // least recently used first: a hit moves to the back, so eviction (front) never takes a plan the current call has just fetched
             Plan *hit = p.get();
             std::rotate(&p, &p + 1, e->plans.data() + e->plans.size());
@@ -287,10 +277,11 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     const auto build_t0 = std::chrono::steady_clock::now();
     std::unique_ptr<Plan> up(new Plan());
     Plan &pl = *up;
+    pl.key = k; pl.opt_gen = gen;
+    const int mode = k.mode, B = k.B; const size_t L = k.L, frame16k = k.frame16k; const uint32_t skip_head = k.skip_head, R = k.R;
+    const bool with_index = k.with_index, with_protect = k.with_protect;
+    const bool nof0 = mode == 0 && e->sy && !e->sy->has_f0;      // a model without pitch guidance: no pitch branch, no source, no protect launch (plan_key)
     pl.autotune = e->autotune != 0 && B > 4;          // (queue_igemm: trials on this device while the plan is built; plans of <= 4 streams keep the latency-tuned rules)
-    pl.mode = mode; pl.L = L; pl.frame16k = frame16k; pl.skip_head = skip_head; pl.R = R; pl.B = B; pl.with_index = with_index; pl.with_protect = with_protect; pl.with_taps = e->taps_on != 0; pl.plain_plan = e->taps_on == 1; pl.bucket = bucket_B > 0;
-    pl.slot = slot; pl.opt_gen = gen; pl.bf3 = e->gemm_precision == 1;
-    pl.R2 = R2; pl.fstage = fstage; pl.f0_method = key_f0; pl.crepe_decoder = key_dec; pl.fcpe_threshold = key_thr; pl.nprobe = with_index ? e->index_nprobe : 0; pl.knn_k = with_index ? e->index_k : KNN_K;
     pl.d_in = pl.arena.floats((size_t)B * L + 64);
     T1 src0; float *d_pitchf0 = nullptr; int *d_pitch0 = nullptr;
     size_t rm_begin = 0, rm_end = 0;
@@ -377,7 +368,7 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
         // synthesizer is queued yet.  Behind op_ret_end, so recover_retrieval replays it with the rest of the chunk (on the re-gathered, re-blended phone)
         if (with_protect) {
             T1 cvo = pl.cv_out; const StreamState *stp = e->d_state; const float *pf = d_pitchf0;
-            if (pl.with_taps && phone.bs == (long long)C * phone.ld && cvo.bs == (long long)C * cvo.ld) {       // (streams back to back, as make_t1 lays them out)
+            if (pl.key.with_taps && phone.bs == (long long)C * phone.ld && cvo.bs == (long long)C * cvo.ld) {       // (streams back to back, as make_t1 lays them out)
                 // what the stage reads, every stream of the plan (phone_ct and cv.out are stream 0's): the blended rows [B][C][R] and the ContentVec output [B][C][T]
                 T1 blend = phone; blend.B = 1; blend.C = B * C;
                 add_tap(pl, "phone_blend", blend);
@@ -387,9 +378,9 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
             pl.ops.push_back([=](hipStream_t s) { launch_protect_mix(s, B, stp, pf, cvo.p, cvo.ld, cvo.bs, C, T, (int)skip_head, (int)R, phone.p, phone.ld, phone.bs); });
             // tap of every stream of the plan, stream-major [B][C][R] (the streams of a plan tensor lie back to back)
             T1 all = phone; all.B = 1; all.C = B * C;
-            if (pl.with_taps) add_tap(pl, "phone_prot", all);
+            if (pl.key.with_taps) add_tap(pl, "phone_prot", all);
         }
-        if (pl.with_taps) {
+        if (pl.key.with_taps) {
             // the call's pitchf rows as the synthesizer gets them, every stream of the plan: [B][R]
             T1 pft; pft.p = d_pitchf0; pft.B = 1; pft.C = B; pft.T = (int)R; pft.ld = (int)R; pft.halo = 0; pft.bs = (long long)B * R;
             add_tap(pl, "pitchf", pft);
@@ -410,20 +401,12 @@ static Plan *get_plan(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32
     HIPCHK(hipDeviceSynchronize());
     e->last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - build_t0).count();
     e->last_tuned = pl.tuned_layers; e->last_changed = pl.tune_changed; e->last_hits = pl.tune_hits; e->last_tune_ms = pl.tune_ms;
-    // bounded plan cache (each geometry owns its activation arena and graph; rvc_set_plan_cache): evict the least recently used
-    while ((int)e->plans.size() >= e->plan_cap) { if (e->last_plan == e->plans.front().get()) e->last_plan = nullptr; e->plans.erase(e->plans.begin()); }
+    evict_lru(e, (size_t)e->plan_cap - 1);      // bounded plan cache (rvc_set_plan_cache)
     e->plans.push_back(std::move(up));
     return e->plans.back().get();
 }
 
 static void run_plan(rvc_engine *e, Plan &pl);
-// what the index builder (retrieval.hip) needs of the planner: rvc_hubert's plan whatever the stream count, and one run of it
-Plan *hubert_plan(rvc_engine *e, size_t L)
-{
-    struct One { rvc_engine *e; int n; explicit One(rvc_engine *e_) : e(e_), n(e_->n_streams) { e->n_streams = 1; } ~One() { e->n_streams = n; } } one(e);
-    return get_plan(e, 1, L, 0, 0, 0);
-}
-void run_hubert_plan(rvc_engine *e, Plan &pl) { run_plan(e, pl); }
 
 static void issue_ops(rvc_engine *e, Plan &pl, bool capturing)
 {
@@ -482,9 +465,6 @@ static void run_plan(rvc_engine *e, Plan &pl)
 
 
 // ------------------------------- formant shift ----------------------------------------
-static_assert(offsetof(StreamState, f_ident) + sizeof(int) - offsetof(StreamState, f_tab) == sizeof(FormantDesc), "StreamState formant fields != FormantDesc");
-static_assert(offsetof(StreamState, c_strength) + sizeof(float) - offsetof(StreamState, c_on) == sizeof(F0Cond), "StreamState pitch-control fields != F0Cond");
-static_assert(offsetof(StreamState, protect) == offsetof(StreamState, c_strength) + sizeof(float), "StreamState::protect sits behind the pitch-control words");
 static_assert(sizeof(StreamState) % 4 == 0, "state_gather_kernel copies StreamState in 32-bit words");
 
 // the device form of the filter table o -> n, built once per engine (the descriptors of a captured graph's streams point at it)
@@ -507,18 +487,18 @@ static void formant_geo(rvc_engine *e, int s, uint32_t R, uint32_t *R2, bool *re
     size_t r2 = R, ur = 0;
     const size_t upp = (size_t)e->sy->upp();
     if (R < 1) { *R2 = R; *res = false; return; }        // (rejected by the planner)
-    if (!formant_geometry(R, (size_t)e->sy->sr, e->formant[s], &r2, &ur)) throw ShapeError("formant shift: geometry out of range");
+    if (!formant_geometry(R, (size_t)e->sy->sr, e->settings[s].formant, &r2, &ur)) throw ShapeError("formant shift: geometry out of range");
     *R2 = (uint32_t)r2; *res = ur != upp;
 }
 
-// the descriptor of stream s (StreamState::f_*) for return_length R
+// the descriptor of stream s (StreamCtl::f) for return_length R
 static FormantDesc formant_desc(rvc_engine *e, int s, uint32_t R)
 {
     size_t R2 = R, ur = 0;
     const size_t upp = (size_t)e->sy->upp();
     FormantDesc d{};
     if (R < 1) return d;
-    if (!formant_geometry(R, (size_t)e->sy->sr, e->formant[s], &R2, &ur)) throw ShapeError("formant shift: geometry out of range");
+    if (!formant_geometry(R, (size_t)e->sy->sr, e->settings[s].formant, &R2, &ur)) throw ShapeError("formant shift: geometry out of range");
     if (ur == upp) {
         if (R2 < R) throw ShapeError("formant shift: decoder shorter than the chunk");
         d.ident = 1;
@@ -547,39 +527,66 @@ static bool formant_key(rvc_engine *e, uint32_t R, const std::vector<int> *ids, 
     return true;
 }
 
+// The key of the plan that serves a call: everything PlanKey holds but `slot` (the caller's), from the call's geometry and the engine's settings.  bucket_ids: the
+// streams of a bucket plan (else every stream).  An infer key of streams whose formant shifts give different decoder lengths does not exist: callers ask
+// formant_key first and bucket such streams by R2.
+static PlanKey plan_key(rvc_engine *e, int mode, size_t L, size_t frame16k, uint32_t skip_head, uint32_t R, const std::vector<int> *bucket_ids = nullptr)
+{
+    PlanKey k;
+    k.mode = mode; k.L = L; k.frame16k = frame16k; k.skip_head = skip_head; k.R = k.R2 = R;
+    k.bucket = bucket_ids != nullptr; k.B = bucket_ids ? (int)bucket_ids->size() : e->n_streams;
+    if (mode == 0 && !formant_key(e, R, bucket_ids, &k.R2, &k.fstage)) throw std::logic_error("plan key: streams with different decoder lengths");
+    if (!k.fstage) k.R2 = R;
+    // A model without pitch guidance (ModelSY::has_f0 false; DESIGN.md section 22): its infer plan has no pitch branch, no source and no protect launch.  The
+    // engine's f0 method and CREPE decoder are no part of such a plan's key; the hubert and pitch plans keep theirs
+    const bool nof0 = mode == 0 && e->sy && !e->sy->has_f0;
+    k.f0_method = nof0 ? 0 : e->f0_method;
+    k.crepe_decoder = !nof0 && is_crepe(e->f0_method) ? e->crepe_decoder : 0;
+    k.fcpe_threshold = k.f0_method == RVC_F0_FCPE ? e->fcpe_threshold : 0.0;          // FCPE's voicing threshold is baked into its decoder's launch
+    k.with_index = mode == 0 && e->index.rows && e->index_rate > 0.f;
+    // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams has it on.  Which value
+    // a stream has is no part of the key: the kernel reads it every chunk.  (Upstream applies protect only where it has a pitch)
+    if (k.with_index && !nof0)
+        for (int j = 0; j < k.B; j++) k.with_protect = k.with_protect || e->settings[bucket_ids ? (*bucket_ids)[j] : j].protect < PROTECT_OFF;
+    k.bf3 = e->gemm_precision == 1; k.with_taps = e->taps_on != 0; k.plain_plan = e->taps_on == 1;
+    k.nprobe = k.with_index ? e->index_nprobe : 0; k.knn_k = k.with_index ? e->index_k : KNN_K;
+    return k;
+}
+
+// what the index builder (retrieval.hip) needs of the planner: rvc_hubert's plan whatever the stream count, and one run of it
+Plan *hubert_plan(rvc_engine *e, size_t L)
+{
+    struct One { rvc_engine *e; int n; explicit One(rvc_engine *e_) : e(e_), n(e_->n_streams) { e->n_streams = 1; } ~One() { e->n_streams = n; } } one(e);
+    return get_plan(e, plan_key(e, 1, L, 0, 0, 0));
+}
+void run_hubert_plan(rvc_engine *e, Plan &pl) { run_plan(e, pl); }
+
 static float uppower(int32_t pitch_shift) { return ldexpf(1.0f, pitch_shift / 12); }   // rvc.rs:121, truncating division (Q1)
 
-// Per-call parameters: the seed (CallParams) and one pitch-shift multiplier PER STREAM (StreamState::uppower: every stream of a batch
-// is its own caller with its own settings, obs-rvc/src/lib.rs:701-707).  shifts == nullptr: `pitch_shift` for every stream.
-// Rs (infer calls: the return_length of every stream): the multiplier also carries the stream's formant factor (float)2^(-phi / 12), and
-// the stream's formant descriptor is written next to it; without Rs (hubert / pitch) no formant factor and the descriptors stay.
-// Every call: a stream with a semitone transpose st != 0 has (float)2^(st / 12) multiplied in last (st = 0 multiplies by nothing), and the
-// stream's other pitch controls (F0Cond) are copied when they differ from what the device holds.
+// Per-call parameters: the seed (CallParams) and the controls of every stream (StreamState::ctl: every stream of a batch is its own caller with its own
+// settings, obs-rvc/src/lib.rs:701-707).  The multiplier: uppower(pitch_shift) -- shifts == nullptr: `pitch_shift` for every stream --, with Rs (infer calls: the
+// return_length of every stream) times the stream's formant factor (float)2^(-phi / 12), and a semitone transpose st != 0 multiplies (float)2^(st / 12) in last
+// (st = 0 multiplies by nothing).  The formant descriptor is made for Rs; without Rs (hubert / pitch) the descriptors stay what the device holds.
 static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *shifts = nullptr, const uint32_t *Rs = nullptr)
 {
     const int B = e->n_streams;
-    std::vector<float> up(B);
-    std::vector<FormantDesc> fd((size_t)B, FormantDesc{});
-    std::vector<F0Cond> fc((size_t)B);
-    std::vector<float> pr((size_t)B);
-    if (!Rs && (int)e->pushed_fd.size() == B) fd = e->pushed_fd;
+    std::vector<StreamCtl> ctl((size_t)B, StreamCtl{});
+    const bool keep_f = !Rs && (int)e->pushed_ctl.size() == B;
     for (int b = 0; b < B; b++) {
-        up[b] = uppower(shifts ? shifts[b] : pitch_shift);
+        const rvc_engine::StreamSettings &set = e->settings[b];
+        StreamCtl &c = ctl[b];
+        c.uppower = uppower(shifts ? shifts[b] : pitch_shift);
         if (Rs) {
-            up[b] *= (float)std::pow(2.0, -e->formant[b] / 12.0);
-            fd[b] = formant_desc(e, b, Rs[b]);
-        }
-        const rvc_engine::PitchCtl &pc = e->pitch_ctl[b];
-        if (pc.semitones != 0.0) up[b] *= (float)std::pow(2.0, pc.semitones / 12.0);
-        fc[b] = f0cond_pack(pc.lo, pc.hi, pc.radius, pc.mask, pc.strength);
-        pr[b] = (float)e->protect[b];
+            c.uppower *= (float)std::pow(2.0, -set.formant / 12.0);
+            c.f = formant_desc(e, b, Rs[b]);
+        } else if (keep_f) c.f = e->pushed_ctl[b].f;
+        if (set.pitch.semitones != 0.0) c.uppower *= (float)std::pow(2.0, set.pitch.semitones / 12.0);
+        c.c = f0cond_pack(set.pitch.lo, set.pitch.hi, set.pitch.radius, set.pitch.mask, set.pitch.strength);
+        c.protect = (float)set.protect;
     }
     // The device already holds these values (every write to them is ordered on the main stream, and the last one wrote exactly this):
     // nothing to copy -- a small H2D copy is a 4-5 us blit kernel in front of both branches of every chunk otherwise.
-    bool same = e->pushed_valid && e->pushed_seed == e->seed && (int)e->pushed_up.size() == B && (int)e->pushed_fd.size() == B;
-    const bool fc_same = same && e->pushed_fc == fc, pr_same = same && e->pushed_pr == pr;
-    for (int b = 0; b < B && same; b++) same = e->pushed_up[b] == up[b] && e->pushed_fd[b] == fd[b];
-    if (same && fc_same && pr_same) return;
+    if (e->pushed_valid && e->pushed_seed == e->seed && e->pushed_ctl == ctl) return;
     if (e->pipeline) HIPCHK(hipDeviceSynchronize());   // the f0 branch of the next chunk may already be running: drain before the values change
     // every call writes its own pinned block: an unsynchronised call's copy may still be pending when the next call arrives
     if (!e->pushed_valid || e->pushed_seed != e->seed) {
@@ -593,16 +600,10 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
     // would otherwise overwrite a block whose copy is still pending: ADVICE r3)
     const unsigned us = e->up_slot++ & 7u;
     if (e->ev_up_used[us]) HIPCHK(hipEventSynchronize(e->ev_up[us]));
-    float *hu = e->h_up + (size_t)us * 4096;
-    FormantDesc *hf = e->h_fd + (size_t)us * 4096;
-    F0Cond *hc = e->h_fc + (size_t)us * 4096;
-    float *hp = e->h_pr + (size_t)us * 4096;
-    for (int b = 0; b < B; b++) { hu[b] = up[b]; hf[b] = fd[b]; hc[b] = fc[b]; hp[b] = pr[b]; }
-    e->pushed_up = up; e->pushed_fd = fd; e->pushed_fc = fc; e->pushed_pr = pr;
-    HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, uppower), sizeof(StreamState), hu, sizeof(float), sizeof(float), (size_t)B, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, f_tab), sizeof(StreamState), hf, sizeof(FormantDesc), sizeof(FormantDesc), (size_t)B, hipMemcpyHostToDevice, e->stream));
-    if (!fc_same) HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, c_on), sizeof(StreamState), hc, sizeof(F0Cond), sizeof(F0Cond), (size_t)B, hipMemcpyHostToDevice, e->stream));
-    if (!pr_same) HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, protect), sizeof(StreamState), hp, sizeof(float), sizeof(float), (size_t)B, hipMemcpyHostToDevice, e->stream));
+    StreamCtl *h = e->h_ctl + (size_t)us * 4096;
+    std::copy(ctl.begin(), ctl.end(), h);
+    HIPCHK(hipMemcpy2DAsync((char *)e->d_state + offsetof(StreamState, ctl), sizeof(StreamState), h, sizeof(StreamCtl), sizeof(StreamCtl), (size_t)B, hipMemcpyHostToDevice, e->stream));
+    e->pushed_ctl = std::move(ctl);
     if (!e->ev_up[us]) HIPCHK(hipEventCreateWithFlags(&e->ev_up[us], hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->ev_up[us], e->stream)); e->ev_up_used[us] = true;
     e->pushed_seed = e->seed; e->pushed_valid = true;
@@ -639,8 +640,7 @@ static rvc_status check_status(rvc_engine *e)
         if (e->h_status[c] != 0) { HIPCHK(hipMemcpy((char *)(e->d_state + c) + offsetof(StreamState, status), &zero, sizeof(int), hipMemcpyHostToDevice)); e->h_status[c] = 0; }
     if (any & ST_HANDOFF) {
         // a GRU step that gave up waiting left its hand-off granules behind: the plans are rebuilt before the next call
-        HIPCHK(hipDeviceSynchronize());
-        e->plans.clear(); e->last_plan = nullptr;
+        drop_plans(e);
         e->err = "a cross-workgroup hand-off timed out (GRU recurrence)";
         return RVC_BACKEND;
     }
@@ -669,7 +669,7 @@ static rvc_status final_status(rvc_engine *e)      // callers that cannot recomp
 static rvc_status recover_retrieval(rvc_engine *e, Plan &pl)
 {
     if (pl.knn_fallback.empty() || pl.op_ret_end <= pl.op_ret_begin) { e->err = "the one-launch retrieval's hand-off timed out (no fallback on this plan)"; return RVC_BACKEND; }
-    hipLaunchKernelGGL(rewind_chunk_kernel, dim3((pl.B + 63) / 64), dim3(64), 0, e->stream, e->d_state, pl.B);
+    hipLaunchKernelGGL(rewind_chunk_kernel, dim3((pl.key.B + 63) / 64), dim3(64), 0, e->stream, e->d_state, pl.key.B);
     const size_t n = pl.ops.v.size();
     for (size_t i = pl.op_phone; i < pl.op_ret_begin; i++) if (pl.ops.kind[i] == 0) pl.ops.v[i](e->stream);
     for (auto &op : pl.knn_fallback) op(e->stream);
@@ -697,7 +697,7 @@ static rvc_status run_buckets(rvc_engine *e, std::vector<BucketRun> &work, const
         Plan *pl = w.pl; const std::vector<int> &ids = w.ids; const int Bk = (int)ids.size();
         HIPCHK(hipMemcpyAsync(e->d_bucket_idx, ids.data(), sizeof(int) * Bk, hipMemcpyHostToDevice, e->stream));
         hipLaunchKernelGGL(state_gather_kernel, dim3(Bk), dim3(256), 0, e->stream, e->d_state, e->d_state_bucket, e->d_bucket_idx, 0);
-        for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(pl->d_in + (size_t)j * pl->L, in(ids[j]), pl->L * sizeof(float), in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+        for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(pl->d_in + (size_t)j * pl->key.L, in(ids[j]), pl->key.L * sizeof(float), in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
         pl->cur_in = nullptr; pl->cur_out = nullptr;
         run_plan(e, *pl);
         for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(out(ids[j]), pl->audio.p + (size_t)j * pl->N, pl->N * sizeof(float), out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
@@ -747,10 +747,7 @@ rvc_status rvc_create(const char *data_path, int device, rvc_engine **out)
         HIPCHK(hipEventCreateWithFlags(&e->ev_cp, hipEventDisableTiming));
         HIPCHK(hipHostMalloc((void **)&e->h_status, 4096 * sizeof(int)));
         memset(e->h_status, 0, 4096 * sizeof(int));
-        HIPCHK(hipHostMalloc((void **)&e->h_up, (size_t)8 * 4096 * sizeof(float)));
-        HIPCHK(hipHostMalloc((void **)&e->h_fd, (size_t)8 * 4096 * sizeof(FormantDesc)));
-        HIPCHK(hipHostMalloc((void **)&e->h_fc, (size_t)8 * 4096 * sizeof(F0Cond)));
-        HIPCHK(hipHostMalloc((void **)&e->h_pr, (size_t)8 * 4096 * sizeof(float)));
+        HIPCHK(hipHostMalloc((void **)&e->h_ctl, (size_t)8 * 4096 * sizeof(StreamCtl)));
         init_constants(e);
         alloc_state(e);
     } catch (const std::exception &x) {
@@ -779,10 +776,7 @@ void rvc_destroy(rvc_engine *e)
     if (e->d_cp) (void)hipFree(e->d_cp);
     if (e->h_cp) (void)hipHostFree(e->h_cp);
     if (e->h_status) (void)hipHostFree(e->h_status);
-    if (e->h_up) (void)hipHostFree(e->h_up);
-    if (e->h_fd) (void)hipHostFree(e->h_fd);
-    if (e->h_fc) (void)hipHostFree(e->h_fc);
-    if (e->h_pr) (void)hipHostFree(e->h_pr);
+    if (e->h_ctl) (void)hipHostFree(e->h_ctl);
     for (auto &kv : e->ftabs) { (void)hipFree(kv.second.tab); (void)hipFree(kv.second.kb); }
     for (int i = 0; i < 8; i++) if (e->ev_up[i]) (void)hipEventDestroy(e->ev_up[i]);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -807,8 +801,7 @@ rvc_status rvc_load_contentvec(rvc_engine *e, int model_version)
         const int dim = model_version == RVC_VERSION_V1 ? 256 : 768, layer = model_version == RVC_VERSION_V1 ? 9 : 12;   // enums.rs:10-23
         char name[64]; snprintf(name, sizeof name, "vec-%d-layer-%d.rvcw", dim, layer);
         Blob b(e->data_path + "/contentvec/" + name);
-        HIPCHK(hipDeviceSynchronize());      // unsynchronised calls may still be running on the plans freed below
-        e->plans.clear(); e->last_plan = nullptr;
+        drop_plans(e);
         e->cv.reset(new ModelCV(b));
         configure_aux_streams(e);       // (the f0 partition depends on the ContentVec depth)
         return RVC_OK;
@@ -819,8 +812,7 @@ rvc_status rvc_load_model(rvc_engine *e, const char *model_path)
 {
     return guarded(e, [&]() {
         Blob b(native_path(model_path ? model_path : ""));
-        HIPCHK(hipDeviceSynchronize());      // unsynchronised calls may still be running on the plans freed below
-        e->plans.clear(); e->last_plan = nullptr;
+        drop_plans(e);
         e->sy.reset(new ModelSY(b));
         return RVC_OK;
     });
@@ -831,8 +823,7 @@ rvc_status rvc_load_f0(rvc_engine *e, int pitch_algorithm)
     (void)pitch_algorithm;   // only Rmvpe exists (enums.rs:26-28); unknown values map to it (enums.rs:96-103)
     return guarded(e, [&]() {
         Blob b(e->data_path + "/f0/rmvpe.rvcw");
-        HIPCHK(hipDeviceSynchronize());      // unsynchronised calls may still be running on the plans freed below
-        e->plans.clear(); e->last_plan = nullptr;
+        drop_plans(e);
         e->rm.reset(new ModelRM(b));
         e->f0_method = RVC_F0_RMVPE;
         return RVC_OK;
@@ -918,15 +909,12 @@ rvc_status rvc_speaker_mix(rvc_engine *e, int32_t *sid, double *weight, size_t c
 void rvc_unload_model(rvc_engine *e)
 {
     if (!e) return;
-    (void)hipSetDevice(e->device);
-    (void)hipDeviceSynchronize();
-    e->plans.clear(); e->last_plan = nullptr;
-    e->sy.reset();
+    (void)guarded(e, [&]() { drop_plans(e); e->sy.reset(); return RVC_OK; });
 }
 
 static rvc_status run_single_input(rvc_engine *e, Plan *pl, const float *input, size_t n, int32_t pitch_shift)
 {
-    HIPCHK(hipMemcpyAsync(pl->d_in, input, n * sizeof(float) * (size_t)pl->B, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(pl->d_in, input, n * sizeof(float) * (size_t)pl->key.B, hipMemcpyHostToDevice, e->stream));
     push_call_params(e, pitch_shift);
     run_plan(e, *pl);
     return RVC_OK;
@@ -938,7 +926,7 @@ rvc_status rvc_hubert(rvc_engine *e, const float *input, size_t n, float *out, s
     return guarded(e, [&]() {
         if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;
         if (e->n_streams != 1) throw ShapeError("hubert() is a single-stream call");
-        Plan *pl = get_plan(e, 1, n, 0, 0, 0);
+        Plan *pl = get_plan(e, plan_key(e, 1, n, 0, 0, 0));
         dims[0] = 1; dims[1] = (size_t)pl->C; dims[2] = (size_t)pl->T;
         if (cap < (size_t)pl->C * pl->T) return RVC_SHAPE;
         run_single_input(e, pl, input, n, 0);
@@ -953,7 +941,7 @@ rvc_status rvc_extract_feature(rvc_engine *e, const float *input, size_t n, floa
     return guarded(e, [&]() {
         if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;
         if (e->n_streams != 1) throw ShapeError("extract_feature() is a single-stream call");
-        Plan *pl = get_plan(e, 1, n, 0, 0, 0);
+        Plan *pl = get_plan(e, plan_key(e, 1, n, 0, 0, 0));
         const size_t T2 = 2 * (size_t)pl->T + 1;
         dims[0] = 1; dims[1] = T2; dims[2] = (size_t)pl->C;
         if (cap < T2 * pl->C) return RVC_SHAPE;
@@ -969,7 +957,7 @@ rvc_status rvc_pitch(rvc_engine *e, const float *input, size_t n, int32_t pitch_
     return guarded(e, [&]() {
         if (!e->f0_method) return RVC_F0_NOT_LOADED;   // the reference hits unreachable!() here (rvc.rs:125)
         if (e->n_streams != 1) throw ShapeError("pitch() is a single-stream call");
-        Plan *pl = get_plan(e, 2, n, sample_frame_16k_size, 0, 0);
+        Plan *pl = get_plan(e, plan_key(e, 2, n, sample_frame_16k_size, 0, 0));
         *out_len = (size_t)pl->Tm;
         if (cap < (size_t)pl->Tm) return RVC_SHAPE;
         run_single_input(e, pl, input, n, pitch_shift);
@@ -992,9 +980,7 @@ static rvc_status infer_r2_buckets(rvc_engine *e, const void *input, bool input_
     ensure_bucket_state(e);
     std::vector<BucketRun> work;
     for (auto &kv : by) {
-        uint32_t r2 = 0; bool fstage = false;
-        formant_key(e, return_length, &kv.second, &r2, &fstage);
-        Plan *pl = get_plan(e, 0, n, frame16k, skip_head, return_length, 0, (int)kv.second.size(), r2, fstage, &kv.second);
+        Plan *pl = get_plan(e, plan_key(e, 0, n, frame16k, skip_head, return_length, &kv.second));
         if (out_len) *out_len = pl->N;
         if (cap < pl->N) return RVC_SHAPE;
         work.push_back({pl, kv.second});
@@ -1013,14 +999,16 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
     if (!e->cv) return RVC_CONTENTVEC_NOT_LOADED;        // rvc.rs:85-88 (via extract_feature at rvc.rs:151)
     if (!e->f0_method && e->sy->has_f0) return RVC_F0_NOT_LOADED;         // reference: unreachable!() at rvc.rs:125; a model without pitch guidance needs no tracker
     if (!e->sy->has_f0 && e->pipeline) throw ShapeError("chunk pipelining overlaps the two front branches of consecutive chunks: a model without pitch guidance has no such pair (rvc_set_pipeline(e, 0))");
-    uint32_t R2 = return_length; bool fstage = false;
-    if (!formant_key(e, return_length, nullptr, &R2, &fstage))
+    uint32_t r2 = 0; bool fstage = false;
+    if (!formant_key(e, return_length, nullptr, &r2, &fstage))      // streams with different decoder lengths have no one plan: bucketed by R2
         return infer_r2_buckets(e, input, input_on_device, n, frame16k, pitch_shift, skip_head, return_length, out, out_on_device, cap, out_len, shifts);
     const bool pipe = e->pipeline && !sync && input_on_device && out_on_device && e->partitioned && !e->use_graph && !e->profile_on && !e->taps_on;
-    Plan *pl = get_plan(e, 0, n, frame16k, skip_head, return_length, pipe ? (e->pipe_slot ^= 1) : 0, 0, R2, fstage);
+    PlanKey key = plan_key(e, 0, n, frame16k, skip_head, return_length);
+    key.slot = pipe ? (e->pipe_slot ^= 1) : 0;
+    Plan *pl = get_plan(e, key);
     if (out_len) *out_len = pl->N;
     if (cap < pl->N) return RVC_SHAPE;
-    const int B = pl->B;
+    const int B = pl->key.B;
     {
         std::vector<uint32_t> Rs((size_t)B, return_length);
         push_call_params(e, pitch_shift, shifts, Rs.data());
@@ -1031,7 +1019,7 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
     static const bool no_direct = tune_env("RVC_NO_DIRECT_IO") != nullptr;
     const bool direct_in = input_on_device && !pipe && !e->use_graph && pl->in_direct_ok && !no_direct;
     // (folded streams address the output with 32-bit offsets stream * cap: a caller-chosen cap beyond that range keeps the copy)
-    const bool direct_out = out_on_device && !e->use_graph && pl->out_direct_ok && !no_direct && (long long)pl->B * (long long)cap < (1LL << 29);
+    const bool direct_out = out_on_device && !e->use_graph && pl->out_direct_ok && !no_direct && (long long)pl->key.B * (long long)cap < (1LL << 29);
     pl->cur_in = direct_in ? (const float *)input : nullptr;
     pl->cur_out = direct_out ? (float *)out : nullptr; pl->cur_out_bs = (long long)cap;
     if (pipe) {
@@ -1054,7 +1042,7 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
     if (!pl->ev_done) HIPCHK(hipEventCreateWithFlags(&pl->ev_done, hipEventDisableTiming));
     HIPCHK(hipEventRecord(pl->ev_done, e->stream));
     pl->ev_done_valid = true;
-    e->last_knn_rows = pl->with_index ? return_length : 0;
+    e->last_knn_rows = pl->key.with_index ? return_length : 0;
     e->status_queued = true;        // the chunk's last kernel writes the status words into the host-mapped block (advance_chunk_kernel)
     if (!sync) return RVC_OK;
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -1145,9 +1133,7 @@ rvc_status rvc_infer_batch_g(rvc_engine *e, const float *const *inputs, const si
         // plans first (a geometry the engine rejects must not leave some buckets already advanced), then the work
         std::vector<BucketRun> work;
         for (auto &kv : buckets) {
-            uint32_t r2 = 0; bool fstage = false;
-            formant_key(e, kv.first.rl, &kv.second, &r2, &fstage);
-            Plan *pl = get_plan(e, 0, kv.first.n, kv.first.f, kv.first.sh, kv.first.rl, 0, (int)kv.second.size(), r2, fstage, &kv.second);
+            Plan *pl = get_plan(e, plan_key(e, 0, kv.first.n, kv.first.f, kv.first.sh, kv.first.rl, &kv.second));
             for (int s : kv.second) { if (out_lens) out_lens[s] = pl->N; if (caps[s] < pl->N) return RVC_SHAPE; }
             work.push_back({pl, kv.second});
         }
@@ -1202,8 +1188,7 @@ rvc_status rvc_set_plan_autotune(rvc_engine *e, int on)
     return guarded(e, [&]() {
         const int v = on ? 1 : 0;
         if (v != e->autotune) {
-            HIPCHK(hipDeviceSynchronize());
-            e->plans.clear(); e->last_plan = nullptr;
+            drop_plans(e);
             e->autotune = v;
         }
         return RVC_OK;
@@ -1229,7 +1214,7 @@ rvc_status rvc_set_plan_cache(rvc_engine *e, int n_plans)
         if (n_plans < 2 || n_plans > 256) throw ShapeError("plan cache size out of range (2..256)");
         HIPCHK(hipDeviceSynchronize());
         e->plan_cap = n_plans;
-        while ((int)e->plans.size() > e->plan_cap) { if (e->last_plan == e->plans.front().get()) e->last_plan = nullptr; e->plans.erase(e->plans.begin()); }
+        evict_lru(e, (size_t)e->plan_cap);
         return RVC_OK;
     });
 }
@@ -1282,58 +1267,49 @@ void rvc_get_pitch_cache(rvc_engine *e, int stream, float *out1024)
     });
 }
 
-// formant shift (the plugin's resonance shift, obs-rvc/src/lib.rs:80,103,176,369-375,446-451; formant.hip.h): semitones in [-5, 5]
-rvc_status rvc_set_formant_shift(rvc_engine *e, double semitones)
-{
-    return guarded(e, [&]() {
-        if (!(semitones >= -FORMANT_MAX && semitones <= FORMANT_MAX)) throw ShapeError("formant shift: semitones outside [-5, 5]");
-        e->formant_default = semitones;
-        for (auto &v : e->formant) v = semitones;
-        return RVC_OK;
-    });
-}
-rvc_status rvc_set_formant_shift_stream(rvc_engine *e, int stream, double semitones)
-{
-    return guarded(e, [&]() {
-        if (stream < 0 || stream >= e->n_streams) throw ShapeError("formant shift: stream out of range");
-        if (!(semitones >= -FORMANT_MAX && semitones <= FORMANT_MAX)) throw ShapeError("formant shift: semitones outside [-5, 5]");
-        e->formant[stream] = semitones;
-        return RVC_OK;
-    });
-}
-
-// pitch controls (f0cond.hip.h; DESIGN.md "Pitch controls"): per stream, read by the pitch tail every chunk, no part of a plan's identity.  The
-// engine-wide calls set every stream and the default of streams rvc_set_streams adds later; rvc_reset_state leaves the values alone.
-static rvc_status set_pitch_ctl(rvc_engine *e, const int *stream, const char *what, const std::function<const char *()> &check, const std::function<void(rvc_engine::PitchCtl &)> &set)
+// The per-stream settings (rvc_engine::StreamSettings): formant shift (the plugin's resonance shift, obs-rvc/src/lib.rs:80,103,176,369-375,446-451; formant.hip.h;
+// semitones in [-5, 5]), the pitch controls (f0cond.hip.h; DESIGN.md "Pitch controls") and consonant protection (protect.hip.h; DESIGN.md "Consonant protection";
+// [0, 0.5], 0.5 = off).  stream == nullptr: the engine-wide call, which sets every stream and the default of streams rvc_set_streams adds later; rvc_reset_state
+// leaves the values alone.  bad: what is wrong with the value (nullptr = nothing), reported behind a stream out of range.  The next call pushes what changed.
+using StreamSettings = rvc_engine::StreamSettings;
+static rvc_status set_stream_setting(rvc_engine *e, const int *stream, const char *what, const char *bad, const std::function<void(StreamSettings &)> &set)
 {
     return guarded(e, [&]() {
         if (stream && (*stream < 0 || *stream >= e->n_streams)) throw ShapeError(std::string(what) + ": stream out of range");
-        if (const char *bad = check()) throw ShapeError(std::string(what) + ": " + bad);
-        if (stream) set(e->pitch_ctl[*stream]);
-        else { set(e->pitch_ctl_default); for (auto &c : e->pitch_ctl) set(c); }
+        if (bad) throw ShapeError(std::string(what) + ": " + bad);
+        if (stream) set(e->settings[*stream]);
+        else { set(e->settings_default); for (auto &c : e->settings) set(c); }
         return RVC_OK;
     });
 }
+static rvc_status set_formant(rvc_engine *e, const int *stream, double st)
+{
+    return set_stream_setting(e, stream, "formant shift", st >= -FORMANT_MAX && st <= FORMANT_MAX ? nullptr : "semitones outside [-5, 5]", [&](StreamSettings &c) { c.formant = st; });
+}
 static rvc_status set_pitch_semitones(rvc_engine *e, const int *stream, double st)
 {
-    return set_pitch_ctl(e, stream, "pitch semitones", [&]() -> const char * { return st >= -PITCH_SEMITONES_MAX && st <= PITCH_SEMITONES_MAX ? nullptr : "semitones outside [-24, 24]"; },
-                         [&](rvc_engine::PitchCtl &c) { c.semitones = st; });
+    return set_stream_setting(e, stream, "pitch semitones", st >= -PITCH_SEMITONES_MAX && st <= PITCH_SEMITONES_MAX ? nullptr : "semitones outside [-24, 24]",
+                              [&](StreamSettings &c) { c.pitch.semitones = st; });
 }
 static rvc_status set_f0_range(rvc_engine *e, const int *stream, double lo, double hi)
 {
-    return set_pitch_ctl(e, stream, "f0 range", [&]() -> const char * { return lo >= 0.0 && hi >= lo ? nullptr : "needs 0 <= lo_hz <= hi_hz"; },
-                         [&](rvc_engine::PitchCtl &c) { c.lo = (float)lo; c.hi = (float)hi; });
+    return set_stream_setting(e, stream, "f0 range", lo >= 0.0 && hi >= lo ? nullptr : "needs 0 <= lo_hz <= hi_hz", [&](StreamSettings &c) { c.pitch.lo = (float)lo; c.pitch.hi = (float)hi; });
 }
 static rvc_status set_f0_median(rvc_engine *e, const int *stream, int radius)
 {
-    return set_pitch_ctl(e, stream, "f0 median", [&]() -> const char * { return radius >= 0 && radius <= F0_MEDIAN_MAX ? nullptr : "radius outside 0..7"; },
-                         [&](rvc_engine::PitchCtl &c) { c.radius = radius; });
+    return set_stream_setting(e, stream, "f0 median", radius >= 0 && radius <= F0_MEDIAN_MAX ? nullptr : "radius outside 0..7", [&](StreamSettings &c) { c.pitch.radius = radius; });
 }
 static rvc_status set_f0_snap(rvc_engine *e, const int *stream, uint32_t mask, double strength)
 {
-    return set_pitch_ctl(e, stream, "f0 snap", [&]() -> const char * { return mask > 0xFFFu ? "pitch-class mask has bits above bit 11" : (strength >= 0.0 && strength <= 1.0 ? nullptr : "strength outside [0, 1]"); },
-                         [&](rvc_engine::PitchCtl &c) { c.mask = mask; c.strength = (float)strength; });
+    return set_stream_setting(e, stream, "f0 snap", mask > 0xFFFu ? "pitch-class mask has bits above bit 11" : (strength >= 0.0 && strength <= 1.0 ? nullptr : "strength outside [0, 1]"),
+                              [&](StreamSettings &c) { c.pitch.mask = mask; c.pitch.strength = (float)strength; });
 }
+static rvc_status set_protect(rvc_engine *e, const int *stream, double protect)
+{
+    return set_stream_setting(e, stream, "protect", protect >= 0.0 && protect <= PROTECT_OFF ? nullptr : "value outside [0, 0.5]", [&](StreamSettings &c) { c.protect = protect; });
+}
+rvc_status rvc_set_formant_shift(rvc_engine *e, double semitones) { return set_formant(e, nullptr, semitones); }
+rvc_status rvc_set_formant_shift_stream(rvc_engine *e, int stream, double semitones) { return set_formant(e, &stream, semitones); }
 rvc_status rvc_set_pitch_semitones(rvc_engine *e, double semitones) { return set_pitch_semitones(e, nullptr, semitones); }
 rvc_status rvc_set_pitch_semitones_stream(rvc_engine *e, int stream, double semitones) { return set_pitch_semitones(e, &stream, semitones); }
 rvc_status rvc_set_f0_range(rvc_engine *e, double lo_hz, double hi_hz) { return set_f0_range(e, nullptr, lo_hz, hi_hz); }
@@ -1342,18 +1318,6 @@ rvc_status rvc_set_f0_median(rvc_engine *e, int radius) { return set_f0_median(e
 rvc_status rvc_set_f0_median_stream(rvc_engine *e, int stream, int radius) { return set_f0_median(e, &stream, radius); }
 rvc_status rvc_set_f0_snap(rvc_engine *e, uint32_t pitch_class_mask, double strength) { return set_f0_snap(e, nullptr, pitch_class_mask, strength); }
 rvc_status rvc_set_f0_snap_stream(rvc_engine *e, int stream, uint32_t pitch_class_mask, double strength) { return set_f0_snap(e, &stream, pitch_class_mask, strength); }
-
-// consonant protection (protect.hip.h; DESIGN.md "Consonant protection"): per stream, [0, 0.5], 0.5 = off; the semantics of the pitch controls
-static rvc_status set_protect(rvc_engine *e, const int *stream, double protect)
-{
-    return guarded(e, [&]() {
-        if (stream && (*stream < 0 || *stream >= e->n_streams)) throw ShapeError("protect: stream out of range");
-        if (!(protect >= 0.0 && protect <= PROTECT_OFF)) throw ShapeError("protect: value outside [0, 0.5]");
-        if (stream) e->protect[*stream] = protect;
-        else { e->protect_default = protect; for (auto &v : e->protect) v = protect; }
-        return RVC_OK;
-    });
-}
 rvc_status rvc_set_protect(rvc_engine *e, double protect) { return set_protect(e, nullptr, protect); }
 rvc_status rvc_set_protect_stream(rvc_engine *e, int stream, double protect) { return set_protect(e, &stream, protect); }
 
@@ -1518,7 +1482,7 @@ static rvc_status read_tap(rvc_engine *e, const char *name, int stream, float *o
     return guarded(e, [&]() {
         Plan *pl = e->last_plan;
         if (!pl || !name) return RVC_SHAPE;
-        if (stream < 0 || stream >= pl->B) { e->err = "tap: the last call's plan has no such stream"; return RVC_SHAPE; }
+        if (stream < 0 || stream >= pl->key.B) { e->err = "tap: the last call's plan has no such stream"; return RVC_SHAPE; }
         HIPCHK(hipDeviceSynchronize());
         for (auto &t : pl->taps) {
             if (t.name != name) continue;

@@ -233,40 +233,53 @@ struct OpList {
     void join(int s) { v.push_back(Op()); sid.push_back(s); kind.push_back(2); }
 };
 
+// Everything that decides whether a cached plan serves a call.  engine.hip plan_key derives it from the engine and the call (callers add only `slot`), get_plan
+// compares it as a whole and a new plan starts as a copy of it: a field added here is compared and assigned by construction.
+struct PlanKey {
+    int mode = 0;                 // 0 infer, 1 hubert only, 2 pitch only
+    int B = 1; size_t L = 0, frame16k = 0; uint32_t skip_head = 0, R = 0;
+    // formant shift (formant.hip.h): fstage = the plan has the formant stage (some stream stretches or resamples); the decoder then runs
+    // on R2 frames and formant_resample_kernel brings every stream back to R upp samples.  fstage = false: R2 = R
+    uint32_t R2 = 0; bool fstage = false;
+    int slot = 0;                 // chunk pipelining (rvc_set_pipeline): plans alternate between two slots
+    bool bucket = false;          // a plan of a bucketed call: built for a subset of the streams on the gathered state block (rvc_engine::d_state_bucket)
+    bool with_index = false;      // an index is loaded and the index rate is above 0: the plan has the retrieval section
+    bool with_protect = false;    // with_index and some stream of the plan has protect < 0.5: the plan carries protect_mix_kernel (protect.hip.h)
+    bool bf3 = false;             // rvc_set_gemm_precision(e, 1): ContentVec's 1x1 GEMMs on the split-bf16 kernel (exploratory)
+    bool with_taps = false;       // rvc_enable_taps: level 2 taps the production plan ...
+    bool plain_plan = false;      // ... level 1 the explicit plan (LayerNorm launches, WaveNets layer by layer)
+    int f0_method = 0;            // the engine's f0 method (the plan's f0 branch is that method's; 0 on the infer plan of a model without pitch guidance)
+    int crepe_decoder = 0;        // ... and, for the CREPE methods, the engine's decoder (0 = Viterbi, 1 = arg-max; 0 on every other plan)
+    double fcpe_threshold = 0;    // ... and, for FCPE, the engine's voicing threshold (baked into the decoder's launch; 0 on every other plan)
+    int nprobe = 0;               // the engine's index_nprobe (with_index plans; 0 = flat search)
+    int knn_k = KNN_K;            // the engine's index_k: the K of the retrieval kernels and the width of d_knn_idx / d_knn_dist
+    bool operator==(const PlanKey &o) const
+    {
+        return std::tie(mode, B, L, frame16k, skip_head, R, R2, fstage, slot, bucket, with_index, with_protect, bf3, with_taps, plain_plan, f0_method, crepe_decoder, fcpe_threshold, nprobe, knn_k) ==
+               std::tie(o.mode, o.B, o.L, o.frame16k, o.skip_head, o.R, o.R2, o.fstage, o.slot, o.bucket, o.with_index, o.with_protect, o.bf3, o.with_taps, o.plain_plan, o.f0_method,
+                        o.crepe_decoder, o.fcpe_threshold, o.nprobe, o.knn_k);
+    }
+};
+
 struct Plan {
     Arena arena;
     OpList ops;
     std::vector<TapRec> taps;
-    // geometry
-    int B = 1; size_t L = 0, frame16k = 0; uint32_t skip_head = 0, R = 0;
-    int T = 0, Tm = 0, C = 0; size_t N = 0;
-    bool with_index = false, with_taps = false;
-    bool with_protect = false;    // with_index and some stream of the plan had protect < 0.5 when it was built: the plan carries protect_mix_kernel (protect.hip.h)
-    bool bucket = false;          // a plan of rvc_infer_batch_g: built for a subset of the streams on the gathered state block (rvc_engine::d_state_bucket)
+    PlanKey key;
+    int T = 0, Tm = 0, C = 0; size_t N = 0;      // derived geometry
     // gather tables by content (round 6): the 3x3 layers of one RMVPE level have identical k -> offset tables; with one device copy per distinct table the second
     // and later layers of a level find it in the L2 instead of fetching a cold 6 KB table from HBM in front of their first operand gather
     std::map<std::vector<int>, const int *> koff_tabs;
     bool rm_fuse = false;         // RMVPE's shallow ConvBlockRes as one launch each (model_rmvpe.hip; decided per plan from the engine's f0 partition)
-    bool bf3 = false;             // built under rvc_set_gemm_precision(e, 1): ContentVec's 1x1 GEMMs on the split-bf16 kernel (exploratory)
     bool autotune = false;        // rvc_set_plan_autotune: layers with several eligible kernels / tiles are chosen by timing them at plan build (plan.hip queue_igemm)
     double tune_ms = 0; int tuned_layers = 0, tune_changed = 0, tune_hits = 0;      // time spent in trials, layers tuned here / changed against the rules / taken from the process cache
-    bool plain_plan = false;      // taps level 1: the explicit plan (LayerNorm launches, WaveNets layer by layer); level 2 taps the production plan
-    int mode = 0;   // 0 infer, 1 hubert only, 2 pitch only
-    int f0_method = 0;            // the engine's f0 method when the plan was built (its f0 branch is that method's)
-    int crepe_decoder = 0;        // ... and, for the CREPE methods, the engine's decoder (0 = Viterbi, 1 = arg-max; 0 on every other plan)
-    double fcpe_threshold = 0;    // ... and, for FCPE, the engine's voicing threshold (baked into the decoder's launch; 0 on every other plan)
-    // formant shift (formant.hip.h): fstage = the plan has the formant stage (some stream stretches or resamples); the decoder then runs
-    // on R2 frames and formant_resample_kernel brings every stream back to R upp samples.  fstage = false: today's plan, R2 = R
-    uint32_t R2 = 0; bool fstage = false;
-    int dec_frames() const { return fstage ? (int)R2 : (int)R; }
+    int dec_frames() const { return key.fstage ? (int)key.R2 : (int)key.R; }
     // I/O tensors
     float *d_in = nullptr;  // [B][L]
     T1 cv_out, audio;
     float *d_f0 = nullptr;  // [B][Tm]
     float *d_feat = nullptr; // extract_feature output (1,2T+1,C)
     int *d_knn_idx = nullptr; float *d_knn_dist = nullptr;
-    int nprobe = 0;                                    // the engine's index_nprobe when the plan was built (with_index plans; 0 = flat search)
-    int knn_k = KNN_K;                                 // the engine's index_k when the plan was built: the K of its retrieval kernels and the width of d_knn_idx / d_knn_dist
     int *d_ivf_scanned = nullptr; int ivf_queries = 0;  // IVF retrieval: rows scanned per (stream, query) of the last run, and how many such words
     int *d_knn_overflow = nullptr;                     // many-stream retrieval: one word per stream, raised when its candidate set overflowed (nullptr on the one-launch form)
     // one-launch retrieval: its ticket counters, and what runs instead when a selector gave up (engine.hip recover_retrieval)
@@ -284,8 +297,8 @@ struct Plan {
     std::vector<float *> owned_dev;   // plan-time repacked weights
     // timeline probe (RVC_STAMPS=1): one device timestamp per section boundary
     unsigned long long *d_stamps = nullptr; std::vector<std::string> stamp_names;
-    // chunk pipelining (rvc_set_pipeline): plans alternate between two slots; ev_done marks the end of this plan's previous chunk
-    int slot = 0; hipEvent_t ev_done = nullptr; bool ev_done_valid = false;
+    // chunk pipelining (rvc_set_pipeline, PlanKey::slot): ev_done marks the end of this plan's previous chunk
+    hipEvent_t ev_done = nullptr; bool ev_done_valid = false;
     // per-call pointers (eager launches): the kernels that read the input / write the audio take them at launch time, so a device-resident
     // caller needs no staging copy in front of the chunk and no copy behind it (a captured graph bakes pointers: it keeps d_in / audio)
     const float *cur_in = nullptr; float *cur_out = nullptr; long long cur_out_bs = 0;
@@ -530,20 +543,20 @@ struct rvc_engine {
     hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
     std::unique_ptr<ModelCV> cv;
     std::unique_ptr<ModelRM> rm;
-    int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights), RVC_F0_CREPE / _TINY (cr_full / cr_tiny); engine-wide and part of a plan's identity
+    int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights), RVC_F0_CREPE / _TINY (cr_full / cr_tiny); engine-wide (PlanKey)
     std::unique_ptr<ModelCR> cr_full, cr_tiny;        // each stays loaded once read: going back to it costs no file and keeps its plans
     std::unique_ptr<ModelFC> fc;                      // FCPE (RVC_F0_FCPE), kept once read like the CREPE presets
-    double fcpe_threshold = 0.006;                    // rvc_set_fcpe_threshold: f0 = 0 where the top posterior is at or below it; engine-wide and part of an FCPE plan's identity
-    int crepe_decoder = 0;                            // rvc_set_crepe_decoder: 0 = Viterbi, 1 = arg-max; engine-wide and part of a CREPE plan's identity
+    double fcpe_threshold = 0.006;                    // rvc_set_fcpe_threshold: f0 = 0 where the top posterior is at or below it; engine-wide (PlanKey)
+    int crepe_decoder = 0;                            // rvc_set_crepe_decoder: 0 = Viterbi, 1 = arg-max; engine-wide (PlanKey)
     std::unique_ptr<ModelSY> sy;
     // constants for the mel front end
     float *d_window = nullptr, *d_twiddle = nullptr, *d_basis = nullptr; int *d_band = nullptr;
     // retrieval index: what is loaded (index) and the caller's preferences, which are no part of it.  index_nprobe: 0 = flat search, else the lists probed per
-    // query; engine-wide and part of a plan's identity; a new index or a dropped IVF structure resets it
+    // query; engine-wide (PlanKey); a new index or a dropped IVF structure resets it
     rvc::RetrievalIndex index;
     float index_rate = 0.f;
     int index_nprobe = 0;
-    int index_k = KNN_K;                                        // neighbours blended per query (rvc_set_index_k: 4 or 8); the caller's preference, kept across index loads; part of a plan's identity
+    int index_k = KNN_K;                                        // neighbours blended per query (rvc_set_index_k: 4 or 8); the caller's preference, kept across index loads (PlanKey)
     // the last k-means training of an IVF structure (rvc_train_index_ivf; kmeans.hip.h): what rvc_index_ivf_train_info reports
     bool km_valid = false; int km_iters_run = 0; size_t km_moved_last = 0; std::vector<double> km_obj; double km_ms[3] = {0, 0, 0};
     rvc::IndexBuild *ib = nullptr;                              // an open index build (rvc_index_build_begin .. _finish / _abort; retrieval.hip); never touches `index` before finish
@@ -555,7 +568,7 @@ struct rvc_engine {
     CallParams *d_cp = nullptr, *h_cp = nullptr;   // h_cp: ring of 64 pinned blocks, one per call (an async copy reads its block later)
     unsigned cp_slot = 0; hipEvent_t ev_cp = nullptr;
     uint32_t seed = 0, stream_id0 = 0;
-    // plans (keyed by geometry)
+    // plans (keyed by PlanKey, least recently used first)
     std::vector<std::unique_ptr<Plan>> plans;
     Plan *last_plan = nullptr;
     int gemm_precision = 0;           // 0 = fp32 everywhere (the product), 1 = split-bf16 for ContentVec's 1x1 GEMMs at many streams (exploratory)
@@ -570,29 +583,23 @@ struct rvc_engine {
     // offline throughput mode: consecutive unsynchronised infer_device calls overlap chunk i+1's two front branches with chunk i's
     // synthesizer (two plan slots; the branch streams are ordered by events instead of forking from the main stream)
     bool pipeline = false, pipe_now = false; int pipe_slot = 0; hipEvent_t ev_in = nullptr; const void *pipe_input = nullptr; size_t pipe_input_bytes = 0;
-    std::vector<float> pushed_up; uint32_t pushed_seed = 0; bool pushed_valid = false;      // what the device holds: per-stream multipliers, seed
-    float *h_up = nullptr; unsigned up_slot = 0;        // pinned ring of 8 blocks of 4096 per-stream multipliers (async strided copies read them later)
-    hipEvent_t ev_up[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ev_up_used[8] = {false, false, false, false, false, false, false, false};      // completion of the copy that last read a block
+    // per-stream controls (StreamCtl, state.hip.h): what the device holds (with the seed), and a pinned ring of 8 blocks of 4096, one block per strided copy that
+    // changes them (the async copy reads its block later; ev_up: completion of the copy that last read a block).  engine.hip push_call_params
+    std::vector<rvc::StreamCtl> pushed_ctl; uint32_t pushed_seed = 0; bool pushed_valid = false;
+    rvc::StreamCtl *h_ctl = nullptr; unsigned up_slot = 0;
+    hipEvent_t ev_up[8] = {}; bool ev_up_used[8] = {};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.f;
     size_t last_knn_rows = 0;
-    // formant shift (formant.hip.h): semitones per stream (rvc_set_formant_shift[_stream]) and the default of new streams; filter tables by
-    // ratio (o, n), device memory for the engine's life (a captured graph's descriptors point at them); the descriptors the device holds
-    std::vector<double> formant; double formant_default = 0.0;
-    std::map<std::pair<int, int>, rvc::FormantTable> ftabs;
-    std::vector<rvc::FormantDesc> pushed_fd;
-    rvc::FormantDesc *h_fd = nullptr;     // pinned ring of 8 blocks of 4096 descriptors, written and read with h_up's blocks
-    // pitch controls (f0cond.hip.h; rvc_set_pitch_semitones / f0_range / f0_median / f0_snap [_stream]): per stream and the default of new streams.  No part
-    // of a plan's identity: the transpose is a factor of the pushed multiplier, the rest travels as F0Cond words next to the formant descriptor
+    // The settings behind the controls, per stream and the default of streams rvc_set_streams adds later (rvc_reset_state leaves them alone): formant shift in
+    // semitones (rvc_set_formant_shift[_stream]), the pitch controls (f0cond.hip.h; rvc_set_pitch_semitones / f0_range / f0_median / f0_snap [_stream]) and consonant
+    // protection ([0, 0.5], 0.5 = off; rvc_set_protect[_stream]).  What of them is a plan's identity is PlanKey's R2 / fstage and with_protect; the values travel in
+    // StreamCtl (the transpose as a factor of the multiplier) and are not.
     struct PitchCtl { double semitones = 0.0; float lo = 0.f, hi = INFINITY; int radius = 0; uint32_t mask = 0; float strength = 0.f; };
-    std::vector<PitchCtl> pitch_ctl; PitchCtl pitch_ctl_default;
-    std::vector<rvc::F0Cond> pushed_fc;
-    rvc::F0Cond *h_fc = nullptr;          // pinned ring of 8 blocks of 4096, as h_fd
-    // consonant protection (protect.hip.h; rvc_set_protect[_stream]): per stream and the default of new streams, [0, 0.5], 0.5 = off.  Whether ANY stream
-    // of a plan is below 0.5 is part of the plan's identity (with_protect); the values travel as StreamState::protect and are not
-    std::vector<double> protect; double protect_default = rvc::PROTECT_OFF;
-    std::vector<float> pushed_pr;
-    float *h_pr = nullptr;                // pinned ring of 8 blocks of 4096, as h_fd
+    struct StreamSettings { double formant = 0.0; PitchCtl pitch; double protect = rvc::PROTECT_OFF; };
+    std::vector<StreamSettings> settings; StreamSettings settings_default;
+    // formant filter tables by ratio (o, n): device memory for the engine's life (a captured graph's descriptors point at them)
+    std::map<std::pair<int, int>, rvc::FormantTable> ftabs;
     // the file converter (convert.hip.h): the high-pass taps on the device (uploaded by the first call that filters) and what
     // rvc_convert_info reports of the last completed convert
     rvc::DevBuf<float> hp_taps;
@@ -703,8 +710,9 @@ struct IndexBuild {
 void index_build_reserve(rvc_engine *e, IndexBuild &b, size_t upper, size_t need);
 void index_build_append(rvc_engine *e, IndexBuild &b, const float *cv, int C, int T, int ld);
 void index_build_abort(rvc_engine *e);
-// engine.hip: the one-stream ContentVec-only plan of length L -- rvc_hubert's plan, get_plan(e, 1, L, 0, 0, 0) -- whatever rvc_set_streams says, and one run of
-// it on the engine's stream over the samples already in pl.d_in
+// engine.hip: the one-stream ContentVec-only plan of length L -- rvc_hubert's plan -- whatever rvc_set_streams says, and one run of it on the engine's stream
+// over the samples already in pl.d_in; drop_plans: synchronise the device, then forget every cached plan (whoever changes what plans were built on calls it)
+void drop_plans(rvc_engine *e);
 Plan *hubert_plan(rvc_engine *e, size_t L);
 void run_hubert_plan(rvc_engine *e, Plan &pl);
 }  // namespace rvc

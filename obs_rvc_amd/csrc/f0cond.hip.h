@@ -3,24 +3,20 @@
 //   median   scipy.signal.medfilt(f, 2 r + 1), r <= 7: rows outside the window count as 0, unvoiced zeros take part as values
 //   snap     n = 69 + 12 log2(f / 440); target = the nearest MIDI note whose pitch class is in the mask (a tie goes to the lower note);
 //            f' = f 2^(s (target - n) / 12)
-// The semitone transpose is no stage of its own: the host folds (float)2^(st / 12) into StreamState::uppower (engine.hip push_call_params).
-// The stream's settings are four words of StreamState (F0Cond); c_on == 0 = every control neutral, and the tail skips the stage on that one word.
+// The semitone transpose is no stage of its own: the host folds (float)2^(st / 12) into StreamCtl::uppower (engine.hip push_call_params).
+// The stream's settings are four words of StreamState (StreamCtl::c); on == 0 = every control neutral, and the tail skips the stage on that one word.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <stdint.h>
+#include "state.hip.h"
 
 namespace rvc {
 
 constexpr double PITCH_SEMITONES_MAX = 24.0;
 constexpr int F0_MEDIAN_MAX = 7;
 
-// the conditioning fields of StreamState (c_on .. c_strength) as the host writes them
-//   c_on: bits 0-3 the median radius, bits 4-15 the pitch-class mask (bit 4 + k = class k, C = 0; 0 when strength = 0), bit 16 the range gate
-struct F0Cond {
-    uint32_t on; float lo, hi, strength;
-    bool operator==(const F0Cond &x) const { return on == x.on && lo == x.lo && hi == x.hi && strength == x.strength; }
-};
+// (F0Cond, the conditioning words as the host writes them: state.hip.h)
 constexpr uint32_t F0C_GATE = 1u << 16;
 static inline F0Cond f0cond_pack(float lo, float hi, int radius, uint32_t mask, float strength)
 {

@@ -28,11 +28,7 @@ static inline bool formant_geometry(size_t R, size_t sr, double semitones, size_
     return *upp_res >= 1;
 }
 
-// the formant fields of StreamState (f_tab .. f_ident) as the host writes them
-struct FormantDesc {
-    const float *tab; const int *kb; int o, n, w, kt, nx, ident;
-    bool operator==(const FormantDesc &x) const { return tab == x.tab && kb == x.kb && o == x.o && n == x.n && w == x.w && kt == x.kt && nx == x.nx && ident == x.ident; }
-};
+// (FormantDesc, a stream's descriptor of the stage: state.hip.h)
 // Device form of a table: row j keeps only its span of nonzero fp32 taps, [kb[j], kb[j] + Kt).  The taps left out are exact zeros, so
 // the sum is the same sum over the full row.
 struct FormantTable { float *tab = nullptr; int *kb = nullptr; int o = 0, n = 0, w = 0, Kt = 0; };

@@ -141,7 +141,7 @@ float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k)
     {
         const size_t bpn = crepe_backpointer_bytes(B, Tm);
         unsigned char *bp = bpn ? (unsigned char *)A.alloc(bpn) : nullptr;
-        const int decoder = pl.crepe_decoder; const float *tab = m.f0tab;
+        const int decoder = pl.key.crepe_decoder; const float *tab = m.f0tab;
         pl.ops.push_back([=](hipStream_t s) { launch_crepe_decode(s, B, prob, Tm, decoder, tab, bp, f0, nullptr, nullptr); });
     }
     { T1 t; t.p = f0; t.B = B; t.C = 1; t.T = Tm; t.ld = Tm; t.bs = Tm; add_tap(pl, "cr.f0", t); }

@@ -156,7 +156,7 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
         x = y; T = To;
     }
     add_tap(pl, "cv.feat", x);
-    const bool fuse_ln = B <= LN_FOLD_MAX_STREAMS && m.has_folded && !pl.plain_plan && !test_opt("RVC_NO_LN_FUSE");
+    const bool fuse_ln = B <= LN_FOLD_MAX_STREAMS && m.has_folded && !pl.key.plain_plan && !test_opt("RVC_NO_LN_FUSE");
     const int E = m.embed;
     T1 h = make_t1(A, B, E, T, m.pos_k / 2);
     if (fuse_ln && m.proj_wsum) { ConvOpts o; o.ln_wsum = m.proj_wsum; o.ln_rows = m.conv_dim; add_conv1d(pl, m.proj_f, x, h, 1, 0, 1, o); }
@@ -180,7 +180,7 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
             if (raw) { ConvOpts o; o.ln_wsum = Ly.qkv_wsum; o.ln_stats_out = st_a; o.ln_rows = E; add_conv1d(pl, Ly.qkv_f, h2, qkv, 1, 0, 1, o); raw_st = st_a; }
             else add_conv1d(pl, Ly.qkv, h2, qkv, 1, 0, 1);
         } else
-        { ConvOpts o; o.bf3 = pl.bf3; add_conv1d(pl, Ly.qkv, h2, qkv, 1, 0, 1, o); }
+        { ConvOpts o; o.bf3 = pl.key.bf3; add_conv1d(pl, Ly.qkv, h2, qkv, 1, 0, 1, o); }
         add_attention(pl, qkv, att, m.heads);
         if (fuse_ln) {
             float *st_1 = A.floats((size_t)2 * T + 16);
@@ -194,13 +194,13 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L)
             if (l + 1 < m.run_layers) { raw = true; raw_g = Ly.ln2_g; raw_b = Ly.ln2_b; }
             else { add_layernorm(pl, h2, Ly.ln2_g, Ly.ln2_b); raw = false; }
         } else {
-        { ConvOpts o; o.bf3 = pl.bf3; o.res = h2.p; o.res_cs = h2.ld; o.res_bs = h2.bs; add_conv1d(pl, Ly.o, att, h2, 1, 0, 1, o); }
+        { ConvOpts o; o.bf3 = pl.key.bf3; o.res = h2.p; o.res_cs = h2.ld; o.res_bs = h2.bs; add_conv1d(pl, Ly.o, att, h2, 1, 0, 1, o); }
         add_layernorm(pl, h2, Ly.ln1_g, Ly.ln1_b);
-        { ConvOpts o; o.bf3 = pl.bf3; o.act = ACT_GELU; add_conv1d(pl, Ly.ff1, h2, ff, 1, 0, 1, o); }
-        { ConvOpts o; o.bf3 = pl.bf3; o.res = h2.p; o.res_cs = h2.ld; o.res_bs = h2.bs; add_conv1d(pl, Ly.ff2, ff, h2, 1, 0, 1, o); }
+        { ConvOpts o; o.bf3 = pl.key.bf3; o.act = ACT_GELU; add_conv1d(pl, Ly.ff1, h2, ff, 1, 0, 1, o); }
+        { ConvOpts o; o.bf3 = pl.key.bf3; o.res = h2.p; o.res_cs = h2.ld; o.res_bs = h2.bs; add_conv1d(pl, Ly.ff2, ff, h2, 1, 0, 1, o); }
         add_layernorm(pl, h2, Ly.ln2_g, Ly.ln2_b);
         }
-        if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, raw ? "cv.l%d.raw" : "cv.l%d", l); add_tap(pl, nm, h2); } else if (l % 4 == 3) add_stamp(pl, "cv.l4");
+        if (pl.key.with_taps) { char nm[32]; snprintf(nm, sizeof nm, raw ? "cv.l%d.raw" : "cv.l%d", l); add_tap(pl, nm, h2); } else if (l % 4 == 3) add_stamp(pl, "cv.l4");
     }
     T1 out = h2;
     if (m.out_dim != E) { out = make_t1(A, B, m.out_dim, T, 0); add_conv1d(pl, m.final_proj, h2, out, 1, 0, 1); }

@@ -153,7 +153,7 @@ float *build_fcpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k)
     add_conv1d(pl, m.out, n, logit, 1, 0, 1);
     float *prob = A.floats((size_t)B * Tm * FCPE_BINS), *f0 = A.floats((size_t)B * Tm);
     {
-        const float *tab = m.f0tab; const double thr = pl.fcpe_threshold;
+        const float *tab = m.f0tab; const double thr = pl.key.fcpe_threshold;
         pl.ops.push_back([=](hipStream_t s) { launch_fcpe_decode(s, B, Tm, logit.p, logit.ld, logit.bs, nullptr, prob, tab, thr, f0, nullptr); });
     }
     { T1 t; t.p = prob; t.B = B; t.C = Tm; t.T = FCPE_BINS; t.ld = FCPE_BINS; t.bs = (long long)Tm * FCPE_BINS; add_tap(pl, "fc.prob", t); }

@@ -304,7 +304,7 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
     float *d_mel = A.floats((size_t)B * 128 * Tm);
     add_mel_frontend(e, pl, B, pl.d_in, (long long)L, (int)L, (int)fr, Tm, d_mel, img, m.bn_scale, m.bn_shift);
     add_stamp(pl, "rm.mel0");
-    if (pl.with_taps) { T1 t; t.p = d_mel; t.B = B; t.C = 128; t.T = Tm; t.ld = Tm; t.halo = 0; t.bs = 128LL * Tm; add_tap(pl, "rm.mel", t); }
+    if (pl.key.with_taps) { T1 t; t.p = d_mel; t.B = B; t.C = 128; t.T = Tm; t.ld = Tm; t.halo = 0; t.bs = 128LL * Tm; add_tap(pl, "rm.mel", t); }
     // encoder; every level's pre-pool output is written straight into the second half of the decoder's concat buffer
     std::vector<T2> cat(m.levels);
     {
@@ -329,7 +329,7 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
             x = add_res_block(pl, m.enc[lv][j], xin, out, j + 1 < m.n_blocks ? &m.enc[lv][j + 1] : (lv + 1 < m.levels ? &m.enc[lv + 1][0] : nullptr), (j == 0 && pooled_in_block) ? &pool_from : nullptr,
                           pooled_by_block ? &p : nullptr);
         }
-        if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "rm.enc%d", lv); add_tap2(pl, nm, x); }
+        if (pl.key.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "rm.enc%d", lv); add_tap2(pl, nm, x); }
         // the next level's first block stages AvgPool2d(2, 2) of this level's output itself when it is a fused block (one more launch off the f0 branch)
         pooled_in_block = next_takes_pool;
         if (pooled_in_block) pool_from = x;
@@ -345,7 +345,7 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
         { ConvOpts o; o.act = ACT_RELU; add_convT2d(pl, m.up[lv], x, cat[sl].chans(0, co), o); }
         x = cat[sl];
         for (int j = 0; j < m.n_blocks; j++) { T2 out = make_t2(A, B, co, H, W); x = add_res_block(pl, m.dec[lv][j], x, out, j + 1 < m.n_blocks ? &m.dec[lv][j + 1] : (lv + 1 < m.levels ? &m.dec[lv + 1][0] : nullptr)); }
-        if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "rm.dec%d", lv); add_tap2(pl, nm, x); }
+        if (pl.key.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "rm.dec%d", lv); add_tap2(pl, nm, x); }
     }
     const int Hg = m.gru_hidden, I = 3 * m.n_mels;
     T1 feat = make_t1(A, B, I, Tm, 0), gi = make_t1(A, B, 6 * Hg, Tm, 0), gout = make_t1(A, B, 2 * Hg, Tm, 0), sal = make_t1(A, B, m.n_out, Tm, 0);
@@ -364,7 +364,7 @@ T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool u
     add_conv1d(pl, m.gru_ih, feat, gi, 1, 0, 1);
     add_gru(pl, gi, gout, Hg, m.whh, m.whhT, m.bhh, &e->d_state[0].status, (int)(sizeof(StreamState) / sizeof(int)));
     { ConvOpts o; o.act = ACT_SIGMOID; add_conv1d(pl, m.fc, gout, sal, 1, 0, 1, o); }
-    if (pl.with_taps) { add_tap(pl, "rm.sal_ct", sal); add_tap(pl, "rm.gru_ct", gout); add_tap(pl, "rm.cnn_ct", feat); } else add_stamp(pl, "rm.sal");
+    if (pl.key.with_taps) { add_tap(pl, "rm.sal_ct", sal); add_tap(pl, "rm.gru_ct", gout); add_tap(pl, "rm.cnn_ct", feat); } else add_stamp(pl, "rm.sal");
     return sal;
 }
 
@@ -397,11 +397,11 @@ void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update
     const int Tm = pl.Tm;
     pl.d_f0 = A.floats((size_t)B * Tm);
     if (!update_cache) { add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, false, 0, 0, 0, 0, nullptr, nullptr, f0_in); return; }
-    const int R = (int)pl.R;
+    const int R = (int)pl.key.R;
     const size_t shift = frame16k / 160;                                   // rvc.rs:168
     if (shift > 1024 || Tm < 5) throw PanicError("pitch cache shift out of range");
     const long long cache_start = 1024 + 4 - Tm;                            // rvc.rs:172
-    const long long read_start = 1024 - (long long)hubert_length + pl.skip_head;   // rvc.rs:176
+    const long long read_start = 1024 - (long long)hubert_length + pl.key.skip_head;   // rvc.rs:176
     if (cache_start < 0 || read_start < 0 || read_start + R > 1024) throw PanicError("pitch cache slice out of range");
     float *pitchf = A.floats((size_t)B * R);
     int *pitch = (int *)A.alloc((size_t)B * R * sizeof(int));

@@ -428,7 +428,7 @@ T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
     ModelSY &m = *e->sy;
     if (!m.has_f0) throw std::logic_error("NSF source on a model without pitch guidance");
     Arena &A = pl.arena;
-    const int R = (int)pl.R, R2 = pl.dec_frames();
+    const int R = (int)pl.key.R, R2 = pl.dec_frames();
     const int upp = m.upp();
     const size_t N = (size_t)R * upp;
     if (R > 512) throw ShapeError("return_length too long for the NSF source kernel");
@@ -436,7 +436,7 @@ T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf)
     T1 src = make_t1(A, B, 1, (int)N, max_sf + 2);
     add_nsf_source(pl, B, d_pitchf, src, R, upp, (float)m.sr, m.src_w, m.src_b, e->d_state, e->d_cp, R2, R);        // formant shift: f0 x R2 / R compensates the time stretch below (1 without one)
     add_tap(pl, "sy.src", src);
-    if (!pl.fstage) return src;
+    if (!pl.key.fstage) return src;
     // formant shift: the source stretched to R2 frames (formant.hip.h)
     T1 srci = src;
     if (R2 != R) {
@@ -473,7 +473,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
 {
     ModelSY &m = *e->sy;
     Arena &A = pl.arena;
-    const int R = (int)pl.R, H = m.hidden, I = m.inter, F = m.filter, half = I / 2;
+    const int R = (int)pl.key.R, H = m.hidden, I = m.inter, F = m.filter, half = I / 2;
     const int HALO = 4;
     if (m.enc_k / 2 > HALO || m.wn_k / 2 > HALO) throw ShapeError("synth kernel sizes exceed the halo");
     T1 z = make_t1(A, B, I, R, HALO), zf = make_t1(A, B, I, R, HALO);
@@ -488,7 +488,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         add_tap(pl, "sy.emb", x);
         T1 qkv = make_t1(A, B, 3 * H, R, 0), att = make_t1(A, B, H, R, 0), ff = make_t1(A, B, F, R, HALO);
         // one stream: the second LayerNorm of every encoder layer is folded into the next projection (see build_contentvec)
-        const bool fuse_ln = B <= LN_FOLD_MAX_STREAMS && m.has_folded && !pl.plain_plan && !test_opt("RVC_NO_LN_FUSE");
+        const bool fuse_ln = B <= LN_FOLD_MAX_STREAMS && m.has_folded && !pl.key.plain_plan && !test_opt("RVC_NO_LN_FUSE");
         bool raw = false; const float *raw_g = nullptr, *raw_b = nullptr; float *raw_st = nullptr;
         for (int l = 0; l < m.enc_layers; l++) {
             ModelSY::Layer &Ly = m.layers[l];
@@ -510,7 +510,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         // one stream: WaveNets with their res_skip layers composed away and post + next pre merged (ModelSY::compose_flows): 21 launches for
         // four flows instead of 40.  U[k] = [ones16 | h0 (H) | a_0 .. a_{n-1} | z (I)]; flow k reads U[k & 1] and writes h0 and z of U[(k + 1) & 1]
         static const int wn_max_b = tune_env("RVC_WN_COMPOSE_MAX") ? atoi(tune_env("RVC_WN_COMPOSE_MAX")) : 8;
-        const bool wn_composed = B <= wn_max_b && H % 16 == 0 && I == H && !pl.plain_plan && !test_opt("RVC_NO_WN_COMPOSE");      // (launch-bound up to a few streams)
+        const bool wn_composed = B <= wn_max_b && H % 16 == 0 && I == H && !pl.key.plain_plan && !test_opt("RVC_NO_WN_COMPOSE");      // (launch-bound up to a few streams)
         T1 U[2];
         const int u_z = 16 + H + H * m.wn_layers;                     // first latent row of U
         if (wn_composed) {
@@ -545,7 +545,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
                 if (fi > 0) add_conv1d_two(pl, Fw.posth, Fw.postc, Fw.pair_bias, Uc.rows(16 + H, H * m.wn_layers + I), Un.rows(16, H), Un.rows(u_z, I));
                 else add_conv1d(pl, Fw.postc, Uc.rows(16 + H, H * m.wn_layers + I), Un.rows(u_z, I), 1, 0, 1);
                 if (fi == 0) z = Un.rows(u_z, I);
-                if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.flow%d", fi); add_tap(pl, nm, Un.rows(u_z, I)); } else add_stamp(pl, "sy.flow");
+                if (pl.key.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.flow%d", fi); add_tap(pl, nm, Un.rows(u_z, I)); } else add_stamp(pl, "sy.flow");
                 continue;
             }
             add_conv1d(pl, Fw.pre, x0, hs, 1, 0, 1);                       // hh = pre(x0), skip = 0
@@ -556,7 +556,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
                 else add_conv1d(pl, Fw.rs[j], acts, skip, 1, 0, 1, o);
             }
             { ConvOpts o; o.scale = -1.f; o.accumulate = true; add_conv1d(pl, Fw.post, skip, x1, 1, 0, 1, o); }
-            if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.flow%d", fi); add_tap(pl, nm, z); } else add_stamp(pl, "sy.flow");
+            if (pl.key.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.flow%d", fi); add_tap(pl, nm, z); } else add_stamp(pl, "sy.flow");
         }
         if (m.flow_n & 1) {
             // odd number of flips: materialise the last one
@@ -568,7 +568,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
     add_tap(pl, "sy.z", z);
     const int upp = m.upp();
     const int R2 = pl.dec_frames();
-    if (pl.fstage) {
+    if (pl.key.fstage) {
         // formant shift: the latent stretched to R2 frames; the decoder runs on them (formant.hip.h)
         if (R2 != R) {
             T1 zi = make_t1(A, B, I, R2, HALO); dim3 grid((I * R2 + 255) / 256, B); T1 zs = z;
@@ -602,7 +602,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         int sf = 1; for (int q = i + 1; q < m.n_ups; q++) sf *= m.up_rate[q];
         { ConvOpts o; o.accumulate = true; if (i + 1 < m.n_ups) add_conv1d(pl, m.ncs[i], src, u, sf, sf / 2, 1, o); else add_conv1d(pl, m.ncs[i], src, u, 1, 0, 1, o); }
         }
-        if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.up%d", i); add_tap(pl, nm, u); } else add_stamp(pl, "sy.up");
+        if (pl.key.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.up%d", i); add_tap(pl, nm, u); } else add_stamp(pl, "sy.up");
         // the n_rb ResBlock chains of a stage are independent until their average
         T1 xs = make_t1(A, B, co, Tn, DH);
         std::vector<T1> finals;
@@ -632,7 +632,7 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
         // epilogue stores (j = 0) or adds (j > 0) its output x 1 / n_rb -- instead of three stored tensors and an averaging launch per
         // stage (round 6: 4 launches and ~1 GB of reads + writes per 64-stream step).  The split-bf16 kernels have no accumulating
         // epilogue: those plans keep the averaging launch.
-        const bool mean_in_epilogue = !fused && !pl.bf3 && test_opt_int("RVC_MEAN3", 0) == 0;     // (test hook RVC_MEAN3 = 1: the averaging launch)
+        const bool mean_in_epilogue = !fused && !pl.key.bf3 && test_opt_int("RVC_MEAN3", 0) == 0;     // (test hook RVC_MEAN3 = 1: the averaging launch)
         for (int j = 0; j < m.n_rb && !fused; j++) {
             const int k = m.rb_k[j];
             T1 ra = make_t1(A, B, co, Tn, DH), rb = make_t1(A, B, co, Tn, DH), tt = make_t1(A, B, co, Tn, DH), fin = mean_in_epilogue ? xs : make_t1(A, B, co, Tn, 0);
@@ -658,10 +658,10 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
             dim3 grid((co * Tn + 255) / 256, B);
             pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(mean3_kernel, grid, dim3(256), 0, s, f0, f1, f2, fi.ld, fi.bs, xs.p, xs.ld, xs.bs, co, Tn, inv); });
         }
-        if (pl.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.rb%d", i); add_tap(pl, nm, xs); } else add_stamp(pl, "sy.rb");
+        if (pl.key.with_taps) { char nm[32]; snprintf(nm, sizeof nm, "sy.rb%d", i); add_tap(pl, nm, xs); } else add_stamp(pl, "sy.rb");
         xd = xs; c = co; Tc = Tn;
     }
-    if (pl.fstage) {
+    if (pl.key.fstage) {
         // formant shift: the decoder's output y2 (R2 upp samples) back to the model rate, R upp samples per stream, by each stream's own
         // descriptor; the kernel writes the caller's buffer when the call provides one (Plan::cur_out)
         T1 dec = make_t1(A, B, 1, Tc, 0);
@@ -677,14 +677,14 @@ void build_synth(rvc_engine *e, Plan &pl, int B, const T1 &phone, const T1 &src,
             hipLaunchKernelGGL(formant_resample_kernel, grid, dim3(256), 0, s, dec.p, dec.bs, y, ybs, No, st);
         });
         pl.N = (size_t)No;
-        pl.out_direct_ok = !pl.with_taps;
+        pl.out_direct_ok = !pl.key.with_taps;
         add_stamp(pl, "sy.audio");
         return;
     }
     pl.audio = make_t1(A, B, 1, Tc, 0);
     { ConvOpts o; o.pre_act = ACT_LRELU; o.pre_slope = 0.01f; o.act = ACT_TANH; o.no_bias = true; o.final_out = true; add_conv1d(pl, m.dec_post, xd, pl.audio, 1, 3, 1, o); }
     pl.N = (size_t)Tc;
-    pl.out_direct_ok = pl.audio.ld == Tc && !pl.with_taps && pl.final_out_honoured;     // (queue_igemm says whether the launch path it chose writes the caller's buffer)
+    pl.out_direct_ok = pl.audio.ld == Tc && !pl.key.with_taps && pl.final_out_honoured;     // (queue_igemm says whether the launch path it chose writes the caller's buffer)
     if (pl.audio.ld != Tc) {
         // make the output rows contiguous [B][N] for the device-pointer API
         T1 a2; a2.p = A.floats((size_t)B * Tc); a2.B = B; a2.C = 1; a2.T = Tc; a2.ld = Tc; a2.halo = 0; a2.bs = Tc;

@@ -500,7 +500,7 @@ static bool queue_conv32s(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD
     if (c.ch.kind != 0 && c.ch.kind != 1) return false;          // (a trial of another kernel family)
     const bool chosen = c.ch.kind == 1;                           // (a trial of THIS family: the size rules below are what is being measured)
     const int mode = chosen ? 2 : test_opt_int("RVC_CONV32S", 1);
-    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.y_ws != 1 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part || p.bf3 || c.pl.bf3) return false;
+    if (!mode || p.fold_n || p.x_ld <= 0 || p.x_hs || p.x_ws != 1 || p.y_hm || p.y_ws != 1 || p.glu || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || p.part || p.bf3 || c.pl.key.bf3) return false;
     if (mode < 2 && (B <= 4 || p.N < 200 || p.M < 32)) return false;
     for (const PhaseD &q : phv) if (q.act_p1 != 0 || q.y_off != 0 || q.y_pos != 0) return false;
     // tile by the height of the weight panel; every wave owns 32 x 64 outputs (round 5 sweep of six tiles per layer at 8 / 16 / 32 / 64 streams, gpurun_out
@@ -563,7 +563,7 @@ static bool queue_conv32s(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD
 static bool queue_bf3(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &phv)
 {
     const int nchunks = p.K / 16;
-    if (!((p.bf3 || c.pl.bf3) && !p.glu && !c.ln_fold && B == 1 && p.x_hs == 0 && p.y_hm == 0 && p.M >= 128 && nchunks >= 2 && !p.accumulate &&
+    if (!((p.bf3 || c.pl.key.bf3) && !p.glu && !c.ln_fold && B == 1 && p.x_hs == 0 && p.y_hm == 0 && p.M >= 128 && nchunks >= 2 && !p.accumulate &&
           (size_t)nchunks * 64 + 2 * 2 * 128 * 48 <= 60 * 1024 &&
           (long long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.nphase >= 250)) return false;
     const bool pre = p.pre_act != ACT_NONE;
@@ -736,8 +736,8 @@ static bool queue_tiled(GemmCall &c, IgemmP p, int B)
     // igemm32l_kernel (one-phase 1-D layers, buffer loads with scalar offsets): its 128 x 64 tile beats the 128 x 128 tile of either kernel on every layer it can
     // take -- the 3072-row projection (64 streams 36.12 -> 35.81 ms), the 2304-row one (35.31 -> 35.05), the strided stem (35.28 -> 35.05; 16 / 32 streams
     // 11.35 / 19.70 -> 11.23 / 19.50) -- so those layers move there (test hook RVC_G32L_TALL = 0: keep the 128 x 128 tile)
-    const bool g32l_on = p.lin_cs4 != 0 && p.nphase == 1 && !pre && !p.bf3 && !c.pl.bf3 && test_opt_int("RVC_G32L", 1) != 0;
-    const bool g32t_on = !g32l_on && p.lin_cs4 == 0 && p.nphase == 1 && B == 1 && p.x_hs == 0 && p.y_hm == 0 && !p.bf3 && !c.pl.bf3 && !p.glu &&
+    const bool g32l_on = p.lin_cs4 != 0 && p.nphase == 1 && !pre && !p.bf3 && !c.pl.key.bf3 && test_opt_int("RVC_G32L", 1) != 0;
+    const bool g32t_on = !g32l_on && p.lin_cs4 == 0 && p.nphase == 1 && B == 1 && p.x_hs == 0 && p.y_hm == 0 && !p.bf3 && !c.pl.key.bf3 && !p.glu &&
                          test_opt_int("RVC_G32L", 1) != 0 && test_opt_int("RVC_G32L_TAB", 1) != 0;
     if ((g32l_on || (g32t_on && !pre)) && lds_cfg == 3 && c.ch.kind != 3 && test_opt_int("RVC_G32L_TALL", 1) != 0) lds_cfg = 7;
     if (lds_cfg < 0) return false;
@@ -1009,7 +1009,7 @@ static double tune_trial(const Plan &pl, const IgemmP &p, int B, const std::vect
     Plan &tp = *scratch;
     HIPCHK(hipStreamSynchronize(tune_stream()));          // (the previous trial's launches still read the tables that are about to be overwritten)
     tp.ops = OpList(); tp.descs.clear(); tp.koff_tabs.clear(); tp.arena.rewind();
-    tp.B = pl.B; tp.bf3 = pl.bf3; tp.autotune = false; tp.profile = false; tp.igemm_flops = 0; tp.n_igemm = 0;
+    tp.key.B = pl.key.B; tp.key.bf3 = pl.key.bf3; tp.autotune = false; tp.profile = false; tp.igemm_flops = 0; tp.n_igemm = 0;
     Choice b;
     try { b = queue_igemm_impl(tp, p, B, koff, phases, false, c); }
     catch (...) { return -1.0; }
@@ -1045,7 +1045,7 @@ void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const 
         queue_igemm_impl(pl, p, B, koff, phases, final_out, c);
         return;
     }
-    if (!pl.autotune || B <= 4 || pl.bf3 || p.bf3 || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || planner_hook_set()) { queue_igemm_impl(pl, p, B, koff, phases, final_out, Choice()); return; }
+    if (!pl.autotune || B <= 4 || pl.key.bf3 || p.bf3 || p.ln_wsum || p.ln_stats_in || p.ln_stats_out || planner_hook_set()) { queue_igemm_impl(pl, p, B, koff, phases, final_out, Choice()); return; }
     // layer signature: everything the kernels' speed depends on (shape, strides, taps, epilogue class), not the tensors
     std::string key;
     {
@@ -1503,7 +1503,7 @@ void add_stamp(Plan &pl, const char *name)
 void add_tap(Plan &pl, const char *name, const T1 &t)
 {
     add_stamp(pl, name);
-    if (!pl.with_taps) return;
+    if (!pl.key.with_taps) return;
     // snapshot into a private contiguous-row tensor so later in-place ops do not clobber it: every stream of the tensor, each from its own
     // slice (t.bs), stream-major (rvc_get_tap reads stream 0, rvc_debug_tap any of them)
     T1 snap = make_t1(pl.arena, t.B, t.C, t.T, 0);
@@ -1516,7 +1516,7 @@ void add_tap(Plan &pl, const char *name, const T1 &t)
 void add_tap2(Plan &pl, const char *name, const T2 &t)
 {
     add_stamp(pl, name);
-    if (!pl.with_taps) return;
+    if (!pl.key.with_taps) return;
     TapRec r; r.name = name; r.rank = 2; r.t2 = t; pl.taps.push_back(r);   // RMVPE images are never overwritten
 }
 

@@ -1,6 +1,6 @@
 // protect.hip.h -- consonant protection (upstream RVC's `protect`; DESIGN.md "Consonant protection"): on the unvoiced rows of a chunk the
 // index-blended features are mixed back towards the raw ContentVec features,
-//   phone[c][r] = p phone[c][r] + (1 - p) raw[c][r]        for every row r with pitchf[r] < 1.0f,   p = StreamState::protect
+//   phone[c][r] = p phone[c][r] + (1 - p) raw[c][r]        for every row r with pitchf[r] < 1.0f,   p = StreamCtl::protect
 // one launch behind the join of the two front branches, on the plans that use the index and have a stream with p < 0.5 (engine.hip get_plan).
 // raw[c][r] is the element gather_phone_kernel wrote before the retrieval: the ContentVec output is never written by the retrieval, so it is read
 // again through the same column rule (phone_src_col) instead of being copied.
@@ -31,7 +31,7 @@ protect_mix_kernel(const StreamState *__restrict__ st, const float *__restrict__
                    int skip_head, int R, float *__restrict__ phone, int ph_cs, long long ph_bs)
 {
     const int b = blockIdx.y;
-    const float p = st[b].protect;
+    const float p = st[b].ctl.protect;
     if (!(p < (float)PROTECT_OFF)) return;                      // this stream is off (uniform over the workgroup)
     const int r = blockIdx.x * PROTECT_ROWS + threadIdx.x;
     if (r >= R) return;

@@ -21,7 +21,7 @@ static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_r
 {
         if (!e->index.ivf.cent) throw ShapeError("no IVF structure attached to the index");
         const int nlist = (int)e->index.ivf.nlist, Q = B * nq;
-        const int nprobe = std::min(pl.nprobe, nlist);
+        const int nprobe = std::min(pl.key.nprobe, nlist);
         float *D = pl.arena.floats((size_t)Q * nlist);
         int *scanned = (int *)pl.arena.alloc((size_t)Q * sizeof(int));
         pl.d_ivf_scanned = scanned; pl.ivf_queries = Q;
@@ -47,7 +47,7 @@ static void build_ivf(rvc_engine *e, Plan &pl, int B, int C, int nq, int first_r
             const size_t lds = ((size_t)IVF_TILE + C) * sizeof(float);
             if (lds > 144 * 1024) throw ShapeError("feature dimension too large for the retrieval kernel");
             dim3 grid(nq, B);
-            const auto scan_kernel = KNN_KERNEL_FOR(ivf_scan_blend, pl.knn_k);
+            const auto scan_kernel = KNN_KERNEL_FOR(ivf_scan_blend, pl.key.knn_k);
             pl.ops.push_back([=](hipStream_t s) {
                 const ProfEvent *pe = plp->prof_slot(0, 0, -1, "knn_ivf_scan");     // (bytes: the rows the probe sets held, read back by rvc_profile_last_knn)
                 if (pe) hipExtLaunchKernelGGL(scan_kernel, grid, dim3(256), (uint32_t)lds, s, pe->a, pe->b, 0, sp);
@@ -63,13 +63,13 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
         const int first_raw = std::min((int)skip_head / 2, T - 1), last_raw = std::min((int)(skip_head + R - 1) / 2, T - 1);
         const int nq = last_raw - first_raw + 1;
         const int nblk = (int)((e->index.n + 255) / 256);
-        const int K = pl.knn_k;
+        const int K = pl.key.knn_k;
         if (K != KNN_K && K != KNN_KMAX) throw ShapeError("k must be 4 or 8");
         if (e->index.n < (size_t)K) throw ShapeError("index needs at least " + std::to_string(K) + " vectors");
         pl.d_knn_idx = (int *)pl.arena.alloc((size_t)B * R * K * sizeof(int));
         pl.d_knn_dist = pl.arena.floats((size_t)B * R * K);
         T1 cvo = pl.cv_out;
-        if (pl.nprobe > 0) { build_ivf(e, pl, B, C, nq, first_raw, skip_head, R, T, phone, cvo); return; }
+        if (pl.key.nprobe > 0) { build_ivf(e, pl, B, C, nq, first_raw, skip_head, R, T, phone, cvo); return; }
         // Stage A + B: approximate distances on the matrix cores in one pass over the index (HBM-bound), exact re-rank of a
         // provably sufficient candidate set.
         const bool fast = C % 16 == 0 && !test_opt("RVC_KNN_EXHAUSTIVE");
@@ -123,7 +123,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
             // What the engine runs instead when a selector gave up (ST_KNN_TIMEOUT: a workgroup of the launch did not arrive in time, e.g. on a GPU
             // shared with another process): the exhaustive exact scan over the row-major index + merge + blend, built into a list of its own.
             // The chunk is then recomputed from `phone` on and the call returns RVC_OK (engine.hip recover_retrieval).
-            if (!pl.bucket) {
+            if (!pl.key.bucket) {
                 OpList main_ops = std::move(pl.ops);
                 pl.ops = OpList();
                 build_exhaustive(e, pl, B, C, nq, nblk, first_raw, skip_head, R, T, phone, cvo, false, nullptr);
@@ -177,7 +177,7 @@ void build_retrieval(rvc_engine *e, Plan &pl, int B, int T, int C, uint32_t skip
 static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int nblk, int first_raw, uint32_t skip_head, uint32_t R, int T, const T1 &phone, const T1 &cvo,
                              bool fast, int *d_overflow, float *d_q, float *cand_d, int *cand_i)
 {
-        const int K = pl.knn_k;
+        const int K = pl.key.knn_k;
         if (!d_q) {
             d_q = pl.arena.floats((size_t)B * nq * C);
             cand_d = pl.arena.floats((size_t)B * nq * nblk * K);
@@ -213,7 +213,7 @@ static void build_exhaustive(rvc_engine *e, Plan &pl, int B, int C, int nq, int 
 static void drop_index_ivf(rvc_engine *e)
 {
     e->index.ivf = IvfLists(); e->index_nprobe = 0;
-    e->plans.clear(); e->last_plan = nullptr;
+    drop_plans(e);
 }
 
 // The CSR of an assignment (list offsets + row permutation, rows ascending inside every list) by the counting sort of ivf.hip.h, queued on the engine's stream:
@@ -337,7 +337,7 @@ static int kmeans_lloyd(rvc_engine *e, KmeansWork &w, const std::vector<int32_t>
 static void drop_index(rvc_engine *e)
 {
     e->index = RetrievalIndex(); e->index_nprobe = 0;
-    e->plans.clear(); e->last_plan = nullptr;
+    drop_plans(e);
 }
 
 // The one way a matrix becomes the engine's index: rvc_load_index[_device], rvc_index_build_finish and rvc_index_broadcast all end here.  Everything the
@@ -529,14 +529,14 @@ rvc_status rvc_get_knn(rvc_engine *e, int32_t *idx, float *dist, size_t cap_rows
     return guarded(e, [&]() {
         Plan *pl = e->last_plan;
         // (after rvc_infer_batch_g the last plan is one geometry bucket's, in bucket-local stream order: no rows are reported for such a call)
-        if (!pl || !pl->with_index || !e->last_knn_rows) { if (rows) *rows = 0; return RVC_OK; }
+        if (!pl || !pl->key.with_index || !e->last_knn_rows) { if (rows) *rows = 0; return RVC_OK; }
         // stream 0's return_length rows always; the further streams' rows (stream-major) as far as the caller's capacity holds whole streams
-        if (cap_rows < pl->R) { if (rows) *rows = pl->R; return RVC_SHAPE; }
-        const size_t r = pl->R * std::min((size_t)pl->B, cap_rows / pl->R);
+        if (cap_rows < pl->key.R) { if (rows) *rows = pl->key.R; return RVC_SHAPE; }
+        const size_t r = pl->key.R * std::min((size_t)pl->key.B, cap_rows / pl->key.R);
         if (rows) *rows = r;
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(idx, pl->d_knn_idx, r * pl->knn_k * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(dist, pl->d_knn_dist, r * pl->knn_k * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(idx, pl->d_knn_idx, r * pl->key.knn_k * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist, pl->d_knn_dist, r * pl->key.knn_k * sizeof(float), hipMemcpyDeviceToHost));
         return RVC_OK;
     });
 }

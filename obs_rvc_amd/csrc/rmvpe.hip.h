@@ -173,7 +173,7 @@ static __global__ __launch_bounds__(1024) void pitch_post_kernel(PitchP p)
     __shared__ int idxs[1024];
     const int b = blockIdx.x, t = threadIdx.x;
     StreamState *st = p.st + b;
-    const float up = st->uppower;        // per stream: every stream of a batch is its own caller with its own pitch shift (obs-rvc/src/lib.rs:701-707)
+    const float up = st->ctl.uppower;        // per stream: every stream of a batch is its own caller with its own pitch shift (obs-rvc/src/lib.rs:701-707)
     // Row scan split over bin groups: thread (tt = t % TT, grp = t / TT) scans bins [grp*BPG, ...) of time step tt (loads
     // coalesced along time), then group 0 combines.  Same result as the sequential scan of the zero-padded row (368 wide,
     // "first strictly greater wins", padded[0] = 0): start = first index of the maximum if it is > 0, else 0.
@@ -220,10 +220,10 @@ static __global__ __launch_bounds__(1024) void pitch_post_kernel(PitchP p)
     }
     __syncthreads();
     // pitch controls (f0cond.hip.h): gate, median and scale snap on the multiplied rows, for either f0 method and for update = 0; a stream with every
-    // control neutral (c_on == 0, uniform over the workgroup) passes with this one load
-    const uint32_t con = st->c_on;
+    // control neutral (ctl.c.on == 0, uniform over the workgroup) passes with this one load
+    const uint32_t con = st->ctl.c.on;
     if (con) {
-        const float lo = st->c_lo, hi = st->c_hi, strength = st->c_strength;
+        const float lo = st->ctl.c.lo, hi = st->ctl.c.hi, strength = st->ctl.c.strength;
         if (grp == 0 && tt < p.Tm) f0s[tt] = f0cond_gate(hz_out, con, lo, hi);
         __syncthreads();
         if (grp == 0 && tt < p.Tm) hz_out = f0cond_row(f0s, p.Tm, tt, con, strength);     // (kept in the register across the barrier: the neighbours still read f0s[])

@@ -314,7 +314,7 @@ rvc_status rvc_session_process(rvc_session *s, const float *input_sample, size_t
                 // (the plan infer_common will run: its formant key; streams in several formant buckets run synchronously anyway)
                 uint32_t r2 = 0; bool fstage = false;
                 if (formant_key(e, (uint32_t)s->model_return_length, nullptr, &r2, &fstage)) {
-                    Plan *peek = get_plan(e, 0, (size_t)s->input_buffer_16k_size, (size_t)s->sample_frame_16k, (uint32_t)s->skip_head, (uint32_t)s->model_return_length, 0, 0, r2, fstage);
+                    Plan *peek = get_plan(e, plan_key(e, 0, (size_t)s->input_buffer_16k_size, (size_t)s->sample_frame_16k, (uint32_t)s->skip_head, (uint32_t)s->model_return_length));
                     sync_infer = !peek->knn_fallback.empty();
                 } else sync_infer = true;
             }

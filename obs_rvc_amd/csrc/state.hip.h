@@ -9,30 +9,43 @@ namespace rvc {
 // per-stream state + per-call parameters
 // ------------------------------------------------------------------------------------
 struct CallParams {
-    float uppower;          // (round 2: one multiplier per call; now per stream, StreamState::uppower -- kept for layout)
+    float uppower;          // (round 2: one multiplier per call; now per stream, StreamCtl::uppower -- kept for layout)
     uint32_t seed;
     uint32_t chunk_base;    // chunk counter of stream 0 is chunk[b] (kept per stream on device)
     int pad_;
+};
+// formant stage of a stream (formant.hip.h; synth.hip.h formant_resample_kernel) as the host writes it
+struct FormantDesc {
+    const float *tab;       // [n][kt] filter rows (the engine's table cache), nullptr when ident
+    const int *kb;          // [n] first tap of each row
+    int o, n, w, kt, nx, ident;     // ratio o -> n, left width, taps per row, valid input samples (R upp_res), 1 = copy
+    bool operator==(const FormantDesc &x) const { return tab == x.tab && kb == x.kb && o == x.o && n == x.n && w == x.w && kt == x.kt && nx == x.nx && ident == x.ident; }
+};
+// pitch controls of a stream (f0cond.hip.h, read by pitch_post_kernel every chunk).  The semitone transpose has no field: it is a factor of uppower
+//   on: 0 = every control neutral (the tail skips the stage); bits 0-3 the median radius, bits 4-15 the pitch-class mask (bit 4 + k = class k, C = 0; 0 when
+//   strength = 0), bit 16 the range gate
+struct F0Cond {
+    uint32_t on; float lo, hi, strength;      // range gate in Hz; scale snap strength, (0, 1]
+    bool operator==(const F0Cond &x) const { return on == x.on && lo == x.lo && hi == x.hi && strength == x.strength; }
+};
+// Everything of a stream that the host sets and the kernels only read: one block of StreamState, written by one strided copy (engine.hip push_call_params).
+struct StreamCtl {
+    FormantDesc f;
+    F0Cond c;
+    float uppower;          // this stream's 2^(pitch_shift / 12), truncating division (rvc.rs:121), times its formant multiplier 2^(-phi / 12): every stream is its own caller
+    // consonant protection (protect.hip.h protect_mix_kernel): the value itself, [0, 0.5], 0.5 = off.  A zero-filled state therefore means FULL protection:
+    // whoever builds a state by hand sets the word (debug.hip does)
+    float protect;
+    bool operator==(const StreamCtl &x) const { return f == x.f && c == x.c && uppower == x.uppower && protect == x.protect; }
 };
 struct StreamState {        // one per stream
     float cache_pitchf[1024];   // rvc.rs:42
     uint32_t chunk;
     uint32_t stream_id;
     int status;             // 0 ok, else a set of ST_* bits (atomicOr by the kernels, read and cleared by the host: engine.hip check_status)
-    float uppower;          // this stream's 2^(pitch_shift / 12), truncating division (rvc.rs:121), times its formant multiplier 2^(-phi / 12): every stream is its own caller
-    // formant stage of this stream (synth.hip.h formant_resample_kernel; written by the host with the multiplier, engine.hip push_call_params)
-    const float *f_tab;     // [n][kt] filter rows (the engine's table cache), nullptr when f_ident
-    const int *f_kb;        // [n] first tap of each row
-    int f_o, f_n, f_w, f_kt, f_nx, f_ident;     // ratio o -> n, left width, taps per row, valid input samples (R upp_res), 1 = copy
-    // pitch controls of this stream (f0cond.hip.h F0Cond, read by pitch_post_kernel every chunk; written by the host like the formant fields).  The
-    // semitone transpose has no field: it is a factor of uppower
-    uint32_t c_on;          // 0 = every control neutral (the tail skips the stage); bits 0-3 median radius, 4-15 pitch-class mask, 16 range gate
-    float c_lo, c_hi;       // range gate in Hz
-    float c_strength;       // scale snap strength, (0, 1]
-    // consonant protection of this stream (protect.hip.h protect_mix_kernel; written by the host like the pitch controls): the value itself, [0, 0.5],
-    // 0.5 = off.  A zero-filled state therefore means FULL protection: whoever builds a state by hand sets the word (debug.hip does)
-    float protect;
+    StreamCtl ctl;
 };
+static_assert(sizeof(StreamCtl) == 64 && sizeof(StreamState) == 4176, "StreamState layout");
 #define KNN_K 4                            // neighbours per retrieval query: the default and the minimum (knn.hip.h kernels are template <int K>) ...
 #define KNN_KMAX 8                         // ... and upstream's eight (rvc_set_index_k; an index holds at least k rows)
 constexpr double PROTECT_OFF = 0.5;       // the setting lives in [0, PROTECT_OFF]; PROTECT_OFF and above = no protection (upstream: `protect < 0.5` enables it)

@@ -171,7 +171,7 @@ static __global__ __launch_bounds__(256) void time_lerp_kernel(const float *x, i
     y[(long long)b * ybs + (long long)c * yld + i] = __fmul_rn(1.f - l, row[i0]) + __fmul_rn(l, row[i1]);
 }
 
-// Back to the model rate, per stream from its descriptor (StreamState::f_*, so that the streams of one plan may differ and a captured
+// Back to the model rate, per stream from its descriptor (StreamState::ctl.f, so that the streams of one plan may differ and a captured
 // graph stays valid when the shift changes): y[q n + j] = sum_t ht[j][t] x[q o + kb[j] + t - w], x = y2[0 : nx] and zero outside;
 // an identity stream (upp_res = upp) copies y2[0 : N].  One thread per output sample.
 static __global__ __launch_bounds__(256) void formant_resample_kernel(const float *x, long long xbs, float *y, long long ybs, int N, const StreamState *st)
@@ -181,10 +181,10 @@ static __global__ __launch_bounds__(256) void formant_resample_kernel(const floa
     const StreamState &s = st[b];
     const float *row = x + (long long)b * xbs;
     float *out = y + (long long)b * ybs;
-    if (s.f_ident) { out[i] = row[i]; return; }
-    const int n = s.f_n, q = i / n, j = i - q * n, Kt = s.f_kt, nx = s.f_nx;
-    const float *h = s.f_tab + (long long)j * Kt;
-    const int base = q * s.f_o + s.f_kb[j] - s.f_w;
+    if (s.ctl.f.ident) { out[i] = row[i]; return; }
+    const int n = s.ctl.f.n, q = i / n, j = i - q * n, Kt = s.ctl.f.kt, nx = s.ctl.f.nx;
+    const float *h = s.ctl.f.tab + (long long)j * Kt;
+    const int base = q * s.ctl.f.o + s.ctl.f.kb[j] - s.ctl.f.w;
     float acc = 0.f;
     for (int t = 0; t < Kt; t++) {
         const int k = base + t;
