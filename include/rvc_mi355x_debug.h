@@ -215,6 +215,9 @@ int rvc_debug_weight_slabs(int device, int *count, size_t *bytes);
 /* the kernel the planner chose for this thread's last rvc_debug_conv*_check / rvc_debug_layer launch ("reg", "g32", "c32s", ...), or the variant of
  * its last rvc_debug_op */
 const char *rvc_debug_last_kernel(void);
+/* the whole description of this thread's last implicit-GEMM launch queued, as rvc_debug_profile_dump prints it ("reg M=20 N=37 K=16384 ... split=2": split > 1
+ * is the two-stage grid-level split-K, partial sums finished by splitk_epilogue_kernel) */
+const char *rvc_debug_last_desc(void);
 /* host only: the formant resampler's full filter table h[n][K] (o -> n, K = 2 w + o; obs_rvc_amd/csrc/formant.hip.h) as fp32.  *width = K;
  * returns 0, 1 when cap < n K (nothing written to out), -1 for bad arguments */
 int rvc_debug_formant_table(size_t o, size_t n, float *out, size_t cap, size_t *width);

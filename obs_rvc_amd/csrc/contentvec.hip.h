@@ -1,7 +1,7 @@
 // contentvec.hip.h -- ContentVec's first layer (Conv1d + GroupNorm + GELU in one kernel, and the stand-alone GroupNorm + GELU).  Included by
 // model_cv.hip only.
 #pragma once
-#include "igemm.hip.h"
+#include "igemm_common.hip.h"
 #include "reduce.hip.h"
 
 namespace rvc {

@@ -13,7 +13,7 @@
 // packing of the whole family (lane (row r, k-slot s) reads the float4 of fragment r >> 4, quad 2u + s: MFMA (u, j) takes channel (2u + s) * 4 + j).
 // The streams stay a grid dimension (a tile never straddles two streams: its staged columns are one contiguous range of one row set).
 #pragma once
-#include "igemm.hip.h"
+#include "igemm_common.hip.h"
 
 namespace rvc {
 

@@ -33,7 +33,7 @@
 //                       reach = (KW - 1) * dil <= 64, independent of Cin; at the decoder's reach of 50: BN = 32 23 616 B, BN = 64 32 832 B,
 //                       BN = 128 51 264 B (the K shares' reduction, 8 KB, reuses them).
 #pragma once
-#include "igemm.hip.h"
+#include "igemm_common.hip.h"
 #include "conv32s.hip.h"
 
 namespace rvc {

@@ -955,6 +955,15 @@ const char *rvc_debug_last_kernel(void)
     return buf.c_str();
 }
 
+// the whole description of this thread's most recently queued implicit-GEMM launch (what rvc_debug_profile_dump prints per launch): tests read the fields
+// after the family, e.g. "split=2" for the two-stage grid-level split-K
+const char *rvc_debug_last_desc(void)
+{
+    static thread_local std::string buf;
+    buf = g_last_desc;
+    return buf.c_str();
+}
+
 // test aid: launches (ops) of the last call's plan
 int rvc_debug_last_plan(rvc_engine *e, int *n_ops)
 {

@@ -10,7 +10,7 @@
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
 // (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
-// or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm.hip.h) are instantiated by the
+// or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm2 / igemm2w / igemm_lds / igemm32 / igemm_bf3 / igemm_splitk .hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
 #include "../../include/rvc_mi355x.h"
@@ -329,6 +329,7 @@ struct Plan {
 extern unsigned long long *g_kprobe;      // tuning build (-DRVC_KPROBE): destination of the per-wave phase stamps
 extern int g_last_waves, g_last_wgs, g_ncu;
 extern thread_local char g_last_kernel[32];      // this thread's most recently queued launch: implicit-GEMM family ("reg", "g32", "c32s", ...) or op variant ("attn_mfma2", "ln_strip12", ...)
+extern thread_local char g_last_desc[200];       // ... and the whole description of the last implicit-GEMM launch queued ("reg M=.. N=.. ... split=2")
 void queue_igemm(Plan &pl, IgemmP p, int B, const std::vector<int> &koff, const std::vector<PhaseD> &phases, bool final_out = false);
 // one GEMM-class launch of the planner (description, FLOPs, launch shape, profile slot, final_out): launch(q, ea, eb, stream) gets the IgemmP to use and the
 // slot's events.  Defined and instantiated in plan.hip (the body is inlined into the op, as lean as a hand-written one)
@@ -443,7 +444,7 @@ struct ModelFC {
     ModelFC(const ModelFC &) = delete; ModelFC &operator=(const ModelFC &) = delete;
 };
 
-// GLU row packing of a WaveNet in-layer (igemm.hip.h glu_store): packed row f*16 + kq*4 + r <- model row f*8 + kq*2 + (r&1) of the tanh half (r < 2)
+// GLU row packing of a WaveNet in-layer (igemm_common.hip.h glu_store): packed row f*16 + kq*4 + r <- model row f*8 + kq*2 + (r&1) of the tanh half (r < 2)
 // or the sigmoid half (r >= 2, + H).  w: [2H][K] in model row order, bias: [2H]
 template <typename T> void glu_pack_rows(const T *w, const float *bias, int H, size_t K, std::vector<float> &wp, std::vector<float> &bp);      // (model_synth.hip: float and double)
 // ... the map itself, both ways (H a multiple of 8): the packed row that holds model row m of [2H], and the model row packed row p holds.  glu_pack_rows

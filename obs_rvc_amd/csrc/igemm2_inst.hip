@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include "igemm_launch.h"
+#include "igemm2.hip.h"
 
 #ifndef RVC_IGEMM2_CFG
 #error "compile with -DRVC_IGEMM2_CFG=<0..4>"

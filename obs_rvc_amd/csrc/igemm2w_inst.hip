@@ -1,9 +1,10 @@
 // igemm2w_inst.hip (-DRVC_G2W_PART=0..2: one unit per wave tile, compiled in parallel) -- instantiations of igemm2w_kernel, the register-direct
-// 32x32x2 kernel of the table-free 1x1 layers at a few streams (igemm.hip.h): wave tiles 32 x 32, 64 x 32, 64 x 64, each with 1 / 2 / 3 / 4 / 6 / 8
+// 32x32x2 kernel of the table-free 1x1 layers at a few streams (igemm2w.hip.h): wave tiles 32 x 32, 64 x 32, 64 x 64, each with 1 / 2 / 3 / 4 / 6 / 8
 // waves per workgroup splitting K.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include "igemm_launch.h"
+#include "igemm2w.hip.h"
 
 #ifndef RVC_G2W_PART
 #define RVC_G2W_PART 0

@@ -6,7 +6,7 @@
 // a gather (stream, column) never changes and the row's offset is an SGPR, the weights the same; nphase == 1, so the descriptor is the kernel argument.
 // Anatomy, tile shapes, LDS layout ([2][BN][16 k + 4]), MFMA operand order and epilogue are igemm32_kernel's.
 #pragma once
-#include "igemm.hip.h"
+#include "igemm32.hip.h"          // (G32Occ: the occupancy rule per register tile is igemm32_kernel's)
 
 namespace rvc {
 

@@ -1,7 +1,8 @@
-// igemm_bf3_inst.hip -- instantiation of the exploratory split-bf16 GEMM (igemm_bf3_kernel, igemm.hip.h) and of its weight packer.
+// igemm_bf3_inst.hip -- instantiation of the exploratory split-bf16 GEMM (igemm_bf3_kernel, igemm_bf3.hip.h) and of its weight packer.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include "igemm_launch.h"
+#include "igemm_bf3.hip.h"
 
 namespace rvc {
 

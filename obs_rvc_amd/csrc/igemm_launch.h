@@ -1,7 +1,8 @@
 // igemm_launch.h -- host-side entry points of the implicit-GEMM kernel family.  The template instantiations are compiled in their
-// own translation units (igemm2_inst.hip once per tile configuration, igemm_tiled_inst.hip) so that the library builds in parallel.
+// own translation units (igemm2_inst.hip once per tile configuration, igemm_tiled_inst.hip, ...) so that the library builds in parallel; each
+// of them includes the header of the kernel it instantiates.  Here only what every caller needs: the parameter block (igemm_common.hip.h).
 #pragma once
-#include "igemm.hip.h"
+#include "igemm_common.hip.h"
 
 namespace rvc {
 
@@ -16,8 +17,9 @@ void launch_igemm2_cfg1(int ks, bool pre, bool lin, const IgemmP &p, dim3 grid, 
 void launch_igemm2_cfg2(int ks, bool pre, bool lin, const IgemmP &p, dim3 grid, size_t lds, hipStream_t s, hipEvent_t ea, hipEvent_t eb);
 void launch_igemm2_cfg3(int ks, bool pre, bool lin, const IgemmP &p, dim3 grid, size_t lds, hipStream_t s, hipEvent_t ea, hipEvent_t eb);
 void launch_igemm2_cfg4(int ks, bool pre, bool lin, const IgemmP &p, dim3 grid, size_t lds, hipStream_t s, hipEvent_t ea, hipEvent_t eb);
-// the first-generation kernel remains for the two-stage grid-level split-K (offset table too long for LDS): 16x16 tiles only
-void launch_igemm_v1(bool pre, const IgemmP &p, dim3 grid, hipStream_t s);
+// first stage of the two-stage grid-level split-K (offset table too long for LDS; igemm_splitk.hip.h): 16x16 tiles, partial sums into IgemmP::part.
+// grid = (tiles / 4, batch * nphase * ksplit); splitk_epilogue_kernel (plan_ops.hip.h) is the second stage
+void launch_igemm_splitk(bool pre, const IgemmP &p, dim3 grid, hipStream_t s);
 // workgroup-tiled throughput kernels: lc 0-2 / 6 = igemm_lds_kernel (128x128, 64x256, 32x256, 48x256), 3-5 / 7 / 8 = igemm32_kernel
 void launch_igemm_tiled(int lc, bool pre, const IgemmP &p, dim3 grid, size_t lds, hipStream_t s, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr);
 

@@ -1,8 +1,11 @@
-// igemm_tiled_inst.hip (-DRVC_TILED_PART=0..3: four units, compiled in parallel) -- the dispatcher over the five igemm2 tile configurations, the first-generation kernel (grid-level split-K
-// fallback) and the instantiations of the workgroup-tiled throughput kernels (igemm_lds_kernel, igemm32_kernel).
+// igemm_tiled_inst.hip (-DRVC_TILED_PART=0..3: four units, compiled in parallel) -- the dispatcher over the five igemm2 tile configurations, the first stage of the
+// two-stage grid-level split-K (igemm_splitk_kernel) and the instantiations of the workgroup-tiled throughput kernels (igemm_lds_kernel, igemm32_kernel).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include "igemm_launch.h"
+#include "igemm_lds.hip.h"
+#include "igemm32.hip.h"
+#include "igemm_splitk.hip.h"
 
 #ifndef RVC_TILED_PART
 #define RVC_TILED_PART 0
@@ -22,11 +25,11 @@ void launch_igemm2(int cfg, int ks, bool pre, bool lin, const IgemmP &p, dim3 gr
     }
 }
 
-void launch_igemm_v1(bool pre, const IgemmP &p, dim3 grid, hipStream_t s)
+void launch_igemm_splitk(bool pre, const IgemmP &p, dim3 grid, hipStream_t s)
 {
     const size_t lds = (size_t)p.chunks_per_split * 16 * sizeof(int);
-    if (pre) hipLaunchKernelGGL((igemm_kernel<1, 1, 12, 1, true>), grid, dim3(256), lds, s, p);
-    else hipLaunchKernelGGL((igemm_kernel<1, 1, 12, 1, false>), grid, dim3(256), lds, s, p);
+    if (pre) hipLaunchKernelGGL(igemm_splitk_kernel<true>, grid, dim3(256), lds, s, p);
+    else hipLaunchKernelGGL(igemm_splitk_kernel<false>, grid, dim3(256), lds, s, p);
 }
 
 void launch_igemm_tiled(int lc, bool pre, const IgemmP &p, dim3 grid, size_t lds, hipStream_t s, hipEvent_t ea, hipEvent_t eb)

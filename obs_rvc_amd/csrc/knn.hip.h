@@ -1,7 +1,7 @@
 // knn.hip.h -- the kernels of the flat-L2 retrieval: index layouts, the scan / merge pair, the one-launch scan + select, the matrix-core candidate search.
 // Included by retrieval.hip only (KNN_K: state.hip.h); ivf.hip.h builds on its distance and blend device functions.
 #pragma once
-#include "igemm.hip.h"
+#include "igemm_common.hip.h"
 #include "state.hip.h"
 #include "reduce.hip.h"
 

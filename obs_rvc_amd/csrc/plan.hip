@@ -261,12 +261,17 @@ void merge_convs(const std::vector<ConvW *> &cs)
     }
 }
 
-// (launch_igemm2 / launch_igemm_v1 / launch_igemm_tiled: igemm_launch.h -- the template instantiations are separate translation units)
+// (launch_igemm2 / launch_igemm_splitk / launch_igemm_tiled: igemm_launch.h -- the template instantiations are separate translation units)
 
 unsigned long long *g_kprobe = nullptr;   // tuning build (-DRVC_KPROBE): destination of the per-wave phase stamps
 int g_last_waves = 0, g_last_wgs = 0;
 thread_local char g_last_kernel[32] = "";
-static void note_kernel(const char *d) { size_t i = 0; for (; i < sizeof(g_last_kernel) - 1 && d[i] && d[i] != ' '; i++) g_last_kernel[i] = d[i]; g_last_kernel[i] = 0; }
+thread_local char g_last_desc[200] = "";
+static void note_kernel(const char *d)
+{
+    size_t i = 0; for (; i < sizeof(g_last_kernel) - 1 && d[i] && d[i] != ' '; i++) g_last_kernel[i] = d[i]; g_last_kernel[i] = 0;
+    snprintf(g_last_desc, sizeof g_last_desc, "%s", d);
+}
 
 // Every GEMM-class launch of the planner is queued here: its description (rvc_debug_profile_dump, rvc_debug_last_kernel), the plan's FLOP count, the
 // launch shape of the last queued kernel.  At run time the op takes a profile slot and hands `launch` the IgemmP to use: the plan's own, or -- final_out,
@@ -624,7 +629,7 @@ static void g2w_rule(const IgemmP &p, int nchunks, int &gt, int &gk)
     gt = 0; gk = g2w_ksplit(p.M, p.N, nchunks);
 }
 
-// igemm2w_kernel: register-direct 32x32x2 tiles for the table-free 1x1 layers at a few streams (igemm.hip.h).  Test hook RVC_FORCE_G2W = "tile,ks"
+// igemm2w_kernel: register-direct 32x32x2 tiles for the table-free 1x1 layers at a few streams (igemm2w.hip.h).  Test hook RVC_FORCE_G2W = "tile,ks"
 // (tile 0 = 32 x 32 per wave, 1 = 64 x 32, 2 = 64 x 64; ks = 1 / 2 / 3 / 4 / 6 / 8 waves splitting K) forces it wherever it is eligible.
 static bool queue_g2w(GemmCall &c, IgemmP p, int B)
 {
@@ -747,7 +752,7 @@ static bool queue_tiled(GemmCall &c, IgemmP p, int B)
     p.ksplit = 1; p.chunks_per_split = nchunks;
     p.ntm = (p.M + bm - 1) / bm; p.ntn = (p.N + bn - 1) / bn;
     // tile order of the tiled kernels when the streams are folded into N: m fastest over XCD-local tile ids (1), or over the raw block index (2)
-    // where that keeps a large weight matrix partitioned over the XCDs (igemm.hip.h, xcd_tile_id)
+    // where that keeps a large weight matrix partitioned over the XCDs (igemm_common.hip.h, xcd_tile_id)
     p.m_fast = p.fold_n ? ((p.ntm % 8 == 0 && (size_t)p.M * (size_t)c.ksum * sizeof(float) > ((size_t)4 << 20)) ? 2 : 1) : 0;
     dim3 grid(p.ntm * p.ntn, B * p.nphase);
     const bool g32k = lc >= 3 && lc != 6;            // igemm32_kernel keeps its activation tile column-major, [2][bn][20]
@@ -878,7 +883,7 @@ static void queue_reg(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &p
     dim3 grid(wg_ks > 1 ? ntiles : (ntiles + 3) / 4, B * p.nphase * ksplit);
     dim3 egrid((unsigned)(((long long)p.M * p.N + 255) / 256), B * p.nphase);
     // lean kernel: x = fast tile axis (m when m_fast, else n; 4 tiles per workgroup without the in-workgroup K split), y = slow axis
-    const bool lean = ksplit == 1 && !tune_env("RVC_OLD_IGEMM");
+    const bool lean = ksplit == 1;
     const bool lin = lean && p.lin_cs4 != 0 && p.nphase == 1 && !pre && !tune_env("RVC_NO_LIN");
     size_t lds2 = 0;
     if (lean) {
@@ -895,16 +900,16 @@ static void queue_reg(GemmCall &c, IgemmP p, int B, const std::vector<PhaseD> &p
         if (p.ln_wsum && !lin) throw std::logic_error("LayerNorm consumer did not get the table-free kernel");
     }
     char d[200];
-    snprintf(d, sizeof d, "reg M=%d N=%d K=%d B=%d nph=%d tile=%dx%d ks=%d mfast=%d grid=%ux%ux%u pre=%d lin=%d ksum=%.0f", p.M, p.N, p.K, B, p.nphase, 16 * kMF[cfg], 16 * kNF[cfg], wg_ks, p.m_fast, grid.x, grid.y, grid.z, (int)pre, (int)lin, c.ksum);
+    snprintf(d, sizeof d, "reg M=%d N=%d K=%d B=%d nph=%d tile=%dx%d ks=%d mfast=%d grid=%ux%ux%u pre=%d lin=%d ksum=%.0f split=%d", p.M, p.N, p.K, B, p.nphase, 16 * kMF[cfg], 16 * kNF[cfg], wg_ks, p.m_fast, grid.x, grid.y, grid.z, (int)pre, (int)lin, c.ksum, ksplit);
     // (the two-stage grid split-K fallback writes through a second kernel and keeps the plan's own tensor: final_out on the lean path only; it records
     //  the profile events around both of its launches)
     queue_gemm_launch(c.pl, d, 2.0 * p.M * (double)p.N * c.ksum * B, (int)(grid.x * grid.y * grid.z), wg_ks > 1 ? wg_ks : 4, c.final_out && lean, p,
                       [=](const IgemmP &q, hipEvent_t ea, hipEvent_t eb, hipStream_t s) {
                           if (lean) { launch_igemm2(cfg, wg_ks, pre, lin, q, grid, lds2, s, ea, eb); return; }
-                          if (ea && ksplit > 1) HIPCHK(hipEventRecord(ea, s));
-                          launch_igemm_v1(pre, q, grid, s);
-                          if (ksplit > 1) hipLaunchKernelGGL(splitk_epilogue_kernel, egrid, dim3(256), 0, s, q);
-                          if (eb && ksplit > 1) HIPCHK(hipEventRecord(eb, s));
+                          if (ea) HIPCHK(hipEventRecord(ea, s));
+                          launch_igemm_splitk(pre, q, grid, s);
+                          hipLaunchKernelGGL(splitk_epilogue_kernel, egrid, dim3(256), 0, s, q);
+                          if (eb) HIPCHK(hipEventRecord(eb, s));
                       });
     c.built = Choice{4, cfg, wg_ks};
 }

@@ -1,7 +1,7 @@
-// plan_ops.hip.h -- the kernels plan.hip launches besides the implicit-GEMM family (igemm.hip.h): the second stage of a split-K launch, LayerNorm,
+// plan_ops.hip.h -- the kernels plan.hip launches besides the implicit-GEMM family (igemm*.hip.h): the second stage of a split-K launch, LayerNorm,
 // attention (plain and relative-position), the GRU recurrence and the timeline stamp.  Included by plan.hip only.
 #pragma once
-#include "igemm.hip.h"
+#include "igemm_common.hip.h"
 #include "state.hip.h"
 #include "reduce.hip.h"
 

@@ -16,7 +16,7 @@
 // is a ds_read_b32 from the staged tile: lane (column li, k-slot kq) reads channel 4 c4 + kq at pixel(li) + tap offset.  The four waves split M first
 // (Cout / 16 panels: the weight stream is then read once per workgroup) and N second.
 #pragma once
-#include "igemm.hip.h"
+#include "igemm_common.hip.h"
 
 namespace rvc {
 

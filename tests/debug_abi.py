@@ -68,6 +68,7 @@ def lib():
     L.rvc_debug_conv_check.argtypes = L.rvc_debug_conv2d_check.argtypes = [vp] + [C.c_int] * 7
     L.rvc_debug_conv_check.restype = L.rvc_debug_conv2d_check.restype = C.c_double
     L.rvc_debug_last_kernel.restype = C.c_char_p
+    L.rvc_debug_last_desc.restype = C.c_char_p
     L.rvc_debug_tap.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rvc_debug_tap.restype = C.c_int
     return L
@@ -90,6 +91,10 @@ class Handle:
 
     def last_kernel(self):
         return self.L.rvc_debug_last_kernel().decode()
+
+    def last_desc(self):
+        """the whole description of the last implicit-GEMM launch queued: "reg M=.. N=.. K=.. ... split=2" """
+        return self.L.rvc_debug_last_desc().decode()
 
     def last_error(self):
         return self.L.rvc_last_error_message(self.h).decode()

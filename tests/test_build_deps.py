@@ -73,7 +73,7 @@ def test_every_plain_kernel_has_one_home():
     for f, k in (("plan_ops.hip.h", "gru_multi_kernel"), ("knn.hip.h", "knn_scan_select_kernel"), ("igemm_bf3_inst.hip", "bf3_pack_kernel"),
                  ("protect.hip.h", "protect_mix_kernel"), ("synth.hip.h", "formant_resample_kernel"), ("chunk.hip.h", "post_sola_kernel")):
         assert k in holders.get(f, ()), (f, k)
-    assert not any("layernorm_ct_kernel" in v or "igemm_kernel" in v for v in holders.values())      # templates are not counted
+    assert not any("layernorm_ct_kernel" in v or "igemm_splitk_kernel" in v for v in holders.values())      # templates are not counted
     units = {(src, tuple(flags)): set(deps) for src, flags, deps in _native.UNITS}
     for f, names in holders.items():
         owners = [u for u, deps in units.items() if f in deps]
@@ -85,3 +85,33 @@ def test_every_plain_kernel_has_one_home():
             seen[k] = f
     shared = set(_native._include_closure("engine_int.h")) & set(holders)
     assert not shared, "engine_int.h reaches headers that define kernels: %s" % sorted(shared)
+
+
+# one header per kernel of the implicit-GEMM family (igemm_common.hip.h holds what they share and defines no kernel)
+KERNEL_HEADERS = {"igemm2.hip.h", "igemm2w.hip.h", "igemm_lds.hip.h", "igemm32.hip.h", "igemm_bf3.hip.h", "igemm_splitk.hip.h"}
+# the kernel headers each unit may reach: what it instantiates (igemm32l borrows igemm32_kernel's occupancy rule); every unit not listed reaches none
+EXPECTED_KERNEL_HEADERS = {"igemm2_inst.hip": {"igemm2.hip.h"}, "igemm2w_inst.hip": {"igemm2w.hip.h"}, "igemm_bf3_inst.hip": {"igemm_bf3.hip.h"},
+                           "igemm_tiled_inst.hip": {"igemm_lds.hip.h", "igemm32.hip.h", "igemm_splitk.hip.h"}, "igemm32l_inst.hip": {"igemm32.hip.h"}}
+ENGINE_UNITS = ("engine.hip", "retrieval.hip", "calib.hip", "debug.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "model_crepe.hip",
+                "model_fcpe.hip", "model_synth.hip")
+
+
+def test_every_unit_reaches_only_the_kernel_headers_it_instantiates():
+    assert not os.path.exists(os.path.join(_native.CSRC, "igemm.hip.h"))          # no umbrella header: it would put the whole closure back
+    assert all(os.path.exists(os.path.join(_native.CSRC, h)) for h in KERNEL_HEADERS | {"igemm_common.hip.h"})
+    srcs = {src for src, _, _ in _native.UNITS}
+    assert set(EXPECTED_KERNEL_HEADERS) <= srcs and set(ENGINE_UNITS) <= srcs and {s for s in srcs if s.startswith("model_")} <= set(ENGINE_UNITS)
+    for src, flags, deps in _native.UNITS:
+        assert set(deps) & KERNEL_HEADERS == EXPECTED_KERNEL_HEADERS.get(src, set()), (src, flags, sorted(set(deps) & KERNEL_HEADERS))
+    for src in ENGINE_UNITS:          # the engine, the planner, the plan builders, retrieval, the calibration and the test hooks launch through igemm_launch.h alone
+        assert EXPECTED_KERNEL_HEADERS.get(src, set()) == set()
+
+
+def test_an_edit_to_one_kernel_header_rebuilds_only_its_units():
+    # the object cache is keyed on a unit's flags and the contents of its closure (_native._unit_key): a unit's key changes with a file iff the file is in the closure
+    def touched(header):
+        return {src for src, _, deps in _native.UNITS if header in deps}
+    assert touched("igemm32.hip.h") == {"igemm_tiled_inst.hip", "igemm32l_inst.hip"}
+    assert touched("igemm2.hip.h") == {"igemm2_inst.hip"} and touched("igemm2w.hip.h") == {"igemm2w_inst.hip"} and touched("igemm_bf3.hip.h") == {"igemm_bf3_inst.hip"}
+    assert touched("igemm_lds.hip.h") == touched("igemm_splitk.hip.h") == {"igemm_tiled_inst.hip"}
+    assert touched("igemm_common.hip.h") >= set(ENGINE_UNITS) - {"calib.hip"}

@@ -115,7 +115,14 @@ CASES = [
     Case("knn_bcast_res", "retrieval.hip:104 (broadcast residual, scale -2, no bias)", cin=768, cout=48, t_in=1001, t_out=1001, res=2, scale=-2.0,
          no_bias=1),
     Case("cnn_transposed", "model_rmvpe.hip:218 (Conv2d 3x3, output transposed)", form=4, cin=16, cout=3, t_in=37, t_out=128, y_ws=1),
+    # K = 16384: the offset table (64 KiB) exceeds the 60 KiB of LDS the kernels give it, so the layer runs as two grid-level K splits of 512 chunks whose
+    # partial sums splitk_epilogue_kernel finishes (plan.hip queue_reg).  M = 20 leaves a partial second row of 16 x 16 tiles, N = 37 a partial third column.
+    Case("splitk", "model_crepe.hip (long-K layers: table too long for LDS, two-stage split-K)", streams=(1, 3), cin=1024, cout=20, kw=16, pad=8, t_in=37,
+         t_out=37, x_halo=8),
+    Case("splitk_pre_res_acc", "model_crepe.hip (the same, fused input LeakyReLU and every term of the second stage's epilogue)", streams=(1, 3), cin=1024,
+         cout=20, kw=16, pad=8, t_in=37, t_out=37, x_halo=8, r_halo=4, pre_act=LR, pre_slope=0.1, res=1, accumulate=1, scale=1.0 / 3, act=LR, slope=0.1),
 ]
+SPLITK = [c for c in CASES if c.name.startswith("splitk")]
 # full-length production shapes, under the rules only
 FULL = [
     Case("full_stem_gelu", "model_cv.hip:51-53", streams=(1, 64), cin=512, cout=512, kw=3, stride=2, t_in=447, t_out=223, act=R.ACT_GELU),
@@ -292,6 +299,7 @@ class Layer(Handle):
         if rc != 0:
             return "?", ["rvc_debug_layer failed (%d): %s" % (rc, self.last_error())]
         fam = self.last_kernel()
+        self.outputs = [y[yi] for yi in yidx]          # (the interiors of this run's output tensors, for the tests that compare bits)
         bad = []
         if not same_bits(x, x0):
             bad.append("input tensor changed at %d positions" % int(np.count_nonzero(x.view(np.uint32) != x0.view(np.uint32))))
@@ -370,6 +378,12 @@ def runs_of(case):
 # Never: strided layers on tile / c32s (the stem, the noise convs), the polyphase transposed conv on tile / c32s (its table walks taps backwards, its
 # output columns are strided), the pair launch (per-phase activation and output tensor) and the gated in-layer on anything but reg; the 1-row
 # weight panel of the decoder's last layer on the tiled kernels (fewer than 17 rows); the RMVPE head (3 rows, 2-D) on anything but reg.
+# K = 16384 (splitk*): the offset table is 64 KiB, over the 60 KiB every family that keeps it in LDS allows -- g32 / g32t / lds (queue_tiled), every tile and K
+# split of reg (queue_reg fits(): no RVC_FORCE_CFG run, and a forced choice 4,cfg,ks falls back to the rules), and the streams are not folded into N.  What is
+# left under the rules, at every stream count, is reg's two-stage grid-level split-K (16 x 16 tiles, partial sums, splitk_epilogue_kernel; the batch stays a
+# grid dimension): the forced-choice runs at 6 and 20 streams land there too, except the conv32s choices (1,*,*), which take the layer -- a stride-1 1-D
+# convolution of 1024 = 32 x 32 channels with a tap reach of 15, no table in LDS -- as does RVC_CONV32S = 2 at one stream.  conv_tile declines: its staged rows
+# (1024 channels x 79 columns) need 316 KB of LDS.  That the rules' runs really are the two-stage path is asserted in test_long_k_layer_runs_the_two_stage_split_k.
 _STRIDED_TAB = {"reg", "g32", "g32t"}
 _TAPS = {"reg", "g32", "g32t", "tile", "c32s"}
 _ONE_BY_ONE = {"reg", "g32", "g32l", "g2w", "c32s"}
@@ -380,7 +394,7 @@ EXPECTED = dict(
      "noise_sf12": _STRIDED_TAB, "pos_T48": {"reg", "tile"}, "pos_T37": {"reg", "tile"}, "pair": {"reg"}, "pair_T37": {"reg"}, "glu": {"reg"},
      "glu_composed": {"reg"}, "rs_accumulate": _ONE_BY_ONE, "post_scale_m1": _ONE_BY_ONE, "rb_mean_first": _TAPS, "rb_mean_acc": _TAPS, "ff1_relu": _TAPS,
      "ff2_res_self": _TAPS - {"tile"}, "dec_post_tanh": {"reg", "tile", "c32s"}, "fc_sigmoid": _ONE_BY_ONE, "cv_ff1_gelu": _ONE_BY_ONE | {"lds"},
-     "knn_bcast_res": _ONE_BY_ONE, "cnn_transposed": {"reg"}},
+     "knn_bcast_res": _ONE_BY_ONE, "cnn_transposed": {"reg"}, "splitk": {"reg", "c32s"}, "splitk_pre_res_acc": {"reg", "c32s"}},
     **{c.name: {"reg", "g32"} if c.p["cout"] > 16 else {"reg"} for c in CASES if c.p["form"] == 1},
     **{c.name: {"reg", "g32", "tile", "c32s"} if c.p["cout"] > 16 else {"reg"} for c in CASES if c.p["form"] == 2})
 
@@ -411,3 +425,17 @@ def test_layer_form(layer, case):
 def test_full_length_layer_under_the_rules(layer, case):
     seen, fails = _check(layer, case, [("rules", s, {}) for s in case.streams])
     assert not fails, "%s (%s):\n  %s" % (case.name, case.site, "\n  ".join(fails))
+
+
+@pytest.mark.parametrize("case", SPLITK, ids=lambda c: c.name)
+def test_long_k_layer_runs_the_two_stage_split_k(layer, case):
+    """Under the rules a layer whose offset table cannot fit in LDS is the register-direct family's grid-level split-K: the launch description says how many
+    K splits wrote partial sums ("split=2": 1024 chunks in two slices of 512), on 16 x 16 tiles without the in-workgroup K split.  Values, stray writes: as
+    every run.  The CRC32 of the output is printed: the path sums K in a fixed order, so the same library gives the same bits on every run."""
+    for streams in case.streams:
+        fam, bad = layer.run(case, streams)
+        desc = layer.last_desc()
+        print("%s @ %d streams: crc32 %08x  [%s]" % (case.name, streams, zlib.crc32(np.ascontiguousarray(layer.outputs[0]).tobytes()), desc))
+        assert not bad, (case.name, streams, bad)
+        f = dict(w.split("=", 1) for w in desc.split()[1:] if "=" in w)
+        assert fam == "reg" and f["split"] == "2" and f["tile"] == "16x16" and f["ks"] == "1" and f["B"] == str(streams) and f["K"] == "16384", desc
