@@ -45,6 +45,9 @@ pub const RVC_F0_YIN: c_int = 2;
 pub const RVC_F0_CREPE: c_int = 4;
 pub const RVC_F0_CREPE_TINY: c_int = 5;
 pub const RVC_F0_FCPE: c_int = 7;
+pub const RVC_F0_HYBRID: c_int = 8;
+pub const RVC_HYBRID_VOTE: c_int = 0;
+pub const RVC_HYBRID_MEDIAN: c_int = 1;
 pub const RVC_CREPE_VITERBI: c_int = 0;
 pub const RVC_CREPE_ARGMAX: c_int = 1;
 pub const RVC_DENOISE_INPUT: c_int = 0;
@@ -80,6 +83,9 @@ extern "C" {
     // ---- FCPE (RVC_F0_FCPE: <data>/f0/fcpe.rvcw): its voicing threshold in [0, 1), default 0.006
     pub fn rvc_set_fcpe_threshold(e: *mut RvcEngine, threshold: c_double) -> c_int;
     pub fn rvc_fcpe_threshold(e: *mut RvcEngine) -> c_double;
+    // ---- hybrid f0 (RVC_F0_HYBRID): 1 to 4 distinct members, the first the lead, combined per frame under RVC_HYBRID_VOTE (default) or RVC_HYBRID_MEDIAN
+    pub fn rvc_load_f0_hybrid(e: *mut RvcEngine, methods: *const c_int, n: c_int, mode: c_int) -> c_int;
+    pub fn rvc_f0_hybrid(e: *mut RvcEngine, methods: *mut c_int, cap: c_int, mode: *mut c_int) -> c_int;
 
     // ---- retrieval index, noise seed, state
     pub fn rvc_load_index(e: *mut RvcEngine, vectors: *const c_float, n: usize, dim: usize) -> c_int;

@@ -133,6 +133,23 @@ impl RvcInfer {
         unsafe { ffi::rvc_fcpe_threshold(self.handle) }
     }
 
+    /// Not in the reference: hybrid f0 -- 1 to 4 distinct members (`ffi::RVC_F0_RMVPE`, `_YIN`, `_CREPE`, `_CREPE_TINY`, `_FCPE`), the first the lead, run on
+    /// the same audio and combined per frame under `ffi::RVC_HYBRID_VOTE` (majority voicing, median of the voiced values) or `ffi::RVC_HYBRID_MEDIAN`
+    /// (the forks' plain median).  All or nothing: on an error the method in force stays.  (Written without a Rust toolchain at hand, like the rest of this shim.)
+    pub fn load_f0_hybrid(&mut self, methods: &[i32], mode: i32) -> Result<(), BackendError> {
+        self.check_load(unsafe { ffi::rvc_load_f0_hybrid(self.handle, methods.as_ptr(), methods.len() as i32, mode) })
+    }
+
+    /// Not in the reference: the members (the lead first) and the mode of the hybrid in force, `None` when the method is no hybrid
+    pub fn f0_hybrid(&self) -> Option<(Vec<i32>, i32)> {
+        let (mut m, mut mode) = ([0i32; 4], 0i32);
+        let n = unsafe { ffi::rvc_f0_hybrid(self.handle, m.as_mut_ptr(), 4, &mut mode) };
+        if n <= 0 {
+            return None;
+        }
+        Some((m[..(n as usize).min(4)].to_vec(), mode))
+    }
+
     /// rvc.rs:77-79
     pub fn unload_model(&mut self) {
         unsafe { ffi::rvc_unload_model(self.handle) }

@@ -107,6 +107,26 @@ int rvc_crepe_decoder(rvc_engine *e);
  * may be changed between calls and holds from the next call on (part of an FCPE plan's identity); values outside [0, 1) and NaN: RVC_SHAPE. */
 rvc_status rvc_set_fcpe_threshold(rvc_engine *e, double threshold);
 double rvc_fcpe_threshold(rvc_engine *e);
+/* Hybrid f0 (the forks' `hybrid[rmvpe+fcpe]`; DESIGN.md "Hybrid f0"): 1 to 4 distinct members out of the five methods above run on the same audio, one after
+ * another on the f0 branch, and their unshifted f0 rows are combined per stream and frame; the combined row takes the pitch tail every method takes (shift, pitch
+ * controls, cache, get_f0_post).  methods[0] is the LEAD.  A member is voiced on a frame iff its value is > 0.  With n members of which v are voiced:
+ *   RVC_HYBRID_VOTE   (the default of the front ends) voiced iff 2 v > n, or 2 v == n and the lead is voiced; an unvoiced frame gives 0, a voiced one the median
+ *                     of the v voiced values
+ *   RVC_HYBRID_MEDIAN the median of all n values, unvoiced ones entering as 0: the forks' plain median, kept for parity -- it halves f0 where two members
+ *                     disagree on voicing, which is why it is not the default
+ * (median of an even count: 0.5f * (a + b) of the two middle values).  A hybrid of one member is that method, bit for bit.  Each member keeps its engine-wide
+ * settings (rvc_set_crepe_decoder, rvc_set_fcpe_threshold, RMVPE's 0.03) and its own limits and refusals (CREPE: streams x frames <= 65535).
+ * rvc_load_f0_hybrid loads every member as rvc_load_f0_method would (same files, read once and kept where that holds) and makes the hybrid the engine's method:
+ * rvc_f0_method then returns RVC_F0_HYBRID; rvc_load_f0_method / rvc_load_f0 go back to a single method.  All or nothing: a member's missing file (RVC_BACKEND),
+ * n outside 1..4, a repeated member, a value that is no single method, a mode other than 0 / 1 (RVC_SHAPE with a message) leave the method, the members and the
+ * loaded weights as they were.  rvc_load_f0_method(e, RVC_F0_HYBRID) is RVC_SHAPE: it names no members.  Engine-wide, part of a plan's identity (the ordered
+ * members and the mode).  rvc_f0_hybrid writes the members in order (at most cap) and the mode (either pointer may be null) and returns n, 0 when the
+ * method is no hybrid. */
+#define RVC_F0_HYBRID 8
+#define RVC_HYBRID_VOTE   0
+#define RVC_HYBRID_MEDIAN 1
+rvc_status rvc_load_f0_hybrid(rvc_engine *e, const int *methods, int n, int mode);
+int rvc_f0_hybrid(rvc_engine *e, int *methods, int cap, int *mode);
 /* Models trained without pitch guidance (upstream's SynthesizerTrnMs{256,768}NSFsid_nono, `f0: 0` in the checkpoint; blob config key f0 = 0; DESIGN.md
  * section 22): 1 = the loaded model has pitch guidance, 0 = it has none, -1 = no model loaded.  On a no-f0 model no call of the infer family (rvc_infer*,
  * rvc_session_process, rvc_convert*, rvc_convert_file*) needs an f0 method or runs one that is loaded: pitch_shift / has_pitch_shift, the pitch controls

@@ -125,6 +125,13 @@ int rvc_debug_fcpe_decode(rvc_engine *e, const float *prob, int B, int Tm, float
 /* fcpe_glu_dw_silu_kernel alone, launched as an FCPE plan launches it, on contiguous arrays: z [B][2 I][T] (value rows, then gate rows), w [I][31], bias [I]
  * -> y_out [B][I][T] = silu(bias + depthwise31(z[:I] * sigmoid(z[I:])), zero padding 15).  B in [1, 64], I and T in [1, 4096].  0 = done, else an rvc_status. */
 int rvc_debug_fcpe_dw(rvc_engine *e, const float *z, const float *w, const float *bias, int B, int I, int T, float *y_out);
+/* f0_hybrid_kernel alone (obs_rvc_amd/csrc/f0_hybrid.hip.h; DESIGN.md "Hybrid f0"), launched as a hybrid plan launches it, on the caller's member rows
+ * rows [n][B][Tm] (Hz, lead first; mode RVC_HYBRID_VOTE / RVC_HYBRID_MEDIAN) -> out [B][Tm], the row a plan hands to the pitch tail.  sal (may be NULL): a salience
+ * [B][360][Tm] that the launch decodes as RMVPE's in place of member rm_at (rows[rm_at] is then not read; rm_f0_out [B][Tm], may be NULL, gets the decoded row);
+ * with sal NULL rm_at must be -1.  ms_out (may be NULL): the launch's time between two HIP events.  Reads no weights and no state but the status word of streams
+ * 0 .. B - 1 (a decode that runs off the salience raises ST_PANIC there, as in a plan).  n in [1, 4], B in [1, the engine's streams], Tm in [1, 1024] (RVC_SHAPE
+ * otherwise).  0 = done, else an rvc_status. */
+int rvc_debug_f0_hybrid(rvc_engine *e, const float *rows, int n, int B, int Tm, int mode, const float *sal, int rm_at, float *out, float *rm_f0_out, float *ms_out);
 /* the caller-side post-processing, the session's ring updates and a converter of several streams (obs_rvc_amd/csrc/chunk.hip.h, session.hip.h, resample.hip.h;
  * DESIGN.md "Post-processing and resamplers: what is tested"), each launch queued as rvc_session_process queues it, on the caller's arrays with the caller's
  * stream strides.  op: buffers buf[0..3] (each the WHOLE allocation, [streams][stride] floats, uploaded before the launches and downloaded after them: the

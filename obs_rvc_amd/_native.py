@@ -28,6 +28,7 @@ SYMBOLS = [
     "rvc_session_create", "rvc_session_destroy", "rvc_session_process", "rvc_session_frame_size", "rvc_session_set_params", "rvc_session_set_params_stream", "rvc_session_geometry",
     "rvc_set_formant_shift", "rvc_set_formant_shift_stream", "rvc_formant_geometry",
     "rvc_load_f0_method", "rvc_f0_method", "rvc_set_crepe_decoder", "rvc_crepe_decoder", "rvc_model_has_f0", "rvc_set_fcpe_threshold", "rvc_fcpe_threshold",
+    "rvc_load_f0_hybrid", "rvc_f0_hybrid",
     "rvc_set_pitch_semitones", "rvc_set_pitch_semitones_stream", "rvc_set_f0_range", "rvc_set_f0_range_stream",
     "rvc_set_f0_median", "rvc_set_f0_median_stream", "rvc_set_f0_snap", "rvc_set_f0_snap_stream",
     "rvc_set_protect", "rvc_set_protect_stream",
@@ -373,6 +374,10 @@ def lib():
         L.rvc_fcpe_threshold.restype = C.c_double
         L.rvc_debug_fcpe_decode.argtypes = [vp, fp, C.c_int, C.c_int, fp, vp]
         L.rvc_debug_fcpe_dw.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp]
+    if hasattr(L, "rvc_load_f0_hybrid") or not override:
+        L.rvc_load_f0_hybrid.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.c_int]
+        L.rvc_f0_hybrid.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+        L.rvc_debug_f0_hybrid.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, fp, fp]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
     if hasattr(L, "rvc_model_speakers") or not override:

@@ -1,4 +1,4 @@
-"""python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny|fcpe] [--index I --index-rate r --index-k 4|8 --nprobe p]
+"""python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny|fcpe|"hybrid[a+b..]" --f0-hybrid-mode vote|median] [--index I --index-rate r --index-k 4|8 --nprobe p]
        [--pitch semitones] [--formant st] [--protect p] [--streams S] [--window k --context C --crossfade X] [--no-highpass] [--rate out_rate]
        [--rms-mix-rate r] [--resampler blocks|device] [--sid N | --sid-mix 0:0.3,2:0.7]
 
@@ -26,8 +26,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--model", required=True, help="the voice: <model>.rvcw (or its .onnx sibling's name)")
     p.add_argument("--data", default=None, help="the engine's data directory (contentvec/, f0/); default: the model zoo of the package")
     p.add_argument("--version", type=int, choices=(1, 2), default=2, help="RVC model version: 1 = 256-dim features, 2 = 768-dim (default)")
-    p.add_argument("--f0", choices=("rmvpe", "yin", "crepe-full", "crepe-tiny", "fcpe"), default="rmvpe",
-                   help="f0 method (default rmvpe; not loaded for a model without pitch guidance); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw; fcpe reads <data>/f0/fcpe.rvcw")
+    p.add_argument("--f0", type=f0_arg, default="rmvpe", metavar="{%s,hybrid[a+b..]}" % ",".join(F0_CHOICES),
+                   help="f0 method (default rmvpe; not loaded for a model without pitch guidance); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw; fcpe reads <data>/f0/fcpe.rvcw; "
+                        "hybrid[rmvpe+fcpe] (quote it) runs 1 to 4 of them and combines their answers per frame, the first member breaking ties")
+    p.add_argument("--f0-hybrid-mode", choices=("vote", "median"), default="vote",
+                   help="how a hybrid combines: vote = majority voicing, median of the voiced values (default); median = plain median with unvoiced members as 0 (the forks')")
     p.add_argument("--index", default=None, help="retrieval index: a Faiss .index file or a .npy matrix")
     p.add_argument("--index-rate", type=float, default=0.75, help="share of the retrieved features (default 0.75, with --index only)")
     p.add_argument("--index-k", type=int, choices=(4, 8), default=8, help="neighbours blended per frame (default 8, upstream's)")
@@ -80,6 +83,23 @@ def parse_args(argv=None) -> argparse.Namespace:
     if a.rate < 0 or a.rate % 100:
         p.error("--rate is a multiple of 100")
     return a
+
+
+F0_CHOICES = ("rmvpe", "yin", "crepe-full", "crepe-tiny", "fcpe")
+
+
+def f0_arg(text: str) -> str:
+    """--f0: one of F0_CHOICES, or the forks' hybrid[a+b+..] of 1 to 4 distinct ones (-> lower case, blanks removed); anything else is refused"""
+    from .rvc_common import parse_f0_hybrid
+    try:
+        members = parse_f0_hybrid(text, F0_CHOICES)
+    except ValueError as x:
+        raise argparse.ArgumentTypeError(str(x))
+    if members is not None:
+        return "hybrid[%s]" % "+".join(members)
+    if text not in F0_CHOICES:
+        raise argparse.ArgumentTypeError("invalid choice: %r (choose from %s, or hybrid[a+b..])" % (text, ", ".join(F0_CHOICES)))
+    return text
 
 
 def parse_sid_mix(text: str) -> dict:
@@ -143,7 +163,10 @@ def main(argv=None) -> int:
     eng.load_contentvec(a.version)
     eng.load_model(a.model)
     if eng.model_has_f0():      # (a model trained without pitch guidance runs no tracker: --f0 names none for it)
-        eng.load_f0_method(a.f0)
+        if a.f0.startswith("hybrid["):
+            eng.load_f0_hybrid(a.f0[len("hybrid["):-1].split("+"), mode=a.f0_hybrid_mode)
+        else:
+            eng.load_f0_method(a.f0)
     eng.set_streams(a.streams)
     if a.sid is not None:
         eng.set_speaker(a.sid)

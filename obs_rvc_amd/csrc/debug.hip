@@ -662,6 +662,35 @@ int rvc_debug_fcpe_dw(rvc_engine *e, const float *z, const float *w, const float
     });
 }
 
+// test aid: the hybrid-f0 launch alone (f0_hybrid.hip.h; tests/test_gpu_f0_hybrid.py) on the caller's member rows [n][B][Tm] and, optionally, a salience
+// [B][360][Tm] decoded in place of member rm_at, through the launch a plan uses (launch_f0_hybrid)
+int rvc_debug_f0_hybrid(rvc_engine *e, const float *rows, int n, int B, int Tm, int mode, const float *sal, int rm_at, float *out, float *rm_f0_out, float *ms_out)
+{
+    return (int)guarded(e, [&]() {
+        if (!rows || !out || n < 1 || n > HYBRID_MEMBERS_MAX || B < 1 || B > e->n_streams || Tm < 1 || Tm > 1024 || (mode != 0 && mode != 1) ||
+            (sal ? (rm_at < 0 || rm_at >= n) : rm_at != -1))
+            throw ShapeError("f0 hybrid: n in [1, 4], B in [1, streams], Tm in [1, 1024], mode 0 or 1, rm_at in [0, n) with a salience and -1 without");
+        const size_t bt = (size_t)B * Tm;
+        DevBuf<float> d_rows, d_sal, d_out, d_rm;
+        d_rows.alloc((size_t)n * bt); d_out.alloc(bt); d_rm.alloc(bt);
+        HIPCHK(hipMemcpy(d_rows.get(), rows, (size_t)n * bt * sizeof(float), hipMemcpyHostToDevice));
+        if (sal) { d_sal.alloc(bt * 360); HIPCHK(hipMemcpy(d_sal.get(), sal, bt * 360 * sizeof(float), hipMemcpyHostToDevice)); }
+        const float *rp[HYBRID_MEMBERS_MAX] = {};
+        for (int i = 0; i < n; i++) rp[i] = d_rows.get() + (size_t)i * bt;
+        DevTimer tm;
+        HIPCHK(hipDeviceSynchronize());
+        tm.start(e->stream);
+        launch_f0_hybrid(e->stream, B, Tm, n, mode, rp, rm_at, sal ? d_sal.get() : nullptr, Tm, 360LL * Tm, e->d_state, d_rm.get(), d_out.get());
+        tm.stop(e->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (ms_out) *ms_out = tm.ms();
+        HIPCHK(hipMemcpy(out, d_out.get(), bt * sizeof(float), hipMemcpyDeviceToHost));
+        if (rm_f0_out && sal) HIPCHK(hipMemcpy(rm_f0_out, d_rm.get(), bt * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
 // test aid: the caller-side post-processing, the session's ring updates and a converter of several streams (chunk.hip.h, session.hip.h, resample.hip.h;
 // tests/test_gpu_post.py) on the caller's arrays with the caller's stream strides, each launch queued as the session queues it (engine_int.h launch_post_* /
 // launch_ring_* / launch_resampler).  Every size is checked against the strides on the host before anything is queued.

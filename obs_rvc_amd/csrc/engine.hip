@@ -224,8 +224,8 @@ static void alloc_state(rvc_engine *e)
 
 // ------------------------------- plan -------------------------------------------------
 static inline bool is_crepe(int method) { return method == RVC_F0_CREPE || method == RVC_F0_CREPE_TINY; }
-// the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, CREPE's or FCPE's network and decoder; behind each the same pitch tail
-// (shift, cache, get_f0_post)
+// the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, CREPE's or FCPE's network and decoder, or -- a hybrid -- several of
+// them and the launch that combines their rows; behind each the same pitch tail (shift, cache, get_f0_post)
 static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache, size_t hubert_length, float **pitchf_out, int **pitch_out)
 {
     if (e->f0_method == RVC_F0_YIN) {
@@ -233,8 +233,29 @@ static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, 
         build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
         return;
     }
+    if (e->f0_method == RVC_F0_HYBRID) {
+        // hybrid: the members' own builders one after another on this branch's stream -- no further stream, fork or join --, then one
+        // launch that decodes RMVPE's salience (if a member) and combines the rows, and the pitch tail on the combined row as on any f0_in
+        int mem[HYBRID_MEMBERS_MAX]; const int n = hybrid_unpack(pl.key.hybrid, mem);
+        if (n < 1) throw std::logic_error("f0 method");
+        const float *rows[HYBRID_MEMBERS_MAX] = {}; int rm_at = -1; T1 sal;
+        bool both_crepe = false;
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) both_crepe = both_crepe || (mem[i] == RVC_F0_CREPE && mem[j] == RVC_F0_CREPE_TINY);
+        for (int i = 0; i < n; i++) {
+            if (mem[i] == RVC_F0_RMVPE) {
+                if (!e->rm) throw std::logic_error("f0 method");
+                sal = build_rmvpe(e, pl, B, L, frame16k, update_cache); rm_at = i;
+            } else if (mem[i] == RVC_F0_YIN) rows[i] = build_yin(e, pl, B, L, frame16k);
+            else if (is_crepe(mem[i])) rows[i] = build_crepe(e, pl, B, L, frame16k, mem[i], both_crepe && mem[i] == RVC_F0_CREPE_TINY ? "crt" : "cr");
+            else if (mem[i] == RVC_F0_FCPE) rows[i] = build_fcpe(e, pl, B, L, frame16k);
+            else throw std::logic_error("f0 method");
+        }
+        const float *f0 = add_f0_hybrid(e, pl, B, n, pl.key.hybrid_mode, rows, rm_at, sal);
+        build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
+        return;
+    }
     if (is_crepe(e->f0_method)) {
-        const float *f0 = build_crepe(e, pl, B, L, frame16k);
+        const float *f0 = build_crepe(e, pl, B, L, frame16k, e->f0_method);
         build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
         return;
     }
@@ -541,8 +562,14 @@ static PlanKey plan_key(rvc_engine *e, int mode, size_t L, size_t frame16k, uint
     // engine's f0 method and CREPE decoder are no part of such a plan's key; the hubert and pitch plans keep theirs
     const bool nof0 = mode == 0 && e->sy && !e->sy->has_f0;
     k.f0_method = nof0 ? 0 : e->f0_method;
-    k.crepe_decoder = !nof0 && is_crepe(e->f0_method) ? e->crepe_decoder : 0;
-    k.fcpe_threshold = k.f0_method == RVC_F0_FCPE ? e->fcpe_threshold : 0.0;          // FCPE's voicing threshold is baked into its decoder's launch
+    // a hybrid (rvc_load_f0_hybrid): the ordered members and the mode, and a member's setting where that member is present
+    bool has_crepe = is_crepe(k.f0_method), has_fcpe = k.f0_method == RVC_F0_FCPE;
+    if (k.f0_method == RVC_F0_HYBRID) {
+        k.hybrid = hybrid_pack(e->hybrid_m, e->hybrid_n); k.hybrid_mode = e->hybrid_mode;
+        for (int i = 0; i < e->hybrid_n; i++) { has_crepe = has_crepe || is_crepe(e->hybrid_m[i]); has_fcpe = has_fcpe || e->hybrid_m[i] == RVC_F0_FCPE; }
+    }
+    k.crepe_decoder = has_crepe ? e->crepe_decoder : 0;
+    k.fcpe_threshold = has_fcpe ? e->fcpe_threshold : 0.0;          // FCPE's voicing threshold is baked into its decoder's launch
     k.with_index = mode == 0 && e->index.rows && e->index_rate > 0.f;
     // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams has it on.  Which value
     // a stream has is no part of the key: the kernel reads it every chunk.  (Upstream applies protect only where it has a pitch)
@@ -825,7 +852,7 @@ rvc_status rvc_load_f0(rvc_engine *e, int pitch_algorithm)
         Blob b(e->data_path + "/f0/rmvpe.rvcw");
         drop_plans(e);
         e->rm.reset(new ModelRM(b));
-        e->f0_method = RVC_F0_RMVPE;
+        e->f0_method = RVC_F0_RMVPE; e->hybrid_n = 0;
         return RVC_OK;
     });
 }
@@ -842,18 +869,58 @@ rvc_status rvc_load_f0_method(rvc_engine *e, int method)
                 Blob b(e->data_path + (method == RVC_F0_CREPE ? "/f0/crepe-full.rvcw" : "/f0/crepe-tiny.rvcw"));
                 slot.reset(new ModelCR(b));
             }
-            e->f0_method = method;
+            e->f0_method = method; e->hybrid_n = 0;
             return RVC_OK;
         }
         if (method == RVC_F0_FCPE) {
             if (!e->fc) { Blob b(e->data_path + "/f0/fcpe.rvcw"); e->fc.reset(new ModelFC(b)); }          // read once and kept, as the CREPE presets are
-            e->f0_method = method;
+            e->f0_method = method; e->hybrid_n = 0;
             return RVC_OK;
         }
+        if (method == RVC_F0_HYBRID) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY or RVC_F0_FCPE (RVC_F0_HYBRID names no members: rvc_load_f0_hybrid)");
         if (method != RVC_F0_YIN) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY or RVC_F0_FCPE");
-        e->f0_method = RVC_F0_YIN;
+        e->f0_method = RVC_F0_YIN; e->hybrid_n = 0;
         return RVC_OK;
     });
+}
+// Hybrid f0: `n` distinct single methods, the first one the lead, combined per frame under `mode`.  Every member is loaded as
+// rvc_load_f0_method loads it -- RMVPE's file is read again and the plans are dropped, a CREPE preset and FCPE are read once and kept -- but all files are read
+// before anything of the engine changes: a refusal leaves the method, the members and the loaded weights as they were.
+rvc_status rvc_load_f0_hybrid(rvc_engine *e, const int *methods, int n, int mode)
+{
+    return guarded(e, [&]() {
+        if (!methods || n < 1 || n > HYBRID_MEMBERS_MAX) throw ShapeError("f0 hybrid: 1 to 4 members");
+        if (mode != RVC_HYBRID_VOTE && mode != RVC_HYBRID_MEDIAN) throw ShapeError("f0 hybrid: mode RVC_HYBRID_VOTE or RVC_HYBRID_MEDIAN");
+        for (int i = 0; i < n; i++) {
+            const int m = methods[i];
+            if (m != RVC_F0_RMVPE && m != RVC_F0_YIN && !is_crepe(m) && m != RVC_F0_FCPE)
+                throw ShapeError("f0 hybrid: a member is RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY or RVC_F0_FCPE");
+            for (int j = 0; j < i; j++) if (methods[j] == m) throw ShapeError("f0 hybrid: a member is named twice");
+        }
+        std::unique_ptr<ModelRM> rm; std::unique_ptr<ModelCR> cr_full, cr_tiny; std::unique_ptr<ModelFC> fc;
+        for (int i = 0; i < n; i++) {
+            const int m = methods[i];
+            if (m == RVC_F0_RMVPE) { Blob b(e->data_path + "/f0/rmvpe.rvcw"); rm.reset(new ModelRM(b)); }
+            else if (m == RVC_F0_CREPE && !e->cr_full) { Blob b(e->data_path + "/f0/crepe-full.rvcw"); cr_full.reset(new ModelCR(b)); }
+            else if (m == RVC_F0_CREPE_TINY && !e->cr_tiny) { Blob b(e->data_path + "/f0/crepe-tiny.rvcw"); cr_tiny.reset(new ModelCR(b)); }
+            else if (m == RVC_F0_FCPE && !e->fc) { Blob b(e->data_path + "/f0/fcpe.rvcw"); fc.reset(new ModelFC(b)); }
+        }
+        if (rm) { drop_plans(e); e->rm = std::move(rm); }      // (as rvc_load_f0: the plans were built on the weights replaced here)
+        if (cr_full) e->cr_full = std::move(cr_full);
+        if (cr_tiny) e->cr_tiny = std::move(cr_tiny);
+        if (fc) e->fc = std::move(fc);
+        e->f0_method = RVC_F0_HYBRID; e->hybrid_n = n; e->hybrid_mode = mode;
+        for (int i = 0; i < HYBRID_MEMBERS_MAX; i++) e->hybrid_m[i] = i < n ? methods[i] : 0;
+        return RVC_OK;
+    });
+}
+// the members (the lead first; at most `cap` are written) and the mode of the hybrid in force -> its number of members, 0 when the method is no hybrid
+int rvc_f0_hybrid(rvc_engine *e, int *methods, int cap, int *mode)
+{
+    if (!e || e->f0_method != RVC_F0_HYBRID) return 0;
+    for (int i = 0; i < e->hybrid_n && i < cap && methods; i++) methods[i] = e->hybrid_m[i];
+    if (mode) *mode = e->hybrid_mode;
+    return e->hybrid_n;
 }
 int rvc_f0_method(rvc_engine *e) { return e ? e->f0_method : 0; }
 // the kind of the loaded synthesizer: 1 = trained with pitch guidance, 0 = without (config key f0 = 0: no tracker runs), -1 = none loaded

@@ -2,14 +2,14 @@
 //   plan.hip         the planner: device memory, prepared convolution weights, the op list, implicit-GEMM tile selection, test-hook table
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
 //   model_yin.hip    YIN f0 (build_yin)                      model_crepe.hip   CREPE f0 (build_crepe, the decoder's launch)
-//   model_fcpe.hip   FCPE f0 (build_fcpe, the decoder's and the depthwise kernel's launches)
+//   model_fcpe.hip   FCPE f0 (build_fcpe, the decoder's and the depthwise kernel's launches)     (hybrid f0: engine.hip build_f0 queues the members, model_rmvpe.hip the combine)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
 //   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter, with
 //                    resample_whole.hip.h and change_rms.hip.h)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
-// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, yin.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
+// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, f0_hybrid.hip.h, yin.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
 // or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm2 / igemm2w / igemm_lds / igemm32 / igemm_bf3 / igemm_splitk .hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
@@ -251,15 +251,23 @@ struct PlanKey {
     int f0_method = 0;            // the engine's f0 method (the plan's f0 branch is that method's; 0 on the infer plan of a model without pitch guidance)
     int crepe_decoder = 0;        // ... and, for the CREPE methods, the engine's decoder (0 = Viterbi, 1 = arg-max; 0 on every other plan)
     double fcpe_threshold = 0;    // ... and, for FCPE, the engine's voicing threshold (baked into the decoder's launch; 0 on every other plan)
+    // ... and, for RVC_F0_HYBRID, the members in the caller's order, 4 bits each from bit 0 (hybrid_pack), and the combination mode; both 0 on every other plan.  A
+    // hybrid plan carries crepe_decoder / fcpe_threshold when a CREPE preset / FCPE is among its members
+    uint32_t hybrid = 0; int hybrid_mode = 0;
     int nprobe = 0;               // the engine's index_nprobe (with_index plans; 0 = flat search)
     int knn_k = KNN_K;            // the engine's index_k: the K of the retrieval kernels and the width of d_knn_idx / d_knn_dist
     bool operator==(const PlanKey &o) const
     {
-        return std::tie(mode, B, L, frame16k, skip_head, R, R2, fstage, slot, bucket, with_index, with_protect, bf3, with_taps, plain_plan, f0_method, crepe_decoder, fcpe_threshold, nprobe, knn_k) ==
+        return std::tie(mode, B, L, frame16k, skip_head, R, R2, fstage, slot, bucket, with_index, with_protect, bf3, with_taps, plain_plan, f0_method, crepe_decoder, fcpe_threshold, hybrid, hybrid_mode, nprobe, knn_k) ==
                std::tie(o.mode, o.B, o.L, o.frame16k, o.skip_head, o.R, o.R2, o.fstage, o.slot, o.bucket, o.with_index, o.with_protect, o.bf3, o.with_taps, o.plain_plan, o.f0_method,
-                        o.crepe_decoder, o.fcpe_threshold, o.nprobe, o.knn_k);
+                        o.crepe_decoder, o.fcpe_threshold, o.hybrid, o.hybrid_mode, o.nprobe, o.knn_k);
     }
 };
+
+// the members of a hybrid f0 method as PlanKey::hybrid holds them, and back: -> the number of members
+constexpr int HYBRID_MEMBERS_MAX = 4;
+static inline uint32_t hybrid_pack(const int *m, int n) { uint32_t k = 0; for (int i = 0; i < n; i++) k |= (uint32_t)(m[i] & 15) << (4 * i); return k; }
+static inline int hybrid_unpack(uint32_t k, int m[HYBRID_MEMBERS_MAX]) { int n = 0; for (; n < HYBRID_MEMBERS_MAX && ((k >> (4 * n)) & 15); n++) m[n] = (int)((k >> (4 * n)) & 15); return n; }
 
 struct Plan {
     Arena arena;
@@ -547,6 +555,7 @@ struct rvc_engine {
     int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights), RVC_F0_CREPE / _TINY (cr_full / cr_tiny); engine-wide (PlanKey)
     std::unique_ptr<ModelCR> cr_full, cr_tiny;        // each stays loaded once read: going back to it costs no file and keeps its plans
     std::unique_ptr<ModelFC> fc;                      // FCPE (RVC_F0_FCPE), kept once read like the CREPE presets
+    int hybrid_n = 0, hybrid_m[rvc::HYBRID_MEMBERS_MAX] = {}, hybrid_mode = 0;      // f0_method == RVC_F0_HYBRID: the members (the lead first) and the mode (rvc_load_f0_hybrid); hybrid_n = 0 otherwise
     double fcpe_threshold = 0.006;                    // rvc_set_fcpe_threshold: f0 = 0 where the top posterior is at or below it; engine-wide (PlanKey)
     int crepe_decoder = 0;                            // rvc_set_crepe_decoder: 0 = Viterbi, 1 = arg-max; engine-wide (PlanKey)
     std::unique_ptr<ModelSY> sy;
@@ -629,7 +638,8 @@ T1 build_contentvec(rvc_engine *e, Plan &pl, int B, size_t L);
 T1 build_rmvpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache);
 void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update_cache, size_t frame16k, size_t hubert_length, float **pitchf_out, int **pitch_out, const float *f0_in = nullptr);
 float *build_yin(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
-float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
+// (method: the preset, RVC_F0_CREPE or RVC_F0_CREPE_TINY; pre: the prefix of its tap and stamp names -- a hybrid of both presets names the second one apart)
+float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, int method, const char *pre = "cr");
 // CREPE's decoder alone (crepe_decode_kernel, crepe.hip.h): the plan's launch and rvc_debug_crepe_decode's (debug.hip).  prob [B][Tm][360]; bp: B * Tm * 360 bytes of
 // back-pointers where crepe_backpointer_bytes says so (long windows; shorter ones keep them in LDS); bins / pd may be null
 std::vector<float> crepe_f0_table();
@@ -643,6 +653,13 @@ std::vector<float> fcpe_f0_table();
 float fcpe_cent_step();
 void launch_fcpe_decode(hipStream_t s, int B, int Tm, const float *logit, int l_ld, long long l_bs, const float *prob_in, float *prob, const float *f0tab, double threshold, float *f0, int *bins);
 void launch_fcpe_glu_dw(hipStream_t s, int B, int I, int T, const float *z, int z_ld, long long z_bs, const float *w, const float *bias, float *y, int y_ld, long long y_bs);
+// hybrid f0 (f0_hybrid.hip.h): one launch that decodes RMVPE's salience sal [B][360][ld] to unshifted Hz when RMVPE is member rm_at (-1:
+// not a member, sal unread) and combines the n member rows [B][Tm] (rows[0] the lead's; rows[rm_at] unread) into out [B][Tm].  launch_f0_hybrid: the plan's
+// launch (add_f0_hybrid queues it and returns the combined row, which build_pitch_post takes as f0_in) and rvc_debug_f0_hybrid's (debug.hip).  rm_f0: RMVPE's
+// decoded row, may be null
+void launch_f0_hybrid(hipStream_t s, int B, int Tm, int n, int mode, const float *const *rows, int rm_at, const float *sal, int sal_cs, long long sal_bs, StreamState *st,
+                      float *rm_f0, float *out);
+float *add_f0_hybrid(rvc_engine *e, Plan &pl, int B, int n, int mode, const float *const *rows, int rm_at, const T1 &sal);
 T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf);
 // the head and the tail of the f0 branch and ContentVec's first layer as plan helpers: the builders above call them, and so does rvc_debug_front (debug.hip)
 void add_conv0_front(Plan &pl, const ConvW &cw, const float *w_raw, const float *gn_g, const float *gn_b, int kt, int st, const T1 &x, const T1 &y);

@@ -77,9 +77,9 @@ static void add_crepe_conv(Plan &pl, const ConvW &cw, const T1 &x, const T1 &y)
 }
 
 // raw f0 [B][Tm] of the last f0_extractor_frame samples of each stream of pl.d_in ([B][L]), on RMVPE's frame grid: build_yin's contract
-float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k)
+float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, int method, const char *pre)
 {
-    const ModelCR *mp = e->f0_method == RVC_F0_CREPE ? e->cr_full.get() : e->cr_tiny.get();
+    const ModelCR *mp = method == RVC_F0_CREPE ? e->cr_full.get() : e->cr_tiny.get();
     if (!mp) throw std::logic_error("f0 method");
     const ModelCR &m = *mp;
     const size_t fr = 5120 * ((frame16k + 800 - 1) / 5120 + 1) - 160;     // rmvpe.rs:256
@@ -101,7 +101,7 @@ float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k)
         Plan *plp = &pl;
         pl.ops.push_back([=](hipStream_t s) { CrepeFrameP f2 = fp; if (plp->cur_in) f2.audio = plp->cur_in; hipLaunchKernelGGL(crepe_frame_kernel, grid, dim3(256), 0, s, f2); });
     }
-    add_tap(pl, "cr.frames", view(x, Tm, CREPE_FRAME, x.ld));
+    add_tap(pl, (std::string(pre) + ".frames").c_str(), view(x, Tm, CREPE_FRAME, x.ld));
     // one scratch tensor takes every layer's conv + bias (the pool behind it has consumed it before the next layer writes)
     const T1 y0 = make_t1(A, F, kCrepeCh[0] * m.cap, kCrepeLen[1], 0);
     const int feat = 4 * kCrepeCh[5] * m.cap;
@@ -126,7 +126,7 @@ float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k)
         }
         const dim3 grid((unsigned)((pp.total + 255) / 256));
         pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(crepe_bn_pool_kernel, grid, dim3(256), 0, s, pp); });
-        add_tap(pl, fmt("cr.p%d", l + 1).c_str(), tap);
+        add_tap(pl, (pre + fmt(".p%d", l + 1)).c_str(), tap);
     }
     const T1 logit = make_t1(A, B, CREPE_BINS, Tm, 0);
     add_conv1d(pl, m.fc, cls, logit, 1, 0, 1);
@@ -136,7 +136,7 @@ float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k)
         const dim3 grid((unsigned)((total + 255) / 256));
         pl.ops.push_back([=](hipStream_t s) { hipLaunchKernelGGL(crepe_sigmoid_kernel, grid, dim3(256), 0, s, logit.p, logit.ld, logit.bs, Tm, total, prob); });
     }
-    { T1 t; t.p = prob; t.B = B; t.C = Tm; t.T = CREPE_BINS; t.ld = CREPE_BINS; t.bs = (long long)Tm * CREPE_BINS; add_tap(pl, "cr.prob", t); }
+    { T1 t; t.p = prob; t.B = B; t.C = Tm; t.T = CREPE_BINS; t.ld = CREPE_BINS; t.bs = (long long)Tm * CREPE_BINS; add_tap(pl, (std::string(pre) + ".prob").c_str(), t); }
     float *f0 = A.floats((size_t)B * Tm);
     {
         const size_t bpn = crepe_backpointer_bytes(B, Tm);
@@ -144,7 +144,7 @@ float *build_crepe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k)
         const int decoder = pl.key.crepe_decoder; const float *tab = m.f0tab;
         pl.ops.push_back([=](hipStream_t s) { launch_crepe_decode(s, B, prob, Tm, decoder, tab, bp, f0, nullptr, nullptr); });
     }
-    { T1 t; t.p = f0; t.B = B; t.C = 1; t.T = Tm; t.ld = Tm; t.bs = Tm; add_tap(pl, "cr.f0", t); }
+    { T1 t; t.p = f0; t.B = B; t.C = 1; t.T = Tm; t.ld = Tm; t.bs = Tm; add_tap(pl, (std::string(pre) + ".f0").c_str(), t); }
     return f0;
 }
 

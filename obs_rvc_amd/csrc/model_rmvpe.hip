@@ -2,6 +2,7 @@
 #include "engine_int.h"
 #include "rmvpe.hip.h"
 #include "rmblock.hip.h"
+#include "f0_hybrid.hip.h"
 
 namespace rvc {
 
@@ -407,6 +408,38 @@ void build_pitch_post(rvc_engine *e, Plan &pl, int B, const T1 &sal, bool update
     int *pitch = (int *)A.alloc((size_t)B * R * sizeof(int));
     add_pitch_post(pl, B, sal, Tm, e->d_state, e->d_cp, pl.d_f0, true, (long long)shift, cache_start, read_start, R, pitchf, pitch, f0_in);
     *pitchf_out = pitchf; *pitch_out = pitch;
+}
+
+// hybrid f0 (f0_hybrid.hip.h): the one launch behind the members' builders.  A workgroup per stream: 1024 threads when it decodes RMVPE's
+// salience (pitch_post_kernel's scan shape), else a thread per frame rounded up to a wave -- a latency item of at most B x 1024 values, nothing to fill the chip with
+void launch_f0_hybrid(hipStream_t s, int B, int Tm, int n, int mode, const float *const *rows, int rm_at, const float *sal, int sal_cs, long long sal_bs, StreamState *st,
+                      float *rm_f0, float *out)
+{
+    if (B < 1 || Tm < 1 || Tm > 1024 || n < 1 || n > HYBRID_MAX || (mode != 0 && mode != 1) || rm_at < -1 || rm_at >= n || !out) throw ShapeError("f0 hybrid: shape");
+    HybridP hp{};
+    for (int i = 0; i < n; i++) { if (i != rm_at && !rows[i]) throw ShapeError("f0 hybrid: a member row is missing"); hp.row[i] = i == rm_at ? nullptr : rows[i]; }
+    if (rm_at >= 0 && (!sal || !st)) throw ShapeError("f0 hybrid: RMVPE's salience is missing");
+    hp.n = n; hp.mode = mode; hp.Tm = Tm; hp.rm_at = rm_at;
+    hp.sal = sal; hp.sal_cs = sal_cs; hp.sal_bs = sal_bs; hp.threshold = 0.03f;   // rvc.rs:122
+    hp.st = st; hp.rm_f0 = rm_f0; hp.out = out;
+    const int threads = rm_at >= 0 ? 1024 : (Tm + 63) / 64 * 64;
+    hipLaunchKernelGGL(f0_hybrid_kernel, dim3(B), dim3(threads), 0, s, hp);
+}
+
+float *add_f0_hybrid(rvc_engine *e, Plan &pl, int B, int n, int mode, const float *const *rows, int rm_at, const T1 &sal)
+{
+    static_assert(HYBRID_MAX == HYBRID_MEMBERS_MAX, "the kernel's member count is the key's");
+    const int Tm = pl.Tm;
+    if (rm_at >= 0 && (sal.C != 360 || sal.T != Tm)) throw ShapeError("pitch decode: salience shape");
+    float *out = pl.arena.floats((size_t)B * Tm);
+    float *rm_f0 = rm_at >= 0 && pl.key.with_taps ? pl.arena.floats((size_t)B * Tm) : nullptr;
+    struct Rows { const float *r[HYBRID_MAX]; } rr{};
+    for (int i = 0; i < n && i < HYBRID_MAX; i++) rr.r[i] = rows[i];
+    StreamState *st = e->d_state;
+    pl.ops.push_back([=](hipStream_t s) { launch_f0_hybrid(s, B, Tm, n, mode, rr.r, rm_at, sal.p, sal.ld, sal.bs, st, rm_f0, out); });
+    if (rm_f0) { T1 t; t.p = rm_f0; t.B = B; t.C = 1; t.T = Tm; t.ld = Tm; t.bs = Tm; add_tap(pl, "hy.rm_f0", t); }
+    { T1 t; t.p = out; t.B = B; t.C = 1; t.T = Tm; t.ld = Tm; t.bs = Tm; add_tap(pl, "hy.f0", t); }
+    return out;
 }
 
 }  // namespace rvc

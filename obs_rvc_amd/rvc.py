@@ -9,8 +9,8 @@ import os
 import numpy as np
 
 from . import _native
-from .rvc_common import (CREPE_ARGMAX, CREPE_VITERBI, CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_RMVPE, F0_YIN, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
-                         RvcInferError, RvcModelVersion, scale_mask)
+from .rvc_common import (CREPE_ARGMAX, CREPE_VITERBI, CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_HYBRID, F0_RMVPE, F0_YIN, HYBRID_MAX_MEMBERS, HYBRID_MEDIAN, HYBRID_VOTE, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
+                         RvcInferError, RvcModelVersion, parse_f0_hybrid, scale_mask)
 
 _FP = C.POINTER(C.c_float)
 
@@ -63,6 +63,9 @@ class RvcInfer:
         """The engine's f0 method: "rmvpe" / F0_RMVPE (loads <data>/f0/rmvpe.rvcw, as load_f0), "yin" / F0_YIN (needs no file), "crepe" = "crepe-full" / F0_CREPE
         (<data>/f0/crepe-full.rvcw), "crepe-tiny" / F0_CREPE_TINY (<data>/f0/crepe-tiny.rvcw) or "fcpe" / F0_FCPE (<data>/f0/fcpe.rvcw)."""
         if isinstance(method, str):
+            members = parse_f0_hybrid(method, self._F0_NAMES)      # "hybrid[rmvpe+fcpe]", the forks' form, under the default mode (load_f0_hybrid)
+            if members is not None:
+                return self.load_f0_hybrid(members)
             if method.lower() not in self._F0_NAMES:
                 raise ValueError("f0 method: 'rmvpe', 'yin', 'crepe' (= 'crepe-full'), 'crepe-tiny' or 'fcpe', not %r" % method)
             method = self._F0_NAMES[method.lower()]
@@ -70,8 +73,48 @@ class RvcInfer:
 
     @property
     def f0_method(self) -> int:
-        """0 = none loaded, F0_RMVPE, F0_YIN, F0_CREPE, F0_CREPE_TINY, F0_FCPE"""
+        """0 = none loaded, F0_RMVPE, F0_YIN, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_HYBRID"""
         return int(self._L.rvc_f0_method(self._h))
+
+    _HYBRID_MODES = {"vote": HYBRID_VOTE, "median": HYBRID_MEDIAN}
+
+    @classmethod
+    def _hybrid_args(cls, methods, mode):
+        """load_f0_hybrid's arguments as the C call takes them, checked here first (no device needed): -> ([method ids], mode id)"""
+        if isinstance(methods, (str, bytes)) or not 1 <= len(methods) <= HYBRID_MAX_MEMBERS:
+            raise ValueError("f0 hybrid: a list of 1 to %d members" % HYBRID_MAX_MEMBERS)
+        ids = []
+        for m in methods:
+            if isinstance(m, str):
+                if m.lower() not in cls._F0_NAMES:
+                    raise ValueError("f0 hybrid member: 'rmvpe', 'yin', 'crepe' (= 'crepe-full'), 'crepe-tiny' or 'fcpe', not %r" % m)
+                m = cls._F0_NAMES[m.lower()]
+            if int(m) not in cls._F0_NAMES.values():
+                raise ValueError("f0 hybrid member: %r is no single f0 method" % (m,))
+            ids.append(int(m))
+        if len(set(ids)) != len(ids):
+            raise ValueError("f0 hybrid: a member is named twice")
+        if isinstance(mode, str):
+            if mode.lower() not in cls._HYBRID_MODES:
+                raise ValueError("f0 hybrid mode: 'vote' or 'median', not %r" % mode)
+            mode = cls._HYBRID_MODES[mode.lower()]
+        if int(mode) not in (HYBRID_VOTE, HYBRID_MEDIAN):
+            raise ValueError("f0 hybrid mode: HYBRID_VOTE or HYBRID_MEDIAN, not %r" % (mode,))
+        return ids, int(mode)
+
+    def load_f0_hybrid(self, methods, mode="vote"):
+        """Hybrid f0: 1 to 4 distinct members (names or F0_* values; the first is the lead) run on the same audio and combined per frame.  mode "vote" /
+        HYBRID_VOTE (the default): a frame is voiced iff most members say so (the lead breaks a tie) and takes the median of the voiced values; "median" /
+        HYBRID_MEDIAN: the forks' plain median with unvoiced members entering as 0, which halves f0 where two members disagree on voicing.  Loads every member's
+        weights as load_f0_method would; all or nothing."""
+        ids, mode = self._hybrid_args(methods, mode)
+        self._chk(self._L.rvc_load_f0_hybrid(self._h, (C.c_int * len(ids))(*ids), len(ids), mode))
+
+    def f0_hybrid(self):
+        """The hybrid in force as ([F0_* of the members, the lead first], mode), None when the f0 method is no hybrid"""
+        m, mode = (C.c_int * HYBRID_MAX_MEMBERS)(), C.c_int()
+        n = int(self._L.rvc_f0_hybrid(self._h, m, HYBRID_MAX_MEMBERS, C.byref(mode)))
+        return ([int(m[i]) for i in range(n)], int(mode.value)) if n else None
 
     def set_crepe_decoder(self, decoder):
         """CREPE's decoder: "viterbi" / CREPE_VITERBI (the default) or "argmax" / CREPE_ARGMAX; engine-wide"""

@@ -12,6 +12,9 @@ CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER = 0, 1
 F0_RMVPE, F0_YIN = 1, 2
 F0_CREPE, F0_CREPE_TINY = 4, 5          # (3 is no method: it stays the unknown value it was)
 F0_FCPE = 7                             # (nor is 6)
+F0_HYBRID = 8                           # rvc_load_f0_hybrid: several of the above combined per frame (RVC_HYBRID_VOTE / _MEDIAN)
+HYBRID_VOTE, HYBRID_MEDIAN = 0, 1
+HYBRID_MAX_MEMBERS = 4
 # CREPE's decoders (rvc_set_crepe_decoder, RVC_CREPE_*)
 CREPE_VITERBI, CREPE_ARGMAX = 0, 1
 # input gate: a threshold at or below this many dB switches it off
@@ -22,6 +25,26 @@ DENOISE_INPUT, DENOISE_OUTPUT = 0, 1
 SCALE_CHROMATIC = 0xFFF
 _SCALE_STEPS = {"major": (0, 2, 4, 5, 7, 9, 11), "minor": (0, 2, 3, 5, 7, 8, 10), "chromatic": tuple(range(12))}
 _NOTE_NAMES = {"c": 0, "d": 2, "e": 4, "f": 5, "g": 7, "a": 9, "b": 11}
+
+
+def parse_f0_hybrid(text: str, names):
+    """The forks' bracket form of a hybrid f0 method: "hybrid[rmvpe+fcpe+crepe-tiny]" -> ["rmvpe", "fcpe", "crepe-tiny"] (lower case, the order kept: the first
+    member is the lead).  `names`: the member names accepted.  None when `text` is not of the form hybrid[...] at all; ValueError when it is but names no valid
+    hybrid: an empty or unknown member, a member named twice, more than HYBRID_MAX_MEMBERS."""
+    t = text.strip().lower()
+    if not t.startswith("hybrid"):
+        return None
+    if not (t.startswith("hybrid[") and t.endswith("]")):
+        raise ValueError("hybrid f0: write hybrid[a+b], e.g. hybrid[rmvpe+fcpe], not %r" % text)
+    members = [m.strip() for m in t[len("hybrid["):-1].split("+")]
+    for m in members:
+        if m not in names:
+            raise ValueError("hybrid f0: %r is no member (%s)" % (m, ", ".join(sorted(names))))
+    if len(set(members)) != len(members):
+        raise ValueError("hybrid f0: a member is named twice in %r" % text)
+    if not 1 <= len(members) <= HYBRID_MAX_MEMBERS:
+        raise ValueError("hybrid f0: 1 to %d members, not %d" % (HYBRID_MAX_MEMBERS, len(members)))
+    return members
 
 
 def scale_mask(root, kind: str = "major") -> int:
