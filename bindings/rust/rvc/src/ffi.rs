@@ -46,6 +46,7 @@ pub const RVC_F0_CREPE: c_int = 4;
 pub const RVC_F0_CREPE_TINY: c_int = 5;
 pub const RVC_F0_FCPE: c_int = 7;
 pub const RVC_F0_HYBRID: c_int = 8;
+pub const RVC_F0_PM: c_int = 9;
 pub const RVC_HYBRID_VOTE: c_int = 0;
 pub const RVC_HYBRID_MEDIAN: c_int = 1;
 pub const RVC_CREPE_VITERBI: c_int = 0;
@@ -68,7 +69,7 @@ extern "C" {
     pub fn rvc_infer(e: *mut RvcEngine, input: *const c_float, n: usize, sample_frame_16k_size: usize, has_pitch_shift: c_int,
                      pitch_shift: i32, skip_head: u32, return_length: u32, out: *mut c_float, cap: usize, out_len: *mut usize) -> c_int;
     pub fn rvc_last_error_message(e: *mut RvcEngine) -> *const c_char;
-    // ---- f0 method: RVC_F0_RMVPE (= rvc_load_f0) or RVC_F0_YIN (no weight file)
+    // ---- f0 method: RVC_F0_RMVPE (= rvc_load_f0), RVC_F0_YIN or RVC_F0_PM (no weight file)
     pub fn rvc_load_f0_method(e: *mut RvcEngine, method: c_int) -> c_int;
     pub fn rvc_f0_method(e: *mut RvcEngine) -> c_int;
     pub fn rvc_model_has_f0(e: *mut RvcEngine) -> c_int;

@@ -79,7 +79,8 @@ impl RvcInfer {
 
     /// Not in the reference: the engine's f0 method by `ffi::RVC_F0_RMVPE` (the same as `load_f0`), `ffi::RVC_F0_YIN`, the weight-free
     /// time-domain tracker (no `<data>/f0/rmvpe.rvcw` needed), or `ffi::RVC_F0_CREPE` / `ffi::RVC_F0_CREPE_TINY`
-    /// (`<data>/f0/crepe-full.rvcw` / `crepe-tiny.rvcw`), or `ffi::RVC_F0_FCPE` (`<data>/f0/fcpe.rvcw`)
+    /// (`<data>/f0/crepe-full.rvcw` / `crepe-tiny.rvcw`), or `ffi::RVC_F0_FCPE` (`<data>/f0/fcpe.rvcw`), or `ffi::RVC_F0_PM`, Praat's
+    /// autocorrelation tracker with a Viterbi path over the window (upstream's `pm`; weight-free as YIN)
     pub fn load_f0_method(&mut self, method: i32) -> Result<(), BackendError> {
         self.check_load(unsafe { ffi::rvc_load_f0_method(self.handle, method) })
     }
@@ -133,7 +134,7 @@ impl RvcInfer {
         unsafe { ffi::rvc_fcpe_threshold(self.handle) }
     }
 
-    /// Not in the reference: hybrid f0 -- 1 to 4 distinct members (`ffi::RVC_F0_RMVPE`, `_YIN`, `_CREPE`, `_CREPE_TINY`, `_FCPE`), the first the lead, run on
+    /// Not in the reference: hybrid f0 -- 1 to 4 distinct members (`ffi::RVC_F0_RMVPE`, `_YIN`, `_CREPE`, `_CREPE_TINY`, `_FCPE`, `_PM`), the first the lead, run on
     /// the same audio and combined per frame under `ffi::RVC_HYBRID_VOTE` (majority voicing, median of the voiced values) or `ffi::RVC_HYBRID_MEDIAN`
     /// (the forks' plain median).  All or nothing: on an error the method in force stays.  (Written without a Rust toolchain at hand, like the rest of this shim.)
     pub fn load_f0_hybrid(&mut self, methods: &[i32], mode: i32) -> Result<(), BackendError> {

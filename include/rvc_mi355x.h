@@ -95,7 +95,12 @@ const char *rvc_last_error_message(rvc_engine *e);
  * (python -m obs_rvc_amd.importers fcpe writes it; the sizes come from the blob); a missing file gives what a missing rmvpe.rvcw gives (RVC_BACKEND) and leaves
  * the method as it was.  The values 3 and 6 are not methods. */
 #define RVC_F0_FCPE       7
-rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rvc_load_f0; YIN: needs no file; CREPE, CREPE_TINY, FCPE: see above; other values: RVC_SHAPE */
+/* PM (upstream's f0_method "pm": Praat's to_pitch_ac, Boersma 1993; DESIGN.md "PM pitch"): the second weight-free tracker, on YIN's frames.  Per frame the
+ * autocorrelation of the Hanning-windowed 60 ms window divided by the window's own, up to 14 interpolated peak candidates and an unvoiced one; one Viterbi path
+ * through the candidates of the whole f0 window under Praat's octave-jump and voiced / unvoiced transition costs, so a frame is decided with its neighbours and
+ * not alone as YIN decides it.  Floor 50 Hz, ceiling 1100 Hz, voicing threshold 0.6 (upstream's call), Praat's defaults otherwise; no setter.  Needs no file. */
+#define RVC_F0_PM         9
+rvc_status rvc_load_f0_method(rvc_engine *e, int method);   /* RMVPE: same as rvc_load_f0; YIN, PM: need no file; CREPE, CREPE_TINY, FCPE: see above; other values: RVC_SHAPE */
 int rvc_f0_method(rvc_engine *e);                           /* 0 = none loaded */
 /* CREPE's decoder: 0 = Viterbi (the default, upstream's), 1 = arg-max (the same decoder without the transition term).  Engine-wide, may be changed between
  * calls, part of a CREPE plan's identity; other values: RVC_SHAPE. */
@@ -107,7 +112,7 @@ int rvc_crepe_decoder(rvc_engine *e);
  * may be changed between calls and holds from the next call on (part of an FCPE plan's identity); values outside [0, 1) and NaN: RVC_SHAPE. */
 rvc_status rvc_set_fcpe_threshold(rvc_engine *e, double threshold);
 double rvc_fcpe_threshold(rvc_engine *e);
-/* Hybrid f0 (the forks' `hybrid[rmvpe+fcpe]`; DESIGN.md "Hybrid f0"): 1 to 4 distinct members out of the five methods above run on the same audio, one after
+/* Hybrid f0 (the forks' `hybrid[rmvpe+fcpe]`; DESIGN.md "Hybrid f0"): 1 to 4 distinct members out of the six methods above run on the same audio, one after
  * another on the f0 branch, and their unshifted f0 rows are combined per stream and frame; the combined row takes the pitch tail every method takes (shift, pitch
  * controls, cache, get_f0_post).  methods[0] is the LEAD.  A member is voiced on a frame iff its value is > 0.  With n members of which v are voiced:
  *   RVC_HYBRID_VOTE   (the default of the front ends) voiced iff 2 v > n, or 2 v == n and the lead is voiced; an unvoiced frame gives 0, a voiced one the median

@@ -132,6 +132,15 @@ int rvc_debug_fcpe_dw(rvc_engine *e, const float *z, const float *w, const float
  * 0 .. B - 1 (a decode that runs off the salience raises ST_PANIC there, as in a plan).  n in [1, 4], B in [1, the engine's streams], Tm in [1, 1024] (RVC_SHAPE
  * otherwise).  0 = done, else an rvc_status. */
 int rvc_debug_f0_hybrid(rvc_engine *e, const float *rows, int n, int B, int Tm, int mode, const float *sal, int rm_at, float *out, float *rm_f0_out, float *ms_out);
+/* The kernels of the PM f0 method alone (obs_rvc_amd/csrc/pm.hip.h; DESIGN.md "PM pitch"), launched as a PM plan launches them.  Candidate arrays: cand_n [B][Tm]
+ * (0 .. 14 voiced candidates), cand_f / cand_s / cand_delta [B][Tm][15] (frequency in Hz, strength, local score; entry 0 is the unvoiced candidate, 1 .. n the
+ * voiced ones in ascending lag).
+ *   (a) audio != NULL: pm_peak_kernel + pm_cand_kernel on audio [B][n], whose last `frame` samples are the f0 window (Tm = 1 + frame / 160); the candidate arrays
+ *       are written.  With path_out and f0_out given the path kernel runs on them as well.
+ *   (b) audio == NULL: pm_path_kernel on the caller's cand_n / cand_f / cand_delta (cand_s may be NULL; n and frame are not looked at); path_out [B][Tm] takes the
+ *       chosen candidate of every frame and f0_out [B][Tm] its frequency (0 = unvoiced).
+ * B in [1, 64], Tm in [1, 1024]. */
+int rvc_debug_pm(rvc_engine *e, const float *audio, int B, int n, int frame, int Tm, int *cand_n, float *cand_f, float *cand_s, float *cand_delta, int *path_out, float *f0_out);
 /* the caller-side post-processing, the session's ring updates and a converter of several streams (obs_rvc_amd/csrc/chunk.hip.h, session.hip.h, resample.hip.h;
  * DESIGN.md "Post-processing and resamplers: what is tested"), each launch queued as rvc_session_process queues it, on the caller's arrays with the caller's
  * stream strides.  op: buffers buf[0..3] (each the WHOLE allocation, [streams][stride] floats, uploaded before the launches and downloaded after them: the

@@ -64,7 +64,7 @@ def _include_closure(src):
 # implicit-GEMM template instantiations are the bulk of the compile time; as separate units they build in parallel (5 min -> about 1.5 min on 8 cores)
 # and are not rebuilt when only the engine changes.
 UNITS = [(src, flags, _include_closure(src)) for src, flags in
-         [(u, []) for u in ("engine.hip", "debug.hip", "calib.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "model_crepe.hip", "model_fcpe.hip", "model_synth.hip", "retrieval.hip")] +
+         [(u, []) for u in ("engine.hip", "debug.hip", "calib.hip", "plan.hip", "model_cv.hip", "model_rmvpe.hip", "model_yin.hip", "f0_pm.hip", "model_crepe.hip", "model_fcpe.hip", "model_synth.hip", "retrieval.hip")] +
          [("igemm2_inst.hip", ["-DRVC_IGEMM2_CFG=%d" % c]) for c in range(5)] +
          [("igemm_tiled_inst.hip", ["-DRVC_TILED_PART=%d" % c]) for c in range(4)] +
          [("igemm2w_inst.hip", ["-DRVC_G2W_PART=%d" % c]) for c in range(3)] +
@@ -378,6 +378,8 @@ def lib():
         L.rvc_load_f0_hybrid.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.c_int]
         L.rvc_f0_hybrid.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
         L.rvc_debug_f0_hybrid.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, fp, fp]
+    if hasattr(L, "rvc_debug_pm") or not override:
+        L.rvc_debug_pm.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, fp, fp, fp, vp, fp]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
     if hasattr(L, "rvc_model_speakers") or not override:

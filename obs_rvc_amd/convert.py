@@ -1,4 +1,4 @@
-"""python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny|fcpe|"hybrid[a+b..]" --f0-hybrid-mode vote|median] [--index I --index-rate r --index-k 4|8 --nprobe p]
+"""python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny|fcpe|pm|"hybrid[a+b..]" --f0-hybrid-mode vote|median] [--index I --index-rate r --index-k 4|8 --nprobe p]
        [--pitch semitones] [--formant st] [--protect p] [--streams S] [--window k --context C --crossfade X] [--no-highpass] [--rate out_rate]
        [--rms-mix-rate r] [--resampler blocks|device] [--sid N | --sid-mix 0:0.3,2:0.7]
 
@@ -27,7 +27,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--data", default=None, help="the engine's data directory (contentvec/, f0/); default: the model zoo of the package")
     p.add_argument("--version", type=int, choices=(1, 2), default=2, help="RVC model version: 1 = 256-dim features, 2 = 768-dim (default)")
     p.add_argument("--f0", type=f0_arg, default="rmvpe", metavar="{%s,hybrid[a+b..]}" % ",".join(F0_CHOICES),
-                   help="f0 method (default rmvpe; not loaded for a model without pitch guidance); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw; fcpe reads <data>/f0/fcpe.rvcw; "
+                   help="f0 method (default rmvpe; not loaded for a model without pitch guidance); the CREPE presets are named by their weight files, <data>/f0/crepe-full.rvcw and crepe-tiny.rvcw; fcpe reads <data>/f0/fcpe.rvcw; yin and pm (Praat's autocorrelation tracker) need no file; "
                         "hybrid[rmvpe+fcpe] (quote it) runs 1 to 4 of them and combines their answers per frame, the first member breaking ties")
     p.add_argument("--f0-hybrid-mode", choices=("vote", "median"), default="vote",
                    help="how a hybrid combines: vote = majority voicing, median of the voiced values (default); median = plain median with unvoiced members as 0 (the forks')")
@@ -85,7 +85,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return a
 
 
-F0_CHOICES = ("rmvpe", "yin", "crepe-full", "crepe-tiny", "fcpe")
+F0_CHOICES = ("rmvpe", "yin", "crepe-full", "crepe-tiny", "fcpe", "pm")
 
 
 def f0_arg(text: str) -> str:

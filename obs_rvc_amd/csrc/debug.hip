@@ -691,6 +691,46 @@ int rvc_debug_f0_hybrid(rvc_engine *e, const float *rows, int n, int B, int Tm, 
     });
 }
 
+// test aid: the PM method's kernels alone (pm.hip.h; tests/test_gpu_pm.py), through the launches a plan uses: (a) peak + candidates on the caller's audio, (b) the
+// path on the caller's candidate arrays (include/rvc_mi355x_debug.h)
+int rvc_debug_pm(rvc_engine *e, const float *audio, int B, int n, int frame, int Tm, int *cand_n, float *cand_f, float *cand_s, float *cand_delta, int *path_out, float *f0_out)
+{
+    return (int)guarded(e, [&]() {
+        if (B < 1 || B > 64 || Tm < 1 || Tm > 1024 || !cand_n || !cand_f || !cand_delta || (!path_out) != (!f0_out)) throw ShapeError("pm: B in [1, 64], Tm in [1, 1024], candidate arrays");
+        if (audio && (!cand_s || n < 1 || frame < 1 || frame > n || Tm != 1 + frame / 160)) throw ShapeError("pm: frame in [1, n], Tm = 1 + frame / 160");
+        if (!audio && !path_out) throw ShapeError("pm: nothing to do");
+        const size_t bt = (size_t)B * Tm, nc = bt * 15;
+        DevBuf<float> d_audio, d_rw, d_gpk, d_f, d_s, d_d, d_f0; DevBuf<int> d_n, d_path;
+        d_n.alloc(bt); d_f.alloc(nc); d_s.alloc(nc); d_d.alloc(nc); d_path.alloc(bt); d_f0.alloc(bt);
+        if (audio) {
+            const std::vector<float> rw = pm_rw_table();
+            d_audio.alloc((size_t)B * n); d_rw.alloc(rw.size()); d_gpk.alloc((size_t)B * 2);
+            HIPCHK(hipMemcpy(d_audio.get(), audio, (size_t)B * n * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_rw.get(), rw.data(), rw.size() * sizeof(float), hipMemcpyHostToDevice));
+        } else {
+            HIPCHK(hipMemcpy(d_n.get(), cand_n, bt * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_f.get(), cand_f, nc * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_d.get(), cand_delta, nc * sizeof(float), hipMemcpyHostToDevice));
+        }
+        HIPCHK(hipDeviceSynchronize());
+        if (audio) launch_pm_cand(e->stream, B, d_audio.get(), n, n, frame, Tm, d_rw.get(), d_gpk.get(), d_n.get(), d_f.get(), d_s.get(), d_d.get());
+        if (path_out) launch_pm_path(e->stream, B, Tm, d_n.get(), d_f.get(), d_d.get(), d_path.get(), d_f0.get());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (audio) {
+            HIPCHK(hipMemcpy(cand_n, d_n.get(), bt * sizeof(int), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(cand_f, d_f.get(), nc * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(cand_s, d_s.get(), nc * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(cand_delta, d_d.get(), nc * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        if (path_out) {
+            HIPCHK(hipMemcpy(path_out, d_path.get(), bt * sizeof(int), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(f0_out, d_f0.get(), bt * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        return RVC_OK;
+    });
+}
+
 // test aid: the caller-side post-processing, the session's ring updates and a converter of several streams (chunk.hip.h, session.hip.h, resample.hip.h;
 // tests/test_gpu_post.py) on the caller's arrays with the caller's stream strides, each launch queued as the session queues it (engine_int.h launch_post_* /
 // launch_ring_* / launch_resampler).  Every size is checked against the strides on the host before anything is queued.

@@ -224,12 +224,17 @@ static void alloc_state(rvc_engine *e)
 
 // ------------------------------- plan -------------------------------------------------
 static inline bool is_crepe(int method) { return method == RVC_F0_CREPE || method == RVC_F0_CREPE_TINY; }
-// the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, CREPE's or FCPE's network and decoder, or -- a hybrid -- several of
+// the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, PM's three launches, CREPE's or FCPE's network and decoder, or -- a hybrid -- several of
 // them and the launch that combines their rows; behind each the same pitch tail (shift, cache, get_f0_post)
 static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache, size_t hubert_length, float **pitchf_out, int **pitch_out)
 {
     if (e->f0_method == RVC_F0_YIN) {
         const float *f0 = build_yin(e, pl, B, L, frame16k);
+        build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
+        return;
+    }
+    if (e->f0_method == RVC_F0_PM) {
+        const float *f0 = build_pm(e, pl, B, L, frame16k);
         build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
         return;
     }
@@ -246,6 +251,7 @@ static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, 
                 if (!e->rm) throw std::logic_error("f0 method");
                 sal = build_rmvpe(e, pl, B, L, frame16k, update_cache); rm_at = i;
             } else if (mem[i] == RVC_F0_YIN) rows[i] = build_yin(e, pl, B, L, frame16k);
+            else if (mem[i] == RVC_F0_PM) rows[i] = build_pm(e, pl, B, L, frame16k);
             else if (is_crepe(mem[i])) rows[i] = build_crepe(e, pl, B, L, frame16k, mem[i], both_crepe && mem[i] == RVC_F0_CREPE_TINY ? "crt" : "cr");
             else if (mem[i] == RVC_F0_FCPE) rows[i] = build_fcpe(e, pl, B, L, frame16k);
             else throw std::logic_error("f0 method");
@@ -856,7 +862,7 @@ rvc_status rvc_load_f0(rvc_engine *e, int pitch_algorithm)
         return RVC_OK;
     });
 }
-// the f0 method by its own constants (rvc_load_f0 keeps the reference's one-variant enum): RMVPE loads its weights, YIN has none.  The method is part of
+// the f0 method by its own constants (rvc_load_f0 keeps the reference's one-variant enum): RMVPE loads its weights, YIN and PM have none.  The method is part of
 // a plan's key, so a plan built for one never serves the other.
 rvc_status rvc_load_f0_method(rvc_engine *e, int method)
 {
@@ -877,9 +883,9 @@ rvc_status rvc_load_f0_method(rvc_engine *e, int method)
             e->f0_method = method; e->hybrid_n = 0;
             return RVC_OK;
         }
-        if (method == RVC_F0_HYBRID) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY or RVC_F0_FCPE (RVC_F0_HYBRID names no members: rvc_load_f0_hybrid)");
-        if (method != RVC_F0_YIN) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY or RVC_F0_FCPE");
-        e->f0_method = RVC_F0_YIN; e->hybrid_n = 0;
+        if (method == RVC_F0_HYBRID) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY, RVC_F0_FCPE or RVC_F0_PM (RVC_F0_HYBRID names no members: rvc_load_f0_hybrid)");
+        if (method != RVC_F0_YIN && method != RVC_F0_PM) throw ShapeError("f0 method: RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY, RVC_F0_FCPE or RVC_F0_PM");
+        e->f0_method = method; e->hybrid_n = 0;          // (YIN and PM have no weights)
         return RVC_OK;
     });
 }
@@ -893,8 +899,8 @@ rvc_status rvc_load_f0_hybrid(rvc_engine *e, const int *methods, int n, int mode
         if (mode != RVC_HYBRID_VOTE && mode != RVC_HYBRID_MEDIAN) throw ShapeError("f0 hybrid: mode RVC_HYBRID_VOTE or RVC_HYBRID_MEDIAN");
         for (int i = 0; i < n; i++) {
             const int m = methods[i];
-            if (m != RVC_F0_RMVPE && m != RVC_F0_YIN && !is_crepe(m) && m != RVC_F0_FCPE)
-                throw ShapeError("f0 hybrid: a member is RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY or RVC_F0_FCPE");
+            if (m != RVC_F0_RMVPE && m != RVC_F0_YIN && !is_crepe(m) && m != RVC_F0_FCPE && m != RVC_F0_PM)
+                throw ShapeError("f0 hybrid: a member is RVC_F0_RMVPE, RVC_F0_YIN, RVC_F0_CREPE, RVC_F0_CREPE_TINY, RVC_F0_FCPE or RVC_F0_PM");
             for (int j = 0; j < i; j++) if (methods[j] == m) throw ShapeError("f0 hybrid: a member is named twice");
         }
         std::unique_ptr<ModelRM> rm; std::unique_ptr<ModelCR> cr_full, cr_tiny; std::unique_ptr<ModelFC> fc;

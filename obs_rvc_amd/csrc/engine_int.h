@@ -2,14 +2,14 @@
 //   plan.hip         the planner: device memory, prepared convolution weights, the op list, implicit-GEMM tile selection, test-hook table
 //   model_cv.hip     ContentVec (build_contentvec)          model_rmvpe.hip   RMVPE + decode (build_rmvpe, build_pitch_post)
 //   model_yin.hip    YIN f0 (build_yin)                      model_crepe.hip   CREPE f0 (build_crepe, the decoder's launch)
-//   model_fcpe.hip   FCPE f0 (build_fcpe, the decoder's and the depthwise kernel's launches)     (hybrid f0: engine.hip build_f0 queues the members, model_rmvpe.hip the combine)
+//   model_fcpe.hip   FCPE f0 (build_fcpe, the decoder's and the depthwise kernel's launches)     f0_pm.hip   "pm" f0 (build_pm and its launches)     (hybrid f0: engine.hip build_f0 queues the members, model_rmvpe.hip the combine)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
 //   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter, with
 //                    resample_whole.hip.h and change_rms.hip.h)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
-// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, f0_hybrid.hip.h, yin.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
+// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, f0_hybrid.hip.h, yin.hip.h, pm.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
 // or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm2 / igemm2w / igemm_lds / igemm32 / igemm_bf3 / igemm_splitk .hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
@@ -552,7 +552,7 @@ struct rvc_engine {
     hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
     std::unique_ptr<ModelCV> cv;
     std::unique_ptr<ModelRM> rm;
-    int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN (no weights), RVC_F0_CREPE / _TINY (cr_full / cr_tiny); engine-wide (PlanKey)
+    int f0_method = 0;                                // 0 none, RVC_F0_RMVPE (rm is loaded), RVC_F0_YIN / RVC_F0_PM (no weights), RVC_F0_CREPE / _TINY (cr_full / cr_tiny); engine-wide (PlanKey)
     std::unique_ptr<ModelCR> cr_full, cr_tiny;        // each stays loaded once read: going back to it costs no file and keeps its plans
     std::unique_ptr<ModelFC> fc;                      // FCPE (RVC_F0_FCPE), kept once read like the CREPE presets
     int hybrid_n = 0, hybrid_m[rvc::HYBRID_MEMBERS_MAX] = {}, hybrid_mode = 0;      // f0_method == RVC_F0_HYBRID: the members (the lead first) and the mode (rvc_load_f0_hybrid); hybrid_n = 0 otherwise
@@ -646,6 +646,12 @@ std::vector<float> crepe_f0_table();
 size_t crepe_backpointer_bytes(int B, int Tm);
 void launch_crepe_decode(hipStream_t s, int B, const float *prob, int Tm, int decoder, const float *f0tab, unsigned char *bp, float *f0, int *bins, float *pd);
 float *build_fcpe(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
+// "pm", Praat's autocorrelation tracker (f0_pm.hip, pm.hip.h): build_yin's contract.  launch_pm_cand: the stream peaks and the candidates of
+// every frame (gpk [B][2]; cn [B][Tm]; cf / cs / cd [B][Tm][15]); launch_pm_path: the Viterbi path over them (path, f0 [B][Tm]).  Both are rvc_debug_pm's launches
+float *build_pm(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k);
+std::vector<float> pm_rw_table();
+void launch_pm_cand(hipStream_t s, int B, const float *audio, long long audio_bs, int n, int frame, int Tm, const float *rw, float *gpk, int *cn, float *cf, float *cs, float *cd);
+void launch_pm_path(hipStream_t s, int B, int Tm, const int *cn, const float *cf, const float *cd, int *path, float *f0);
 // FCPE's decoder and its GLU + depthwise + SiLU kernel alone (fcpe.hip.h): the plan's launches and the debug entries' (debug.hip).  Decoder: logit [B][360][l_ld]
 // (sigmoid applied, posteriors written to prob [B][Tm][360]) or, with logit null, the caller's posteriors prob_in; bins may be null.  Depthwise: z [B][2 I][z_ld] ->
 // y [B][I][y_ld], w [I][31], bias [I]

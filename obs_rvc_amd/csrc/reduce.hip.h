@@ -38,5 +38,17 @@ __device__ __forceinline__ float block_sum(float v, float *red)
     for (int i = 0; i < nw; i++) t += red[i];
     return t;
 }
+// ... and the largest value of the block, under the same conditions
+__device__ __forceinline__ float block_max(float v, float *red)
+{
+    v = wave_max(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    float t = red[0];
+    for (int i = 1; i < nw; i++) t = fmaxf(t, red[i]);
+    return t;
+}
 
 }  // namespace rvc

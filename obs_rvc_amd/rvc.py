@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _native
-from .rvc_common import (CREPE_ARGMAX, CREPE_VITERBI, CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_HYBRID, F0_RMVPE, F0_YIN, HYBRID_MAX_MEMBERS, HYBRID_MEDIAN, HYBRID_VOTE, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
+from .rvc_common import (CREPE_ARGMAX, CREPE_VITERBI, CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_HYBRID, F0_PM, F0_RMVPE, F0_YIN, HYBRID_MAX_MEMBERS, HYBRID_MEDIAN, HYBRID_VOTE, SCALE_C_MAJOR, SCALE_CHROMATIC, PitchAlgorithm,  # noqa: F401
                          RvcInferError, RvcModelVersion, parse_f0_hybrid, scale_mask)
 
 _FP = C.POINTER(C.c_float)
@@ -57,23 +57,24 @@ class RvcInfer:
     def load_f0(self, pitch_algorithm=PitchAlgorithm.Rmvpe):
         self._chk(self._L.rvc_load_f0(self._h, int(PitchAlgorithm.from_value(pitch_algorithm))))
 
-    _F0_NAMES = {"rmvpe": F0_RMVPE, "yin": F0_YIN, "crepe": F0_CREPE, "crepe-full": F0_CREPE, "crepe-tiny": F0_CREPE_TINY, "fcpe": F0_FCPE}
+    _F0_NAMES = {"rmvpe": F0_RMVPE, "yin": F0_YIN, "crepe": F0_CREPE, "crepe-full": F0_CREPE, "crepe-tiny": F0_CREPE_TINY, "fcpe": F0_FCPE, "pm": F0_PM}
 
     def load_f0_method(self, method):
         """The engine's f0 method: "rmvpe" / F0_RMVPE (loads <data>/f0/rmvpe.rvcw, as load_f0), "yin" / F0_YIN (needs no file), "crepe" = "crepe-full" / F0_CREPE
-        (<data>/f0/crepe-full.rvcw), "crepe-tiny" / F0_CREPE_TINY (<data>/f0/crepe-tiny.rvcw) or "fcpe" / F0_FCPE (<data>/f0/fcpe.rvcw)."""
+        (<data>/f0/crepe-full.rvcw), "crepe-tiny" / F0_CREPE_TINY (<data>/f0/crepe-tiny.rvcw) or "fcpe" / F0_FCPE (<data>/f0/fcpe.rvcw), or "pm" / F0_PM (Praat's autocorrelation
+        tracker, weight-free as YIN)."""
         if isinstance(method, str):
             members = parse_f0_hybrid(method, self._F0_NAMES)      # "hybrid[rmvpe+fcpe]", the forks' form, under the default mode (load_f0_hybrid)
             if members is not None:
                 return self.load_f0_hybrid(members)
             if method.lower() not in self._F0_NAMES:
-                raise ValueError("f0 method: 'rmvpe', 'yin', 'crepe' (= 'crepe-full'), 'crepe-tiny' or 'fcpe', not %r" % method)
+                raise ValueError("f0 method: 'rmvpe', 'yin', 'crepe' (= 'crepe-full'), 'crepe-tiny', 'fcpe' or 'pm', not %r" % method)
             method = self._F0_NAMES[method.lower()]
         self._chk(self._L.rvc_load_f0_method(self._h, int(method)))
 
     @property
     def f0_method(self) -> int:
-        """0 = none loaded, F0_RMVPE, F0_YIN, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_HYBRID"""
+        """0 = none loaded, F0_RMVPE, F0_YIN, F0_CREPE, F0_CREPE_TINY, F0_FCPE, F0_PM, F0_HYBRID"""
         return int(self._L.rvc_f0_method(self._h))
 
     _HYBRID_MODES = {"vote": HYBRID_VOTE, "median": HYBRID_MEDIAN}
@@ -87,7 +88,7 @@ class RvcInfer:
         for m in methods:
             if isinstance(m, str):
                 if m.lower() not in cls._F0_NAMES:
-                    raise ValueError("f0 hybrid member: 'rmvpe', 'yin', 'crepe' (= 'crepe-full'), 'crepe-tiny' or 'fcpe', not %r" % m)
+                    raise ValueError("f0 hybrid member: 'rmvpe', 'yin', 'crepe' (= 'crepe-full'), 'crepe-tiny', 'fcpe' or 'pm', not %r" % m)
                 m = cls._F0_NAMES[m.lower()]
             if int(m) not in cls._F0_NAMES.values():
                 raise ValueError("f0 hybrid member: %r is no single f0 method" % (m,))

@@ -12,6 +12,7 @@ CROSSFADE_LINEAR, CROSSFADE_PHASE_VOCODER = 0, 1
 F0_RMVPE, F0_YIN = 1, 2
 F0_CREPE, F0_CREPE_TINY = 4, 5          # (3 is no method: it stays the unknown value it was)
 F0_FCPE = 7                             # (nor is 6)
+F0_PM = 9                               # Praat's autocorrelation tracker (upstream's "pm"), weight-free as YIN
 F0_HYBRID = 8                           # rvc_load_f0_hybrid: several of the above combined per frame (RVC_HYBRID_VOTE / _MEDIAN)
 HYBRID_VOTE, HYBRID_MEDIAN = 0, 1
 HYBRID_MAX_MEMBERS = 4
