@@ -156,6 +156,11 @@ extern "C" {
     // ---- consonant protection (upstream's `protect`): [0, 0.5], 0.5 = off; unvoiced rows are mixed back towards the raw ContentVec features
     pub fn rvc_set_protect(e: *mut RvcEngine, protect: f64) -> c_int;
     pub fn rvc_set_protect_stream(e: *mut RvcEngine, stream: c_int, protect: f64) -> c_int;
+    pub fn rvc_set_f0_override_stream(e: *mut RvcEngine, stream: c_int, hz: *const c_float, n: usize) -> c_int;
+    pub fn rvc_set_f0_override_hold(e: *mut RvcEngine, hold: c_int) -> c_int;
+    pub fn rvc_set_f0_curve(e: *mut RvcEngine, t_sec: *const f64, hz: *const c_float, n: usize) -> c_int;
+    pub fn rvc_f0_curve_grid(e: *mut RvcEngine, n_frames: usize, out: *mut c_float, cap: usize) -> c_int;
+    pub fn rvc_convert_f0(e: *mut RvcEngine, hz: *mut c_float, cap: usize, n_frames: *mut usize) -> c_int;
 
     // ---- multi-GPU: the one collective (index broadcast at load, RCCL over xGMI)
     pub fn rvc_rccl_unique_id(id128: *mut c_void) -> c_int;

@@ -314,6 +314,42 @@ impl RvcInfer {
         let rc = unsafe { ffi::rvc_set_protect(self.handle, protect) };
         self.check(rc)
     }
+
+    /// f0 from outside: `hz` rows for the END of the next f0 window of `stream` (NaN keeps the tracker's value, 0 = unvoiced, else up to 20000 Hz); an empty slice
+    /// clears.  The rows are transposed like any f0; consumed by the stream's next infer call unless `set_f0_override_hold(true)`
+    pub fn set_f0_override(&mut self, stream: i32, hz: &[f32]) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_f0_override_stream(self.handle, stream, hz.as_ptr(), hz.len()) };
+        self.check(rc)
+    }
+
+    pub fn set_f0_override_hold(&mut self, hold: bool) -> Result<(), RvcInferError> {
+        let rc = unsafe { ffi::rvc_set_f0_override_hold(self.handle, hold as i32) };
+        self.check(rc)
+    }
+
+    /// the f0 curve of the recording the converter calls convert next: breakpoints `t_sec` (strictly increasing) and `hz` of one length; empty slices clear
+    pub fn set_f0_curve(&mut self, t_sec: &[f64], hz: &[f32]) -> Result<(), RvcInferError> {
+        let n = if t_sec.len() == hz.len() { hz.len() } else { return self.check(ffi::RVC_SHAPE) };
+        let rc = unsafe { ffi::rvc_set_f0_curve(self.handle, t_sec.as_ptr(), hz.as_ptr(), n) };
+        self.check(rc)
+    }
+
+    /// the first `n_frames` rows of the curve's 10 ms grid as the device builds it (NaN = keep the tracker's value)
+    pub fn f0_curve_grid(&mut self, n_frames: usize) -> Result<Vec<f32>, RvcInferError> {
+        let mut out = vec![0f32; n_frames];
+        let rc = unsafe { ffi::rvc_f0_curve_grid(self.handle, n_frames, out.as_mut_ptr(), out.len()) };
+        self.check(rc).map(|_| out)
+    }
+
+    /// the conditioned f0 of the last completed conversion, one value per 10 ms frame of the recording
+    pub fn convert_f0(&mut self) -> Result<Vec<f32>, RvcInferError> {
+        let mut n: usize = 0;
+        unsafe { ffi::rvc_convert_f0(self.handle, std::ptr::null_mut(), 0, &mut n) };
+        let mut out = vec![0f32; n.max(1)];
+        let rc = unsafe { ffi::rvc_convert_f0(self.handle, out.as_mut_ptr(), out.len(), &mut n) };
+        out.truncate(n);
+        self.check(rc).map(|_| out)
+    }
 }
 
 impl Drop for RvcInfer {

@@ -284,6 +284,32 @@ rvc_status rvc_set_f0_snap_stream(rvc_engine *e, int stream, uint32_t pitch_clas
 rvc_status rvc_set_protect(rvc_engine *e, double protect);                 /* [0, 0.5]; 0.5 = off; NaN / out of range: RVC_SHAPE */
 rvc_status rvc_set_protect_stream(rvc_engine *e, int stream, double protect);
 
+/* ---- f0 from outside: a per-chunk override of a stream's f0 rows, and upstream RVC's "f0 curve file" for a whole recording (DESIGN.md "f0 from outside") ---- */
+/* Override rows: a stream may bring n <= 1024 rows in Hz for the END of its next f0 window (row i of n is window row Tm - n + i; the window's Tm is that of the
+ * consuming call, 1 + f0 frame / 160).  A NaN row keeps the tracker's value, 0 is unvoiced, anything else is a finite value in (0, 20000].  The rows REPLACE the
+ * f0 method's rows in front of everything else: the multiplier (pitch_shift, formant factor, rvc_set_pitch_semitones), range gate, median, snap, the pitch cache
+ * and protect apply to them as to the tracker's.  So -- unlike upstream, which pastes its curve behind its transpose -- an override and a curve are transposed like
+ * any f0: for absolute values call with pitch_shift = 0 and rvc_set_pitch_semitones(e, 0).  The tracker still runs, and an f0 method must be loaded; a model
+ * without pitch guidance ignores overrides and curve.
+ *   rvc_set_f0_override_stream: hz == NULL or n == 0 clears.  RVC_SHAPE (state unchanged): a bad stream number, n > 1024, a negative or infinite value or one above
+ *     20000.  n greater than the window's Tm is refused (RVC_SHAPE, nothing run, the override stays) by the call that would consume it.
+ *   rvc_set_f0_override_hold: 0 (default): an override is consumed by the next infer call of its stream (rvc_infer*, rvc_infer_batch_g, the session; rvc_pitch
+ *     honours and consumes stream 0's); 1: it stays until cleared.  rvc_reset_state and rvc_set_streams clear pending overrides.
+ * Whether ANY stream of a call has an override is part of a plan's identity (the first such call builds a plan); the values are not: they travel in front of the
+ * chunk and hold under graph replay, chunk pipelining, rvc_infer_batch_g and the session.  Calls without an override run the launches they always ran.
+ * The curve: n >= 1 breakpoints (t seconds strictly increasing and finite, hz 0 or in (0, 20000]) of ONE recording, used by rvc_convert* / rvc_convert_file* only
+ * (they clear the streams' overrides first; streaming calls never read the curve; model loads leave it alone).  Grid row j stands for j / 100 s: between two voiced
+ * breakpoints linear, next to a 0 the nearer breakpoint's value (a tie goes to the earlier), on the last breakpoint its value, NaN outside [t_0, t_n-1].
+ *   rvc_set_f0_curve: n == 0 clears; RVC_SHAPE and the old curve kept on bad input.  rvc_f0_curve_grid: the first n_frames rows of the grid as the device builds
+ *     it (all NaN without a curve); cap < n_frames: RVC_SHAPE.
+ *   rvc_convert_f0: the conditioned f0 (what the synthesizer got) of the last completed conversion, one value per 10 ms frame of the recording; RVC_SHAPE before
+ *     a conversion has completed, for a model without pitch guidance, or with cap short (*n_frames is still written). */
+rvc_status rvc_set_f0_override_stream(rvc_engine *e, int stream, const float *hz, size_t n);
+rvc_status rvc_set_f0_override_hold(rvc_engine *e, int hold);
+rvc_status rvc_set_f0_curve(rvc_engine *e, const double *t_sec, const float *hz, size_t n);
+rvc_status rvc_f0_curve_grid(rvc_engine *e, size_t n_frames, float *out, size_t cap);
+rvc_status rvc_convert_f0(rvc_engine *e, float *hz, size_t cap, size_t *n_frames);
+
 /* ---- multi-GPU (BASELINE configs[4]; no counterpart in the reference: one RvcInfer per process, rvc.rs:133-134) ---- */
 /* Streams shard across GPUs with NO per-chunk collective: one process + one engine per GPU, stream s on rank s mod world.  The one
  * exchange step is at load: the shared retrieval index travels from rank 0 into every rank's HBM with ONE ncclBroadcast over

@@ -42,6 +42,7 @@ SYMBOLS = [
     "rvc_index_build_begin", "rvc_index_build_add", "rvc_index_build_add_device", "rvc_index_build_info", "rvc_index_build_finish", "rvc_index_build_abort",
     "rvc_convert_geometry", "rvc_convert", "rvc_convert_device", "rvc_convert_info", "rvc_sola_stitch", "rvc_highpass",
     "rvc_resample_geometry", "rvc_resample", "rvc_resample_device", "rvc_change_rms", "rvc_convert_file", "rvc_convert_file_device", "rvc_convert_file_info",
+    "rvc_set_f0_override_stream", "rvc_set_f0_override_hold", "rvc_set_f0_curve", "rvc_f0_curve_grid", "rvc_convert_f0",
 ]
 
 
@@ -380,6 +381,13 @@ def lib():
         L.rvc_debug_f0_hybrid.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, fp, fp]
     if hasattr(L, "rvc_debug_pm") or not override:
         L.rvc_debug_pm.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, fp, fp, fp, vp, fp]
+    if hasattr(L, "rvc_set_f0_override_stream") or not override:
+        L.rvc_set_f0_override_stream.argtypes = [vp, C.c_int, fp, sz]
+        L.rvc_set_f0_override_hold.argtypes = [vp, C.c_int]
+        L.rvc_set_f0_curve.argtypes = [vp, C.POINTER(C.c_double), fp, sz]
+        L.rvc_f0_curve_grid.argtypes = [vp, sz, fp, sz]
+        L.rvc_convert_f0.argtypes = [vp, fp, sz, C.POINTER(sz)]
+        L.rvc_debug_f0_override.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int, fp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.c_int, fp]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
     if hasattr(L, "rvc_model_speakers") or not override:

@@ -49,8 +49,21 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="sample-rate conversion: blocks = the streaming converter block by block (default), device = the whole-signal converter")
     p.add_argument("--sid", type=int, default=None, help="speaker id of a multi-speaker model (default: the speaker baked into the model file)")
     p.add_argument("--sid-mix", default=None, help="a blend of up to 8 speakers as id:weight pairs, e.g. 0:0.3,2:0.7 (weights are normalised)")
+    p.add_argument("--f0-file", default=None, metavar="PATH",
+                   help="an f0 curve for the recording, upstream's format: one `t,f0` pair per line (seconds, Hz; 0 = unvoiced), blank lines and # comments "
+                        "ignored.  Frames between the first and the last time take the curve instead of the tracker's value.  Unlike upstream the curve is "
+                        "transposed like any f0: it is absolute only with --pitch 0")
+    p.add_argument("--f0-out", default=None, metavar="PATH", help="write the f0 the synthesizer got, one `t,f0` pair per 10 ms frame (the format --f0-file reads)")
     p.add_argument("--device", type=int, default=-1)
     a = p.parse_args(argv)
+    if a.f0_file is not None:
+        try:
+            with open(a.f0_file) as fh:
+                a.f0_curve = parse_f0_curve(fh.read())
+        except (OSError, ValueError) as x:
+            p.error("--f0-file %s: %s" % (a.f0_file, x))
+    else:
+        a.f0_curve = None
     if a.sid is not None and a.sid_mix is not None:
         p.error("--sid and --sid-mix exclude each other")
     if a.sid is not None and a.sid < 0:
@@ -100,6 +113,39 @@ def f0_arg(text: str) -> str:
     if text not in F0_CHOICES:
         raise argparse.ArgumentTypeError("invalid choice: %r (choose from %s, or hybrid[a+b..])" % (text, ", ".join(F0_CHOICES)))
     return text
+
+
+def parse_f0_curve(text: str):
+    """upstream's f0 curve file: one `t,f0` pair per line, seconds and Hz; blank lines and # comments (whole lines or trailing) are ignored.  -> (t float64 [n],
+    hz float32 [n]) with n >= 1, t strictly increasing, hz 0 or in (0, 20000]: what rvc_set_f0_curve takes.  ValueError names the line"""
+    t, hz = [], []
+    for no, line in enumerate(text.splitlines(), 1):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        parts = line.split(",")
+        try:
+            if len(parts) != 2:
+                raise ValueError
+            ti, hi = float(parts[0]), float(parts[1])
+        except ValueError:
+            raise ValueError("line %d: %r is no `t,f0` pair" % (no, line)) from None
+        if not np.isfinite(ti) or (t and ti <= t[-1]):
+            raise ValueError("line %d: the time %r is not finite or not after the line before" % (no, parts[0].strip()))
+        if not 0.0 <= hi <= 20000.0:
+            raise ValueError("line %d: the f0 %r is not 0 or in (0, 20000] Hz" % (no, parts[1].strip()))
+        t.append(ti); hz.append(hi)
+    if not t:
+        raise ValueError("no `t,f0` pair")
+    return np.asarray(t, np.float64), np.asarray(hz, np.float32)
+
+
+def format_f0_curve(hz) -> str:
+    """one `t,f0` line per 10 ms frame: what --f0-out writes and parse_f0_curve reads back to the same float32 values.  The file is always one --f0-file
+    accepts: a frame that is not a number or negative is written as 0 (unvoiced), one above 20000 Hz (a transposed value can be) as 20000"""
+    hz = np.asarray(hz, np.float32)
+    hz = np.where(hz >= 0, np.minimum(hz, np.float32(20000.0)), np.float32(0.0))
+    return "".join("%.2f,%.9g\n" % (j / 100.0, float(v)) for j, v in enumerate(hz))
 
 
 def parse_sid_mix(text: str) -> dict:
@@ -162,6 +208,10 @@ def main(argv=None) -> int:
     eng = RvcInfer(a.data or W.default_zoo_root("full"), device=a.device)
     eng.load_contentvec(a.version)
     eng.load_model(a.model)
+    if a.f0_out is not None and not eng.model_has_f0():      # (before anything is converted or written)
+        print("--f0-out: %s was trained without pitch guidance and has no f0" % a.model, file=sys.stderr)
+        eng.close()
+        return 2
     if eng.model_has_f0():      # (a model trained without pitch guidance runs no tracker: --f0 names none for it)
         if a.f0.startswith("hybrid["):
             eng.load_f0_hybrid(a.f0[len("hybrid["):-1].split("+"), mode=a.f0_hybrid_mode)
@@ -178,6 +228,8 @@ def main(argv=None) -> int:
     eng.set_pitch_semitones(a.pitch)
     eng.set_formant_shift(a.formant)
     eng.set_protect(a.protect)
+    if a.f0_curve is not None:
+        eng.set_f0_curve(*a.f0_curve)
     if a.resampler == "device" or a.rms_mix_rate < 1.0:
         y, out_rate = eng.convert_file(x, rate, k=a.window, context=a.context, crossfade=a.crossfade, pitch_shift=0, highpass=a.highpass, rms_mix_rate=a.rms_mix_rate,
                                        out_rate=a.rate)
@@ -191,6 +243,9 @@ def main(argv=None) -> int:
         if out_rate != model_rate:
             y = _resample(eng, y, model_rate, out_rate)
         write_wav(a.output, y, out_rate)
+    if a.f0_out is not None:
+        with open(a.f0_out, "w") as fh:
+            fh.write(format_f0_curve(eng.convert_f0()))
     print("%s: %.2f s at %d Hz from %d windows in %d batches; device ms: high-pass %.2f, model %.2f, stitch %.2f, total %.2f"
           % (a.output, len(y) / out_rate, out_rate, info["windows"], info["batches"], info["ms_highpass"], info["ms_model"], info["ms_stitch"], info["ms_total"]))
     eng.close()

@@ -85,9 +85,27 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
     hipStream_t st = e->stream;
     const size_t S = (size_t)e->n_streams, W = g.windows, batches = (W + S - 1) / S;
     const size_t sola_len = g.X * g.zc, search = g.Q * g.zc, frame = g.H * g.zc, ylen = g.return_length * g.zc;
-    e->conv.valid = false;
+    e->conv.valid = false; e->conv_f0_valid = false;
     HIPCHK(hipDeviceSynchronize());
-    reset_state(e);
+    reset_state(e);          // (pending f0 overrides of the streams go with it: a conversion uses the curve alone)
+    // f0 from outside.  The f0 front end takes the last fr samples of a window and reflect-pads them by 512, so f0 row t of window w is
+    // centred on sample 160 (w H - C) + (n - fr) + 160 t of the recording: grid row w H - Cg + t with Cg = C - (n - fr) / 160.  (fr = n for every geometry
+    // convert_geometry makes; the check stays.)  The curve's grid is built once; each batch's plan gathers from it, and the conditioned rows of each window's
+    // hop [Cg, Cg + H) go back onto the grid for rvc_convert_f0
+    const bool has_f0 = e->sy->has_f0;
+    const size_t fr = 5120 * ((g.sf + 799) / 5120 + 1) - 160;
+    if (has_f0 && (fr > g.n || (g.n - fr) % 160 != 0 || (g.n - fr) / 160 > g.C)) throw ShapeError("convert: the f0 rows of a window are not centred on the recording's 10 ms grid");
+    const int Cg = (int)(g.C - (g.n - fr) / 160);
+    const bool curve = has_f0 && e->curve_n > 0;
+    struct CurveGuard { rvc_engine *e; ~CurveGuard() { e->conv_curve = false; e->ov_dirty = true; } } curve_guard{e};
+    DevBuf<float> f0grid;
+    bool export_ok = has_f0;
+    if (has_f0) f0grid.alloc(g.Nf);
+    if (curve) {
+        e->curve_grid.alloc(g.Nf);
+        launch_f0_curve_grid(st, e->curve_t.get(), e->curve_hz.get(), (int)e->curve_n, e->curve_grid.get(), (long long)g.Nf);
+        e->conv_curve = true;
+    }
     DevTimer t_total, t_hp;
     t_total.start(st);
     DevBuf<float> filtered;
@@ -110,16 +128,26 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
         hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, (long long)n, win.get(), (int)g.n, (long long)w0, nw,
                            (int)g.H, (int)g.C);
         size_t got = 0;
+        if (curve) e->conv_call = F0OvCall{e->curve_grid.get(), (long long)g.Nf, 1, (int)w0, nw, (int)g.H, Cg, 0};
         const rvc_status rc = infer_common(e, win.get(), true, g.n, g.sf, pitch_shift, (uint32_t)g.skip_head, (uint32_t)g.return_length, y.get(), true, ylen, &got, true);
         if (rc != RVC_OK) return rc;
         if (got != ylen) throw ShapeError("convert: the synthesizer does not produce sample_rate / 100 samples per frame");
         ev[3 * b + 1].record(st);
         launch_stitch(st, y.get(), (long long)ylen, (int)w0, nw, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out, (long long)g.out_samples);
         ev[3 * b + 2].record(st);
+        // the batch's conditioned f0 rows onto the grid, behind the timed sections: in ms[3] (total), in neither ms[1] (model) nor ms[2] (stitch).  The plan's rows
+        // stay until the next batch's pitch tail, which this stream orders behind the launch
+        if (export_ok) {
+            const Plan *pl = e->last_plan;      // (streams in several formant buckets ran through several plans: no export then)
+            if (pl && !pl->key.bucket && pl->d_f0 && pl->key.B == (int)S && (size_t)Cg + g.H <= (size_t)pl->Tm)
+                launch_f0_export(st, pl->d_f0, pl->Tm, (int)w0, nw, (int)g.H, Cg, f0grid.get(), (long long)g.Nf);
+            else export_ok = false;
+        }
     }
     t_total.stop(st);
     e->conv.offsets.assign(W, 0);
     HIPCHK(hipMemcpyAsync(e->conv.offsets.data(), offs.get(), W * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (export_ok) { e->conv_f0.assign(g.Nf, 0.f); HIPCHK(hipMemcpyAsync(e->conv_f0.data(), f0grid.get(), g.Nf * sizeof(float), hipMemcpyDeviceToHost, st)); }
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     double ms_model = 0, ms_stitch = 0;
@@ -130,7 +158,7 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
     }
     e->conv.windows = W; e->conv.batches = batches;
     e->conv.ms[0] = highpass ? (double)t_hp.ms() : 0.0; e->conv.ms[1] = ms_model; e->conv.ms[2] = ms_stitch; e->conv.ms[3] = (double)t_total.ms();
-    e->conv.valid = true;
+    e->conv.valid = true; e->conv_f0_valid = export_ok;
     if (keep_filtered) *keep_filtered = std::move(filtered);
     return RVC_OK;
 }

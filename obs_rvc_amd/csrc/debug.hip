@@ -731,6 +731,64 @@ int rvc_debug_pm(rvc_engine *e, const float *audio, int B, int n, int frame, int
     });
 }
 
+// test aid: the kernels of "f0 from outside" alone (f0_override.hip.h; tests/test_gpu_f0_override.py), through the launches the engine uses (include/rvc_mi355x_debug.h)
+int rvc_debug_f0_override(rvc_engine *e, int op, const float *rows, int B, int Tm, const float *ov, const int *ov_n, const long long *geo, const double *t, int n_bp, float *out)
+{
+    return (int)guarded(e, [&]() {
+        if (op < 0 || op > 3 || !out || !ov) throw ShapeError("f0 override: op in [0, 3], arrays");
+        const long long LIM = 1LL << 24;
+        hipStream_t st = e->stream;
+        if (op == 2) {
+            if (!t || !geo || n_bp < 1 || n_bp > LIM || geo[0] < 1 || geo[0] > LIM) throw ShapeError("f0 override: breakpoints in [1, 2^24], Nf in [1, 2^24]");
+            const size_t Nf = (size_t)geo[0];
+            DevBuf<double> d_t; DevBuf<float> d_hz, d_g;
+            d_t.alloc((size_t)n_bp); d_hz.alloc((size_t)n_bp); d_g.alloc(Nf);
+            HIPCHK(hipMemcpy(d_t.get(), t, (size_t)n_bp * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_hz.get(), ov, (size_t)n_bp * sizeof(float), hipMemcpyHostToDevice));
+            launch_f0_curve_grid(st, d_t.get(), d_hz.get(), n_bp, d_g.get(), (long long)Nf);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipMemcpy(out, d_g.get(), Nf * sizeof(float), hipMemcpyDeviceToHost));
+            return RVC_OK;
+        }
+        if (!rows || B < 1 || B > 64 || Tm < 1 || Tm > F0_OV_ROWS) throw ShapeError("f0 override: B in [1, 64], Tm in [1, 1024]");
+        const size_t bt = (size_t)B * Tm;
+        DevBuf<float> d_rows, d_out, d_ov; DevBuf<int> d_cnt; DevBuf<F0OvCall> d_call;
+        d_rows.alloc(bt);
+        HIPCHK(hipMemcpy(d_rows.get(), rows, bt * sizeof(float), hipMemcpyHostToDevice));
+        F0OvCall call{};
+        if (op == 0) {
+            if (!ov_n) throw ShapeError("f0 override: counts");
+            for (int b = 0; b < B; b++) if (ov_n[b] < 0 || ov_n[b] > Tm) throw ShapeError("f0 override: a count outside [0, Tm]");
+            d_ov.alloc((size_t)B * F0_OV_ROWS); d_cnt.alloc((size_t)B);
+            HIPCHK(hipMemcpy(d_ov.get(), ov, (size_t)B * F0_OV_ROWS * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_cnt.get(), ov_n, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+        } else {
+            if (!geo || geo[0] < 1 || geo[0] > LIM || geo[1] < 0 || geo[1] > LIM || geo[2] < 0 || geo[2] > B || geo[3] < 1 || geo[3] > F0_OV_ROWS || geo[4] < 0 || geo[4] > F0_OV_ROWS)
+                throw ShapeError("f0 override: geometry {Nf, w0, nw, H, C}");
+            if (op == 3 && geo[4] + geo[3] > Tm) throw ShapeError("f0 override: the hop [C, C + H) lies outside the window");
+            const size_t Nf = (size_t)geo[0];
+            d_ov.alloc(Nf);
+            HIPCHK(hipMemcpy(d_ov.get(), op == 1 ? ov : out, Nf * sizeof(float), hipMemcpyHostToDevice));
+            call = F0OvCall{d_ov.get(), (long long)Nf, 1, (int)geo[1], (int)geo[2], (int)geo[3], (int)geo[4], 0};
+        }
+        if (op == 3) {
+            launch_f0_export(st, d_rows.get(), Tm, (int)geo[1], (int)geo[2], (int)geo[3], (int)geo[4], d_ov.get(), geo[0]);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipMemcpy(out, d_ov.get(), (size_t)geo[0] * sizeof(float), hipMemcpyDeviceToHost));
+            return RVC_OK;
+        }
+        d_out.alloc(bt); d_call.alloc(1);
+        HIPCHK(hipMemcpy(d_call.get(), &call, sizeof call, hipMemcpyHostToDevice));
+        launch_f0_override(st, B, Tm, d_rows.get(), d_out.get(), d_call.get(), d_cnt.get(), d_ov.get(), nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(out, d_out.get(), bt * sizeof(float), hipMemcpyDeviceToHost));
+        return RVC_OK;
+    });
+}
+
 // test aid: the caller-side post-processing, the session's ring updates and a converter of several streams (chunk.hip.h, session.hip.h, resample.hip.h;
 // tests/test_gpu_post.py) on the caller's arrays with the caller's stream strides, each launch queued as the session queues it (engine_int.h launch_post_* /
 // launch_ring_* / launch_resampler).  Every size is checked against the strides on the host before anything is queued.

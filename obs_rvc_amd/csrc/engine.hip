@@ -7,6 +7,7 @@
 #include "engine_int.h"
 #include "chunk.hip.h"
 #include "crossfade.hip.h"
+#include "f0_override.hip.h"
 #include <chrono>
 
 // The HIP runtime multiplexes all streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The engine runs four
@@ -39,6 +40,21 @@ void launch_protect_mix(hipStream_t s, int B, const StreamState *st, const float
                         float *phone, int ph_cs, long long ph_bs)
 {
     hipLaunchKernelGGL(protect_mix_kernel, protect_grid(R, B, C), dim3(PROTECT_ROWS, PROTECT_LANES), 0, s, st, pitchf, cv, cv_cs, cv_bs, C, T, skip_head, R, phone, ph_cs, ph_bs);
+}
+
+// f0 from outside (f0_override.hip.h): the three launches, for the engine below and for rvc_debug_f0_override (debug.hip)
+void launch_f0_override(hipStream_t s, int B, int Tm, const float *f, float *out, const F0OvCall *call, const int *cnt, const float *rows, const int *map)
+{
+    hipLaunchKernelGGL(f0_override_kernel, dim3((Tm + 255) / 256, B), dim3(256), 0, s, f, out, Tm, call, cnt, rows, map);
+}
+void launch_f0_curve_grid(hipStream_t s, const double *t, const float *hz, int n, float *grid, long long Nf)
+{
+    hipLaunchKernelGGL(f0_curve_grid_kernel, dim3((unsigned)((Nf + 255) / 256)), dim3(256), 0, s, t, hz, n, grid, Nf);
+}
+void launch_f0_export(hipStream_t s, const float *f0, int Tm, int w0, int nw, int H, int C, float *grid, long long Nf)
+{
+    if (nw < 1 || H < 1) return;
+    hipLaunchKernelGGL(f0_export_kernel, dim3((H + 255) / 256, nw), dim3(256), 0, s, f0, Tm, w0, H, C, grid, Nf);
 }
 
 // the caller-side post-processing launches (chunk.hip.h), B streams each: rvc_envelop_mixing, sola_step_host and rvc_session_process queue them through
@@ -103,6 +119,21 @@ static void reset_state(rvc_engine *e)
     for (int b = 0; b < e->n_streams; b++) { memset(&st[b], 0, sizeof(StreamState)); st[b].stream_id = e->stream_id0 + (uint32_t)b; }
     HIPCHK(hipMemcpy(e->d_state, st.data(), sizeof(StreamState) * e->n_streams, hipMemcpyHostToDevice));
     e->pushed_valid = false;       // (the per-stream multipliers live in StreamState)
+    for (auto &v : e->ov) v.clear();      // pending f0 overrides go with the state; the curve of rvc_set_f0_curve stays
+    e->ov_dirty = true;
+}
+
+// the device block of the f0 overrides: F0OvCall (64 bytes) | one count per stream | rows [streams][F0_OV_ROWS].  `streams` is e->ov.size(): the engine's own
+// stream count, also while a bucket plan is being built on fewer
+static_assert(sizeof(F0OvCall) <= 64, "the override block keeps 64 bytes for the call");
+static inline size_t ov_rows_off(size_t S) { return 64 + (S * sizeof(int) + 63) / 64 * 64; }
+static void ensure_ov(rvc_engine *e)
+{
+    if (e->d_ov) return;
+    const size_t S = e->ov.size(), bytes = ov_rows_off(S) + S * F0_OV_ROWS * sizeof(float);
+    HIPCHK(hipMalloc(&e->d_ov, bytes));
+    HIPCHK(hipMemset(e->d_ov, 0, bytes));
+    e->ov_dirty = true;
 }
 
 // CU partition for the two concurrent branches of a chunk at low stream counts: the f0 branch (RMVPE: ~140 short weight-streaming
@@ -217,6 +248,8 @@ static void alloc_state(rvc_engine *e)
     if (e->d_state) (void)hipFree(e->d_state);
     if (e->d_state_bucket) { (void)hipFree(e->d_state_bucket); e->d_state_bucket = nullptr; }
     if (e->d_bucket_idx) { (void)hipFree(e->d_bucket_idx); e->d_bucket_idx = nullptr; }
+    if (e->d_ov) { (void)hipFree(e->d_ov); e->d_ov = nullptr; }
+    e->ov.assign((size_t)e->n_streams, std::vector<float>());
     HIPCHK(hipMalloc(&e->d_state, sizeof(StreamState) * e->n_streams));
     e->settings.resize(e->n_streams, e->settings_default);   // existing streams keep their settings, new ones get the default
     reset_state(e);
@@ -226,8 +259,42 @@ static void alloc_state(rvc_engine *e)
 static inline bool is_crepe(int method) { return method == RVC_F0_CREPE || method == RVC_F0_CREPE_TINY; }
 // the f0 branch of the engine's method: RMVPE's network and salience decode, the YIN launch, PM's three launches, CREPE's or FCPE's network and decoder, or -- a hybrid -- several of
 // them and the launch that combines their rows; behind each the same pitch tail (shift, cache, get_f0_post)
+// f0 from outside: between the method's row buffer and the pitch tail, one launch that selects every row against the override the call
+// brings for it.  The launch reads the engine's override block (push_overrides fills it in front of the chunk), a bucket plan through the bucket's stream numbers
+static const float *add_f0_override(rvc_engine *e, Plan &pl, int B, const float *f0)
+{
+    ensure_ov(e);
+    const int Tm = pl.Tm;
+    if (Tm < 1 || Tm > F0_OV_ROWS) throw ShapeError("f0 override: the f0 window has more than 1024 rows");
+    float *out = pl.arena.floats((size_t)B * Tm);
+    const F0OvCall *call = (const F0OvCall *)e->d_ov; const int *cnt = (const int *)(e->d_ov + 64); const float *rows = (const float *)(e->d_ov + ov_rows_off(e->ov.size()));
+    const int *map = pl.key.bucket ? e->d_bucket_idx : nullptr;
+    pl.ops.push_back([=](hipStream_t s) { launch_f0_override(s, B, Tm, f0, out, call, cnt, rows, map); });
+    add_stamp(pl, "f0.override");
+    { T1 t; t.p = out; t.B = B; t.C = 1; t.T = Tm; t.ld = Tm; t.bs = Tm; add_tap(pl, "ov.f0", t); }
+    return out;
+}
+
 static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, bool update_cache, size_t hubert_length, float **pitchf_out, int **pitch_out)
 {
+    if (pl.key.f0_override) {
+        // the method's rows as a plain buffer -- RMVPE through the stand-alone decode of a hybrid of one, which is RMVPE bit for bit (section 25) --, the select, the tail
+        const float *f0 = nullptr;
+        if (e->f0_method == RVC_F0_YIN) f0 = build_yin(e, pl, B, L, frame16k);
+        else if (e->f0_method == RVC_F0_PM) f0 = build_pm(e, pl, B, L, frame16k);
+        else if (is_crepe(e->f0_method)) f0 = build_crepe(e, pl, B, L, frame16k, e->f0_method);
+        else if (e->f0_method == RVC_F0_FCPE) f0 = build_fcpe(e, pl, B, L, frame16k);
+        else if (e->f0_method == RVC_F0_RMVPE) {
+            if (!e->rm) throw std::logic_error("f0 method");
+            const T1 sal = build_rmvpe(e, pl, B, L, frame16k, update_cache);
+            const float *rows[HYBRID_MEMBERS_MAX] = {};
+            f0 = add_f0_hybrid(e, pl, B, 1, RVC_HYBRID_VOTE, rows, 0, sal);
+        }
+        if (f0) {
+            build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, add_f0_override(e, pl, B, f0));
+            return;
+        }
+    }
     if (e->f0_method == RVC_F0_YIN) {
         const float *f0 = build_yin(e, pl, B, L, frame16k);
         build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
@@ -257,7 +324,7 @@ static void build_f0(rvc_engine *e, Plan &pl, int B, size_t L, size_t frame16k, 
             else throw std::logic_error("f0 method");
         }
         const float *f0 = add_f0_hybrid(e, pl, B, n, pl.key.hybrid_mode, rows, rm_at, sal);
-        build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, f0);
+        build_pitch_post(e, pl, B, T1{}, update_cache, frame16k, hubert_length, pitchf_out, pitch_out, pl.key.f0_override ? add_f0_override(e, pl, B, f0) : f0);
         return;
     }
     if (is_crepe(e->f0_method)) {
@@ -576,6 +643,12 @@ static PlanKey plan_key(rvc_engine *e, int mode, size_t L, size_t frame16k, uint
     }
     k.crepe_decoder = has_crepe ? e->crepe_decoder : 0;
     k.fcpe_threshold = has_fcpe ? e->fcpe_threshold : 0.0;          // FCPE's voicing threshold is baked into its decoder's launch
+    // f0 from outside: whether ANY stream of the plan brings an override -- or the call is a conversion window under a curve -- decides the
+    // plan's launch list (the rule of with_protect); which values is no part of the key.  A model without pitch guidance ignores both
+    if (!nof0 && mode != 1 && k.f0_method) {
+        if (e->conv_curve) k.f0_override = mode == 0;
+        else for (int j = 0; j < k.B; j++) { const size_t s = (size_t)(bucket_ids ? (*bucket_ids)[j] : j); k.f0_override = k.f0_override || (s < e->ov.size() && !e->ov[s].empty()); }
+    }
     k.with_index = mode == 0 && e->index.rows && e->index_rate > 0.f;
     // consonant protection (protect.hip.h): one more launch, only on plans that use the index and only when one of the plan's streams has it on.  Which value
     // a stream has is no part of the key: the kernel reads it every chunk.  (Upstream applies protect only where it has a pitch)
@@ -645,6 +718,68 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
         HIPCHK(hipEventRecord(e->ev_cp, e->stream));
         HIPCHK(hipStreamWaitEvent(e->aux[0], e->ev_cp, 0));
         HIPCHK(hipStreamWaitEvent(e->aux[2], e->ev_cp, 0));
+    }
+}
+
+// f0 from outside: what a call does about the pending overrides.
+// override_fits: an override longer than the plan's f0 window is refused by the call that would consume it, before anything is queued.
+static void override_fits(rvc_engine *e, const Plan &pl, const std::vector<int> *ids = nullptr)
+{
+    if (!pl.key.f0_override || e->conv_curve) return;
+    for (int j = 0; j < pl.key.B; j++) {
+        const size_t s = (size_t)(ids ? (*ids)[j] : j);
+        if (s < e->ov.size() && e->ov[s].size() > (size_t)pl.Tm) throw ShapeError("f0 override: more rows than the call's f0 window has");
+    }
+}
+// push_overrides: in front of a chunk whose plan has the select, the override block goes to the device when it is behind the host's -- the call, the counts and the
+// rows of the streams that have any, from one pinned block -- on the stream the chunk's f0 branch is ordered behind: the main stream (the branch forks from it;
+// a replayed graph is launched into it; the copy is never captured), or the f0 stream itself for a pipelined call, whose front branches do not fork.
+static void push_overrides(rvc_engine *e, const Plan &pl, bool pipe)
+{
+    if (!pl.key.f0_override || !e->d_ov) return;
+    if (!e->conv_curve && !e->ov_dirty) return;
+    hipStream_t cs = pipe ? e->aux[0] : e->stream;
+    if (e->ov_stream && e->ov_stream != cs) HIPCHK(hipStreamSynchronize(e->ov_stream));      // (a call of the other kind: its copies and its select ran over there)
+    e->ov_stream = cs;
+    const size_t S = e->ov.size(), head = 64 + S * sizeof(int);
+    size_t need = head;
+    if (!e->conv_curve) for (auto &v : e->ov) need += v.size() * sizeof(float);
+    rvc_engine::OvBlock &blk = e->ov_ring[e->ov_slot++ & 7u];
+    if (blk.used) HIPCHK(hipEventSynchronize(blk.ev));      // a block is rewritten only after the copies that read it have completed
+    if (blk.cap < need) {
+        if (blk.p) (void)hipHostFree(blk.p);
+        blk.p = nullptr; blk.cap = 0;
+        const size_t cap = (need + 4095) / 4096 * 4096;
+        HIPCHK(hipHostMalloc((void **)&blk.p, cap));
+        blk.cap = cap;
+    }
+    memset(blk.p, 0, head);
+    F0OvCall *call = (F0OvCall *)blk.p; int *cnt = (int *)(blk.p + 64);
+    if (e->conv_curve) *call = e->conv_call;
+    else for (size_t s = 0; s < S; s++) cnt[s] = (int)e->ov[s].size();
+    HIPCHK(hipMemcpyAsync(e->d_ov, blk.p, head, hipMemcpyHostToDevice, cs));
+    if (!e->conv_curve) {
+        size_t at = head;
+        for (size_t s = 0; s < S; s++) {
+            const size_t nb = e->ov[s].size() * sizeof(float);
+            if (!nb) continue;
+            memcpy(blk.p + at, e->ov[s].data(), nb);
+            HIPCHK(hipMemcpyAsync(e->d_ov + ov_rows_off(S) + s * F0_OV_ROWS * sizeof(float), blk.p + at, nb, hipMemcpyHostToDevice, cs));
+            at += nb;
+        }
+    }
+    if (!blk.ev) HIPCHK(hipEventCreateWithFlags(&blk.ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(blk.ev, cs)); blk.used = true;
+    e->ov_dirty = e->conv_curve;      // (a conversion leaves its own call in the block)
+}
+// consume_overrides: behind the call that read them, unless they are held
+static void consume_overrides(rvc_engine *e, const std::vector<int> *ids = nullptr)
+{
+    if (e->ov_hold) return;
+    const size_t n = ids ? ids->size() : e->ov.size();
+    for (size_t j = 0; j < n; j++) {
+        const size_t s = ids ? (size_t)(*ids)[j] : j;
+        if (s < e->ov.size() && !e->ov[s].empty()) { e->ov[s].clear(); e->ov_dirty = true; }
     }
 }
 
@@ -726,8 +861,10 @@ static rvc_status run_buckets(rvc_engine *e, std::vector<BucketRun> &work, const
 {
     for (auto &w : work)
         { bool ok = false; for (auto &p : e->plans) ok = ok || p.get() == w.pl; if (!ok) throw std::logic_error("bucketed call: a plan of this call left the cache"); }
+    for (auto &w : work) override_fits(e, *w.pl, &w.ids);
     for (auto &w : work) {
         Plan *pl = w.pl; const std::vector<int> &ids = w.ids; const int Bk = (int)ids.size();
+        push_overrides(e, *pl, false);
         HIPCHK(hipMemcpyAsync(e->d_bucket_idx, ids.data(), sizeof(int) * Bk, hipMemcpyHostToDevice, e->stream));
         hipLaunchKernelGGL(state_gather_kernel, dim3(Bk), dim3(256), 0, e->stream, e->d_state, e->d_state_bucket, e->d_bucket_idx, 0);
         for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(pl->d_in + (size_t)j * pl->key.L, in(ids[j]), pl->key.L * sizeof(float), in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
@@ -735,6 +872,7 @@ static rvc_status run_buckets(rvc_engine *e, std::vector<BucketRun> &work, const
         run_plan(e, *pl);
         for (int j = 0; j < Bk; j++) HIPCHK(hipMemcpyAsync(out(ids[j]), pl->audio.p + (size_t)j * pl->N, pl->N * sizeof(float), out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
         hipLaunchKernelGGL(state_gather_kernel, dim3(Bk), dim3(256), 0, e->stream, e->d_state, e->d_state_bucket, e->d_bucket_idx, 1);
+        consume_overrides(e, &ids);
         HIPCHK(hipStreamSynchronize(e->stream));        // (ids / the pinned-less host buffers of this bucket are free again; the next bucket reuses the state block)
     }
     e->last_knn_rows = 0;
@@ -810,6 +948,8 @@ void rvc_destroy(rvc_engine *e)
     if (e->h_cp) (void)hipHostFree(e->h_cp);
     if (e->h_status) (void)hipHostFree(e->h_status);
     if (e->h_ctl) (void)hipHostFree(e->h_ctl);
+    if (e->d_ov) (void)hipFree(e->d_ov);
+    for (auto &b : e->ov_ring) { if (b.p) (void)hipHostFree(b.p); if (b.ev) (void)hipEventDestroy(b.ev); }
     for (auto &kv : e->ftabs) { (void)hipFree(kv.second.tab); (void)hipFree(kv.second.kb); }
     for (int i = 0; i < 8; i++) if (e->ev_up[i]) (void)hipEventDestroy(e->ev_up[i]);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -1033,7 +1173,10 @@ rvc_status rvc_pitch(rvc_engine *e, const float *input, size_t n, int32_t pitch_
         Plan *pl = get_plan(e, plan_key(e, 2, n, sample_frame_16k_size, 0, 0));
         *out_len = (size_t)pl->Tm;
         if (cap < (size_t)pl->Tm) return RVC_SHAPE;
+        override_fits(e, *pl);
+        push_overrides(e, *pl, false);
         run_single_input(e, pl, input, n, pitch_shift);
+        consume_overrides(e);
         HIPCHK(hipMemcpyAsync(out, pl->d_f0, (size_t)pl->Tm * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         queue_status(e);
         HIPCHK(hipStreamSynchronize(e->stream));
@@ -1082,10 +1225,12 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
     if (out_len) *out_len = pl->N;
     if (cap < pl->N) return RVC_SHAPE;
     const int B = pl->key.B;
+    override_fits(e, *pl);
     {
         std::vector<uint32_t> Rs((size_t)B, return_length);
         push_call_params(e, pitch_shift, shifts, Rs.data());
     }
+    push_overrides(e, *pl, pipe);
     // Device-resident callers: the first kernels read the caller's buffer and the last one writes the caller's buffer (eager launches
     // take the pointers at launch time) -- no staging copy in front of the chunk, no copy behind it.  A captured graph bakes its
     // pointers and keeps both copies; pipelined calls keep the input copy (it decouples the caller's buffer from the chunk in flight).
@@ -1109,6 +1254,7 @@ static rvc_status infer_common(rvc_engine *e, const void *input, bool input_on_d
     e->pipe_now = pipe;
     run_plan(e, *pl);
     e->pipe_now = false;
+    if (!e->conv_curve) consume_overrides(e);
     if (!direct_out)
         HIPCHK(hipMemcpy2DAsync(out, cap * sizeof(float), pl->audio.p, pl->N * sizeof(float), pl->N * sizeof(float), B,
                                 out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
@@ -1393,6 +1539,76 @@ rvc_status rvc_set_f0_snap(rvc_engine *e, uint32_t pitch_class_mask, double stre
 rvc_status rvc_set_f0_snap_stream(rvc_engine *e, int stream, uint32_t pitch_class_mask, double strength) { return set_f0_snap(e, &stream, pitch_class_mask, strength); }
 rvc_status rvc_set_protect(rvc_engine *e, double protect) { return set_protect(e, nullptr, protect); }
 rvc_status rvc_set_protect_stream(rvc_engine *e, int stream, double protect) { return set_protect(e, &stream, protect); }
+
+// f0 from outside.  A set call only records: the rows travel in front of the next chunk of a plan that has the select (push_overrides)
+static const char *f0_value_bad(float v, bool nan_ok)
+{
+    if (v != v) return nan_ok ? nullptr : "a curve value is NaN";
+    return v >= 0.f && v <= F0_OV_MAX_HZ ? nullptr : "a value is negative, infinite or above 20000 Hz";
+}
+rvc_status rvc_set_f0_override_stream(rvc_engine *e, int stream, const float *hz, size_t n)
+{
+    return guarded(e, [&]() {
+        if (stream < 0 || (size_t)stream >= e->ov.size()) throw ShapeError("f0 override: stream out of range");
+        if (!hz) n = 0;
+        if (n > (size_t)F0_OV_ROWS) throw ShapeError("f0 override: more than 1024 rows");
+        for (size_t i = 0; i < n; i++) if (const char *bad = f0_value_bad(hz[i], true)) throw ShapeError(std::string("f0 override: ") + bad);
+        if (n == 0 && e->ov[stream].empty()) return RVC_OK;
+        e->ov[stream].assign(hz, hz + n);
+        e->ov_dirty = true;
+        return RVC_OK;
+    });
+}
+rvc_status rvc_set_f0_override_hold(rvc_engine *e, int hold)
+{
+    return guarded(e, [&]() {
+        if (hold != 0 && hold != 1) throw ShapeError("f0 override hold: 0 or 1");
+        e->ov_hold = hold != 0;
+        return RVC_OK;
+    });
+}
+rvc_status rvc_set_f0_curve(rvc_engine *e, const double *t_sec, const float *hz, size_t n)
+{
+    return guarded(e, [&]() {
+        if (n == 0) { e->curve_t.reset(); e->curve_hz.reset(); e->curve_n = 0; return RVC_OK; }
+        if (!t_sec || !hz) throw ShapeError("f0 curve: null array");
+        if (n > (size_t)1 << 24) throw ShapeError("f0 curve: more than 2^24 breakpoints");
+        for (size_t i = 0; i < n; i++) {
+            if (!std::isfinite(t_sec[i])) throw ShapeError("f0 curve: a time is not finite");
+            if (i && !(t_sec[i] > t_sec[i - 1])) throw ShapeError("f0 curve: times must be strictly increasing");
+            if (const char *bad = f0_value_bad(hz[i], false)) throw ShapeError(std::string("f0 curve: ") + bad);
+        }
+        DevBuf<double> dt; DevBuf<float> dh;
+        dt.alloc(n); dh.alloc(n);
+        HIPCHK(hipMemcpy(dt.get(), t_sec, n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dh.get(), hz, n * sizeof(float), hipMemcpyHostToDevice));
+        e->curve_t = std::move(dt); e->curve_hz = std::move(dh); e->curve_n = n;
+        return RVC_OK;
+    });
+}
+rvc_status rvc_f0_curve_grid(rvc_engine *e, size_t n_frames, float *out, size_t cap)
+{
+    return guarded(e, [&]() {
+        if (n_frames < 1 || n_frames > (size_t)1 << 30) throw ShapeError("f0 curve grid: frame count out of range");
+        if (!out || cap < n_frames) throw ShapeError("f0 curve grid: output buffer too small");
+        DevBuf<float> g; g.alloc(n_frames);
+        launch_f0_curve_grid(e->stream, e->curve_t.get(), e->curve_hz.get(), (int)e->curve_n, g.get(), (long long)n_frames);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, g.get(), n_frames * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        return RVC_OK;
+    });
+}
+rvc_status rvc_convert_f0(rvc_engine *e, float *hz, size_t cap, size_t *n_frames)
+{
+    return guarded(e, [&]() {
+        if (!e->conv_f0_valid) throw ShapeError("convert_f0: no conversion with a pitch branch has completed on this engine");
+        if (n_frames) *n_frames = e->conv_f0.size();
+        if (!hz || cap < e->conv_f0.size()) throw ShapeError("convert_f0: output buffer too small");
+        std::copy(e->conv_f0.begin(), e->conv_f0.end(), hz);
+        return RVC_OK;
+    });
+}
 
 rvc_status rvc_formant_geometry(size_t return_length, size_t sample_rate, double semitones, size_t out[2])
 {

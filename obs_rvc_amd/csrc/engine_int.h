@@ -9,7 +9,7 @@
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
-// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, f0_hybrid.hip.h, yin.hip.h, pm.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, crossfade.hip.h, stitch.hip.h, ...)
+// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, f0_hybrid.hip.h, yin.hip.h, pm.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, f0_override.hip.h, crossfade.hip.h, stitch.hip.h, ...)
 // or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm2 / igemm2w / igemm_lds / igemm32 / igemm_bf3 / igemm_splitk .hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
@@ -18,6 +18,7 @@
 #include "state.hip.h"
 #include "formant.hip.h"
 #include "f0cond.hip.h"
+#include "f0_override.h"
 #include "igemm_launch.h"
 #include "dev_raii.h"
 #include <hip/hip_ext.h>
@@ -254,13 +255,16 @@ struct PlanKey {
     // ... and, for RVC_F0_HYBRID, the members in the caller's order, 4 bits each from bit 0 (hybrid_pack), and the combination mode; both 0 on every other plan.  A
     // hybrid plan carries crepe_decoder / fcpe_threshold when a CREPE preset / FCPE is among its members
     uint32_t hybrid = 0; int hybrid_mode = 0;
+    // f0 from outside: some stream of the call has a pending override, or the call is a conversion window under a curve.  Such a plan builds
+    // its f0 branch through a plain row buffer, runs f0_override_kernel on it and feeds the pitch tail through f0_in; the values are no part of the key
+    bool f0_override = false;
     int nprobe = 0;               // the engine's index_nprobe (with_index plans; 0 = flat search)
     int knn_k = KNN_K;            // the engine's index_k: the K of the retrieval kernels and the width of d_knn_idx / d_knn_dist
     bool operator==(const PlanKey &o) const
     {
-        return std::tie(mode, B, L, frame16k, skip_head, R, R2, fstage, slot, bucket, with_index, with_protect, bf3, with_taps, plain_plan, f0_method, crepe_decoder, fcpe_threshold, hybrid, hybrid_mode, nprobe, knn_k) ==
+        return std::tie(mode, B, L, frame16k, skip_head, R, R2, fstage, slot, bucket, with_index, with_protect, bf3, with_taps, plain_plan, f0_method, crepe_decoder, fcpe_threshold, hybrid, hybrid_mode, f0_override, nprobe, knn_k) ==
                std::tie(o.mode, o.B, o.L, o.frame16k, o.skip_head, o.R, o.R2, o.fstage, o.slot, o.bucket, o.with_index, o.with_protect, o.bf3, o.with_taps, o.plain_plan, o.f0_method,
-                        o.crepe_decoder, o.fcpe_threshold, o.hybrid, o.hybrid_mode, o.nprobe, o.knn_k);
+                        o.crepe_decoder, o.fcpe_threshold, o.hybrid, o.hybrid_mode, o.f0_override, o.nprobe, o.knn_k);
     }
 };
 
@@ -616,6 +620,17 @@ struct rvc_engine {
     struct ConvertInfo { bool valid = false; size_t windows = 0, batches = 0; std::vector<int32_t> offsets; double ms[4] = {0, 0, 0, 0}; } conv;
     // ... and rvc_convert_file_info of the last completed rvc_convert_file
     struct FileInfo { bool valid = false; double ms[7] = {0, 0, 0, 0, 0, 0, 0}; size_t rate_out = 0; float peak = 0.f; } file;
+    // f0 from outside (f0_override.hip.h).  ov[s]: the pending override rows of stream s (empty = none), for the END of its next f0 window;
+    // ov_hold: an override stays until cleared instead of being consumed by the next call of its stream.  d_ov: the device block a plan with the select reads
+    // every chunk -- F0OvCall | count per stream | rows [streams][1024] -- allocated with the first such plan, freed with the stream states (alloc_state, which
+    // drops the plans that bake its address); ov_dirty: the block is behind `ov`.  ov_ring: pinned blocks the block's copies are queued from, each reused only
+    // after its copies have completed.  curve_*: the recording's curve for rvc_convert* (breakpoints in HBM) and, during a conversion that uses it, its grid
+    std::vector<std::vector<float>> ov; bool ov_hold = false, ov_dirty = true;
+    char *d_ov = nullptr; hipStream_t ov_stream = nullptr;
+    struct OvBlock { char *p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } ov_ring[8]; unsigned ov_slot = 0;
+    rvc::DevBuf<double> curve_t; rvc::DevBuf<float> curve_hz, curve_grid; size_t curve_n = 0;
+    bool conv_curve = false; rvc::F0OvCall conv_call{};          // inside convert_run with a curve: the gather of the batch at hand
+    std::vector<float> conv_f0; bool conv_f0_valid = false;      // the conditioned f0 of the last completed conversion on the 10 ms grid (rvc_convert_f0)
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };
@@ -666,6 +681,12 @@ void launch_fcpe_glu_dw(hipStream_t s, int B, int I, int T, const float *z, int 
 void launch_f0_hybrid(hipStream_t s, int B, int Tm, int n, int mode, const float *const *rows, int rm_at, const float *sal, int sal_cs, long long sal_bs, StreamState *st,
                       float *rm_f0, float *out);
 float *add_f0_hybrid(rvc_engine *e, Plan &pl, int B, int n, int mode, const float *const *rows, int rm_at, const T1 &sal);
+// f0 from outside (f0_override.hip.h), each launch as the engine queues it (engine.hip) and as rvc_debug_f0_override does (debug.hip).
+// launch_f0_override: out [B][Tm] = the rows f [B][Tm] selected against the overrides `call` describes (cnt [streams], rows [streams][1024]; map: the engine stream of
+// each plan stream, or null).  launch_f0_curve_grid: n breakpoints (device) -> grid [Nf].  launch_f0_export: the rows f0 [nw][Tm] of windows w0 .. onto grid [Nf]
+void launch_f0_override(hipStream_t s, int B, int Tm, const float *f, float *out, const F0OvCall *call, const int *cnt, const float *rows, const int *map);
+void launch_f0_curve_grid(hipStream_t s, const double *t, const float *hz, int n, float *grid, long long Nf);
+void launch_f0_export(hipStream_t s, const float *f0, int Tm, int w0, int nw, int H, int C, float *grid, long long Nf);
 T1 build_nsf_source(rvc_engine *e, Plan &pl, int B, float *d_pitchf);
 // the head and the tail of the f0 branch and ContentVec's first layer as plan helpers: the builders above call them, and so does rvc_debug_front (debug.hip)
 void add_conv0_front(Plan &pl, const ConvW &cw, const float *w_raw, const float *gn_g, const float *gn_b, int kt, int st, const T1 &x, const T1 &y);

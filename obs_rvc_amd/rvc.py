@@ -654,6 +654,49 @@ class RvcInfer:
         else:
             self._chk(self._L.rvc_set_protect_stream(self._h, int(stream), float(value)))
 
+    def set_f0_override(self, stream: int, hz):
+        """f0 from outside (rvc_set_f0_override_stream): `hz` rows in Hz for the END of the next f0 window of `stream` -- NaN keeps the tracker's value, 0 is
+        unvoiced, else a finite value in (0, 20000]; None or an empty array clears.  The rows replace the tracker's in front of every pitch setting, so they are
+        transposed like any f0 (absolute values need pitch_shift 0 and set_pitch_semitones(0)).  Consumed by the stream's next infer call unless
+        set_f0_override_hold(True)."""
+        if hz is None or len(hz) == 0:
+            self._chk(self._L.rvc_set_f0_override_stream(self._h, int(stream), None, 0))
+            return
+        hz = np.ascontiguousarray(hz, np.float32)
+        if hz.ndim != 1:
+            raise RvcInferError(5, "f0 override: a one-dimensional array of Hz")
+        self._chk(self._L.rvc_set_f0_override_stream(self._h, int(stream), hz.ctypes.data_as(C.POINTER(C.c_float)), len(hz)))
+
+    def set_f0_override_hold(self, hold: bool):
+        """False (default): an override is consumed by the next infer call of its stream; True: it stays until cleared (rvc_set_f0_override_hold)"""
+        self._chk(self._L.rvc_set_f0_override_hold(self._h, 1 if hold else 0))
+
+    def set_f0_curve(self, t, hz):
+        """The f0 curve of the recording convert() / convert_file() convert next (rvc_set_f0_curve; upstream's "f0 curve file"): breakpoints t (seconds, strictly
+        increasing) and hz (0 = unvoiced, else up to 20000).  Frames between the first and the last time take the curve instead of the tracker's value; the curve
+        is transposed like any f0.  Streaming calls never read it."""
+        t, hz = np.ascontiguousarray(t, np.float64), np.ascontiguousarray(hz, np.float32)
+        if t.ndim != 1 or t.shape != hz.shape or len(t) < 1:
+            raise RvcInferError(5, "f0 curve: two one-dimensional arrays of one length, at least one breakpoint")
+        self._chk(self._L.rvc_set_f0_curve(self._h, t.ctypes.data_as(C.POINTER(C.c_double)), hz.ctypes.data_as(C.POINTER(C.c_float)), len(t)))
+
+    def clear_f0_curve(self):
+        self._chk(self._L.rvc_set_f0_curve(self._h, None, None, 0))
+
+    def f0_curve_grid(self, n_frames: int) -> np.ndarray:
+        """the first n_frames rows of the curve's 10 ms grid as the device builds it, NaN = "keep the tracker's value" (rvc_f0_curve_grid)"""
+        out = np.empty(int(n_frames), np.float32)
+        self._chk(self._L.rvc_f0_curve_grid(self._h, len(out), out.ctypes.data_as(C.POINTER(C.c_float)), len(out)))
+        return out
+
+    def convert_f0(self) -> np.ndarray:
+        """the conditioned f0 of the last completed conversion, one value per 10 ms frame of the recording (rvc_convert_f0)"""
+        n = C.c_size_t(0)
+        self._L.rvc_convert_f0(self._h, None, 0, C.byref(n))
+        out = np.empty(max(int(n.value), 1), np.float32)
+        self._chk(self._L.rvc_convert_f0(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
+        return out[: int(n.value)]
+
     @staticmethod
     def formant_geometry(return_length: int, sample_rate: int, semitones: float):
         """-> (R2, upp_res): the decoder's frame count and the resampler's input samples per frame of a formant shift
