@@ -161,6 +161,17 @@ extern "C" {
     pub fn rvc_set_f0_curve(e: *mut RvcEngine, t_sec: *const f64, hz: *const c_float, n: usize) -> c_int;
     pub fn rvc_f0_curve_grid(e: *mut RvcEngine, n_frames: usize, out: *mut c_float, cap: usize) -> c_int;
     pub fn rvc_convert_f0(e: *mut RvcEngine, hz: *mut c_float, cap: usize, n_frames: *mut usize) -> c_int;
+    // f0 analysis of a whole recording (no synthesizer), exact order statistics of the voiced rows, auto-transpose of the file converter (target 0 = off;
+    // step 0 / 1 / 12; limit 0..24 semitones)
+    pub fn rvc_analyze_f0(e: *mut RvcEngine, pcm16k: *const c_float, n: usize, k: usize, context: usize, crossfade: usize, highpass: c_int, hz: *mut c_float,
+                          cap: usize, n_frames: *mut usize) -> c_int;
+    pub fn rvc_analyze_f0_device(e: *mut RvcEngine, d_pcm16k: *const c_void, n: usize, k: usize, context: usize, crossfade: usize, highpass: c_int,
+                                 d_hz: *mut c_void, cap: usize, n_frames: *mut usize) -> c_int;
+    pub fn rvc_f0_stats(e: *mut RvcEngine, hz: *const c_float, n: usize, quantile: *const c_double, nq: usize, out_hz: *mut c_float, voiced: *mut usize) -> c_int;
+    pub fn rvc_f0_stats_stream(e: *mut RvcEngine, stream: c_int, quantile: *const c_double, nq: usize, out_hz: *mut c_float, voiced: *mut usize) -> c_int;
+    pub fn rvc_set_auto_transpose(e: *mut RvcEngine, target_hz: c_double, step: c_int, limit: c_double) -> c_int;
+    pub fn rvc_auto_transpose(e: *mut RvcEngine, target_hz: *mut c_double, step: *mut c_int, limit: *mut c_double) -> c_int;
+    pub fn rvc_auto_transpose_info(e: *mut RvcEngine, median_hz: *mut c_float, voiced: *mut usize, semitones: *mut c_double, ms: *mut c_double) -> c_int;
 
     // ---- multi-GPU: the one collective (index broadcast at load, RCCL over xGMI)
     pub fn rvc_rccl_unique_id(id128: *mut c_void) -> c_int;

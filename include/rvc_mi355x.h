@@ -554,6 +554,42 @@ rvc_status rvc_convert_file_device(rvc_engine *e, const void *d_pcm, size_t n, s
    peak = max |out| (exact); any pointer may be NULL.  RVC_SHAPE before one has completed */
 rvc_status rvc_convert_file_info(rvc_engine *e, double ms[7], size_t *rate_out, float *peak);
 
+/* ---- f0 analysis, order statistics and auto-transpose (the forks' "proposed pitch") ---- */
+/* rvc_analyze_f0: the f0 of a whole 16 kHz recording on the 10 ms grid, Nf = ceil(n / 160) rows in Hz with 0 = unvoiced, without the synthesizer.  The windows
+ * are rvc_convert's (same geometry and defaults for k, context, crossfade = 0; same gather; S = rvc_set_streams windows per batch, a short last batch
+ * zero-padded); each batch runs the pitch-only plan of that geometry at S streams, and the hop rows of each window go onto the grid.  A row is the f0 method's
+ * own, single or hybrid: what rvc_pitch returns for that window with pitch_shift = 0, every pitch control neutral and no override -- the multiplier, range gate,
+ * median, snap and formant factor do not apply whatever the streams' settings are (the tail runs under a neutral control block; the settings are not touched).
+ * The call begins with what rvc_reset_state does and leaves the state that way.  Needs an f0 method (RVC_F0_NOT_LOADED), neither a voice model nor
+ * ContentVec.  highpass != 0: rvc_highpass first.  RVC_SHAPE with a message: n = 0, a bad geometry (the converter's checks), cap short (*n_frames is written);
+ * each member of a hybrid keeps its own limits (CREPE: streams x frames <= 65535). */
+rvc_status rvc_analyze_f0(rvc_engine *e, const float *pcm16k, size_t n, size_t k, size_t context, size_t crossfade, int highpass, float *hz, size_t cap,
+                          size_t *n_frames);
+/* device-resident variant (HIP device pointers on the engine's device); returns synchronised */
+rvc_status rvc_analyze_f0_device(rvc_engine *e, const void *d_pcm16k, size_t n, size_t k, size_t context, size_t crossfade, int highpass, void *d_hz, size_t cap,
+                                 size_t *n_frames);
+/* Exact order statistics of the voiced rows.  A row is voiced iff it is finite and > 0.  With the v voiced rows sorted ascending as s[0 .. v), quantile p in
+ * [0, 1] gives s[floor(p (v - 1))], the product in double: p = 0.5 is the lower median; the result is an element of the input, bit for bit -- no interpolation,
+ * no averaging.  v = 0: every out_hz is 0 and *voiced = 0.  A radix select on the IEEE bit pattern on the device; only the nq values and v come back.
+ * rvc_f0_stats takes n host rows; rvc_f0_stats_stream the 1024-row pitch cache of a stream where it lies.  The pitch cache holds CONDITIONED f0 -- behind
+ * pitch_shift, the semitone transpose and the pitch controls: a host that wants the raw median of a live stream reads it while its transpose is 0.
+ * RVC_SHAPE: n = 0 or above 2^30, nq outside [1, 8], a quantile outside [0, 1] or NaN, a bad stream number. */
+rvc_status rvc_f0_stats(rvc_engine *e, const float *hz, size_t n, const double *quantile, size_t nq, float *out_hz, size_t *voiced);
+rvc_status rvc_f0_stats_stream(rvc_engine *e, int stream, const double *quantile, size_t nq, float *out_hz, size_t *voiced);
+/* Auto-transpose of the file converter.  target_hz = 0 (the default) = off, else in (0, 20000]; step 0 = exact, 1 = whole semitones, 12 = whole octaves;
+ * limit in [0, 24] semitones (the front ends default to 12).  Anything else: RVC_SHAPE, state unchanged.  With a target set and a model with pitch guidance,
+ * rvc_convert* and rvc_convert_file* run, in front of their first batch, rvc_analyze_f0 on the signal the model will see (16 kHz, behind the high-pass when it
+ * is on) with the call's own k, context and crossfade; merge the f0 curve in when one is in force (row = isnan(curve) ? tracked : curve); take the lower
+ * median m; a = 12 log2(target / m) in double, rounded to the step (ties to even), clamped to [-limit, limit], 0 when no row is voiced.  For the duration of
+ * the call every stream's multiplier takes the factor (float)2^(a / 12) behind the rvc_set_pitch_semitones factor (a = 0 multiplies by nothing); it is no
+ * part of a plan's identity and is gone on every way out of the call.  pitch_shift and the semitones compose with it; a model without pitch guidance skips
+ * all of it; streaming calls never read the setting.  The conversion proper starts from the same reset state as with the setting off.
+ * rvc_auto_transpose_info: of the last conversion that ran the analysis -- the median, the voiced rows, a, device ms {analysis, merge + select}; RVC_SHAPE
+ * before one has. */
+rvc_status rvc_set_auto_transpose(rvc_engine *e, double target_hz, int step, double limit);
+rvc_status rvc_auto_transpose(rvc_engine *e, double *target_hz, int *step, double *limit);
+rvc_status rvc_auto_transpose_info(rvc_engine *e, float *median_hz, size_t *voiced, double *semitones, double ms[2]);
+
 /* ---- what THIS GPU sustains, measured in-run (bench.py; boxes of one pool differ by ~10 % on matrix-core-bound work) ---- */
 /* rvc_calibrate: ~50 ms of device time.  A bare v_mfma_f32_32x32x2_f32 stream on every SIMD (four waves per SIMD, non-zero operands) -> fp32 matrix-core
  * TFLOP/s actually reached and the shader clock it ran at (s_memtime cycles per s_memrealtime tick); a float4 read stream over 1 GiB -> HBM TB/s. */

@@ -43,6 +43,7 @@ SYMBOLS = [
     "rvc_convert_geometry", "rvc_convert", "rvc_convert_device", "rvc_convert_info", "rvc_sola_stitch", "rvc_highpass",
     "rvc_resample_geometry", "rvc_resample", "rvc_resample_device", "rvc_change_rms", "rvc_convert_file", "rvc_convert_file_device", "rvc_convert_file_info",
     "rvc_set_f0_override_stream", "rvc_set_f0_override_hold", "rvc_set_f0_curve", "rvc_f0_curve_grid", "rvc_convert_f0",
+    "rvc_analyze_f0", "rvc_analyze_f0_device", "rvc_f0_stats", "rvc_f0_stats_stream", "rvc_set_auto_transpose", "rvc_auto_transpose", "rvc_auto_transpose_info",
 ]
 
 
@@ -388,6 +389,15 @@ def lib():
         L.rvc_f0_curve_grid.argtypes = [vp, sz, fp, sz]
         L.rvc_convert_f0.argtypes = [vp, fp, sz, C.POINTER(sz)]
         L.rvc_debug_f0_override.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int, fp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.c_int, fp]
+    if hasattr(L, "rvc_analyze_f0") or not override:
+        dp = C.POINTER(C.c_double)
+        L.rvc_analyze_f0.argtypes = [vp, fp, sz, sz, sz, sz, C.c_int, fp, sz, C.POINTER(sz)]
+        L.rvc_analyze_f0_device.argtypes = [vp, vp, sz, sz, sz, sz, C.c_int, vp, sz, C.POINTER(sz)]
+        L.rvc_f0_stats.argtypes = [vp, fp, sz, dp, sz, fp, C.POINTER(sz)]
+        L.rvc_f0_stats_stream.argtypes = [vp, C.c_int, dp, sz, fp, C.POINTER(sz)]
+        L.rvc_set_auto_transpose.argtypes = [vp, C.c_double, C.c_int, C.c_double]
+        L.rvc_auto_transpose.argtypes = [vp, dp, C.POINTER(C.c_int), dp]
+        L.rvc_auto_transpose_info.argtypes = [vp, fp, C.POINTER(sz), dp, dp]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
     if hasattr(L, "rvc_model_speakers") or not override:

@@ -1,12 +1,15 @@
 """python -m obs_rvc_amd.convert in.wav -o out.wav --model M [--data D] [--version 2] [--f0 rmvpe|yin|crepe-full|crepe-tiny|fcpe|pm|"hybrid[a+b..]" --f0-hybrid-mode vote|median] [--index I --index-rate r --index-k 4|8 --nprobe p]
        [--pitch semitones] [--formant st] [--protect p] [--streams S] [--window k --context C --crossfade X] [--no-highpass] [--rate out_rate]
        [--rms-mix-rate r] [--resampler blocks|device] [--sid N | --sid-mix 0:0.3,2:0.7]
+       [--auto-pitch HZ | --auto-pitch-from REF.wav] [--auto-pitch-step 0|1|12] [--auto-pitch-limit st] [--analyze-only --f0-out PATH]
 
 Upstream's "model inference" tab with this engine: a WAV file through RvcInfer.convert -- windows of one geometry run `--streams` at a
 time through the batched infer path and are SOLA-stitched on the GPU -- and the result written as 16-bit PCM.  The WAV file is read with
 build_index.read_wav and written with the standard library; like upstream the output is divided by peak / 0.99 when its peak exceeds 1.  Argument parsing and
 WAV writing are plain functions; only main() touches the GPU.  With --resampler device, or --rms-mix-rate below 1 (upstream's volume envelope), the file goes
-through RvcInfer.convert_file instead: both rate conversions and the envelope run on the GPU too, and the peak comes back with the audio."""
+through RvcInfer.convert_file instead: both rate conversions and the envelope run on the GPU too, and the peak comes back with the audio.
+--auto-pitch / --auto-pitch-from: the recording's median f0 is measured first and transposed onto a target (the forks' "proposed
+pitch"); --analyze-only writes the recording's f0 to --f0-out and converts nothing."""
 from __future__ import annotations
 
 import argparse
@@ -22,8 +25,8 @@ from .build_index import read_wav
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(prog="python -m obs_rvc_amd.convert", description="convert a WAV recording to a voice on the GPU")
     p.add_argument("input", help="the WAV file to convert (16-bit or 32-bit integer PCM, mono or stereo)")
-    p.add_argument("-o", "--output", required=True, help="the WAV file to write (16-bit PCM, mono)")
-    p.add_argument("--model", required=True, help="the voice: <model>.rvcw (or its .onnx sibling's name)")
+    p.add_argument("-o", "--output", default=None, help="the WAV file to write (16-bit PCM, mono); required unless --analyze-only")
+    p.add_argument("--model", default=None, help="the voice: <model>.rvcw (or its .onnx sibling's name); required unless --analyze-only")
     p.add_argument("--data", default=None, help="the engine's data directory (contentvec/, f0/); default: the model zoo of the package")
     p.add_argument("--version", type=int, choices=(1, 2), default=2, help="RVC model version: 1 = 256-dim features, 2 = 768-dim (default)")
     p.add_argument("--f0", type=f0_arg, default="rmvpe", metavar="{%s,hybrid[a+b..]}" % ",".join(F0_CHOICES),
@@ -54,8 +57,25 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "ignored.  Frames between the first and the last time take the curve instead of the tracker's value.  Unlike upstream the curve is "
                         "transposed like any f0: it is absolute only with --pitch 0")
     p.add_argument("--f0-out", default=None, metavar="PATH", help="write the f0 the synthesizer got, one `t,f0` pair per 10 ms frame (the format --f0-file reads)")
+    p.add_argument("--auto-pitch", type=float, default=0.0, metavar="HZ",
+                   help="auto-transpose: move the recording's median f0 onto HZ (Applio's defaults: 155 for a male voice, 255 for a female one); 0 = off (default)")
+    p.add_argument("--auto-pitch-from", default=None, metavar="REF.wav", help="auto-transpose onto the median f0 of a recording of the target voice")
+    p.add_argument("--auto-pitch-step", type=int, choices=AUTO_PITCH_STEPS, default=1, help="round the transpose to 1 = whole semitones (default), 12 = whole octaves, 0 = not at all")
+    p.add_argument("--auto-pitch-limit", type=float, default=12.0, help="the largest auto-transpose in semitones, 0..24 (default 12)")
+    p.add_argument("--analyze-only", action="store_true", help="write the recording's f0 (no transpose, no pitch control) to --f0-out and convert nothing; needs no --model")
     p.add_argument("--device", type=int, default=-1)
     a = p.parse_args(argv)
+    if a.analyze_only:
+        if a.f0_out is None:
+            p.error("--analyze-only writes the f0 to --f0-out: name the file")
+    elif a.model is None or a.output is None:
+        p.error("the following arguments are required: -o/--output, --model")
+    if not 0.0 <= a.auto_pitch <= 20000.0:
+        p.error("--auto-pitch is a frequency in Hz, up to 20000 (0 = off)")
+    if a.auto_pitch > 0.0 and a.auto_pitch_from is not None:
+        p.error("--auto-pitch and --auto-pitch-from exclude each other")
+    if not 0.0 <= a.auto_pitch_limit <= 24.0:
+        p.error("--auto-pitch-limit is 0..24 semitones")
     if a.f0_file is not None:
         try:
             with open(a.f0_file) as fh:
@@ -99,6 +119,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 F0_CHOICES = ("rmvpe", "yin", "crepe-full", "crepe-tiny", "fcpe", "pm")
+AUTO_PITCH_STEPS = (0, 1, 12)
 
 
 def f0_arg(text: str) -> str:
@@ -206,6 +227,25 @@ def main(argv=None) -> int:
     from . import weights as W
     from .rvc import RvcInfer
     eng = RvcInfer(a.data or W.default_zoo_root("full"), device=a.device)
+
+    def load_f0():
+        if a.f0.startswith("hybrid["):
+            eng.load_f0_hybrid(a.f0[len("hybrid["):-1].split("+"), mode=a.f0_hybrid_mode)
+        else:
+            eng.load_f0_method(a.f0)
+
+    def to_16k(sig, r):
+        return sig if r == 16000 else (eng.resample(sig, r, 16000) if a.resampler == "device" else _resample(eng, sig, r, 16000))
+    if a.analyze_only:      # the recording's own f0 and nothing else: no ContentVec, no voice model
+        load_f0()
+        eng.set_streams(a.streams)
+        hz = eng.analyze_f0(to_16k(x, rate), window=a.window, context=a.context, crossfade=a.crossfade, highpass=a.highpass)
+        with open(a.f0_out, "w") as fh:
+            fh.write(format_f0_curve(hz))
+        med, voiced = eng.f0_stats(hz)
+        print("%s: %d frames, %d voiced, median f0 %.2f Hz" % (a.f0_out, len(hz), voiced, float(med[0])))
+        eng.close()
+        return 0
     eng.load_contentvec(a.version)
     eng.load_model(a.model)
     if a.f0_out is not None and not eng.model_has_f0():      # (before anything is converted or written)
@@ -213,10 +253,7 @@ def main(argv=None) -> int:
         eng.close()
         return 2
     if eng.model_has_f0():      # (a model trained without pitch guidance runs no tracker: --f0 names none for it)
-        if a.f0.startswith("hybrid["):
-            eng.load_f0_hybrid(a.f0[len("hybrid["):-1].split("+"), mode=a.f0_hybrid_mode)
-        else:
-            eng.load_f0_method(a.f0)
+        load_f0()
     eng.set_streams(a.streams)
     if a.sid is not None:
         eng.set_speaker(a.sid)
@@ -230,6 +267,22 @@ def main(argv=None) -> int:
     eng.set_protect(a.protect)
     if a.f0_curve is not None:
         eng.set_f0_curve(*a.f0_curve)
+    auto = eng.model_has_f0() and (a.auto_pitch > 0.0 or a.auto_pitch_from is not None)
+    if auto:
+        target = a.auto_pitch
+        if a.auto_pitch_from is not None:      # the target voice's own median, measured as the input's will be
+            ref, ref_rate = read_wav(a.auto_pitch_from)
+            if not len(ref):
+                print("%s holds no samples" % a.auto_pitch_from, file=sys.stderr)
+                eng.close()
+                return 2
+            med, voiced = eng.f0_stats(eng.analyze_f0(to_16k(ref, ref_rate), window=a.window, context=a.context, crossfade=a.crossfade, highpass=a.highpass))
+            if not voiced:
+                print("--auto-pitch-from: %s has no voiced frame" % a.auto_pitch_from, file=sys.stderr)
+                eng.close()
+                return 2
+            target = float(med[0])
+        eng.set_auto_transpose(target, a.auto_pitch_step, a.auto_pitch_limit)
     if a.resampler == "device" or a.rms_mix_rate < 1.0:
         y, out_rate = eng.convert_file(x, rate, k=a.window, context=a.context, crossfade=a.crossfade, pitch_shift=0, highpass=a.highpass, rms_mix_rate=a.rms_mix_rate,
                                        out_rate=a.rate)
@@ -246,6 +299,10 @@ def main(argv=None) -> int:
     if a.f0_out is not None:
         with open(a.f0_out, "w") as fh:
             fh.write(format_f0_curve(eng.convert_f0()))
+    if auto:
+        t = eng.auto_transpose_info()
+        print("auto-pitch: median f0 %.2f Hz over %d voiced frames, target %.2f Hz -> %+.2f semitones (device ms: analysis %.2f, select %.2f)"
+              % (float(t["median_hz"]), t["voiced"], eng.auto_transpose()["target_hz"], t["semitones"], t["ms_analysis"], t["ms_select"]))
     print("%s: %.2f s at %d Hz from %d windows in %d batches; device ms: high-pass %.2f, model %.2f, stitch %.2f, total %.2f"
           % (a.output, len(y) / out_rate, out_rate, info["windows"], info["batches"], info["ms_highpass"], info["ms_model"], info["ms_stitch"], info["ms_total"]))
     eng.close()

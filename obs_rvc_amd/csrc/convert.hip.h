@@ -4,12 +4,20 @@
 // infer_common on the engine's S streams (window w = i S + s on stream s in batch i) and are stitched by the plugin's SOLA step in its LINEAR crossfade,
 // chained over the windows on the device (stitch.hip.h).  In front of it the optional 48 Hz high-pass (highpass.hip.h).  Per batch: one gather launch,
 // one infer call with its one synchronisation, two stitch launches; the signal, S window inputs, S window outputs, the tails and the output stay in HBM.
+// f0_analyze.hip.h (included below): the same windows through the pitch-only plan -- rvc_analyze_f0 --, order statistics of f0 rows, and auto-transpose.
 #pragma once
 #include "convert_geometry.h"
 #include "highpass.hip.h"
 #include "stitch.hip.h"
 #include "resample_whole.hip.h"
 #include "change_rms.hip.h"
+
+namespace rvc {
+// (what f0_analyze.hip.h uses of this file, defined below)
+static void launch_highpass(rvc_engine *e, const float *d_x, size_t n, float *d_y);
+static void launch_window_gather(hipStream_t st, const float *sig, long long N, float *dst, int n, int S, long long w0, int nw, int H, int C);
+}
+#include "f0_analyze.hip.h"
 
 namespace rvc {
 
@@ -25,6 +33,11 @@ static __global__ void window_gather_kernel(const float *sig, long long N, float
         if (src >= 0 && src < N) v = sig[src];
     }
     dst[(long long)s * n + i] = v;
+}
+
+static void launch_window_gather(hipStream_t st, const float *sig, long long N, float *dst, int n, int S, long long w0, int nw, int H, int C)
+{
+    hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, N, dst, n, w0, nw, H, C);
 }
 
 static void launch_highpass(rvc_engine *e, const float *d_x, size_t n, float *d_y)
@@ -116,6 +129,16 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
         launch_highpass(e, d_pcm, n, filtered.get());
         t_hp.stop(st);
         sig = filtered.get();
+    }
+    // auto-transpose (f0_analyze.hip.h): with a target set, the f0 of the signal the model will see is analysed first -- the call's own
+    // windows through the pitch-only plan --, the curve merged in, and 12 log2(target / median) semitones become one more factor of every stream's multiplier
+    // until the call returns, on whatever path.  Off (the default): nothing is queued here
+    struct AutoGuard { rvc_engine *e; ~AutoGuard() { e->auto_mul = 0.f; } } auto_guard{e};
+    if (has_f0 && e->at_target > 0.0) {
+        float mul = 0.f;
+        const rvc_status rc = auto_transpose_run(e, sig, n, g, curve ? e->curve_grid.get() : nullptr, &mul);
+        if (rc != RVC_OK) return rc;
+        e->auto_mul = mul;
     }
     DevBuf<float> win, y, tails; DevBuf<int> offs;
     win.alloc(S * g.n + 64); y.alloc(S * ylen + 64); tails.alloc((W + 1) * sola_len); offs.alloc(W);

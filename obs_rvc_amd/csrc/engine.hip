@@ -673,7 +673,10 @@ static float uppower(int32_t pitch_shift) { return ldexpf(1.0f, pitch_shift / 12
 // settings, obs-rvc/src/lib.rs:701-707).  The multiplier: uppower(pitch_shift) -- shifts == nullptr: `pitch_shift` for every stream --, with Rs (infer calls: the
 // return_length of every stream) times the stream's formant factor (float)2^(-phi / 12), and a semitone transpose st != 0 multiplies (float)2^(st / 12) in last
 // (st = 0 multiplies by nothing).  The formant descriptor is made for Rs; without Rs (hubert / pitch) the descriptors stay what the device holds.
-static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *shifts = nullptr, const uint32_t *Rs = nullptr)
+// neutral (rvc_analyze_f0): the multiplier is 1 and every pitch control is off whatever the streams' settings say -- the tracker's own rows come out of the tail;
+// the settings themselves are not touched, and the next call pushes them again because the block it compares against differs.
+// rvc_engine::auto_mul (a conversion under auto-transpose): one more factor behind the semitone factor
+static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *shifts = nullptr, const uint32_t *Rs = nullptr, bool neutral = false)
 {
     const int B = e->n_streams;
     std::vector<StreamCtl> ctl((size_t)B, StreamCtl{});
@@ -686,7 +689,9 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
             c.uppower *= (float)std::pow(2.0, -set.formant / 12.0);
             c.f = formant_desc(e, b, Rs[b]);
         } else if (keep_f) c.f = e->pushed_ctl[b].f;
+        if (neutral) { c.c = f0cond_pack(0.f, INFINITY, 0, 0u, 0.f); c.protect = (float)set.protect; continue; }
         if (set.pitch.semitones != 0.0) c.uppower *= (float)std::pow(2.0, set.pitch.semitones / 12.0);
+        if (e->auto_mul != 0.f) c.uppower *= e->auto_mul;
         c.c = f0cond_pack(set.pitch.lo, set.pitch.hi, set.pitch.radius, set.pitch.mask, set.pitch.strength);
         c.protect = (float)set.protect;
     }

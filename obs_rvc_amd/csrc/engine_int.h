@@ -5,11 +5,11 @@
 //   model_fcpe.hip   FCPE f0 (build_fcpe, the decoder's and the depthwise kernel's launches)     f0_pm.hip   "pm" f0 (build_pm and its launches)     (hybrid f0: engine.hip build_f0 queues the members, model_rmvpe.hip the combine)
 //   model_synth.hip  the synthesizer (build_synth, ...)      retrieval.hip     flat-L2 index: install_index, device-side layouts (RetrievalIndex), the plan's search section
 //   engine.hip       the engine object, plans, the C ABI (+ session.hip.h, resample.hip.h, rccl_bcast.hip.h, convert.hip.h: the file converter, with
-//                    resample_whole.hip.h and change_rms.hip.h)
+//                    resample_whole.hip.h, change_rms.hip.h and f0_analyze.hip.h: f0 analysis, order statistics, auto-transpose)
 //   debug.hip        the test and tuning aids of include/rvc_mi355x_debug.h that build plans of their own (rvc_debug_layer / _op / _front, the *_check aids)
 // The model structs (weights as prepared at load) are defined here; their loaders are in the model's unit.  Kernels: a non-template __global__ function is
 // compiled into the device code of every unit that includes its definition, launched or not, so each lives in a header that exactly one unit includes
-// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, f0_hybrid.hip.h, yin.hip.h, pm.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, f0_override.hip.h, crossfade.hip.h, stitch.hip.h, ...)
+// (plan_ops.hip.h, contentvec.hip.h, rmvpe.hip.h, rmblock.hip.h, f0_hybrid.hip.h, yin.hip.h, pm.hip.h, crepe.hip.h, fcpe.hip.h, synth.hip.h, knn.hip.h, chunk.hip.h, protect.hip.h, f0_override.hip.h, f0_select.hip.h, crossfade.hip.h, stitch.hip.h, ...)
 // or in that unit's .hip file, and no header included from here defines one.  The implicit-GEMM templates (igemm2 / igemm2w / igemm_lds / igemm32 / igemm_bf3 / igemm_splitk .hip.h) are instantiated by the
 // *_inst.hip units.
 #pragma once
@@ -631,6 +631,14 @@ struct rvc_engine {
     rvc::DevBuf<double> curve_t; rvc::DevBuf<float> curve_hz, curve_grid; size_t curve_n = 0;
     bool conv_curve = false; rvc::F0OvCall conv_call{};          // inside convert_run with a curve: the gather of the batch at hand
     std::vector<float> conv_f0; bool conv_f0_valid = false;      // the conditioned f0 of the last completed conversion on the 10 ms grid (rvc_convert_f0)
+    // f0 analysis and auto-transpose (f0_analyze.hip.h, f0_select.hip.h).  sel_ws: the select's workspace, allocated by the first select.
+    // at_*: rvc_set_auto_transpose (target 0 = off).  auto_mul: inside a conversion that transposes by a != 0 the factor (float)2^(a / 12) every stream's
+    // multiplier takes behind its semitone factor (push_call_params), 0 = none -- set and removed by convert_run alone, so streaming calls never see it.
+    // at_info: what rvc_auto_transpose_info reports of the last conversion that ran the analysis
+    rvc::DevBuf<uint32_t> sel_ws;
+    double at_target = 0.0; int at_step = 1; double at_limit = 12.0;
+    float auto_mul = 0.f;
+    struct AutoInfo { bool valid = false; float median = 0.f; size_t voiced = 0; double semitones = 0.0; double ms[2] = {0, 0}; } at_info;
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };

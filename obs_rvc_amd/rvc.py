@@ -697,6 +697,61 @@ class RvcInfer:
         self._chk(self._L.rvc_convert_f0(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
         return out[: int(n.value)]
 
+    # -- f0 analysis, order statistics, auto-transpose ------------------------
+    def analyze_f0(self, pcm16k, window: int = 0, context: int = 0, crossfade: int = 0, highpass: bool = True) -> np.ndarray:
+        """rvc_analyze_f0: the f0 of a whole 16 kHz recording, one value per 10 ms frame (0 = unvoiced), through convert()'s windows and the pitch-only plan --
+        no synthesizer, no voice model needed.  The tracker's own rows: no transpose, no pitch control applies."""
+        x = np.ascontiguousarray(pcm16k, np.float32)
+        if x.ndim != 1:
+            raise RvcInferError(5, "analyze_f0: a recording is a 1-D array")
+        out = np.empty(-(-len(x) // 160), np.float32)
+        n = C.c_size_t()
+        self._chk(self._L.rvc_analyze_f0(self._h, x.ctypes.data_as(_FP), len(x), int(window), int(context), int(crossfade), 1 if highpass else 0,
+                                         out.ctypes.data_as(_FP), len(out), C.byref(n)))
+        return out[: n.value]
+
+    @staticmethod
+    def _quantiles(quantiles):
+        q = np.atleast_1d(np.asarray(quantiles, np.float64))
+        if q.ndim != 1 or not 1 <= len(q) <= 8 or not np.all((q >= 0.0) & (q <= 1.0)):
+            raise RvcInferError(5, "f0_stats: 1 to 8 quantiles in [0, 1]")
+        return np.ascontiguousarray(q)
+
+    def f0_stats(self, hz, quantiles=(0.5,)):
+        """rvc_f0_stats: exact order statistics of the voiced rows (finite and > 0) of `hz`: quantile p is sorted[floor(p (v - 1))], an element of the input
+        (0.5 = the lower median) -> (float32 array per quantile, v); all zeros when nothing is voiced"""
+        x = np.ascontiguousarray(hz, np.float32)
+        if x.ndim != 1:
+            raise RvcInferError(5, "f0_stats: a one-dimensional array of Hz")
+        q = self._quantiles(quantiles)
+        out, v = np.zeros(len(q), np.float32), C.c_size_t()
+        self._chk(self._L.rvc_f0_stats(self._h, x.ctypes.data_as(_FP), len(x), q.ctypes.data_as(C.POINTER(C.c_double)), len(q), out.ctypes.data_as(_FP), C.byref(v)))
+        return out, int(v.value)
+
+    def f0_stats_stream(self, stream: int = 0, quantiles=(0.5,)):
+        """rvc_f0_stats_stream: the same over the stream's 1024-row pitch cache on the device.  The cache holds conditioned f0 (transposed, filtered): read it
+        while the transpose is 0 for the raw median"""
+        q = self._quantiles(quantiles)
+        out, v = np.zeros(len(q), np.float32), C.c_size_t()
+        self._chk(self._L.rvc_f0_stats_stream(self._h, int(stream), q.ctypes.data_as(C.POINTER(C.c_double)), len(q), out.ctypes.data_as(_FP), C.byref(v)))
+        return out, int(v.value)
+
+    def set_auto_transpose(self, target_hz: float, step: int = 1, limit: float = 12.0):
+        """rvc_set_auto_transpose: convert() / convert_file() measure the recording's median f0 first and transpose it onto target_hz (0 = off; Applio's defaults
+        are 155 Hz for a male voice, 255 Hz for a female one).  step 0 = exact, 1 = whole semitones, 12 = whole octaves; limit = the largest transpose, 0..24"""
+        self._chk(self._L.rvc_set_auto_transpose(self._h, float(target_hz), int(step), float(limit)))
+
+    def auto_transpose(self) -> dict:
+        t, s, l = C.c_double(), C.c_int(), C.c_double()
+        self._chk(self._L.rvc_auto_transpose(self._h, C.byref(t), C.byref(s), C.byref(l)))
+        return {"target_hz": t.value, "step": s.value, "limit": l.value}
+
+    def auto_transpose_info(self) -> dict:
+        """of the last conversion that ran the analysis -> {median_hz (float32), voiced, semitones, ms_analysis, ms_select}"""
+        m, v, a, ms = C.c_float(), C.c_size_t(), C.c_double(), (C.c_double * 2)()
+        self._chk(self._L.rvc_auto_transpose_info(self._h, C.byref(m), C.byref(v), C.byref(a), ms))
+        return {"median_hz": np.float32(m.value), "voiced": int(v.value), "semitones": a.value, "ms_analysis": ms[0], "ms_select": ms[1]}
+
     @staticmethod
     def formant_geometry(return_length: int, sample_rate: int, semitones: float):
         """-> (R2, upp_res): the decoder's frame count and the resampler's input samples per frame of a formant shift
