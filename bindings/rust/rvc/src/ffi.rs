@@ -137,6 +137,14 @@ extern "C" {
     pub fn rvc_convert_file_device(e: *mut RvcEngine, d_pcm: *const c_void, n: usize, rate_in: usize, k: usize, context: usize, crossfade: usize, pitch_shift: i32,
                                    highpass: c_int, rms_mix_rate: f64, rate_out: usize, d_out: *mut c_void, cap: usize, out_len: *mut usize) -> c_int;
     pub fn rvc_convert_file_info(e: *mut RvcEngine, ms: *mut f64, rate_out: *mut usize, peak: *mut c_float) -> c_int;
+    // many recordings in one call: declared for the header's sake, the shim has no method for them yet
+    pub fn rvc_convert_many_geometry(n16k: *const usize, n_files: usize, sample_rate: usize, k: usize, context: usize, crossfade: usize, windows: *mut usize,
+                                     out_samples: *mut usize, totals: *mut usize) -> c_int;
+    pub fn rvc_convert_many(e: *mut RvcEngine, pcm16k: *const *const c_float, n: *const usize, n_files: usize, k: usize, context: usize, crossfade: usize,
+                            pitch_shift: i32, highpass: c_int, out: *const *mut c_float, cap: *const usize, out_len: *mut usize) -> c_int;
+    pub fn rvc_convert_many_info(e: *mut RvcEngine, windows_total: *mut usize, batches: *mut usize, offsets: *mut i32, cap_offsets: usize, ms: *mut f64) -> c_int;
+    pub fn rvc_sola_stitch_many(e: *mut RvcEngine, windows: *const c_float, windows_per_file: *const usize, n_files: usize, window_len: usize, sola_len: usize,
+                                search: usize, frame: usize, out: *mut c_float, offsets: *mut i32) -> c_int;
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 

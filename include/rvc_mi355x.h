@@ -590,6 +590,37 @@ rvc_status rvc_set_auto_transpose(rvc_engine *e, double target_hz, int step, dou
 rvc_status rvc_auto_transpose(rvc_engine *e, double *target_hz, int *step, double *limit);
 rvc_status rvc_auto_transpose_info(rvc_engine *e, float *median_hz, size_t *voiced, double *semitones, double ms[2]);
 
+/* ---- many recordings in one call (upstream's "model inference" tab, vc_multi) ---- */
+/* F recordings at 16 kHz, one geometry and one set of settings for all of them: what rvc_convert does to each, with the windows of all files laid end to end
+ * and run S = rvc_set_streams at a time, so that a batch holds windows of several files.  File f with N_f >= 1 samples has the windows rvc_convert_geometry
+ * gives it: Nf_f = ceil(N_f / 160), W_f = ceil(Nf_f / H), out_f = Nf_f zc.  Global window g = P_f + w with P_f = W_0 + ... + W_{f-1}, 0 <= w < W_f; files
+ * stay in the order given and windows in order, nothing is sorted; Wtot = P_F.  Batch i runs globals [i S, min((i + 1) S, Wtot)) on streams 0 ..; only the
+ * last batch is padded with all-zero windows.  Window w of file f reads samples [160 (w H - C), + n) of THAT file, zero outside [0, N_f).  The stitch is
+ * rvc_convert's per file: the tail in front of a file's first window is zeros, a file that continues in the next batch takes the tail it left behind.
+ * Limits: 1 <= F <= 65536, every N_f >= 1, Wtot <= 2^30, sum of out_f <= 2^40; anything else is RVC_SHAPE with a message.
+ * rvc_convert_many BEGINS WITH WHAT rvc_reset_state DOES.  All signals go up once, with highpass != 0 each file is filtered on its own (rvc_highpass's bits,
+ * the zero extension per file), the outputs come down once; every per-stream setting, the index, the f0 method and graph replay apply as to any infer
+ * call; rvc_set_pipeline is ignored.  out[f] takes out_f samples; out_len [F] (may be NULL) is written.  So the result is, bit for bit, the composition:
+ * gather per file, rvc_reset_state, rvc_infer_batch per batch in the packed order, rvc_sola_stitch per file; with one file it is rvc_convert's.
+ * Statuses, in this order: the three *_NOT_LOADED as for rvc_convert, before any argument is looked at; RVC_SHAPE with a message for F out of range, n NULL,
+ * an empty recording, the geometry errors of rvc_convert, the totals above; for auto-transpose in force (rvc_set_auto_transpose: it would take one
+ * multiplier per file) and for an f0 curve set (rvc_set_f0_curve: a curve belongs to one recording); then every out_len[f] is written; a short cap[f] (or
+ * cap NULL); a NULL pointer among pcm16k, out and their entries.  Nothing is launched on a refused call.  After a completed call rvc_convert_info and
+ * rvc_convert_f0 answer as before any conversion has completed. */
+/* host only, pure: windows [F] and out_samples [F] per file, totals = {Wtot, sum of out_samples}; any of the three may be NULL */
+rvc_status rvc_convert_many_geometry(const size_t *n16k, size_t n_files, size_t sample_rate, size_t k, size_t context, size_t crossfade, size_t *windows,
+                                     size_t *out_samples, size_t totals[2]);
+rvc_status rvc_convert_many(rvc_engine *e, const float *const *pcm16k, const size_t *n, size_t n_files, size_t k, size_t context, size_t crossfade,
+                            int32_t pitch_shift, int highpass, float *const *out, const size_t *cap, size_t *out_len);
+/* of the last completed rvc_convert_many: Wtot, the batches, the SOLA offset of every window in global window order (the first cap_offsets of them), device
+   ms = {high-pass, gather + model, stitch, total} as rvc_convert_info's; any pointer may be NULL.  RVC_SHAPE before one has completed */
+rvc_status rvc_convert_many_info(rvc_engine *e, size_t *windows_total, size_t *batches, int32_t *offsets, size_t cap_offsets, double ms[4]);
+/* rvc_sola_stitch for several files at once, the stitch kernels of rvc_convert_many on host buffers: windows [Wtot][window_len] laid end to end, file f
+   holding windows_per_file[f] >= 1 of them, every file's tail starting as zeros: out [Wtot][frame], offsets [Wtot] (may be NULL).  Equal to rvc_sola_stitch
+   of each file's windows, bit for bit.  rvc_sola_stitch's limits; 1 <= n_files <= 65536, Wtot <= 2^24, else RVC_SHAPE */
+rvc_status rvc_sola_stitch_many(rvc_engine *e, const float *windows, const size_t *windows_per_file, size_t n_files, size_t window_len, size_t sola_len,
+                                size_t search, size_t frame, float *out, int32_t *offsets);
+
 /* ---- what THIS GPU sustains, measured in-run (bench.py; boxes of one pool differ by ~10 % on matrix-core-bound work) ---- */
 /* rvc_calibrate: ~50 ms of device time.  A bare v_mfma_f32_32x32x2_f32 stream on every SIMD (four waves per SIMD, non-zero operands) -> fp32 matrix-core
  * TFLOP/s actually reached and the shader clock it ran at (s_memtime cycles per s_memrealtime tick); a float4 read stream over 1 GiB -> HBM TB/s. */

@@ -44,6 +44,7 @@ SYMBOLS = [
     "rvc_resample_geometry", "rvc_resample", "rvc_resample_device", "rvc_change_rms", "rvc_convert_file", "rvc_convert_file_device", "rvc_convert_file_info",
     "rvc_set_f0_override_stream", "rvc_set_f0_override_hold", "rvc_set_f0_curve", "rvc_f0_curve_grid", "rvc_convert_f0",
     "rvc_analyze_f0", "rvc_analyze_f0_device", "rvc_f0_stats", "rvc_f0_stats_stream", "rvc_set_auto_transpose", "rvc_auto_transpose", "rvc_auto_transpose_info",
+    "rvc_convert_many_geometry", "rvc_convert_many", "rvc_convert_many_info", "rvc_sola_stitch_many",
 ]
 
 
@@ -398,6 +399,12 @@ def lib():
         L.rvc_set_auto_transpose.argtypes = [vp, C.c_double, C.c_int, C.c_double]
         L.rvc_auto_transpose.argtypes = [vp, dp, C.POINTER(C.c_int), dp]
         L.rvc_auto_transpose_info.argtypes = [vp, fp, C.POINTER(sz), dp, dp]
+    if hasattr(L, "rvc_convert_many") or not override:
+        szp = C.POINTER(sz)
+        L.rvc_convert_many_geometry.argtypes = [szp, sz, sz, sz, sz, sz, szp, szp, szp]
+        L.rvc_convert_many.argtypes = [vp, C.POINTER(fp), szp, sz, sz, sz, sz, i32, C.c_int, C.POINTER(fp), szp, szp]
+        L.rvc_convert_many_info.argtypes = [vp, szp, szp, C.POINTER(i32), sz, C.POINTER(C.c_double)]
+        L.rvc_sola_stitch_many.argtypes = [vp, fp, szp, sz, sz, sz, sz, sz, fp, C.POINTER(i32)]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
     if hasattr(L, "rvc_model_speakers") or not override:

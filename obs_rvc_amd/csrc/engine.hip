@@ -1818,6 +1818,7 @@ int rvc_debug_tap(rvc_engine *e, const char *name, int stream, float *out, size_
 #include "session.hip.h"
 #include "rccl_bcast.hip.h"
 #include "convert.hip.h"
+#include "convert_many.hip.h"
 
 namespace rvc {
 

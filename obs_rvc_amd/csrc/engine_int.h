@@ -618,6 +618,8 @@ struct rvc_engine {
     // rvc_convert_info reports of the last completed convert
     rvc::DevBuf<float> hp_taps;
     struct ConvertInfo { bool valid = false; size_t windows = 0, batches = 0; std::vector<int32_t> offsets; double ms[4] = {0, 0, 0, 0}; } conv;
+    // ... and rvc_convert_many_info of the last completed rvc_convert_many (convert_many.hip.h): offsets in global window order
+    ConvertInfo many;
     // ... and rvc_convert_file_info of the last completed rvc_convert_file
     struct FileInfo { bool valid = false; double ms[7] = {0, 0, 0, 0, 0, 0, 0}; size_t rate_out = 0; float peak = 0.f; } file;
     // f0 from outside (f0_override.hip.h).  ov[s]: the pending override rows of stream s (empty = none), for the END of its next f0 window;

@@ -540,6 +540,70 @@ class RvcInfer:
                                           off.ctypes.data_as(C.POINTER(C.c_int32))))
         return out, off
 
+    # -- many recordings in one call (rvc_convert_many*) ----------------------
+    @staticmethod
+    def convert_many_geometry(lengths, sample_rate: int, k: int = 0, context: int = 0, crossfade: int = 0) -> dict:
+        """rvc_convert_many_geometry (host only): the packing of recordings of `lengths` samples at 16 kHz for a model at sample_rate ->
+        {windows (per file), output_samples (per file), windows_total, output_total}"""
+        n = [int(v) for v in lengths]
+        if any(v < 0 for v in n):
+            raise RvcInferError(5, "convert_many geometry out of range")
+        F = len(n)
+        arr = (C.c_size_t * max(F, 1))(*n)
+        w, o, tot = (C.c_size_t * max(F, 1))(), (C.c_size_t * max(F, 1))(), (C.c_size_t * 2)()
+        rc = _native.lib().rvc_convert_many_geometry(arr, F, int(sample_rate), int(k), int(context), int(crossfade), w, o, tot)
+        if rc != 0:
+            raise RvcInferError(rc, "convert_many geometry out of range")
+        return {"windows": [int(v) for v in w[:F]], "output_samples": [int(v) for v in o[:F]], "windows_total": int(tot[0]), "output_total": int(tot[1])}
+
+    def convert_many(self, signals, k: int = 0, context: int = 0, crossfade: int = 0, pitch_shift: int = 0, highpass: bool = True):
+        """rvc_convert_many: a list of 16 kHz recordings -> a list of arrays at the model's rate, one per recording in the order given.  One geometry and one set
+        of settings for all; the windows of all recordings are laid end to end and run n_streams at a time, so short recordings share batches.  The call
+        starts from reset_state().  Refused while auto-transpose is in force or an f0 curve is set."""
+        xs = [np.ascontiguousarray(x, np.float32) for x in signals]
+        if any(x.ndim != 1 for x in xs):
+            raise RvcInferError(5, "convert_many: a recording is a 1-D array")
+        F = len(xs)
+        pin = (_FP * max(F, 1))(*[x.ctypes.data_as(_FP) for x in xs])
+        n = (C.c_size_t * max(F, 1))(*[len(x) for x in xs])
+        lens = (C.c_size_t * max(F, 1))()
+        a = (int(k), int(context), int(crossfade), int(pitch_shift or 0), 1 if highpass else 0)
+        # (the first call sizes the outputs: no capacities is short for every recording; every other refusal reports its own status)
+        rc = self._L.rvc_convert_many(self._h, pin, n, F, *a, None, None, lens)
+        if rc != 5 or F == 0 or any(lens[f] == 0 for f in range(F)):
+            self._chk(rc)
+        outs = [np.empty(lens[f], np.float32) for f in range(F)]
+        pout = (_FP * F)(*[o.ctypes.data_as(_FP) for o in outs])
+        cap = (C.c_size_t * F)(*[len(o) for o in outs])
+        self._chk(self._L.rvc_convert_many(self._h, pin, n, F, *a, pout, cap, lens))
+        return outs
+
+    def convert_many_info(self) -> dict:
+        """rvc_convert_many_info of the last convert_many -> {windows, batches, offsets (int32 array, global window order), ms_highpass, ms_model, ms_stitch,
+        ms_total} (device milliseconds)"""
+        w, b = C.c_size_t(), C.c_size_t()
+        ms = (C.c_double * 4)()
+        self._chk(self._L.rvc_convert_many_info(self._h, C.byref(w), C.byref(b), None, 0, ms))
+        off = np.empty(w.value, np.int32)
+        self._chk(self._L.rvc_convert_many_info(self._h, None, None, off.ctypes.data_as(C.POINTER(C.c_int32)), len(off), None))
+        return {"windows": w.value, "batches": b.value, "offsets": off, "ms_highpass": ms[0], "ms_model": ms[1], "ms_stitch": ms[2], "ms_total": ms[3]}
+
+    def sola_stitch_many(self, windows, windows_per_file, sola_len: int, search: int, frame: int):
+        """rvc_sola_stitch_many: sola_stitch of several files at once.  windows (Wtot, window_len) holds the files' windows end to end, windows_per_file their
+        counts; every file's tail starts as zeros -> (audio (Wtot * frame,), offsets (Wtot,) int32), equal to sola_stitch of each file's windows"""
+        y, yp = _f32(windows)
+        if y.ndim != 2:
+            raise RvcInferError(5, "sola_stitch_many: windows is a (windows, window_len) array")
+        wpf = [int(v) for v in windows_per_file]
+        if any(v < 0 for v in wpf) or sum(wpf) != y.shape[0]:
+            raise RvcInferError(5, "sola_stitch_many: windows_per_file does not add up to the number of windows")
+        cnt = (C.c_size_t * max(len(wpf), 1))(*wpf)
+        out = np.empty(y.shape[0] * int(frame), np.float32)
+        off = np.empty(y.shape[0], np.int32)
+        self._chk(self._L.rvc_sola_stitch_many(self._h, yp, cnt, len(wpf), y.shape[1], int(sola_len), int(search), int(frame), out.ctypes.data_as(_FP),
+                                               off.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, off
+
     def highpass(self, pcm16k):
         """rvc_highpass: the converter's 48 Hz zero-phase high-pass (2049-tap FIR) of a 16 kHz signal"""
         x, xp = _f32(pcm16k)
