@@ -42,7 +42,8 @@ double rvc_debug_ln_fold_check(rvc_engine *e, int M, int K, int N, float offset)
  * bias may be NULL (no bias).  x / y / r are the WHOLE allocations of the input, output and residual tensors (guard zones, halos, ld padding,
  * every stream): uploaded before the launch, downloaded after it.  geo[3][8] receives, for x, y, r: allocation size (floats), offset of element
  * (0, 0, 0) from the allocation's start, C, T (2-D: W), ld (row stride), bs (stream stride), cs (channel stride), H (1-D: 1).  With x == NULL only
- * geo is filled.  0 = done, else an rvc_status (rvc_last_error_message). */
+ * geo is filled.  0 = done, else an rvc_status (rvc_last_error_message).  The plan is built under the engine's rvc_set_gemm_precision setting, as a
+ * real plan is: in mode 1 a layer the split-bf16 rule takes runs on igemm_bf3_kernel (rvc_debug_last_kernel: "bf3"). */
 typedef struct rvc_debug_layer_spec {
     int form, streams;
     int cin, cout, kw, stride, pad, dil, groups;

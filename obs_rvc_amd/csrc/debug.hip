@@ -384,6 +384,7 @@ int rvc_debug_layer(rvc_engine *e, const rvc_debug_layer_spec *s, const float *w
         if (!s || !geo || s->streams < 1 || s->form < 0 || s->form > 4 || ((s->form == 2 || s->form == 3) && (s->n < 1 || s->n > 4))) throw ShapeError("layer spec");
         const int B = s->streams, form = s->form, n = form == 3 ? 2 : s->n;
         Plan pl; pl.key.B = B;
+        pl.key.bf3 = e->gemm_precision == 1;      // the engine's setting, as a real plan's key has it (engine.hip): rvc_set_gemm_precision(e, 1) lets queue_bf3 take the layer
         DebugWeights wts;
         DebugGeo gx, gy, gr;
         T1 x1, y1, r1; T2 x2, y2, r2;

@@ -71,6 +71,8 @@ def lib():
     L.rvc_debug_last_desc.restype = C.c_char_p
     L.rvc_debug_tap.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rvc_debug_tap.restype = C.c_int
+    L.rvc_set_gemm_precision.argtypes = [vp, C.c_int]
+    L.rvc_set_gemm_precision.restype = C.c_int
     return L
 
 
@@ -98,6 +100,10 @@ class Handle:
 
     def last_error(self):
         return self.L.rvc_last_error_message(self.h).decode()
+
+    def set_gemm_precision(self, mode):
+        """rvc_set_gemm_precision: 0 = fp32, 1 = the exploratory split-bf16 GEMM wherever queue_bf3 takes a layer (rvc_debug_layer builds its plan under the engine's setting)"""
+        assert self.L.rvc_set_gemm_precision(self.h, int(mode)) == 0, self.last_error()
 
     def close(self):
         self.L.rvc_destroy(self.h)

@@ -41,7 +41,7 @@ def conv1d(x, w, bias=None, stride=1, pad=0, dil=1, groups=1):
         xg = xp[:, g * cig:(g + 1) * cig]
         for k in range(K):
             tap = xg[:, :, k * dil:k * dil + (Tout - 1) * stride + 1:stride]          # x at t * stride + k * dil - pad, t = 0 .. Tout-1
-            out[:, g * cog:(g + 1) * cog] += np.matmul(w[g * cog:(g + 1) * cog, :, k], tap)
+            out[:, g * cog:(g + 1) * cog] += np.matmul(np.ascontiguousarray(w[g * cog:(g + 1) * cog, :, k]), tap)      # (a contiguous tap matrix: the strided view takes matmul's slow path)
     if bias is not None:
         out += np.asarray(bias, np.float64)[None, :, None]
     return out
@@ -53,9 +53,8 @@ def conv_transpose1d(x, w, bias=None, stride=1, pad=0):
     B, Cin, T = x.shape
     _, Cout, K = w.shape
     full = np.zeros((B, Cout, (T - 1) * stride + K), np.float64)
-    for t in range(T):
-        for k in range(K):
-            full[:, :, t * stride + k] += x[:, :, t] @ w[:, :, k]
+    for k in range(K):
+        full[:, :, k:k + (T - 1) * stride + 1:stride] += np.matmul(np.ascontiguousarray(w[:, :, k].T), x)      # tap k of every input position t lands on t * stride + k
     Tout = (T - 1) * stride - 2 * pad + K
     out = full[:, :, pad:pad + Tout].copy()
     if bias is not None:

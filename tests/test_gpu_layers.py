@@ -161,6 +161,56 @@ def _weights(case, rng):
     return ws, b
 
 
+def conv_of(case, xin, ws, j):
+    """the convolution of output tensor j in fp64, without its bias: linear in the (activated) input xin and in the weights ws"""
+    p = case.p
+    f = p["form"]
+    if f == 0:
+        return R.conv1d(xin, ws[0], None, p["stride"], p["pad"], p["dil"], p["groups"])[:, :, :p["t_out"]]      # (Tout = T + 1: the last column is dropped)
+    if f == 1:
+        return R.conv_transpose1d(xin, ws[0], None, p["stride"], p["pad"])
+    if f == 2:
+        xj = xin[:, j * p["cin"]:(j + 1) * p["cin"]] if p["x_grouped"] else xin
+        return R.conv1d(xj, ws[j], None, 1, p["pads"][j], p["dils"][j])
+    if f == 3:
+        return R.conv1d(xin, ws[j], None)
+    return R.conv2d_3x3(xin, ws[0], None)
+
+
+def finish(case, d, convs):
+    """the layer's epilogue in fp64 on convs[j] (conv_of) -> per output tensor: (value, rms of the largest addend)"""
+    p = case.p
+    f = p["form"]
+    refs = []
+    for j, a in enumerate(convs):
+        if d.b is not None:
+            a = a + d.b[j * p["cout"]:(j + 1) * p["cout"]].astype(np.float64).reshape((1, -1) + (1,) * (a.ndim - 2))
+        if p["glu"]:
+            v = R.glu_gate(a)
+            assert v.shape == d.y0[j].shape, (case.name, v.shape, d.y0[j].shape)
+            refs.append((v, R_rms(v)))
+            continue
+        assert a.shape == d.y0[j].shape, (case.name, a.shape, d.y0[j].shape)
+        v = R.act(a, p["act"], p["slope"])
+        addends = [v]
+        if p["res"] == 1:
+            rr = d.r[:, j * p["cout"]:(j + 1) * p["cout"]] if (f == 2 and p["res_grouped"]) else d.r[:, :p["cout"]]
+            addends.append(rr.astype(np.float64))
+        elif p["res"] == 2:
+            addends.append(np.broadcast_to(d.r.astype(np.float64), v.shape))
+        elif p["res"] == 3:
+            addends.append(d.y0[j].astype(np.float64))
+        elif p["res"] == 4:
+            addends.append(d.x.astype(np.float64)[:, :p["cout"], :p["t_out"]])
+        v = sum(addends) * p["scale"]
+        addends = [a_ * abs(p["scale"]) for a_ in addends]
+        if p["accumulate"]:
+            addends.append(d.y0[j].astype(np.float64))
+            v = v + d.y0[j]
+        refs.append((v, max([R_rms(v)] + [R_rms(a_) for a_ in addends])))
+    return refs
+
+
 class Data:
     pass
 
@@ -192,46 +242,8 @@ def data_for(case, streams):
         d.r = rng.uniform(-1, 1, (B, rrows) + oshape[2:]).astype(np.float32)
     elif p["res"] == 2:
         d.r = rng.uniform(-1, 1, (p["t_out"],)).astype(np.float32)
-    # reference, per output tensor: (value, rms of the largest addend)
     xin = R.act(d.x, p["pre_act"], p["pre_slope"]) if p["pre_act"] else d.x.astype(np.float64)
-    refs = []
-    for j in range(n_out):
-        bj = None if d.b is None else d.b[j * p["cout"]:(j + 1) * p["cout"]]
-        if f == 0:
-            a = R.conv1d(xin, d.ws[0], bj, p["stride"], p["pad"], p["dil"], p["groups"])[:, :, :p["t_out"]]      # (Tout = T + 1: the last column is dropped)
-        elif f == 1:
-            a = R.conv_transpose1d(xin, d.ws[0], bj, p["stride"], p["pad"])
-        elif f == 2:
-            xj = xin[:, j * p["cin"]:(j + 1) * p["cin"]] if p["x_grouped"] else xin
-            a = R.conv1d(xj, d.ws[j], bj, 1, p["pads"][j], p["dils"][j])
-        elif f == 3:
-            a = R.conv1d(xin, d.ws[j], bj)
-        else:
-            a = R.conv2d_3x3(xin, d.ws[0], bj)
-        if p["glu"]:
-            v = R.glu_gate(a)
-            assert v.shape == oshape, (case.name, v.shape, oshape)
-            refs.append((v, R_rms(v)))
-            continue
-        assert a.shape == oshape, (case.name, a.shape, oshape)
-        v = R.act(a, p["act"], p["slope"])
-        addends = [v]
-        if p["res"] == 1:
-            rr = d.r[:, j * p["cout"]:(j + 1) * p["cout"]] if (f == 2 and p["res_grouped"]) else d.r[:, :p["cout"]]
-            addends.append(rr.astype(np.float64))
-        elif p["res"] == 2:
-            addends.append(np.broadcast_to(d.r.astype(np.float64), v.shape))
-        elif p["res"] == 3:
-            addends.append(d.y0[j].astype(np.float64))
-        elif p["res"] == 4:
-            addends.append(d.x.astype(np.float64)[:, :p["cout"], :p["t_out"]])
-        v = sum(addends) * p["scale"]
-        addends = [a_ * abs(p["scale"]) for a_ in addends]
-        if p["accumulate"]:
-            addends.append(d.y0[j].astype(np.float64))
-            v = v + d.y0[j]
-        refs.append((v, max([R_rms(v)] + [R_rms(a_) for a_ in addends])))
-    d.refs = refs
+    d.refs = finish(case, d, [conv_of(case, xin, d.ws, j) for j in range(n_out)])
     for k in [k for k in _CACHE if k[0] != case.name]:
         del _CACHE[k]           # (one form at a time: the cache only has to outlive the runs of one form)
     _CACHE[key] = d
@@ -264,8 +276,8 @@ def _y_index(case, g, B, j):
 
 
 class Layer(Handle):
-    def run(self, case, streams):
-        """-> (family, list of problems)"""
+    def run(self, case, streams, tol=TOL):
+        """-> (family, list of problems); self.errors = max err / rms of every output tensor (tol: the bound on it, for a family that does not compute in fp32)"""
         p, B = case.p, streams
         d = data_for(case, streams)
         s = case.spec(streams)
@@ -301,6 +313,7 @@ class Layer(Handle):
         fam = self.last_kernel()
         self.outputs = [y[yi] for yi in yidx]          # (the interiors of this run's output tensors, for the tests that compare bits)
         bad = []
+        self.errors = []
         if not same_bits(x, x0):
             bad.append("input tensor changed at %d positions" % int(np.count_nonzero(x.view(np.uint32) != x0.view(np.uint32))))
         if r is not None and not same_bits(r, r0):
@@ -313,7 +326,8 @@ class Layer(Handle):
         for j, (ref, scale) in enumerate(d.refs):
             got = y[yidx[j]].astype(np.float64)
             e = float(np.max(np.abs(got - ref))) / max(scale, 1e-30) if np.all(np.isfinite(got)) else np.inf
-            if not e < TOL:
+            self.errors.append(e)
+            if not e < tol:
                 wi = np.unravel_index(int(np.argmax(np.abs(got - ref))), ref.shape)
                 bad.append("output %d: max err / rms %.3e at %s (gpu %.6g, ref %.6g)" % (j, e, wi, got[wi], ref[wi]))
         return fam, bad
