@@ -145,6 +145,14 @@ extern "C" {
     pub fn rvc_convert_many_info(e: *mut RvcEngine, windows_total: *mut usize, batches: *mut usize, offsets: *mut i32, cap_offsets: usize, ms: *mut f64) -> c_int;
     pub fn rvc_sola_stitch_many(e: *mut RvcEngine, windows: *const c_float, windows_per_file: *const usize, n_files: usize, window_len: usize, sola_len: usize,
                                 search: usize, frame: usize, out: *mut c_float, offsets: *mut i32) -> c_int;
+    // the file converter's silence gate: threshold <= -60 dB = off, hang 0..1000 frames; declared for the header's sake
+    pub fn rvc_set_convert_silence(e: *mut RvcEngine, threshold_db: c_double, hang_frames: c_int) -> c_int;
+    pub fn rvc_convert_silence(e: *mut RvcEngine, threshold_db: *mut c_double, hang_frames: *mut c_int) -> c_int;
+    pub fn rvc_convert_silence_info(e: *mut RvcEngine, windows_run: *mut usize, windows_skipped: *mut usize, frames_loud: *mut usize, frames_kept: *mut usize,
+                                    ms_analysis: *mut c_double) -> c_int;
+    pub fn rvc_silence_map(e: *mut RvcEngine, pcm16k: *const c_float, n: usize, threshold_db: c_double, hang_frames: c_int, k: usize, context: usize, crossfade: usize,
+                           sample_rate: usize, frame_loud: *mut u8, frame_kept: *mut u8, cap_frames: usize, window_active: *mut u8, window_place: *mut i32,
+                           cap_windows: usize) -> c_int;
     pub fn rvc_set_noise_seed(e: *mut RvcEngine, seed: u32, stream_id: u32);
     pub fn rvc_reset_state(e: *mut RvcEngine);
 

@@ -621,6 +621,34 @@ rvc_status rvc_convert_many_info(rvc_engine *e, size_t *windows_total, size_t *b
 rvc_status rvc_sola_stitch_many(rvc_engine *e, const float *windows, const size_t *windows_per_file, size_t n_files, size_t window_len, size_t sola_len,
                                 size_t search, size_t frame, float *out, int32_t *offsets);
 
+/* ---- the file converter's silence gate (the upstream client's response threshold, slicer2's job) ---- */
+/* Off by default.  With a threshold set, rvc_convert*, rvc_convert_file* (on the resampled and filtered signal), rvc_convert_many, rvc_analyze_f0* and the
+ * analysis pass of auto-transpose measure the signal the model will see and run only the windows that hold something.  In 10 ms frames of 160 samples, the
+ * signal x zero-extended beyond [0, N), Nf = ceil(N / 160):
+ *   frame i is LOUD iff 20 log10(max(rms(x[160 i, 160 i + 640)), 1e-5)) >= threshold_db -- rvc_session_set_input_gate's measure --, decided as
+ *       sumsq >= 640 max(10^(threshold_db / 10), 1e-10) with the sum in fp64 in a fixed order;
+ *   frame i is KEPT iff a loud frame j has |i - j| <= hang_frames;
+ *   window w is ACTIVE iff a kept frame lies in [w H, w H + H + X + Q) n [0, Nf), the frames its return_length covers.
+ * The active windows are compacted in order: the j-th of them runs on stream j % S of batch j / S -- across files, in global window order, for
+ * rvc_convert_many -- and only the last batch is padded with all-zero windows.  A skipped window is neither gathered nor inferred: return_length zc exact zeros
+ * take its place in the unchanged stitch chain, and its f0 rows are 0 in rvc_convert_f0, rvc_analyze_f0 and the auto-transpose analysis.  The result is, bit
+ * for bit, the composition: gather, rvc_reset_state, rvc_infer_batch per compacted batch, zero windows inserted at the skipped positions, rvc_sola_stitch (per
+ * file: rvc_sola_stitch_many).  Noise counters follow the place, so this is NOT the ungated output with holes.  rvc_convert_info / rvc_convert_many_info report
+ * every window (offsets of skipped ones included) and the batches actually run; a call without an active window runs no batch and no model kernel and returns
+ * zeros with RVC_OK.  An f0 curve acts on the windows that run, by absolute frame.  The streaming session and the index builder never read the setting.
+ * rvc_set_convert_silence: engine-wide, kept over model loads; threshold_db <= -60 = off (the session gate's convention), hang_frames in [0, 1000]; NaN or a
+ * hang out of range: RVC_SHAPE, state unchanged.  rvc_convert_silence reads the setting back.  rvc_convert_silence_info: of the last completed call that ran
+ * with the gate (rvc_silence_map included) -- windows run and skipped, loud and kept frames, device ms of the gate's own kernels; RVC_SHAPE before one has.
+ * rvc_silence_map: the analysis alone on host buffers, with its own threshold (applied as given) and hang; needs no model; sample_rate only enters the
+ * geometry check (a multiple of 100).  frame_loud / frame_kept [Nf] (cap_frames), window_active [W] and window_place [W] (cap_windows; place = the window's
+ * rank among the active ones, -1 = skipped); any of the four may be NULL; RVC_SHAPE for n = 0, NaN, a bad hang or geometry, a short cap of a given buffer. */
+rvc_status rvc_set_convert_silence(rvc_engine *e, double threshold_db, int hang_frames);
+rvc_status rvc_convert_silence(rvc_engine *e, double *threshold_db, int *hang_frames);
+rvc_status rvc_convert_silence_info(rvc_engine *e, size_t *windows_run, size_t *windows_skipped, size_t *frames_loud, size_t *frames_kept, double *ms_analysis);
+rvc_status rvc_silence_map(rvc_engine *e, const float *pcm16k, size_t n, double threshold_db, int hang_frames, size_t k, size_t context, size_t crossfade,
+                           size_t sample_rate, uint8_t *frame_loud, uint8_t *frame_kept, size_t cap_frames, uint8_t *window_active, int32_t *window_place,
+                           size_t cap_windows);
+
 /* ---- what THIS GPU sustains, measured in-run (bench.py; boxes of one pool differ by ~10 % on matrix-core-bound work) ---- */
 /* rvc_calibrate: ~50 ms of device time.  A bare v_mfma_f32_32x32x2_f32 stream on every SIMD (four waves per SIMD, non-zero operands) -> fp32 matrix-core
  * TFLOP/s actually reached and the shader clock it ran at (s_memtime cycles per s_memrealtime tick); a float4 read stream over 1 GiB -> HBM TB/s. */

@@ -45,6 +45,7 @@ SYMBOLS = [
     "rvc_set_f0_override_stream", "rvc_set_f0_override_hold", "rvc_set_f0_curve", "rvc_f0_curve_grid", "rvc_convert_f0",
     "rvc_analyze_f0", "rvc_analyze_f0_device", "rvc_f0_stats", "rvc_f0_stats_stream", "rvc_set_auto_transpose", "rvc_auto_transpose", "rvc_auto_transpose_info",
     "rvc_convert_many_geometry", "rvc_convert_many", "rvc_convert_many_info", "rvc_sola_stitch_many",
+    "rvc_set_convert_silence", "rvc_convert_silence", "rvc_convert_silence_info", "rvc_silence_map",
 ]
 
 
@@ -405,6 +406,12 @@ def lib():
         L.rvc_convert_many.argtypes = [vp, C.POINTER(fp), szp, sz, sz, sz, sz, i32, C.c_int, C.POINTER(fp), szp, szp]
         L.rvc_convert_many_info.argtypes = [vp, szp, szp, C.POINTER(i32), sz, C.POINTER(C.c_double)]
         L.rvc_sola_stitch_many.argtypes = [vp, fp, szp, sz, sz, sz, sz, sz, fp, C.POINTER(i32)]
+    if hasattr(L, "rvc_set_convert_silence") or not override:
+        szp, dp, u8p = C.POINTER(sz), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        L.rvc_set_convert_silence.argtypes = [vp, C.c_double, C.c_int]
+        L.rvc_convert_silence.argtypes = [vp, dp, C.POINTER(C.c_int)]
+        L.rvc_convert_silence_info.argtypes = [vp, szp, szp, szp, szp, dp]
+        L.rvc_silence_map.argtypes = [vp, fp, sz, C.c_double, C.c_int, sz, sz, sz, sz, u8p, u8p, sz, u8p, C.POINTER(i32), sz]
     if hasattr(L, "rvc_model_has_f0") or not override:
         L.rvc_model_has_f0.argtypes = [vp]
     if hasattr(L, "rvc_model_speakers") or not override:

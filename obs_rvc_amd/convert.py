@@ -63,6 +63,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--auto-pitch-step", type=int, choices=AUTO_PITCH_STEPS, default=1, help="round the transpose to 1 = whole semitones (default), 12 = whole octaves, 0 = not at all")
     p.add_argument("--auto-pitch-limit", type=float, default=12.0, help="the largest auto-transpose in semitones, 0..24 (default 12)")
     p.add_argument("--analyze-only", action="store_true", help="write the recording's f0 (no transpose, no pitch control) to --f0-out and convert nothing; needs no --model")
+    p.add_argument("--skip-silence", type=float, default=None, metavar="DB",
+                   help="do not run windows in which nothing reaches DB (40 ms RMS in dB, the live gate's measure; above -60, e.g. -50): they become exact silence")
+    p.add_argument("--silence-hang", type=int, default=None, metavar="FRAMES", help="10 ms frames kept on each side of a loud frame, 0..1000 (default 30; with --skip-silence)")
     p.add_argument("--device", type=int, default=-1)
     a = p.parse_args(argv)
     if a.analyze_only:
@@ -76,6 +79,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--auto-pitch and --auto-pitch-from exclude each other")
     if not 0.0 <= a.auto_pitch_limit <= 24.0:
         p.error("--auto-pitch-limit is 0..24 semitones")
+    if a.silence_hang is not None and a.skip_silence is None:
+        p.error("--silence-hang goes with --skip-silence")
+    if a.skip_silence is not None and not -60.0 < a.skip_silence <= 0.0:
+        p.error("--skip-silence is a level in dB above -60 and at most 0")
+    if a.silence_hang is None:
+        a.silence_hang = SILENCE_HANG_DEFAULT
+    if not 0 <= a.silence_hang <= 1000:
+        p.error("--silence-hang is 0..1000 frames")
     if a.f0_file is not None:
         try:
             with open(a.f0_file) as fh:
@@ -120,6 +131,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 F0_CHOICES = ("rmvpe", "yin", "crepe-full", "crepe-tiny", "fcpe", "pm")
 AUTO_PITCH_STEPS = (0, 1, 12)
+SILENCE_HANG_DEFAULT = 30
 
 
 def f0_arg(text: str) -> str:
@@ -239,11 +251,17 @@ def main(argv=None) -> int:
     if a.analyze_only:      # the recording's own f0 and nothing else: no ContentVec, no voice model
         load_f0()
         eng.set_streams(a.streams)
+        if a.skip_silence is not None:
+            eng.set_convert_silence(a.skip_silence, a.silence_hang)
         hz = eng.analyze_f0(to_16k(x, rate), window=a.window, context=a.context, crossfade=a.crossfade, highpass=a.highpass)
         with open(a.f0_out, "w") as fh:
             fh.write(format_f0_curve(hz))
         med, voiced = eng.f0_stats(hz)
-        print("%s: %d frames, %d voiced, median f0 %.2f Hz" % (a.f0_out, len(hz), voiced, float(med[0])))
+        line = "%s: %d frames, %d voiced, median f0 %.2f Hz" % (a.f0_out, len(hz), voiced, float(med[0]))
+        if a.skip_silence is not None:
+            s = eng.convert_silence_info()
+            line += "; %d windows run, %d skipped as silent" % (s["windows_run"], s["windows_skipped"])
+        print(line)
         eng.close()
         return 0
     eng.load_contentvec(a.version)
@@ -267,6 +285,8 @@ def main(argv=None) -> int:
     eng.set_protect(a.protect)
     if a.f0_curve is not None:
         eng.set_f0_curve(*a.f0_curve)
+    if a.skip_silence is not None:
+        eng.set_convert_silence(a.skip_silence, a.silence_hang)
     auto = eng.model_has_f0() and (a.auto_pitch > 0.0 or a.auto_pitch_from is not None)
     if auto:
         target = a.auto_pitch
@@ -303,6 +323,11 @@ def main(argv=None) -> int:
         t = eng.auto_transpose_info()
         print("auto-pitch: median f0 %.2f Hz over %d voiced frames, target %.2f Hz -> %+.2f semitones (device ms: analysis %.2f, select %.2f)"
               % (float(t["median_hz"]), t["voiced"], eng.auto_transpose()["target_hz"], t["semitones"], t["ms_analysis"], t["ms_select"]))
+    if a.skip_silence is not None:
+        s = eng.convert_silence_info()
+        n16 = -(-len(x) * 16000 // rate)      # the gate's frames are those of the 16 kHz signal the model saw
+        print("skip-silence: %d windows run, %d skipped; %d of %d frames kept (device ms: analysis %.2f)"
+              % (s["windows_run"], s["windows_skipped"], s["frames_kept"], -(-n16 // 160), s["ms_analysis"]))
     print("%s: %.2f s at %d Hz from %d windows in %d batches; device ms: high-pass %.2f, model %.2f, stitch %.2f, total %.2f"
           % (a.output, len(y) / out_rate, out_rate, info["windows"], info["batches"], info["ms_highpass"], info["ms_model"], info["ms_stitch"], info["ms_total"]))
     eng.close()

@@ -15,7 +15,7 @@ import os
 import sys
 
 from .build_index import read_wav
-from .convert import F0_CHOICES, f0_arg, parse_sid_mix, write_wav
+from .convert import F0_CHOICES, SILENCE_HANG_DEFAULT, f0_arg, parse_sid_mix, write_wav
 
 PER_RECORDING = ("--auto-pitch", "--f0-file", "--f0-out", "--analyze-only")
 
@@ -45,11 +45,22 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--no-highpass", dest="highpass", action="store_false", help="skip the 48 Hz high-pass in front of the model")
     p.add_argument("--rate", type=int, default=0, help="output sample rate (default: the model's)")
     p.add_argument("--rms-mix-rate", type=float, default=1.0, help="volume envelope, 0..1: 0 = each input's envelope, 1 = the model's own (default)")
+    p.add_argument("--skip-silence", type=float, default=None, metavar="DB",
+                   help="do not run windows in which nothing reaches DB (40 ms RMS in dB, the live gate's measure; above -60, e.g. -50): they become exact silence")
+    p.add_argument("--silence-hang", type=int, default=None, metavar="FRAMES", help="10 ms frames kept on each side of a loud frame, 0..1000 (default 30; with --skip-silence)")
     p.add_argument("--device", type=int, default=-1)
     for arg in (sys.argv[1:] if argv is None else argv):
         if str(arg).startswith(PER_RECORDING):
             p.error("%s belongs to one recording: use python -m obs_rvc_amd.convert for it" % str(arg).split("=", 1)[0])
     a = p.parse_args(argv)
+    if a.silence_hang is not None and a.skip_silence is None:
+        p.error("--silence-hang goes with --skip-silence")
+    if a.skip_silence is not None and not -60.0 < a.skip_silence <= 0.0:
+        p.error("--skip-silence is a level in dB above -60 and at most 0")
+    if a.silence_hang is None:
+        a.silence_hang = SILENCE_HANG_DEFAULT
+    if not 0 <= a.silence_hang <= 1000:
+        p.error("--silence-hang is 0..1000 frames")
     if a.sid is not None and a.sid_mix is not None:
         p.error("--sid and --sid-mix exclude each other")
     if a.sid is not None and a.sid < 0:
@@ -124,6 +135,8 @@ def main(argv=None) -> int:
     eng.set_pitch_semitones(a.pitch)
     eng.set_formant_shift(a.formant)
     eng.set_protect(a.protect)
+    if a.skip_silence is not None:
+        eng.set_convert_silence(a.skip_silence, a.silence_hang)
     x16 = [x if rate == 16000 else eng.resample(x, rate, 16000) for x, rate in recs]
     ys = eng.convert_many(x16, k=a.window, context=a.context, crossfade=a.crossfade, pitch_shift=0, highpass=a.highpass)
     info = eng.convert_many_info()
@@ -139,6 +152,9 @@ def main(argv=None) -> int:
             y = eng.resample(y, model_rate, out_rate)
         write_wav(os.path.join(a.output, os.path.splitext(f)[0] + ".wav"), y, out_rate)
         seconds += len(y) / out_rate
+    if a.skip_silence is not None:
+        s = eng.convert_silence_info()
+        print("skip-silence: %d windows run, %d skipped (device ms: analysis %.2f)" % (s["windows_run"], s["windows_skipped"], s["ms_analysis"]))
     print("%s: %d files, %.2f s at %d Hz from %d windows in %d batches; device ms: high-pass %.2f, model %.2f, stitch %.2f, total %.2f"
           % (a.output, len(names), seconds, out_rate, info["windows"], info["batches"], info["ms_highpass"], info["ms_model"], info["ms_stitch"], info["ms_total"]))
     eng.close()

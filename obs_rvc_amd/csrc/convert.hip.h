@@ -11,11 +11,17 @@
 #include "stitch.hip.h"
 #include "resample_whole.hip.h"
 #include "change_rms.hip.h"
+#include "silence.hip.h"
 
 namespace rvc {
 // (what f0_analyze.hip.h uses of this file, defined below)
 static void launch_highpass(rvc_engine *e, const float *d_x, size_t n, float *d_y);
 static void launch_window_gather(hipStream_t st, const float *sig, long long N, float *dst, int n, int S, long long w0, int nw, int H, int C);
+// the silence gate of a call on one recording (silence.hip.h): the analysis of sig and the tables of a call of one file
+struct SilenceGate { SilenceWork work; ManyDeviceTables tabs; };
+static void silence_gate_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, size_t zero_len, SilenceGate *gate);
+static void silence_gate_report(rvc_engine *e, const SilenceWork &w);
+static inline bool silence_gate_on(const rvc_engine *e) { return e->sil_db > SILENCE_OFF_DB; }
 }
 #include "f0_analyze.hip.h"
 
@@ -49,6 +55,20 @@ static void launch_highpass(rvc_engine *e, const float *d_x, size_t n, float *d_
     }
     if (n > ((size_t)1 << 40)) throw ShapeError("highpass: signal too long");
     hipLaunchKernelGGL(highpass_fir_kernel, dim3((unsigned)((n + HP_TILE - 1) / HP_TILE)), dim3(HP_THREADS), 0, e->stream, d_x, (long long)n, (const float *)e->hp_taps.get(), d_y);
+}
+
+// the gate's analysis of one recording with the engine's setting, queued on the engine's stream; returns behind the call's one read (synchronised)
+static void silence_gate_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, size_t zero_len, SilenceGate *gate)
+{
+    gate->work.begin(e->stream, g.Nf, g.windows, e->sil_db, e->sil_hang, zero_len);
+    silence_single_tables(&gate->tabs, n, g);
+    gate->work.queue_file(e->stream, sig, n, g.Nf, 0, g.windows, 0, g);
+    gate->work.finish(e->stream);
+}
+static void silence_gate_report(rvc_engine *e, const SilenceWork &w)
+{
+    e->sil_info.run = w.A; e->sil_info.skipped = w.W - w.A; e->sil_info.loud = w.n_loud; e->sil_info.kept = w.n_kept; e->sil_info.ms = w.ms;
+    e->sil_info.valid = true;
 }
 
 // the two stitch launches for windows [w0, w0 + nw) whose outputs lie in y [nw][y_bs]
@@ -96,8 +116,10 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
                               DevBuf<float> *keep_filtered = nullptr)
 {
     hipStream_t st = e->stream;
-    const size_t S = (size_t)e->n_streams, W = g.windows, batches = (W + S - 1) / S;
+    const size_t S = (size_t)e->n_streams, W = g.windows;
+    size_t batches = (W + S - 1) / S;
     const size_t sola_len = g.X * g.zc, search = g.Q * g.zc, frame = g.H * g.zc, ylen = g.return_length * g.zc;
+    const bool gated = silence_gate_on(e);
     e->conv.valid = false; e->conv_f0_valid = false;
     HIPCHK(hipDeviceSynchronize());
     reset_state(e);          // (pending f0 overrides of the streams go with it: a conversion uses the curve alone)
@@ -130,13 +152,21 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
         t_hp.stop(st);
         sig = filtered.get();
     }
+    // the silence gate (silence.hip.h): with a threshold set, the signal the model will see is measured first, the active windows are
+    // compacted and only they run; a skipped window enters the stitch as zeros.  Off (the default): nothing is queued here and the loop below is the ungated one
+    SilenceGate gate;
+    if (gated) {
+        silence_gate_run(e, sig, n, g, ylen, &gate);
+        batches = gate.work.batches(S);
+        if (has_f0) HIPCHK(hipMemsetAsync(f0grid.get(), 0, g.Nf * sizeof(float), st));      // (the rows of skipped windows are 0)
+    }
     // auto-transpose (f0_analyze.hip.h): with a target set, the f0 of the signal the model will see is analysed first -- the call's own
-    // windows through the pitch-only plan --, the curve merged in, and 12 log2(target / median) semitones become one more factor of every stream's multiplier
-    // until the call returns, on whatever path.  Off (the default): nothing is queued here
+    // windows through the pitch-only plan (the gate's active ones when it is on) --, the curve merged in, and 12 log2(target / median) semitones become one more
+    // factor of every stream's multiplier until the call returns, on whatever path.  Off (the default): nothing is queued here
     struct AutoGuard { rvc_engine *e; ~AutoGuard() { e->auto_mul = 0.f; } } auto_guard{e};
     if (has_f0 && e->at_target > 0.0) {
         float mul = 0.f;
-        const rvc_status rc = auto_transpose_run(e, sig, n, g, curve ? e->curve_grid.get() : nullptr, &mul);
+        const rvc_status rc = auto_transpose_run(e, sig, n, g, curve ? e->curve_grid.get() : nullptr, &mul, gated ? &gate : nullptr);
         if (rc != RVC_OK) return rc;
         e->auto_mul = mul;
     }
@@ -146,26 +176,37 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
     HIPCHK(hipMemsetAsync(tails.get(), 0, sola_len * sizeof(float), st));       // tails[0]: the stitch starts from silence
     std::vector<DevEvent> ev(3 * batches);
     for (size_t b = 0; b < batches; b++) {
-        const size_t w0 = b * S; const int nw = (int)std::min(S, W - w0);
+        // (gated: w0 is the batch's first PLACE and nw its active windows, of the A in all)
+        const size_t w0 = b * S; const int nw = (int)std::min(S, (gated ? gate.work.A : W) - w0);
         ev[3 * b].record(st);
-        hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, (long long)n, win.get(), (int)g.n, (long long)w0, nw,
+        if (gated) gate.work.gather(st, sig, gate.tabs.t, win.get(), S, w0, g);
+        else hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, (long long)n, win.get(), (int)g.n, (long long)w0, nw,
                            (int)g.H, (int)g.C);
         size_t got = 0;
-        if (curve) e->conv_call = F0OvCall{e->curve_grid.get(), (long long)g.Nf, 1, (int)w0, nw, (int)g.H, Cg, 0};
+        if (curve) e->conv_call = F0OvCall{e->curve_grid.get(), (long long)g.Nf, 1, (int)w0, nw, (int)g.H, Cg, 0, gated ? gate.work.win_of.get() : nullptr};
         const rvc_status rc = infer_common(e, win.get(), true, g.n, g.sf, pitch_shift, (uint32_t)g.skip_head, (uint32_t)g.return_length, y.get(), true, ylen, &got, true);
         if (rc != RVC_OK) return rc;
         if (got != ylen) throw ShapeError("convert: the synthesizer does not produce sample_rate / 100 samples per frame");
         ev[3 * b + 1].record(st);
-        launch_stitch(st, y.get(), (long long)ylen, (int)w0, nw, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out, (long long)g.out_samples);
+        if (gated) gate.work.stitch(st, y.get(), (long long)ylen, w0, nw, gate.tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out);
+        else launch_stitch(st, y.get(), (long long)ylen, (int)w0, nw, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out, (long long)g.out_samples);
         ev[3 * b + 2].record(st);
         // the batch's conditioned f0 rows onto the grid, behind the timed sections: in ms[3] (total), in neither ms[1] (model) nor ms[2] (stitch).  The plan's rows
         // stay until the next batch's pitch tail, which this stream orders behind the launch
         if (export_ok) {
             const Plan *pl = e->last_plan;      // (streams in several formant buckets ran through several plans: no export then)
-            if (pl && !pl->key.bucket && pl->d_f0 && pl->key.B == (int)S && (size_t)Cg + g.H <= (size_t)pl->Tm)
-                launch_f0_export(st, pl->d_f0, pl->Tm, (int)w0, nw, (int)g.H, Cg, f0grid.get(), (long long)g.Nf);
-            else export_ok = false;
+            if (pl && !pl->key.bucket && pl->d_f0 && pl->key.B == (int)S && (size_t)Cg + g.H <= (size_t)pl->Tm) {
+                if (gated) gate.work.export_f0(st, pl->d_f0, pl->Tm, S, w0, (int)g.H, Cg, f0grid.get(), (long long)g.Nf);
+                else launch_f0_export(st, pl->d_f0, pl->Tm, (int)w0, nw, (int)g.H, Cg, f0grid.get(), (long long)g.Nf);
+            } else export_ok = false;
         }
+    }
+    // a gated call without an active window: no batch ran; the stitch walks its W windows of zeros (offsets and output as rvc_sola_stitch's on zeros)
+    DevTimer t_zero;
+    if (gated && batches == 0) {
+        t_zero.start(st);
+        gate.work.stitch(st, y.get(), (long long)ylen, 0, 0, gate.tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out);
+        t_zero.stop(st);
     }
     t_total.stop(st);
     e->conv.offsets.assign(W, 0);
@@ -179,6 +220,8 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
         HIPCHK(hipEventElapsedTime(&a, ev[3 * b].get(), ev[3 * b + 1].get())); HIPCHK(hipEventElapsedTime(&c, ev[3 * b + 1].get(), ev[3 * b + 2].get()));
         ms_model += a; ms_stitch += c;
     }
+    if (gated && batches == 0) ms_stitch = (double)t_zero.ms();
+    if (gated) silence_gate_report(e, gate.work);
     e->conv.windows = W; e->conv.batches = batches;
     e->conv.ms[0] = highpass ? (double)t_hp.ms() : 0.0; e->conv.ms[1] = ms_model; e->conv.ms[2] = ms_stitch; e->conv.ms[3] = (double)t_total.ms();
     e->conv.valid = true; e->conv_f0_valid = export_ok;
@@ -397,6 +440,76 @@ rvc_status rvc_sola_stitch(rvc_engine *e, const float *windows, size_t n_windows
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
         if (offsets) for (size_t i = 0; i < n_windows; i++) offsets[i] = off[i];
+        return RVC_OK;
+    });
+}
+
+// the silence gate of the file converter (silence.hip.h): engine-wide, at or below -60 dB = off (the default), hang in [0, 1000] frames; anything else, NaN
+// included, is refused and changes nothing
+rvc_status rvc_set_convert_silence(rvc_engine *e, double threshold_db, int hang_frames)
+{
+    return guarded(e, [&]() {
+        if (threshold_db != threshold_db) throw ShapeError("convert silence: the threshold is not a number");
+        if (hang_frames < 0 || hang_frames > SILENCE_MAX_HANG) throw ShapeError("convert silence: the hang is in [0, 1000] frames");
+        e->sil_db = threshold_db; e->sil_hang = hang_frames;
+        return RVC_OK;
+    });
+}
+
+rvc_status rvc_convert_silence(rvc_engine *e, double *threshold_db, int *hang_frames)
+{
+    return guarded(e, [&]() {
+        if (threshold_db) *threshold_db = e->sil_db;
+        if (hang_frames) *hang_frames = e->sil_hang;
+        return RVC_OK;
+    });
+}
+
+// of the last completed conversion or analysis that ran with the gate: windows run and skipped, loud and kept frames, device ms of the gate's own kernels
+rvc_status rvc_convert_silence_info(rvc_engine *e, size_t *windows_run, size_t *windows_skipped, size_t *frames_loud, size_t *frames_kept, double *ms_analysis)
+{
+    return guarded(e, [&]() {
+        if (!e->sil_info.valid) throw ShapeError("convert_silence_info: no call has run with the silence gate on this engine");
+        if (windows_run) *windows_run = e->sil_info.run;
+        if (windows_skipped) *windows_skipped = e->sil_info.skipped;
+        if (frames_loud) *frames_loud = e->sil_info.loud;
+        if (frames_kept) *frames_kept = e->sil_info.kept;
+        if (ms_analysis) *ms_analysis = e->sil_info.ms;
+        return RVC_OK;
+    });
+}
+
+// the gate's analysis alone, on host buffers and with its own threshold (applied as given: -60 is a threshold here, not "off") and hang; no model is needed.
+// frame_loud / frame_kept [Nf] (cap_frames), window_active / window_place [W] (cap_windows); any of them may be NULL, a given one with a short cap is RVC_SHAPE
+rvc_status rvc_silence_map(rvc_engine *e, const float *pcm16k, size_t n, double threshold_db, int hang_frames, size_t k, size_t context, size_t crossfade, size_t sample_rate,
+                           uint8_t *frame_loud, uint8_t *frame_kept, size_t cap_frames, uint8_t *window_active, int32_t *window_place, size_t cap_windows)
+{
+    return guarded(e, [&]() {
+        if (n == 0 || !pcm16k) throw ShapeError("silence_map: empty recording");
+        if (threshold_db != threshold_db) throw ShapeError("silence_map: the threshold is not a number");
+        if (hang_frames < 0 || hang_frames > SILENCE_MAX_HANG) throw ShapeError("silence_map: the hang is in [0, 1000] frames");
+        ConvertGeometry g;
+        if (const char *why = convert_geometry(n, sample_rate, k, context, crossfade, &g)) throw ShapeError(why);
+        if (g.windows > (size_t)1 << 30) throw ShapeError("silence_map: recording too long");
+        if ((frame_loud || frame_kept) && cap_frames < g.Nf) throw ShapeError("silence_map: frame buffer too small");
+        if ((window_active || window_place) && cap_windows < g.windows) throw ShapeError("silence_map: window buffer too small");
+        hipStream_t st = e->stream;
+        DevBuf<float> d_in;
+        d_in.alloc(n);
+        HIPCHK(hipMemcpyAsync(d_in.get(), pcm16k, n * sizeof(float), hipMemcpyHostToDevice, st));
+        SilenceWork w;
+        w.begin(st, g.Nf, g.windows, threshold_db, hang_frames, 0);
+        w.queue_file(st, d_in.get(), n, g.Nf, 0, g.windows, 0, g);
+        w.finish(st);
+        std::vector<int> act;
+        if (frame_loud) HIPCHK(hipMemcpyAsync(frame_loud, w.loud.get(), g.Nf, hipMemcpyDeviceToHost, st));
+        if (frame_kept) HIPCHK(hipMemcpyAsync(frame_kept, w.kept.get(), g.Nf, hipMemcpyDeviceToHost, st));
+        if (window_place) HIPCHK(hipMemcpyAsync(window_place, w.place.get(), g.windows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (window_active) { act.resize(g.windows); HIPCHK(hipMemcpyAsync(act.data(), w.active.get(), g.windows * sizeof(int), hipMemcpyDeviceToHost, st)); }
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        if (window_active) for (size_t i = 0; i < g.windows; i++) window_active[i] = (uint8_t)(act[i] != 0);
+        silence_gate_report(e, w);
         return RVC_OK;
     });
 }

@@ -14,13 +14,11 @@
 #include "convert_many_geometry.h"
 #include "stitch.hip.h"
 #include "highpass.hip.h"
+#include "silence.hip.h"
 
 namespace rvc {
 
-struct ManyTables {
-    const int *P; const long long *sig_off, *sig_n, *out_off, *out_n;
-    int n_files;
-};
+// (ManyTables, the device tables of a call, and ManyDeviceTables, their upload: silence.hip.h, whose gated kernels read the same tables)
 
 // the plan's batch input [S][n]: stream s gets global window g0 + s = window w of file f, samples [160 (w H - C), + n) of THAT file, zero outside [0, N_f)
 // -- a sample of the neighbour file in the arena is never read; streams at or beyond nw (the padding of the call's last batch) get zeros
@@ -96,23 +94,6 @@ static void launch_stitch_many(hipStream_t st, const float *y, long long y_bs, i
                        (const float *)tails, (const int *)offsets, out);
 }
 
-// the tables of a call on the device: the four per-file arrays in one allocation and the window prefix sums, copied before upload() returns
-struct ManyDeviceTables {
-    DevBuf<long long> ll; DevBuf<int> P;
-    ManyTables t{};
-    void upload(const std::vector<int> &Pv, const std::vector<long long> &sig_off, const std::vector<long long> &sig_n, const std::vector<long long> &out_off,
-                const std::vector<long long> &out_n)
-    {
-        const size_t F = Pv.size() - 1;
-        std::vector<long long> host(4 * F);
-        for (size_t f = 0; f < F; f++) { host[f] = sig_off[f]; host[F + f] = sig_n[f]; host[2 * F + f] = out_off[f]; host[3 * F + f] = out_n[f]; }
-        ll.alloc(4 * F); P.alloc(F + 1);
-        HIPCHK(hipMemcpy(ll.get(), host.data(), 4 * F * sizeof(long long), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(P.get(), Pv.data(), (F + 1) * sizeof(int), hipMemcpyHostToDevice));
-        t = ManyTables{P.get(), ll.get(), ll.get() + F, ll.get() + 2 * F, ll.get() + 3 * F, (int)F};
-    }
-};
-
 // statuses and arguments of rvc_convert_many, in the order the header documents; fills the packing and out_len[]
 static rvc_status convert_many_check(rvc_engine *e, const float *const *pcm, const size_t *n, size_t n_files, size_t k, size_t context, size_t crossfade, float *const *out,
                                      const size_t *cap, size_t *out_len, ConvertManyGeometry *m)
@@ -136,7 +117,9 @@ static rvc_status convert_many_run(rvc_engine *e, const float *const *pcm, const
 {
     hipStream_t st = e->stream;
     const ConvertGeometry &g = m.g;
-    const size_t F = m.files(), S = (size_t)e->n_streams, W = m.windows_total(), batches = m.batches(S);
+    const size_t F = m.files(), S = (size_t)e->n_streams, W = m.windows_total();
+    size_t batches = m.batches(S);
+    const bool gated = silence_gate_on(e);
     const size_t sola_len = g.X * g.zc, search = g.Q * g.zc, frame = g.H * g.zc, ylen = g.return_length * g.zc;
     e->conv.valid = false; e->conv_f0_valid = false; e->many.valid = false;
     HIPCHK(hipDeviceSynchronize());
@@ -163,25 +146,49 @@ static rvc_status convert_many_run(rvc_engine *e, const float *const *pcm, const
         t_hp.stop(st);
         sig = filtered.get();
     }
+    // the silence gate (silence.hip.h): every file measured on its own, the active windows of all files compacted in global window order
+    SilenceWork gate;
+    if (gated) {
+        size_t frames = 0;
+        for (size_t f = 0; f < F; f++) frames += m.out_samples[f] / g.zc;
+        gate.begin(st, frames, W, e->sil_db, e->sil_hang, ylen);
+        size_t at = 0;
+        for (size_t f = 0; f < F; f++) {
+            const size_t Nf = m.out_samples[f] / g.zc;
+            gate.queue_file(st, sig + m.sig_off[f], m.n[f], Nf, at, m.windows[f], (size_t)m.P[f], g);
+            at += Nf;
+        }
+        gate.finish(st);
+        batches = gate.batches(S);
+    }
     DevBuf<float> win, y, tails; DevBuf<int> offs;
     win.alloc(S * g.n + 64); y.alloc(S * ylen + 64); tails.alloc((W + 1) * sola_len); offs.alloc(W);
     HIPCHK(hipMemsetAsync(win.get(), 0, (S * g.n + 64) * sizeof(float), st));
     HIPCHK(hipMemsetAsync(tails.get(), 0, sola_len * sizeof(float), st));       // row 0: every file's stitch starts from silence
     std::vector<DevEvent> ev(3 * batches);
     for (size_t b = 0; b < batches; b++) {
-        const size_t g0 = b * S; const int nw = (int)std::min(S, W - g0);
+        // (gated: g0 is the batch's first PLACE and nw its active windows, of the A in all)
+        const size_t g0 = b * S; const int nw = (int)std::min(S, (gated ? gate.A : W) - g0);
         int f_first = 0, f_last = 0;
-        m.batch_files(b, S, &f_first, &f_last);
+        if (!gated) m.batch_files(b, S, &f_first, &f_last);
         ev[3 * b].record(st);
-        hipLaunchKernelGGL(window_gather_many_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, tabs.t, win.get(), (int)g.n, (int)g0, nw, (int)g.H,
+        if (gated) gate.gather(st, sig, tabs.t, win.get(), S, g0, g);
+        else hipLaunchKernelGGL(window_gather_many_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, tabs.t, win.get(), (int)g.n, (int)g0, nw, (int)g.H,
                            (int)g.C);
         size_t got = 0;
         const rvc_status rc = infer_common(e, win.get(), true, g.n, g.sf, pitch_shift, (uint32_t)g.skip_head, (uint32_t)g.return_length, y.get(), true, ylen, &got, true);
         if (rc != RVC_OK) { (void)hipStreamSynchronize(st); return rc; }
         if (got != ylen) throw ShapeError("convert_many: the synthesizer does not produce sample_rate / 100 samples per frame");
         ev[3 * b + 1].record(st);
-        launch_stitch_many(st, y.get(), (long long)ylen, (int)g0, nw, f_first, f_last, tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out.get());
+        if (gated) gate.stitch(st, y.get(), (long long)ylen, g0, nw, tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out.get());
+        else launch_stitch_many(st, y.get(), (long long)ylen, (int)g0, nw, f_first, f_last, tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out.get());
         ev[3 * b + 2].record(st);
+    }
+    DevTimer t_zero;      // a gated call without an active window: no batch ran; the stitch walks zeros, as in convert_run
+    if (gated && batches == 0) {
+        t_zero.start(st);
+        gate.stitch(st, y.get(), (long long)ylen, 0, 0, tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out.get());
+        t_zero.stop(st);
     }
     t_total.stop(st);
     // 5. the outputs come down once, per file
@@ -196,6 +203,8 @@ static rvc_status convert_many_run(rvc_engine *e, const float *const *pcm, const
         HIPCHK(hipEventElapsedTime(&a, ev[3 * b].get(), ev[3 * b + 1].get())); HIPCHK(hipEventElapsedTime(&c, ev[3 * b + 1].get(), ev[3 * b + 2].get()));
         ms_model += a; ms_stitch += c;
     }
+    if (gated && batches == 0) ms_stitch = (double)t_zero.ms();
+    if (gated) silence_gate_report(e, gate);
     e->many.windows = W; e->many.batches = batches;
     e->many.ms[0] = highpass ? (double)t_hp.ms() : 0.0; e->many.ms[1] = ms_model; e->many.ms[2] = ms_stitch; e->many.ms[3] = (double)t_total.ms();
     e->many.valid = true;

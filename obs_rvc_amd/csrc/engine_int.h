@@ -641,6 +641,10 @@ struct rvc_engine {
     double at_target = 0.0; int at_step = 1; double at_limit = 12.0;
     float auto_mul = 0.f;
     struct AutoInfo { bool valid = false; float median = 0.f; size_t voiced = 0; double semitones = 0.0; double ms[2] = {0, 0}; } at_info;
+    // the file converter's silence gate (silence.hip.h).  sil_db / sil_hang: rvc_set_convert_silence (at or below -60 dB = off), kept over
+    // model loads.  sil_info: what rvc_convert_silence_info reports of the last completed call that ran with the gate
+    double sil_db = -60.0; int sil_hang = 30;
+    struct SilenceInfo { bool valid = false; size_t run = 0, skipped = 0, loud = 0, kept = 0; double ms = 0.0; } sil_info;
     int *h_status = nullptr;        // pinned, one word per stream (up to 4096)
     bool status_queued = false;     // an async copy of the status words is already in the stream in front of the caller's sync
 };

@@ -33,20 +33,29 @@ static int analyze_cg(const ConvertGeometry &g)
 }
 
 // The analysis proper, device to device: sig [n] at 16 kHz -> grid [g.Nf].  Begins with what rvc_reset_state does and leaves the state that way (a pitch-only
-// plan writes neither the cache nor the chunk counter); returns synchronised, the streams' status words checked
-static rvc_status analyze_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, float *grid)
+// plan writes neither the cache nor the chunk counter); returns synchronised, the streams' status words checked.  gate (the silence gate's analysis of sig,
+// DESIGN.md section 30): only its active windows run, compacted; the caller has zeroed the grid, which keeps 0 in the rows of skipped windows
+static rvc_status analyze_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, float *grid, const SilenceGate *gate = nullptr)
 {
     hipStream_t st = e->stream;
-    const size_t S = (size_t)e->n_streams, W = g.windows, batches = (W + S - 1) / S;
+    const size_t S = (size_t)e->n_streams, W = g.windows, batches = gate ? gate->work.batches(S) : (W + S - 1) / S;
     const int Cg = analyze_cg(g);
     HIPCHK(hipDeviceSynchronize());
     reset_state(e);
+    if (gate && gate->work.A == 0) { HIPCHK(hipStreamSynchronize(st)); return RVC_OK; }      // (nothing to run: no plan is built, the zeroed grid is the result)
     Plan *pl = get_plan(e, plan_key(e, 2, g.n, g.sf, 0, 0));
     if (pl->key.B != (int)S || !pl->d_f0 || (size_t)Cg + g.H > (size_t)pl->Tm) throw ShapeError("analyze_f0: a window's hop lies outside its f0 rows");
     pl->cur_in = nullptr; pl->cur_out = nullptr;
     push_call_params(e, 0, nullptr, nullptr, true);
     for (size_t b = 0; b < batches; b++) {
-        const size_t w0 = b * S; const int nw = (int)std::min(S, W - w0);
+        const size_t w0 = b * S;
+        if (gate) {      // (w0: the batch's first place)
+            gate->work.gather(st, sig, gate->tabs.t, pl->d_in, S, w0, g);
+            run_plan(e, *pl);
+            gate->work.export_f0(st, pl->d_f0, pl->Tm, S, w0, (int)g.H, Cg, grid, (long long)g.Nf);
+            continue;
+        }
+        const int nw = (int)std::min(S, W - w0);
         launch_window_gather(st, sig, (long long)n, pl->d_in, (int)g.n, (int)S, (long long)w0, nw, (int)g.H, (int)g.C);
         run_plan(e, *pl);
         launch_f0_export(st, pl->d_f0, pl->Tm, (int)w0, nw, (int)g.H, Cg, grid, (long long)g.Nf);
@@ -92,7 +101,7 @@ static double auto_transpose_semitones(double target, double median, size_t voic
 // In front of a conversion's first batch (convert_run; a target is set and the model has pitch guidance): the analysis of the signal the model will see, the curve
 // merged in when one is in force (curve_grid: its grid, or null), the lower median, the transpose.  -> the factor every stream's multiplier takes for the rest of
 // the call, 0 = none.  Ends with the engine in the reset state the conversion starts from
-static rvc_status auto_transpose_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, const float *curve_grid, float *mul)
+static rvc_status auto_transpose_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, const float *curve_grid, float *mul, const SilenceGate *gate)
 {
     hipStream_t st = e->stream;
     *mul = 0.f;
@@ -102,7 +111,7 @@ static rvc_status auto_transpose_run(rvc_engine *e, const float *sig, size_t n, 
     DevTimer t_an, t_sel;
     HIPCHK(hipMemsetAsync(grid.get(), 0, g.Nf * sizeof(float), st));
     t_an.start(st);
-    const rvc_status rc = analyze_run(e, sig, n, g, grid.get());
+    const rvc_status rc = analyze_run(e, sig, n, g, grid.get(), gate);
     if (rc != RVC_OK) return rc;
     t_an.stop(st);
     t_sel.start(st);
@@ -142,7 +151,13 @@ rvc_status rvc_analyze_f0_device(rvc_engine *e, const void *d_pcm16k, size_t n, 
             launch_highpass(e, sig, n, filtered.get());
             sig = filtered.get();
         }
-        return analyze_run(e, sig, n, g, (float *)d_hz);
+        if (!silence_gate_on(e)) return analyze_run(e, sig, n, g, (float *)d_hz);
+        SilenceGate gate;
+        silence_gate_run(e, sig, n, g, 0, &gate);
+        HIPCHK(hipMemsetAsync(d_hz, 0, g.Nf * sizeof(float), e->stream));
+        const rvc_status rc = analyze_run(e, sig, n, g, (float *)d_hz, &gate);
+        if (rc == RVC_OK) silence_gate_report(e, gate.work);
+        return rc;
     });
 }
 

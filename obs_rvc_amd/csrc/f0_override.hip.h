@@ -54,7 +54,7 @@ static __global__ __launch_bounds__(256) void f0_override_kernel(const float *__
     float o = __builtin_nanf("");
     if (c.mode == 1) {
         if (s < c.nw) {
-            const long long g = (long long)(c.w0 + s) * c.H - c.C + tt;
+            const long long g = (long long)(c.list ? c.list[c.w0 + s] : c.w0 + s) * c.H - c.C + tt;
             if (g >= 0 && g < c.Nf) o = c.grid[g];
         }
     } else {

@@ -816,6 +816,42 @@ class RvcInfer:
         self._chk(self._L.rvc_auto_transpose_info(self._h, C.byref(m), C.byref(v), C.byref(a), ms))
         return {"median_hz": np.float32(m.value), "voiced": int(v.value), "semitones": a.value, "ms_analysis": ms[0], "ms_select": ms[1]}
 
+    # -- the file converter's silence gate (rvc_set_convert_silence, rvc_silence_map) --
+    def set_convert_silence(self, threshold_db: float, hang_frames: int = 30):
+        """rvc_set_convert_silence: convert(), convert_file(), convert_many(), analyze_f0() and the auto-transpose analysis skip the windows in which no 10 ms frame
+        within hang_frames of their returned frames reaches threshold_db (the session gate's measure: 40 ms RMS in dB).  threshold_db <= -60 = off (the
+        default).  A skipped window is exact zeros in the stitch and 0 in the f0 rows; the windows that run are compacted into full batches."""
+        self._chk(self._L.rvc_set_convert_silence(self._h, float(threshold_db), int(hang_frames)))
+
+    def convert_silence(self) -> dict:
+        t, h = C.c_double(), C.c_int()
+        self._chk(self._L.rvc_convert_silence(self._h, C.byref(t), C.byref(h)))
+        return {"threshold_db": t.value, "hang_frames": h.value, "on": t.value > -60.0}
+
+    def convert_silence_info(self) -> dict:
+        """of the last completed call that ran with the gate -> {windows_run, windows_skipped, frames_loud, frames_kept, ms_analysis}"""
+        v = [C.c_size_t() for _ in range(4)]
+        ms = C.c_double()
+        self._chk(self._L.rvc_convert_silence_info(self._h, *[C.byref(x) for x in v], C.byref(ms)))
+        d = dict(zip(("windows_run", "windows_skipped", "frames_loud", "frames_kept"), (int(x.value) for x in v)))
+        d["ms_analysis"] = ms.value
+        return d
+
+    def silence_map(self, x, threshold_db: float, hang_frames: int = 30, k: int = 0, context: int = 0, crossfade: int = 0, sample_rate: int = 16000) -> dict:
+        """rvc_silence_map: the gate's analysis of a 16 kHz recording alone (no model needed) -> {loud, kept (bool per 10 ms frame), active (bool per window),
+        place (int32 per window: its rank among the active windows, -1 = skipped)}"""
+        s, sp = _f32(x)
+        if s.ndim != 1:
+            raise RvcInferError(5, "silence_map: a recording is a 1-D array")
+        geo = self.convert_geometry(len(s), int(sample_rate), int(k), int(context), int(crossfade))
+        nf, w = geo["output_samples"] // (int(sample_rate) // 100), geo["windows"]
+        loud, kept, act = np.zeros(nf, np.uint8), np.zeros(nf, np.uint8), np.zeros(w, np.uint8)
+        place = np.zeros(w, np.int32)
+        u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._chk(self._L.rvc_silence_map(self._h, sp, len(s), float(threshold_db), int(hang_frames), int(k), int(context), int(crossfade), int(sample_rate),
+                                          u8(loud), u8(kept), nf, u8(act), place.ctypes.data_as(C.POINTER(C.c_int32)), w))
+        return {"loud": loud.astype(bool), "kept": kept.astype(bool), "active": act.astype(bool), "place": place}
+
     @staticmethod
     def formant_geometry(return_length: int, sample_rate: int, semitones: float):
         """-> (R2, upp_res): the decoder's frame count and the resampler's input samples per frame of a formant shift
