@@ -145,6 +145,17 @@ extern "C" {
     pub fn rvc_convert_many_info(e: *mut RvcEngine, windows_total: *mut usize, batches: *mut usize, offsets: *mut i32, cap_offsets: usize, ms: *mut f64) -> c_int;
     pub fn rvc_sola_stitch_many(e: *mut RvcEngine, windows: *const c_float, windows_per_file: *const usize, n_files: usize, window_len: usize, sola_len: usize,
                                 search: usize, frame: usize, out: *mut c_float, offsets: *mut i32) -> c_int;
+    // a pitch per recording for rvc_convert_many: the packed analysis, the segmented select, a transpose list and an auto-transpose
+    // target read by rvc_convert_many alone; declared for the header's sake
+    pub fn rvc_analyze_f0_many(e: *mut RvcEngine, pcm16k: *const *const c_float, n: *const usize, n_files: usize, k: usize, context: usize, crossfade: usize,
+                               highpass: c_int, hz: *const *mut c_float, cap: *const usize, n_frames: *mut usize) -> c_int;
+    pub fn rvc_f0_stats_many(e: *mut RvcEngine, hz: *const c_float, rows_per_file: *const usize, n_files: usize, quantile: *const c_double, nq: usize,
+                             out_hz: *mut c_float, voiced: *mut usize) -> c_int;
+    pub fn rvc_set_convert_many_pitch(e: *mut RvcEngine, semitones: *const c_double, n_files: usize) -> c_int;
+    pub fn rvc_set_convert_many_auto_transpose(e: *mut RvcEngine, target_hz: c_double, step: c_int, limit: c_double) -> c_int;
+    pub fn rvc_convert_many_auto_transpose(e: *mut RvcEngine, target_hz: *mut c_double, step: *mut c_int, limit: *mut c_double) -> c_int;
+    pub fn rvc_convert_many_pitch_info(e: *mut RvcEngine, median_hz: *mut c_float, voiced: *mut usize, auto_semitones: *mut c_double,
+                                       total_semitones: *mut c_double, cap_files: usize, ms: *mut c_double) -> c_int;
     // the file converter's silence gate: threshold <= -60 dB = off, hang 0..1000 frames; declared for the header's sake
     pub fn rvc_set_convert_silence(e: *mut RvcEngine, threshold_db: c_double, hang_frames: c_int) -> c_int;
     pub fn rvc_convert_silence(e: *mut RvcEngine, threshold_db: *mut c_double, hang_frames: *mut c_int) -> c_int;

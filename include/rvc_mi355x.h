@@ -621,6 +621,42 @@ rvc_status rvc_convert_many_info(rvc_engine *e, size_t *windows_total, size_t *b
 rvc_status rvc_sola_stitch_many(rvc_engine *e, const float *windows, const size_t *windows_per_file, size_t n_files, size_t window_len, size_t sola_len,
                                 size_t search, size_t frame, float *out, int32_t *offsets);
 
+/* ---- a pitch per recording for rvc_convert_many (Applio's batch mode proposes a pitch per file) ---- */
+/* rvc_analyze_f0_many: rvc_analyze_f0 of F recordings in one call.  hz[f] takes exactly the rows rvc_analyze_f0 gives file f alone, Nf_f = ceil(N_f / 160),
+ * bit for bit; n_frames [F] (may be NULL) is written.  The windows of all files are packed as rvc_convert_many packs them -- global window order, S =
+ * rvc_set_streams per batch through ONE pitch-only plan, only the last batch padded -- all signals go up once, highpass != 0 filters each file on its own, and
+ * with the silence gate on the active windows of all files are compacted; the rows of skipped windows are 0.  The call begins and ends with what
+ * rvc_reset_state does.  Needs an f0 method only.  Statuses in rvc_convert_many's order: RVC_F0_NOT_LOADED before any argument is looked at; RVC_SHAPE with a
+ * message for F out of range, n NULL, an empty recording, a bad geometry, the totals; then n_frames is written; a short cap[f] (or cap NULL); a NULL pointer
+ * among pcm16k, hz and their entries.  Nothing is launched on a refused call. */
+rvc_status rvc_analyze_f0_many(rvc_engine *e, const float *const *pcm16k, const size_t *n, size_t n_files, size_t k, size_t context, size_t crossfade,
+                               int highpass, float *const *hz, const size_t *cap, size_t *n_frames);
+/* rvc_f0_stats_many: rvc_f0_stats of every file's rows, bit for bit, in one launch.  hz holds the files' rows end to end, rows_per_file [F] their counts;
+ * out_hz [F][nq], voiced [F] (may be NULL).  One workgroup per file runs the radix select with its histograms in LDS; only integers are summed.
+ * RVC_SHAPE: F outside [1, 65536], a file without rows, more than 2^30 rows in all, rvc_f0_stats's limits for nq and the quantiles, a NULL buffer. */
+rvc_status rvc_f0_stats_many(rvc_engine *e, const float *hz, const size_t *rows_per_file, size_t n_files, const double *quantile, size_t nq, float *out_hz,
+                             size_t *voiced);
+/* Two engine-wide settings, kept over model loads and read by rvc_convert_many ONLY (rvc_set_auto_transpose keeps its meaning, and rvc_convert_many stays
+ * refused while it is in force).  rvc_set_convert_many_pitch: one transpose per file of the next calls, each finite and in [-24, 24] semitones (else RVC_SHAPE,
+ * state unchanged); NULL or n_files = 0 clears the list.  A list whose length differs from a call's n_files makes that call RVC_SHAPE with a message; nothing is
+ * launched.  rvc_set_convert_many_auto_transpose: rvc_set_auto_transpose's arguments and checks, target_hz = 0 (the default) = off.
+ * With either on and a model with pitch guidance, rvc_convert_many runs, behind the high-pass and the silence gate and in front of its first batch, the
+ * analysis of rvc_analyze_f0_many on the signals the model will see with the call's own k, context and crossfade; takes the lower median m_f and the voiced
+ * count v_f of every file in one launch (rvc_f0_stats_many at p = 0.5) and brings them down in one copy; computes on the host in double
+ * a_f = 12 log2(target / m_f) rounded to the step (ties to even) and clamped to [-limit, limit] -- 0 with the target off or v_f = 0 -- and
+ * t_f = semitones[f] + a_f; and starts the conversion proper from the reset state.  In every batch a stream that holds a window of file f (under the silence
+ * gate: the window the compaction put there) takes the factor (float)2^(t_f / 12) behind its own rvc_set_pitch_semitones factor; t_f = 0 multiplies by
+ * nothing, padded streams take nothing.  The factor is no part of a plan's identity and is gone on every way out of the call.  So with the engine's own
+ * semitones at 0 the result is, bit for bit, rvc_convert_many's composition with rvc_set_pitch_semitones_stream(s, t_f(s)) (0 for a padded stream) in front
+ * of each rvc_infer_batch.  A model without pitch guidance skips all of it.  rvc_convert_many_info's total includes the pass.
+ * rvc_convert_many_pitch_info: of the last rvc_convert_many that ran the pass, per file (the first cap_files of them) m_f, v_f, a_f, t_f, and device
+ * ms = {analysis, select}; any pointer may be NULL; RVC_SHAPE before one has. */
+rvc_status rvc_set_convert_many_pitch(rvc_engine *e, const double *semitones, size_t n_files);
+rvc_status rvc_set_convert_many_auto_transpose(rvc_engine *e, double target_hz, int step, double limit);
+rvc_status rvc_convert_many_auto_transpose(rvc_engine *e, double *target_hz, int *step, double *limit);
+rvc_status rvc_convert_many_pitch_info(rvc_engine *e, float *median_hz, size_t *voiced, double *auto_semitones, double *total_semitones, size_t cap_files,
+                                       double ms[2]);
+
 /* ---- the file converter's silence gate (the upstream client's response threshold, slicer2's job) ---- */
 /* Off by default.  With a threshold set, rvc_convert*, rvc_convert_file* (on the resampled and filtered signal), rvc_convert_many, rvc_analyze_f0* and the
  * analysis pass of auto-transpose measure the signal the model will see and run only the windows that hold something.  In 10 ms frames of 160 samples, the

@@ -46,6 +46,8 @@ SYMBOLS = [
     "rvc_analyze_f0", "rvc_analyze_f0_device", "rvc_f0_stats", "rvc_f0_stats_stream", "rvc_set_auto_transpose", "rvc_auto_transpose", "rvc_auto_transpose_info",
     "rvc_convert_many_geometry", "rvc_convert_many", "rvc_convert_many_info", "rvc_sola_stitch_many",
     "rvc_set_convert_silence", "rvc_convert_silence", "rvc_convert_silence_info", "rvc_silence_map",
+    "rvc_analyze_f0_many", "rvc_f0_stats_many", "rvc_set_convert_many_pitch", "rvc_set_convert_many_auto_transpose", "rvc_convert_many_auto_transpose",
+    "rvc_convert_many_pitch_info",
 ]
 
 
@@ -406,6 +408,14 @@ def lib():
         L.rvc_convert_many.argtypes = [vp, C.POINTER(fp), szp, sz, sz, sz, sz, i32, C.c_int, C.POINTER(fp), szp, szp]
         L.rvc_convert_many_info.argtypes = [vp, szp, szp, C.POINTER(i32), sz, C.POINTER(C.c_double)]
         L.rvc_sola_stitch_many.argtypes = [vp, fp, szp, sz, sz, sz, sz, sz, fp, C.POINTER(i32)]
+    if hasattr(L, "rvc_analyze_f0_many") or not override:
+        szp, dp = C.POINTER(sz), C.POINTER(C.c_double)
+        L.rvc_analyze_f0_many.argtypes = [vp, C.POINTER(fp), szp, sz, sz, sz, sz, C.c_int, C.POINTER(fp), szp, szp]
+        L.rvc_f0_stats_many.argtypes = [vp, fp, szp, sz, dp, sz, fp, szp]
+        L.rvc_set_convert_many_pitch.argtypes = [vp, dp, sz]
+        L.rvc_set_convert_many_auto_transpose.argtypes = [vp, C.c_double, C.c_int, C.c_double]
+        L.rvc_convert_many_auto_transpose.argtypes = [vp, dp, C.POINTER(C.c_int), dp]
+        L.rvc_convert_many_pitch_info.argtypes = [vp, fp, szp, dp, dp, sz, dp]
     if hasattr(L, "rvc_set_convert_silence") or not override:
         szp, dp, u8p = C.POINTER(sz), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
         L.rvc_set_convert_silence.argtypes = [vp, C.c_double, C.c_int]

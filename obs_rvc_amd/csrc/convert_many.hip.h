@@ -94,6 +94,10 @@ static void launch_stitch_many(hipStream_t st, const float *y, long long y_bs, i
                        (const float *)tails, (const int *)offsets, out);
 }
 
+}  // namespace rvc
+#include "f0_analyze_many.hip.h"
+namespace rvc {
+
 // statuses and arguments of rvc_convert_many, in the order the header documents; fills the packing and out_len[]
 static rvc_status convert_many_check(rvc_engine *e, const float *const *pcm, const size_t *n, size_t n_files, size_t k, size_t context, size_t crossfade, float *const *out,
                                      const size_t *cap, size_t *out_len, ConvertManyGeometry *m)
@@ -104,6 +108,9 @@ static rvc_status convert_many_check(rvc_engine *e, const float *const *pcm, con
     if (const char *why = convert_many_geometry(n, n_files, (size_t)e->sy->sr, k, context, crossfade, m)) throw ShapeError(why);
     if (e->sy->has_f0 && e->at_target > 0.0) throw ShapeError("convert_many: auto-transpose is in force; it takes one multiplier per recording (rvc_set_auto_transpose(e, 0, ..) or rvc_convert per file)");
     if (e->sy->has_f0 && e->curve_n > 0) throw ShapeError("convert_many: an f0 curve is set; a curve belongs to one recording (rvc_set_f0_curve(e, NULL, NULL, 0) or rvc_convert)");
+    if (e->sy->has_f0 && !e->many_semitones.empty() && e->many_semitones.size() != n_files)
+        throw ShapeError("convert_many: the per-file pitch list (rvc_set_convert_many_pitch) has " + std::to_string(e->many_semitones.size()) + " entries, the call " +
+                         std::to_string(n_files) + " recordings");
     if (out_len) for (size_t f = 0; f < n_files; f++) out_len[f] = m->out_samples[f];
     for (size_t f = 0; f < n_files; f++)
         if (!cap || cap[f] < m->out_samples[f]) { e->err = "convert_many: output buffer " + std::to_string(f) + " too small"; return RVC_SHAPE; }
@@ -112,7 +119,9 @@ static rvc_status convert_many_check(rvc_engine *e, const float *const *pcm, con
     return RVC_OK;
 }
 
-// the conversion proper.  Begins with what rvc_reset_state does, as convert_run; no curve, no auto-transpose, no f0 export (refused or out of scope)
+// the conversion proper.  Begins with what rvc_reset_state does, as convert_run; no curve, no engine-wide auto-transpose, no f0 export (refused or out of scope).
+// A per-file pitch (rvc_set_convert_many_pitch / _auto_transpose) runs many_pitch_run in front of the first batch and gives every stream
+// the factor of the file whose window it holds, batch by batch; with both off nothing is queued for it
 static rvc_status convert_many_run(rvc_engine *e, const float *const *pcm, const ConvertManyGeometry &m, int32_t pitch_shift, bool highpass, float *const *out)
 {
     hipStream_t st = e->stream;
@@ -149,17 +158,17 @@ static rvc_status convert_many_run(rvc_engine *e, const float *const *pcm, const
     // the silence gate (silence.hip.h): every file measured on its own, the active windows of all files compacted in global window order
     SilenceWork gate;
     if (gated) {
-        size_t frames = 0;
-        for (size_t f = 0; f < F; f++) frames += m.out_samples[f] / g.zc;
-        gate.begin(st, frames, W, e->sil_db, e->sil_hang, ylen);
-        size_t at = 0;
-        for (size_t f = 0; f < F; f++) {
-            const size_t Nf = m.out_samples[f] / g.zc;
-            gate.queue_file(st, sig + m.sig_off[f], m.n[f], Nf, at, m.windows[f], (size_t)m.P[f], g);
-            at += Nf;
-        }
-        gate.finish(st);
+        many_gate(e, sig, m, ylen, &gate);
         batches = gate.batches(S);
+    }
+    // the per-file pitch: file_mul[f] = (float)2^(t_f / 12), 0 = none; under the gate the file of a stream is the file of the window win_of names
+    struct ManyMulGuard { rvc_engine *e; ~ManyMulGuard() { e->many_mul.clear(); } } mul_guard{e};
+    const bool per_file = e->sy->has_f0 && (!e->many_semitones.empty() || e->many_at_target > 0.0);
+    std::vector<float> file_mul; std::vector<int> win_of;
+    if (per_file) {
+        const rvc_status rc = many_pitch_run(e, sig, m, tabs.t, gated ? &gate : nullptr, &file_mul);
+        if (rc != RVC_OK) { (void)hipStreamSynchronize(st); return rc; }
+        if (gated && gate.A) { win_of.resize(gate.A); HIPCHK(hipMemcpy(win_of.data(), gate.win_of.get(), gate.A * sizeof(int), hipMemcpyDeviceToHost)); }
     }
     DevBuf<float> win, y, tails; DevBuf<int> offs;
     win.alloc(S * g.n + 64); y.alloc(S * ylen + 64); tails.alloc((W + 1) * sola_len); offs.alloc(W);
@@ -175,6 +184,10 @@ static rvc_status convert_many_run(rvc_engine *e, const float *const *pcm, const
         if (gated) gate.gather(st, sig, tabs.t, win.get(), S, g0, g);
         else hipLaunchKernelGGL(window_gather_many_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, tabs.t, win.get(), (int)g.n, (int)g0, nw, (int)g.H,
                            (int)g.C);
+        if (per_file) {
+            e->many_mul.assign(S, 0.f);
+            for (int s = 0; s < nw; s++) e->many_mul[s] = file_mul[many_file_of(m.P.data(), (int)F, gated ? win_of[g0 + s] : (int)(g0 + s))];
+        }
         size_t got = 0;
         const rvc_status rc = infer_common(e, win.get(), true, g.n, g.sf, pitch_shift, (uint32_t)g.skip_head, (uint32_t)g.return_length, y.get(), true, ylen, &got, true);
         if (rc != RVC_OK) { (void)hipStreamSynchronize(st); return rc; }
@@ -251,6 +264,58 @@ rvc_status rvc_convert_many_info(rvc_engine *e, size_t *windows_total, size_t *b
         if (batches) *batches = e->many.batches;
         if (offsets) for (size_t i = 0; i < std::min(cap_offsets, e->many.offsets.size()); i++) offsets[i] = e->many.offsets[i];
         if (ms) for (int i = 0; i < 4; i++) ms[i] = e->many.ms[i];
+        return RVC_OK;
+    });
+}
+
+// the per-file pitch of rvc_convert_many: engine-wide, kept over model loads, read by rvc_convert_many alone.  A refused call changes nothing
+rvc_status rvc_set_convert_many_pitch(rvc_engine *e, const double *semitones, size_t n_files)
+{
+    return guarded(e, [&]() {
+        if (!semitones || n_files == 0) { e->many_semitones.clear(); return RVC_OK; }
+        if (n_files > CONVERT_MANY_MAX_FILES) throw ShapeError("convert_many pitch: more than 65536 entries");
+        for (size_t f = 0; f < n_files; f++)
+            if (!(semitones[f] >= -24.0 && semitones[f] <= 24.0)) throw ShapeError("convert_many pitch: entry " + std::to_string(f) + " is outside [-24, 24] semitones");
+        e->many_semitones.assign(semitones, semitones + n_files);
+        return RVC_OK;
+    });
+}
+
+rvc_status rvc_set_convert_many_auto_transpose(rvc_engine *e, double target_hz, int step, double limit)
+{
+    return guarded(e, [&]() {      // (rvc_set_auto_transpose's checks)
+        if (!(target_hz >= 0.0 && target_hz <= 20000.0)) throw ShapeError("auto transpose: the target is 0 (off) or in (0, 20000] Hz");
+        if (step != 0 && step != 1 && step != 12) throw ShapeError("auto transpose: the step is 0 (exact), 1 (semitones) or 12 (octaves)");
+        if (!(limit >= 0.0 && limit <= 24.0)) throw ShapeError("auto transpose: the limit is in [0, 24] semitones");
+        e->many_at_target = target_hz; e->many_at_step = step; e->many_at_limit = limit;
+        return RVC_OK;
+    });
+}
+
+rvc_status rvc_convert_many_auto_transpose(rvc_engine *e, double *target_hz, int *step, double *limit)
+{
+    return guarded(e, [&]() {
+        if (target_hz) *target_hz = e->many_at_target;
+        if (step) *step = e->many_at_step;
+        if (limit) *limit = e->many_at_limit;
+        return RVC_OK;
+    });
+}
+
+// of the last rvc_convert_many that ran the per-file pitch pass, per file (the first cap_files of them): the lower median, the voiced rows, a_f, t_f; device
+// ms = {analysis, select}; any pointer may be NULL
+rvc_status rvc_convert_many_pitch_info(rvc_engine *e, float *median_hz, size_t *voiced, double *auto_semitones, double *total_semitones, size_t cap_files, double ms[2])
+{
+    return guarded(e, [&]() {
+        const rvc_engine::ManyPitchInfo &pi = e->many_pitch;
+        if (!pi.valid) throw ShapeError("convert_many_pitch_info: no convert_many has run the per-file pitch pass on this engine");
+        for (size_t f = 0; f < std::min(cap_files, pi.median.size()); f++) {
+            if (median_hz) median_hz[f] = pi.median[f];
+            if (voiced) voiced[f] = pi.voiced[f];
+            if (auto_semitones) auto_semitones[f] = pi.a[f];
+            if (total_semitones) total_semitones[f] = pi.t[f];
+        }
+        if (ms) { ms[0] = pi.ms[0]; ms[1] = pi.ms[1]; }
         return RVC_OK;
     });
 }

@@ -35,6 +35,16 @@ static inline RVC_MANY_HD int many_file_of(const int *P, int n_files, int g)
     return lo;
 }
 
+// The f0 rows of many recordings: file f has Nf_f rows on its 10 ms grid, the grids lie end to end in one arena, goff [n_files + 1]
+// their prefix sums.  Hop row h (0 <= h < H) of global window g = window w of file f is row w H + h of that file: -> its place in the arena, or -1 for a row
+// at or beyond Nf_f (the file's last, partial hop: nothing lands in the next file's region)
+static inline RVC_MANY_HD long long many_grid_row(const int *P, const long long *goff, int n_files, int g, int h, int H)
+{
+    const int f = many_file_of(P, n_files, g);
+    const long long row = (long long)(g - P[f]) * H + h;
+    return row < goff[f + 1] - goff[f] ? goff[f] + row : -1;
+}
+
 // the packing of a call.  g: the shared window geometry (its Nf / windows / out_samples are file 0's and not used).  Per file: samples, windows, output
 // samples; the prefix sums P (windows), sig_off (input samples) and out_off (output samples), each [n_files + 1]
 struct ConvertManyGeometry {
@@ -47,6 +57,13 @@ struct ConvertManyGeometry {
     size_t out_total() const { return (size_t)out_off.back(); }
     size_t sig_total() const { return (size_t)sig_off.back(); }
     size_t batches(size_t S) const { return (windows_total() + S - 1) / S; }
+    // the f0 grid arena of the call: prefix sums [n_files + 1] of Nf_f = out_samples[f] / zc
+    std::vector<long long> grid_off() const
+    {
+        std::vector<long long> o(files() + 1, 0);
+        for (size_t f = 0; f < files(); f++) o[f + 1] = o[f] + (long long)(out_samples[f] / g.zc);
+        return o;
+    }
     // the files batch i of S streams touches: [first, last], a contiguous range
     void batch_files(size_t i, size_t S, int *first, int *last) const
     {

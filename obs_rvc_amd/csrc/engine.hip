@@ -675,7 +675,8 @@ static float uppower(int32_t pitch_shift) { return ldexpf(1.0f, pitch_shift / 12
 // (st = 0 multiplies by nothing).  The formant descriptor is made for Rs; without Rs (hubert / pitch) the descriptors stay what the device holds.
 // neutral (rvc_analyze_f0): the multiplier is 1 and every pitch control is off whatever the streams' settings say -- the tracker's own rows come out of the tail;
 // the settings themselves are not touched, and the next call pushes them again because the block it compares against differs.
-// rvc_engine::auto_mul (a conversion under auto-transpose): one more factor behind the semitone factor
+// rvc_engine::auto_mul (a conversion under auto-transpose): one more factor behind the semitone factor; rvc_engine::many_mul (rvc_convert_many with a per-file
+// pitch): the same, per stream
 static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *shifts = nullptr, const uint32_t *Rs = nullptr, bool neutral = false)
 {
     const int B = e->n_streams;
@@ -692,6 +693,7 @@ static void push_call_params(rvc_engine *e, int32_t pitch_shift, const int32_t *
         if (neutral) { c.c = f0cond_pack(0.f, INFINITY, 0, 0u, 0.f); c.protect = (float)set.protect; continue; }
         if (set.pitch.semitones != 0.0) c.uppower *= (float)std::pow(2.0, set.pitch.semitones / 12.0);
         if (e->auto_mul != 0.f) c.uppower *= e->auto_mul;
+        if ((size_t)b < e->many_mul.size() && e->many_mul[b] != 0.f) c.uppower *= e->many_mul[b];
         c.c = f0cond_pack(set.pitch.lo, set.pitch.hi, set.pitch.radius, set.pitch.mask, set.pitch.strength);
         c.protect = (float)set.protect;
     }

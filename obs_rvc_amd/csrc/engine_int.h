@@ -641,6 +641,14 @@ struct rvc_engine {
     double at_target = 0.0; int at_step = 1; double at_limit = 12.0;
     float auto_mul = 0.f;
     struct AutoInfo { bool valid = false; float median = 0.f; size_t voiced = 0; double semitones = 0.0; double ms[2] = {0, 0}; } at_info;
+    // per-file pitch of rvc_convert_many (f0_analyze_many.hip.h), read by rvc_convert_many alone and kept over model loads.
+    // many_semitones: rvc_set_convert_many_pitch, one entry per file of the next call (empty = cleared); many_at_*: rvc_set_convert_many_auto_transpose
+    // (target 0 = off).  many_mul: auto_mul per stream -- inside convert_many_run the factor (float)2^(t_f / 12) of the file whose window the stream holds in
+    // the batch at hand, 0 = none, empty outside the call.  many_pitch: what rvc_convert_many_pitch_info reports of the last call that ran the pass
+    std::vector<double> many_semitones;
+    double many_at_target = 0.0; int many_at_step = 1; double many_at_limit = 12.0;
+    std::vector<float> many_mul;
+    struct ManyPitchInfo { bool valid = false; std::vector<float> median; std::vector<size_t> voiced; std::vector<double> a, t; double ms[2] = {0, 0}; } many_pitch;
     // the file converter's silence gate (silence.hip.h).  sil_db / sil_hang: rvc_set_convert_silence (at or below -60 dB = off), kept over
     // model loads.  sil_info: what rvc_convert_silence_info reports of the last completed call that ran with the gate
     double sil_db = -60.0; int sil_hang = 30;

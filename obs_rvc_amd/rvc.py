@@ -559,7 +559,8 @@ class RvcInfer:
     def convert_many(self, signals, k: int = 0, context: int = 0, crossfade: int = 0, pitch_shift: int = 0, highpass: bool = True):
         """rvc_convert_many: a list of 16 kHz recordings -> a list of arrays at the model's rate, one per recording in the order given.  One geometry and one set
         of settings for all; the windows of all recordings are laid end to end and run n_streams at a time, so short recordings share batches.  The call
-        starts from reset_state().  Refused while auto-transpose is in force or an f0 curve is set."""
+        starts from reset_state().  Refused while auto-transpose is in force or an f0 curve is set; a pitch per recording: set_convert_many_pitch /
+        set_convert_many_auto_transpose."""
         xs = [np.ascontiguousarray(x, np.float32) for x in signals]
         if any(x.ndim != 1 for x in xs):
             raise RvcInferError(5, "convert_many: a recording is a 1-D array")
@@ -576,6 +577,7 @@ class RvcInfer:
         pout = (_FP * F)(*[o.ctypes.data_as(_FP) for o in outs])
         cap = (C.c_size_t * F)(*[len(o) for o in outs])
         self._chk(self._L.rvc_convert_many(self._h, pin, n, F, *a, pout, cap, lens))
+        self._many_n = F      # (how many files convert_many_pitch_info reads by default)
         return outs
 
     def convert_many_info(self) -> dict:
@@ -587,6 +589,64 @@ class RvcInfer:
         off = np.empty(w.value, np.int32)
         self._chk(self._L.rvc_convert_many_info(self._h, None, None, off.ctypes.data_as(C.POINTER(C.c_int32)), len(off), None))
         return {"windows": w.value, "batches": b.value, "offsets": off, "ms_highpass": ms[0], "ms_model": ms[1], "ms_stitch": ms[2], "ms_total": ms[3]}
+
+    # -- a pitch per recording for convert_many -----------------------------
+    def analyze_f0_many(self, signals, window: int = 0, context: int = 0, crossfade: int = 0, highpass: bool = True) -> list:
+        """rvc_analyze_f0_many: analyze_f0 of every recording of a list in one call -- the windows of all of them share batches, as convert_many's -> a list of
+        float32 arrays, one per recording, each what analyze_f0 gives that recording alone"""
+        xs = [np.ascontiguousarray(x, np.float32) for x in signals]
+        if any(x.ndim != 1 for x in xs):
+            raise RvcInferError(5, "analyze_f0_many: a recording is a 1-D array")
+        F = len(xs)
+        outs = [np.empty(-(-len(x) // 160), np.float32) for x in xs]
+        pin = (_FP * max(F, 1))(*[x.ctypes.data_as(_FP) for x in xs])
+        pout = (_FP * max(F, 1))(*[o.ctypes.data_as(_FP) for o in outs])
+        n = (C.c_size_t * max(F, 1))(*[len(x) for x in xs])
+        cap = (C.c_size_t * max(F, 1))(*[len(o) for o in outs])
+        rows = (C.c_size_t * max(F, 1))()
+        self._chk(self._L.rvc_analyze_f0_many(self._h, pin, n, F, int(window), int(context), int(crossfade), 1 if highpass else 0, pout, cap, rows))
+        return [o[: rows[f]] for f, o in enumerate(outs)]
+
+    def f0_stats_many(self, rows_list, quantiles=(0.5,)):
+        """rvc_f0_stats_many: f0_stats of every array of a list in one launch -> (float32 array (files, quantiles), list of voiced counts)"""
+        xs = [np.ascontiguousarray(x, np.float32) for x in rows_list]
+        if any(x.ndim != 1 for x in xs):
+            raise RvcInferError(5, "f0_stats_many: one-dimensional arrays of Hz")
+        q = self._quantiles(quantiles)
+        F = len(xs)
+        hz = np.ascontiguousarray(np.concatenate(xs) if F else np.zeros(0, np.float32))
+        rows = (C.c_size_t * max(F, 1))(*[len(x) for x in xs])
+        out, v = np.zeros((F, len(q)), np.float32), (C.c_size_t * max(F, 1))()
+        self._chk(self._L.rvc_f0_stats_many(self._h, hz.ctypes.data_as(_FP), rows, F, q.ctypes.data_as(C.POINTER(C.c_double)), len(q), out.ctypes.data_as(_FP), v))
+        return out, [int(v[f]) for f in range(F)]
+
+    def set_convert_many_pitch(self, semitones=None):
+        """rvc_set_convert_many_pitch: one transpose in semitones (-24..24) per recording of the next convert_many calls; None or an empty list clears it"""
+        st = [] if semitones is None else [float(v) for v in semitones]
+        arr = (C.c_double * max(len(st), 1))(*st)
+        self._chk(self._L.rvc_set_convert_many_pitch(self._h, arr if st else None, len(st)))
+
+    def set_convert_many_auto_transpose(self, target_hz: float, step: int = 0, limit: float = 12.0):
+        """rvc_set_convert_many_auto_transpose: convert_many measures the median f0 of EVERY recording and transposes each onto target_hz (0 = off); step and
+        limit as set_auto_transpose's.  Composes with set_convert_many_pitch; set_auto_transpose keeps its meaning (one recording) and stays refused by
+        convert_many"""
+        self._chk(self._L.rvc_set_convert_many_auto_transpose(self._h, float(target_hz), int(step), float(limit)))
+
+    def convert_many_auto_transpose(self) -> dict:
+        t, s, l = C.c_double(), C.c_int(), C.c_double()
+        self._chk(self._L.rvc_convert_many_auto_transpose(self._h, C.byref(t), C.byref(s), C.byref(l)))
+        return {"target_hz": t.value, "step": s.value, "limit": l.value}
+
+    def convert_many_pitch_info(self, files: int = None) -> dict:
+        """rvc_convert_many_pitch_info of the last convert_many that ran the per-file pitch pass -> {median_hz (float32 array), voiced (list), auto_semitones,
+        semitones (float64 arrays: a_f and t_f = list + a_f), ms_analysis, ms_select}; files: how many to read (default: those of the last convert_many)"""
+        ms = (C.c_double * 2)()
+        self._chk(self._L.rvc_convert_many_pitch_info(self._h, None, None, None, None, 0, ms))
+        F = int(files) if files is not None else getattr(self, "_many_n", 0)
+        m, v, a, t = np.zeros(F, np.float32), (C.c_size_t * max(F, 1))(), np.zeros(F, np.float64), np.zeros(F, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.rvc_convert_many_pitch_info(self._h, m.ctypes.data_as(_FP), v, a.ctypes.data_as(dp), t.ctypes.data_as(dp), F, None))
+        return {"median_hz": m, "voiced": [int(v[f]) for f in range(F)], "auto_semitones": a, "semitones": t, "ms_analysis": ms[0], "ms_select": ms[1]}
 
     def sola_stitch_many(self, windows, windows_per_file, sola_len: int, search: int, frame: int):
         """rvc_sola_stitch_many: sola_stitch of several files at once.  windows (Wtot, window_len) holds the files' windows end to end, windows_per_file their
