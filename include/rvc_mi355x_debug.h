@@ -147,8 +147,8 @@ int rvc_debug_pm(rvc_engine *e, const float *audio, int B, int n, int frame, int
  *   op 0  select against row buffers: rows [B][Tm], ov [B][1024] (stream b's ov_n[b] rows from its entry 0 on, aligned to the END of the window), out [B][Tm]
  *   op 1  select against a conversion's grid: rows [B][Tm], ov = the grid [Nf], geo; stream b is window w0 + b (b < nw), its row t grid row (w0 + b) H - C + t
  *   op 2  f0_curve_grid_kernel: t [n_bp] seconds, ov = hz [n_bp], geo[0] = Nf, out [Nf]
- *   op 3  f0_export_kernel: rows = the window rows [B][Tm] (B = nw windows from w0 on), geo, out [Nf] -- read first, so frames the launch does not write keep
- *         the caller's value
+ *   op 3  f0_export_many_kernel, the f0 export of every conversion, on a one-file table as rvc_convert runs it: rows = the window rows [B][Tm] (B = nw windows
+ *         from w0 on), geo, out [Nf] -- read first, so frames the launch does not write keep the caller's value
  * B in [1, 64], Tm in [1, 1024], Nf in [1, 2^24]; everything is checked on the host before a launch. */
 int rvc_debug_f0_override(rvc_engine *e, int op, const float *rows, int B, int Tm, const float *ov, const int *ov_n, const long long *geo, const double *t, int n_bp, float *out);
 /* the caller-side post-processing, the session's ring updates and a converter of several streams (obs_rvc_amd/csrc/chunk.hip.h, session.hip.h, resample.hip.h;

@@ -1,83 +1,21 @@
-// convert.hip.h -- conversion of a whole recording (upstream's "model inference" tab, vc_single), included by engine.hip.
+// convert.hip.h -- conversion of whole recordings (DESIGN.md sections 19 and 29; upstream's "model inference" tab, vc_single and vc_multi), included by
+// convert_many.hip.h (engine.hip's unit).
 //
-// The recording is cut into windows of ONE geometry (convert_geometry.h), so one plan serves the whole file; the windows run S at a time through
-// infer_common on the engine's S streams (window w = i S + s on stream s in batch i) and are stitched by the plugin's SOLA step in its LINEAR crossfade,
-// chained over the windows on the device (stitch.hip.h).  In front of it the optional 48 Hz high-pass (highpass.hip.h).  Per batch: one gather launch,
-// one infer call with its one synchronisation, two stitch launches; the signal, S window inputs, S window outputs, the tails and the output stay in HBM.
-// f0_analyze.hip.h (included below): the same windows through the pitch-only plan -- rvc_analyze_f0 --, order statistics of f0 rows, and auto-transpose.
+// The recordings of a call are cut into windows of ONE geometry (convert_geometry.h), so one plan serves the whole call; the windows are laid end to end
+// (convert_many_geometry.h: global window g = P_f + w) and run S at a time through infer_common on the engine's S streams, so a batch may hold the windows of
+// several files and only the last batch of the CALL is padded.  They are stitched by the plugin's SOLA step in its LINEAR crossfade, one offset chain per file,
+// on the device (stitch.hip.h).  In front of it the optional 48 Hz high-pass (highpass.hip.h) and the silence gate (silence.hip.h).  Per batch: one gather
+// launch, one infer call with its one synchronisation, two stitch launches; the signals, S window inputs, S window outputs, the tails and the outputs stay in
+// HBM.  convert_windows_run is the one driver: rvc_convert* is its call of one file (convert_run), rvc_convert_many (convert_many.hip.h) its call of many.
+// f0_analyze.hip.h / f0_analyze_many.hip.h: the same windows through the pitch-only plan, order statistics of f0 rows, and the two auto-transposes.
 #pragma once
 #include "convert_geometry.h"
-#include "highpass.hip.h"
 #include "stitch.hip.h"
 #include "resample_whole.hip.h"
 #include "change_rms.hip.h"
-#include "silence.hip.h"
+#include "f0_analyze_many.hip.h"
 
 namespace rvc {
-// (what f0_analyze.hip.h uses of this file, defined below)
-static void launch_highpass(rvc_engine *e, const float *d_x, size_t n, float *d_y);
-static void launch_window_gather(hipStream_t st, const float *sig, long long N, float *dst, int n, int S, long long w0, int nw, int H, int C);
-// the silence gate of a call on one recording (silence.hip.h): the analysis of sig and the tables of a call of one file
-struct SilenceGate { SilenceWork work; ManyDeviceTables tabs; };
-static void silence_gate_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, size_t zero_len, SilenceGate *gate);
-static void silence_gate_report(rvc_engine *e, const SilenceWork &w);
-static inline bool silence_gate_on(const rvc_engine *e) { return e->sil_db > SILENCE_OFF_DB; }
-}
-#include "f0_analyze.hip.h"
-
-namespace rvc {
-
-// the plan's batch input [S][n]: stream s gets window w0 + s of the signal, samples [160 (w H - C), + n), zero outside [0, N); streams at or beyond nw
-// (the padding of a short last batch) get zeros
-static __global__ void window_gather_kernel(const float *sig, long long N, float *dst, int n, long long w0, int nw, int H, int C)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
-    if (i >= n) return;
-    float v = 0.f;
-    if (s < nw) {
-        const long long src = 160LL * ((w0 + s) * (long long)H - C) + i;
-        if (src >= 0 && src < N) v = sig[src];
-    }
-    dst[(long long)s * n + i] = v;
-}
-
-static void launch_window_gather(hipStream_t st, const float *sig, long long N, float *dst, int n, int S, long long w0, int nw, int H, int C)
-{
-    hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, N, dst, n, w0, nw, H, C);
-}
-
-static void launch_highpass(rvc_engine *e, const float *d_x, size_t n, float *d_y)
-{
-    if (!e->hp_taps) {
-        const std::vector<float> h = highpass_taps();
-        e->hp_taps.alloc(h.size());
-        HIPCHK(hipMemcpy(e->hp_taps.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (n > ((size_t)1 << 40)) throw ShapeError("highpass: signal too long");
-    hipLaunchKernelGGL(highpass_fir_kernel, dim3((unsigned)((n + HP_TILE - 1) / HP_TILE)), dim3(HP_THREADS), 0, e->stream, d_x, (long long)n, (const float *)e->hp_taps.get(), d_y);
-}
-
-// the gate's analysis of one recording with the engine's setting, queued on the engine's stream; returns behind the call's one read (synchronised)
-static void silence_gate_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, size_t zero_len, SilenceGate *gate)
-{
-    gate->work.begin(e->stream, g.Nf, g.windows, e->sil_db, e->sil_hang, zero_len);
-    silence_single_tables(&gate->tabs, n, g);
-    gate->work.queue_file(e->stream, sig, n, g.Nf, 0, g.windows, 0, g);
-    gate->work.finish(e->stream);
-}
-static void silence_gate_report(rvc_engine *e, const SilenceWork &w)
-{
-    e->sil_info.run = w.A; e->sil_info.skipped = w.W - w.A; e->sil_info.loud = w.n_loud; e->sil_info.kept = w.n_kept; e->sil_info.ms = w.ms;
-    e->sil_info.valid = true;
-}
-
-// the two stitch launches for windows [w0, w0 + nw) whose outputs lie in y [nw][y_bs]
-static void launch_stitch(hipStream_t st, const float *y, long long y_bs, int w0, int nw, int sola_len, int search, int frame, float *tails, int *offsets, float *out, long long n_out)
-{
-    hipLaunchKernelGGL(stitch_chain_kernel, dim3(1), dim3(STITCH_CHAIN_THREADS), 0, st, y, y_bs, w0, nw, sola_len, search, frame, tails, offsets);
-    hipLaunchKernelGGL(stitch_assemble_kernel, dim3((unsigned)((frame + STITCH_TILE - 1) / STITCH_TILE), (unsigned)nw), dim3(256), 0, st, y, y_bs, w0, sola_len, frame,
-                       (const float *)tails, (const int *)offsets, out, n_out);
-}
 
 // the statuses of a call that runs the models, as rvc_infer's: before any argument is looked at
 static rvc_status convert_loaded(rvc_engine *e)
@@ -109,33 +47,38 @@ static rvc_status convert_check(rvc_engine *e, const void *pcm, size_t n, size_t
     return RVC_OK;
 }
 
-// the conversion proper, device to device.  Begins with what rvc_reset_state does (pitch caches and chunk counters zeroed), so that a window's result depends
-// on the recording alone; every per-stream setting, the index, the f0 method and graph replay apply as to any infer call.  keep_filtered (rvc_convert_file): the
-// high-passed signal is handed to the caller instead of being freed
-static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const ConvertGeometry &g, int32_t pitch_shift, bool highpass, float *d_out,
-                              DevBuf<float> *keep_filtered = nullptr)
+// what a caller takes of the driver's optional parts
+struct ConvertCall {
+    const char *who;                      // the entry point's name in the refusals
+    rvc_engine::ConvertInfo *info;        // the info block the call reports to: e->conv or e->many
+    bool single;                          // one recording (rvc_convert*): the f0 curve, the engine-wide auto-transpose and the f0 export to e->conv_f0 apply;
+                                          // else (rvc_convert_many) the per-file factors do
+    DevBuf<float> *keep_filtered;         // (rvc_convert_file) the high-passed signal is handed to the caller instead of being freed; or null
+};
+
+// The conversion proper, device to device: d_sig = the signal arena of the call, tabs its tables, d_out the output arena.  Begins with what rvc_reset_state does
+// (pitch caches and chunk counters zeroed), so that a window's result depends on the recording alone; every per-stream setting, the index, the f0 method and
+// graph replay apply as to any infer call.  The callers hold the guards that take the call's settings (curve gather, auto_mul, many_mul) off the engine again
+static rvc_status convert_windows_run(rvc_engine *e, const float *d_sig, const ConvertManyGeometry &m, const ManyTables &tabs, int32_t pitch_shift, bool highpass, float *d_out,
+                                      const ConvertCall &call)
 {
     hipStream_t st = e->stream;
-    const size_t S = (size_t)e->n_streams, W = g.windows;
-    size_t batches = (W + S - 1) / S;
+    const ConvertGeometry &g = m.g;
+    const size_t F = m.files(), S = (size_t)e->n_streams, W = m.windows_total();
+    size_t batches = m.batches(S);
     const size_t sola_len = g.X * g.zc, search = g.Q * g.zc, frame = g.H * g.zc, ylen = g.return_length * g.zc;
     const bool gated = silence_gate_on(e);
-    e->conv.valid = false; e->conv_f0_valid = false;
+    e->conv.valid = false; e->conv_f0_valid = false; call.info->valid = false;
     HIPCHK(hipDeviceSynchronize());
     reset_state(e);          // (pending f0 overrides of the streams go with it: a conversion uses the curve alone)
-    // f0 from outside.  The f0 front end takes the last fr samples of a window and reflect-pads them by 512, so f0 row t of window w is
-    // centred on sample 160 (w H - C) + (n - fr) + 160 t of the recording: grid row w H - Cg + t with Cg = C - (n - fr) / 160.  (fr = n for every geometry
-    // convert_geometry makes; the check stays.)  The curve's grid is built once; each batch's plan gathers from it, and the conditioned rows of each window's
-    // hop [Cg, Cg + H) go back onto the grid for rvc_convert_f0
-    const bool has_f0 = e->sy->has_f0;
-    const size_t fr = 5120 * ((g.sf + 799) / 5120 + 1) - 160;
-    if (has_f0 && (fr > g.n || (g.n - fr) % 160 != 0 || (g.n - fr) / 160 > g.C)) throw ShapeError("convert: the f0 rows of a window are not centred on the recording's 10 ms grid");
-    const int Cg = (int)(g.C - (g.n - fr) / 160);
-    const bool curve = has_f0 && e->curve_n > 0;
-    struct CurveGuard { rvc_engine *e; ~CurveGuard() { e->conv_curve = false; e->ov_dirty = true; } } curve_guard{e};
+    // one recording, f0 from outside: the curve's grid is built once; each batch's plan gathers from it, and the conditioned rows of each
+    // window's hop [Cg, Cg + H) go back onto the grid for rvc_convert_f0 (analyze_cg: Cg and its centring check)
+    const bool single_f0 = call.single && e->sy->has_f0;
+    const int Cg = single_f0 ? analyze_cg(g, call.who) : 0;
+    const bool curve = single_f0 && e->curve_n > 0;
     DevBuf<float> f0grid;
-    bool export_ok = has_f0;
-    if (has_f0) f0grid.alloc(g.Nf);
+    bool export_ok = single_f0;
+    if (single_f0) f0grid.alloc(g.Nf);
     if (curve) {
         e->curve_grid.alloc(g.Nf);
         launch_f0_curve_grid(st, e->curve_t.get(), e->curve_hz.get(), (int)e->curve_n, e->curve_grid.get(), (long long)g.Nf);
@@ -144,73 +87,89 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
     DevTimer t_total, t_hp;
     t_total.start(st);
     DevBuf<float> filtered;
-    const float *sig = d_pcm;
+    const float *sig = d_sig;
     if (highpass) {
-        filtered.alloc(n);
+        filtered.alloc(m.sig_total());
         t_hp.start(st);
-        launch_highpass(e, d_pcm, n, filtered.get());
+        many_highpass(e, d_sig, m, filtered.get());
         t_hp.stop(st);
         sig = filtered.get();
     }
-    // the silence gate (silence.hip.h): with a threshold set, the signal the model will see is measured first, the active windows are
-    // compacted and only they run; a skipped window enters the stitch as zeros.  Off (the default): nothing is queued here and the loop below is the ungated one
-    SilenceGate gate;
+    // the silence gate (silence.hip.h): with a threshold set, the signals the model will see are measured first, every file on its own, the
+    // active windows of all files are compacted in global window order and only they run; a skipped window enters the stitch as zeros.  Off (the default):
+    // nothing is queued here and the loop below is the ungated one
+    SilenceWork work;
+    const SilenceWork *gate = gated ? &work : nullptr;
     if (gated) {
-        silence_gate_run(e, sig, n, g, ylen, &gate);
-        batches = gate.work.batches(S);
-        if (has_f0) HIPCHK(hipMemsetAsync(f0grid.get(), 0, g.Nf * sizeof(float), st));      // (the rows of skipped windows are 0)
+        many_gate(st, sig, m, e->sil_db, e->sil_hang, ylen, &work);
+        batches = work.batches(S);
+        if (single_f0) HIPCHK(hipMemsetAsync(f0grid.get(), 0, g.Nf * sizeof(float), st));      // (the rows of skipped windows are 0)
     }
-    // auto-transpose (f0_analyze.hip.h): with a target set, the f0 of the signal the model will see is analysed first -- the call's own
-    // windows through the pitch-only plan (the gate's active ones when it is on) --, the curve merged in, and 12 log2(target / median) semitones become one more
-    // factor of every stream's multiplier until the call returns, on whatever path.  Off (the default): nothing is queued here
-    struct AutoGuard { rvc_engine *e; ~AutoGuard() { e->auto_mul = 0.f; } } auto_guard{e};
-    if (has_f0 && e->at_target > 0.0) {
+    // the pitch of the call, from the f0 of the signals the model will see -- the call's own windows through the pitch-only plan (the gate's active ones when it
+    // is on).  One recording with a target set: the curve merged in, 12 log2(target / median) semitones become one more factor of every
+    // stream's multiplier until the call returns.  Many recordings with a per-file setting (section 31): file_mul[f] = (float)2^(t_f / 12), 0 = none, and every
+    // stream takes the factor of the file whose window it holds, batch by batch; under the gate that is the file of the window win_of names.  Off (the
+    // default): nothing is queued here
+    const bool per_file = !call.single && e->sy->has_f0 && (!e->many_semitones.empty() || e->many_at_target > 0.0);
+    std::vector<float> file_mul; std::vector<int> win_of;
+    if (single_f0 && e->at_target > 0.0) {
         float mul = 0.f;
-        const rvc_status rc = auto_transpose_run(e, sig, n, g, curve ? e->curve_grid.get() : nullptr, &mul, gated ? &gate : nullptr);
-        if (rc != RVC_OK) return rc;
+        const rvc_status rc = auto_transpose_run(e, sig, m, tabs, curve ? e->curve_grid.get() : nullptr, &mul, gate);
+        if (rc != RVC_OK) { (void)hipStreamSynchronize(st); return rc; }
         e->auto_mul = mul;
+    }
+    if (per_file) {
+        const rvc_status rc = many_pitch_run(e, sig, m, tabs, gate, &file_mul);
+        if (rc != RVC_OK) { (void)hipStreamSynchronize(st); return rc; }
+        if (gated && work.A) { win_of.resize(work.A); HIPCHK(hipMemcpy(win_of.data(), work.win_of.get(), work.A * sizeof(int), hipMemcpyDeviceToHost)); }
     }
     DevBuf<float> win, y, tails; DevBuf<int> offs;
     win.alloc(S * g.n + 64); y.alloc(S * ylen + 64); tails.alloc((W + 1) * sola_len); offs.alloc(W);
     HIPCHK(hipMemsetAsync(win.get(), 0, (S * g.n + 64) * sizeof(float), st));
-    HIPCHK(hipMemsetAsync(tails.get(), 0, sola_len * sizeof(float), st));       // tails[0]: the stitch starts from silence
+    HIPCHK(hipMemsetAsync(tails.get(), 0, sola_len * sizeof(float), st));       // row 0: every file's stitch starts from silence
     std::vector<DevEvent> ev(3 * batches);
     for (size_t b = 0; b < batches; b++) {
-        // (gated: w0 is the batch's first PLACE and nw its active windows, of the A in all)
-        const size_t w0 = b * S; const int nw = (int)std::min(S, (gated ? gate.work.A : W) - w0);
+        // (gated: g0 is the batch's first PLACE and nw its active windows, of the A in all)
+        const size_t g0 = b * S; const int nw = (int)std::min(S, (gated ? work.A : W) - g0);
         ev[3 * b].record(st);
-        if (gated) gate.work.gather(st, sig, gate.tabs.t, win.get(), S, w0, g);
-        else hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, (long long)n, win.get(), (int)g.n, (long long)w0, nw,
-                           (int)g.H, (int)g.C);
+        launch_gather_windows(st, sig, tabs, win.get(), S, gate, g0, nw, g);
+        if (curve) e->conv_call = F0OvCall{e->curve_grid.get(), (long long)g.Nf, 1, (int)g0, nw, (int)g.H, Cg, 0, gated ? work.win_of.get() : nullptr};
+        if (per_file) {
+            e->many_mul.assign(S, 0.f);
+            for (int s = 0; s < nw; s++) e->many_mul[s] = file_mul[many_file_of(m.P.data(), (int)F, gated ? win_of[g0 + s] : (int)(g0 + s))];
+        }
         size_t got = 0;
-        if (curve) e->conv_call = F0OvCall{e->curve_grid.get(), (long long)g.Nf, 1, (int)w0, nw, (int)g.H, Cg, 0, gated ? gate.work.win_of.get() : nullptr};
         const rvc_status rc = infer_common(e, win.get(), true, g.n, g.sf, pitch_shift, (uint32_t)g.skip_head, (uint32_t)g.return_length, y.get(), true, ylen, &got, true);
-        if (rc != RVC_OK) return rc;
-        if (got != ylen) throw ShapeError("convert: the synthesizer does not produce sample_rate / 100 samples per frame");
+        if (rc != RVC_OK) { (void)hipStreamSynchronize(st); return rc; }
+        if (got != ylen) throw ShapeError(std::string(call.who) + ": the synthesizer does not produce sample_rate / 100 samples per frame");
         ev[3 * b + 1].record(st);
-        if (gated) gate.work.stitch(st, y.get(), (long long)ylen, w0, nw, gate.tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out);
-        else launch_stitch(st, y.get(), (long long)ylen, (int)w0, nw, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out, (long long)g.out_samples);
+        if (gated) work.stitch(st, y.get(), (long long)ylen, g0, nw, tabs, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out);
+        else {
+            int f_first = 0, f_last = 0;
+            m.batch_files(b, S, &f_first, &f_last);
+            launch_stitch_many(st, y.get(), (long long)ylen, (int)g0, nw, f_first, f_last, tabs, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out);
+        }
         ev[3 * b + 2].record(st);
         // the batch's conditioned f0 rows onto the grid, behind the timed sections: in ms[3] (total), in neither ms[1] (model) nor ms[2] (stitch).  The plan's rows
         // stay until the next batch's pitch tail, which this stream orders behind the launch
         if (export_ok) {
             const Plan *pl = e->last_plan;      // (streams in several formant buckets ran through several plans: no export then)
-            if (pl && !pl->key.bucket && pl->d_f0 && pl->key.B == (int)S && (size_t)Cg + g.H <= (size_t)pl->Tm) {
-                if (gated) gate.work.export_f0(st, pl->d_f0, pl->Tm, S, w0, (int)g.H, Cg, f0grid.get(), (long long)g.Nf);
-                else launch_f0_export(st, pl->d_f0, pl->Tm, (int)w0, nw, (int)g.H, Cg, f0grid.get(), (long long)g.Nf);
-            } else export_ok = false;
+            if (pl && !pl->key.bucket && pl->d_f0 && pl->key.B == (int)S && (size_t)Cg + g.H <= (size_t)pl->Tm)
+                launch_f0_export_many(st, pl->d_f0, pl->Tm, tabs, S, gate, g0, nw, (int)g.H, Cg, f0grid.get());
+            else export_ok = false;
         }
     }
     // a gated call without an active window: no batch ran; the stitch walks its W windows of zeros (offsets and output as rvc_sola_stitch's on zeros)
     DevTimer t_zero;
     if (gated && batches == 0) {
         t_zero.start(st);
-        gate.work.stitch(st, y.get(), (long long)ylen, 0, 0, gate.tabs.t, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out);
+        work.stitch(st, y.get(), (long long)ylen, 0, 0, tabs, (int)sola_len, (int)search, (int)frame, tails.get(), offs.get(), d_out);
         t_zero.stop(st);
     }
     t_total.stop(st);
-    e->conv.offsets.assign(W, 0);
-    HIPCHK(hipMemcpyAsync(e->conv.offsets.data(), offs.get(), W * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    rvc_engine::ConvertInfo &info = *call.info;
+    info.offsets.assign(W, 0);
+    HIPCHK(hipMemcpyAsync(info.offsets.data(), offs.get(), W * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (export_ok) { e->conv_f0.assign(g.Nf, 0.f); HIPCHK(hipMemcpyAsync(e->conv_f0.data(), f0grid.get(), g.Nf * sizeof(float), hipMemcpyDeviceToHost, st)); }
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
@@ -221,12 +180,24 @@ static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const
         ms_model += a; ms_stitch += c;
     }
     if (gated && batches == 0) ms_stitch = (double)t_zero.ms();
-    if (gated) silence_gate_report(e, gate.work);
-    e->conv.windows = W; e->conv.batches = batches;
-    e->conv.ms[0] = highpass ? (double)t_hp.ms() : 0.0; e->conv.ms[1] = ms_model; e->conv.ms[2] = ms_stitch; e->conv.ms[3] = (double)t_total.ms();
-    e->conv.valid = true; e->conv_f0_valid = export_ok;
-    if (keep_filtered) *keep_filtered = std::move(filtered);
+    if (gated) silence_gate_report(e, work);
+    info.windows = W; info.batches = batches;
+    info.ms[0] = highpass ? (double)t_hp.ms() : 0.0; info.ms[1] = ms_model; info.ms[2] = ms_stitch; info.ms[3] = (double)t_total.ms();
+    info.valid = true; e->conv_f0_valid = export_ok;
+    if (call.keep_filtered) *call.keep_filtered = std::move(filtered);
     return RVC_OK;
+}
+
+// one recording as the call of one file.  keep_filtered (rvc_convert_file): see ConvertCall
+static rvc_status convert_run(rvc_engine *e, const float *d_pcm, size_t n, const ConvertGeometry &g, int32_t pitch_shift, bool highpass, float *d_out,
+                              DevBuf<float> *keep_filtered = nullptr)
+{
+    const ConvertManyGeometry m = convert_many_single(g, n);
+    ManyDeviceTables tabs;
+    tabs.upload(m);
+    struct CurveGuard { rvc_engine *e; ~CurveGuard() { e->conv_curve = false; e->ov_dirty = true; } } curve_guard{e};
+    struct AutoGuard { rvc_engine *e; ~AutoGuard() { e->auto_mul = 0.f; } } auto_guard{e};
+    return convert_windows_run(e, d_pcm, m, tabs.t, pitch_shift, highpass, d_out, ConvertCall{"convert", &e->conv, true, keep_filtered});
 }
 
 // peak[0] = max |x[i]| as the bits of a non-negative float (peak starts as 0; unsigned order = float order there): exact, max is order-free
@@ -316,6 +287,36 @@ static rvc_status convert_file_run(rvc_engine *e, const float *d_pcm, size_t n, 
     e->file.rate_out = f.rate_out; e->file.peak = pk;
     e->file.valid = true;
     return RVC_OK;
+}
+
+// the stitch alone on host buffers, behind the entry points' checks: windows [W][window_len] laid end to end, file f holding globals [P[f], P[f + 1]) and
+// every file's tail starting as zeros -> out [W][frame], offsets [W] (may be null)
+static void sola_stitch_run(rvc_engine *e, const float *windows, const std::vector<int> &P, size_t window_len, size_t sola_len, size_t search, size_t frame, float *out,
+                            int32_t *offsets)
+{
+    const size_t F = P.size() - 1, W = (size_t)P.back();
+    std::vector<long long> zero(F + 1, 0), out_off(F), out_n(F);
+    for (size_t f = 0; f < F; f++) { out_off[f] = (long long)((size_t)P[f] * frame); out_n[f] = (long long)((size_t)(P[f + 1] - P[f]) * frame); }
+    hipStream_t st = e->stream;
+    DevBuf<float> d_y, d_tails, d_out; DevBuf<int> d_off;
+    d_y.alloc(W * window_len); d_tails.alloc((W + 1) * sola_len); d_out.alloc(W * frame); d_off.alloc(W);
+    ManyDeviceTables tabs;
+    tabs.upload(P, zero, zero, out_off, out_n, zero);
+    HIPCHK(hipMemcpyAsync(d_y.get(), windows, W * window_len * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_tails.get(), 0, sola_len * sizeof(float), st));
+    const size_t step = 4096;      // windows per pair of launches (the assembly's grid.y; at most as many files, the chain's grid.x)
+    for (size_t g0 = 0; g0 < W; g0 += step) {
+        const size_t nw = std::min(step, W - g0);
+        const int f_first = many_file_of(P.data(), (int)F, (int)g0), f_last = many_file_of(P.data(), (int)F, (int)(g0 + nw - 1));
+        launch_stitch_many(st, d_y.get() + g0 * window_len, (long long)window_len, (int)g0, (int)nw, f_first, f_last, tabs.t, (int)sola_len, (int)search, (int)frame, d_tails.get(),
+                           d_off.get(), d_out.get());
+    }
+    std::vector<int32_t> off(W);
+    HIPCHK(hipMemcpyAsync(out, d_out.get(), W * frame * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(off.data(), d_off.get(), W * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (offsets) for (size_t i = 0; i < W; i++) offsets[i] = off[i];
 }
 
 }  // namespace rvc
@@ -416,7 +417,8 @@ rvc_status rvc_convert_info(rvc_engine *e, size_t *windows, size_t *batches, int
     });
 }
 
-// the chained LINEAR rvc_sola_step over windows [n_windows][window_len], the tail starting as zeros: out [n_windows][frame], offsets [n_windows] (may be NULL)
+// the chained LINEAR rvc_sola_step over windows [n_windows][window_len], the tail starting as zeros: out [n_windows][frame], offsets [n_windows] (may be NULL).
+// The one-file call of what rvc_sola_stitch_many does (sola_stitch_run above)
 rvc_status rvc_sola_stitch(rvc_engine *e, const float *windows, size_t n_windows, size_t window_len, size_t sola_len, size_t search, size_t frame, float *out, int32_t *offsets)
 {
     return guarded(e, [&]() {
@@ -425,21 +427,7 @@ rvc_status rvc_sola_stitch(rvc_engine *e, const float *windows, size_t n_windows
         if (search > 1023) throw ShapeError("sola_stitch: search range longer than 1023 samples");
         if (sola_len < 1 || frame < sola_len) throw ShapeError("sola_stitch: the frame must be at least as long as the crossfade (a window's tail is then its own samples)");
         if (window_len > (size_t)1 << 28 || window_len < search + frame + sola_len) throw ShapeError("sola_stitch: a window holds fewer than search + frame + sola_len samples");
-        hipStream_t st = e->stream;
-        DevBuf<float> d_y, d_tails, d_out; DevBuf<int> d_off;
-        d_y.alloc(n_windows * window_len); d_tails.alloc((n_windows + 1) * sola_len); d_out.alloc(n_windows * frame); d_off.alloc(n_windows);
-        HIPCHK(hipMemcpyAsync(d_y.get(), windows, n_windows * window_len * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(d_tails.get(), 0, sola_len * sizeof(float), st));
-        const size_t step = 4096;      // windows per pair of launches (the assembly's grid.y)
-        for (size_t w0 = 0; w0 < n_windows; w0 += step)
-            launch_stitch(st, d_y.get() + w0 * window_len, (long long)window_len, (int)w0, (int)std::min(step, n_windows - w0), (int)sola_len, (int)search, (int)frame,
-                          d_tails.get(), d_off.get(), d_out.get(), (long long)(n_windows * frame));
-        std::vector<int32_t> off(n_windows);
-        HIPCHK(hipMemcpyAsync(out, d_out.get(), n_windows * frame * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(off.data(), d_off.get(), n_windows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        if (offsets) for (size_t i = 0; i < n_windows; i++) offsets[i] = off[i];
+        sola_stitch_run(e, windows, {0, (int)n_windows}, window_len, sola_len, search, frame, out, offsets);
         return RVC_OK;
     });
 }
@@ -498,9 +486,7 @@ rvc_status rvc_silence_map(rvc_engine *e, const float *pcm16k, size_t n, double 
         d_in.alloc(n);
         HIPCHK(hipMemcpyAsync(d_in.get(), pcm16k, n * sizeof(float), hipMemcpyHostToDevice, st));
         SilenceWork w;
-        w.begin(st, g.Nf, g.windows, threshold_db, hang_frames, 0);
-        w.queue_file(st, d_in.get(), n, g.Nf, 0, g.windows, 0, g);
-        w.finish(st);
+        many_gate(st, d_in.get(), convert_many_single(g, n), threshold_db, hang_frames, 0, &w);
         std::vector<int> act;
         if (frame_loud) HIPCHK(hipMemcpyAsync(frame_loud, w.loud.get(), g.Nf, hipMemcpyDeviceToHost, st));
         if (frame_kept) HIPCHK(hipMemcpyAsync(frame_kept, w.kept.get(), g.Nf, hipMemcpyDeviceToHost, st));

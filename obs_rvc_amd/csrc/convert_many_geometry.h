@@ -1,7 +1,7 @@
-// convert_many_geometry.h -- the host-only arithmetic of rvc_convert_many: how the windows of F recordings of one geometry are laid
-// end to end and cut into batches of S.  Plain C++, no HIP: rvc_convert_many_geometry and rvc_convert_many call it, and
-// tests/tools/convert_many_host_check.cpp compiles it on its own under the sanitizers.  The one function the kernels share with the host, many_file_of, is
-// marked for both sides when a HIP compiler reads this file.
+// convert_many_geometry.h -- the host-only arithmetic of a windowed call on recordings: how the windows of F recordings of one geometry
+// are laid end to end and cut into batches of S; rvc_convert's recording is the call with F = 1 (convert_many_single).  Plain C++, no HIP: every conversion
+// and analysis calls it, and tests/tools/convert_many_host_check.cpp compiles it on its own under the sanitizers.  The functions the kernels share with the
+// host, many_file_of and many_grid_row, are marked for both sides when a HIP compiler reads this file.
 //
 //   file f, N_f >= 1 samples:  Nf_f = ceil(N_f / 160),  W_f = ceil(Nf_f / H),  out_f = Nf_f zc            (convert_geometry.h, per file)
 //   global window g = P_f + w,  P_f = W_0 + ... + W_{f-1},  0 <= w < W_f;   Wtot = P_F
@@ -45,6 +45,13 @@ static inline RVC_MANY_HD long long many_grid_row(const int *P, const long long 
     return row < goff[f + 1] - goff[f] ? goff[f] + row : -1;
 }
 
+// the per-file tables of a call as the kernels read them, all indexed by file (windowed.hip.h uploads them): P [F + 1] window prefix sums, the file's place in
+// the signal arena and in the output arena, goff [F + 1] the prefix sums of the files' f0 grids
+struct ManyTables {
+    const int *P; const long long *sig_off, *sig_n, *out_off, *out_n, *goff;
+    int n_files;
+};
+
 // the packing of a call.  g: the shared window geometry (its Nf / windows / out_samples are file 0's and not used).  Per file: samples, windows, output
 // samples; the prefix sums P (windows), sig_off (input samples) and out_off (output samples), each [n_files + 1]
 struct ConvertManyGeometry {
@@ -72,6 +79,16 @@ struct ConvertManyGeometry {
         *last = many_file_of(P.data(), (int)files(), (int)(g1 - 1));
     }
 };
+
+// one recording of n samples with geometry g (convert_geometry's, of that n) as the call of one file it is
+static inline ConvertManyGeometry convert_many_single(const ConvertGeometry &g, size_t n)
+{
+    ConvertManyGeometry m;
+    m.g = g;
+    m.n = {n}; m.windows = {g.windows}; m.out_samples = {g.out_samples};
+    m.P = {0, (int)g.windows}; m.sig_off = {0, (long long)n}; m.out_off = {0, (long long)g.out_samples};
+    return m;
+}
 
 // -> nullptr, or what is wrong with the arguments (k, context, crossfade: 0 = the defaults, as convert_geometry)
 static inline const char *convert_many_geometry(const size_t *n16k, size_t n_files, size_t sample_rate, size_t k, size_t context, size_t crossfade, ConvertManyGeometry *m)

@@ -42,7 +42,7 @@ void launch_protect_mix(hipStream_t s, int B, const StreamState *st, const float
     hipLaunchKernelGGL(protect_mix_kernel, protect_grid(R, B, C), dim3(PROTECT_ROWS, PROTECT_LANES), 0, s, st, pitchf, cv, cv_cs, cv_bs, C, T, skip_head, R, phone, ph_cs, ph_bs);
 }
 
-// f0 from outside (f0_override.hip.h): the three launches, for the engine below and for rvc_debug_f0_override (debug.hip)
+// f0 from outside (f0_override.hip.h): the launches, for the engine below and for rvc_debug_f0_override (debug.hip)
 void launch_f0_override(hipStream_t s, int B, int Tm, const float *f, float *out, const F0OvCall *call, const int *cnt, const float *rows, const int *map)
 {
     hipLaunchKernelGGL(f0_override_kernel, dim3((Tm + 255) / 256, B), dim3(256), 0, s, f, out, Tm, call, cnt, rows, map);
@@ -51,11 +51,7 @@ void launch_f0_curve_grid(hipStream_t s, const double *t, const float *hz, int n
 {
     hipLaunchKernelGGL(f0_curve_grid_kernel, dim3((unsigned)((Nf + 255) / 256)), dim3(256), 0, s, t, hz, n, grid, Nf);
 }
-void launch_f0_export(hipStream_t s, const float *f0, int Tm, int w0, int nw, int H, int C, float *grid, long long Nf)
-{
-    if (nw < 1 || H < 1) return;
-    hipLaunchKernelGGL(f0_export_kernel, dim3((H + 255) / 256, nw), dim3(256), 0, s, f0, Tm, w0, H, C, grid, Nf);
-}
+// (launch_f0_export, the third: windows.hip.h, beside the export kernel of the windowed calls)
 
 // the caller-side post-processing launches (chunk.hip.h), B streams each: rvc_envelop_mixing, sola_step_host and rvc_session_process queue them through
 // these, and so does rvc_debug_post (debug.hip)
@@ -1819,7 +1815,6 @@ int rvc_debug_tap(rvc_engine *e, const char *name, int stream, float *out, size_
 #include "denoise.hip.h"
 #include "session.hip.h"
 #include "rccl_bcast.hip.h"
-#include "convert.hip.h"
 #include "convert_many.hip.h"
 
 namespace rvc {

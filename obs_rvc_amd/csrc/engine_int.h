@@ -705,7 +705,8 @@ void launch_f0_hybrid(hipStream_t s, int B, int Tm, int n, int mode, const float
 float *add_f0_hybrid(rvc_engine *e, Plan &pl, int B, int n, int mode, const float *const *rows, int rm_at, const T1 &sal);
 // f0 from outside (f0_override.hip.h), each launch as the engine queues it (engine.hip) and as rvc_debug_f0_override does (debug.hip).
 // launch_f0_override: out [B][Tm] = the rows f [B][Tm] selected against the overrides `call` describes (cnt [streams], rows [streams][1024]; map: the engine stream of
-// each plan stream, or null).  launch_f0_curve_grid: n breakpoints (device) -> grid [Nf].  launch_f0_export: the rows f0 [nw][Tm] of windows w0 .. onto grid [Nf]
+// each plan stream, or null).  launch_f0_curve_grid: n breakpoints (device) -> grid [Nf].  launch_f0_export: the rows f0 [nw][Tm] of windows w0 .. of one recording onto
+// its grid [Nf], through the windowed calls' export kernel on a one-file table (windows.hip.h); returns synchronised
 void launch_f0_override(hipStream_t s, int B, int Tm, const float *f, float *out, const F0OvCall *call, const int *cnt, const float *rows, const int *map);
 void launch_f0_curve_grid(hipStream_t s, const double *t, const float *hz, int n, float *grid, long long Nf);
 void launch_f0_export(hipStream_t s, const float *f0, int Tm, int w0, int nw, int H, int C, float *grid, long long Nf);

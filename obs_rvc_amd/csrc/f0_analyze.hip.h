@@ -1,16 +1,17 @@
-// f0_analyze.hip.h -- the f0 of a whole recording without the synthesizer, exact order statistics of f0 rows, and auto-transpose (the
-// forks' "proposed pitch"), included by convert.hip.h (engine.hip's unit) in front of convert_run.
+// f0_analyze.hip.h -- the f0 of recordings without the synthesizer, exact order statistics of f0 rows, and auto-transpose (the
+// forks' "proposed pitch"), included by f0_analyze_many.hip.h (engine.hip's unit).
 //
-// rvc_analyze_f0 cuts the recording into rvc_convert's windows (convert_geometry.h, window_gather_kernel), runs them S = rvc_set_streams at a time through the
-// pitch-only plan (PlanKey::mode 2, B = S) of that geometry under a NEUTRAL control block -- multiplier 1, every pitch control off, whatever the streams'
-// settings say -- and exports the hop rows of every window onto the 10 ms grid (launch_f0_export).  A row is what rvc_pitch returns for that window with
-// pitch_shift = 0 and neutral controls.  rvc_f0_stats / rvc_f0_stats_stream select quantiles of the voiced rows (f0_select.hip.h).  rvc_set_auto_transpose makes
-// rvc_convert* / rvc_convert_file* run the analysis in front of their first batch, take the lower median and transpose by 12 log2(target / median) semitones
-// for the duration of the call (convert.hip.h convert_run calls auto_transpose_run).
+// An analysis cuts its recordings into the converter's windows (convert_many_geometry.h; windows.hip.h gathers them), runs them S = rvc_set_streams at a time
+// through the pitch-only plan (PlanKey::mode 2, B = S) of that geometry under a NEUTRAL control block -- multiplier 1, every pitch control off, whatever the
+// streams' settings say -- and exports the hop rows of every window onto the 10 ms grids (launch_f0_export_many).  A row is what rvc_pitch returns for that
+// window with pitch_shift = 0 and neutral controls.  analyze_many_run is the one loop: rvc_analyze_f0 is its call of one file, rvc_analyze_f0_many
+// (f0_analyze_many.hip.h) its call of many.  rvc_f0_stats / rvc_f0_stats_stream select quantiles of the voiced rows (f0_select.hip.h).  rvc_set_auto_transpose
+// makes rvc_convert* / rvc_convert_file* run the analysis in front of their first batch, take the lower median and transpose by 12 log2(target / median)
+// semitones for the duration of the call (convert.hip.h calls auto_transpose_run).
 // A stream's pitch cache holds CONDITIONED f0 -- behind pitch_shift, the semitone transpose and the pitch controls: a host that wants the raw median of a live
 // stream from rvc_f0_stats_stream reads it while its transpose is 0.
 #pragma once
-#include "convert_geometry.h"
+#include "windows.hip.h"
 #include "f0_select.hip.h"
 
 namespace rvc {
@@ -24,41 +25,38 @@ static void analyze_shape(size_t n, size_t sample_rate, size_t k, size_t context
     if (g->windows > (size_t)1 << 30) throw ShapeError("analyze_f0: recording too long");
 }
 
-// row offset of a window's f0 rows against the recording's 10 ms grid, as convert_run derives it (and with its centring check)
-static int analyze_cg(const ConvertGeometry &g)
+// row offset of a window's f0 rows against the recording's 10 ms grid.  The f0 front end takes the last fr samples of a window and reflect-pads them by 512, so
+// f0 row t of window w is centred on sample 160 (w H - C) + (n - fr) + 160 t of the recording: grid row w H - Cg + t with Cg = C - (n - fr) / 160.  (fr = n for
+// every geometry convert_geometry makes; the check stays.)  who: the caller's name in the refusal
+static int analyze_cg(const ConvertGeometry &g, const char *who = "analyze_f0")
 {
     const size_t fr = 5120 * ((g.sf + 799) / 5120 + 1) - 160;
-    if (fr > g.n || (g.n - fr) % 160 != 0 || (g.n - fr) / 160 > g.C) throw ShapeError("analyze_f0: the f0 rows of a window are not centred on the recording's 10 ms grid");
+    if (fr > g.n || (g.n - fr) % 160 != 0 || (g.n - fr) / 160 > g.C) throw ShapeError(std::string(who) + ": the f0 rows of a window are not centred on the recording's 10 ms grid");
     return (int)(g.C - (g.n - fr) / 160);
 }
 
-// The analysis proper, device to device: sig [n] at 16 kHz -> grid [g.Nf].  Begins with what rvc_reset_state does and leaves the state that way (a pitch-only
-// plan writes neither the cache nor the chunk counter); returns synchronised, the streams' status words checked.  gate (the silence gate's analysis of sig,
-// DESIGN.md section 30): only its active windows run, compacted; the caller has zeroed the grid, which keeps 0 in the rows of skipped windows
-static rvc_status analyze_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, float *grid, const SilenceGate *gate = nullptr)
+// The analysis proper, device to device: sig = the signal arena of the call, tabs its tables, grid the grid arena (file f's Nf_f rows at tabs.goff[f]).  Begins
+// with what rvc_reset_state does and leaves the state that way (a pitch-only plan writes neither the cache nor the chunk counter); returns synchronised, the
+// streams' status words checked.  gate (the silence gate's analysis of sig): only its active windows run, compacted; the caller has
+// zeroed the grid, which keeps 0 in the rows of skipped windows.  who: the entry point's name in the refusal
+static rvc_status analyze_many_run(rvc_engine *e, const float *sig, const ConvertManyGeometry &m, const ManyTables &tabs, float *grid, const SilenceWork *gate, const char *who)
 {
     hipStream_t st = e->stream;
-    const size_t S = (size_t)e->n_streams, W = g.windows, batches = gate ? gate->work.batches(S) : (W + S - 1) / S;
+    const ConvertGeometry &g = m.g;
+    const size_t S = (size_t)e->n_streams, N = gate ? gate->A : m.windows_total(), batches = (N + S - 1) / S;
     const int Cg = analyze_cg(g);
     HIPCHK(hipDeviceSynchronize());
     reset_state(e);
-    if (gate && gate->work.A == 0) { HIPCHK(hipStreamSynchronize(st)); return RVC_OK; }      // (nothing to run: no plan is built, the zeroed grid is the result)
+    if (N == 0) { HIPCHK(hipStreamSynchronize(st)); return RVC_OK; }      // (a gated call without an active window: no plan is built, the zeroed grid is the result)
     Plan *pl = get_plan(e, plan_key(e, 2, g.n, g.sf, 0, 0));
-    if (pl->key.B != (int)S || !pl->d_f0 || (size_t)Cg + g.H > (size_t)pl->Tm) throw ShapeError("analyze_f0: a window's hop lies outside its f0 rows");
+    if (pl->key.B != (int)S || !pl->d_f0 || (size_t)Cg + g.H > (size_t)pl->Tm) throw ShapeError(std::string(who) + ": a window's hop lies outside its f0 rows");
     pl->cur_in = nullptr; pl->cur_out = nullptr;
     push_call_params(e, 0, nullptr, nullptr, true);
     for (size_t b = 0; b < batches; b++) {
-        const size_t w0 = b * S;
-        if (gate) {      // (w0: the batch's first place)
-            gate->work.gather(st, sig, gate->tabs.t, pl->d_in, S, w0, g);
-            run_plan(e, *pl);
-            gate->work.export_f0(st, pl->d_f0, pl->Tm, S, w0, (int)g.H, Cg, grid, (long long)g.Nf);
-            continue;
-        }
-        const int nw = (int)std::min(S, W - w0);
-        launch_window_gather(st, sig, (long long)n, pl->d_in, (int)g.n, (int)S, (long long)w0, nw, (int)g.H, (int)g.C);
+        const size_t g0 = b * S; const int nw = (int)std::min(S, N - g0);      // (gated: g0 is the batch's first place)
+        launch_gather_windows(st, sig, tabs, pl->d_in, S, gate, g0, nw, g);
         run_plan(e, *pl);
-        launch_f0_export(st, pl->d_f0, pl->Tm, (int)w0, nw, (int)g.H, Cg, grid, (long long)g.Nf);
+        launch_f0_export_many(st, pl->d_f0, pl->Tm, tabs, S, gate, g0, nw, (int)g.H, Cg, grid);
     }
     queue_status(e);
     HIPCHK(hipStreamSynchronize(st));
@@ -89,6 +87,14 @@ static void read_select(rvc_engine *e, size_t nq, float *out_hz, size_t *voiced)
     if (voiced) *voiced = res[F0_SEL_MAXQ];
 }
 
+// the arguments of rvc_set_auto_transpose and rvc_set_convert_many_auto_transpose
+static void auto_transpose_check(double target_hz, int step, double limit)
+{
+    if (!(target_hz >= 0.0 && target_hz <= 20000.0)) throw ShapeError("auto transpose: the target is 0 (off) or in (0, 20000] Hz");
+    if (step != 0 && step != 1 && step != 12) throw ShapeError("auto transpose: the step is 0 (exact), 1 (semitones) or 12 (octaves)");
+    if (!(limit >= 0.0 && limit <= 24.0)) throw ShapeError("auto transpose: the limit is in [0, 24] semitones");
+}
+
 // a = 12 log2(target / m) in double, rounded to the step (ties to even), clamped to [-limit, limit]; no voiced row: 0
 static double auto_transpose_semitones(double target, double median, size_t voiced, int step, double limit)
 {
@@ -98,26 +104,27 @@ static double auto_transpose_semitones(double target, double median, size_t voic
     return std::min(std::max(a, -limit), limit);
 }
 
-// In front of a conversion's first batch (convert_run; a target is set and the model has pitch guidance): the analysis of the signal the model will see, the curve
-// merged in when one is in force (curve_grid: its grid, or null), the lower median, the transpose.  -> the factor every stream's multiplier takes for the rest of
-// the call, 0 = none.  Ends with the engine in the reset state the conversion starts from
-static rvc_status auto_transpose_run(rvc_engine *e, const float *sig, size_t n, const ConvertGeometry &g, const float *curve_grid, float *mul, const SilenceGate *gate)
+// In front of the first batch of a conversion of ONE recording (m: its call of one file; a target is set and the model has pitch guidance): the analysis of the
+// signal the model will see, the curve merged in when one is in force (curve_grid: its grid, or null), the lower median, the transpose.  -> the factor every
+// stream's multiplier takes for the rest of the call, 0 = none.  Ends with the engine in the reset state the conversion starts from
+static rvc_status auto_transpose_run(rvc_engine *e, const float *sig, const ConvertManyGeometry &m, const ManyTables &tabs, const float *curve_grid, float *mul, const SilenceWork *gate)
 {
     hipStream_t st = e->stream;
+    const size_t Nf = m.g.Nf;
     *mul = 0.f;
     e->at_info.valid = false;
     DevBuf<float> grid;
-    grid.alloc(g.Nf);
+    grid.alloc(Nf);
     DevTimer t_an, t_sel;
-    HIPCHK(hipMemsetAsync(grid.get(), 0, g.Nf * sizeof(float), st));
+    HIPCHK(hipMemsetAsync(grid.get(), 0, Nf * sizeof(float), st));
     t_an.start(st);
-    const rvc_status rc = analyze_run(e, sig, n, g, grid.get(), gate);
+    const rvc_status rc = analyze_many_run(e, sig, m, tabs, grid.get(), gate, "analyze_f0");
     if (rc != RVC_OK) return rc;
     t_an.stop(st);
     t_sel.start(st);
-    if (curve_grid) hipLaunchKernelGGL(f0_merge_kernel, dim3((unsigned)((g.Nf + 255) / 256)), dim3(256), 0, st, grid.get(), curve_grid, (long long)g.Nf);
+    if (curve_grid) hipLaunchKernelGGL(f0_merge_kernel, dim3((unsigned)((Nf + 255) / 256)), dim3(256), 0, st, grid.get(), curve_grid, (long long)Nf);
     const double half = 0.5;
-    queue_select(e, grid.get(), g.Nf, &half, 1);
+    queue_select(e, grid.get(), Nf, &half, 1);
     t_sel.stop(st);
     float median = 0.f; size_t voiced = 0;
     read_select(e, 1, &median, &voiced);
@@ -144,6 +151,9 @@ rvc_status rvc_analyze_f0_device(rvc_engine *e, const void *d_pcm16k, size_t n, 
         if (n_frames) *n_frames = g.Nf;
         if (cap < g.Nf) { e->err = "analyze_f0: output buffer too small"; return RVC_SHAPE; }
         if (!d_pcm16k || !d_hz) throw ShapeError("analyze_f0: null buffer");
+        const ConvertManyGeometry m = convert_many_single(g, n);      // the call of one file
+        ManyDeviceTables tabs;
+        tabs.upload(m);
         DevBuf<float> filtered;
         const float *sig = (const float *)d_pcm16k;
         if (highpass) {
@@ -151,12 +161,14 @@ rvc_status rvc_analyze_f0_device(rvc_engine *e, const void *d_pcm16k, size_t n, 
             launch_highpass(e, sig, n, filtered.get());
             sig = filtered.get();
         }
-        if (!silence_gate_on(e)) return analyze_run(e, sig, n, g, (float *)d_hz);
-        SilenceGate gate;
-        silence_gate_run(e, sig, n, g, 0, &gate);
-        HIPCHK(hipMemsetAsync(d_hz, 0, g.Nf * sizeof(float), e->stream));
-        const rvc_status rc = analyze_run(e, sig, n, g, (float *)d_hz, &gate);
-        if (rc == RVC_OK) silence_gate_report(e, gate.work);
+        const bool gated = silence_gate_on(e);
+        SilenceWork gate;
+        if (gated) {
+            many_gate(e->stream, sig, m, e->sil_db, e->sil_hang, 0, &gate);
+            HIPCHK(hipMemsetAsync(d_hz, 0, g.Nf * sizeof(float), e->stream));
+        }
+        const rvc_status rc = analyze_many_run(e, sig, m, tabs.t, (float *)d_hz, gated ? &gate : nullptr, "analyze_f0");
+        if (rc == RVC_OK && gated) silence_gate_report(e, gate);
         return rc;
     });
 }
@@ -210,9 +222,7 @@ rvc_status rvc_f0_stats_stream(rvc_engine *e, int stream, const double *quantile
 rvc_status rvc_set_auto_transpose(rvc_engine *e, double target_hz, int step, double limit)
 {
     return guarded(e, [&]() {
-        if (!(target_hz >= 0.0 && target_hz <= 20000.0)) throw ShapeError("auto transpose: the target is 0 (off) or in (0, 20000] Hz");
-        if (step != 0 && step != 1 && step != 12) throw ShapeError("auto transpose: the step is 0 (exact), 1 (semitones) or 12 (octaves)");
-        if (!(limit >= 0.0 && limit <= 24.0)) throw ShapeError("auto transpose: the limit is in [0, 24] semitones");
+        auto_transpose_check(target_hz, step, limit);
         e->at_target = target_hz; e->at_step = step; e->at_limit = limit;
         return RVC_OK;
     });

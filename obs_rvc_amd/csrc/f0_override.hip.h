@@ -1,5 +1,5 @@
-// f0_override.hip.h -- f0 from outside, included by engine.hip: the grid of a recording's f0 curve, the select of a tracker's rows
-// against override rows in front of the pitch tail, and the export of a conversion's conditioned f0 onto the 10 ms grid.
+// f0_override.hip.h -- f0 from outside, included by engine.hip: the grid of a recording's f0 curve, and the select of a tracker's rows
+// against override rows in front of the pitch tail.  (The export of a conversion's conditioned f0 onto the 10 ms grid: windows.hip.h f0_export_many_kernel.)
 // Plain vector loads and stores, no LDS, no atomics.  The definition is tests/f0_override_ref.py; the operation order below is part of it.
 #pragma once
 #include "f0_override.h"
@@ -63,16 +63,6 @@ static __global__ __launch_bounds__(256) void f0_override_kernel(const float *__
     }
     const float v = f[(long long)b * Tm + tt];
     out[(long long)b * Tm + tt] = o != o ? v : o;
-}
-
-// after a batch of a conversion: the conditioned rows f0 [nw][Tm] of windows w0 .. w0 + nw onto the grid [Nf].  Frame g belongs to the one window whose hop
-// [C, C + H) holds it -- g = w H + (t - C) -- so every frame is written exactly once over the batches, no atomics.  Grid (ceil(H / 256), nw)
-static __global__ __launch_bounds__(256) void f0_export_kernel(const float *__restrict__ f0, int Tm, int w0, int H, int C, float *__restrict__ grid, long long Nf)
-{
-    const int h = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
-    if (h >= H || C + h >= Tm) return;
-    const long long g = (long long)(w0 + s) * H + h;
-    if (g < Nf) grid[g] = f0[(long long)s * Tm + C + h];
 }
 
 }  // namespace rvc

@@ -1,5 +1,5 @@
-// silence.hip.h -- the file converter's silence gate (the upstream client's response threshold, slicer2's job), included by convert.hip.h
-// (engine.hip's unit).  The definition is tests/silence_ref.py.
+// silence.hip.h -- the file converter's silence gate (the upstream client's response threshold, slicer2's job), included by windows.hip.h
+// (engine.hip's unit), whose gather and f0 export read the gate's win_of list.  The definition is tests/silence_ref.py.
 //
 // With rvc_set_convert_silence in force a conversion measures the signal the model will see first and runs only the windows that hold something:
 //   loud[i]    frame i (10 ms, 160 samples) whose 40 ms of signal from its start on reach the threshold: sumsq(x[160 i, 160 i + 640)) >= 640 thr, fp64
@@ -15,29 +15,6 @@
 #include "stitch.hip.h"
 
 namespace rvc {
-
-// the per-file tables of a call on the device (convert_many.hip.h fills them; a single recording is a call of one file): P [F + 1] window prefix sums, the
-// file's place in the signal arena and in the output arena
-struct ManyTables {
-    const int *P; const long long *sig_off, *sig_n, *out_off, *out_n;
-    int n_files;
-};
-// ... uploaded: the four per-file arrays in one allocation and the window prefix sums, copied before upload() returns
-struct ManyDeviceTables {
-    DevBuf<long long> ll; DevBuf<int> P;
-    ManyTables t{};
-    void upload(const std::vector<int> &Pv, const std::vector<long long> &sig_off, const std::vector<long long> &sig_n, const std::vector<long long> &out_off,
-                const std::vector<long long> &out_n)
-    {
-        const size_t F = Pv.size() - 1;
-        std::vector<long long> host(4 * F);
-        for (size_t f = 0; f < F; f++) { host[f] = sig_off[f]; host[F + f] = sig_n[f]; host[2 * F + f] = out_off[f]; host[3 * F + f] = out_n[f]; }
-        ll.alloc(4 * F); P.alloc(F + 1);
-        HIPCHK(hipMemcpy(ll.get(), host.data(), 4 * F * sizeof(long long), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(P.get(), Pv.data(), (F + 1) * sizeof(int), hipMemcpyHostToDevice));
-        t = ManyTables{P.get(), ll.get(), ll.get() + F, ll.get() + 2 * F, ll.get() + 3 * F, (int)F};
-    }
-};
 
 constexpr int SILENCE_SCAN_THREADS = 1024;
 constexpr int SILENCE_MAX_HANG = 1000;
@@ -151,32 +128,6 @@ static __global__ __launch_bounds__(SILENCE_SCAN_THREADS) void silence_compact_k
     if (threadIdx.x == 0) counts[0] = (unsigned long long)carry;
 }
 
-// the plan's batch input [S][n] from the list: stream s gets the (j0 + s)-th active window, global window g = win_of[j0 + s] = window w of file f, samples
-// [160 (w H - C), + n) of that file, zero outside it; streams at or beyond the A active windows (the padding of the last batch) get zeros
-static __global__ __launch_bounds__(256) void window_gather_list_kernel(const float *sig, ManyTables tabs, float *dst, int n, const int *__restrict__ win_of, int j0, int A, int H, int C)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
-    if (i >= n) return;
-    float v = 0.f;
-    if (j0 + s < A) {
-        const int g = win_of[j0 + s], f = many_file_of(tabs.P, tabs.n_files, g), w = g - tabs.P[f];
-        const long long src = 160LL * ((long long)w * H - C) + i;
-        if (src >= 0 && src < tabs.sig_n[f]) v = sig[tabs.sig_off[f] + src];
-    }
-    dst[(long long)s * n + i] = v;
-}
-
-// f0_export_kernel's sibling: the conditioned rows f0 [S][Tm] of the batch's active windows onto the grid [Nf] of ONE recording; rows of skipped windows are
-// not written (the caller zeroes the grid first).  Grid (ceil(H / 256), S)
-static __global__ __launch_bounds__(256) void f0_export_list_kernel(const float *__restrict__ f0, int Tm, const int *__restrict__ win_of, int j0, int A, int H, int C,
-                                                                    float *__restrict__ grid, long long Nf)
-{
-    const int h = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
-    if (h >= H || C + h >= Tm || j0 + s >= A) return;
-    const long long g = (long long)win_of[j0 + s] * H + h;
-    if (g < Nf) grid[g] = f0[(long long)s * Tm + C + h];
-}
-
 // the global windows a compacted batch completes: those behind the last active window of the batch before, up to its own last active window -- and up to the
 // end of the call for the last batch (j0 + nw >= A; with A = 0 one launch of j0 = nw = 0 covers everything)
 __device__ __forceinline__ void silence_batch_range(const int *win_of, int j0, int nw, int A, int W, int *lo, int *hi)
@@ -283,15 +234,6 @@ struct SilenceWork {
         if (A > W) throw std::runtime_error("silence gate: the active count exceeds the window count");
         ms = (double)timer.ms();
     }
-    void gather(hipStream_t st, const float *sig, const ManyTables &tabs, float *dst, size_t S, size_t j0, const ConvertGeometry &g) const
-    {
-        hipLaunchKernelGGL(window_gather_list_kernel, dim3((unsigned)((g.n + 255) / 256), (unsigned)S), dim3(256), 0, st, sig, tabs, dst, (int)g.n, (const int *)win_of.get(), (int)j0,
-                           (int)A, (int)g.H, (int)g.C);
-    }
-    void export_f0(hipStream_t st, const float *f0, int Tm, size_t S, size_t j0, int H, int Cg, float *grid, long long Nf) const
-    {
-        hipLaunchKernelGGL(f0_export_list_kernel, dim3((unsigned)((H + 255) / 256), (unsigned)S), dim3(256), 0, st, f0, Tm, (const int *)win_of.get(), (int)j0, (int)A, H, Cg, grid, Nf);
-    }
     // the two stitch launches behind the batch of active windows [j0, j0 + nw) (nw = 0: a call without an active window)
     void stitch(hipStream_t st, const float *y, long long y_bs, size_t j0, int nw, const ManyTables &tabs, int sola_len, int search, int frame, float *tails, int *offsets, float *out) const
     {
@@ -302,11 +244,5 @@ struct SilenceWork {
                            (const int *)place.get(), (const int *)win_of.get(), (int)j0, nw, (int)A, (int)W, tabs, sola_len, frame, (const float *)tails, (const int *)offsets, out);
     }
 };
-
-// a call of one recording as a call of one file
-static void silence_single_tables(ManyDeviceTables *t, size_t n, const ConvertGeometry &g)
-{
-    t->upload({0, (int)g.windows}, {0}, {(long long)n}, {0}, {(long long)g.out_samples});
-}
 
 }  // namespace rvc

@@ -278,3 +278,25 @@ def test_convert_many_statuses():
             fn()
         assert err.value.code == 5
     e.close()
+
+
+# ---------------------------------------------------------------- 7. the two info blocks through the one driver
+def test_the_info_blocks_stay_apart():
+    """rvc_convert and rvc_convert_many run one driver and report to two blocks.  (The statuses test above pins the other half: rvc_convert_many_info refused before
+    any many call, rvc_convert_info and rvc_convert_f0 refused behind one.)  Here a conversion of one recording FOLLOWS a many call: it reports itself, brings the
+    f0 grid back, and leaves the many call's windows, batches and offsets as they were"""
+    e = engine(3)
+    xs = recordings()
+    guard(e.convert_many, xs[:2], k=K, context=CTX, crossfade=XF, pitch_shift=SHIFT, highpass=False)      # 1 + 3 windows on 3 streams: two batches
+    many = e.convert_many_info()
+    assert many["windows"] == 4 and many["batches"] == 2 and len(many["offsets"]) == 4
+    with pytest.raises(RvcInferError):
+        e.convert_f0()
+    want, _ = guard(e.convert, xs[3], k=K, context=CTX, crossfade=XF, pitch_shift=SHIFT, highpass=False)      # 2 windows: one batch
+    one = e.convert_info()
+    assert one["windows"] == 2 and one["batches"] == 1 and len(one["offsets"]) == 2 and len(want) == OUT[3]
+    assert len(e.convert_f0()) == 55
+    after = e.convert_many_info()
+    assert after["windows"] == 4 and after["batches"] == 2 and after["offsets"].tolist() == many["offsets"].tolist()
+    assert [after[k] for k in ("ms_highpass", "ms_model", "ms_stitch", "ms_total")] == [many[k] for k in ("ms_highpass", "ms_model", "ms_stitch", "ms_total")]
+    e.close()

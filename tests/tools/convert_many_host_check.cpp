@@ -46,6 +46,30 @@ int main()
                 CHECK((size_t)(m.out_off[f + 1] - m.out_off[f]) == g.out_samples && (size_t)(m.sig_off[f + 1] - m.sig_off[f]) == n[f]);
                 // the windows of a file cover its output: (W - 1) H zc < out <= W H zc, so the last window writes the last sample and no window starts beyond it
                 CHECK((g.windows - 1) * H * zc < g.out_samples && g.out_samples <= g.windows * H * zc);
+                // one recording as the call of one file: what convert_many_geometry makes of the list {n_f}, table for table
+                ConvertManyGeometry one_file, single = convert_many_single(g, n[f]);
+                CHECK(convert_many_geometry(&n[f], 1, rate, k, C, X, &one_file) == nullptr);
+                CHECK(single.files() == 1 && single.n == one_file.n && single.windows == one_file.windows && single.out_samples == one_file.out_samples);
+                CHECK(single.P == one_file.P && single.sig_off == one_file.sig_off && single.out_off == one_file.out_off && single.grid_off() == one_file.grid_off());
+                CHECK(single.g.Nf == g.Nf && single.g.n == g.n && single.g.H == g.H && single.g.C == g.C && single.g.zc == g.zc && single.batches(3) == (g.windows + 2) / 3);
+                CHECK(single.grid_off().size() == 2 && single.grid_off()[1] == (long long)g.Nf && many_file_of(single.P.data(), 1, (int)g.windows - 1) == 0);
+            }
+            // goff, the sixth table: prefix sums of Nf_f; the hop rows of a file's windows tile its region of the grid arena, each row once, none beyond it
+            {
+                const std::vector<long long> goff = m.grid_off();
+                CHECK(goff.size() == F + 1 && goff[0] == 0);
+                std::vector<int> hits((size_t)goff[F], 0);
+                for (size_t f = 0; f < F; f++) {
+                    CHECK((size_t)(goff[f + 1] - goff[f]) == m.out_samples[f] / zc && goff[f + 1] > goff[f]);
+                    for (int gw = m.P[f]; gw < m.P[f + 1]; gw++)
+                        for (size_t h = 0; h < H; h++) {
+                            const long long at = many_grid_row(m.P.data(), goff.data(), (int)F, gw, (int)h, (int)H);
+                            CHECK(at == -1 || (at >= goff[f] && at < goff[f + 1]));
+                            CHECK((at == -1) == ((long long)(gw - m.P[f]) * (long long)H + (long long)h >= goff[f + 1] - goff[f]));
+                            if (at >= 0) hits[(size_t)at]++;
+                        }
+                }
+                for (int c : hits) CHECK(c == 1);
             }
             const size_t W = m.windows_total();
             CHECK(m.out_total() == (size_t)m.out_off[F] && m.sig_total() == (size_t)m.sig_off[F]);
